@@ -213,7 +213,7 @@ def test_bench_gather_path_world1(gpu):
     (one full bucket + a partial one); rank 0's checks (global order, planted frames) are part of the JSON line."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29600 + os.getpid() % 300), RANK="0",
                LOCAL_RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-gather", "--steps", "11",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-gather", "--steps", "11",
                         "--warmup", "3", "--samples", str(1 << 24), "--no-cpu-baseline"], env=env, capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -239,7 +239,7 @@ def test_bench_three_ranks_share_one_gpu(gpu):
     port = 29900 + os.getpid() % 90
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", str(world), "--steps", "11", "--warmup", "3", "--samples", str(n), "--no-cpu-baseline"],
+                        "--full", "--gpus", str(world), "--steps", "11", "--warmup", "3", "--samples", str(n), "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1]

@@ -1,6 +1,7 @@
 #!/bin/bash
 # GPU box helper: engine / memory clocks and power while the demod loop runs (rocm-smi sampled once a second)
 mkdir -p gpurun_out
+BENCH_ARGS="--full ${BENCH_ARGS:-}"   # roofline.kernel_ms, read below, is a --full figure
 python bench.py --steps 30000 --warmup 10 --no-cpu-baseline ${BENCH_ARGS:-} > gpurun_out/clk_bench.json 2>/dev/null &
 pid=$!
 sleep 4

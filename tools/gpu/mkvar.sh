@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: mkvar.sh NAME FLAGS...
 set -e
-cd /root/repo
+cd "$(dirname "$0")/../.."
 name=$1; shift
 SRC=air_rs_amd/csrc
 FILES="$SRC/adsb_kernels.hip $SRC/adsb_track.hip $SRC/adsb_api.cpp $SRC/adsb_group.cpp $SRC/host/adsb_packet.cpp $SRC/host/adsb_aircraft.cpp $SRC/host/adsb_threads.cpp $SRC/host/adsb_host_api.cpp"

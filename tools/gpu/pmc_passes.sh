@@ -10,7 +10,7 @@ run_pass() {
   name=$1; shift
   rm -rf $PMC/$name
   echo "pass $name" >> $PMC/progress.txt
-  timeout -k 5 120 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $PMC/$name -o p -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-feed ${BENCH_ARGS:-} > $PMC/$name.json 2> $PMC/$name.err || { tail -5 $PMC/$name.err; return 1; }
+  timeout -k 5 120 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $PMC/$name -o p -- python3 bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-feed ${BENCH_ARGS:-} > $PMC/$name.json 2> $PMC/$name.err || { tail -5 $PMC/$name.err; return 1; }
 }
 run_pass sq1 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU || exit 1
 run_pass sq2 SQ_ACTIVE_INST_LDS SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_SCA SQ_WAVES || exit 1

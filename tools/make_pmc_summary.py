@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Builds profiles/pmc_summary.json from the PMC passes tools/gpu/round_profiles.sh left in gpurun_out/
+"""Builds profiles/pmc_summary.json from the PMC passes tools/gpu/round_profiles.sh left in $OUT (default out/)
 (r_pmc_summary_i8.json, r_pmc_summary_i16.json) and copies the round's bench lines / kernel stats into profiles/."""
 import json
 import os
@@ -7,7 +7,7 @@ import shutil
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.environ.get("OUT") or os.path.join(ROOT, "out"), os.path.join(ROOT, "profiles")
 tag = sys.argv[1] if len(sys.argv) > 1 else "r04"
 
 
