@@ -84,6 +84,13 @@ class AdsbAircraftSummary(C.Structure):
 
 
 ADSB_TRACK_NEW_POSITION = 0x1
+ADSB_TRACK_UNTRACKED = 0x2   # point flag: the frame's aircraft was turned away by a full table
+ADSB_TRACK_TABLE_FULL = 0x1  # table flag: some aircraft was turned away since create / reset
+
+
+class AdsbTrackTableCfg(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("max_aircraft", C.c_uint32), ("max_frames", C.c_uint64),
+                ("seconds_per_sample", C.c_double)]
 
 
 class AdsbPacketView(C.Structure):
@@ -114,6 +121,12 @@ PROTOTYPES = {
     "adsb_track_device": (C.c_int, [C.c_void_p, C.c_double]),
     "adsb_fetch_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t,
                                    _P(C.c_size_t)]),
+    "adsb_track_table_create": (C.c_int, [C.c_void_p, _P(AdsbTrackTableCfg), _P(C.c_void_p)]),
+    "adsb_track_table_destroy": (None, [C.c_void_p]),
+    "adsb_track_table_reset": (C.c_int, [C.c_void_p]),
+    "adsb_track_table_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]),
+    "adsb_track_table_fetch_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), _P(C.c_uint32)]),
     "adsb_cpr_num_zones": (C.c_uint32, [C.c_double]),
     "adsb_cpr_position": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P(C.c_double),
                                     _P(C.c_double)]),

@@ -860,6 +860,172 @@ extern "C" int adsb_fetch_track(adsb_ctx *c, adsb_track_point *points, size_t ma
     return ADSB_OK;
 }
 
+// ---- persistent aircraft table (adsb_track_table_*): the tracker kernels with a TrackTableDev ----------------------
+struct adsb_track_table {
+    adsb_ctx *ctx = nullptr;
+    adsb_track_table_cfg cfg{};
+    adsbk::TrackTableDev dev{};     // index [2^24], records [max_aircraft], size/flags words, slot [max_frames]
+    uint32_t *u32 = nullptr;        // 4 x [max_frames]: keys, vals, sorted keys, sorted vals
+    void *temp = nullptr;
+    size_t temp_bytes = 0;
+    adsb_frame *frames = nullptr;   // [max_frames]: device copy of a host list
+    adsb_frame *pinned = nullptr;   // [max_frames]: pinned staging of that copy
+    hipEvent_t copied = nullptr;    // the last copy out of `pinned` has finished
+    adsb_packet_fields *fields = nullptr; // [max_frames]
+    adsb_track_point *points = nullptr;   // [max_frames], the last update's, frame order
+    uint32_t n_points = 0;
+    bool updated = false;
+};
+
+static void track_table_free(adsb_track_table *t)
+{
+    (void)hipSetDevice(t->ctx->cfg.device);
+    (void)hipStreamSynchronize(t->ctx->aux);
+    if (t->dev.index) (void)hipFree(t->dev.index);
+    if (t->dev.rec) (void)hipFree(t->dev.rec);
+    if (t->dev.size_flags) (void)hipFree(t->dev.size_flags);
+    if (t->dev.slot) (void)hipFree(t->dev.slot);
+    if (t->u32) (void)hipFree(t->u32);
+    if (t->temp) (void)hipFree(t->temp);
+    if (t->frames) (void)hipFree(t->frames);
+    if (t->pinned) (void)hipHostFree(t->pinned);
+    if (t->copied) (void)hipEventDestroy(t->copied);
+    if (t->fields) (void)hipFree(t->fields);
+    if (t->points) (void)hipFree(t->points);
+    delete t;
+}
+
+extern "C" int adsb_track_table_reset(adsb_track_table *t)
+{
+    if (!t) return ADSB_E_ARG;
+    HIPCHK(hipSetDevice(t->ctx->cfg.device));
+    HIPCHK(hipMemsetAsync(t->dev.index, 0, sizeof(uint32_t) << 24, t->ctx->aux));
+    HIPCHK(hipMemsetAsync(t->dev.size_flags, 0, sizeof(uint32_t) * 4, t->ctx->aux));
+    t->n_points = 0;
+    t->updated = false;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_table_create(adsb_ctx *c, const adsb_track_table_cfg *cfg, adsb_track_table **out)
+{
+    if (!c || !cfg || !out || cfg->abi_version != ADSB_ABI_VERSION) return ADSB_E_ARG;
+    if (cfg->max_frames == 0 || cfg->max_frames > 0xFFFFFFFFull || !(cfg->seconds_per_sample > 0.0) ||
+        cfg->max_aircraft > (1u << 24))
+        return ADSB_E_ARG;
+    *out = nullptr;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    adsb_track_table *t = new (std::nothrow) adsb_track_table;
+    if (!t) return ADSB_E_NOMEM;
+    t->ctx = c;
+    t->cfg = *cfg;
+    if (!t->cfg.max_aircraft) t->cfg.max_aircraft = 65536;
+    const size_t nf = (size_t)t->cfg.max_frames;
+    t->dev.max_aircraft = t->cfg.max_aircraft;
+    t->temp_bytes = adsbk::track_sort_temp_bytes(nf);
+    const bool ok = hipMalloc((void **)&t->dev.index, sizeof(uint32_t) << 24) == hipSuccess &&
+                    hipMalloc((void **)&t->dev.rec, sizeof(adsbk::TrackRecord) * t->cfg.max_aircraft) == hipSuccess &&
+                    hipMalloc((void **)&t->dev.size_flags, sizeof(uint32_t) * 4) == hipSuccess &&
+                    hipMalloc((void **)&t->dev.slot, sizeof(uint32_t) * nf) == hipSuccess &&
+                    hipMalloc((void **)&t->u32, sizeof(uint32_t) * 4 * nf) == hipSuccess &&
+                    hipMalloc(&t->temp, t->temp_bytes) == hipSuccess &&
+                    hipMalloc((void **)&t->frames, sizeof(adsb_frame) * nf) == hipSuccess &&
+                    hipHostMalloc((void **)&t->pinned, sizeof(adsb_frame) * nf, hipHostMallocDefault) == hipSuccess &&
+                    hipEventCreateWithFlags(&t->copied, hipEventDisableTiming) == hipSuccess &&
+                    hipMalloc((void **)&t->fields, sizeof(adsb_packet_fields) * nf) == hipSuccess &&
+                    hipMalloc((void **)&t->points, sizeof(adsb_track_point) * nf) == hipSuccess;
+    int rc = ok ? adsb_track_table_reset(t) : ADSB_E_NOMEM;
+    if (rc == ADSB_OK && hipStreamSynchronize(c->aux) != hipSuccess) rc = ADSB_E_NOMEM;
+    if (rc != ADSB_OK) {
+        (void)hipGetLastError();
+        track_table_free(t);
+        return rc;
+    }
+    *out = t;
+    return ADSB_OK;
+}
+
+extern "C" void adsb_track_table_destroy(adsb_track_table *t)
+{
+    if (t) track_table_free(t);
+}
+
+extern "C" int adsb_track_table_update(adsb_track_table *t, const adsb_frame *frames, size_t n, uint64_t sample_base)
+{
+    if (!t || (!frames && n)) return ADSB_E_ARG;
+    if (n > t->cfg.max_frames) return ADSB_E_CAPACITY;
+    adsb_ctx *c = t->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    t->n_points = (uint32_t)n;
+    t->updated = true;
+    if (n == 0) return ADSB_OK;
+    const adsb_frame *list = frames;
+    hipPointerAttribute_t at{};
+    const bool on_device = hipPointerGetAttributes(&at, frames) == hipSuccess && at.type == hipMemoryTypeDevice &&
+                           at.device == c->cfg.device;
+    (void)hipGetLastError(); // a plain host pointer is an error to the query: do not leave it to the launches below
+    if (!on_device) { // through pinned staging, so the caller's array is free when this returns
+        HIPCHK(hipEventSynchronize(t->copied)); // the previous update's copy out of the staging has finished
+        std::memcpy(t->pinned, frames, sizeof(adsb_frame) * n);
+        HIPCHK(hipMemcpyAsync(t->frames, t->pinned, sizeof(adsb_frame) * n, hipMemcpyHostToDevice, c->aux));
+        HIPCHK(hipEventRecord(t->copied, c->aux));
+        list = t->frames;
+    }
+    HIPCHK(adsbk::launch_decode_fields(c->aux, list, nullptr, (uint32_t)n, t->fields));
+    adsbk::TrackArgs a{};
+    a.frames = list;
+    a.fields = t->fields;
+    a.n = (uint32_t)n;
+    a.seconds_per_sample = t->cfg.seconds_per_sample;
+    a.sample_base = sample_base;
+    const size_t nf = (size_t)t->cfg.max_frames;
+    a.keys = t->u32;
+    a.vals = t->u32 + nf;
+    a.skeys = t->u32 + 2 * nf;
+    a.svals = t->u32 + 3 * nf;
+    a.temp = t->temp;
+    a.temp_bytes = t->temp_bytes;
+    a.points = t->points;
+    a.table = &t->dev;
+    HIPCHK(adsbk::launch_track(c->aux, a)); // after the ctx's ordering pass and field decode (same stream)
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_table_fetch_points(adsb_track_table *t, adsb_track_point *points, size_t max_points,
+                                             size_t *n_points)
+{
+    if (!t || (!points && max_points)) return ADSB_E_ARG;
+    if (!t->updated) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(t->ctx->cfg.device));
+    const size_t np = std::min<size_t>(t->n_points, max_points);
+    if (np) HIPCHK(hipMemcpyAsync(points, t->points, sizeof(adsb_track_point) * np, hipMemcpyDeviceToHost, t->ctx->aux));
+    HIPCHK(hipStreamSynchronize(t->ctx->aux));
+    if (n_points) *n_points = np;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_table_fetch(adsb_track_table *t, adsb_aircraft_record *aircraft, size_t max_aircraft,
+                                      size_t *n_aircraft, uint32_t *flags)
+{
+    if (!t || (!aircraft && max_aircraft)) return ADSB_E_ARG;
+    HIPCHK(hipSetDevice(t->ctx->cfg.device));
+    uint32_t sf[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(sf, t->dev.size_flags, sizeof(sf), hipMemcpyDeviceToHost, t->ctx->aux));
+    HIPCHK(hipStreamSynchronize(t->ctx->aux));
+    const size_t size = std::min<size_t>(sf[0], t->cfg.max_aircraft);
+    if (max_aircraft && size) { // slots are in admission order: sort by ICAO here
+        std::vector<adsbk::TrackRecord> recs(size);
+        HIPCHK(hipMemcpyAsync(recs.data(), t->dev.rec, sizeof(adsbk::TrackRecord) * size, hipMemcpyDeviceToHost,
+                              t->ctx->aux));
+        HIPCHK(hipStreamSynchronize(t->ctx->aux));
+        std::sort(recs.begin(), recs.end(),
+                  [](const adsbk::TrackRecord &x, const adsbk::TrackRecord &y) { return x.a.icao < y.a.icao; });
+        for (size_t k = 0; k < std::min(size, max_aircraft); ++k) aircraft[k] = recs[k].a;
+    }
+    if (n_aircraft) *n_aircraft = size;
+    if (flags) *flags = sf[1];
+    return ADSB_OK;
+}
+
 extern "C" int adsb_set_result_target(adsb_ctx *c, void *blob_dev, size_t blob_bytes)
 {
     if (!c) return ADSB_E_ARG;

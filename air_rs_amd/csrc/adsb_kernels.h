@@ -161,21 +161,41 @@ bool tile_stamps_built(); // -DADSB_TILE_STAMPS=1 diagnostic build: DemodArgs::s
 
 // field decode of an ordered frame list (count read from hdr->n_out on the device)
 hipError_t launch_decode_fields(hipStream_t s, const adsb_frame *frames, const Header *hdr, uint32_t cap,
-                                adsb_packet_fields *out);
+                                adsb_packet_fields *out); // hdr == nullptr: exactly cap frames
 
 // tracker + CPR position decode over an ordered frame list (adsb_track.hip)
+// One aircraft of a persistent table (adsb_track_table_*): the public record plus the last even and the last odd
+// position message (aircraft.rs:28-31) that a later update's first position message of the other format pairs with.
+struct TrackRecord {
+    adsb_aircraft_record a;      // n_frames: frames since create / reset
+    double t_even, t_odd;        // time of the last even / odd position message
+    uint32_t even_lat, even_lon, odd_lat, odd_lon;
+    uint32_t have;               // bit 0: an even position message was seen, bit 1: an odd one
+    uint32_t pad;
+};
+constexpr uint32_t kTrackUntracked = 0xFFFFFFFFu; // slot of an aircraft the full table turned away
+struct TrackTableDev {
+    uint32_t *index;             // [1 << 24]: ICAO -> record slot + 1, 0 = absent
+    TrackRecord *rec;            // [max_aircraft]
+    uint32_t *size_flags;        // device words: [0] records in use, [1] ADSB_TRACK_TABLE_FULL
+    uint32_t max_aircraft;
+    uint32_t *slot;              // [n] scratch: record slot + 1 of each sorted frame's aircraft (kTrackUntracked)
+};
 struct TrackArgs {
     const adsb_frame *frames;
     const adsb_packet_fields *fields;
     uint32_t n;                  // frames in the list (host value)
     double seconds_per_sample;
+    uint64_t sample_base;        // frame time = (sample_base + offset) x seconds_per_sample
     uint32_t *keys, *vals, *skeys, *svals; // [n] each (keys/vals are reused as tail flags / positions)
     void *temp;
     size_t temp_bytes;
     adsb_track_point *points;    // [n], frame order
-    adsb_aircraft_record *aircraft; // [max_aircraft], ascending ICAO
+    adsb_aircraft_record *aircraft; // [max_aircraft], ascending ICAO (per-launch form only)
     uint32_t max_aircraft;
-    uint64_t *n_aircraft;        // device word
+    uint64_t *n_aircraft;        // device word (per-launch form only)
+    const TrackTableDev *table;  // nullptr: start from an empty map and summarise into `aircraft` (adsb_track_device);
+                                 // otherwise pair with and merge into the persistent table (adsb_track_table_update)
 };
 size_t track_sort_temp_bytes(size_t n);
 hipError_t launch_track(hipStream_t s, const TrackArgs &a);

@@ -2741,7 +2741,7 @@ __constant__ char kIcaoCharset[65] = "#ABCDEFGHIJKLMNOPQRSTUVWXYZ#####_#########
 __global__ __launch_bounds__(256) void decode_fields_kernel(const adsb_frame *frames, const Header *hdr,
                                                            uint32_t cap, adsb_packet_fields *out)
 {
-    const uint64_t n64 = hdr->n_out;
+    const uint64_t n64 = hdr ? hdr->n_out : cap;
     const uint32_t n = n64 < cap ? (uint32_t)n64 : cap;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

@@ -16,6 +16,16 @@
 //      altitude and time of the last position message, last position that was computed).
 // Time is sample offset x seconds_per_sample (the reference stamps packets with the wall clock, which
 // is excluded from parity).  O(frames) work, a few MB: a latency-bound epilogue.
+//
+// The same kernels also serve a persistent aircraft table (adsb_track_table_*, TrackTableDev): the reference
+// keeps ONE HashMap<u32, Aircraft> for the life of its display thread (tui.rs:22-42, web.rs:115), so a pair may
+// straddle two launches.  With a table, two steps go between 1. and 2.:
+//   1a. per segment, the aircraft's record slot from a direct ICAO index (2^24 words, 0 = absent);
+//   1b. an exclusive scan over "new ICAO" segment heads ranks this list's new aircraft in ascending ICAO order,
+//       which is the order they are admitted in while the table has room (the rest are UNTRACKED);
+// 2. falls back, when its walk reaches the segment start with the window still open, to the record's last
+// even / odd position message from before this list; 3. merges the segment into the record in place (one
+// thread per segment = per distinct ICAO: no atomics).
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -87,93 +97,221 @@ __global__ __launch_bounds__(256) void track_keys_kernel(const adsb_packet_field
     vals[i] = i;
 }
 
+__device__ __forceinline__ double frame_time(const adsb_frame *frames, uint32_t i, uint64_t sample_base,
+                                             double seconds_per_sample)
+{
+    return (double)(sample_base + frames[i].offset) * seconds_per_sample;
+}
+
+// table only, 1a: the record slot (+1, 0 = absent) of every sorted frame's aircraft; is_new marks the head of a
+// segment whose ICAO the table does not hold yet
+__global__ __launch_bounds__(256) void track_lookup_kernel(const uint32_t *skeys, uint32_t n, const uint32_t *index,
+                                                           uint32_t *slot, uint32_t *is_new)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t icao = skeys[s]; // < 2^24: track_keys_kernel masks
+    const uint32_t idx = index[icao];
+    slot[s] = idx;
+    is_new[s] = (idx == 0 && (s == 0 || skeys[s - 1] != icao)) ? 1u : 0u;
+}
+
+// table only, 1b: rank = exclusive scan of is_new; new aircraft get the slots size, size + 1, ... in ascending ICAO
+// order while they are below max_aircraft.  The new size goes to size_flags[2] (every thread here reads [0]);
+// track_pairs_kernel moves it to [0].
+__global__ __launch_bounds__(256) void track_admit_kernel(const uint32_t *skeys, uint32_t n, const uint32_t *is_new,
+                                                          const uint32_t *rank, TrackTableDev t)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t size0 = t.size_flags[0];
+    if (s + 1 == n) {
+        const uint64_t grown = (uint64_t)size0 + rank[s] + is_new[s];
+        t.size_flags[2] = grown < t.max_aircraft ? (uint32_t)grown : t.max_aircraft;
+    }
+    if (t.slot[s] != 0) return; // the table holds this aircraft
+    const bool head = is_new[s] != 0;
+    const uint64_t r = (uint64_t)size0 + rank[s] - (head ? 0u : 1u); // a non-head follows its head's 1 in the scan
+    if (r >= t.max_aircraft) {
+        t.slot[s] = kTrackUntracked;
+        if (head) atomicOr(&t.size_flags[1], ADSB_TRACK_TABLE_FULL);
+        return;
+    }
+    t.slot[s] = (uint32_t)r + 1u;
+    if (!head) return;
+    const uint32_t icao = skeys[s];
+    t.index[icao] = (uint32_t)r + 1u;
+    TrackRecord rec;
+    rec.a.latitude = 0.0;
+    rec.a.longitude = 0.0;
+    rec.a.last_contact = __builtin_nan("");
+    rec.a.icao = icao;
+    rec.a.altitude = 0;
+    rec.a.has_position = 0;
+    rec.a.n_frames = 0;
+    for (int k = 0; k < 8; ++k) rec.a.callsign[k] = 0;
+    rec.t_even = 0.0;
+    rec.t_odd = 0.0;
+    rec.even_lat = rec.even_lon = rec.odd_lat = rec.odd_lon = 0;
+    rec.have = 0;
+    rec.pad = 0;
+    t.rec[r] = rec;
+}
+
 __global__ __launch_bounds__(256) void track_pairs_kernel(const adsb_frame *frames, const adsb_packet_fields *fields,
                                                           const uint32_t *skeys, const uint32_t *svals, uint32_t n,
-                                                          double seconds_per_sample, adsb_track_point *points,
+                                                          double seconds_per_sample, uint64_t sample_base,
+                                                          TrackTableDev t, adsb_track_point *points,
                                                           uint32_t *tail_flag)
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
+    const bool table = t.rec != nullptr;
     const uint32_t icao = skeys[s], i = svals[s];
-    tail_flag[s] = (s + 1 == n || skeys[s + 1] != icao) ? 1u : 0u;
-    const adsb_packet_fields f = fields[i];
     adsb_track_point pt;
     pt.latitude = 0.0;
     pt.longitude = 0.0;
     pt.icao = icao;
     pt.flags = 0;
+    uint32_t slot = 0;
+    if (table) {
+        if (s + 1 == n) t.size_flags[0] = t.size_flags[2]; // nothing reads [0] in this kernel
+        slot = t.slot[s];
+        if (slot == kTrackUntracked) { // turned away by the full table: only icao is valid
+            pt.flags = ADSB_TRACK_UNTRACKED;
+            points[i] = pt;
+            return;
+        }
+    } else {
+        tail_flag[s] = (s + 1 == n || skeys[s + 1] != icao) ? 1u : 0u;
+    }
+    const adsb_packet_fields f = fields[i];
     if (f.msg_kind == 1) { // AircraftPosition (aircraft.rs:54)
-        const double t_i = (double)frames[i].offset * seconds_per_sample;
+        const bool i_odd = f.cpr_odd != 0;
+        const double t_i = frame_time(frames, i, sample_base, seconds_per_sample);
+        bool open = true, pair = false; // open: neither a partner nor a frame outside the window found yet
+        uint32_t p_lat = 0, p_lon = 0;
         for (uint32_t w = s; w > 0;) {
             --w;
             if (skeys[w] != icao) break;
             const uint32_t j = svals[w];
-            const double t_j = (double)frames[j].offset * seconds_per_sample;
-            if (fabs(t_i - t_j) > 10.0) break; // aircraft.rs:68-70, 84-86: too old (and so is anything before it)
+            const double t_j = frame_time(frames, j, sample_base, seconds_per_sample);
+            if (fabs(t_i - t_j) > 10.0) { // aircraft.rs:68-70, 84-86: too old (and so is anything before it)
+                open = false;
+                break;
+            }
             const adsb_packet_fields g = fields[j];
             if (g.msg_kind != 1 || g.cpr_odd == f.cpr_odd) continue;
             // the partner: last_odd_packet / last_even_packet at the time frame i arrives
-            const bool i_odd = f.cpr_odd != 0;
-            const uint32_t e_lat = i_odd ? g.cpr_latitude : f.cpr_latitude, e_lon = i_odd ? g.cpr_longitude : f.cpr_longitude;
-            const uint32_t o_lat = i_odd ? f.cpr_latitude : g.cpr_latitude, o_lon = i_odd ? f.cpr_longitude : g.cpr_longitude;
+            open = false;
+            pair = true;
+            p_lat = g.cpr_latitude;
+            p_lon = g.cpr_longitude;
+            break;
+        }
+        if (open && table) { // the walk reached the segment start: the partner is the record's, from an earlier list
+            const TrackRecord &r = t.rec[slot - 1];
+            if (r.have & (i_odd ? 1u : 2u)) {
+                const double t_j = i_odd ? r.t_even : r.t_odd;
+                if (!(fabs(t_i - t_j) > 10.0)) {
+                    pair = true;
+                    p_lat = i_odd ? r.even_lat : r.odd_lat;
+                    p_lon = i_odd ? r.even_lon : r.odd_lon;
+                }
+            }
+        }
+        if (pair) {
+            const uint32_t e_lat = i_odd ? p_lat : f.cpr_latitude, e_lon = i_odd ? p_lon : f.cpr_longitude;
+            const uint32_t o_lat = i_odd ? f.cpr_latitude : p_lat, o_lon = i_odd ? f.cpr_longitude : p_lon;
             double lat, lon;
             if (geographic_position(e_lat, e_lon, o_lat, o_lon, /*first_is_odd=*/!i_odd, lat, lon)) {
                 pt.latitude = lat;
                 pt.longitude = lon;
                 pt.flags = ADSB_TRACK_NEW_POSITION;
             }
-            break;
         }
     }
     points[i] = pt;
 }
 
+// one thread per segment tail: without a table, the aircraft's record from an empty map into out[tail_pos];
+// with one, this list's frames merged into the aircraft's record in place
 __global__ __launch_bounds__(256) void track_summary_kernel(const adsb_frame *frames, const adsb_packet_fields *fields,
                                                             const adsb_track_point *points, const uint32_t *skeys,
                                                             const uint32_t *svals, const uint32_t *tail_flag,
                                                             const uint32_t *tail_pos, uint32_t n,
-                                                            double seconds_per_sample, adsb_aircraft_record *out,
+                                                            double seconds_per_sample, uint64_t sample_base,
+                                                            TrackTableDev t, adsb_aircraft_record *out,
                                                             uint32_t max_aircraft, uint64_t *n_aircraft)
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n || !tail_flag[s]) return;
-    if (s + 1 == n) *n_aircraft = (uint64_t)tail_pos[s] + 1u;
-    const uint32_t a = tail_pos[s];
-    if (a >= max_aircraft) return;
+    if (s >= n) return;
+    const bool table = t.rec != nullptr;
     const uint32_t icao = skeys[s];
-    adsb_aircraft_record r;
-    r.icao = icao;
-    r.altitude = 0;
-    r.latitude = 0.0;
-    r.longitude = 0.0;
-    r.last_contact = __builtin_nan("");
-    r.has_position = 0;
-    r.n_frames = 0;
-    for (int k = 0; k < 8; ++k) r.callsign[k] = 0;
-    bool have_id = false, have_pos_msg = false;
+    uint32_t a;
+    TrackRecord r;
+    if (table) {
+        if (s + 1 != n && skeys[s + 1] == icao) return;
+        a = t.slot[s];
+        if (a == kTrackUntracked) return;
+        r = t.rec[--a];
+    } else {
+        if (!tail_flag[s]) return;
+        if (s + 1 == n) *n_aircraft = (uint64_t)tail_pos[s] + 1u;
+        a = tail_pos[s];
+        if (a >= max_aircraft) return;
+        r.a.icao = icao;
+        r.a.altitude = 0;
+        r.a.latitude = 0.0;
+        r.a.longitude = 0.0;
+        r.a.last_contact = __builtin_nan("");
+        r.a.has_position = 0;
+        r.a.n_frames = 0;
+        for (int k = 0; k < 8; ++k) r.a.callsign[k] = 0;
+    }
+    bool have_id = false, have_pos_msg = false, have_fix = false, have_even = false, have_odd = false;
+    uint32_t count = 0;
     for (uint32_t w = s + 1; w > 0;) { // newest to oldest
         --w;
         if (skeys[w] != icao) break;
         const uint32_t j = svals[w];
         const adsb_packet_fields g = fields[j];
-        ++r.n_frames;
+        ++count;
         if (g.msg_kind == 0 && !have_id) { // aircraft.rs:105-107
             have_id = true;
-            for (int k = 0; k < 8; ++k) r.callsign[k] = g.callsign[k];
+            for (int k = 0; k < 8; ++k) r.a.callsign[k] = g.callsign[k];
         } else if (g.msg_kind == 1) {
             if (!have_pos_msg) { // aircraft.rs:55-56
                 have_pos_msg = true;
-                r.altitude = g.altitude;
-                r.last_contact = (double)frames[j].offset * seconds_per_sample;
+                r.a.altitude = g.altitude;
+                r.a.last_contact = frame_time(frames, j, sample_base, seconds_per_sample);
             }
-            if (!r.has_position && (points[j].flags & ADSB_TRACK_NEW_POSITION)) { // aircraft.rs:97-102
-                r.has_position = 1;
-                r.latitude = points[j].latitude;
-                r.longitude = points[j].longitude;
+            if (!have_fix && (points[j].flags & ADSB_TRACK_NEW_POSITION)) { // aircraft.rs:97-102
+                have_fix = true;
+                r.a.has_position = 1;
+                r.a.latitude = points[j].latitude;
+                r.a.longitude = points[j].longitude;
+            }
+            if (table && g.cpr_odd && !have_odd) { // aircraft.rs:80-82
+                have_odd = true;
+                r.have |= 2u;
+                r.odd_lat = g.cpr_latitude;
+                r.odd_lon = g.cpr_longitude;
+                r.t_odd = frame_time(frames, j, sample_base, seconds_per_sample);
+            } else if (table && !g.cpr_odd && !have_even) { // aircraft.rs:64-66
+                have_even = true;
+                r.have |= 1u;
+                r.even_lat = g.cpr_latitude;
+                r.even_lon = g.cpr_longitude;
+                r.t_even = frame_time(frames, j, sample_base, seconds_per_sample);
             }
         }
     }
-    out[a] = r;
+    r.a.n_frames += count;
+    if (table)
+        t.rec[a] = r;
+    else
+        out[a] = r.a;
 }
 
 } // namespace
@@ -190,21 +328,39 @@ size_t track_sort_temp_bytes(size_t n)
 
 hipError_t launch_track(hipStream_t st, const TrackArgs &a)
 {
-    if (a.n == 0) return hipMemsetAsync(a.n_aircraft, 0, sizeof(uint64_t), st);
+    if (a.n == 0) return a.table ? hipSuccess : hipMemsetAsync(a.n_aircraft, 0, sizeof(uint64_t), st);
     const uint32_t n = a.n, blocks = (n + 255) / 256;
+    TrackTableDev t{};
+    if (a.table) t = *a.table;
     hipLaunchKernelGGL(track_keys_kernel, dim3(blocks), dim3(256), 0, st, a.fields, n, a.keys, a.vals);
     size_t tb = a.temp_bytes;
     hipError_t e = rocprim::radix_sort_pairs(a.temp, tb, (const uint32_t *)a.keys, a.skeys, (const uint32_t *)a.vals,
                                              a.svals, (size_t)n, 0, 24, st);
     if (e != hipSuccess) return e;
+    if (a.table) {
+        hipLaunchKernelGGL(track_lookup_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, t.index, t.slot,
+                           a.keys /* reused: is_new */);
+        tb = a.temp_bytes;
+        e = rocprim::exclusive_scan(a.temp, tb, (const uint32_t *)a.keys, a.vals /* reused: rank */, 0u, (size_t)n,
+                                    rocprim::plus<uint32_t>(), st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(track_admit_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, a.keys, a.vals, t);
+        hipLaunchKernelGGL(track_pairs_kernel, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.skeys, a.svals, n,
+                           a.seconds_per_sample, a.sample_base, t, a.points, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(track_summary_kernel, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.points, a.skeys,
+                           a.svals, (const uint32_t *)nullptr, (const uint32_t *)nullptr, n, a.seconds_per_sample,
+                           a.sample_base, t, (adsb_aircraft_record *)nullptr, 0u, (uint64_t *)nullptr);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(track_pairs_kernel, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.skeys, a.svals, n,
-                       a.seconds_per_sample, a.points, a.keys /* reused: tail flags */);
+                       a.seconds_per_sample, a.sample_base, t, a.points, a.keys /* reused: tail flags */);
     tb = a.temp_bytes;
     e = rocprim::exclusive_scan(a.temp, tb, (const uint32_t *)a.keys, a.vals /* reused: tail positions */, 0u, (size_t)n,
                                 rocprim::plus<uint32_t>(), st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(track_summary_kernel, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.points, a.skeys,
-                       a.svals, a.keys, a.vals, n, a.seconds_per_sample, a.aircraft, a.max_aircraft, a.n_aircraft);
+                       a.svals, a.keys, a.vals, n, a.seconds_per_sample, a.sample_base, t, a.aircraft, a.max_aircraft,
+                       a.n_aircraft);
     return hipGetLastError();
 }
 

@@ -503,6 +503,65 @@ class Feed:
         return out[:n_out.value].copy(), flags.value, first.value
 
 
+class TrackTable:
+    """adsb_track_table_*: one aircraft table on the device that lives across launches (the reference's
+    HashMap<u32, Aircraft> of its display thread), fed one ordered frame list per update."""
+
+    def __init__(self, dem, max_aircraft=0, max_frames=1 << 16, seconds_per_sample=0.5e-6):
+        self._lib, self._dem = dem._lib, dem
+        cfg = L.AdsbTrackTableCfg(L.ADSB_ABI_VERSION, int(max_aircraft), int(max_frames), float(seconds_per_sample))
+        h = C.c_void_p()
+        L.check(self._lib.adsb_track_table_create(dem.handle, C.byref(cfg), C.byref(h)), "adsb_track_table_create")
+        self._h, self.max_frames = h, int(max_frames)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.adsb_track_table_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self):
+        L.check(self._lib.adsb_track_table_reset(self._h), "adsb_track_table_reset")
+
+    def update(self, frames, sample_base=0):
+        """frames: FRAME_DTYPE array in ascending offset (host); packet time = (sample_base + offset) x sps."""
+        frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+        L.check(self._lib.adsb_track_table_update(self._h, frames.ctypes.data if len(frames) else None, len(frames),
+                                                  int(sample_base)), "adsb_track_table_update")
+
+    def update_device(self, dev_ptr, n, sample_base=0):
+        """n frames at dev_ptr in the ctx device's memory (e.g. result_device() after fetch_counts())."""
+        L.check(self._lib.adsb_track_table_update(self._h, dev_ptr, int(n), int(sample_base)), "adsb_track_table_update")
+
+    def points(self):
+        """One TRACK_POINT_DTYPE record per frame of the last update, in its order."""
+        out = np.zeros(max(self.max_frames, 1), dtype=TRACK_POINT_DTYPE)
+        n = C.c_size_t()
+        L.check(self._lib.adsb_track_table_fetch_points(self._h, out.ctypes.data, len(out), C.byref(n)),
+                "adsb_track_table_fetch_points")
+        return out[:n.value].copy()
+
+    def aircraft(self):
+        """(AIRCRAFT_DTYPE records of the whole table in ascending ICAO, table flags)."""
+        n, flags = C.c_size_t(), C.c_uint32()
+        L.check(self._lib.adsb_track_table_fetch(self._h, None, 0, C.byref(n), C.byref(flags)), "adsb_track_table_fetch")
+        out = np.zeros(max(n.value, 1), dtype=AIRCRAFT_DTYPE)
+        L.check(self._lib.adsb_track_table_fetch(self._h, out.ctypes.data, len(out), C.byref(n), C.byref(flags)),
+                "adsb_track_table_fetch")
+        return out[:n.value].copy(), flags.value
+
+
 def packet_new(frame_bytes):
     """AdsbPacket::new (packet.rs:25-49) -> AdsbPacketView."""
     b = (C.c_uint8 * 14)(*bytes(frame_bytes))

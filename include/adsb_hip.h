@@ -232,7 +232,8 @@ int adsb_fields_device(adsb_ctx *ctx, const adsb_packet_fields **fields_dev);
  * threads do with every AdsbPacket, `handle_aircraft_update` (src/adsb/aircraft.rs:158-165 ->
  * Aircraft::handle_packet, aircraft.rs:48-111 -> cpr::calculate_geographic_position, cpr.rs:135-147),
  * applied to the ordered frame list of the last single-channel launch, starting from an empty aircraft
- * map (like the demodulation itself, no state is carried between launches).  Packet time = frame offset
+ * map (like the demodulation itself, no state is carried between launches; adsb_track_table_* below keeps
+ * one aircraft map across launches, as the reference's display threads do).  Packet time = frame offset
  * x seconds_per_sample (the reference stamps the wall clock; excluded from parity).  f64 arithmetic;
  * parity with the reference is by tolerance (its own tests use 1e-4 degrees).
  */
@@ -259,6 +260,48 @@ int adsb_track_device(adsb_ctx *ctx, double seconds_per_sample);
  * ICAO addresses in the list even if fewer records were copied. */
 int adsb_fetch_track(adsb_ctx *ctx, adsb_track_point *points, size_t max_points, size_t *n_points,
                      adsb_aircraft_record *aircraft, size_t max_aircraft, size_t *n_aircraft);
+
+/*
+ * Persistent aircraft table on the device: the reference keeps ONE HashMap<u32, Aircraft> for the life of its
+ * display thread (src/adsb/tui.rs:22-42, src/adsb/web.rs:115) and pairs an even and an odd position message up to
+ * 10 s apart (aircraft.rs:62-95) -- far longer than one 20 000-sample buffer (10 ms at 2 MSPS).  A table applies
+ * ordered frame lists one after the other with handle_aircraft_update semantics (aircraft.rs:48-111,158-165):
+ * cutting one list into any sequence of updates gives the same points and the same final table, and one update
+ * on an empty table gives what adsb_track_device gives on the same list.  Packet time = (sample_base + frame
+ * offset) x seconds_per_sample: with a feed in per-buffer mode (carry = 0) sample_base is adsb_feed_pop's
+ * *first_sample; with carry = 1 (absolute offsets) it is 0.  One table per receiver (an update takes one ordered
+ * list).  Aircraft are never evicted (nor are they in the reference); the table costs 64 MiB of device memory for
+ * its ICAO index plus 88 bytes per aircraft and about 100 bytes per frame of max_frames.  The ctx must outlive
+ * the table; like the ctx, a table is not thread-safe.
+ */
+#define ADSB_TRACK_UNTRACKED 0x2u  /* point flag: this frame's aircraft was not admitted (table full); only icao valid */
+#define ADSB_TRACK_TABLE_FULL 0x1u /* table flag: some aircraft was turned away since create / reset                  */
+typedef struct adsb_track_table adsb_track_table;
+typedef struct adsb_track_table_cfg {
+    uint32_t abi_version;        /* ADSB_ABI_VERSION                                                           */
+    uint32_t max_aircraft;       /* distinct ICAO addresses kept until reset; 0: 65536; at most 2^24            */
+    uint64_t max_frames;         /* longest frame list one update accepts (1 .. 2^32 - 1)                       */
+    double   seconds_per_sample; /* packet time = (sample_base + frame.offset) x this; 0.5e-6 at 2 MSPS         */
+} adsb_track_table_cfg;
+int adsb_track_table_create(adsb_ctx *ctx, const adsb_track_table_cfg *cfg, adsb_track_table **out_table);
+void adsb_track_table_destroy(adsb_track_table *table);
+/* Empties the map and clears the flags (ordered after the table's last update). */
+int adsb_track_table_reset(adsb_track_table *table);
+/*
+ * Applies one ordered frame list (ascending offset).  `frames` is host memory or device memory of the ctx's
+ * device (e.g. adsb_result_device after adsb_fetch_counts).  Host frames have been copied when this returns; the
+ * kernels run asynchronously on the ctx stream, ordered after the ctx's last launch.  New ICAO addresses of one
+ * update are admitted in ascending order while the table has room; the frames of the others get
+ * ADSB_TRACK_UNTRACKED and the table ADSB_TRACK_TABLE_FULL.  ADSB_E_CAPACITY for n > max_frames.
+ */
+int adsb_track_table_update(adsb_track_table *table, const adsb_frame *frames, size_t n, uint64_t sample_base);
+/* Waits; one point per frame of the LAST update, in its order (ADSB_E_STATE before any update). */
+int adsb_track_table_fetch_points(adsb_track_table *table, adsb_track_point *points, size_t max_points,
+                                  size_t *n_points);
+/* Waits; the whole table in ascending ICAO (n_frames = frames since create / reset); *n_aircraft = table size even
+ * if it exceeds max_aircraft; *flags (optional) = ADSB_TRACK_TABLE_FULL or 0. */
+int adsb_track_table_fetch(adsb_track_table *table, adsb_aircraft_record *aircraft, size_t max_aircraft,
+                           size_t *n_aircraft, uint32_t *flags);
 
 /*
  * ---- several GPUs behind one call ---------------------------------------------------------
