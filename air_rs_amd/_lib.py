@@ -93,6 +93,11 @@ class AdsbTrackTableCfg(C.Structure):
                 ("seconds_per_sample", C.c_double)]
 
 
+class AdsbTrackBankCfg(C.Structure):
+    _fields_ = [("abi_version", C.c_uint32), ("n_receivers", C.c_uint32), ("max_aircraft", C.c_uint32),
+                ("reserved", C.c_uint32), ("max_frames", C.c_uint64), ("seconds_per_sample", C.c_double)]
+
+
 class AdsbPacketView(C.Structure):
     _fields_ = [("packet", C.c_uint8 * 14), ("downlink_format", C.c_uint8), ("capability", C.c_uint8),
                 ("icao", C.c_uint32), ("msg_type", C.c_uint8), ("msg_kind", C.c_int32),
@@ -127,6 +132,14 @@ PROTOTYPES = {
     "adsb_track_table_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]),
     "adsb_track_table_fetch_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_table_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), _P(C.c_uint32)]),
+    "adsb_track_bank_create": (C.c_int, [C.c_void_p, _P(AdsbTrackBankCfg), _P(C.c_void_p)]),
+    "adsb_track_bank_destroy": (None, [C.c_void_p]),
+    "adsb_track_bank_reset": (C.c_int, [C.c_void_p]),
+    "adsb_track_bank_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_uint64), _P(C.c_uint64)]),
+    "adsb_track_bank_update_launch": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "adsb_track_bank_fetch_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_bank_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), _P(C.c_uint64),
+                                        _P(C.c_uint32)]),
     "adsb_cpr_num_zones": (C.c_uint32, [C.c_double]),
     "adsb_cpr_position": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P(C.c_double),
                                     _P(C.c_double)]),

@@ -1026,6 +1026,268 @@ extern "C" int adsb_track_table_fetch(adsb_track_table *t, adsb_aircraft_record 
     return ADSB_OK;
 }
 
+// ---- a bank of persistent tables, one per receiver (adsb_track_bank_*): the tracker kernels with a TrackBankDev ----
+struct adsb_track_bank {
+    adsb_ctx *ctx = nullptr;
+    adsb_track_bank_cfg cfg{};
+    adsbk::TrackBankDev dev{};      // hash, records [R x max_aircraft], per-receiver words, prefix, per-frame scan words
+    adsbk::TrackTableDev tab{};     // what the shared kernels read: rec = dev.rec, slot [max_frames]
+    uint32_t *words = nullptr;      // [3R]: size, flags, size_next (dev.size / dev.flags / dev.size_next)
+    uint64_t *meta = nullptr;       // device [2R + 1]: prefix of the host counts [R + 1], then sample_base [R]
+    uint64_t *meta_pinned = nullptr; // pinned staging of meta
+    uint32_t *u32 = nullptr;        // 4 x [max_frames]: keys, vals, sorted keys, sorted vals
+    void *temp = nullptr;
+    size_t temp_bytes = 0;
+    adsb_frame *frames = nullptr;   // [max_frames]: device copy of a host list
+    adsb_frame *pinned = nullptr;   // [max_frames]: pinned staging of that copy
+    hipEvent_t copied = nullptr;    // the last copies out of `pinned` and `meta_pinned` have finished
+    adsb_packet_fields *fields = nullptr; // [max_frames]
+    adsb_track_point *points = nullptr;   // [max_frames], the last update's, list order
+    uint32_t n_points = 0;
+    bool updated = false;
+};
+
+static void track_bank_free(adsb_track_bank *b)
+{
+    (void)hipSetDevice(b->ctx->cfg.device);
+    (void)hipStreamSynchronize(b->ctx->aux);
+    for (void *p : {(void *)b->dev.hash, (void *)b->dev.rec, (void *)b->words, (void *)b->dev.prefix, (void *)b->meta,
+                    (void *)b->dev.mark, (void *)b->dev.excl, (void *)b->dev.seg_slot, (void *)b->tab.slot,
+                    (void *)b->u32, b->temp, (void *)b->frames, (void *)b->fields, (void *)b->points})
+        if (p) (void)hipFree(p);
+    if (b->pinned) (void)hipHostFree(b->pinned);
+    if (b->meta_pinned) (void)hipHostFree(b->meta_pinned);
+    if (b->copied) (void)hipEventDestroy(b->copied);
+    delete b;
+}
+
+extern "C" int adsb_track_bank_reset(adsb_track_bank *b)
+{
+    if (!b) return ADSB_E_ARG;
+    HIPCHK(hipSetDevice(b->ctx->cfg.device));
+    HIPCHK(hipMemsetAsync(b->dev.hash, 0, sizeof(unsigned long long) * (b->dev.hash_mask + 1), b->ctx->aux));
+    HIPCHK(hipMemsetAsync(b->words, 0, sizeof(uint32_t) * 3 * b->cfg.n_receivers, b->ctx->aux));
+    b->n_points = 0;
+    b->updated = false;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_create(adsb_ctx *c, const adsb_track_bank_cfg *cfg, adsb_track_bank **out)
+{
+    if (!c || !cfg || !out || cfg->abi_version != ADSB_ABI_VERSION || cfg->reserved != 0) return ADSB_E_ARG;
+    if (cfg->n_receivers == 0 || cfg->n_receivers > 256 || cfg->max_frames == 0 || cfg->max_frames > 0xFFFFFFFFull ||
+        !(cfg->seconds_per_sample > 0.0) || cfg->max_aircraft > (1u << 24))
+        return ADSB_E_ARG;
+    *out = nullptr;
+    const uint32_t nr = cfg->n_receivers, max_ac = cfg->max_aircraft ? cfg->max_aircraft : 65536u;
+    const uint64_t n_rec = (uint64_t)nr * max_ac;
+    if (n_rec >= 0xFFFFFFFFull) return ADSB_E_NOMEM; // slot + 1 must fit 32 bits: 2^32 records would need > 350 GiB
+    HIPCHK(hipSetDevice(c->cfg.device));
+    adsb_track_bank *b = new (std::nothrow) adsb_track_bank;
+    if (!b) return ADSB_E_NOMEM;
+    b->ctx = c;
+    b->cfg = *cfg;
+    b->cfg.max_aircraft = max_ac;
+    const size_t nf = (size_t)b->cfg.max_frames;
+    uint64_t cap = 1;
+    while (cap < 2 * n_rec) cap <<= 1;
+    b->dev.hash_mask = cap - 1;
+    b->dev.max_aircraft = max_ac;
+    b->dev.n_receivers = nr;
+    uint32_t bits = 0;
+    while ((1u << bits) < nr) ++bits;
+    b->dev.key_bits = 24 + bits;
+    b->temp_bytes = adsbk::track_bank_temp_bytes(nf);
+    bool ok = hipMalloc((void **)&b->dev.hash, sizeof(unsigned long long) * cap) == hipSuccess &&
+              hipMalloc((void **)&b->dev.rec, sizeof(adsbk::TrackRecord) * n_rec) == hipSuccess &&
+              hipMalloc((void **)&b->words, sizeof(uint32_t) * 3 * nr) == hipSuccess &&
+              hipMalloc((void **)&b->dev.prefix, sizeof(uint32_t) * (nr + 1)) == hipSuccess &&
+              hipMalloc((void **)&b->meta, sizeof(uint64_t) * (2 * nr + 1)) == hipSuccess &&
+              hipHostMalloc((void **)&b->meta_pinned, sizeof(uint64_t) * (2 * nr + 1), hipHostMallocDefault) == hipSuccess &&
+              hipMalloc((void **)&b->dev.mark, sizeof(unsigned long long) * nf) == hipSuccess &&
+              hipMalloc((void **)&b->dev.excl, sizeof(unsigned long long) * nf) == hipSuccess &&
+              hipMalloc((void **)&b->dev.seg_slot, sizeof(uint32_t) * nf) == hipSuccess &&
+              hipMalloc((void **)&b->tab.slot, sizeof(uint32_t) * nf) == hipSuccess &&
+              hipMalloc((void **)&b->u32, sizeof(uint32_t) * 4 * nf) == hipSuccess &&
+              hipMalloc(&b->temp, b->temp_bytes) == hipSuccess &&
+              hipMalloc((void **)&b->frames, sizeof(adsb_frame) * nf) == hipSuccess &&
+              hipHostMalloc((void **)&b->pinned, sizeof(adsb_frame) * nf, hipHostMallocDefault) == hipSuccess &&
+              hipEventCreateWithFlags(&b->copied, hipEventDisableTiming) == hipSuccess &&
+              hipMalloc((void **)&b->fields, sizeof(adsb_packet_fields) * nf) == hipSuccess &&
+              hipMalloc((void **)&b->points, sizeof(adsb_track_point) * nf) == hipSuccess;
+    if (ok) {
+        b->dev.size = b->words;
+        b->dev.flags = b->words + nr;
+        b->dev.size_next = b->words + 2 * nr;
+        b->dev.sample_base = b->meta + nr + 1;
+        b->tab.rec = b->dev.rec;
+        b->tab.max_aircraft = max_ac;
+    }
+    int rc = ok ? adsb_track_bank_reset(b) : ADSB_E_NOMEM;
+    if (rc == ADSB_OK && hipStreamSynchronize(c->aux) != hipSuccess) rc = ADSB_E_NOMEM;
+    if (rc != ADSB_OK) {
+        (void)hipGetLastError();
+        track_bank_free(b);
+        return rc;
+    }
+    *out = b;
+    return ADSB_OK;
+}
+
+extern "C" void adsb_track_bank_destroy(adsb_track_bank *b)
+{
+    if (b) track_bank_free(b);
+}
+
+// Enqueues the bank's kernels over n frames at `list` (device) with the receiver split src_prefix[0..n_src]; meta's
+// sample_base part has been filled by the caller (and the staging copy enqueued).
+static int track_bank_run(adsb_track_bank *b, const adsb_frame *list, uint32_t n, const uint64_t *src_prefix,
+                          uint32_t n_src)
+{
+    adsb_ctx *c = b->ctx;
+    HIPCHK(adsbk::launch_decode_fields(c->aux, list, nullptr, n, b->fields));
+    adsbk::TrackBankDev dev = b->dev;
+    dev.src_prefix = src_prefix;
+    dev.n_src = n_src;
+    adsbk::TrackArgs a{};
+    a.frames = list;
+    a.fields = b->fields;
+    a.n = n;
+    a.seconds_per_sample = b->cfg.seconds_per_sample;
+    const size_t nf = (size_t)b->cfg.max_frames;
+    a.keys = b->u32;
+    a.vals = b->u32 + nf;
+    a.skeys = b->u32 + 2 * nf;
+    a.svals = b->u32 + 3 * nf;
+    a.temp = b->temp;
+    a.temp_bytes = b->temp_bytes;
+    a.points = b->points;
+    a.table = &b->tab;
+    a.bank = &dev;
+    HIPCHK(adsbk::launch_track(c->aux, a));
+    return ADSB_OK;
+}
+
+// Stages sample_base (and, for a host split, the counts' prefix) through meta_pinned; frames_host: also the frames.
+static int track_bank_stage(adsb_track_bank *b, const uint64_t *counts, const uint64_t *sample_base,
+                            const adsb_frame *frames_host, size_t n)
+{
+    adsb_ctx *c = b->ctx;
+    const uint32_t nr = b->cfg.n_receivers;
+    HIPCHK(hipEventSynchronize(b->copied)); // the previous update's copies out of the staging have finished
+    uint64_t *m = b->meta_pinned;
+    m[0] = 0;
+    for (uint32_t r = 0; r < nr; ++r) {
+        m[r + 1] = m[r] + (counts ? counts[r] : 0);
+        m[nr + 1 + r] = sample_base ? sample_base[r] : 0;
+    }
+    HIPCHK(hipMemcpyAsync(b->meta, m, sizeof(uint64_t) * (2 * nr + 1), hipMemcpyHostToDevice, c->aux));
+    if (frames_host) {
+        std::memcpy(b->pinned, frames_host, sizeof(adsb_frame) * n);
+        HIPCHK(hipMemcpyAsync(b->frames, b->pinned, sizeof(adsb_frame) * n, hipMemcpyHostToDevice, c->aux));
+    }
+    HIPCHK(hipEventRecord(b->copied, c->aux));
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_update(adsb_track_bank *b, const adsb_frame *frames, size_t n, const uint64_t *counts,
+                                      const uint64_t *sample_base)
+{
+    if (!b || (!frames && n) || (!counts && n)) return ADSB_E_ARG;
+    if (counts) {
+        uint64_t sum = 0;
+        for (uint32_t r = 0; r < b->cfg.n_receivers; ++r) {
+            if (counts[r] > n - sum) return ADSB_E_ARG;
+            sum += counts[r];
+        }
+        if (sum != n) return ADSB_E_ARG;
+    }
+    if (n > b->cfg.max_frames) return ADSB_E_CAPACITY;
+    adsb_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    b->n_points = (uint32_t)n;
+    b->updated = true;
+    if (n == 0) return ADSB_OK;
+    hipPointerAttribute_t at{};
+    const bool on_device = hipPointerGetAttributes(&at, frames) == hipSuccess && at.type == hipMemoryTypeDevice &&
+                           at.device == c->cfg.device;
+    (void)hipGetLastError(); // a plain host pointer is an error to the query: do not leave it to the launches below
+    int rc = track_bank_stage(b, counts, sample_base, on_device ? nullptr : frames, n);
+    if (rc != ADSB_OK) return rc;
+    return track_bank_run(b, on_device ? frames : b->frames, (uint32_t)n, b->meta, b->cfg.n_receivers);
+}
+
+extern "C" int adsb_track_bank_update_launch(adsb_track_bank *b, const uint64_t *sample_base)
+{
+    if (!b) return ADSB_E_ARG;
+    adsb_ctx *c = b->ctx;
+    if (!c->launched) return ADSB_E_STATE;
+    if (c->last_channels > b->cfg.n_receivers) return ADSB_E_ARG;
+    int rc = sync_header(c); // the list's length, as adsb_fetch_counts (and the rebuild after a slot-pool overflow)
+    if (rc != ADSB_OK) return rc;
+    const uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
+    if (n > b->cfg.max_frames) return ADSB_E_CAPACITY;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    b->n_points = (uint32_t)n;
+    b->updated = true;
+    if (n == 0) return ADSB_OK;
+    if ((rc = track_bank_stage(b, nullptr, sample_base, nullptr, 0)) != ADSB_OK) return rc;
+    adsb_ctx::ResultSet &r = c->rs[c->last];
+    // the channel split as adsb_fetch's per_channel_counts reads it: chan_prefix clipped to the list
+    if ((rc = track_bank_run(b, c->last_out, (uint32_t)n, r.chan_prefix, c->last_channels)) != ADSB_OK) return rc;
+    if (c->own_aux) { // the launch that reuses this result set waits for these kernels too
+        HIPCHK(hipEventRecord(r.g_done, c->aux));
+        r.g_pending = true;
+    }
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_fetch_points(adsb_track_bank *b, adsb_track_point *points, size_t max_points,
+                                            size_t *n_points)
+{
+    if (!b || (!points && max_points)) return ADSB_E_ARG;
+    if (!b->updated) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(b->ctx->cfg.device));
+    const size_t np = std::min<size_t>(b->n_points, max_points);
+    if (np) HIPCHK(hipMemcpyAsync(points, b->points, sizeof(adsb_track_point) * np, hipMemcpyDeviceToHost, b->ctx->aux));
+    HIPCHK(hipStreamSynchronize(b->ctx->aux));
+    if (n_points) *n_points = np;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_fetch(adsb_track_bank *b, adsb_aircraft_record *aircraft, size_t max_aircraft,
+                                     size_t *n_aircraft, uint64_t *per_receiver_counts, uint32_t *flags)
+{
+    if (!b || (!aircraft && max_aircraft)) return ADSB_E_ARG;
+    adsb_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const uint32_t nr = b->cfg.n_receivers, max_ac = b->cfg.max_aircraft;
+    std::vector<uint32_t> w(2 * (size_t)nr);
+    HIPCHK(hipMemcpyAsync(w.data(), b->words, sizeof(uint32_t) * w.size(), hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    size_t total = 0, copied = 0;
+    std::vector<adsbk::TrackRecord> recs;
+    for (uint32_t r = 0; r < nr; ++r) {
+        const size_t size = std::min<uint32_t>(w[r], max_ac);
+        total += size;
+        const size_t take = std::min(size, max_aircraft - copied);
+        if (take) { // slots are in admission order: sort each receiver's records by ICAO here
+            recs.resize(size);
+            HIPCHK(hipMemcpyAsync(recs.data(), b->dev.rec + (size_t)r * max_ac, sizeof(adsbk::TrackRecord) * size,
+                                  hipMemcpyDeviceToHost, c->aux));
+            HIPCHK(hipStreamSynchronize(c->aux));
+            std::sort(recs.begin(), recs.end(),
+                      [](const adsbk::TrackRecord &x, const adsbk::TrackRecord &y) { return x.a.icao < y.a.icao; });
+            for (size_t k = 0; k < take; ++k) aircraft[copied + k] = recs[k].a;
+        }
+        copied += take;
+        if (per_receiver_counts) per_receiver_counts[r] = take;
+        if (flags) flags[r] = w[nr + r];
+    }
+    if (n_aircraft) *n_aircraft = total;
+    return ADSB_OK;
+}
+
 extern "C" int adsb_set_result_target(adsb_ctx *c, void *blob_dev, size_t blob_bytes)
 {
     if (!c) return ADSB_E_ARG;

@@ -181,6 +181,27 @@ struct TrackTableDev {
     uint32_t max_aircraft;
     uint32_t *slot;              // [n] scratch: record slot + 1 of each sorted frame's aircraft (kTrackUntracked)
 };
+// A bank of persistent tables, one per receiver (adsb_track_bank_*): sort key = receiver << 24 | icao, an open-addressing
+// hash of that key -> record slot + 1 instead of the table's direct ICAO index, per-receiver sizes and flags.
+struct TrackBankDev {
+    unsigned long long *hash;    // [hash_mask + 1]: (record slot + 1) << 32 | key, 0 = empty (insert by atomicCAS)
+    uint64_t hash_mask;          // capacity - 1, capacity a power of two >= 2 x n_receivers x max_aircraft
+    TrackRecord *rec;            // [n_receivers x max_aircraft]: receiver r's records at [r x max_aircraft, ...)
+    uint32_t *size;              // [n_receivers] records in use
+    uint32_t *flags;             // [n_receivers] ADSB_TRACK_TABLE_FULL
+    uint32_t *size_next;         // [n_receivers] staging: the admission kernel's new sizes, moved to size by the pairs kernel
+    uint32_t max_aircraft;       // per receiver
+    uint32_t n_receivers;
+    uint32_t *prefix;            // [n_receivers + 1]: frames of the list before each receiver's first (last = n); also
+                                 // where each receiver's first frame sits in sorted order
+    const uint64_t *sample_base; // [n_receivers]: frame time = (sample_base[r] + offset) x seconds_per_sample
+    const uint64_t *src_prefix;  // [n_src + 1] (device): the receiver split as given (host counts' prefix, or the
+    uint32_t n_src;              // launch's chan_prefix); clipped to n into `prefix`, receivers >= n_src get nothing
+    uint32_t key_bits;           // 24 + ceil(log2 n_receivers)
+    unsigned long long *mark;    // [n] per sorted frame: segment head << 32 | head of a key the hash does not hold
+    unsigned long long *excl;    // [n] exclusive scan of mark
+    uint32_t *seg_slot;          // [n] per segment (hi of the scan): record slot + 1 (kTrackUntracked)
+};
 struct TrackArgs {
     const adsb_frame *frames;
     const adsb_packet_fields *fields;
@@ -196,8 +217,11 @@ struct TrackArgs {
     uint64_t *n_aircraft;        // device word (per-launch form only)
     const TrackTableDev *table;  // nullptr: start from an empty map and summarise into `aircraft` (adsb_track_device);
                                  // otherwise pair with and merge into the persistent table (adsb_track_table_update)
+    const TrackBankDev *bank;    // non-null: the list holds several receivers' frames (adsb_track_bank_update); `table`
+                                 // then carries the bank's records in rec and the per-frame slot scratch in slot
 };
 size_t track_sort_temp_bytes(size_t n);
+size_t track_bank_temp_bytes(size_t n); // the bank's sort (32 bits) and 64-bit scan
 hipError_t launch_track(hipStream_t s, const TrackArgs &a);
 
 // test / measurement kernels

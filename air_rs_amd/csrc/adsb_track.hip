@@ -26,6 +26,15 @@
 // 2. falls back, when its walk reaches the segment start with the window still open, to the record's last
 // even / odd position message from before this list; 3. merges the segment into the record in place (one
 // thread per segment = per distinct ICAO: no atomics).
+//
+// A bank (adsb_track_bank_*, TrackBankDev) is N such tables, one per receiver, updated by ONE dispatch sequence over a
+// multi-channel list (receiver r's frames, then receiver r+1's, ...).  The sort key becomes receiver << 24 | icao over
+// 24 + ceil(log2 N) bits, so segments never mix receivers and receiver r's frames sit at [prefix[r], prefix[r+1]) in
+// sorted order.  A direct 2^24 index per receiver would cost 64 MiB x N, so 1a probes an open-addressing hash of the
+// key instead, once per segment head; 1b scans (segment head, new key) pairs in one 64-bit word, which gives every
+// frame its segment and every new key its rank, made per receiver by subtracting the rank at prefix[r].  Slots come
+// from that rank alone (receiver r's records live at [r x max_aircraft, (r+1) x max_aircraft)), never from where the
+// hash put an entry, so no result depends on insert order.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -103,6 +112,25 @@ __device__ __forceinline__ double frame_time(const adsb_frame *frames, uint32_t 
     return (double)(sample_base + frames[i].offset) * seconds_per_sample;
 }
 
+__device__ __forceinline__ TrackRecord empty_record(uint32_t icao)
+{
+    TrackRecord rec;
+    rec.a.latitude = 0.0;
+    rec.a.longitude = 0.0;
+    rec.a.last_contact = __builtin_nan("");
+    rec.a.icao = icao;
+    rec.a.altitude = 0;
+    rec.a.has_position = 0;
+    rec.a.n_frames = 0;
+    for (int k = 0; k < 8; ++k) rec.a.callsign[k] = 0;
+    rec.t_even = 0.0;
+    rec.t_odd = 0.0;
+    rec.even_lat = rec.even_lon = rec.odd_lat = rec.odd_lon = 0;
+    rec.have = 0;
+    rec.pad = 0;
+    return rec;
+}
+
 // table only, 1a: the record slot (+1, 0 = absent) of every sorted frame's aircraft; is_new marks the head of a
 // segment whose ICAO the table does not hold yet
 __global__ __launch_bounds__(256) void track_lookup_kernel(const uint32_t *skeys, uint32_t n, const uint32_t *index,
@@ -141,40 +169,142 @@ __global__ __launch_bounds__(256) void track_admit_kernel(const uint32_t *skeys,
     if (!head) return;
     const uint32_t icao = skeys[s];
     t.index[icao] = (uint32_t)r + 1u;
-    TrackRecord rec;
-    rec.a.latitude = 0.0;
-    rec.a.longitude = 0.0;
-    rec.a.last_contact = __builtin_nan("");
-    rec.a.icao = icao;
-    rec.a.altitude = 0;
-    rec.a.has_position = 0;
-    rec.a.n_frames = 0;
-    for (int k = 0; k < 8; ++k) rec.a.callsign[k] = 0;
-    rec.t_even = 0.0;
-    rec.t_odd = 0.0;
-    rec.even_lat = rec.even_lon = rec.odd_lat = rec.odd_lon = 0;
-    rec.have = 0;
-    rec.pad = 0;
-    t.rec[r] = rec;
+    t.rec[r] = empty_record(icao);
 }
 
+// bank only: the receiver split clipped to the list (prefix[0] = 0, prefix[k] = n for k >= n_src), as adsb_fetch's
+// per_channel_counts cut the first n frames
+__device__ __forceinline__ uint32_t bank_prefix(const TrackBankDev &b, uint32_t k, uint32_t n)
+{
+    if (k == 0) return 0;
+    if (k >= b.n_src) return n;
+    const uint64_t p = b.src_prefix[k];
+    return p < n ? (uint32_t)p : n;
+}
+
+__device__ __forceinline__ uint64_t bank_hash(uint32_t key) // fmix64 (MurmurHash3's finaliser)
+{
+    uint64_t x = key;
+    x ^= x >> 33;
+    x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33;
+    x *= 0xc4ceb9fe1a85ec53ull;
+    x ^= x >> 33;
+    return x;
+}
+
+// bank only: key = receiver << 24 | icao (receiver of frame i: the last k with prefix[k] <= i); threads 0..N also
+// write the clipped prefix the later kernels read
+__global__ __launch_bounds__(256) void track_bank_keys_kernel(const adsb_packet_fields *fields, uint32_t n,
+                                                              TrackBankDev b, uint32_t *keys, uint32_t *vals)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i <= b.n_receivers) b.prefix[i] = bank_prefix(b, i, n);
+    if (i >= n) return;
+    uint32_t lo = 0, hi = b.n_src < b.n_receivers ? b.n_src : b.n_receivers; // prefix[lo] <= i < prefix[hi] (= n)
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (bank_prefix(b, mid, n) <= i)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    keys[i] = lo << 24 | (fields[i].icao & 0xFFFFFFu);
+    vals[i] = i;
+}
+
+// bank only, 1a: segment heads probe the hash (slot[s] = record slot + 1 or 0); mark = head << 32 | new key
+__global__ __launch_bounds__(256) void track_bank_lookup_kernel(const uint32_t *skeys, uint32_t n, TrackBankDev b,
+                                                                uint32_t *slot)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s];
+    if (s != 0 && skeys[s - 1] == key) {
+        b.mark[s] = 0;
+        return;
+    }
+    uint32_t found = 0;
+    for (uint64_t h = bank_hash(key) & b.hash_mask;; h = (h + 1) & b.hash_mask) { // load <= 1/2: an empty entry exists
+        const unsigned long long e = b.hash[h];
+        if (e == 0) break;
+        if ((uint32_t)e == key) {
+            found = (uint32_t)(e >> 32);
+            break;
+        }
+    }
+    slot[s] = found;
+    b.mark[s] = 1ull << 32 | (found ? 0u : 1u);
+}
+
+// bank only, 1b: excl = exclusive scan of mark: hi = segment number of a head, lo = new keys before s.  A new key of
+// receiver r gets slot size[r] + (its rank - the rank at prefix[r]) while that is below max_aircraft; the head
+// inserts it into the hash (distinct keys: no two threads insert the same one) and publishes its segment's slot in
+// seg_slot.  The last frame of each receiver stages the receiver's new size in size_next (every thread here reads
+// size); track_pairs_kernel moves it.
+__global__ __launch_bounds__(256) void track_bank_admit_kernel(const uint32_t *skeys, uint32_t n, TrackBankDev b,
+                                                               const uint32_t *slot)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s], r = key >> 24;
+    const uint64_t m = b.mark[s], e = b.excl[s];
+    const uint32_t rank0 = (uint32_t)b.excl[b.prefix[r]], size0 = b.size[r];
+    if (s + 1 == b.prefix[r + 1]) {
+        const uint64_t grown = (uint64_t)size0 + (uint32_t)e + (uint32_t)m - rank0;
+        b.size_next[r] = grown < b.max_aircraft ? (uint32_t)grown : b.max_aircraft;
+    }
+    if (!(m >> 32)) return; // not a segment head
+    const uint32_t g = (uint32_t)(e >> 32);
+    if (slot[s] != 0) { // the receiver holds this aircraft
+        b.seg_slot[g] = slot[s];
+        return;
+    }
+    const uint64_t local = (uint64_t)size0 + (uint32_t)e - rank0;
+    if (local >= b.max_aircraft) {
+        b.seg_slot[g] = kTrackUntracked;
+        atomicOr(&b.flags[r], ADSB_TRACK_TABLE_FULL);
+        return;
+    }
+    const uint32_t a = r * b.max_aircraft + (uint32_t)local; // < n_receivers x max_aircraft < 2^32 - 1 (create checks)
+    const unsigned long long entry = (unsigned long long)(a + 1u) << 32 | key;
+    for (uint64_t h = bank_hash(key) & b.hash_mask;; h = (h + 1) & b.hash_mask)
+        if (atomicCAS(&b.hash[h], 0ull, entry) == 0ull) break;
+    b.rec[a] = empty_record(key & 0xFFFFFFu);
+    b.seg_slot[g] = a + 1u;
+}
+
+template <bool kBank>
 __global__ __launch_bounds__(256) void track_pairs_kernel(const adsb_frame *frames, const adsb_packet_fields *fields,
                                                           const uint32_t *skeys, const uint32_t *svals, uint32_t n,
                                                           double seconds_per_sample, uint64_t sample_base,
-                                                          TrackTableDev t, adsb_track_point *points,
+                                                          TrackTableDev t, TrackBankDev b, adsb_track_point *points,
                                                           uint32_t *tail_flag)
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
     const bool table = t.rec != nullptr;
-    const uint32_t icao = skeys[s], i = svals[s];
+    const uint32_t key = skeys[s], i = svals[s];
+    const uint32_t icao = kBank ? key & 0xFFFFFFu : key;
     adsb_track_point pt;
     pt.latitude = 0.0;
     pt.longitude = 0.0;
     pt.icao = icao;
     pt.flags = 0;
     uint32_t slot = 0;
-    if (table) {
+    if (kBank) { // every frame takes its segment's slot (seg_slot) and keeps it in t.slot for track_summary_kernel
+        const uint32_t r = key >> 24;
+        sample_base = b.sample_base[r];
+        if (s + 1 == b.prefix[r + 1]) b.size[r] = b.size_next[r]; // nothing reads size in this kernel
+        const bool head = s == 0 || skeys[s - 1] != key;
+        slot = b.seg_slot[(uint32_t)(b.excl[s] >> 32) - (head ? 0u : 1u)];
+        t.slot[s] = slot;
+        if (slot == kTrackUntracked) {
+            pt.flags = ADSB_TRACK_UNTRACKED;
+            points[i] = pt;
+            return;
+        }
+    } else if (table) {
         if (s + 1 == n) t.size_flags[0] = t.size_flags[2]; // nothing reads [0] in this kernel
         slot = t.slot[s];
         if (slot == kTrackUntracked) { // turned away by the full table: only icao is valid
@@ -193,7 +323,7 @@ __global__ __launch_bounds__(256) void track_pairs_kernel(const adsb_frame *fram
         uint32_t p_lat = 0, p_lon = 0;
         for (uint32_t w = s; w > 0;) {
             --w;
-            if (skeys[w] != icao) break;
+            if (skeys[w] != key) break;
             const uint32_t j = svals[w];
             const double t_j = frame_time(frames, j, sample_base, seconds_per_sample);
             if (fabs(t_i - t_j) > 10.0) { // aircraft.rs:68-70, 84-86: too old (and so is anything before it)
@@ -235,23 +365,26 @@ __global__ __launch_bounds__(256) void track_pairs_kernel(const adsb_frame *fram
 }
 
 // one thread per segment tail: without a table, the aircraft's record from an empty map into out[tail_pos];
-// with one, this list's frames merged into the aircraft's record in place
+// with one (or a bank), this list's frames merged into the aircraft's record in place
+template <bool kBank>
 __global__ __launch_bounds__(256) void track_summary_kernel(const adsb_frame *frames, const adsb_packet_fields *fields,
                                                             const adsb_track_point *points, const uint32_t *skeys,
                                                             const uint32_t *svals, const uint32_t *tail_flag,
                                                             const uint32_t *tail_pos, uint32_t n,
                                                             double seconds_per_sample, uint64_t sample_base,
-                                                            TrackTableDev t, adsb_aircraft_record *out,
+                                                            TrackTableDev t, TrackBankDev b, adsb_aircraft_record *out,
                                                             uint32_t max_aircraft, uint64_t *n_aircraft)
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
     const bool table = t.rec != nullptr;
-    const uint32_t icao = skeys[s];
+    const uint32_t key = skeys[s];
+    const uint32_t icao = kBank ? key & 0xFFFFFFu : key;
+    if (kBank) sample_base = b.sample_base[key >> 24];
     uint32_t a;
     TrackRecord r;
     if (table) {
-        if (s + 1 != n && skeys[s + 1] == icao) return;
+        if (s + 1 != n && skeys[s + 1] == key) return;
         a = t.slot[s];
         if (a == kTrackUntracked) return;
         r = t.rec[--a];
@@ -273,7 +406,7 @@ __global__ __launch_bounds__(256) void track_summary_kernel(const adsb_frame *fr
     uint32_t count = 0;
     for (uint32_t w = s + 1; w > 0;) { // newest to oldest
         --w;
-        if (skeys[w] != icao) break;
+        if (skeys[w] != key) break;
         const uint32_t j = svals[w];
         const adsb_packet_fields g = fields[j];
         ++count;
@@ -326,12 +459,47 @@ size_t track_sort_temp_bytes(size_t n)
     return (sort_bytes > scan_bytes ? sort_bytes : scan_bytes) + 256;
 }
 
+size_t track_bank_temp_bytes(size_t n)
+{
+    size_t sort_bytes = 0, scan_bytes = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                    (const uint32_t *)nullptr, (uint32_t *)nullptr, n, 0, 32, (hipStream_t)0);
+    (void)rocprim::exclusive_scan(nullptr, scan_bytes, (const unsigned long long *)nullptr,
+                                  (unsigned long long *)nullptr, 0ull, n, rocprim::plus<unsigned long long>(),
+                                  (hipStream_t)0);
+    return (sort_bytes > scan_bytes ? sort_bytes : scan_bytes) + 256;
+}
+
 hipError_t launch_track(hipStream_t st, const TrackArgs &a)
 {
     if (a.n == 0) return a.table ? hipSuccess : hipMemsetAsync(a.n_aircraft, 0, sizeof(uint64_t), st);
     const uint32_t n = a.n, blocks = (n + 255) / 256;
     TrackTableDev t{};
     if (a.table) t = *a.table;
+    TrackBankDev b{};
+    if (a.bank) { // a.table: the bank's records and slot scratch
+        b = *a.bank;
+        const uint32_t kblocks = ((n > b.n_receivers ? n : b.n_receivers + 1u) + 255u) / 256u;
+        hipLaunchKernelGGL(track_bank_keys_kernel, dim3(kblocks), dim3(256), 0, st, a.fields, n, b, a.keys, a.vals);
+        size_t tb = a.temp_bytes;
+        hipError_t e = rocprim::radix_sort_pairs(a.temp, tb, (const uint32_t *)a.keys, a.skeys,
+                                                 (const uint32_t *)a.vals, a.svals, (size_t)n, 0, b.key_bits, st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(track_bank_lookup_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, b, t.slot);
+        tb = a.temp_bytes;
+        e = rocprim::exclusive_scan(a.temp, tb, (const unsigned long long *)b.mark, b.excl, 0ull, (size_t)n,
+                                    rocprim::plus<unsigned long long>(), st);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(track_bank_admit_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, b,
+                           (const uint32_t *)t.slot);
+        hipLaunchKernelGGL(track_pairs_kernel<true>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.skeys,
+                           a.svals, n, a.seconds_per_sample, (uint64_t)0, t, b, a.points, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(track_summary_kernel<true>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.points,
+                           a.skeys, a.svals, (const uint32_t *)nullptr, (const uint32_t *)nullptr, n,
+                           a.seconds_per_sample, (uint64_t)0, t, b, (adsb_aircraft_record *)nullptr, 0u,
+                           (uint64_t *)nullptr);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(track_keys_kernel, dim3(blocks), dim3(256), 0, st, a.fields, n, a.keys, a.vals);
     size_t tb = a.temp_bytes;
     hipError_t e = rocprim::radix_sort_pairs(a.temp, tb, (const uint32_t *)a.keys, a.skeys, (const uint32_t *)a.vals,
@@ -345,22 +513,23 @@ hipError_t launch_track(hipStream_t st, const TrackArgs &a)
                                     rocprim::plus<uint32_t>(), st);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(track_admit_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, a.keys, a.vals, t);
-        hipLaunchKernelGGL(track_pairs_kernel, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.skeys, a.svals, n,
-                           a.seconds_per_sample, a.sample_base, t, a.points, (uint32_t *)nullptr);
-        hipLaunchKernelGGL(track_summary_kernel, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.points, a.skeys,
-                           a.svals, (const uint32_t *)nullptr, (const uint32_t *)nullptr, n, a.seconds_per_sample,
-                           a.sample_base, t, (adsb_aircraft_record *)nullptr, 0u, (uint64_t *)nullptr);
+        hipLaunchKernelGGL(track_pairs_kernel<false>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.skeys,
+                           a.svals, n, a.seconds_per_sample, a.sample_base, t, b, a.points, (uint32_t *)nullptr);
+        hipLaunchKernelGGL(track_summary_kernel<false>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.points,
+                           a.skeys, a.svals, (const uint32_t *)nullptr, (const uint32_t *)nullptr, n,
+                           a.seconds_per_sample, a.sample_base, t, b, (adsb_aircraft_record *)nullptr, 0u,
+                           (uint64_t *)nullptr);
         return hipGetLastError();
     }
-    hipLaunchKernelGGL(track_pairs_kernel, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.skeys, a.svals, n,
-                       a.seconds_per_sample, a.sample_base, t, a.points, a.keys /* reused: tail flags */);
+    hipLaunchKernelGGL(track_pairs_kernel<false>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.skeys, a.svals,
+                       n, a.seconds_per_sample, a.sample_base, t, b, a.points, a.keys /* reused: tail flags */);
     tb = a.temp_bytes;
     e = rocprim::exclusive_scan(a.temp, tb, (const uint32_t *)a.keys, a.vals /* reused: tail positions */, 0u, (size_t)n,
                                 rocprim::plus<uint32_t>(), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(track_summary_kernel, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.points, a.skeys,
-                       a.svals, a.keys, a.vals, n, a.seconds_per_sample, a.sample_base, t, a.aircraft, a.max_aircraft,
-                       a.n_aircraft);
+    hipLaunchKernelGGL(track_summary_kernel<false>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.points,
+                       a.skeys, a.svals, a.keys, a.vals, n, a.seconds_per_sample, a.sample_base, t, b, a.aircraft,
+                       a.max_aircraft, a.n_aircraft);
     return hipGetLastError();
 }
 

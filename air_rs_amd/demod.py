@@ -562,6 +562,89 @@ class TrackTable:
         return out[:n.value].copy(), flags.value
 
 
+class TrackBank:
+    """adsb_track_bank_*: n_receivers independent aircraft tables on the device (one HashMap<u32, Aircraft> per
+    receiver's display thread), all updated by one call over a multi-receiver frame list; receiver r equals a
+    TrackTable fed receiver r's part of every update."""
+
+    def __init__(self, dem, n_receivers, max_aircraft=0, max_frames=1 << 16, seconds_per_sample=0.5e-6):
+        self._lib, self._dem = dem._lib, dem
+        cfg = L.AdsbTrackBankCfg(L.ADSB_ABI_VERSION, int(n_receivers), int(max_aircraft), 0, int(max_frames),
+                                 float(seconds_per_sample))
+        h = C.c_void_p()
+        L.check(self._lib.adsb_track_bank_create(dem.handle, C.byref(cfg), C.byref(h)), "adsb_track_bank_create")
+        self._h, self.n_receivers, self.max_frames = h, int(n_receivers), int(max_frames)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.adsb_track_bank_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _u64s(self, values, what):
+        """None / a scalar (the same for every receiver) / a per-receiver sequence -> a uint64[n_receivers] array."""
+        if values is None:
+            return None
+        if np.ndim(values) == 0:
+            values = [int(values)] * self.n_receivers
+        values = [int(v) for v in values]
+        if len(values) != self.n_receivers:
+            raise ValueError(f"{what}: {len(values)} values for {self.n_receivers} receivers")
+        return (C.c_uint64 * self.n_receivers)(*values)
+
+    def reset(self):
+        L.check(self._lib.adsb_track_bank_reset(self._h), "adsb_track_bank_reset")
+
+    def update(self, frames, counts, sample_base=None):
+        """frames: FRAME_DTYPE array (host), receiver 0's frames in ascending offset, then receiver 1's, ...;
+        counts: frames of each receiver; sample_base: scalar or per receiver (frame time = (base + offset) x sps)."""
+        frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+        L.check(self._lib.adsb_track_bank_update(self._h, frames.ctypes.data if len(frames) else None, len(frames),
+                                                 self._u64s(counts, "counts"), self._u64s(sample_base, "sample_base")),
+                "adsb_track_bank_update")
+
+    def update_device(self, dev_ptr, n, counts, sample_base=None):
+        """n frames at dev_ptr in the ctx device's memory, split by counts as for update()."""
+        L.check(self._lib.adsb_track_bank_update(self._h, dev_ptr, int(n), self._u64s(counts, "counts"),
+                                                 self._u64s(sample_base, "sample_base")), "adsb_track_bank_update")
+
+    def update_launch(self, sample_base=None):
+        """The ctx's last launch, channel k -> receiver k: what fetch() returns, read in device memory."""
+        L.check(self._lib.adsb_track_bank_update_launch(self._h, self._u64s(sample_base, "sample_base")),
+                "adsb_track_bank_update_launch")
+
+    def points(self):
+        """One TRACK_POINT_DTYPE record per frame of the last update, in its list order."""
+        out = np.zeros(max(self.max_frames, 1), dtype=TRACK_POINT_DTYPE)
+        n = C.c_size_t()
+        L.check(self._lib.adsb_track_bank_fetch_points(self._h, out.ctypes.data, len(out), C.byref(n)),
+                "adsb_track_bank_fetch_points")
+        return out[:n.value].copy()
+
+    def aircraft(self):
+        """(list of n_receivers AIRCRAFT_DTYPE arrays, each in ascending ICAO; list of per-receiver flags)."""
+        n = C.c_size_t()
+        counts = (C.c_uint64 * self.n_receivers)()
+        flags = (C.c_uint32 * self.n_receivers)()
+        L.check(self._lib.adsb_track_bank_fetch(self._h, None, 0, C.byref(n), None, None), "adsb_track_bank_fetch")
+        out = np.zeros(max(n.value, 1), dtype=AIRCRAFT_DTYPE)
+        L.check(self._lib.adsb_track_bank_fetch(self._h, out.ctypes.data, len(out), C.byref(n), counts, flags),
+                "adsb_track_bank_fetch")
+        edges = np.concatenate([[0], np.cumsum(list(counts))]).astype(np.int64)
+        return [out[edges[r]:edges[r + 1]].copy() for r in range(self.n_receivers)], list(flags)
+
+
 def packet_new(frame_bytes):
     """AdsbPacket::new (packet.rs:25-49) -> AdsbPacketView."""
     b = (C.c_uint8 * 14)(*bytes(frame_bytes))

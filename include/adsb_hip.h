@@ -45,8 +45,8 @@ extern "C" {
 /* Only ever seen by device-side consumers (adsb_result_device's header, adsb_set_result_target's blob):
  * the launch ran out of temporary frame slots (far more gate survivors than max_out + one tile: constant or
  * all-zero input), so the list holds n_out entries of which some are not written yet.  The host
- * entry points that wait for a launch (adsb_fetch, adsb_fetch_counts, adsb_fetch_fields, adsb_track_device)
- * re-run the affected tiles, complete the list IN PLACE (blob included) and clear the flag; a consumer
+ * entry points that wait for a launch (adsb_fetch, adsb_fetch_counts, adsb_fetch_fields, adsb_track_device,
+ * adsb_track_bank_update_launch) re-run the affected tiles, complete the list IN PLACE (blob included) and clear the flag; a consumer
  * that reads the device copy directly must check it and call adsb_fetch_counts() first when it is set. */
 #define ADSB_FLAG_INCOMPLETE 0x2u
 
@@ -302,6 +302,56 @@ int adsb_track_table_fetch_points(adsb_track_table *table, adsb_track_point *poi
  * if it exceeds max_aircraft; *flags (optional) = ADSB_TRACK_TABLE_FULL or 0. */
 int adsb_track_table_fetch(adsb_track_table *table, adsb_aircraft_record *aircraft, size_t max_aircraft,
                            size_t *n_aircraft, uint32_t *flags);
+
+/*
+ * A bank of persistent tables, one per receiver: what N display threads hold, one HashMap<u32, Aircraft> each
+ * (src/adsb/tui.rs:22-42, web.rs:115), for a ctx that batches N receivers into one multi-channel launch.  Receiver r
+ * behaves exactly like an adsb_track_table of its own with the bank's max_aircraft and seconds_per_sample, fed
+ * receiver r's part of every update with sample_base[r]: its points and records are bit-identical to that table's,
+ * also when the same ICAO is active on several receivers at once.  One update applies every receiver's part with one
+ * dispatch sequence (the table's: field decode, sort by receiver << 24 | icao, lookup, admission, pairs, merge).
+ * New ICAO addresses are admitted per receiver in ascending order while that receiver has room; a full receiver sets
+ * ADSB_TRACK_TABLE_FULL for itself and marks its turned-away frames ADSB_TRACK_UNTRACKED.  Device memory: 88 bytes
+ * per record of n_receivers x max_aircraft, 8 bytes per entry of a hash of (receiver, ICAO) with the next power of two
+ * >= 2 x n_receivers x max_aircraft entries, about 120 bytes per frame of max_frames (64 receivers x 65536 aircraft:
+ * 369 MiB of records + 64 MiB of hash).  The ctx must outlive the bank; a bank is not thread-safe.
+ */
+typedef struct adsb_track_bank adsb_track_bank;
+typedef struct adsb_track_bank_cfg {
+    uint32_t abi_version;        /* ADSB_ABI_VERSION                                                           */
+    uint32_t n_receivers;        /* 1 .. 256                                                                   */
+    uint32_t max_aircraft;       /* PER RECEIVER, kept until reset; 0: 65536; at most 2^24                     */
+    uint32_t reserved;           /* 0                                                                          */
+    uint64_t max_frames;         /* longest list one update accepts, all receivers together (1 .. 2^32 - 1)   */
+    double   seconds_per_sample; /* frame time of receiver r = (sample_base[r] + offset) x this                */
+} adsb_track_bank_cfg;
+int adsb_track_bank_create(adsb_ctx *ctx, const adsb_track_bank_cfg *cfg, adsb_track_bank **out_bank);
+void adsb_track_bank_destroy(adsb_track_bank *bank);
+/* Empties every receiver and clears the flags (ordered after the bank's last update). */
+int adsb_track_bank_reset(adsb_track_bank *bank);
+/*
+ * Applies one multi-receiver list: receiver 0's frames in ascending offset, then receiver 1's, ... (adsb_fetch's
+ * layout).  counts[n_receivers] (host) must sum to n (NULL only with n = 0); sample_base[n_receivers] (host, NULL: all
+ * 0) times receiver r's frames.  `frames` in host memory (copied when this returns) or on the ctx's device; kernels
+ * run asynchronously on the ctx stream.  ADSB_E_CAPACITY for n > max_frames.
+ */
+int adsb_track_bank_update(adsb_track_bank *bank, const adsb_frame *frames, size_t n, const uint64_t *counts,
+                           const uint64_t *sample_base);
+/*
+ * Applies the ctx's last launch, channel k -> receiver k (receivers at or above its channel count get no frames):
+ * exactly the frames and per-channel split adsb_fetch / per_channel_counts would return for max_out = the ctx's
+ * (same header sync and slot-pool repair as adsb_fetch_counts), read in device memory.  sample_base as for update.
+ * ADSB_E_ARG if the launch had more channels than the bank has receivers; ADSB_E_STATE before any launch.
+ */
+int adsb_track_bank_update_launch(adsb_track_bank *bank, const uint64_t *sample_base);
+/* Waits; one point per frame of the LAST update, in its list order (ADSB_E_STATE before any update). */
+int adsb_track_bank_fetch_points(adsb_track_bank *bank, adsb_track_point *points, size_t max_points,
+                                 size_t *n_points);
+/* Waits; every receiver's records, receiver 0 first, each in ascending ICAO, up to max_aircraft in all;
+ * per_receiver_counts[n_receivers] (optional) = records of each receiver in `aircraft`; *n_aircraft = records held
+ * in total even if more than max_aircraft; flags[n_receivers] (optional) = ADSB_TRACK_TABLE_FULL or 0 each. */
+int adsb_track_bank_fetch(adsb_track_bank *bank, adsb_aircraft_record *aircraft, size_t max_aircraft,
+                          size_t *n_aircraft, uint64_t *per_receiver_counts, uint32_t *flags);
 
 /*
  * ---- several GPUs behind one call ---------------------------------------------------------
