@@ -132,6 +132,8 @@ PROTOTYPES = {
     "adsb_track_table_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]),
     "adsb_track_table_fetch_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_table_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), _P(C.c_uint32)]),
+    "adsb_track_table_expire": (C.c_int, [C.c_void_p, C.c_double]),
+    "adsb_track_table_fetch_last_heard": (C.c_int, [C.c_void_p, _P(C.c_double), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_bank_create": (C.c_int, [C.c_void_p, _P(AdsbTrackBankCfg), _P(C.c_void_p)]),
     "adsb_track_bank_destroy": (None, [C.c_void_p]),
     "adsb_track_bank_reset": (C.c_int, [C.c_void_p]),
@@ -140,6 +142,8 @@ PROTOTYPES = {
     "adsb_track_bank_fetch_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_bank_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), _P(C.c_uint64),
                                         _P(C.c_uint32)]),
+    "adsb_track_bank_expire": (C.c_int, [C.c_void_p, _P(C.c_double)]),
+    "adsb_track_bank_fetch_last_heard": (C.c_int, [C.c_void_p, _P(C.c_double), C.c_size_t, _P(C.c_size_t)]),
     "adsb_cpr_num_zones": (C.c_uint32, [C.c_double]),
     "adsb_cpr_position": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P(C.c_double),
                                     _P(C.c_double)]),

@@ -9,6 +9,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -873,9 +874,19 @@ struct adsb_track_table {
     hipEvent_t copied = nullptr;    // the last copy out of `pinned` has finished
     adsb_packet_fields *fields = nullptr; // [max_frames]
     adsb_track_point *points = nullptr;   // [max_frames], the last update's, frame order
+    uint32_t *exp_u32 = nullptr;    // 2 x [max_aircraft]: expire's keep flags and their scan
+    void *exp_temp = nullptr;       // expire's scan
+    size_t exp_temp_bytes = 0;
     uint32_t n_points = 0;
     bool updated = false;
 };
+
+// Records of a table or of one bank receiver (slots in admission order) as fetch returns them: ascending ICAO.
+static void sort_by_icao(std::vector<adsbk::TrackRecord> &recs)
+{
+    std::sort(recs.begin(), recs.end(),
+              [](const adsbk::TrackRecord &x, const adsbk::TrackRecord &y) { return x.a.icao < y.a.icao; });
+}
 
 static void track_table_free(adsb_track_table *t)
 {
@@ -892,6 +903,8 @@ static void track_table_free(adsb_track_table *t)
     if (t->copied) (void)hipEventDestroy(t->copied);
     if (t->fields) (void)hipFree(t->fields);
     if (t->points) (void)hipFree(t->points);
+    if (t->exp_u32) (void)hipFree(t->exp_u32);
+    if (t->exp_temp) (void)hipFree(t->exp_temp);
     delete t;
 }
 
@@ -922,6 +935,7 @@ extern "C" int adsb_track_table_create(adsb_ctx *c, const adsb_track_table_cfg *
     const size_t nf = (size_t)t->cfg.max_frames;
     t->dev.max_aircraft = t->cfg.max_aircraft;
     t->temp_bytes = adsbk::track_sort_temp_bytes(nf);
+    t->exp_temp_bytes = adsbk::track_expire_temp_bytes(t->cfg.max_aircraft);
     const bool ok = hipMalloc((void **)&t->dev.index, sizeof(uint32_t) << 24) == hipSuccess &&
                     hipMalloc((void **)&t->dev.rec, sizeof(adsbk::TrackRecord) * t->cfg.max_aircraft) == hipSuccess &&
                     hipMalloc((void **)&t->dev.size_flags, sizeof(uint32_t) * 4) == hipSuccess &&
@@ -932,7 +946,9 @@ extern "C" int adsb_track_table_create(adsb_ctx *c, const adsb_track_table_cfg *
                     hipHostMalloc((void **)&t->pinned, sizeof(adsb_frame) * nf, hipHostMallocDefault) == hipSuccess &&
                     hipEventCreateWithFlags(&t->copied, hipEventDisableTiming) == hipSuccess &&
                     hipMalloc((void **)&t->fields, sizeof(adsb_packet_fields) * nf) == hipSuccess &&
-                    hipMalloc((void **)&t->points, sizeof(adsb_track_point) * nf) == hipSuccess;
+                    hipMalloc((void **)&t->points, sizeof(adsb_track_point) * nf) == hipSuccess &&
+                    hipMalloc((void **)&t->exp_u32, sizeof(uint32_t) * 2 * t->cfg.max_aircraft) == hipSuccess &&
+                    hipMalloc(&t->exp_temp, t->exp_temp_bytes) == hipSuccess;
     int rc = ok ? adsb_track_table_reset(t) : ADSB_E_NOMEM;
     if (rc == ADSB_OK && hipStreamSynchronize(c->aux) != hipSuccess) rc = ADSB_E_NOMEM;
     if (rc != ADSB_OK) {
@@ -1017,12 +1033,46 @@ extern "C" int adsb_track_table_fetch(adsb_track_table *t, adsb_aircraft_record 
         HIPCHK(hipMemcpyAsync(recs.data(), t->dev.rec, sizeof(adsbk::TrackRecord) * size, hipMemcpyDeviceToHost,
                               t->ctx->aux));
         HIPCHK(hipStreamSynchronize(t->ctx->aux));
-        std::sort(recs.begin(), recs.end(),
-                  [](const adsbk::TrackRecord &x, const adsbk::TrackRecord &y) { return x.a.icao < y.a.icao; });
+        sort_by_icao(recs);
         for (size_t k = 0; k < std::min(size, max_aircraft); ++k) aircraft[k] = recs[k].a;
     }
     if (n_aircraft) *n_aircraft = size;
     if (flags) *flags = sf[1];
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_table_expire(adsb_track_table *t, double before)
+{
+    if (!t || std::isnan(before)) return ADSB_E_ARG;
+    HIPCHK(hipSetDevice(t->ctx->cfg.device));
+    adsbk::ExpireArgs a{};
+    a.table = &t->dev;
+    a.cut.before[0] = before;
+    a.keep = t->exp_u32;
+    a.rank = t->exp_u32 + t->cfg.max_aircraft;
+    a.temp = t->exp_temp;
+    a.temp_bytes = t->exp_temp_bytes;
+    HIPCHK(adsbk::launch_track_expire(t->ctx->aux, a)); // after the table's last update (same stream)
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_table_fetch_last_heard(adsb_track_table *t, double *last_heard, size_t max, size_t *n)
+{
+    if (!t || (!last_heard && max)) return ADSB_E_ARG;
+    HIPCHK(hipSetDevice(t->ctx->cfg.device));
+    uint32_t sf[4] = {0, 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(sf, t->dev.size_flags, sizeof(sf), hipMemcpyDeviceToHost, t->ctx->aux));
+    HIPCHK(hipStreamSynchronize(t->ctx->aux));
+    const size_t size = std::min<size_t>(sf[0], t->cfg.max_aircraft);
+    if (max && size) { // the order of adsb_track_table_fetch
+        std::vector<adsbk::TrackRecord> recs(size);
+        HIPCHK(hipMemcpyAsync(recs.data(), t->dev.rec, sizeof(adsbk::TrackRecord) * size, hipMemcpyDeviceToHost,
+                              t->ctx->aux));
+        HIPCHK(hipStreamSynchronize(t->ctx->aux));
+        sort_by_icao(recs);
+        for (size_t k = 0; k < std::min(size, max); ++k) last_heard[k] = recs[k].last_heard;
+    }
+    if (n) *n = size;
     return ADSB_OK;
 }
 
@@ -1043,6 +1093,9 @@ struct adsb_track_bank {
     hipEvent_t copied = nullptr;    // the last copies out of `pinned` and `meta_pinned` have finished
     adsb_packet_fields *fields = nullptr; // [max_frames]
     adsb_track_point *points = nullptr;   // [max_frames], the last update's, list order
+    uint32_t *exp_u32 = nullptr;    // 2 x [R x max_aircraft]: expire's keep flags and their scan
+    void *exp_temp = nullptr;       // expire's scan
+    size_t exp_temp_bytes = 0;
     uint32_t n_points = 0;
     bool updated = false;
 };
@@ -1053,7 +1106,8 @@ static void track_bank_free(adsb_track_bank *b)
     (void)hipStreamSynchronize(b->ctx->aux);
     for (void *p : {(void *)b->dev.hash, (void *)b->dev.rec, (void *)b->words, (void *)b->dev.prefix, (void *)b->meta,
                     (void *)b->dev.mark, (void *)b->dev.excl, (void *)b->dev.seg_slot, (void *)b->tab.slot,
-                    (void *)b->u32, b->temp, (void *)b->frames, (void *)b->fields, (void *)b->points})
+                    (void *)b->u32, b->temp, (void *)b->frames, (void *)b->fields, (void *)b->points,
+                    (void *)b->exp_u32, b->exp_temp})
         if (p) (void)hipFree(p);
     if (b->pinned) (void)hipHostFree(b->pinned);
     if (b->meta_pinned) (void)hipHostFree(b->meta_pinned);
@@ -1075,7 +1129,7 @@ extern "C" int adsb_track_bank_reset(adsb_track_bank *b)
 extern "C" int adsb_track_bank_create(adsb_ctx *c, const adsb_track_bank_cfg *cfg, adsb_track_bank **out)
 {
     if (!c || !cfg || !out || cfg->abi_version != ADSB_ABI_VERSION || cfg->reserved != 0) return ADSB_E_ARG;
-    if (cfg->n_receivers == 0 || cfg->n_receivers > 256 || cfg->max_frames == 0 || cfg->max_frames > 0xFFFFFFFFull ||
+    if (cfg->n_receivers == 0 || cfg->n_receivers > adsbk::kMaxReceivers || cfg->max_frames == 0 || cfg->max_frames > 0xFFFFFFFFull ||
         !(cfg->seconds_per_sample > 0.0) || cfg->max_aircraft > (1u << 24))
         return ADSB_E_ARG;
     *out = nullptr;
@@ -1098,6 +1152,7 @@ extern "C" int adsb_track_bank_create(adsb_ctx *c, const adsb_track_bank_cfg *cf
     while ((1u << bits) < nr) ++bits;
     b->dev.key_bits = 24 + bits;
     b->temp_bytes = adsbk::track_bank_temp_bytes(nf);
+    b->exp_temp_bytes = adsbk::track_expire_temp_bytes(n_rec);
     bool ok = hipMalloc((void **)&b->dev.hash, sizeof(unsigned long long) * cap) == hipSuccess &&
               hipMalloc((void **)&b->dev.rec, sizeof(adsbk::TrackRecord) * n_rec) == hipSuccess &&
               hipMalloc((void **)&b->words, sizeof(uint32_t) * 3 * nr) == hipSuccess &&
@@ -1114,7 +1169,9 @@ extern "C" int adsb_track_bank_create(adsb_ctx *c, const adsb_track_bank_cfg *cf
               hipHostMalloc((void **)&b->pinned, sizeof(adsb_frame) * nf, hipHostMallocDefault) == hipSuccess &&
               hipEventCreateWithFlags(&b->copied, hipEventDisableTiming) == hipSuccess &&
               hipMalloc((void **)&b->fields, sizeof(adsb_packet_fields) * nf) == hipSuccess &&
-              hipMalloc((void **)&b->points, sizeof(adsb_track_point) * nf) == hipSuccess;
+              hipMalloc((void **)&b->points, sizeof(adsb_track_point) * nf) == hipSuccess &&
+              hipMalloc((void **)&b->exp_u32, sizeof(uint32_t) * 2 * n_rec) == hipSuccess &&
+              hipMalloc(&b->exp_temp, b->exp_temp_bytes) == hipSuccess;
     if (ok) {
         b->dev.size = b->words;
         b->dev.flags = b->words + nr;
@@ -1276,8 +1333,7 @@ extern "C" int adsb_track_bank_fetch(adsb_track_bank *b, adsb_aircraft_record *a
             HIPCHK(hipMemcpyAsync(recs.data(), b->dev.rec + (size_t)r * max_ac, sizeof(adsbk::TrackRecord) * size,
                                   hipMemcpyDeviceToHost, c->aux));
             HIPCHK(hipStreamSynchronize(c->aux));
-            std::sort(recs.begin(), recs.end(),
-                      [](const adsbk::TrackRecord &x, const adsbk::TrackRecord &y) { return x.a.icao < y.a.icao; });
+            sort_by_icao(recs);
             for (size_t k = 0; k < take; ++k) aircraft[copied + k] = recs[k].a;
         }
         copied += take;
@@ -1285,6 +1341,55 @@ extern "C" int adsb_track_bank_fetch(adsb_track_bank *b, adsb_aircraft_record *a
         if (flags) flags[r] = w[nr + r];
     }
     if (n_aircraft) *n_aircraft = total;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_expire(adsb_track_bank *b, const double *before)
+{
+    if (!b || !before) return ADSB_E_ARG;
+    adsbk::ExpireArgs a{};
+    for (uint32_t r = 0; r < b->cfg.n_receivers; ++r) { // n_receivers <= kMaxReceivers (create checks)
+        if (std::isnan(before[r])) return ADSB_E_ARG;
+        a.cut.before[r] = before[r];                     // by value in the kernel's arguments: no staging, no wait
+    }
+    HIPCHK(hipSetDevice(b->ctx->cfg.device));
+    const size_t n_rec = (size_t)b->cfg.n_receivers * b->cfg.max_aircraft;
+    a.table = &b->tab;
+    a.bank = &b->dev;
+    a.keep = b->exp_u32;
+    a.rank = b->exp_u32 + n_rec;
+    a.temp = b->exp_temp;
+    a.temp_bytes = b->exp_temp_bytes;
+    HIPCHK(adsbk::launch_track_expire(b->ctx->aux, a)); // after the bank's last update (same stream)
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_fetch_last_heard(adsb_track_bank *b, double *last_heard, size_t max, size_t *n)
+{
+    if (!b || (!last_heard && max)) return ADSB_E_ARG;
+    adsb_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const uint32_t nr = b->cfg.n_receivers, max_ac = b->cfg.max_aircraft;
+    std::vector<uint32_t> w(nr);
+    HIPCHK(hipMemcpyAsync(w.data(), b->dev.size, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    size_t total = 0, copied = 0;
+    std::vector<adsbk::TrackRecord> recs;
+    for (uint32_t r = 0; r < nr; ++r) { // the order of adsb_track_bank_fetch
+        const size_t size = std::min<uint32_t>(w[r], max_ac);
+        total += size;
+        const size_t take = std::min(size, max - copied);
+        if (take) {
+            recs.resize(size);
+            HIPCHK(hipMemcpyAsync(recs.data(), b->dev.rec + (size_t)r * max_ac, sizeof(adsbk::TrackRecord) * size,
+                                  hipMemcpyDeviceToHost, c->aux));
+            HIPCHK(hipStreamSynchronize(c->aux));
+            sort_by_icao(recs);
+            for (size_t k = 0; k < take; ++k) last_heard[copied + k] = recs[k].last_heard;
+        }
+        copied += take;
+    }
+    if (n) *n = total;
     return ADSB_OK;
 }
 

@@ -172,12 +172,15 @@ struct TrackRecord {
     uint32_t even_lat, even_lon, odd_lat, odd_lon;
     uint32_t have;               // bit 0: an even position message was seen, bit 1: an odd one
     uint32_t pad;
+    double last_heard;           // time of the last frame of any kind (adsb_track_*_expire evicts on it)
 };
+static_assert(sizeof(TrackRecord) == 96, "TrackRecord: the header's memory figures assume 96 bytes");
 constexpr uint32_t kTrackUntracked = 0xFFFFFFFFu; // slot of an aircraft the full table turned away
 struct TrackTableDev {
     uint32_t *index;             // [1 << 24]: ICAO -> record slot + 1, 0 = absent
     TrackRecord *rec;            // [max_aircraft]
-    uint32_t *size_flags;        // device words: [0] records in use, [1] ADSB_TRACK_TABLE_FULL
+    uint32_t *size_flags;        // device words: [0] records in use, [1] ADSB_TRACK_TABLE_FULL, [2] / [3] staging of
+                                 // [0] for the update's admission / for expire
     uint32_t max_aircraft;
     uint32_t *slot;              // [n] scratch: record slot + 1 of each sorted frame's aircraft (kTrackUntracked)
 };
@@ -189,7 +192,8 @@ struct TrackBankDev {
     TrackRecord *rec;            // [n_receivers x max_aircraft]: receiver r's records at [r x max_aircraft, ...)
     uint32_t *size;              // [n_receivers] records in use
     uint32_t *flags;             // [n_receivers] ADSB_TRACK_TABLE_FULL
-    uint32_t *size_next;         // [n_receivers] staging: the admission kernel's new sizes, moved to size by the pairs kernel
+    uint32_t *size_next;         // [n_receivers] staging: the admission kernel's new sizes, moved to size by the pairs
+                                 // kernel; expire stages the old sizes here
     uint32_t max_aircraft;       // per receiver
     uint32_t n_receivers;
     uint32_t *prefix;            // [n_receivers + 1]: frames of the list before each receiver's first (last = n); also
@@ -220,6 +224,21 @@ struct TrackArgs {
     const TrackBankDev *bank;    // non-null: the list holds several receivers' frames (adsb_track_bank_update); `table`
                                  // then carries the bank's records in rec and the per-frame slot scratch in slot
 };
+// expire (adsb_track_table_expire / adsb_track_bank_expire): a record survives unless last_heard < before[receiver]
+constexpr uint32_t kMaxReceivers = 256;
+struct ExpireCut {
+    double before[kMaxReceivers]; // [0] for a table
+};
+struct ExpireArgs {
+    const TrackTableDev *table;  // the table, or for a bank its records (rec) and max_aircraft
+    const TrackBankDev *bank;    // nullptr: a table
+    ExpireCut cut;
+    uint32_t *keep, *rank;       // [n_rec] each, n_rec = max_aircraft (x n_receivers)
+    void *temp;
+    size_t temp_bytes;
+};
+size_t track_expire_temp_bytes(size_t n_rec);
+hipError_t launch_track_expire(hipStream_t s, const ExpireArgs &a);
 size_t track_sort_temp_bytes(size_t n);
 size_t track_bank_temp_bytes(size_t n); // the bank's sort (32 bits) and 64-bit scan
 hipError_t launch_track(hipStream_t s, const TrackArgs &a);

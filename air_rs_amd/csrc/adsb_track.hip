@@ -35,6 +35,14 @@
 // frame its segment and every new key its rank, made per receiver by subtracting the rank at prefix[r].  Slots come
 // from that rank alone (receiver r's records live at [r x max_aircraft, (r+1) x max_aircraft)), never from where the
 // hash put an entry, so no result depends on insert order.
+//
+// Expire (adsb_track_table_expire / adsb_track_bank_expire) evicts every record whose last frame of any kind is older
+// than a cut, without a host round trip: a mark kernel flags the survivors of [0, size) (sized by max_aircraft, the
+// size being a device word), a rocPRIM scan ranks them, and a compaction kernel closes the holes in place: the k-th
+// survivor at or above the new size moves into the k-th hole below it, so sources and destinations are disjoint.  The
+// table's direct index is fixed by the same kernel (evicted ICAOs cleared, moved ones rewritten); a bank's hash cannot
+// drop entries (a hole in a probe chain would hide later keys), so it is cleared and every survivor reinserted.  A bank
+// does this per receiver region with one scan over all receivers, each region's rank made local as admission does.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -128,6 +136,7 @@ __device__ __forceinline__ TrackRecord empty_record(uint32_t icao)
     rec.even_lat = rec.even_lon = rec.odd_lat = rec.odd_lon = 0;
     rec.have = 0;
     rec.pad = 0;
+    rec.last_heard = 0.0; // the merge of the admitting list sets it
     return rec;
 }
 
@@ -441,13 +450,127 @@ __global__ __launch_bounds__(256) void track_summary_kernel(const adsb_frame *fr
         }
     }
     r.a.n_frames += count;
-    if (table)
+    if (table) {
+        r.last_heard = frame_time(frames, svals[s], sample_base, seconds_per_sample); // the segment's last frame
         t.rec[a] = r;
-    else
+    } else {
         out[a] = r.a;
+    }
+}
+
+// expire, 1: keep[g] = 1 for a record in use whose last frame is not older than the cut (last_heard < before evicts).
+// Record g is slot i of receiver r (a table: r = 0).  Slot 0 stages the old size where the compaction kernel reads it
+// (size_flags[3] / size_next[r]), since that kernel writes the new one.
+template <bool kBank>
+__global__ __launch_bounds__(256) void track_expire_mark_kernel(TrackTableDev t, TrackBankDev b, ExpireCut cut,
+                                                                uint32_t *keep, uint64_t n_rec)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_rec) return;
+    const uint32_t r = kBank ? (uint32_t)(g / t.max_aircraft) : 0u;
+    const uint32_t i = (uint32_t)(g - (uint64_t)r * t.max_aircraft);
+    const uint32_t size = kBank ? b.size[r] : t.size_flags[0];
+    if (i == 0) {
+        if (kBank)
+            b.size_next[r] = size;
+        else
+            t.size_flags[3] = size;
+    }
+    keep[g] = (i < size && !(t.rec[g].last_heard < cut.before[r])) ? 1u : 0u;
+}
+
+// expire, 2 (after the exclusive scan rank of keep): the new size S = survivors; an evicted record below S is a hole
+// that takes the k-th survivor at or above S (k = holes before it), found by a binary search over the local ranks.
+// Holes are below S and the survivors they take at or above it, so no thread reads a record another one writes.  A
+// table fixes its index here: the entries of evicted ICAOs are cleared, the moved ones point at their new slot.
+template <bool kBank>
+__global__ __launch_bounds__(256) void track_expire_compact_kernel(TrackTableDev t, TrackBankDev b,
+                                                                   const uint32_t *keep, const uint32_t *rank,
+                                                                   uint64_t n_rec)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_rec) return;
+    const uint32_t r = kBank ? (uint32_t)(g / t.max_aircraft) : 0u;
+    const uint64_t base = (uint64_t)r * t.max_aircraft;
+    const uint32_t i = (uint32_t)(g - base);
+    const uint32_t size = kBank ? b.size_next[r] : t.size_flags[3];
+    const uint32_t rank0 = rank[base];
+    const uint32_t survivors = size ? rank[base + size - 1] + keep[base + size - 1] - rank0 : 0u;
+    if (i == 0) {
+        if (kBank)
+            b.size[r] = survivors;
+        else
+            t.size_flags[0] = survivors;
+    }
+    if (i >= size || keep[g]) return;
+    if (!kBank) t.index[t.rec[g].a.icao] = 0;
+    if (i >= survivors) return;
+    // a hole below `survivors` (so at least one survivor sits in [survivors, size)): k-th hole <- k-th such survivor,
+    // the one whose local rank is m; it is the last slot in [survivors, size) with local rank <= m
+    const uint32_t m = rank[base + survivors] - rank0 + (i - (rank[g] - rank0));
+    uint32_t lo = survivors, hi = size; // local rank(lo) <= m; hi = size or local rank(hi) > m
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (rank[base + mid] - rank0 > m)
+            hi = mid;
+        else
+            lo = mid;
+    }
+    const TrackRecord moved = t.rec[base + lo];
+    t.rec[g] = moved;
+    if (!kBank) t.index[moved.a.icao] = i + 1u;
+}
+
+// expire, 3 (bank only, after the hash was cleared): every surviving record reinserts (slot + 1) << 32 | key
+__global__ __launch_bounds__(256) void track_bank_rehash_kernel(TrackTableDev t, TrackBankDev b, uint64_t n_rec)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_rec) return;
+    const uint32_t r = (uint32_t)(g / t.max_aircraft);
+    if ((uint32_t)(g - (uint64_t)r * t.max_aircraft) >= b.size[r]) return;
+    const uint32_t key = r << 24 | (t.rec[g].a.icao & 0xFFFFFFu);
+    const unsigned long long entry = (unsigned long long)(g + 1u) << 32 | key;
+    for (uint64_t h = bank_hash(key) & b.hash_mask;; h = (h + 1) & b.hash_mask) // load <= 1/2: an empty entry exists
+        if (atomicCAS(&b.hash[h], 0ull, entry) == 0ull) break;
 }
 
 } // namespace
+
+size_t track_expire_temp_bytes(size_t n_rec)
+{
+    size_t scan_bytes = 0;
+    (void)rocprim::exclusive_scan(nullptr, scan_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, n_rec,
+                                  rocprim::plus<uint32_t>(), (hipStream_t)0);
+    return scan_bytes + 256;
+}
+
+hipError_t launch_track_expire(hipStream_t st, const ExpireArgs &a)
+{
+    const TrackTableDev t = *a.table;
+    TrackBankDev b{};
+    if (a.bank) b = *a.bank;
+    const uint64_t n_rec = (uint64_t)t.max_aircraft * (a.bank ? b.n_receivers : 1u);
+    if (n_rec == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)((n_rec + 255) / 256);
+    if (a.bank)
+        hipLaunchKernelGGL(track_expire_mark_kernel<true>, dim3(blocks), dim3(256), 0, st, t, b, a.cut, a.keep, n_rec);
+    else
+        hipLaunchKernelGGL(track_expire_mark_kernel<false>, dim3(blocks), dim3(256), 0, st, t, b, a.cut, a.keep, n_rec);
+    size_t tb = a.temp_bytes;
+    hipError_t e = rocprim::exclusive_scan(a.temp, tb, (const uint32_t *)a.keep, a.rank, 0u, (size_t)n_rec,
+                                           rocprim::plus<uint32_t>(), st);
+    if (e != hipSuccess) return e;
+    if (!a.bank) {
+        hipLaunchKernelGGL(track_expire_compact_kernel<false>, dim3(blocks), dim3(256), 0, st, t, b,
+                           (const uint32_t *)a.keep, (const uint32_t *)a.rank, n_rec);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(track_expire_compact_kernel<true>, dim3(blocks), dim3(256), 0, st, t, b,
+                       (const uint32_t *)a.keep, (const uint32_t *)a.rank, n_rec);
+    if ((e = hipMemsetAsync(b.hash, 0, sizeof(unsigned long long) * (b.hash_mask + 1), st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(track_bank_rehash_kernel, dim3(blocks), dim3(256), 0, st, t, b, n_rec);
+    return hipGetLastError();
+}
 
 size_t track_sort_temp_bytes(size_t n)
 {

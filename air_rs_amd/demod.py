@@ -561,6 +561,20 @@ class TrackTable:
                 "adsb_track_table_fetch")
         return out[:n.value].copy(), flags.value
 
+    def expire(self, before):
+        """Evicts every aircraft whose last frame of any kind is older than `before` seconds (asynchronous)."""
+        L.check(self._lib.adsb_track_table_expire(self._h, float(before)), "adsb_track_table_expire")
+
+    def last_heard(self):
+        """float64 last-heard times (seconds), aligned with aircraft()[0]."""
+        n = C.c_size_t()
+        L.check(self._lib.adsb_track_table_fetch_last_heard(self._h, None, 0, C.byref(n)),
+                "adsb_track_table_fetch_last_heard")
+        out = np.zeros(max(n.value, 1), dtype=np.float64)
+        L.check(self._lib.adsb_track_table_fetch_last_heard(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), len(out),
+                                                            C.byref(n)), "adsb_track_table_fetch_last_heard")
+        return out[:n.value].copy()
+
 
 class TrackBank:
     """adsb_track_bank_*: n_receivers independent aircraft tables on the device (one HashMap<u32, Aircraft> per
@@ -643,6 +657,27 @@ class TrackBank:
                 "adsb_track_bank_fetch")
         edges = np.concatenate([[0], np.cumsum(list(counts))]).astype(np.int64)
         return [out[edges[r]:edges[r + 1]].copy() for r in range(self.n_receivers)], list(flags)
+
+    def expire(self, before):
+        """Evicts, on every receiver r, the aircraft whose last frame is older than before[r] seconds; `before` is a
+        scalar (the same for every receiver) or a per-receiver sequence (-inf: keep all).  Asynchronous."""
+        if np.ndim(before) == 0:
+            before = [float(before)] * self.n_receivers
+        before = [float(v) for v in before]
+        if len(before) != self.n_receivers:
+            raise ValueError(f"before: {len(before)} values for {self.n_receivers} receivers")
+        L.check(self._lib.adsb_track_bank_expire(self._h, (C.c_double * self.n_receivers)(*before)),
+                "adsb_track_bank_expire")
+
+    def last_heard(self):
+        """list of n_receivers float64 arrays of last-heard times (seconds), aligned with aircraft()[0]."""
+        recs, _ = self.aircraft()                         # the per-receiver split of the same records
+        n = C.c_size_t()
+        out = np.zeros(max(sum(len(x) for x in recs), 1), dtype=np.float64)
+        L.check(self._lib.adsb_track_bank_fetch_last_heard(self._h, out.ctypes.data_as(C.POINTER(C.c_double)),
+                                                           len(out), C.byref(n)), "adsb_track_bank_fetch_last_heard")
+        edges = np.concatenate([[0], np.cumsum([len(x) for x in recs])]).astype(np.int64)
+        return [out[edges[r]:edges[r + 1]].copy() for r in range(self.n_receivers)]
 
 
 def packet_new(frame_bytes):

@@ -270,9 +270,10 @@ int adsb_fetch_track(adsb_ctx *ctx, adsb_track_point *points, size_t max_points,
  * on an empty table gives what adsb_track_device gives on the same list.  Packet time = (sample_base + frame
  * offset) x seconds_per_sample: with a feed in per-buffer mode (carry = 0) sample_base is adsb_feed_pop's
  * *first_sample; with carry = 1 (absolute offsets) it is 0.  One table per receiver (an update takes one ordered
- * list).  Aircraft are never evicted (nor are they in the reference); the table costs 64 MiB of device memory for
- * its ICAO index plus 88 bytes per aircraft and about 100 bytes per frame of max_frames.  The ctx must outlive
- * the table; like the ctx, a table is not thread-safe.
+ * list).  Aircraft stay until adsb_track_table_expire evicts them (the reference's map is unbounded and never does;
+ * this one has max_aircraft places) or until reset.  The table costs 64 MiB of device memory for its ICAO index plus
+ * 104 bytes per aircraft of max_aircraft (a 96-byte record and 8 bytes of expire scratch) and about 100 bytes per
+ * frame of max_frames.  The ctx must outlive the table; like the ctx, a table is not thread-safe.
  */
 #define ADSB_TRACK_UNTRACKED 0x2u  /* point flag: this frame's aircraft was not admitted (table full); only icao valid */
 #define ADSB_TRACK_TABLE_FULL 0x1u /* table flag: some aircraft was turned away since create / reset                  */
@@ -302,6 +303,23 @@ int adsb_track_table_fetch_points(adsb_track_table *table, adsb_track_point *poi
  * if it exceeds max_aircraft; *flags (optional) = ADSB_TRACK_TABLE_FULL or 0. */
 int adsb_track_table_fetch(adsb_track_table *table, adsb_aircraft_record *aircraft, size_t max_aircraft,
                            size_t *n_aircraft, uint32_t *flags);
+/*
+ * Expiry.  An aircraft's LAST HEARD time is (sample_base + offset) x seconds_per_sample of the last frame of ANY kind
+ * that an update applied to it (UNTRACKED frames do not count); unlike last_contact (position messages only, NaN
+ * without one) every admitted aircraft has one.
+ * adsb_track_table_expire evicts every aircraft with last_heard < before (strictly older).  An evicted aircraft is
+ * gone as if it had never been admitted: heard again, it is admitted as a new aircraft (ascending-ICAO rule) with no
+ * CPR halves, callsign or altitude, n_frames = 0 and last_contact NaN, so a frame no longer pairs with a CPR half
+ * held from before the eviction.  The freed places are room again: afterwards the table size is the survivors.
+ * Asynchronous: it runs on the ctx stream after the table's last update, the next update sees its result, and it
+ * never waits for the device.  It does not clear ADSB_TRACK_TABLE_FULL (that means "since create / reset"; only reset
+ * clears it) and does not change what fetch_points returns for the last update.  -INFINITY evicts nothing, INFINITY
+ * everything.  ADSB_E_ARG for a NULL table or a NaN before.
+ */
+int adsb_track_table_expire(adsb_track_table *table, double before);
+/* Waits; one last-heard time (seconds) per record, in exactly the order adsb_track_table_fetch returns the records;
+ * *n = table size even if it exceeds max.  ADSB_E_ARG for a NULL table, or NULL last_heard with max > 0. */
+int adsb_track_table_fetch_last_heard(adsb_track_table *table, double *last_heard, size_t max, size_t *n);
 
 /*
  * A bank of persistent tables, one per receiver: what N display threads hold, one HashMap<u32, Aircraft> each
@@ -311,10 +329,11 @@ int adsb_track_table_fetch(adsb_track_table *table, adsb_aircraft_record *aircra
  * also when the same ICAO is active on several receivers at once.  One update applies every receiver's part with one
  * dispatch sequence (the table's: field decode, sort by receiver << 24 | icao, lookup, admission, pairs, merge).
  * New ICAO addresses are admitted per receiver in ascending order while that receiver has room; a full receiver sets
- * ADSB_TRACK_TABLE_FULL for itself and marks its turned-away frames ADSB_TRACK_UNTRACKED.  Device memory: 88 bytes
- * per record of n_receivers x max_aircraft, 8 bytes per entry of a hash of (receiver, ICAO) with the next power of two
- * >= 2 x n_receivers x max_aircraft entries, about 120 bytes per frame of max_frames (64 receivers x 65536 aircraft:
- * 369 MiB of records + 64 MiB of hash).  The ctx must outlive the bank; a bank is not thread-safe.
+ * ADSB_TRACK_TABLE_FULL for itself and marks its turned-away frames ADSB_TRACK_UNTRACKED.  Device memory: 104 bytes
+ * per record of n_receivers x max_aircraft (96 of record, 8 of expire scratch), 8 bytes per entry of a hash of
+ * (receiver, ICAO) with the next power of two >= 2 x n_receivers x max_aircraft entries, about 120 bytes per frame of
+ * max_frames (64 receivers x 65536 aircraft: 384 MiB of records + 32 MiB of expire scratch + 64 MiB of hash).  The
+ * ctx must outlive the bank; a bank is not thread-safe.
  */
 typedef struct adsb_track_bank adsb_track_bank;
 typedef struct adsb_track_bank_cfg {
@@ -352,6 +371,14 @@ int adsb_track_bank_fetch_points(adsb_track_bank *bank, adsb_track_point *points
  * in total even if more than max_aircraft; flags[n_receivers] (optional) = ADSB_TRACK_TABLE_FULL or 0 each. */
 int adsb_track_bank_fetch(adsb_track_bank *bank, adsb_aircraft_record *aircraft, size_t max_aircraft,
                           size_t *n_aircraft, uint64_t *per_receiver_counts, uint32_t *flags);
+/* adsb_track_table_expire for every receiver r with its own cut before[n_receivers] (host; -INFINITY: keep all):
+ * receiver r stays bit-identical to a table of its own given the same updates and the same expire calls.  Per
+ * receiver, the size becomes the survivors and the flag is kept.  ADSB_E_ARG for a NULL bank or before array, or a NaN
+ * in it. */
+int adsb_track_bank_expire(adsb_track_bank *bank, const double *before);
+/* Waits; one last-heard time per record, in exactly the order adsb_track_bank_fetch returns the records; *n = records
+ * held in total even if more than max.  ADSB_E_ARG for a NULL bank, or NULL last_heard with max > 0. */
+int adsb_track_bank_fetch_last_heard(adsb_track_bank *bank, double *last_heard, size_t max, size_t *n);
 
 /*
  * ---- several GPUs behind one call ---------------------------------------------------------
