@@ -93,6 +93,18 @@ class AdsbTrackTableCfg(C.Structure):
                 ("seconds_per_sample", C.c_double)]
 
 
+ADSB_VELOCITY_SPEED = 0x1      # adsb_velocity.flags: speed_kt holds a value
+ADSB_VELOCITY_DIRECTION = 0x2  # direction_deg holds a value
+ADSB_VELOCITY_VRATE = 0x4      # vertical_rate_fpm holds a value
+
+
+class AdsbVelocity(C.Structure):
+    _fields_ = [("time", C.c_double), ("speed_kt", C.c_float), ("direction_deg", C.c_float),
+                ("vertical_rate_fpm", C.c_int32), ("v_ew_kt", C.c_int16), ("v_ns_kt", C.c_int16),
+                ("subtype", C.c_uint8), ("flags", C.c_uint8), ("vrate_baro", C.c_uint8), ("airspeed_tas", C.c_uint8),
+                ("reserved", C.c_uint32)]
+
+
 class AdsbTrackBankCfg(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("n_receivers", C.c_uint32), ("max_aircraft", C.c_uint32),
                 ("reserved", C.c_uint32), ("max_frames", C.c_uint64), ("seconds_per_sample", C.c_double)]
@@ -134,6 +146,7 @@ PROTOTYPES = {
     "adsb_track_table_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), _P(C.c_uint32)]),
     "adsb_track_table_expire": (C.c_int, [C.c_void_p, C.c_double]),
     "adsb_track_table_fetch_last_heard": (C.c_int, [C.c_void_p, _P(C.c_double), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_fetch_velocity": (C.c_int, [C.c_void_p, _P(AdsbVelocity), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_bank_create": (C.c_int, [C.c_void_p, _P(AdsbTrackBankCfg), _P(C.c_void_p)]),
     "adsb_track_bank_destroy": (None, [C.c_void_p]),
     "adsb_track_bank_reset": (C.c_int, [C.c_void_p]),
@@ -144,6 +157,7 @@ PROTOTYPES = {
                                         _P(C.c_uint32)]),
     "adsb_track_bank_expire": (C.c_int, [C.c_void_p, _P(C.c_double)]),
     "adsb_track_bank_fetch_last_heard": (C.c_int, [C.c_void_p, _P(C.c_double), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_bank_fetch_velocity": (C.c_int, [C.c_void_p, _P(AdsbVelocity), C.c_size_t, _P(C.c_size_t)]),
     "adsb_cpr_num_zones": (C.c_uint32, [C.c_double]),
     "adsb_cpr_position": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P(C.c_double),
                                     _P(C.c_double)]),

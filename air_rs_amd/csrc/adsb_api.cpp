@@ -1056,9 +1056,11 @@ extern "C" int adsb_track_table_expire(adsb_track_table *t, double before)
     return ADSB_OK;
 }
 
-extern "C" int adsb_track_table_fetch_last_heard(adsb_track_table *t, double *last_heard, size_t max, size_t *n)
+// Waits; out[k] = get(record k) for the records in the order of adsb_track_table_fetch; *n = table size
+template <class T, class Get>
+static int track_table_fetch_each(adsb_track_table *t, T *out, size_t max, size_t *n, Get get)
 {
-    if (!t || (!last_heard && max)) return ADSB_E_ARG;
+    if (!t || (!out && max)) return ADSB_E_ARG;
     HIPCHK(hipSetDevice(t->ctx->cfg.device));
     uint32_t sf[4] = {0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(sf, t->dev.size_flags, sizeof(sf), hipMemcpyDeviceToHost, t->ctx->aux));
@@ -1070,10 +1072,20 @@ extern "C" int adsb_track_table_fetch_last_heard(adsb_track_table *t, double *la
                               t->ctx->aux));
         HIPCHK(hipStreamSynchronize(t->ctx->aux));
         sort_by_icao(recs);
-        for (size_t k = 0; k < std::min(size, max); ++k) last_heard[k] = recs[k].last_heard;
+        for (size_t k = 0; k < std::min(size, max); ++k) out[k] = get(recs[k]);
     }
     if (n) *n = size;
     return ADSB_OK;
+}
+
+extern "C" int adsb_track_table_fetch_last_heard(adsb_track_table *t, double *last_heard, size_t max, size_t *n)
+{
+    return track_table_fetch_each(t, last_heard, max, n, [](const adsbk::TrackRecord &r) { return r.last_heard; });
+}
+
+extern "C" int adsb_track_table_fetch_velocity(adsb_track_table *t, adsb_velocity *velocity, size_t max, size_t *n)
+{
+    return track_table_fetch_each(t, velocity, max, n, [](const adsbk::TrackRecord &r) { return r.vel; });
 }
 
 // ---- a bank of persistent tables, one per receiver (adsb_track_bank_*): the tracker kernels with a TrackBankDev ----
@@ -1364,9 +1376,11 @@ extern "C" int adsb_track_bank_expire(adsb_track_bank *b, const double *before)
     return ADSB_OK;
 }
 
-extern "C" int adsb_track_bank_fetch_last_heard(adsb_track_bank *b, double *last_heard, size_t max, size_t *n)
+// Waits; out[k] = get(record k) for the records in the order of adsb_track_bank_fetch; *n = records held in total
+template <class T, class Get>
+static int track_bank_fetch_each(adsb_track_bank *b, T *out, size_t max, size_t *n, Get get)
 {
-    if (!b || (!last_heard && max)) return ADSB_E_ARG;
+    if (!b || (!out && max)) return ADSB_E_ARG;
     adsb_ctx *c = b->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
     const uint32_t nr = b->cfg.n_receivers, max_ac = b->cfg.max_aircraft;
@@ -1385,12 +1399,22 @@ extern "C" int adsb_track_bank_fetch_last_heard(adsb_track_bank *b, double *last
                                   hipMemcpyDeviceToHost, c->aux));
             HIPCHK(hipStreamSynchronize(c->aux));
             sort_by_icao(recs);
-            for (size_t k = 0; k < take; ++k) last_heard[copied + k] = recs[k].last_heard;
+            for (size_t k = 0; k < take; ++k) out[copied + k] = get(recs[k]);
         }
         copied += take;
     }
     if (n) *n = total;
     return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_fetch_last_heard(adsb_track_bank *b, double *last_heard, size_t max, size_t *n)
+{
+    return track_bank_fetch_each(b, last_heard, max, n, [](const adsbk::TrackRecord &r) { return r.last_heard; });
+}
+
+extern "C" int adsb_track_bank_fetch_velocity(adsb_track_bank *b, adsb_velocity *velocity, size_t max, size_t *n)
+{
+    return track_bank_fetch_each(b, velocity, max, n, [](const adsbk::TrackRecord &r) { return r.vel; });
 }
 
 extern "C" int adsb_set_result_target(adsb_ctx *c, void *blob_dev, size_t blob_bytes)

@@ -173,8 +173,9 @@ struct TrackRecord {
     uint32_t have;               // bit 0: an even position message was seen, bit 1: an odd one
     uint32_t pad;
     double last_heard;           // time of the last frame of any kind (adsb_track_*_expire evicts on it)
+    adsb_velocity vel;           // the last airborne-velocity message (TC 19, ST 1-4); subtype 0 = none yet
 };
-static_assert(sizeof(TrackRecord) == 96, "TrackRecord: the header's memory figures assume 96 bytes");
+static_assert(sizeof(TrackRecord) == 128, "TrackRecord: one cache line; the header's memory figures assume 128 bytes");
 constexpr uint32_t kTrackUntracked = 0xFFFFFFFFu; // slot of an aircraft the full table turned away
 struct TrackTableDev {
     uint32_t *index;             // [1 << 24]: ICAO -> record slot + 1, 0 = absent

@@ -43,6 +43,11 @@
 // table's direct index is fixed by the same kernel (evicted ICAOs cleared, moved ones rewritten); a bank's hash cannot
 // drop entries (a hole in a probe chain would hide later keys), so it is cleared and every survivor reinserted.  A bank
 // does this per receiver region with one scan over all receivers, each region's rank made local as admission does.
+//
+// Airborne velocity (DF17 TC 19, which the reference leaves undecoded): with a table or bank, step 3 also finds the
+// segment's newest velocity message of subtype 1-4 on its walk and decodes it from the frame bytes into the record's
+// `vel`; a segment without one keeps the record's.  Admission starts a record with none, expire moves whole records,
+// and the per-launch form (adsb_track_device) has no velocity.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -137,7 +142,65 @@ __device__ __forceinline__ TrackRecord empty_record(uint32_t icao)
     rec.have = 0;
     rec.pad = 0;
     rec.last_heard = 0.0; // the merge of the admitting list sets it
+    rec.vel = adsb_velocity{};
+    rec.vel.time = __builtin_nan(""); // subtype 0, flags 0: no velocity message yet
     return rec;
+}
+
+// ME bits [first, first + width) of the 56-bit ME field (bit 0 = the top bit of frame byte 4)
+__device__ __forceinline__ uint32_t me_bits(uint64_t me, int first, int width)
+{
+    return (uint32_t)(me >> (56 - first - width)) & ((1u << width) - 1u);
+}
+
+// An airborne-velocity message (DF17 TC 19, ST 1-4; the header's decode rules) from the 14 frame bytes; false for
+// ST 0 and 5-7, which are none.  f64 arithmetic with one rounding to f32; the sum of squares is exact in int32.
+__device__ bool velocity_decode(const uint8_t *bytes, double time, adsb_velocity &v)
+{
+    uint64_t me = 0;
+    for (int k = 4; k < 11; ++k) me = me << 8 | bytes[k];
+    const uint32_t st = me_bits(me, 5, 3);
+    if (st < 1 || st > 4) return false;
+    const int k = (st == 2 || st == 4) ? 4 : 1;
+    v = adsb_velocity{};
+    v.time = time;
+    v.subtype = (uint8_t)st;
+    if (st <= 2) {
+        const uint32_t vew = me_bits(me, 14, 10), vns = me_bits(me, 25, 10);
+        if (vew != 0 && vns != 0) {
+            const int ew = (me_bits(me, 13, 1) ? -1 : 1) * (int)(vew - 1u) * k;
+            const int ns = (me_bits(me, 24, 1) ? -1 : 1) * (int)(vns - 1u) * k;
+            const double speed = sqrt((double)(ew * ew + ns * ns));
+            v.v_ew_kt = (int16_t)ew;
+            v.v_ns_kt = (int16_t)ns;
+            v.speed_kt = (float)speed;
+            v.flags = ADSB_VELOCITY_SPEED;
+            if (speed > 0.0) {
+                double d = atan2((double)ew, (double)ns) * 180.0 / 3.14159265358979323846264338327950288;
+                if (d < 0.0) d += 360.0;
+                v.direction_deg = (float)d;
+                v.flags |= ADSB_VELOCITY_DIRECTION;
+            }
+        }
+    } else {
+        if (me_bits(me, 13, 1)) {
+            v.direction_deg = (float)((double)me_bits(me, 14, 10) * 360.0 / 1024.0);
+            v.flags = ADSB_VELOCITY_DIRECTION;
+        }
+        const uint32_t airspeed = me_bits(me, 25, 10);
+        if (airspeed != 0) {
+            v.speed_kt = (float)((double)(airspeed - 1u) * k);
+            v.airspeed_tas = (uint8_t)me_bits(me, 24, 1);
+            v.flags |= ADSB_VELOCITY_SPEED;
+        }
+    }
+    const uint32_t vr = me_bits(me, 37, 9);
+    if (vr != 0) {
+        v.vertical_rate_fpm = (me_bits(me, 36, 1) ? -1 : 1) * (int32_t)(vr - 1u) * 64;
+        v.vrate_baro = (uint8_t)me_bits(me, 35, 1);
+        v.flags |= ADSB_VELOCITY_VRATE;
+    }
+    return true;
 }
 
 // table only, 1a: the record slot (+1, 0 = absent) of every sorted frame's aircraft; is_new marks the head of a
@@ -412,13 +475,17 @@ __global__ __launch_bounds__(256) void track_summary_kernel(const adsb_frame *fr
         for (int k = 0; k < 8; ++k) r.a.callsign[k] = 0;
     }
     bool have_id = false, have_pos_msg = false, have_fix = false, have_even = false, have_odd = false;
-    uint32_t count = 0;
+    uint32_t count = 0, vel_j = kTrackUntracked; // vel_j: the newest velocity message (table / bank only)
     for (uint32_t w = s + 1; w > 0;) { // newest to oldest
         --w;
         if (skeys[w] != key) break;
         const uint32_t j = svals[w];
         const adsb_packet_fields g = fields[j];
         ++count;
+        if (table && g.msg_type == 19 && vel_j == kTrackUntracked) { // TC 19: ST 1-4 only (velocity_decode)
+            const uint32_t st = frames[j].bytes[4] & 7u;
+            if (st >= 1 && st <= 4) vel_j = j;
+        }
         if (g.msg_kind == 0 && !have_id) { // aircraft.rs:105-107
             have_id = true;
             for (int k = 0; k < 8; ++k) r.a.callsign[k] = g.callsign[k];
@@ -452,6 +519,9 @@ __global__ __launch_bounds__(256) void track_summary_kernel(const adsb_frame *fr
     r.a.n_frames += count;
     if (table) {
         r.last_heard = frame_time(frames, svals[s], sample_base, seconds_per_sample); // the segment's last frame
+        if (vel_j != kTrackUntracked)
+            (void)velocity_decode(frames[vel_j].bytes, frame_time(frames, vel_j, sample_base, seconds_per_sample),
+                                  r.vel);
         t.rec[a] = r;
     } else {
         out[a] = r.a;

@@ -73,6 +73,10 @@ def synth_slot(cfg, channel, slot):
 TRACK_POINT_DTYPE = np.dtype([("latitude", "<f8"), ("longitude", "<f8"), ("icao", "<u4"), ("flags", "<u4")])
 AIRCRAFT_DTYPE = np.dtype([("latitude", "<f8"), ("longitude", "<f8"), ("last_contact", "<f8"), ("icao", "<u4"),
                            ("altitude", "<i4"), ("has_position", "<u4"), ("n_frames", "<u4"), ("callsign", "S8")])
+VELOCITY_DTYPE = np.dtype([("time", "<f8"), ("speed_kt", "<f4"), ("direction_deg", "<f4"),
+                           ("vertical_rate_fpm", "<i4"), ("v_ew_kt", "<i2"), ("v_ns_kt", "<i2"), ("subtype", "u1"),
+                           ("flags", "u1"), ("vrate_baro", "u1"), ("airspeed_tas", "u1"), ("reserved", "<u4")])
+assert VELOCITY_DTYPE.itemsize == C.sizeof(L.AdsbVelocity) == 32
 
 
 class Tracker:
@@ -575,6 +579,16 @@ class TrackTable:
                                                             C.byref(n)), "adsb_track_table_fetch_last_heard")
         return out[:n.value].copy()
 
+    def velocity(self):
+        """VELOCITY_DTYPE records (each aircraft's last airborne-velocity message), aligned with aircraft()[0]."""
+        n = C.c_size_t()
+        L.check(self._lib.adsb_track_table_fetch_velocity(self._h, None, 0, C.byref(n)),
+                "adsb_track_table_fetch_velocity")
+        out = np.zeros(max(n.value, 1), dtype=VELOCITY_DTYPE)
+        L.check(self._lib.adsb_track_table_fetch_velocity(self._h, out.ctypes.data_as(C.POINTER(L.AdsbVelocity)),
+                                                          len(out), C.byref(n)), "adsb_track_table_fetch_velocity")
+        return out[:n.value].copy()
+
 
 class TrackBank:
     """adsb_track_bank_*: n_receivers independent aircraft tables on the device (one HashMap<u32, Aircraft> per
@@ -676,6 +690,16 @@ class TrackBank:
         out = np.zeros(max(sum(len(x) for x in recs), 1), dtype=np.float64)
         L.check(self._lib.adsb_track_bank_fetch_last_heard(self._h, out.ctypes.data_as(C.POINTER(C.c_double)),
                                                            len(out), C.byref(n)), "adsb_track_bank_fetch_last_heard")
+        edges = np.concatenate([[0], np.cumsum([len(x) for x in recs])]).astype(np.int64)
+        return [out[edges[r]:edges[r + 1]].copy() for r in range(self.n_receivers)]
+
+    def velocity(self):
+        """list of n_receivers VELOCITY_DTYPE arrays, aligned with aircraft()[0]."""
+        recs, _ = self.aircraft()                         # the per-receiver split of the same records
+        n = C.c_size_t()
+        out = np.zeros(max(sum(len(x) for x in recs), 1), dtype=VELOCITY_DTYPE)
+        L.check(self._lib.adsb_track_bank_fetch_velocity(self._h, out.ctypes.data_as(C.POINTER(L.AdsbVelocity)),
+                                                         len(out), C.byref(n)), "adsb_track_bank_fetch_velocity")
         edges = np.concatenate([[0], np.cumsum([len(x) for x in recs])]).astype(np.int64)
         return [out[edges[r]:edges[r + 1]].copy() for r in range(self.n_receivers)]
 

@@ -272,7 +272,7 @@ int adsb_fetch_track(adsb_ctx *ctx, adsb_track_point *points, size_t max_points,
  * *first_sample; with carry = 1 (absolute offsets) it is 0.  One table per receiver (an update takes one ordered
  * list).  Aircraft stay until adsb_track_table_expire evicts them (the reference's map is unbounded and never does;
  * this one has max_aircraft places) or until reset.  The table costs 64 MiB of device memory for its ICAO index plus
- * 104 bytes per aircraft of max_aircraft (a 96-byte record and 8 bytes of expire scratch) and about 100 bytes per
+ * 136 bytes per aircraft of max_aircraft (a 128-byte record and 8 bytes of expire scratch) and about 100 bytes per
  * frame of max_frames.  The ctx must outlive the table; like the ctx, a table is not thread-safe.
  */
 #define ADSB_TRACK_UNTRACKED 0x2u  /* point flag: this frame's aircraft was not admitted (table full); only icao valid */
@@ -320,6 +320,38 @@ int adsb_track_table_expire(adsb_track_table *table, double before);
 /* Waits; one last-heard time (seconds) per record, in exactly the order adsb_track_table_fetch returns the records;
  * *n = table size even if it exceeds max.  ADSB_E_ARG for a NULL table, or NULL last_heard with max > 0. */
 int adsb_track_table_fetch_last_heard(adsb_track_table *table, double *last_heard, size_t max, size_t *n);
+/*
+ * Airborne velocity.  Every record also keeps its aircraft's last airborne-velocity message (DF17 TC 19, subtype
+ * 1-4; the reference decodes none and prints "n/a" in its Velocity column).  ME bit 0 is the top bit of frame byte
+ * 4 (TC = ME bits 0-4, ST = 5-7); k = 4 for ST 2 and 4 (supersonic), else 1.
+ *   ST 1-2: Dew 13, Vew 14-23, Dns 24, Vns 25-34.  Vew != 0 and Vns != 0: v_ew = +-(Vew - 1) k (- if Dew), v_ns
+ *           likewise, speed = sqrt(v_ew^2 + v_ns^2) (SPEED); if speed > 0 also direction = atan2(v_ew, v_ns) in
+ *           degrees, [0, 360) (DIRECTION).
+ *   ST 3-4: status 13, heading 14-23, type 24, airspeed 25-34.  status = 1: direction = heading x 360 / 1024
+ *           (DIRECTION); airspeed != 0: speed = (airspeed - 1) k, airspeed_tas = type (SPEED).
+ *   ST 1-4: VrSrc 35, Svr 36, Vr 37-45.  Vr != 0: vertical_rate = +-(Vr - 1) x 64 (- if Svr), vrate_baro = VrSrc
+ *           (VRATE).
+ * ST 0 and 5-7 are no velocity message: the record keeps what it had.  f64 arithmetic, rounded once to f32.  The
+ * newest such message of an update wins; an admitted (or re-admitted, after expire) aircraft starts with none.
+ */
+#define ADSB_VELOCITY_SPEED     0x1u /* speed_kt holds a value          */
+#define ADSB_VELOCITY_DIRECTION 0x2u /* direction_deg holds a value     */
+#define ADSB_VELOCITY_VRATE     0x4u /* vertical_rate_fpm holds a value */
+typedef struct adsb_velocity {  /* an aircraft's last airborne-velocity message (DF17 TC 19, subtype 1-4), 32 bytes */
+    double   time;              /* seconds: the table's frame time of that message; NaN if none yet            */
+    float    speed_kt;          /* ST 1-2: ground speed; ST 3-4: airspeed; 0 unless ADSB_VELOCITY_SPEED        */
+    float    direction_deg;     /* ST 1-2: track over ground [0, 360); ST 3-4: heading; 0 unless ..._DIRECTION  */
+    int32_t  vertical_rate_fpm; /* positive = climbing; 0 unless ADSB_VELOCITY_VRATE                            */
+    int16_t  v_ew_kt, v_ns_kt;  /* ST 1-2 with SPEED: signed components, east and north positive; else 0          */
+    uint8_t  subtype;           /* 1-4; 0 = no velocity message since admission                                */
+    uint8_t  flags;             /* ADSB_VELOCITY_*                                                              */
+    uint8_t  vrate_baro;        /* 1 = barometric vertical rate, 0 = GNSS (only with VRATE)                     */
+    uint8_t  airspeed_tas;      /* ST 3-4 with SPEED: 1 = true airspeed, 0 = indicated                          */
+    uint32_t reserved;          /* 0 */
+} adsb_velocity;
+/* Waits; one velocity per record, in exactly the order adsb_track_table_fetch returns the records; *n = table size
+ * even if it exceeds max.  ADSB_E_ARG for a NULL table, or NULL velocity with max > 0. */
+int adsb_track_table_fetch_velocity(adsb_track_table *table, adsb_velocity *velocity, size_t max, size_t *n);
 
 /*
  * A bank of persistent tables, one per receiver: what N display threads hold, one HashMap<u32, Aircraft> each
@@ -329,10 +361,10 @@ int adsb_track_table_fetch_last_heard(adsb_track_table *table, double *last_hear
  * also when the same ICAO is active on several receivers at once.  One update applies every receiver's part with one
  * dispatch sequence (the table's: field decode, sort by receiver << 24 | icao, lookup, admission, pairs, merge).
  * New ICAO addresses are admitted per receiver in ascending order while that receiver has room; a full receiver sets
- * ADSB_TRACK_TABLE_FULL for itself and marks its turned-away frames ADSB_TRACK_UNTRACKED.  Device memory: 104 bytes
- * per record of n_receivers x max_aircraft (96 of record, 8 of expire scratch), 8 bytes per entry of a hash of
+ * ADSB_TRACK_TABLE_FULL for itself and marks its turned-away frames ADSB_TRACK_UNTRACKED.  Device memory: 136 bytes
+ * per record of n_receivers x max_aircraft (128 of record, 8 of expire scratch), 8 bytes per entry of a hash of
  * (receiver, ICAO) with the next power of two >= 2 x n_receivers x max_aircraft entries, about 120 bytes per frame of
- * max_frames (64 receivers x 65536 aircraft: 384 MiB of records + 32 MiB of expire scratch + 64 MiB of hash).  The
+ * max_frames (64 receivers x 65536 aircraft: 512 MiB of records + 32 MiB of expire scratch + 64 MiB of hash).  The
  * ctx must outlive the bank; a bank is not thread-safe.
  */
 typedef struct adsb_track_bank adsb_track_bank;
@@ -379,6 +411,10 @@ int adsb_track_bank_expire(adsb_track_bank *bank, const double *before);
 /* Waits; one last-heard time per record, in exactly the order adsb_track_bank_fetch returns the records; *n = records
  * held in total even if more than max.  ADSB_E_ARG for a NULL bank, or NULL last_heard with max > 0. */
 int adsb_track_bank_fetch_last_heard(adsb_track_bank *bank, double *last_heard, size_t max, size_t *n);
+/* Waits; one velocity (adsb_track_table_fetch_velocity) per record, in exactly the order adsb_track_bank_fetch
+ * returns the records; *n = records held in total even if more than max.  ADSB_E_ARG for a NULL bank, or NULL
+ * velocity with max > 0. */
+int adsb_track_bank_fetch_velocity(adsb_track_bank *bank, adsb_velocity *velocity, size_t max, size_t *n);
 
 /*
  * ---- several GPUs behind one call ---------------------------------------------------------

@@ -5,9 +5,12 @@
   tools/replay.py capture.c16                 # the reference's format (utils.rs:22-43), reference semantics
   tools/replay.py capture.bin --format u8     # raw rtl_sdr capture (unsigned bytes)
   tools/replay.py capture.c16 --carry --tail  # also decode frames straddling buffers and the last chunk
+  tools/replay.py capture.c16 --aircraft      # the final aircraft table instead (tui.rs:65-95, Velocity filled)
 
 Everything below the argument parsing is one call through the C ABI (adsb_replay_file, include/adsb_host.h).
-The "Processed Time" line carries no value (the reference prints the wall clock there)."""
+The "Processed Time" line carries no value (the reference prints the wall clock there).  With --aircraft, the frames
+go through one device track table (2 MSPS, one update) and the table is printed tab-separated with the columns of
+the reference's TUI; its Velocity column, always "n/a" there, holds the last airborne-velocity message's speed."""
 import argparse
 import os
 import sys
@@ -15,6 +18,32 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import air_rs_amd as A  # noqa: E402
 from air_rs_amd import _lib as L  # noqa: E402
+
+
+SECONDS_PER_SAMPLE = 0.5e-6  # 2 MSPS
+
+
+def aircraft_table(d, frames, n_samples):
+    """The capture's final aircraft table as tab-separated text: tui.rs:95's columns, rows by age (tui.rs:69), then
+    ICAO.  Age = whole seconds from each aircraft's last frame to the end of the capture."""
+    with A.TrackTable(d, max_frames=max(len(frames), 1), seconds_per_sample=SECONDS_PER_SAMPLE) as t:
+        t.update(frames)
+        recs, _ = t.aircraft()
+        vel, heard = t.velocity(), t.last_heard()
+    now = n_samples * SECONDS_PER_SAMPLE
+    rows = []
+    for rec, v, lh in zip(recs, vel, heard):
+        pos, age = bool(rec["has_position"]), int(now - lh)
+        rows.append((age, int(rec["icao"]), "\t".join([
+            f"{int(rec['icao']):x}",
+            rec["callsign"].decode("latin-1"),                       # S8: trailing NULs already stripped
+            f"{int(rec['altitude'])}",
+            f"{float(rec['latitude']):.6f}" if pos else "n/a",
+            f"{float(rec['longitude']):.6f}" if pos else "n/a",
+            f"{float(v['speed_kt']):.0f}" if v["flags"] & A.ADSB_VELOCITY_SPEED else "n/a",
+            f"{age}"])))
+    rows.sort(key=lambda r: (r[0], r[1]))
+    return "ICAO\tCallsign\tAltitude\tLatitude\tLongitude\tVelocity\tAge\n" + "".join(r[2] + "\n" for r in rows)
 
 
 def main():
@@ -26,6 +55,7 @@ def main():
     ap.add_argument("--tail", action="store_true", help="also send the last chunk (not reference behaviour)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--summary", action="store_true", help="print counts to stderr")
+    ap.add_argument("--aircraft", action="store_true", help="print the final aircraft table instead of the stream text")
     a = ap.parse_args()
     fmt = a.format or ("c16" if a.file.endswith(".c16") else "u8")
     st = A.ADSB_SAMPLE_I16 if fmt == "c16" else A.ADSB_SAMPLE_I8
@@ -35,6 +65,8 @@ def main():
         frames, n_buf, n_samp, text = d.replay_file(a.file, L.ADSB_FILE_C16 if fmt == "c16" else L.ADSB_FILE_U8,
                                                     chunk_len=a.chunk, carry=a.carry, send_tail=a.tail,
                                                     max_frames=max(n_max // 200, 1 << 16))
+        if a.aircraft:
+            text = aircraft_table(d, frames, n_samp)
     sys.stdout.write(text)
     if a.summary:
         print(f"{n_samp} samples, {n_buf} buffers of {a.chunk}, {len(frames)} packets", file=sys.stderr)
