@@ -105,6 +105,21 @@ class AdsbVelocity(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+ADSB_FUSED_NONE = 0xFFFF            # adsb_fused_aircraft.*_receiver: no contributing record has that quantity
+ADSB_TRACK_FUSED_TRUNCATED = 0x1    # fetch_fused flag: more distinct ICAOs than max_fused
+
+
+class AdsbFusedAircraft(C.Structure):
+    """adsb_fused_aircraft; `velocity` stands for the header's eleven fields velocity_time .. velocity_reserved, which
+    are an adsb_velocity bit for bit."""
+    _fields_ = [("latitude", C.c_double), ("longitude", C.c_double), ("position_time", C.c_double),
+                ("last_contact", C.c_double), ("last_heard", C.c_double), ("n_frames", C.c_uint64),
+                ("icao", C.c_uint32), ("altitude", C.c_int32), ("n_receivers", C.c_uint16),
+                ("heard_receiver", C.c_uint16), ("contact_receiver", C.c_uint16), ("position_receiver", C.c_uint16),
+                ("callsign_receiver", C.c_uint16), ("velocity_receiver", C.c_uint16), ("has_position", C.c_uint32),
+                ("callsign", C.c_char * 8), ("velocity", AdsbVelocity), ("reserved", C.c_uint64 * 2)]
+
+
 class AdsbTrackBankCfg(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("n_receivers", C.c_uint32), ("max_aircraft", C.c_uint32),
                 ("reserved", C.c_uint32), ("max_frames", C.c_uint64), ("seconds_per_sample", C.c_double)]
@@ -158,6 +173,11 @@ PROTOTYPES = {
     "adsb_track_bank_expire": (C.c_int, [C.c_void_p, _P(C.c_double)]),
     "adsb_track_bank_fetch_last_heard": (C.c_int, [C.c_void_p, _P(C.c_double), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_bank_fetch_velocity": (C.c_int, [C.c_void_p, _P(AdsbVelocity), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_bank_fuse_reserve": (C.c_int, [C.c_void_p, C.c_size_t]),
+    "adsb_track_bank_fuse": (C.c_int, [C.c_void_p, C.c_double]),
+    "adsb_track_bank_fetch_fused": (C.c_int, [C.c_void_p, _P(AdsbFusedAircraft), C.c_size_t, _P(C.c_size_t),
+                                              _P(C.c_size_t), _P(C.c_uint32)]),
+    "adsb_track_bank_fused_device": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p)]),
     "adsb_cpr_num_zones": (C.c_uint32, [C.c_double]),
     "adsb_cpr_position": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P(C.c_double),
                                     _P(C.c_double)]),

@@ -1110,12 +1110,37 @@ struct adsb_track_bank {
     size_t exp_temp_bytes = 0;
     uint32_t n_points = 0;
     bool updated = false;
+    // the fused view (adsb_track_bank_fuse_*): all of it allocated by fuse_reserve, nothing before
+    void *fuse_keys = nullptr;      // 2 x [places] sort keys (uint32_t, uint64_t above kFuseWideReceivers): in, sorted
+    uint32_t *fuse_vals = nullptr;  // 2 x [places]: places in, sorted
+    uint32_t *fuse_start = nullptr; // [fuse_max]
+    adsb_fused_aircraft *fuse_out = nullptr; // [fuse_max]
+    uint64_t *fuse_counts = nullptr; // device [3]: records written, distinct ICAOs, ADSB_TRACK_FUSED_TRUNCATED
+    void *fuse_temp = nullptr;
+    size_t fuse_temp_bytes = 0;
+    size_t fuse_max = 0;            // 0: no reserve
+    uint32_t fuse_lanes = 0;
+    bool fused = false;             // a fuse ran since the last reserve
 };
+
+static void track_bank_fuse_free(adsb_track_bank *b)
+{
+    for (void *p : {b->fuse_keys, (void *)b->fuse_vals, (void *)b->fuse_start, (void *)b->fuse_out,
+                    (void *)b->fuse_counts, b->fuse_temp})
+        if (p) (void)hipFree(p);
+    b->fuse_keys = b->fuse_temp = nullptr;
+    b->fuse_vals = b->fuse_start = nullptr;
+    b->fuse_out = nullptr;
+    b->fuse_counts = nullptr;
+    b->fuse_max = 0;
+    b->fused = false;
+}
 
 static void track_bank_free(adsb_track_bank *b)
 {
     (void)hipSetDevice(b->ctx->cfg.device);
     (void)hipStreamSynchronize(b->ctx->aux);
+    track_bank_fuse_free(b);
     for (void *p : {(void *)b->dev.hash, (void *)b->dev.rec, (void *)b->words, (void *)b->dev.prefix, (void *)b->meta,
                     (void *)b->dev.mark, (void *)b->dev.excl, (void *)b->dev.seg_slot, (void *)b->tab.slot,
                     (void *)b->u32, b->temp, (void *)b->frames, (void *)b->fields, (void *)b->points,
@@ -1415,6 +1440,96 @@ extern "C" int adsb_track_bank_fetch_last_heard(adsb_track_bank *b, double *last
 extern "C" int adsb_track_bank_fetch_velocity(adsb_track_bank *b, adsb_velocity *velocity, size_t max, size_t *n)
 {
     return track_bank_fetch_each(b, velocity, max, n, [](const adsbk::TrackRecord &r) { return r.vel; });
+}
+
+// ---- the fused view of a bank: one record per ICAO over all receivers (adsb_track.hip, launch_track_fuse) ----
+extern "C" int adsb_track_bank_fuse_reserve(adsb_track_bank *b, size_t max_fused)
+{
+    if (!b) return ADSB_E_ARG;
+    adsb_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipStreamSynchronize(c->aux)); // a fuse may still read what is freed here
+    track_bank_fuse_free(b);
+    const uint32_t nr = b->cfg.n_receivers;
+    const size_t places = (size_t)nr * b->cfg.max_aircraft;
+    const size_t cap = max_fused == 0 || max_fused > places ? places : max_fused; // more than `places` cannot occur
+    const size_t key_bytes = nr > adsbk::kFuseWideReceivers ? sizeof(uint64_t) : sizeof(uint32_t);
+    b->fuse_temp_bytes = adsbk::track_fuse_temp_bytes(places, nr);
+    b->fuse_lanes = nr == 1 ? 1u : 4u; // measured: DESIGN 4.4f (16 and 64 lanes lost on runs of 64 and of 1 alike)
+    if (const char *fl = getenv("ADSB_FUSE_LANES")) { // measurement knob: lanes per ICAO in the reduction
+        const int v = atoi(fl);
+        if (v == 1 || v == 4) b->fuse_lanes = (uint32_t)v;
+    }
+    const bool ok = hipMalloc(&b->fuse_keys, 2 * key_bytes * places) == hipSuccess &&
+                    hipMalloc((void **)&b->fuse_vals, 2 * sizeof(uint32_t) * places) == hipSuccess &&
+                    hipMalloc((void **)&b->fuse_start, sizeof(uint32_t) * cap) == hipSuccess &&
+                    hipMalloc((void **)&b->fuse_out, sizeof(adsb_fused_aircraft) * cap) == hipSuccess &&
+                    hipMalloc((void **)&b->fuse_counts, sizeof(uint64_t) * 3) == hipSuccess &&
+                    hipMalloc(&b->fuse_temp, b->fuse_temp_bytes) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        track_bank_fuse_free(b);
+        return ADSB_E_NOMEM;
+    }
+    b->fuse_max = cap;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_fuse(adsb_track_bank *b, double since)
+{
+    if (!b || std::isnan(since)) return ADSB_E_ARG;
+    if (!b->fuse_max) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(b->ctx->cfg.device));
+    const size_t places = (size_t)b->cfg.n_receivers * b->cfg.max_aircraft;
+    const size_t key_bytes = b->cfg.n_receivers > adsbk::kFuseWideReceivers ? sizeof(uint64_t) : sizeof(uint32_t);
+    adsbk::FuseArgs a{};
+    a.bank = &b->dev;
+    a.since = since;                 // by value in the kernel's arguments, as expire's cuts: no staging, no wait
+    a.keys = b->fuse_keys;
+    a.skeys = (char *)b->fuse_keys + key_bytes * places;
+    a.vals = b->fuse_vals;
+    a.svals = b->fuse_vals + places;
+    a.seg_start = b->fuse_start;
+    a.out = b->fuse_out;
+    a.counts = b->fuse_counts;
+    a.max_fused = b->fuse_max;
+    a.temp = b->fuse_temp;
+    a.temp_bytes = b->fuse_temp_bytes;
+    a.lanes = b->fuse_lanes;
+    HIPCHK(adsbk::launch_track_fuse(b->ctx->aux, a)); // after the bank's last update / expire / reset (same stream)
+    b->fused = true;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_fetch_fused(adsb_track_bank *b, adsb_fused_aircraft *out, size_t max, size_t *n,
+                                           size_t *n_total, uint32_t *flags)
+{
+    if (!b || (!out && max)) return ADSB_E_ARG;
+    if (!b->fused) return ADSB_E_STATE;
+    adsb_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    uint64_t w[3];
+    HIPCHK(hipMemcpyAsync(w, b->fuse_counts, sizeof(w), hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    const size_t take = std::min<size_t>(std::min<uint64_t>(w[0], b->fuse_max), max);
+    if (take) {
+        HIPCHK(hipMemcpyAsync(out, b->fuse_out, sizeof(adsb_fused_aircraft) * take, hipMemcpyDeviceToHost, c->aux));
+        HIPCHK(hipStreamSynchronize(c->aux));
+    }
+    if (n) *n = take;
+    if (n_total) *n_total = (size_t)w[1];
+    if (flags) *flags = (uint32_t)w[2];
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_fused_device(adsb_track_bank *b, const adsb_fused_aircraft **fused_dev,
+                                            const uint64_t **counts_dev)
+{
+    if (!b) return ADSB_E_ARG;
+    if (!b->fused) return ADSB_E_STATE;
+    if (fused_dev) *fused_dev = b->fuse_out;
+    if (counts_dev) *counts_dev = b->fuse_counts;
+    return ADSB_OK;
 }
 
 extern "C" int adsb_set_result_target(adsb_ctx *c, void *blob_dev, size_t blob_bytes)

@@ -2,6 +2,7 @@
 // kernels (adsb_kernels.hip).  Internal; the public boundary is include/adsb_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/adsb_hip.h"
@@ -243,6 +244,30 @@ hipError_t launch_track_expire(hipStream_t s, const ExpireArgs &a);
 size_t track_sort_temp_bytes(size_t n);
 size_t track_bank_temp_bytes(size_t n); // the bank's sort (32 bits) and 64-bit scan
 hipError_t launch_track(hipStream_t s, const TrackArgs &a);
+
+// the fused view of a bank (adsb_track_bank_fuse): every receiver's contributing records sorted by ICAO then receiver
+// and reduced to one adsb_fused_aircraft per ICAO; reads the bank only
+static_assert(sizeof(adsb_fused_aircraft) == 128 && offsetof(adsb_fused_aircraft, velocity_time) == 80 &&
+                  offsetof(adsb_fused_aircraft, reserved) == 80 + sizeof(adsb_velocity) &&
+                  offsetof(adsb_fused_aircraft, velocity_reserved) == 80 + offsetof(adsb_velocity, reserved),
+              "adsb_fused_aircraft: one cache line, an adsb_velocity bit for bit at offset 80");
+constexpr uint32_t kFuseWideReceivers = 128; // above this, ICAO << 8 | receiver plus the 'no record' bit needs 33 bits
+struct FuseArgs {
+    const TrackBankDev *bank;
+    double since;                // a record contributes iff it is held and last_heard >= since
+    void *keys, *skeys;          // [places] each, places = n_receivers x max_aircraft: uint32_t sort keys, uint64_t with
+                                 // more than kFuseWideReceivers receivers; keys is reused after the sort
+    uint32_t *vals, *svals;      // [places] each: the record's place; vals is reused as the scan's output
+    uint32_t *seg_start;         // [max_fused]: where each ICAO's run starts in sorted order
+    adsb_fused_aircraft *out;    // [max_fused]
+    uint64_t *counts;            // device words: [0] records written, [1] distinct ICAOs, [2] ADSB_TRACK_FUSED_TRUNCATED
+    uint64_t max_fused;          // 1 .. places
+    void *temp;
+    size_t temp_bytes;
+    uint32_t lanes;              // lanes that share one ICAO's reduction: 1 or 4
+};
+size_t track_fuse_temp_bytes(size_t places, uint32_t n_receivers);
+hipError_t launch_track_fuse(hipStream_t s, const FuseArgs &a);
 
 // test / measurement kernels
 hipError_t launch_magnitudes(hipStream_t s, int sample_type, int mag_mode, const void *iq,

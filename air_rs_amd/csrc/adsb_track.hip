@@ -48,6 +48,15 @@
 // segment's newest velocity message of subtype 1-4 on its walk and decodes it from the frame bytes into the record's
 // `vel`; a segment without one keeps the record's.  Admission starts a record with none, expire moves whole records,
 // and the per-launch form (adsb_track_device) has no velocity.
+//
+// The fused view (adsb_track_bank_fuse) turns a bank's N maps into one picture, each ICAO once, without touching the
+// bank: a key kernel writes icao << rbits | receiver for every contributing record (held, last_heard >= since) and
+// 1 << (24 + rbits) for every other place, so those sort last and never look like an aircraft (all ones would:
+// ICAO FFFFFF on the last of 2^rbits receivers); a rocPRIM sort over 25 + rbits bits makes one run per ICAO with its
+// receivers ascending; a scan of the ICAO changes numbers the runs; one group of 1 or 4 lanes per run picks, per
+// quantity, the record with the greatest time (ties: the lowest sorted position = the lowest receiver), and the
+// workgroup writes its 128-byte output records once, through LDS.  All sizes are device words; the total and the
+// truncation flag are published by the last thread of the kernel that stores the run starts.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -604,6 +613,210 @@ __global__ __launch_bounds__(256) void track_bank_rehash_kernel(TrackTableDev t,
         if (atomicCAS(&b.hash[h], 0ull, entry) == 0ull) break;
 }
 
+// ---- the fused view of a bank --------------------------------------------------------------------------------------
+constexpr uint32_t kFuseNone = 0xFFFFFFFFu; // a sorted position: no record yet
+
+// fuse, 1: one thread per place p = r x max_aircraft + slot
+template <class K>
+__global__ __launch_bounds__(256) void fuse_keys_kernel(TrackBankDev b, double since, uint32_t rbits, K *keys,
+                                                        uint32_t *vals, uint64_t places)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= places) return;
+    const uint32_t r = (uint32_t)(p / b.max_aircraft);
+    K key = (K)1 << (24 + rbits);
+    if ((uint32_t)(p - (uint64_t)r * b.max_aircraft) < b.size[r]) {
+        const TrackRecord &rec = b.rec[p];
+        if (rec.last_heard >= since) key = (K)(rec.a.icao & 0xFFFFFFu) << rbits | r;
+    }
+    keys[p] = key;
+    vals[p] = (uint32_t)p;
+}
+
+// 1 where an ICAO's run starts in sorted order (the scan's input, and fuse_starts_kernel's test)
+template <class K>
+struct FuseHead {
+    const K *skeys;
+    uint32_t rbits;
+    __device__ __forceinline__ uint32_t operator()(uint32_t s) const
+    {
+        const uint32_t icao = (uint32_t)(skeys[s] >> rbits);
+        return (icao < (1u << 24) && (s == 0 || (uint32_t)(skeys[s - 1] >> rbits) != icao)) ? 1u : 0u;
+    }
+};
+
+// fuse, 3 (after the exclusive scan excl of the heads): run g starts at seg_start[g]; the last thread publishes the
+// counts and the flag
+template <class K>
+__global__ __launch_bounds__(256) void fuse_starts_kernel(FuseHead<K> head, const uint32_t *excl, uint64_t places,
+                                                          uint64_t max_fused, uint32_t *seg_start, uint64_t *counts)
+{
+    const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= places) return;
+    const uint32_t h = head((uint32_t)s), g = excl[s];
+    if (h && g < max_fused) seg_start[g] = (uint32_t)s;
+    if (s + 1 == places) {
+        const uint64_t total = (uint64_t)g + h;
+        counts[0] = total < max_fused ? total : max_fused;
+        counts[1] = total;
+        counts[2] = total > max_fused ? ADSB_TRACK_FUSED_TRUNCATED : 0u;
+    }
+}
+
+// the newest record so far for one quantity: the greatest time, and among equal times the lowest sorted position
+struct FuseBest {
+    double t;
+    uint32_t w; // sorted position, kFuseNone: no candidate
+    __device__ __forceinline__ void take(double t2, uint32_t w2)
+    {
+        if (w2 != kFuseNone && (w == kFuseNone || t2 > t || (t2 == t && w2 < w))) {
+            t = t2;
+            w = w2;
+        }
+    }
+    template <int G>
+    __device__ __forceinline__ void across() // every lane of the group ends with the group's best
+    {
+        for (int m = G / 2; m > 0; m >>= 1) take(__shfl_xor(t, m, G), __shfl_xor(w, m, G));
+    }
+};
+
+// fuse, 4: G lanes per ICAO run (1 .. n_receivers records, receivers ascending), 256 / G runs per workgroup.  Lane l
+// looks at the run's records l, l + G, ...; a butterfly leaves every lane with the five winners, the frame sum and the
+// count; lane 0 copies the winners' fields into the workgroup's stage in LDS, and the whole workgroup stores the stage
+// as consecutive 16-byte pieces (a lane storing its own 128-byte record would touch every line eight times).
+template <class K, int G>
+__global__ __launch_bounds__(256) void fuse_reduce_kernel(const TrackRecord *rec, const K *skeys, const uint32_t *svals,
+                                                          const uint32_t *seg_start, const uint64_t *counts,
+                                                          uint32_t rbits, uint64_t places, adsb_fused_aircraft *out)
+{
+    constexpr uint32_t kRuns = 256 / G;
+    __shared__ __attribute__((aligned(16))) adsb_fused_aircraft stage[kRuns];
+    const uint64_t n_out = counts[0], g0 = (uint64_t)blockIdx.x * kRuns;
+    if (g0 >= n_out) return; // the whole workgroup leaves
+    const uint32_t run = threadIdx.x / G, lane = threadIdx.x % G;
+    if (g0 + run < n_out) { // a group is inside as a whole: the shuffles below stay among its G lanes
+        const uint32_t start = seg_start[g0 + run];
+        const uint32_t icao = (uint32_t)(skeys[start] >> rbits);
+        FuseBest heard{0.0, kFuseNone}, contact{0.0, kFuseNone}, fix{0.0, kFuseNone}, ident{0.0, kFuseNone},
+            vel{0.0, kFuseNone};
+        uint64_t frames = 0;
+        uint32_t n = 0;
+        for (uint64_t w = (uint64_t)start + lane; w < places && (uint32_t)(skeys[w] >> rbits) == icao; w += G) {
+            const TrackRecord &r = rec[svals[w]];
+            const double lc = r.a.last_contact, lh = r.last_heard;
+            uint64_t cs;
+            __builtin_memcpy(&cs, r.a.callsign, 8);
+            heard.take(lh, (uint32_t)w);
+            if (lc == lc) contact.take(lc, (uint32_t)w);
+            if (r.a.has_position) fix.take(lc, (uint32_t)w);
+            if (cs != 0) ident.take(lh, (uint32_t)w);
+            if (r.vel.subtype != 0) vel.take(r.vel.time, (uint32_t)w);
+            frames += r.a.n_frames;
+            ++n;
+        }
+        heard.across<G>();
+        contact.across<G>();
+        fix.across<G>();
+        ident.across<G>();
+        vel.across<G>();
+        for (int m = G / 2; m > 0; m >>= 1) {
+            frames += __shfl_xor(frames, m, G);
+            n += __shfl_xor(n, m, G);
+        }
+        if (lane == 0) {
+            const uint32_t rmask = (1u << rbits) - 1u;
+            adsb_fused_aircraft f{}; // reserved, and every quantity nobody has: 0
+            f.icao = icao;
+            f.n_frames = frames;
+            f.n_receivers = (uint16_t)n;
+            f.heard_receiver = (uint16_t)((uint32_t)skeys[heard.w] & rmask); // a run has at least one record
+            f.last_heard = heard.t;
+            f.contact_receiver = f.position_receiver = f.callsign_receiver = f.velocity_receiver = ADSB_FUSED_NONE;
+            f.last_contact = f.position_time = f.velocity_time = __builtin_nan("");
+            if (contact.w != kFuseNone) {
+                f.contact_receiver = (uint16_t)((uint32_t)skeys[contact.w] & rmask);
+                f.last_contact = contact.t;
+                f.altitude = rec[svals[contact.w]].a.altitude;
+            }
+            if (fix.w != kFuseNone) {
+                const TrackRecord &r = rec[svals[fix.w]];
+                f.position_receiver = (uint16_t)((uint32_t)skeys[fix.w] & rmask);
+                f.has_position = 1;
+                f.latitude = r.a.latitude;
+                f.longitude = r.a.longitude;
+                f.position_time = r.a.last_contact;
+            }
+            if (ident.w != kFuseNone) {
+                f.callsign_receiver = (uint16_t)((uint32_t)skeys[ident.w] & rmask);
+                __builtin_memcpy(f.callsign, rec[svals[ident.w]].a.callsign, 8);
+            }
+            if (vel.w != kFuseNone) {
+                const adsb_velocity v = rec[svals[vel.w]].vel; // field by field: plain moves keep every bit
+                f.velocity_receiver = (uint16_t)((uint32_t)skeys[vel.w] & rmask);
+                f.velocity_time = v.time;
+                f.speed_kt = v.speed_kt;
+                f.direction_deg = v.direction_deg;
+                f.vertical_rate_fpm = v.vertical_rate_fpm;
+                f.v_ew_kt = v.v_ew_kt;
+                f.v_ns_kt = v.v_ns_kt;
+                f.velocity_subtype = v.subtype;
+                f.velocity_flags = v.flags;
+                f.vrate_baro = v.vrate_baro;
+                f.airspeed_tas = v.airspeed_tas;
+                f.velocity_reserved = v.reserved;
+            }
+            stage[run] = f;
+        }
+    }
+    __syncthreads();
+    const uint32_t pieces = (uint32_t)(n_out - g0 < kRuns ? n_out - g0 : kRuns) * (uint32_t)(sizeof(adsb_fused_aircraft) / 16);
+    const uint4 *src = (const uint4 *)stage;
+    uint4 *dst = (uint4 *)(out + g0); // 128-byte records in hipMalloc'ed memory: 16-byte aligned
+    for (uint32_t i = threadIdx.x; i < pieces; i += 256) dst[i] = src[i];
+}
+
+template <class K>
+hipError_t fuse_sort_scan(void *temp, size_t &sort_bytes, size_t &scan_bytes, const K *keys, K *skeys,
+                          const uint32_t *vals, uint32_t *svals, uint32_t *excl, size_t places, uint32_t rbits,
+                          hipStream_t st)
+{
+    hipError_t e = rocprim::radix_sort_pairs(temp, sort_bytes, keys, skeys, vals, svals, places, 0, 25 + rbits, st);
+    if (e != hipSuccess) return e;
+    const auto heads = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u),
+                                                        FuseHead<K>{skeys, rbits});
+    return rocprim::exclusive_scan(temp, scan_bytes, heads, excl, 0u, places, rocprim::plus<uint32_t>(), st);
+}
+
+template <class K>
+hipError_t launch_fuse(hipStream_t st, const FuseArgs &a)
+{
+    const TrackBankDev b = *a.bank;
+    const uint64_t places = (uint64_t)b.n_receivers * b.max_aircraft;
+    const uint32_t rbits = b.key_bits - 24, blocks = (uint32_t)((places + 255) / 256);
+    K *keys = (K *)a.keys, *skeys = (K *)a.skeys;
+    hipLaunchKernelGGL(fuse_keys_kernel<K>, dim3(blocks), dim3(256), 0, st, b, a.since, rbits, keys, a.vals, places);
+    size_t sort_bytes = a.temp_bytes, scan_bytes = a.temp_bytes;
+    uint32_t *excl = a.vals; // the sort has read vals
+    hipError_t e = fuse_sort_scan<K>(a.temp, sort_bytes, scan_bytes, keys, skeys, a.vals, a.svals, excl, (size_t)places,
+                                     rbits, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(fuse_starts_kernel<K>, dim3(blocks), dim3(256), 0, st, FuseHead<K>{skeys, rbits},
+                       (const uint32_t *)excl, places, a.max_fused, a.seg_start, a.counts);
+    const dim3 grid((uint32_t)((a.max_fused * a.lanes + 255) / 256)); // workgroups past counts[0] leave at once
+#define ADSB_FUSE_REDUCE(G)                                                                                            \
+    hipLaunchKernelGGL((fuse_reduce_kernel<K, G>), grid, dim3(256), 0, st, (const TrackRecord *)b.rec,                 \
+                       (const K *)skeys, (const uint32_t *)a.svals, (const uint32_t *)a.seg_start,                     \
+                       (const uint64_t *)a.counts, rbits, places, a.out)
+    switch (a.lanes) {
+    case 1: ADSB_FUSE_REDUCE(1); break;
+    case 4: ADSB_FUSE_REDUCE(4); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef ADSB_FUSE_REDUCE
+    return hipGetLastError();
+}
+
 } // namespace
 
 size_t track_expire_temp_bytes(size_t n_rec)
@@ -640,6 +853,25 @@ hipError_t launch_track_expire(hipStream_t st, const ExpireArgs &a)
     if ((e = hipMemsetAsync(b.hash, 0, sizeof(unsigned long long) * (b.hash_mask + 1), st)) != hipSuccess) return e;
     hipLaunchKernelGGL(track_bank_rehash_kernel, dim3(blocks), dim3(256), 0, st, t, b, n_rec);
     return hipGetLastError();
+}
+
+size_t track_fuse_temp_bytes(size_t places, uint32_t n_receivers)
+{
+    uint32_t rbits = 0;
+    while ((1u << rbits) < n_receivers) ++rbits;
+    size_t sort_bytes = 0, scan_bytes = 0;
+    if (n_receivers > kFuseWideReceivers)
+        (void)fuse_sort_scan<uint64_t>(nullptr, sort_bytes, scan_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, places,
+                                       rbits, (hipStream_t)0);
+    else
+        (void)fuse_sort_scan<uint32_t>(nullptr, sort_bytes, scan_bytes, nullptr, nullptr, nullptr, nullptr, nullptr, places,
+                                       rbits, (hipStream_t)0);
+    return (sort_bytes > scan_bytes ? sort_bytes : scan_bytes) + 256;
+}
+
+hipError_t launch_track_fuse(hipStream_t st, const FuseArgs &a)
+{
+    return a.bank->n_receivers > kFuseWideReceivers ? launch_fuse<uint64_t>(st, a) : launch_fuse<uint32_t>(st, a);
 }
 
 size_t track_sort_temp_bytes(size_t n)

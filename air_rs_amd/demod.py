@@ -5,6 +5,7 @@ example ``torch.Tensor.data_ptr()``) carry HBM-resident ones.  Frames come back 
 structured array with the adsb_frame layout.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -77,6 +78,13 @@ VELOCITY_DTYPE = np.dtype([("time", "<f8"), ("speed_kt", "<f4"), ("direction_deg
                            ("vertical_rate_fpm", "<i4"), ("v_ew_kt", "<i2"), ("v_ns_kt", "<i2"), ("subtype", "u1"),
                            ("flags", "u1"), ("vrate_baro", "u1"), ("airspeed_tas", "u1"), ("reserved", "<u4")])
 assert VELOCITY_DTYPE.itemsize == C.sizeof(L.AdsbVelocity) == 32
+FUSED_DTYPE = np.dtype([("latitude", "<f8"), ("longitude", "<f8"), ("position_time", "<f8"), ("last_contact", "<f8"),
+                        ("last_heard", "<f8"), ("n_frames", "<u8"), ("icao", "<u4"), ("altitude", "<i4"),
+                        ("n_receivers", "<u2"), ("heard_receiver", "<u2"), ("contact_receiver", "<u2"),
+                        ("position_receiver", "<u2"), ("callsign_receiver", "<u2"), ("velocity_receiver", "<u2"),
+                        ("has_position", "<u4"), ("callsign", "S8"), ("velocity", VELOCITY_DTYPE),
+                        ("reserved", "<u8", (2,))])
+assert FUSED_DTYPE.itemsize == C.sizeof(L.AdsbFusedAircraft) == 128
 
 
 class Tracker:
@@ -602,6 +610,7 @@ class TrackBank:
         h = C.c_void_p()
         L.check(self._lib.adsb_track_bank_create(dem.handle, C.byref(cfg), C.byref(h)), "adsb_track_bank_create")
         self._h, self.n_receivers, self.max_frames = h, int(n_receivers), int(max_frames)
+        self._fuse_reserved = None       # max_fused of the last fuse_reserve
 
     def close(self):
         if getattr(self, "_h", None):
@@ -702,6 +711,44 @@ class TrackBank:
                                                          len(out), C.byref(n)), "adsb_track_bank_fetch_velocity")
         edges = np.concatenate([[0], np.cumsum([len(x) for x in recs])]).astype(np.int64)
         return [out[edges[r]:edges[r + 1]].copy() for r in range(self.n_receivers)]
+
+    def fuse(self, since=-math.inf, max_fused=None):
+        """The fused view: one FUSED_DTYPE record per distinct ICAO over all receivers, ascending ICAO, from the records
+        with last_heard >= since.  Reserves on first use and whenever max_fused changes (None: as reserved before, or
+        n_receivers x max_aircraft), fuses on the device and fetches.  Returns (records, n_total, flags): n_total counts
+        the distinct ICAOs even when they exceed max_fused, and flags then has ADSB_TRACK_FUSED_TRUNCATED."""
+        want = 0 if max_fused is None else int(max_fused)
+        if want < 0:
+            raise ValueError("max_fused must be positive, or None")
+        if self._fuse_reserved is None or (max_fused is not None and want != self._fuse_reserved):
+            self.fuse_reserve(want)
+        L.check(self._lib.adsb_track_bank_fuse(self._h, float(since)), "adsb_track_bank_fuse")
+        n, total, flags = C.c_size_t(), C.c_size_t(), C.c_uint32()
+        L.check(self._lib.adsb_track_bank_fetch_fused(self._h, None, 0, C.byref(n), C.byref(total), C.byref(flags)),
+                "adsb_track_bank_fetch_fused")
+        out = np.zeros(max(total.value, 1), dtype=FUSED_DTYPE)
+        L.check(self._lib.adsb_track_bank_fetch_fused(self._h, out.ctypes.data_as(C.POINTER(L.AdsbFusedAircraft)),
+                                                      len(out), C.byref(n), C.byref(total), C.byref(flags)),
+                "adsb_track_bank_fetch_fused")
+        return out[:n.value].copy(), int(total.value), int(flags.value)
+
+    def fuse_reserve(self, max_fused=0):
+        """adsb_track_bank_fuse_reserve: memory for up to max_fused fused records (0: n_receivers x max_aircraft)."""
+        L.check(self._lib.adsb_track_bank_fuse_reserve(self._h, int(max_fused)), "adsb_track_bank_fuse_reserve")
+        self._fuse_reserved = int(max_fused)
+
+    def fuse_async(self, since=-math.inf):
+        """adsb_track_bank_fuse alone: enqueues the fusion on the ctx stream (after fuse_reserve) and returns."""
+        L.check(self._lib.adsb_track_bank_fuse(self._h, float(since)), "adsb_track_bank_fuse")
+
+    def fused_device(self):
+        """(device address of the fused records, device address of uint64[2]: records written, distinct ICAOs) of the
+        last fuse, for consumers that stay on the GPU; valid on the ctx stream, no synchronisation."""
+        rec, counts = C.c_void_p(), C.c_void_p()
+        L.check(self._lib.adsb_track_bank_fused_device(self._h, C.byref(rec), C.byref(counts)),
+                "adsb_track_bank_fused_device")
+        return rec.value, counts.value
+
 
 
 def packet_new(frame_bytes):

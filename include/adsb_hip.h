@@ -417,6 +417,85 @@ int adsb_track_bank_fetch_last_heard(adsb_track_bank *bank, double *last_heard, 
 int adsb_track_bank_fetch_velocity(adsb_track_bank *bank, adsb_velocity *velocity, size_t max, size_t *n);
 
 /*
+ * The fused view of a bank: ONE picture of what all receivers hear, each aircraft (ICAO address) once, in ascending
+ * ICAO, computed and kept on the device.  A record of receiver r CONTRIBUTES iff it is held (what adsb_track_bank_fetch
+ * would return) and its last_heard >= since (the complement of expire's last_heard < before: fuse(since = t) is
+ * fuse(-INFINITY) after an expire with before[r] = t for every r).  Every quantity of a fused record comes whole from
+ * ONE contributing record, copied bit for bit, never averaged or recomputed; the *_receiver fields name that receiver:
+ *   last_heard:                          the greatest last_heard;
+ *   last_contact, altitude:              the greatest last_contact among records whose last_contact is not NaN;
+ *   latitude, longitude, position_time:  the greatest last_contact among records with has_position.  A record keeps no
+ *                                        time of its fix (its position can be older than its last_contact, when its
+ *                                        newest position message completed no pair), so position_time is that record's
+ *                                        last_contact and is named for what it is;
+ *   callsign:                            among records whose callsign has a non-zero byte, the greatest last_heard (a
+ *                                        record keeps no time of its identification message);
+ *   velocity (the eleven fields from velocity_time to velocity_reserved: an adsb_velocity bit for bit, in its order):
+ *                                        among records with subtype != 0, the greatest time.
+ * Every tie goes to the lowest receiver index; nothing depends on hash placement, atomics or scheduling, so two calls
+ * on the same bank give the same bytes.  n_frames is the sum and n_receivers the count over the contributing records
+ * (n_frames counts receptions: a message heard by three receivers counts three times).  Times of different receivers
+ * are compared as stored, (sample_base[r] + offset) x seconds_per_sample: they are on one clock only if the caller's
+ * sample_base values are.  An even message of one receiver is never paired with an odd one of another.
+ * The bank is only read: no record, size, flag or point changes.  Device memory, all of it allocated by
+ * adsb_track_bank_fuse_reserve and none before: per place of n_receivers x max_aircraft 16 bytes of sort keys and
+ * values (24 with more than 128 receivers) plus rocPRIM's sort scratch (about 8 more), and 132 bytes per record of
+ * max_fused (64 receivers x 65536 aircraft: 64 MiB + 33.75 MiB, and 8.25 MiB for max_fused = 65536: 106 MiB measured;
+ * 626 MiB with max_fused = 0).
+ */
+#define ADSB_FUSED_NONE 0xFFFFu            /* a *_receiver field: no contributing record has that quantity           */
+#define ADSB_TRACK_FUSED_TRUNCATED 0x1u    /* more distinct ICAOs than max_fused: the lowest max_fused ICAOs are kept */
+typedef struct adsb_fused_aircraft {  /* 128 bytes, one per distinct ICAO, ascending ICAO */
+    double   latitude, longitude;     /* of position_receiver's record; 0 unless has_position                        */
+    double   position_time;           /* last_contact of position_receiver's record; NaN unless has_position         */
+    double   last_contact;            /* of contact_receiver's record; NaN if none                                    */
+    double   last_heard;              /* of heard_receiver's record                                                   */
+    uint64_t n_frames;                /* sum of the contributing records' n_frames                                    */
+    uint32_t icao;
+    int32_t  altitude;                /* of contact_receiver's record; 0 if none                                      */
+    uint16_t n_receivers;             /* contributing receivers, 1 .. 256                                             */
+    uint16_t heard_receiver;          /* whose last_heard that is                                                     */
+    uint16_t contact_receiver;        /* whose last_contact and altitude; ADSB_FUSED_NONE                             */
+    uint16_t position_receiver;       /* whose latitude, longitude and position_time; ADSB_FUSED_NONE                 */
+    uint16_t callsign_receiver;       /* whose callsign; ADSB_FUSED_NONE                                              */
+    uint16_t velocity_receiver;       /* whose velocity; ADSB_FUSED_NONE                                              */
+    uint32_t has_position;
+    char     callsign[8];             /* zeros if none                                                                */
+    double   velocity_time;           /* offset 80: adsb_velocity.time (NaN if none) ...                              */
+    float    speed_kt;
+    float    direction_deg;
+    int32_t  vertical_rate_fpm;
+    int16_t  v_ew_kt, v_ns_kt;
+    uint8_t  velocity_subtype;        /* adsb_velocity.subtype; 0 if none (then the flags are 0 and the rest 0 too)   */
+    uint8_t  velocity_flags;          /* adsb_velocity.flags: ADSB_VELOCITY_*                                         */
+    uint8_t  vrate_baro;
+    uint8_t  airspeed_tas;
+    uint32_t velocity_reserved;       /* ... adsb_velocity.reserved, offset 108                                       */
+    uint64_t reserved[2];             /* 0 */
+} adsb_fused_aircraft;
+/* Allocates (or, called again, resizes) what adsb_track_bank_fuse needs for up to max_fused fused records; 0: the worst
+ * case n_receivers x max_aircraft (every record a different ICAO: 512 MiB of output for 64 x 65536, so name a figure).
+ * May wait for the device.  A bank that never reserves allocates nothing and behaves exactly as before.  ADSB_E_ARG for
+ * a NULL bank, ADSB_E_NOMEM if the memory is not to be had (an earlier reserve is then gone too). */
+int adsb_track_bank_fuse_reserve(adsb_track_bank *bank, size_t max_fused);
+/* Computes the fused view of the records with last_heard >= since (-INFINITY: all held records; INFINITY: none).
+ * Asynchronous: one dispatch sequence on the ctx stream after the bank's last update / expire / reset (keys, rocPRIM
+ * radix sort by ICAO then receiver, scan of the ICAO changes, one reduction per ICAO); it never waits for the device
+ * and copies nothing from or to the host.  ADSB_E_ARG for a NULL bank or a NaN since, ADSB_E_STATE without a reserve. */
+int adsb_track_bank_fuse(adsb_track_bank *bank, double since);
+/* Waits; copies min(records written, max) records of the last fuse, ascending ICAO; *n (optional) = records copied,
+ * *n_total (optional) = distinct ICAOs even when they exceed max_fused, *flags (optional) then has
+ * ADSB_TRACK_FUSED_TRUNCATED.  ADSB_E_ARG for a NULL bank, or NULL out with max > 0; ADSB_E_STATE before any fuse
+ * (since the last reserve). */
+int adsb_track_bank_fetch_fused(adsb_track_bank *bank, adsb_fused_aircraft *out, size_t max, size_t *n,
+                                size_t *n_total, uint32_t *flags);
+/* Does not synchronise: device pointers to the fused records and to two words, counts_dev[0] = records written,
+ * counts_dev[1] = distinct ICAOs, both valid on the ctx stream after the last fuse, until the next fuse or reserve.
+ * Either pointer argument may be NULL.  ADSB_E_STATE before any fuse. */
+int adsb_track_bank_fused_device(adsb_track_bank *bank, const adsb_fused_aircraft **fused_dev,
+                                 const uint64_t **counts_dev);
+
+/*
  * ---- several GPUs behind one call ---------------------------------------------------------
  * The reference's thread 2 is one function on one thread (src/adsb.rs:92, spawned at adsb.rs:147); a group is the
  * drop-in for that function when the buffer should be spread over N devices: one context per member, the offsets
