@@ -178,6 +178,16 @@ PROTOTYPES = {
     "adsb_track_bank_fetch_fused": (C.c_int, [C.c_void_p, _P(AdsbFusedAircraft), C.c_size_t, _P(C.c_size_t),
                                               _P(C.c_size_t), _P(C.c_uint32)]),
     "adsb_track_bank_fused_device": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p)]),
+    "adsb_track_table_summaries_reserve": (C.c_int, [C.c_void_p]),
+    "adsb_track_table_fetch_summaries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_summaries_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "adsb_track_table_fetch_changed": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_double), _P(AdsbVelocity), C.c_size_t,
+                                                 _P(C.c_size_t)]),
+    "adsb_track_bank_summaries_reserve": (C.c_int, [C.c_void_p]),
+    "adsb_track_bank_fetch_summaries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_bank_summaries_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "adsb_track_bank_fetch_changed": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_double), _P(AdsbVelocity), C.c_size_t,
+                                                _P(C.c_size_t), _P(C.c_uint64)]),
     "adsb_cpr_num_zones": (C.c_uint32, [C.c_double]),
     "adsb_cpr_position": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P(C.c_double),
                                     _P(C.c_double)]),

@@ -861,6 +861,101 @@ extern "C" int adsb_fetch_track(adsb_ctx *c, adsb_track_point *points, size_t ma
     return ADSB_OK;
 }
 
+// ---- per-frame summaries and the changed list of a table or bank (adsb_track_*_summaries_reserve) -------------------
+// Everything here is allocated by the reserve; `dev.out` null = no reserve.
+struct TrackSummaries {
+    adsbk::TrackSumDev dev{};
+    adsbk::TrackRecord *changed_rec = nullptr; // [changed_cap]: fetch_changed's device-side gather
+    size_t changed_cap = 0;         // min(max_frames, record places): an update cannot touch more aircraft
+    bool updated = false;           // an update ran since the reserve (and since the last reset)
+    bool changed_valid = false;     // the last operation was an update: the changed list's slots still hold
+};
+
+static void track_summaries_free(TrackSummaries &s)
+{
+    for (void *p : {(void *)s.dev.scan, (void *)s.dev.out, (void *)s.dev.changed, (void *)s.dev.n_changed, s.dev.temp,
+                    (void *)s.changed_rec})
+        if (p) (void)hipFree(p);
+    s = TrackSummaries{};
+}
+
+// May wait for the device (hipMalloc); a second reserve keeps what the first one made
+static int track_summaries_reserve(TrackSummaries &s, size_t max_frames, size_t places)
+{
+    if (s.dev.out) return ADSB_OK;
+    s.changed_cap = std::min(max_frames, places);
+    s.dev.temp_bytes = adsbk::track_summaries_temp_bytes(max_frames);
+    const bool ok = hipMalloc((void **)&s.dev.scan, sizeof(adsbk::TrackSumTuple) * max_frames) == hipSuccess &&
+                    hipMalloc((void **)&s.dev.changed, sizeof(uint32_t) * max_frames) == hipSuccess &&
+                    hipMalloc((void **)&s.dev.n_changed, sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc(&s.dev.temp, s.dev.temp_bytes) == hipSuccess &&
+                    hipMalloc((void **)&s.changed_rec, sizeof(adsbk::TrackRecord) * s.changed_cap) == hipSuccess &&
+                    hipMalloc((void **)&s.dev.out, sizeof(adsb_aircraft_record) * max_frames) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        track_summaries_free(s);
+        return ADSB_E_NOMEM;
+    }
+    return ADSB_OK;
+}
+
+// What every update does for the summaries besides handing `dev` to launch_track
+static void track_summaries_mark_update(TrackSummaries &s)
+{
+    if (!s.dev.out) return;
+    s.updated = true;
+    s.changed_valid = true;
+}
+
+// Waits; n_frames: frames of the last update (host-known)
+static int track_summaries_fetch(adsb_ctx *c, TrackSummaries &s, size_t n_frames, adsb_aircraft_record *out, size_t max,
+                                 size_t *n)
+{
+    if (!s.dev.out || !s.updated) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const size_t take = std::min(n_frames, max);
+    if (take) HIPCHK(hipMemcpyAsync(out, s.dev.out, sizeof(adsb_aircraft_record) * take, hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    if (n) *n = n_frames;
+    return ADSB_OK;
+}
+
+// Waits; gathers the changed list's records on the device and copies only them.  rec: the table's / bank's records;
+// counts (optional, [n_receivers]): how many of the records returned belong to each receiver (slot / max_aircraft).
+static int track_summaries_fetch_changed(adsb_ctx *c, TrackSummaries &s, const adsbk::TrackRecord *rec, size_t n_frames,
+                                         uint32_t max_aircraft, uint32_t n_receivers, adsb_aircraft_record *out,
+                                         double *last_heard, adsb_velocity *velocity, size_t max, size_t *n,
+                                         uint64_t *counts)
+{
+    if (!s.dev.out || !s.updated || !s.changed_valid) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (counts) std::fill(counts, counts + n_receivers, (uint64_t)0);
+    uint32_t nc = 0;
+    if (n_frames) { // an empty update launched nothing: its list is empty, and the device word is an older update's
+        const uint32_t most = (uint32_t)std::min(std::min(n_frames, s.changed_cap), max);
+        HIPCHK(adsbk::launch_track_changed(c->aux, rec, s.dev, most, s.changed_rec));
+        HIPCHK(hipMemcpyAsync(&nc, s.dev.n_changed, sizeof(nc), hipMemcpyDeviceToHost, c->aux));
+        HIPCHK(hipStreamSynchronize(c->aux));
+        const size_t take = std::min<size_t>(nc, most);
+        if (take) {
+            std::vector<adsbk::TrackRecord> recs(take);
+            std::vector<uint32_t> slots(take);
+            HIPCHK(hipMemcpyAsync(recs.data(), s.changed_rec, sizeof(adsbk::TrackRecord) * take, hipMemcpyDeviceToHost,
+                                  c->aux));
+            HIPCHK(hipMemcpyAsync(slots.data(), s.dev.changed, sizeof(uint32_t) * take, hipMemcpyDeviceToHost, c->aux));
+            HIPCHK(hipStreamSynchronize(c->aux));
+            for (size_t k = 0; k < take; ++k) {
+                if (out) out[k] = recs[k].a;
+                if (last_heard) last_heard[k] = recs[k].last_heard;
+                if (velocity) velocity[k] = recs[k].vel;
+                if (counts) ++counts[slots[k] / max_aircraft]; // a bank's slot = receiver x max_aircraft + place
+            }
+        }
+    }
+    if (n) *n = nc;
+    return ADSB_OK;
+}
+
 // ---- persistent aircraft table (adsb_track_table_*): the tracker kernels with a TrackTableDev ----------------------
 struct adsb_track_table {
     adsb_ctx *ctx = nullptr;
@@ -879,6 +974,7 @@ struct adsb_track_table {
     size_t exp_temp_bytes = 0;
     uint32_t n_points = 0;
     bool updated = false;
+    TrackSummaries sum;             // adsb_track_table_summaries_reserve
 };
 
 // Records of a table or of one bank receiver (slots in admission order) as fetch returns them: ascending ICAO.
@@ -892,6 +988,7 @@ static void track_table_free(adsb_track_table *t)
 {
     (void)hipSetDevice(t->ctx->cfg.device);
     (void)hipStreamSynchronize(t->ctx->aux);
+    track_summaries_free(t->sum);
     if (t->dev.index) (void)hipFree(t->dev.index);
     if (t->dev.rec) (void)hipFree(t->dev.rec);
     if (t->dev.size_flags) (void)hipFree(t->dev.size_flags);
@@ -916,6 +1013,7 @@ extern "C" int adsb_track_table_reset(adsb_track_table *t)
     HIPCHK(hipMemsetAsync(t->dev.size_flags, 0, sizeof(uint32_t) * 4, t->ctx->aux));
     t->n_points = 0;
     t->updated = false;
+    t->sum.updated = t->sum.changed_valid = false;
     return ADSB_OK;
 }
 
@@ -973,6 +1071,7 @@ extern "C" int adsb_track_table_update(adsb_track_table *t, const adsb_frame *fr
     HIPCHK(hipSetDevice(c->cfg.device));
     t->n_points = (uint32_t)n;
     t->updated = true;
+    track_summaries_mark_update(t->sum); // an empty update: no summaries, an empty changed list
     if (n == 0) return ADSB_OK;
     const adsb_frame *list = frames;
     hipPointerAttribute_t at{};
@@ -1002,8 +1101,38 @@ extern "C" int adsb_track_table_update(adsb_track_table *t, const adsb_frame *fr
     a.temp_bytes = t->temp_bytes;
     a.points = t->points;
     a.table = &t->dev;
+    a.sum = t->sum.dev.out ? &t->sum.dev : nullptr;
     HIPCHK(adsbk::launch_track(c->aux, a)); // after the ctx's ordering pass and field decode (same stream)
     return ADSB_OK;
+}
+
+extern "C" int adsb_track_table_summaries_reserve(adsb_track_table *t)
+{
+    if (!t) return ADSB_E_ARG;
+    HIPCHK(hipSetDevice(t->ctx->cfg.device));
+    return track_summaries_reserve(t->sum, (size_t)t->cfg.max_frames, t->cfg.max_aircraft);
+}
+
+extern "C" int adsb_track_table_fetch_summaries(adsb_track_table *t, adsb_aircraft_record *out, size_t max, size_t *n)
+{
+    if (!t || (!out && max)) return ADSB_E_ARG;
+    return track_summaries_fetch(t->ctx, t->sum, t->n_points, out, max, n);
+}
+
+extern "C" int adsb_track_table_summaries_device(adsb_track_table *t, const adsb_aircraft_record **dev)
+{
+    if (!t) return ADSB_E_ARG;
+    if (!t->sum.dev.out || !t->sum.updated) return ADSB_E_STATE;
+    if (dev) *dev = t->sum.dev.out;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_table_fetch_changed(adsb_track_table *t, adsb_aircraft_record *rec, double *last_heard,
+                                              adsb_velocity *velocity, size_t max, size_t *n)
+{
+    if (!t) return ADSB_E_ARG;
+    return track_summaries_fetch_changed(t->ctx, t->sum, t->dev.rec, t->n_points, t->cfg.max_aircraft, 1, rec,
+                                         last_heard, velocity, max, n, nullptr);
 }
 
 extern "C" int adsb_track_table_fetch_points(adsb_track_table *t, adsb_track_point *points, size_t max_points,
@@ -1053,6 +1182,7 @@ extern "C" int adsb_track_table_expire(adsb_track_table *t, double before)
     a.temp = t->exp_temp;
     a.temp_bytes = t->exp_temp_bytes;
     HIPCHK(adsbk::launch_track_expire(t->ctx->aux, a)); // after the table's last update (same stream)
+    t->sum.changed_valid = false; // slots move
     return ADSB_OK;
 }
 
@@ -1110,6 +1240,7 @@ struct adsb_track_bank {
     size_t exp_temp_bytes = 0;
     uint32_t n_points = 0;
     bool updated = false;
+    TrackSummaries sum;             // adsb_track_bank_summaries_reserve
     // the fused view (adsb_track_bank_fuse_*): all of it allocated by fuse_reserve, nothing before
     void *fuse_keys = nullptr;      // 2 x [places] sort keys (uint32_t, uint64_t above kFuseWideReceivers): in, sorted
     uint32_t *fuse_vals = nullptr;  // 2 x [places]: places in, sorted
@@ -1141,6 +1272,7 @@ static void track_bank_free(adsb_track_bank *b)
     (void)hipSetDevice(b->ctx->cfg.device);
     (void)hipStreamSynchronize(b->ctx->aux);
     track_bank_fuse_free(b);
+    track_summaries_free(b->sum);
     for (void *p : {(void *)b->dev.hash, (void *)b->dev.rec, (void *)b->words, (void *)b->dev.prefix, (void *)b->meta,
                     (void *)b->dev.mark, (void *)b->dev.excl, (void *)b->dev.seg_slot, (void *)b->tab.slot,
                     (void *)b->u32, b->temp, (void *)b->frames, (void *)b->fields, (void *)b->points,
@@ -1160,6 +1292,7 @@ extern "C" int adsb_track_bank_reset(adsb_track_bank *b)
     HIPCHK(hipMemsetAsync(b->words, 0, sizeof(uint32_t) * 3 * b->cfg.n_receivers, b->ctx->aux));
     b->n_points = 0;
     b->updated = false;
+    b->sum.updated = b->sum.changed_valid = false;
     return ADSB_OK;
 }
 
@@ -1258,6 +1391,7 @@ static int track_bank_run(adsb_track_bank *b, const adsb_frame *list, uint32_t n
     a.points = b->points;
     a.table = &b->tab;
     a.bank = &dev;
+    a.sum = b->sum.dev.out ? &b->sum.dev : nullptr;
     HIPCHK(adsbk::launch_track(c->aux, a));
     return ADSB_OK;
 }
@@ -1301,6 +1435,7 @@ extern "C" int adsb_track_bank_update(adsb_track_bank *b, const adsb_frame *fram
     HIPCHK(hipSetDevice(c->cfg.device));
     b->n_points = (uint32_t)n;
     b->updated = true;
+    track_summaries_mark_update(b->sum); // an empty update: no summaries, an empty changed list
     if (n == 0) return ADSB_OK;
     hipPointerAttribute_t at{};
     const bool on_device = hipPointerGetAttributes(&at, frames) == hipSuccess && at.type == hipMemoryTypeDevice &&
@@ -1324,6 +1459,7 @@ extern "C" int adsb_track_bank_update_launch(adsb_track_bank *b, const uint64_t 
     HIPCHK(hipSetDevice(c->cfg.device));
     b->n_points = (uint32_t)n;
     b->updated = true;
+    track_summaries_mark_update(b->sum); // an empty update: no summaries, an empty changed list
     if (n == 0) return ADSB_OK;
     if ((rc = track_bank_stage(b, nullptr, sample_base, nullptr, 0)) != ADSB_OK) return rc;
     adsb_ctx::ResultSet &r = c->rs[c->last];
@@ -1398,7 +1534,38 @@ extern "C" int adsb_track_bank_expire(adsb_track_bank *b, const double *before)
     a.temp = b->exp_temp;
     a.temp_bytes = b->exp_temp_bytes;
     HIPCHK(adsbk::launch_track_expire(b->ctx->aux, a)); // after the bank's last update (same stream)
+    b->sum.changed_valid = false; // slots move
     return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_summaries_reserve(adsb_track_bank *b)
+{
+    if (!b) return ADSB_E_ARG;
+    HIPCHK(hipSetDevice(b->ctx->cfg.device));
+    return track_summaries_reserve(b->sum, (size_t)b->cfg.max_frames, (size_t)b->cfg.n_receivers * b->cfg.max_aircraft);
+}
+
+extern "C" int adsb_track_bank_fetch_summaries(adsb_track_bank *b, adsb_aircraft_record *out, size_t max, size_t *n)
+{
+    if (!b || (!out && max)) return ADSB_E_ARG;
+    return track_summaries_fetch(b->ctx, b->sum, b->n_points, out, max, n);
+}
+
+extern "C" int adsb_track_bank_summaries_device(adsb_track_bank *b, const adsb_aircraft_record **dev)
+{
+    if (!b) return ADSB_E_ARG;
+    if (!b->sum.dev.out || !b->sum.updated) return ADSB_E_STATE;
+    if (dev) *dev = b->sum.dev.out;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_fetch_changed(adsb_track_bank *b, adsb_aircraft_record *rec, double *last_heard,
+                                             adsb_velocity *velocity, size_t max, size_t *n,
+                                             uint64_t *per_receiver_counts)
+{
+    if (!b) return ADSB_E_ARG;
+    return track_summaries_fetch_changed(b->ctx, b->sum, b->dev.rec, b->n_points, b->cfg.max_aircraft,
+                                         b->cfg.n_receivers, rec, last_heard, velocity, max, n, per_receiver_counts);
 }
 
 // Waits; out[k] = get(record k) for the records in the order of adsb_track_bank_fetch; *n = records held in total

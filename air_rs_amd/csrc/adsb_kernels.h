@@ -208,6 +208,22 @@ struct TrackBankDev {
     unsigned long long *excl;    // [n] exclusive scan of mark
     uint32_t *seg_slot;          // [n] per segment (hi of the scan): record slot + 1 (kTrackUntracked)
 };
+// Per-frame summaries and the changed list of a table / bank update (adsb_track_*_summaries_reserve): all of it
+// allocated by the reserve.  One segmented inclusive max-scan over the sorted list gives every frame the sorted
+// position + 1 (0 = none in its segment so far) of its segment's head and of the last identification message,
+// position message and frame with a new position at or before it; cnt is a plain running sum of the segment heads
+// the table tracks, which ranks the changed list.
+struct TrackSumTuple {
+    uint32_t head, id, pos, fix, cnt;
+};
+struct TrackSumDev {
+    TrackSumTuple *scan;         // [max_frames]: the scan's output, sorted order
+    adsb_aircraft_record *out;   // [max_frames]: one summary per frame of the last update, list order
+    uint32_t *changed;           // [max_frames]: record slot of every tracked segment, sorted order (= ascending ICAO)
+    uint32_t *n_changed;         // device word: how many of them
+    void *temp;                  // the scan's scratch
+    size_t temp_bytes;
+};
 struct TrackArgs {
     const adsb_frame *frames;
     const adsb_packet_fields *fields;
@@ -225,6 +241,7 @@ struct TrackArgs {
                                  // otherwise pair with and merge into the persistent table (adsb_track_table_update)
     const TrackBankDev *bank;    // non-null: the list holds several receivers' frames (adsb_track_bank_update); `table`
                                  // then carries the bank's records in rec and the per-frame slot scratch in slot
+    const TrackSumDev *sum;      // non-null (table / bank only): also the per-frame summaries and the changed list
 };
 // expire (adsb_track_table_expire / adsb_track_bank_expire): a record survives unless last_heard < before[receiver]
 constexpr uint32_t kMaxReceivers = 256;
@@ -244,6 +261,10 @@ hipError_t launch_track_expire(hipStream_t s, const ExpireArgs &a);
 size_t track_sort_temp_bytes(size_t n);
 size_t track_bank_temp_bytes(size_t n); // the bank's sort (32 bits) and 64-bit scan
 hipError_t launch_track(hipStream_t s, const TrackArgs &a);
+size_t track_summaries_temp_bytes(size_t n);
+// out[k] = rec[sum.changed[k]] for k < min(*sum.n_changed, max_n): the changed list's records, gathered on the device
+hipError_t launch_track_changed(hipStream_t s, const TrackRecord *rec, const TrackSumDev &sum, uint32_t max_n,
+                                TrackRecord *out);
 
 // the fused view of a bank (adsb_track_bank_fuse): every receiver's contributing records sorted by ICAO then receiver
 // and reduced to one adsb_fused_aircraft per ICAO; reads the bank only

@@ -57,6 +57,15 @@
 // quantity, the record with the greatest time (ties: the lowest sorted position = the lowest receiver), and the
 // workgroup writes its 128-byte output records once, through LDS.  All sizes are device words; the total and the
 // truncation flag are published by the last thread of the kernel that stores the run starts.
+//
+// Per-frame summaries and the changed list (adsb_track_*_summaries_reserve; a table or bank that reserved): what the
+// reference's web thread broadcasts, the packet's aircraft as it stands right after every packet (web.rs:117-128).
+// Between 2. and 3. (3. overwrites the record the summaries start from): one segmented inclusive max-scan over the
+// sorted list (rocPRIM, a 20-byte tuple computed by a transform iterator) gives every frame the sorted position of its
+// segment's head and of the last identification message, position message and new position at or before it, plus its
+// segment's rank among the tracked ones; one thread per frame then builds the 48-byte summary from at most three source
+// frames and the pre-update record, with 3.'s expressions, and stores it at the frame's list index; segment tails
+// write their record slot at their rank (the changed list).  Linear in the list however long one aircraft's part is.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -537,6 +546,119 @@ __global__ __launch_bounds__(256) void track_summary_kernel(const adsb_frame *fr
     }
 }
 
+// ---- per-frame summaries and the changed list (table / bank with a summaries reserve) -----------------------------
+// The scan's input at sorted position s, computed where the scan loads it (no tuple buffer, no kernel of its own):
+// s + 1 in every component that frame s "writes", by the merge's own tests.  Frames of an aircraft the table turned
+// away write nothing and are not counted.
+struct SumInput {
+    const uint32_t *skeys, *svals, *slot;
+    const adsb_packet_fields *fields;
+    const adsb_track_point *points;
+    __device__ __forceinline__ TrackSumTuple operator()(uint32_t s) const
+    {
+        const bool head = s == 0 || skeys[s - 1] != skeys[s];
+        const bool tracked = slot[s] != kTrackUntracked;
+        const uint32_t i = svals[s], kind = fields[i].msg_kind, at = tracked ? s + 1u : 0u;
+        TrackSumTuple v;
+        v.head = head ? s + 1u : 0u;
+        v.id = kind == 0 ? at : 0u;                                                       // aircraft.rs:105-107
+        v.pos = kind == 1 ? at : 0u;                                                      // aircraft.rs:55-56
+        v.fix = (kind == 1 && (points[i].flags & ADSB_TRACK_NEW_POSITION)) ? at : 0u;     // aircraft.rs:97-102
+        v.cnt = (head && tracked) ? 1u : 0u;
+        return v;
+    }
+};
+
+// Segmented max: a right operand that holds a segment head starts over (its components are those of its last
+// segment); otherwise the left head stays and the later writer wins.  Associative, so the scan's result does not depend
+// on how rocPRIM groups the operands; cnt is summed across segments.
+struct SumOp {
+    __device__ __forceinline__ TrackSumTuple operator()(const TrackSumTuple &l, const TrackSumTuple &r) const
+    {
+        TrackSumTuple o = r;
+        if (!r.head) {
+            o.head = l.head;
+            o.id = l.id > r.id ? l.id : r.id;
+            o.pos = l.pos > r.pos ? l.pos : r.pos;
+            o.fix = l.fix > r.fix ? l.fix : r.fix;
+        }
+        o.cnt = l.cnt + r.cnt;
+        return o;
+    }
+};
+
+// One thread per sorted frame s, after the scan and BEFORE the merge (t.rec[slot] still is the record from before this
+// update; admission wrote empty_record for a new aircraft): the aircraft as Aircraft::handle_packet leaves it after
+// frame s, from at most three source frames and that record, with the merge's expressions, stored at the frame's list
+// index.  A segment tail also puts its record slot on the changed list at its rank.
+template <bool kBank>
+__global__ __launch_bounds__(256) void track_frame_summary_kernel(const adsb_frame *frames,
+                                                                  const adsb_packet_fields *fields,
+                                                                  const adsb_track_point *points, const uint32_t *skeys,
+                                                                  const uint32_t *svals, uint32_t n,
+                                                                  double seconds_per_sample, uint64_t sample_base,
+                                                                  TrackTableDev t, TrackBankDev b, TrackSumDev sum)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s], i = svals[s], slot = t.slot[s];
+    const uint32_t icao = kBank ? key & 0xFFFFFFu : key;
+    if (kBank) sample_base = b.sample_base[key >> 24];
+    const TrackSumTuple w = sum.scan[s];
+    if (s + 1 == n) *sum.n_changed = w.cnt;
+    adsb_aircraft_record r;
+    if (slot == kTrackUntracked) {
+        r = empty_record(icao).a;
+    } else {
+        r = t.rec[slot - 1].a;
+        r.icao = icao;
+        if (w.id) {
+            const adsb_packet_fields g = fields[svals[w.id - 1]];
+            for (int k = 0; k < 8; ++k) r.callsign[k] = g.callsign[k];
+        }
+        if (w.pos) {
+            const uint32_t j = svals[w.pos - 1];
+            r.altitude = fields[j].altitude;
+            r.last_contact = frame_time(frames, j, sample_base, seconds_per_sample);
+        }
+        if (w.fix) {
+            const uint32_t j = svals[w.fix - 1];
+            r.has_position = 1;
+            r.latitude = points[j].latitude;
+            r.longitude = points[j].longitude;
+        }
+        r.n_frames += s + 2u - w.head; // w.head - 1 = the segment's first sorted position
+        if (s + 1 == n || skeys[s + 1] != key) sum.changed[w.cnt - 1] = slot - 1; // a tracked segment: cnt >= 1
+    }
+    sum.out[i] = r;
+}
+
+// the changed list's records, eight lanes per 128-byte record
+__global__ __launch_bounds__(256) void track_changed_gather_kernel(const TrackRecord *rec, const uint32_t *changed,
+                                                                   const uint32_t *n_changed, uint32_t max_n,
+                                                                   TrackRecord *out)
+{
+    const uint32_t g = (blockIdx.x * blockDim.x + threadIdx.x) >> 3, lane = threadIdx.x & 7u;
+    const uint32_t nc = *n_changed;
+    if (g >= (nc < max_n ? nc : max_n)) return;
+    ((uint4 *)(out + g))[lane] = ((const uint4 *)(rec + changed[g]))[lane];
+}
+
+template <bool kBank>
+hipError_t launch_frame_summaries(hipStream_t st, const TrackArgs &a, const TrackTableDev &t, const TrackBankDev &b)
+{
+    const TrackSumDev &sum = *a.sum;
+    const auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u),
+                                                     SumInput{a.skeys, a.svals, t.slot, a.fields, a.points});
+    size_t tb = sum.temp_bytes;
+    hipError_t e = rocprim::inclusive_scan(sum.temp, tb, in, sum.scan, (size_t)a.n, SumOp(), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(track_frame_summary_kernel<kBank>, dim3((a.n + 255) / 256), dim3(256), 0, st, a.frames, a.fields,
+                       (const adsb_track_point *)a.points, (const uint32_t *)a.skeys, (const uint32_t *)a.svals, a.n,
+                       a.seconds_per_sample, kBank ? (uint64_t)0 : a.sample_base, t, b, sum);
+    return hipSuccess;
+}
+
 // expire, 1: keep[g] = 1 for a record in use whose last frame is not older than the cut (last_heard < before evicts).
 // Record g is slot i of receiver r (a table: r = 0).  Slot 0 stages the old size where the compaction kernel reads it
 // (size_flags[3] / size_next[r]), since that kernel writes the new one.
@@ -895,6 +1017,24 @@ size_t track_bank_temp_bytes(size_t n)
     return (sort_bytes > scan_bytes ? sort_bytes : scan_bytes) + 256;
 }
 
+size_t track_summaries_temp_bytes(size_t n)
+{
+    size_t scan_bytes = 0;
+    (void)rocprim::inclusive_scan(nullptr, scan_bytes, (const TrackSumTuple *)nullptr, (TrackSumTuple *)nullptr, n,
+                                  SumOp(), (hipStream_t)0);
+    return scan_bytes + 256;
+}
+
+hipError_t launch_track_changed(hipStream_t st, const TrackRecord *rec, const TrackSumDev &sum, uint32_t max_n,
+                                TrackRecord *out)
+{
+    if (max_n == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)max_n * 8 + 255) / 256); // eight lanes per record
+    hipLaunchKernelGGL(track_changed_gather_kernel, dim3(blocks), dim3(256), 0, st, rec, (const uint32_t *)sum.changed,
+                       (const uint32_t *)sum.n_changed, max_n, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_track(hipStream_t st, const TrackArgs &a)
 {
     if (a.n == 0) return a.table ? hipSuccess : hipMemsetAsync(a.n_aircraft, 0, sizeof(uint64_t), st);
@@ -919,6 +1059,7 @@ hipError_t launch_track(hipStream_t st, const TrackArgs &a)
                            (const uint32_t *)t.slot);
         hipLaunchKernelGGL(track_pairs_kernel<true>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.skeys,
                            a.svals, n, a.seconds_per_sample, (uint64_t)0, t, b, a.points, (uint32_t *)nullptr);
+        if (a.sum && (e = launch_frame_summaries<true>(st, a, t, b)) != hipSuccess) return e; // before the merge
         hipLaunchKernelGGL(track_summary_kernel<true>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.points,
                            a.skeys, a.svals, (const uint32_t *)nullptr, (const uint32_t *)nullptr, n,
                            a.seconds_per_sample, (uint64_t)0, t, b, (adsb_aircraft_record *)nullptr, 0u,
@@ -940,6 +1081,7 @@ hipError_t launch_track(hipStream_t st, const TrackArgs &a)
         hipLaunchKernelGGL(track_admit_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, a.keys, a.vals, t);
         hipLaunchKernelGGL(track_pairs_kernel<false>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.skeys,
                            a.svals, n, a.seconds_per_sample, a.sample_base, t, b, a.points, (uint32_t *)nullptr);
+        if (a.sum && (e = launch_frame_summaries<false>(st, a, t, b)) != hipSuccess) return e; // before the merge
         hipLaunchKernelGGL(track_summary_kernel<false>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.points,
                            a.skeys, a.svals, (const uint32_t *)nullptr, (const uint32_t *)nullptr, n,
                            a.seconds_per_sample, a.sample_base, t, b, (adsb_aircraft_record *)nullptr, 0u,

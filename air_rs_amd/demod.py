@@ -597,6 +597,51 @@ class TrackTable:
                                                           len(out), C.byref(n)), "adsb_track_table_fetch_velocity")
         return out[:n.value].copy()
 
+    def summaries_reserve(self):
+        """adsb_track_table_summaries_reserve: from now on every update also leaves one summary per frame and the
+        changed list on the device."""
+        L.check(self._lib.adsb_track_table_summaries_reserve(self._h), "adsb_track_table_summaries_reserve")
+
+    def summaries(self):
+        """One AIRCRAFT_DTYPE record per frame of the last update, in its order: the frame's aircraft as it stands
+        right after that frame (what the reference's web thread broadcasts per packet)."""
+        return _fetch_summaries(self._lib.adsb_track_table_fetch_summaries, self._h, "adsb_track_table_fetch_summaries")
+
+    def summaries_device(self):
+        """Device address of the last update's summaries; valid on the ctx stream, no synchronisation."""
+        dev = C.c_void_p()
+        L.check(self._lib.adsb_track_table_summaries_device(self._h, C.byref(dev)), "adsb_track_table_summaries_device")
+        return dev.value
+
+    def changed(self):
+        """(records, last_heard, velocity) of the aircraft the last update touched, ascending ICAO: the matching rows
+        of aircraft()[0], last_heard() and velocity(), without copying the table."""
+        return _fetch_changed(self._lib.adsb_track_table_fetch_changed, self._h, "adsb_track_table_fetch_changed")[:3]
+
+
+def _fetch_summaries(fn, handle, where):
+    n = C.c_size_t()
+    L.check(fn(handle, None, 0, C.byref(n)), where)
+    out = np.zeros(max(n.value, 1), dtype=AIRCRAFT_DTYPE)
+    L.check(fn(handle, out.ctypes.data, len(out), C.byref(n)), where)
+    return out[:n.value].copy()
+
+
+def _fetch_changed(fn, handle, where, n_receivers=None):
+    """(records, last_heard, velocity, per-receiver counts or None) of adsb_track_{table,bank}_fetch_changed"""
+    n = C.c_size_t()
+    extra = () if n_receivers is None else (None,)
+    L.check(fn(handle, None, None, None, 0, C.byref(n), *extra), where)
+    size = max(n.value, 1)
+    recs, heard = np.zeros(size, dtype=AIRCRAFT_DTYPE), np.zeros(size, dtype=np.float64)
+    vel = np.zeros(size, dtype=VELOCITY_DTYPE)
+    counts = None if n_receivers is None else (C.c_uint64 * n_receivers)()
+    L.check(fn(handle, recs.ctypes.data, heard.ctypes.data_as(C.POINTER(C.c_double)),
+               vel.ctypes.data_as(C.POINTER(L.AdsbVelocity)), size, C.byref(n), *(() if counts is None else (counts,))),
+            where)
+    return (recs[:n.value].copy(), heard[:n.value].copy(), vel[:n.value].copy(),
+            None if counts is None else [int(x) for x in counts])
+
 
 class TrackBank:
     """adsb_track_bank_*: n_receivers independent aircraft tables on the device (one HashMap<u32, Aircraft> per
@@ -749,6 +794,27 @@ class TrackBank:
                 "adsb_track_bank_fused_device")
         return rec.value, counts.value
 
+    def summaries_reserve(self):
+        """adsb_track_bank_summaries_reserve: from now on every update also leaves one summary per frame and the
+        changed list on the device."""
+        L.check(self._lib.adsb_track_bank_summaries_reserve(self._h), "adsb_track_bank_summaries_reserve")
+
+    def summaries(self):
+        """One AIRCRAFT_DTYPE record per frame of the last update, in its list order (receiver 0's frames first): the
+        frame's aircraft on its receiver as it stands right after that frame."""
+        return _fetch_summaries(self._lib.adsb_track_bank_fetch_summaries, self._h, "adsb_track_bank_fetch_summaries")
+
+    def summaries_device(self):
+        """Device address of the last update's summaries; valid on the ctx stream, no synchronisation."""
+        dev = C.c_void_p()
+        L.check(self._lib.adsb_track_bank_summaries_device(self._h, C.byref(dev)), "adsb_track_bank_summaries_device")
+        return dev.value
+
+    def changed(self):
+        """(records, last_heard, velocity, per-receiver counts) of the aircraft the last update touched: receiver 0's in
+        ascending ICAO, then receiver 1's, ...; rows of aircraft(), last_heard() and velocity()."""
+        return _fetch_changed(self._lib.adsb_track_bank_fetch_changed, self._h, "adsb_track_bank_fetch_changed",
+                              self.n_receivers)
 
 
 def packet_new(frame_bytes):

@@ -496,6 +496,60 @@ int adsb_track_bank_fused_device(adsb_track_bank *bank, const adsb_fused_aircraf
                                  const uint64_t **counts_dev);
 
 /*
+ * Per-frame summaries and the changed list: what the reference's web thread emits.  It calls handle_aircraft_update for
+ * every packet and broadcasts that aircraft's AircraftSummary as it stands right after that packet (src/adsb/web.rs:
+ * 117-128, aircraft.rs:141-149,158-165).  With a reserve, every update of a table or bank also leaves, on the device,
+ *   (1) one adsb_aircraft_record per frame of that update, in its list order (the order of fetch_points): the frame's
+ *       aircraft as Aircraft::handle_packet (aircraft.rs:48-111) leaves it after that frame, starting from the record
+ *       the table held before the update (an empty one for an aircraft this update admits, also after an expire):
+ *         callsign:                of the last identification message at or before the frame, else the record's;
+ *         altitude, last_contact:  of the last position message at or before it, else the record's;
+ *         latitude, longitude, has_position: of the last frame at or before it whose point has
+ *                                  ADSB_TRACK_NEW_POSITION, else the record's;
+ *         n_frames:                the record's count plus the aircraft's frames of this update up to and including it;
+ *       a frame whose point is ADSB_TRACK_UNTRACKED gets its icao and otherwise an empty record (zeros, last_contact
+ *       NaN, n_frames 0).  The expressions are the merge's, so bit for bit: the summary at an aircraft's last frame of
+ *       an update is its record as fetch returns it after the update; a list cut into any sequence of updates gives,
+ *       concatenated, the summaries of one update; receiver r's part of a bank's equals a table's of its own;
+ *   (2) the changed list: the record slots of the distinct aircraft the update applied at least one frame to (UNTRACKED
+ *       ones excluded), in ascending ICAO (bank: receiver 0's, then receiver 1's, ...), and their number.
+ * Both come from one more scan over the sorted list (a segmented maximum of "sorted position of the last writer" per
+ * quantity, rocPRIM) and one kernel with a thread per frame, between the pairs step and the merge: linear in the list
+ * however long one aircraft's part is, no atomics, two runs give the same bytes.  Asynchronous on the ctx stream like
+ * the rest of the update.  Device memory, all of it allocated by the reserve and none before: 72 bytes per frame of
+ * max_frames (48 of summary, 20 of scan values, 4 of changed list) plus rocPRIM's scan scratch, and 128 bytes per
+ * record of min(max_frames, max_aircraft x receivers) for fetch_changed's gather.  A table or bank that never reserves
+ * allocates nothing, launches exactly the kernels it launched before and behaves as before.
+ */
+/* Allocates the above; from then on every update also computes the summaries and the changed list.  May wait for the
+ * device.  A second reserve changes nothing.  ADSB_E_ARG for a NULL table, ADSB_E_NOMEM if the memory is not to be
+ * had. */
+int adsb_track_table_summaries_reserve(adsb_track_table *table);
+/* Waits; copies min(*n, max) summaries of the LAST update, *n (optional) = its frames.  ADSB_E_STATE without a reserve,
+ * or before any update since the reserve or the last reset; ADSB_E_ARG for a NULL table, or NULL out with max > 0.
+ * Like fetch_points, a later expire does not change what it returns. */
+int adsb_track_table_fetch_summaries(adsb_track_table *table, adsb_aircraft_record *out, size_t max, size_t *n);
+/* Does not synchronise: the device address of the summaries, valid on the ctx stream after the last update until the
+ * next one (as many as that update had frames).  Same ADSB_E_STATE / ADSB_E_ARG rules; dev may be NULL. */
+int adsb_track_table_summaries_device(adsb_track_table *table, const adsb_aircraft_record **dev);
+/* Waits; the aircraft the last update touched, ascending ICAO, each with its record, last-heard time and velocity
+ * exactly as adsb_track_table_fetch, _fetch_last_heard and _fetch_velocity would return for it now, byte for byte; any
+ * of the three arrays may be NULL; min(*n, max) entries are written, *n (optional) = how many there are.  The records
+ * are gathered on the device and only they are copied (the table is neither copied nor sorted).  Valid while the last
+ * operation on the table was that update: ADSB_E_STATE after an expire or reset (slots move) until the next update,
+ * and without a reserve or an update since it.  ADSB_E_ARG for a NULL table. */
+int adsb_track_table_fetch_changed(adsb_track_table *table, adsb_aircraft_record *rec, double *last_heard,
+                                   adsb_velocity *velocity, size_t max, size_t *n);
+/* The same for a bank: summaries in the update's list order (receiver 0's frames, then receiver 1's, ...), the changed
+ * list receiver by receiver, each in ascending ICAO; per_receiver_counts[n_receivers] (optional) = entries of each
+ * receiver among those written. */
+int adsb_track_bank_summaries_reserve(adsb_track_bank *bank);
+int adsb_track_bank_fetch_summaries(adsb_track_bank *bank, adsb_aircraft_record *out, size_t max, size_t *n);
+int adsb_track_bank_summaries_device(adsb_track_bank *bank, const adsb_aircraft_record **dev);
+int adsb_track_bank_fetch_changed(adsb_track_bank *bank, adsb_aircraft_record *rec, double *last_heard,
+                                  adsb_velocity *velocity, size_t max, size_t *n, uint64_t *per_receiver_counts);
+
+/*
  * ---- several GPUs behind one call ---------------------------------------------------------
  * The reference's thread 2 is one function on one thread (src/adsb.rs:92, spawned at adsb.rs:147); a group is the
  * drop-in for that function when the buffer should be spread over N devices: one context per member, the offsets

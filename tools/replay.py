@@ -6,12 +6,21 @@
   tools/replay.py capture.bin --format u8     # raw rtl_sdr capture (unsigned bytes)
   tools/replay.py capture.c16 --carry --tail  # also decode frames straddling buffers and the last chunk
   tools/replay.py capture.c16 --aircraft      # the final aircraft table instead (tui.rs:65-95, Velocity filled)
+  tools/replay.py capture.c16 --web           # what the web thread broadcasts instead: one JSON line per packet
 
 Everything below the argument parsing is one call through the C ABI (adsb_replay_file, include/adsb_host.h).
 The "Processed Time" line carries no value (the reference prints the wall clock there).  With --aircraft, the frames
 go through one device track table (2 MSPS, one update) and the table is printed tab-separated with the columns of
-the reference's TUI; its Velocity column, always "n/a" there, holds the last airborne-velocity message's speed."""
+the reference's TUI; its Velocity column, always "n/a" there, holds the last airborne-velocity message's speed.
+With --web, the frames go through one device track table with a summaries reserve, one update per buffer, and every
+frame's summary is printed as one JSON line: the reference's serialisation of AircraftSummary (aircraft.rs:14-23,
+cpr.rs:10-16, camelCase), which its web thread sends for every packet (web.rs:117-128).  lastContact is whole seconds
+of frame time (0 when the aircraft has had no position message): the reference stamps the wall clock there.  Floats
+are printed with Python's shortest round-trip repr.  The TEXT has not been compared with a Rust build's (there is no
+Rust toolchain); only the values are checked, against the oracle."""
 import argparse
+import json
+import math
 import os
 import sys
 
@@ -46,6 +55,35 @@ def aircraft_table(d, frames, n_samples):
     return "ICAO\tCallsign\tAltitude\tLatitude\tLongitude\tVelocity\tAge\n" + "".join(r[2] + "\n" for r in rows)
 
 
+def summary_json(rec):
+    """One summaries() record as the reference's AircraftSummary JSON (key order of the struct)."""
+    contact = float(rec["last_contact"])
+    return json.dumps({
+        "icao": int(rec["icao"]),
+        "callsign": rec["callsign"].decode("latin-1"),           # S8: trailing NULs already stripped
+        "altitude": int(rec["altitude"]),
+        "geoPosition": {"latitude": float(rec["latitude"]), "longitude": float(rec["longitude"])}
+        if rec["has_position"] else None,
+        "lastContact": 0 if math.isnan(contact) else int(contact)}, separators=(",", ":"))
+
+
+def web_stream(d, frames, chunk):
+    """One JSON line per frame: the frame's aircraft right after it, one table update per buffer of `chunk` samples."""
+    lines = []
+    with A.TrackTable(d, max_frames=max(len(frames), 1), seconds_per_sample=SECONDS_PER_SAMPLE) as t:
+        t.summaries_reserve()
+        a = 0
+        while a < len(frames):
+            buf = int(frames[a]["offset"]) // chunk
+            b = a
+            while b < len(frames) and int(frames[b]["offset"]) // chunk == buf:
+                b += 1
+            t.update(frames[a:b])
+            lines.extend(summary_json(rec) for rec in t.summaries())
+            a = b
+    return "".join(line + "\n" for line in lines)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("file")
@@ -56,6 +94,7 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--summary", action="store_true", help="print counts to stderr")
     ap.add_argument("--aircraft", action="store_true", help="print the final aircraft table instead of the stream text")
+    ap.add_argument("--web", action="store_true", help="print one AircraftSummary JSON line per packet instead")
     a = ap.parse_args()
     fmt = a.format or ("c16" if a.file.endswith(".c16") else "u8")
     st = A.ADSB_SAMPLE_I16 if fmt == "c16" else A.ADSB_SAMPLE_I8
@@ -67,6 +106,8 @@ def main():
                                                     max_frames=max(n_max // 200, 1 << 16))
         if a.aircraft:
             text = aircraft_table(d, frames, n_samp)
+        elif a.web:
+            text = web_stream(d, frames, a.chunk)
     sys.stdout.write(text)
     if a.summary:
         print(f"{n_samp} samples, {n_buf} buffers of {a.chunk}, {len(frames)} packets", file=sys.stderr)
