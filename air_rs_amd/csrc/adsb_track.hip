@@ -140,6 +140,11 @@ __global__ __launch_bounds__(256) void track_keys_kernel(const adsb_packet_field
 __device__ __forceinline__ double frame_time(const adsb_frame *frames, uint32_t i, uint64_t sample_base,
                                              double seconds_per_sample)
 {
+    // the header's t, one ROUNDED product.  Contraction is off for this multiply (hipcc contracts by default, and here
+    // __dmul_rn is a plain product that contracts too): inlined into fabs(t_i - t_j) > 10.0 it would otherwise become
+    // fma(-x_j, sps, t_i) with x_j * sps unrounded, which calls about half of the pairs that are exactly 10 s apart
+    // at 0.5e-6 s per sample too old, while the record fallback, the oracle and the host mirror accept them
+#pragma clang fp contract(off)
     return (double)(sample_base + frames[i].offset) * seconds_per_sample;
 }
 

@@ -269,8 +269,13 @@ int adsb_fetch_track(adsb_ctx *ctx, adsb_track_point *points, size_t max_points,
  * cutting one list into any sequence of updates gives the same points and the same final table, and one update
  * on an empty table gives what adsb_track_device gives on the same list.  Packet time = (sample_base + frame
  * offset) x seconds_per_sample: with a feed in per-buffer mode (carry = 0) sample_base is adsb_feed_pop's
- * *first_sample; with carry = 1 (absolute offsets) it is 0.  One table per receiver (an update takes one ordered
- * list).  Aircraft stay until adsb_track_table_expire evicts them (the reference's map is unbounded and never does;
+ * *first_sample; with carry = 1 (absolute offsets) it is 0.  That time is ONE f64 value, the u64 sum converted to
+ * f64 and multiplied once, each step rounded to nearest; the 10 s window compares two such rounded times
+ * (too old iff |t_i - t_j| > 10.0, aircraft.rs:68-70), whether the partner is in the same update or in the table
+ * from an earlier one, so at any sample period (0.5e-6 as well as 2^-20) partners exactly round(10 /
+ * seconds_per_sample) samples apart pair wherever that difference of rounded products is not above 10.0, and every
+ * cut of a list gives the same bytes at that boundary too.  Frames with equal offsets are applied in list order.
+ * One table per receiver (an update takes one ordered list).  Aircraft stay until adsb_track_table_expire evicts them (the reference's map is unbounded and never does;
  * this one has max_aircraft places) or until reset.  The table costs 64 MiB of device memory for its ICAO index plus
  * 136 bytes per aircraft of max_aircraft (a 128-byte record and 8 bytes of expire scratch) and about 100 bytes per
  * frame of max_frames.  The ctx must outlive the table; like the ctx, a table is not thread-safe.

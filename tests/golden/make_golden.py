@@ -114,6 +114,29 @@ def main():
         latitude=np.array([s.latitude for s in table]), longitude=np.array([s.longitude for s in table]))
     print(f"tracker_traffic    {len(traffic)} frames, {len(table)} aircraft, {int(new.sum())} positions")
 
+    # 8. the same for a small hostile traffic (tests/hostile_traffic.py: CPR edges, the 10 s window at 2 MSPS sample
+    #    positions up to beyond 2^53, every kind of message, segment shapes); times are sample x sps, formed in the test
+    from tests import hostile_traffic as H
+    hostile = H.hostile_traffic(orc, **H.GOLDEN)
+    trk = orc.tracker()
+    new = np.zeros(len(hostile), dtype=np.uint8)
+    pos = np.zeros((len(hostile), 2), dtype=np.float64)
+    for k, (fr, t) in enumerate(zip(hostile.frames, hostile.times().tolist())):
+        got, s = trk.update(bytes(fr), t)
+        new[k] = got
+        if got:
+            pos[k] = (s.latitude, s.longitude)
+    table = sorted(trk.aircraft(), key=lambda s: s.icao)
+    np.savez_compressed(
+        os.path.join(OUT, "hostile_traffic.npz"),
+        samples=hostile.samples, sps=np.float64(hostile.sps), frames=hostile.frames, new_position=new, position=pos,
+        icao=np.array([s.icao for s in table], dtype=np.uint32), callsign=np.array([s.callsign for s in table]),
+        altitude=np.array([s.altitude for s in table], dtype=np.int32),
+        has_position=np.array([s.has_position for s in table], dtype=np.uint8),
+        latitude=np.array([s.latitude for s in table]), longitude=np.array([s.longitude for s in table]),
+        last_contact=np.array([s.last_contact for s in table]))
+    print(f"hostile_traffic    {len(hostile)} frames, {len(table)} aircraft, {int(new.sum())} positions")
+
 
 if __name__ == "__main__":
     main()
