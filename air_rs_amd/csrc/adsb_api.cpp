@@ -1,4 +1,5 @@
-// adsb_api.cpp -- the extern "C" boundary (include/adsb_hip.h) over the gfx950 kernels.
+// adsb_api.cpp -- the extern "C" boundary (include/adsb_hip.h) over the gfx950 scan kernels; the tracker's part of the
+// boundary (adsb_track_*, adsb_fetch_track) is adsb_track_api.cpp.
 //
 // Replaces, per received buffer, the body of the reference's thread 2 loop
 // (src/adsb.rs:95-116).  There is NO CPU fallback: without a HIP device adsb_create() fails with
@@ -14,112 +15,11 @@
 #include <new>
 #include <vector>
 
-#include "adsb_kernels.h"
+#include "adsb_ctx.h"
 #include "adsb_synth.h"
 
 using adsbk::kTile;
 using adsbk::kWindow;
-
-namespace {
-constexpr int kTimingRing = 512;
-}
-
-struct adsb_ctx {
-    adsb_cfg cfg{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int mag_mode = 0;
-    uint32_t bps = 2; // bytes per IQ sample
-
-    // device buffers
-    void *staging = nullptr;        // host-fed input (cfg.host_staging)
-    // Two result sets, used alternately: the ordering pass of launch i runs on `aux` while the
-    // demod kernel of launch i+1 already runs on `stream` (they touch different sets).
-    struct ResultSet {
-        adsbk::Seg *seg = nullptr;       // [n_tiles_max]
-        adsb_frame *slots = nullptr;     // [n_tiles_max * kQuota] fixed region, then the pool [cap_slots]
-        adsb_frame *out = nullptr;       // [max_out]
-        adsbk::Header *hdr = nullptr;
-        uint64_t *chan_prefix = nullptr; // [max_channels + 1]: frames before each channel's first tile; last = total
-        hipEvent_t k_done = nullptr, g_done = nullptr;
-        bool g_pending = false;
-        // the launch whose results this set holds (the streaming front end fetches the older of two launches
-        // in flight: view_launch() makes it the one the fetch / re-plan code below works on)
-        struct Launch {
-            const void *iq = nullptr;
-            uint32_t channels = 0, tpc = 0, tiles = 0, cap = 0, idx = 0;
-            uint64_t samples = 0, stride = 0, base = 0;
-            adsb_frame *out = nullptr;
-            bool valid = false;
-        } li;
-    } rs[2];
-    hipStream_t aux = nullptr;      // ordering pass + result copies (== stream unless ADSB_OVERLAP_ORDERING=1)
-    bool own_aux = false;
-    adsb_packet_fields *fields = nullptr; // [max_out], allocated on first adsb_decode_fields_device_async
-    bool fields_current = false;    // fields[] belongs to the last launch
-    // tracker (allocated on first adsb_track_device)
-    uint32_t *trk_u32 = nullptr;    // 4 x [max_out]: keys, vals, sorted keys, sorted vals
-    void *trk_temp = nullptr;
-    size_t trk_temp_bytes = 0;
-    adsb_track_point *trk_points = nullptr;      // [max_out]
-    adsb_aircraft_record *trk_aircraft = nullptr; // [max_out]
-    uint64_t *trk_n_aircraft = nullptr;
-    uint32_t trk_n = 0;             // frames the last tracker run covered
-    bool trk_done = false;
-    void *ext_blob = nullptr;       // caller-owned [32-byte header | frames] target for the next launches
-    size_t ext_frames = 0;          // frame capacity of ext_blob
-    adsb_frame *last_out = nullptr; // where the last launch's ordered list went
-    uint32_t last_cap = 0;
-    bool fused_pass_only = false;   // adsb_debug_fused_pass_only (measurement)
-    uint64_t stream_base = 0;       // adsb_set_stream_base: added to the offsets of the following launches
-    uint64_t last_base = 0;         // ... of the last launch (re-runs of its tiles use the same)
-    uint32_t launch_idx = 0;        // launches so far
-    uint32_t last = 0;              // result set of the last launch
-    uint32_t *out_start = nullptr;  // [n_tiles_max + 1]  (slot-overflow re-run path only)
-    uint64_t *lb = nullptr;         // finish_order's exchange words: one per workgroup, then one per 64 workgroups
-    uint32_t lb_groups_at = 0;
-    uint32_t *scratch = nullptr;    // 16 dwords: probe result, read-kernel sink
-    unsigned long long *stamps = nullptr; // cycle counters of diagnostic builds (64 bytes per tile with -DADSB_TILE_STAMPS=1)
-    size_t stamps_bytes = 0;
-    int scan = adsbk::kScanRoot;    // which i8 scan kernel (ADSB_SCAN=nsq selects the A/B kernel at adsb_create)
-    // The one-dispatch path for small buffers (adsbk::launch_small): per result set a pinned, device-writable blob
-    // [32-byte header | frames | u64 sequence number] and a device counter; a pinned input buffer for adsb_demod().
-    struct Small {
-        bool enabled = true, ready = false;
-        char *blob[2] = {nullptr, nullptr};
-        uint32_t cap = 0;            // frames per blob
-        uint32_t *done = nullptr;    // device: 2 words
-        char *in_host = nullptr;     // pinned copy of adsb_demod()'s buffer (allocated on first use)
-        uint64_t seq = 0;
-        uint64_t max_samples = 0;    // longest buffer the path takes
-    } sm;
-    bool pool_off = false;          // adsb_debug_pool_limit: the shared slot pool hands out nothing (test knob)
-    uint32_t stall_blk = 0xFFFFFFFFu; // adsb_debug_finish_stall: this workgroup of finish_order withholds its exchange word (test knob)
-    uint32_t cap_slots = 0;
-    uint32_t n_tiles_max = 0;
-
-    // pinned host mirrors
-    adsbk::Header *hdr_host = nullptr;
-
-    // last launch
-    bool launched = false;
-    const void *last_iq = nullptr;
-    uint32_t last_channels = 0;
-    uint64_t last_samples = 0, last_stride = 0;
-    uint32_t last_tpc = 0, last_tiles = 0;
-
-    // timing
-    int timing = 0;                 // 0 off; N: events on every N-th launch
-    hipEvent_t ev[kTimingRing][4] = {}; // scan kernel, finishing kernel: start/end each
-    bool ev_made = false;
-    uint32_t ev_count = 0;
-};
-
-#define HIPCHK(x)                                  \
-    do {                                           \
-        hipError_t e_ = (x);                       \
-        if (e_ != hipSuccess) return (int)e_;      \
-    } while (0)
 
 static uint32_t tiles_for(uint64_t n_samples, int sample_type, int scan)
 {
@@ -628,7 +528,6 @@ static int small_wait(adsb_ctx *c, uint32_t set, uint64_t seq, bool at_least = f
     return ADSB_OK;
 }
 
-static int sync_header(adsb_ctx *c);
 // Hands the finished list of result set `set` (a small launch that small_wait has seen complete) to the caller.
 static int small_collect(adsb_ctx *c, uint32_t set, adsb_frame *out, size_t max_out, size_t *n_out, uint64_t *total_found,
                          uint32_t *flags)
@@ -702,7 +601,7 @@ static int rerun_in_batches(adsb_ctx *c, adsb_ctx::ResultSet &r)
     return rc;
 }
 
-static int sync_header(adsb_ctx *c)
+int sync_header(adsb_ctx *c)
 {
     if (!c->launched) return ADSB_E_STATE;
     HIPCHK(hipSetDevice(c->cfg.device));
@@ -800,904 +699,6 @@ extern "C" int adsb_fetch_fields(adsb_ctx *c, adsb_packet_fields *out, size_t ma
     return ADSB_OK;
 }
 
-
-extern "C" int adsb_track_device(adsb_ctx *c, double seconds_per_sample)
-{
-    if (!c || !(seconds_per_sample > 0.0)) return ADSB_E_ARG;
-    if (!c->launched) return ADSB_E_STATE;
-    if (c->last_channels != 1) return ADSB_E_ARG;
-    int rc = sync_header(c); // the list's length (and the rebuild after a slot-pool overflow)
-    if (rc != ADSB_OK) return rc;
-    if (!c->fields_current && (rc = adsb_decode_fields_device_async(c)) != ADSB_OK) return rc;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    const size_t cap = (size_t)c->cfg.max_out;
-    if (!c->trk_u32) {
-        c->trk_temp_bytes = adsbk::track_sort_temp_bytes(cap);
-        if (hipMalloc((void **)&c->trk_u32, sizeof(uint32_t) * 4 * cap) != hipSuccess ||
-            hipMalloc(&c->trk_temp, c->trk_temp_bytes) != hipSuccess ||
-            hipMalloc((void **)&c->trk_points, sizeof(adsb_track_point) * cap) != hipSuccess ||
-            hipMalloc((void **)&c->trk_aircraft, sizeof(adsb_aircraft_record) * cap) != hipSuccess ||
-            hipMalloc((void **)&c->trk_n_aircraft, sizeof(uint64_t)) != hipSuccess)
-            return ADSB_E_NOMEM;
-    }
-    const uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
-    adsbk::TrackArgs a{};
-    a.frames = c->last_out;
-    a.fields = c->fields;
-    a.n = (uint32_t)n;
-    a.seconds_per_sample = seconds_per_sample;
-    a.keys = c->trk_u32;
-    a.vals = c->trk_u32 + cap;
-    a.skeys = c->trk_u32 + 2 * cap;
-    a.svals = c->trk_u32 + 3 * cap;
-    a.temp = c->trk_temp;
-    a.temp_bytes = c->trk_temp_bytes;
-    a.points = c->trk_points;
-    a.aircraft = c->trk_aircraft;
-    a.max_aircraft = (uint32_t)cap;
-    a.n_aircraft = c->trk_n_aircraft;
-    HIPCHK(adsbk::launch_track(c->aux, a)); // same stream as the ordering pass and the field decode
-    c->trk_n = (uint32_t)n;
-    c->trk_done = true;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_fetch_track(adsb_ctx *c, adsb_track_point *points, size_t max_points, size_t *n_points,
-                                adsb_aircraft_record *aircraft, size_t max_aircraft, size_t *n_aircraft)
-{
-    if (!c || (!points && max_points) || (!aircraft && max_aircraft)) return ADSB_E_ARG;
-    if (!c->trk_done) return ADSB_E_STATE;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    uint64_t na = 0;
-    HIPCHK(hipMemcpyAsync(&na, c->trk_n_aircraft, sizeof(uint64_t), hipMemcpyDeviceToHost, c->aux));
-    HIPCHK(hipStreamSynchronize(c->aux));
-    const size_t np = std::min<size_t>(c->trk_n, max_points);
-    const size_t nac = std::min<size_t>((size_t)na, max_aircraft);
-    if (np) HIPCHK(hipMemcpyAsync(points, c->trk_points, sizeof(adsb_track_point) * np, hipMemcpyDeviceToHost, c->aux));
-    if (nac) HIPCHK(hipMemcpyAsync(aircraft, c->trk_aircraft, sizeof(adsb_aircraft_record) * nac, hipMemcpyDeviceToHost, c->aux));
-    HIPCHK(hipStreamSynchronize(c->aux));
-    if (n_points) *n_points = np;
-    if (n_aircraft) *n_aircraft = (size_t)na;
-    return ADSB_OK;
-}
-
-// ---- per-frame summaries and the changed list of a table or bank (adsb_track_*_summaries_reserve) -------------------
-// Everything here is allocated by the reserve; `dev.out` null = no reserve.
-struct TrackSummaries {
-    adsbk::TrackSumDev dev{};
-    adsbk::TrackRecord *changed_rec = nullptr; // [changed_cap]: fetch_changed's device-side gather
-    size_t changed_cap = 0;         // min(max_frames, record places): an update cannot touch more aircraft
-    bool updated = false;           // an update ran since the reserve (and since the last reset)
-    bool changed_valid = false;     // the last operation was an update: the changed list's slots still hold
-};
-
-static void track_summaries_free(TrackSummaries &s)
-{
-    for (void *p : {(void *)s.dev.scan, (void *)s.dev.out, (void *)s.dev.changed, (void *)s.dev.n_changed, s.dev.temp,
-                    (void *)s.changed_rec})
-        if (p) (void)hipFree(p);
-    s = TrackSummaries{};
-}
-
-// May wait for the device (hipMalloc); a second reserve keeps what the first one made
-static int track_summaries_reserve(TrackSummaries &s, size_t max_frames, size_t places)
-{
-    if (s.dev.out) return ADSB_OK;
-    s.changed_cap = std::min(max_frames, places);
-    s.dev.temp_bytes = adsbk::track_summaries_temp_bytes(max_frames);
-    const bool ok = hipMalloc((void **)&s.dev.scan, sizeof(adsbk::TrackSumTuple) * max_frames) == hipSuccess &&
-                    hipMalloc((void **)&s.dev.changed, sizeof(uint32_t) * max_frames) == hipSuccess &&
-                    hipMalloc((void **)&s.dev.n_changed, sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc(&s.dev.temp, s.dev.temp_bytes) == hipSuccess &&
-                    hipMalloc((void **)&s.changed_rec, sizeof(adsbk::TrackRecord) * s.changed_cap) == hipSuccess &&
-                    hipMalloc((void **)&s.dev.out, sizeof(adsb_aircraft_record) * max_frames) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        track_summaries_free(s);
-        return ADSB_E_NOMEM;
-    }
-    return ADSB_OK;
-}
-
-// What every update does for the summaries besides handing `dev` to launch_track
-static void track_summaries_mark_update(TrackSummaries &s)
-{
-    if (!s.dev.out) return;
-    s.updated = true;
-    s.changed_valid = true;
-}
-
-// Waits; n_frames: frames of the last update (host-known)
-static int track_summaries_fetch(adsb_ctx *c, TrackSummaries &s, size_t n_frames, adsb_aircraft_record *out, size_t max,
-                                 size_t *n)
-{
-    if (!s.dev.out || !s.updated) return ADSB_E_STATE;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    const size_t take = std::min(n_frames, max);
-    if (take) HIPCHK(hipMemcpyAsync(out, s.dev.out, sizeof(adsb_aircraft_record) * take, hipMemcpyDeviceToHost, c->aux));
-    HIPCHK(hipStreamSynchronize(c->aux));
-    if (n) *n = n_frames;
-    return ADSB_OK;
-}
-
-// Waits; gathers the changed list's records on the device and copies only them.  rec: the table's / bank's records;
-// counts (optional, [n_receivers]): how many of the records returned belong to each receiver (slot / max_aircraft).
-static int track_summaries_fetch_changed(adsb_ctx *c, TrackSummaries &s, const adsbk::TrackRecord *rec, size_t n_frames,
-                                         uint32_t max_aircraft, uint32_t n_receivers, adsb_aircraft_record *out,
-                                         double *last_heard, adsb_velocity *velocity, size_t max, size_t *n,
-                                         uint64_t *counts)
-{
-    if (!s.dev.out || !s.updated || !s.changed_valid) return ADSB_E_STATE;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    if (counts) std::fill(counts, counts + n_receivers, (uint64_t)0);
-    uint32_t nc = 0;
-    if (n_frames) { // an empty update launched nothing: its list is empty, and the device word is an older update's
-        const uint32_t most = (uint32_t)std::min(std::min(n_frames, s.changed_cap), max);
-        HIPCHK(adsbk::launch_track_changed(c->aux, rec, s.dev, most, s.changed_rec));
-        HIPCHK(hipMemcpyAsync(&nc, s.dev.n_changed, sizeof(nc), hipMemcpyDeviceToHost, c->aux));
-        HIPCHK(hipStreamSynchronize(c->aux));
-        const size_t take = std::min<size_t>(nc, most);
-        if (take) {
-            std::vector<adsbk::TrackRecord> recs(take);
-            std::vector<uint32_t> slots(take);
-            HIPCHK(hipMemcpyAsync(recs.data(), s.changed_rec, sizeof(adsbk::TrackRecord) * take, hipMemcpyDeviceToHost,
-                                  c->aux));
-            HIPCHK(hipMemcpyAsync(slots.data(), s.dev.changed, sizeof(uint32_t) * take, hipMemcpyDeviceToHost, c->aux));
-            HIPCHK(hipStreamSynchronize(c->aux));
-            for (size_t k = 0; k < take; ++k) {
-                if (out) out[k] = recs[k].a;
-                if (last_heard) last_heard[k] = recs[k].last_heard;
-                if (velocity) velocity[k] = recs[k].vel;
-                if (counts) ++counts[slots[k] / max_aircraft]; // a bank's slot = receiver x max_aircraft + place
-            }
-        }
-    }
-    if (n) *n = nc;
-    return ADSB_OK;
-}
-
-// ---- persistent aircraft table (adsb_track_table_*): the tracker kernels with a TrackTableDev ----------------------
-struct adsb_track_table {
-    adsb_ctx *ctx = nullptr;
-    adsb_track_table_cfg cfg{};
-    adsbk::TrackTableDev dev{};     // index [2^24], records [max_aircraft], size/flags words, slot [max_frames]
-    uint32_t *u32 = nullptr;        // 4 x [max_frames]: keys, vals, sorted keys, sorted vals
-    void *temp = nullptr;
-    size_t temp_bytes = 0;
-    adsb_frame *frames = nullptr;   // [max_frames]: device copy of a host list
-    adsb_frame *pinned = nullptr;   // [max_frames]: pinned staging of that copy
-    hipEvent_t copied = nullptr;    // the last copy out of `pinned` has finished
-    adsb_packet_fields *fields = nullptr; // [max_frames]
-    adsb_track_point *points = nullptr;   // [max_frames], the last update's, frame order
-    uint32_t *exp_u32 = nullptr;    // 2 x [max_aircraft]: expire's keep flags and their scan
-    void *exp_temp = nullptr;       // expire's scan
-    size_t exp_temp_bytes = 0;
-    uint32_t n_points = 0;
-    bool updated = false;
-    TrackSummaries sum;             // adsb_track_table_summaries_reserve
-};
-
-// Records of a table or of one bank receiver (slots in admission order) as fetch returns them: ascending ICAO.
-static void sort_by_icao(std::vector<adsbk::TrackRecord> &recs)
-{
-    std::sort(recs.begin(), recs.end(),
-              [](const adsbk::TrackRecord &x, const adsbk::TrackRecord &y) { return x.a.icao < y.a.icao; });
-}
-
-static void track_table_free(adsb_track_table *t)
-{
-    (void)hipSetDevice(t->ctx->cfg.device);
-    (void)hipStreamSynchronize(t->ctx->aux);
-    track_summaries_free(t->sum);
-    if (t->dev.index) (void)hipFree(t->dev.index);
-    if (t->dev.rec) (void)hipFree(t->dev.rec);
-    if (t->dev.size_flags) (void)hipFree(t->dev.size_flags);
-    if (t->dev.slot) (void)hipFree(t->dev.slot);
-    if (t->u32) (void)hipFree(t->u32);
-    if (t->temp) (void)hipFree(t->temp);
-    if (t->frames) (void)hipFree(t->frames);
-    if (t->pinned) (void)hipHostFree(t->pinned);
-    if (t->copied) (void)hipEventDestroy(t->copied);
-    if (t->fields) (void)hipFree(t->fields);
-    if (t->points) (void)hipFree(t->points);
-    if (t->exp_u32) (void)hipFree(t->exp_u32);
-    if (t->exp_temp) (void)hipFree(t->exp_temp);
-    delete t;
-}
-
-extern "C" int adsb_track_table_reset(adsb_track_table *t)
-{
-    if (!t) return ADSB_E_ARG;
-    HIPCHK(hipSetDevice(t->ctx->cfg.device));
-    HIPCHK(hipMemsetAsync(t->dev.index, 0, sizeof(uint32_t) << 24, t->ctx->aux));
-    HIPCHK(hipMemsetAsync(t->dev.size_flags, 0, sizeof(uint32_t) * 4, t->ctx->aux));
-    t->n_points = 0;
-    t->updated = false;
-    t->sum.updated = t->sum.changed_valid = false;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_table_create(adsb_ctx *c, const adsb_track_table_cfg *cfg, adsb_track_table **out)
-{
-    if (!c || !cfg || !out || cfg->abi_version != ADSB_ABI_VERSION) return ADSB_E_ARG;
-    if (cfg->max_frames == 0 || cfg->max_frames > 0xFFFFFFFFull || !(cfg->seconds_per_sample > 0.0) ||
-        cfg->max_aircraft > (1u << 24))
-        return ADSB_E_ARG;
-    *out = nullptr;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    adsb_track_table *t = new (std::nothrow) adsb_track_table;
-    if (!t) return ADSB_E_NOMEM;
-    t->ctx = c;
-    t->cfg = *cfg;
-    if (!t->cfg.max_aircraft) t->cfg.max_aircraft = 65536;
-    const size_t nf = (size_t)t->cfg.max_frames;
-    t->dev.max_aircraft = t->cfg.max_aircraft;
-    t->temp_bytes = adsbk::track_sort_temp_bytes(nf);
-    t->exp_temp_bytes = adsbk::track_expire_temp_bytes(t->cfg.max_aircraft);
-    const bool ok = hipMalloc((void **)&t->dev.index, sizeof(uint32_t) << 24) == hipSuccess &&
-                    hipMalloc((void **)&t->dev.rec, sizeof(adsbk::TrackRecord) * t->cfg.max_aircraft) == hipSuccess &&
-                    hipMalloc((void **)&t->dev.size_flags, sizeof(uint32_t) * 4) == hipSuccess &&
-                    hipMalloc((void **)&t->dev.slot, sizeof(uint32_t) * nf) == hipSuccess &&
-                    hipMalloc((void **)&t->u32, sizeof(uint32_t) * 4 * nf) == hipSuccess &&
-                    hipMalloc(&t->temp, t->temp_bytes) == hipSuccess &&
-                    hipMalloc((void **)&t->frames, sizeof(adsb_frame) * nf) == hipSuccess &&
-                    hipHostMalloc((void **)&t->pinned, sizeof(adsb_frame) * nf, hipHostMallocDefault) == hipSuccess &&
-                    hipEventCreateWithFlags(&t->copied, hipEventDisableTiming) == hipSuccess &&
-                    hipMalloc((void **)&t->fields, sizeof(adsb_packet_fields) * nf) == hipSuccess &&
-                    hipMalloc((void **)&t->points, sizeof(adsb_track_point) * nf) == hipSuccess &&
-                    hipMalloc((void **)&t->exp_u32, sizeof(uint32_t) * 2 * t->cfg.max_aircraft) == hipSuccess &&
-                    hipMalloc(&t->exp_temp, t->exp_temp_bytes) == hipSuccess;
-    int rc = ok ? adsb_track_table_reset(t) : ADSB_E_NOMEM;
-    if (rc == ADSB_OK && hipStreamSynchronize(c->aux) != hipSuccess) rc = ADSB_E_NOMEM;
-    if (rc != ADSB_OK) {
-        (void)hipGetLastError();
-        track_table_free(t);
-        return rc;
-    }
-    *out = t;
-    return ADSB_OK;
-}
-
-extern "C" void adsb_track_table_destroy(adsb_track_table *t)
-{
-    if (t) track_table_free(t);
-}
-
-extern "C" int adsb_track_table_update(adsb_track_table *t, const adsb_frame *frames, size_t n, uint64_t sample_base)
-{
-    if (!t || (!frames && n)) return ADSB_E_ARG;
-    if (n > t->cfg.max_frames) return ADSB_E_CAPACITY;
-    adsb_ctx *c = t->ctx;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    t->n_points = (uint32_t)n;
-    t->updated = true;
-    track_summaries_mark_update(t->sum); // an empty update: no summaries, an empty changed list
-    if (n == 0) return ADSB_OK;
-    const adsb_frame *list = frames;
-    hipPointerAttribute_t at{};
-    const bool on_device = hipPointerGetAttributes(&at, frames) == hipSuccess && at.type == hipMemoryTypeDevice &&
-                           at.device == c->cfg.device;
-    (void)hipGetLastError(); // a plain host pointer is an error to the query: do not leave it to the launches below
-    if (!on_device) { // through pinned staging, so the caller's array is free when this returns
-        HIPCHK(hipEventSynchronize(t->copied)); // the previous update's copy out of the staging has finished
-        std::memcpy(t->pinned, frames, sizeof(adsb_frame) * n);
-        HIPCHK(hipMemcpyAsync(t->frames, t->pinned, sizeof(adsb_frame) * n, hipMemcpyHostToDevice, c->aux));
-        HIPCHK(hipEventRecord(t->copied, c->aux));
-        list = t->frames;
-    }
-    HIPCHK(adsbk::launch_decode_fields(c->aux, list, nullptr, (uint32_t)n, t->fields));
-    adsbk::TrackArgs a{};
-    a.frames = list;
-    a.fields = t->fields;
-    a.n = (uint32_t)n;
-    a.seconds_per_sample = t->cfg.seconds_per_sample;
-    a.sample_base = sample_base;
-    const size_t nf = (size_t)t->cfg.max_frames;
-    a.keys = t->u32;
-    a.vals = t->u32 + nf;
-    a.skeys = t->u32 + 2 * nf;
-    a.svals = t->u32 + 3 * nf;
-    a.temp = t->temp;
-    a.temp_bytes = t->temp_bytes;
-    a.points = t->points;
-    a.table = &t->dev;
-    a.sum = t->sum.dev.out ? &t->sum.dev : nullptr;
-    HIPCHK(adsbk::launch_track(c->aux, a)); // after the ctx's ordering pass and field decode (same stream)
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_table_summaries_reserve(adsb_track_table *t)
-{
-    if (!t) return ADSB_E_ARG;
-    HIPCHK(hipSetDevice(t->ctx->cfg.device));
-    return track_summaries_reserve(t->sum, (size_t)t->cfg.max_frames, t->cfg.max_aircraft);
-}
-
-extern "C" int adsb_track_table_fetch_summaries(adsb_track_table *t, adsb_aircraft_record *out, size_t max, size_t *n)
-{
-    if (!t || (!out && max)) return ADSB_E_ARG;
-    return track_summaries_fetch(t->ctx, t->sum, t->n_points, out, max, n);
-}
-
-extern "C" int adsb_track_table_summaries_device(adsb_track_table *t, const adsb_aircraft_record **dev)
-{
-    if (!t) return ADSB_E_ARG;
-    if (!t->sum.dev.out || !t->sum.updated) return ADSB_E_STATE;
-    if (dev) *dev = t->sum.dev.out;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_table_fetch_changed(adsb_track_table *t, adsb_aircraft_record *rec, double *last_heard,
-                                              adsb_velocity *velocity, size_t max, size_t *n)
-{
-    if (!t) return ADSB_E_ARG;
-    return track_summaries_fetch_changed(t->ctx, t->sum, t->dev.rec, t->n_points, t->cfg.max_aircraft, 1, rec,
-                                         last_heard, velocity, max, n, nullptr);
-}
-
-extern "C" int adsb_track_table_fetch_points(adsb_track_table *t, adsb_track_point *points, size_t max_points,
-                                             size_t *n_points)
-{
-    if (!t || (!points && max_points)) return ADSB_E_ARG;
-    if (!t->updated) return ADSB_E_STATE;
-    HIPCHK(hipSetDevice(t->ctx->cfg.device));
-    const size_t np = std::min<size_t>(t->n_points, max_points);
-    if (np) HIPCHK(hipMemcpyAsync(points, t->points, sizeof(adsb_track_point) * np, hipMemcpyDeviceToHost, t->ctx->aux));
-    HIPCHK(hipStreamSynchronize(t->ctx->aux));
-    if (n_points) *n_points = np;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_table_fetch(adsb_track_table *t, adsb_aircraft_record *aircraft, size_t max_aircraft,
-                                      size_t *n_aircraft, uint32_t *flags)
-{
-    if (!t || (!aircraft && max_aircraft)) return ADSB_E_ARG;
-    HIPCHK(hipSetDevice(t->ctx->cfg.device));
-    uint32_t sf[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(sf, t->dev.size_flags, sizeof(sf), hipMemcpyDeviceToHost, t->ctx->aux));
-    HIPCHK(hipStreamSynchronize(t->ctx->aux));
-    const size_t size = std::min<size_t>(sf[0], t->cfg.max_aircraft);
-    if (max_aircraft && size) { // slots are in admission order: sort by ICAO here
-        std::vector<adsbk::TrackRecord> recs(size);
-        HIPCHK(hipMemcpyAsync(recs.data(), t->dev.rec, sizeof(adsbk::TrackRecord) * size, hipMemcpyDeviceToHost,
-                              t->ctx->aux));
-        HIPCHK(hipStreamSynchronize(t->ctx->aux));
-        sort_by_icao(recs);
-        for (size_t k = 0; k < std::min(size, max_aircraft); ++k) aircraft[k] = recs[k].a;
-    }
-    if (n_aircraft) *n_aircraft = size;
-    if (flags) *flags = sf[1];
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_table_expire(adsb_track_table *t, double before)
-{
-    if (!t || std::isnan(before)) return ADSB_E_ARG;
-    HIPCHK(hipSetDevice(t->ctx->cfg.device));
-    adsbk::ExpireArgs a{};
-    a.table = &t->dev;
-    a.cut.before[0] = before;
-    a.keep = t->exp_u32;
-    a.rank = t->exp_u32 + t->cfg.max_aircraft;
-    a.temp = t->exp_temp;
-    a.temp_bytes = t->exp_temp_bytes;
-    HIPCHK(adsbk::launch_track_expire(t->ctx->aux, a)); // after the table's last update (same stream)
-    t->sum.changed_valid = false; // slots move
-    return ADSB_OK;
-}
-
-// Waits; out[k] = get(record k) for the records in the order of adsb_track_table_fetch; *n = table size
-template <class T, class Get>
-static int track_table_fetch_each(adsb_track_table *t, T *out, size_t max, size_t *n, Get get)
-{
-    if (!t || (!out && max)) return ADSB_E_ARG;
-    HIPCHK(hipSetDevice(t->ctx->cfg.device));
-    uint32_t sf[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(sf, t->dev.size_flags, sizeof(sf), hipMemcpyDeviceToHost, t->ctx->aux));
-    HIPCHK(hipStreamSynchronize(t->ctx->aux));
-    const size_t size = std::min<size_t>(sf[0], t->cfg.max_aircraft);
-    if (max && size) { // the order of adsb_track_table_fetch
-        std::vector<adsbk::TrackRecord> recs(size);
-        HIPCHK(hipMemcpyAsync(recs.data(), t->dev.rec, sizeof(adsbk::TrackRecord) * size, hipMemcpyDeviceToHost,
-                              t->ctx->aux));
-        HIPCHK(hipStreamSynchronize(t->ctx->aux));
-        sort_by_icao(recs);
-        for (size_t k = 0; k < std::min(size, max); ++k) out[k] = get(recs[k]);
-    }
-    if (n) *n = size;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_table_fetch_last_heard(adsb_track_table *t, double *last_heard, size_t max, size_t *n)
-{
-    return track_table_fetch_each(t, last_heard, max, n, [](const adsbk::TrackRecord &r) { return r.last_heard; });
-}
-
-extern "C" int adsb_track_table_fetch_velocity(adsb_track_table *t, adsb_velocity *velocity, size_t max, size_t *n)
-{
-    return track_table_fetch_each(t, velocity, max, n, [](const adsbk::TrackRecord &r) { return r.vel; });
-}
-
-// ---- a bank of persistent tables, one per receiver (adsb_track_bank_*): the tracker kernels with a TrackBankDev ----
-struct adsb_track_bank {
-    adsb_ctx *ctx = nullptr;
-    adsb_track_bank_cfg cfg{};
-    adsbk::TrackBankDev dev{};      // hash, records [R x max_aircraft], per-receiver words, prefix, per-frame scan words
-    adsbk::TrackTableDev tab{};     // what the shared kernels read: rec = dev.rec, slot [max_frames]
-    uint32_t *words = nullptr;      // [3R]: size, flags, size_next (dev.size / dev.flags / dev.size_next)
-    uint64_t *meta = nullptr;       // device [2R + 1]: prefix of the host counts [R + 1], then sample_base [R]
-    uint64_t *meta_pinned = nullptr; // pinned staging of meta
-    uint32_t *u32 = nullptr;        // 4 x [max_frames]: keys, vals, sorted keys, sorted vals
-    void *temp = nullptr;
-    size_t temp_bytes = 0;
-    adsb_frame *frames = nullptr;   // [max_frames]: device copy of a host list
-    adsb_frame *pinned = nullptr;   // [max_frames]: pinned staging of that copy
-    hipEvent_t copied = nullptr;    // the last copies out of `pinned` and `meta_pinned` have finished
-    adsb_packet_fields *fields = nullptr; // [max_frames]
-    adsb_track_point *points = nullptr;   // [max_frames], the last update's, list order
-    uint32_t *exp_u32 = nullptr;    // 2 x [R x max_aircraft]: expire's keep flags and their scan
-    void *exp_temp = nullptr;       // expire's scan
-    size_t exp_temp_bytes = 0;
-    uint32_t n_points = 0;
-    bool updated = false;
-    TrackSummaries sum;             // adsb_track_bank_summaries_reserve
-    // the fused view (adsb_track_bank_fuse_*): all of it allocated by fuse_reserve, nothing before
-    void *fuse_keys = nullptr;      // 2 x [places] sort keys (uint32_t, uint64_t above kFuseWideReceivers): in, sorted
-    uint32_t *fuse_vals = nullptr;  // 2 x [places]: places in, sorted
-    uint32_t *fuse_start = nullptr; // [fuse_max]
-    adsb_fused_aircraft *fuse_out = nullptr; // [fuse_max]
-    uint64_t *fuse_counts = nullptr; // device [3]: records written, distinct ICAOs, ADSB_TRACK_FUSED_TRUNCATED
-    void *fuse_temp = nullptr;
-    size_t fuse_temp_bytes = 0;
-    size_t fuse_max = 0;            // 0: no reserve
-    uint32_t fuse_lanes = 0;
-    bool fused = false;             // a fuse ran since the last reserve
-};
-
-static void track_bank_fuse_free(adsb_track_bank *b)
-{
-    for (void *p : {b->fuse_keys, (void *)b->fuse_vals, (void *)b->fuse_start, (void *)b->fuse_out,
-                    (void *)b->fuse_counts, b->fuse_temp})
-        if (p) (void)hipFree(p);
-    b->fuse_keys = b->fuse_temp = nullptr;
-    b->fuse_vals = b->fuse_start = nullptr;
-    b->fuse_out = nullptr;
-    b->fuse_counts = nullptr;
-    b->fuse_max = 0;
-    b->fused = false;
-}
-
-static void track_bank_free(adsb_track_bank *b)
-{
-    (void)hipSetDevice(b->ctx->cfg.device);
-    (void)hipStreamSynchronize(b->ctx->aux);
-    track_bank_fuse_free(b);
-    track_summaries_free(b->sum);
-    for (void *p : {(void *)b->dev.hash, (void *)b->dev.rec, (void *)b->words, (void *)b->dev.prefix, (void *)b->meta,
-                    (void *)b->dev.mark, (void *)b->dev.excl, (void *)b->dev.seg_slot, (void *)b->tab.slot,
-                    (void *)b->u32, b->temp, (void *)b->frames, (void *)b->fields, (void *)b->points,
-                    (void *)b->exp_u32, b->exp_temp})
-        if (p) (void)hipFree(p);
-    if (b->pinned) (void)hipHostFree(b->pinned);
-    if (b->meta_pinned) (void)hipHostFree(b->meta_pinned);
-    if (b->copied) (void)hipEventDestroy(b->copied);
-    delete b;
-}
-
-extern "C" int adsb_track_bank_reset(adsb_track_bank *b)
-{
-    if (!b) return ADSB_E_ARG;
-    HIPCHK(hipSetDevice(b->ctx->cfg.device));
-    HIPCHK(hipMemsetAsync(b->dev.hash, 0, sizeof(unsigned long long) * (b->dev.hash_mask + 1), b->ctx->aux));
-    HIPCHK(hipMemsetAsync(b->words, 0, sizeof(uint32_t) * 3 * b->cfg.n_receivers, b->ctx->aux));
-    b->n_points = 0;
-    b->updated = false;
-    b->sum.updated = b->sum.changed_valid = false;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_bank_create(adsb_ctx *c, const adsb_track_bank_cfg *cfg, adsb_track_bank **out)
-{
-    if (!c || !cfg || !out || cfg->abi_version != ADSB_ABI_VERSION || cfg->reserved != 0) return ADSB_E_ARG;
-    if (cfg->n_receivers == 0 || cfg->n_receivers > adsbk::kMaxReceivers || cfg->max_frames == 0 || cfg->max_frames > 0xFFFFFFFFull ||
-        !(cfg->seconds_per_sample > 0.0) || cfg->max_aircraft > (1u << 24))
-        return ADSB_E_ARG;
-    *out = nullptr;
-    const uint32_t nr = cfg->n_receivers, max_ac = cfg->max_aircraft ? cfg->max_aircraft : 65536u;
-    const uint64_t n_rec = (uint64_t)nr * max_ac;
-    if (n_rec >= 0xFFFFFFFFull) return ADSB_E_NOMEM; // slot + 1 must fit 32 bits: 2^32 records would need > 350 GiB
-    HIPCHK(hipSetDevice(c->cfg.device));
-    adsb_track_bank *b = new (std::nothrow) adsb_track_bank;
-    if (!b) return ADSB_E_NOMEM;
-    b->ctx = c;
-    b->cfg = *cfg;
-    b->cfg.max_aircraft = max_ac;
-    const size_t nf = (size_t)b->cfg.max_frames;
-    uint64_t cap = 1;
-    while (cap < 2 * n_rec) cap <<= 1;
-    b->dev.hash_mask = cap - 1;
-    b->dev.max_aircraft = max_ac;
-    b->dev.n_receivers = nr;
-    uint32_t bits = 0;
-    while ((1u << bits) < nr) ++bits;
-    b->dev.key_bits = 24 + bits;
-    b->temp_bytes = adsbk::track_bank_temp_bytes(nf);
-    b->exp_temp_bytes = adsbk::track_expire_temp_bytes(n_rec);
-    bool ok = hipMalloc((void **)&b->dev.hash, sizeof(unsigned long long) * cap) == hipSuccess &&
-              hipMalloc((void **)&b->dev.rec, sizeof(adsbk::TrackRecord) * n_rec) == hipSuccess &&
-              hipMalloc((void **)&b->words, sizeof(uint32_t) * 3 * nr) == hipSuccess &&
-              hipMalloc((void **)&b->dev.prefix, sizeof(uint32_t) * (nr + 1)) == hipSuccess &&
-              hipMalloc((void **)&b->meta, sizeof(uint64_t) * (2 * nr + 1)) == hipSuccess &&
-              hipHostMalloc((void **)&b->meta_pinned, sizeof(uint64_t) * (2 * nr + 1), hipHostMallocDefault) == hipSuccess &&
-              hipMalloc((void **)&b->dev.mark, sizeof(unsigned long long) * nf) == hipSuccess &&
-              hipMalloc((void **)&b->dev.excl, sizeof(unsigned long long) * nf) == hipSuccess &&
-              hipMalloc((void **)&b->dev.seg_slot, sizeof(uint32_t) * nf) == hipSuccess &&
-              hipMalloc((void **)&b->tab.slot, sizeof(uint32_t) * nf) == hipSuccess &&
-              hipMalloc((void **)&b->u32, sizeof(uint32_t) * 4 * nf) == hipSuccess &&
-              hipMalloc(&b->temp, b->temp_bytes) == hipSuccess &&
-              hipMalloc((void **)&b->frames, sizeof(adsb_frame) * nf) == hipSuccess &&
-              hipHostMalloc((void **)&b->pinned, sizeof(adsb_frame) * nf, hipHostMallocDefault) == hipSuccess &&
-              hipEventCreateWithFlags(&b->copied, hipEventDisableTiming) == hipSuccess &&
-              hipMalloc((void **)&b->fields, sizeof(adsb_packet_fields) * nf) == hipSuccess &&
-              hipMalloc((void **)&b->points, sizeof(adsb_track_point) * nf) == hipSuccess &&
-              hipMalloc((void **)&b->exp_u32, sizeof(uint32_t) * 2 * n_rec) == hipSuccess &&
-              hipMalloc(&b->exp_temp, b->exp_temp_bytes) == hipSuccess;
-    if (ok) {
-        b->dev.size = b->words;
-        b->dev.flags = b->words + nr;
-        b->dev.size_next = b->words + 2 * nr;
-        b->dev.sample_base = b->meta + nr + 1;
-        b->tab.rec = b->dev.rec;
-        b->tab.max_aircraft = max_ac;
-    }
-    int rc = ok ? adsb_track_bank_reset(b) : ADSB_E_NOMEM;
-    if (rc == ADSB_OK && hipStreamSynchronize(c->aux) != hipSuccess) rc = ADSB_E_NOMEM;
-    if (rc != ADSB_OK) {
-        (void)hipGetLastError();
-        track_bank_free(b);
-        return rc;
-    }
-    *out = b;
-    return ADSB_OK;
-}
-
-extern "C" void adsb_track_bank_destroy(adsb_track_bank *b)
-{
-    if (b) track_bank_free(b);
-}
-
-// Enqueues the bank's kernels over n frames at `list` (device) with the receiver split src_prefix[0..n_src]; meta's
-// sample_base part has been filled by the caller (and the staging copy enqueued).
-static int track_bank_run(adsb_track_bank *b, const adsb_frame *list, uint32_t n, const uint64_t *src_prefix,
-                          uint32_t n_src)
-{
-    adsb_ctx *c = b->ctx;
-    HIPCHK(adsbk::launch_decode_fields(c->aux, list, nullptr, n, b->fields));
-    adsbk::TrackBankDev dev = b->dev;
-    dev.src_prefix = src_prefix;
-    dev.n_src = n_src;
-    adsbk::TrackArgs a{};
-    a.frames = list;
-    a.fields = b->fields;
-    a.n = n;
-    a.seconds_per_sample = b->cfg.seconds_per_sample;
-    const size_t nf = (size_t)b->cfg.max_frames;
-    a.keys = b->u32;
-    a.vals = b->u32 + nf;
-    a.skeys = b->u32 + 2 * nf;
-    a.svals = b->u32 + 3 * nf;
-    a.temp = b->temp;
-    a.temp_bytes = b->temp_bytes;
-    a.points = b->points;
-    a.table = &b->tab;
-    a.bank = &dev;
-    a.sum = b->sum.dev.out ? &b->sum.dev : nullptr;
-    HIPCHK(adsbk::launch_track(c->aux, a));
-    return ADSB_OK;
-}
-
-// Stages sample_base (and, for a host split, the counts' prefix) through meta_pinned; frames_host: also the frames.
-static int track_bank_stage(adsb_track_bank *b, const uint64_t *counts, const uint64_t *sample_base,
-                            const adsb_frame *frames_host, size_t n)
-{
-    adsb_ctx *c = b->ctx;
-    const uint32_t nr = b->cfg.n_receivers;
-    HIPCHK(hipEventSynchronize(b->copied)); // the previous update's copies out of the staging have finished
-    uint64_t *m = b->meta_pinned;
-    m[0] = 0;
-    for (uint32_t r = 0; r < nr; ++r) {
-        m[r + 1] = m[r] + (counts ? counts[r] : 0);
-        m[nr + 1 + r] = sample_base ? sample_base[r] : 0;
-    }
-    HIPCHK(hipMemcpyAsync(b->meta, m, sizeof(uint64_t) * (2 * nr + 1), hipMemcpyHostToDevice, c->aux));
-    if (frames_host) {
-        std::memcpy(b->pinned, frames_host, sizeof(adsb_frame) * n);
-        HIPCHK(hipMemcpyAsync(b->frames, b->pinned, sizeof(adsb_frame) * n, hipMemcpyHostToDevice, c->aux));
-    }
-    HIPCHK(hipEventRecord(b->copied, c->aux));
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_bank_update(adsb_track_bank *b, const adsb_frame *frames, size_t n, const uint64_t *counts,
-                                      const uint64_t *sample_base)
-{
-    if (!b || (!frames && n) || (!counts && n)) return ADSB_E_ARG;
-    if (counts) {
-        uint64_t sum = 0;
-        for (uint32_t r = 0; r < b->cfg.n_receivers; ++r) {
-            if (counts[r] > n - sum) return ADSB_E_ARG;
-            sum += counts[r];
-        }
-        if (sum != n) return ADSB_E_ARG;
-    }
-    if (n > b->cfg.max_frames) return ADSB_E_CAPACITY;
-    adsb_ctx *c = b->ctx;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    b->n_points = (uint32_t)n;
-    b->updated = true;
-    track_summaries_mark_update(b->sum); // an empty update: no summaries, an empty changed list
-    if (n == 0) return ADSB_OK;
-    hipPointerAttribute_t at{};
-    const bool on_device = hipPointerGetAttributes(&at, frames) == hipSuccess && at.type == hipMemoryTypeDevice &&
-                           at.device == c->cfg.device;
-    (void)hipGetLastError(); // a plain host pointer is an error to the query: do not leave it to the launches below
-    int rc = track_bank_stage(b, counts, sample_base, on_device ? nullptr : frames, n);
-    if (rc != ADSB_OK) return rc;
-    return track_bank_run(b, on_device ? frames : b->frames, (uint32_t)n, b->meta, b->cfg.n_receivers);
-}
-
-extern "C" int adsb_track_bank_update_launch(adsb_track_bank *b, const uint64_t *sample_base)
-{
-    if (!b) return ADSB_E_ARG;
-    adsb_ctx *c = b->ctx;
-    if (!c->launched) return ADSB_E_STATE;
-    if (c->last_channels > b->cfg.n_receivers) return ADSB_E_ARG;
-    int rc = sync_header(c); // the list's length, as adsb_fetch_counts (and the rebuild after a slot-pool overflow)
-    if (rc != ADSB_OK) return rc;
-    const uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
-    if (n > b->cfg.max_frames) return ADSB_E_CAPACITY;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    b->n_points = (uint32_t)n;
-    b->updated = true;
-    track_summaries_mark_update(b->sum); // an empty update: no summaries, an empty changed list
-    if (n == 0) return ADSB_OK;
-    if ((rc = track_bank_stage(b, nullptr, sample_base, nullptr, 0)) != ADSB_OK) return rc;
-    adsb_ctx::ResultSet &r = c->rs[c->last];
-    // the channel split as adsb_fetch's per_channel_counts reads it: chan_prefix clipped to the list
-    if ((rc = track_bank_run(b, c->last_out, (uint32_t)n, r.chan_prefix, c->last_channels)) != ADSB_OK) return rc;
-    if (c->own_aux) { // the launch that reuses this result set waits for these kernels too
-        HIPCHK(hipEventRecord(r.g_done, c->aux));
-        r.g_pending = true;
-    }
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_bank_fetch_points(adsb_track_bank *b, adsb_track_point *points, size_t max_points,
-                                            size_t *n_points)
-{
-    if (!b || (!points && max_points)) return ADSB_E_ARG;
-    if (!b->updated) return ADSB_E_STATE;
-    HIPCHK(hipSetDevice(b->ctx->cfg.device));
-    const size_t np = std::min<size_t>(b->n_points, max_points);
-    if (np) HIPCHK(hipMemcpyAsync(points, b->points, sizeof(adsb_track_point) * np, hipMemcpyDeviceToHost, b->ctx->aux));
-    HIPCHK(hipStreamSynchronize(b->ctx->aux));
-    if (n_points) *n_points = np;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_bank_fetch(adsb_track_bank *b, adsb_aircraft_record *aircraft, size_t max_aircraft,
-                                     size_t *n_aircraft, uint64_t *per_receiver_counts, uint32_t *flags)
-{
-    if (!b || (!aircraft && max_aircraft)) return ADSB_E_ARG;
-    adsb_ctx *c = b->ctx;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    const uint32_t nr = b->cfg.n_receivers, max_ac = b->cfg.max_aircraft;
-    std::vector<uint32_t> w(2 * (size_t)nr);
-    HIPCHK(hipMemcpyAsync(w.data(), b->words, sizeof(uint32_t) * w.size(), hipMemcpyDeviceToHost, c->aux));
-    HIPCHK(hipStreamSynchronize(c->aux));
-    size_t total = 0, copied = 0;
-    std::vector<adsbk::TrackRecord> recs;
-    for (uint32_t r = 0; r < nr; ++r) {
-        const size_t size = std::min<uint32_t>(w[r], max_ac);
-        total += size;
-        const size_t take = std::min(size, max_aircraft - copied);
-        if (take) { // slots are in admission order: sort each receiver's records by ICAO here
-            recs.resize(size);
-            HIPCHK(hipMemcpyAsync(recs.data(), b->dev.rec + (size_t)r * max_ac, sizeof(adsbk::TrackRecord) * size,
-                                  hipMemcpyDeviceToHost, c->aux));
-            HIPCHK(hipStreamSynchronize(c->aux));
-            sort_by_icao(recs);
-            for (size_t k = 0; k < take; ++k) aircraft[copied + k] = recs[k].a;
-        }
-        copied += take;
-        if (per_receiver_counts) per_receiver_counts[r] = take;
-        if (flags) flags[r] = w[nr + r];
-    }
-    if (n_aircraft) *n_aircraft = total;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_bank_expire(adsb_track_bank *b, const double *before)
-{
-    if (!b || !before) return ADSB_E_ARG;
-    adsbk::ExpireArgs a{};
-    for (uint32_t r = 0; r < b->cfg.n_receivers; ++r) { // n_receivers <= kMaxReceivers (create checks)
-        if (std::isnan(before[r])) return ADSB_E_ARG;
-        a.cut.before[r] = before[r];                     // by value in the kernel's arguments: no staging, no wait
-    }
-    HIPCHK(hipSetDevice(b->ctx->cfg.device));
-    const size_t n_rec = (size_t)b->cfg.n_receivers * b->cfg.max_aircraft;
-    a.table = &b->tab;
-    a.bank = &b->dev;
-    a.keep = b->exp_u32;
-    a.rank = b->exp_u32 + n_rec;
-    a.temp = b->exp_temp;
-    a.temp_bytes = b->exp_temp_bytes;
-    HIPCHK(adsbk::launch_track_expire(b->ctx->aux, a)); // after the bank's last update (same stream)
-    b->sum.changed_valid = false; // slots move
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_bank_summaries_reserve(adsb_track_bank *b)
-{
-    if (!b) return ADSB_E_ARG;
-    HIPCHK(hipSetDevice(b->ctx->cfg.device));
-    return track_summaries_reserve(b->sum, (size_t)b->cfg.max_frames, (size_t)b->cfg.n_receivers * b->cfg.max_aircraft);
-}
-
-extern "C" int adsb_track_bank_fetch_summaries(adsb_track_bank *b, adsb_aircraft_record *out, size_t max, size_t *n)
-{
-    if (!b || (!out && max)) return ADSB_E_ARG;
-    return track_summaries_fetch(b->ctx, b->sum, b->n_points, out, max, n);
-}
-
-extern "C" int adsb_track_bank_summaries_device(adsb_track_bank *b, const adsb_aircraft_record **dev)
-{
-    if (!b) return ADSB_E_ARG;
-    if (!b->sum.dev.out || !b->sum.updated) return ADSB_E_STATE;
-    if (dev) *dev = b->sum.dev.out;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_bank_fetch_changed(adsb_track_bank *b, adsb_aircraft_record *rec, double *last_heard,
-                                             adsb_velocity *velocity, size_t max, size_t *n,
-                                             uint64_t *per_receiver_counts)
-{
-    if (!b) return ADSB_E_ARG;
-    return track_summaries_fetch_changed(b->ctx, b->sum, b->dev.rec, b->n_points, b->cfg.max_aircraft,
-                                         b->cfg.n_receivers, rec, last_heard, velocity, max, n, per_receiver_counts);
-}
-
-// Waits; out[k] = get(record k) for the records in the order of adsb_track_bank_fetch; *n = records held in total
-template <class T, class Get>
-static int track_bank_fetch_each(adsb_track_bank *b, T *out, size_t max, size_t *n, Get get)
-{
-    if (!b || (!out && max)) return ADSB_E_ARG;
-    adsb_ctx *c = b->ctx;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    const uint32_t nr = b->cfg.n_receivers, max_ac = b->cfg.max_aircraft;
-    std::vector<uint32_t> w(nr);
-    HIPCHK(hipMemcpyAsync(w.data(), b->dev.size, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost, c->aux));
-    HIPCHK(hipStreamSynchronize(c->aux));
-    size_t total = 0, copied = 0;
-    std::vector<adsbk::TrackRecord> recs;
-    for (uint32_t r = 0; r < nr; ++r) { // the order of adsb_track_bank_fetch
-        const size_t size = std::min<uint32_t>(w[r], max_ac);
-        total += size;
-        const size_t take = std::min(size, max - copied);
-        if (take) {
-            recs.resize(size);
-            HIPCHK(hipMemcpyAsync(recs.data(), b->dev.rec + (size_t)r * max_ac, sizeof(adsbk::TrackRecord) * size,
-                                  hipMemcpyDeviceToHost, c->aux));
-            HIPCHK(hipStreamSynchronize(c->aux));
-            sort_by_icao(recs);
-            for (size_t k = 0; k < take; ++k) out[copied + k] = get(recs[k]);
-        }
-        copied += take;
-    }
-    if (n) *n = total;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_bank_fetch_last_heard(adsb_track_bank *b, double *last_heard, size_t max, size_t *n)
-{
-    return track_bank_fetch_each(b, last_heard, max, n, [](const adsbk::TrackRecord &r) { return r.last_heard; });
-}
-
-extern "C" int adsb_track_bank_fetch_velocity(adsb_track_bank *b, adsb_velocity *velocity, size_t max, size_t *n)
-{
-    return track_bank_fetch_each(b, velocity, max, n, [](const adsbk::TrackRecord &r) { return r.vel; });
-}
-
-// ---- the fused view of a bank: one record per ICAO over all receivers (adsb_track.hip, launch_track_fuse) ----
-extern "C" int adsb_track_bank_fuse_reserve(adsb_track_bank *b, size_t max_fused)
-{
-    if (!b) return ADSB_E_ARG;
-    adsb_ctx *c = b->ctx;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    HIPCHK(hipStreamSynchronize(c->aux)); // a fuse may still read what is freed here
-    track_bank_fuse_free(b);
-    const uint32_t nr = b->cfg.n_receivers;
-    const size_t places = (size_t)nr * b->cfg.max_aircraft;
-    const size_t cap = max_fused == 0 || max_fused > places ? places : max_fused; // more than `places` cannot occur
-    const size_t key_bytes = nr > adsbk::kFuseWideReceivers ? sizeof(uint64_t) : sizeof(uint32_t);
-    b->fuse_temp_bytes = adsbk::track_fuse_temp_bytes(places, nr);
-    b->fuse_lanes = nr == 1 ? 1u : 4u; // measured: DESIGN 4.4f (16 and 64 lanes lost on runs of 64 and of 1 alike)
-    if (const char *fl = getenv("ADSB_FUSE_LANES")) { // measurement knob: lanes per ICAO in the reduction
-        const int v = atoi(fl);
-        if (v == 1 || v == 4) b->fuse_lanes = (uint32_t)v;
-    }
-    const bool ok = hipMalloc(&b->fuse_keys, 2 * key_bytes * places) == hipSuccess &&
-                    hipMalloc((void **)&b->fuse_vals, 2 * sizeof(uint32_t) * places) == hipSuccess &&
-                    hipMalloc((void **)&b->fuse_start, sizeof(uint32_t) * cap) == hipSuccess &&
-                    hipMalloc((void **)&b->fuse_out, sizeof(adsb_fused_aircraft) * cap) == hipSuccess &&
-                    hipMalloc((void **)&b->fuse_counts, sizeof(uint64_t) * 3) == hipSuccess &&
-                    hipMalloc(&b->fuse_temp, b->fuse_temp_bytes) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        track_bank_fuse_free(b);
-        return ADSB_E_NOMEM;
-    }
-    b->fuse_max = cap;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_bank_fuse(adsb_track_bank *b, double since)
-{
-    if (!b || std::isnan(since)) return ADSB_E_ARG;
-    if (!b->fuse_max) return ADSB_E_STATE;
-    HIPCHK(hipSetDevice(b->ctx->cfg.device));
-    const size_t places = (size_t)b->cfg.n_receivers * b->cfg.max_aircraft;
-    const size_t key_bytes = b->cfg.n_receivers > adsbk::kFuseWideReceivers ? sizeof(uint64_t) : sizeof(uint32_t);
-    adsbk::FuseArgs a{};
-    a.bank = &b->dev;
-    a.since = since;                 // by value in the kernel's arguments, as expire's cuts: no staging, no wait
-    a.keys = b->fuse_keys;
-    a.skeys = (char *)b->fuse_keys + key_bytes * places;
-    a.vals = b->fuse_vals;
-    a.svals = b->fuse_vals + places;
-    a.seg_start = b->fuse_start;
-    a.out = b->fuse_out;
-    a.counts = b->fuse_counts;
-    a.max_fused = b->fuse_max;
-    a.temp = b->fuse_temp;
-    a.temp_bytes = b->fuse_temp_bytes;
-    a.lanes = b->fuse_lanes;
-    HIPCHK(adsbk::launch_track_fuse(b->ctx->aux, a)); // after the bank's last update / expire / reset (same stream)
-    b->fused = true;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_bank_fetch_fused(adsb_track_bank *b, adsb_fused_aircraft *out, size_t max, size_t *n,
-                                           size_t *n_total, uint32_t *flags)
-{
-    if (!b || (!out && max)) return ADSB_E_ARG;
-    if (!b->fused) return ADSB_E_STATE;
-    adsb_ctx *c = b->ctx;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    uint64_t w[3];
-    HIPCHK(hipMemcpyAsync(w, b->fuse_counts, sizeof(w), hipMemcpyDeviceToHost, c->aux));
-    HIPCHK(hipStreamSynchronize(c->aux));
-    const size_t take = std::min<size_t>(std::min<uint64_t>(w[0], b->fuse_max), max);
-    if (take) {
-        HIPCHK(hipMemcpyAsync(out, b->fuse_out, sizeof(adsb_fused_aircraft) * take, hipMemcpyDeviceToHost, c->aux));
-        HIPCHK(hipStreamSynchronize(c->aux));
-    }
-    if (n) *n = take;
-    if (n_total) *n_total = (size_t)w[1];
-    if (flags) *flags = (uint32_t)w[2];
-    return ADSB_OK;
-}
-
-extern "C" int adsb_track_bank_fused_device(adsb_track_bank *b, const adsb_fused_aircraft **fused_dev,
-                                            const uint64_t **counts_dev)
-{
-    if (!b) return ADSB_E_ARG;
-    if (!b->fused) return ADSB_E_STATE;
-    if (fused_dev) *fused_dev = b->fuse_out;
-    if (counts_dev) *counts_dev = b->fuse_counts;
-    return ADSB_OK;
-}
 
 extern "C" int adsb_set_result_target(adsb_ctx *c, void *blob_dev, size_t blob_bytes)
 {

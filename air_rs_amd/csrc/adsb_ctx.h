@@ -1,0 +1,109 @@
+// adsb_ctx.h -- what the two halves of the C boundary share: the context (adsb_api.cpp owns it; adsb_track_api.cpp
+// reads the last launch and uses the tracker scratch), the error macro, and the one function the tracker needs from
+// adsb_api.cpp.  Internal.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "adsb_kernels.h"
+
+constexpr int kTimingRing = 512;
+
+struct adsb_ctx {
+    adsb_cfg cfg{};
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    int mag_mode = 0;
+    uint32_t bps = 2; // bytes per IQ sample
+
+    // device buffers
+    void *staging = nullptr;        // host-fed input (cfg.host_staging)
+    // Two result sets, used alternately: the ordering pass of launch i runs on `aux` while the
+    // demod kernel of launch i+1 already runs on `stream` (they touch different sets).
+    struct ResultSet {
+        adsbk::Seg *seg = nullptr;       // [n_tiles_max]
+        adsb_frame *slots = nullptr;     // [n_tiles_max * kQuota] fixed region, then the pool [cap_slots]
+        adsb_frame *out = nullptr;       // [max_out]
+        adsbk::Header *hdr = nullptr;
+        uint64_t *chan_prefix = nullptr; // [max_channels + 1]: frames before each channel's first tile; last = total
+        hipEvent_t k_done = nullptr, g_done = nullptr;
+        bool g_pending = false;
+        // the launch whose results this set holds (the streaming front end fetches the older of two launches
+        // in flight: view_launch() makes it the one the fetch / re-plan code below works on)
+        struct Launch {
+            const void *iq = nullptr;
+            uint32_t channels = 0, tpc = 0, tiles = 0, cap = 0, idx = 0;
+            uint64_t samples = 0, stride = 0, base = 0;
+            adsb_frame *out = nullptr;
+            bool valid = false;
+        } li;
+    } rs[2];
+    hipStream_t aux = nullptr;      // ordering pass + result copies (== stream unless ADSB_OVERLAP_ORDERING=1)
+    bool own_aux = false;
+    adsb_packet_fields *fields = nullptr; // [max_out], allocated on first adsb_decode_fields_device_async
+    bool fields_current = false;    // fields[] belongs to the last launch
+    // tracker (allocated on first adsb_track_device)
+    uint32_t *trk_u32 = nullptr;    // 4 x [max_out]: keys, vals, sorted keys, sorted vals
+    void *trk_temp = nullptr;
+    size_t trk_temp_bytes = 0;
+    adsb_track_point *trk_points = nullptr;      // [max_out]
+    adsb_aircraft_record *trk_aircraft = nullptr; // [max_out]
+    uint64_t *trk_n_aircraft = nullptr;
+    uint32_t trk_n = 0;             // frames the last tracker run covered
+    bool trk_done = false;
+    void *ext_blob = nullptr;       // caller-owned [32-byte header | frames] target for the next launches
+    size_t ext_frames = 0;          // frame capacity of ext_blob
+    adsb_frame *last_out = nullptr; // where the last launch's ordered list went
+    uint32_t last_cap = 0;
+    bool fused_pass_only = false;   // adsb_debug_fused_pass_only (measurement)
+    uint64_t stream_base = 0;       // adsb_set_stream_base: added to the offsets of the following launches
+    uint64_t last_base = 0;         // ... of the last launch (re-runs of its tiles use the same)
+    uint32_t launch_idx = 0;        // launches so far
+    uint32_t last = 0;              // result set of the last launch
+    uint32_t *out_start = nullptr;  // [n_tiles_max + 1]  (slot-overflow re-run path only)
+    uint64_t *lb = nullptr;         // finish_order's exchange words: one per workgroup, then one per 64 workgroups
+    uint32_t lb_groups_at = 0;
+    uint32_t *scratch = nullptr;    // 16 dwords: probe result, read-kernel sink
+    unsigned long long *stamps = nullptr; // cycle counters of diagnostic builds (64 bytes per tile with -DADSB_TILE_STAMPS=1)
+    size_t stamps_bytes = 0;
+    int scan = adsbk::kScanRoot;    // which i8 scan kernel (ADSB_SCAN=nsq selects the A/B kernel at adsb_create)
+    // The one-dispatch path for small buffers (adsbk::launch_small): per result set a pinned, device-writable blob
+    // [32-byte header | frames | u64 sequence number] and a device counter; a pinned input buffer for adsb_demod().
+    struct Small {
+        bool enabled = true, ready = false;
+        char *blob[2] = {nullptr, nullptr};
+        uint32_t cap = 0;            // frames per blob
+        uint32_t *done = nullptr;    // device: 2 words
+        char *in_host = nullptr;     // pinned copy of adsb_demod()'s buffer (allocated on first use)
+        uint64_t seq = 0;
+        uint64_t max_samples = 0;    // longest buffer the path takes
+    } sm;
+    bool pool_off = false;          // adsb_debug_pool_limit: the shared slot pool hands out nothing (test knob)
+    uint32_t stall_blk = 0xFFFFFFFFu; // adsb_debug_finish_stall: this workgroup of finish_order withholds its exchange word (test knob)
+    uint32_t cap_slots = 0;
+    uint32_t n_tiles_max = 0;
+
+    // pinned host mirrors
+    adsbk::Header *hdr_host = nullptr;
+
+    // last launch
+    bool launched = false;
+    const void *last_iq = nullptr;
+    uint32_t last_channels = 0;
+    uint64_t last_samples = 0, last_stride = 0;
+    uint32_t last_tpc = 0, last_tiles = 0;
+
+    // timing
+    int timing = 0;                 // 0 off; N: events on every N-th launch
+    hipEvent_t ev[kTimingRing][4] = {}; // scan kernel, finishing kernel: start/end each
+    bool ev_made = false;
+    uint32_t ev_count = 0;
+};
+
+#define HIPCHK(x)                                  \
+    do {                                           \
+        hipError_t e_ = (x);                       \
+        if (e_ != hipSuccess) return (int)e_;      \
+    } while (0)
+
+// Waits for the last launch's header in c->hdr_host (and rebuilds the list after a slot-pool overflow): adsb_api.cpp
+__attribute__((visibility("hidden"))) int sync_header(adsb_ctx *c);

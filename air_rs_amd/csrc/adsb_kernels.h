@@ -1,5 +1,5 @@
-// adsb_kernels.h -- launch interface between the C-ABI layer (adsb_api.cpp) and the gfx950
-// kernels (adsb_kernels.hip).  Internal; the public boundary is include/adsb_hip.h.
+// adsb_kernels.h -- launch interface between the C-ABI layer (adsb_api.cpp, adsb_track_api.cpp) and the gfx950
+// kernels (adsb_kernels.hip, adsb_track.hip).  Internal; the public boundary is include/adsb_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -178,32 +178,34 @@ struct TrackRecord {
 };
 static_assert(sizeof(TrackRecord) == 128, "TrackRecord: one cache line; the header's memory figures assume 128 bytes");
 constexpr uint32_t kTrackUntracked = 0xFFFFFFFFu; // slot of an aircraft the full table turned away
-struct TrackTableDev {
-    uint32_t *index;             // [1 << 24]: ICAO -> record slot + 1, 0 = absent
-    TrackRecord *rec;            // [max_aircraft]
-    uint32_t *size_flags;        // device words: [0] records in use, [1] ADSB_TRACK_TABLE_FULL, [2] / [3] staging of
-                                 // [0] for the update's admission / for expire
-    uint32_t max_aircraft;
-    uint32_t *slot;              // [n] scratch: record slot + 1 of each sorted frame's aircraft (kTrackUntracked)
-};
-// A bank of persistent tables, one per receiver (adsb_track_bank_*): sort key = receiver << 24 | icao, an open-addressing
-// hash of that key -> record slot + 1 instead of the table's direct ICAO index, per-receiver sizes and flags.
-struct TrackBankDev {
-    unsigned long long *hash;    // [hash_mask + 1]: (record slot + 1) << 32 | key, 0 = empty (insert by atomicCAS)
-    uint64_t hash_mask;          // capacity - 1, capacity a power of two >= 2 x n_receivers x max_aircraft
+// The three forms of the tracker: one launch's list from an empty map (adsb_track_device), a persistent table
+// (adsb_track_table_*), a bank of persistent tables, one per receiver (adsb_track_bank_*).  The one thing that tells them
+// apart, in TrackArgs / ExpireArgs and as the kernels' template parameter.
+enum class TrackKind : uint32_t { kLaunch, kTable, kBank };
+// The device view of a table or bank.  A table is the n_receivers == 1 case of the common part and finds an aircraft
+// through a direct ICAO index; a bank sorts by receiver << 24 | icao and probes an open-addressing hash of that key
+// (a direct index per receiver would cost 64 MiB each), with per-frame scan words of its own.
+struct TrackStoreDev {
+    // common
     TrackRecord *rec;            // [n_receivers x max_aircraft]: receiver r's records at [r x max_aircraft, ...)
+    uint32_t max_aircraft;       // per receiver
+    uint32_t n_receivers;        // a table: 1
     uint32_t *size;              // [n_receivers] records in use
     uint32_t *flags;             // [n_receivers] ADSB_TRACK_TABLE_FULL
     uint32_t *size_next;         // [n_receivers] staging: the admission kernel's new sizes, moved to size by the pairs
                                  // kernel; expire stages the old sizes here
-    uint32_t max_aircraft;       // per receiver
-    uint32_t n_receivers;
+    uint32_t *slot;              // [n] scratch: record slot + 1 of each sorted frame's aircraft (kTrackUntracked)
+    // table only
+    uint32_t *index;             // [1 << 24]: ICAO -> record slot + 1, 0 = absent
+    // bank only
+    unsigned long long *hash;    // [hash_mask + 1]: (record slot + 1) << 32 | key, 0 = empty (insert by atomicCAS)
+    uint64_t hash_mask;          // capacity - 1, capacity a power of two >= 2 x n_receivers x max_aircraft
+    uint32_t key_bits;           // 24 + ceil(log2 n_receivers)
     uint32_t *prefix;            // [n_receivers + 1]: frames of the list before each receiver's first (last = n); also
                                  // where each receiver's first frame sits in sorted order
     const uint64_t *sample_base; // [n_receivers]: frame time = (sample_base[r] + offset) x seconds_per_sample
     const uint64_t *src_prefix;  // [n_src + 1] (device): the receiver split as given (host counts' prefix, or the
     uint32_t n_src;              // launch's chan_prefix); clipped to n into `prefix`, receivers >= n_src get nothing
-    uint32_t key_bits;           // 24 + ceil(log2 n_receivers)
     unsigned long long *mark;    // [n] per sorted frame: segment head << 32 | head of a key the hash does not hold
     unsigned long long *excl;    // [n] exclusive scan of mark
     uint32_t *seg_slot;          // [n] per segment (hi of the scan): record slot + 1 (kTrackUntracked)
@@ -237,10 +239,10 @@ struct TrackArgs {
     adsb_aircraft_record *aircraft; // [max_aircraft], ascending ICAO (per-launch form only)
     uint32_t max_aircraft;
     uint64_t *n_aircraft;        // device word (per-launch form only)
-    const TrackTableDev *table;  // nullptr: start from an empty map and summarise into `aircraft` (adsb_track_device);
-                                 // otherwise pair with and merge into the persistent table (adsb_track_table_update)
-    const TrackBankDev *bank;    // non-null: the list holds several receivers' frames (adsb_track_bank_update); `table`
-                                 // then carries the bank's records in rec and the per-frame slot scratch in slot
+    TrackKind kind;              // kLaunch: start from an empty map and summarise into `aircraft` (adsb_track_device);
+                                 // kTable: pair with and merge into the persistent table (adsb_track_table_update);
+                                 // kBank: the list holds several receivers' frames (adsb_track_bank_update)
+    const TrackStoreDev *store;  // the table / bank (kLaunch: unused)
     const TrackSumDev *sum;      // non-null (table / bank only): also the per-frame summaries and the changed list
 };
 // expire (adsb_track_table_expire / adsb_track_bank_expire): a record survives unless last_heard < before[receiver]
@@ -249,8 +251,8 @@ struct ExpireCut {
     double before[kMaxReceivers]; // [0] for a table
 };
 struct ExpireArgs {
-    const TrackTableDev *table;  // the table, or for a bank its records (rec) and max_aircraft
-    const TrackBankDev *bank;    // nullptr: a table
+    TrackKind kind;              // kTable or kBank
+    const TrackStoreDev *store;
     ExpireCut cut;
     uint32_t *keep, *rank;       // [n_rec] each, n_rec = max_aircraft (x n_receivers)
     void *temp;
@@ -274,7 +276,7 @@ static_assert(sizeof(adsb_fused_aircraft) == 128 && offsetof(adsb_fused_aircraft
               "adsb_fused_aircraft: one cache line, an adsb_velocity bit for bit at offset 80");
 constexpr uint32_t kFuseWideReceivers = 128; // above this, ICAO << 8 | receiver plus the 'no record' bit needs 33 bits
 struct FuseArgs {
-    const TrackBankDev *bank;
+    const TrackStoreDev *bank;
     double since;                // a record contributes iff it is held and last_heard >= since
     void *keys, *skeys;          // [places] each, places = n_receivers x max_aircraft: uint32_t sort keys, uint64_t with
                                  // more than kFuseWideReceivers receivers; keys is reused after the sort

@@ -17,7 +17,8 @@
 // Time is sample offset x seconds_per_sample (the reference stamps packets with the wall clock, which
 // is excluded from parity).  O(frames) work, a few MB: a latency-bound epilogue.
 //
-// The same kernels also serve a persistent aircraft table (adsb_track_table_*, TrackTableDev): the reference
+// The same kernels also serve a persistent aircraft table (adsb_track_table_*; TrackKind::kTable, its device view a
+// TrackStoreDev with one receiver): the reference
 // keeps ONE HashMap<u32, Aircraft> for the life of its display thread (tui.rs:22-42, web.rs:115), so a pair may
 // straddle two launches.  With a table, two steps go between 1. and 2.:
 //   1a. per segment, the aircraft's record slot from a direct ICAO index (2^24 words, 0 = absent);
@@ -27,14 +28,19 @@
 // even / odd position message from before this list; 3. merges the segment into the record in place (one
 // thread per segment = per distinct ICAO: no atomics).
 //
-// A bank (adsb_track_bank_*, TrackBankDev) is N such tables, one per receiver, updated by ONE dispatch sequence over a
-// multi-channel list (receiver r's frames, then receiver r+1's, ...).  The sort key becomes receiver << 24 | icao over
-// 24 + ceil(log2 N) bits, so segments never mix receivers and receiver r's frames sit at [prefix[r], prefix[r+1]) in
-// sorted order.  A direct 2^24 index per receiver would cost 64 MiB x N, so 1a probes an open-addressing hash of the
-// key instead, once per segment head; 1b scans (segment head, new key) pairs in one 64-bit word, which gives every
-// frame its segment and every new key its rank, made per receiver by subtracting the rank at prefix[r].  Slots come
-// from that rank alone (receiver r's records live at [r x max_aircraft, (r+1) x max_aircraft)), never from where the
-// hash put an entry, so no result depends on insert order.
+// A bank (adsb_track_bank_*; TrackKind::kBank, the same TrackStoreDev with N receivers) is N such tables, one per
+// receiver, updated by ONE dispatch sequence over a multi-channel list (receiver r's frames, then receiver r+1's,
+// ...).  The sort key becomes receiver << 24 | icao over 24 + ceil(log2 N) bits, so segments never mix receivers and
+// receiver r's frames sit at [prefix[r], prefix[r+1]) in sorted order.  A direct 2^24 index per receiver would cost 64
+// MiB x N, so 1a probes an open-addressing hash of the key instead, once per segment head; 1b scans (segment head, new
+// key) pairs in one 64-bit word, which gives every frame its segment and every new key its rank, made per receiver by
+// subtracting the rank at prefix[r].  Slots come from that rank alone (receiver r's records live at [r x max_aircraft,
+// (r+1) x max_aircraft)), never from where the hash put an entry, so no result depends on insert order.
+//
+// Table and bank share everything but how a segment finds its record slot (keys, lookup, admit: the table's direct
+// index with a 32-bit scan, the bank's hash with a 64-bit one).  What follows admission -- pairs, summaries, merge, and
+// expire's mark and compaction -- is one kernel template over TrackKind that reads the state words size[r], flags[r],
+// size_next[r] of receiver r, r = 0 for a table.
 //
 // Expire (adsb_track_table_expire / adsb_track_bank_expire) evicts every record whose last frame of any kind is older
 // than a cut, without a host round trip: a mark kernel flags the survivors of [0, size) (sized by max_aircraft, the
@@ -240,24 +246,24 @@ __global__ __launch_bounds__(256) void track_lookup_kernel(const uint32_t *skeys
 }
 
 // table only, 1b: rank = exclusive scan of is_new; new aircraft get the slots size, size + 1, ... in ascending ICAO
-// order while they are below max_aircraft.  The new size goes to size_flags[2] (every thread here reads [0]);
-// track_pairs_kernel moves it to [0].
+// order while they are below max_aircraft.  The new size goes to size_next[0] (every thread here reads size[0]);
+// track_pairs_kernel moves it to size[0].
 __global__ __launch_bounds__(256) void track_admit_kernel(const uint32_t *skeys, uint32_t n, const uint32_t *is_new,
-                                                          const uint32_t *rank, TrackTableDev t)
+                                                          const uint32_t *rank, TrackStoreDev t)
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
-    const uint32_t size0 = t.size_flags[0];
+    const uint32_t size0 = t.size[0];
     if (s + 1 == n) {
         const uint64_t grown = (uint64_t)size0 + rank[s] + is_new[s];
-        t.size_flags[2] = grown < t.max_aircraft ? (uint32_t)grown : t.max_aircraft;
+        t.size_next[0] = grown < t.max_aircraft ? (uint32_t)grown : t.max_aircraft;
     }
     if (t.slot[s] != 0) return; // the table holds this aircraft
     const bool head = is_new[s] != 0;
     const uint64_t r = (uint64_t)size0 + rank[s] - (head ? 0u : 1u); // a non-head follows its head's 1 in the scan
     if (r >= t.max_aircraft) {
         t.slot[s] = kTrackUntracked;
-        if (head) atomicOr(&t.size_flags[1], ADSB_TRACK_TABLE_FULL);
+        if (head) atomicOr(&t.flags[0], ADSB_TRACK_TABLE_FULL);
         return;
     }
     t.slot[s] = (uint32_t)r + 1u;
@@ -269,7 +275,7 @@ __global__ __launch_bounds__(256) void track_admit_kernel(const uint32_t *skeys,
 
 // bank only: the receiver split clipped to the list (prefix[0] = 0, prefix[k] = n for k >= n_src), as adsb_fetch's
 // per_channel_counts cut the first n frames
-__device__ __forceinline__ uint32_t bank_prefix(const TrackBankDev &b, uint32_t k, uint32_t n)
+__device__ __forceinline__ uint32_t bank_prefix(const TrackStoreDev &b, uint32_t k, uint32_t n)
 {
     if (k == 0) return 0;
     if (k >= b.n_src) return n;
@@ -291,7 +297,7 @@ __device__ __forceinline__ uint64_t bank_hash(uint32_t key) // fmix64 (MurmurHas
 // bank only: key = receiver << 24 | icao (receiver of frame i: the last k with prefix[k] <= i); threads 0..N also
 // write the clipped prefix the later kernels read
 __global__ __launch_bounds__(256) void track_bank_keys_kernel(const adsb_packet_fields *fields, uint32_t n,
-                                                              TrackBankDev b, uint32_t *keys, uint32_t *vals)
+                                                              TrackStoreDev b, uint32_t *keys, uint32_t *vals)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i <= b.n_receivers) b.prefix[i] = bank_prefix(b, i, n);
@@ -309,8 +315,7 @@ __global__ __launch_bounds__(256) void track_bank_keys_kernel(const adsb_packet_
 }
 
 // bank only, 1a: segment heads probe the hash (slot[s] = record slot + 1 or 0); mark = head << 32 | new key
-__global__ __launch_bounds__(256) void track_bank_lookup_kernel(const uint32_t *skeys, uint32_t n, TrackBankDev b,
-                                                                uint32_t *slot)
+__global__ __launch_bounds__(256) void track_bank_lookup_kernel(const uint32_t *skeys, uint32_t n, TrackStoreDev b)
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
@@ -328,7 +333,7 @@ __global__ __launch_bounds__(256) void track_bank_lookup_kernel(const uint32_t *
             break;
         }
     }
-    slot[s] = found;
+    b.slot[s] = found;
     b.mark[s] = 1ull << 32 | (found ? 0u : 1u);
 }
 
@@ -337,8 +342,7 @@ __global__ __launch_bounds__(256) void track_bank_lookup_kernel(const uint32_t *
 // inserts it into the hash (distinct keys: no two threads insert the same one) and publishes its segment's slot in
 // seg_slot.  The last frame of each receiver stages the receiver's new size in size_next (every thread here reads
 // size); track_pairs_kernel moves it.
-__global__ __launch_bounds__(256) void track_bank_admit_kernel(const uint32_t *skeys, uint32_t n, TrackBankDev b,
-                                                               const uint32_t *slot)
+__global__ __launch_bounds__(256) void track_bank_admit_kernel(const uint32_t *skeys, uint32_t n, TrackStoreDev b)
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
@@ -351,8 +355,8 @@ __global__ __launch_bounds__(256) void track_bank_admit_kernel(const uint32_t *s
     }
     if (!(m >> 32)) return; // not a segment head
     const uint32_t g = (uint32_t)(e >> 32);
-    if (slot[s] != 0) { // the receiver holds this aircraft
-        b.seg_slot[g] = slot[s];
+    if (b.slot[s] != 0) { // the receiver holds this aircraft
+        b.seg_slot[g] = b.slot[s];
         return;
     }
     const uint64_t local = (uint64_t)size0 + (uint32_t)e - rank0;
@@ -369,39 +373,35 @@ __global__ __launch_bounds__(256) void track_bank_admit_kernel(const uint32_t *s
     b.seg_slot[g] = a + 1u;
 }
 
-template <bool kBank>
+// d: the table / bank (kLaunch: unused, tail_flag instead).  r: the frame's receiver, 0 for a table.
+template <TrackKind K>
 __global__ __launch_bounds__(256) void track_pairs_kernel(const adsb_frame *frames, const adsb_packet_fields *fields,
                                                           const uint32_t *skeys, const uint32_t *svals, uint32_t n,
                                                           double seconds_per_sample, uint64_t sample_base,
-                                                          TrackTableDev t, TrackBankDev b, adsb_track_point *points,
+                                                          TrackStoreDev d, adsb_track_point *points,
                                                           uint32_t *tail_flag)
 {
+    constexpr bool kBank = K == TrackKind::kBank, kStore = K != TrackKind::kLaunch;
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
-    const bool table = t.rec != nullptr;
     const uint32_t key = skeys[s], i = svals[s];
-    const uint32_t icao = kBank ? key & 0xFFFFFFu : key;
+    const uint32_t icao = kBank ? key & 0xFFFFFFu : key, r = kBank ? key >> 24 : 0u;
     adsb_track_point pt;
     pt.latitude = 0.0;
     pt.longitude = 0.0;
     pt.icao = icao;
     pt.flags = 0;
     uint32_t slot = 0;
-    if (kBank) { // every frame takes its segment's slot (seg_slot) and keeps it in t.slot for track_summary_kernel
-        const uint32_t r = key >> 24;
-        sample_base = b.sample_base[r];
-        if (s + 1 == b.prefix[r + 1]) b.size[r] = b.size_next[r]; // nothing reads size in this kernel
-        const bool head = s == 0 || skeys[s - 1] != key;
-        slot = b.seg_slot[(uint32_t)(b.excl[s] >> 32) - (head ? 0u : 1u)];
-        t.slot[s] = slot;
-        if (slot == kTrackUntracked) {
-            pt.flags = ADSB_TRACK_UNTRACKED;
-            points[i] = pt;
-            return;
+    if (kStore) {
+        if (kBank) sample_base = d.sample_base[r];
+        if (s + 1 == (kBank ? d.prefix[r + 1] : n)) d.size[r] = d.size_next[r]; // nothing reads size in this kernel
+        if (kBank) { // every frame takes its segment's slot (seg_slot) and keeps it in d.slot for the kernels below
+            const bool head = s == 0 || skeys[s - 1] != key;
+            slot = d.seg_slot[(uint32_t)(d.excl[s] >> 32) - (head ? 0u : 1u)];
+            d.slot[s] = slot;
+        } else {
+            slot = d.slot[s];
         }
-    } else if (table) {
-        if (s + 1 == n) t.size_flags[0] = t.size_flags[2]; // nothing reads [0] in this kernel
-        slot = t.slot[s];
         if (slot == kTrackUntracked) { // turned away by the full table: only icao is valid
             pt.flags = ADSB_TRACK_UNTRACKED;
             points[i] = pt;
@@ -434,14 +434,14 @@ __global__ __launch_bounds__(256) void track_pairs_kernel(const adsb_frame *fram
             p_lon = g.cpr_longitude;
             break;
         }
-        if (open && table) { // the walk reached the segment start: the partner is the record's, from an earlier list
-            const TrackRecord &r = t.rec[slot - 1];
-            if (r.have & (i_odd ? 1u : 2u)) {
-                const double t_j = i_odd ? r.t_even : r.t_odd;
+        if (open && kStore) { // the walk reached the segment start: the partner is the record's, from an earlier list
+            const TrackRecord &rec = d.rec[slot - 1];
+            if (rec.have & (i_odd ? 1u : 2u)) {
+                const double t_j = i_odd ? rec.t_even : rec.t_odd;
                 if (!(fabs(t_i - t_j) > 10.0)) {
                     pair = true;
-                    p_lat = i_odd ? r.even_lat : r.odd_lat;
-                    p_lon = i_odd ? r.even_lon : r.odd_lon;
+                    p_lat = i_odd ? rec.even_lat : rec.odd_lat;
+                    p_lon = i_odd ? rec.even_lon : rec.odd_lon;
                 }
             }
         }
@@ -461,41 +461,34 @@ __global__ __launch_bounds__(256) void track_pairs_kernel(const adsb_frame *fram
 
 // one thread per segment tail: without a table, the aircraft's record from an empty map into out[tail_pos];
 // with one (or a bank), this list's frames merged into the aircraft's record in place
-template <bool kBank>
+template <TrackKind K>
 __global__ __launch_bounds__(256) void track_summary_kernel(const adsb_frame *frames, const adsb_packet_fields *fields,
                                                             const adsb_track_point *points, const uint32_t *skeys,
                                                             const uint32_t *svals, const uint32_t *tail_flag,
                                                             const uint32_t *tail_pos, uint32_t n,
                                                             double seconds_per_sample, uint64_t sample_base,
-                                                            TrackTableDev t, TrackBankDev b, adsb_aircraft_record *out,
+                                                            TrackStoreDev d, adsb_aircraft_record *out,
                                                             uint32_t max_aircraft, uint64_t *n_aircraft)
 {
+    constexpr bool kBank = K == TrackKind::kBank, table = K != TrackKind::kLaunch; // table: a table or a bank
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
-    const bool table = t.rec != nullptr;
     const uint32_t key = skeys[s];
     const uint32_t icao = kBank ? key & 0xFFFFFFu : key;
-    if (kBank) sample_base = b.sample_base[key >> 24];
+    if (kBank) sample_base = d.sample_base[key >> 24];
     uint32_t a;
     TrackRecord r;
     if (table) {
         if (s + 1 != n && skeys[s + 1] == key) return;
-        a = t.slot[s];
+        a = d.slot[s];
         if (a == kTrackUntracked) return;
-        r = t.rec[--a];
+        r = d.rec[--a];
     } else {
         if (!tail_flag[s]) return;
         if (s + 1 == n) *n_aircraft = (uint64_t)tail_pos[s] + 1u;
         a = tail_pos[s];
         if (a >= max_aircraft) return;
-        r.a.icao = icao;
-        r.a.altitude = 0;
-        r.a.latitude = 0.0;
-        r.a.longitude = 0.0;
-        r.a.last_contact = __builtin_nan("");
-        r.a.has_position = 0;
-        r.a.n_frames = 0;
-        for (int k = 0; k < 8; ++k) r.a.callsign[k] = 0;
+        r.a = empty_record(icao).a;
     }
     bool have_id = false, have_pos_msg = false, have_fix = false, have_even = false, have_odd = false;
     uint32_t count = 0, vel_j = kTrackUntracked; // vel_j: the newest velocity message (table / bank only)
@@ -545,7 +538,7 @@ __global__ __launch_bounds__(256) void track_summary_kernel(const adsb_frame *fr
         if (vel_j != kTrackUntracked)
             (void)velocity_decode(frames[vel_j].bytes, frame_time(frames, vel_j, sample_base, seconds_per_sample),
                                   r.vel);
-        t.rec[a] = r;
+        d.rec[a] = r;
     } else {
         out[a] = r.a;
     }
@@ -592,30 +585,31 @@ struct SumOp {
     }
 };
 
-// One thread per sorted frame s, after the scan and BEFORE the merge (t.rec[slot] still is the record from before this
+// One thread per sorted frame s, after the scan and BEFORE the merge (d.rec[slot] still is the record from before this
 // update; admission wrote empty_record for a new aircraft): the aircraft as Aircraft::handle_packet leaves it after
 // frame s, from at most three source frames and that record, with the merge's expressions, stored at the frame's list
 // index.  A segment tail also puts its record slot on the changed list at its rank.
-template <bool kBank>
+template <TrackKind K>
 __global__ __launch_bounds__(256) void track_frame_summary_kernel(const adsb_frame *frames,
                                                                   const adsb_packet_fields *fields,
                                                                   const adsb_track_point *points, const uint32_t *skeys,
                                                                   const uint32_t *svals, uint32_t n,
                                                                   double seconds_per_sample, uint64_t sample_base,
-                                                                  TrackTableDev t, TrackBankDev b, TrackSumDev sum)
+                                                                  TrackStoreDev d, TrackSumDev sum)
 {
+    constexpr bool kBank = K == TrackKind::kBank;
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
-    const uint32_t key = skeys[s], i = svals[s], slot = t.slot[s];
+    const uint32_t key = skeys[s], i = svals[s], slot = d.slot[s];
     const uint32_t icao = kBank ? key & 0xFFFFFFu : key;
-    if (kBank) sample_base = b.sample_base[key >> 24];
+    if (kBank) sample_base = d.sample_base[key >> 24];
     const TrackSumTuple w = sum.scan[s];
     if (s + 1 == n) *sum.n_changed = w.cnt;
     adsb_aircraft_record r;
     if (slot == kTrackUntracked) {
         r = empty_record(icao).a;
     } else {
-        r = t.rec[slot - 1].a;
+        r = d.rec[slot - 1].a;
         r.icao = icao;
         if (w.id) {
             const adsb_packet_fields g = fields[svals[w.id - 1]];
@@ -649,67 +643,58 @@ __global__ __launch_bounds__(256) void track_changed_gather_kernel(const TrackRe
     ((uint4 *)(out + g))[lane] = ((const uint4 *)(rec + changed[g]))[lane];
 }
 
-template <bool kBank>
-hipError_t launch_frame_summaries(hipStream_t st, const TrackArgs &a, const TrackTableDev &t, const TrackBankDev &b)
+template <TrackKind K>
+hipError_t launch_frame_summaries(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d)
 {
     const TrackSumDev &sum = *a.sum;
     const auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u),
-                                                     SumInput{a.skeys, a.svals, t.slot, a.fields, a.points});
+                                                     SumInput{a.skeys, a.svals, d.slot, a.fields, a.points});
     size_t tb = sum.temp_bytes;
     hipError_t e = rocprim::inclusive_scan(sum.temp, tb, in, sum.scan, (size_t)a.n, SumOp(), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(track_frame_summary_kernel<kBank>, dim3((a.n + 255) / 256), dim3(256), 0, st, a.frames, a.fields,
+    hipLaunchKernelGGL(track_frame_summary_kernel<K>, dim3((a.n + 255) / 256), dim3(256), 0, st, a.frames, a.fields,
                        (const adsb_track_point *)a.points, (const uint32_t *)a.skeys, (const uint32_t *)a.svals, a.n,
-                       a.seconds_per_sample, kBank ? (uint64_t)0 : a.sample_base, t, b, sum);
+                       a.seconds_per_sample, a.sample_base, d, sum);
     return hipSuccess;
 }
 
 // expire, 1: keep[g] = 1 for a record in use whose last frame is not older than the cut (last_heard < before evicts).
 // Record g is slot i of receiver r (a table: r = 0).  Slot 0 stages the old size where the compaction kernel reads it
-// (size_flags[3] / size_next[r]), since that kernel writes the new one.
-template <bool kBank>
-__global__ __launch_bounds__(256) void track_expire_mark_kernel(TrackTableDev t, TrackBankDev b, ExpireCut cut,
-                                                                uint32_t *keep, uint64_t n_rec)
+// (size_next[r]), since that kernel writes the new one; the pairs kernel of an update has consumed its own staging before
+// anything later on the stream runs.
+template <TrackKind K>
+__global__ __launch_bounds__(256) void track_expire_mark_kernel(TrackStoreDev d, ExpireCut cut, uint32_t *keep,
+                                                                uint64_t n_rec)
 {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_rec) return;
-    const uint32_t r = kBank ? (uint32_t)(g / t.max_aircraft) : 0u;
-    const uint32_t i = (uint32_t)(g - (uint64_t)r * t.max_aircraft);
-    const uint32_t size = kBank ? b.size[r] : t.size_flags[0];
-    if (i == 0) {
-        if (kBank)
-            b.size_next[r] = size;
-        else
-            t.size_flags[3] = size;
-    }
-    keep[g] = (i < size && !(t.rec[g].last_heard < cut.before[r])) ? 1u : 0u;
+    const uint32_t r = K == TrackKind::kBank ? (uint32_t)(g / d.max_aircraft) : 0u;
+    const uint32_t i = (uint32_t)(g - (uint64_t)r * d.max_aircraft);
+    const uint32_t size = d.size[r];
+    if (i == 0) d.size_next[r] = size;
+    keep[g] = (i < size && !(d.rec[g].last_heard < cut.before[r])) ? 1u : 0u;
 }
 
 // expire, 2 (after the exclusive scan rank of keep): the new size S = survivors; an evicted record below S is a hole
 // that takes the k-th survivor at or above S (k = holes before it), found by a binary search over the local ranks.
 // Holes are below S and the survivors they take at or above it, so no thread reads a record another one writes.  A
 // table fixes its index here: the entries of evicted ICAOs are cleared, the moved ones point at their new slot.
-template <bool kBank>
-__global__ __launch_bounds__(256) void track_expire_compact_kernel(TrackTableDev t, TrackBankDev b,
-                                                                   const uint32_t *keep, const uint32_t *rank,
-                                                                   uint64_t n_rec)
+template <TrackKind K>
+__global__ __launch_bounds__(256) void track_expire_compact_kernel(TrackStoreDev d, const uint32_t *keep,
+                                                                   const uint32_t *rank, uint64_t n_rec)
 {
+    constexpr bool kBank = K == TrackKind::kBank;
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_rec) return;
-    const uint32_t r = kBank ? (uint32_t)(g / t.max_aircraft) : 0u;
-    const uint64_t base = (uint64_t)r * t.max_aircraft;
+    const uint32_t r = kBank ? (uint32_t)(g / d.max_aircraft) : 0u;
+    const uint64_t base = (uint64_t)r * d.max_aircraft;
     const uint32_t i = (uint32_t)(g - base);
-    const uint32_t size = kBank ? b.size_next[r] : t.size_flags[3];
+    const uint32_t size = d.size_next[r];
     const uint32_t rank0 = rank[base];
     const uint32_t survivors = size ? rank[base + size - 1] + keep[base + size - 1] - rank0 : 0u;
-    if (i == 0) {
-        if (kBank)
-            b.size[r] = survivors;
-        else
-            t.size_flags[0] = survivors;
-    }
+    if (i == 0) d.size[r] = survivors;
     if (i >= size || keep[g]) return;
-    if (!kBank) t.index[t.rec[g].a.icao] = 0;
+    if (!kBank) d.index[d.rec[g].a.icao] = 0;
     if (i >= survivors) return;
     // a hole below `survivors` (so at least one survivor sits in [survivors, size)): k-th hole <- k-th such survivor,
     // the one whose local rank is m; it is the last slot in [survivors, size) with local rank <= m
@@ -722,19 +707,19 @@ __global__ __launch_bounds__(256) void track_expire_compact_kernel(TrackTableDev
         else
             lo = mid;
     }
-    const TrackRecord moved = t.rec[base + lo];
-    t.rec[g] = moved;
-    if (!kBank) t.index[moved.a.icao] = i + 1u;
+    const TrackRecord moved = d.rec[base + lo];
+    d.rec[g] = moved;
+    if (!kBank) d.index[moved.a.icao] = i + 1u;
 }
 
 // expire, 3 (bank only, after the hash was cleared): every surviving record reinserts (slot + 1) << 32 | key
-__global__ __launch_bounds__(256) void track_bank_rehash_kernel(TrackTableDev t, TrackBankDev b, uint64_t n_rec)
+__global__ __launch_bounds__(256) void track_bank_rehash_kernel(TrackStoreDev b, uint64_t n_rec)
 {
     const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n_rec) return;
-    const uint32_t r = (uint32_t)(g / t.max_aircraft);
-    if ((uint32_t)(g - (uint64_t)r * t.max_aircraft) >= b.size[r]) return;
-    const uint32_t key = r << 24 | (t.rec[g].a.icao & 0xFFFFFFu);
+    const uint32_t r = (uint32_t)(g / b.max_aircraft);
+    if ((uint32_t)(g - (uint64_t)r * b.max_aircraft) >= b.size[r]) return;
+    const uint32_t key = r << 24 | (b.rec[g].a.icao & 0xFFFFFFu);
     const unsigned long long entry = (unsigned long long)(g + 1u) << 32 | key;
     for (uint64_t h = bank_hash(key) & b.hash_mask;; h = (h + 1) & b.hash_mask) // load <= 1/2: an empty entry exists
         if (atomicCAS(&b.hash[h], 0ull, entry) == 0ull) break;
@@ -745,7 +730,7 @@ constexpr uint32_t kFuseNone = 0xFFFFFFFFu; // a sorted position: no record yet
 
 // fuse, 1: one thread per place p = r x max_aircraft + slot
 template <class K>
-__global__ __launch_bounds__(256) void fuse_keys_kernel(TrackBankDev b, double since, uint32_t rbits, K *keys,
+__global__ __launch_bounds__(256) void fuse_keys_kernel(TrackStoreDev b, double since, uint32_t rbits, K *keys,
                                                         uint32_t *vals, uint64_t places)
 {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -918,7 +903,7 @@ hipError_t fuse_sort_scan(void *temp, size_t &sort_bytes, size_t &scan_bytes, co
 template <class K>
 hipError_t launch_fuse(hipStream_t st, const FuseArgs &a)
 {
-    const TrackBankDev b = *a.bank;
+    const TrackStoreDev b = *a.bank;
     const uint64_t places = (uint64_t)b.n_receivers * b.max_aircraft;
     const uint32_t rbits = b.key_bits - 24, blocks = (uint32_t)((places + 255) / 256);
     K *keys = (K *)a.keys, *skeys = (K *)a.skeys;
@@ -954,32 +939,33 @@ size_t track_expire_temp_bytes(size_t n_rec)
     return scan_bytes + 256;
 }
 
-hipError_t launch_track_expire(hipStream_t st, const ExpireArgs &a)
+namespace {
+// mark -> scan -> compaction; a bank then clears its hash and reinserts the survivors
+template <TrackKind K>
+hipError_t track_expire(hipStream_t st, const ExpireArgs &a)
 {
-    const TrackTableDev t = *a.table;
-    TrackBankDev b{};
-    if (a.bank) b = *a.bank;
-    const uint64_t n_rec = (uint64_t)t.max_aircraft * (a.bank ? b.n_receivers : 1u);
+    const TrackStoreDev d = *a.store;
+    const uint64_t n_rec = (uint64_t)d.max_aircraft * d.n_receivers;
     if (n_rec == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t)((n_rec + 255) / 256);
-    if (a.bank)
-        hipLaunchKernelGGL(track_expire_mark_kernel<true>, dim3(blocks), dim3(256), 0, st, t, b, a.cut, a.keep, n_rec);
-    else
-        hipLaunchKernelGGL(track_expire_mark_kernel<false>, dim3(blocks), dim3(256), 0, st, t, b, a.cut, a.keep, n_rec);
+    hipLaunchKernelGGL(track_expire_mark_kernel<K>, dim3(blocks), dim3(256), 0, st, d, a.cut, a.keep, n_rec);
     size_t tb = a.temp_bytes;
     hipError_t e = rocprim::exclusive_scan(a.temp, tb, (const uint32_t *)a.keep, a.rank, 0u, (size_t)n_rec,
                                            rocprim::plus<uint32_t>(), st);
     if (e != hipSuccess) return e;
-    if (!a.bank) {
-        hipLaunchKernelGGL(track_expire_compact_kernel<false>, dim3(blocks), dim3(256), 0, st, t, b,
-                           (const uint32_t *)a.keep, (const uint32_t *)a.rank, n_rec);
-        return hipGetLastError();
+    hipLaunchKernelGGL(track_expire_compact_kernel<K>, dim3(blocks), dim3(256), 0, st, d, (const uint32_t *)a.keep,
+                       (const uint32_t *)a.rank, n_rec);
+    if (K == TrackKind::kBank) {
+        if ((e = hipMemsetAsync(d.hash, 0, sizeof(unsigned long long) * (d.hash_mask + 1), st)) != hipSuccess) return e;
+        hipLaunchKernelGGL(track_bank_rehash_kernel, dim3(blocks), dim3(256), 0, st, d, n_rec);
     }
-    hipLaunchKernelGGL(track_expire_compact_kernel<true>, dim3(blocks), dim3(256), 0, st, t, b,
-                       (const uint32_t *)a.keep, (const uint32_t *)a.rank, n_rec);
-    if ((e = hipMemsetAsync(b.hash, 0, sizeof(unsigned long long) * (b.hash_mask + 1), st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(track_bank_rehash_kernel, dim3(blocks), dim3(256), 0, st, t, b, n_rec);
     return hipGetLastError();
+}
+} // namespace
+
+hipError_t launch_track_expire(hipStream_t st, const ExpireArgs &a)
+{
+    return a.kind == TrackKind::kBank ? track_expire<TrackKind::kBank>(st, a) : track_expire<TrackKind::kTable>(st, a);
 }
 
 size_t track_fuse_temp_bytes(size_t places, uint32_t n_receivers)
@@ -1040,69 +1026,67 @@ hipError_t launch_track_changed(hipStream_t st, const TrackRecord *rec, const Tr
     return hipGetLastError();
 }
 
+namespace {
+// What follows the sort (and, with a table or bank, lookup and admission): pairs, then per-frame summaries if reserved
+// and the merge into the records; the per-launch form ranks its segment tails and summarises into a.aircraft instead.
+template <TrackKind K>
+hipError_t track_tail(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d)
+{
+    constexpr bool kStore = K != TrackKind::kLaunch;
+    const uint32_t n = a.n, blocks = (n + 255) / 256;
+    uint32_t *tail_flag = kStore ? nullptr : a.keys, *tail_pos = kStore ? nullptr : a.vals; // reused
+    hipLaunchKernelGGL(track_pairs_kernel<K>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.skeys, a.svals, n,
+                       a.seconds_per_sample, a.sample_base, d, a.points, tail_flag);
+    hipError_t e = hipSuccess;
+    if constexpr (kStore) {
+        if (a.sum) e = launch_frame_summaries<K>(st, a, d); // before the merge
+    } else {
+        size_t tb = a.temp_bytes;
+        e = rocprim::exclusive_scan(a.temp, tb, (const uint32_t *)tail_flag, tail_pos, 0u, (size_t)n,
+                                    rocprim::plus<uint32_t>(), st);
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(track_summary_kernel<K>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.points, a.skeys,
+                       a.svals, (const uint32_t *)tail_flag, (const uint32_t *)tail_pos, n, a.seconds_per_sample,
+                       a.sample_base, d, a.aircraft, a.max_aircraft, a.n_aircraft);
+    return hipGetLastError();
+}
+} // namespace
+
 hipError_t launch_track(hipStream_t st, const TrackArgs &a)
 {
-    if (a.n == 0) return a.table ? hipSuccess : hipMemsetAsync(a.n_aircraft, 0, sizeof(uint64_t), st);
+    const bool store = a.kind != TrackKind::kLaunch;
+    if (a.n == 0) return store ? hipSuccess : hipMemsetAsync(a.n_aircraft, 0, sizeof(uint64_t), st);
     const uint32_t n = a.n, blocks = (n + 255) / 256;
-    TrackTableDev t{};
-    if (a.table) t = *a.table;
-    TrackBankDev b{};
-    if (a.bank) { // a.table: the bank's records and slot scratch
-        b = *a.bank;
-        const uint32_t kblocks = ((n > b.n_receivers ? n : b.n_receivers + 1u) + 255u) / 256u;
-        hipLaunchKernelGGL(track_bank_keys_kernel, dim3(kblocks), dim3(256), 0, st, a.fields, n, b, a.keys, a.vals);
-        size_t tb = a.temp_bytes;
+    const TrackStoreDev d = store ? *a.store : TrackStoreDev{};
+    size_t tb = a.temp_bytes;
+    if (a.kind == TrackKind::kBank) {
+        const uint32_t kblocks = ((n > d.n_receivers ? n : d.n_receivers + 1u) + 255u) / 256u;
+        hipLaunchKernelGGL(track_bank_keys_kernel, dim3(kblocks), dim3(256), 0, st, a.fields, n, d, a.keys, a.vals);
         hipError_t e = rocprim::radix_sort_pairs(a.temp, tb, (const uint32_t *)a.keys, a.skeys,
-                                                 (const uint32_t *)a.vals, a.svals, (size_t)n, 0, b.key_bits, st);
+                                                 (const uint32_t *)a.vals, a.svals, (size_t)n, 0, d.key_bits, st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(track_bank_lookup_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, b, t.slot);
+        hipLaunchKernelGGL(track_bank_lookup_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, d);
         tb = a.temp_bytes;
-        e = rocprim::exclusive_scan(a.temp, tb, (const unsigned long long *)b.mark, b.excl, 0ull, (size_t)n,
+        e = rocprim::exclusive_scan(a.temp, tb, (const unsigned long long *)d.mark, d.excl, 0ull, (size_t)n,
                                     rocprim::plus<unsigned long long>(), st);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(track_bank_admit_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, b,
-                           (const uint32_t *)t.slot);
-        hipLaunchKernelGGL(track_pairs_kernel<true>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.skeys,
-                           a.svals, n, a.seconds_per_sample, (uint64_t)0, t, b, a.points, (uint32_t *)nullptr);
-        if (a.sum && (e = launch_frame_summaries<true>(st, a, t, b)) != hipSuccess) return e; // before the merge
-        hipLaunchKernelGGL(track_summary_kernel<true>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.points,
-                           a.skeys, a.svals, (const uint32_t *)nullptr, (const uint32_t *)nullptr, n,
-                           a.seconds_per_sample, (uint64_t)0, t, b, (adsb_aircraft_record *)nullptr, 0u,
-                           (uint64_t *)nullptr);
-        return hipGetLastError();
+        hipLaunchKernelGGL(track_bank_admit_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, d);
+        return track_tail<TrackKind::kBank>(st, a, d);
     }
     hipLaunchKernelGGL(track_keys_kernel, dim3(blocks), dim3(256), 0, st, a.fields, n, a.keys, a.vals);
-    size_t tb = a.temp_bytes;
     hipError_t e = rocprim::radix_sort_pairs(a.temp, tb, (const uint32_t *)a.keys, a.skeys, (const uint32_t *)a.vals,
                                              a.svals, (size_t)n, 0, 24, st);
     if (e != hipSuccess) return e;
-    if (a.table) {
-        hipLaunchKernelGGL(track_lookup_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, t.index, t.slot,
-                           a.keys /* reused: is_new */);
-        tb = a.temp_bytes;
-        e = rocprim::exclusive_scan(a.temp, tb, (const uint32_t *)a.keys, a.vals /* reused: rank */, 0u, (size_t)n,
-                                    rocprim::plus<uint32_t>(), st);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(track_admit_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, a.keys, a.vals, t);
-        hipLaunchKernelGGL(track_pairs_kernel<false>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.skeys,
-                           a.svals, n, a.seconds_per_sample, a.sample_base, t, b, a.points, (uint32_t *)nullptr);
-        if (a.sum && (e = launch_frame_summaries<false>(st, a, t, b)) != hipSuccess) return e; // before the merge
-        hipLaunchKernelGGL(track_summary_kernel<false>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.points,
-                           a.skeys, a.svals, (const uint32_t *)nullptr, (const uint32_t *)nullptr, n,
-                           a.seconds_per_sample, a.sample_base, t, b, (adsb_aircraft_record *)nullptr, 0u,
-                           (uint64_t *)nullptr);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(track_pairs_kernel<false>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.skeys, a.svals,
-                       n, a.seconds_per_sample, a.sample_base, t, b, a.points, a.keys /* reused: tail flags */);
+    if (!store) return track_tail<TrackKind::kLaunch>(st, a, d);
+    hipLaunchKernelGGL(track_lookup_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, d.index, d.slot,
+                       a.keys /* reused: is_new */);
     tb = a.temp_bytes;
-    e = rocprim::exclusive_scan(a.temp, tb, (const uint32_t *)a.keys, a.vals /* reused: tail positions */, 0u, (size_t)n,
+    e = rocprim::exclusive_scan(a.temp, tb, (const uint32_t *)a.keys, a.vals /* reused: rank */, 0u, (size_t)n,
                                 rocprim::plus<uint32_t>(), st);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(track_summary_kernel<false>, dim3(blocks), dim3(256), 0, st, a.frames, a.fields, a.points,
-                       a.skeys, a.svals, a.keys, a.vals, n, a.seconds_per_sample, a.sample_base, t, b, a.aircraft,
-                       a.max_aircraft, a.n_aircraft);
-    return hipGetLastError();
+    hipLaunchKernelGGL(track_admit_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, a.keys, a.vals, d);
+    return track_tail<TrackKind::kTable>(st, a, d);
 }
 
 } // namespace adsbk

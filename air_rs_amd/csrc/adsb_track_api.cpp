@@ -1,0 +1,803 @@
+// adsb_track_api.cpp -- the tracker's part of the extern "C" boundary (include/adsb_hip.h) over adsb_track.hip: the
+// per-launch tracker (adsb_track_device), the persistent table (adsb_track_table_*) and the bank of tables
+// (adsb_track_bank_*).  A table and a bank are one host-side store (TrackStore: a table is a store with one receiver),
+// and every entry point below is its argument checks plus a call of a helper written once.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <new>
+#include <vector>
+
+#include "adsb_ctx.h"
+
+using adsbk::TrackKind;
+using adsbk::TrackRecord;
+
+// What launch_track needs whatever the form: the list, u32 = 4 x [cap] (keys, vals, sorted keys, sorted vals)
+static adsbk::TrackArgs track_args(TrackKind kind, const adsb_frame *frames, const adsb_packet_fields *fields, size_t n,
+                                   double seconds_per_sample, uint32_t *u32, size_t cap, void *temp, size_t temp_bytes,
+                                   adsb_track_point *points)
+{
+    adsbk::TrackArgs a{};
+    a.kind = kind;
+    a.frames = frames;
+    a.fields = fields;
+    a.n = (uint32_t)n;
+    a.seconds_per_sample = seconds_per_sample;
+    a.keys = u32;
+    a.vals = u32 + cap;
+    a.skeys = u32 + 2 * cap;
+    a.svals = u32 + 3 * cap;
+    a.temp = temp;
+    a.temp_bytes = temp_bytes;
+    a.points = points;
+    return a;
+}
+
+extern "C" int adsb_track_device(adsb_ctx *c, double seconds_per_sample)
+{
+    if (!c || !(seconds_per_sample > 0.0)) return ADSB_E_ARG;
+    if (!c->launched) return ADSB_E_STATE;
+    if (c->last_channels != 1) return ADSB_E_ARG;
+    int rc = sync_header(c); // the list's length (and the rebuild after a slot-pool overflow)
+    if (rc != ADSB_OK) return rc;
+    if (!c->fields_current && (rc = adsb_decode_fields_device_async(c)) != ADSB_OK) return rc;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const size_t cap = (size_t)c->cfg.max_out;
+    if (!c->trk_u32) {
+        c->trk_temp_bytes = adsbk::track_sort_temp_bytes(cap);
+        if (hipMalloc((void **)&c->trk_u32, sizeof(uint32_t) * 4 * cap) != hipSuccess ||
+            hipMalloc(&c->trk_temp, c->trk_temp_bytes) != hipSuccess ||
+            hipMalloc((void **)&c->trk_points, sizeof(adsb_track_point) * cap) != hipSuccess ||
+            hipMalloc((void **)&c->trk_aircraft, sizeof(adsb_aircraft_record) * cap) != hipSuccess ||
+            hipMalloc((void **)&c->trk_n_aircraft, sizeof(uint64_t)) != hipSuccess)
+            return ADSB_E_NOMEM;
+    }
+    const uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
+    adsbk::TrackArgs a = track_args(TrackKind::kLaunch, c->last_out, c->fields, n, seconds_per_sample, c->trk_u32, cap,
+                                    c->trk_temp, c->trk_temp_bytes, c->trk_points);
+    a.aircraft = c->trk_aircraft;
+    a.max_aircraft = (uint32_t)cap;
+    a.n_aircraft = c->trk_n_aircraft;
+    HIPCHK(adsbk::launch_track(c->aux, a)); // same stream as the ordering pass and the field decode
+    c->trk_n = (uint32_t)n;
+    c->trk_done = true;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_fetch_track(adsb_ctx *c, adsb_track_point *points, size_t max_points, size_t *n_points,
+                                adsb_aircraft_record *aircraft, size_t max_aircraft, size_t *n_aircraft)
+{
+    if (!c || (!points && max_points) || (!aircraft && max_aircraft)) return ADSB_E_ARG;
+    if (!c->trk_done) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    uint64_t na = 0;
+    HIPCHK(hipMemcpyAsync(&na, c->trk_n_aircraft, sizeof(uint64_t), hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    const size_t np = std::min<size_t>(c->trk_n, max_points);
+    const size_t nac = std::min<size_t>((size_t)na, max_aircraft);
+    if (np) HIPCHK(hipMemcpyAsync(points, c->trk_points, sizeof(adsb_track_point) * np, hipMemcpyDeviceToHost, c->aux));
+    if (nac) HIPCHK(hipMemcpyAsync(aircraft, c->trk_aircraft, sizeof(adsb_aircraft_record) * nac, hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    if (n_points) *n_points = np;
+    if (n_aircraft) *n_aircraft = (size_t)na;
+    return ADSB_OK;
+}
+
+// ---- the store behind adsb_track_table_* and adsb_track_bank_* -----------------------------------------------------
+// Per-frame summaries and the changed list (adsb_track_*_summaries_reserve): everything here is allocated by the
+// reserve; `dev.out` null = no reserve.
+struct TrackSummaries {
+    adsbk::TrackSumDev dev{};
+    TrackRecord *changed_rec = nullptr; // [changed_cap]: fetch_changed's device-side gather
+    size_t changed_cap = 0;         // min(max_frames, record places): an update cannot touch more aircraft
+    bool updated = false;           // an update ran since the reserve (and since the last reset)
+    bool changed_valid = false;     // the last operation was an update: the changed list's slots still hold
+};
+
+// What a table and a bank share.  A table is a store with one receiver, found through dev.index; a bank finds its
+// records through dev.hash and adds the receiver split's staging and the fused view (adsb_track_bank below).
+struct TrackStore {
+    adsb_ctx *ctx = nullptr;
+    TrackKind kind = TrackKind::kTable;
+    uint64_t max_frames = 0;
+    double seconds_per_sample = 0.0;
+    uint32_t n_receivers = 0, max_aircraft = 0; // max_aircraft: per receiver
+    adsbk::TrackStoreDev dev{};     // records [R x max_aircraft], slot [max_frames]; index [2^24] or hash, prefix, scan words
+    uint32_t *words = nullptr;      // [3R]: size, flags, size_next (dev.size / dev.flags / dev.size_next)
+    uint32_t *u32 = nullptr;        // 4 x [max_frames]: keys, vals, sorted keys, sorted vals
+    void *temp = nullptr;
+    size_t temp_bytes = 0;
+    adsb_frame *frames = nullptr;   // [max_frames]: device copy of a host list
+    adsb_frame *pinned = nullptr;   // [max_frames]: pinned staging of that copy
+    hipEvent_t copied = nullptr;    // the last copies out of the pinned staging (a bank: and meta_pinned) have finished
+    adsb_packet_fields *fields = nullptr; // [max_frames]
+    adsb_track_point *points = nullptr;   // [max_frames], the last update's, list order
+    uint32_t *exp_u32 = nullptr;    // 2 x [R x max_aircraft]: expire's keep flags and their scan
+    void *exp_temp = nullptr;       // expire's scan
+    size_t exp_temp_bytes = 0;
+    uint32_t n_points = 0;
+    bool updated = false;
+    TrackSummaries sum;
+
+    size_t places() const { return (size_t)n_receivers * max_aircraft; }
+};
+
+struct adsb_track_table : TrackStore {};
+
+struct adsb_track_bank : TrackStore {
+    uint64_t *meta = nullptr;       // device [2R + 1]: prefix of the host counts [R + 1], then sample_base [R]
+    uint64_t *meta_pinned = nullptr; // pinned staging of meta
+    // the fused view (adsb_track_bank_fuse_*): all of it allocated by fuse_reserve, nothing before
+    void *fuse_keys = nullptr;      // 2 x [places] sort keys (uint32_t, uint64_t above kFuseWideReceivers): in, sorted
+    uint32_t *fuse_vals = nullptr;  // 2 x [places]: places in, sorted
+    uint32_t *fuse_start = nullptr; // [fuse_max]
+    adsb_fused_aircraft *fuse_out = nullptr; // [fuse_max]
+    uint64_t *fuse_counts = nullptr; // device [3]: records written, distinct ICAOs, ADSB_TRACK_FUSED_TRUNCATED
+    void *fuse_temp = nullptr;
+    size_t fuse_temp_bytes = 0;
+    size_t fuse_max = 0;            // 0: no reserve
+    uint32_t fuse_lanes = 0;
+    bool fused = false;             // a fuse ran since the last reserve
+};
+
+static void free_all(std::initializer_list<void *> list)
+{
+    for (void *p : list)
+        if (p) (void)hipFree(p);
+}
+
+static void track_summaries_free(TrackSummaries &s)
+{
+    free_all({s.dev.scan, s.dev.out, s.dev.changed, s.dev.n_changed, s.dev.temp, s.changed_rec});
+    s = TrackSummaries{};
+}
+
+// Sizes, and the buffers a table and a bank share; false: an allocation failed (the caller releases what was made)
+static bool store_alloc(TrackStore &s, adsb_ctx *c, TrackKind kind, uint32_t n_receivers, uint32_t max_aircraft, uint64_t max_frames,
+                        double seconds_per_sample, size_t temp_bytes)
+{
+    s.ctx = c;
+    s.kind = kind;
+    s.max_frames = max_frames;
+    s.seconds_per_sample = seconds_per_sample;
+    s.dev.n_receivers = s.n_receivers = n_receivers;
+    s.dev.max_aircraft = s.max_aircraft = max_aircraft;
+    s.temp_bytes = temp_bytes;
+    s.exp_temp_bytes = adsbk::track_expire_temp_bytes(s.places());
+    const size_t nf = (size_t)max_frames;
+    const bool ok = hipMalloc((void **)&s.dev.rec, sizeof(TrackRecord) * s.places()) == hipSuccess &&
+                    hipMalloc((void **)&s.words, sizeof(uint32_t) * 3 * n_receivers) == hipSuccess &&
+                    hipMalloc((void **)&s.dev.slot, sizeof(uint32_t) * nf) == hipSuccess &&
+                    hipMalloc((void **)&s.u32, sizeof(uint32_t) * 4 * nf) == hipSuccess &&
+                    hipMalloc(&s.temp, s.temp_bytes) == hipSuccess &&
+                    hipMalloc((void **)&s.frames, sizeof(adsb_frame) * nf) == hipSuccess &&
+                    hipHostMalloc((void **)&s.pinned, sizeof(adsb_frame) * nf, hipHostMallocDefault) == hipSuccess &&
+                    hipEventCreateWithFlags(&s.copied, hipEventDisableTiming) == hipSuccess &&
+                    hipMalloc((void **)&s.fields, sizeof(adsb_packet_fields) * nf) == hipSuccess &&
+                    hipMalloc((void **)&s.points, sizeof(adsb_track_point) * nf) == hipSuccess &&
+                    hipMalloc((void **)&s.exp_u32, sizeof(uint32_t) * 2 * s.places()) == hipSuccess &&
+                    hipMalloc(&s.exp_temp, s.exp_temp_bytes) == hipSuccess;
+    if (ok) {
+        s.dev.size = s.words;
+        s.dev.flags = s.words + n_receivers;
+        s.dev.size_next = s.words + 2 * n_receivers;
+    }
+    return ok;
+}
+
+// Waits for the stream, then frees whatever of the store exists (the table's and the bank's device-view buffers too)
+static void store_release(TrackStore &s)
+{
+    (void)hipSetDevice(s.ctx->cfg.device);
+    (void)hipStreamSynchronize(s.ctx->aux);
+    track_summaries_free(s.sum);
+    free_all({s.dev.rec, s.words, s.dev.slot, s.dev.index, s.dev.hash, s.dev.prefix, s.dev.mark, s.dev.excl,
+              s.dev.seg_slot, s.u32, s.temp, s.frames, s.fields, s.points, s.exp_u32, s.exp_temp});
+    if (s.pinned) (void)hipHostFree(s.pinned);
+    if (s.copied) (void)hipEventDestroy(s.copied);
+}
+
+static int store_reset(TrackStore *s)
+{
+    if (!s) return ADSB_E_ARG;
+    HIPCHK(hipSetDevice(s->ctx->cfg.device));
+    if (s->kind == TrackKind::kTable)
+        HIPCHK(hipMemsetAsync(s->dev.index, 0, sizeof(uint32_t) << 24, s->ctx->aux));
+    else
+        HIPCHK(hipMemsetAsync(s->dev.hash, 0, sizeof(unsigned long long) * (s->dev.hash_mask + 1), s->ctx->aux));
+    HIPCHK(hipMemsetAsync(s->words, 0, sizeof(uint32_t) * 3 * s->n_receivers, s->ctx->aux));
+    s->n_points = 0;
+    s->updated = false;
+    s->sum.updated = s->sum.changed_valid = false;
+    return ADSB_OK;
+}
+
+// The end of a create: the first reset and a wait for it; a store that could not be completed is destroyed
+template <class S>
+static int store_created(S *s, bool allocated, void (*destroy)(S *), S **out)
+{
+    int rc = allocated ? store_reset(s) : ADSB_E_NOMEM;
+    if (rc == ADSB_OK && hipStreamSynchronize(s->ctx->aux) != hipSuccess) rc = ADSB_E_NOMEM;
+    if (rc != ADSB_OK) {
+        (void)hipGetLastError();
+        destroy(s);
+        return rc;
+    }
+    *out = s;
+    return ADSB_OK;
+}
+
+static bool in_device_memory(const adsb_ctx *c, const void *p)
+{
+    hipPointerAttribute_t at{};
+    const bool yes = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice &&
+                     at.device == c->cfg.device;
+    (void)hipGetLastError(); // a plain host pointer is an error to the query: do not leave it to the launches after it
+    return yes;
+}
+
+// Host frames through the pinned staging, so the caller's array is free when the update returns.  The caller has waited
+// for s.copied before (the previous update's copy out of the staging has finished) and records it after.
+static int store_stage_frames(TrackStore &s, const adsb_frame *host, size_t n)
+{
+    std::memcpy(s.pinned, host, sizeof(adsb_frame) * n);
+    HIPCHK(hipMemcpyAsync(s.frames, s.pinned, sizeof(adsb_frame) * n, hipMemcpyHostToDevice, s.ctx->aux));
+    return ADSB_OK;
+}
+
+// The bookkeeping every update starts with (an empty one too: no summaries, an empty changed list); false: n == 0,
+// nothing to launch
+static bool store_begin_update(TrackStore &s, size_t n)
+{
+    s.n_points = (uint32_t)n;
+    s.updated = true;
+    if (s.sum.dev.out) s.sum.updated = s.sum.changed_valid = true;
+    return n != 0;
+}
+
+// Enqueues field decode and the tracker kernels over n frames at `list` (device), after the ctx's ordering pass and
+// field decode (same stream); dev: s.dev, or a bank's copy of it with this update's receiver split
+static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t sample_base,
+                     const adsbk::TrackStoreDev &dev)
+{
+    HIPCHK(adsbk::launch_decode_fields(s.ctx->aux, list, nullptr, (uint32_t)n, s.fields));
+    adsbk::TrackArgs a = track_args(s.kind, list, s.fields, n, s.seconds_per_sample, s.u32, (size_t)s.max_frames,
+                                    s.temp, s.temp_bytes, s.points);
+    a.sample_base = sample_base;
+    a.store = &dev;
+    a.sum = s.sum.dev.out ? &s.sum.dev : nullptr;
+    HIPCHK(adsbk::launch_track(s.ctx->aux, a));
+    return ADSB_OK;
+}
+
+static int store_fetch_points(TrackStore *s, adsb_track_point *points, size_t max_points, size_t *n_points)
+{
+    if (!s || (!points && max_points)) return ADSB_E_ARG;
+    if (!s->updated) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(s->ctx->cfg.device));
+    const size_t np = std::min<size_t>(s->n_points, max_points);
+    if (np) HIPCHK(hipMemcpyAsync(points, s->points, sizeof(adsb_track_point) * np, hipMemcpyDeviceToHost, s->ctx->aux));
+    HIPCHK(hipStreamSynchronize(s->ctx->aux));
+    if (n_points) *n_points = np;
+    return ADSB_OK;
+}
+
+// Records of one receiver (slots in admission order) as fetch returns them: ascending ICAO.
+static void sort_by_icao(std::vector<TrackRecord> &recs)
+{
+    std::sort(recs.begin(), recs.end(), [](const TrackRecord &x, const TrackRecord &y) { return x.a.icao < y.a.icao; });
+}
+
+// Waits.  Receiver by receiver: its records (slots are in admission order) sorted by ICAO, out[k] = get(record) for
+// the first `max` records in all and nothing past them; *n = records held in all, counts[r] = records COPIED for
+// receiver r, flags[r] = its device flags word (each optional).
+template <class T, class Get>
+static int store_fetch(TrackStore *s, T *out, size_t max, size_t *n, uint64_t *counts, uint32_t *flags, Get get)
+{
+    if (!s || (!out && max)) return ADSB_E_ARG;
+    adsb_ctx *c = s->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const uint32_t nr = s->n_receivers;
+    std::vector<uint32_t> w(2 * (size_t)nr); // sizes, then flags
+    HIPCHK(hipMemcpyAsync(w.data(), s->words, sizeof(uint32_t) * w.size(), hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    size_t total = 0, copied = 0;
+    std::vector<TrackRecord> recs;
+    for (uint32_t r = 0; r < nr; ++r) {
+        const size_t size = std::min<uint32_t>(w[r], s->max_aircraft);
+        total += size;
+        const size_t take = std::min(size, max - copied);
+        if (take) {
+            recs.resize(size);
+            HIPCHK(hipMemcpyAsync(recs.data(), s->dev.rec + (size_t)r * s->max_aircraft, sizeof(TrackRecord) * size,
+                                  hipMemcpyDeviceToHost, c->aux));
+            HIPCHK(hipStreamSynchronize(c->aux));
+            sort_by_icao(recs);
+            for (size_t k = 0; k < take; ++k) out[copied + k] = get(recs[k]);
+        }
+        copied += take;
+        if (counts) counts[r] = take;
+        if (flags) flags[r] = w[nr + r];
+    }
+    if (n) *n = total;
+    return ADSB_OK;
+}
+
+static adsb_aircraft_record record_of(const TrackRecord &r) { return r.a; }
+static double last_heard_of(const TrackRecord &r) { return r.last_heard; }
+static adsb_velocity velocity_of(const TrackRecord &r) { return r.vel; }
+
+// before: [n_receivers] cuts
+static int store_expire(TrackStore *s, const double *before)
+{
+    if (!s || !before) return ADSB_E_ARG;
+    adsbk::ExpireArgs a{};
+    for (uint32_t r = 0; r < s->n_receivers; ++r) { // n_receivers <= kMaxReceivers (create checks)
+        if (std::isnan(before[r])) return ADSB_E_ARG;
+        a.cut.before[r] = before[r];                 // by value in the kernel's arguments: no staging, no wait
+    }
+    HIPCHK(hipSetDevice(s->ctx->cfg.device));
+    a.kind = s->kind;
+    a.store = &s->dev;
+    a.keep = s->exp_u32;
+    a.rank = s->exp_u32 + s->places();
+    a.temp = s->exp_temp;
+    a.temp_bytes = s->exp_temp_bytes;
+    HIPCHK(adsbk::launch_track_expire(s->ctx->aux, a)); // after the store's last update (same stream)
+    s->sum.changed_valid = false; // slots move
+    return ADSB_OK;
+}
+
+// May wait for the device (hipMalloc); a second reserve keeps what the first one made
+static int store_summaries_reserve(TrackStore *st)
+{
+    if (!st) return ADSB_E_ARG;
+    HIPCHK(hipSetDevice(st->ctx->cfg.device));
+    TrackSummaries &s = st->sum;
+    if (s.dev.out) return ADSB_OK;
+    const size_t max_frames = (size_t)st->max_frames;
+    s.changed_cap = std::min(max_frames, st->places());
+    s.dev.temp_bytes = adsbk::track_summaries_temp_bytes(max_frames);
+    const bool ok = hipMalloc((void **)&s.dev.scan, sizeof(adsbk::TrackSumTuple) * max_frames) == hipSuccess &&
+                    hipMalloc((void **)&s.dev.changed, sizeof(uint32_t) * max_frames) == hipSuccess &&
+                    hipMalloc((void **)&s.dev.n_changed, sizeof(uint32_t)) == hipSuccess &&
+                    hipMalloc(&s.dev.temp, s.dev.temp_bytes) == hipSuccess &&
+                    hipMalloc((void **)&s.changed_rec, sizeof(TrackRecord) * s.changed_cap) == hipSuccess &&
+                    hipMalloc((void **)&s.dev.out, sizeof(adsb_aircraft_record) * max_frames) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        track_summaries_free(s);
+        return ADSB_E_NOMEM;
+    }
+    return ADSB_OK;
+}
+
+// Waits
+static int store_fetch_summaries(TrackStore *st, adsb_aircraft_record *out, size_t max, size_t *n)
+{
+    if (!st || (!out && max)) return ADSB_E_ARG;
+    if (!st->sum.dev.out || !st->sum.updated) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(st->ctx->cfg.device));
+    const size_t n_frames = st->n_points, take = std::min(n_frames, max);
+    if (take)
+        HIPCHK(hipMemcpyAsync(out, st->sum.dev.out, sizeof(adsb_aircraft_record) * take, hipMemcpyDeviceToHost,
+                              st->ctx->aux));
+    HIPCHK(hipStreamSynchronize(st->ctx->aux));
+    if (n) *n = n_frames;
+    return ADSB_OK;
+}
+
+static int store_summaries_device(TrackStore *st, const adsb_aircraft_record **dev)
+{
+    if (!st) return ADSB_E_ARG;
+    if (!st->sum.dev.out || !st->sum.updated) return ADSB_E_STATE;
+    if (dev) *dev = st->sum.dev.out;
+    return ADSB_OK;
+}
+
+// Waits; gathers the changed list's records on the device and copies only them.  counts (optional, [n_receivers]): how
+// many of the records returned belong to each receiver (slot / max_aircraft).
+static int store_fetch_changed(TrackStore *st, adsb_aircraft_record *out, double *last_heard, adsb_velocity *velocity,
+                               size_t max, size_t *n, uint64_t *counts)
+{
+    if (!st) return ADSB_E_ARG;
+    TrackSummaries &s = st->sum;
+    adsb_ctx *c = st->ctx;
+    if (!s.dev.out || !s.updated || !s.changed_valid) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (counts) std::fill(counts, counts + st->n_receivers, (uint64_t)0);
+    uint32_t nc = 0;
+    if (st->n_points) { // an empty update launched nothing: its list is empty, and the device word is an older update's
+        const uint32_t most = (uint32_t)std::min(std::min<size_t>(st->n_points, s.changed_cap), max);
+        HIPCHK(adsbk::launch_track_changed(c->aux, st->dev.rec, s.dev, most, s.changed_rec));
+        HIPCHK(hipMemcpyAsync(&nc, s.dev.n_changed, sizeof(nc), hipMemcpyDeviceToHost, c->aux));
+        HIPCHK(hipStreamSynchronize(c->aux));
+        const size_t take = std::min<size_t>(nc, most);
+        if (take) {
+            std::vector<TrackRecord> recs(take);
+            std::vector<uint32_t> slots(take);
+            HIPCHK(hipMemcpyAsync(recs.data(), s.changed_rec, sizeof(TrackRecord) * take, hipMemcpyDeviceToHost, c->aux));
+            HIPCHK(hipMemcpyAsync(slots.data(), s.dev.changed, sizeof(uint32_t) * take, hipMemcpyDeviceToHost, c->aux));
+            HIPCHK(hipStreamSynchronize(c->aux));
+            for (size_t k = 0; k < take; ++k) {
+                if (out) out[k] = recs[k].a;
+                if (last_heard) last_heard[k] = recs[k].last_heard;
+                if (velocity) velocity[k] = recs[k].vel;
+                if (counts) ++counts[slots[k] / st->max_aircraft]; // a slot = receiver x max_aircraft + place
+            }
+        }
+    }
+    if (n) *n = nc;
+    return ADSB_OK;
+}
+
+// ---- persistent aircraft table (adsb_track_table_*) ------------------------------------------------------------------
+static void track_table_free(adsb_track_table *t)
+{
+    store_release(*t);
+    delete t;
+}
+
+extern "C" int adsb_track_table_reset(adsb_track_table *t) { return store_reset(t); }
+
+extern "C" int adsb_track_table_create(adsb_ctx *c, const adsb_track_table_cfg *cfg, adsb_track_table **out)
+{
+    if (!c || !cfg || !out || cfg->abi_version != ADSB_ABI_VERSION) return ADSB_E_ARG;
+    if (cfg->max_frames == 0 || cfg->max_frames > 0xFFFFFFFFull || !(cfg->seconds_per_sample > 0.0) ||
+        cfg->max_aircraft > (1u << 24))
+        return ADSB_E_ARG;
+    *out = nullptr;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    adsb_track_table *t = new (std::nothrow) adsb_track_table;
+    if (!t) return ADSB_E_NOMEM;
+    const bool ok = store_alloc(*t, c, TrackKind::kTable, 1, cfg->max_aircraft ? cfg->max_aircraft : 65536u, cfg->max_frames,
+                                cfg->seconds_per_sample, adsbk::track_sort_temp_bytes((size_t)cfg->max_frames)) &&
+                    hipMalloc((void **)&t->dev.index, sizeof(uint32_t) << 24) == hipSuccess;
+    return store_created(t, ok, track_table_free, out);
+}
+
+extern "C" void adsb_track_table_destroy(adsb_track_table *t)
+{
+    if (t) track_table_free(t);
+}
+
+extern "C" int adsb_track_table_update(adsb_track_table *t, const adsb_frame *frames, size_t n, uint64_t sample_base)
+{
+    if (!t || (!frames && n)) return ADSB_E_ARG;
+    if (n > t->max_frames) return ADSB_E_CAPACITY;
+    adsb_ctx *c = t->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (!store_begin_update(*t, n)) return ADSB_OK;
+    const adsb_frame *list = frames;
+    if (!in_device_memory(c, frames)) {
+        HIPCHK(hipEventSynchronize(t->copied)); // the previous update's copy out of the staging has finished
+        int rc = store_stage_frames(*t, frames, n);
+        if (rc != ADSB_OK) return rc;
+        HIPCHK(hipEventRecord(t->copied, c->aux));
+        list = t->frames;
+    }
+    return store_run(*t, list, n, sample_base, t->dev);
+}
+
+extern "C" int adsb_track_table_summaries_reserve(adsb_track_table *t) { return store_summaries_reserve(t); }
+
+extern "C" int adsb_track_table_fetch_summaries(adsb_track_table *t, adsb_aircraft_record *out, size_t max, size_t *n)
+{
+    return store_fetch_summaries(t, out, max, n);
+}
+
+extern "C" int adsb_track_table_summaries_device(adsb_track_table *t, const adsb_aircraft_record **dev)
+{
+    return store_summaries_device(t, dev);
+}
+
+extern "C" int adsb_track_table_fetch_changed(adsb_track_table *t, adsb_aircraft_record *rec, double *last_heard,
+                                              adsb_velocity *velocity, size_t max, size_t *n)
+{
+    return store_fetch_changed(t, rec, last_heard, velocity, max, n, nullptr);
+}
+
+extern "C" int adsb_track_table_fetch_points(adsb_track_table *t, adsb_track_point *points, size_t max_points,
+                                             size_t *n_points)
+{
+    return store_fetch_points(t, points, max_points, n_points);
+}
+
+extern "C" int adsb_track_table_fetch(adsb_track_table *t, adsb_aircraft_record *aircraft, size_t max_aircraft,
+                                      size_t *n_aircraft, uint32_t *flags)
+{
+    return store_fetch(t, aircraft, max_aircraft, n_aircraft, nullptr, flags, record_of);
+}
+
+extern "C" int adsb_track_table_expire(adsb_track_table *t, double before)
+{
+    if (!t || std::isnan(before)) return ADSB_E_ARG; // before the handle is read
+    return store_expire(t, &before);
+}
+
+extern "C" int adsb_track_table_fetch_last_heard(adsb_track_table *t, double *last_heard, size_t max, size_t *n)
+{
+    return store_fetch(t, last_heard, max, n, nullptr, nullptr, last_heard_of);
+}
+
+extern "C" int adsb_track_table_fetch_velocity(adsb_track_table *t, adsb_velocity *velocity, size_t max, size_t *n)
+{
+    return store_fetch(t, velocity, max, n, nullptr, nullptr, velocity_of);
+}
+
+// ---- a bank of persistent tables, one per receiver (adsb_track_bank_*) ----------------------------------------------
+static void track_bank_fuse_free(adsb_track_bank *b)
+{
+    free_all({b->fuse_keys, b->fuse_vals, b->fuse_start, b->fuse_out, b->fuse_counts, b->fuse_temp});
+    b->fuse_keys = b->fuse_temp = nullptr;
+    b->fuse_vals = b->fuse_start = nullptr;
+    b->fuse_out = nullptr;
+    b->fuse_counts = nullptr;
+    b->fuse_max = 0;
+    b->fused = false;
+}
+
+static void track_bank_free(adsb_track_bank *b)
+{
+    store_release(*b);
+    track_bank_fuse_free(b);
+    free_all({b->meta});
+    if (b->meta_pinned) (void)hipHostFree(b->meta_pinned);
+    delete b;
+}
+
+extern "C" int adsb_track_bank_reset(adsb_track_bank *b) { return store_reset(b); }
+
+extern "C" int adsb_track_bank_create(adsb_ctx *c, const adsb_track_bank_cfg *cfg, adsb_track_bank **out)
+{
+    if (!c || !cfg || !out || cfg->abi_version != ADSB_ABI_VERSION || cfg->reserved != 0) return ADSB_E_ARG;
+    if (cfg->n_receivers == 0 || cfg->n_receivers > adsbk::kMaxReceivers || cfg->max_frames == 0 || cfg->max_frames > 0xFFFFFFFFull ||
+        !(cfg->seconds_per_sample > 0.0) || cfg->max_aircraft > (1u << 24))
+        return ADSB_E_ARG;
+    *out = nullptr;
+    const uint32_t nr = cfg->n_receivers, max_ac = cfg->max_aircraft ? cfg->max_aircraft : 65536u;
+    const uint64_t n_rec = (uint64_t)nr * max_ac;
+    if (n_rec >= 0xFFFFFFFFull) return ADSB_E_NOMEM; // slot + 1 must fit 32 bits: 2^32 records would need > 350 GiB
+    HIPCHK(hipSetDevice(c->cfg.device));
+    adsb_track_bank *b = new (std::nothrow) adsb_track_bank;
+    if (!b) return ADSB_E_NOMEM;
+    const size_t nf = (size_t)cfg->max_frames;
+    uint64_t cap = 1;
+    while (cap < 2 * n_rec) cap <<= 1;
+    b->dev.hash_mask = cap - 1;
+    uint32_t bits = 0;
+    while ((1u << bits) < nr) ++bits;
+    b->dev.key_bits = 24 + bits;
+    const bool ok = store_alloc(*b, c, TrackKind::kBank, nr, max_ac, cfg->max_frames, cfg->seconds_per_sample,
+                                adsbk::track_bank_temp_bytes(nf)) &&
+                    hipMalloc((void **)&b->dev.hash, sizeof(unsigned long long) * cap) == hipSuccess &&
+                    hipMalloc((void **)&b->dev.prefix, sizeof(uint32_t) * (nr + 1)) == hipSuccess &&
+                    hipMalloc((void **)&b->meta, sizeof(uint64_t) * (2 * nr + 1)) == hipSuccess &&
+                    hipHostMalloc((void **)&b->meta_pinned, sizeof(uint64_t) * (2 * nr + 1), hipHostMallocDefault) == hipSuccess &&
+                    hipMalloc((void **)&b->dev.mark, sizeof(unsigned long long) * nf) == hipSuccess &&
+                    hipMalloc((void **)&b->dev.excl, sizeof(unsigned long long) * nf) == hipSuccess &&
+                    hipMalloc((void **)&b->dev.seg_slot, sizeof(uint32_t) * nf) == hipSuccess;
+    if (ok) b->dev.sample_base = b->meta + nr + 1;
+    return store_created(b, ok, track_bank_free, out);
+}
+
+extern "C" void adsb_track_bank_destroy(adsb_track_bank *b)
+{
+    if (b) track_bank_free(b);
+}
+
+// Enqueues the bank's kernels over n frames at `list` (device) with the receiver split src_prefix[0..n_src]; meta's
+// sample_base part has been filled by the caller (and the staging copy enqueued).
+static int track_bank_run(adsb_track_bank *b, const adsb_frame *list, size_t n, const uint64_t *src_prefix,
+                          uint32_t n_src)
+{
+    adsbk::TrackStoreDev dev = b->dev;
+    dev.src_prefix = src_prefix;
+    dev.n_src = n_src;
+    return store_run(*b, list, n, 0, dev);
+}
+
+// Stages sample_base (and, for a host split, the counts' prefix) through meta_pinned; frames_host: also the frames.
+static int track_bank_stage(adsb_track_bank *b, const uint64_t *counts, const uint64_t *sample_base,
+                            const adsb_frame *frames_host, size_t n)
+{
+    adsb_ctx *c = b->ctx;
+    const uint32_t nr = b->n_receivers;
+    HIPCHK(hipEventSynchronize(b->copied)); // the previous update's copies out of the staging have finished
+    uint64_t *m = b->meta_pinned;
+    m[0] = 0;
+    for (uint32_t r = 0; r < nr; ++r) {
+        m[r + 1] = m[r] + (counts ? counts[r] : 0);
+        m[nr + 1 + r] = sample_base ? sample_base[r] : 0;
+    }
+    HIPCHK(hipMemcpyAsync(b->meta, m, sizeof(uint64_t) * (2 * nr + 1), hipMemcpyHostToDevice, c->aux));
+    if (frames_host) {
+        int rc = store_stage_frames(*b, frames_host, n);
+        if (rc != ADSB_OK) return rc;
+    }
+    HIPCHK(hipEventRecord(b->copied, c->aux));
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_update(adsb_track_bank *b, const adsb_frame *frames, size_t n, const uint64_t *counts,
+                                      const uint64_t *sample_base)
+{
+    if (!b || (!frames && n) || (!counts && n)) return ADSB_E_ARG;
+    if (counts) {
+        uint64_t sum = 0;
+        for (uint32_t r = 0; r < b->n_receivers; ++r) {
+            if (counts[r] > n - sum) return ADSB_E_ARG;
+            sum += counts[r];
+        }
+        if (sum != n) return ADSB_E_ARG;
+    }
+    if (n > b->max_frames) return ADSB_E_CAPACITY;
+    adsb_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (!store_begin_update(*b, n)) return ADSB_OK;
+    const bool on_device = in_device_memory(c, frames);
+    int rc = track_bank_stage(b, counts, sample_base, on_device ? nullptr : frames, n);
+    if (rc != ADSB_OK) return rc;
+    return track_bank_run(b, on_device ? frames : b->frames, n, b->meta, b->n_receivers);
+}
+
+extern "C" int adsb_track_bank_update_launch(adsb_track_bank *b, const uint64_t *sample_base)
+{
+    if (!b) return ADSB_E_ARG;
+    adsb_ctx *c = b->ctx;
+    if (!c->launched) return ADSB_E_STATE;
+    if (c->last_channels > b->n_receivers) return ADSB_E_ARG;
+    int rc = sync_header(c); // the list's length, as adsb_fetch_counts (and the rebuild after a slot-pool overflow)
+    if (rc != ADSB_OK) return rc;
+    const uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
+    if (n > b->max_frames) return ADSB_E_CAPACITY;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (!store_begin_update(*b, (size_t)n)) return ADSB_OK;
+    if ((rc = track_bank_stage(b, nullptr, sample_base, nullptr, 0)) != ADSB_OK) return rc;
+    adsb_ctx::ResultSet &r = c->rs[c->last];
+    // the channel split as adsb_fetch's per_channel_counts reads it: chan_prefix clipped to the list
+    if ((rc = track_bank_run(b, c->last_out, (size_t)n, r.chan_prefix, c->last_channels)) != ADSB_OK) return rc;
+    if (c->own_aux) { // the launch that reuses this result set waits for these kernels too
+        HIPCHK(hipEventRecord(r.g_done, c->aux));
+        r.g_pending = true;
+    }
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_fetch_points(adsb_track_bank *b, adsb_track_point *points, size_t max_points,
+                                            size_t *n_points)
+{
+    return store_fetch_points(b, points, max_points, n_points);
+}
+
+extern "C" int adsb_track_bank_fetch(adsb_track_bank *b, adsb_aircraft_record *aircraft, size_t max_aircraft,
+                                     size_t *n_aircraft, uint64_t *per_receiver_counts, uint32_t *flags)
+{
+    return store_fetch(b, aircraft, max_aircraft, n_aircraft, per_receiver_counts, flags, record_of);
+}
+
+extern "C" int adsb_track_bank_expire(adsb_track_bank *b, const double *before) { return store_expire(b, before); }
+
+extern "C" int adsb_track_bank_summaries_reserve(adsb_track_bank *b) { return store_summaries_reserve(b); }
+
+extern "C" int adsb_track_bank_fetch_summaries(adsb_track_bank *b, adsb_aircraft_record *out, size_t max, size_t *n)
+{
+    return store_fetch_summaries(b, out, max, n);
+}
+
+extern "C" int adsb_track_bank_summaries_device(adsb_track_bank *b, const adsb_aircraft_record **dev)
+{
+    return store_summaries_device(b, dev);
+}
+
+extern "C" int adsb_track_bank_fetch_changed(adsb_track_bank *b, adsb_aircraft_record *rec, double *last_heard,
+                                             adsb_velocity *velocity, size_t max, size_t *n,
+                                             uint64_t *per_receiver_counts)
+{
+    return store_fetch_changed(b, rec, last_heard, velocity, max, n, per_receiver_counts);
+}
+
+extern "C" int adsb_track_bank_fetch_last_heard(adsb_track_bank *b, double *last_heard, size_t max, size_t *n)
+{
+    return store_fetch(b, last_heard, max, n, nullptr, nullptr, last_heard_of);
+}
+
+extern "C" int adsb_track_bank_fetch_velocity(adsb_track_bank *b, adsb_velocity *velocity, size_t max, size_t *n)
+{
+    return store_fetch(b, velocity, max, n, nullptr, nullptr, velocity_of);
+}
+
+// ---- the fused view of a bank: one record per ICAO over all receivers (adsb_track.hip, launch_track_fuse) ----
+extern "C" int adsb_track_bank_fuse_reserve(adsb_track_bank *b, size_t max_fused)
+{
+    if (!b) return ADSB_E_ARG;
+    adsb_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipStreamSynchronize(c->aux)); // a fuse may still read what is freed here
+    track_bank_fuse_free(b);
+    const uint32_t nr = b->n_receivers;
+    const size_t places = b->places();
+    const size_t cap = max_fused == 0 || max_fused > places ? places : max_fused; // more than `places` cannot occur
+    const size_t key_bytes = nr > adsbk::kFuseWideReceivers ? sizeof(uint64_t) : sizeof(uint32_t);
+    b->fuse_temp_bytes = adsbk::track_fuse_temp_bytes(places, nr);
+    b->fuse_lanes = nr == 1 ? 1u : 4u; // measured: DESIGN 4.4f (16 and 64 lanes lost on runs of 64 and of 1 alike)
+    if (const char *fl = getenv("ADSB_FUSE_LANES")) { // measurement knob: lanes per ICAO in the reduction
+        const int v = atoi(fl);
+        if (v == 1 || v == 4) b->fuse_lanes = (uint32_t)v;
+    }
+    const bool ok = hipMalloc(&b->fuse_keys, 2 * key_bytes * places) == hipSuccess &&
+                    hipMalloc((void **)&b->fuse_vals, 2 * sizeof(uint32_t) * places) == hipSuccess &&
+                    hipMalloc((void **)&b->fuse_start, sizeof(uint32_t) * cap) == hipSuccess &&
+                    hipMalloc((void **)&b->fuse_out, sizeof(adsb_fused_aircraft) * cap) == hipSuccess &&
+                    hipMalloc((void **)&b->fuse_counts, sizeof(uint64_t) * 3) == hipSuccess &&
+                    hipMalloc(&b->fuse_temp, b->fuse_temp_bytes) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        track_bank_fuse_free(b);
+        return ADSB_E_NOMEM;
+    }
+    b->fuse_max = cap;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_fuse(adsb_track_bank *b, double since)
+{
+    if (!b || std::isnan(since)) return ADSB_E_ARG;
+    if (!b->fuse_max) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(b->ctx->cfg.device));
+    const size_t places = b->places();
+    const size_t key_bytes = b->n_receivers > adsbk::kFuseWideReceivers ? sizeof(uint64_t) : sizeof(uint32_t);
+    adsbk::FuseArgs a{};
+    a.bank = &b->dev;
+    a.since = since;                 // by value in the kernel's arguments, as expire's cuts: no staging, no wait
+    a.keys = b->fuse_keys;
+    a.skeys = (char *)b->fuse_keys + key_bytes * places;
+    a.vals = b->fuse_vals;
+    a.svals = b->fuse_vals + places;
+    a.seg_start = b->fuse_start;
+    a.out = b->fuse_out;
+    a.counts = b->fuse_counts;
+    a.max_fused = b->fuse_max;
+    a.temp = b->fuse_temp;
+    a.temp_bytes = b->fuse_temp_bytes;
+    a.lanes = b->fuse_lanes;
+    HIPCHK(adsbk::launch_track_fuse(b->ctx->aux, a)); // after the bank's last update / expire / reset (same stream)
+    b->fused = true;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_fetch_fused(adsb_track_bank *b, adsb_fused_aircraft *out, size_t max, size_t *n,
+                                           size_t *n_total, uint32_t *flags)
+{
+    if (!b || (!out && max)) return ADSB_E_ARG;
+    if (!b->fused) return ADSB_E_STATE;
+    adsb_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    uint64_t w[3];
+    HIPCHK(hipMemcpyAsync(w, b->fuse_counts, sizeof(w), hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    const size_t take = std::min<size_t>(std::min<uint64_t>(w[0], b->fuse_max), max);
+    if (take) {
+        HIPCHK(hipMemcpyAsync(out, b->fuse_out, sizeof(adsb_fused_aircraft) * take, hipMemcpyDeviceToHost, c->aux));
+        HIPCHK(hipStreamSynchronize(c->aux));
+    }
+    if (n) *n = take;
+    if (n_total) *n_total = (size_t)w[1];
+    if (flags) *flags = (uint32_t)w[2];
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_fused_device(adsb_track_bank *b, const adsb_fused_aircraft **fused_dev,
+                                            const uint64_t **counts_dev)
+{
+    if (!b) return ADSB_E_ARG;
+    if (!b->fused) return ADSB_E_STATE;
+    if (fused_dev) *fused_dev = b->fuse_out;
+    if (counts_dev) *counts_dev = b->fuse_counts;
+    return ADSB_OK;
+}

@@ -515,20 +515,35 @@ class Feed:
         return out[:n_out.value].copy(), flags.value, first.value
 
 
-class TrackTable:
-    """adsb_track_table_*: one aircraft table on the device that lives across launches (the reference's
-    HashMap<u32, Aircraft> of its display thread), fed one ordered frame list per update."""
+class _TrackStore:
+    """What TrackTable and TrackBank share: lifecycle, points, the summaries, and the helpers of the fetches.  A subclass
+    sets _prefix, which selects its C functions (adsb_track_table_ / adsb_track_bank_)."""
+    _prefix = None
 
-    def __init__(self, dem, max_aircraft=0, max_frames=1 << 16, seconds_per_sample=0.5e-6):
+    def _open(self, dem, cfg, max_frames):
         self._lib, self._dem = dem._lib, dem
-        cfg = L.AdsbTrackTableCfg(L.ADSB_ABI_VERSION, int(max_aircraft), int(max_frames), float(seconds_per_sample))
         h = C.c_void_p()
-        L.check(self._lib.adsb_track_table_create(dem.handle, C.byref(cfg), C.byref(h)), "adsb_track_table_create")
+        L.check(getattr(self._lib, self._prefix + "create")(dem.handle, C.byref(cfg), C.byref(h)), self._prefix + "create")
         self._h, self.max_frames = h, int(max_frames)
+
+    def _call(self, name, *args):
+        L.check(getattr(self._lib, self._prefix + name)(self._h, *args), self._prefix + name)
+
+    def _fetch(self, name, dtypes, probe=(), extra=(), size=None):
+        """<prefix><name>(handle, one buffer per dtype, max, &n, *extra): asks for n with no buffer (and `probe` in
+        place of `extra`) unless the caller knows `size`, allocates, fetches; -> one array per dtype, n long."""
+        n = C.c_size_t()
+        if size is None:
+            self._call(name, *[None] * len(dtypes), 0, C.byref(n), *probe)
+            size = n.value
+        outs = [np.zeros(max(size, 1), dtype=d) for d in dtypes]
+        types = getattr(self._lib, self._prefix + name).argtypes[1:1 + len(dtypes)]
+        self._call(name, *[o.ctypes.data_as(t) for o, t in zip(outs, types)], len(outs[0]), C.byref(n), *extra)
+        return [o[:n.value].copy() for o in outs]
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.adsb_track_table_destroy(self._h)
+            getattr(self._lib, self._prefix + "destroy")(self._h)
             self._h = None
 
     def __enter__(self):
@@ -544,135 +559,83 @@ class TrackTable:
             pass
 
     def reset(self):
-        L.check(self._lib.adsb_track_table_reset(self._h), "adsb_track_table_reset")
-
-    def update(self, frames, sample_base=0):
-        """frames: FRAME_DTYPE array in ascending offset (host); packet time = (sample_base + offset) x sps."""
-        frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
-        L.check(self._lib.adsb_track_table_update(self._h, frames.ctypes.data if len(frames) else None, len(frames),
-                                                  int(sample_base)), "adsb_track_table_update")
-
-    def update_device(self, dev_ptr, n, sample_base=0):
-        """n frames at dev_ptr in the ctx device's memory (e.g. result_device() after fetch_counts())."""
-        L.check(self._lib.adsb_track_table_update(self._h, dev_ptr, int(n), int(sample_base)), "adsb_track_table_update")
+        self._call("reset")
 
     def points(self):
-        """One TRACK_POINT_DTYPE record per frame of the last update, in its order."""
-        out = np.zeros(max(self.max_frames, 1), dtype=TRACK_POINT_DTYPE)
-        n = C.c_size_t()
-        L.check(self._lib.adsb_track_table_fetch_points(self._h, out.ctypes.data, len(out), C.byref(n)),
-                "adsb_track_table_fetch_points")
-        return out[:n.value].copy()
-
-    def aircraft(self):
-        """(AIRCRAFT_DTYPE records of the whole table in ascending ICAO, table flags)."""
-        n, flags = C.c_size_t(), C.c_uint32()
-        L.check(self._lib.adsb_track_table_fetch(self._h, None, 0, C.byref(n), C.byref(flags)), "adsb_track_table_fetch")
-        out = np.zeros(max(n.value, 1), dtype=AIRCRAFT_DTYPE)
-        L.check(self._lib.adsb_track_table_fetch(self._h, out.ctypes.data, len(out), C.byref(n), C.byref(flags)),
-                "adsb_track_table_fetch")
-        return out[:n.value].copy(), flags.value
-
-    def expire(self, before):
-        """Evicts every aircraft whose last frame of any kind is older than `before` seconds (asynchronous)."""
-        L.check(self._lib.adsb_track_table_expire(self._h, float(before)), "adsb_track_table_expire")
-
-    def last_heard(self):
-        """float64 last-heard times (seconds), aligned with aircraft()[0]."""
-        n = C.c_size_t()
-        L.check(self._lib.adsb_track_table_fetch_last_heard(self._h, None, 0, C.byref(n)),
-                "adsb_track_table_fetch_last_heard")
-        out = np.zeros(max(n.value, 1), dtype=np.float64)
-        L.check(self._lib.adsb_track_table_fetch_last_heard(self._h, out.ctypes.data_as(C.POINTER(C.c_double)), len(out),
-                                                            C.byref(n)), "adsb_track_table_fetch_last_heard")
-        return out[:n.value].copy()
-
-    def velocity(self):
-        """VELOCITY_DTYPE records (each aircraft's last airborne-velocity message), aligned with aircraft()[0]."""
-        n = C.c_size_t()
-        L.check(self._lib.adsb_track_table_fetch_velocity(self._h, None, 0, C.byref(n)),
-                "adsb_track_table_fetch_velocity")
-        out = np.zeros(max(n.value, 1), dtype=VELOCITY_DTYPE)
-        L.check(self._lib.adsb_track_table_fetch_velocity(self._h, out.ctypes.data_as(C.POINTER(L.AdsbVelocity)),
-                                                          len(out), C.byref(n)), "adsb_track_table_fetch_velocity")
-        return out[:n.value].copy()
+        """One TRACK_POINT_DTYPE record per frame of the last update, in its list order."""
+        return self._fetch("fetch_points", [TRACK_POINT_DTYPE], size=self.max_frames)[0]
 
     def summaries_reserve(self):
-        """adsb_track_table_summaries_reserve: from now on every update also leaves one summary per frame and the
-        changed list on the device."""
-        L.check(self._lib.adsb_track_table_summaries_reserve(self._h), "adsb_track_table_summaries_reserve")
+        """adsb_track_{table,bank}_summaries_reserve: from now on every update also leaves one summary per frame and
+        the changed list on the device."""
+        self._call("summaries_reserve")
 
     def summaries(self):
-        """One AIRCRAFT_DTYPE record per frame of the last update, in its order: the frame's aircraft as it stands
-        right after that frame (what the reference's web thread broadcasts per packet)."""
-        return _fetch_summaries(self._lib.adsb_track_table_fetch_summaries, self._h, "adsb_track_table_fetch_summaries")
+        """One AIRCRAFT_DTYPE record per frame of the last update, in its list order (a bank: receiver 0's frames
+        first): the frame's aircraft (a bank: on its receiver) as it stands right after that frame, which is what the
+        reference's web thread broadcasts per packet."""
+        return self._fetch("fetch_summaries", [AIRCRAFT_DTYPE])[0]
 
     def summaries_device(self):
         """Device address of the last update's summaries; valid on the ctx stream, no synchronisation."""
         dev = C.c_void_p()
-        L.check(self._lib.adsb_track_table_summaries_device(self._h, C.byref(dev)), "adsb_track_table_summaries_device")
+        self._call("summaries_device", C.byref(dev))
         return dev.value
+
+
+class TrackTable(_TrackStore):
+    """adsb_track_table_*: one aircraft table on the device that lives across launches (the reference's
+    HashMap<u32, Aircraft> of its display thread), fed one ordered frame list per update."""
+    _prefix = "adsb_track_table_"
+
+    def __init__(self, dem, max_aircraft=0, max_frames=1 << 16, seconds_per_sample=0.5e-6):
+        self._open(dem, L.AdsbTrackTableCfg(L.ADSB_ABI_VERSION, int(max_aircraft), int(max_frames),
+                                            float(seconds_per_sample)), max_frames)
+
+    def update(self, frames, sample_base=0):
+        """frames: FRAME_DTYPE array in ascending offset (host); packet time = (sample_base + offset) x sps."""
+        frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+        self._call("update", frames.ctypes.data if len(frames) else None, len(frames), int(sample_base))
+
+    def update_device(self, dev_ptr, n, sample_base=0):
+        """n frames at dev_ptr in the ctx device's memory (e.g. result_device() after fetch_counts())."""
+        self._call("update", dev_ptr, int(n), int(sample_base))
+
+    def aircraft(self):
+        """(AIRCRAFT_DTYPE records of the whole table in ascending ICAO, table flags)."""
+        flags = C.c_uint32()
+        recs, = self._fetch("fetch", [AIRCRAFT_DTYPE], (C.byref(flags),), (C.byref(flags),))
+        return recs, flags.value
+
+    def expire(self, before):
+        """Evicts every aircraft whose last frame of any kind is older than `before` seconds (asynchronous)."""
+        self._call("expire", float(before))
+
+    def last_heard(self):
+        """float64 last-heard times (seconds), aligned with aircraft()[0]."""
+        return self._fetch("fetch_last_heard", [np.float64])[0]
+
+    def velocity(self):
+        """VELOCITY_DTYPE records (each aircraft's last airborne-velocity message), aligned with aircraft()[0]."""
+        return self._fetch("fetch_velocity", [VELOCITY_DTYPE])[0]
 
     def changed(self):
         """(records, last_heard, velocity) of the aircraft the last update touched, ascending ICAO: the matching rows
         of aircraft()[0], last_heard() and velocity(), without copying the table."""
-        return _fetch_changed(self._lib.adsb_track_table_fetch_changed, self._h, "adsb_track_table_fetch_changed")[:3]
+        return tuple(self._fetch("fetch_changed", [AIRCRAFT_DTYPE, np.float64, VELOCITY_DTYPE]))
 
 
-def _fetch_summaries(fn, handle, where):
-    n = C.c_size_t()
-    L.check(fn(handle, None, 0, C.byref(n)), where)
-    out = np.zeros(max(n.value, 1), dtype=AIRCRAFT_DTYPE)
-    L.check(fn(handle, out.ctypes.data, len(out), C.byref(n)), where)
-    return out[:n.value].copy()
-
-
-def _fetch_changed(fn, handle, where, n_receivers=None):
-    """(records, last_heard, velocity, per-receiver counts or None) of adsb_track_{table,bank}_fetch_changed"""
-    n = C.c_size_t()
-    extra = () if n_receivers is None else (None,)
-    L.check(fn(handle, None, None, None, 0, C.byref(n), *extra), where)
-    size = max(n.value, 1)
-    recs, heard = np.zeros(size, dtype=AIRCRAFT_DTYPE), np.zeros(size, dtype=np.float64)
-    vel = np.zeros(size, dtype=VELOCITY_DTYPE)
-    counts = None if n_receivers is None else (C.c_uint64 * n_receivers)()
-    L.check(fn(handle, recs.ctypes.data, heard.ctypes.data_as(C.POINTER(C.c_double)),
-               vel.ctypes.data_as(C.POINTER(L.AdsbVelocity)), size, C.byref(n), *(() if counts is None else (counts,))),
-            where)
-    return (recs[:n.value].copy(), heard[:n.value].copy(), vel[:n.value].copy(),
-            None if counts is None else [int(x) for x in counts])
-
-
-class TrackBank:
+class TrackBank(_TrackStore):
     """adsb_track_bank_*: n_receivers independent aircraft tables on the device (one HashMap<u32, Aircraft> per
     receiver's display thread), all updated by one call over a multi-receiver frame list; receiver r equals a
     TrackTable fed receiver r's part of every update."""
+    _prefix = "adsb_track_bank_"
 
     def __init__(self, dem, n_receivers, max_aircraft=0, max_frames=1 << 16, seconds_per_sample=0.5e-6):
-        self._lib, self._dem = dem._lib, dem
-        cfg = L.AdsbTrackBankCfg(L.ADSB_ABI_VERSION, int(n_receivers), int(max_aircraft), 0, int(max_frames),
-                                 float(seconds_per_sample))
-        h = C.c_void_p()
-        L.check(self._lib.adsb_track_bank_create(dem.handle, C.byref(cfg), C.byref(h)), "adsb_track_bank_create")
-        self._h, self.n_receivers, self.max_frames = h, int(n_receivers), int(max_frames)
+        self._open(dem, L.AdsbTrackBankCfg(L.ADSB_ABI_VERSION, int(n_receivers), int(max_aircraft), 0, int(max_frames),
+                                           float(seconds_per_sample)), max_frames)
+        self.n_receivers = int(n_receivers)
         self._fuse_reserved = None       # max_fused of the last fuse_reserve
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.adsb_track_bank_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def _u64s(self, values, what):
         """None / a scalar (the same for every receiver) / a per-receiver sequence -> a uint64[n_receivers] array."""
@@ -685,46 +648,32 @@ class TrackBank:
             raise ValueError(f"{what}: {len(values)} values for {self.n_receivers} receivers")
         return (C.c_uint64 * self.n_receivers)(*values)
 
-    def reset(self):
-        L.check(self._lib.adsb_track_bank_reset(self._h), "adsb_track_bank_reset")
+    def _split(self, out, counts):
+        """One array of all receivers' rows -> a list of n_receivers arrays, counts[r] rows each."""
+        edges = np.concatenate([[0], np.cumsum(list(counts))]).astype(np.int64)
+        return [out[edges[r]:edges[r + 1]].copy() for r in range(self.n_receivers)]
 
     def update(self, frames, counts, sample_base=None):
         """frames: FRAME_DTYPE array (host), receiver 0's frames in ascending offset, then receiver 1's, ...;
         counts: frames of each receiver; sample_base: scalar or per receiver (frame time = (base + offset) x sps)."""
         frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
-        L.check(self._lib.adsb_track_bank_update(self._h, frames.ctypes.data if len(frames) else None, len(frames),
-                                                 self._u64s(counts, "counts"), self._u64s(sample_base, "sample_base")),
-                "adsb_track_bank_update")
+        self._call("update", frames.ctypes.data if len(frames) else None, len(frames), self._u64s(counts, "counts"),
+                   self._u64s(sample_base, "sample_base"))
 
     def update_device(self, dev_ptr, n, counts, sample_base=None):
         """n frames at dev_ptr in the ctx device's memory, split by counts as for update()."""
-        L.check(self._lib.adsb_track_bank_update(self._h, dev_ptr, int(n), self._u64s(counts, "counts"),
-                                                 self._u64s(sample_base, "sample_base")), "adsb_track_bank_update")
+        self._call("update", dev_ptr, int(n), self._u64s(counts, "counts"), self._u64s(sample_base, "sample_base"))
 
     def update_launch(self, sample_base=None):
         """The ctx's last launch, channel k -> receiver k: what fetch() returns, read in device memory."""
-        L.check(self._lib.adsb_track_bank_update_launch(self._h, self._u64s(sample_base, "sample_base")),
-                "adsb_track_bank_update_launch")
-
-    def points(self):
-        """One TRACK_POINT_DTYPE record per frame of the last update, in its list order."""
-        out = np.zeros(max(self.max_frames, 1), dtype=TRACK_POINT_DTYPE)
-        n = C.c_size_t()
-        L.check(self._lib.adsb_track_bank_fetch_points(self._h, out.ctypes.data, len(out), C.byref(n)),
-                "adsb_track_bank_fetch_points")
-        return out[:n.value].copy()
+        self._call("update_launch", self._u64s(sample_base, "sample_base"))
 
     def aircraft(self):
         """(list of n_receivers AIRCRAFT_DTYPE arrays, each in ascending ICAO; list of per-receiver flags)."""
-        n = C.c_size_t()
         counts = (C.c_uint64 * self.n_receivers)()
         flags = (C.c_uint32 * self.n_receivers)()
-        L.check(self._lib.adsb_track_bank_fetch(self._h, None, 0, C.byref(n), None, None), "adsb_track_bank_fetch")
-        out = np.zeros(max(n.value, 1), dtype=AIRCRAFT_DTYPE)
-        L.check(self._lib.adsb_track_bank_fetch(self._h, out.ctypes.data, len(out), C.byref(n), counts, flags),
-                "adsb_track_bank_fetch")
-        edges = np.concatenate([[0], np.cumsum(list(counts))]).astype(np.int64)
-        return [out[edges[r]:edges[r + 1]].copy() for r in range(self.n_receivers)], list(flags)
+        out, = self._fetch("fetch", [AIRCRAFT_DTYPE], (None, None), (counts, flags))
+        return self._split(out, counts), list(flags)
 
     def expire(self, before):
         """Evicts, on every receiver r, the aircraft whose last frame is older than before[r] seconds; `before` is a
@@ -734,28 +683,20 @@ class TrackBank:
         before = [float(v) for v in before]
         if len(before) != self.n_receivers:
             raise ValueError(f"before: {len(before)} values for {self.n_receivers} receivers")
-        L.check(self._lib.adsb_track_bank_expire(self._h, (C.c_double * self.n_receivers)(*before)),
-                "adsb_track_bank_expire")
+        self._call("expire", (C.c_double * self.n_receivers)(*before))
+
+    def _aligned(self, name, dtype):
+        """fetch_last_heard / fetch_velocity as a list of n_receivers arrays, aligned with aircraft()[0]."""
+        sizes = [len(x) for x in self.aircraft()[0]]      # the per-receiver split of the same records
+        return self._split(self._fetch(name, [dtype], size=sum(sizes))[0], sizes)
 
     def last_heard(self):
         """list of n_receivers float64 arrays of last-heard times (seconds), aligned with aircraft()[0]."""
-        recs, _ = self.aircraft()                         # the per-receiver split of the same records
-        n = C.c_size_t()
-        out = np.zeros(max(sum(len(x) for x in recs), 1), dtype=np.float64)
-        L.check(self._lib.adsb_track_bank_fetch_last_heard(self._h, out.ctypes.data_as(C.POINTER(C.c_double)),
-                                                           len(out), C.byref(n)), "adsb_track_bank_fetch_last_heard")
-        edges = np.concatenate([[0], np.cumsum([len(x) for x in recs])]).astype(np.int64)
-        return [out[edges[r]:edges[r + 1]].copy() for r in range(self.n_receivers)]
+        return self._aligned("fetch_last_heard", np.float64)
 
     def velocity(self):
         """list of n_receivers VELOCITY_DTYPE arrays, aligned with aircraft()[0]."""
-        recs, _ = self.aircraft()                         # the per-receiver split of the same records
-        n = C.c_size_t()
-        out = np.zeros(max(sum(len(x) for x in recs), 1), dtype=VELOCITY_DTYPE)
-        L.check(self._lib.adsb_track_bank_fetch_velocity(self._h, out.ctypes.data_as(C.POINTER(L.AdsbVelocity)),
-                                                         len(out), C.byref(n)), "adsb_track_bank_fetch_velocity")
-        edges = np.concatenate([[0], np.cumsum([len(x) for x in recs])]).astype(np.int64)
-        return [out[edges[r]:edges[r + 1]].copy() for r in range(self.n_receivers)]
+        return self._aligned("fetch_velocity", VELOCITY_DTYPE)
 
     def fuse(self, since=-math.inf, max_fused=None):
         """The fused view: one FUSED_DTYPE record per distinct ICAO over all receivers, ascending ICAO, from the records
@@ -767,54 +708,36 @@ class TrackBank:
             raise ValueError("max_fused must be positive, or None")
         if self._fuse_reserved is None or (max_fused is not None and want != self._fuse_reserved):
             self.fuse_reserve(want)
-        L.check(self._lib.adsb_track_bank_fuse(self._h, float(since)), "adsb_track_bank_fuse")
+        self.fuse_async(since)
         n, total, flags = C.c_size_t(), C.c_size_t(), C.c_uint32()
-        L.check(self._lib.adsb_track_bank_fetch_fused(self._h, None, 0, C.byref(n), C.byref(total), C.byref(flags)),
-                "adsb_track_bank_fetch_fused")
+        self._call("fetch_fused", None, 0, C.byref(n), C.byref(total), C.byref(flags))
         out = np.zeros(max(total.value, 1), dtype=FUSED_DTYPE)
-        L.check(self._lib.adsb_track_bank_fetch_fused(self._h, out.ctypes.data_as(C.POINTER(L.AdsbFusedAircraft)),
-                                                      len(out), C.byref(n), C.byref(total), C.byref(flags)),
-                "adsb_track_bank_fetch_fused")
+        self._call("fetch_fused", out.ctypes.data_as(C.POINTER(L.AdsbFusedAircraft)), len(out), C.byref(n),
+                   C.byref(total), C.byref(flags))
         return out[:n.value].copy(), int(total.value), int(flags.value)
 
     def fuse_reserve(self, max_fused=0):
         """adsb_track_bank_fuse_reserve: memory for up to max_fused fused records (0: n_receivers x max_aircraft)."""
-        L.check(self._lib.adsb_track_bank_fuse_reserve(self._h, int(max_fused)), "adsb_track_bank_fuse_reserve")
+        self._call("fuse_reserve", int(max_fused))
         self._fuse_reserved = int(max_fused)
 
     def fuse_async(self, since=-math.inf):
         """adsb_track_bank_fuse alone: enqueues the fusion on the ctx stream (after fuse_reserve) and returns."""
-        L.check(self._lib.adsb_track_bank_fuse(self._h, float(since)), "adsb_track_bank_fuse")
+        self._call("fuse", float(since))
 
     def fused_device(self):
         """(device address of the fused records, device address of uint64[2]: records written, distinct ICAOs) of the
         last fuse, for consumers that stay on the GPU; valid on the ctx stream, no synchronisation."""
         rec, counts = C.c_void_p(), C.c_void_p()
-        L.check(self._lib.adsb_track_bank_fused_device(self._h, C.byref(rec), C.byref(counts)),
-                "adsb_track_bank_fused_device")
+        self._call("fused_device", C.byref(rec), C.byref(counts))
         return rec.value, counts.value
-
-    def summaries_reserve(self):
-        """adsb_track_bank_summaries_reserve: from now on every update also leaves one summary per frame and the
-        changed list on the device."""
-        L.check(self._lib.adsb_track_bank_summaries_reserve(self._h), "adsb_track_bank_summaries_reserve")
-
-    def summaries(self):
-        """One AIRCRAFT_DTYPE record per frame of the last update, in its list order (receiver 0's frames first): the
-        frame's aircraft on its receiver as it stands right after that frame."""
-        return _fetch_summaries(self._lib.adsb_track_bank_fetch_summaries, self._h, "adsb_track_bank_fetch_summaries")
-
-    def summaries_device(self):
-        """Device address of the last update's summaries; valid on the ctx stream, no synchronisation."""
-        dev = C.c_void_p()
-        L.check(self._lib.adsb_track_bank_summaries_device(self._h, C.byref(dev)), "adsb_track_bank_summaries_device")
-        return dev.value
 
     def changed(self):
         """(records, last_heard, velocity, per-receiver counts) of the aircraft the last update touched: receiver 0's in
         ascending ICAO, then receiver 1's, ...; rows of aircraft(), last_heard() and velocity()."""
-        return _fetch_changed(self._lib.adsb_track_bank_fetch_changed, self._h, "adsb_track_bank_fetch_changed",
-                              self.n_receivers)
+        counts = (C.c_uint64 * self.n_receivers)()
+        rows = self._fetch("fetch_changed", [AIRCRAFT_DTYPE, np.float64, VELOCITY_DTYPE], (None,), (counts,))
+        return (*rows, [int(x) for x in counts])
 
 
 def packet_new(frame_bytes):

@@ -10,8 +10,7 @@ cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 mkdir -p air_rs_amd/lib/variants
 SRC=air_rs_amd/csrc
-FILES="$SRC/adsb_kernels.hip $SRC/adsb_track.hip $SRC/adsb_api.cpp $SRC/adsb_group.cpp
-    $SRC/host/adsb_packet.cpp $SRC/host/adsb_aircraft.cpp $SRC/host/adsb_threads.cpp $SRC/host/adsb_host_api.cpp"
+FILES=$(sed "s|^|$SRC/|" $SRC/sources.list) # the library's sources: one list, read by tools/build_variant.sh and tools/gpu/mkvar.sh too
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -pthread -Wall -Wno-unused-function"
 $HIPCC $FLAGS $FILES -o air_rs_amd/lib/libadsb_hip.so &
 $HIPCC $FLAGS -DADSB_AB_KERNELS=1 $FILES -o air_rs_amd/lib/variants/libadsb_hip_ab.so &
