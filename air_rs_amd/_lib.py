@@ -67,6 +67,14 @@ class AdsbPacketFields(C.Structure):
                 ("callsign", C.c_char * 8)]
 
 
+ADSB_LEVEL_VALID = 0x1  # adsb_frame_level.flags: the frame's window lay inside the buffer
+
+
+class AdsbFrameLevel(C.Structure):
+    _fields_ = [("signal_sum", C.c_uint64), ("noise_sum", C.c_uint64), ("peak", C.c_uint32), ("pulse_min", C.c_uint32),
+                ("quiet_max", C.c_uint32), ("weak_bits", C.c_uint16), ("flags", C.c_uint16)]
+
+
 class AdsbTrackPoint(C.Structure):
     _fields_ = [("latitude", C.c_double), ("longitude", C.c_double), ("icao", C.c_uint32), ("flags", C.c_uint32)]
 
@@ -150,6 +158,11 @@ PROTOTYPES = {
     "adsb_decode_fields_device_async": (C.c_int, [C.c_void_p]),
     "adsb_fetch_fields": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "adsb_fields_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "adsb_levels_device_async": (C.c_int, [C.c_void_p]),
+    "adsb_fetch_levels": (C.c_int, [C.c_void_p, _P(AdsbFrameLevel), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_levels_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "adsb_levels_of": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t,
+                                 _P(AdsbFrameLevel)]),
     "adsb_track_device": (C.c_int, [C.c_void_p, C.c_double]),
     "adsb_fetch_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t,
                                    _P(C.c_size_t)]),
@@ -260,6 +273,9 @@ PROTOTYPES = {
     "adsb_save_c16": (C.c_int, [C.c_char_p, C.c_void_p, C.c_size_t]),
     "adsb_load_u8": (C.c_int, [C.c_char_p, _P(_P(C.c_int8)), _P(C.c_size_t)]),
     "adsb_free": (None, [C.c_void_p]),
+    "adsb_host_frame_levels": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t,
+                                         _P(AdsbFrameLevel)]),
+    "adsb_level_dbfs": (C.c_double, [C.c_int, C.c_uint64, C.c_uint32]),
 }
 
 _lib = None

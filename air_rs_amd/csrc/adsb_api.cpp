@@ -64,6 +64,9 @@ extern "C" void adsb_destroy(adsb_ctx *c)
     }
     (void)hipFree(c->out_start);
     (void)hipFree(c->fields);
+    (void)hipFree(c->levels);
+    (void)hipFree(c->lvof_out);
+    (void)hipFree(c->lvof_frames);
     (void)hipFree(c->trk_u32);
     (void)hipFree(c->trk_temp);
     (void)hipFree(c->trk_points);
@@ -359,6 +362,7 @@ extern "C" int adsb_demod_device_async(adsb_ctx *c, const void *iq_dev, uint32_t
     c->last_base = c->stream_base;
     c->launched = true;
     c->fields_current = false;
+    c->levels_current = false;
     c->trk_done = false;
 
     // Launch i uses result set i & 1.  (ADSB_OVERLAP_ORDERING=1: the finishing kernel of launch i runs on `aux` beside
@@ -417,6 +421,7 @@ static void view_launch(adsb_ctx *c, uint32_t set)
     c->last_iq = li.iq; c->last_channels = li.channels; c->last_samples = li.samples; c->last_stride = li.stride;
     c->last_base = li.base; c->last_tpc = li.tpc; c->last_tiles = li.tiles; c->last_out = li.out; c->last_cap = li.cap;
     c->fields_current = false;
+    c->levels_current = false;
     c->trk_done = false;
 }
 
@@ -481,6 +486,7 @@ static int small_launch(adsb_ctx *c, const void *iq, size_t n_samples, uint64_t 
     c->last_base = c->stream_base;
     c->launched = true;
     c->fields_current = false;
+    c->levels_current = false;
     c->trk_done = false;
     const uint32_t i = c->launch_idx, set = i & 1u;
     adsb_ctx::ResultSet &r = c->rs[set];
@@ -613,7 +619,8 @@ int sync_header(adsb_ctx *c)
         int rc = rerun_in_batches(c, r);
         if (rc != ADSB_OK) return rc;
         c->hdr_host->retry = 0;
-        c->fields_current = false; // the list was rebuilt: decoded fields / tracker output are stale
+        c->fields_current = false; // the list was rebuilt: decoded fields / levels / tracker output are stale
+        c->levels_current = false;
         c->trk_done = false;
     }
     return ADSB_OK;
@@ -699,6 +706,130 @@ extern "C" int adsb_fetch_fields(adsb_ctx *c, adsb_packet_fields *out, size_t ma
     return ADSB_OK;
 }
 
+
+// ---- per-frame signal and noise power (adsb_levels.hip) ----------------------------------------------------------------
+// The levels kernel walks its frames in a grid-stride loop, one wave each: the grid is sized from the device (a few
+// waves per SIMD hide the latency of the scattered 480-byte reads), not from max_out, and never above one wave per frame.
+static uint32_t levels_grid(adsb_ctx *c, uint64_t cap)
+{
+    if (!c->levels_blocks) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->cfg.device) != hipSuccess || cus <= 0) {
+            (void)hipGetLastError();
+            cus = 256;
+        }
+        c->levels_blocks = (uint32_t)cus * 8u; // 8 blocks of 4 waves per CU: 8 waves per SIMD
+    }
+    return (uint32_t)std::min<uint64_t>((cap + 3) / 4, c->levels_blocks);
+}
+
+extern "C" int adsb_levels_device_async(adsb_ctx *c)
+{
+    if (!c) return ADSB_E_ARG;
+    if (!c->launched) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (!c->levels && hipMalloc((void **)&c->levels, sizeof(adsb_frame_level) * (size_t)c->cfg.max_out) != hipSuccess) {
+        (void)hipGetLastError();
+        return ADSB_E_NOMEM;
+    }
+    adsbk::LevelsArgs a{};
+    a.iq = c->last_iq;
+    a.n_samples = c->last_samples;
+    a.channel_stride = c->last_stride;
+    a.offset_base = c->last_base;
+    a.frames = c->last_out;
+    a.hdr = c->rs[c->last].hdr;
+    a.cap = c->last_cap;
+    a.n_channels = c->last_channels;
+    a.chan_prefix = c->rs[c->last].chan_prefix;
+    a.out = c->levels;
+    // same stream as the ordering pass, so it sees the finished list and header
+    HIPCHK(adsbk::launch_frame_levels(c->aux, c->cfg.sample_type, a, levels_grid(c, a.cap)));
+    c->levels_current = true;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_levels_device(adsb_ctx *c, const adsb_frame_level **levels_dev)
+{
+    if (!c || !levels_dev) return ADSB_E_ARG;
+    *levels_dev = c->levels;
+    return c->levels ? ADSB_OK : ADSB_E_STATE;
+}
+
+extern "C" int adsb_fetch_levels(adsb_ctx *c, adsb_frame_level *out, size_t max_out, size_t *n_out)
+{
+    if (!c || !n_out || (!out && max_out)) return ADSB_E_ARG;
+    if (!c->launched || !c->levels || !c->levels_current) return ADSB_E_STATE;
+    int rc = sync_header(c);
+    if (rc != ADSB_OK) return rc;
+    // the wait found holes in the list and rebuilt it (slot-pool overflow): the levels enqueued before are of the list
+    // with holes.  Again, for the rebuilt one (the host has waited for the rebuild).
+    if (!c->levels_current && (rc = adsb_levels_device_async(c)) != ADSB_OK) return rc;
+    uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
+    if (n > max_out) n = max_out;
+    if (n) HIPCHK(hipMemcpyAsync(out, c->levels, sizeof(adsb_frame_level) * n, hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    *n_out = (size_t)n;
+    return ADSB_OK;
+}
+
+static bool levels_in_device_memory(const adsb_ctx *c, const void *p)
+{
+    hipPointerAttribute_t at{};
+    const bool yes = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice &&
+                     at.device == c->cfg.device;
+    (void)hipGetLastError(); // a plain host pointer is an error to the query: do not leave it to the launches after it
+    return yes;
+}
+
+template <typename T>
+static int grow_device(T **p, size_t *have, size_t want)
+{
+    if (*have >= want) return ADSB_OK;
+    (void)hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    if (hipMalloc((void **)p, sizeof(T) * want) != hipSuccess) {
+        (void)hipGetLastError();
+        return ADSB_E_NOMEM;
+    }
+    *have = want;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_levels_of(adsb_ctx *c, const void *iq_dev, size_t n_samples, uint64_t first_sample_index,
+                              const adsb_frame *frames, size_t n, adsb_frame_level *out)
+{
+    if (!c || !iq_dev || ((!frames || !out) && n)) return ADSB_E_ARG;
+    if ((uintptr_t)iq_dev & (c->bps - 1u)) return ADSB_E_ARG;
+    if (n > 0xFFFFFFFFull) return ADSB_E_CAPACITY;
+    if (n == 0) return ADSB_OK;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipStreamSynchronize(c->aux)); // an earlier call's kernel may still read the scratch that is about to grow
+    int rc = grow_device(&c->lvof_out, &c->lvof_out_n, n);
+    if (rc != ADSB_OK) return rc;
+    const adsb_frame *list = frames;
+    if (!levels_in_device_memory(c, frames)) {
+        if ((rc = grow_device(&c->lvof_frames, &c->lvof_frames_n, n)) != ADSB_OK) return rc;
+        HIPCHK(hipMemcpyAsync(c->lvof_frames, frames, sizeof(adsb_frame) * n, hipMemcpyHostToDevice, c->aux));
+        list = c->lvof_frames;
+    }
+    adsbk::LevelsArgs a{};
+    a.iq = iq_dev;
+    a.n_samples = n_samples;
+    a.channel_stride = n_samples;
+    a.offset_base = first_sample_index;
+    a.frames = list;
+    a.hdr = nullptr;
+    a.cap = (uint32_t)n;
+    a.n_channels = 1;
+    a.chan_prefix = nullptr;
+    a.out = c->lvof_out;
+    HIPCHK(adsbk::launch_frame_levels(c->aux, c->cfg.sample_type, a, levels_grid(c, n)));
+    HIPCHK(hipMemcpyAsync(out, c->lvof_out, sizeof(adsb_frame_level) * n, hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    return ADSB_OK;
+}
 
 extern "C" int adsb_set_result_target(adsb_ctx *c, void *blob_dev, size_t blob_bytes)
 {

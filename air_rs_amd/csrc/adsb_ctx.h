@@ -41,6 +41,13 @@ struct adsb_ctx {
     bool own_aux = false;
     adsb_packet_fields *fields = nullptr; // [max_out], allocated on first adsb_decode_fields_device_async
     bool fields_current = false;    // fields[] belongs to the last launch
+    adsb_frame_level *levels = nullptr; // [max_out], allocated on first adsb_levels_device_async
+    bool levels_current = false;    // levels[] belongs to the last launch
+    // adsb_levels_of's own scratch (grown on demand): the records, and the device copy of a host frame list
+    adsb_frame_level *lvof_out = nullptr;
+    adsb_frame *lvof_frames = nullptr;
+    size_t lvof_out_n = 0, lvof_frames_n = 0;
+    uint32_t levels_blocks = 0;     // the levels kernel's largest grid: a few waves per SIMD of this device
     // tracker (allocated on first adsb_track_device)
     uint32_t *trk_u32 = nullptr;    // 4 x [max_out]: keys, vals, sorted keys, sorted vals
     void *trk_temp = nullptr;

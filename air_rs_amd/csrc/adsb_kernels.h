@@ -164,6 +164,23 @@ bool tile_stamps_built(); // -DADSB_TILE_STAMPS=1 diagnostic build: DemodArgs::s
 hipError_t launch_decode_fields(hipStream_t s, const adsb_frame *frames, const Header *hdr, uint32_t cap,
                                 adsb_packet_fields *out); // hdr == nullptr: exactly cap frames
 
+// per-frame power statistics of an ordered frame list (adsb_levels.hip): one wavefront per frame reads the 240 samples
+// the frame was decoded from
+struct LevelsArgs {
+    const void *iq;              // channel 0, sample 0 (device-visible; aligned to one sample)
+    uint64_t n_samples;          // per channel
+    uint64_t channel_stride;     // samples between channel starts
+    uint64_t offset_base;        // frame i sits at sample frames[i].offset - offset_base of its channel
+    const adsb_frame *frames;
+    const Header *hdr;           // count = min(hdr->n_out, cap), read on the device; nullptr: exactly cap frames
+    uint32_t cap;
+    uint32_t n_channels;         // 1: every frame is channel 0's and chan_prefix is not read
+    const uint64_t *chan_prefix; // [n_channels + 1]: frames of the list before each channel's first
+    adsb_frame_level *out;       // [cap]
+};
+// blocks: the grid (4 waves per block, frames in a grid-stride loop); sized from the device by the caller
+hipError_t launch_frame_levels(hipStream_t s, int sample_type, const LevelsArgs &a, uint32_t blocks);
+
 // tracker + CPR position decode over an ordered frame list (adsb_track.hip)
 // One aircraft of a persistent table (adsb_track_table_*): the public record plus the last even and the last odd
 // position message (aircraft.rs:28-31) that a later update's first position message of the other format pairs with.

@@ -22,6 +22,11 @@ FIELDS_DTYPE = np.dtype([("icao", "<u4"), ("altitude", "<i4"), ("cpr_latitude", 
                          ("cpr_odd", "u1"), ("callsign", "S8")])
 assert FIELDS_DTYPE.itemsize == C.sizeof(L.AdsbPacketFields) == 32
 
+LEVEL_DTYPE = np.dtype([("signal_sum", "<u8"), ("noise_sum", "<u8"), ("peak", "<u4"), ("pulse_min", "<u4"),
+                        ("quiet_max", "<u4"), ("weak_bits", "<u2"), ("flags", "<u2")])
+assert LEVEL_DTYPE.itemsize == C.sizeof(L.AdsbFrameLevel) == 32
+LEVEL_PULSE_SAMPLES, LEVEL_QUIET_SAMPLES = 116, 124  # of a frame's 240: what signal_sum and noise_sum add up
+
 WINDOW = 240  # 16 preamble + 112*2 samples (reference src/adsb.rs:98)
 
 
@@ -42,6 +47,37 @@ def synth_fill_host(cfg, sample_type, channel, first_sample, n_samples):
     L.check(L.load().adsb_synth_fill_host(C.byref(cfg), sample_type, channel, first_sample,
                                           n_samples, out.ctypes.data), "adsb_synth_fill_host")
     return out
+
+
+def _sample_type_of(iq):
+    iq = np.asarray(iq)
+    if iq.dtype == np.int8:
+        return L.ADSB_SAMPLE_I8
+    if iq.dtype == np.int16:
+        return L.ADSB_SAMPLE_I16
+    raise TypeError(f"IQ samples are int8 or int16, not {iq.dtype}")
+
+
+def host_frame_levels(iq, frames, first_sample=0):
+    """adsb_host_frame_levels, the CPU mirror of AdsbDemod.levels_of: one LEVEL_DTYPE record per frame of `frames`
+    (FRAME_DTYPE) from the one-channel host buffer iq (int8 or int16, shape (n, 2)), whose sample 0 is stream sample
+    first_sample.  A frame whose 240 samples are not all inside iq gets flags 0 and zeros."""
+    st = _sample_type_of(iq)
+    iq = np.ascontiguousarray(iq)
+    n_samples = iq.size // 2
+    frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+    out = np.zeros(max(len(frames), 1), dtype=LEVEL_DTYPE)
+    keep = iq if iq.size else np.zeros(2, dtype=iq.dtype)      # a non-NULL pointer for an empty buffer
+    L.check(L.load().adsb_host_frame_levels(st, keep.ctypes.data, n_samples, int(first_sample),
+                                            frames.ctypes.data if len(frames) else None, len(frames),
+                                            out.ctypes.data_as(C.POINTER(L.AdsbFrameLevel))), "adsb_host_frame_levels")
+    return out[:len(frames)].copy()
+
+
+def level_dbfs(sample_type, total, n_samples):
+    """adsb_level_dbfs: 10 log10(total / n_samples / full scale) -- a LEVEL_DTYPE sum as mean power in dBFS (-inf for
+    0).  level_dbfs(st, rec["signal_sum"], LEVEL_PULSE_SAMPLES), level_dbfs(st, rec["noise_sum"], LEVEL_QUIET_SAMPLES)."""
+    return float(L.load().adsb_level_dbfs(int(sample_type), int(total), int(n_samples)))
 
 
 def measure_feed(device, sample_type, chunk, seconds=0.15):
@@ -141,6 +177,7 @@ class AdsbDemod:
         h = C.c_void_p()
         L.check(self._lib.adsb_create(C.byref(cfg), C.byref(h)), "adsb_create")
         self._h = h
+        self.device = device
         self.sample_type = sample_type
         self.max_out = max_out
         self.max_channels = max_channels
@@ -282,6 +319,44 @@ class AdsbDemod:
         n = C.c_size_t()
         L.check(self._lib.adsb_fetch_fields(self._h, out.ctypes.data, cap, C.byref(n)), "adsb_fetch_fields")
         return out[:n.value].copy()
+
+    def levels_async(self):
+        """adsb_levels_device_async alone: enqueues the last launch's per-frame power statistics and returns."""
+        L.check(self._lib.adsb_levels_device_async(self._h), "adsb_levels_device_async")
+
+    def levels(self, max_out=None):
+        """Per-frame signal and noise power of the last launch's frames, on the device -> LEVEL_DTYPE array in frame
+        order.  Enqueues the kernel first unless levels_async() already did for this launch."""
+        cap = self.max_out if max_out is None else max_out
+        out = np.zeros(max(cap, 1), dtype=LEVEL_DTYPE)
+        n = C.c_size_t()
+        ptr = out.ctypes.data_as(C.POINTER(L.AdsbFrameLevel))
+        rc = self._lib.adsb_fetch_levels(self._h, ptr, cap, C.byref(n))
+        if rc == L.ADSB_E_STATE:               # not enqueued for this launch yet
+            self.levels_async()
+            rc = self._lib.adsb_fetch_levels(self._h, ptr, cap, C.byref(n))
+        L.check(rc, "adsb_fetch_levels")
+        return out[:n.value].copy()
+
+    def levels_device(self):
+        """Device address of the records levels_async() fills; valid on the ctx stream, no synchronisation."""
+        dev = C.c_void_p()
+        L.check(self._lib.adsb_levels_device(self._h, C.byref(dev)), "adsb_levels_device")
+        return dev.value
+
+    def levels_of(self, dev_ptr, n_samples, frames, first_sample=0):
+        """adsb_levels_of: LEVEL_DTYPE records of any frame list against n_samples samples of the ctx's sample type at
+        dev_ptr (one channel, device memory) whose sample 0 is stream sample first_sample.  frames: a FRAME_DTYPE array
+        (host), or (device pointer, count).  Blocking; the last launch's levels stay as they are."""
+        if isinstance(frames, tuple):
+            ptr, n = int(frames[0]), int(frames[1])
+        else:
+            frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+            ptr, n = (frames.ctypes.data if len(frames) else None), len(frames)
+        out = np.zeros(max(n, 1), dtype=LEVEL_DTYPE)
+        L.check(self._lib.adsb_levels_of(self._h, dev_ptr, int(n_samples), int(first_sample), ptr, n,
+                                         out.ctypes.data_as(C.POINTER(L.AdsbFrameLevel))), "adsb_levels_of")
+        return out[:n].copy()
 
     def set_result_target(self, dev_ptr, nbytes):
         """Next launches write [32-byte header | frames] straight into caller-owned HBM (None: reset)."""

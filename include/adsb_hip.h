@@ -228,6 +228,49 @@ int adsb_fetch_fields(adsb_ctx *ctx, adsb_packet_fields *out, size_t max_out, si
 int adsb_fields_device(adsb_ctx *ctx, const adsb_packet_fields **fields_dev);
 
 /*
+ * Per-frame signal and noise power.  The reference's gate is declared to return "high value, signal power, noise
+ * power" (src/adsb/demod.rs:16-17), returns zeros for the two powers (demod.rs:56) and thread 2 drops them
+ * (src/adsb.rs:103).  Here: exact integer statistics of the 240 samples a frame was decoded from, one 32-byte record
+ * per frame, in frame order.  Sample power is p = I^2 + Q^2 on the stored integers (i8: at most 32768; i16: at most
+ * 2^31, from (-32768, -32768)).  With w = offset - first_sample_index the frame's position in its buffer and bit b
+ * (0..111) of bytes[] AS RETURNED (MSB first, after any repair), the 116 PULSE samples are w+0, w+2, w+7, w+9
+ * (demod.rs:20-24) and, per bit, w+16+2b if the bit is 1, else w+16+2b+1; the other 124 are the QUIET samples.
+ */
+#define ADSB_LEVEL_VALID 0x1u
+typedef struct adsb_frame_level {   /* 32 bytes */
+    uint64_t signal_sum;   /* sum of p over the 116 pulse samples                         */
+    uint64_t noise_sum;    /* sum of p over the 124 quiet samples                         */
+    uint32_t peak;         /* max p over all 240                                          */
+    uint32_t pulse_min;    /* min p over the pulse samples                                */
+    uint32_t quiet_max;    /* max p over the quiet samples                                */
+    uint16_t weak_bits;    /* bits whose pulse-sample p < 2 x their quiet-sample p (u64)  */
+    uint16_t flags;        /* ADSB_LEVEL_VALID; 0: window not inside the buffer, rest 0   */
+} adsb_frame_level;
+/* Enqueues the levels of the last launch's list behind its ordering pass (like adsb_decode_fields_device_async; the
+ * count is read on the device, the host does not wait).  Reads the launch's input again: the buffer handed to
+ * adsb_demod_device_async (every channel; adsb_set_stream_base and adsb_set_result_target are honoured) or
+ * adsb_demod's copy of it must still be intact, which it is until the next call that launches.  Needs cfg.max_out
+ * records of ctx memory, allocated on first use; a ctx that never calls it allocates nothing and launches exactly
+ * the kernels it launched before.  ADSB_E_STATE before any launch.
+ * NOT for feeds: while a feed is open the older launch's input may already be overwritten (two buffers in flight
+ * over two staging slots), and the one-dispatch path is one dispatch on purpose.  A feed's consumer holds the host
+ * buffer: adsb_host_frame_levels (adsb_host.h) gives the same records from it. */
+int adsb_levels_device_async(adsb_ctx *ctx);
+/* Waits and copies min(frames of the list, max_out) records; *n_out = how many.  If the wait found the list rebuilt
+ * (ADSB_FLAG_INCOMPLETE, slot-pool overflow), the levels are computed again for the rebuilt list first.
+ * ADSB_E_STATE if no levels were enqueued for the last launch. */
+int adsb_fetch_levels(adsb_ctx *ctx, adsb_frame_level *out, size_t max_out, size_t *n_out);
+/* Device pointer to the records (valid until the next levels call on this ctx); does not synchronise. */
+int adsb_levels_device(adsb_ctx *ctx, const adsb_frame_level **levels_dev);
+/* Any frame list against any ONE-channel device buffer of the ctx's sample type (iq_dev aligned to one sample):
+ * frame i sits at sample frames[i].offset - first_sample_index.  `frames` is host memory or device memory of the
+ * ctx's device, `out` host memory of n records; blocking.  A frame whose 240-sample window is not wholly inside
+ * [0, n_samples) -- offset < first_sample_index included -- gets flags = 0 and zeros, and nothing of it is read.
+ * Uses scratch of its own: the last launch's levels stay as they are.  ADSB_E_CAPACITY for n >= 2^32. */
+int adsb_levels_of(adsb_ctx *ctx, const void *iq_dev, size_t n_samples, uint64_t first_sample_index,
+                   const adsb_frame *frames, size_t n, adsb_frame_level *out);
+
+/*
  * Tracker + global CPR position decode on the device: what the reference's display
  * threads do with every AdsbPacket, `handle_aircraft_update` (src/adsb/aircraft.rs:158-165 ->
  * Aircraft::handle_packet, aircraft.rs:48-111 -> cpr::calculate_geographic_position, cpr.rs:135-147),

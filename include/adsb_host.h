@@ -98,6 +98,20 @@ int adsb_replay_file(adsb_ctx *ctx, const char *path, int file_format, size_t ch
                      adsb_frame *frames, size_t max_frames, size_t *n_frames, uint64_t *n_buffers,
                      uint64_t *n_samples, char *text, size_t text_cap, size_t *text_len);
 
+/*
+ * CPU mirror of adsb_levels_of (adsb_hip.h, "Per-frame signal and noise power"): the same records, in plain C++,
+ * from a one-channel HOST buffer of n_samples interleaved samples of sample_type.  Frame i sits at sample
+ * frames[i].offset - first_sample_index; a frame whose 240-sample window is not wholly inside [0, n_samples) gets
+ * flags = 0 and zeros, and nothing of it is read.  What a feed's consumer, who holds the host buffer, uses.
+ * ADSB_E_ARG for a bad sample_type, NULL iq, or NULL frames / out with n > 0.
+ */
+int adsb_host_frame_levels(int sample_type, const void *iq, size_t n_samples, uint64_t first_sample_index,
+                           const adsb_frame *frames, size_t n, adsb_frame_level *out);
+/* 10 log10(sum / n_samples / FS) with FS = 32768 (ADSB_SAMPLE_I8) or 2^31 (ADSB_SAMPLE_I16): the mean power of
+ * n_samples samples whose p add up to `sum`, in dB below a full-scale sample.  -INFINITY for sum == 0; NaN for a bad
+ * sample_type or n_samples == 0.  adsb_level_dbfs(st, level.signal_sum, 116) and (st, level.noise_sum, 124). */
+double adsb_level_dbfs(int sample_type, uint64_t sum, uint32_t n_samples);
+
 /* ---- behind the channel: tracker + CPR ------------------------------------------- */
 
 /* cpr.rs:39-54 calc_num_zones; cpr.rs:135-147 calculate_geographic_position (returns 1 = Some, 0 = None).

@@ -7,6 +7,7 @@
   tools/replay.py capture.c16 --carry --tail  # also decode frames straddling buffers and the last chunk
   tools/replay.py capture.c16 --aircraft      # the final aircraft table instead (tui.rs:65-95, Velocity filled)
   tools/replay.py capture.c16 --web           # what the web thread broadcasts instead: one JSON line per packet
+  tools/replay.py capture.c16 --levels        # signal and noise power of every packet instead, tab-separated
 
 Everything below the argument parsing is one call through the C ABI (adsb_replay_file, include/adsb_host.h).
 The "Processed Time" line carries no value (the reference prints the wall clock there).  With --aircraft, the frames
@@ -16,7 +17,10 @@ With --web, the frames go through one device track table with a summaries reserv
 frame's summary is printed as one JSON line: the reference's serialisation of AircraftSummary (aircraft.rs:14-23,
 cpr.rs:10-16, camelCase), which its web thread sends for every packet (web.rs:117-128).  lastContact is whole seconds
 of frame time (0 when the aircraft has had no position message): the reference stamps the wall clock there.  Floats
-are printed with Python's shortest round-trip repr.  The TEXT has not been compared with a Rust build's (there is no
+are printed with Python's shortest round-trip repr.  With --levels, one line per packet: offset, ICAO (hex), signal
+dBFS, noise dBFS, their difference, weak bits -- the mean power of the packet's 116 pulse samples and of its 124 quiet
+samples against a full-scale sample, one decimal, "-inf" for a sum of zero; computed on the device over the capture in
+device memory (adsb_levels_of), in overlapping pieces if the capture is large.  The TEXT has not been compared with a Rust build's (there is no
 Rust toolchain); only the values are checked, against the oracle."""
 import argparse
 import json
@@ -84,6 +88,40 @@ def web_stream(d, frames, chunk):
     return "".join(line + "\n" for line in lines)
 
 
+LEVELS_PIECE = 1 << 26  # samples of the capture in device memory at a time (--levels)
+
+
+def read_capture(path, fmt):
+    """The capture as the library reads it: (n, 2) int16 for .c16, int8 (x - 128) for raw rtl_sdr bytes."""
+    import numpy as np
+    if fmt == "c16":
+        return np.fromfile(path, dtype="<i2").reshape(-1, 2)
+    return (np.fromfile(path, dtype=np.uint8) ^ 0x80).view(np.int8).reshape(-1, 2)
+
+
+def level_lines(d, st, frames, iq, piece=LEVELS_PIECE):
+    """One tab-separated line per frame: offset, ICAO, signal dBFS, noise dBFS, signal - noise, weak bits.  The
+    capture goes to device memory piece by piece; neighbouring pieces overlap by 239 samples, so every frame's 240
+    samples lie in the piece that owns its offset."""
+    import numpy as np
+    import torch
+    lines, step = [], piece - (A.WINDOW - 1)
+    offsets = frames["offset"].astype(np.int64)
+    for start in range(0, max(len(iq) - (A.WINDOW - 1), 1), step):
+        mine = frames[(offsets >= start) & (offsets < start + step)]
+        if not len(mine):
+            continue
+        part = torch.from_numpy(np.ascontiguousarray(iq[start:start + piece])).to(f"cuda:{d.device}")
+        levels = d.levels_of(part.data_ptr(), part.shape[0], mine, first_sample=start)
+        del part
+        for f, lv in zip(mine, levels):
+            sig = A.level_dbfs(st, lv["signal_sum"], A.LEVEL_PULSE_SAMPLES)
+            noise = A.level_dbfs(st, lv["noise_sum"], A.LEVEL_QUIET_SAMPLES)
+            icao = int(f["bytes"][1]) << 16 | int(f["bytes"][2]) << 8 | int(f["bytes"][3])
+            lines.append(f"{int(f['offset'])}\t{icao:x}\t{sig:.1f}\t{noise:.1f}\t{sig - noise:.1f}\t{int(lv['weak_bits'])}")
+    return "".join(line + "\n" for line in lines)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("file")
@@ -95,6 +133,7 @@ def main():
     ap.add_argument("--summary", action="store_true", help="print counts to stderr")
     ap.add_argument("--aircraft", action="store_true", help="print the final aircraft table instead of the stream text")
     ap.add_argument("--web", action="store_true", help="print one AircraftSummary JSON line per packet instead")
+    ap.add_argument("--levels", action="store_true", help="print signal and noise power of every packet instead")
     a = ap.parse_args()
     fmt = a.format or ("c16" if a.file.endswith(".c16") else "u8")
     st = A.ADSB_SAMPLE_I16 if fmt == "c16" else A.ADSB_SAMPLE_I8
@@ -108,6 +147,8 @@ def main():
             text = aircraft_table(d, frames, n_samp)
         elif a.web:
             text = web_stream(d, frames, a.chunk)
+        elif a.levels:
+            text = level_lines(d, st, frames, read_capture(a.file, fmt))
     sys.stdout.write(text)
     if a.summary:
         print(f"{n_samp} samples, {n_buf} buffers of {a.chunk}, {len(frames)} packets", file=sys.stderr)
