@@ -7,7 +7,7 @@ from ._lib import (ADSB_LEVEL_VALID, ADSB_FUSED_NONE, ADSB_TRACK_FUSED_TRUNCATED
                    ADSB_VELOCITY_DIRECTION, ADSB_VELOCITY_SPEED, ADSB_VELOCITY_VRATE,
                    ADSB_E_NODEVICE, ADSB_E_SHORT, ADSB_E_STATE,
                    ADSB_FLAG_INCOMPLETE, ADSB_FLAG_TRUNCATED, ADSB_OK, ADSB_SAMPLE_I8, ADSB_SAMPLE_I16, AdsbError, load)
-from .demod import (AIRCRAFT_DTYPE, FIELDS_DTYPE, FRAME_DTYPE, FUSED_DTYPE, LEVEL_DTYPE, LEVEL_PULSE_SAMPLES, LEVEL_QUIET_SAMPLES,
+from .demod import (AIRCRAFT_DTYPE, AIRCRAFT_LEVEL_DTYPE, FUSED_LEVEL_DTYPE, FIELDS_DTYPE, FRAME_DTYPE, FUSED_DTYPE, LEVEL_DTYPE, LEVEL_PULSE_SAMPLES, LEVEL_QUIET_SAMPLES,
                     host_frame_levels, level_dbfs, TRACK_POINT_DTYPE, VELOCITY_DTYPE, WINDOW, AdsbDemod, AdsbGroup, Feed, Tracker,
                     TrackBank, TrackTable,
                     group_plan,
@@ -19,7 +19,7 @@ __all__ = [
     "ADSB_FLAG_INCOMPLETE", "ADSB_FLAG_TRUNCATED", "ADSB_SAMPLE_I8", "ADSB_SAMPLE_I16", "AdsbError", "load", "FRAME_DTYPE",
     "FIELDS_DTYPE", "TRACK_POINT_DTYPE", "AIRCRAFT_DTYPE", "ADSB_TRACK_NEW_POSITION", "Tracker",
     "ADSB_TRACK_UNTRACKED", "ADSB_TRACK_TABLE_FULL", "TrackTable", "TrackBank", "cpr_position",
-    "FUSED_DTYPE", "ADSB_FUSED_NONE", "ADSB_TRACK_FUSED_TRUNCATED",
+    "FUSED_DTYPE", "ADSB_FUSED_NONE", "ADSB_TRACK_FUSED_TRUNCATED", "AIRCRAFT_LEVEL_DTYPE", "FUSED_LEVEL_DTYPE",
     "VELOCITY_DTYPE", "ADSB_VELOCITY_SPEED", "ADSB_VELOCITY_DIRECTION", "ADSB_VELOCITY_VRATE",
     "WINDOW", "AdsbDemod", "AdsbGroup", "group_plan", "Feed", "packet_display", "packet_new", "packet_new_from_string",
     "LEVEL_DTYPE", "ADSB_LEVEL_VALID", "LEVEL_PULSE_SAMPLES", "LEVEL_QUIET_SAMPLES", "host_frame_levels", "level_dbfs",

@@ -128,6 +128,22 @@ class AdsbFusedAircraft(C.Structure):
                 ("callsign", C.c_char * 8), ("velocity", AdsbVelocity), ("reserved", C.c_uint64 * 2)]
 
 
+class AdsbAircraftLevel(C.Structure):
+    """adsb_aircraft_level: an aircraft's signal level beside its record (tables and banks with a levels reserve)."""
+    _fields_ = [("signal_total", C.c_uint64), ("noise_total", C.c_uint64), ("last_signal_sum", C.c_uint64),
+                ("last_noise_sum", C.c_uint64), ("max_signal_sum", C.c_uint64), ("last_time", C.c_double),
+                ("n_levels", C.c_uint32), ("peak", C.c_uint32), ("weak_bits_total", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class AdsbFusedLevel(C.Structure):
+    """adsb_fused_level: one per fused record, same order; `strongest` stands for the header's ten fields
+    strongest_signal_total .. strongest_reserved, which are an adsb_aircraft_level bit for bit."""
+    _fields_ = [("strongest", AdsbAircraftLevel), ("signal_total", C.c_uint64), ("noise_total", C.c_uint64),
+                ("n_levels", C.c_uint64), ("strongest_receiver", C.c_uint16), ("level_receivers", C.c_uint16),
+                ("reserved", C.c_uint32)]
+
+
 class AdsbTrackBankCfg(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("n_receivers", C.c_uint32), ("max_aircraft", C.c_uint32),
                 ("reserved", C.c_uint32), ("max_frames", C.c_uint64), ("seconds_per_sample", C.c_double)]
@@ -201,6 +217,17 @@ PROTOTYPES = {
     "adsb_track_bank_summaries_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "adsb_track_bank_fetch_changed": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_double), _P(AdsbVelocity), C.c_size_t,
                                                 _P(C.c_size_t), _P(C.c_uint64)]),
+    "adsb_track_table_levels_reserve": (C.c_int, [C.c_void_p]),
+    "adsb_track_table_update_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]),
+    "adsb_track_table_fetch_levels": (C.c_int, [C.c_void_p, _P(AdsbAircraftLevel), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_levels_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "adsb_track_bank_levels_reserve": (C.c_int, [C.c_void_p]),
+    "adsb_track_bank_levels_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "adsb_track_bank_update_levels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_uint64),
+                                                _P(C.c_uint64)]),
+    "adsb_track_bank_update_launch_levels": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "adsb_track_bank_fetch_levels": (C.c_int, [C.c_void_p, _P(AdsbAircraftLevel), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_bank_fetch_fused_levels": (C.c_int, [C.c_void_p, _P(AdsbFusedLevel), C.c_size_t, _P(C.c_size_t)]),
     "adsb_cpr_num_zones": (C.c_uint32, [C.c_double]),
     "adsb_cpr_position": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P(C.c_double),
                                     _P(C.c_double)]),

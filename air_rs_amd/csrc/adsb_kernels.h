@@ -212,6 +212,8 @@ struct TrackStoreDev {
     uint32_t *size_next;         // [n_receivers] staging: the admission kernel's new sizes, moved to size by the pairs
                                  // kernel; expire stages the old sizes here
     uint32_t *slot;              // [n] scratch: record slot + 1 of each sorted frame's aircraft (kTrackUntracked)
+    adsb_aircraft_level *lvl;    // [n_receivers x max_aircraft] beside rec, or null: no levels reserve (then admission
+                                 // and expire touch nothing more than they did)
     // table only
     uint32_t *index;             // [1 << 24]: ICAO -> record slot + 1, 0 = absent
     // bank only
@@ -243,6 +245,23 @@ struct TrackSumDev {
     void *temp;                  // the scan's scratch
     size_t temp_bytes;
 };
+// Per-aircraft signal levels of a table / bank update (adsb_track_*_levels_reserve): all of it allocated by the reserve.
+// One segmented inclusive scan over the sorted list sums, per aircraft, what its COUNTED frames carry (tracked, and the
+// frame's level record valid); every component combines by saturating add, max, or "the later sorted position", so the
+// result does not depend on how rocPRIM groups the operands.  newest = sorted position + 1 of the last counted frame,
+// 0 = none: last_* are read from that frame by the tail kernel, not carried.
+struct TrackLvlTuple {
+    uint64_t signal, noise, max_signal;
+    uint32_t n, peak, weak, newest;
+    uint32_t head;               // the operand holds a segment head
+    uint32_t pad;
+};
+static_assert(sizeof(TrackLvlTuple) == 48, "TrackLvlTuple: the header's memory figures assume 48 bytes");
+struct TrackLvlDev {
+    TrackLvlTuple *scan;         // [max_frames]: the scan's output, sorted order
+    void *temp;                  // the scan's scratch
+    size_t temp_bytes;
+};
 struct TrackArgs {
     const adsb_frame *frames;
     const adsb_packet_fields *fields;
@@ -261,6 +280,8 @@ struct TrackArgs {
                                  // kBank: the list holds several receivers' frames (adsb_track_bank_update)
     const TrackStoreDev *store;  // the table / bank (kLaunch: unused)
     const TrackSumDev *sum;      // non-null (table / bank only): also the per-frame summaries and the changed list
+    const adsb_frame_level *levels; // [n] (device), list order: with lvl non-null (and store->lvl), merged into the
+    const TrackLvlDev *lvl;      // per-aircraft level records; null: the level records stay as they are
 };
 // expire (adsb_track_table_expire / adsb_track_bank_expire): a record survives unless last_heard < before[receiver]
 constexpr uint32_t kMaxReceivers = 256;
@@ -281,6 +302,9 @@ size_t track_sort_temp_bytes(size_t n);
 size_t track_bank_temp_bytes(size_t n); // the bank's sort (32 bits) and 64-bit scan
 hipError_t launch_track(hipStream_t s, const TrackArgs &a);
 size_t track_summaries_temp_bytes(size_t n);
+size_t track_levels_temp_bytes(size_t n);
+// every level record of [0, places) empty: zeros, last_time NaN (the levels reserve)
+hipError_t launch_track_levels_clear(hipStream_t s, adsb_aircraft_level *lvl, size_t places);
 // out[k] = rec[sum.changed[k]] for k < min(*sum.n_changed, max_n): the changed list's records, gathered on the device
 hipError_t launch_track_changed(hipStream_t s, const TrackRecord *rec, const TrackSumDev &sum, uint32_t max_n,
                                 TrackRecord *out);
@@ -291,6 +315,11 @@ static_assert(sizeof(adsb_fused_aircraft) == 128 && offsetof(adsb_fused_aircraft
                   offsetof(adsb_fused_aircraft, reserved) == 80 + sizeof(adsb_velocity) &&
                   offsetof(adsb_fused_aircraft, velocity_reserved) == 80 + offsetof(adsb_velocity, reserved),
               "adsb_fused_aircraft: one cache line, an adsb_velocity bit for bit at offset 80");
+static_assert(sizeof(adsb_aircraft_level) == 64 && sizeof(adsb_fused_level) == 96 &&
+                  offsetof(adsb_fused_level, strongest_last_time) == offsetof(adsb_aircraft_level, last_time) &&
+                  offsetof(adsb_fused_level, strongest_reserved) == offsetof(adsb_aircraft_level, reserved) &&
+                  offsetof(adsb_fused_level, signal_total) == 64,
+              "adsb_fused_level: an adsb_aircraft_level bit for bit at offset 0, then the sums");
 constexpr uint32_t kFuseWideReceivers = 128; // above this, ICAO << 8 | receiver plus the 'no record' bit needs 33 bits
 struct FuseArgs {
     const TrackStoreDev *bank;
@@ -300,6 +329,7 @@ struct FuseArgs {
     uint32_t *vals, *svals;      // [places] each: the record's place; vals is reused as the scan's output
     uint32_t *seg_start;         // [max_fused]: where each ICAO's run starts in sorted order
     adsb_fused_aircraft *out;    // [max_fused]
+    adsb_fused_level *lvl_out;   // [max_fused], or null: no fused levels (then bank->lvl is not read)
     uint64_t *counts;            // device words: [0] records written, [1] distinct ICAOs, [2] ADSB_TRACK_FUSED_TRUNCATED
     uint64_t max_fused;          // 1 .. places
     void *temp;

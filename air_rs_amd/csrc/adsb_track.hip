@@ -72,6 +72,15 @@
 // segment's rank among the tracked ones; one thread per frame then builds the 48-byte summary from at most three source
 // frames and the pre-update record, with 3.'s expressions, and stores it at the frame's list index; segment tails
 // write their record slot at their rank (the changed list).  Linear in the list however long one aircraft's part is.
+//
+// Per-aircraft signal levels (adsb_track_*_levels_reserve; the *_update_levels forms): a side array of one 64-byte
+// adsb_aircraft_level per record place.  After 2. (which fixes a bank's d.slot), independent of 3.: one segmented
+// inclusive scan over the sorted list (rocPRIM, a 48-byte tuple computed by a transform iterator from the frame's level
+// record) adds up every segment's counted frames by saturating add / max / "later sorted position"; one thread per
+// segment tail merges the result into the side record at slot - 1 and reads last_* from the newest counted frame.
+// Admission empties the level record of a place it admits, expire's compaction moves it with the record; both only when
+// the side array exists.  The fused view gets one adsb_fused_level per fused record from a kernel of its own after the
+// reduction: one thread per ICAO run picks the receiver with the greatest mean by exact cross-multiplication.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -176,6 +185,25 @@ __device__ __forceinline__ TrackRecord empty_record(uint32_t icao)
     return rec;
 }
 
+__device__ __forceinline__ adsb_aircraft_level empty_level()
+{
+    adsb_aircraft_level l{};
+    l.last_time = __builtin_nan("");
+    return l;
+}
+
+__device__ __forceinline__ uint64_t sat_add64(uint64_t a, uint64_t b)
+{
+    const uint64_t c = a + b;
+    return c < a ? ~0ull : c;
+}
+
+__device__ __forceinline__ uint32_t sat_add32(uint32_t a, uint32_t b)
+{
+    const uint32_t c = a + b;
+    return c < a ? ~0u : c;
+}
+
 // ME bits [first, first + width) of the 56-bit ME field (bit 0 = the top bit of frame byte 4)
 __device__ __forceinline__ uint32_t me_bits(uint64_t me, int first, int width)
 {
@@ -271,6 +299,7 @@ __global__ __launch_bounds__(256) void track_admit_kernel(const uint32_t *skeys,
     const uint32_t icao = skeys[s];
     t.index[icao] = (uint32_t)r + 1u;
     t.rec[r] = empty_record(icao);
+    if (t.lvl) t.lvl[r] = empty_level();
 }
 
 // bank only: the receiver split clipped to the list (prefix[0] = 0, prefix[k] = n for k >= n_src), as adsb_fetch's
@@ -370,6 +399,7 @@ __global__ __launch_bounds__(256) void track_bank_admit_kernel(const uint32_t *s
     for (uint64_t h = bank_hash(key) & b.hash_mask;; h = (h + 1) & b.hash_mask)
         if (atomicCAS(&b.hash[h], 0ull, entry) == 0ull) break;
     b.rec[a] = empty_record(key & 0xFFFFFFu);
+    if (b.lvl) b.lvl[a] = empty_level();
     b.seg_slot[g] = a + 1u;
 }
 
@@ -658,6 +688,105 @@ hipError_t launch_frame_summaries(hipStream_t st, const TrackArgs &a, const Trac
     return hipSuccess;
 }
 
+// ---- per-aircraft signal levels (table / bank with a levels reserve) -----------------------------------------------
+// The scan's input at sorted position s, computed where the scan loads it: the frame's level record if the frame is
+// counted (its aircraft tracked, the record valid), else nothing but the head mark.
+struct LvlInput {
+    const uint32_t *skeys, *svals, *slot;
+    const adsb_frame_level *levels;
+    __device__ __forceinline__ TrackLvlTuple operator()(uint32_t s) const
+    {
+        TrackLvlTuple v{};
+        v.head = (s == 0 || skeys[s - 1] != skeys[s]) ? 1u : 0u;
+        if (slot[s] != kTrackUntracked) {
+            const adsb_frame_level l = levels[svals[s]];
+            if (l.flags & ADSB_LEVEL_VALID) {
+                v.signal = v.max_signal = l.signal_sum;
+                v.noise = l.noise_sum;
+                v.n = 1;
+                v.peak = l.peak;
+                v.weak = l.weak_bits;
+                v.newest = s + 1u;
+            }
+        }
+        return v;
+    }
+};
+
+// Segmented: a right operand that holds a segment head starts over; otherwise saturating sums, maxima, and the later
+// counted position (positions ascend, so the later one is the greater one).  Associative.
+struct LvlOp {
+    __device__ __forceinline__ TrackLvlTuple operator()(const TrackLvlTuple &l, const TrackLvlTuple &r) const
+    {
+        TrackLvlTuple o = r;
+        if (!r.head) {
+            o.head = l.head;
+            o.signal = sat_add64(l.signal, r.signal);
+            o.noise = sat_add64(l.noise, r.noise);
+            o.max_signal = l.max_signal > r.max_signal ? l.max_signal : r.max_signal;
+            o.n = sat_add32(l.n, r.n);
+            o.peak = l.peak > r.peak ? l.peak : r.peak;
+            o.weak = sat_add32(l.weak, r.weak);
+            o.newest = l.newest > r.newest ? l.newest : r.newest;
+        }
+        return o;
+    }
+};
+
+// One thread per segment tail with a counted frame: this update's part merged into the aircraft's level record
+template <TrackKind K>
+__global__ __launch_bounds__(256) void track_levels_merge_kernel(const adsb_frame *frames,
+                                                                 const adsb_frame_level *levels, const uint32_t *skeys,
+                                                                 const uint32_t *svals, uint32_t n,
+                                                                 double seconds_per_sample, uint64_t sample_base,
+                                                                 TrackStoreDev d, const TrackLvlTuple *scan)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s];
+    if (s + 1 != n && skeys[s + 1] == key) return;
+    const uint32_t slot = d.slot[s];
+    if (slot == kTrackUntracked) return;
+    const TrackLvlTuple w = scan[s];
+    if (!w.newest) return; // no counted frame: the record stays
+    if (K == TrackKind::kBank) sample_base = d.sample_base[key >> 24];
+    const uint32_t j = svals[w.newest - 1];
+    const adsb_frame_level last = levels[j];
+    adsb_aircraft_level a = d.lvl[slot - 1];
+    a.signal_total = sat_add64(a.signal_total, w.signal);
+    a.noise_total = sat_add64(a.noise_total, w.noise);
+    a.last_signal_sum = last.signal_sum;
+    a.last_noise_sum = last.noise_sum;
+    a.max_signal_sum = a.max_signal_sum > w.max_signal ? a.max_signal_sum : w.max_signal;
+    a.last_time = frame_time(frames, j, sample_base, seconds_per_sample);
+    a.n_levels = sat_add32(a.n_levels, w.n);
+    a.peak = a.peak > w.peak ? a.peak : w.peak;
+    a.weak_bits_total = sat_add32(a.weak_bits_total, w.weak);
+    a.reserved = 0;
+    d.lvl[slot - 1] = a;
+}
+
+template <TrackKind K>
+hipError_t launch_levels_merge(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d)
+{
+    const TrackLvlDev &lv = *a.lvl;
+    const auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u),
+                                                     LvlInput{a.skeys, a.svals, d.slot, a.levels});
+    size_t tb = lv.temp_bytes;
+    hipError_t e = rocprim::inclusive_scan(lv.temp, tb, in, lv.scan, (size_t)a.n, LvlOp(), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(track_levels_merge_kernel<K>, dim3((a.n + 255) / 256), dim3(256), 0, st, a.frames, a.levels,
+                       (const uint32_t *)a.skeys, (const uint32_t *)a.svals, a.n, a.seconds_per_sample, a.sample_base, d,
+                       (const TrackLvlTuple *)lv.scan);
+    return hipSuccess;
+}
+
+__global__ __launch_bounds__(256) void track_levels_clear_kernel(adsb_aircraft_level *lvl, uint64_t places)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < places) lvl[p] = empty_level();
+}
+
 // expire, 1: keep[g] = 1 for a record in use whose last frame is not older than the cut (last_heard < before evicts).
 // Record g is slot i of receiver r (a table: r = 0).  Slot 0 stages the old size where the compaction kernel reads it
 // (size_next[r]), since that kernel writes the new one; the pairs kernel of an update has consumed its own staging before
@@ -709,6 +838,7 @@ __global__ __launch_bounds__(256) void track_expire_compact_kernel(TrackStoreDev
     }
     const TrackRecord moved = d.rec[base + lo];
     d.rec[g] = moved;
+    if (d.lvl) d.lvl[g] = d.lvl[base + lo];
     if (!kBank) d.index[moved.a.icao] = i + 1u;
 }
 
@@ -888,6 +1018,54 @@ __global__ __launch_bounds__(256) void fuse_reduce_kernel(const TrackRecord *rec
     for (uint32_t i = threadIdx.x; i < pieces; i += 256) dst[i] = src[i];
 }
 
+// fuse, 5 (banks with a levels reserve): one thread per written fused record walks its ICAO run (receivers ascending)
+// over the level records beside the bank's records.  a is stronger than b iff a.signal_total x b.n_levels >
+// b.signal_total x a.n_levels, as 96-bit products (high and low word of a 64 x 64 multiply); only a strictly greater
+// mean replaces the best so far, so ties stay with the lowest receiver.
+template <class K>
+__global__ __launch_bounds__(256) void fuse_levels_kernel(const adsb_aircraft_level *lvl, const K *skeys,
+                                                          const uint32_t *svals, const uint32_t *seg_start,
+                                                          const uint64_t *counts, uint32_t rbits, uint64_t places,
+                                                          adsb_fused_level *out)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= counts[0]) return;
+    const uint32_t start = seg_start[g], rmask = (1u << rbits) - 1u;
+    const uint32_t icao = (uint32_t)(skeys[start] >> rbits);
+    adsb_fused_level f{};
+    adsb_aircraft_level strongest = empty_level(); // f's first 64 bytes
+    f.strongest_receiver = ADSB_FUSED_NONE;
+    uint64_t best_total = 0, best_n = 0, best_w = 0; // the strongest so far: its totals and sorted position; n 0 = none
+    uint32_t heard = 0;
+    for (uint64_t w = start; w < places && (uint32_t)(skeys[w] >> rbits) == icao; ++w) {
+        const adsb_aircraft_level &a = lvl[svals[w]];
+        const uint64_t total = a.signal_total, n = a.n_levels;
+        f.signal_total = sat_add64(f.signal_total, total);
+        f.noise_total = sat_add64(f.noise_total, a.noise_total);
+        f.n_levels += n;
+        if (n == 0) continue;
+        ++heard;
+        bool better = best_n == 0;
+        if (!better) { // total x best_n against best_total x n
+            const uint64_t new_lo = total * best_n, new_hi = __umul64hi(total, best_n);
+            const uint64_t old_lo = best_total * n, old_hi = __umul64hi(best_total, n);
+            better = new_hi > old_hi || (new_hi == old_hi && new_lo > old_lo);
+        }
+        if (better) {
+            best_total = total;
+            best_n = n;
+            best_w = w;
+        }
+    }
+    if (best_n) { // the record whole, from memory, once
+        strongest = lvl[svals[best_w]];
+        f.strongest_receiver = (uint16_t)((uint32_t)skeys[best_w] & rmask);
+    }
+    __builtin_memcpy(&f, &strongest, sizeof(strongest));
+    f.level_receivers = (uint16_t)heard;
+    out[g] = f;
+}
+
 template <class K>
 hipError_t fuse_sort_scan(void *temp, size_t &sort_bytes, size_t &scan_bytes, const K *keys, K *skeys,
                           const uint32_t *vals, uint32_t *svals, uint32_t *excl, size_t places, uint32_t rbits,
@@ -926,6 +1104,10 @@ hipError_t launch_fuse(hipStream_t st, const FuseArgs &a)
     default: return hipErrorInvalidValue;
     }
 #undef ADSB_FUSE_REDUCE
+    if (a.lvl_out) // workgroups past counts[0] leave at once
+        hipLaunchKernelGGL(fuse_levels_kernel<K>, dim3((uint32_t)((a.max_fused + 255) / 256)), dim3(256), 0, st,
+                           (const adsb_aircraft_level *)b.lvl, (const K *)skeys, (const uint32_t *)a.svals,
+                           (const uint32_t *)a.seg_start, (const uint64_t *)a.counts, rbits, places, a.lvl_out);
     return hipGetLastError();
 }
 
@@ -1016,6 +1198,22 @@ size_t track_summaries_temp_bytes(size_t n)
     return scan_bytes + 256;
 }
 
+size_t track_levels_temp_bytes(size_t n)
+{
+    size_t scan_bytes = 0;
+    (void)rocprim::inclusive_scan(nullptr, scan_bytes, (const TrackLvlTuple *)nullptr, (TrackLvlTuple *)nullptr, n,
+                                  LvlOp(), (hipStream_t)0);
+    return scan_bytes + 256;
+}
+
+hipError_t launch_track_levels_clear(hipStream_t st, adsb_aircraft_level *lvl, size_t places)
+{
+    if (places == 0) return hipSuccess;
+    hipLaunchKernelGGL(track_levels_clear_kernel, dim3((uint32_t)((places + 255) / 256)), dim3(256), 0, st, lvl,
+                       (uint64_t)places);
+    return hipGetLastError();
+}
+
 hipError_t launch_track_changed(hipStream_t st, const TrackRecord *rec, const TrackSumDev &sum, uint32_t max_n,
                                 TrackRecord *out)
 {
@@ -1039,6 +1237,8 @@ hipError_t track_tail(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d
                        a.seconds_per_sample, a.sample_base, d, a.points, tail_flag);
     hipError_t e = hipSuccess;
     if constexpr (kStore) {
+        if (a.lvl && d.lvl) e = launch_levels_merge<K>(st, a, d); // needs d.slot only: independent of the record merge
+        if (e != hipSuccess) return e;
         if (a.sum) e = launch_frame_summaries<K>(st, a, d); // before the merge
     } else {
         size_t tb = a.temp_bytes;

@@ -123,6 +123,10 @@ struct TrackStore {
     uint32_t n_points = 0;
     bool updated = false;
     TrackSummaries sum;
+    // per-aircraft levels (adsb_track_*_levels_reserve): all of it allocated by the reserve; dev.lvl null = no reserve
+    adsbk::TrackLvlDev lvl{};
+    adsb_frame_level *lvl_frames = nullptr; // [max_frames]: device copy of a host levels array
+    adsb_frame_level *lvl_pinned = nullptr; // [max_frames]: pinned staging of that copy (s.copied covers it too)
 
     size_t places() const { return (size_t)n_receivers * max_aircraft; }
 };
@@ -137,6 +141,8 @@ struct adsb_track_bank : TrackStore {
     uint32_t *fuse_vals = nullptr;  // 2 x [places]: places in, sorted
     uint32_t *fuse_start = nullptr; // [fuse_max]
     adsb_fused_aircraft *fuse_out = nullptr; // [fuse_max]
+    adsb_fused_level *fuse_lvl_out = nullptr; // [fuse_max]: only with a levels reserve too (the second reserve makes it)
+    bool fused_levels = false;      // the last fuse also computed fuse_lvl_out
     uint64_t *fuse_counts = nullptr; // device [3]: records written, distinct ICAOs, ADSB_TRACK_FUSED_TRUNCATED
     void *fuse_temp = nullptr;
     size_t fuse_temp_bytes = 0;
@@ -149,6 +155,15 @@ static void free_all(std::initializer_list<void *> list)
 {
     for (void *p : list)
         if (p) (void)hipFree(p);
+}
+
+static void track_levels_free(TrackStore &s)
+{
+    free_all({s.dev.lvl, s.lvl.scan, s.lvl.temp, s.lvl_frames});
+    if (s.lvl_pinned) (void)hipHostFree(s.lvl_pinned);
+    s.dev.lvl = nullptr;
+    s.lvl = adsbk::TrackLvlDev{};
+    s.lvl_frames = s.lvl_pinned = nullptr;
 }
 
 static void track_summaries_free(TrackSummaries &s)
@@ -196,6 +211,7 @@ static void store_release(TrackStore &s)
     (void)hipSetDevice(s.ctx->cfg.device);
     (void)hipStreamSynchronize(s.ctx->aux);
     track_summaries_free(s.sum);
+    track_levels_free(s);
     free_all({s.dev.rec, s.words, s.dev.slot, s.dev.index, s.dev.hash, s.dev.prefix, s.dev.mark, s.dev.excl,
               s.dev.seg_slot, s.u32, s.temp, s.frames, s.fields, s.points, s.exp_u32, s.exp_temp});
     if (s.pinned) (void)hipHostFree(s.pinned);
@@ -250,6 +266,14 @@ static int store_stage_frames(TrackStore &s, const adsb_frame *host, size_t n)
     return ADSB_OK;
 }
 
+// The same for a host levels array (the *_update_levels forms), under the same event
+static int store_stage_levels(TrackStore &s, const adsb_frame_level *host, size_t n)
+{
+    std::memcpy(s.lvl_pinned, host, sizeof(adsb_frame_level) * n);
+    HIPCHK(hipMemcpyAsync(s.lvl_frames, s.lvl_pinned, sizeof(adsb_frame_level) * n, hipMemcpyHostToDevice, s.ctx->aux));
+    return ADSB_OK;
+}
+
 // The bookkeeping every update starts with (an empty one too: no summaries, an empty changed list); false: n == 0,
 // nothing to launch
 static bool store_begin_update(TrackStore &s, size_t n)
@@ -261,9 +285,10 @@ static bool store_begin_update(TrackStore &s, size_t n)
 }
 
 // Enqueues field decode and the tracker kernels over n frames at `list` (device), after the ctx's ordering pass and
-// field decode (same stream); dev: s.dev, or a bank's copy of it with this update's receiver split
+// field decode (same stream); dev: s.dev, or a bank's copy of it with this update's receiver split; levels (device,
+// or null): also the level merge
 static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t sample_base,
-                     const adsbk::TrackStoreDev &dev)
+                     const adsbk::TrackStoreDev &dev, const adsb_frame_level *levels = nullptr)
 {
     HIPCHK(adsbk::launch_decode_fields(s.ctx->aux, list, nullptr, (uint32_t)n, s.fields));
     adsbk::TrackArgs a = track_args(s.kind, list, s.fields, n, s.seconds_per_sample, s.u32, (size_t)s.max_frames,
@@ -271,6 +296,8 @@ static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t s
     a.sample_base = sample_base;
     a.store = &dev;
     a.sum = s.sum.dev.out ? &s.sum.dev : nullptr;
+    a.levels = levels;
+    a.lvl = levels ? &s.lvl : nullptr;
     HIPCHK(adsbk::launch_track(s.ctx->aux, a));
     return ADSB_OK;
 }
@@ -436,6 +463,76 @@ static int store_fetch_changed(TrackStore *st, adsb_aircraft_record *out, double
     return ADSB_OK;
 }
 
+// May wait for the device (hipMalloc, and the wait for the clear); a second reserve keeps what the first one made
+static int store_levels_reserve(TrackStore *st)
+{
+    if (!st) return ADSB_E_ARG;
+    HIPCHK(hipSetDevice(st->ctx->cfg.device));
+    if (st->dev.lvl) return ADSB_OK;
+    const size_t nf = (size_t)st->max_frames;
+    st->lvl.temp_bytes = adsbk::track_levels_temp_bytes(nf);
+    const bool ok = hipMalloc((void **)&st->dev.lvl, sizeof(adsb_aircraft_level) * st->places()) == hipSuccess &&
+                    hipMalloc((void **)&st->lvl.scan, sizeof(adsbk::TrackLvlTuple) * nf) == hipSuccess &&
+                    hipMalloc(&st->lvl.temp, st->lvl.temp_bytes) == hipSuccess &&
+                    hipMalloc((void **)&st->lvl_frames, sizeof(adsb_frame_level) * nf) == hipSuccess &&
+                    hipHostMalloc((void **)&st->lvl_pinned, sizeof(adsb_frame_level) * nf, hipHostMallocDefault) == hipSuccess &&
+                    adsbk::launch_track_levels_clear(st->ctx->aux, st->dev.lvl, st->places()) == hipSuccess &&
+                    hipStreamSynchronize(st->ctx->aux) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        track_levels_free(*st);
+        return ADSB_E_NOMEM;
+    }
+    return ADSB_OK;
+}
+
+// Waits.  As store_fetch, receiver by receiver in ascending ICAO: the level record beside each record.
+static int store_fetch_levels(TrackStore *s, adsb_aircraft_level *out, size_t max, size_t *n)
+{
+    if (!s || (!out && max)) return ADSB_E_ARG;
+    if (!s->dev.lvl) return ADSB_E_STATE;
+    adsb_ctx *c = s->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const uint32_t nr = s->n_receivers;
+    std::vector<uint32_t> w(nr); // sizes
+    HIPCHK(hipMemcpyAsync(w.data(), s->words, sizeof(uint32_t) * w.size(), hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    size_t total = 0, copied = 0;
+    std::vector<TrackRecord> recs;
+    std::vector<adsb_aircraft_level> lv;
+    std::vector<uint32_t> order;
+    for (uint32_t r = 0; r < nr; ++r) {
+        const size_t size = std::min<uint32_t>(w[r], s->max_aircraft);
+        total += size;
+        const size_t take = std::min(size, max - copied);
+        if (take) {
+            recs.resize(size);
+            lv.resize(size);
+            order.resize(size);
+            HIPCHK(hipMemcpyAsync(recs.data(), s->dev.rec + (size_t)r * s->max_aircraft, sizeof(TrackRecord) * size,
+                                  hipMemcpyDeviceToHost, c->aux));
+            HIPCHK(hipMemcpyAsync(lv.data(), s->dev.lvl + (size_t)r * s->max_aircraft, sizeof(adsb_aircraft_level) * size,
+                                  hipMemcpyDeviceToHost, c->aux));
+            HIPCHK(hipStreamSynchronize(c->aux));
+            for (size_t k = 0; k < size; ++k) order[k] = (uint32_t)k;
+            std::sort(order.begin(), order.end(),
+                      [&](uint32_t x, uint32_t y) { return recs[x].a.icao < recs[y].a.icao; }); // distinct per receiver
+            for (size_t k = 0; k < take; ++k) out[copied + k] = lv[order[k]];
+        }
+        copied += take;
+    }
+    if (n) *n = total;
+    return ADSB_OK;
+}
+
+static int store_levels_device(TrackStore *s, const adsb_aircraft_level **dev)
+{
+    if (!s) return ADSB_E_ARG;
+    if (!s->dev.lvl) return ADSB_E_STATE;
+    if (dev) *dev = s->dev.lvl;
+    return ADSB_OK;
+}
+
 // ---- persistent aircraft table (adsb_track_table_*) ------------------------------------------------------------------
 static void track_table_free(adsb_track_table *t)
 {
@@ -466,22 +563,52 @@ extern "C" void adsb_track_table_destroy(adsb_track_table *t)
     if (t) track_table_free(t);
 }
 
-extern "C" int adsb_track_table_update(adsb_track_table *t, const adsb_frame *frames, size_t n, uint64_t sample_base)
+// levels: null for the plain update
+static int track_table_update(adsb_track_table *t, const adsb_frame *frames, const adsb_frame_level *levels, size_t n,
+                              uint64_t sample_base)
 {
-    if (!t || (!frames && n)) return ADSB_E_ARG;
     if (n > t->max_frames) return ADSB_E_CAPACITY;
     adsb_ctx *c = t->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
     if (!store_begin_update(*t, n)) return ADSB_OK;
     const adsb_frame *list = frames;
-    if (!in_device_memory(c, frames)) {
-        HIPCHK(hipEventSynchronize(t->copied)); // the previous update's copy out of the staging has finished
-        int rc = store_stage_frames(*t, frames, n);
+    const bool frames_host = !in_device_memory(c, frames), levels_host = levels && !in_device_memory(c, levels);
+    if (frames_host || levels_host) {
+        HIPCHK(hipEventSynchronize(t->copied)); // the previous update's copies out of the staging have finished
+        int rc = frames_host ? store_stage_frames(*t, frames, n) : ADSB_OK;
+        if (rc == ADSB_OK && levels_host) rc = store_stage_levels(*t, levels, n);
         if (rc != ADSB_OK) return rc;
         HIPCHK(hipEventRecord(t->copied, c->aux));
-        list = t->frames;
+        if (frames_host) list = t->frames;
+        if (levels_host) levels = t->lvl_frames;
     }
-    return store_run(*t, list, n, sample_base, t->dev);
+    return store_run(*t, list, n, sample_base, t->dev, levels);
+}
+
+extern "C" int adsb_track_table_update(adsb_track_table *t, const adsb_frame *frames, size_t n, uint64_t sample_base)
+{
+    if (!t || (!frames && n)) return ADSB_E_ARG;
+    return track_table_update(t, frames, nullptr, n, sample_base);
+}
+
+extern "C" int adsb_track_table_levels_reserve(adsb_track_table *t) { return store_levels_reserve(t); }
+
+extern "C" int adsb_track_table_update_levels(adsb_track_table *t, const adsb_frame *frames,
+                                              const adsb_frame_level *levels, size_t n, uint64_t sample_base)
+{
+    if (!t || (!frames && n) || (!levels && n)) return ADSB_E_ARG;
+    if (!t->dev.lvl) return ADSB_E_STATE;
+    return track_table_update(t, frames, n ? levels : nullptr, n, sample_base);
+}
+
+extern "C" int adsb_track_table_fetch_levels(adsb_track_table *t, adsb_aircraft_level *out, size_t max, size_t *n)
+{
+    return store_fetch_levels(t, out, max, n);
+}
+
+extern "C" int adsb_track_table_levels_device(adsb_track_table *t, const adsb_aircraft_level **dev)
+{
+    return store_levels_device(t, dev);
 }
 
 extern "C" int adsb_track_table_summaries_reserve(adsb_track_table *t) { return store_summaries_reserve(t); }
@@ -533,7 +660,9 @@ extern "C" int adsb_track_table_fetch_velocity(adsb_track_table *t, adsb_velocit
 // ---- a bank of persistent tables, one per receiver (adsb_track_bank_*) ----------------------------------------------
 static void track_bank_fuse_free(adsb_track_bank *b)
 {
-    free_all({b->fuse_keys, b->fuse_vals, b->fuse_start, b->fuse_out, b->fuse_counts, b->fuse_temp});
+    free_all({b->fuse_keys, b->fuse_vals, b->fuse_start, b->fuse_out, b->fuse_lvl_out, b->fuse_counts, b->fuse_temp});
+    b->fuse_lvl_out = nullptr;
+    b->fused_levels = false;
     b->fuse_keys = b->fuse_temp = nullptr;
     b->fuse_vals = b->fuse_start = nullptr;
     b->fuse_out = nullptr;
@@ -594,17 +723,18 @@ extern "C" void adsb_track_bank_destroy(adsb_track_bank *b)
 // Enqueues the bank's kernels over n frames at `list` (device) with the receiver split src_prefix[0..n_src]; meta's
 // sample_base part has been filled by the caller (and the staging copy enqueued).
 static int track_bank_run(adsb_track_bank *b, const adsb_frame *list, size_t n, const uint64_t *src_prefix,
-                          uint32_t n_src)
+                          uint32_t n_src, const adsb_frame_level *levels = nullptr)
 {
     adsbk::TrackStoreDev dev = b->dev;
     dev.src_prefix = src_prefix;
     dev.n_src = n_src;
-    return store_run(*b, list, n, 0, dev);
+    return store_run(*b, list, n, 0, dev, levels);
 }
 
-// Stages sample_base (and, for a host split, the counts' prefix) through meta_pinned; frames_host: also the frames.
+// Stages sample_base (and, for a host split, the counts' prefix) through meta_pinned; frames_host / levels_host: also
+// the frames / the level records.
 static int track_bank_stage(adsb_track_bank *b, const uint64_t *counts, const uint64_t *sample_base,
-                            const adsb_frame *frames_host, size_t n)
+                            const adsb_frame *frames_host, size_t n, const adsb_frame_level *levels_host = nullptr)
 {
     adsb_ctx *c = b->ctx;
     const uint32_t nr = b->n_receivers;
@@ -620,14 +750,18 @@ static int track_bank_stage(adsb_track_bank *b, const uint64_t *counts, const ui
         int rc = store_stage_frames(*b, frames_host, n);
         if (rc != ADSB_OK) return rc;
     }
+    if (levels_host) {
+        int rc = store_stage_levels(*b, levels_host, n);
+        if (rc != ADSB_OK) return rc;
+    }
     HIPCHK(hipEventRecord(b->copied, c->aux));
     return ADSB_OK;
 }
 
-extern "C" int adsb_track_bank_update(adsb_track_bank *b, const adsb_frame *frames, size_t n, const uint64_t *counts,
-                                      const uint64_t *sample_base)
+// levels: null for the plain update
+static int track_bank_update(adsb_track_bank *b, const adsb_frame *frames, const adsb_frame_level *levels, size_t n,
+                             const uint64_t *counts, const uint64_t *sample_base)
 {
-    if (!b || (!frames && n) || (!counts && n)) return ADSB_E_ARG;
     if (counts) {
         uint64_t sum = 0;
         for (uint32_t r = 0; r < b->n_receivers; ++r) {
@@ -640,15 +774,56 @@ extern "C" int adsb_track_bank_update(adsb_track_bank *b, const adsb_frame *fram
     adsb_ctx *c = b->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
     if (!store_begin_update(*b, n)) return ADSB_OK;
-    const bool on_device = in_device_memory(c, frames);
-    int rc = track_bank_stage(b, counts, sample_base, on_device ? nullptr : frames, n);
+    const bool on_device = in_device_memory(c, frames), levels_host = levels && !in_device_memory(c, levels);
+    int rc = track_bank_stage(b, counts, sample_base, on_device ? nullptr : frames, n, levels_host ? levels : nullptr);
     if (rc != ADSB_OK) return rc;
-    return track_bank_run(b, on_device ? frames : b->frames, n, b->meta, b->n_receivers);
+    return track_bank_run(b, on_device ? frames : b->frames, n, b->meta, b->n_receivers,
+                          levels_host ? b->lvl_frames : levels);
 }
 
-extern "C" int adsb_track_bank_update_launch(adsb_track_bank *b, const uint64_t *sample_base)
+extern "C" int adsb_track_bank_update(adsb_track_bank *b, const adsb_frame *frames, size_t n, const uint64_t *counts,
+                                      const uint64_t *sample_base)
 {
-    if (!b) return ADSB_E_ARG;
+    if (!b || (!frames && n) || (!counts && n)) return ADSB_E_ARG;
+    return track_bank_update(b, frames, nullptr, n, counts, sample_base);
+}
+
+extern "C" int adsb_track_bank_levels_reserve(adsb_track_bank *b)
+{
+    int rc = store_levels_reserve(b);
+    if (rc != ADSB_OK || !b->fuse_max || b->fuse_lvl_out) return rc;
+    // the fuse reserve came first: the fused level records are this reserve's to make
+    if (hipMalloc((void **)&b->fuse_lvl_out, sizeof(adsb_fused_level) * b->fuse_max) != hipSuccess) {
+        (void)hipGetLastError();
+        b->fuse_lvl_out = nullptr;
+        track_levels_free(*b);
+        return ADSB_E_NOMEM;
+    }
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_update_levels(adsb_track_bank *b, const adsb_frame *frames,
+                                             const adsb_frame_level *levels, size_t n, const uint64_t *counts,
+                                             const uint64_t *sample_base)
+{
+    if (!b || (!frames && n) || (!levels && n) || (!counts && n)) return ADSB_E_ARG;
+    if (!b->dev.lvl) return ADSB_E_STATE;
+    return track_bank_update(b, frames, n ? levels : nullptr, n, counts, sample_base);
+}
+
+extern "C" int adsb_track_bank_fetch_levels(adsb_track_bank *b, adsb_aircraft_level *out, size_t max, size_t *n)
+{
+    return store_fetch_levels(b, out, max, n);
+}
+
+extern "C" int adsb_track_bank_levels_device(adsb_track_bank *b, const adsb_aircraft_level **dev)
+{
+    return store_levels_device(b, dev);
+}
+
+// with_levels: also the ctx's levels of the same launch (adsb_track_bank_update_launch_levels)
+static int track_bank_update_launch(adsb_track_bank *b, const uint64_t *sample_base, bool with_levels)
+{
     adsb_ctx *c = b->ctx;
     if (!c->launched) return ADSB_E_STATE;
     if (c->last_channels > b->n_receivers) return ADSB_E_ARG;
@@ -657,16 +832,34 @@ extern "C" int adsb_track_bank_update_launch(adsb_track_bank *b, const uint64_t 
     const uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
     if (n > b->max_frames) return ADSB_E_CAPACITY;
     HIPCHK(hipSetDevice(c->cfg.device));
+    // not enqueued yet for this launch, or of the list with holes that sync_header has just rebuilt: (again) now, on
+    // the stream the tracker's kernels follow on; before the store's bookkeeping, which an error here leaves as it was
+    if (with_levels && n && !(c->levels && c->levels_current) && (rc = adsb_levels_device_async(c)) != ADSB_OK) return rc;
     if (!store_begin_update(*b, (size_t)n)) return ADSB_OK;
     if ((rc = track_bank_stage(b, nullptr, sample_base, nullptr, 0)) != ADSB_OK) return rc;
     adsb_ctx::ResultSet &r = c->rs[c->last];
     // the channel split as adsb_fetch's per_channel_counts reads it: chan_prefix clipped to the list
-    if ((rc = track_bank_run(b, c->last_out, (size_t)n, r.chan_prefix, c->last_channels)) != ADSB_OK) return rc;
+    if ((rc = track_bank_run(b, c->last_out, (size_t)n, r.chan_prefix, c->last_channels,
+                             with_levels ? c->levels : nullptr)) != ADSB_OK)
+        return rc;
     if (c->own_aux) { // the launch that reuses this result set waits for these kernels too
         HIPCHK(hipEventRecord(r.g_done, c->aux));
         r.g_pending = true;
     }
     return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_update_launch(adsb_track_bank *b, const uint64_t *sample_base)
+{
+    if (!b) return ADSB_E_ARG;
+    return track_bank_update_launch(b, sample_base, false);
+}
+
+extern "C" int adsb_track_bank_update_launch_levels(adsb_track_bank *b, const uint64_t *sample_base)
+{
+    if (!b) return ADSB_E_ARG;
+    if (!b->dev.lvl) return ADSB_E_STATE;
+    return track_bank_update_launch(b, sample_base, true);
 }
 
 extern "C" int adsb_track_bank_fetch_points(adsb_track_bank *b, adsb_track_point *points, size_t max_points,
@@ -734,6 +927,7 @@ extern "C" int adsb_track_bank_fuse_reserve(adsb_track_bank *b, size_t max_fused
                     hipMalloc((void **)&b->fuse_vals, 2 * sizeof(uint32_t) * places) == hipSuccess &&
                     hipMalloc((void **)&b->fuse_start, sizeof(uint32_t) * cap) == hipSuccess &&
                     hipMalloc((void **)&b->fuse_out, sizeof(adsb_fused_aircraft) * cap) == hipSuccess &&
+                    (!b->dev.lvl || hipMalloc((void **)&b->fuse_lvl_out, sizeof(adsb_fused_level) * cap) == hipSuccess) &&
                     hipMalloc((void **)&b->fuse_counts, sizeof(uint64_t) * 3) == hipSuccess &&
                     hipMalloc(&b->fuse_temp, b->fuse_temp_bytes) == hipSuccess;
     if (!ok) {
@@ -761,6 +955,7 @@ extern "C" int adsb_track_bank_fuse(adsb_track_bank *b, double since)
     a.svals = b->fuse_vals + places;
     a.seg_start = b->fuse_start;
     a.out = b->fuse_out;
+    a.lvl_out = b->dev.lvl ? b->fuse_lvl_out : nullptr; // both reserves: the fused levels too
     a.counts = b->fuse_counts;
     a.max_fused = b->fuse_max;
     a.temp = b->fuse_temp;
@@ -768,6 +963,26 @@ extern "C" int adsb_track_bank_fuse(adsb_track_bank *b, double since)
     a.lanes = b->fuse_lanes;
     HIPCHK(adsbk::launch_track_fuse(b->ctx->aux, a)); // after the bank's last update / expire / reset (same stream)
     b->fused = true;
+    b->fused_levels = a.lvl_out != nullptr;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_bank_fetch_fused_levels(adsb_track_bank *b, adsb_fused_level *out, size_t max, size_t *n)
+{
+    if (!b || (!out && max)) return ADSB_E_ARG;
+    if (!b->fused || !b->fused_levels) return ADSB_E_STATE;
+    adsb_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    uint64_t written = 0;
+    HIPCHK(hipMemcpyAsync(&written, b->fuse_counts, sizeof(written), hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    written = std::min<uint64_t>(written, b->fuse_max);
+    const size_t take = std::min<size_t>((size_t)written, max);
+    if (take) {
+        HIPCHK(hipMemcpyAsync(out, b->fuse_lvl_out, sizeof(adsb_fused_level) * take, hipMemcpyDeviceToHost, c->aux));
+        HIPCHK(hipStreamSynchronize(c->aux));
+    }
+    if (n) *n = (size_t)written;
     return ADSB_OK;
 }
 

@@ -121,6 +121,14 @@ FUSED_DTYPE = np.dtype([("latitude", "<f8"), ("longitude", "<f8"), ("position_ti
                         ("has_position", "<u4"), ("callsign", "S8"), ("velocity", VELOCITY_DTYPE),
                         ("reserved", "<u8", (2,))])
 assert FUSED_DTYPE.itemsize == C.sizeof(L.AdsbFusedAircraft) == 128
+AIRCRAFT_LEVEL_DTYPE = np.dtype([("signal_total", "<u8"), ("noise_total", "<u8"), ("last_signal_sum", "<u8"),
+                                 ("last_noise_sum", "<u8"), ("max_signal_sum", "<u8"), ("last_time", "<f8"),
+                                 ("n_levels", "<u4"), ("peak", "<u4"), ("weak_bits_total", "<u4"), ("reserved", "<u4")])
+assert AIRCRAFT_LEVEL_DTYPE.itemsize == C.sizeof(L.AdsbAircraftLevel) == 64
+FUSED_LEVEL_DTYPE = np.dtype([("strongest", AIRCRAFT_LEVEL_DTYPE), ("signal_total", "<u8"), ("noise_total", "<u8"),
+                              ("n_levels", "<u8"), ("strongest_receiver", "<u2"), ("level_receivers", "<u2"),
+                              ("reserved", "<u4")])
+assert FUSED_LEVEL_DTYPE.itemsize == C.sizeof(L.AdsbFusedLevel) == 96
 
 
 class Tracker:
@@ -657,6 +665,26 @@ class _TrackStore:
         self._call("summaries_device", C.byref(dev))
         return dev.value
 
+    def levels_reserve(self):
+        """adsb_track_{table,bank}_levels_reserve: one AIRCRAFT_LEVEL_DTYPE record beside every aircraft record, which
+        an update given `levels` merges the frames' LEVEL_DTYPE records into."""
+        self._call("levels_reserve")
+
+    def levels_device(self):
+        """Device address of the level records, one per record place in slot order (a bank: receiver r's from place
+        r x max_aircraft); no synchronisation."""
+        dev = C.c_void_p()
+        self._call("levels_device", C.byref(dev))
+        return dev.value
+
+    @staticmethod
+    def _host_levels(levels, n):
+        """A host LEVEL_DTYPE array of n records -> (the array to keep alive, its address or None)."""
+        levels = np.ascontiguousarray(levels, dtype=LEVEL_DTYPE)
+        if len(levels) != n:
+            raise ValueError(f"levels: {len(levels)} records for {n} frames")
+        return levels, (levels.ctypes.data if n else None)
+
 
 class TrackTable(_TrackStore):
     """adsb_track_table_*: one aircraft table on the device that lives across launches (the reference's
@@ -667,14 +695,28 @@ class TrackTable(_TrackStore):
         self._open(dem, L.AdsbTrackTableCfg(L.ADSB_ABI_VERSION, int(max_aircraft), int(max_frames),
                                             float(seconds_per_sample)), max_frames)
 
-    def update(self, frames, sample_base=0):
-        """frames: FRAME_DTYPE array in ascending offset (host); packet time = (sample_base + offset) x sps."""
+    def update(self, frames, sample_base=0, levels=None):
+        """frames: FRAME_DTYPE array in ascending offset (host); packet time = (sample_base + offset) x sps.  levels
+        (after levels_reserve): the frames' LEVEL_DTYPE records (host), merged into the aircraft's level records."""
         frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
-        self._call("update", frames.ctypes.data if len(frames) else None, len(frames), int(sample_base))
+        ptr = frames.ctypes.data if len(frames) else None
+        if levels is None:
+            self._call("update", ptr, len(frames), int(sample_base))
+        else:
+            keep, lptr = self._host_levels(levels, len(frames))
+            self._call("update_levels", ptr, lptr, len(frames), int(sample_base))
 
-    def update_device(self, dev_ptr, n, sample_base=0):
-        """n frames at dev_ptr in the ctx device's memory (e.g. result_device() after fetch_counts())."""
-        self._call("update", dev_ptr, int(n), int(sample_base))
+    def update_device(self, dev_ptr, n, sample_base=0, levels_ptr=None):
+        """n frames at dev_ptr in the ctx device's memory (e.g. result_device() after fetch_counts()).  levels_ptr
+        (after levels_reserve): their n level records, on the device (e.g. levels_device()) or a host address."""
+        if levels_ptr is None:
+            self._call("update", dev_ptr, int(n), int(sample_base))
+        else:
+            self._call("update_levels", dev_ptr, levels_ptr, int(n), int(sample_base))
+
+    def levels(self):
+        """AIRCRAFT_LEVEL_DTYPE records (each aircraft's signal level), aligned with aircraft()[0]."""
+        return self._fetch("fetch_levels", [AIRCRAFT_LEVEL_DTYPE])[0]
 
     def aircraft(self):
         """(AIRCRAFT_DTYPE records of the whole table in ascending ICAO, table flags)."""
@@ -728,20 +770,32 @@ class TrackBank(_TrackStore):
         edges = np.concatenate([[0], np.cumsum(list(counts))]).astype(np.int64)
         return [out[edges[r]:edges[r + 1]].copy() for r in range(self.n_receivers)]
 
-    def update(self, frames, counts, sample_base=None):
+    def update(self, frames, counts, sample_base=None, levels=None):
         """frames: FRAME_DTYPE array (host), receiver 0's frames in ascending offset, then receiver 1's, ...;
-        counts: frames of each receiver; sample_base: scalar or per receiver (frame time = (base + offset) x sps)."""
+        counts: frames of each receiver; sample_base: scalar or per receiver (frame time = (base + offset) x sps);
+        levels (after levels_reserve): the frames' LEVEL_DTYPE records (host), merged into the level records."""
         frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
-        self._call("update", frames.ctypes.data if len(frames) else None, len(frames), self._u64s(counts, "counts"),
-                   self._u64s(sample_base, "sample_base"))
+        ptr = frames.ctypes.data if len(frames) else None
+        split = (self._u64s(counts, "counts"), self._u64s(sample_base, "sample_base"))
+        if levels is None:
+            self._call("update", ptr, len(frames), *split)
+        else:
+            keep, lptr = self._host_levels(levels, len(frames))
+            self._call("update_levels", ptr, lptr, len(frames), *split)
 
-    def update_device(self, dev_ptr, n, counts, sample_base=None):
-        """n frames at dev_ptr in the ctx device's memory, split by counts as for update()."""
-        self._call("update", dev_ptr, int(n), self._u64s(counts, "counts"), self._u64s(sample_base, "sample_base"))
+    def update_device(self, dev_ptr, n, counts, sample_base=None, levels_ptr=None):
+        """n frames at dev_ptr in the ctx device's memory, split by counts as for update().  levels_ptr (after
+        levels_reserve): their n level records, on the device or a host address."""
+        split = (self._u64s(counts, "counts"), self._u64s(sample_base, "sample_base"))
+        if levels_ptr is None:
+            self._call("update", dev_ptr, int(n), *split)
+        else:
+            self._call("update_levels", dev_ptr, levels_ptr, int(n), *split)
 
-    def update_launch(self, sample_base=None):
-        """The ctx's last launch, channel k -> receiver k: what fetch() returns, read in device memory."""
-        self._call("update_launch", self._u64s(sample_base, "sample_base"))
+    def update_launch(self, sample_base=None, levels=False):
+        """The ctx's last launch, channel k -> receiver k: what fetch() returns, read in device memory.  levels=True
+        (after levels_reserve): with the launch's levels, which are enqueued here if they have not been."""
+        self._call("update_launch_levels" if levels else "update_launch", self._u64s(sample_base, "sample_base"))
 
     def aircraft(self):
         """(list of n_receivers AIRCRAFT_DTYPE arrays, each in ascending ICAO; list of per-receiver flags)."""
@@ -772,6 +826,15 @@ class TrackBank(_TrackStore):
     def velocity(self):
         """list of n_receivers VELOCITY_DTYPE arrays, aligned with aircraft()[0]."""
         return self._aligned("fetch_velocity", VELOCITY_DTYPE)
+
+    def levels(self):
+        """list of n_receivers AIRCRAFT_LEVEL_DTYPE arrays, aligned with aircraft()[0]."""
+        return self._aligned("fetch_levels", AIRCRAFT_LEVEL_DTYPE)
+
+    def fused_levels(self):
+        """FUSED_LEVEL_DTYPE records of the last fuse_async() / fuse(), one per fused record in the same order; needs
+        both fuse_reserve and levels_reserve before that fuse."""
+        return self._fetch("fetch_fused_levels", [FUSED_LEVEL_DTYPE])[0]
 
     def fuse(self, since=-math.inf, max_fused=None):
         """The fused view: one FUSED_DTYPE record per distinct ICAO over all receivers, ascending ICAO, from the records

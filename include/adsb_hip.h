@@ -598,6 +598,113 @@ int adsb_track_bank_fetch_changed(adsb_track_bank *bank, adsb_aircraft_record *r
                                   adsb_velocity *velocity, size_t max, size_t *n, uint64_t *per_receiver_counts);
 
 /*
+ * Per-aircraft signal levels: the per-frame power statistics (adsb_frame_level) kept per aircraft, beside its record.
+ * With a levels reserve a table or bank holds one 64-byte adsb_aircraft_level per record place, and the *_levels
+ * forms of update merge a list's level records into them.  Frame j of an update is COUNTED for its aircraft iff its
+ * point is not ADSB_TRACK_UNTRACKED and levels[j].flags has ADSB_LEVEL_VALID.  Over an aircraft's counted frames:
+ *   signal_total, noise_total, weak_bits_total, n_levels: sums that SATURATE at the field's maximum (2^64 - 1,
+ *       2^32 - 1) and stay there;
+ *   max_signal_sum, peak: maxima (exact, also once a total has saturated);
+ *   last_signal_sum, last_noise_sum, last_time: of the NEWEST counted frame, the last one in list order (frames with
+ *       equal offsets are applied in list order, as for the merge); last_time is the store's frame time of that frame,
+ *       (sample_base + offset) x seconds_per_sample, the same single rounded product as every other time of the store.
+ * An EMPTY level record is all zeros with last_time NaN.  An aircraft's is empty at admission, at re-admission after
+ * an expire, after a reset, and while the store held the aircraft from before the reserve, until its next counted
+ * frame.  Expire moves a survivor's level record with its record.  Every field combines by an associative,
+ * commutative rule (saturating add, max, newest by position), so the records are bit-exact whatever shape the
+ * reduction takes: one list (frames and levels alike) cut into any sequence of updates gives the same 64 bytes per
+ * aircraft, receiver r of a bank equals a table of its own, and two runs give the same bytes.  The mean signal power
+ * of an aircraft is signal_total / (116 x n_levels); once signal_total has saturated that mean is a LOWER BOUND.
+ * On the device: after the pairs step, one segmented inclusive scan over the sorted list (rocPRIM, a 48-byte tuple
+ * computed where the scan loads it) and one thread per segment tail that merges into the side record: linear in the
+ * list however long one aircraft's part is, no atomics.  Device memory, all of it allocated by the reserve and none
+ * before: 64 bytes per place of n_receivers x max_aircraft, and per frame of max_frames 32 bytes of device staging
+ * for a host levels array, 48 bytes of scan values plus rocPRIM's scan scratch; 32 bytes per frame of pinned host
+ * memory (64 receivers x 65536 aircraft: 256 MiB of level records).  A table or bank that never reserves allocates
+ * nothing, launches exactly the kernels it launched before and returns the same bytes; the plain update of a store
+ * that did reserve behaves as before too and leaves the level records alone (apart from admission emptying a place).
+ * fetch_changed and the per-frame summaries carry no levels.
+ */
+typedef struct adsb_aircraft_level {  /* 64 bytes, one per record place, beside the 128-byte record */
+    uint64_t signal_total;     /* saturating sum of signal_sum over the counted frames            */
+    uint64_t noise_total;      /* saturating sum of noise_sum                                     */
+    uint64_t last_signal_sum;  /* of the newest counted frame                                     */
+    uint64_t last_noise_sum;
+    uint64_t max_signal_sum;   /* greatest signal_sum of a counted frame                          */
+    double   last_time;        /* the store's frame time of the newest counted frame; NaN if none */
+    uint32_t n_levels;         /* counted frames, saturating                                      */
+    uint32_t peak;             /* max of peak over the counted frames                             */
+    uint32_t weak_bits_total;  /* saturating sum of weak_bits                                     */
+    uint32_t reserved;         /* 0 */
+} adsb_aircraft_level;
+/* Allocates the above and empties every level record.  May wait for the device.  A second reserve changes nothing.
+ * ADSB_E_ARG for a NULL table, ADSB_E_NOMEM if the memory is not to be had. */
+int adsb_track_table_levels_reserve(adsb_track_table *table);
+/* adsb_track_table_update plus the level merge: points, records, summaries and the changed list are byte for byte what
+ * update gives on the same frames.  levels[n] is the frames' level records in list order; `frames` and `levels` may
+ * each be host memory or memory of the ctx's device, independently; host arrays have been copied when this returns.
+ * A table's path from a launch: adsb_result_device (after adsb_fetch_counts) and adsb_levels_device (after
+ * adsb_levels_device_async) give the two device arrays.  A feed's consumer passes adsb_host_frame_levels output as a
+ * host array.  ADSB_E_ARG for a NULL table, or NULL frames or levels with n > 0; ADSB_E_STATE without a reserve;
+ * ADSB_E_CAPACITY for n > max_frames; n = 0 is ADSB_OK. */
+int adsb_track_table_update_levels(adsb_track_table *table, const adsb_frame *frames, const adsb_frame_level *levels,
+                                   size_t n, uint64_t sample_base);
+/* Waits; one level record per aircraft, in exactly the order adsb_track_table_fetch returns the records (ascending
+ * ICAO); *n = records held even if more than max.  ADSB_E_ARG for a NULL table, or NULL out with max > 0;
+ * ADSB_E_STATE without a reserve. */
+int adsb_track_table_fetch_levels(adsb_track_table *table, adsb_aircraft_level *out, size_t max, size_t *n);
+/* Does not synchronise: the device address of the level records, one per record PLACE (max_aircraft of them; a bank:
+ * receiver r's at [r x max_aircraft, (r + 1) x max_aircraft)), in slot order, which is admission order and not ICAO
+ * order, for consumers that stay on the GPU; valid on the ctx stream for the life of the store.  dev may be NULL.
+ * ADSB_E_ARG for a NULL table, ADSB_E_STATE without a reserve. */
+int adsb_track_table_levels_device(adsb_track_table *table, const adsb_aircraft_level **dev);
+/* The same for a bank; fetch_levels receiver by receiver, each in ascending ICAO, as adsb_track_bank_fetch. */
+int adsb_track_bank_levels_reserve(adsb_track_bank *bank);
+int adsb_track_bank_update_levels(adsb_track_bank *bank, const adsb_frame *frames, const adsb_frame_level *levels,
+                                  size_t n, const uint64_t *counts, const uint64_t *sample_base);
+/* adsb_track_bank_update_launch with the ctx's levels of the same launch: enqueues adsb_levels_device_async itself if
+ * the ctx's levels are not those of the last launch, and again for the rebuilt list when the header sync rebuilt it
+ * (slot-pool overflow), as adsb_fetch_levels does.  Errors of the levels call are passed through.  ADSB_E_STATE
+ * without a reserve or before any launch. */
+int adsb_track_bank_update_launch_levels(adsb_track_bank *bank, const uint64_t *sample_base);
+int adsb_track_bank_fetch_levels(adsb_track_bank *bank, adsb_aircraft_level *out, size_t max, size_t *n);
+int adsb_track_bank_levels_device(adsb_track_bank *bank, const adsb_aircraft_level **dev);
+/*
+ * Fused levels.  A bank with both a fuse reserve and a levels reserve also computes, in adsb_track_bank_fuse, one
+ * adsb_fused_level per fused record, in the same order (under truncation: for the written records only), over the same
+ * contributing records.  The STRONGEST receiver is the one with the greatest mean signal signal_total / n_levels among
+ * the contributing records with n_levels > 0, compared exactly by cross-multiplication (a.signal_total x b.n_levels
+ * against b.signal_total x a.n_levels, 96-bit integer products, no floating point); ties go to the lowest receiver.  A
+ * saturated signal_total makes that record's mean a lower bound, and it is compared as such.  The array of max_fused
+ * records (96 bytes each) is allocated by whichever of the two reserves comes second; a repeated fuse_reserve resizes
+ * it.  The 128-byte fused records are what they are without a levels reserve.  A kernel of its own after the fuse's
+ * reduction, one thread per fused record over the sorted places.
+ */
+typedef struct adsb_fused_level {     /* 96 bytes, one per fused record, same order */
+    /* the first ten fields are strongest_receiver's adsb_aircraft_level, bit for bit and in its order (offset 0); an
+     * empty one if none */
+    uint64_t strongest_signal_total;
+    uint64_t strongest_noise_total;
+    uint64_t strongest_last_signal_sum;
+    uint64_t strongest_last_noise_sum;
+    uint64_t strongest_max_signal_sum;
+    double   strongest_last_time;
+    uint32_t strongest_n_levels;
+    uint32_t strongest_peak;
+    uint32_t strongest_weak_bits_total;
+    uint32_t strongest_reserved;
+    uint64_t signal_total, noise_total; /* saturating sums over the contributing records               */
+    uint64_t n_levels;                /* sum of their n_levels                                         */
+    uint16_t strongest_receiver;      /* ADSB_FUSED_NONE if no contributing record has n_levels > 0    */
+    uint16_t level_receivers;         /* contributing records with n_levels > 0                        */
+    uint32_t reserved;                /* 0 */
+} adsb_fused_level;
+/* Waits; copies min(records written, max) level records of the last fuse; *n (optional) = records written by that fuse
+ * even if more than max.  ADSB_E_ARG for a NULL bank, or NULL out with max > 0; ADSB_E_STATE if the last fuse computed
+ * no levels: no fuse yet (since the last fuse reserve), or one of the two reserves was missing when it ran. */
+int adsb_track_bank_fetch_fused_levels(adsb_track_bank *bank, adsb_fused_level *out, size_t max, size_t *n);
+
+/*
  * ---- several GPUs behind one call ---------------------------------------------------------
  * The reference's thread 2 is one function on one thread (src/adsb.rs:92, spawned at adsb.rs:147); a group is the
  * drop-in for that function when the buffer should be spread over N devices: one context per member, the offsets

@@ -8,6 +8,7 @@
   tools/replay.py capture.c16 --aircraft      # the final aircraft table instead (tui.rs:65-95, Velocity filled)
   tools/replay.py capture.c16 --web           # what the web thread broadcasts instead: one JSON line per packet
   tools/replay.py capture.c16 --levels        # signal and noise power of every packet instead, tab-separated
+  tools/replay.py capture.c16 --aircraft --levels   # the aircraft table with two more columns: RSSI and SNR
 
 Everything below the argument parsing is one call through the C ABI (adsb_replay_file, include/adsb_host.h).
 The "Processed Time" line carries no value (the reference prints the wall clock there).  With --aircraft, the frames
@@ -20,7 +21,11 @@ of frame time (0 when the aircraft has had no position message): the reference s
 are printed with Python's shortest round-trip repr.  With --levels, one line per packet: offset, ICAO (hex), signal
 dBFS, noise dBFS, their difference, weak bits -- the mean power of the packet's 116 pulse samples and of its 124 quiet
 samples against a full-scale sample, one decimal, "-inf" for a sum of zero; computed on the device over the capture in
-device memory (adsb_levels_of), in overlapping pieces if the capture is large.  The TEXT has not been compared with a Rust build's (there is no
+device memory (adsb_levels_of), in overlapping pieces if the capture is large.  With --aircraft --levels, the table's
+update also merges every frame's level record (the host mirror's, adsb_host_frame_levels) into the aircraft's level
+record on the device, and two columns are appended: RSSI, the aircraft's mean signal power in dBFS over its 116 x
+n_levels pulse samples, and SNR, that minus its mean noise power in dBFS over 124 x n_levels quiet samples, one decimal,
+"n/a" in both for an aircraft without a counted frame; --aircraft alone prints what it always printed.  The TEXT has not been compared with a Rust build's (there is no
 Rust toolchain); only the values are checked, against the oracle."""
 import argparse
 import json
@@ -36,16 +41,38 @@ from air_rs_amd import _lib as L  # noqa: E402
 SECONDS_PER_SAMPLE = 0.5e-6  # 2 MSPS
 
 
-def aircraft_table(d, frames, n_samples):
+def mean_dbfs(st, total, n_samples):
+    """adsb_level_dbfs in Python floats (its n_samples is 32 bits; an aircraft's 116 x n_levels need not fit)."""
+    full_scale = 32768.0 if st == A.ADSB_SAMPLE_I8 else 2147483648.0
+    return -math.inf if total == 0 else 10.0 * math.log10(float(total) / float(n_samples) / full_scale)
+
+
+def level_columns(st, lv):
+    """RSSI and SNR of one AIRCRAFT_LEVEL_DTYPE record."""
+    n = int(lv["n_levels"])
+    if n == 0:
+        return ["n/a", "n/a"]
+    sig = mean_dbfs(st, int(lv["signal_total"]), A.LEVEL_PULSE_SAMPLES * n)
+    noise = mean_dbfs(st, int(lv["noise_total"]), A.LEVEL_QUIET_SAMPLES * n)
+    return [f"{sig:.1f}", f"{sig - noise:.1f}"]
+
+
+def aircraft_table(d, frames, n_samples, st=None, frame_levels=None):
     """The capture's final aircraft table as tab-separated text: tui.rs:95's columns, rows by age (tui.rs:69), then
-    ICAO.  Age = whole seconds from each aircraft's last frame to the end of the capture."""
+    ICAO.  Age = whole seconds from each aircraft's last frame to the end of the capture.  frame_levels (one
+    LEVEL_DTYPE record per frame, with st the sample type): also the columns RSSI and SNR."""
     with A.TrackTable(d, max_frames=max(len(frames), 1), seconds_per_sample=SECONDS_PER_SAMPLE) as t:
-        t.update(frames)
+        if frame_levels is None:
+            t.update(frames)
+        else:
+            t.levels_reserve()
+            t.update(frames, levels=frame_levels)
         recs, _ = t.aircraft()
         vel, heard = t.velocity(), t.last_heard()
+        levels = [None] * len(recs) if frame_levels is None else t.levels()
     now = n_samples * SECONDS_PER_SAMPLE
     rows = []
-    for rec, v, lh in zip(recs, vel, heard):
+    for rec, v, lh, lv in zip(recs, vel, heard, levels):
         pos, age = bool(rec["has_position"]), int(now - lh)
         rows.append((age, int(rec["icao"]), "\t".join([
             f"{int(rec['icao']):x}",
@@ -54,9 +81,10 @@ def aircraft_table(d, frames, n_samples):
             f"{float(rec['latitude']):.6f}" if pos else "n/a",
             f"{float(rec['longitude']):.6f}" if pos else "n/a",
             f"{float(v['speed_kt']):.0f}" if v["flags"] & A.ADSB_VELOCITY_SPEED else "n/a",
-            f"{age}"])))
+            f"{age}"] + ([] if lv is None else level_columns(st, lv)))))
     rows.sort(key=lambda r: (r[0], r[1]))
-    return "ICAO\tCallsign\tAltitude\tLatitude\tLongitude\tVelocity\tAge\n" + "".join(r[2] + "\n" for r in rows)
+    head = "ICAO\tCallsign\tAltitude\tLatitude\tLongitude\tVelocity\tAge" + ("" if frame_levels is None else "\tRSSI\tSNR")
+    return head + "\n" + "".join(r[2] + "\n" for r in rows)
 
 
 def summary_json(rec):
@@ -133,7 +161,7 @@ def main():
     ap.add_argument("--summary", action="store_true", help="print counts to stderr")
     ap.add_argument("--aircraft", action="store_true", help="print the final aircraft table instead of the stream text")
     ap.add_argument("--web", action="store_true", help="print one AircraftSummary JSON line per packet instead")
-    ap.add_argument("--levels", action="store_true", help="print signal and noise power of every packet instead")
+    ap.add_argument("--levels", action="store_true", help="print signal and noise power of every packet instead; with --aircraft: two more columns, RSSI and SNR")
     a = ap.parse_args()
     fmt = a.format or ("c16" if a.file.endswith(".c16") else "u8")
     st = A.ADSB_SAMPLE_I16 if fmt == "c16" else A.ADSB_SAMPLE_I8
@@ -143,7 +171,9 @@ def main():
         frames, n_buf, n_samp, text = d.replay_file(a.file, L.ADSB_FILE_C16 if fmt == "c16" else L.ADSB_FILE_U8,
                                                     chunk_len=a.chunk, carry=a.carry, send_tail=a.tail,
                                                     max_frames=max(n_max // 200, 1 << 16))
-        if a.aircraft:
+        if a.aircraft and a.levels:
+            text = aircraft_table(d, frames, n_samp, st, A.host_frame_levels(read_capture(a.file, fmt), frames))
+        elif a.aircraft:
             text = aircraft_table(d, frames, n_samp)
         elif a.web:
             text = web_stream(d, frames, a.chunk)
