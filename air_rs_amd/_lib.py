@@ -6,6 +6,8 @@ a HIP device ``adsb_create`` returns ADSB_E_NODEVICE.
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # ADSB_HIP_LIB lets tuning experiments point at another build of the same library
 LIB_PATH = os.environ.get("ADSB_HIP_LIB") or os.path.join(_HERE, "lib", "libadsb_hip.so")
@@ -144,6 +146,46 @@ class AdsbFusedLevel(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+ADSB_FIX_VALID = 0x1      # adsb_fix.flags / adsb_frame_fix.flags: the record holds a fix
+ADSB_FIX_SURFACE = 0x2    # from a surface message (TC 5-8)
+ADSB_FIX_ALT = 0x4        # altitude holds a value (TC 9-18)
+ADSB_FIX_SPEED = 0x8      # ground_speed_kt holds a value
+ADSB_FIX_TRACK = 0x10     # track_deg holds a value
+ADSB_FIX_REJECTED = 0x20  # adsb_frame_fix.flags only: a position message turned away
+
+
+class AdsbSite(C.Structure):
+    """adsb_site: a receiver's position (degrees) and the greatest range (NM, (0, 180]) it accepts a fix at."""
+    _fields_ = [("latitude", C.c_double), ("longitude", C.c_double), ("max_range_nm", C.c_double)]
+
+
+class AdsbFix(C.Structure):
+    """adsb_fix: an aircraft's newest single-message position beside its record (tables and banks with a fixes
+    reserve)."""
+    _fields_ = [("time", C.c_double), ("latitude", C.c_double), ("longitude", C.c_double), ("range_nm", C.c_float),
+                ("bearing_deg", C.c_float), ("ground_speed_kt", C.c_float), ("track_deg", C.c_float),
+                ("altitude", C.c_int32), ("n_fixes", C.c_uint32), ("n_rejected", C.c_uint32), ("type_code", C.c_uint8),
+                ("flags", C.c_uint8), ("cpr_odd", C.c_uint8), ("reserved8", C.c_uint8), ("reserved", C.c_uint32)]
+
+
+class AdsbFrameFix(C.Structure):
+    _fields_ = [("latitude", C.c_double), ("longitude", C.c_double), ("range_nm", C.c_float),
+                ("bearing_deg", C.c_float), ("icao", C.c_uint32), ("flags", C.c_uint32)]
+
+
+SITE = np.dtype([("latitude", "<f8"), ("longitude", "<f8"), ("max_range_nm", "<f8")])
+# the struct's fields, and its 4 bytes of tail padding (zero) as a field of their own, so that every copy of a record
+# carries all 64 bytes and tobytes() is the C record
+FIX_DTYPE = np.dtype([("time", "<f8"), ("latitude", "<f8"), ("longitude", "<f8"), ("range_nm", "<f4"),
+                      ("bearing_deg", "<f4"), ("ground_speed_kt", "<f4"), ("track_deg", "<f4"), ("altitude", "<i4"),
+                      ("n_fixes", "<u4"), ("n_rejected", "<u4"), ("type_code", "u1"), ("flags", "u1"), ("cpr_odd", "u1"),
+                      ("reserved8", "u1"), ("reserved", "<u4"), ("_pad", "<u4")])
+FRAME_FIX_DTYPE = np.dtype([("latitude", "<f8"), ("longitude", "<f8"), ("range_nm", "<f4"), ("bearing_deg", "<f4"),
+                            ("icao", "<u4"), ("flags", "<u4")])
+assert SITE.itemsize == C.sizeof(AdsbSite) == 24 and FIX_DTYPE.itemsize == C.sizeof(AdsbFix) == 64
+assert FRAME_FIX_DTYPE.itemsize == C.sizeof(AdsbFrameFix) == 32
+
+
 class AdsbTrackBankCfg(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("n_receivers", C.c_uint32), ("max_aircraft", C.c_uint32),
                 ("reserved", C.c_uint32), ("max_frames", C.c_uint64), ("seconds_per_sample", C.c_double)]
@@ -228,6 +270,14 @@ PROTOTYPES = {
     "adsb_track_bank_update_launch_levels": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
     "adsb_track_bank_fetch_levels": (C.c_int, [C.c_void_p, _P(AdsbAircraftLevel), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_bank_fetch_fused_levels": (C.c_int, [C.c_void_p, _P(AdsbFusedLevel), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_fixes_reserve": (C.c_int, [C.c_void_p, _P(AdsbSite)]),
+    "adsb_track_table_fetch_fixes": (C.c_int, [C.c_void_p, _P(AdsbFix), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_fixes_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "adsb_track_table_fetch_frame_fixes": (C.c_int, [C.c_void_p, _P(AdsbFrameFix), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_bank_fixes_reserve": (C.c_int, [C.c_void_p, _P(AdsbSite)]),
+    "adsb_track_bank_fetch_fixes": (C.c_int, [C.c_void_p, _P(AdsbFix), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_bank_fixes_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "adsb_track_bank_fetch_frame_fixes": (C.c_int, [C.c_void_p, _P(AdsbFrameFix), C.c_size_t, _P(C.c_size_t)]),
     "adsb_cpr_num_zones": (C.c_uint32, [C.c_double]),
     "adsb_cpr_position": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, _P(C.c_double),
                                     _P(C.c_double)]),
@@ -303,6 +353,7 @@ PROTOTYPES = {
     "adsb_host_frame_levels": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t,
                                          _P(AdsbFrameLevel)]),
     "adsb_level_dbfs": (C.c_double, [C.c_int, C.c_uint64, C.c_uint32]),
+    "adsb_host_fix_of": (C.c_int, [_P(AdsbSite), _P(C.c_uint8 * 14), C.c_double, _P(AdsbFix), _P(C.c_uint32)]),
 }
 
 _lib = None

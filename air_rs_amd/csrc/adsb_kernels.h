@@ -214,6 +214,8 @@ struct TrackStoreDev {
     uint32_t *slot;              // [n] scratch: record slot + 1 of each sorted frame's aircraft (kTrackUntracked)
     adsb_aircraft_level *lvl;    // [n_receivers x max_aircraft] beside rec, or null: no levels reserve (then admission
                                  // and expire touch nothing more than they did)
+    adsb_fix *fix;               // [n_receivers x max_aircraft] beside rec, or null: no fixes reserve (likewise)
+    const adsb_site *site;       // [n_receivers] with fix: the site receiver r's frames decode against
     // table only
     uint32_t *index;             // [1 << 24]: ICAO -> record slot + 1, 0 = absent
     // bank only
@@ -262,6 +264,22 @@ struct TrackLvlDev {
     void *temp;                  // the scan's scratch
     size_t temp_bytes;
 };
+// Positions from single messages (adsb_track_*_fixes_reserve; adsb_fix.h has the decode): all of it allocated by the
+// reserve.  One thread per sorted frame decodes into out / rem at the frame's list index; one segmented inclusive scan
+// over the sorted list carries, per aircraft, the sorted position + 1 of the later ACCEPTED position message (0 = none)
+// and saturating counts of accepted and rejected ones; one thread per segment tail merges into store->fix.
+struct TrackFixTuple {
+    uint32_t head;               // the operand holds a segment head
+    uint32_t newest, n_ok, n_rej;
+};
+struct FixRem;                   // adsb_fix.h: 16 bytes per frame
+struct TrackFixDev {
+    adsb_frame_fix *out;         // [max_frames]: one per frame of the last update, list order
+    FixRem *rem;                 // [max_frames]: the rest of what a fix takes from its frame, list order
+    TrackFixTuple *scan;         // [max_frames]: the scan's output, sorted order
+    void *temp;                  // the scan's scratch
+    size_t temp_bytes;
+};
 struct TrackArgs {
     const adsb_frame *frames;
     const adsb_packet_fields *fields;
@@ -282,6 +300,7 @@ struct TrackArgs {
     const TrackSumDev *sum;      // non-null (table / bank only): also the per-frame summaries and the changed list
     const adsb_frame_level *levels; // [n] (device), list order: with lvl non-null (and store->lvl), merged into the
     const TrackLvlDev *lvl;      // per-aircraft level records; null: the level records stay as they are
+    const TrackFixDev *fix;      // non-null (with store->fix and store->site): also the per-frame fixes and their merge
 };
 // expire (adsb_track_table_expire / adsb_track_bank_expire): a record survives unless last_heard < before[receiver]
 constexpr uint32_t kMaxReceivers = 256;
@@ -305,6 +324,9 @@ size_t track_summaries_temp_bytes(size_t n);
 size_t track_levels_temp_bytes(size_t n);
 // every level record of [0, places) empty: zeros, last_time NaN (the levels reserve)
 hipError_t launch_track_levels_clear(hipStream_t s, adsb_aircraft_level *lvl, size_t places);
+size_t track_fixes_temp_bytes(size_t n);
+// every fix of [0, places) empty: zeros, time NaN (the fixes reserve, and reset)
+hipError_t launch_track_fixes_clear(hipStream_t s, adsb_fix *fix, size_t places);
 // out[k] = rec[sum.changed[k]] for k < min(*sum.n_changed, max_n): the changed list's records, gathered on the device
 hipError_t launch_track_changed(hipStream_t s, const TrackRecord *rec, const TrackSumDev &sum, uint32_t max_n,
                                 TrackRecord *out);

@@ -81,12 +81,20 @@
 // Admission empties the level record of a place it admits, expire's compaction moves it with the record; both only when
 // the side array exists.  The fused view gets one adsb_fused_level per fused record from a kernel of its own after the
 // reduction: one thread per ICAO run picks the receiver with the greatest mean by exact cross-multiplication.
+//
+// Positions from single messages (adsb_track_*_fixes_reserve): a side array of one 64-byte adsb_fix per record place and
+// one site per receiver.  After 2., independent of 3.: one thread per frame decodes its bytes against its receiver's site
+// (adsb_fix.h: the locally unambiguous CPR decode, range and bearing; the text the CPU mirror compiles too), one
+// segmented inclusive scan (16-byte tuple) finds every segment's newest accepted position message and counts, one thread
+// per segment tail merges into the side record.  Admission empties the fix of a place it admits, expire's compaction
+// moves it with the record; both only when the side array exists.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
 #include <rocprim/rocprim.hpp>
 
+#include "adsb_fix.h"
 #include "adsb_kernels.h"
 
 namespace adsbk {
@@ -95,25 +103,7 @@ namespace {
 
 __device__ __forceinline__ double cpr_to_float(uint32_t cpr) { return (double)cpr / 131072.0; } // cpr.rs:22-25
 
-__device__ __forceinline__ uint32_t floor_as_u32(double x) // Rust `x.floor() as u32`: saturating, NaN -> 0
-{
-    const double f = floor(x);
-    if (!(f >= 0.0)) return 0u;
-    if (f >= 4294967295.0) return 4294967295u;
-    return (uint32_t)f;
-}
-
-__device__ uint32_t calc_num_zones(double lat) // cpr.rs:39-54
-{
-    if (lat == 0.0) return 59;
-    if (lat == 87.0 || lat == -87.0) return 2;
-    if (lat < -87.0 || lat > 87.0) return 1;
-    const double pi = 3.14159265358979323846264338327950288;
-    const double int1 = 1.0 - cos(pi / 30.0);
-    const double int2 = cos(pi / 180.0 * lat);
-    const double int3 = (2.0 * pi) / acos(1.0 - (int1 / (int2 * int2)));
-    return floor_as_u32(int3);
-}
+// calc_num_zones (cpr.rs:39-54), floor_as_u32 and me_bits: adsb_fix.h, shared with the single-message decode
 
 // cpr.rs:135-147 (+ 63-88, 90-127); first_is_odd: the older message's format
 __device__ bool geographic_position(uint32_t even_lat_u, uint32_t even_lon_u, uint32_t odd_lat_u, uint32_t odd_lon_u,
@@ -202,12 +192,6 @@ __device__ __forceinline__ uint32_t sat_add32(uint32_t a, uint32_t b)
 {
     const uint32_t c = a + b;
     return c < a ? ~0u : c;
-}
-
-// ME bits [first, first + width) of the 56-bit ME field (bit 0 = the top bit of frame byte 4)
-__device__ __forceinline__ uint32_t me_bits(uint64_t me, int first, int width)
-{
-    return (uint32_t)(me >> (56 - first - width)) & ((1u << width) - 1u);
 }
 
 // An airborne-velocity message (DF17 TC 19, ST 1-4; the header's decode rules) from the 14 frame bytes; false for
@@ -300,6 +284,7 @@ __global__ __launch_bounds__(256) void track_admit_kernel(const uint32_t *skeys,
     t.index[icao] = (uint32_t)r + 1u;
     t.rec[r] = empty_record(icao);
     if (t.lvl) t.lvl[r] = empty_level();
+    if (t.fix) ((FixWords *)t.fix)[r] = fix_empty();
 }
 
 // bank only: the receiver split clipped to the list (prefix[0] = 0, prefix[k] = n for k >= n_src), as adsb_fetch's
@@ -400,6 +385,7 @@ __global__ __launch_bounds__(256) void track_bank_admit_kernel(const uint32_t *s
         if (atomicCAS(&b.hash[h], 0ull, entry) == 0ull) break;
     b.rec[a] = empty_record(key & 0xFFFFFFu);
     if (b.lvl) b.lvl[a] = empty_level();
+    if (b.fix) ((FixWords *)b.fix)[a] = fix_empty();
     b.seg_slot[g] = a + 1u;
 }
 
@@ -787,6 +773,116 @@ __global__ __launch_bounds__(256) void track_levels_clear_kernel(adsb_aircraft_l
     if (p < places) lvl[p] = empty_level();
 }
 
+// ---- positions from single messages (table / bank with a fixes reserve) --------------------------------------------
+// One thread per sorted frame s, after the pairs kernel (which fixes a bank's d.slot): the frame's bytes decoded against
+// its receiver's site (adsb_fix.h) into out / rem at the frame's LIST index.  A frame of an aircraft the table turned
+// away gets its icao and nothing else, so the scan below counts nothing for it.
+template <TrackKind K>
+__global__ __launch_bounds__(256) void track_fix_decode_kernel(const adsb_frame *frames, const uint32_t *skeys,
+                                                               const uint32_t *svals, uint32_t n, TrackStoreDev d,
+                                                               TrackFixDev fx)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t i = svals[s]; // < n: a permutation of the list
+    const uint32_t r = K == TrackKind::kBank ? skeys[s] >> 24 : 0u; // < n_receivers (track_bank_keys_kernel)
+    adsb_frame_fix f;
+    FixRem rem;
+    fix_decode(d.site[r], frames[i].bytes, f, rem);
+    if (d.slot[s] == kTrackUntracked) {
+        const uint32_t icao = f.icao;
+        f = adsb_frame_fix{};
+        f.icao = icao;
+        rem = FixRem{};
+    }
+    fx.out[i] = f;
+    fx.rem[i] = rem;
+}
+
+// The scan's input at sorted position s, computed where the scan loads it from the frame's decoded flags
+struct FixInput {
+    const uint32_t *skeys, *svals;
+    const adsb_frame_fix *out;
+    __device__ __forceinline__ TrackFixTuple operator()(uint32_t s) const
+    {
+        const uint32_t flags = out[svals[s]].flags;
+        TrackFixTuple v;
+        v.head = (s == 0 || skeys[s - 1] != skeys[s]) ? 1u : 0u;
+        v.newest = (flags & ADSB_FIX_VALID) ? s + 1u : 0u;
+        v.n_ok = (flags & ADSB_FIX_VALID) ? 1u : 0u;
+        v.n_rej = (flags & ADSB_FIX_REJECTED) ? 1u : 0u;
+        return v;
+    }
+};
+
+// Segmented: a right operand that holds a segment head starts over; otherwise saturating sums and the later accepted
+// position (positions ascend, so the later one is the greater one).  Associative.
+struct FixOp {
+    __device__ __forceinline__ TrackFixTuple operator()(const TrackFixTuple &l, const TrackFixTuple &r) const
+    {
+        TrackFixTuple o = r;
+        if (!r.head) {
+            o.head = l.head;
+            o.newest = l.newest > r.newest ? l.newest : r.newest;
+            o.n_ok = sat_add32(l.n_ok, r.n_ok);
+            o.n_rej = sat_add32(l.n_rej, r.n_rej);
+        }
+        return o;
+    }
+};
+
+// One thread per segment tail with a position message: this update's part merged into the aircraft's fix
+template <TrackKind K>
+__global__ __launch_bounds__(256) void track_fix_merge_kernel(const adsb_frame *frames, const uint32_t *skeys,
+                                                              const uint32_t *svals, uint32_t n,
+                                                              double seconds_per_sample, uint64_t sample_base,
+                                                              TrackStoreDev d, TrackFixDev fx)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s];
+    if (s + 1 != n && skeys[s + 1] == key) return;
+    const uint32_t slot = d.slot[s];
+    if (slot == kTrackUntracked) return;
+    const TrackFixTuple w = fx.scan[s];
+    if (!w.n_ok && !w.n_rej) return; // no position message: the fix stays
+    if (K == TrackKind::kBank) sample_base = d.sample_base[key >> 24];
+    FixWords words = ((const FixWords *)d.fix)[slot - 1];
+    adsb_fix a;
+    __builtin_memcpy(&a, &words, sizeof(a));
+    if (w.newest) {
+        const uint32_t j = svals[w.newest - 1];
+        fix_take(a, fx.out[j], fx.rem[j], frame_time(frames, j, sample_base, seconds_per_sample));
+    }
+    a.n_fixes = sat_add32(a.n_fixes, w.n_ok);
+    a.n_rejected = sat_add32(a.n_rejected, w.n_rej);
+    __builtin_memcpy(&words, &a, sizeof(a));
+    ((FixWords *)d.fix)[slot - 1] = words;
+}
+
+template <TrackKind K>
+hipError_t launch_fix_merge(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d)
+{
+    const TrackFixDev &fx = *a.fix;
+    const dim3 grid((a.n + 255) / 256);
+    hipLaunchKernelGGL(track_fix_decode_kernel<K>, grid, dim3(256), 0, st, a.frames, (const uint32_t *)a.skeys,
+                       (const uint32_t *)a.svals, a.n, d, fx);
+    const auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u),
+                                                     FixInput{a.skeys, a.svals, fx.out});
+    size_t tb = fx.temp_bytes;
+    hipError_t e = rocprim::inclusive_scan(fx.temp, tb, in, fx.scan, (size_t)a.n, FixOp(), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(track_fix_merge_kernel<K>, grid, dim3(256), 0, st, a.frames, (const uint32_t *)a.skeys,
+                       (const uint32_t *)a.svals, a.n, a.seconds_per_sample, a.sample_base, d, fx);
+    return hipSuccess;
+}
+
+__global__ __launch_bounds__(256) void track_fixes_clear_kernel(FixWords *fix, uint64_t places)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < places) fix[p] = fix_empty();
+}
+
 // expire, 1: keep[g] = 1 for a record in use whose last frame is not older than the cut (last_heard < before evicts).
 // Record g is slot i of receiver r (a table: r = 0).  Slot 0 stages the old size where the compaction kernel reads it
 // (size_next[r]), since that kernel writes the new one; the pairs kernel of an update has consumed its own staging before
@@ -839,6 +935,7 @@ __global__ __launch_bounds__(256) void track_expire_compact_kernel(TrackStoreDev
     const TrackRecord moved = d.rec[base + lo];
     d.rec[g] = moved;
     if (d.lvl) d.lvl[g] = d.lvl[base + lo];
+    if (d.fix) ((FixWords *)d.fix)[g] = ((const FixWords *)d.fix)[base + lo];
     if (!kBank) d.index[moved.a.icao] = i + 1u;
 }
 
@@ -1206,6 +1303,22 @@ size_t track_levels_temp_bytes(size_t n)
     return scan_bytes + 256;
 }
 
+size_t track_fixes_temp_bytes(size_t n)
+{
+    size_t scan_bytes = 0;
+    (void)rocprim::inclusive_scan(nullptr, scan_bytes, (const TrackFixTuple *)nullptr, (TrackFixTuple *)nullptr, n,
+                                  FixOp(), (hipStream_t)0);
+    return scan_bytes + 256;
+}
+
+hipError_t launch_track_fixes_clear(hipStream_t st, adsb_fix *fix, size_t places)
+{
+    if (places == 0) return hipSuccess;
+    hipLaunchKernelGGL(track_fixes_clear_kernel, dim3((uint32_t)((places + 255) / 256)), dim3(256), 0, st,
+                       (FixWords *)fix, (uint64_t)places);
+    return hipGetLastError();
+}
+
 hipError_t launch_track_levels_clear(hipStream_t st, adsb_aircraft_level *lvl, size_t places)
 {
     if (places == 0) return hipSuccess;
@@ -1238,6 +1351,8 @@ hipError_t track_tail(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d
     hipError_t e = hipSuccess;
     if constexpr (kStore) {
         if (a.lvl && d.lvl) e = launch_levels_merge<K>(st, a, d); // needs d.slot only: independent of the record merge
+        if (e != hipSuccess) return e;
+        if (a.fix && d.fix) e = launch_fix_merge<K>(st, a, d); // needs d.slot and the frame bytes only
         if (e != hipSuccess) return e;
         if (a.sum) e = launch_frame_summaries<K>(st, a, d); // before the merge
     } else {

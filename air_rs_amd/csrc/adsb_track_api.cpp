@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "adsb_ctx.h"
+#include "adsb_fix.h"
 
 using adsbk::TrackKind;
 using adsbk::TrackRecord;
@@ -127,6 +128,8 @@ struct TrackStore {
     adsbk::TrackLvlDev lvl{};
     adsb_frame_level *lvl_frames = nullptr; // [max_frames]: device copy of a host levels array
     adsb_frame_level *lvl_pinned = nullptr; // [max_frames]: pinned staging of that copy (s.copied covers it too)
+    // positions from single messages (adsb_track_*_fixes_reserve): all of it allocated by the reserve; dev.fix null = none
+    adsbk::TrackFixDev fix{};
 
     size_t places() const { return (size_t)n_receivers * max_aircraft; }
 };
@@ -164,6 +167,14 @@ static void track_levels_free(TrackStore &s)
     s.dev.lvl = nullptr;
     s.lvl = adsbk::TrackLvlDev{};
     s.lvl_frames = s.lvl_pinned = nullptr;
+}
+
+static void track_fixes_free(TrackStore &s)
+{
+    free_all({s.dev.fix, (void *)s.dev.site, s.fix.out, s.fix.rem, s.fix.scan, s.fix.temp});
+    s.dev.fix = nullptr;
+    s.dev.site = nullptr;
+    s.fix = adsbk::TrackFixDev{};
 }
 
 static void track_summaries_free(TrackSummaries &s)
@@ -212,6 +223,7 @@ static void store_release(TrackStore &s)
     (void)hipStreamSynchronize(s.ctx->aux);
     track_summaries_free(s.sum);
     track_levels_free(s);
+    track_fixes_free(s);
     free_all({s.dev.rec, s.words, s.dev.slot, s.dev.index, s.dev.hash, s.dev.prefix, s.dev.mark, s.dev.excl,
               s.dev.seg_slot, s.u32, s.temp, s.frames, s.fields, s.points, s.exp_u32, s.exp_temp});
     if (s.pinned) (void)hipHostFree(s.pinned);
@@ -227,6 +239,7 @@ static int store_reset(TrackStore *s)
     else
         HIPCHK(hipMemsetAsync(s->dev.hash, 0, sizeof(unsigned long long) * (s->dev.hash_mask + 1), s->ctx->aux));
     HIPCHK(hipMemsetAsync(s->words, 0, sizeof(uint32_t) * 3 * s->n_receivers, s->ctx->aux));
+    if (s->dev.fix) HIPCHK(adsbk::launch_track_fixes_clear(s->ctx->aux, s->dev.fix, s->places()));
     s->n_points = 0;
     s->updated = false;
     s->sum.updated = s->sum.changed_valid = false;
@@ -298,6 +311,7 @@ static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t s
     a.sum = s.sum.dev.out ? &s.sum.dev : nullptr;
     a.levels = levels;
     a.lvl = levels ? &s.lvl : nullptr;
+    a.fix = dev.fix ? &s.fix : nullptr;
     HIPCHK(adsbk::launch_track(s.ctx->aux, a));
     return ADSB_OK;
 }
@@ -486,11 +500,14 @@ static int store_levels_reserve(TrackStore *st)
     return ADSB_OK;
 }
 
-// Waits.  As store_fetch, receiver by receiver in ascending ICAO: the level record beside each record.
-static int store_fetch_levels(TrackStore *s, adsb_aircraft_level *out, size_t max, size_t *n)
+// Waits.  As store_fetch, receiver by receiver in ascending ICAO: the side record (a level record, a fix) beside each
+// record; side: the store's device array of them, one per place.
+template <class T>
+static int store_fetch_side(TrackStore *s, T *side_of(TrackStore &), T *out, size_t max, size_t *n)
 {
     if (!s || (!out && max)) return ADSB_E_ARG;
-    if (!s->dev.lvl) return ADSB_E_STATE;
+    const T *side = side_of(*s);
+    if (!side) return ADSB_E_STATE;
     adsb_ctx *c = s->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
     const uint32_t nr = s->n_receivers;
@@ -499,7 +516,7 @@ static int store_fetch_levels(TrackStore *s, adsb_aircraft_level *out, size_t ma
     HIPCHK(hipStreamSynchronize(c->aux));
     size_t total = 0, copied = 0;
     std::vector<TrackRecord> recs;
-    std::vector<adsb_aircraft_level> lv;
+    std::vector<T> lv;
     std::vector<uint32_t> order;
     for (uint32_t r = 0; r < nr; ++r) {
         const size_t size = std::min<uint32_t>(w[r], s->max_aircraft);
@@ -511,7 +528,7 @@ static int store_fetch_levels(TrackStore *s, adsb_aircraft_level *out, size_t ma
             order.resize(size);
             HIPCHK(hipMemcpyAsync(recs.data(), s->dev.rec + (size_t)r * s->max_aircraft, sizeof(TrackRecord) * size,
                                   hipMemcpyDeviceToHost, c->aux));
-            HIPCHK(hipMemcpyAsync(lv.data(), s->dev.lvl + (size_t)r * s->max_aircraft, sizeof(adsb_aircraft_level) * size,
+            HIPCHK(hipMemcpyAsync((void *)lv.data(), side + (size_t)r * s->max_aircraft, sizeof(T) * size,
                                   hipMemcpyDeviceToHost, c->aux));
             HIPCHK(hipStreamSynchronize(c->aux));
             for (size_t k = 0; k < size; ++k) order[k] = (uint32_t)k;
@@ -522,6 +539,74 @@ static int store_fetch_levels(TrackStore *s, adsb_aircraft_level *out, size_t ma
         copied += take;
     }
     if (n) *n = total;
+    return ADSB_OK;
+}
+
+static adsb_aircraft_level *levels_of(TrackStore &s) { return s.dev.lvl; }
+static adsb_fix *fixes_of(TrackStore &s) { return s.dev.fix; }
+
+static int store_fetch_levels(TrackStore *s, adsb_aircraft_level *out, size_t max, size_t *n)
+{
+    return store_fetch_side(s, levels_of, out, max, n);
+}
+
+// ---- positions from single messages -----------------------------------------------------------------------------------
+// sites: [n_receivers], checked by the caller.  Waits for the device (the sizes, hipMalloc, the clear).
+static int store_fixes_reserve(TrackStore *st, const adsb_site *sites)
+{
+    adsb_ctx *c = st->ctx;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const uint32_t nr = st->n_receivers;
+    std::vector<uint32_t> sizes(nr);
+    HIPCHK(hipMemcpyAsync(sizes.data(), st->words, sizeof(uint32_t) * nr, hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    for (uint32_t r = 0; r < nr; ++r)
+        if (sizes[r] != 0) return ADSB_E_STATE; // its aircraft's fixes would miss the frames heard so far
+    if (!st->dev.fix) {
+        const size_t nf = (size_t)st->max_frames;
+        st->fix.temp_bytes = adsbk::track_fixes_temp_bytes(nf);
+        const bool ok = hipMalloc((void **)&st->dev.fix, sizeof(adsb_fix) * st->places()) == hipSuccess &&
+                        hipMalloc((void **)&st->dev.site, sizeof(adsb_site) * nr) == hipSuccess &&
+                        hipMalloc((void **)&st->fix.out, sizeof(adsb_frame_fix) * nf) == hipSuccess &&
+                        hipMalloc((void **)&st->fix.rem, sizeof(adsbk::FixRem) * nf) == hipSuccess &&
+                        hipMalloc((void **)&st->fix.scan, sizeof(adsbk::TrackFixTuple) * nf) == hipSuccess &&
+                        hipMalloc(&st->fix.temp, st->fix.temp_bytes) == hipSuccess &&
+                        adsbk::launch_track_fixes_clear(c->aux, st->dev.fix, st->places()) == hipSuccess &&
+                        hipStreamSynchronize(c->aux) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            track_fixes_free(*st);
+            return ADSB_E_NOMEM;
+        }
+    }
+    // the stream is idle: a plain copy from the caller's array
+    HIPCHK(hipMemcpy((void *)st->dev.site, sites, sizeof(adsb_site) * nr, hipMemcpyHostToDevice));
+    return ADSB_OK;
+}
+
+static int store_fetch_fixes(TrackStore *s, adsb_fix *out, size_t max, size_t *n)
+{
+    return store_fetch_side(s, fixes_of, out, max, n);
+}
+
+static int store_fixes_device(TrackStore *s, const adsb_fix **dev)
+{
+    if (!s) return ADSB_E_ARG;
+    if (!s->dev.fix) return ADSB_E_STATE;
+    if (dev) *dev = s->dev.fix;
+    return ADSB_OK;
+}
+
+// Waits; the last update's per-frame fixes, as store_fetch_points
+static int store_fetch_frame_fixes(TrackStore *s, adsb_frame_fix *out, size_t max, size_t *n)
+{
+    if (!s || (!out && max)) return ADSB_E_ARG;
+    if (!s->dev.fix || !s->updated) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(s->ctx->cfg.device));
+    const size_t take = std::min<size_t>(s->n_points, max);
+    if (take) HIPCHK(hipMemcpyAsync(out, s->fix.out, sizeof(adsb_frame_fix) * take, hipMemcpyDeviceToHost, s->ctx->aux));
+    HIPCHK(hipStreamSynchronize(s->ctx->aux));
+    if (n) *n = take;
     return ADSB_OK;
 }
 
@@ -609,6 +694,27 @@ extern "C" int adsb_track_table_fetch_levels(adsb_track_table *t, adsb_aircraft_
 extern "C" int adsb_track_table_levels_device(adsb_track_table *t, const adsb_aircraft_level **dev)
 {
     return store_levels_device(t, dev);
+}
+
+extern "C" int adsb_track_table_fixes_reserve(adsb_track_table *t, const adsb_site *site)
+{
+    if (!t || !site || !adsbk::fix_site_ok(*site)) return ADSB_E_ARG; // before the handle is read
+    return store_fixes_reserve(t, site);
+}
+
+extern "C" int adsb_track_table_fetch_fixes(adsb_track_table *t, adsb_fix *out, size_t max, size_t *n)
+{
+    return store_fetch_fixes(t, out, max, n);
+}
+
+extern "C" int adsb_track_table_fixes_device(adsb_track_table *t, const adsb_fix **dev)
+{
+    return store_fixes_device(t, dev);
+}
+
+extern "C" int adsb_track_table_fetch_frame_fixes(adsb_track_table *t, adsb_frame_fix *out, size_t max, size_t *n)
+{
+    return store_fetch_frame_fixes(t, out, max, n);
 }
 
 extern "C" int adsb_track_table_summaries_reserve(adsb_track_table *t) { return store_summaries_reserve(t); }
@@ -875,6 +981,29 @@ extern "C" int adsb_track_bank_fetch(adsb_track_bank *b, adsb_aircraft_record *a
 }
 
 extern "C" int adsb_track_bank_expire(adsb_track_bank *b, const double *before) { return store_expire(b, before); }
+
+extern "C" int adsb_track_bank_fixes_reserve(adsb_track_bank *b, const adsb_site *sites)
+{
+    if (!b || !sites) return ADSB_E_ARG;
+    for (uint32_t r = 0; r < b->n_receivers; ++r)
+        if (!adsbk::fix_site_ok(sites[r])) return ADSB_E_ARG;
+    return store_fixes_reserve(b, sites);
+}
+
+extern "C" int adsb_track_bank_fetch_fixes(adsb_track_bank *b, adsb_fix *out, size_t max, size_t *n)
+{
+    return store_fetch_fixes(b, out, max, n);
+}
+
+extern "C" int adsb_track_bank_fixes_device(adsb_track_bank *b, const adsb_fix **dev)
+{
+    return store_fixes_device(b, dev);
+}
+
+extern "C" int adsb_track_bank_fetch_frame_fixes(adsb_track_bank *b, adsb_frame_fix *out, size_t max, size_t *n)
+{
+    return store_fetch_frame_fixes(b, out, max, n);
+}
 
 extern "C" int adsb_track_bank_summaries_reserve(adsb_track_bank *b) { return store_summaries_reserve(b); }
 

@@ -27,6 +27,7 @@ LEVEL_DTYPE = np.dtype([("signal_sum", "<u8"), ("noise_sum", "<u8"), ("peak", "<
 assert LEVEL_DTYPE.itemsize == C.sizeof(L.AdsbFrameLevel) == 32
 LEVEL_PULSE_SAMPLES, LEVEL_QUIET_SAMPLES = 116, 124  # of a frame's 240: what signal_sum and noise_sum add up
 
+SITE, FIX_DTYPE, FRAME_FIX_DTYPE = L.SITE, L.FIX_DTYPE, L.FRAME_FIX_DTYPE  # fixes_reserve / fixes / frame_fixes
 WINDOW = 240  # 16 preamble + 112*2 samples (reference src/adsb.rs:98)
 
 
@@ -72,6 +73,33 @@ def host_frame_levels(iq, frames, first_sample=0):
                                             frames.ctypes.data if len(frames) else None, len(frames),
                                             out.ctypes.data_as(C.POINTER(L.AdsbFrameLevel))), "adsb_host_frame_levels")
     return out[:len(frames)].copy()
+
+
+def _sites(sites, n):
+    """n sites as a SITE array: a SITE array, or (latitude, longitude[, max_range_nm = 180]) tuples."""
+    if isinstance(sites, np.ndarray) and sites.dtype == SITE:
+        out = np.ascontiguousarray(sites).reshape(-1)
+    else:
+        out = np.zeros(len(sites), dtype=SITE)
+        for k, site in enumerate(sites):
+            site = tuple(site)
+            out[k] = (site[0], site[1], site[2] if len(site) > 2 else 180.0)
+    if len(out) != n:
+        raise ValueError(f"sites: {len(out)} for {n} receivers")
+    return out
+
+
+def host_fix_of(site, frame_bytes, time=0.0):
+    """adsb_host_fix_of, the CPU mirror of a fixes reserve's per-frame decode: (FIX_DTYPE record of an aircraft whose
+    only frame is this one, heard at `time` from `site`; the frame's FRAME_FIX_DTYPE flags).  site: (latitude,
+    longitude[, max_range_nm = 180]) or a SITE record.  Needs no device."""
+    s = _sites(site.reshape(-1) if isinstance(site, np.ndarray) else [site], 1)
+    b = (C.c_uint8 * 14)(*bytes(frame_bytes))
+    out = np.zeros(1, dtype=FIX_DTYPE)
+    flags = C.c_uint32()
+    L.check(L.load().adsb_host_fix_of(s.ctypes.data_as(C.POINTER(L.AdsbSite)), C.byref(b), float(time),
+                                      out.ctypes.data_as(C.POINTER(L.AdsbFix)), C.byref(flags)), "adsb_host_fix_of")
+    return out[0], flags.value
 
 
 def level_dbfs(sample_type, total, n_samples):
@@ -677,6 +705,21 @@ class _TrackStore:
         self._call("levels_device", C.byref(dev))
         return dev.value
 
+    def _fixes_reserve(self, sites, n):
+        s = _sites(sites, n)
+        self._call("fixes_reserve", s.ctypes.data_as(C.POINTER(L.AdsbSite)))
+
+    def fixes_device(self):
+        """Device address of the fixes, one per record place in slot order (as levels_device); no synchronisation."""
+        dev = C.c_void_p()
+        self._call("fixes_device", C.byref(dev))
+        return dev.value
+
+    def frame_fixes(self):
+        """One FRAME_FIX_DTYPE record per frame of the last update, in its list order: the frame's own position from its
+        receiver's site, ADSB_FIX_REJECTED if it was turned away, flags 0 if it is no position message."""
+        return self._fetch("fetch_frame_fixes", [FRAME_FIX_DTYPE], size=self.max_frames)[0]
+
     @staticmethod
     def _host_levels(levels, n):
         """A host LEVEL_DTYPE array of n records -> (the array to keep alive, its address or None)."""
@@ -717,6 +760,17 @@ class TrackTable(_TrackStore):
     def levels(self):
         """AIRCRAFT_LEVEL_DTYPE records (each aircraft's signal level), aligned with aircraft()[0]."""
         return self._fetch("fetch_levels", [AIRCRAFT_LEVEL_DTYPE])[0]
+
+    def fixes_reserve(self, site):
+        """adsb_track_table_fixes_reserve: from now on every update also decodes each position message on its own
+        against `site` ((latitude, longitude[, max_range_nm = 180]) or a SITE record) and keeps the newest fix per
+        aircraft.  The table must hold no aircraft."""
+        self._fixes_reserve(site.reshape(-1) if isinstance(site, np.ndarray) else [site], 1)
+
+    def fixes(self):
+        """FIX_DTYPE records (each aircraft's newest single-message position, with range and bearing from the site),
+        aligned with aircraft()[0]."""
+        return self._fetch("fetch_fixes", [FIX_DTYPE])[0]
 
     def aircraft(self):
         """(AIRCRAFT_DTYPE records of the whole table in ascending ICAO, table flags)."""
@@ -830,6 +884,15 @@ class TrackBank(_TrackStore):
     def levels(self):
         """list of n_receivers AIRCRAFT_LEVEL_DTYPE arrays, aligned with aircraft()[0]."""
         return self._aligned("fetch_levels", AIRCRAFT_LEVEL_DTYPE)
+
+    def fixes_reserve(self, sites):
+        """adsb_track_bank_fixes_reserve: as TrackTable.fixes_reserve with one site per receiver (a SITE array or a
+        sequence of (latitude, longitude[, max_range_nm = 180]))."""
+        self._fixes_reserve(sites, self.n_receivers)
+
+    def fixes(self):
+        """list of n_receivers FIX_DTYPE arrays, aligned with aircraft()[0]."""
+        return self._aligned("fetch_fixes", FIX_DTYPE)
 
     def fused_levels(self):
         """FUSED_LEVEL_DTYPE records of the last fuse_async() / fuse(), one per fused record in the same order; needs

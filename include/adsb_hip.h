@@ -705,6 +705,98 @@ typedef struct adsb_fused_level {     /* 96 bytes, one per fused record, same or
 int adsb_track_bank_fetch_fused_levels(adsb_track_bank *bank, adsb_fused_level *out, size_t max, size_t *n);
 
 /*
+ * Positions from single messages, relative to the receiver site.  The records' position needs an even and an odd
+ * airborne message within 10 s (the reference's calculate_geographic_position).  With a fixes reserve a table or bank
+ * also decodes every position message ON ITS OWN against the site of the receiver that heard it (the locally
+ * unambiguous CPR decode), and keeps the newest such fix per aircraft in one 64-byte adsb_fix beside its record, with
+ * range and bearing from the site.  That also covers what the pair decode never reports: aircraft heard with one CPR
+ * format only, surface messages (TC 5-8, with ground speed and track) and airborne messages with GNSS height (TC 20-22).
+ *
+ * A frame is a POSITION MESSAGE if DF = 17 and TC is 5-8 (surface), 9-18 or 20-22 (airborne).  With ME bit 0 the top
+ * bit of frame byte 4: F (odd) = ME bit 21, lat_cpr = ME bits 22-38, lon_cpr = ME bits 39-55.  y = lat_cpr / 2^17,
+ * x = lon_cpr / 2^17, span = 360 (airborne) or 90 (surface), i = F, mod(a, b) = a - b floor(a / b), site (lat_s, lon_s):
+ *     dLat = span / (60 - i)
+ *     j    = floor(lat_s / dLat) + floor(0.5 + mod(lat_s, dLat) / dLat - y)
+ *     lat  = dLat (j + y)
+ *     dLon = span / max(NL(lat) - i, 1)                NL: the number of longitude zones (cpr.rs:39-54)
+ *     m    = floor(lon_s / dLon) + floor(0.5 + mod(lon_s, dLon) / dLon - x)
+ *     lon  = dLon (m + x), brought into [-180, 180] (cpr.rs:27-31)
+ * range = haversine distance from the site in nautical miles (R = 3440.065 NM), bearing = the initial bearing
+ * atan2(sin dl cos p2, cos p1 sin p2 - sin p1 cos p2 cos dl) in degrees in [0, 360); all of it f64, each rounded to
+ * f32 once.  The frame is REJECTED (counted in n_rejected, the fix stays) if |lat| > 90 or the range exceeds the
+ * site's limit: max_range_nm for an airborne message, min(max_range_nm, 45) for a surface one.  The decode picks the
+ * position nearest the site among those half a zone apart, so it is right only for aircraft within half a zone: 180 NM
+ * airborne, 45 NM surface; hence max_range_nm must lie in (0, 180].
+ * Surface messages: movement = ME bits 5-11: 0 and 125-127 no speed; 1: 0 kt; 2-8: 0.125 + (m - 2) 0.125; 9-12:
+ * 1 + (m - 9) 0.25; 13-38: 2 + (m - 13) 0.5; 39-93: 15 + (m - 39); 94-108: 70 + (m - 94) 2; 109-123:
+ * 100 + (m - 109) 5; 124: 175 kt.  ME bit 12 set: track = ME bits 13-19 x 360 / 128 degrees.  TC 9-18 carry the
+ * altitude of the field decode (adsb_packet_fields.altitude); TC 20-22 carry none here (ADSB_FIX_ALT clear).
+ *
+ * The NEWEST accepted position message wins (the last one in list order); n_fixes and n_rejected are saturating sums
+ * over the aircraft's frames since admission.  An aircraft's fix is EMPTY (time NaN, all else zero) at admission, at
+ * re-admission after an expire and after a reset; expire moves a survivor's fix with its record.  A frame's decode
+ * depends on the frame and the site only and the merge is associative, so one list cut into any sequence of updates
+ * gives the same 64 bytes per aircraft, and receiver r of a bank equals a table with receiver r's site.
+ * With a reserve every form of update (update, update_levels, update_launch*, host or device lists) also merges the
+ * fixes.  On the device, after the pairs step: one thread per frame decodes from the frame bytes into one
+ * adsb_frame_fix (and 16 bytes more), one segmented inclusive scan over the sorted list (rocPRIM, a 16-byte tuple:
+ * head mark, later accepted position, saturating counts) and one thread per segment tail that merges into the side
+ * record: linear in the list however long one aircraft's part is, no atomics.  Device memory, all of it allocated by
+ * the reserve: 64 bytes per place of n_receivers x max_aircraft, 24 bytes per receiver, and 64 bytes per frame of
+ * max_frames plus rocPRIM's scan scratch.  A store that never reserves allocates nothing, launches exactly the
+ * kernels it launched before, and records, points, velocity, levels and summaries are the same bytes either way.  The
+ * fused view carries no fixes.
+ */
+typedef struct adsb_site {           /* a receiver's position and how far it trusts a local decode */
+    double latitude, longitude;      /* degrees, [-90, 90] and [-180, 180] */
+    double max_range_nm;             /* (0, 180] */
+} adsb_site;
+#define ADSB_FIX_VALID    0x1u  /* the record holds a fix                          */
+#define ADSB_FIX_SURFACE  0x2u  /* from a surface message (TC 5-8)                 */
+#define ADSB_FIX_ALT      0x4u  /* altitude holds a value (TC 9-18)                */
+#define ADSB_FIX_SPEED    0x8u  /* ground_speed_kt holds a value (surface)         */
+#define ADSB_FIX_TRACK    0x10u /* track_deg holds a value (surface)               */
+#define ADSB_FIX_REJECTED 0x20u /* adsb_frame_fix only: a position message turned away (then nothing else is set but
+                                   ADSB_FIX_SURFACE, and the position fields are 0) */
+typedef struct adsb_fix {            /* 64 bytes, one per record place, beside the 128-byte record */
+    double   time;                   /* table frame time of the message this fix came from; NaN if none yet */
+    double   latitude, longitude;    /* degrees */
+    float    range_nm, bearing_deg;  /* from the site */
+    float    ground_speed_kt, track_deg; /* surface only; 0 unless flagged */
+    int32_t  altitude;               /* feet; 0 unless ADSB_FIX_ALT */
+    uint32_t n_fixes, n_rejected;    /* saturating, since admission */
+    uint8_t  type_code, flags, cpr_odd, reserved8;
+    uint32_t reserved;               /* 0; the four bytes of padding after it are 0 too */
+} adsb_fix;
+typedef struct adsb_frame_fix {      /* 32 bytes, one per frame of the last update, in its order */
+    double   latitude, longitude;
+    float    range_nm, bearing_deg;
+    uint32_t icao;
+    uint32_t flags;                  /* ADSB_FIX_*; 0: no position message, or an aircraft the full table turned away */
+} adsb_frame_fix;
+/* Allocates the above, keeps the site and empties every fix.  Waits for the device.  On a store that holds no aircraft
+ * (new, or after a reset) a repeated reserve replaces the site.  ADSB_E_ARG for a NULL table or site, a NaN in the
+ * site, a latitude outside [-90, 90], a longitude outside [-180, 180] or a range outside (0, 180] (all checked before
+ * the table is touched); ADSB_E_STATE if the table holds aircraft; ADSB_E_NOMEM if the memory is not to be had. */
+int adsb_track_table_fixes_reserve(adsb_track_table *table, const adsb_site *site);
+/* Waits; one fix per aircraft, in exactly the order adsb_track_table_fetch returns the records (ascending ICAO);
+ * *n = records held even if more than max.  ADSB_E_ARG for a NULL table, or NULL out with max > 0; ADSB_E_STATE
+ * without a reserve. */
+int adsb_track_table_fetch_fixes(adsb_track_table *table, adsb_fix *out, size_t max, size_t *n);
+/* Does not synchronise: the device address of the fixes, one per record PLACE in slot order (as
+ * adsb_track_table_levels_device); dev may be NULL.  ADSB_E_ARG for a NULL table, ADSB_E_STATE without a reserve. */
+int adsb_track_table_fixes_device(adsb_track_table *table, const adsb_fix **dev);
+/* Waits; one adsb_frame_fix per frame of the last update, in its list order, as adsb_track_table_fetch_points: copies
+ * min(frames, max), *n = copied.  ADSB_E_STATE without a reserve or before the first update. */
+int adsb_track_table_fetch_frame_fixes(adsb_track_table *table, adsb_frame_fix *out, size_t max, size_t *n);
+/* The same for a bank: sites[n_receivers], receiver r's frames decode against sites[r]; fetch_fixes receiver by
+ * receiver, each in ascending ICAO, as adsb_track_bank_fetch. */
+int adsb_track_bank_fixes_reserve(adsb_track_bank *bank, const adsb_site *sites);
+int adsb_track_bank_fetch_fixes(adsb_track_bank *bank, adsb_fix *out, size_t max, size_t *n);
+int adsb_track_bank_fixes_device(adsb_track_bank *bank, const adsb_fix **dev);
+int adsb_track_bank_fetch_frame_fixes(adsb_track_bank *bank, adsb_frame_fix *out, size_t max, size_t *n);
+
+/*
  * ---- several GPUs behind one call ---------------------------------------------------------
  * The reference's thread 2 is one function on one thread (src/adsb.rs:92, spawned at adsb.rs:147); a group is the
  * drop-in for that function when the buffer should be spread over N devices: one context per member, the offsets

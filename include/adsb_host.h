@@ -112,6 +112,16 @@ int adsb_host_frame_levels(int sample_type, const void *iq, size_t n_samples, ui
  * sample_type or n_samples == 0.  adsb_level_dbfs(st, level.signal_sum, 116) and (st, level.noise_sum, 124). */
 double adsb_level_dbfs(int sample_type, uint64_t sum, uint32_t n_samples);
 
+/*
+ * CPU mirror of the per-frame fix decode of a table or bank with a fixes reserve (adsb_hip.h, "Positions from single
+ * messages"): the same program text as the device's, no device needed.  *out = the adsb_fix of an aircraft whose only
+ * frame since admission is this one, heard at frame time `time` by a receiver at *site: accepted: the fix with
+ * n_fixes = 1; rejected: the empty fix with n_rejected = 1; no position message: the empty fix.  *frame_flags
+ * (optional) = the frame's adsb_frame_fix.flags.  ADSB_E_ARG for a NULL site, bytes or out, or a site that
+ * adsb_track_table_fixes_reserve would refuse.
+ */
+int adsb_host_fix_of(const adsb_site *site, const uint8_t bytes[14], double time, adsb_fix *out, uint32_t *frame_flags);
+
 /* ---- behind the channel: tracker + CPR ------------------------------------------- */
 
 /* cpr.rs:39-54 calc_num_zones; cpr.rs:135-147 calculate_geographic_position (returns 1 = Some, 0 = None).

@@ -9,6 +9,7 @@
   tools/replay.py capture.c16 --web           # what the web thread broadcasts instead: one JSON line per packet
   tools/replay.py capture.c16 --levels        # signal and noise power of every packet instead, tab-separated
   tools/replay.py capture.c16 --aircraft --levels   # the aircraft table with two more columns: RSSI and SNR
+  tools/replay.py capture.c16 --aircraft --site 51.5,-0.1      # ... with five more: each aircraft's own fix from the site
 
 Everything below the argument parsing is one call through the C ABI (adsb_replay_file, include/adsb_host.h).
 The "Processed Time" line carries no value (the reference prints the wall clock there).  With --aircraft, the frames
@@ -25,7 +26,13 @@ device memory (adsb_levels_of), in overlapping pieces if the capture is large.  
 update also merges every frame's level record (the host mirror's, adsb_host_frame_levels) into the aircraft's level
 record on the device, and two columns are appended: RSSI, the aircraft's mean signal power in dBFS over its 116 x
 n_levels pulse samples, and SNR, that minus its mean noise power in dBFS over 124 x n_levels quiet samples, one decimal,
-"n/a" in both for an aircraft without a counted frame; --aircraft alone prints what it always printed.  The TEXT has not been compared with a Rust build's (there is no
+"n/a" in both for an aircraft without a counted frame; --aircraft alone prints what it always printed.  With --aircraft
+--site LAT,LON[,RANGE_NM] (degrees, nautical miles; default range 180) the table gets a fixes reserve with that receiver
+site and five columns are appended (after RSSI and SNR if both are asked for): FixLat and FixLon, the position of the
+aircraft's newest position message decoded on its own against the site (six decimals; this also covers surface
+messages and aircraft heard with one CPR format only, which Latitude and Longitude never show), Range in nautical miles
+and Bearing in degrees from the site (one decimal), and GS, a surface message's ground speed in knots (one decimal);
+"n/a" for a missing value (write a negative latitude as --site=-33.9,151.2).  The TEXT has not been compared with a Rust build's (there is no
 Rust toolchain); only the values are checked, against the oracle."""
 import argparse
 import json
@@ -57,11 +64,31 @@ def level_columns(st, lv):
     return [f"{sig:.1f}", f"{sig - noise:.1f}"]
 
 
-def aircraft_table(d, frames, n_samples, st=None, frame_levels=None):
+def parse_site(text):
+    """LAT,LON[,RANGE_NM] -> (latitude, longitude, max_range_nm)"""
+    parts = [float(x) for x in text.split(",")]
+    if len(parts) not in (2, 3):
+        raise argparse.ArgumentTypeError("expected LAT,LON[,RANGE_NM]")
+    return (parts[0], parts[1], parts[2] if len(parts) == 3 else 180.0)
+
+
+def fix_columns(fx):
+    """FixLat, FixLon, Range, Bearing and GS of one FIX_DTYPE record."""
+    if not fx["flags"] & A.ADSB_FIX_VALID:
+        return ["n/a"] * 5
+    return [f"{float(fx['latitude']):.6f}", f"{float(fx['longitude']):.6f}", f"{float(fx['range_nm']):.1f}",
+            f"{float(fx['bearing_deg']):.1f}",
+            f"{float(fx['ground_speed_kt']):.1f}" if fx["flags"] & A.ADSB_FIX_SPEED else "n/a"]
+
+
+def aircraft_table(d, frames, n_samples, st=None, frame_levels=None, site=None):
     """The capture's final aircraft table as tab-separated text: tui.rs:95's columns, rows by age (tui.rs:69), then
     ICAO.  Age = whole seconds from each aircraft's last frame to the end of the capture.  frame_levels (one
-    LEVEL_DTYPE record per frame, with st the sample type): also the columns RSSI and SNR."""
+    LEVEL_DTYPE record per frame, with st the sample type): also the columns RSSI and SNR.  site ((latitude, longitude,
+    max_range_nm)): also FixLat, FixLon, Range, Bearing and GS."""
     with A.TrackTable(d, max_frames=max(len(frames), 1), seconds_per_sample=SECONDS_PER_SAMPLE) as t:
+        if site is not None:
+            t.fixes_reserve(site)
         if frame_levels is None:
             t.update(frames)
         else:
@@ -70,9 +97,10 @@ def aircraft_table(d, frames, n_samples, st=None, frame_levels=None):
         recs, _ = t.aircraft()
         vel, heard = t.velocity(), t.last_heard()
         levels = [None] * len(recs) if frame_levels is None else t.levels()
+        fixes = [None] * len(recs) if site is None else t.fixes()
     now = n_samples * SECONDS_PER_SAMPLE
     rows = []
-    for rec, v, lh, lv in zip(recs, vel, heard, levels):
+    for rec, v, lh, lv, fx in zip(recs, vel, heard, levels, fixes):
         pos, age = bool(rec["has_position"]), int(now - lh)
         rows.append((age, int(rec["icao"]), "\t".join([
             f"{int(rec['icao']):x}",
@@ -81,9 +109,10 @@ def aircraft_table(d, frames, n_samples, st=None, frame_levels=None):
             f"{float(rec['latitude']):.6f}" if pos else "n/a",
             f"{float(rec['longitude']):.6f}" if pos else "n/a",
             f"{float(v['speed_kt']):.0f}" if v["flags"] & A.ADSB_VELOCITY_SPEED else "n/a",
-            f"{age}"] + ([] if lv is None else level_columns(st, lv)))))
+            f"{age}"] + ([] if lv is None else level_columns(st, lv)) + ([] if fx is None else fix_columns(fx)))))
     rows.sort(key=lambda r: (r[0], r[1]))
     head = "ICAO\tCallsign\tAltitude\tLatitude\tLongitude\tVelocity\tAge" + ("" if frame_levels is None else "\tRSSI\tSNR")
+    head += "" if site is None else "\tFixLat\tFixLon\tRange\tBearing\tGS"
     return head + "\n" + "".join(r[2] + "\n" for r in rows)
 
 
@@ -162,7 +191,11 @@ def main():
     ap.add_argument("--aircraft", action="store_true", help="print the final aircraft table instead of the stream text")
     ap.add_argument("--web", action="store_true", help="print one AircraftSummary JSON line per packet instead")
     ap.add_argument("--levels", action="store_true", help="print signal and noise power of every packet instead; with --aircraft: two more columns, RSSI and SNR")
+    ap.add_argument("--site", type=parse_site, default=None, metavar="LAT,LON[,RANGE_NM]",
+                    help="with --aircraft: the receiver's position; five more columns: FixLat, FixLon, Range, Bearing, GS")
     a = ap.parse_args()
+    if a.site is not None and not a.aircraft:
+        ap.error("--site needs --aircraft")
     fmt = a.format or ("c16" if a.file.endswith(".c16") else "u8")
     st = A.ADSB_SAMPLE_I16 if fmt == "c16" else A.ADSB_SAMPLE_I8
     n_max = os.path.getsize(a.file) // (4 if fmt == "c16" else 2)
@@ -172,9 +205,10 @@ def main():
                                                     chunk_len=a.chunk, carry=a.carry, send_tail=a.tail,
                                                     max_frames=max(n_max // 200, 1 << 16))
         if a.aircraft and a.levels:
-            text = aircraft_table(d, frames, n_samp, st, A.host_frame_levels(read_capture(a.file, fmt), frames))
+            text = aircraft_table(d, frames, n_samp, st, A.host_frame_levels(read_capture(a.file, fmt), frames),
+                                  site=a.site)
         elif a.aircraft:
-            text = aircraft_table(d, frames, n_samp)
+            text = aircraft_table(d, frames, n_samp, site=a.site)
         elif a.web:
             text = web_stream(d, frames, a.chunk)
         elif a.levels:
