@@ -77,6 +77,15 @@ class AdsbFrameLevel(C.Structure):
                 ("quiet_max", C.c_uint32), ("weak_bits", C.c_uint16), ("flags", C.c_uint16)]
 
 
+ADSB_WIRE_BEAST, ADSB_WIRE_AVR, ADSB_WIRE_AVR_MLAT = 0, 1, 2  # adsb_wire_cfg.format
+ADSB_WIRE_MAX_BYTES = 44                                     # the longest encoded frame (Beast, every byte doubled)
+
+
+class AdsbWireCfg(C.Structure):
+    """adsb_wire_cfg: format, whether Beast carries the signal byte, and the constant added to 6 x offset."""
+    _fields_ = [("format", C.c_uint32), ("signal", C.c_uint32), ("tick_bias", C.c_uint64)]
+
+
 class AdsbTrackPoint(C.Structure):
     _fields_ = [("latitude", C.c_double), ("longitude", C.c_double), ("icao", C.c_uint32), ("flags", C.c_uint32)]
 
@@ -221,6 +230,13 @@ PROTOTYPES = {
     "adsb_levels_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "adsb_levels_of": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t,
                                  _P(AdsbFrameLevel)]),
+    "adsb_wire_device_async": (C.c_int, [C.c_void_p, _P(AdsbWireCfg)]),
+    "adsb_fetch_wire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t,
+                                  _P(C.c_size_t)]),
+    "adsb_wire_device": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p)]),
+    "adsb_wire_of": (C.c_int, [C.c_void_p, _P(AdsbWireCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                               _P(C.c_size_t), C.c_void_p]),
+    "adsb_debug_wire_geometry": (C.c_int, [_P(C.c_uint32), _P(C.c_uint32)]),
     "adsb_track_device": (C.c_int, [C.c_void_p, C.c_double]),
     "adsb_fetch_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t,
                                    _P(C.c_size_t)]),
@@ -353,6 +369,8 @@ PROTOTYPES = {
     "adsb_host_frame_levels": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t,
                                          _P(AdsbFrameLevel)]),
     "adsb_level_dbfs": (C.c_double, [C.c_int, C.c_uint64, C.c_uint32]),
+    "adsb_host_wire_encode": (C.c_int, [_P(AdsbWireCfg), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_size_t, _P(C.c_size_t), C.c_void_p]),
     "adsb_host_fix_of": (C.c_int, [_P(AdsbSite), _P(C.c_uint8 * 14), C.c_double, _P(AdsbFix), _P(C.c_uint32)]),
 }
 

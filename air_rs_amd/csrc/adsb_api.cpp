@@ -17,6 +17,7 @@
 
 #include "adsb_ctx.h"
 #include "adsb_synth.h"
+#include "adsb_wire.h"
 
 using adsbk::kTile;
 using adsbk::kWindow;
@@ -67,6 +68,14 @@ extern "C" void adsb_destroy(adsb_ctx *c)
     (void)hipFree(c->levels);
     (void)hipFree(c->lvof_out);
     (void)hipFree(c->lvof_frames);
+    for (adsb_ctx::Wire *w : {&c->wire, &c->wof}) {
+        (void)hipFree(w->out);
+        (void)hipFree(w->ends);
+        (void)hipFree(w->block);
+        (void)hipFree(w->hdr);
+    }
+    (void)hipFree(c->wof_frames);
+    (void)hipFree(c->wof_levels);
     (void)hipFree(c->trk_u32);
     (void)hipFree(c->trk_temp);
     (void)hipFree(c->trk_points);
@@ -363,6 +372,7 @@ extern "C" int adsb_demod_device_async(adsb_ctx *c, const void *iq_dev, uint32_t
     c->launched = true;
     c->fields_current = false;
     c->levels_current = false;
+    c->wire_current = false;
     c->trk_done = false;
 
     // Launch i uses result set i & 1.  (ADSB_OVERLAP_ORDERING=1: the finishing kernel of launch i runs on `aux` beside
@@ -422,6 +432,7 @@ static void view_launch(adsb_ctx *c, uint32_t set)
     c->last_base = li.base; c->last_tpc = li.tpc; c->last_tiles = li.tiles; c->last_out = li.out; c->last_cap = li.cap;
     c->fields_current = false;
     c->levels_current = false;
+    c->wire_current = false;
     c->trk_done = false;
 }
 
@@ -487,6 +498,7 @@ static int small_launch(adsb_ctx *c, const void *iq, size_t n_samples, uint64_t 
     c->launched = true;
     c->fields_current = false;
     c->levels_current = false;
+    c->wire_current = false;
     c->trk_done = false;
     const uint32_t i = c->launch_idx, set = i & 1u;
     adsb_ctx::ResultSet &r = c->rs[set];
@@ -621,6 +633,7 @@ int sync_header(adsb_ctx *c)
         c->hdr_host->retry = 0;
         c->fields_current = false; // the list was rebuilt: decoded fields / levels / tracker output are stale
         c->levels_current = false;
+        c->wire_current = false;
         c->trk_done = false;
     }
     return ADSB_OK;
@@ -828,6 +841,162 @@ extern "C" int adsb_levels_of(adsb_ctx *c, const void *iq_dev, size_t n_samples,
     HIPCHK(adsbk::launch_frame_levels(c->aux, c->cfg.sample_type, a, levels_grid(c, n)));
     HIPCHK(hipMemcpyAsync(out, c->lvof_out, sizeof(adsb_frame_level) * n, hipMemcpyDeviceToHost, c->aux));
     HIPCHK(hipStreamSynchronize(c->aux));
+    return ADSB_OK;
+}
+
+// ---- wire output: Beast binary / AVR text (adsb_wire.hip) ---------------------------------------------------------------
+static int wire_reserve(adsb_ctx::Wire *w, size_t frames)
+{
+    if (frames * (uint64_t)adsbk::kWireMaxBytes > 0xFFFFFFFFull) return ADSB_E_CAPACITY; // ends[] are 32 bits wide
+    if (w->frames >= frames && w->hdr) return ADSB_OK;
+    (void)hipFree(w->out);
+    (void)hipFree(w->ends);
+    (void)hipFree(w->block);
+    (void)hipFree(w->hdr);
+    *w = adsb_ctx::Wire{};
+    const size_t f = std::max<size_t>(frames, 1);
+    if (hipMalloc((void **)&w->out, f * adsbk::kWireMaxBytes) != hipSuccess ||
+        hipMalloc((void **)&w->ends, f * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc((void **)&w->block, (size_t)adsbk::wire_blocks(f) * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc((void **)&w->hdr, 2 * sizeof(uint64_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(w->out);
+        (void)hipFree(w->ends);
+        (void)hipFree(w->block);
+        (void)hipFree(w->hdr);
+        *w = adsb_ctx::Wire{};
+        return ADSB_E_NOMEM;
+    }
+    w->frames = frames;
+    return ADSB_OK;
+}
+
+static adsbk::WireArgs wire_args(const adsb_ctx *c, const adsb_ctx::Wire &w, const adsb_wire_cfg &cfg)
+{
+    adsbk::WireArgs a{};
+    a.format = cfg.format;
+    a.sample_type = c->cfg.sample_type;
+    a.tick_bias = cfg.tick_bias;
+    a.out = w.out;
+    a.ends = w.ends;
+    a.block = w.block;
+    a.wire_hdr = w.hdr;
+    return a;
+}
+
+static bool wire_wants_levels(const adsb_wire_cfg &cfg) { return cfg.signal != 0 && cfg.format == ADSB_WIRE_BEAST; }
+
+extern "C" int adsb_wire_device_async(adsb_ctx *c, const adsb_wire_cfg *cfg)
+{
+    if (!c || !adsbk::wire_cfg_ok(cfg)) return ADSB_E_ARG;
+    if (!c->launched) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    int rc = wire_reserve(&c->wire, (size_t)c->cfg.max_out);
+    if (rc != ADSB_OK) return rc;
+    if (wire_wants_levels(*cfg) && !c->levels_current && (rc = adsb_levels_device_async(c)) != ADSB_OK) return rc;
+    adsbk::WireArgs a = wire_args(c, c->wire, *cfg);
+    a.frames = c->last_out;
+    a.levels = wire_wants_levels(*cfg) ? c->levels : nullptr;
+    a.hdr = c->rs[c->last].hdr;
+    a.cap = c->last_cap;
+    // same stream as the ordering pass (and the levels kernel), so it sees the finished list, header and levels
+    HIPCHK(adsbk::launch_wire(c->aux, a));
+    c->wire_cfg = *cfg;
+    c->wire_current = true;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_wire_device(adsb_ctx *c, const uint8_t **bytes_dev, const uint32_t **ends_dev, const void **header_dev)
+{
+    if (!c) return ADSB_E_ARG;
+    if (bytes_dev) *bytes_dev = c->wire.out;
+    if (ends_dev) *ends_dev = c->wire.ends;
+    if (header_dev) *header_dev = c->wire.hdr;
+    return c->wire.hdr ? ADSB_OK : ADSB_E_STATE;
+}
+
+// The finished stream of `w` (n frames encoded on c->aux) to the host: the whole of it if cap holds it, else the longest
+// prefix of whole frames; ends[] takes min(n, max_ends) entries.
+static int wire_copy_out(adsb_ctx *c, const adsb_ctx::Wire &w, uint8_t *out, size_t cap, size_t *n_bytes, uint32_t *ends,
+                         size_t max_ends, size_t *n_frames)
+{
+    uint64_t hdr[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(hdr, w.hdr, sizeof(hdr), hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    const size_t total = (size_t)hdr[0], n = (size_t)hdr[1];
+    size_t take = total;
+    std::vector<uint32_t> all;
+    const uint32_t *host_ends = nullptr;
+    const size_t n_ends = ends ? std::min(n, max_ends) : 0;
+    if (total > cap) { // whole frames only: the last end at or below cap
+        all.resize(n);
+        HIPCHK(hipMemcpyAsync(all.data(), w.ends, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->aux));
+        HIPCHK(hipStreamSynchronize(c->aux));
+        const size_t k = (size_t)(std::upper_bound(all.begin(), all.end(), (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu)) - all.begin());
+        take = k ? all[k - 1] : 0;
+        host_ends = all.data();
+    }
+    if (take) HIPCHK(hipMemcpyAsync(out, w.out, take, hipMemcpyDeviceToHost, c->aux));
+    if (n_ends) {
+        if (host_ends) std::memcpy(ends, host_ends, sizeof(uint32_t) * n_ends);
+        else HIPCHK(hipMemcpyAsync(ends, w.ends, sizeof(uint32_t) * n_ends, hipMemcpyDeviceToHost, c->aux));
+    }
+    HIPCHK(hipStreamSynchronize(c->aux));
+    *n_bytes = total;
+    if (n_frames) *n_frames = n;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_fetch_wire(adsb_ctx *c, uint8_t *out, size_t cap, size_t *n_bytes, uint32_t *ends, size_t max_ends,
+                               size_t *n_frames)
+{
+    if (!c || !n_bytes || !n_frames || (!out && cap) || (!ends && max_ends)) return ADSB_E_ARG;
+    if (!c->launched || !c->wire.hdr || !c->wire_current) return ADSB_E_STATE;
+    int rc = sync_header(c);
+    if (rc != ADSB_OK) return rc;
+    // the wait found holes in the list and rebuilt it (slot-pool overflow): the stream enqueued before is of the list
+    // with holes.  Again, for the rebuilt one (and its levels, which the same wait marked stale).
+    if (!c->wire_current) {
+        const adsb_wire_cfg cfg = c->wire_cfg;
+        if ((rc = adsb_wire_device_async(c, &cfg)) != ADSB_OK) return rc;
+    }
+    return wire_copy_out(c, c->wire, out, cap, n_bytes, ends, max_ends, n_frames);
+}
+
+extern "C" int adsb_wire_of(adsb_ctx *c, const adsb_wire_cfg *cfg, const adsb_frame *frames, const adsb_frame_level *levels,
+                            size_t n, uint8_t *out, size_t cap, size_t *n_bytes, uint32_t *ends)
+{
+    if (!c || !adsbk::wire_cfg_ok(cfg) || !n_bytes || (!frames && n) || (!out && cap)) return ADSB_E_ARG;
+    if (n * (uint64_t)adsbk::kWireMaxBytes > 0xFFFFFFFFull) return ADSB_E_CAPACITY;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    HIPCHK(hipStreamSynchronize(c->aux)); // an earlier call's kernels may still use the scratch that is about to grow
+    int rc = wire_reserve(&c->wof, n);
+    if (rc != ADSB_OK) return rc;
+    const adsb_frame *list = frames;
+    if (n && !levels_in_device_memory(c, frames)) {
+        if ((rc = grow_device(&c->wof_frames, &c->wof_frames_n, n)) != ADSB_OK) return rc;
+        HIPCHK(hipMemcpyAsync(c->wof_frames, frames, sizeof(adsb_frame) * n, hipMemcpyHostToDevice, c->aux));
+        list = c->wof_frames;
+    }
+    const adsb_frame_level *lv = wire_wants_levels(*cfg) ? levels : nullptr;
+    if (n && lv && !levels_in_device_memory(c, lv)) {
+        if ((rc = grow_device(&c->wof_levels, &c->wof_levels_n, n)) != ADSB_OK) return rc;
+        HIPCHK(hipMemcpyAsync(c->wof_levels, lv, sizeof(adsb_frame_level) * n, hipMemcpyHostToDevice, c->aux));
+        lv = c->wof_levels;
+    }
+    adsbk::WireArgs a = wire_args(c, c->wof, *cfg);
+    a.frames = list;
+    a.levels = lv;
+    a.hdr = nullptr;
+    a.cap = (uint32_t)n;
+    HIPCHK(adsbk::launch_wire(c->aux, a));
+    return wire_copy_out(c, c->wof, out, cap, n_bytes, ends, n, nullptr);
+}
+
+extern "C" int adsb_debug_wire_geometry(uint32_t *frames_per_block, uint32_t *scan_threads)
+{
+    if (frames_per_block) *frames_per_block = adsbk::kWireBlockFrames;
+    if (scan_threads) *scan_threads = adsbk::kWireScanThreads;
     return ADSB_OK;
 }
 

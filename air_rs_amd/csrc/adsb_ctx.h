@@ -48,6 +48,20 @@ struct adsb_ctx {
     adsb_frame *lvof_frames = nullptr;
     size_t lvof_out_n = 0, lvof_frames_n = 0;
     uint32_t levels_blocks = 0;     // the levels kernel's largest grid: a few waves per SIMD of this device
+    // wire output (adsb_wire.hip), allocated on first adsb_wire_device_async: the stream, the frames' ends, one word per
+    // workgroup, the stream's header; and adsb_wire_of's own scratch (grown on demand) with the device copies of host lists
+    struct Wire {
+        uint8_t *out = nullptr;     // [44 x frames]
+        uint32_t *ends = nullptr;   // [frames]
+        uint32_t *block = nullptr;  // [wire_blocks(frames)]
+        uint64_t *hdr = nullptr;    // {n_bytes, n_frames}
+        size_t frames = 0;          // what the four hold
+    } wire, wof;
+    adsb_frame *wof_frames = nullptr;
+    adsb_frame_level *wof_levels = nullptr;
+    size_t wof_frames_n = 0, wof_levels_n = 0;
+    adsb_wire_cfg wire_cfg{};       // of the last adsb_wire_device_async
+    bool wire_current = false;      // wire.out belongs to the last launch
     // tracker (allocated on first adsb_track_device)
     uint32_t *trk_u32 = nullptr;    // 4 x [max_out]: keys, vals, sorted keys, sorted vals
     void *trk_temp = nullptr;

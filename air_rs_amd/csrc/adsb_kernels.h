@@ -181,6 +181,25 @@ struct LevelsArgs {
 // blocks: the grid (4 waves per block, frames in a grid-stride loop); sized from the device by the caller
 hipError_t launch_frame_levels(hipStream_t s, int sample_type, const LevelsArgs &a, uint32_t blocks);
 
+// an ordered frame list as one stream of Beast binary or AVR text (adsb_wire.hip): three dispatches, see there
+constexpr uint32_t kWireBlockFrames = 256; // frames (= threads) per workgroup of the lengths and write kernels
+constexpr uint32_t kWireScanThreads = 256; // threads of the one workgroup that scans the workgroups' totals
+constexpr uint32_t wire_blocks(uint64_t cap) { return (uint32_t)((cap + kWireBlockFrames - 1) / kWireBlockFrames); }
+struct WireArgs {
+    const adsb_frame *frames;
+    const adsb_frame_level *levels; // [cap], or null: signal byte 0
+    const Header *hdr;           // count = min(hdr->n_out, cap), read on the device; nullptr: exactly cap frames
+    uint32_t cap;                // 44 x cap < 2^32
+    uint32_t format;             // ADSB_WIRE_*
+    int sample_type;             // the full scale of the signal byte
+    uint64_t tick_bias;
+    uint8_t *out;                // [44 x cap], dword-aligned
+    uint32_t *ends;              // [cap]
+    uint32_t *block;             // [wire_blocks(cap)]: each workgroup's total, then where its span starts
+    uint64_t *wire_hdr;          // {bytes in the stream, frames in it}
+};
+hipError_t launch_wire(hipStream_t s, const WireArgs &a);
+
 // tracker + CPR position decode over an ordered frame list (adsb_track.hip)
 // One aircraft of a persistent table (adsb_track_table_*): the public record plus the last even and the last odd
 // position message (aircraft.rs:28-31) that a later update's first position message of the other format pairs with.

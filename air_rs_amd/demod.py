@@ -102,6 +102,49 @@ def host_fix_of(site, frame_bytes, time=0.0):
     return out[0], flags.value
 
 
+WIRE_FORMATS = {"beast": L.ADSB_WIRE_BEAST, "avr": L.ADSB_WIRE_AVR, "avr_mlat": L.ADSB_WIRE_AVR_MLAT}
+
+
+def _wire_cfg(format, signal, tick_bias):
+    fmt = WIRE_FORMATS[format] if isinstance(format, str) else int(format)
+    return L.AdsbWireCfg(fmt, 1 if signal else 0, int(tick_bias))
+
+
+def _host_list(arr, dtype, n=None):
+    """(array kept alive, pointer or None, count) of a host record list."""
+    arr = np.ascontiguousarray(arr, dtype=dtype)
+    if n is not None and len(arr) != n:
+        raise ValueError(f"{len(arr)} level records for {n} frames")
+    return arr, (arr.ctypes.data if len(arr) else None), len(arr)
+
+
+def host_wire_encode(frames, levels=None, format="beast", sample_type=L.ADSB_SAMPLE_I8, tick_bias=0, cap=None):
+    """adsb_host_wire_encode, the CPU mirror of AdsbDemod.wire_of: (stream as bytes, ends as a uint32 array) of the
+    FRAME_DTYPE list `frames` with their LEVEL_DTYPE records `levels` (None: signal byte 0; sample_type gives its full
+    scale).  cap (default: enough): room in the output; with less than the stream needs, `bytes` holds the longest
+    prefix of whole frames and `ends` still has every frame's end.  Needs no device."""
+    frames, fptr, n = _host_list(frames, FRAME_DTYPE)
+    lptr = None
+    if levels is not None:
+        levels, lptr, _ = _host_list(levels, LEVEL_DTYPE, n)
+    cfg = _wire_cfg(format, levels is not None, tick_bias)
+    room = L.ADSB_WIRE_MAX_BYTES * n if cap is None else int(cap)
+    out = np.zeros(max(room, 1), dtype=np.uint8)
+    ends = np.zeros(max(n, 1), dtype=np.uint32)
+    total = C.c_size_t()
+    L.check(L.load().adsb_host_wire_encode(C.byref(cfg), int(sample_type), fptr, lptr, n, out.ctypes.data, room,
+                                           C.byref(total), ends.ctypes.data), "adsb_host_wire_encode")
+    return _wire_result(out, room, ends[:n].copy(), total.value)
+
+
+def _wire_result(out, room, ends, total):
+    """The bytes the call wrote: the stream, or its longest prefix of whole frames within `room`."""
+    if total > room:
+        fit = ends[ends <= room]
+        total = int(fit[-1]) if len(fit) else 0
+    return out[:total].tobytes(), ends
+
+
 def level_dbfs(sample_type, total, n_samples):
     """adsb_level_dbfs: 10 log10(total / n_samples / full scale) -- a LEVEL_DTYPE sum as mean power in dBFS (-inf for
     0).  level_dbfs(st, rec["signal_sum"], LEVEL_PULSE_SAMPLES), level_dbfs(st, rec["noise_sum"], LEVEL_QUIET_SAMPLES)."""
@@ -393,6 +436,66 @@ class AdsbDemod:
         L.check(self._lib.adsb_levels_of(self._h, dev_ptr, int(n_samples), int(first_sample), ptr, n,
                                          out.ctypes.data_as(C.POINTER(L.AdsbFrameLevel))), "adsb_levels_of")
         return out[:n].copy()
+
+    def wire_async(self, format="beast", signal=True, tick_bias=0):
+        """adsb_wire_device_async alone: enqueues the last launch's list as Beast binary ("beast") or AVR text ("avr",
+        "avr_mlat") behind its ordering pass and returns.  signal: Beast's signal byte from the launch's levels, which
+        are enqueued here if they have not been.  Timestamp = 6 x offset + tick_bias, mod 2^48."""
+        cfg = _wire_cfg(format, signal, tick_bias)
+        L.check(self._lib.adsb_wire_device_async(self._h, C.byref(cfg)), "adsb_wire_device_async")
+
+    def wire(self, format="beast", signal=True, tick_bias=0):
+        """The last launch's frames as one stream: (bytes, ends), ends[i] the exclusive end of frame i's bytes (uint32).
+        Encoded on the device; a second call with another format replaces the first's stream."""
+        self.wire_async(format, signal, tick_bias)
+        return self.fetch_wire()
+
+    def fetch_wire(self, cap=None, max_ends=None):
+        """adsb_fetch_wire: waits for the stream wire_async() enqueued -> (bytes, ends).  cap / max_ends (default: what
+        the stream needs): room for bytes and ends; with less room, whole frames only."""
+        total, n = C.c_size_t(), C.c_size_t()
+        if cap is None or max_ends is None:      # the sizes first; the stream stays where it is
+            L.check(self._lib.adsb_fetch_wire(self._h, None, 0, C.byref(total), None, 0, C.byref(n)), "adsb_fetch_wire")
+        room = total.value if cap is None else int(cap)
+        n_ends = n.value if max_ends is None else int(max_ends)
+        out = np.zeros(max(room, 1), dtype=np.uint8)
+        ends = np.zeros(max(n_ends, 1), dtype=np.uint32)
+        L.check(self._lib.adsb_fetch_wire(self._h, out.ctypes.data, room, C.byref(total), ends.ctypes.data, n_ends,
+                                          C.byref(n)), "adsb_fetch_wire")
+        ends = ends[:min(n_ends, n.value)].copy()
+        if total.value <= room:
+            return out[:total.value].tobytes(), ends
+        all_ends = ends if len(ends) == n.value else self.fetch_wire(cap=0)[1]
+        return _wire_result(out, room, all_ends, total.value)[0], ends
+
+    def wire_device(self):
+        """adsb_wire_device: device addresses (stream, ends, {u64 n_bytes, u64 n_frames}); no synchronisation."""
+        b, e, h = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        L.check(self._lib.adsb_wire_device(self._h, C.byref(b), C.byref(e), C.byref(h)), "adsb_wire_device")
+        return b.value, e.value, h.value
+
+    def wire_of(self, frames, levels=None, format="beast", tick_bias=0, cap=None):
+        """adsb_wire_of: any frame list with any level list as one stream -> (bytes, ends).  frames: a FRAME_DTYPE array
+        (host) or (device pointer, count); levels: None (signal byte 0), a LEVEL_DTYPE array (host) or a device pointer.
+        cap: room for the bytes (default: enough); with less, whole frames only.  Blocking; the last launch's wire
+        output stays as it is."""
+        if isinstance(frames, tuple):
+            fptr, n = int(frames[0]), int(frames[1])
+        else:
+            frames, fptr, n = _host_list(frames, FRAME_DTYPE)
+        lptr = None
+        if isinstance(levels, int):
+            lptr = levels
+        elif levels is not None:
+            levels, lptr, _ = _host_list(levels, LEVEL_DTYPE, n)
+        cfg = _wire_cfg(format, levels is not None, tick_bias)
+        room = L.ADSB_WIRE_MAX_BYTES * n if cap is None else int(cap)
+        out = np.zeros(max(room, 1), dtype=np.uint8)
+        ends = np.zeros(max(n, 1), dtype=np.uint32)
+        total = C.c_size_t()
+        L.check(self._lib.adsb_wire_of(self._h, C.byref(cfg), fptr, lptr, n, out.ctypes.data, room, C.byref(total),
+                                       ends.ctypes.data), "adsb_wire_of")
+        return _wire_result(out, room, ends[:n].copy(), total.value)
 
     def set_result_target(self, dev_ptr, nbytes):
         """Next launches write [32-byte header | frames] straight into caller-owned HBM (None: reset)."""

@@ -271,6 +271,69 @@ int adsb_levels_of(adsb_ctx *ctx, const void *iq_dev, size_t n_samples, uint64_t
                    const adsb_frame *frames, size_t n, adsb_frame_level *out);
 
 /*
+ * Wire output: a frame list as Beast binary or AVR text, the formats readsb / dump1090 network inputs, tar1090,
+ * Virtual Radar Server, mlat-client and feeder clients speak, encoded on the device.
+ *   TIMESTAMP  t = (6 x frame.offset + tick_bias) mod 2^48: the 12 MHz multilateration clock, six ticks per 2 MSPS
+ *     sample.  frame.offset is absolute across launches and ranks once adsb_set_stream_base is used.  tick_bias = 0
+ *     stamps the first preamble sample (dump1090's convention for long messages is the END of the message); the
+ *     caller's constant is the only configuration, nothing else is inferred.
+ *   SIGNAL BYTE  s = 0 with signal == 0, with a NULL level list, or for a level record without ADSB_LEVEL_VALID.
+ *     Otherwise s = 255 x sqrt(signal_sum / (116 x FS)) rounded half up, clamped to 255 and raised to 1 when
+ *     signal_sum > 0, with FS the full scale of adsb_level_dbfs (32768 for ADSB_SAMPLE_I8, 2^31 for ADSB_SAMPLE_I16).
+ *     Computed exactly in integers: s is the largest s in 0..255 with (2s-1)^2 x 116 x FS <= 4 x 255^2 x signal_sum
+ *     (every product fits uint64: the largest left side is 509^2 x 116 x 2^31, about 6.5e16).  No floating point:
+ *     device, CPU mirror and any model agree to the bit.
+ *   ADSB_WIRE_BEAST     1A 33, then 6 bytes of t big-endian, then s, then the 14 frame bytes; every 0x1A among those
+ *                       21 bytes is written twice.  23..44 bytes.
+ *   ADSB_WIRE_AVR       '*', 28 upper-case hex digits, ';', '\n'.  31 bytes.
+ *   ADSB_WIRE_AVR_MLAT  '@', 12 upper-case hex digits of t, 28 hex digits, ';', '\n'.  43 bytes.  (The AVR forms carry
+ *                       no signal byte: `signal` is ignored.)
+ * The output is ONE contiguous byte stream in list order (channel 0's frames in ascending offset, then channel 1's,
+ * ...) and uint32 ends[n]: the exclusive end offset of each frame's bytes, so ends[i-1] .. ends[i] is frame i (from 0
+ * for frame 0) and ends[n-1] is the stream's length.  With adsb_fetch's per_channel_counts a consumer cuts the stream
+ * per receiver without parsing it.  The stream is byte-identical from run to run.
+ */
+#define ADSB_WIRE_BEAST 0u
+#define ADSB_WIRE_AVR 1u
+#define ADSB_WIRE_AVR_MLAT 2u
+#define ADSB_WIRE_MAX_BYTES 44 /* the longest encoded frame */
+typedef struct adsb_wire_cfg {
+    uint32_t format;     /* ADSB_WIRE_*                                               */
+    uint32_t signal;     /* != 0: the Beast signal byte from the frames' level records */
+    uint64_t tick_bias;  /* < 2^48                                                     */
+} adsb_wire_cfg;
+/* Enqueues the encoding of the last launch's list behind its ordering pass (three small dispatches; the count is read
+ * on the device, the host does not wait).  A second call on the same launch replaces the first's output.  With
+ * signal != 0 (Beast) and no levels enqueued for this launch it enqueues adsb_levels_device_async itself first, so
+ * that call's conditions hold: like it, NOT for use while a feed is open when signal != 0 (a feed's consumer encodes
+ * the popped frames with adsb_host_wire_encode, adsb_host.h).  Buffers are allocated on first use: 44 x cfg.max_out
+ * bytes, cfg.max_out ends, one word per 256 frames; a ctx that never calls it allocates nothing and launches exactly
+ * the kernels it launched before.  ADSB_E_ARG for a NULL ctx or cfg, an unknown format or tick_bias >= 2^48;
+ * ADSB_E_STATE before any launch; ADSB_E_CAPACITY when 44 x cfg.max_out does not fit uint32. */
+int adsb_wire_device_async(adsb_ctx *ctx, const adsb_wire_cfg *cfg);
+/* Waits.  If the wait found the list rebuilt (ADSB_FLAG_INCOMPLETE, slot-pool overflow), the stream is encoded again
+ * for the rebuilt list first, as adsb_fetch_levels does.  *n_bytes = the stream's length and *n_frames = the frames in
+ * it, whatever the capacities.  `out` receives the whole stream if cap holds it, else whole frames only: the longest
+ * prefix of frames that fits.  `ends` (may be NULL with max_ends 0) receives min(*n_frames, max_ends) entries.
+ * ADSB_E_STATE if no wire output was enqueued for the last launch. */
+int adsb_fetch_wire(adsb_ctx *ctx, uint8_t *out, size_t cap, size_t *n_bytes, uint32_t *ends, size_t max_ends,
+                    size_t *n_frames);
+/* For device-side consumers; does not synchronise.  The stream, ends[] and the stream's header
+ * { uint64 n_bytes; uint64 n_frames } in device memory (each optional), valid until the next wire call on this ctx
+ * and ordered like adsb_levels_device's records.  ADSB_E_STATE before the first adsb_wire_device_async. */
+int adsb_wire_device(adsb_ctx *ctx, const uint8_t **bytes_dev, const uint32_t **ends_dev, const void **header_dev);
+/* Any frame list with any level list (levels NULL: s = 0), each in host memory or in device memory of the ctx's
+ * device; frames no demodulator would emit are encoded like any other.  Blocking.  out / cap / *n_bytes as
+ * adsb_fetch_wire; ends (host, may be NULL) receives all n entries.  Uses scratch of its own: the last launch's wire
+ * output stays as it is.  ADSB_E_CAPACITY when 44 x n does not fit uint32. */
+int adsb_wire_of(adsb_ctx *ctx, const adsb_wire_cfg *cfg, const adsb_frame *frames,
+                 const adsb_frame_level *levels /* NULL: s = 0 */, size_t n, uint8_t *out, size_t cap, size_t *n_bytes,
+                 uint32_t *ends);
+/* Frames per workgroup of the encoder's kernels and threads of its totals scan (either may be NULL): the sizes at
+ * which the encoder takes another path, for tests.  The stream does not depend on them. */
+int adsb_debug_wire_geometry(uint32_t *frames_per_block, uint32_t *scan_threads);
+
+/*
  * Tracker + global CPR position decode on the device: what the reference's display
  * threads do with every AdsbPacket, `handle_aircraft_update` (src/adsb/aircraft.rs:158-165 ->
  * Aircraft::handle_packet, aircraft.rs:48-111 -> cpr::calculate_geographic_position, cpr.rs:135-147),

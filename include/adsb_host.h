@@ -113,6 +113,19 @@ int adsb_host_frame_levels(int sample_type, const void *iq, size_t n_samples, ui
 double adsb_level_dbfs(int sample_type, uint64_t sum, uint32_t n_samples);
 
 /*
+ * CPU mirror of adsb_wire_of (adsb_hip.h, "Wire output"): the same bytes from the same program text as the device's, no
+ * device needed.  frames[n] with levels[n] (NULL: s = 0), both host memory; sample_type gives the signal byte's full
+ * scale.  out / cap / *n_bytes as adsb_fetch_wire: the whole stream if cap holds it, else the longest prefix of whole
+ * frames, and *n_bytes = the stream's full length either way; ends (may be NULL) receives all n entries.  What a
+ * feed's consumer uses on popped frames, together with adsb_host_frame_levels.  ADSB_E_ARG for a NULL cfg or n_bytes,
+ * an unknown format, tick_bias >= 2^48, a bad sample_type, NULL frames with n > 0 or NULL out with cap > 0;
+ * ADSB_E_CAPACITY when 44 x n does not fit uint32.
+ */
+int adsb_host_wire_encode(const adsb_wire_cfg *cfg, int sample_type, const adsb_frame *frames,
+                          const adsb_frame_level *levels /* NULL: s = 0 */, size_t n, uint8_t *out, size_t cap,
+                          size_t *n_bytes, uint32_t *ends);
+
+/*
  * CPU mirror of the per-frame fix decode of a table or bank with a fixes reserve (adsb_hip.h, "Positions from single
  * messages"): the same program text as the device's, no device needed.  *out = the adsb_fix of an aircraft whose only
  * frame since admission is this one, heard at frame time `time` by a receiver at *site: accepted: the fix with

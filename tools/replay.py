@@ -10,6 +10,8 @@
   tools/replay.py capture.c16 --levels        # signal and noise power of every packet instead, tab-separated
   tools/replay.py capture.c16 --aircraft --levels   # the aircraft table with two more columns: RSSI and SNR
   tools/replay.py capture.c16 --aircraft --site 51.5,-0.1      # ... with five more: each aircraft's own fix from the site
+  tools/replay.py capture.c16 --beast out.bin # also write every packet as Beast binary (readsb / dump1090 / tar1090 input)
+  tools/replay.py capture.c16 --avr out.txt   # ... as AVR text, one "*...;" line per packet; --mlat: "@" + timestamp + ...
 
 Everything below the argument parsing is one call through the C ABI (adsb_replay_file, include/adsb_host.h).
 The "Processed Time" line carries no value (the reference prints the wall clock there).  With --aircraft, the frames
@@ -32,7 +34,11 @@ site and five columns are appended (after RSSI and SNR if both are asked for): F
 aircraft's newest position message decoded on its own against the site (six decimals; this also covers surface
 messages and aircraft heard with one CPR format only, which Latitude and Longitude never show), Range in nautical miles
 and Bearing in degrees from the site (one decimal), and GS, a surface message's ground speed in knots (one decimal);
-"n/a" for a missing value (write a negative latitude as --site=-33.9,151.2).  The TEXT has not been compared with a Rust build's (there is no
+"n/a" for a missing value (write a negative latitude as --site=-33.9,151.2).  With --beast FILE / --avr FILE the
+whole capture's packets are also written to FILE as one stream, encoded on the device (adsb_wire_of): Beast binary with
+the 12 MHz timestamp 6 x offset + N (--tick-bias N, default 0: the first preamble sample) and the signal byte from the
+packets' level records, or AVR text ("*" lines; with --mlat "@" lines that carry the timestamp).  Offsets are positions
+in the whole capture, so the timestamps run on across chunks.  The TEXT has not been compared with a Rust build's (there is no
 Rust toolchain); only the values are checked, against the oracle."""
 import argparse
 import json
@@ -179,6 +185,17 @@ def level_lines(d, st, frames, iq, piece=LEVELS_PIECE):
     return "".join(line + "\n" for line in lines)
 
 
+def write_wire(d, frames, a, fmt):
+    """--beast / --avr: the capture's frames as one stream, encoded on the device."""
+    if a.beast:
+        levels = A.host_frame_levels(read_capture(a.file, fmt), frames)
+        with open(a.beast, "wb") as fh:
+            fh.write(d.wire_of(frames, levels, format="beast", tick_bias=a.tick_bias)[0])
+    if a.avr:
+        with open(a.avr, "wb") as fh:
+            fh.write(d.wire_of(frames, None, format="avr_mlat" if a.mlat else "avr", tick_bias=a.tick_bias)[0])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("file")
@@ -193,7 +210,15 @@ def main():
     ap.add_argument("--levels", action="store_true", help="print signal and noise power of every packet instead; with --aircraft: two more columns, RSSI and SNR")
     ap.add_argument("--site", type=parse_site, default=None, metavar="LAT,LON[,RANGE_NM]",
                     help="with --aircraft: the receiver's position; five more columns: FixLat, FixLon, Range, Bearing, GS")
+    ap.add_argument("--beast", metavar="FILE", help="also write the packets to FILE as Beast binary")
+    ap.add_argument("--avr", metavar="FILE", help="also write the packets to FILE as AVR text")
+    ap.add_argument("--mlat", action="store_true", help="with --avr: the '@' form, which carries the 12 MHz timestamp")
+    ap.add_argument("--tick-bias", type=int, default=0, metavar="N", help="added to every timestamp (12 MHz ticks, < 2^48)")
     a = ap.parse_args()
+    if a.mlat and not a.avr:
+        ap.error("--mlat needs --avr")
+    if not 0 <= a.tick_bias < 1 << 48:
+        ap.error("--tick-bias is 0 .. 2^48 - 1")
     if a.site is not None and not a.aircraft:
         ap.error("--site needs --aircraft")
     fmt = a.format or ("c16" if a.file.endswith(".c16") else "u8")
@@ -213,6 +238,7 @@ def main():
             text = web_stream(d, frames, a.chunk)
         elif a.levels:
             text = level_lines(d, st, frames, read_capture(a.file, fmt))
+        write_wire(d, frames, a, fmt)
     sys.stdout.write(text)
     if a.summary:
         print(f"{n_samp} samples, {n_buf} buffers of {a.chunk}, {len(frames)} packets", file=sys.stderr)
