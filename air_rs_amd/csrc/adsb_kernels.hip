@@ -109,6 +109,25 @@ __device__ __forceinline__ void dot4x8_sacc(u32x4 v, int c, int n[8])
           "v"(a6), "v"(a7), "s"(c));
 }
 
+// The same eight dots for mags8_i8, which needs only four masks: per dword x = (I0,Q0,I1,Q1), a = x . (x & 0xFFFF) =
+// c + n0 (masked, as above) and b = x . x = c + n0 + n1 (no mask); the odd sample's n1 is their difference, taken
+// inside the packed FMA mags8_i8 pays for anyway.  Same hazard rule, same s_nop 2.
+__device__ __forceinline__ void dot4x8_pair_sacc(u32x4 v, int c, int a[4], int b[4])
+{
+    const uint32_t m0 = v.x & 0xFFFFu, m1 = v.y & 0xFFFFu, m2 = v.z & 0xFFFFu, m3 = v.w & 0xFFFFu;
+    asm("v_dot4_i32_i8 %0, %8, %12, %16\n\t"
+        "v_dot4_i32_i8 %1, %9, %13, %16\n\t"
+        "v_dot4_i32_i8 %2, %10, %14, %16\n\t"
+        "v_dot4_i32_i8 %3, %11, %15, %16\n\t"
+        "v_dot4_i32_i8 %4, %8, %8, %16\n\t"
+        "v_dot4_i32_i8 %5, %9, %9, %16\n\t"
+        "v_dot4_i32_i8 %6, %10, %10, %16\n\t"
+        "v_dot4_i32_i8 %7, %11, %11, %16\n\t"
+        "s_nop 2"
+        : "=&v"(a[0]), "=&v"(a[1]), "=&v"(a[2]), "=&v"(a[3]), "=&v"(b[0]), "=&v"(b[1]), "=&v"(b[2]), "=&v"(b[3])
+        : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w), "v"(m0), "v"(m1), "v"(m2), "v"(m3), "s"(c));
+}
+
 // CRC-24 syndrome table (used by count_candidate only -- tiles that lost their slots are counted in place, a cold
 // path; finish_order has its own byte table and sorted syndromes): kSyn[j] = x^(111-j) mod 0x1FFF409, j = 0..111 (bit j
 // MSB-first of the 112-bit frame).  XOR over the set bits of a frame is CRC24(data) ^ crc_field; for j < 88 it is
@@ -137,6 +156,12 @@ __constant__ SynTable kSyn = make_syn();
 // gets from f64 sqrt + `as u32` (utils.rs:48).  n + 0.5 is formed without an int->float
 // convert: the dot product accumulates onto 0x4B000000 (2^23 as float bits), so the integer
 // result reinterpreted as float is 2^23 + n, and one subtraction of (2^23 - 0.5) is exact.
+// mags8_i8 masks only the even sample of each dword.  With A = 2^23 + n0 (masked dot) and B = 2^23 + n0 + n1
+// (whole dword; < 2^24, exact as a float), the odd sample's argument is fma(A, -(1 - 2^-24), B) =
+// n1 + 0.5 + n0 * 2^-24 (the product is exact inside the FMA), i.e. n1 + d with d in [0.5, 0.502] before the
+// result is rounded (to nearest, or toward zero under MAGMODE 1) onto a grid no coarser than 2^-8.
+// floor(sqrt(n + d)) = floor(sqrt(n)) for any d in (0, 1); sqrt(n1 + d) stays 1.376e-3 away from every integer
+// (every n1 <= 32768, both roundings, root +-2 ulp: tests/test_pair_dot_model.py), the margin n + 0.5 has.
 template <int MAGMODE> __device__ __forceinline__ float mag_root_i8(int n_plus_2p23)
 {
     float f = __builtin_bit_cast(float, n_plus_2p23) - 8388607.5f;
@@ -150,16 +175,21 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int MAGMODE>
 __device__ __forceinline__ void mags8_i8(u32x4 v, uint32_t &lo, uint32_t &hi)
 {
-    int n[8];
-    dot4x8_sacc(v, 0x4B000000, n);
-    // n + 0.5 for two samples per instruction (v_pk_add_f32; see mag_root_i8 for the constant)
+    int a[4], b[4];
+    dot4x8_pair_sacc(v, 0x4B000000, a, b);
+    // two dwords per packed instruction: even samples n0 + 0.5 (v_pk_add_f32), odd samples n1 + 0.5 + n0 * 2^-24
+    // (v_pk_fma_f32; see mag_root_i8 for the constants).  Sample 2k is f[2k], sample 2k + 1 is f[2k + 1].
     float f[8];
 #pragma unroll
-    for (int k = 0; k < 8; k += 2) {
-        f32x2 t = {__builtin_bit_cast(float, n[k]), __builtin_bit_cast(float, n[k + 1])};
-        t = t - (f32x2){8388607.5f, 8388607.5f};
-        f[k] = t.x;
-        f[k + 1] = t.y;
+    for (int k = 0; k < 4; k += 2) {
+        f32x2 ta = {__builtin_bit_cast(float, a[k]), __builtin_bit_cast(float, a[k + 1])};
+        f32x2 tb = {__builtin_bit_cast(float, b[k]), __builtin_bit_cast(float, b[k + 1])};
+        f32x2 te = ta - (f32x2){8388607.5f, 8388607.5f};
+        f32x2 to = __builtin_elementwise_fma(ta, (f32x2){-0x1.fffffep-1f, -0x1.fffffep-1f}, tb);
+        f[2 * k] = te.x;
+        f[2 * k + 1] = to.x;
+        f[2 * k + 2] = te.y;
+        f[2 * k + 3] = to.y;
     }
     float r[8];
 #pragma unroll

@@ -12,9 +12,17 @@ mkdir -p air_rs_amd/lib/variants
 SRC=air_rs_amd/csrc
 FILES=$(sed "s|^|$SRC/|" $SRC/sources.list) # the library's sources: one list, read by tools/build_variant.sh and tools/gpu/mkvar.sh too
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -pthread -Wall -Wno-unused-function"
+# a failed compile must not leave the previous library behind to be reported (and timed) as the new one
+rm -f air_rs_amd/lib/libadsb_hip.so air_rs_amd/lib/variants/libadsb_hip_ab.so
 $HIPCC $FLAGS $FILES -o air_rs_amd/lib/libadsb_hip.so &
+pid_product=$!
 $HIPCC $FLAGS -DADSB_AB_KERNELS=1 $FILES -o air_rs_amd/lib/variants/libadsb_hip_ab.so &
+pid_ab=$!
 gcc -O3 -std=c99 -fPIC -shared -Wall -Wextra oracle/adsb_oracle.c -o oracle/libadsb_oracle.so -lm
-wait
+# `wait` without arguments returns 0 whatever the jobs returned: wait for each by PID
+rc=0
+wait $pid_product || rc=$?
+wait $pid_ab || rc=$?
+[ $rc -eq 0 ] || { echo "build.sh: a hipcc job failed (exit $rc)" >&2; exit $rc; }
 test -s air_rs_amd/lib/libadsb_hip.so && test -s air_rs_amd/lib/variants/libadsb_hip_ab.so
 echo "built air_rs_amd/lib/libadsb_hip.so air_rs_amd/lib/variants/libadsb_hip_ab.so oracle/libadsb_oracle.so"

@@ -82,7 +82,9 @@ new = {
         {"what": "tile loads: sweep constant in the SGPR offset; one register for the DF17 bit constant", "valu_instructions_per_wave": 1386.3, "valu_slots_per_wave": 1521.4},
         {"what": "slicer: SDWA byte compare + add-with-carry per bit", "valu_instructions_per_wave": 1367.4, "valu_slots_per_wave": 1502.5},
         {"what": "round 3: 16384-offset tiles (runs of 32; per wave per tile, i.e. per HALF as many samples as the rows above), 19 KB of LDS, "
-                 "8 workgroups per CU", "valu_instructions_per_wave": round(i8["demod_tiles"]["SQ_INSTS_VALU"] / i8["demod_tiles"]["SQ_WAVES"], 1),
+                 "8 workgroups per CU", "valu_instructions_per_wave": 740.7, "valu_slots_per_wave": 809.8},
+        {"what": "phase 1: one mask per dword, the odd sample's I^2+Q^2 as the difference of two dots inside a packed FMA "
+                 "(profiles/pair_dot_checks.txt)", "valu_instructions_per_wave": round(i8["demod_tiles"]["SQ_INSTS_VALU"] / i8["demod_tiles"]["SQ_WAVES"], 1),
          "valu_slots_per_wave": round(i8["demod_tiles"]["SQ_ACTIVE_INST_VALU"] / i8["demod_tiles"]["SQ_WAVES"], 1)},
     ],
     "demod_tiles_cs16_history": old.get("demod_tiles_cs16_history") or [
