@@ -1,4 +1,4 @@
-// adsb_sieve.inc -- the SIEVE scan (i8, kScanSieve); included by adsb_kernels.hip inside namespace adsbk.
+// ab/sieve.inc -- the SIEVE scan (i8, kScanSieve); included by adsb_kernels.hip inside namespace adsbk.
 //
 // The root scan is bound by VALU issue (DESIGN.md section 5): 5.5 issue slots per sample for floor(sqrt(I^2+Q^2)), 4.8 for the
 // sliding 16 + 10 tap ordering test, on an LDS image it has to transpose.  The sieve replaces both by ONE BIT PAIR per sample:
@@ -23,7 +23,8 @@
 //     PPM bits of the survivors by 16-lane groups with one root per pair (floor(sqrt(x)) > floor(sqrt(y)) iff r(x)^2 > y).
 //     (Re-reading them from global memory instead -- ADSB_SV_IMG=0: 6.6 KB of LDS, eight workgroups per CU -- costs two dependent
 //     round trips per tile: 0.229 ms against 0.200.)  Survivors go to the tile's frame slots exactly as the root scan leaves
-//     them: Seg, slots and finish_order are shared.
+//     them: Seg, slots and finish_order are shared, and so is the survivor hand-over (hand_over, adsb_kernels.hip) on the
+//     path that coarse or constant input takes.
 // Geometry: the root scan's (kTile = 16384 offsets, kThreads = 256); 39 KB of LDS per workgroup: four workgroups per CU.
 // Measured (profiles/r04_ab_sieve.txt): loads + image + relation bits alone 0.154 ms (the read ceiling), + taps 0.170, complete
 // 0.200 ms (root scan: 0.190): bit-exact, not faster -- an A/B kernel (-DADSB_AB_KERNELS=1).
@@ -354,13 +355,7 @@ __device__ __forceinline__ void sieve_tile_body(const DemodArgs &p, const uint32
     SvSrc src;
     src.lds = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char *)(smem + L::kOffImg);
     src.rsrc = tile_rsrc<2, kSvMag>(p, tp, true);
-    if (tid == 0 && first) {
-        p.hdr->retry = 0;
-        if (p.count_groups) { // first pass of a launch: the finishing kernel ORs this launch's flags in
-            p.hdr->flags = 0;
-            if (p.hdr_pub) p.hdr_pub[2] = 0;
-        }
-    }
+    clear_launch_flags(p, first, tid);
     if (tid < 16) misc[tid] = 0; // [4 + wave]: the wave's candidates; [8]: valid frames (tiles without slots only); [13]: survivors;
                                  // [14]: the workgroup path is needed
     // [phase:1 sieve: relation bits]
@@ -484,12 +479,7 @@ __device__ __forceinline__ void sieve_tile_body(const DemodArgs &p, const uint32
                         const bool have2 = ci < n_s;
                         const uint32_t off = have2 ? sv[ci] : 0u;
                         const uint32_t byte = sieve_slice_byte(img_lds, off, l);
-                        if (have2) {
-                            unsigned char *rec = reinterpret_cast<unsigned char *>(p.slots + (size_t)(tile * kQuota + ci));
-                            const uint64_t o64 = abs0 + off;
-                            if (l < 14) rec[8 + l] = (unsigned char)byte;
-                            else reinterpret_cast<uint32_t *>(rec)[l - 14] = l == 14 ? (uint32_t)o64 : (uint32_t)(o64 >> 32);
-                        }
+                        if (have2) put_record(p.slots + (size_t)(tile * kQuota + ci), abs0 + off, byte, l);
                     }
                 }
             }
@@ -534,12 +524,7 @@ __device__ __forceinline__ void sieve_tile_body(const DemodArgs &p, const uint32
                             const bool have2 = ci < n_s; // uniform within the 16-lane group
                             const uint32_t off = have2 ? ws[ci] : 0u;
                             const uint32_t byte = sieve_slice_byte(img_lds, off, l);
-                            if (have2) {
-                                unsigned char *rec = reinterpret_cast<unsigned char *>(p.slots + (size_t)(tile * kQuota + sb + ci));
-                                const uint64_t o64 = abs0 + off;
-                                if (l < 14) rec[8 + l] = (unsigned char)byte;
-                                else reinterpret_cast<uint32_t *>(rec)[l - 14] = l == 14 ? (uint32_t)o64 : (uint32_t)(o64 >> 32);
-                            }
+                            if (have2) put_record(p.slots + (size_t)(tile * kQuota + sb + ci), abs0 + off, byte, l);
                         }
                     }
                 }
@@ -550,107 +535,32 @@ __device__ __forceinline__ void sieve_tile_body(const DemodArgs &p, const uint32
 #endif
     __syncthreads();
     if (misc[14] == 0) { // (workgroup-uniform) the usual case: Seg::cand counts SURVIVORS, as after the root scan
-        if (tid == 0) {
-            Seg e;
-            e.base = tile * kQuota;
-            e.cand = misc[13];
-            e.valid = 0;
-            e.decoded = 0;
-            p.seg[tile] = e; // (finish_order reads it)
-        }
+        if (tid == 0) write_seg(p, tile, tile * kQuota, misc[13], 0);
         return;
     }
 
     // [phase:3 sieve: the workgroup path (coarse or constant input: many candidates)]
-    // The candidate bitmap is compacted in offset order by workgroup-wide prefix sums, every candidate gets a slot from the pool,
-    // the exact gate runs one LANE per entry of a chunk, and one it rejects leaves a record whose offset is all ones (finish_order
-    // skips it); the others are sliced by 16-lane groups.
+    // The root scan's hand-over on the candidate bitmap (there is no list: kCountBitmap): compacted in offset order by
+    // workgroup-wide prefix sums, every candidate gets a slot from the pool, the exact gate runs one LANE per entry of a chunk
+    // (kListCap <= kThreads) and marks what it rejects in place (bit 15), the others are sliced by 16-lane groups; a rejected
+    // entry leaves a record whose offset is all ones (finish_order skips it).
     const SvSrc &img_lds = src;
-    const uint64_t abs0 = sample0 + p.offset_base;
-    const uint32_t g = tid >> 4, l = tid & 15;
-    auto put = [&](uint32_t slot, uint64_t o64, uint32_t byte) { // one record by its 16-lane group
-        unsigned char *rec = reinterpret_cast<unsigned char *>(p.slots + (size_t)slot);
-        if (l < 14) rec[8 + l] = (unsigned char)byte;
-        else reinterpret_cast<uint32_t *>(rec)[l - 14] = l == 14 ? (uint32_t)o64 : (uint32_t)(o64 >> 32);
-    };
-    // entries src[0 .. ncl): tile offset, bit 15 = rejected by the gate (record with an all-ones offset, no slicing)
-    auto slice_round = [&](const uint16_t *src, uint32_t slot0, uint32_t ncl, bool count_only) {
-        for (uint32_t r = 0; r < ncl; r += kThreads / 16) {
-            if (r + 4 * wave >= ncl) break; // none of this wave's four groups has an entry
-            const uint32_t ci = r + g;
-            const bool have = ci < ncl; // uniform within the 16-lane group
-            const uint32_t ent = have ? src[ci] : 0x8000u, off = ent & 0x7FFFu;
-            const bool rej = (ent & 0x8000u) != 0;
-            uint32_t byte = 0;
-            if (__builtin_amdgcn_ballot_w64(!rej) != 0) byte = sieve_slice_byte(img_lds, off, l); // (wave-uniform)
-            if (count_only) {
-                const bool valid = count_candidate(have && !rej, byte, l, lane);
-                if (valid && l == 0) atomicAdd(&misc[8], 1u);
-            } else if (have) {
-                put(slot0 + ci, rej ? ~0ull : abs0 + off, byte);
-            }
-        }
-    };
-    u32x4 cw = {0, 0, 0, 0}; // bitmap words 4 tid .. 4 tid + 3
-    if (4 * tid < (uint32_t)(kSvTile / 32)) cw = reinterpret_cast<const u32x4 *>(cand)[tid];
-    const uint32_t cnt = __builtin_popcount(cw.x) + __builtin_popcount(cw.y) + __builtin_popcount(cw.z) + __builtin_popcount(cw.w);
-    uint32_t incl = cnt;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t t = __shfl_up(incl, d, 64);
-        if ((int)lane >= d) incl += t;
-    }
     __syncthreads(); // (every thread has read misc[14]: misc[0 .. 3] are free)
-    if (lane == 63) misc[wave] = incl;
-    __syncthreads();
-    uint32_t wbase = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) {
-        uint32_t t = misc[w];
-        wbase += (w < (int)wave) ? t : 0u;
-        total += t;
-    }
-    const uint32_t my_first = wbase + incl - cnt;
-    if (tid == 0) {
-        const unsigned long long b64 = atomicAdd(&p.hdr->alloc, (unsigned long long)total);
-        // (pool_off: test knob, adsb_debug_pool_limit -- every tile over its quota loses its slots)
-        misc[9] = (!p.pool_off && b64 + total <= (unsigned long long)p.cap_slots) ? p.pool_first + (uint32_t)b64 : kNoBase;
-    }
-    __syncthreads();
-    const uint32_t base_slot = misc[9];
-    for (uint32_t chunk = 0; chunk < total; chunk += kListCap) {
-        if (cnt) {
-            uint32_t idx = my_first;
-            const uint32_t words[4] = {cw.x, cw.y, cw.z, cw.w};
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                uint32_t bits = words[k];
-                while (bits) {
-                    const uint32_t b = (uint32_t)__builtin_ctz(bits);
-                    bits &= bits - 1;
-                    if (idx >= chunk && idx < chunk + kListCap) list[idx - chunk] = (uint16_t)((4 * tid + k) * 32 + b);
-                    ++idx;
-                }
+    hand_over<kSvTile, 32>(
+        p, tile, sample0, kCountBitmap, cand, list, misc, tid, lane, wave,
+        [&](const bool have, const uint32_t ent, const uint32_t l, bool &dropped) {
+            dropped = (ent & 0x8000u) != 0;
+            uint32_t byte = 0;
+            if (__builtin_amdgcn_ballot_w64(have && !dropped) != 0) byte = sieve_slice_byte(img_lds, ent & 0x7FFFu, l); // (wave-uniform)
+            return byte;
+        },
+        [&](uint16_t *entries, const uint32_t n) {
+            if (tid < n) {
+                const uint32_t off = entries[tid];
+                if (!sieve_gate_lane(img_lds, off)) entries[tid] = (uint16_t)(off | 0x8000u);
             }
-        }
-        __syncthreads();
-        const uint32_t ncl = (total - chunk) < (uint32_t)kListCap ? (total - chunk) : (uint32_t)kListCap;
-        if (tid < ncl) { // the exact gate on this chunk (kListCap <= kThreads): rejected entries are marked in place
-            const uint32_t off = list[tid];
-            if (!sieve_gate_lane(img_lds, off)) list[tid] = (uint16_t)(off | 0x8000u);
-        }
-        __syncthreads();
-        slice_round(list, base_slot + chunk, ncl, base_slot == kNoBase);
-        __syncthreads();
-    }
-    if (tid == 0) {
-        Seg e;
-        e.base = base_slot;
-        e.cand = total;
-        e.valid = misc[8];
-        e.decoded = base_slot == kNoBase ? 1u : 0u;
-        p.seg[tile] = e; // (finish_order reads it)
-    }
+            __syncthreads();
+        });
 }
 
 // one tile (the small-buffer kernel's workgroups)

@@ -39,24 +39,25 @@ constexpr int tile_offsets(int sample_type)
     return sample_type == ADSB_SAMPLE_I8 ? kTile : 2 * kThreads * kRunI16;
 }
 constexpr int kTileMax = kTile > 2 * kThreads * kRunI16 ? kTile : 2 * kThreads * kRunI16;
-// Which i8 scan kernel a context launches (adsb_create reads ADSB_SCAN from the environment; default root):
+// Which i8 scan kernel a context launches (adsb_create reads ADSB_SCAN from the environment; default root).  The product's
+// is in adsb_kernels.hip; the other four are laboratory scans, one file each under ab/, kernels in -DADSB_AB_KERNELS=1 builds only:
 //   kScanRoot: floor(sqrt(n)) per sample (v_sqrt_f32), u8 magnitudes in LDS -- the product's kernel
 //   kScanNsq : the gate runs on n = I^2+Q^2 (no root per sample; exact: DESIGN.md section 4.1b), 2 bytes of LDS per
-//              sample; the round-3 A/B kernel (fewer VALU slots, half the resident workgroups: slower)
+//              sample (ab/nsq.inc): the round-3 A/B kernel (fewer VALU slots, half the resident workgroups: slower)
 constexpr int kScanNsq = 0, kScanRoot = 1, kScanReg = 2, kScanCode = 3, kScanSieve = 4;
 //   kScanCode: the gate slides over an 8-bit LOG code of n = I^2+Q^2 (one quarter-rate v_cvt_pk_fp8_f32 per pair of samples
 //              instead of a root per sample); a superset test on codes, the few uncertain survivors are decided from the
-//              samples themselves (adsb_kernels.hip, "the code scan"): a round-4 A/B kernel (bit-exact, not faster)
+//              samples themselves (ab/code.inc): a round-4 A/B kernel (bit-exact, not faster)
 //   kScanSieve: one pair of relation bits per sample (neighbouring samples compared, no root), the gate's fourteen adjacent taps as
 //              shifts and ANDs of 64-bit words, the few candidates decided exactly from the raw samples kept in LDS
-//              (adsb_sieve.inc): the round-4 A/B kernel (bit-exact, 0.200 ms against the root scan's 0.190)
+//              (ab/sieve.inc): the round-4 A/B kernel (bit-exact, 0.200 ms against the root scan's 0.190)
 //   kScanReg : the nsq gate from registers, no LDS image (every wave a chunk of 4032 offsets; window overlap by DPP from
-//              the neighbouring lane); tiles of 16128 offsets
+//              the neighbouring lane); tiles of 16128 offsets (ab/reg.inc)
 constexpr int kRegTile = 4 * 2 * 63 * 32; // offsets per tile of the register scan: four waves x 4032
 #ifndef ADSB_SV_SWEEPS
 #define ADSB_SV_SWEEPS 8                  // 16-byte loads per lane and tile of the sieve scan (8: 16384-offset tiles, four workgroups
 #endif                                    // per CU; 6: 12288, five -- measured no faster, profiles/r04_ab_sieve.txt)
-constexpr int kSieveTile = ADSB_SV_SWEEPS * kThreads * 8; // offsets per tile of the sieve scan (adsb_sieve.inc)
+constexpr int kSieveTile = ADSB_SV_SWEEPS * kThreads * 8; // offsets per tile of the sieve scan (ab/sieve.inc)
 // offsets per tile of a context (the scan kind is fixed at adsb_create)
 constexpr int tile_offsets_of(int sample_type, int scan)
 {
@@ -157,7 +158,7 @@ constexpr int kFinishTilesPerWg = 32;
 hipError_t launch_small(hipStream_t s, int sample_type, int mag_mode, int scan, const DemodArgs &p, const FinishArgs &f,
                         const SmallArgs &sm);
 
-bool ab_kernels_built();  // -DADSB_AB_KERNELS=1: the A/B scan kernels (nsq, reg, code) are in this library
+bool ab_kernels_built();  // -DADSB_AB_KERNELS=1: the A/B scan kernels (nsq, reg, code, sieve) are in this library
 bool tile_stamps_built(); // -DADSB_TILE_STAMPS=1 diagnostic build: DemodArgs::stamps holds 64 bytes per tile
 
 // field decode of an ordered frame list (count read from hdr->n_out on the device)

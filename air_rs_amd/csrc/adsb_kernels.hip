@@ -32,8 +32,10 @@
 //   reference's mpsc channel would deliver them in.
 // Buffers of at most 32 tiles (the reference's own 20 000-sample buffers) take ONE dispatch (demod_small: the tile body
 // per workgroup, the last workgroup to arrive runs the finishing block and writes into pinned host memory).
-// The product library carries one i8 scan (kScanRoot) and CS16's; the kernels measured against it (kScanNsq, kScanReg,
-// kScanCode, kScanSieve: bit-exact, none faster) are compiled with -DADSB_AB_KERNELS=1 only.
+// This file is the product: one i8 scan (kScanRoot), CS16's, finish_order, the small-buffer kernel and the launchers.  The
+// laboratory scans measured against the root scan (kScanNsq, kScanReg, kScanCode, kScanSieve: bit-exact, none faster) live
+// in ab/nsq.inc, ab/reg.inc, ab/code.inc and ab/sieve.inc, included in one place below; their kernels are compiled with
+// -DADSB_AB_KERNELS=1 only.  They share the root scan's tile prologue and survivor hand-over (tile_prologue, hand_over).
 #include <hip/hip_ext.h>
 #include <utility>
 #include <cstdlib>
@@ -86,32 +88,12 @@ template <bool F16> __device__ __forceinline__ uint32_t pkmin3(uint32_t a, uint3
 }
 
 // [phase:1 magnitude (helpers)]  (markers read by tools/isa_slots.py)
-// Eight I^2+Q^2 sums (one 16-byte load = 8 samples) as VOP3P v_dot4_i32_i8 with the accumulator in
-// an SGPR.  Why asm: for the builtin hipcc picks the VOP2 v_dot4c form, which needs a v_mov per
-// call to preload the constant accumulator.  gfx950 needs 3 wait states between a DOT writing a
-// VGPR and a different VALU reading it; hipcc pads nothing for asm, so the block ends in s_nop 2
-// (the eight dots themselves may issue back to back).
-__device__ __forceinline__ void dot4x8_sacc(u32x4 v, int c, int n[8])
-{
-    const uint32_t a0 = v.x & 0xFFFFu, a1 = v.x & 0xFFFF0000u, a2 = v.y & 0xFFFFu, a3 = v.y & 0xFFFF0000u,
-                   a4 = v.z & 0xFFFFu, a5 = v.z & 0xFFFF0000u, a6 = v.w & 0xFFFFu, a7 = v.w & 0xFFFF0000u;
-    asm("v_dot4_i32_i8 %0, %8, %12, %20\n\t"
-        "v_dot4_i32_i8 %1, %8, %13, %20\n\t"
-        "v_dot4_i32_i8 %2, %9, %14, %20\n\t"
-        "v_dot4_i32_i8 %3, %9, %15, %20\n\t"
-        "v_dot4_i32_i8 %4, %10, %16, %20\n\t"
-        "v_dot4_i32_i8 %5, %10, %17, %20\n\t"
-        "v_dot4_i32_i8 %6, %11, %18, %20\n\t"
-        "v_dot4_i32_i8 %7, %11, %19, %20\n\t"
-        "s_nop 2"
-        : "=&v"(n[0]), "=&v"(n[1]), "=&v"(n[2]), "=&v"(n[3]), "=&v"(n[4]), "=&v"(n[5]), "=&v"(n[6]), "=&v"(n[7])
-        : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w), "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(a4), "v"(a5),
-          "v"(a6), "v"(a7), "s"(c));
-}
-
-// The same eight dots for mags8_i8, which needs only four masks: per dword x = (I0,Q0,I1,Q1), a = x . (x & 0xFFFF) =
-// c + n0 (masked, as above) and b = x . x = c + n0 + n1 (no mask); the odd sample's n1 is their difference, taken
-// inside the packed FMA mags8_i8 pays for anyway.  Same hazard rule, same s_nop 2.
+// Eight dots per 16-byte load (8 samples) for mags8_i8, as VOP3P v_dot4_i32_i8 with the accumulator c in an SGPR.  Per
+// dword x = (I0,Q0,I1,Q1): a = x . (x & 0xFFFF) = c + n0 (masked) and b = x . x = c + n0 + n1 (no mask); the odd sample's
+// n1 is their difference, taken inside the packed FMA mags8_i8 pays for anyway: four masks where one dot per sample
+// needs eight.  Why asm: for the builtin hipcc picks the VOP2 v_dot4c form, which needs a v_mov per call to preload the
+// constant accumulator.  gfx950 needs 3 wait states between a DOT writing a VGPR and a different VALU reading it;
+// hipcc pads nothing for asm, so the block ends in s_nop 2 (the eight dots themselves may issue back to back).
 __device__ __forceinline__ void dot4x8_pair_sacc(u32x4 v, int c, int a[4], int b[4])
 {
     const uint32_t m0 = v.x & 0xFFFFu, m1 = v.y & 0xFFFFu, m2 = v.z & 0xFFFFu, m3 = v.w & 0xFFFFu;
@@ -304,42 +286,9 @@ template <int ST> struct MagT;
 template <> struct MagT<ADSB_SAMPLE_I8> { typedef uint8_t type; };
 template <> struct MagT<ADSB_SAMPLE_I16> { typedef uint16_t type; };
 
-// ---- the nsq image (i8, kScanNsq): what phase 1 leaves in LDS for the gate and the slicer ------------------------
-// One dword per PAIR of samples half a tile apart: logical dword q in [0, kNsqLog) holds v(q) in its low half and
-// v(q + kNsqHalf) in its high half, v(k) = I_k^2 + Q_k^2 + 72 (<= 32840).  That pair is exactly what lane L's
-// two runs (offsets 32 L + o and kNsqHalf + 32 L + o) need in one VGPR at step o: the gate reads it as it is, no
-// unpacking.  Dwords kNsqHalf .. kNsqHalf+255 repeat samples as low halves that dwords 0..255 hold as high halves
-// (the halo of run A's last lanes).  Physical dword = q + 4 (q >> 6): four pad dwords per 64 put the 16-byte reads
-// of a ds_read_b128 lane group (lane L starts at 32 L) on sixteen different slots of the 64 banks.
-constexpr int kNsqBias = 72;                 // 9 * 8: (v >> 3) = (n >> 3) + 9 exactly
-constexpr int kNsqHalf = kTile / 2;          // 8192
-constexpr int kNsqLog = kNsqHalf + kHalo;    // logical dwords
-#ifndef ADSB_NSQ_PAD_SHIFT
-#define ADSB_NSQ_PAD_SHIFT 6 // four pad dwords per 2^6 logical dwords (5: per 32 -- also conflict-free for the stores, 6 % more LDS)
-#endif
-constexpr int kNsqPadShift = ADSB_NSQ_PAD_SHIFT;
-__host__ __device__ constexpr uint32_t nsq_phys(uint32_t q) { return q + 4u * (q >> kNsqPadShift); }
-constexpr int kNsqPhys = (int)nsq_phys(kNsqLog);  // 8976 dwords = 35904 bytes
-static_assert(kNsqHalf % 64 == 0 && kHalo % 64 == 0 && kRun == 32 && (kNsqPadShift == 5 || kNsqPadShift == 6),
-              "nsq image: pads every 32 or 64 dwords, runs of 32");
-
-// The u8 magnitude image of the i8 root scan, optionally padded (-DADSB_MAG_PAD=1): 16 bytes after every 256.  The gate's
-// ds_read_b128 has lane L start at byte 32 L: the sixteen lanes of a read group span 512 bytes, two passes over the 64
-// banks (lanes L and L + 8 on the same four banks: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.27 for the kernel).  With
-// the pad lanes 8-15 sit four banks further: conflict-free.  Physical byte = b + 16 (b >> 8).
-#ifndef ADSB_MAG_PAD
-#define ADSB_MAG_PAD 0
-#endif
-template <int ST, int SCAN> struct MagPad {
-    static constexpr bool on = ADSB_MAG_PAD != 0 && ST == ADSB_SAMPLE_I8 && SCAN == kScanRoot;
-};
-template <bool PAD> __host__ __device__ constexpr uint32_t mag_phys(uint32_t b) { return PAD ? b + 16u * (b >> 8) : b; }
-
-template <int ST, int SCAN = kScanRoot> struct Lds {
+template <int ST> struct Lds {
     typedef typename MagT<ST>::type mag_t;
-    static constexpr bool kNsq = ST == ADSB_SAMPLE_I8 && SCAN == kScanNsq;
-    static constexpr int kMagBytes = kNsq ? kNsqPhys * 4
-                                          : (int)((mag_phys<MagPad<ST, SCAN>::on>((uint32_t)TileCfg<ST>::kMagT * (uint32_t)sizeof(mag_t)) + 15u) & ~15u);
+    static constexpr int kMagBytes = (TileCfg<ST>::kMagT * (int)sizeof(mag_t) + 15) & ~15;
     static constexpr int kOffCand = kMagBytes;                 // one word per run of 32 offsets: survivor bitmap
     static constexpr int kOffList = kOffCand + 2 * kThreads * 4 * ((TileCfg<ST>::kRunT + 31) / 32); // kListCap x u16
     static constexpr int kOffMisc = kOffList + kListCap * 2;   // 16 x u32
@@ -388,14 +337,6 @@ __device__ __forceinline__ uint32_t row16_xor(uint32_t v)
     v ^= ADSB_DPP(v, 0x140); // row_mirror
     return v;
 }
-__device__ __forceinline__ uint32_t row16_sum(uint32_t v)
-{
-    v += ADSB_DPP(v, 0xB1);
-    v += ADSB_DPP(v, 0x4E);
-    v += ADSB_DPP(v, 0x141);
-    v += ADSB_DPP(v, 0x140);
-    return v;
-}
 
 // ---- PPM slice + CRC-24 + single-bit repair of one candidate by a 16-lane group --------------------------
 // Lane l slices frame byte l (magnitudes off+16+16l .. +15, demod.rs:97-101).  The 24-byte record
@@ -404,7 +345,7 @@ __device__ __forceinline__ uint32_t row16_sum(uint32_t v)
 // [phase:3 slice_byte (helper; inlined twice)]
 // The PPM slice of one frame byte (demod.rs:92-131 + 180-201 in closed form): bit (7-k) = m[16 lb + 2k] > m[16 lb + 2k + 1]
 // over the magnitudes off+16+16*lb .. +15 of the tile in LDS; strict, a tie gives 0.
-template <int ST, bool PAD = false>
+template <int ST>
 __device__ __forceinline__ uint32_t slice_byte(const typename MagT<ST>::type *mag, const uint32_t off, const uint32_t lb)
 {
     uint32_t byte = 0;
@@ -417,18 +358,7 @@ __device__ __forceinline__ uint32_t slice_byte(const typename MagT<ST>::type *ma
         const uint32_t pidx = off + 16 + 16 * lb;
         const uint32_t *mw = reinterpret_cast<const uint32_t *>(mag) + (pidx >> 2);
         const uint32_t sh = pidx & 3;
-        uint32_t d0, d1, d2, d3, d4;
-        if constexpr (PAD) { // (the five dwords may lie either side of a pad: physical dword = d + 4 (d >> 6))
-            const uint32_t *m0 = reinterpret_cast<const uint32_t *>(mag);
-            const uint32_t di = pidx >> 2;
-            d0 = m0[di + 4u * (di >> 6)];
-            d1 = m0[di + 1u + 4u * ((di + 1u) >> 6)];
-            d2 = m0[di + 2u + 4u * ((di + 2u) >> 6)];
-            d3 = m0[di + 3u + 4u * ((di + 3u) >> 6)];
-            d4 = m0[di + 4u + 4u * ((di + 4u) >> 6)];
-        } else {
-            d0 = mw[0], d1 = mw[1], d2 = mw[2], d3 = mw[3], d4 = mw[4];
-        }
+        const uint32_t d0 = mw[0], d1 = mw[1], d2 = mw[2], d3 = mw[3], d4 = mw[4];
         uint32_t w[4] = {__builtin_amdgcn_alignbyte(d1, d0, sh), __builtin_amdgcn_alignbyte(d2, d1, sh),
                          __builtin_amdgcn_alignbyte(d3, d2, sh), __builtin_amdgcn_alignbyte(d4, d3, sh)};
         // dword k = [a0, b0, a1, b1] holds pairs 2k and 2k+1, bit = (a > b), MSB first: one SDWA byte compare per
@@ -458,70 +388,6 @@ __device__ __forceinline__ uint32_t slice_byte(const typename MagT<ST>::type *ma
             : "vcc");
     }
     return byte;
-}
-
-// [phase:3 slice_byte (nsq image)]
-// The same slice from the nsq image (i8, kScanNsq).  The reference compares truncated roots (demod.rs:106 on the
-// output of utils.rs:46-52): bit = floor(sqrt(x)) > floor(sqrt(y)) = (r * r > y) with r = floor(sqrt(x)) -- r * r is the
-// largest square <= x, so a square lies in (y, x] exactly when r * r > y.  One root per PAIR, survivors only
-// (224 samples per survivor ~ 0.1 roots per sample of the stream).  r = trunc(sqrtf(x + 0.5)) is exact for x <= 32768
-// (sqrt(x + 0.5) is >= 1.3e-3 from every integer there; v_sqrt_f32 errs by 1 ulp ~ 1e-5).
-// A 16-lane group works on one survivor at tile offset `off`; the group's window of 224 samples starts at logical
-// dword q + 16 of its half (half = off >= kNsqHalf).  Lane l reads the 16 consecutive samples of 16-aligned chunk
-// (q + 16) / 16 + l, moved up by one sample when q + 16 is odd (so that pairs never straddle two lanes), slices its
-// 8 pairs, and frame byte l is put together from the chunks of lanes l and l + 1 (one DPP row shift):
-// chunk bit j of lane l is frame bit 8 l + j - sh, sh = ((q + 16) % 16) / 2.  All 16 lanes of a group must be active.
-__device__ __forceinline__ uint32_t nsq_slice_byte(const uint32_t *img, const uint32_t off, const uint32_t l)
-{
-    const uint32_t half = off >= (uint32_t)kNsqHalf ? 1u : 0u;
-    const uint32_t base = off - half * (uint32_t)kNsqHalf + 16u; // logical dword of the first data sample
-    const uint32_t e = base & 15u, par = e & 1u, sh = e >> 1;
-    const uint32_t v = (base >> 4) + l;                            // this lane's 16-sample chunk
-    const uint32_t a1 = nsq_phys(16u * v) + par;                  // physical dword of its first sample
-    // its last sample sits behind a pad when the chunk ends a padded block and was moved up by one
-    constexpr uint32_t kChunksPerBlock = (1u << kNsqPadShift) / 16u;
-    const uint32_t a2 = a1 + 15u + (((v & (kChunksPerBlock - 1u)) == kChunksPerBlock - 1u ? 4u : 0u) & (0u - par));
-    uint32_t d[16];
-#pragma unroll
-    for (int j = 0; j < 15; ++j) d[j] = img[a1 + j];
-    d[15] = img[a2];
-    // (x, y) of a pair into one register: x in the low half, y in the high half (selectors 0-3: 2nd operand)
-    const uint32_t sel = half ? 0x07060302u : 0x05040100u;
-    uint32_t w[8], r2[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        w[j] = __builtin_amdgcn_perm(d[2 * j + 1], d[2 * j], sel);
-        const float fx = (float)(w[j] & 0xFFFFu) - ((float)kNsqBias - 0.5f); // n + 0.5
-        const uint32_t r = (uint32_t)__builtin_amdgcn_sqrtf(fx);
-        r2[j] = __umul24(r, r) + (uint32_t)kNsqBias; // (r <= 181; one v_mad_u32_u24)
-    }
-    // bit j = r2 > y, MSB first: one SDWA compare per pair into its own SGPR pair, then chunk = chunk + chunk +
-    // carry-in per pair (v_addc): no v_cndmask.  All eight compares come first: gfx950 wants 2 wait states between a
-    // VALU writing an SGPR and a VALU reading it, and hipcc pads nothing inside asm.
-    uint32_t chunk = 0;
-    uint64_t m0, m1, m2, m3, m4, m5, m6, m7;
-    asm("v_cmp_gt_u32_sdwa %1, %9, %17 src0_sel:DWORD src1_sel:WORD_1\n\t"
-        "v_cmp_gt_u32_sdwa %2, %10, %18 src0_sel:DWORD src1_sel:WORD_1\n\t"
-        "v_cmp_gt_u32_sdwa %3, %11, %19 src0_sel:DWORD src1_sel:WORD_1\n\t"
-        "v_cmp_gt_u32_sdwa %4, %12, %20 src0_sel:DWORD src1_sel:WORD_1\n\t"
-        "v_cmp_gt_u32_sdwa %5, %13, %21 src0_sel:DWORD src1_sel:WORD_1\n\t"
-        "v_cmp_gt_u32_sdwa %6, %14, %22 src0_sel:DWORD src1_sel:WORD_1\n\t"
-        "v_cmp_gt_u32_sdwa %7, %15, %23 src0_sel:DWORD src1_sel:WORD_1\n\t"
-        "v_cmp_gt_u32_sdwa %8, %16, %24 src0_sel:DWORD src1_sel:WORD_1\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %1\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %2\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %3\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %4\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %5\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %6\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %7\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %8"
-        : "+v"(chunk), "=&s"(m0), "=&s"(m1), "=&s"(m2), "=&s"(m3), "=&s"(m4), "=&s"(m5), "=&s"(m6), "=&s"(m7)
-        : "v"(r2[0]), "v"(r2[1]), "v"(r2[2]), "v"(r2[3]), "v"(r2[4]), "v"(r2[5]), "v"(r2[6]), "v"(r2[7]),
-          "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]), "v"(w[6]), "v"(w[7])
-        : "vcc");
-    const uint32_t next = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)chunk, 0x101 /* row_shl:1 */, 0xF, 0xF, true);
-    return (((chunk << 8) | next) >> (8u - sh)) & 0xFFu;
 }
 
 // [phase:3 count_candidate (tiles without slots only: cold)]
@@ -600,26 +466,14 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const DemodArgs &p, 
 #define TSTAMP(k) do { } while (0)
 #endif
 
-#ifndef ADSB_ABL_PHASES
-#define ADSB_ABL_PHASES 3 // measurement only (no frames come out below 3): 1 = magnitudes only, 2 = magnitudes + gate
-#endif
-#ifndef ADSB_ABL_NOCMP
-#define ADSB_ABL_NOCMP 0 // measurement only (wrong results): gate without compares and branches
-#endif
 // The product library carries ONE i8 scan kernel (kScanRoot; x its three magnitude modes) and CS16's.  The kernels round 3 and
-// round 4 measured against it -- kScanNsq, kScanReg, kScanCode: all bit-exact, none faster -- are compiled only with
+// round 4 measured against it -- kScanNsq, kScanReg, kScanCode, kScanSieve (ab/*.inc): all bit-exact, none faster -- are compiled only with
 // -DADSB_AB_KERNELS=1 (build.sh puts that build in air_rs_amd/lib/variants/libadsb_hip_ab.so; tests/test_gpu_ab_kernels.py
 // runs one parity smoke per kernel through it; tools/gpu/ab.sh times them).
 #ifndef ADSB_AB_KERNELS
 #define ADSB_AB_KERNELS 0
 #endif
 bool ab_kernels_built() { return ADSB_AB_KERNELS != 0; }
-#ifndef ADSB_PRIO
-#define ADSB_PRIO 0 // A/B (s_setprio): 1 = prologue + loads at priority 3, 2 = phase 3 at priority 2, 3 = both
-#endif
-#ifndef ADSB_GATE_GROUP
-#define ADSB_GATE_GROUP 1 // steps per wave-uniform test in demod_tiles (see gate_phase)
-#endif
 
 // survivor bitmap words -> the lane's survivors appended (unordered) to the LDS list; shared by both gates
 template <int RUN, int NT>
@@ -670,23 +524,17 @@ __device__ __forceinline__ void gate_collect(uint32_t *candA, uint32_t *candB, u
     }
 }
 
-// ---- the gate (phase 2 of both tile kernels) --------------------------------------------------
+// ---- the gate (phase 2 of the tile kernels) --------------------------------------------------
 // Preamble + DF17 ordering test (demod.rs:17-57) for the 2 x kRun offsets this lane owns:
 // run A = offsets [tid*RUN, +RUN), run B = [(tid+NT)*RUN, +RUN) of the tile whose magnitudes
 // are in `mag`.  Survivors are OR-ed into the lane's words of the LDS bitmap `cand` and appended,
-// unordered, to `list` (their number is added to *count).  No barriers inside (except what `hook`, called
-// before step HOOK_AT, does); `tid` < NT; 2 NT RUN = kTile.
-struct NoHook {
-    __device__ __forceinline__ void operator()() const {}
-};
-
+// unordered, to `list` (their number is added to *count).  No barriers inside; `tid` < NT; 2 NT RUN = kTile.
 // [phase:2 gate: set-up]
-template <int ST, int GROUP, int RUN, int NT, int HOOK_AT = -1, class HOOK = NoHook, bool F16OK = (ST == ADSB_SAMPLE_I8), bool PAD = false>
+template <int ST, int RUN, int NT, bool F16OK = (ST == ADSB_SAMPLE_I8)>
 __device__ __forceinline__ void gate_phase(const typename MagT<ST>::type *mag, uint32_t *cand, uint16_t *list,
-                                           uint32_t *count, const uint32_t tid, const uint32_t n_valid,
-                                           HOOK hook = HOOK())
+                                           uint32_t *count, const uint32_t tid, const uint32_t n_valid)
 {
-    static_assert(RUN % GROUP == 0 && (RUN == 16 || RUN == 32 || RUN == 64), "steps are taken GROUP at a time; 1 or 2 bitmap words per run");
+    static_assert(RUN == 16 || RUN == 32 || RUN == 64, "1 or 2 bitmap words per run");
     constexpr int WPR = (RUN + 31) / 32; // bitmap words per run (a run of 16 uses the low half of its word)
     constexpr int SPG = 16 / (int)sizeof(typename MagT<ST>::type); // magnitudes per 16-byte LDS granule
     // Survivor bitmap: WPR words per run (offset min(RUN, 32) w + b of the tile is bit b of word w), owned by this
@@ -696,25 +544,17 @@ __device__ __forceinline__ void gate_phase(const typename MagT<ST>::type *mag, u
     for (int k = 0; k < WPR; ++k) candA[k] = candB[k] = 0u;
     // (offsets at or beyond n_valid do not exist in the reference loop, adsb.rs:98: masked out in gate_collect)
     constexpr int kGran = (RUN + 26 + SPG - 1) / SPG + 1; // granules a run may touch
-    static_assert(!PAD || (ST == ADSB_SAMPLE_I8 && RUN == 32 && (NT * RUN) % 256 == 0), "the padded image: u8 magnitudes, runs of 32 bytes");
-    // (padded image: a run starts at physical byte 32 k + 16 (k >> 3); its granules 2 and 3 lie behind the next pad for
-    // the last run of a 256-byte row, k % 8 == 7 -- the same lanes for both runs, NT being a multiple of 8: a second
-    // base pointer, no arithmetic per granule)
-    const u32x4 *ga = reinterpret_cast<const u32x4 *>(mag + mag_phys<PAD>(tid * RUN));
-    const u32x4 *gb = reinterpret_cast<const u32x4 *>(mag + mag_phys<PAD>((tid + NT) * RUN));
-    const uint32_t hop = PAD && (tid & 7u) == 7u ? 1u : 0u;
-    const u32x4 *ga2 = ga + hop, *gb2 = gb + hop;
+    const u32x4 *ga = reinterpret_cast<const u32x4 *>(mag + tid * RUN);
+    const u32x4 *gb = reinterpret_cast<const u32x4 *>(mag + (tid + NT) * RUN);
     uint32_t ra[kGran * 4], rb[kGran * 4];
     constexpr int kAhead = 48 / SPG; // granules resident ahead of the current block
 #pragma unroll
     for (int g = 0; g < kAhead; ++g) {
-        u32x4 a = (PAD && g >= 2) ? ga2[g] : ga[g], b = (PAD && g >= 2) ? gb2[g] : gb[g];
+        u32x4 a = ga[g], b = gb[g];
         ra[4 * g] = a.x; ra[4 * g + 1] = a.y; ra[4 * g + 2] = a.z; ra[4 * g + 3] = a.w;
         rb[4 * g] = b.x; rb[4 * g + 1] = b.y; rb[4 * g + 2] = b.z; rb[4 * g + 3] = b.w;
     }
 
-    // Sliding state shared by neighbouring offsets (all indices are compile-time after
-    // unrolling): N[j] sample pair, H2[j] = min(N[j], N[j+2]), W3[j] = max(N[j..j+2]).
     // Sliding state shared by neighbouring offsets (all indices are compile-time after
     // unrolling).  With F[j] = max N[j + {0,2,3,4,5}] the twelve low slots of offset o are
     // F[o+1] u F[o+8] u {o+13,14,15}: one new W3, one new F and one 3-input max per offset.
@@ -731,92 +571,50 @@ __device__ __forceinline__ void gate_phase(const typename MagT<ST>::type *mag, u
     for (int j = 1; j < 8; ++j) F[j] = pkmax3<F16OK>(N[j], W3[j + 2], N[j + 5]);
 
     // [phase:2 gate: steps]
-    // GROUP consecutive steps share one wave-uniform test: their 8 x GROUP min/max instructions form one
-    // basic block (independent chains the scheduler can interleave) and the common path takes one
-    // scalar branch per GROUP steps.  GROUP = 1 is what the many-waves-per-SIMD tile kernel uses; the
-    // streaming kernel, whose gate waves are alone on their SIMD's VALU, needs the larger blocks.
-#if ADSB_ABL_NOCMP
-    uint32_t abl_acc = 0;
-#endif
+    // Every step ends in one wave-uniform test: the common path takes one scalar branch per step (what the
+    // many-waves-per-SIMD tile kernel wants: other waves fill the gaps between a step's 8 min/max instructions).
 #pragma unroll
-    for (int o0 = 0; o0 < RUN; o0 += GROUP) {
-        if (o0 == HOOK_AT) hook(); // the streaming kernel places a workgroup barrier inside the gate
-        bool pa[GROUP], pb[GROUP];
-        bool any = false; // per lane; the wave-wide OR is one ballot below (an s_or chain of the compare masks)
-#pragma unroll
-        for (int gi = 0; gi < GROUP; ++gi) {
-            const int o = o0 + gi;
-            if (o % SPG == 0) { // keep 48 samples resident ahead of the block that starts here
-                const int g = o / SPG + kAhead;
-                if (g * SPG < RUN + 26) {
-                    u32x4 a = (PAD && g >= 2) ? ga2[g] : ga[g], b = (PAD && g >= 2) ? gb2[g] : gb[g];
-                    ra[4 * g] = a.x; ra[4 * g + 1] = a.y; ra[4 * g + 2] = a.z; ra[4 * g + 3] = a.w;
-                    rb[4 * g] = b.x; rb[4 * g + 1] = b.y; rb[4 * g + 2] = b.z; rb[4 * g + 3] = b.w;
-                }
+    for (int o = 0; o < RUN; ++o) {
+        if (o % SPG == 0) { // keep 48 samples resident ahead of the block that starts here
+            const int g = o / SPG + kAhead;
+            if (g * SPG < RUN + 26) {
+                u32x4 a = ga[g], b = gb[g];
+                ra[4 * g] = a.x; ra[4 * g + 1] = a.y; ra[4 * g + 2] = a.z; ra[4 * g + 3] = a.w;
+                rb[4 * g] = b.x; rb[4 * g + 1] = b.y; rb[4 * g + 2] = b.z; rb[4 * g + 3] = b.w;
             }
-            // pairs are unpacked 26 samples ahead so the (rare) DF17 check below finds its ten
-            // samples already in registers
-            N[o + 25] = pair_at<ST>(ra, rb, o + 25);
-            W3[o + 13] = pkmax3<F16OK>(N[o + 13], N[o + 14], N[o + 15]);
-            F[o + 8] = pkmax3<F16OK>(N[o + 8], W3[o + 10], N[o + 13]);           // lows 8,10,11,12,13
-            const uint32_t lo = pkmax3<F16OK>(F[o + 1], F[o + 8], W3[o + 13]);   // + 1,3,4,5,6 + 13,14,15
-            H2[o + 7] = pkmin(N[o + 7], N[o + 9]);
-            const uint32_t hi = pkmin(H2[o], H2[o + 7]);                      // highs 0,2,7,9
-#if ADSB_ABL_NOCMP
-            abl_acc ^= hi ^ lo; // measurement only: keeps the min/max chain alive without compares/branches
-            pa[gi] = pb[gi] = false;
-#else
-            pa[gi] = (uint16_t)hi >= (uint16_t)lo;
-            pb[gi] = (hi >> 16) >= (lo >> 16);
-            any |= pa[gi] | pb[gi];
-#endif
         }
+        // pairs are unpacked 26 samples ahead so the (rare) DF17 check below finds its ten
+        // samples already in registers
+        N[o + 25] = pair_at<ST>(ra, rb, o + 25);
+        W3[o + 13] = pkmax3<F16OK>(N[o + 13], N[o + 14], N[o + 15]);
+        F[o + 8] = pkmax3<F16OK>(N[o + 8], W3[o + 10], N[o + 13]);           // lows 8,10,11,12,13
+        const uint32_t lo = pkmax3<F16OK>(F[o + 1], F[o + 8], W3[o + 13]);   // + 1,3,4,5,6 + 13,14,15
+        H2[o + 7] = pkmin(N[o + 7], N[o + 9]);
+        const uint32_t hi = pkmin(H2[o], H2[o + 7]);                      // highs 0,2,7,9
+        const bool pa = (uint16_t)hi >= (uint16_t)lo;
+        const bool pb = (hi >> 16) >= (lo >> 16);
         // [phase:2 gate: DF17 (cold)]
-        // wave-uniform test (a scalar branch, no exec juggling): the block below is entered by
-        // the whole wave when any lane passes; its effects are masked by pa/pb anyway
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(any) != 0, 0)) {
-#pragma unroll
-            for (int gi = 0; gi < GROUP; ++gi) {
-                const int o = o0 + gi;
-                if (GROUP == 1 || __builtin_amdgcn_ballot_w64(pa[gi] | pb[gi]) != 0) {
-                    // DF17 part of the gate (demod.rs:45-54)
-                    const uint32_t dh = pkmin3<F16OK>(pkmin3<F16OK>(N[o + 16], N[o + 19], N[o + 21]), N[o + 23], N[o + 24]);
-                    const uint32_t dl = pkmax3<F16OK>(pkmax3<F16OK>(N[o + 17], N[o + 18], N[o + 20]), N[o + 22], N[o + 25]);
-                    const bool da = (uint16_t)dh >= (uint16_t)dl;
-                    const bool db = (dh >> 16) >= (dl >> 16);
-                    // (offsets at or beyond n_valid are masked out of the bitmap words after the loop, in the one
-                    // tile per channel that has any, instead of two compares here)
-                    uint32_t bit = 1u << (o & 31);
-                    asm("" : "+v"(bit)); // one v_mov for both stores (hipcc rematerialises the constant per exec region)
-                    if (pa[gi] & da) atomicOr(candA + (o >> 5), bit);
-                    if (pb[gi] & db) atomicOr(candB + (o >> 5), bit);
-                }
-            }
+        // wave-uniform test (a scalar branch, no exec juggling; the wave-wide OR is one ballot, an s_or of the compare
+        // masks): the block below is entered by the whole wave when any lane passes; its effects are masked by pa/pb anyway
+        if (__builtin_expect(__builtin_amdgcn_ballot_w64(pa | pb) != 0, 0)) {
+            // DF17 part of the gate (demod.rs:45-54)
+            const uint32_t dh = pkmin3<F16OK>(pkmin3<F16OK>(N[o + 16], N[o + 19], N[o + 21]), N[o + 23], N[o + 24]);
+            const uint32_t dl = pkmax3<F16OK>(pkmax3<F16OK>(N[o + 17], N[o + 18], N[o + 20]), N[o + 22], N[o + 25]);
+            const bool da = (uint16_t)dh >= (uint16_t)dl;
+            const bool db = (dh >> 16) >= (dl >> 16);
+            // (offsets at or beyond n_valid are masked out of the bitmap words after the loop, in the one
+            // tile per channel that has any, instead of two compares here)
+            uint32_t bit = 1u << (o & 31);
+            asm("" : "+v"(bit)); // one v_mov for both stores (hipcc rematerialises the constant per exec region)
+            if (pa & da) atomicOr(candA + (o >> 5), bit);
+            if (pb & db) atomicOr(candB + (o >> 5), bit);
         }
     }
     // [phase:2 gate: survivor list]
-#if ADSB_ABL_NOCMP
-    if (abl_acc == 0x12345678u) atomicOr(candA, 1u);
-#endif
     gate_collect<RUN, NT>(candA, candB, list, count, tid, n_valid);
 }
 
 // [phase:end]
-// The same descriptor as four dwords (for inline asm): base, base_hi (stride 0), num_records, flags.
-template <int BPS, int MAG = kMag>
-__device__ __forceinline__ u32x4 tile_rsrc_words(const DemodArgs &p, const TilePos &t, bool live)
-{
-    const uint64_t base = (uint64_t)(uintptr_t)((const char *)p.iq + ((uint64_t)t.ch * p.channel_stride + t.sample0) * BPS);
-    const uint64_t remain = (p.n_samples - t.sample0) * BPS;
-    const uint32_t nrec = remain > (uint64_t)(MAG * BPS) ? (uint32_t)(MAG * BPS) : (uint32_t)remain;
-    u32x4 w;
-    w.x = __builtin_amdgcn_readfirstlane((uint32_t)base);
-    w.y = __builtin_amdgcn_readfirstlane((uint32_t)(base >> 32) & 0xFFFFu);
-    w.z = __builtin_amdgcn_readfirstlane(live ? nrec : 0u);
-    w.w = 0x00020000u;
-    return w;
-}
-
 // Cache policy of the streaming IQ loads: 2 = nt (read once, do not keep): measured 3 % faster than the
 // default policy on the 1 GiB buffer (0.233 vs 0.241 ms).
 #ifndef ADSB_LOAD_AUX
@@ -850,7 +648,7 @@ __device__ __forceinline__ void issue_tile_loads(const DemodArgs &p, const TileP
 
 // raw IQ -> magnitudes in LDS (u8 for i8 input, u16 for i16).  Returns (wave-uniform, CS16 only) whether this wave saw
 // a magnitude that is not an ordered f16 bit pattern (>= 0x7C00 = 31744): the gate then takes its integer form.
-template <int ST, int MAGMODE, bool PAD = false>
+template <int ST, int MAGMODE>
 __device__ __forceinline__ bool magnitudes_to_lds(const u32x4 (&raw)[P1<ST>::kIters], typename MagT<ST>::type *mag, uint32_t tid)
 {
     uint32_t mx = 0;
@@ -865,222 +663,186 @@ __device__ __forceinline__ bool magnitudes_to_lds(const u32x4 (&raw)[P1<ST>::kIt
                 mags4_i16(raw[it], lo, hi);
                 mx = pkmax(mx, pkmax(lo, hi)); // (samples past the channel end read as zero)
             }
-            // (padded image: s = it * 2048 + 8 tid, so s >> 8 = 8 it + (tid >> 5): the pad is a constant per sweep plus a
-            // per-lane term -- written out so that the sweep's part folds into the store's immediate offset)
-            const uint32_t sp = PAD ? s + 16u * (tid >> 5) + (uint32_t)it * (16u * (kThreads * P1<ST>::kSPL / 256)) : s;
-            if (s < (uint32_t)TileCfg<ST>::kMagT) *reinterpret_cast<uint2 *>(mag + sp) = make_uint2(lo, hi);
+            if (s < (uint32_t)TileCfg<ST>::kMagT) *reinterpret_cast<uint2 *>(mag + s) = make_uint2(lo, hi);
         }
     }
     return ST == ADSB_SAMPLE_I16 && __builtin_amdgcn_ballot_w64(((mx & 0xFFFFu) >= 0x7C00u) || ((mx >> 16) >= 0x7C00u)) != 0;
 }
 
-// [phase:1 nsq (loads, dots, stores)]
-// ---- phase 1 of the nsq scan: raw i8 IQ -> the nsq image --------------------------------------------------------
-// One sweep of a lane = 16 bytes at sample q0 (eight "A" samples, low halves) and 16 bytes at sample q0 + kNsqHalf
-// (eight "B" samples, high halves) -> eight packed dwords -> two ds_write_b128.  kNsqIters sweeps of the workgroup
-// cover the image; the last one is the 256-dword halo (lanes 0-31 only).
-constexpr int kNsqIters = (kNsqLog + kThreads * 8 - 1) / (kThreads * 8);
-constexpr int kNsqFull = kNsqLog / (kThreads * 8);  // sweeps every lane takes part in
-constexpr int kNsqTail = kNsqLog % (kThreads * 8);  // logical dwords of the last, partial sweep (the halo: 256)
-static_assert(kNsqIters - kNsqFull <= 1 && kNsqTail % 8 == 0, "at most one partial sweep of whole lanes");
-
-__device__ __forceinline__ void nsq_issue_loads(const DemodArgs &p, const TilePos &tp, uint32_t tid,
-                                                u32x4 (&ra)[kNsqIters], u32x4 (&rb)[kNsqIters])
+// [phase:1 magnitude (loads, stores)]
+// The tile prologue of every scan, between the issue of a tile's loads and their first use: the launch's first workgroup
+// clears the result header's flags, every workgroup its two LDS counters.
+__device__ __forceinline__ void clear_launch_flags(const DemodArgs &p, const bool first, const uint32_t tid)
 {
-    __amdgpu_buffer_rsrc_t rsrc = tile_rsrc<2, kMag>(p, tp, true);
-    // (the sweep's constant goes into the SGPR offset, which the descriptor's bounds check covers:
-    // tools/ubench/soffset_probe.hip; reads past the channel end return zeros)
-#pragma unroll
-    for (int it = 0; it < kNsqFull; ++it) {
-        ra[it] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, tid * 16, (uint32_t)it * (kThreads * 16), ADSB_LOAD_AUX);
-        rb[it] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, tid * 16, (uint32_t)it * (kThreads * 16) + 2 * kNsqHalf, ADSB_LOAD_AUX);
+    if (tid == 0 && first) {
+        p.hdr->retry = 0;
+        if (p.count_groups) { // first pass of a launch: the finishing kernel ORs this launch's flags in
+            p.hdr->flags = 0;
+            if (p.hdr_pub) p.hdr_pub[2] = 0;
+        }
     }
-    if (kNsqTail && __builtin_amdgcn_readfirstlane(tid & ~63u) * 8 < (uint32_t)kNsqTail) { // (whole waves past the halo skip it)
-        ra[kNsqFull] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, tid * 16, (uint32_t)kNsqFull * (kThreads * 16), ADSB_LOAD_AUX);
-        rb[kNsqFull] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, tid * 16, (uint32_t)kNsqFull * (kThreads * 16) + 2 * kNsqHalf, ADSB_LOAD_AUX);
+}
+__device__ __forceinline__ void tile_prologue(const DemodArgs &p, const bool first, uint32_t *misc, const uint32_t tid)
+{
+    clear_launch_flags(p, first, tid);
+    if (tid == 0) {
+        misc[8] = 0;  // valid-frame counter (tiles without slots only)
+        misc[12] = 0; // survivor counter
     }
 }
 
-// 8 A samples + 8 B samples -> 8 dwords (B's v << 16) | A's v, v = I^2 + Q^2 + 72.
-//   A: v_and (the sample's two bytes) + v_dot4_i32_i8 accumulating onto the SGPR constant 0x00480048 (the bias of
-//      both halves at once);
-//   B: v_perm to the i16 pair (I * 256, Q * 256) + v_dot2_i32_i16 accumulating onto A's result: (I^2 + Q^2) << 16.
-//      (n = 32768, I = Q = -128, wraps to the right bits.)
-// 2 VALU per sample, packing included.  gfx950 wants 3 wait states between a DOT and a different VALU reading its
-// result and hipcc pads nothing inside asm: the dot2 reads its dot4 eight instructions later, and the block ends in
-// s_nop 2.
-__device__ __forceinline__ void nsq_pack16(u32x4 a, u32x4 b, uint32_t (&d)[8])
+// [phase:3 hand-over: slots, offsets, sliced bytes]
+// ---- phase 3 of every scan: the survivor hand-over -------------------------------------------------------------------
+// Every survivor gets a frame slot, its absolute offset and its 14 sliced bytes (the image is here, in
+// LDS).  CRC-24, repair, ordering inside the tile and the valid-frame count are finish_order's work, one
+// LANE per survivor instead of sixteen.  (With the whole decode in this kernel a tile's 33 KB of LDS were
+// held through a latency-bound epilogue: 19 % of the kernel time for 13 % of its instructions.)
+
+// One record by its 16-lane group, one lane per frame byte: offset + 14 raw bytes (no CRC verdict yet).
+__device__ __forceinline__ void put_record(adsb_frame *slot, const uint64_t o64, const uint32_t byte, const uint32_t l)
 {
-    const uint32_t a0 = a.x & 0xFFFFu, a1 = a.x & 0xFFFF0000u, a2 = a.y & 0xFFFFu, a3 = a.y & 0xFFFF0000u,
-                   a4 = a.z & 0xFFFFu, a5 = a.z & 0xFFFF0000u, a6 = a.w & 0xFFFFu, a7 = a.w & 0xFFFF0000u;
-    // bytes [0, I, 0, Q] of the even / odd sample of a dword (selector 0x0C = a zero byte)
-    const uint32_t h0 = __builtin_amdgcn_perm(b.x, b.x, 0x010C000Cu), h1 = __builtin_amdgcn_perm(b.x, b.x, 0x030C020Cu),
-                   h2 = __builtin_amdgcn_perm(b.y, b.y, 0x010C000Cu), h3 = __builtin_amdgcn_perm(b.y, b.y, 0x030C020Cu),
-                   h4 = __builtin_amdgcn_perm(b.z, b.z, 0x010C000Cu), h5 = __builtin_amdgcn_perm(b.z, b.z, 0x030C020Cu),
-                   h6 = __builtin_amdgcn_perm(b.w, b.w, 0x010C000Cu), h7 = __builtin_amdgcn_perm(b.w, b.w, 0x030C020Cu);
-    const uint32_t bias2 = (uint32_t)kNsqBias * 0x00010001u;
-    asm("v_dot4_i32_i8 %0, %8, %12, %28\n\t"
-        "v_dot4_i32_i8 %1, %8, %13, %28\n\t"
-        "v_dot4_i32_i8 %2, %9, %14, %28\n\t"
-        "v_dot4_i32_i8 %3, %9, %15, %28\n\t"
-        "v_dot4_i32_i8 %4, %10, %16, %28\n\t"
-        "v_dot4_i32_i8 %5, %10, %17, %28\n\t"
-        "v_dot4_i32_i8 %6, %11, %18, %28\n\t"
-        "v_dot4_i32_i8 %7, %11, %19, %28\n\t"
-        "v_dot2_i32_i16 %0, %20, %20, %0\n\t"
-        "v_dot2_i32_i16 %1, %21, %21, %1\n\t"
-        "v_dot2_i32_i16 %2, %22, %22, %2\n\t"
-        "v_dot2_i32_i16 %3, %23, %23, %3\n\t"
-        "v_dot2_i32_i16 %4, %24, %24, %4\n\t"
-        "v_dot2_i32_i16 %5, %25, %25, %5\n\t"
-        "v_dot2_i32_i16 %6, %26, %26, %6\n\t"
-        "v_dot2_i32_i16 %7, %27, %27, %7\n\t"
-        "s_nop 2"
-        : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[2]), "=&v"(d[3]), "=&v"(d[4]), "=&v"(d[5]), "=&v"(d[6]), "=&v"(d[7])
-        : "v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w), "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(a4), "v"(a5), "v"(a6), "v"(a7),
-          "v"(h0), "v"(h1), "v"(h2), "v"(h3), "v"(h4), "v"(h5), "v"(h6), "v"(h7), "s"(bias2));
+    unsigned char *rec = reinterpret_cast<unsigned char *>(slot);
+    if (l < 14) rec[8 + l] = (unsigned char)byte;
+    else reinterpret_cast<uint32_t *>(rec)[l - 14] = l == 14 ? (uint32_t)o64 : (uint32_t)(o64 >> 32);
 }
 
-// raw IQ -> the nsq image.  Returns (wave-uniform) whether this wave saw a value that is not an ordered f16 bit
-// pattern: v >= 0x7C00, i.e. |I| and |Q| both >= 125 (nine values of n, 31752 .. 32768).  The running
-// v_pk_minimum3_f16 finds them all: 0x7C01..0x7FFF are NaNs, which minimum3 propagates, 0x8048 (n = 32768) is a
-// negative number, and 0x7C00 (+infinity, which a minimum would not see) is no sum of two squares of i8 values.
-__device__ __forceinline__ bool nsq_image_to_lds(const u32x4 (&ra)[kNsqIters], const u32x4 (&rb)[kNsqIters], uint32_t *img, uint32_t tid)
+// Seg::valid is written by the decode kernel, except for a tile that lost its slots (counted in place)
+__device__ __forceinline__ void write_seg(const DemodArgs &p, const uint32_t tile, const uint32_t base_slot, const uint32_t cand,
+                                          const uint32_t valid)
 {
-    uint32_t lo = 0x7BFF7BFFu; // largest finite pattern
-    const uint32_t q_t = tid * 8;
-    uint32_t *dst = img + nsq_phys(q_t);
-    auto sweep = [&](const int it, const bool store) {
-        uint32_t d[8];
-        nsq_pack16(ra[it], rb[it], d);
+    Seg e;
+    e.base = base_slot;
+    e.cand = cand;
+    e.valid = valid;
+    e.decoded = base_slot == kNoBase ? 1u : 0u;
+    p.seg[tile] = e; // (finish_order reads it)
+}
+
+// The hand-over of a tile of TILE offsets whose gate left `total` survivors: their bitmap in `cand` (BITS offsets per
+// word) and, when there are at most kSparseCap, their offsets, unordered, in `list`.  Call it behind the barrier that
+// ends the gate.  `total` = kCountBitmap: there is no list and no count, only the bitmap (the sieve scan's workgroup path).
+//   slicer(have, off, l, dropped), called by all lanes of a 16-lane group (l = tid & 15: the lane's place in it; `have` =
+//     the group has a survivor, list entry `off`), returns this lane's frame byte -- l < 14: byte l, lanes 14 / 15: any --
+//     and sets `dropped` when the samples themselves reject the survivor after all (the code and sieve scans; the record
+//     then carries an all-ones offset, which finish_order skips).
+//   recheck(list, n), called by the whole workgroup for every chunk of n list entries drawn from the bitmap, before they
+//     are sliced (the sieve scan runs its exact gate there and marks entries; it brings its own barrier).
+// lane, wave = tid & 63, tid >> 6, which every caller holds already (derived again in here, the CS16 kernel's instructions
+// come out in another order).  Writes the tile's Seg.  Uses misc[0 .. 3], misc[8] (valid frames of a tile without slots), misc[9].
+constexpr uint32_t kCountBitmap = 0xFFFFFFFFu;
+struct NoRecheck {
+    __device__ __forceinline__ void operator()(uint16_t *, uint32_t) const {}
+};
+template <int TILE, int BITS, class SLICER, class RECHECK = NoRecheck>
+__device__ __forceinline__ void hand_over(const DemodArgs &p, const uint32_t tile, const uint64_t sample0, uint32_t total,
+                                          const uint32_t *cand, uint16_t *list, uint32_t *misc, const uint32_t tid,
+                                          const uint32_t lane, const uint32_t wave, SLICER slicer, RECHECK recheck = RECHECK())
+{
+    const bool dense = total > (uint32_t)kSparseCap;
+    u32x4 cw = {0, 0, 0, 0};
+    uint32_t cnt = 0, my_first = 0;
+    if (dense) {
+        // dense fallback: ordered compaction of the bitmap by workgroup-wide prefix sums
+        // bitmap: offset BITS w + b of the tile is bit b of word w; words 4*tid .. 4*tid+3 per thread
+        if (4 * tid < (uint32_t)(TILE / BITS)) cw = reinterpret_cast<const u32x4 *>(cand)[tid];
+        cnt = __builtin_popcount(cw.x) + __builtin_popcount(cw.y) + __builtin_popcount(cw.z) +
+              __builtin_popcount(cw.w);
+        uint32_t incl = cnt;
 #pragma unroll
-        for (int k = 0; k < 8; k += 2) lo = pkmin3<true>(lo, d[k], d[k + 1]);
-        if (store) { // (8 kThreads is a multiple of 64: the sweep is a constant offset)
-            u32x4 *w = reinterpret_cast<u32x4 *>(dst + nsq_phys(it * kThreads * 8));
-            w[0] = u32x4{d[0], d[1], d[2], d[3]};
-            w[1] = u32x4{d[4], d[5], d[6], d[7]};
+        for (int d = 1; d < 64; d <<= 1) {
+            uint32_t t = __shfl_up(incl, d, 64);
+            if ((int)lane >= d) incl += t;
+        }
+        if (lane == 63) misc[wave] = incl;
+        __syncthreads();
+        uint32_t wbase = 0;
+        total = 0;
+#pragma unroll
+        for (int w = 0; w < kThreads / 64; ++w) {
+            uint32_t t = misc[w];
+            wbase += (w < (int)wave) ? t : 0u;
+            total += t;
+        }
+        my_first = wbase + incl - cnt; // index of this thread's first candidate
+    }
+
+    // Frame slots: the tile's own fixed region when the survivors fit (no atomics), otherwise
+    // one allocation from the shared pool.  In the usual case (a handful of survivors) every thread knows
+    // the base without asking tid 0, and the list is complete since the barrier above: no further barrier.
+    const bool simple = !dense && total <= kQuota;
+    const uint64_t abs0 = sample0 + p.offset_base; // absolute offset of this tile's offset 0
+    uint32_t base_slot = tile * kQuota;
+    // 16-lane groups slice one survivor each, one lane per frame byte, and store offset + 14 raw bytes
+    // into the survivor's slot: 16 survivors per workgroup round
+    const uint32_t g = tid >> 4, l = tid & 15;
+    auto slice_round = [&](uint32_t slot0, uint32_t ncl) {
+        for (uint32_t r = 0; r < ncl; r += kThreads / 16) {
+            if (r + 4 * wave >= ncl) break; // none of this wave's four groups has a survivor
+            const uint32_t ci = r + g;
+            const bool have = ci < ncl; // uniform within the 16-lane group
+            const uint32_t off = have ? list[ci] : 0u;
+            bool dropped;
+            const uint32_t byte = slicer(have, off, l, dropped);
+            if (have) put_record(p.slots + (size_t)slot0 + ci, dropped ? ~0ull : abs0 + off, byte, l);
         }
     };
-#pragma unroll
-    for (int it = 0; it < kNsqFull; ++it) sweep(it, true);
-    if (kNsqTail && __builtin_amdgcn_readfirstlane(tid & ~63u) * 8 < (uint32_t)kNsqTail) sweep(kNsqFull, q_t < (uint32_t)kNsqTail);
-    return __builtin_amdgcn_ballot_w64(((lo & 0xFFFFu) >= 0x7C00u) || ((lo >> 16) >= 0x7C00u)) != 0;
-}
-
-// [phase:2 nsq gate: set-up]
-// ---- the gate on the nsq image ------------------------------------------------------------------------------------
-// The reference orders truncated roots s(.) = floor(sqrt(.)) (demod.rs:27-36, 48-54 on utils.rs:46-52): pass when
-// s(a) >= s(b), a = the smallest "high" n, b = the largest "low" n (s is monotone, so the minimum / maximum of the
-// roots are the roots of the minimum / maximum).  On n itself:  a >= b passes outright;  a < b passes only if
-// s(a) = s(b), which forces b - a <= 2 s(a) <= 2 sqrt(a) <= a / 8 + 8 (AM-GM).  So with the biased values v = n + 72
-//     b' <= t(a'),   t(x) = x + (x >> 3)          [ = n_a + (n_a >> 3) + 9 + 72 ]
-// is an exact SUPERSET test in two packed instructions; lanes that pass it for the preamble AND the DF17 group are
-// survivors at once when a' >= b' in both, and only the rest (a < b inside the band: a handful per million offsets)
-// take two roots per group in a cold block.  Per step (two offsets) the common path is 3 three-input max, 2 min,
-// shift, add, 2 compares = 9 VALU on values that need no unpacking.
-// F16OK: every value of the tile is below 0x7C00, an ordered f16 pattern (v_pk_maximum3_f16 / v_pk_minimum3_f16);
-// otherwise pairs of integer v_pk_max_u16 / v_pk_min_u16.
-__device__ __forceinline__ uint32_t nsq_band(uint32_t x)
-{
-    const u16x2 v = __builtin_bit_cast(u16x2, x);
-    return __builtin_bit_cast(uint32_t, (u16x2)(v + (v >> 3)));
-}
-__device__ __forceinline__ uint32_t nsq_root(uint32_t v) // floor(sqrt(v - 72)), exact for v - 72 <= 32768
-{
-    return (uint32_t)__builtin_amdgcn_sqrtf((float)v - ((float)kNsqBias - 0.5f));
-}
-
-#ifndef ADSB_NSQ_AHEAD
-#define ADSB_NSQ_AHEAD 12 // granules of four pairs resident ahead of the current block in the nsq gate (>= 8)
-#endif
-template <bool F16OK>
-__device__ __forceinline__ void gate_phase_nsq(const uint32_t *img, uint32_t *cand, uint16_t *list, uint32_t *count,
-                                               const uint32_t tid, const uint32_t n_valid)
-{
-    constexpr int RUN = kRun, NT = kThreads;
-    uint32_t *candA = cand + tid, *candB = cand + (tid + NT);
-    *candA = 0u;
-    *candB = 0u;
-    // run A = offsets 32 tid + o, run B = kNsqHalf + 32 tid + o: logical dwords 32 tid + j, j < RUN + 26: this lane's
-    // 32 and the first 28 of the next lane's (which may lie behind a pad)
-    const u32x4 *g0 = reinterpret_cast<const u32x4 *>(img + nsq_phys(32 * tid));
-    const u32x4 *g1 = reinterpret_cast<const u32x4 *>(img + nsq_phys(32 * tid + 32));
-    constexpr int kGran = (RUN + 26 + 3) / 4; // 15 granules of four pairs
-    constexpr int kAhead = ADSB_NSQ_AHEAD;    // 48 pairs resident ahead of the current block
-    uint32_t N[kGran * 4];
-    auto fetch = [&](int g) {
-        const u32x4 x = g < 8 ? g0[g] : g1[g - 8];
-        N[4 * g] = x.x; N[4 * g + 1] = x.y; N[4 * g + 2] = x.z; N[4 * g + 3] = x.w;
-    };
-#pragma unroll
-    for (int g = 0; g < kAhead; ++g) fetch(g);
-    //   N[j]  pair of values               H2[j] = min(N[j], N[j+2])
-    //   W3[j] = max(N[j..j+2])             F[j]  = max(N[j], W3[j+2], N[j+5])
-    // highs of offset o: min(H2[o], H2[o+7]);  lows: max(F[o+1], F[o+8], W3[o+13])
-    uint32_t H2[RUN + 8], W3[RUN + 16], F[RUN + 9];
-#pragma unroll
-    for (int j = 0; j < 7; ++j) H2[j] = pkmin(N[j], N[j + 2]);
-#pragma unroll
-    for (int j = 3; j < 13; ++j) W3[j] = pkmax3<F16OK>(N[j], N[j + 1], N[j + 2]);
-#pragma unroll
-    for (int j = 1; j < 8; ++j) F[j] = pkmax3<F16OK>(N[j], W3[j + 2], N[j + 5]);
-
-    // [phase:2 nsq gate: steps]
-#pragma unroll
-    for (int o = 0; o < RUN; ++o) {
-        if (o % 4 == 0) { // keep 48 pairs resident ahead of the block that starts here
-            const int g = o / 4 + kAhead;
-            if (g < kGran) fetch(g);
+    if (simple) {
+        slice_round(base_slot, total); // unordered list (finish_order ranks it): survivor j -> slot j
+    } else {
+        if (tid == 0) {
+            const unsigned long long b64 = atomicAdd(&p.hdr->alloc, (unsigned long long)total);
+            // (pool_off: test knob, adsb_debug_pool_limit -- every tile over its quota loses its slots)
+            misc[9] = (!p.pool_off && b64 + total <= (unsigned long long)p.cap_slots) ? p.pool_first + (uint32_t)b64 : kNoBase;
         }
-        W3[o + 13] = pkmax3<F16OK>(N[o + 13], N[o + 14], N[o + 15]);
-        F[o + 8] = pkmax3<F16OK>(N[o + 8], W3[o + 10], N[o + 13]);           // lows 8,10,11,12,13
-        const uint32_t lo = pkmax3<F16OK>(F[o + 1], F[o + 8], W3[o + 13]);   // + 1,3,4,5,6 + 13,14,15
-        H2[o + 7] = pkmin(N[o + 7], N[o + 9]);
-        const uint32_t hi = pkmin(H2[o], H2[o + 7]);                      // highs 0,2,7,9
-        const uint32_t t = nsq_band(hi);
-        const bool pa = (uint16_t)t >= (uint16_t)lo;
-        const bool pb = (t >> 16) >= (lo >> 16);
-        // [phase:2 nsq gate: DF17 (cold)]
-        // wave-uniform tests (scalar branches, no exec juggling): a block is entered by the whole wave when any
-        // lane needs it; its effects are masked by the lanes' own flags
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(pa | pb) != 0, 0)) {
-            // DF17 part of the gate (demod.rs:45-54), the same superset test
-            const uint32_t dh = pkmin3<F16OK>(pkmin3<F16OK>(N[o + 16], N[o + 19], N[o + 21]), N[o + 23], N[o + 24]);
-            const uint32_t dl = pkmax3<F16OK>(pkmax3<F16OK>(N[o + 17], N[o + 18], N[o + 20]), N[o + 22], N[o + 25]);
-            const uint32_t t2 = nsq_band(dh);
-            bool sa = pa & ((uint16_t)t2 >= (uint16_t)dl);
-            bool sb = pb & ((t2 >> 16) >= (dl >> 16));
-            if (__builtin_amdgcn_ballot_w64(sa | sb) != 0) {
-                // inside both bands.  Exact at once where both groups are ordered on n itself ...
-                const bool ea = ((uint16_t)hi >= (uint16_t)lo) & ((uint16_t)dh >= (uint16_t)dl);
-                const bool eb = ((hi >> 16) >= (lo >> 16)) & ((dh >> 16) >= (dl >> 16));
-                // [phase:2 nsq gate: roots (cold)]
-                if (__builtin_expect(__builtin_amdgcn_ballot_w64((sa & !ea) | (sb & !eb)) != 0, 0)) {
-                    // ... the rest by the truncated roots themselves (utils.rs:46-52): ties after truncation pass
-                    const bool ra = nsq_root(hi & 0xFFFFu) >= nsq_root(lo & 0xFFFFu) && nsq_root(dh & 0xFFFFu) >= nsq_root(dl & 0xFFFFu);
-                    const bool rb = nsq_root(hi >> 16) >= nsq_root(lo >> 16) && nsq_root(dh >> 16) >= nsq_root(dl >> 16);
-                    sa = sa && (ea || ra);
-                    sb = sb && (eb || rb);
+        __syncthreads();
+        base_slot = misc[9];
+        for (uint32_t chunk = 0; chunk < total; chunk += kListCap) {
+            if (dense && cnt) {
+                uint32_t idx = my_first;
+                const uint32_t words[4] = {cw.x, cw.y, cw.z, cw.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    uint32_t bits = words[k];
+                    while (bits) {
+                        const uint32_t b = __builtin_ctz(bits);
+                        bits &= bits - 1;
+                        if (idx >= chunk && idx < chunk + kListCap)
+                            list[idx - chunk] = (uint16_t)((4 * tid + k) * BITS + b);
+                        ++idx;
+                    }
                 }
-                // (offsets at or beyond n_valid are masked out of the bitmap words afterwards, in the one tile per
-                // channel that has any)
-                uint32_t bit = 1u << o;
-                asm("" : "+v"(bit)); // one v_mov for both stores
-                if (sa) atomicOr(candA, bit);
-                if (sb) atomicOr(candB, bit);
             }
+            __syncthreads();
+            const uint32_t ncl = (total - chunk) < (uint32_t)kListCap ? (total - chunk) : (uint32_t)kListCap;
+            if (dense) recheck(list, ncl);
+            if (base_slot != kNoBase) {
+                slice_round(base_slot + chunk, ncl); // (ordered when dense; 33..64 survivors: unordered like the simple case)
+            } else {
+                // The slot store is full (pathological input: SURVEY F8).  The host re-plans from exact counts,
+                // so this tile's survivors are decoded HERE, from the image in LDS, only to be counted.
+                for (uint32_t r = 0; r < ncl; r += kThreads / 16) {
+                    if (r + 4 * wave >= ncl) break; // none of this wave's four groups has a candidate
+                    const uint32_t ci = r + g;
+                    const bool have = ci < ncl; // uniform within the 16-lane group
+                    const uint32_t off = have ? list[ci] : 0u;
+                    bool dropped;
+                    const uint32_t byte = slicer(have, off, l, dropped);
+                    const bool valid = count_candidate(have && !dropped, byte, l, lane);
+                    if (valid && l == 0) atomicAdd(&misc[8], 1u);
+                }
+            }
+            __syncthreads();
         }
     }
-    // [phase:2 nsq gate: survivor list]
-    gate_collect<RUN, NT>(candA, candB, list, count, tid, n_valid);
+    if (tid == 0) write_seg(p, tile, base_slot, total, misc[8]);
 }
 
 // [phase:end]
 // demod_tiles: one workgroup = one tile; the hardware dispatcher starts the next tile as soon as one retires, which
 // staggers the phases of a CU's co-resident workgroups.  Per tile:
-//   phase 1  the tile's raw IQ (16-byte loads, all in flight at once) becomes the LDS image: i8/kScanRoot and CS16:
-//            floor(sqrt) magnitudes (u8 / u16); i8/kScanNsq (the A/B kernel): pairs of biased I^2+Q^2;     ... barrier
-//   phase 2  preamble + DF17 gate over the tile's offsets (gate_phase / gate_phase_nsq);                    ... barrier
+//   phase 1  the tile's raw IQ (16-byte loads, all in flight at once) becomes the LDS image: floor(sqrt)
+//            magnitudes (u8 / u16);                                                                         ... barrier
+//   phase 2  preamble + DF17 gate over the tile's offsets (gate_phase);                                     ... barrier
 //   phase 3  every survivor gets a frame slot, its offset and its 14 sliced bytes; CRC-24, repair and ordering are
 //            finish_order's (below).
 // Measured alternatives: persistent workgroups drawing tiles from per-XCD ticket counters with
@@ -1088,29 +850,21 @@ __device__ __forceinline__ void gate_phase_nsq(const uint32_t *img, uint32_t *ca
 // registers, SGPR spills) and come out 7 % slower; several tiles per workgroup with the next tile's loads in flight
 // need 147 VGPRs (3 waves per SIMD): 0.25-0.27 ms against 0.182.  The instruction count is what bounds this kernel.
 // Waves per SIMD the register allocation is held to = workgroups per CU the LDS image allows (4 waves per workgroup):
-// 8 for the i8 root scan (u8 magnitudes: 19 KB), 4 for the 16-bit images (nsq, CS16: 35-38 KB).
+// 8 for the i8 root scan (u8 magnitudes: 19 KB), ADSB_SCAN_WAVES for the 16-bit images (CS16; the nsq scan, ab/nsq.inc).
 #ifndef ADSB_SCAN_WAVES
 #define ADSB_SCAN_WAVES 4
 #endif
-#ifndef ADSB_REG_ABL
-#define ADSB_REG_ABL 0
-#endif
-#ifndef ADSB_REG_WAVES
-#define ADSB_REG_WAVES 5 // waves per SIMD the register scan's allocation is held to (86-96 VGPRs)
-#endif
 // The tile body: everything one workgroup does for one tile (`first` = it is the launch's first workgroup: it clears
-// the result header's flags).  smem: Lds<ST, SCAN>::kTotal bytes, 16-byte aligned.
-template <int ST, int MAGMODE, int SCAN>
+// the result header's flags).  smem: Lds<ST>::kTotal bytes, 16-byte aligned.
+template <int ST, int MAGMODE>
 __device__ __forceinline__ void scan_tile(const DemodArgs &p, const uint32_t tile, const bool first, unsigned char *smem)
 {
-    typedef Lds<ST, SCAN> L;
+    typedef Lds<ST> L;
     typedef TileCfg<ST> TC; // tile length of this sample type
     typedef typename L::mag_t mag_t;
-    constexpr bool NSQ = L::kNsq;
     static_assert(kThreads / 64 <= 4, "misc[4 + wave] must stay below misc[8]");
 
     mag_t *mag = reinterpret_cast<mag_t *>(smem);
-    uint32_t *img = reinterpret_cast<uint32_t *>(smem); // (nsq) the same bytes as pairs of biased squared magnitudes
     uint32_t *cand = reinterpret_cast<uint32_t *>(smem + L::kOffCand);
     uint16_t *list = reinterpret_cast<uint16_t *>(smem + L::kOffList);
     uint32_t *misc = reinterpret_cast<uint32_t *>(smem + L::kOffMisc);
@@ -1118,10 +872,7 @@ __device__ __forceinline__ void scan_tile(const DemodArgs &p, const uint32_t til
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63, wave = tid >> 6;
 
-#if ADSB_PRIO & 1 // (A/B: a new workgroup's prologue and loads go out ahead of the resident waves' arithmetic)
-    __builtin_amdgcn_s_setprio(3);
-#endif
-    if (!NSQ && MAGMODE == 1) __builtin_amdgcn_s_setreg((1 | (0 << 6) | ((2 - 1) << 11)), 3);
+    if (MAGMODE == 1) __builtin_amdgcn_s_setreg((1 | (0 << 6) | ((2 - 1) << 11)), 3);
 #if ADSB_TILE_STAMPS
     unsigned long long ts_prev = 0;
     uint32_t ts_seg[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1135,181 +886,47 @@ __device__ __forceinline__ void scan_tile(const DemodArgs &p, const uint32_t til
         const uint32_t n_valid = tp.n_valid;
         // [phase:1 magnitude (loads, stores)]
         // ---- phase 1, first half: the loads go out before anything else --------------------------------------------
-        u32x4 raw[NSQ ? 1 : P1<ST>::kIters];
-        u32x4 raw_a[NSQ ? kNsqIters : 1], raw_b[NSQ ? kNsqIters : 1];
-        if constexpr (NSQ) nsq_issue_loads(p, tp, tid, raw_a, raw_b);
-        else issue_tile_loads<ST>(p, tp, true, tid, raw);
-#if ADSB_PRIO & 1
-        __builtin_amdgcn_s_setprio(0);
-#endif
+        u32x4 raw[P1<ST>::kIters];
+        issue_tile_loads<ST>(p, tp, true, tid, raw);
         TSTAMP(0); // prologue, loads issued
-        if (tid == 0 && first) {
-            p.hdr->retry = 0;
-            if (p.count_groups) { // first pass of a launch: the finishing kernel ORs this launch's flags in
-                p.hdr->flags = 0;
-                if (p.hdr_pub) p.hdr_pub[2] = 0;
-            }
-        }
-        if (tid == 0) {
-            misc[8] = 0;  // valid-frame counter
-            misc[12] = 0; // survivor counter
-        }
+        tile_prologue(p, first, misc, tid);
 #if ADSB_TILE_STAMPS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (diagnostic build only) the whole wait for the loads ...
         TSTAMP(6);                                       // ... as its own segment
 #endif
         // ---- phase 1, second half: raw IQ -> the LDS image ---------------------------------------------------
-        bool wave_big;
-        if constexpr (NSQ) wave_big = nsq_image_to_lds(raw_a, raw_b, img, tid);
-        else wave_big = magnitudes_to_lds<ST, MAGMODE, MagPad<ST, SCAN>::on>(raw, mag, tid);
-        if ((NSQ || ST == ADSB_SAMPLE_I16) && lane == 0) misc[4 + wave] = wave_big ? 1u : 0u; // (every wave writes its own word)
+        const bool wave_big = magnitudes_to_lds<ST, MAGMODE>(raw, mag, tid);
+        if (ST == ADSB_SAMPLE_I16 && lane == 0) misc[4 + wave] = wave_big ? 1u : 0u; // (every wave writes its own word)
         TSTAMP(1); // phase 1 arithmetic
         __syncthreads();
         TSTAMP(2); // barrier
-#if ADSB_ABL_PHASES < 2
-        // (keeps the LDS stores of phase 1 alive; never true for real data)
-        if (smem[tid * 64] == 0xFD && smem[tid * 64 + 1] == 0xFE && n_valid == 7) misc[12] = 1;
-#else
 
         // [phase:2 gate: call]
         // ---- phase 2: preamble + DF17 gate, two runs per lane, packed u16x2 --------------------
-        if constexpr (NSQ || ST == ADSB_SAMPLE_I16) {
-            // the 3-input f16 gate whenever every value of the tile is an ordered f16 pattern (nsq: unless some sample
-            // has |I| and |Q| >= 125; CS16: any signal below 2/3 of full scale); the integer gate otherwise
+        if constexpr (ST == ADSB_SAMPLE_I16) {
+            // the 3-input f16 gate whenever every value of the tile is an ordered f16 pattern (any signal below 2/3 of
+            // full scale); the integer gate otherwise
             uint32_t any_big = 0;
 #pragma unroll
             for (int w = 0; w < kThreads / 64; ++w) any_big |= misc[4 + w];
             const bool big = any_big != 0; // (workgroup-uniform)
-            if constexpr (NSQ) {
-                if (!big) gate_phase_nsq<true>(img, cand, list, &misc[12], tid, n_valid);
-                else gate_phase_nsq<false>(img, cand, list, &misc[12], tid, n_valid);
-            } else {
-                if (!big) gate_phase<ST, ADSB_GATE_GROUP, TC::kRunT, kThreads, -1, NoHook, true>(mag, cand, list, &misc[12], tid, n_valid);
-                else gate_phase<ST, ADSB_GATE_GROUP, TC::kRunT, kThreads, -1, NoHook, false>(mag, cand, list, &misc[12], tid, n_valid);
-            }
+            if (!big) gate_phase<ST, TC::kRunT, kThreads, true>(mag, cand, list, &misc[12], tid, n_valid);
+            else gate_phase<ST, TC::kRunT, kThreads, false>(mag, cand, list, &misc[12], tid, n_valid);
         } else {
-            gate_phase<ST, ADSB_GATE_GROUP, TC::kRunT, kThreads, -1, NoHook, (ST == ADSB_SAMPLE_I8), MagPad<ST, SCAN>::on>(mag, cand, list, &misc[12], tid, n_valid);
+            gate_phase<ST, TC::kRunT, kThreads>(mag, cand, list, &misc[12], tid, n_valid);
         }
-#endif
         TSTAMP(3); // phase 2
         __syncthreads();
         TSTAMP(4); // barrier
 
-#if ADSB_PRIO & 2 // (A/B: the tail of a tile ahead of other waves' arithmetic: the workgroup retires, the next one's loads start)
-        __builtin_amdgcn_s_setprio(2);
-#endif
         // [phase:3 hand-over: slots, offsets, sliced bytes]
         // ---- phase 3: PPM slice of the gate survivors; the CRC stage is a kernel of its own --------------------
-        // Every survivor gets a frame slot, its absolute offset and its 14 sliced bytes (the image is here, in
-        // LDS).  CRC-24, repair, ordering inside the tile and the valid-frame count are finish_order's work, one
-        // LANE per survivor instead of sixteen.  (With the whole decode in this kernel a tile's 33 KB of LDS were
-        // held through a latency-bound epilogue: 19 % of the kernel time for 13 % of its instructions.)
-        uint32_t total = misc[12];
-#if ADSB_ABL_PHASES < 3
-        if (total != 0x7FFFFFFFu) total = 0; // survivors are counted (phase 2 stays alive) but not handed over
-#endif
-        const bool dense = total > (uint32_t)kSparseCap;
         constexpr int kBitsPerWord = TC::kRunT < 32 ? TC::kRunT : 32; // offsets per survivor-bitmap word (gate_phase)
-        u32x4 cw = {0, 0, 0, 0};
-        uint32_t cnt = 0, my_first = 0;
-        if (dense) {
-            // dense fallback: ordered compaction of the bitmap by workgroup-wide prefix sums
-            // bitmap: offset kBitsPerWord w + b of the tile is bit b of word w; words 4*tid .. 4*tid+3 per thread
-            if (4 * tid < (uint32_t)(TC::kTileT / kBitsPerWord)) cw = reinterpret_cast<const u32x4 *>(cand)[tid];
-            cnt = __builtin_popcount(cw.x) + __builtin_popcount(cw.y) + __builtin_popcount(cw.z) +
-                  __builtin_popcount(cw.w);
-            uint32_t incl = cnt;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                uint32_t t = __shfl_up(incl, d, 64);
-                if ((int)lane >= d) incl += t;
-            }
-            if (lane == 63) misc[wave] = incl;
-            __syncthreads();
-            uint32_t wbase = 0;
-            total = 0;
-#pragma unroll
-            for (int w = 0; w < kThreads / 64; ++w) {
-                uint32_t t = misc[w];
-                wbase += (w < (int)wave) ? t : 0u;
-                total += t;
-            }
-            my_first = wbase + incl - cnt; // index of this thread's first candidate
-        }
-
-        // Frame slots: the tile's own fixed region when the survivors fit (no atomics), otherwise
-        // one allocation from the shared pool.  In the usual case (a handful of survivors) every thread knows
-        // the base without asking tid 0, and the list is complete since the barrier above: no further barrier.
-        const bool simple = !dense && total <= kQuota;
-        const uint64_t abs0 = sample0 + p.offset_base; // absolute offset of this tile's offset 0
-        uint32_t base_slot = tile * kQuota;
-        // 16-lane groups slice one survivor each, one lane per frame byte, and store offset + 14 raw bytes (no CRC
-        // verdict yet) into the survivor's slot: 16 survivors per workgroup round
-        const uint32_t g = tid >> 4, l = tid & 15;
-        auto slice_one = [&](uint32_t off) {
-            if constexpr (NSQ) return nsq_slice_byte(img, off, l);
-            else return slice_byte<ST, MagPad<ST, SCAN>::on>(mag, off, l < 14 ? l : 13);
-        };
-        auto slice_round = [&](uint32_t slot0, uint32_t ncl) {
-            for (uint32_t r = 0; r < ncl; r += kThreads / 16) {
-                if (r + 4 * wave >= ncl) break; // none of this wave's four groups has a survivor
-                const uint32_t ci = r + g;
-                const bool have = ci < ncl; // uniform within the 16-lane group
-                const uint32_t off = have ? list[ci] : 0u;
-                const uint32_t byte = slice_one(off);
-                if (have) {
-                    unsigned char *rec = reinterpret_cast<unsigned char *>(p.slots + (size_t)slot0 + ci);
-                    const uint64_t o64 = abs0 + off;
-                    if (l < 14) rec[8 + l] = (unsigned char)byte;
-                    else reinterpret_cast<uint32_t *>(rec)[l - 14] = l == 14 ? (uint32_t)o64 : (uint32_t)(o64 >> 32);
-                }
-            }
-        };
-        if (simple) {
-            slice_round(base_slot, total); // unordered list (finish_order ranks it): survivor j -> slot j
-        } else {
-            if (tid == 0) {
-                const unsigned long long b64 = atomicAdd(&p.hdr->alloc, (unsigned long long)total);
-                // (pool_off: test knob, adsb_debug_pool_limit -- every tile over its quota loses its slots)
-                misc[9] = (!p.pool_off && b64 + total <= (unsigned long long)p.cap_slots) ? p.pool_first + (uint32_t)b64 : kNoBase;
-            }
-            __syncthreads();
-            base_slot = misc[9];
-            for (uint32_t chunk = 0; chunk < total; chunk += kListCap) {
-                if (dense && cnt) {
-                    uint32_t idx = my_first;
-                    const uint32_t words[4] = {cw.x, cw.y, cw.z, cw.w};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        uint32_t bits = words[k];
-                        while (bits) {
-                            const uint32_t b = __builtin_ctz(bits);
-                            bits &= bits - 1;
-                            if (idx >= chunk && idx < chunk + kListCap)
-                                list[idx - chunk] = (uint16_t)((4 * tid + k) * kBitsPerWord + b);
-                            ++idx;
-                        }
-                    }
-                }
-                __syncthreads();
-                const uint32_t ncl = (total - chunk) < (uint32_t)kListCap ? (total - chunk) : (uint32_t)kListCap;
-                if (base_slot != kNoBase) {
-                    slice_round(base_slot + chunk, ncl); // (ordered when dense; 33..64 survivors: unordered like the simple case)
-                } else {
-                    // The slot store is full (pathological input: SURVEY F8).  The host re-plans from exact counts,
-                    // so this tile's survivors are decoded HERE, from the image in LDS, only to be counted.
-                    for (uint32_t r = 0; r < ncl; r += kThreads / 16) {
-                        if (r + 4 * wave >= ncl) break; // none of this wave's four groups has a candidate
-                        const uint32_t ci = r + g;
-                        const bool have = ci < ncl; // uniform within the 16-lane group
-                        const uint32_t off = have ? list[ci] : 0u;
-                        const bool valid = count_candidate(have, slice_one(off), l, lane);
-                        if (valid && l == 0) atomicAdd(&misc[8], 1u);
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        hand_over<TC::kTileT, kBitsPerWord>(p, tile, sample0, misc[12], cand, list, misc, tid, lane, wave,
+                                            [=](const bool, const uint32_t off, const uint32_t l, bool &dropped) {
+                                                dropped = false; // (the magnitudes are exact: the gate's verdict stands)
+                                                return slice_byte<ST>(mag, off, l < 14 ? l : 13);
+                                            });
         TSTAMP(5); // phase 3
 #if ADSB_TILE_STAMPS
         if ((tid & 63u) == 0 && (wave == 0 || wave == 3)) {
@@ -1319,18 +936,9 @@ __device__ __forceinline__ void scan_tile(const DemodArgs &p, const uint32_t til
             if (wave) dst[6] = ts_seg[8]; // wave 3's load wait is wave 0's: its slot carries the s_memtime stamp
         }
 #endif
-        // Seg::valid is written by the decode kernel, except for a tile that lost its slots (counted above)
-        if (tid == 0) {
-            Seg e;
-            e.base = base_slot;
-            e.cand = total;
-            e.valid = misc[8];
-            e.decoded = base_slot == kNoBase ? 1u : 0u;
-            p.seg[tile] = e; // (finish_order reads it)
-        }
     }
     // [phase:end]
-    if (!NSQ && MAGMODE == 1) __builtin_amdgcn_s_setreg((1 | (0 << 6) | ((2 - 1) << 11)), 0);
+    if (MAGMODE == 1) __builtin_amdgcn_s_setreg((1 | (0 << 6) | ((2 - 1) << 11)), 0);
 }
 
 // Which tile a workgroup takes.  The dispatcher deals workgroups to the eight XCDs round-robin (workgroup b runs on XCD b mod 8:
@@ -1354,11 +962,11 @@ __device__ __forceinline__ uint32_t tile_of_workgroup(uint32_t b, uint32_t n)
 #endif
 }
 
-template <int ST, int MAGMODE, int SCAN>
-__global__ __launch_bounds__(kThreads, (ST == ADSB_SAMPLE_I8 && SCAN == kScanRoot) ? 8 : ADSB_SCAN_WAVES) void demod_tiles(DemodArgs p)
+template <int ST, int MAGMODE>
+__global__ __launch_bounds__(kThreads, ST == ADSB_SAMPLE_I8 ? 8 : ADSB_SCAN_WAVES) void demod_tiles(DemodArgs p)
 {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[Lds<ST, SCAN>::kTotal];
-    scan_tile<ST, MAGMODE, SCAN>(p, p.tile_first + tile_of_workgroup(blockIdx.x, p.tile_count), blockIdx.x == 0, smem);
+    __shared__ __attribute__((aligned(16))) unsigned char smem[Lds<ST>::kTotal];
+    scan_tile<ST, MAGMODE>(p, p.tile_first + tile_of_workgroup(blockIdx.x, p.tile_count), blockIdx.x == 0, smem);
 }
 
 // ---- CRC-24 + single-bit repair of the sliced survivors (demod.rs:71-81; crc.rs:10-65) --------------------------
@@ -1539,9 +1147,6 @@ __device__ __forceinline__ uint32_t finish_big_tile(const FinishArgs &a, const S
     return n_good;
 }
 
-#ifndef ADSB_FIN_ABL
-#define ADSB_FIN_ABL 0 // measurement only (wrong results): 1 no exchange, 2 no CRC / search, 3 no stores of the list, 4 empty kernel
-#endif
 constexpr int kFinLdsWords = 256 + 128 + 2 * kFinTiles; // tables, per-tile counts, per-tile positions
 // What workgroup `blk` of `n_blk` does (lds: kFinLdsWords words).
 // PUB_ATOMIC: the caller-owned header copy's flags word is updated with 64-bit atomic ORs (device memory: finish_order).  The
@@ -1591,12 +1196,8 @@ __device__ __forceinline__ void finish_block(const FinishArgs &a, const uint32_t
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         const uint32_t idx = wave * 8 + p * 4 + g;
-#if ADSB_FIN_ABL == 2
-        valid[p] = small_[p] && sub < e[p].cand && (w[p][2] & 1u) == 0;
-#else
         // (offset all ones: a survivor of the code gate that the samples themselves rejected -- no record)
         valid[p] = finish_record(w[p], small_[p] && sub < e[p].cand && w[p][1] != 0xFFFFFFFFu, crc_tab, syn_sorted);
-#endif
         // place inside the tile: rank by offset among the valid frames of the 16-lane row.  A tile's offsets lie within
         // 2^15 of each other: relative to the row's first survivor they fit 16 bits (wrap-safe); bit 16 = does not count.
         // (relative to the row's first RECORD: a rejected survivor's all-ones offset is no reference)
@@ -1635,7 +1236,7 @@ __device__ __forceinline__ void finish_block(const FinishArgs &a, const uint32_t
         }
         const uint32_t total = __shfl(incl, kFinTiles - 1, 64);
         unsigned long long before = 0; // valid frames in all earlier workgroups
-        if (a.out_start == nullptr && ADSB_FIN_ABL != 1) {
+        if (a.out_start == nullptr) {
             const unsigned long long tag = ((unsigned long long)a.epoch << 34) | ((unsigned long long)kLbReady << 32);
             uint64_t *lb_a = a.lb, *lb_s = a.lb + a.lb_groups_at; // one word per workgroup | one per 64 workgroups
             if (lane == 0 && blk != a.stall_blk) __hip_atomic_store(lb_a + blk, tag | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1762,7 +1363,7 @@ __device__ __forceinline__ void finish_block(const FinishArgs &a, const uint32_t
     for (int p = 0; p < 2; ++p) {
         const uint32_t idx = wave * 8 + p * 4 + g, tile = tile0 + idx;
         const uint32_t dst = tpos[idx] + rank[p];
-        if (valid[p] && dst < a.max_out && tpos[idx] != 0xFFFFFFFFu && ADSB_FIN_ABL != 3) store_record(a.out + dst, w[p]);
+        if (valid[p] && dst < a.max_out && tpos[idx] != 0xFFFFFFFFu) store_record(a.out + dst, w[p]);
         if (sub == 0 && tile < t_end) {
             if (small_[p]) a.seg[tile].valid = counts[idx];
             // a tile that lost its slots (the pool was full) but whose frames are wanted: the host re-plans
@@ -1794,9 +1395,6 @@ __device__ __forceinline__ void finish_block(const FinishArgs &a, const uint32_t
 
 __global__ __launch_bounds__(kFinThreads) void finish_order(FinishArgs a)
 {
-#if ADSB_FIN_ABL == 4
-    if (a.max_out != 0xFFFFFFF1u) return;
-#endif
     __shared__ uint32_t lds[kFinLdsWords];
     finish_block<true>(a, blockIdx.x, gridDim.x, lds);
 }
@@ -1809,815 +1407,13 @@ hipError_t launch_finish(hipStream_t s, const FinishArgs &a, hipEvent_t e0, hipE
     return hipGetLastError();
 }
 
-// ---- the register scan (i8, kScanReg): the nsq gate without an LDS image -----------------------------------------------
-// The nsq scan needs 10 % fewer instructions than the root scan and loses, because its image
-// takes 2 bytes of LDS per sample and halves the resident workgroups.  Here the image never exists.  Every WAVE takes a
-// chunk of 4032 offsets on its own: lane L slides along run A = offsets 32 L .. 32 L + 31 and run B = run A + 2016, packed
-// in the halves of one VGPR as in the nsq scan.  The wave reads its chunk fully coalesced (lane i takes granule
-// i + 64 g), turns the granules round in a wave-private 4 KB of LDS so that every lane holds ITS OWN 32 + 32 samples, and
-// packs them into 32 VGPRs of v = I^2 + Q^2 + 72.  The 26 samples of window beyond a lane's run are its right
-// neighbour's first 26 values -- the same registers one lane up: ONE DPP move each (wave_shl:1), where an image costs a
-// store and a load per value and a workgroup barrier.  Lane 63 only supplies them (its run A is lane 0's run B, its run
-// B belongs to the next chunk): 63 of 64 lanes produce offsets.  No barrier between loads and gate, no per-sample root,
-// no unpacking: 128 (v) + 26 (DPP) + 312 (gate) VALU per 64 offsets where the root scan takes ~ 770, and 18 KB of LDS per
-// workgroup.  Survivors are sliced from the IQ bytes themselves (L2-hot), roots only for their 112 pairs.
-// A tile (= workgroup = Seg entry = 32 frame slots) is four chunks: 16128 offsets.
-constexpr int kRegB = 63 * 32, kRegChunk = 2 * kRegB;
-template <bool F16OK>
-__device__ __forceinline__ void reg_gate(const uint32_t (&N)[32], uint32_t &bitsA, uint32_t &bitsB)
-{
-    uint32_t NX[26];
-#pragma unroll
-    for (int j = 0; j < 26; ++j) NX[j] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)N[j], 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
-#define RN(j) ((j) < 32 ? N[(j) < 32 ? (j) : 0] : NX[(j) >= 32 ? (j) - 32 : 0])
-    uint32_t H2[32 + 8], W3[32 + 16], F[32 + 9];
-#pragma unroll
-    for (int j = 0; j < 7; ++j) H2[j] = pkmin(RN(j), RN(j + 2));
-#pragma unroll
-    for (int j = 3; j < 13; ++j) W3[j] = pkmax3<F16OK>(RN(j), RN(j + 1), RN(j + 2));
-#pragma unroll
-    for (int j = 1; j < 8; ++j) F[j] = pkmax3<F16OK>(RN(j), W3[j + 2], RN(j + 5));
-#pragma unroll
-    for (int o = 0; o < 32; ++o) {
-        W3[o + 13] = pkmax3<F16OK>(RN(o + 13), RN(o + 14), RN(o + 15));
-        F[o + 8] = pkmax3<F16OK>(RN(o + 8), W3[o + 10], RN(o + 13));
-        const uint32_t lo = pkmax3<F16OK>(F[o + 1], F[o + 8], W3[o + 13]);
-        H2[o + 7] = pkmin(RN(o + 7), RN(o + 9));
-        const uint32_t hi = pkmin(H2[o], H2[o + 7]);
-        const uint32_t t = nsq_band(hi);
-        const bool pa = (uint16_t)t >= (uint16_t)lo;
-        const bool pb = (t >> 16) >= (lo >> 16);
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(pa | pb) != 0, 0)) {
-            const uint32_t dh = pkmin3<F16OK>(pkmin3<F16OK>(RN(o + 16), RN(o + 19), RN(o + 21)), RN(o + 23), RN(o + 24));
-            const uint32_t dl = pkmax3<F16OK>(pkmax3<F16OK>(RN(o + 17), RN(o + 18), RN(o + 20)), RN(o + 22), RN(o + 25));
-            const uint32_t t2 = nsq_band(dh);
-            bool sa = pa & ((uint16_t)t2 >= (uint16_t)dl);
-            bool sb = pb & ((t2 >> 16) >= (dl >> 16));
-            if (__builtin_amdgcn_ballot_w64(sa | sb) != 0) {
-                const bool ea = ((uint16_t)hi >= (uint16_t)lo) & ((uint16_t)dh >= (uint16_t)dl);
-                const bool eb = ((hi >> 16) >= (lo >> 16)) & ((dh >> 16) >= (dl >> 16));
-                if (__builtin_expect(__builtin_amdgcn_ballot_w64((sa & !ea) | (sb & !eb)) != 0, 0)) {
-                    const bool ra = nsq_root(hi & 0xFFFFu) >= nsq_root(lo & 0xFFFFu) && nsq_root(dh & 0xFFFFu) >= nsq_root(dl & 0xFFFFu);
-                    const bool rb = nsq_root(hi >> 16) >= nsq_root(lo >> 16) && nsq_root(dh >> 16) >= nsq_root(dl >> 16);
-                    sa = sa && (ea || ra);
-                    sb = sb && (eb || rb);
-                }
-                if (sa) bitsA |= 1u << o;
-                if (sb) bitsB |= 1u << o;
-            }
-        }
-    }
-#undef RN
-}
-
-// (wave-private staging in LDS: lane i wrote granule i + 64 g and gets the granules of its own run back, 4 L .. 4 L + 3;
-// the granule index is XOR-swizzled so that both the writes and the 64-byte-strided reads of a 16-lane group fall on
-// distinct banks.  Lines read with 64-byte strides straight from memory, 2 lanes per 128-byte line and instruction,
-// measured 0.174 ms per GiB against 0.168 this way and 0.156 for the coalesced read alone.)
-__device__ __forceinline__ uint32_t reg_swz(uint32_t q) { return q ^ ((q >> 4) & 3u); }
-__device__ __forceinline__ void reg_transpose(u32x4 *stage, const u32x4 (&in)[4], u32x4 (&out)[4], uint32_t lane)
-{
-#pragma unroll
-    for (int g = 0; g < 4; ++g) stage[reg_swz(lane + 64u * g)] = in[g];
-    // (same wave: LDS operations complete in order; no barrier)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = stage[reg_swz(4u * lane + k)];
-}
-
-static_assert(kRegTile == 4 * kRegChunk && kThreads == 256, "four waves, one chunk each");
-struct RegLds {
-#ifndef ADSB_REG_STAGE_BYTES
-#define ADSB_REG_STAGE_BYTES 4096
-#endif
-    static constexpr int kOffCand = 4 * ADSB_REG_STAGE_BYTES;   // wave-private staging: 4 KB per wave
-    static constexpr int kOffList = kOffCand + 2048;            // survivor bitmap: 504 words (offset 32 w + b = bit b of word w)
-    static constexpr int kOffMisc = kOffList + kListCap * 2;
-    static constexpr int kTotal = kOffMisc + 64;
-};
-
-// Frame byte l of the survivor at tile offset `off`, sliced from the IQ bytes (one lane per byte, 16 samples = 8 pairs
-// each; lanes 14/15 repeat byte 13).  The reference compares truncated roots (demod.rs:106 on utils.rs:46-52):
-// bit = floor(sqrt(x)) > floor(sqrt(y)) = (r * r > y), r = floor(sqrt(x)) -- r * r is the largest square <= x, so a
-// square lies in (y, x] exactly when r * r > y.  r = trunc(sqrtf(x + 0.5)) is exact for x <= 32768.
-__device__ __forceinline__ uint32_t reg_slice_byte(__amdgpu_buffer_rsrc_t rsrc, const uint32_t off, const uint32_t l)
-{
-    const uint32_t b = 2u * (off + 16u + 16u * (l < 14u ? l : 13u)); // byte of the lane's first sample in the tile
-    const uint32_t base = b & ~3u, sh = b & 3u;
-    uint32_t d[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) d[k] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, base + 4u * k, 0, 0);
-    uint32_t byte = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint32_t w = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh); // [I_a, Q_a, I_b, Q_b]
-        const uint32_t na = (uint32_t)__builtin_amdgcn_sdot4((int)(w & 0xFFFFu), (int)w, 0, false);
-        const uint32_t nb = (uint32_t)__builtin_amdgcn_sdot4((int)(w & 0xFFFF0000u), (int)w, 0, false);
-        const uint32_t r = (uint32_t)__builtin_amdgcn_sqrtf((float)na + 0.5f);
-        byte |= (r * r > nb ? 1u : 0u) << (7 - k);
-    }
-    return byte;
-}
-
-__device__ __forceinline__ void scan_tile_reg(const DemodArgs &p, const uint32_t tile, const bool first, unsigned char *smem)
-{
-    typedef RegLds L;
-    uint32_t *cand = reinterpret_cast<uint32_t *>(smem + L::kOffCand);
-    uint16_t *list = reinterpret_cast<uint16_t *>(smem + L::kOffList);
-    uint32_t *misc = reinterpret_cast<uint32_t *>(smem + L::kOffMisc);
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const TilePos tp = tile_pos<kRegTile>(p, tile);
-    const uint64_t sample0 = tp.sample0;
-    const uint32_t n_valid = tp.n_valid;
-    __amdgpu_buffer_rsrc_t rsrc = tile_rsrc<2, kRegTile + kHalo>(p, tp, true);
-    // ---- the chunk's samples: eight coalesced 16-byte loads per lane, all in flight -------------------------------------
-    u32x4 la[4], lb[4];
-    const uint32_t chunk_byte = __builtin_amdgcn_readfirstlane(wave) * (2u * kRegChunk);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        la[g] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16u, chunk_byte + 1024u * g, ADSB_LOAD_AUX);
-        lb[g] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16u, chunk_byte + 2u * kRegB + 1024u * g, ADSB_LOAD_AUX);
-    }
-    if (tid == 0 && first) {
-        p.hdr->retry = 0;
-        if (p.count_groups) { // first pass of a launch: the finishing kernel ORs this launch's flags in
-            p.hdr->flags = 0;
-            if (p.hdr_pub) p.hdr_pub[2] = 0;
-        }
-    }
-    if (tid == 0) {
-        misc[8] = 0;  // valid-frame counter
-        misc[12] = 0; // survivor counter
-    }
-    uint32_t bitsA = 0, bitsB = 0;
-    {
-        u32x4 ra[4], rb[4];
-        u32x4 *stage = reinterpret_cast<u32x4 *>(smem) + (ADSB_REG_STAGE_BYTES / 16) * wave;
-        reg_transpose(stage, la, ra, lane);
-        reg_transpose(stage, lb, rb, lane);
-        uint32_t N[32];
-        uint32_t lo = 0x7BFF7BFFu; // (the same detection of values that are no ordered f16 patterns as nsq_image_to_lds)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            uint32_t d[8];
-            nsq_pack16(ra[g], rb[g], d);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) N[8 * g + k] = d[k];
-#pragma unroll
-            for (int k = 0; k < 8; k += 2) lo = pkmin3<true>(lo, d[k], d[k + 1]);
-        }
-        const bool big = __builtin_amdgcn_ballot_w64(((lo & 0xFFFFu) >= 0x7C00u) || ((lo >> 16) >= 0x7C00u)) != 0; // (per wave)
-        if (!big) reg_gate<true>(N, bitsA, bitsB);
-        else reg_gate<false>(N, bitsA, bitsB);
-    }
-#if ADSB_REG_ABL == 2 // (measurement: loads + gate only, as the prototype)
-    if ((bitsA | bitsB) == 0x12345678u && n_valid == 7) misc[8] = 1;
-    return;
-#endif
-    // offsets that do not exist (adsb.rs:98: the channel's last 240 samples start no window), and lane 63
-    const uint32_t oa = wave * (uint32_t)kRegChunk + 32u * lane, ob = oa + (uint32_t)kRegB;
-    const uint32_t va = (lane < 63u && n_valid > oa) ? n_valid - oa : 0u, vb = (lane < 63u && n_valid > ob) ? n_valid - ob : 0u;
-    bitsA &= va >= 32u ? 0xFFFFFFFFu : ((1u << va) - 1u);
-    bitsB &= vb >= 32u ? 0xFFFFFFFFu : ((1u << vb) - 1u);
-    // the tile's survivor bitmap (read by the dense path only) and, unordered, its survivor list
-    if (lane < 63u) {
-        cand[wave * 126u + lane] = bitsA;
-        cand[wave * 126u + 63u + lane] = bitsB;
-    }
-    if (bitsA | bitsB) {
-        uint32_t pos = atomicAdd(&misc[12], (uint32_t)(__builtin_popcount(bitsA) + __builtin_popcount(bitsB)));
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            uint32_t bits = k ? bitsB : bitsA;
-            const uint32_t o0 = k ? ob : oa;
-            while (bits) {
-                const uint32_t bpos = __builtin_ctz(bits);
-                bits &= bits - 1;
-                if (pos < (uint32_t)kSparseCap) list[pos] = (uint16_t)(o0 + bpos);
-                ++pos;
-            }
-        }
-    }
-    __syncthreads();
-
-    // ---- hand-over: every survivor gets a frame slot, its absolute offset and its 14 sliced bytes (as scan_tile's phase 3) --
-    uint32_t total = p.fused_pass_only ? 0u : misc[12];
-#if ADSB_REG_ABL == 1 // (measurement: survivors counted, not handed over)
-    if (total != 0x7FFFFFFFu) total = 0;
-#endif
-    const bool dense = total > (uint32_t)kSparseCap;
-    u32x4 cw = {0, 0, 0, 0};
-    uint32_t cnt = 0, my_first = 0;
-    if (dense) { // ordered compaction of the bitmap by workgroup-wide prefix sums; words 4 tid .. 4 tid + 3 per thread
-        if (4 * tid < (uint32_t)(kRegTile / 32)) cw = reinterpret_cast<const u32x4 *>(cand)[tid];
-        cnt = __builtin_popcount(cw.x) + __builtin_popcount(cw.y) + __builtin_popcount(cw.z) + __builtin_popcount(cw.w);
-        uint32_t incl = cnt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            uint32_t t = __shfl_up(incl, d, 64);
-            if ((int)lane >= d) incl += t;
-        }
-        if (lane == 63) misc[wave] = incl;
-        __syncthreads();
-        uint32_t wbase = 0;
-        total = 0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) {
-            uint32_t t = misc[w];
-            wbase += (w < (int)wave) ? t : 0u;
-            total += t;
-        }
-        my_first = wbase + incl - cnt;
-    }
-    const bool simple = !dense && total <= kQuota;
-    const uint64_t abs0 = sample0 + p.offset_base; // absolute offset of this tile's offset 0
-    uint32_t base_slot = tile * kQuota;
-    const uint32_t g = tid >> 4, l = tid & 15;
-    auto slice_round = [&](uint32_t slot0, uint32_t ncl) {
-        for (uint32_t r = 0; r < ncl; r += kThreads / 16) {
-            if (r + 4 * wave >= ncl) break; // none of this wave's four groups has a survivor
-            const uint32_t ci = r + g;
-            const bool have = ci < ncl; // uniform within the 16-lane group
-            const uint32_t off = have ? list[ci] : 0u;
-            const uint32_t byte = reg_slice_byte(rsrc, off, l);
-            if (have) {
-                unsigned char *rec = reinterpret_cast<unsigned char *>(p.slots + (size_t)slot0 + ci);
-                const uint64_t o64 = abs0 + off;
-                if (l < 14) rec[8 + l] = (unsigned char)byte;
-                else reinterpret_cast<uint32_t *>(rec)[l - 14] = l == 14 ? (uint32_t)o64 : (uint32_t)(o64 >> 32);
-            }
-        }
-    };
-    if (simple) {
-        slice_round(base_slot, total);
-    } else {
-        if (tid == 0) {
-            const unsigned long long b64 = atomicAdd(&p.hdr->alloc, (unsigned long long)total);
-            misc[9] = (!p.pool_off && b64 + total <= (unsigned long long)p.cap_slots) ? p.pool_first + (uint32_t)b64 : kNoBase;
-        }
-        __syncthreads();
-        base_slot = misc[9];
-        for (uint32_t chunk = 0; chunk < total; chunk += kListCap) {
-            if (dense && cnt) {
-                uint32_t idx = my_first;
-                const uint32_t words[4] = {cw.x, cw.y, cw.z, cw.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    uint32_t bits = words[k];
-                    while (bits) {
-                        const uint32_t bpos = __builtin_ctz(bits);
-                        bits &= bits - 1;
-                        if (idx >= chunk && idx < chunk + kListCap) list[idx - chunk] = (uint16_t)((4 * tid + k) * 32 + bpos);
-                        ++idx;
-                    }
-                }
-            }
-            __syncthreads();
-            const uint32_t ncl = (total - chunk) < (uint32_t)kListCap ? (total - chunk) : (uint32_t)kListCap;
-            if (base_slot != kNoBase) {
-                slice_round(base_slot + chunk, ncl);
-            } else { // the slot store is full: this tile's survivors are decoded here only to be counted
-                for (uint32_t r = 0; r < ncl; r += kThreads / 16) {
-                    if (r + 4 * wave >= ncl) break;
-                    const uint32_t ci = r + g;
-                    const bool have = ci < ncl;
-                    const uint32_t off = have ? list[ci] : 0u;
-                    const bool valid = count_candidate(have, reg_slice_byte(rsrc, off, l), l, lane);
-                    if (valid && l == 0) atomicAdd(&misc[8], 1u);
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (tid == 0) {
-        Seg e;
-        e.base = base_slot;
-        e.cand = total;
-        e.valid = misc[8];
-        e.decoded = base_slot == kNoBase ? 1u : 0u;
-        p.seg[tile] = e;
-    }
-}
-
-#if ADSB_AB_KERNELS
-__global__ __launch_bounds__(kThreads, ADSB_REG_WAVES) void demod_tiles_reg(DemodArgs p)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char smem[RegLds::kTotal];
-    scan_tile_reg(p, p.tile_first + tile_of_workgroup(blockIdx.x, p.tile_count), blockIdx.x == 0, smem);
-}
-#endif
-
-// ---- the code scan (i8, kScanCode): the gate on an 8-bit LOG code of n = I^2 + Q^2, no root per sample --------------------
-// The root scan spends 3.5 of its 5.5 phase-1 issue slots per sample on floor(sqrt(n)) (v_sqrt_f32 alone holds the SIMD
-// for 8 cycles) and is VALU-issue-bound.  The gate (demod.rs:17-57) only ORDERS truncated roots, and every survivor is
-// checked again before it leaves the kernel, so the image the gate slides over may be any monotone 8-bit code c(n) as
-// long as the test on codes passes wherever the reference's test on floor(sqrt) passes (a SUPERSET test) and whatever
-// it lets through is decided exactly afterwards:
-//   * c(n) = e4m3((n + 16) / 128): one v_pk_fma_f32 + one v_cvt_pk_fp8_f32 per PAIR of samples (a quarter-rate
-//     conversion: 1 slot per sample where root + pack take 3.5).  Monotone in n; 8 codes per octave of n + 16.
-//   * the gate's values are 16-bit lanes [other sample's code | code << 8]: the code in the HIGH byte of an f16 bit
-//     pattern below 0x7C00, so v_pk_maximum3_f16 / v_pk_min_u16 order them by code (the low byte only breaks ties
-//     between equal codes and never reaches a decision: all compares are on byte 1 / byte 3).  An image dword holds the
-//     codes of samples 2q, 2q+1 of the tile's first half and of its second half: [A(2q), A(2q+1), B(2q), B(2q+1)] -- the
-//     dword as it is serves sample 2q+1 of a lane's two runs, shifted left by 8 bits sample 2q: half an unpacking
-//     instruction per step where the root image needs one v_perm.
-//   * floor(sqrt(hi)) >= floor(sqrt(lo)) holds exactly when lo <= top(hi), the largest n with hi's root.  On codes:
-//     c(lo) <= byte1(S(pattern(hi))) with S(x) = 1.5 x + 2^-7 in f16 ARITHMETIC on the pattern (one v_pk_fma_f16): the
-//     f16 value of a pattern grows like (n + 16)^2, so one multiply-add bends the slack the way 2 sqrt(n) needs -- wide
-//     (in codes) at low levels, one code at high ones.  That byte1(S(c(n) << 8)) >= c(top(n)) for EVERY n is checked on
-//     the device, through these very instructions, when a context is created (adsb_create fails otherwise), and again
-//     by tests/test_gpu_code_scan.py.
-//   * a survivor of the code gate is CERTAIN when the codes themselves are strictly ordered (then n is) in both groups,
-//     and a sliced bit is certain when c(x) > byte1(S(c(y))) (bit 1) or c(x) < c(y) (bit 0).  Anything else (0.6 per
-//     tile on the synthetic stream) is decided from the samples themselves: the 16-lane group re-reads its 240 samples
-//     (L2 / Infinity Cache; 480 bytes) and runs the reference's arithmetic -- floor(sqrt) by v_sqrt_f32 of n + 0.5 --
-//     on them.  A survivor that fails there leaves a record whose offset is all ones; finish_order skips it.
-// Everything downstream (slots, Seg, finish_order, the small-buffer kernel) is the root scan's.
-constexpr int kCodeHalf = kTile / 2;                    // samples in the half a lane's run A / run B slides over
-constexpr int kCodeLog = (kCodeHalf + kHalo) / 2;       // logical dwords of the image (two samples of each half per dword)
-// The gate's ds_read_b128 has lane L start at dword 16 L: lanes L, L+4, L+8, L+12 of a 16-lane read group fall on the same
-// banks (4-way).  -DADSB_CODE_PAD=1 puts 4 pad dwords after every 64 (conflict-free; the slicer then pays for the address
-// arithmetic): measured no faster (profiles/r04_ab_code_pad.txt) -- the LDS is 20 % busy either way.
-#ifndef ADSB_CODE_PAD
-#define ADSB_CODE_PAD 0
-#endif
-#ifndef ADSB_CODE_ABL
-#define ADSB_CODE_ABL 0
-#endif
-__host__ __device__ constexpr uint32_t code_phys(uint32_t q) { return ADSB_CODE_PAD ? q + 4u * (q >> 6) : q; }
-constexpr int kCodePhys = (int)code_phys(kCodeLog);
-constexpr int kCodeBias = 16;                           // c(n) = e4m3((n + kCodeBias) * 2^-kCodeShift)
-constexpr int kCodeShift = 7;
-constexpr uint32_t kCodeSlackMul = 0x3E003E00u;         // 1.5    (f16 x 2)
-constexpr uint32_t kCodeSlackAdd = 0x20002000u;         // 2^-7   (f16 x 2)
-static_assert(kRun == 32 && kThreads == 256 && kCodeHalf % (kThreads * 8) == 0 && kHalo == 256, "code scan geometry");
-
-struct CodeLds {
-    static constexpr int kOffCand = kCodePhys * 4;                 // survivor bitmap: word w = offsets 32 w .. 32 w + 31
-    static constexpr int kOffList = kOffCand + 2 * kThreads * 4;   // kListCap x u16
-    static constexpr int kOffMisc = kOffList + kListCap * 2;
-    static constexpr int kTotal = kOffMisc + 64;
-};
-static_assert(CodeLds::kTotal <= 20480, "eight workgroups per CU");
-
-// the threshold pattern of a pair of code patterns (see above): byte 1 / byte 3 of the result are what lows compare with
-__device__ __forceinline__ uint32_t code_slack(uint32_t x, uint32_t add = kCodeSlackAdd)
-{
-    const f16x2 r = __builtin_elementwise_fma(__builtin_bit_cast(f16x2, x), __builtin_bit_cast(f16x2, kCodeSlackMul),
-                                              __builtin_bit_cast(f16x2, add));
-    return __builtin_bit_cast(uint32_t, r);
-}
-__device__ __forceinline__ uint32_t byte1(uint32_t x) { return (x >> 8) & 0xFFu; }
-__device__ __forceinline__ uint32_t byte3(uint32_t x) { return x >> 24; }
-
-// (2^23 + n) as float bits (what the dot4 leaves) -> (n + kCodeBias) * 2^-kCodeShift, two samples per v_pk_fma_f32 (exact)
-__device__ __forceinline__ f32x2 code_arg(int n0, int n1)
-{
-    constexpr float s = 1.0f / (float)(1 << kCodeShift), t = ((float)kCodeBias - 8388608.0f) / (float)(1 << kCodeShift);
-    const f32x2 f = {__builtin_bit_cast(float, n0), __builtin_bit_cast(float, n1)};
-    return __builtin_elementwise_fma(f, (f32x2){s, s}, (f32x2){t, t});
-}
-
-// probe (adsb_create, tests): out[n] = c(n) | byte1(S(c(n) << 8)) << 8 for n = 0 .. 32768, through the scan's own code
-__global__ void code_probe_kernel(uint16_t *out)
-{
-    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
-    if (n > 32768u) return;
-    const f32x2 x = code_arg((int)(0x4B000000u + n), (int)(0x4B000000u + n));
-    const uint32_t c = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(x.x, x.y, 0, false) & 0xFFu;
-    out[n] = (uint16_t)(c | (byte1(code_slack(c << 8)) << 8));
-}
-hipError_t launch_code_probe(hipStream_t s, uint16_t *dev_out32769)
-{
-    hipLaunchKernelGGL(code_probe_kernel, dim3(129), dim3(256), 0, s, dev_out32769);
-    return hipGetLastError();
-}
-
-// [phase:1 code (loads, dots, conversions, stores)]
-constexpr int kCodeFull = kCodeHalf / (kThreads * 8);   // sweeps every lane takes part in (4); one more covers the halo
-__device__ __forceinline__ void code_issue_loads(__amdgpu_buffer_rsrc_t rsrc, uint32_t tid, u32x4 (&ra)[kCodeFull + 1], u32x4 (&rb)[kCodeFull + 1])
-{
-    // (the sweep's constant goes into the SGPR offset, which the descriptor's bounds check covers; reads past the channel
-    // end return zeros)
-#pragma unroll
-    for (int it = 0; it < kCodeFull; ++it) {
-        ra[it] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, tid * 16, (uint32_t)it * (kThreads * 16), ADSB_LOAD_AUX);
-        rb[it] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, tid * 16, (uint32_t)it * (kThreads * 16) + 2 * kCodeHalf, ADSB_LOAD_AUX);
-    }
-    if (__builtin_amdgcn_readfirstlane(tid & ~63u) * 8 < (uint32_t)kHalo) { // the halo: 256 samples of each half (wave 0, lanes 0-31)
-        ra[kCodeFull] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, tid * 16, (uint32_t)kCodeFull * (kThreads * 16), ADSB_LOAD_AUX);
-        rb[kCodeFull] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, tid * 16, (uint32_t)kCodeFull * (kThreads * 16) + 2 * kCodeHalf, ADSB_LOAD_AUX);
-    }
-}
-// 8 samples of the first half + the 8 samples half a tile further -> four image dwords
-__device__ __forceinline__ u32x4 code_pack16(u32x4 a, u32x4 b)
-{
-    int n[8];
-    uint32_t d[4];
-    dot4x8_sacc(a, 0x4B000000, n);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const f32x2 x = code_arg(n[2 * j], n[2 * j + 1]);
-        // (asm: the builtin ties the destination -- the conversion keeps its other half -- and costs a v_mov per dword; that
-        // half is overwritten below, so whatever the register held will do)
-        asm("v_cvt_pk_fp8_f32 %0, %1, %2" : "=v"(d[j]) : "v"(x.x), "v"(x.y));
-    }
-    dot4x8_sacc(b, 0x4B000000, n);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const f32x2 x = code_arg(n[2 * j], n[2 * j + 1]);
-        d[j] = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(x.x, x.y, (int)d[j], true);
-    }
-    return u32x4{d[0], d[1], d[2], d[3]};
-}
-__device__ __forceinline__ void code_image_to_lds(const u32x4 (&ra)[kCodeFull + 1], const u32x4 (&rb)[kCodeFull + 1], uint32_t *img, uint32_t tid)
-{
-    // logical dword of a lane's four in sweep `it`: it * 1024 + 4 tid; its pad 4 (it * 16 + (tid >> 4)): a constant per sweep
-    u32x4 *dst = reinterpret_cast<u32x4 *>(img + code_phys(4 * tid));
-#pragma unroll
-    for (int it = 0; it < kCodeFull; ++it) dst[(int)code_phys(it * kThreads * 4) / 4] = code_pack16(ra[it], rb[it]);
-    if (__builtin_amdgcn_readfirstlane(tid & ~63u) * 8 < (uint32_t)kHalo) {
-        const u32x4 d = code_pack16(ra[kCodeFull], rb[kCodeFull]);
-        if (tid * 8 < (uint32_t)kHalo) dst[(int)code_phys(kCodeFull * kThreads * 4) / 4] = d;
-    }
-}
-
-// [phase:2 code gate]
-// Preamble + DF17 superset test for the 2 x 32 offsets this lane owns: run A = offsets 32 tid + o, run B = kCodeHalf +
-// 32 tid + o.  Offsets that pass both groups on codes are OR-ed into the lane's words of the LDS bitmap (candA / candB).
-__device__ __forceinline__ void gate_phase_code(const uint32_t *img, uint32_t *candA, uint32_t *candB, const uint32_t tid, const uint32_t abl_key = 0)
-{
-    constexpr int RUN = kRun;
-    // (survivors are OR-ed straight into the lane's two bitmap words in LDS: accumulators in registers cost four copies
-    // per step at every join of the unrolled steps)
-    *candA = 0u;
-    *candB = 0u;
-    uint32_t slack_add = kCodeSlackAdd; // (VOP3P takes one scalar operand: the other constant lives in a VGPR, once)
-    asm volatile("" : "+v"(slack_add));
-    // logical dwords 16 tid + k, k < 29: this lane's 16 and the first 13 of the next lane's (which may lie behind a pad)
-    const u32x4 *g0 = reinterpret_cast<const u32x4 *>(img + code_phys(16 * tid));
-    const u32x4 *g1 = reinterpret_cast<const u32x4 *>(img + code_phys(16 * tid + 16));
-    constexpr int kGran = (RUN + 26 + 7) / 8; // granules of four dwords = eight samples of each run
-    constexpr int kAhead = 6;                 // 48 samples resident ahead of the current step
-    uint32_t W[kGran * 4];
-    auto fetch = [&](int g) {
-        const u32x4 x = g < 4 ? g0[g] : g1[g - 4];
-        W[4 * g] = x.x; W[4 * g + 1] = x.y; W[4 * g + 2] = x.z; W[4 * g + 3] = x.w;
-    };
-#pragma unroll
-    for (int g = 0; g < kAhead; ++g) fetch(g);
-    //   N[j]  the pair of code patterns of sample j  H2[j] = min(N[j], N[j+2])
-    //   W3[j] = max(N[j..j+2])                       F[j]  = max(N[j], W3[j+2], N[j+5])
-    // highs of offset o: min(H2[o], H2[o+7]);  lows: max(F[o+1], F[o+8], W3[o+13])
-    uint32_t N[RUN + 26], H2[RUN + 8], W3[RUN + 16], F[RUN + 9];
-#define ADSB_CODE_N(j) (((j) & 1) ? W[(j) >> 1] : (W[(j) >> 1] << 8))
-#pragma unroll
-    for (int k = 0; k < 25; ++k) N[k] = ADSB_CODE_N(k);
-#pragma unroll
-    for (int j = 0; j < 7; ++j) H2[j] = pkmin(N[j], N[j + 2]);
-#pragma unroll
-    for (int j = 3; j < 13; ++j) W3[j] = pkmax3<true>(N[j], N[j + 1], N[j + 2]);
-#pragma unroll
-    for (int j = 1; j < 8; ++j) F[j] = pkmax3<true>(N[j], W3[j + 2], N[j + 5]);
-#pragma unroll
-    for (int o = 0; o < RUN; ++o) {
-        if (o % 8 == 0) {
-            const int g = o / 8 + kAhead;
-            if (g < kGran) fetch(g);
-        }
-        N[o + 25] = ADSB_CODE_N(o + 25);
-        W3[o + 13] = pkmax3<true>(N[o + 13], N[o + 14], N[o + 15]);
-        F[o + 8] = pkmax3<true>(N[o + 8], W3[o + 10], N[o + 13]);           // lows 8,10,11,12,13
-        const uint32_t lo = pkmax3<true>(F[o + 1], F[o + 8], W3[o + 13]);   // + 1,3,4,5,6 + 13,14,15
-        H2[o + 7] = pkmin(N[o + 7], N[o + 9]);
-        const uint32_t hi = pkmin(H2[o], H2[o + 7]);                        // highs 0,2,7,9
-        const uint32_t th = code_slack(hi, slack_add);
-        const bool pa = byte1(th) >= byte1(lo);
-        const bool pb = byte3(th) >= byte3(lo);
-        // wave-uniform tests (scalar branches): a block is entered by the whole wave when any lane needs it
-#if ADSB_CODE_ABL == 1 // (measurement only, wrong results: the hot path alone -- the cold block is never entered)
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64((pa | pb) && abl_key == 7u) != 0, 0)) { // (n_valid == 7: never)
-#else
-        if (__builtin_expect(__builtin_amdgcn_ballot_w64(pa | pb) != 0, 0)) {
-#endif
-            // DF17 part of the gate (demod.rs:45-54), the same superset test
-            const uint32_t dh = pkmin3<true>(pkmin3<true>(N[o + 16], N[o + 19], N[o + 21]), N[o + 23], N[o + 24]);
-            const uint32_t dl = pkmax3<true>(pkmax3<true>(N[o + 17], N[o + 18], N[o + 20]), N[o + 22], N[o + 25]);
-            const uint32_t t2 = code_slack(dh, slack_add);
-            const bool sa = pa & (byte1(t2) >= byte1(dl));
-            const bool sb = pb & (byte3(t2) >= byte3(dl));
-            uint32_t bit = 1u << o;
-            asm("" : "+v"(bit)); // one v_mov for both stores
-            if (sa) atomicOr(candA, bit);
-            if (sb) atomicOr(candB, bit);
-        }
-    }
-#undef ADSB_CODE_N
-}
-
-// [phase:3 code slicer]
-// One survivor (tile offset `off`) by its 16-lane group, from the codes.  Lane l < 14: frame byte l -- bit = 1 where
-// c(x) > byte1(S(c(y))) (then floor(sqrt(x)) > floor(sqrt(y)): x lies above every n that shares y's root), 0 where
-// c(x) < c(y) (then x < y).  Lane 14 looks at the preamble's 16 samples, lane 15 at the ten DF17 samples: the gate's
-// verdict is CERTAIN where the codes themselves are strictly ordered (then n is).  Returns the lane's byte; `unc_mask` =
-// the wave's lanes that saw a pair / a group which is neither: the samples themselves decide (exact_from_raw).
-__device__ __forceinline__ uint32_t code_slice_byte(const uint32_t *img, const uint32_t off, const uint32_t l, unsigned long long &unc_mask)
-{
-    const uint32_t h = off >= (uint32_t)kCodeHalf ? 1u : 0u;
-    // the lane's first sample, counted inside its half: byte l's sixteen, the preamble's (lane 14), DF17's (lane 15)
-    const uint32_t s0 = off - h * (uint32_t)kCodeHalf + (l < 14u ? 16u + 16u * l : (l == 14u ? 0u : 16u));
-    const uint32_t e = s0 & 1u, q = s0 >> 1;
-    uint32_t D[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) D[i] = img[code_phys(q + (uint32_t)i)];
-    // [0, c(y), 0, c(x)] of the lane's pair k (x = its sample 2k, y = 2k+1) by one v_perm over dwords k, k+1 (selectors
-    // 0-3: 2nd operand, 4-7: 1st, 0x0C: zero): e = 0: bytes 2h, 2h+1 of dword k;  e = 1: byte 2h+1 of dword k, byte 2h of k+1
-    const uint32_t cx_sel = 2u * h + e, cy_sel = e ? 4u + 2u * h : 2u * h + 1u;
-    const uint32_t sel = 0x000C000Cu | (cy_sel << 8) | (cx_sel << 24);
-    uint32_t xy[8], t[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        xy[k] = __builtin_amdgcn_perm(D[k + 1], D[k], sel);
-        t[k] = code_slack(xy[k]);
-    }
-    // bit k = c(x) > byte1(S(c(y))), MSB first: one SDWA compare per pair into its own SGPR pair, then byte = byte + byte +
-    // carry-in per pair (v_addc): no v_cndmask.  All eight compares come first: gfx950 wants 2 wait states between a VALU
-    // writing an SGPR and a VALU reading it, and hipcc pads nothing inside asm.
-    uint32_t byte = 0;
-    uint64_t m0, m1, m2, m3, m4, m5, m6, m7;
-    asm("v_cmp_gt_u32_sdwa %1, %9, %17 src0_sel:BYTE_3 src1_sel:BYTE_1\n\t"
-        "v_cmp_gt_u32_sdwa %2, %10, %18 src0_sel:BYTE_3 src1_sel:BYTE_1\n\t"
-        "v_cmp_gt_u32_sdwa %3, %11, %19 src0_sel:BYTE_3 src1_sel:BYTE_1\n\t"
-        "v_cmp_gt_u32_sdwa %4, %12, %20 src0_sel:BYTE_3 src1_sel:BYTE_1\n\t"
-        "v_cmp_gt_u32_sdwa %5, %13, %21 src0_sel:BYTE_3 src1_sel:BYTE_1\n\t"
-        "v_cmp_gt_u32_sdwa %6, %14, %22 src0_sel:BYTE_3 src1_sel:BYTE_1\n\t"
-        "v_cmp_gt_u32_sdwa %7, %15, %23 src0_sel:BYTE_3 src1_sel:BYTE_1\n\t"
-        "v_cmp_gt_u32_sdwa %8, %16, %24 src0_sel:BYTE_3 src1_sel:BYTE_1\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %1\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %2\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %3\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %4\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %5\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %6\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %7\n\t"
-        "v_addc_co_u32_e64 %0, vcc, %0, %0, %8"
-        : "+v"(byte), "=&s"(m0), "=&s"(m1), "=&s"(m2), "=&s"(m3), "=&s"(m4), "=&s"(m5), "=&s"(m6), "=&s"(m7)
-        : "v"(xy[0]), "v"(xy[1]), "v"(xy[2]), "v"(xy[3]), "v"(xy[4]), "v"(xy[5]), "v"(xy[6]), "v"(xy[7]),
-          "v"(t[0]), "v"(t[1]), "v"(t[2]), "v"(t[3]), "v"(t[4]), "v"(t[5]), "v"(t[6]), "v"(t[7])
-        : "vcc");
-    // a pair is decided when bit 1 is certain (above) or c(x) < c(y); the lane masks stay in scalar registers
-    const uint64_t ms[8] = {m0, m1, m2, m3, m4, m5, m6, m7};
-    unsigned long long decided = ~0ull;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) decided &= ms[k] | __builtin_amdgcn_ballot_w64(byte3(xy[k]) < byte1(xy[k]));
-    // even samples sit in the high halves, odd ones in the low halves (patterns c << 8)
-    // preamble (demod.rs:20-22): highs 0, 2, 7, 9; lows the other twelve
-    const uint32_t p1 = pkmin(xy[0], xy[1]), p2 = pkmin(xy[3], xy[4]);                       // hi: {0, 2} | lo: {7, 9}
-    const uint32_t ma = pkmax3<true>(xy[2], xy[3], xy[4]), mb = pkmax3<true>(xy[5], xy[6], xy[7]); // hi: {4,6,8}, {10,12,14}
-    const uint32_t mc = pkmax3<true>(xy[0], xy[1], xy[2]);                                    // lo: {1,3,5}; mb lo: {11,13,15}
-    const uint32_t pre_hi = min(p1 >> 16, p2 & 0xFFFFu);
-    const uint32_t pre_lo = max(max(ma >> 16, mb >> 16), max(mc & 0xFFFFu, mb & 0xFFFFu));
-    // DF17 (demod.rs:41-44) on the lane's samples 0 .. 9: highs 0, 3, 5, 7, 8; lows 1, 2, 4, 6, 9
-    const uint32_t q1 = pkmin(xy[0], xy[4]), q2 = pkmin3<true>(xy[1], xy[2], xy[3]);         // hi: {0, 8} | lo: {3, 5, 7}
-    const uint32_t r1 = pkmax3<true>(xy[1], xy[2], xy[3]), r2 = pkmax(xy[0], xy[4]);         // hi: {2, 4, 6} | lo: {1, 9}
-    const uint32_t df_hi = min(q1 >> 16, q2 & 0xFFFFu), df_lo = max(r1 >> 16, r2 & 0xFFFFu);
-    const unsigned long long pre_ok = __builtin_amdgcn_ballot_w64(pre_hi > pre_lo), df_ok = __builtin_amdgcn_ballot_w64(df_hi > df_lo);
-    constexpr unsigned long long k14 = 0x4000400040004000ull, k15 = 0x8000800080008000ull; // lane 14 / 15 of every group
-    unc_mask = (~decided & ~(k14 | k15)) | (~pre_ok & k14) | (~df_ok & k15);
-    return byte;
-}
-
-// [phase:3 exact_from_raw (uncertain survivors only: cold)]
-// The reference's own arithmetic on a survivor's 240 samples, by its 16-lane group (ALL 16 lanes active): lane l < 14
-// takes frame byte l (samples off + 16 + 16 l .. + 15 of the tile), lane 14 the preamble (samples off .. off + 15), lane 15
-// repeats lane 14.  m = floor(sqrt(I^2+Q^2)) as utils.rs:46-52 (v_sqrt_f32 of n + 0.5, truncated: exact for n <= 32768).
-// Returns the lane's byte; gate_ok (group-uniform) = the preamble test on lane 14's magnitudes (demod.rs:23-36) and the
-// DF17 test on the first ten of lane 0's (demod.rs:45-54).
-__device__ __forceinline__ uint32_t exact_from_raw(__amdgpu_buffer_rsrc_t rsrc, const uint32_t off, const uint32_t l, const uint32_t lane, bool &gate_ok)
-{
-    const uint32_t s = off + (l < 14u ? 16u + 16u * l : 0u);
-    const uint32_t a = 2u * s, base = a & ~3u, sh = a & 3u; // (sh = 0 or 2)
-    const u32x4 v0 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, base, 0, 0), v1 = __builtin_amdgcn_raw_buffer_load_b128(rsrc, base + 16u, 0, 0);
-    const uint32_t v2 = __builtin_amdgcn_raw_buffer_load_b32(rsrc, base + 32u, 0, 0);
-    const uint32_t d[9] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2};
-    uint32_t m[16];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint32_t w = __builtin_amdgcn_alignbyte(d[k + 1], d[k], sh); // [I, Q, I', Q'] of samples 2k, 2k+1
-        const int n0 = __builtin_amdgcn_sdot4((int)(w & 0xFFFFu), (int)w, 0x4B000000, false);
-        const int n1 = __builtin_amdgcn_sdot4((int)(w & 0xFFFF0000u), (int)w, 0x4B000000, false);
-        m[2 * k] = (uint32_t)__builtin_amdgcn_sqrtf(__builtin_bit_cast(float, n0) - 8388607.5f);
-        m[2 * k + 1] = (uint32_t)__builtin_amdgcn_sqrtf(__builtin_bit_cast(float, n1) - 8388607.5f);
-    }
-    uint32_t byte = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) byte |= (m[2 * k] > m[2 * k + 1] ? 1u : 0u) << (7 - k);
-    auto mn = [](uint32_t x, uint32_t y) { return x < y ? x : y; };
-    auto mx = [](uint32_t x, uint32_t y) { return x > y ? x : y; };
-    const uint32_t hi = mn(mn(m[0], m[2]), mn(m[7], m[9]));
-    const uint32_t lo = mx(mx(mx(mx(m[1], m[3]), mx(m[4], m[5])), mx(mx(m[6], m[8]), mx(m[10], m[11]))), mx(mx(m[12], m[13]), mx(m[14], m[15])));
-    const uint32_t dh = mn(mn(mn(m[0], m[3]), mn(m[5], m[7])), m[8]);
-    const uint32_t dl = mx(mx(mx(m[1], m[2]), mx(m[4], m[6])), m[9]);
-    const unsigned long long pm = __builtin_amdgcn_ballot_w64(hi >= lo), dm = __builtin_amdgcn_ballot_w64(dh >= dl);
-    const uint32_t g0 = lane & 48u;
-    gate_ok = (((pm >> (g0 + 14u)) & (dm >> g0)) & 1ull) != 0;
-    return byte;
-}
-
-// [phase:end]
-__device__ __forceinline__ void scan_tile_code(const DemodArgs &p, const uint32_t tile, const bool first, unsigned char *smem)
-{
-    typedef CodeLds L;
-    uint32_t *img = reinterpret_cast<uint32_t *>(smem);
-    uint32_t *cand = reinterpret_cast<uint32_t *>(smem + L::kOffCand);
-    uint16_t *list = reinterpret_cast<uint16_t *>(smem + L::kOffList);
-    uint32_t *misc = reinterpret_cast<uint32_t *>(smem + L::kOffMisc);
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const TilePos tp = tile_pos<kTile>(p, tile);
-    const uint64_t sample0 = tp.sample0;
-    const uint32_t n_valid = tp.n_valid;
-    __amdgpu_buffer_rsrc_t rsrc = tile_rsrc<2, kMag>(p, tp, true);
-    // [phase:1 code (loads, dots, conversions, stores)]
-    u32x4 ra[kCodeFull + 1], rb[kCodeFull + 1];
-    code_issue_loads(rsrc, tid, ra, rb);
-    if (tid == 0 && first) {
-        p.hdr->retry = 0;
-        if (p.count_groups) { // first pass of a launch: the finishing kernel ORs this launch's flags in
-            p.hdr->flags = 0;
-            if (p.hdr_pub) p.hdr_pub[2] = 0;
-        }
-    }
-    if (tid == 0) {
-        misc[8] = 0;  // valid-frame counter (tiles without slots only)
-        misc[12] = 0; // survivor counter
-    }
-    code_image_to_lds(ra, rb, img, tid);
-    __syncthreads();
-#if ADSB_ABL_PHASES < 2
-    if (smem[tid * 64] == 0xFD && smem[tid * 64 + 1] == 0xFE && n_valid == 7) misc[12] = 1;
-#else
-    // [phase:2 code gate]
-    gate_phase_code(img, cand + tid, cand + kThreads + tid, tid, n_valid);
-    {
-        // (word w of the bitmap = offsets 32 w .. 32 w + 31: the lane's run A is word tid, its run B word kThreads + tid)
-        uint32_t bitsA = cand[tid], bitsB = cand[kThreads + tid];
-        const uint32_t oa = tid * (uint32_t)kRun, ob = oa + (uint32_t)kCodeHalf;
-        // offsets at or beyond n_valid do not exist in the reference loop (adsb.rs:98): the ragged last tile of a channel
-        if (n_valid < (uint32_t)kTile) { // (wave-uniform)
-            const uint32_t va = n_valid > oa ? n_valid - oa : 0u, vb = n_valid > ob ? n_valid - ob : 0u;
-            bitsA &= va >= 32u ? 0xFFFFFFFFu : ((1u << va) - 1u);
-            bitsB &= vb >= 32u ? 0xFFFFFFFFu : ((1u << vb) - 1u);
-            cand[tid] = bitsA; // (the dense path reads the bitmap itself)
-            cand[kThreads + tid] = bitsB;
-        }
-        // survivors are rare (a handful per tile): the few lanes that have any append their offsets, unordered, to the list
-        if (bitsA | bitsB) {
-            uint32_t pos = atomicAdd(&misc[12], (uint32_t)(__builtin_popcount(bitsA) + __builtin_popcount(bitsB)));
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                uint32_t bits = k ? bitsB : bitsA;
-                const uint32_t o0 = k ? ob : oa;
-                while (bits) {
-                    const uint32_t b = (uint32_t)__builtin_ctz(bits);
-                    bits &= bits - 1;
-                    if (pos < (uint32_t)kSparseCap) list[pos] = (uint16_t)(o0 + b);
-                    ++pos;
-                }
-            }
-        }
-    }
-#endif
-    __syncthreads();
-
-    // [phase:3 hand-over: slots, offsets, sliced bytes]
-    // Every survivor of the code gate gets a frame slot, its absolute offset and its 14 sliced bytes; one that the samples
-    // themselves reject gets an all-ones offset (finish_order skips it).  CRC-24, repair, ordering: finish_order.
-    uint32_t total = p.fused_pass_only ? 0u : misc[12];
-#if ADSB_ABL_PHASES < 3
-    if (total != 0x7FFFFFFFu) total = 0;
-#endif
-    const bool dense = total > (uint32_t)kSparseCap;
-    u32x4 cw = {0, 0, 0, 0};
-    uint32_t cnt = 0, my_first = 0;
-    if (dense) { // ordered compaction of the bitmap by workgroup-wide prefix sums; words 4 tid .. 4 tid + 3 per thread
-        if (4 * tid < (uint32_t)(kTile / 32)) cw = reinterpret_cast<const u32x4 *>(cand)[tid];
-        cnt = __builtin_popcount(cw.x) + __builtin_popcount(cw.y) + __builtin_popcount(cw.z) + __builtin_popcount(cw.w);
-        uint32_t incl = cnt;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            uint32_t t = __shfl_up(incl, d, 64);
-            if ((int)lane >= d) incl += t;
-        }
-        if (lane == 63) misc[wave] = incl;
-        __syncthreads();
-        uint32_t wbase = 0;
-        total = 0;
-#pragma unroll
-        for (int w = 0; w < kThreads / 64; ++w) {
-            uint32_t t = misc[w];
-            wbase += (w < (int)wave) ? t : 0u;
-            total += t;
-        }
-        my_first = wbase + incl - cnt;
-    }
-    const bool simple = !dense && total <= kQuota;
-    const uint64_t abs0 = sample0 + p.offset_base; // absolute offset of this tile's offset 0
-    uint32_t base_slot = tile * kQuota;
-    const uint32_t g = tid >> 4, l = tid & 15;
-    // one survivor per 16-lane group: its byte from the codes, or -- gate or some pair uncertain -- from the samples
-    auto slice_one = [&](const bool have, const uint32_t off, bool &dropped) {
-        unsigned long long um;
-        uint32_t byte = code_slice_byte(img, off, l, um);
-        um &= __builtin_amdgcn_ballot_w64(have);
-        const bool grp_unc = ((um >> (lane & 48u)) & 0xFFFFull) != 0;
-        dropped = false;
-        if (um != 0) { // (wave-uniform) some group of this wave needs the samples themselves
-            bool ok;
-            const uint32_t eb = exact_from_raw(rsrc, off, l, lane, ok);
-            if (grp_unc) {
-                byte = eb;
-                dropped = !ok;
-            }
-        }
-        return byte;
-    };
-    auto slice_round = [&](uint32_t slot0, uint32_t ncl) {
-        for (uint32_t r = 0; r < ncl; r += kThreads / 16) {
-            if (r + 4 * wave >= ncl) break; // none of this wave's four groups has a survivor
-            const uint32_t ci = r + g;
-            const bool have = ci < ncl; // uniform within the 16-lane group
-            const uint32_t off = have ? list[ci] : 0u;
-            bool dropped;
-            const uint32_t byte = slice_one(have, off, dropped);
-            if (have) {
-                unsigned char *rec = reinterpret_cast<unsigned char *>(p.slots + (size_t)slot0 + ci);
-                const uint64_t o64 = dropped ? ~0ull : abs0 + off;
-                if (l < 14) rec[8 + l] = (unsigned char)byte;
-                else reinterpret_cast<uint32_t *>(rec)[l - 14] = l == 14 ? (uint32_t)o64 : (uint32_t)(o64 >> 32);
-            }
-        }
-    };
-    if (simple) {
-        slice_round(base_slot, total); // unordered list (finish_order ranks it): survivor j -> slot j
-    } else {
-        if (tid == 0) {
-            const unsigned long long b64 = atomicAdd(&p.hdr->alloc, (unsigned long long)total);
-            misc[9] = (!p.pool_off && b64 + total <= (unsigned long long)p.cap_slots) ? p.pool_first + (uint32_t)b64 : kNoBase;
-        }
-        __syncthreads();
-        base_slot = misc[9];
-        for (uint32_t chunk = 0; chunk < total; chunk += kListCap) {
-            if (dense && cnt) {
-                uint32_t idx = my_first;
-                const uint32_t words[4] = {cw.x, cw.y, cw.z, cw.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    uint32_t bits = words[k];
-                    while (bits) {
-                        const uint32_t b = (uint32_t)__builtin_ctz(bits);
-                        bits &= bits - 1;
-                        if (idx >= chunk && idx < chunk + kListCap) list[idx - chunk] = (uint16_t)((4 * tid + k) * 32 + b);
-                        ++idx;
-                    }
-                }
-            }
-            __syncthreads();
-            const uint32_t ncl = (total - chunk) < (uint32_t)kListCap ? (total - chunk) : (uint32_t)kListCap;
-            if (base_slot != kNoBase) {
-                slice_round(base_slot + chunk, ncl);
-            } else { // the slot store is full: this tile's survivors are decoded here only to be counted
-                for (uint32_t r = 0; r < ncl; r += kThreads / 16) {
-                    if (r + 4 * wave >= ncl) break;
-                    const uint32_t ci = r + g;
-                    const bool have = ci < ncl;
-                    const uint32_t off = have ? list[ci] : 0u;
-                    bool dropped;
-                    const uint32_t byte = slice_one(have, off, dropped);
-                    const bool valid = count_candidate(have && !dropped, byte, l, lane);
-                    if (valid && l == 0) atomicAdd(&misc[8], 1u);
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (tid == 0) {
-        Seg e;
-        e.base = base_slot;
-        e.cand = total;
-        e.valid = misc[8];
-        e.decoded = base_slot == kNoBase ? 1u : 0u;
-        p.seg[tile] = e;
-    }
-}
-
-#if ADSB_AB_KERNELS
-__global__ __launch_bounds__(kThreads, 8) void demod_tiles_code(DemodArgs p)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char smem[CodeLds::kTotal];
-    scan_tile_code(p, p.tile_first + tile_of_workgroup(blockIdx.x, p.tile_count), blockIdx.x == 0, smem);
-}
-#endif
-
-#include "adsb_sieve.inc"
+// ---- the laboratory scans (A/B: bit-exact, none faster) -------------------------------------------------------------
+// Each file holds one scan: image layout, loads, gate, slicer, scan_tile_*, its kernel (-DADSB_AB_KERNELS=1 only) and its
+// private knobs.  (The device bodies and the two probe kernels the C ABI exposes in every build are always compiled.)
+#include "ab/nsq.inc"
+#include "ab/reg.inc"
+#include "ab/code.inc"
+#include "ab/sieve.inc"
 
 // ---- small buffers: scan + finish in ONE dispatch, results straight into host memory --------------------------------------
 // A buffer of at most kFinTiles tiles (the reference's own buffers: 20 000 samples = 2 tiles, adsb.rs:77-79; an SDR's MTU-
@@ -2630,13 +1426,14 @@ static_assert(kFinThreads == kThreads, "the small-buffer kernel runs both bodies
 template <int ST, int MAGMODE, int SCAN>
 __global__ __launch_bounds__(kThreads, 4) void demod_small(DemodArgs p, FinishArgs f, SmallArgs sm)
 {
-    constexpr int kScanBytes = SCAN == kScanSieve ? SieveLds::kTotal : SCAN == kScanReg ? RegLds::kTotal : SCAN == kScanCode ? CodeLds::kTotal : Lds<ST, (SCAN == kScanReg || SCAN == kScanCode || SCAN == kScanSieve) ? kScanRoot : SCAN>::kTotal, kFinBytes = kFinLdsWords * 4;
+    constexpr int kScanBytes = SCAN == kScanSieve ? SieveLds::kTotal : SCAN == kScanReg ? RegLds::kTotal : SCAN == kScanCode ? CodeLds::kTotal : SCAN == kScanNsq ? NsqLds::kTotal : Lds<ST>::kTotal, kFinBytes = kFinLdsWords * 4;
     __shared__ __attribute__((aligned(16))) unsigned char smem[kScanBytes > kFinBytes ? kScanBytes : kFinBytes];
     __shared__ uint32_t last_flag;
     if constexpr (SCAN == kScanSieve) scan_tile_sieve(p, p.tile_first + blockIdx.x, blockIdx.x == 0, smem);
     else if constexpr (SCAN == kScanReg) scan_tile_reg(p, p.tile_first + blockIdx.x, blockIdx.x == 0, smem);
     else if constexpr (SCAN == kScanCode) scan_tile_code(p, p.tile_first + blockIdx.x, blockIdx.x == 0, smem);
-    else scan_tile<ST, MAGMODE, SCAN>(p, p.tile_first + blockIdx.x, blockIdx.x == 0, smem);
+    else if constexpr (SCAN == kScanNsq) scan_tile_nsq(p, p.tile_first + blockIdx.x, blockIdx.x == 0, smem);
+    else scan_tile<ST, MAGMODE>(p, p.tile_first + blockIdx.x, blockIdx.x == 0, smem);
     // hand-off to whichever workgroup arrives last (cdna_hip_programming.md Guideline 16: every storing wave drains its
     // stores, the workgroup's barrier, one lane's agent-scope release, then the counter; the reader acquires)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2716,9 +1513,9 @@ static hipError_t launch_demod_st(hipStream_t s, int mag_mode, const DemodArgs &
     dim3 grid(grid_x), block(kThreads);
     if (ST == ADSB_SAMPLE_I16) mag_mode = 0; // the CS16 magnitude chain does not depend on the converter's rounding
     switch (mag_mode) {
-    case 0: hipExtLaunchKernelGGL((demod_tiles<ST, 0, kScanRoot>), grid, block, 0, s, e0, e1, 0, a); break;
-    case 1: hipExtLaunchKernelGGL((demod_tiles<ST, ST == ADSB_SAMPLE_I8 ? 1 : 0, kScanRoot>), grid, block, 0, s, e0, e1, 0, a); break;
-    default: hipExtLaunchKernelGGL((demod_tiles<ST, ST == ADSB_SAMPLE_I8 ? 2 : 0, kScanRoot>), grid, block, 0, s, e0, e1, 0, a); break;
+    case 0: hipExtLaunchKernelGGL((demod_tiles<ST, 0>), grid, block, 0, s, e0, e1, 0, a); break;
+    case 1: hipExtLaunchKernelGGL((demod_tiles<ST, ST == ADSB_SAMPLE_I8 ? 1 : 0>), grid, block, 0, s, e0, e1, 0, a); break;
+    default: hipExtLaunchKernelGGL((demod_tiles<ST, ST == ADSB_SAMPLE_I8 ? 2 : 0>), grid, block, 0, s, e0, e1, 0, a); break;
     }
     return hipGetLastError();
 }
@@ -2745,7 +1542,7 @@ hipError_t launch_demod(hipStream_t s, int sample_type, int mag_mode, int scan, 
         return hipGetLastError();
     }
     if (sample_type == ADSB_SAMPLE_I8 && scan == kScanNsq) {
-        hipExtLaunchKernelGGL((demod_tiles<ADSB_SAMPLE_I8, 0, kScanNsq>), dim3(a.tile_count), dim3(kThreads), 0, s, e0, e1, 0, a);
+        hipExtLaunchKernelGGL(demod_tiles_nsq, dim3(a.tile_count), dim3(kThreads), 0, s, e0, e1, 0, a);
         return hipGetLastError();
     }
     if (sample_type == ADSB_SAMPLE_I8 && scan == kScanReg) {
@@ -2868,35 +1665,6 @@ hipError_t launch_magnitudes(hipStream_t s, int sample_type, int mag_mode, const
     } else {
         hipLaunchKernelGGL((magnitudes_kernel<ADSB_SAMPLE_I8, 2>), grid, block, 0, s, iq, n, out);
     }
-    return hipGetLastError();
-}
-
-// nsq test hook: v = I^2 + Q^2 + 72 of n i8 samples through the scan kernel's own packing code (every group of 8
-// samples is packed once as the "A" AND the "B" operand: both halves must agree, else 0xFFFF is reported).
-__global__ void nsq_values_kernel(const void *iq, size_t n, uint16_t *out)
-{
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    const size_t groups = (n + 7) / 8;
-    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += stride) {
-        const uint16_t *src = reinterpret_cast<const uint16_t *>(iq) + g * 8;
-        uint16_t tmp[8];
-        for (int k = 0; k < 8; ++k) tmp[k] = (g * 8 + k < n) ? src[k] : (uint16_t)0;
-        u32x4 v;
-        v.x = tmp[0] | ((uint32_t)tmp[1] << 16);
-        v.y = tmp[2] | ((uint32_t)tmp[3] << 16);
-        v.z = tmp[4] | ((uint32_t)tmp[5] << 16);
-        v.w = tmp[6] | ((uint32_t)tmp[7] << 16);
-        uint32_t d[8];
-        nsq_pack16(v, v, d);
-        for (int k = 0; k < 8; ++k)
-            if (g * 8 + k < n) out[g * 8 + k] = (d[k] & 0xFFFFu) == (d[k] >> 16) ? (uint16_t)(d[k] & 0xFFFFu) : (uint16_t)0xFFFFu;
-    }
-}
-
-hipError_t launch_nsq_values(hipStream_t s, const void *iq, size_t n, uint16_t *out)
-{
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(nsq_values_kernel, dim3(1024), dim3(256), 0, s, iq, n, out);
     return hipGetLastError();
 }
 

@@ -55,6 +55,17 @@ def test_constant_saturated_coarse(dem, oracle):
         _check(dem, oracle, rng.integers(-amp, amp + 1, size=(150_000, 2), dtype=np.int8))
 
 
+def test_hand_over_count_edges(dem, oracle):
+    """240 + k constant samples = exactly k survivors in one ragged tile, TILE + 240 + k = a full dense tile in front of it:
+    the quota edge (32 | 33), the unordered-list edge (64 | 65), one | two chunks of the list (128 | 129), a third (300)"""
+    for k in (1, 32, 33, 64, 65, 128, 129, 300):
+        for dense_tiles in (0, 1):
+            iq = np.empty((dense_tiles * TILE + 240 + k, 2), dtype=np.int8)
+            iq[:] = (-128, -128) if k == 129 else (3, 4)
+            frames = _check(dem, oracle, iq)
+            assert len(frames) == dense_tiles * TILE + k
+
+
 def test_error_mix_and_planted_frames(dem, oracle):
     cfg = A.synth_default(seed=77, slot_len=600, pct_flip_data=20, pct_flip_crc=10, pct_flip_two=10)
     iq = A.synth_fill_host(cfg, A.ADSB_SAMPLE_I8, 0, 0, 2_000_000)

@@ -1,4 +1,4 @@
-"""CPU-tier checks of the arithmetic the sieve scan (air_rs_amd/csrc/adsb_sieve.inc, A/B build) rests on.
+"""CPU-tier checks of the arithmetic the sieve scan (air_rs_amd/csrc/ab/sieve.inc, A/B build) rests on.
 
 The kernel itself is compared with the oracle on the GPU (tests/ab_cases.py under ADSB_SCAN=sieve); here the claims its header
 makes are checked exhaustively in numpy, with the float32 operations the kernel uses:
@@ -69,7 +69,7 @@ def test_gate_implies_all_fourteen_taps():
 
 
 def test_tap_algebra_on_words_equals_the_fourteen_taps():
-    """sv_taps (adsb_sieve.inc): Y = L & G>>1, Z = Y & Y>>2, A = G & Y>>1, P = A & Z>>6 & G>>16 & Z>>18 & L>>22 & G>>24 on a 96-bit
+    """sv_taps (ab/sieve.inc): Y = L & G>>1, Z = Y & Y>>2, A = G & Y>>1, P = A & Z>>6 & G>>16 & Z>>18 & L>>22 & G>>24 on a 96-bit
     window, restated on Python integers, against the fourteen taps evaluated one by one."""
     rng = np.random.default_rng(11)
     m96 = (1 << 96) - 1

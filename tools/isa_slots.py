@@ -83,7 +83,8 @@ def main():
     a = ap.parse_args()
 
     srcdir = os.path.dirname(os.path.abspath(a.src))
-    markers = phase_ranges([os.path.join(srcdir, f) for f in os.listdir(srcdir) if f.endswith((".hip", ".h"))])
+    # (the source directory and what it includes from below it: csrc/ab/*.inc)
+    markers = phase_ranges([os.path.join(d, f) for d, _, fs in os.walk(srcdir) for f in fs if f.endswith((".hip", ".h", ".inc"))])
 
     with tempfile.TemporaryDirectory() as td:
         s_path = os.path.join(td, "k.s")
@@ -102,7 +103,7 @@ def main():
         if s.startswith(".loc"):
             # innermost location first, then the inlined-at chain: take the first one inside the source directory
             for path, line in re.findall(r"([^\s:\[;]+):(\d+):\d+", s):
-                if os.path.dirname(os.path.abspath(path)) == srcdir and int(line) > 0:
+                if (os.path.abspath(path) + os.sep).startswith(srcdir + os.sep) and int(line) > 0:
                     cur = (os.path.basename(path), int(line))
                     break
             continue

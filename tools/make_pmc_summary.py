@@ -71,7 +71,7 @@ new = {
     # the code scan (round 4, ADSB_SCAN=code in the -DADSB_AB_KERNELS=1 build: the gate on an 8-bit log code of I^2+Q^2, no root per sample)
     "i8_code_scan": ({"demod_tiles": {"derived": derived(code["demod_tiles"], 1 << 29, 2), "raw": code["demod_tiles"]}} if code else None),
     # the sieve scan (round 4, ADSB_SCAN=sieve in the A/B build: two relation bits per sample, the gate's adjacent taps on 64-bit words,
-    # candidates decided exactly from a raw image in LDS -- four workgroups per CU; adsb_sieve.inc)
+    # candidates decided exactly from a raw image in LDS -- four workgroups per CU; ab/sieve.inc)
     "i8_sieve_scan": ({"demod_tiles": {"derived": derived(sieve["demod_tiles"], 1 << 29, 2), "raw": sieve["demod_tiles"]}} if sieve else None),
     "before_the_split": before,
     # the scan kernel's PMC rows as it was trimmed after the split (each measured by the same passes, one MI355X box each)
