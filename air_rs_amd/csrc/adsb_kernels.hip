@@ -475,7 +475,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const DemodArgs &p, 
 #endif
 bool ab_kernels_built() { return ADSB_AB_KERNELS != 0; }
 
-// survivor bitmap words -> the lane's survivors appended (unordered) to the LDS list; shared by both gates
+// survivor bitmap words -> the lane's survivors appended (unordered) to the LDS list, behind a gate's steps: the nsq scan's
+// (ab/nsq.inc); gate_phase appends where it finds them
 template <int RUN, int NT>
 __device__ __forceinline__ void gate_collect(uint32_t *candA, uint32_t *candB, uint16_t *list, uint32_t *count,
                                              const uint32_t tid, const uint32_t n_valid)
@@ -524,11 +525,41 @@ __device__ __forceinline__ void gate_collect(uint32_t *candA, uint32_t *candB, u
     }
 }
 
+// One survivor, appended (unordered) to the LDS list by the lane that found it; *count is the tile's survivor number
+// whether or not the list holds them all (more than kSparseCap: phase 3 draws them from the bitmap).
+__device__ __forceinline__ void gate_append(uint16_t *list, uint32_t *count, const uint32_t off, const uint32_t n_valid)
+{
+    if (off < n_valid) { // (offsets at or beyond n_valid do not exist in the reference loop, adsb.rs:98)
+        // (the returning LDS add by hand: hipcc's atomicAdd gathers the wave's lanes into one add first, with three more
+        // registers than the unrolled steps around this block leave free; a handful of lanes add one each instead)
+        uint32_t pos = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)count;
+        const uint32_t one = 1u;
+        asm volatile("ds_add_rtn_u32 %0, %0, %1\n\ts_waitcnt lgkmcnt(0)" : "+v"(pos) : "v"(one) : "memory");
+        if (pos < (uint32_t)kSparseCap) list[pos] = (uint16_t)off;
+    }
+}
+
+// The ragged last tile of a channel: bits of offsets at or beyond n_valid leave the lane's bitmap words.
+template <int RUN, int NT>
+__device__ __forceinline__ void gate_mask_tail(uint32_t *candA, uint32_t *candB, const uint32_t tid, const uint32_t n_valid)
+{
+    constexpr int WPR = (RUN + 31) / 32;
+    const uint32_t sa = tid * RUN, sb = (tid + NT) * RUN;
+    const uint32_t va = n_valid > sa ? (n_valid - sa) : 0u, vb = n_valid > sb ? (n_valid - sb) : 0u;
+#pragma unroll
+    for (int k = 0; k < WPR; ++k) {
+        const uint32_t la = va > 32u * k ? va - 32u * k : 0u, lb = vb > 32u * k ? vb - 32u * k : 0u;
+        candA[k] &= la >= 32u ? 0xFFFFFFFFu : ((1u << la) - 1u);
+        candB[k] &= lb >= 32u ? 0xFFFFFFFFu : ((1u << lb) - 1u);
+    }
+}
+
 // ---- the gate (phase 2 of the tile kernels) --------------------------------------------------
 // Preamble + DF17 ordering test (demod.rs:17-57) for the 2 x kRun offsets this lane owns:
 // run A = offsets [tid*RUN, +RUN), run B = [(tid+NT)*RUN, +RUN) of the tile whose magnitudes
-// are in `mag`.  Survivors are OR-ed into the lane's words of the LDS bitmap `cand` and appended,
-// unordered, to `list` (their number is added to *count).  No barriers inside; `tid` < NT; 2 NT RUN = kTile.
+// are in `mag`.  Survivors are OR-ed into the lane's words of the LDS bitmap `cand` and appended, where they are found,
+// unordered, to `list` (their number is added to *count).  `list` and `count` must be LDS: gate_append adds with a DS
+// instruction.  No barriers inside; `tid` < NT; 2 NT RUN = kTile.
 // [phase:2 gate: set-up]
 template <int ST, int RUN, int NT, bool F16OK = (ST == ADSB_SAMPLE_I8)>
 __device__ __forceinline__ void gate_phase(const typename MagT<ST>::type *mag, uint32_t *cand, uint16_t *list,
@@ -542,7 +573,6 @@ __device__ __forceinline__ void gate_phase(const typename MagT<ST>::type *mag, u
     uint32_t *candA = cand + WPR * tid, *candB = cand + WPR * (tid + NT);
 #pragma unroll
     for (int k = 0; k < WPR; ++k) candA[k] = candB[k] = 0u;
-    // (offsets at or beyond n_valid do not exist in the reference loop, adsb.rs:98: masked out in gate_collect)
     constexpr int kGran = (RUN + 26 + SPG - 1) / SPG + 1; // granules a run may touch
     const u32x4 *ga = reinterpret_cast<const u32x4 *>(mag + tid * RUN);
     const u32x4 *gb = reinterpret_cast<const u32x4 *>(mag + (tid + NT) * RUN);
@@ -593,6 +623,8 @@ __device__ __forceinline__ void gate_phase(const typename MagT<ST>::type *mag, u
         const uint32_t hi = pkmin(H2[o], H2[o + 7]);                      // highs 0,2,7,9
         const bool pa = (uint16_t)hi >= (uint16_t)lo;
         const bool pb = (hi >> 16) >= (lo >> 16);
+        // (the compares' own scalar masks, for the cold block: taken here, next to the compares, they are no instruction)
+        const unsigned long long mpa = __builtin_amdgcn_ballot_w64(pa), mpb = __builtin_amdgcn_ballot_w64(pb);
         // [phase:2 gate: DF17 (cold)]
         // wave-uniform test (a scalar branch, no exec juggling; the wave-wide OR is one ballot, an s_or of the compare
         // masks): the block below is entered by the whole wave when any lane passes; its effects are masked by pa/pb anyway
@@ -600,18 +632,32 @@ __device__ __forceinline__ void gate_phase(const typename MagT<ST>::type *mag, u
             // DF17 part of the gate (demod.rs:45-54)
             const uint32_t dh = pkmin3<F16OK>(pkmin3<F16OK>(N[o + 16], N[o + 19], N[o + 21]), N[o + 23], N[o + 24]);
             const uint32_t dl = pkmax3<F16OK>(pkmax3<F16OK>(N[o + 17], N[o + 18], N[o + 20]), N[o + 22], N[o + 25]);
-            const bool da = (uint16_t)dh >= (uint16_t)dl;
-            const bool db = (dh >> 16) >= (dl >> 16);
-            // (offsets at or beyond n_valid are masked out of the bitmap words after the loop, in the one
-            // tile per channel that has any, instead of two compares here)
-            uint32_t bit = 1u << (o & 31);
-            asm("" : "+v"(bit)); // one v_mov for both stores (hipcc rematerialises the constant per exec region)
-            if (pa & da) atomicOr(candA + (o >> 5), bit);
-            if (pb & db) atomicOr(candB + (o >> 5), bit);
+            // (the verdicts as scalar masks, ANDed on the scalar side -- a ballot of a combined predicate costs hipcc a
+            // v_cndmask and a v_cmp; dh and dl are dead from here, their registers serve the append)
+            const unsigned long long sva = mpa & __builtin_amdgcn_ballot_w64((uint16_t)dh >= (uint16_t)dl);
+            const unsigned long long svb = mpb & __builtin_amdgcn_ballot_w64((dh >> 16) >= (dl >> 16));
+            if (__builtin_expect((sva | svb) != 0, 0)) { // a survivor: about eight times per tile, in one wave
+                // (the masks back as lane predicates: an exec mask each, no vector instruction)
+                const bool va = __builtin_amdgcn_inverse_ballot_w64(sva), vb = __builtin_amdgcn_inverse_ballot_w64(svb);
+                // (offsets at or beyond n_valid are masked out of the bitmap words after the loop, in the one
+                // tile per channel that has any; the append tests them itself, one compare executed only here)
+                uint32_t bit = 1u << (o & 31);
+                asm("" : "+v"(bit)); // one v_mov for both stores (hipcc rematerialises the constant per exec region)
+                if (va) atomicOr(candA + (o >> 5), bit);
+                if (vb) atomicOr(candB + (o >> 5), bit);
+                // (the lane's number taken afresh here: as a product hoisted out of the steps it would hold a
+                // register through all of them)
+                uint32_t t = tid;
+                asm("" : "+v"(t));
+                if (va) gate_append(list, count, t * RUN + o, n_valid);
+                if (vb) gate_append(list, count, (t + NT) * RUN + o, n_valid);
+            }
         }
     }
     // [phase:2 gate: survivor list]
-    gate_collect<RUN, NT>(candA, candB, list, count, tid, n_valid);
+    // The list is complete: every survivor was appended where it was found.  Only the ragged last tile of a channel has
+    // anything left to do -- the dense path of phase 3 reads the bitmap itself, so bits at or beyond n_valid leave it.
+    if (n_valid < (uint32_t)(2 * NT * RUN)) gate_mask_tail<RUN, NT>(candA, candB, tid, n_valid); // (wave-uniform)
 }
 
 // [phase:end]
@@ -728,7 +774,8 @@ __device__ __forceinline__ void write_seg(const DemodArgs &p, const uint32_t til
 //   recheck(list, n), called by the whole workgroup for every chunk of n list entries drawn from the bitmap, before they
 //     are sliced (the sieve scan runs its exact gate there and marks entries; it brings its own barrier).
 // lane, wave = tid & 63, tid >> 6, which every caller holds already (derived again in here, the CS16 kernel's instructions
-// come out in another order).  Writes the tile's Seg.  Uses misc[0 .. 3], misc[8] (valid frames of a tile without slots), misc[9].
+// come out in another order).  Writes the tile's Seg: ahead of the slicing when the survivors fit the tile's own slots (nothing in
+// this launch reads it; finish_order is a later one), after it otherwise.  Uses misc[0 .. 3], misc[8] (valid frames of a tile without slots), misc[9].
 constexpr uint32_t kCountBitmap = 0xFFFFFFFFu;
 struct NoRecheck {
     __device__ __forceinline__ void operator()(uint16_t *, uint32_t) const {}
@@ -736,8 +783,37 @@ struct NoRecheck {
 template <int TILE, int BITS, class SLICER, class RECHECK = NoRecheck>
 __device__ __forceinline__ void hand_over(const DemodArgs &p, const uint32_t tile, const uint64_t sample0, uint32_t total,
                                           const uint32_t *cand, uint16_t *list, uint32_t *misc, const uint32_t tid,
-                                          const uint32_t lane, const uint32_t wave, SLICER slicer, RECHECK recheck = RECHECK())
+                                          const uint32_t lane, uint32_t wave, SLICER slicer, RECHECK recheck = RECHECK())
 {
+    // `total` comes out of LDS and `wave` out of tid: both are wave-uniform, which hipcc cannot know.  As scalars, every
+    // test on them below is a scalar branch, and a wave without a survivor to slice -- in the normal tile, waves 2 and 3
+    // -- leaves on the first of them with no set-up behind it.
+    total = __builtin_amdgcn_readfirstlane(total);
+    wave = __builtin_amdgcn_readfirstlane(wave);
+    const uint64_t abs0 = sample0 + p.offset_base; // absolute offset of this tile's offset 0
+    // 16-lane groups slice one survivor each, one lane per frame byte, and store offset + 14 raw bytes
+    // into the survivor's slot: 16 survivors per workgroup round
+    const uint32_t g = tid >> 4, l = tid & 15;
+    auto slice_round = [&](uint32_t slot0, uint32_t ncl) {
+        for (uint32_t r = 0; r + 4 * wave < ncl; r += kThreads / 16) { // (later waves: none of their four groups has a survivor)
+            const uint32_t ci = r + g;
+            const bool have = ci < ncl; // uniform within the 16-lane group
+            const uint32_t off = have ? list[ci] : 0u;
+            bool dropped;
+            const uint32_t byte = slicer(have, off, l, dropped);
+            if (have) put_record(p.slots + (size_t)slot0 + ci, dropped ? ~0ull : abs0 + off, byte, l);
+        }
+    };
+
+    // Frame slots: the tile's own fixed region when the survivors fit (no atomics), otherwise one allocation from the
+    // shared pool.  In the usual case (a handful of survivors) every thread knows the base without asking tid 0, and the
+    // list is complete since the barrier that ended the gate: no further barrier.
+    if (total <= kQuota) {
+        if (tid == 0) write_seg(p, tile, tile * kQuota, total, misc[8]);
+        slice_round(tile * kQuota, total); // unordered list (finish_order ranks it): survivor j -> slot j
+        return;
+    }
+
     const bool dense = total > (uint32_t)kSparseCap;
     u32x4 cw = {0, 0, 0, 0};
     uint32_t cnt = 0, my_first = 0;
@@ -764,75 +840,52 @@ __device__ __forceinline__ void hand_over(const DemodArgs &p, const uint32_t til
             total += t;
         }
         my_first = wbase + incl - cnt; // index of this thread's first candidate
+        total = __builtin_amdgcn_readfirstlane(total);
     }
 
-    // Frame slots: the tile's own fixed region when the survivors fit (no atomics), otherwise
-    // one allocation from the shared pool.  In the usual case (a handful of survivors) every thread knows
-    // the base without asking tid 0, and the list is complete since the barrier above: no further barrier.
-    const bool simple = !dense && total <= kQuota;
-    const uint64_t abs0 = sample0 + p.offset_base; // absolute offset of this tile's offset 0
-    uint32_t base_slot = tile * kQuota;
-    // 16-lane groups slice one survivor each, one lane per frame byte, and store offset + 14 raw bytes
-    // into the survivor's slot: 16 survivors per workgroup round
-    const uint32_t g = tid >> 4, l = tid & 15;
-    auto slice_round = [&](uint32_t slot0, uint32_t ncl) {
-        for (uint32_t r = 0; r < ncl; r += kThreads / 16) {
-            if (r + 4 * wave >= ncl) break; // none of this wave's four groups has a survivor
-            const uint32_t ci = r + g;
-            const bool have = ci < ncl; // uniform within the 16-lane group
-            const uint32_t off = have ? list[ci] : 0u;
-            bool dropped;
-            const uint32_t byte = slicer(have, off, l, dropped);
-            if (have) put_record(p.slots + (size_t)slot0 + ci, dropped ? ~0ull : abs0 + off, byte, l);
-        }
-    };
-    if (simple) {
-        slice_round(base_slot, total); // unordered list (finish_order ranks it): survivor j -> slot j
-    } else {
-        if (tid == 0) {
-            const unsigned long long b64 = atomicAdd(&p.hdr->alloc, (unsigned long long)total);
-            // (pool_off: test knob, adsb_debug_pool_limit -- every tile over its quota loses its slots)
-            misc[9] = (!p.pool_off && b64 + total <= (unsigned long long)p.cap_slots) ? p.pool_first + (uint32_t)b64 : kNoBase;
+    // more than the tile's quota, or drawn from the bitmap: one allocation from the shared pool
+    if (tid == 0) {
+        const unsigned long long b64 = atomicAdd(&p.hdr->alloc, (unsigned long long)total);
+        // (pool_off: test knob, adsb_debug_pool_limit -- every tile over its quota loses its slots)
+        misc[9] = (!p.pool_off && b64 + total <= (unsigned long long)p.cap_slots) ? p.pool_first + (uint32_t)b64 : kNoBase;
+    }
+    __syncthreads();
+    const uint32_t base_slot = misc[9];
+    for (uint32_t chunk = 0; chunk < total; chunk += kListCap) {
+        if (dense && cnt) {
+            uint32_t idx = my_first;
+            const uint32_t words[4] = {cw.x, cw.y, cw.z, cw.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                uint32_t bits = words[k];
+                while (bits) {
+                    const uint32_t b = __builtin_ctz(bits);
+                    bits &= bits - 1;
+                    if (idx >= chunk && idx < chunk + kListCap)
+                        list[idx - chunk] = (uint16_t)((4 * tid + k) * BITS + b);
+                    ++idx;
+                }
+            }
         }
         __syncthreads();
-        base_slot = misc[9];
-        for (uint32_t chunk = 0; chunk < total; chunk += kListCap) {
-            if (dense && cnt) {
-                uint32_t idx = my_first;
-                const uint32_t words[4] = {cw.x, cw.y, cw.z, cw.w};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    uint32_t bits = words[k];
-                    while (bits) {
-                        const uint32_t b = __builtin_ctz(bits);
-                        bits &= bits - 1;
-                        if (idx >= chunk && idx < chunk + kListCap)
-                            list[idx - chunk] = (uint16_t)((4 * tid + k) * BITS + b);
-                        ++idx;
-                    }
-                }
+        const uint32_t ncl = (total - chunk) < (uint32_t)kListCap ? (total - chunk) : (uint32_t)kListCap;
+        if (dense) recheck(list, ncl);
+        if (base_slot != kNoBase) {
+            slice_round(base_slot + chunk, ncl); // (ordered when dense; 33..64 survivors: unordered like the simple case)
+        } else {
+            // The slot store is full (pathological input: SURVEY F8).  The host re-plans from exact counts,
+            // so this tile's survivors are decoded HERE, from the image in LDS, only to be counted.
+            for (uint32_t r = 0; r + 4 * wave < ncl; r += kThreads / 16) { // (later waves: none of their four groups has a candidate)
+                const uint32_t ci = r + g;
+                const bool have = ci < ncl; // uniform within the 16-lane group
+                const uint32_t off = have ? list[ci] : 0u;
+                bool dropped;
+                const uint32_t byte = slicer(have, off, l, dropped);
+                const bool valid = count_candidate(have && !dropped, byte, l, lane);
+                if (valid && l == 0) atomicAdd(&misc[8], 1u);
             }
-            __syncthreads();
-            const uint32_t ncl = (total - chunk) < (uint32_t)kListCap ? (total - chunk) : (uint32_t)kListCap;
-            if (dense) recheck(list, ncl);
-            if (base_slot != kNoBase) {
-                slice_round(base_slot + chunk, ncl); // (ordered when dense; 33..64 survivors: unordered like the simple case)
-            } else {
-                // The slot store is full (pathological input: SURVEY F8).  The host re-plans from exact counts,
-                // so this tile's survivors are decoded HERE, from the image in LDS, only to be counted.
-                for (uint32_t r = 0; r < ncl; r += kThreads / 16) {
-                    if (r + 4 * wave >= ncl) break; // none of this wave's four groups has a candidate
-                    const uint32_t ci = r + g;
-                    const bool have = ci < ncl; // uniform within the 16-lane group
-                    const uint32_t off = have ? list[ci] : 0u;
-                    bool dropped;
-                    const uint32_t byte = slicer(have, off, l, dropped);
-                    const bool valid = count_candidate(have && !dropped, byte, l, lane);
-                    if (valid && l == 0) atomicAdd(&misc[8], 1u);
-                }
-            }
-            __syncthreads();
         }
+        __syncthreads();
     }
     if (tid == 0) write_seg(p, tile, base_slot, total, misc[8]);
 }

@@ -73,6 +73,8 @@ new = {
     # the sieve scan (round 4, ADSB_SCAN=sieve in the A/B build: two relation bits per sample, the gate's adjacent taps on 64-bit words,
     # candidates decided exactly from a raw image in LDS -- four workgroups per CU; ab/sieve.inc)
     "i8_sieve_scan": ({"demod_tiles": {"derived": derived(sieve["demod_tiles"], 1 << 29, 2), "raw": sieve["demod_tiles"]}} if sieve else None),
+    # the VALU-only counter pass of the survivor-work change (parent and new in one session), carried over as recorded
+    "i8_survivor_work_valu_pass": old.get("i8_survivor_work_valu_pass"),
     "before_the_split": before,
     # the scan kernel's PMC rows as it was trimmed after the split (each measured by the same passes, one MI355X box each)
     "demod_tiles_i8_history": [
@@ -84,8 +86,10 @@ new = {
         {"what": "round 3: 16384-offset tiles (runs of 32; per wave per tile, i.e. per HALF as many samples as the rows above), 19 KB of LDS, "
                  "8 workgroups per CU", "valu_instructions_per_wave": 740.7, "valu_slots_per_wave": 809.8},
         {"what": "phase 1: one mask per dword, the odd sample's I^2+Q^2 as the difference of two dots inside a packed FMA "
-                 "(profiles/pair_dot_checks.txt)", "valu_instructions_per_wave": round(i8["demod_tiles"]["SQ_INSTS_VALU"] / i8["demod_tiles"]["SQ_WAVES"], 1),
-         "valu_slots_per_wave": round(i8["demod_tiles"]["SQ_ACTIVE_INST_VALU"] / i8["demod_tiles"]["SQ_WAVES"], 1)},
+                 "(profiles/pair_dot_checks.txt)", "valu_instructions_per_wave": 707.7, "valu_slots_per_wave": 776.8},
+        # (a VALU-only pass of its own, not this tool's input: the figures are those of profiles/survivor_work_checks.txt)
+        {"what": "survivors appended to the list inside the cold block (no gate_collect); hand_over on a scalar survivor count and wave number "
+                 "(profiles/survivor_work_checks.txt)", "valu_instructions_per_wave": 675.4, "valu_slots_per_wave": 742.4},
     ],
     "demod_tiles_cs16_history": old.get("demod_tiles_cs16_history") or [
         {"what": "whole decode inside demod_tiles", "valu_instructions_per_wave": 1155, "valu_slots_per_wave": 1223},
