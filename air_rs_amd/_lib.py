@@ -86,6 +86,25 @@ class AdsbWireCfg(C.Structure):
     _fields_ = [("format", C.c_uint32), ("signal", C.c_uint32), ("tick_bias", C.c_uint64)]
 
 
+class AdsbCorrelateCfg(C.Structure):
+    """adsb_correlate_cfg: the window in samples, and whether adsb_correlate_launch takes the launch's levels."""
+    _fields_ = [("window", C.c_uint32), ("use_levels", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class AdsbMessage(C.Structure):
+    """adsb_message: one transmission, however many receivers heard it (64 bytes)."""
+    _fields_ = [("time", C.c_uint64), ("bytes", C.c_uint8 * 14), ("status", C.c_uint8), ("fixed_bit", C.c_uint8),
+                ("first", C.c_uint32), ("n_receptions", C.c_uint32), ("n_receivers", C.c_uint16),
+                ("first_receiver", C.c_uint16), ("best_receiver", C.c_uint16), ("reserved", C.c_uint16),
+                ("n_clean", C.c_uint32), ("reserved2", C.c_uint32), ("span", C.c_uint64),
+                ("best_signal_sum", C.c_uint64)]
+
+
+class AdsbReception(C.Structure):
+    """adsb_reception: one receiver's hearing of a message (16 bytes)."""
+    _fields_ = [("time", C.c_uint64), ("frame", C.c_uint32), ("receiver", C.c_uint16), ("reserved", C.c_uint16)]
+
+
 class AdsbTrackPoint(C.Structure):
     _fields_ = [("latitude", C.c_double), ("longitude", C.c_double), ("icao", C.c_uint32), ("flags", C.c_uint32)]
 
@@ -237,6 +256,13 @@ PROTOTYPES = {
     "adsb_wire_of": (C.c_int, [C.c_void_p, _P(AdsbWireCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                _P(C.c_size_t), C.c_void_p]),
     "adsb_debug_wire_geometry": (C.c_int, [_P(C.c_uint32), _P(C.c_uint32)]),
+    "adsb_correlate_launch": (C.c_int, [C.c_void_p, _P(AdsbCorrelateCfg), C.c_void_p]),
+    "adsb_correlate_of": (C.c_int, [C.c_void_p, _P(AdsbCorrelateCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                    C.c_uint32, C.c_void_p]),
+    "adsb_fetch_correlated": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t,
+                                        _P(C.c_size_t)]),
+    "adsb_correlated_device": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p)]),
+    "adsb_debug_correlate_geometry": (C.c_int, [_P(C.c_uint32)]),
     "adsb_track_device": (C.c_int, [C.c_void_p, C.c_double]),
     "adsb_fetch_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t,
                                    _P(C.c_size_t)]),
@@ -371,6 +397,8 @@ PROTOTYPES = {
     "adsb_level_dbfs": (C.c_double, [C.c_int, C.c_uint64, C.c_uint32]),
     "adsb_host_wire_encode": (C.c_int, [_P(AdsbWireCfg), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.c_size_t, _P(C.c_size_t), C.c_void_p]),
+    "adsb_host_correlate": (C.c_int, [_P(AdsbCorrelateCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
+                                      C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p]),
     "adsb_host_fix_of": (C.c_int, [_P(AdsbSite), _P(C.c_uint8 * 14), C.c_double, _P(AdsbFix), _P(C.c_uint32)]),
 }
 

@@ -77,6 +77,7 @@ extern "C" void adsb_destroy(adsb_ctx *c)
     (void)hipFree(c->wof_frames);
     (void)hipFree(c->wof_levels);
     (void)hipFree(c->trk_u32);
+    (void)hipFree(c->corr.block);
     (void)hipFree(c->trk_temp);
     (void)hipFree(c->trk_points);
     (void)hipFree(c->trk_aircraft);

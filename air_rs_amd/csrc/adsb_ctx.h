@@ -62,6 +62,17 @@ struct adsb_ctx {
     size_t wof_frames_n = 0, wof_levels_n = 0;
     adsb_wire_cfg wire_cfg{};       // of the last adsb_wire_device_async
     bool wire_current = false;      // wire.out belongs to the last launch
+    // correlate (adsb_correlate.hip), allocated on first adsb_correlate_launch / adsb_correlate_of and grown on demand:
+    // one hipMalloc carved into the kernels' arrays, the receivers' prefix and bases, and device copies of host lists
+    struct Corr {
+        void *block = nullptr;      // everything in `a` below points into it
+        size_t frames = 0;          // what it holds
+        adsbk::CorrArgs a{};        // scratch and result pointers (frames, levels, n, ... are set per call)
+        uint64_t *prefix = nullptr, *base = nullptr; // [257], [256]
+        adsb_frame *in_frames = nullptr;             // [frames]
+        adsb_frame_level *in_levels = nullptr;       // [frames]
+        bool done = false;          // a correlate call has been enqueued
+    } corr;
     // tracker (allocated on first adsb_track_device)
     uint32_t *trk_u32 = nullptr;    // 4 x [max_out]: keys, vals, sorted keys, sorted vals
     void *trk_temp = nullptr;

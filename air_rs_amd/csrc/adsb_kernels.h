@@ -201,6 +201,31 @@ struct WireArgs {
 };
 hipError_t launch_wire(hipStream_t s, const WireArgs &a);
 
+// receptions of one transmission across receivers (adsb_correlate.hip): the dispatch sequence is described there
+constexpr uint32_t kCorrBlock = 256; // receptions (= threads) per workgroup of the key and write kernels
+struct CorrAgg;                      // adsb_correlate.h
+struct CorrArgs {
+    const adsb_frame *frames;        // [n], adsb_fetch's layout
+    const adsb_frame_level *levels;  // [n] or null
+    uint32_t n, n_receivers, window;
+    const uint64_t *prefix;          // [n_receivers + 1]: list index of each receiver's first frame; last = n
+    const uint64_t *base;            // [n_receivers] or null: all 0
+    // scratch, [n] each
+    uint64_t *t, *lo, *hi, *head_t;  // per list index: T and the key words; per sorted position: the head's T, sorted
+    uint32_t *rx, *ord, *pos, *midx; // receiver per list index; list index per group-order position; group-order
+                                     // position per output position; heads up to and including an output position
+    CorrAgg *scan;                   // per group-order position: the aggregate of its group up to it
+    void *temp;
+    size_t temp_bytes;               // >= corr_temp_bytes(n)
+    // results
+    adsb_message *msgs;              // [n]
+    adsb_frame *frames_out;          // [n]
+    adsb_reception *recs;            // [n]
+    uint64_t *hdr;                   // {n_messages, n_receptions}
+};
+size_t corr_temp_bytes(size_t n);
+hipError_t launch_correlate(hipStream_t s, const CorrArgs &a);
+
 // tracker + CPR position decode over an ordered frame list (adsb_track.hip)
 // One aircraft of a persistent table (adsb_track_table_*): the public record plus the last even and the last odd
 // position message (aircraft.rs:28-31) that a later update's first position message of the other format pairs with.

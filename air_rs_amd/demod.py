@@ -145,6 +145,57 @@ def _wire_result(out, room, ends, total):
     return out[:total].tobytes(), ends
 
 
+MESSAGE_DTYPE = np.dtype([("time", "<u8"), ("bytes", "u1", (14,)), ("status", "u1"), ("fixed_bit", "u1"), ("first", "<u4"),
+                          ("n_receptions", "<u4"), ("n_receivers", "<u2"), ("first_receiver", "<u2"),
+                          ("best_receiver", "<u2"), ("reserved", "<u2"), ("n_clean", "<u4"), ("reserved2", "<u4"),
+                          ("span", "<u8"), ("best_signal_sum", "<u8")])
+assert MESSAGE_DTYPE.itemsize == C.sizeof(L.AdsbMessage) == 64
+RECEPTION_DTYPE = np.dtype([("time", "<u8"), ("frame", "<u4"), ("receiver", "<u2"), ("reserved", "<u2")])
+assert RECEPTION_DTYPE.itemsize == C.sizeof(L.AdsbReception) == 16
+
+
+def _u64_list(values, n, what):
+    """(array kept alive, pointer or None) of n uint64 values (None: a NULL pointer)."""
+    if values is None:
+        return None, None
+    arr = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1)
+    if len(arr) != n:
+        raise ValueError(f"{what}: {len(arr)} values for {n} receivers")
+    return arr, arr.ctypes.data
+
+
+def frames_of_messages(messages):
+    """Bytes 0..23 of every MESSAGE_DTYPE record as a FRAME_DTYPE list (offset = time): what the device also writes
+    contiguously as frames_out."""
+    messages = np.ascontiguousarray(messages, dtype=MESSAGE_DTYPE)
+    out = np.zeros(len(messages), dtype=FRAME_DTYPE)
+    out["offset"], out["bytes"] = messages["time"], messages["bytes"]
+    out["status"], out["fixed_bit"] = messages["status"], messages["fixed_bit"]
+    return out
+
+
+def host_correlate(frames, counts, window, sample_base=None, levels=None):
+    """adsb_host_correlate, the CPU mirror of AdsbDemod.correlate_of: (messages, frames, receptions) as MESSAGE_DTYPE,
+    FRAME_DTYPE and RECEPTION_DTYPE arrays of the multi-receiver FRAME_DTYPE list `frames` (receiver 0's frames, then
+    receiver 1's, ...; counts[r] frames each), with sample_base[r] added to receiver r's offsets and the frames'
+    LEVEL_DTYPE records `levels` (None: no best receiver).  window: samples.  Needs no device."""
+    frames, fptr, n = _host_list(frames, FRAME_DTYPE)
+    lptr = None
+    if levels is not None:
+        levels, lptr, _ = _host_list(levels, LEVEL_DTYPE, n)
+    counts = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    base, bptr = _u64_list(sample_base, len(counts), "sample_base")
+    cfg = L.AdsbCorrelateCfg(int(window), 0, 0)
+    msgs = np.zeros(max(n, 1), dtype=MESSAGE_DTYPE)
+    fout = np.zeros(max(n, 1), dtype=FRAME_DTYPE)
+    recs = np.zeros(max(n, 1), dtype=RECEPTION_DTYPE)
+    n_msgs = C.c_size_t()
+    L.check(L.load().adsb_host_correlate(C.byref(cfg), fptr, lptr, n, counts.ctypes.data if len(counts) else None,
+                                         len(counts), bptr, msgs.ctypes.data, n, C.byref(n_msgs), fout.ctypes.data,
+                                         recs.ctypes.data), "adsb_host_correlate")
+    return msgs[:n_msgs.value].copy(), fout[:n_msgs.value].copy(), recs[:n].copy()
+
+
 def level_dbfs(sample_type, total, n_samples):
     """adsb_level_dbfs: 10 log10(total / n_samples / full scale) -- a LEVEL_DTYPE sum as mean power in dBFS (-inf for
     0).  level_dbfs(st, rec["signal_sum"], LEVEL_PULSE_SAMPLES), level_dbfs(st, rec["noise_sum"], LEVEL_QUIET_SAMPLES)."""
@@ -496,6 +547,66 @@ class AdsbDemod:
         L.check(self._lib.adsb_wire_of(self._h, C.byref(cfg), fptr, lptr, n, out.ctypes.data, room, C.byref(total),
                                        ends.ctypes.data), "adsb_wire_of")
         return _wire_result(out, room, ends[:n].copy(), total.value)
+
+    def correlate_async(self, window, sample_base=None, levels=False):
+        """adsb_correlate_launch alone: the last launch's list, channel k as receiver k, correlated on the device.
+        window: samples; sample_base: one uint64 per channel (None: zeros); levels: take the launch's levels (enqueued
+        here if they have not been) for best_receiver / best_signal_sum."""
+        base, bptr = _u64_list(sample_base, self._last_channels, "sample_base")
+        cfg = L.AdsbCorrelateCfg(int(window), 1 if levels else 0, 0)
+        L.check(self._lib.adsb_correlate_launch(self._h, C.byref(cfg), bptr), "adsb_correlate_launch")
+
+    def correlate(self, window, sample_base=None, levels=False):
+        """The last launch's frames as one de-duplicated, time-ordered message list: (messages, frames, receptions) as
+        MESSAGE_DTYPE, FRAME_DTYPE and RECEPTION_DTYPE arrays.  See correlate_async."""
+        self.correlate_async(window, sample_base, levels)
+        return self.fetch_correlated()
+
+    def correlate_of(self, frames, counts, window, sample_base=None, levels=None):
+        """adsb_correlate_of: any multi-receiver list -> (messages, frames, receptions).  frames: a FRAME_DTYPE array
+        (host) or (device pointer, count), receiver 0's frames first, counts[r] each; levels: None, a LEVEL_DTYPE array
+        (host) or a device pointer; sample_base: one uint64 per receiver (None: zeros); window: samples."""
+        self.correlate_of_async(frames, counts, window, sample_base, levels)
+        return self.fetch_correlated()
+
+    def correlate_of_async(self, frames, counts, window, sample_base=None, levels=None):
+        """adsb_correlate_of alone: enqueues and returns once the host arrays are copied."""
+        if isinstance(frames, tuple):
+            fptr, n = int(frames[0]), int(frames[1])
+        else:
+            frames, fptr, n = _host_list(frames, FRAME_DTYPE)
+        lptr = None
+        if isinstance(levels, int):
+            lptr = levels
+        elif levels is not None:
+            levels, lptr, _ = _host_list(levels, LEVEL_DTYPE, n)
+        counts = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+        base, bptr = _u64_list(sample_base, len(counts), "sample_base")
+        cfg = L.AdsbCorrelateCfg(int(window), 0, 0)
+        L.check(self._lib.adsb_correlate_of(self._h, C.byref(cfg), fptr, lptr, n,
+                                            counts.ctypes.data if len(counts) else None, len(counts), bptr),
+                "adsb_correlate_of")
+
+    def fetch_correlated(self):
+        """adsb_fetch_correlated: waits for the last correlate call -> (messages, frames, receptions); frames are the
+        messages' first 24 bytes, the list correlated_device() has on the device."""
+        n_msgs, n_recs = C.c_size_t(), C.c_size_t()
+        L.check(self._lib.adsb_fetch_correlated(self._h, None, 0, C.byref(n_msgs), None, 0, C.byref(n_recs)),
+                "adsb_fetch_correlated")
+        msgs = np.zeros(max(n_msgs.value, 1), dtype=MESSAGE_DTYPE)
+        recs = np.zeros(max(n_recs.value, 1), dtype=RECEPTION_DTYPE)
+        L.check(self._lib.adsb_fetch_correlated(self._h, msgs.ctypes.data, n_msgs.value, C.byref(n_msgs), recs.ctypes.data,
+                                                n_recs.value, C.byref(n_recs)), "adsb_fetch_correlated")
+        msgs = msgs[:n_msgs.value].copy()
+        return msgs, frames_of_messages(msgs), recs[:n_recs.value].copy()
+
+    def correlated_device(self):
+        """adsb_correlated_device: device addresses (messages, frames, receptions, {u64 n_messages, u64 n_receptions});
+        no synchronisation."""
+        m, f, r, h = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        L.check(self._lib.adsb_correlated_device(self._h, C.byref(m), C.byref(f), C.byref(r), C.byref(h)),
+                "adsb_correlated_device")
+        return m.value, f.value, r.value, h.value
 
     def set_result_target(self, dev_ptr, nbytes):
         """Next launches write [32-byte header | frames] straight into caller-owned HBM (None: reset)."""

@@ -334,6 +334,90 @@ int adsb_wire_of(adsb_ctx *ctx, const adsb_wire_cfg *cfg, const adsb_frame *fram
 int adsb_debug_wire_geometry(uint32_t *frames_per_block, uint32_t *scan_threads);
 
 /*
+ * Correlate: a multi-receiver frame list as ONE de-duplicated, time-ordered message list, with every message's
+ * receptions (receiver and sample time) -- what an aggregator forwards once, what one track table pairs across
+ * receivers, and what a multilateration solver takes as input.  Stateless; computed on the device.
+ *   INPUT  frames[n] in adsb_fetch's layout: receiver 0's frames in ascending offset, then receiver 1's, ...;
+ *     counts[R] summing to n, 1 <= R <= 256; sample_base[R] (NULL: all 0); optionally levels[n], the frames'
+ *     adsb_frame_level records; window, in samples.  n < 2^32.  The layout is an input contract, as for
+ *     adsb_track_bank_update: the result for an unordered list is defined by the same rules, not checked.
+ *   RECEPTION j is list index j, heard by receiver r(j).  Its time T_j = sample_base[r] + frames[j].offset (uint64
+ *     arithmetic mod 2^64; the caller keeps it from wrapping); its key K_j = the 14 frame bytes as one big-endian
+ *     112-bit integer, all 112 bits taking part.
+ *   GROUP ORDER  receptions ordered by (K, T, j), ascending, all unsigned.
+ *   HEADS  a reception starts a new group when it is first in group order, or its K differs from its predecessor's, or
+ *     T - T_pred > window.  A chain rule: a group is a maximal run of equal bytes whose consecutive gaps are all
+ *     <= window (window = 0: only equal times group).  Two receptions of ONE receiver that decodes the same bytes at
+ *     two nearby offsets are both in the group, which is why n_receivers and n_receptions are separate fields.
+ *   MESSAGE  one per group; its time is the T of the group's first reception.  Messages are listed in ascending
+ *     (time, K), a pair that is unique per group (two groups with equal K and equal time would have chained).
+ *     Bytes 0..23 of an adsb_message are an adsb_frame with offset = time; the same 24 bytes are also written
+ *     contiguously as adsb_frame frames_out[n_messages]: ascending offset, ties in ascending bytes, a valid argument
+ *     for adsb_track_table_update(..., sample_base = 0), adsb_wire_of and adsb_levels_of.
+ *   RECEPTIONS  receptions[n], message by message in message order and in (T, j) order inside a message: message m owns
+ *     receptions[first .. first + n_receptions).
+ * Nothing depends on atomics, hash placement or scheduling: two runs give the same bytes.
+ */
+typedef struct adsb_message {      /* 64 bytes */
+    uint64_t time;            /* earliest reception's T                                               */
+    uint8_t  bytes[14];       /* the key                                                              */
+    uint8_t  status;          /* least status over the receptions                                     */
+    uint8_t  fixed_bit;       /* fixed_bit of the first reception in group order with that status     */
+    uint32_t first;           /* index of its first entry in receptions[]                             */
+    uint32_t n_receptions;
+    uint16_t n_receivers;     /* distinct receivers in the group                                      */
+    uint16_t first_receiver;  /* receiver of the earliest reception (ties: lowest list index)         */
+    uint16_t best_receiver;   /* receiver of the reception with the greatest signal_sum among those whose level
+                                 has ADSB_LEVEL_VALID (ties: earliest in group order); 0xFFFF if none or no levels */
+    uint16_t reserved;        /* 0 */
+    uint32_t n_clean;         /* receptions with status == 0                                          */
+    uint32_t reserved2;       /* 0 */
+    uint64_t span;            /* latest T minus earliest T of the group                               */
+    uint64_t best_signal_sum; /* 0 if best_receiver is 0xFFFF                                         */
+} adsb_message;
+typedef struct adsb_reception {    /* 16 bytes */
+    uint64_t time;            /* T */
+    uint32_t frame;           /* the index j in the input list */
+    uint16_t receiver;
+    uint16_t reserved;        /* 0 */
+} adsb_reception;
+typedef struct adsb_correlate_cfg {
+    uint32_t window;          /* samples */
+    uint32_t use_levels;      /* adsb_correlate_launch: != 0 takes the launch's levels; ignored by adsb_correlate_of */
+    uint64_t reserved;
+} adsb_correlate_cfg;
+/* The ctx's last launch, channel k -> receiver k: the same header sync and slot-pool repair as adsb_fetch_counts (it
+ * waits for the launch), then the correlate sequence enqueued on the ctx's stream.  use_levels != 0 takes the ctx's
+ * levels of that launch, enqueuing adsb_levels_device_async if they are not there (and again for a rebuilt list), as
+ * adsb_track_bank_update_launch_levels does; that call's conditions then hold.  sample_base[n_channels] or NULL.
+ * Buffers are allocated on first use, sized by cfg.max_out: 224 bytes per frame (64 + 24 + 16 of results, 72 of group
+ * aggregate, 48 of times, key words and orders) plus the sorts' temporary storage (about 16 more per frame); a ctx
+ * that never calls it allocates nothing and launches exactly the kernels it launched before.  ADSB_E_ARG for a NULL ctx or cfg or a
+ * launch with more than 256 channels; ADSB_E_STATE before any launch. */
+int adsb_correlate_launch(adsb_ctx *ctx, const adsb_correlate_cfg *cfg, const uint64_t *sample_base);
+/* Any list: frames / levels (NULL allowed) each in host memory or in device memory of the ctx's device; counts and
+ * sample_base (NULL allowed) host memory.  Asynchronous on the ctx's stream once the host arrays are copied.  Grows the
+ * buffers when n exceeds them (may wait for earlier work), and replaces the result of an earlier correlate call.
+ * ADSB_E_ARG for a NULL ctx or cfg, n_receivers outside 1..256, NULL counts, counts not summing to n, or NULL frames
+ * with n > 0; ADSB_E_CAPACITY for n >= 2^32.  n = 0 is ADSB_OK with empty results. */
+int adsb_correlate_of(adsb_ctx *ctx, const adsb_correlate_cfg *cfg, const adsb_frame *frames,
+                      const adsb_frame_level *levels, size_t n, const uint64_t *counts, uint32_t n_receivers,
+                      const uint64_t *sample_base);
+/* Waits.  *n_msgs / *n_recs (each may be NULL) are the totals, whatever the capacities; msgs receives
+ * min(*n_msgs, max_msgs) messages and recs min(*n_recs, max_recs) receptions (NULL allowed with capacity 0).
+ * ADSB_E_STATE before any correlate call. */
+int adsb_fetch_correlated(adsb_ctx *ctx, adsb_message *msgs, size_t max_msgs, size_t *n_msgs, adsb_reception *recs,
+                          size_t max_recs, size_t *n_recs);
+/* For device-side consumers; does not synchronise.  messages[], frames_out[], receptions[] and the header
+ * { uint64 n_messages; uint64 n_receptions } in device memory (each optional), valid until the next correlate call on
+ * this ctx and ordered on the ctx's stream behind it.  ADSB_E_STATE before any correlate call. */
+int adsb_correlated_device(adsb_ctx *ctx, const adsb_message **msgs_dev, const adsb_frame **frames_dev,
+                           const adsb_reception **recs_dev, const void **header_dev);
+/* Threads (= receptions) per workgroup of the correlate kernels: the size at which they take another path, for tests.
+ * The result does not depend on it. */
+int adsb_debug_correlate_geometry(uint32_t *threads_per_block);
+
+/*
  * Tracker + global CPR position decode on the device: what the reference's display
  * threads do with every AdsbPacket, `handle_aircraft_update` (src/adsb/aircraft.rs:158-165 ->
  * Aircraft::handle_packet, aircraft.rs:48-111 -> cpr::calculate_geographic_position, cpr.rs:135-147),

@@ -126,6 +126,19 @@ int adsb_host_wire_encode(const adsb_wire_cfg *cfg, int sample_type, const adsb_
                           size_t *n_bytes, uint32_t *ends);
 
 /*
+ * CPU mirror of adsb_correlate_of (adsb_hip.h, "Correlate"): the same messages, frames and receptions, built from the
+ * same key compare, head rule and aggregate combine as the device's, no device needed.  frames[n] with levels[n] (NULL:
+ * best_receiver 0xFFFF), counts[n_receivers] and sample_base[n_receivers] (NULL: all 0), all host memory.  recs
+ * receives all n receptions; msgs and frames_out (either may be NULL) receive min(*n_msgs, max_msgs) entries, and
+ * *n_msgs = the message count whatever max_msgs.  What a feed's consumer that holds several receivers' popped lists
+ * uses.  ADSB_E_ARG for a NULL cfg, counts or n_msgs, n_receivers outside 1..256, counts not summing to n, NULL frames
+ * or recs with n > 0; ADSB_E_CAPACITY for n >= 2^32.
+ */
+int adsb_host_correlate(const adsb_correlate_cfg *cfg, const adsb_frame *frames, const adsb_frame_level *levels, size_t n,
+                        const uint64_t *counts, uint32_t n_receivers, const uint64_t *sample_base, adsb_message *msgs,
+                        size_t max_msgs, size_t *n_msgs, adsb_frame *frames_out, adsb_reception *recs);
+
+/*
  * CPU mirror of the per-frame fix decode of a table or bank with a fixes reserve (adsb_hip.h, "Positions from single
  * messages"): the same program text as the device's, no device needed.  *out = the adsb_fix of an aircraft whose only
  * frame since admission is this one, heard at frame time `time` by a receiver at *site: accepted: the fix with
