@@ -86,6 +86,27 @@ class AdsbWireCfg(C.Structure):
     _fields_ = [("format", C.c_uint32), ("signal", C.c_uint32), ("tick_bias", C.c_uint64)]
 
 
+ADSB_WIRE_IN_CRC, ADSB_WIRE_IN_DF17 = 0x1, 0x2                 # adsb_wire_in_cfg.filter
+
+
+class AdsbWireInCfg(C.Structure):
+    """adsb_wire_in_cfg: what adsb_wire_in_of / adsb_host_wire_parse read and keep."""
+    _fields_ = [("format", C.c_uint32), ("filter", C.c_uint32), ("tick_bias", C.c_uint64), ("max_frames", C.c_uint64),
+                ("sample_type", C.c_int32), ("levels", C.c_uint32)]
+
+
+class AdsbWireRx(C.Structure):
+    """adsb_wire_rx: how one parsed frame arrived (16 bytes)."""
+    _fields_ = [("ticks", C.c_uint64), ("pos", C.c_uint32), ("signal", C.c_uint8), ("kind", C.c_uint8),
+                ("receiver", C.c_uint16)]
+
+
+class AdsbWireInHeader(C.Structure):
+    """adsb_wire_in_header: the totals of one parse (64 bytes)."""
+    _fields_ = [(k, C.c_uint64) for k in ("n_frames", "total_found", "n_marks", "n_cut", "n_unknown", "n_other",
+                                          "n_rejected", "flags")]
+
+
 class AdsbCorrelateCfg(C.Structure):
     """adsb_correlate_cfg: the window in samples, and whether adsb_correlate_launch takes the launch's levels."""
     _fields_ = [("window", C.c_uint32), ("use_levels", C.c_uint32), ("reserved", C.c_uint64)]
@@ -256,6 +277,11 @@ PROTOTYPES = {
     "adsb_wire_of": (C.c_int, [C.c_void_p, _P(AdsbWireCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                _P(C.c_size_t), C.c_void_p]),
     "adsb_debug_wire_geometry": (C.c_int, [_P(C.c_uint32), _P(C.c_uint32)]),
+    "adsb_wire_in_of": (C.c_int, [C.c_void_p, _P(AdsbWireInCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32]),
+    "adsb_fetch_wire_in": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t),
+                                     C.c_void_p, C.c_void_p, C.c_uint32, _P(AdsbWireInHeader)]),
+    "adsb_wire_in_device": (C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 6),
+    "adsb_debug_wire_in_geometry": (C.c_int, [_P(C.c_uint32), _P(C.c_uint32)]),
     "adsb_correlate_launch": (C.c_int, [C.c_void_p, _P(AdsbCorrelateCfg), C.c_void_p]),
     "adsb_correlate_of": (C.c_int, [C.c_void_p, _P(AdsbCorrelateCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                     C.c_uint32, C.c_void_p]),
@@ -397,6 +423,9 @@ PROTOTYPES = {
     "adsb_level_dbfs": (C.c_double, [C.c_int, C.c_uint64, C.c_uint32]),
     "adsb_host_wire_encode": (C.c_int, [_P(AdsbWireCfg), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.c_size_t, _P(C.c_size_t), C.c_void_p]),
+    "adsb_host_wire_parse": (C.c_int, [_P(AdsbWireInCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p,
+                                       _P(AdsbWireInHeader)]),
     "adsb_host_correlate": (C.c_int, [_P(AdsbCorrelateCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
                                       C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p]),
     "adsb_host_fix_of": (C.c_int, [_P(AdsbSite), _P(C.c_uint8 * 14), C.c_double, _P(AdsbFix), _P(C.c_uint32)]),

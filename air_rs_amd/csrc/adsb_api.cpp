@@ -78,6 +78,8 @@ extern "C" void adsb_destroy(adsb_ctx *c)
     (void)hipFree(c->wof_levels);
     (void)hipFree(c->trk_u32);
     (void)hipFree(c->corr.block);
+    (void)hipFree(c->win.block);
+    (void)hipFree(c->win.in);
     (void)hipFree(c->trk_temp);
     (void)hipFree(c->trk_points);
     (void)hipFree(c->trk_aircraft);

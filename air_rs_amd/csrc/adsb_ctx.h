@@ -73,6 +73,20 @@ struct adsb_ctx {
         adsb_frame_level *in_levels = nullptr;       // [frames]
         bool done = false;          // a correlate call has been enqueued
     } corr;
+    // wire input (adsb_wire_in.hip), allocated on first adsb_wire_in_of and grown on demand: one hipMalloc carved into the
+    // kernels' arrays and the results, and the device copy of a host input
+    struct WireIn {
+        void *block = nullptr;      // everything in `a` below points into it
+        size_t bytes = 0, frames = 0; // the input length and the frames it is good for
+        bool levels = false;        // ... with level records
+        adsbk::WireInArgs a{};      // scratch and result pointers (the input and the cfg are set per call)
+        uint32_t *ends = nullptr;   // [256]
+        uint8_t *in = nullptr;      // [in_bytes], of a host input
+        size_t in_bytes = 0;
+        uint32_t n_streams = 0;     // of the last call
+        bool with_levels = false;   // the last call wrote level records
+        bool done = false;          // a call has been enqueued
+    } win;
     // tracker (allocated on first adsb_track_device)
     uint32_t *trk_u32 = nullptr;    // 4 x [max_out]: keys, vals, sorted keys, sorted vals
     void *trk_temp = nullptr;

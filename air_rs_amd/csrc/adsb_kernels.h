@@ -201,6 +201,38 @@ struct WireArgs {
 };
 hipError_t launch_wire(hipStream_t s, const WireArgs &a);
 
+// byte streams of Beast binary or AVR text back into an ordered frame list (adsb_wire_in.hip): six dispatches, see there
+constexpr uint32_t kWireInBlockBytes = 4096; // bytes of the stream per workgroup span
+constexpr uint32_t kWireInThreads = 256;     // threads per span: 16 bytes each
+constexpr uint32_t kWireInScanThreads = 256; // threads of the one workgroup that scans the spans' words
+static_assert(kWireInThreads * 16 == kWireInBlockBytes, "16 bytes per thread");
+struct WireInTally;                          // adsb_wire_in.h
+struct WireInArgs {
+    const uint32_t *words;       // the dword that holds bytes[0]: stream byte g is byte g + lead from here
+    uint32_t lead;               // 0..3
+    uint32_t n_bytes;
+    uint32_t n_streams;          // 1..256
+    const uint32_t *ends;        // [n_streams] ascending exclusive ends, the last = n_bytes
+    uint32_t format, filter;     // ADSB_WIRE_*, ADSB_WIRE_IN_*
+    uint64_t tick_bias;
+    int sample_type;             // the full scale of the level records
+    uint32_t cap;                // frames kept
+    uint32_t n_spans;            // ceil((lead + n_bytes) / kWireInBlockBytes)
+    // scratch
+    uint32_t *last;              // [n_spans] 1 + the place in its span of the span's last byte that is not 0x1A; 0: none
+    uint64_t *carry;             // [n_spans] 1 + (lead + the position) of the last such byte in front of the span; 0: none
+    WireInTally *tally;          // [n_spans] the span's counters; `kept` becomes the list index of its first frame
+    uint32_t *inc, *tail;        // [n_streams] 1 + the incomplete mark's position (0: none); consumed without one
+    // results
+    adsb_frame *frames;          // [cap]
+    adsb_wire_rx *rx;            // [cap]
+    adsb_frame_level *levels;    // [cap] or null
+    uint64_t *counts, *consumed; // [n_streams]
+    adsb_wire_in_header *hdr;
+};
+constexpr uint32_t wire_in_spans(uint64_t lead_plus_bytes) { return (uint32_t)((lead_plus_bytes + kWireInBlockBytes - 1) / kWireInBlockBytes); }
+hipError_t launch_wire_in(hipStream_t s, const WireInArgs &a);
+
 // receptions of one transmission across receivers (adsb_correlate.hip): the dispatch sequence is described there
 constexpr uint32_t kCorrBlock = 256; // receptions (= threads) per workgroup of the key and write kernels
 struct CorrAgg;                      // adsb_correlate.h

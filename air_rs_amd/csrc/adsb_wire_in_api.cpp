@@ -1,0 +1,189 @@
+// adsb_wire_in_api.cpp -- the C boundary of the wire input (include/adsb_hip.h, "Wire input"): argument checks, the one
+// device block the kernels' arrays are carved from, the copy of a host input, and the fetch.  The kernels are
+// adsb_wire_in.hip.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "adsb_ctx.h"
+#include "adsb_wire_in.h"
+
+static bool win_in_device_memory(const adsb_ctx *c, const void *p)
+{
+    hipPointerAttribute_t at{};
+    const bool yes = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice &&
+                     at.device == c->cfg.device;
+    (void)hipGetLastError(); // a plain host pointer is an error to the query: do not leave it to the launches after it
+    return yes;
+}
+
+// One block for an input of `bytes` bytes and `frames` kept frames.  Every array starts 256-byte aligned.
+static int win_reserve(adsb_ctx *c, size_t bytes, size_t frames, bool levels)
+{
+    adsb_ctx::WireIn &k = c->win;
+    if (k.block && k.bytes >= bytes && k.frames >= frames && (k.levels || !levels)) return ADSB_OK;
+    if (k.block) HIPCHK(hipStreamSynchronize(c->aux)); // an earlier call's kernels may still use the block
+    bytes = std::max(bytes, k.bytes);
+    frames = std::max(frames, k.frames);
+    levels = levels || k.levels;
+    (void)hipFree(k.block);
+    k.block = nullptr;
+    k.bytes = k.frames = 0;
+    k.levels = k.done = false;
+    const size_t f = std::max<size_t>(frames, 1);
+    const size_t spans = (size_t)adsbk::wire_in_spans((uint64_t)bytes + 3) + 1; // whatever the input's alignment
+    size_t total = 0;
+    const auto take = [&total](size_t n) {
+        const size_t at = total;
+        total += (n + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t o_last = take(4 * spans), o_carry = take(8 * spans), o_tally = take(sizeof(adsbk::WireInTally) * spans);
+    const size_t o_inc = take(4 * adsbk::kWireInMaxStreams), o_tail = take(4 * adsbk::kWireInMaxStreams);
+    const size_t o_ends = take(4 * adsbk::kWireInMaxStreams);
+    const size_t o_frames = take(sizeof(adsb_frame) * f), o_rx = take(sizeof(adsb_wire_rx) * f);
+    const size_t o_levels = take(levels ? sizeof(adsb_frame_level) * f : 0);
+    const size_t o_counts = take(8 * adsbk::kWireInMaxStreams), o_consumed = take(8 * adsbk::kWireInMaxStreams);
+    const size_t o_hdr = take(sizeof(adsb_wire_in_header));
+    char *b = nullptr;
+    if (hipMalloc((void **)&b, total) != hipSuccess) {
+        (void)hipGetLastError();
+        return ADSB_E_NOMEM;
+    }
+    k.block = b;
+    k.bytes = bytes;
+    k.frames = frames;
+    k.levels = levels;
+    adsbk::WireInArgs &a = k.a;
+    a = adsbk::WireInArgs{};
+    a.last = (uint32_t *)(b + o_last);
+    a.carry = (uint64_t *)(b + o_carry);
+    a.tally = (adsbk::WireInTally *)(b + o_tally);
+    a.inc = (uint32_t *)(b + o_inc);
+    a.tail = (uint32_t *)(b + o_tail);
+    k.ends = (uint32_t *)(b + o_ends);
+    a.frames = (adsb_frame *)(b + o_frames);
+    a.rx = (adsb_wire_rx *)(b + o_rx);
+    a.levels = levels ? (adsb_frame_level *)(b + o_levels) : nullptr;
+    a.counts = (uint64_t *)(b + o_counts);
+    a.consumed = (uint64_t *)(b + o_consumed);
+    a.hdr = (adsb_wire_in_header *)(b + o_hdr);
+    return ADSB_OK;
+}
+
+// The checked ends of the streams as 32-bit words; ADSB_E_ARG / ADSB_E_CAPACITY as adsb_wire_in_of documents.  Shared
+// with nothing: the CPU mirror checks the same in its own file, without the HIP runtime.
+static int win_check(const adsb_wire_in_cfg *cfg, const uint8_t *bytes, size_t n_bytes, const uint64_t *stream_ends,
+                     uint32_t n_streams, std::vector<uint32_t> *ends)
+{
+    if (!adsbk::wire_in_cfg_ok(cfg) || !stream_ends || (!bytes && n_bytes) || n_streams < 1 ||
+        n_streams > adsbk::kWireInMaxStreams)
+        return ADSB_E_ARG;
+    if ((uint64_t)n_bytes > 0xFFFFFFFFull) return ADSB_E_CAPACITY;
+    ends->resize(n_streams);
+    uint64_t prev = 0;
+    for (uint32_t r = 0; r < n_streams; ++r) {
+        if (stream_ends[r] < prev || stream_ends[r] > (uint64_t)n_bytes) return ADSB_E_ARG;
+        (*ends)[r] = (uint32_t)(prev = stream_ends[r]);
+    }
+    return prev == (uint64_t)n_bytes ? ADSB_OK : ADSB_E_ARG;
+}
+
+extern "C" int adsb_wire_in_of(adsb_ctx *c, const adsb_wire_in_cfg *cfg, const uint8_t *bytes, size_t n_bytes,
+                               const uint64_t *stream_ends, uint32_t n_streams)
+{
+    if (!c) return ADSB_E_ARG;
+    std::vector<uint32_t> ends;
+    int rc = win_check(cfg, bytes, n_bytes, stream_ends, n_streams, &ends);
+    if (rc != ADSB_OK) return rc;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const size_t most = n_bytes / adsbk::kWireInMinBytes; // frames that can exist
+    const size_t cap = cfg->max_frames ? (size_t)std::min<uint64_t>(cfg->max_frames, most) : most;
+    if ((rc = win_reserve(c, n_bytes, cap, cfg->levels != 0)) != ADSB_OK) return rc;
+    adsb_ctx::WireIn &k = c->win;
+    const uint8_t *in = bytes;
+    if (n_bytes && !win_in_device_memory(c, bytes)) {
+        if (k.in_bytes < n_bytes) {
+            if (k.in) HIPCHK(hipStreamSynchronize(c->aux)); // an earlier call's kernels may still read it
+            (void)hipFree(k.in);
+            k.in = nullptr;
+            k.in_bytes = 0;
+            if (hipMalloc((void **)&k.in, (n_bytes + 3) & ~(size_t)3) != hipSuccess) { // whole dwords
+                (void)hipGetLastError();
+                return ADSB_E_NOMEM;
+            }
+            k.in_bytes = n_bytes;
+        }
+        HIPCHK(hipMemcpyAsync(k.in, bytes, n_bytes, hipMemcpyHostToDevice, c->aux));
+        in = k.in;
+    }
+    HIPCHK(hipMemcpyAsync(k.ends, ends.data(), sizeof(uint32_t) * n_streams, hipMemcpyHostToDevice, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux)); // the host arrays are the caller's (and this frame's) again
+    adsbk::WireInArgs a = k.a;
+    a.lead = n_bytes ? (uint32_t)((uintptr_t)in & 3u) : 0u;
+    a.words = n_bytes ? (const uint32_t *)((uintptr_t)in - a.lead) : (const uint32_t *)k.ends; // (not read when empty)
+    a.n_bytes = (uint32_t)n_bytes;
+    a.n_streams = n_streams;
+    a.ends = k.ends;
+    a.format = cfg->format;
+    a.filter = cfg->filter;
+    a.tick_bias = cfg->tick_bias;
+    a.sample_type = cfg->sample_type;
+    a.cap = (uint32_t)cap;
+    a.n_spans = adsbk::wire_in_spans((uint64_t)a.lead + n_bytes);
+    if (!cfg->levels) a.levels = nullptr;
+    HIPCHK(adsbk::launch_wire_in(c->aux, a));
+    k.n_streams = n_streams;
+    k.with_levels = cfg->levels != 0;
+    k.done = true;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_fetch_wire_in(adsb_ctx *c, adsb_frame *frames, adsb_wire_rx *rx, adsb_frame_level *levels, size_t max,
+                                  size_t *n, uint64_t *counts, uint64_t *consumed, uint32_t n_streams,
+                                  adsb_wire_in_header *header)
+{
+    if (!c) return ADSB_E_ARG;
+    const adsb_ctx::WireIn &k = c->win;
+    if (!k.done || (levels && !k.with_levels)) return ADSB_E_STATE;
+    if (n_streams > k.n_streams) return ADSB_E_ARG;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    adsb_wire_in_header h{};
+    HIPCHK(hipMemcpyAsync(&h, k.a.hdr, sizeof(h), hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    const size_t m = std::min<size_t>((size_t)h.n_frames, max);
+    if (m && frames) HIPCHK(hipMemcpyAsync(frames, k.a.frames, sizeof(adsb_frame) * m, hipMemcpyDeviceToHost, c->aux));
+    if (m && rx) HIPCHK(hipMemcpyAsync(rx, k.a.rx, sizeof(adsb_wire_rx) * m, hipMemcpyDeviceToHost, c->aux));
+    if (m && levels) HIPCHK(hipMemcpyAsync(levels, k.a.levels, sizeof(adsb_frame_level) * m, hipMemcpyDeviceToHost, c->aux));
+    if (n_streams && counts) HIPCHK(hipMemcpyAsync(counts, k.a.counts, 8 * (size_t)n_streams, hipMemcpyDeviceToHost, c->aux));
+    if (n_streams && consumed)
+        HIPCHK(hipMemcpyAsync(consumed, k.a.consumed, 8 * (size_t)n_streams, hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux));
+    if (n) *n = m;
+    if (header) *header = h;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_wire_in_device(adsb_ctx *c, const adsb_frame **frames_dev, const adsb_wire_rx **rx_dev,
+                                   const adsb_frame_level **levels_dev, const uint64_t **counts_dev,
+                                   const uint64_t **consumed_dev, const void **header_dev)
+{
+    if (!c) return ADSB_E_ARG;
+    const adsb_ctx::WireIn &k = c->win;
+    if (!k.done) return ADSB_E_STATE;
+    if (frames_dev) *frames_dev = k.a.frames;
+    if (rx_dev) *rx_dev = k.a.rx;
+    if (levels_dev) *levels_dev = k.with_levels ? k.a.levels : nullptr;
+    if (counts_dev) *counts_dev = k.a.counts;
+    if (consumed_dev) *consumed_dev = k.a.consumed;
+    if (header_dev) *header_dev = k.a.hdr;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_debug_wire_in_geometry(uint32_t *bytes_per_block, uint32_t *scan_threads)
+{
+    if (bytes_per_block) *bytes_per_block = adsbk::kWireInBlockBytes;
+    if (scan_threads) *scan_threads = adsbk::kWireInScanThreads;
+    return ADSB_OK;
+}

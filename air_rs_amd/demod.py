@@ -4,6 +4,7 @@ Mirrors the C ABI one to one; numpy arrays carry host buffers, integer device po
 example ``torch.Tensor.data_ptr()``) carry HBM-resident ones.  Frames come back as a numpy
 structured array with the adsb_frame layout.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -143,6 +144,69 @@ def _wire_result(out, room, ends, total):
         fit = ends[ends <= room]
         total = int(fit[-1]) if len(fit) else 0
     return out[:total].tobytes(), ends
+
+
+WIRE_RX_DTYPE = np.dtype([("ticks", "<u8"), ("pos", "<u4"), ("signal", "u1"), ("kind", "u1"), ("receiver", "<u2")])
+assert WIRE_RX_DTYPE.itemsize == C.sizeof(L.AdsbWireRx) == 16
+WIRE_IN_HEADER_DTYPE = np.dtype([(k, "<u8") for k in ("n_frames", "total_found", "n_marks", "n_cut", "n_unknown",
+                                                       "n_other", "n_rejected", "flags")])
+assert WIRE_IN_HEADER_DTYPE.itemsize == C.sizeof(L.AdsbWireInHeader) == 64
+WIRE_IN_FILTERS = {"crc": L.ADSB_WIRE_IN_CRC, "df17": L.ADSB_WIRE_IN_DF17}
+WireIn = collections.namedtuple("WireIn", "frames rx levels counts consumed header")
+WireIn.__doc__ = """One parse of wire input: FRAME_DTYPE frames, WIRE_RX_DTYPE rx, LEVEL_DTYPE levels (None without
+levels=True), uint64 counts and consumed per stream, and the WIRE_IN_HEADER_DTYPE record."""
+
+
+def _wire_in_cfg(format, filter, tick_bias, max_frames, sample_type, levels):
+    fmt = WIRE_FORMATS[format] if isinstance(format, str) else int(format)
+    if isinstance(filter, str):
+        filter = [filter]
+    bits = int(filter) if isinstance(filter, int) else sum(WIRE_IN_FILTERS[f] for f in (filter or ()))
+    return L.AdsbWireInCfg(fmt, bits, int(tick_bias), int(max_frames), int(sample_type), 1 if levels else 0)
+
+
+def _wire_in_input(data, stream_ends):
+    """(array kept alive or None, pointer or None, n_bytes, uint64 ends) of bytes-like / uint8 array / (device pointer,
+    length) input; stream_ends None: one stream."""
+    if isinstance(data, tuple):
+        keep, ptr, n = None, int(data[0]), int(data[1])
+    else:
+        keep = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+        ptr, n = (keep.ctypes.data if len(keep) else None), len(keep)
+    ends = np.ascontiguousarray([n] if stream_ends is None else stream_ends, dtype=np.uint64).reshape(-1)
+    return keep, (ptr if n else None), n, ends
+
+
+def _wire_in_room(n_bytes, max_frames, levels):
+    room = n_bytes // 23 if not max_frames else min(int(max_frames), n_bytes // 23)
+    return (room, np.zeros(max(room, 1), dtype=FRAME_DTYPE), np.zeros(max(room, 1), dtype=WIRE_RX_DTYPE),
+            np.zeros(max(room, 1), dtype=LEVEL_DTYPE) if levels else None)
+
+
+def _wire_in_result(fr, rx, lv, n, counts, consumed, hdr):
+    header = np.frombuffer(bytes(hdr), dtype=WIRE_IN_HEADER_DTYPE)[0]
+    return WireIn(fr[:n].copy(), rx[:n].copy(), None if lv is None else lv[:n].copy(), counts, consumed, header)
+
+
+def host_wire_parse(data, stream_ends=None, format="beast", filter=0, tick_bias=0, max_frames=0,
+                    sample_type=L.ADSB_SAMPLE_I8, levels=False):
+    """adsb_host_wire_parse, the CPU mirror of AdsbDemod.wire_in_of: one or many streams of Beast binary ("beast") or AVR
+    text ("avr", "avr_mlat": both read '*' and '@' lines) laid end to end in `data` (bytes-like or a uint8 array), with
+    their ascending exclusive ends (None: one stream), back into a WireIn.  filter: 0, "crc", "df17", a list of those or
+    the ADSB_WIRE_IN_* bits; levels: level records from the signal bytes, on sample_type's full scale.  Needs no
+    device."""
+    keep, ptr, n, ends = _wire_in_input(data, stream_ends)
+    cfg = _wire_in_cfg(format, filter, tick_bias, max_frames, sample_type, levels)
+    room, fr, rx, lv = _wire_in_room(n, max_frames, levels)
+    counts, consumed = np.zeros(len(ends), dtype=np.uint64), np.zeros(len(ends), dtype=np.uint64)
+    got, hdr = C.c_size_t(), L.AdsbWireInHeader()
+    L.check(L.load().adsb_host_wire_parse(C.byref(cfg), ptr, n, ends.ctypes.data if len(ends) else None, len(ends),
+                                          fr.ctypes.data, rx.ctypes.data, None if lv is None else lv.ctypes.data, room,
+                                          C.byref(got), counts.ctypes.data if len(ends) else None,
+                                          consumed.ctypes.data if len(ends) else None, C.byref(hdr)),
+            "adsb_host_wire_parse")
+    return _wire_in_result(fr, rx, lv, got.value, counts, consumed, hdr)
 
 
 MESSAGE_DTYPE = np.dtype([("time", "<u8"), ("bytes", "u1", (14,)), ("status", "u1"), ("fixed_bit", "u1"), ("first", "<u4"),
@@ -547,6 +611,49 @@ class AdsbDemod:
         L.check(self._lib.adsb_wire_of(self._h, C.byref(cfg), fptr, lptr, n, out.ctypes.data, room, C.byref(total),
                                        ends.ctypes.data), "adsb_wire_of")
         return _wire_result(out, room, ends[:n].copy(), total.value)
+
+    def wire_in_of_async(self, data, stream_ends=None, format="beast", filter=0, tick_bias=0, max_frames=0,
+                         levels=False):
+        """adsb_wire_in_of alone: enqueues the parse of one or many streams of Beast binary or AVR text and returns once
+        the host arrays are copied.  data: bytes-like or a uint8 array (host), or (device pointer, length); stream_ends:
+        the streams' ascending exclusive ends (None: one stream).  See host_wire_parse for the rest; the level records
+        are on this context's sample type's full scale."""
+        keep, ptr, n, ends = _wire_in_input(data, stream_ends)
+        cfg = _wire_in_cfg(format, filter, tick_bias, max_frames, self.sample_type, levels)
+        L.check(self._lib.adsb_wire_in_of(self._h, C.byref(cfg), ptr, n, ends.ctypes.data if len(ends) else None,
+                                          len(ends)), "adsb_wire_in_of")
+        self._wire_in = (len(ends), bool(levels))
+
+    def fetch_wire_in(self):
+        """adsb_fetch_wire_in: waits for the parse wire_in_of_async() enqueued -> WireIn."""
+        n_streams, levels = getattr(self, "_wire_in", (0, False))
+        hdr, got = L.AdsbWireInHeader(), C.c_size_t()
+        L.check(self._lib.adsb_fetch_wire_in(self._h, None, None, None, 0, C.byref(got), None, None, 0, C.byref(hdr)),
+                "adsb_fetch_wire_in")                 # the sizes first; the lists stay where they are
+        room = int(hdr.n_frames)
+        fr, rx = np.zeros(max(room, 1), dtype=FRAME_DTYPE), np.zeros(max(room, 1), dtype=WIRE_RX_DTYPE)
+        lv = np.zeros(max(room, 1), dtype=LEVEL_DTYPE) if levels else None
+        counts, consumed = np.zeros(n_streams, dtype=np.uint64), np.zeros(n_streams, dtype=np.uint64)
+        L.check(self._lib.adsb_fetch_wire_in(self._h, fr.ctypes.data, rx.ctypes.data,
+                                             None if lv is None else lv.ctypes.data, room, C.byref(got),
+                                             counts.ctypes.data if n_streams else None,
+                                             consumed.ctypes.data if n_streams else None, n_streams, C.byref(hdr)),
+                "adsb_fetch_wire_in")
+        return _wire_in_result(fr, rx, lv, got.value, counts, consumed, hdr)
+
+    def wire_in_of(self, data, stream_ends=None, format="beast", filter=0, tick_bias=0, max_frames=0, levels=False):
+        """Beast binary or AVR text back into frames, parsed on the device -> WireIn (frames, rx, levels, counts,
+        consumed, header).  frames / levels / counts are arguments for correlate_of, TrackBank.update and wire_of;
+        consumed[r] is where stream r's next chunk starts.  See wire_in_of_async."""
+        self.wire_in_of_async(data, stream_ends, format, filter, tick_bias, max_frames, levels)
+        return self.fetch_wire_in()
+
+    def wire_in_device(self):
+        """adsb_wire_in_device: device addresses (frames, rx, levels or None, counts, consumed, header); no
+        synchronisation."""
+        p = [C.c_void_p() for _ in range(6)]
+        L.check(self._lib.adsb_wire_in_device(self._h, *[C.byref(x) for x in p]), "adsb_wire_in_device")
+        return tuple(x.value for x in p)
 
     def correlate_async(self, window, sample_base=None, levels=False):
         """adsb_correlate_launch alone: the last launch's list, channel k as receiver k, correlated on the device.

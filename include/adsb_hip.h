@@ -334,6 +334,105 @@ int adsb_wire_of(adsb_ctx *ctx, const adsb_wire_cfg *cfg, const adsb_frame *fram
 int adsb_debug_wire_geometry(uint32_t *frames_per_block, uint32_t *scan_threads);
 
 /*
+ * Wire input: the inverse of the wire output.  One or many byte streams of Beast binary or AVR text, as distributed
+ * receivers (readsb, dump1090, Beast splitters, mlat-client) send them over TCP, parsed on the device into the ordered
+ * adsb_frame[] every consumer behind the demodulator takes, with per-frame receive records, optional level records and
+ * per-stream counts[] that drop straight into adsb_correlate_of, adsb_track_bank_update(_levels) and adsb_wire_of.
+ *   INPUT  bytes[n_bytes] is R streams laid end to end, 1 <= R <= 256; stream_ends[R] holds ascending exclusive ends,
+ *     the last equal to n_bytes; n_bytes < 2^32.  Streams are parsed independently: a stream's first byte has no
+ *     predecessor, and nothing reads past a stream's end.  Below, B[0..N) is one stream.
+ *   BEAST (ADSB_WIRE_BEAST)
+ *     MARKS  Take every maximal run of 0x1A bytes B[a..b) that is followed by a byte inside the stream (b < N).  If its
+ *       length b - a is odd, its last byte b-1 is a MARK and B[b] is the mark's type byte.  Even runs hold no mark.  A run
+ *       that reaches the end of the stream holds no mark.
+ *     LENGTHS  Types '1', '2' and '3' carry 2, 7 and 14 message bytes after 6 timestamp bytes and 1 signal byte.  Any
+ *       other type byte makes the mark UNKNOWN: it is counted and nothing is read for it.
+ *     READING a known mark starts at b+1 and un-escapes 7 + len bytes.  A byte other than 0x1A is taken as is.  1A 1A
+ *       yields one 0x1A.  A 0x1A whose next byte exists and is not 0x1A means the frame is CUT; that byte is itself a
+ *       mark by the parity rule.  Needing a byte at or past N, including the partner of a final 0x1A, means the frame is
+ *       INCOMPLETE.  Otherwise the frame is COMPLETE.
+ *     Complete '3' frames that pass the filters are emitted.  Complete '1' and '2' frames are counted (n_other) and not
+ *       emitted.  Complete frames never overlap.  Only the last mark of a stream can be incomplete.
+ *     CONSUMED  If the stream has an incomplete mark at m, consumed = m.  Otherwise let k be the number of trailing 0x1A
+ *       bytes of the stream that no complete frame consumed, and consumed = N - (k mod 2).
+ *     CHUNKS  The caller's next chunk is B[consumed..) + new bytes.  Parsing a stream in chunks of any sizes this way
+ *       yields exactly the frames of parsing it whole, at the same absolute positions.  The carried tail is never
+ *       longer than 43 bytes.
+ *   AVR (ADSB_WIRE_AVR accepts both the '*' and the '@' form; ADSB_WIRE_AVR_MLAT is the same value set)
+ *     A candidate is any B[p] in {'*', '@'}; h is the number of consecutive hex digits after it, in either case,
+ *     counted up to 41.  If the byte after the digits is ';': '*' with h = 28 is a long frame; '@' with h = 40 is a long
+ *     frame with a 12-digit timestamp; '*' with 4 or 14 digits and '@' with 16 or 26 digits are counted as n_other;
+ *     anything else is cut.  If the digits reach the end of the stream with h at most 28 for '*' or at most 40 for '@',
+ *     the candidate is incomplete and consumed = p.  Otherwise consumed = N.  Bytes between frames ('\n', '\r\n',
+ *     anything) are skipped.
+ *   OUTPUTS, all in stream order: receiver 0's frames by position, then receiver 1's, and so on.
+ *     adsb_frame frames[n]: bytes = the 14 message bytes, status = 0, fixed_bit = 0xFF, offset = ((t - tick_bias) mod
+ *       2^48) / 6 rounded down, the exact inverse of the encoder's timestamp for offsets below 2^48 / 6.  Plain '*'
+ *       lines have t = 0.
+ *     adsb_wire_rx rx[n]: the raw t, the position of the mark or lead byte inside its own stream, the signal byte, the
+ *       kind ('3', '*' or '@') and the receiver (the stream's index).
+ *     adsb_frame_level levels[n] when cfg.levels != 0.  For a signal byte s > 0: flags = ADSB_LEVEL_VALID and signal_sum
+ *       = the smallest sum whose signal byte is s for cfg.sample_type's full scale, ceil((2s-1)^2 x 116 x FS /
+ *       (4 x 255^2)), and 1 for s = 1; every other field 0.  For s = 0 or AVR: an all-zero record.  With this,
+ *       adsb_wire_of(parse(x)) reproduces x's signal bytes, and correlate's best_receiver works on network input.
+ *     uint64 counts[R] (frames of each stream in the list) and uint64 consumed[R] (per stream, relative to its start).
+ *     adsb_wire_in_header: n_frames (in the list), total_found, n_marks (AVR: candidates), n_cut, n_unknown, n_other,
+ *       n_rejected, flags.
+ *   FILTERS (cfg.filter bits).  A rejected frame is still a complete frame for framing and for consumed; it is counted
+ *     in n_rejected and not emitted.  ADSB_WIRE_IN_CRC keeps a long frame only if crc24(bytes[0..11]) ^ bytes[11..14]
+ *     == 0 (generator 0x1FFF409; no repair, a Beast sender has already done its own).  ADSB_WIRE_IN_DF17 keeps it only
+ *     if bytes[0] >> 3 == 17.
+ *   CAPACITY  cfg.max_frames = 0 means n_bytes / 23, which can never truncate.  Otherwise the first max_frames frames
+ *     in order are kept, flags has ADSB_FLAG_TRUNCATED, counts[] are clipped to the list and total_found is the full
+ *     number.
+ * Nothing depends on atomics or scheduling: two runs give the same bytes.
+ */
+#define ADSB_WIRE_IN_CRC 0x1u
+#define ADSB_WIRE_IN_DF17 0x2u
+typedef struct adsb_wire_in_cfg {
+    uint32_t format;      /* ADSB_WIRE_*                                                       */
+    uint32_t filter;      /* ADSB_WIRE_IN_* bits                                               */
+    uint64_t tick_bias;   /* < 2^48                                                            */
+    uint64_t max_frames;  /* 0: n_bytes / 23                                                   */
+    int32_t  sample_type; /* ADSB_SAMPLE_*: the full scale of the level records (with levels) */
+    uint32_t levels;      /* != 0: level records beside the frames                             */
+} adsb_wire_in_cfg;
+typedef struct adsb_wire_rx {      /* 16 bytes */
+    uint64_t ticks;           /* the raw timestamp t; 0 for a plain '*' line                  */
+    uint32_t pos;             /* position of the mark or lead byte inside its own stream      */
+    uint8_t  signal;          /* Beast's signal byte; 0 for AVR                               */
+    uint8_t  kind;            /* '3', '*' or '@'                                              */
+    uint16_t receiver;        /* the stream's index                                           */
+} adsb_wire_rx;
+typedef struct adsb_wire_in_header { /* 64 bytes */
+    uint64_t n_frames, total_found, n_marks, n_cut, n_unknown, n_other, n_rejected, flags;
+} adsb_wire_in_header;
+/* Parses.  `bytes` is host memory or device memory of the ctx's device; stream_ends is host memory.  Asynchronous on the
+ * ctx's stream once host arrays are copied.  Buffers are allocated on first use and grown when needed (may wait for
+ * earlier work): per input byte about 0.01 bytes of scan words, per frame of capacity 40 bytes (72 with levels), and a
+ * copy of a host input; a ctx that never calls it allocates nothing and launches exactly the kernels it launched before.
+ * Replaces the result of an earlier call.  n_bytes = 0 and empty streams are ADSB_OK.  ADSB_E_ARG for a NULL ctx, cfg or
+ * stream_ends, NULL bytes with n_bytes > 0, an unknown format, tick_bias >= 2^48, a bad sample_type with levels,
+ * n_streams outside 1..256, or ends that are not ascending or do not end at n_bytes; ADSB_E_CAPACITY for n_bytes >= 2^32. */
+int adsb_wire_in_of(adsb_ctx *ctx, const adsb_wire_in_cfg *cfg, const uint8_t *bytes, size_t n_bytes,
+                    const uint64_t *stream_ends, uint32_t n_streams);
+/* Waits and copies; each output may be NULL.  frames, rx and levels receive min(header.n_frames, max) entries and *n
+ * that number; counts and consumed receive n_streams entries each (at most the parsed call's); *header the totals,
+ * whatever the capacities.  ADSB_E_STATE before any adsb_wire_in_of, or for levels when that call had cfg.levels == 0;
+ * ADSB_E_ARG for a NULL ctx or n_streams above the parsed call's. */
+int adsb_fetch_wire_in(adsb_ctx *ctx, adsb_frame *frames, adsb_wire_rx *rx, adsb_frame_level *levels, size_t max,
+                       size_t *n, uint64_t *counts, uint64_t *consumed, uint32_t n_streams, adsb_wire_in_header *header);
+/* For device-side consumers; does not synchronise.  The arrays of the last adsb_wire_in_of in device memory (each
+ * optional; *levels_dev is NULL when that call had cfg.levels == 0), valid until the next wire-input call on this ctx
+ * and ordered on the ctx's stream behind it.  ADSB_E_STATE before any adsb_wire_in_of. */
+int adsb_wire_in_device(adsb_ctx *ctx, const adsb_frame **frames_dev, const adsb_wire_rx **rx_dev,
+                        const adsb_frame_level **levels_dev, const uint64_t **counts_dev, const uint64_t **consumed_dev,
+                        const void **header_dev);
+/* Bytes per workgroup span of the parser's kernels and threads of its one-workgroup scans (either may be NULL): the
+ * sizes at which the parser takes another path, for tests.  The result does not depend on them. */
+int adsb_debug_wire_in_geometry(uint32_t *bytes_per_block, uint32_t *scan_threads);
+
+/*
  * Correlate: a multi-receiver frame list as ONE de-duplicated, time-ordered message list, with every message's
  * receptions (receiver and sample time) -- what an aggregator forwards once, what one track table pairs across
  * receivers, and what a multilateration solver takes as input.  Stateless; computed on the device.

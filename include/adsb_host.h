@@ -126,6 +126,17 @@ int adsb_host_wire_encode(const adsb_wire_cfg *cfg, int sample_type, const adsb_
                           size_t *n_bytes, uint32_t *ends);
 
 /*
+ * CPU mirror of adsb_wire_in_of + adsb_fetch_wire_in (adsb_hip.h, "Wire input"): the same outputs from the same program
+ * text as the device's, no device needed.  bytes and stream_ends as there, all host memory.  frames, rx and levels
+ * (each may be NULL; levels is filled only with cfg.levels != 0) receive min(header.n_frames, max) entries and *n
+ * (optional) that number; counts[n_streams], consumed[n_streams] and *header are optional.  What a feed-side consumer
+ * without a GPU uses.  The same argument errors as adsb_wire_in_of.
+ */
+int adsb_host_wire_parse(const adsb_wire_in_cfg *cfg, const uint8_t *bytes, size_t n_bytes, const uint64_t *stream_ends,
+                         uint32_t n_streams, adsb_frame *frames, adsb_wire_rx *rx, adsb_frame_level *levels, size_t max,
+                         size_t *n, uint64_t *counts, uint64_t *consumed, adsb_wire_in_header *header);
+
+/*
  * CPU mirror of adsb_correlate_of (adsb_hip.h, "Correlate"): the same messages, frames and receptions, built from the
  * same key compare, head rule and aggregate combine as the device's, no device needed.  frames[n] with levels[n] (NULL:
  * best_receiver 0xFFFF), counts[n_receivers] and sample_base[n_receivers] (NULL: all 0), all host memory.  recs

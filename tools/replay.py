@@ -12,6 +12,8 @@
   tools/replay.py capture.c16 --aircraft --site 51.5,-0.1      # ... with five more: each aircraft's own fix from the site
   tools/replay.py capture.c16 --beast out.bin # also write every packet as Beast binary (readsb / dump1090 / tar1090 input)
   tools/replay.py capture.c16 --avr out.txt   # ... as AVR text, one "*...;" line per packet; --mlat: "@" + timestamp + ...
+  tools/replay.py out.bin --beast-in          # FILE is a Beast capture (a receiver's TCP stream) instead of IQ
+  tools/replay.py out.txt --avr-in            # ... an AVR text capture, "*" and "@" lines alike
 
 Everything below the argument parsing is one call through the C ABI (adsb_replay_file, include/adsb_host.h).
 The "Processed Time" line carries no value (the reference prints the wall clock there).  With --aircraft, the frames
@@ -38,7 +40,11 @@ and Bearing in degrees from the site (one decimal), and GS, a surface message's 
 whole capture's packets are also written to FILE as one stream, encoded on the device (adsb_wire_of): Beast binary with
 the 12 MHz timestamp 6 x offset + N (--tick-bias N, default 0: the first preamble sample) and the signal byte from the
 packets' level records, or AVR text ("*" lines; with --mlat "@" lines that carry the timestamp).  Offsets are positions
-in the whole capture, so the timestamps run on across chunks.  The TEXT has not been compared with a Rust build's (there is no
+in the whole capture, so the timestamps run on across chunks.  With --beast-in / --avr-in the positional file holds
+Beast binary or AVR text instead of samples: it is parsed on the device (adsb_wire_in_of) in 64 KiB chunks, the unparsed
+tail of each carried into the next by `consumed`, frame offsets = (timestamp - N) / 6 (--tick-bias N), and everything
+that prints from a frame list works on it: the stream text, --aircraft (with --levels: RSSI from the Beast signal
+bytes), --web, --beast, --avr.  --levels alone needs the samples.  The TEXT has not been compared with a Rust build's (there is no
 Rust toolchain); only the values are checked, against the oracle."""
 import argparse
 import json
@@ -185,10 +191,35 @@ def level_lines(d, st, frames, iq, piece=LEVELS_PIECE):
     return "".join(line + "\n" for line in lines)
 
 
-def write_wire(d, frames, a, fmt):
+WIRE_IN_CHUNK = 1 << 16  # bytes of a Beast / AVR capture parsed at a time
+
+
+def read_wire(d, path, wire_format, tick_bias, chunk=WIRE_IN_CHUNK):
+    """--beast-in / --avr-in: (frames, their level records) of a Beast or AVR capture, parsed on the device chunk by
+    chunk; what a chunk leaves unparsed (an incomplete last frame) goes in front of the next."""
+    import numpy as np
+    frames, levels, tail = [np.zeros(0, dtype=A.FRAME_DTYPE)], [np.zeros(0, dtype=A.LEVEL_DTYPE)], b""
+    with open(path, "rb") as fh:
+        while True:
+            new = fh.read(chunk)
+            if not new:
+                break
+            got = d.wire_in_of(tail + new, format=wire_format, tick_bias=tick_bias, levels=True)
+            frames.append(got.frames)
+            levels.append(got.levels)
+            tail = (tail + new)[int(got.consumed[0]):]
+    return np.concatenate(frames), np.concatenate(levels)
+
+
+def stream_text(frames):
+    """What the stream thread prints for a frame list (adsb.rs:156-158)."""
+    return "".join("\n" + A.packet_display(f["bytes"].tobytes()) + "\n" for f in frames)
+
+
+def write_wire(d, frames, a, fmt, levels=None):
     """--beast / --avr: the capture's frames as one stream, encoded on the device."""
     if a.beast:
-        levels = A.host_frame_levels(read_capture(a.file, fmt), frames)
+        levels = A.host_frame_levels(read_capture(a.file, fmt), frames) if levels is None else levels
         with open(a.beast, "wb") as fh:
             fh.write(d.wire_of(frames, levels, format="beast", tick_bias=a.tick_bias)[0])
     if a.avr:
@@ -213,6 +244,8 @@ def main():
     ap.add_argument("--beast", metavar="FILE", help="also write the packets to FILE as Beast binary")
     ap.add_argument("--avr", metavar="FILE", help="also write the packets to FILE as AVR text")
     ap.add_argument("--mlat", action="store_true", help="with --avr: the '@' form, which carries the 12 MHz timestamp")
+    ap.add_argument("--beast-in", action="store_true", help="FILE is a Beast binary capture instead of IQ")
+    ap.add_argument("--avr-in", action="store_true", help="FILE is an AVR text capture instead of IQ")
     ap.add_argument("--tick-bias", type=int, default=0, metavar="N", help="added to every timestamp (12 MHz ticks, < 2^48)")
     a = ap.parse_args()
     if a.mlat and not a.avr:
@@ -221,11 +254,28 @@ def main():
         ap.error("--tick-bias is 0 .. 2^48 - 1")
     if a.site is not None and not a.aircraft:
         ap.error("--site needs --aircraft")
+    if a.beast_in and a.avr_in:
+        ap.error("--beast-in and --avr-in exclude each other")
+    wire_in = "beast" if a.beast_in else "avr" if a.avr_in else None
+    if wire_in and a.levels and not a.aircraft:
+        ap.error("--levels alone needs the samples")
     fmt = a.format or ("c16" if a.file.endswith(".c16") else "u8")
     st = A.ADSB_SAMPLE_I16 if fmt == "c16" else A.ADSB_SAMPLE_I8
     n_max = os.path.getsize(a.file) // (4 if fmt == "c16" else 2)
     with A.AdsbDemod(device=a.device, sample_type=st, max_samples=a.chunk + 240, max_out=a.chunk + 240,
                      host_staging=False) as d:
+        if wire_in:
+            frames, parsed_levels = read_wire(d, a.file, wire_in, a.tick_bias)
+            n_buf, n_samp = 0, (int(frames["offset"].max()) + A.WINDOW if len(frames) else 0)
+            if a.aircraft:
+                text = aircraft_table(d, frames, n_samp, st, parsed_levels if a.levels else None, site=a.site)
+            else:
+                text = web_stream(d, frames, a.chunk) if a.web else stream_text(frames)
+            write_wire(d, frames, a, fmt, parsed_levels)
+            sys.stdout.write(text)
+            if a.summary:
+                print(f"{os.path.getsize(a.file)} bytes, {len(frames)} packets", file=sys.stderr)
+            return
         frames, n_buf, n_samp, text = d.replay_file(a.file, L.ADSB_FILE_C16 if fmt == "c16" else L.ADSB_FILE_U8,
                                                     chunk_len=a.chunk, carry=a.carry, send_tail=a.tail,
                                                     max_frames=max(n_max // 200, 1 << 16))
