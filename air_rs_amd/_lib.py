@@ -126,6 +126,50 @@ class AdsbReception(C.Structure):
     _fields_ = [("time", C.c_uint64), ("frame", C.c_uint32), ("receiver", C.c_uint16), ("reserved", C.c_uint16)]
 
 
+ADSB_MLAT_C = 299792458.0 / 1.0003                           # propagation in air, m/s
+ADSB_MLAT_MAX_RECEPTIONS = 256
+ADSB_MLAT_TIME_RECEPTION, ADSB_MLAT_TIME_TICKS = 0, 1         # adsb_mlat_cfg.time_source
+ADSB_MLAT_USE_ALTITUDE = 0x1                                 # adsb_mlat_cfg.flags
+ADSB_MLAT_ATTEMPTED, ADSB_MLAT_CONVERGED, ADSB_MLAT_ALTITUDE, ADSB_MLAT_TOO_FEW = 0x1, 0x2, 0x4, 0x8  # adsb_mlat_fix.flags
+ADSB_MLAT_TOO_MANY, ADSB_MLAT_SINGULAR, ADSB_MLAT_REJECTED_RESIDUAL, ADSB_MLAT_REJECTED_RANGE = 0x10, 0x20, 0x40, 0x80
+ADSB_MLAT_VALID, ADSB_MLAT_BAD_INDEX = 0x100, 0x200
+ADSB_MLAT_HDR_BAD_INDEX = 0x1                                # adsb_mlat_header.flags
+
+
+class AdsbMlatReceiver(C.Structure):
+    """adsb_mlat_receiver: WGS84 degrees, metres above the ellipsoid, and the clock's offset in seconds (32 bytes)."""
+    _fields_ = [("latitude", C.c_double), ("longitude", C.c_double), ("height_m", C.c_double),
+                ("clock_offset_s", C.c_double)]
+
+
+class AdsbMlatCfg(C.Structure):
+    """adsb_mlat_cfg: the time source, the altitude switch, and the solver's limits; 0 takes each default (64 bytes)."""
+    _fields_ = [("time_source", C.c_uint32), ("flags", C.c_uint32), ("min_receivers", C.c_uint32),
+                ("max_iterations", C.c_uint32), ("seconds_per_tick", C.c_double), ("step_tol_m", C.c_double),
+                ("max_residual_m", C.c_double), ("max_range_m", C.c_double), ("default_altitude_m", C.c_double),
+                ("reserved", C.c_uint64)]
+
+
+class AdsbMlatFix(C.Structure):
+    """adsb_mlat_fix: where one message was sent from (64 bytes)."""
+    _fields_ = [("latitude", C.c_double), ("longitude", C.c_double), ("height_m", C.c_double), ("time_s", C.c_double),
+                ("residual_rms_m", C.c_float), ("pdop", C.c_float), ("hdop", C.c_float), ("vdop", C.c_float),
+                ("n_used", C.c_uint16), ("iterations", C.c_uint16), ("flags", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class AdsbMlatHeader(C.Structure):
+    """adsb_mlat_header: the totals of one multilaterate call (32 bytes)."""
+    _fields_ = [(k, C.c_uint64) for k in ("n_messages", "n_attempted", "n_valid", "flags")]
+
+
+MLAT_RECEIVER_DTYPE = np.dtype([("latitude", "<f8"), ("longitude", "<f8"), ("height_m", "<f8"), ("clock_offset_s", "<f8")])
+MLAT_FIX_DTYPE = np.dtype([("latitude", "<f8"), ("longitude", "<f8"), ("height_m", "<f8"), ("time_s", "<f8"),
+                           ("residual_rms_m", "<f4"), ("pdop", "<f4"), ("hdop", "<f4"), ("vdop", "<f4"), ("n_used", "<u2"),
+                           ("iterations", "<u2"), ("flags", "<u4"), ("reserved", "<u8")])
+assert MLAT_RECEIVER_DTYPE.itemsize == C.sizeof(AdsbMlatReceiver) == 32
+assert MLAT_FIX_DTYPE.itemsize == C.sizeof(AdsbMlatFix) == 64 and C.sizeof(AdsbMlatCfg) == 64
+
+
 class AdsbTrackPoint(C.Structure):
     _fields_ = [("latitude", C.c_double), ("longitude", C.c_double), ("icao", C.c_uint32), ("flags", C.c_uint32)]
 
@@ -289,6 +333,12 @@ PROTOTYPES = {
                                         _P(C.c_size_t)]),
     "adsb_correlated_device": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p), _P(C.c_void_p)]),
     "adsb_debug_correlate_geometry": (C.c_int, [_P(C.c_uint32)]),
+    "adsb_multilaterate": (C.c_int, [C.c_void_p, _P(AdsbMlatCfg), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "adsb_multilaterate_of": (C.c_int, [C.c_void_p, _P(AdsbMlatCfg), C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "adsb_fetch_mlat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), _P(AdsbMlatHeader)]),
+    "adsb_mlat_device": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p)]),
+    "adsb_debug_mlat_geometry": (C.c_int, [_P(C.c_uint32), _P(C.c_uint32)]),
     "adsb_track_device": (C.c_int, [C.c_void_p, C.c_double]),
     "adsb_fetch_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t,
                                    _P(C.c_size_t)]),
@@ -428,6 +478,8 @@ PROTOTYPES = {
                                        _P(AdsbWireInHeader)]),
     "adsb_host_correlate": (C.c_int, [_P(AdsbCorrelateCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
                                       C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p]),
+    "adsb_host_multilaterate": (C.c_int, [_P(AdsbMlatCfg), C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, _P(AdsbMlatHeader)]),
     "adsb_host_fix_of": (C.c_int, [_P(AdsbSite), _P(C.c_uint8 * 14), C.c_double, _P(AdsbFix), _P(C.c_uint32)]),
 }
 

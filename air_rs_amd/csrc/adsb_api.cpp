@@ -78,6 +78,13 @@ extern "C" void adsb_destroy(adsb_ctx *c)
     (void)hipFree(c->wof_levels);
     (void)hipFree(c->trk_u32);
     (void)hipFree(c->corr.block);
+    (void)hipFree(c->mlat.fixes);
+    (void)hipFree(c->mlat.temp);
+    (void)hipFree(c->mlat.hdr);
+    (void)hipFree(c->mlat.stations);
+    (void)hipFree(c->mlat.in_msgs);
+    (void)hipFree(c->mlat.in_recs);
+    (void)hipFree(c->mlat.in_rx);
     (void)hipFree(c->win.block);
     (void)hipFree(c->win.in);
     (void)hipFree(c->trk_temp);

@@ -104,6 +104,7 @@ static int corr_run(adsb_ctx *c, const adsb_correlate_cfg &cfg, const adsb_frame
     }
     HIPCHK(adsbk::launch_correlate(c->aux, a));
     k.done = true;
+    k.n = a.n;
     return ADSB_OK;
 }
 

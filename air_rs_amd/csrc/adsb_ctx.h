@@ -72,7 +72,23 @@ struct adsb_ctx {
         adsb_frame *in_frames = nullptr;             // [frames]
         adsb_frame_level *in_levels = nullptr;       // [frames]
         bool done = false;          // a correlate call has been enqueued
+        uint32_t n = 0;             // receptions of the last call's list (what adsb_multilaterate sizes its grid by)
     } corr;
+    // multilaterate (adsb_mlat.hip), allocated on first adsb_multilaterate / adsb_multilaterate_of and grown on demand:
+    // the fixes, the header, the stations, the reduction's temporary storage, and device copies of host lists
+    struct Mlat {
+        adsb_mlat_fix *fixes = nullptr;      // [msgs]
+        size_t msgs = 0;
+        void *temp = nullptr;
+        size_t temp_bytes = 0;
+        adsb_mlat_header *hdr = nullptr;
+        adsbk::MlatStation *stations = nullptr; // [256]
+        adsb_message *in_msgs = nullptr;     // [in_msgs_n], of a host list
+        adsb_reception *in_recs = nullptr;   // [in_recs_n]
+        adsb_wire_rx *in_rx = nullptr;       // [in_rx_n]
+        size_t in_msgs_n = 0, in_recs_n = 0, in_rx_n = 0;
+        bool done = false;          // a multilaterate call has been enqueued
+    } mlat;
     // wire input (adsb_wire_in.hip), allocated on first adsb_wire_in_of and grown on demand: one hipMalloc carved into the
     // kernels' arrays and the results, and the device copy of a host input
     struct WireIn {

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/adsb_hip.h"
+#include "adsb_mlat.h"
 
 namespace adsbk {
 
@@ -257,6 +258,27 @@ struct CorrArgs {
 };
 size_t corr_temp_bytes(size_t n);
 hipError_t launch_correlate(hipStream_t s, const CorrArgs &a);
+
+// transmitter positions from correlated receptions (adsb_mlat.hip; adsb_mlat.h has the solver's text)
+constexpr uint32_t kMlatBlock = 256;                          // threads per workgroup of mlat_solve
+constexpr uint32_t kMlatPerBlock = kMlatBlock / kMlatLanes;   // messages per workgroup: 16 lanes each
+struct MlatArgs {
+    const adsb_message *msgs;        // [n_msgs]
+    const adsb_reception *recs;      // [n_recs]
+    const adsb_wire_rx *rx;          // [n_rx] or null (TIME_RECEPTION)
+    const uint64_t *counts_dev;      // null, or {n_msgs, n_recs} in device memory (a correlate header): the counts below
+                                     // are then upper bounds that size the grid, and these the lists' lengths
+    uint32_t n_msgs, n_recs, n_rx, n_receivers;
+    const MlatStation *stations;     // [n_receivers]
+    MlatParams p;
+    void *temp;
+    size_t temp_bytes;               // >= mlat_temp_bytes(n_msgs)
+    // results
+    adsb_mlat_fix *fixes;            // [n_msgs]
+    adsb_mlat_header *hdr;
+};
+size_t mlat_temp_bytes(size_t n_msgs);
+hipError_t launch_mlat(hipStream_t s, const MlatArgs &a);
 
 // tracker + CPR position decode over an ordered frame list (adsb_track.hip)
 // One aircraft of a persistent table (adsb_track_table_*): the public record plus the last even and the last odd

@@ -260,6 +260,60 @@ def host_correlate(frames, counts, window, sample_base=None, levels=None):
     return msgs[:n_msgs.value].copy(), fout[:n_msgs.value].copy(), recs[:n].copy()
 
 
+MLAT_FIX_DTYPE, MLAT_RECEIVER_DTYPE = L.MLAT_FIX_DTYPE, L.MLAT_RECEIVER_DTYPE
+MLAT_HEADER_DTYPE = np.dtype([(k, "<u8") for k in ("n_messages", "n_attempted", "n_valid", "flags")])
+assert MLAT_HEADER_DTYPE.itemsize == C.sizeof(L.AdsbMlatHeader) == 32
+MLAT_TIME_SOURCES = {"reception": L.ADSB_MLAT_TIME_RECEPTION, "ticks": L.ADSB_MLAT_TIME_TICKS}
+
+
+def _mlat_cfg(time_source="reception", seconds_per_tick=0.0, use_altitude=False, min_receivers=0, max_iterations=0,
+              step_tol_m=0.0, max_residual_m=0.0, max_range_m=0.0, default_altitude_m=0.0):
+    src = MLAT_TIME_SOURCES[time_source] if isinstance(time_source, str) else int(time_source)
+    return L.AdsbMlatCfg(src, L.ADSB_MLAT_USE_ALTITUDE if use_altitude else 0, int(min_receivers), int(max_iterations),
+                         float(seconds_per_tick), float(step_tol_m), float(max_residual_m), float(max_range_m),
+                         float(default_altitude_m), 0)
+
+
+def _mlat_receivers(receivers):
+    """An MLAT_RECEIVER_DTYPE array of such an array or of (latitude, longitude, height_m[, clock_offset_s = 0])
+    tuples."""
+    if isinstance(receivers, np.ndarray) and receivers.dtype == MLAT_RECEIVER_DTYPE:
+        return np.ascontiguousarray(receivers).reshape(-1)
+    out = np.zeros(len(receivers), dtype=MLAT_RECEIVER_DTYPE)
+    for k, r in enumerate(receivers):
+        r = tuple(r)
+        out[k] = (r[0], r[1], r[2], r[3] if len(r) > 3 else 0.0)
+    return out
+
+
+def _mlat_list(arr, dtype):
+    """(kept alive, pointer or None, count) of a host array, None, or a (device pointer, count) pair."""
+    if arr is None:
+        return None, None, 0
+    if isinstance(arr, tuple):
+        return None, (int(arr[0]) if arr[1] else None), int(arr[1])
+    return _host_list(arr, dtype)
+
+
+def host_multilaterate(receivers, messages, receptions, rx=None, **cfg):
+    """adsb_host_multilaterate, the CPU mirror of AdsbDemod.multilaterate_of: (MLAT_FIX_DTYPE fixes, one per message;
+    the MLAT_HEADER_DTYPE record) of a correlate result (MESSAGE_DTYPE, RECEPTION_DTYPE) heard by `receivers`
+    (MLAT_RECEIVER_DTYPE, or (latitude, longitude, height_m[, clock_offset_s]) tuples).  rx: the WIRE_RX_DTYPE records of
+    the correlated list, for time_source="ticks".  Keywords: time_source ("reception" / "ticks"), seconds_per_tick,
+    use_altitude, min_receivers, max_iterations, step_tol_m, max_residual_m, max_range_m, default_altitude_m; 0 takes
+    each default.  Needs no device."""
+    rcv = _mlat_receivers(receivers)
+    c = _mlat_cfg(**cfg)
+    msgs, mptr, nm = _host_list(messages, MESSAGE_DTYPE)
+    recs, rptr, nr = _host_list(receptions, RECEPTION_DTYPE)
+    rxa, xptr, nx = _mlat_list(rx, WIRE_RX_DTYPE)
+    fixes = np.zeros(max(nm, 1), dtype=MLAT_FIX_DTYPE)
+    hdr = L.AdsbMlatHeader()
+    L.check(L.load().adsb_host_multilaterate(C.byref(c), rcv.ctypes.data if len(rcv) else None, len(rcv), mptr, nm, rptr,
+                                             nr, xptr, nx, fixes.ctypes.data, C.byref(hdr)), "adsb_host_multilaterate")
+    return fixes[:nm].copy(), np.frombuffer(bytes(hdr), dtype=MLAT_HEADER_DTYPE)[0]
+
+
 def level_dbfs(sample_type, total, n_samples):
     """adsb_level_dbfs: 10 log10(total / n_samples / full scale) -- a LEVEL_DTYPE sum as mean power in dBFS (-inf for
     0).  level_dbfs(st, rec["signal_sum"], LEVEL_PULSE_SAMPLES), level_dbfs(st, rec["noise_sum"], LEVEL_QUIET_SAMPLES)."""
@@ -714,6 +768,55 @@ class AdsbDemod:
         L.check(self._lib.adsb_correlated_device(self._h, C.byref(m), C.byref(f), C.byref(r), C.byref(h)),
                 "adsb_correlated_device")
         return m.value, f.value, r.value, h.value
+
+    def multilaterate_async(self, receivers, rx=None, **cfg):
+        """adsb_multilaterate alone: the last correlate call's result, solved where it lies on the device; nothing is
+        read back.  rx: None, a WIRE_RX_DTYPE array (host) or a device pointer (wire_in_device()[1]) with one record per
+        frame of the correlated list.  See host_multilaterate for receivers and the keywords."""
+        rcv = _mlat_receivers(receivers)
+        c = _mlat_cfg(**cfg)
+        keep, xptr = (None, rx) if isinstance(rx, int) else _mlat_list(rx, WIRE_RX_DTYPE)[:2]
+        L.check(self._lib.adsb_multilaterate(self._h, C.byref(c), rcv.ctypes.data if len(rcv) else None, len(rcv), xptr),
+                "adsb_multilaterate")
+
+    def multilaterate(self, receivers, rx=None, **cfg):
+        """Where each message of the last correlate call was sent from -> (MLAT_FIX_DTYPE fixes, header).  See
+        multilaterate_async."""
+        self.multilaterate_async(receivers, rx, **cfg)
+        return self.fetch_mlat()
+
+    def multilaterate_of_async(self, receivers, messages, receptions, rx=None, **cfg):
+        """adsb_multilaterate_of alone: any correlate result, each list a host array or a (device pointer, count)
+        pair; enqueues and returns once the host arrays are copied."""
+        rcv = _mlat_receivers(receivers)
+        c = _mlat_cfg(**cfg)
+        msgs, mptr, nm = _mlat_list(messages, MESSAGE_DTYPE)
+        recs, rptr, nr = _mlat_list(receptions, RECEPTION_DTYPE)
+        rxa, xptr, nx = _mlat_list(rx, WIRE_RX_DTYPE)
+        L.check(self._lib.adsb_multilaterate_of(self._h, C.byref(c), rcv.ctypes.data if len(rcv) else None, len(rcv), mptr,
+                                                nm, rptr, nr, xptr, nx), "adsb_multilaterate_of")
+
+    def multilaterate_of(self, receivers, messages, receptions, rx=None, **cfg):
+        """adsb_multilaterate_of -> (MLAT_FIX_DTYPE fixes, header).  See host_multilaterate, its CPU mirror."""
+        self.multilaterate_of_async(receivers, messages, receptions, rx, **cfg)
+        return self.fetch_mlat()
+
+    def fetch_mlat(self):
+        """adsb_fetch_mlat: waits for the last multilaterate call -> (fixes, the MLAT_HEADER_DTYPE record)."""
+        hdr, got = L.AdsbMlatHeader(), C.c_size_t()
+        rc = self._lib.adsb_fetch_mlat(self._h, None, 0, C.byref(got), C.byref(hdr))   # the count first
+        if rc not in (L.ADSB_OK, L.ADSB_E_ARG):
+            L.check(rc, "adsb_fetch_mlat")
+        n = int(hdr.n_messages)
+        fixes = np.zeros(max(n, 1), dtype=MLAT_FIX_DTYPE)
+        L.check(self._lib.adsb_fetch_mlat(self._h, fixes.ctypes.data, n, C.byref(got), C.byref(hdr)), "adsb_fetch_mlat")
+        return fixes[:got.value].copy(), np.frombuffer(bytes(hdr), dtype=MLAT_HEADER_DTYPE)[0]
+
+    def mlat_device(self):
+        """adsb_mlat_device: device addresses (fixes, header); no synchronisation."""
+        f, h = C.c_void_p(), C.c_void_p()
+        L.check(self._lib.adsb_mlat_device(self._h, C.byref(f), C.byref(h)), "adsb_mlat_device")
+        return f.value, h.value
 
     def set_result_target(self, dev_ptr, nbytes):
         """Next launches write [32-byte header | frames] straight into caller-owned HBM (None: reset)."""

@@ -517,6 +517,141 @@ int adsb_correlated_device(adsb_ctx *ctx, const adsb_message **msgs_dev, const a
 int adsb_debug_correlate_geometry(uint32_t *threads_per_block);
 
 /*
+ * Multilaterate: where each correlated message was sent from, solved from the times its receivers heard it.  One small
+ * non-linear least-squares problem per message, all messages of a list in one kernel; f64; stateless.
+ *   INPUT  a correlate result msgs[M] / recs[N]; adsb_mlat_receiver receivers[R], 1 <= R <= 256, WGS84 degrees and
+ *     metres above the ellipsoid, with each receiver's clock offset in seconds (what its clock shows minus true time);
+ *     optionally adsb_wire_rx rx[n_rx], the wire-input records of the list that was correlated, indexed by
+ *     adsb_reception.frame; an adsb_mlat_cfg.
+ *   TIME  cfg.time_source = ADSB_MLAT_TIME_RECEPTION takes adsb_reception.time, in units of cfg.seconds_per_tick (> 0;
+ *     for this project's own channels the sample period).  ADSB_MLAT_TIME_TICKS takes rx[frame].ticks, the raw 48-bit
+ *     timestamp that wire input keeps at full resolution, in units of cfg.seconds_per_tick (0: 1 / 12e6).  Only
+ *     differences against the first used reception are taken, as integers before anything becomes a double:
+ *     RECEPTION: (int64)(t_i - t_0) of the uint64 difference; TICKS: (t_i - t_0) mod 2^48, sign-extended into
+ *     [-2^47, 2^47).  The measured range difference of reception i is
+ *       rho_i = c x ((double)dticks_i x seconds_per_tick - (clock_offset_s[r_i] - clock_offset_s[r_0]))
+ *     with c = ADSB_MLAT_C, light in air.
+ *   USED  Inside a message (receptions are in (T, j) order) reception k = 0, 1, ... is USED iff no reception k' < k of
+ *     the message has the same receiver: one time per receiver, the earliest.  Reception 0 is always used and is "the
+ *     first used reception" above.  A message with more than ADSB_MLAT_MAX_RECEPTIONS receptions is not attempted
+ *     (TOO_MANY).  need = max(cfg.min_receivers, floor) with floor = 3 for a message with an altitude and 4 without
+ *     (min_receivers = 0: the floor alone); fewer used receptions than need: not attempted (TOO_FEW).
+ *   ALTITUDE  With ADSB_MLAT_USE_ALTITUDE in cfg.flags, a message with bytes[0] >> 3 in {17, 18}, type code (ME bits
+ *     0-4) 9..18, a non-zero 12-bit altitude code (ME bits 8-19) and its Q bit (ME bit 15) set HAS AN ALTITUDE:
+ *     (25 N - 1000) ft x 0.3048 m, N = the code's other 11 bits.  It adds one equation, h(p) - altitude = 0.
+ *   MODEL  Unknowns (x, y, z, d): ECEF metres and d = c x (emission time - time of the first used reception).  Residual
+ *     of used reception i at station s_i: |p - s_i| + d - rho_i; its Jacobian row is ((p - s_i) / |p - s_i|, 1), the
+ *     unit vector taken as 0 when |p - s_i| = 0.  h(p) is Bowring's closed form with TWO refinement steps:
+ *     P = sqrt(x^2 + y^2), beta = atan2(a z, b P); twice: phi = atan2(z + e'^2 b sin^3 beta, P - e^2 a cos^3 beta),
+ *     beta = atan2(b sin phi, a cos phi); h = P cos phi + z sin phi - a sqrt(1 - e^2 sin^2 phi); lambda from x / P and
+ *     y / P (P = 0: cos lambda = 1).  The altitude row's Jacobian is the ellipsoid normal (cos phi cos lambda,
+ *     cos phi sin lambda, sin phi, 0).  a = 6378137, f = 1 / 298.257223563.
+ *   SUMS  The cost is the sum of squared residuals.  Every sum over receptions (the 10 entries of JtJ, the 4 of Jtr,
+ *     the cost; the 3 coordinate sums of the centroid) is 16 partial sums folded in a butterfly: partial l adds the
+ *     terms of the used receptions k = l (mod 16) in ascending k, starting from 0; then four rounds v[l] = v[l] +
+ *     v[l ^ m] for m = 8, 4, 2, 1.  The altitude row is added to the folded sums last.  All f64, contraction off.
+ *   SOLVER  Levenberg-Marquardt on the 4 x 4 normal equations: (JtJ + lambda diag(JtJ)) delta = -Jtr, lambda from 1e-3,
+ *     divided by 10 after an accepted step and multiplied by 10 after a rejected one, kept inside [1e-12, 1e12].  A
+ *     step is accepted iff the cost at p + delta is <= the cost at p.  A stage is converged when a step's position part
+ *     is shorter than cfg.step_tol_m (0: 0.01 m), accepted or not; it takes at most cfg.max_iterations steps (0: 24; at
+ *     most 1000).  The linear solve is an L D Lt factorisation in the order x, y, z, d without pivoting; a pivot that
+ *     is not greater than 1e-12 x its diagonal entry gives SINGULAR and ends the solve.
+ *     Stage 1 holds the height: the altitude equation with the message's altitude, or with cfg.default_altitude_m
+ *     (0: 10000 m) when it has none.  It starts from the centroid of the used receivers' ECEF positions moved along its
+ *     own ellipsoid normal to that height, with d = -|p - s_0|.  Stage 2 starts from stage 1's result (converged or
+ *     not) and solves the message's real equations; lambda starts again.  A message with an altitude runs stage 1 only.
+ *     Ground receivers are nearly coplanar, and a free solve started from the centroid falls through their plane into
+ *     the mirror solution for one emitter in seven; started from the height-held solution it does not.
+ *   OUTPUT  adsb_mlat_fix fixes[M], index for index with msgs[].  latitude / longitude in degrees, height_m above the
+ *     ellipsoid, time_s = d / c (emission relative to the first used reception's true time), residual_rms_m =
+ *     sqrt(cost / equations) of the last stage, n_used, iterations (steps of both stages), and the dilutions from the
+ *     position block of the inverse of the last stage's undamped JtJ at the solution (the same factorisation and pivot
+ *     rule; SINGULAR leaves them 0): pdop = sqrt(trace), hdop / vdop after rotating the block to local east / north / up.
+ *     flags: ATTEMPTED; ALTITUDE (the message's altitude was used); CONVERGED (the last stage converged);
+ *     REJECTED_RESIDUAL (residual_rms_m > cfg.max_residual_m; 0: no limit); REJECTED_RANGE (farther from the used
+ *     receivers' centroid than cfg.max_range_m; 0: 500 km); VALID = CONVERGED and neither SINGULAR nor rejected.  A
+ *     fix that was not attempted holds its reason (TOO_FEW, TOO_MANY, BAD_INDEX), n_used where known, and zeros.
+ *     BAD_INDEX: a reception's receiver >= R, a message's receptions past recs[N], or with TICKS a frame >= n_rx; found
+ *     on the device, never read.  adsb_mlat_header { n_messages, n_attempted, n_valid, flags } comes from a reduction
+ *     over the fixes; flags has ADSB_MLAT_HDR_BAD_INDEX if any fix has BAD_INDEX.
+ * No atomics, nothing depends on scheduling: two runs give the same bytes.  The CPU mirror (adsb_host_multilaterate)
+ * evaluates the same text in the same order; what may differ is the last bit of the math library (atan2, sin, cos) in
+ * the height formula and the output conversion, and whatever device and host sqrt and division differ by.
+ */
+#define ADSB_MLAT_C (299792458.0 / 1.0003) /* m/s */
+#define ADSB_MLAT_MAX_RECEPTIONS 256
+#define ADSB_MLAT_TIME_RECEPTION 0u
+#define ADSB_MLAT_TIME_TICKS 1u
+#define ADSB_MLAT_USE_ALTITUDE 0x1u        /* adsb_mlat_cfg.flags */
+#define ADSB_MLAT_ATTEMPTED 0x1u           /* adsb_mlat_fix.flags */
+#define ADSB_MLAT_CONVERGED 0x2u
+#define ADSB_MLAT_ALTITUDE 0x4u
+#define ADSB_MLAT_TOO_FEW 0x8u
+#define ADSB_MLAT_TOO_MANY 0x10u
+#define ADSB_MLAT_SINGULAR 0x20u
+#define ADSB_MLAT_REJECTED_RESIDUAL 0x40u
+#define ADSB_MLAT_REJECTED_RANGE 0x80u
+#define ADSB_MLAT_VALID 0x100u
+#define ADSB_MLAT_BAD_INDEX 0x200u
+#define ADSB_MLAT_HDR_BAD_INDEX 0x1u       /* adsb_mlat_header.flags */
+typedef struct adsb_mlat_receiver { /* 32 bytes */
+    double latitude, longitude;   /* degrees, [-90, 90] and [-180, 180]                           */
+    double height_m;              /* above the ellipsoid, [-1000, 100000]                         */
+    double clock_offset_s;        /* what this receiver's clock shows minus true time, |.| <= 1e6 */
+} adsb_mlat_receiver;
+typedef struct adsb_mlat_cfg {      /* 64 bytes */
+    uint32_t time_source;         /* ADSB_MLAT_TIME_*                                             */
+    uint32_t flags;               /* ADSB_MLAT_USE_ALTITUDE                                       */
+    uint32_t min_receivers;       /* 0: the floor (3 with an altitude, 4 without); at most 256    */
+    uint32_t max_iterations;      /* per stage; 0: 24; at most 1000                               */
+    double   seconds_per_tick;    /* RECEPTION: > 0; TICKS: 0 = 1 / 12e6                          */
+    double   step_tol_m;          /* 0: 0.01                                                      */
+    double   max_residual_m;      /* 0: no limit                                                  */
+    double   max_range_m;         /* 0: 500e3                                                     */
+    double   default_altitude_m;  /* 0: 10000                                                     */
+    uint64_t reserved;            /* 0 */
+} adsb_mlat_cfg;
+typedef struct adsb_mlat_fix {      /* 64 bytes */
+    double   latitude, longitude; /* degrees */
+    double   height_m;
+    double   time_s;
+    float    residual_rms_m, pdop, hdop, vdop;
+    uint16_t n_used, iterations;
+    uint32_t flags;               /* ADSB_MLAT_* */
+    uint64_t reserved;            /* 0 */
+} adsb_mlat_fix;
+typedef struct adsb_mlat_header {   /* 32 bytes */
+    uint64_t n_messages, n_attempted, n_valid, flags;
+} adsb_mlat_header;
+/* The ctx's last correlate result (adsb_correlate_launch or adsb_correlate_of), solved where it lies: enqueued on the
+ * ctx's stream behind it, nothing read back.  receivers is host memory; rx (NULL with TIME_RECEPTION) is host memory or
+ * device memory of the ctx's device and holds one record per frame of the correlated list, e.g. adsb_wire_in_device's.
+ * Buffers are allocated on first use and grown when needed (may wait for earlier work): 64 bytes per message of
+ * capacity, 8 KiB of stations, the reduction's temporary storage, and copies of host lists; a ctx that never calls it
+ * allocates nothing and launches exactly the kernels it launched before.  Replaces the result of an earlier
+ * multilaterate call.  ADSB_E_ARG for a NULL ctx, cfg or receivers, n_receivers outside 1..256, a receiver or cfg value
+ * that is not finite or out of the ranges above, an unknown time_source or flag, TICKS without rx; ADSB_E_STATE before
+ * any correlate call. */
+int adsb_multilaterate(adsb_ctx *ctx, const adsb_mlat_cfg *cfg, const adsb_mlat_receiver *receivers, uint32_t n_receivers,
+                       const adsb_wire_rx *rx);
+/* Any lists: msgs[n_msgs], recs[n_recs] and rx[n_rx] (NULL / 0 with TIME_RECEPTION), each in host memory or in device
+ * memory of the ctx's device.  Asynchronous on the ctx's stream once host arrays are copied.  The errors above, and
+ * ADSB_E_ARG for NULL msgs or recs with a count > 0; ADSB_E_CAPACITY for a count >= 2^32. */
+int adsb_multilaterate_of(adsb_ctx *ctx, const adsb_mlat_cfg *cfg, const adsb_mlat_receiver *receivers,
+                          uint32_t n_receivers, const adsb_message *msgs, size_t n_msgs, const adsb_reception *recs,
+                          size_t n_recs, const adsb_wire_rx *rx, size_t n_rx);
+/* Waits and copies: fixes receives min(header.n_messages, max) records and *n (optional) that number; *header
+ * (optional) the totals whatever max.  ADSB_E_STATE before any multilaterate call; ADSB_E_ARG for a NULL ctx, NULL
+ * fixes with max > 0, or, after copying, when the header has ADSB_MLAT_HDR_BAD_INDEX. */
+int adsb_fetch_mlat(adsb_ctx *ctx, adsb_mlat_fix *fixes, size_t max, size_t *n, adsb_mlat_header *header);
+/* For device-side consumers; does not synchronise.  fixes[] and the header in device memory (each optional), valid until
+ * the next multilaterate call on this ctx and ordered on the ctx's stream behind it.  ADSB_E_STATE before any. */
+int adsb_mlat_device(adsb_ctx *ctx, const adsb_mlat_fix **fixes_dev, const void **header_dev);
+/* Lanes that share one message and messages per workgroup of the solver kernel (either may be NULL): the sizes at which
+ * it takes another path, for tests.  The result does not depend on them. */
+int adsb_debug_mlat_geometry(uint32_t *lanes_per_message, uint32_t *messages_per_block);
+
+/*
  * Tracker + global CPR position decode on the device: what the reference's display
  * threads do with every AdsbPacket, `handle_aircraft_update` (src/adsb/aircraft.rs:158-165 ->
  * Aircraft::handle_packet, aircraft.rs:48-111 -> cpr::calculate_geographic_position, cpr.rs:135-147),

@@ -150,6 +150,17 @@ int adsb_host_correlate(const adsb_correlate_cfg *cfg, const adsb_frame *frames,
                         size_t max_msgs, size_t *n_msgs, adsb_frame *frames_out, adsb_reception *recs);
 
 /*
+ * CPU mirror of adsb_multilaterate_of (adsb_hip.h, "Multilaterate"): the same fixes and header from the same program text
+ * as the device's -- the solver, and the 16 partial sums of every sum over receptions folded in the same butterfly -- on
+ * one core, no device needed.  All arrays host memory; rx / n_rx may be NULL / 0 with ADSB_MLAT_TIME_RECEPTION; fixes
+ * receives n_msgs records; *header is optional.  The same argument errors as adsb_multilaterate_of, and ADSB_E_ARG for
+ * NULL fixes with n_msgs > 0; ADSB_E_ARG after writing everything when a message has ADSB_MLAT_BAD_INDEX.
+ */
+int adsb_host_multilaterate(const adsb_mlat_cfg *cfg, const adsb_mlat_receiver *receivers, uint32_t n_receivers,
+                            const adsb_message *msgs, size_t n_msgs, const adsb_reception *recs, size_t n_recs,
+                            const adsb_wire_rx *rx, size_t n_rx, adsb_mlat_fix *fixes, adsb_mlat_header *header);
+
+/*
  * CPU mirror of the per-frame fix decode of a table or bank with a fixes reserve (adsb_hip.h, "Positions from single
  * messages"): the same program text as the device's, no device needed.  *out = the adsb_fix of an aircraft whose only
  * frame since admission is this one, heard at frame time `time` by a receiver at *site: accepted: the fix with
