@@ -1,5 +1,6 @@
-// adsb_api.cpp -- the extern "C" boundary (include/adsb_hip.h) over the gfx950 scan kernels; the tracker's part of the
-// boundary (adsb_track_*, adsb_fetch_track) is adsb_track_api.cpp.
+// adsb_api.cpp -- the extern "C" boundary (include/adsb_hip.h) over the gfx950 scan kernels: the context, the launches,
+// the fetch and the decoded fields.  Every other part of the boundary has a file of its own: adsb_track_api.cpp,
+// adsb_levels_api.cpp, adsb_wire_api.cpp, adsb_wire_in_api.cpp, adsb_correlate_api.cpp, adsb_mlat_api.cpp.
 //
 // Replaces, per received buffer, the body of the reference's thread 2 loop
 // (src/adsb.rs:95-116).  There is NO CPU fallback: without a HIP device adsb_create() fails with
@@ -17,7 +18,6 @@
 
 #include "adsb_ctx.h"
 #include "adsb_synth.h"
-#include "adsb_wire.h"
 
 using adsbk::kTile;
 using adsbk::kWindow;
@@ -53,7 +53,6 @@ extern "C" void adsb_destroy(adsb_ctx *c)
             for (auto &x : e)
                 if (x) (void)hipEventDestroy(x);
     if (c->own_aux && c->aux) (void)hipStreamSynchronize(c->aux);
-    (void)hipFree(c->staging);
     for (auto &r : c->rs) {
         (void)hipFree(r.seg);
         (void)hipFree(r.slots);
@@ -63,38 +62,11 @@ extern "C" void adsb_destroy(adsb_ctx *c)
         if (r.k_done) (void)hipEventDestroy(r.k_done);
         if (r.g_done) (void)hipEventDestroy(r.g_done);
     }
-    (void)hipFree(c->out_start);
-    (void)hipFree(c->fields);
-    (void)hipFree(c->levels);
-    (void)hipFree(c->lvof_out);
-    (void)hipFree(c->lvof_frames);
-    for (adsb_ctx::Wire *w : {&c->wire, &c->wof}) {
-        (void)hipFree(w->out);
-        (void)hipFree(w->ends);
-        (void)hipFree(w->block);
-        (void)hipFree(w->hdr);
-    }
-    (void)hipFree(c->wof_frames);
-    (void)hipFree(c->wof_levels);
-    (void)hipFree(c->trk_u32);
-    (void)hipFree(c->corr.block);
-    (void)hipFree(c->mlat.fixes);
-    (void)hipFree(c->mlat.temp);
-    (void)hipFree(c->mlat.hdr);
-    (void)hipFree(c->mlat.stations);
-    (void)hipFree(c->mlat.in_msgs);
-    (void)hipFree(c->mlat.in_recs);
-    (void)hipFree(c->mlat.in_rx);
-    (void)hipFree(c->win.block);
-    (void)hipFree(c->win.in);
-    (void)hipFree(c->trk_temp);
-    (void)hipFree(c->trk_points);
-    (void)hipFree(c->trk_aircraft);
-    (void)hipFree(c->trk_n_aircraft);
-    (void)hipFree(c->scratch);
-    (void)hipFree(c->stamps);
-    (void)hipFree(c->lb);
-    (void)hipFree(c->sm.done);
+    void *const owned[] = {c->staging, c->out_start, c->fields, c->levels, c->lvof_out.p, c->lvof_frames.p, c->wire.mem.p,
+                           c->wof.mem.p, c->wof_frames.p, c->wof_levels.p, c->corr.mem.p, c->mlat.mem.p, c->mlat.in_msgs.p,
+                           c->mlat.in_recs.p, c->mlat.in_rx.p, c->win.mem.p, c->win.in.p, c->trk_u32, c->trk_temp,
+                           c->trk_points, c->trk_aircraft, c->trk_n_aircraft, c->scratch, c->stamps, c->lb, c->sm.done};
+    for (void *p : owned) (void)hipFree(p);
     for (char *b : c->sm.blob) if (b) (void)hipHostFree(b);
     if (c->sm.in_host) (void)hipHostFree(c->sm.in_host);
     if (c->own_aux && c->aux) (void)hipStreamDestroy(c->aux);
@@ -726,287 +698,6 @@ extern "C" int adsb_fetch_fields(adsb_ctx *c, adsb_packet_fields *out, size_t ma
     if (n) HIPCHK(hipMemcpyAsync(out, c->fields, sizeof(adsb_packet_fields) * n, hipMemcpyDeviceToHost, c->aux));
     HIPCHK(hipStreamSynchronize(c->aux));
     *n_out = (size_t)n;
-    return ADSB_OK;
-}
-
-
-// ---- per-frame signal and noise power (adsb_levels.hip) ----------------------------------------------------------------
-// The levels kernel walks its frames in a grid-stride loop, one wave each: the grid is sized from the device (a few
-// waves per SIMD hide the latency of the scattered 480-byte reads), not from max_out, and never above one wave per frame.
-static uint32_t levels_grid(adsb_ctx *c, uint64_t cap)
-{
-    if (!c->levels_blocks) {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->cfg.device) != hipSuccess || cus <= 0) {
-            (void)hipGetLastError();
-            cus = 256;
-        }
-        c->levels_blocks = (uint32_t)cus * 8u; // 8 blocks of 4 waves per CU: 8 waves per SIMD
-    }
-    return (uint32_t)std::min<uint64_t>((cap + 3) / 4, c->levels_blocks);
-}
-
-extern "C" int adsb_levels_device_async(adsb_ctx *c)
-{
-    if (!c) return ADSB_E_ARG;
-    if (!c->launched) return ADSB_E_STATE;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    if (!c->levels && hipMalloc((void **)&c->levels, sizeof(adsb_frame_level) * (size_t)c->cfg.max_out) != hipSuccess) {
-        (void)hipGetLastError();
-        return ADSB_E_NOMEM;
-    }
-    adsbk::LevelsArgs a{};
-    a.iq = c->last_iq;
-    a.n_samples = c->last_samples;
-    a.channel_stride = c->last_stride;
-    a.offset_base = c->last_base;
-    a.frames = c->last_out;
-    a.hdr = c->rs[c->last].hdr;
-    a.cap = c->last_cap;
-    a.n_channels = c->last_channels;
-    a.chan_prefix = c->rs[c->last].chan_prefix;
-    a.out = c->levels;
-    // same stream as the ordering pass, so it sees the finished list and header
-    HIPCHK(adsbk::launch_frame_levels(c->aux, c->cfg.sample_type, a, levels_grid(c, a.cap)));
-    c->levels_current = true;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_levels_device(adsb_ctx *c, const adsb_frame_level **levels_dev)
-{
-    if (!c || !levels_dev) return ADSB_E_ARG;
-    *levels_dev = c->levels;
-    return c->levels ? ADSB_OK : ADSB_E_STATE;
-}
-
-extern "C" int adsb_fetch_levels(adsb_ctx *c, adsb_frame_level *out, size_t max_out, size_t *n_out)
-{
-    if (!c || !n_out || (!out && max_out)) return ADSB_E_ARG;
-    if (!c->launched || !c->levels || !c->levels_current) return ADSB_E_STATE;
-    int rc = sync_header(c);
-    if (rc != ADSB_OK) return rc;
-    // the wait found holes in the list and rebuilt it (slot-pool overflow): the levels enqueued before are of the list
-    // with holes.  Again, for the rebuilt one (the host has waited for the rebuild).
-    if (!c->levels_current && (rc = adsb_levels_device_async(c)) != ADSB_OK) return rc;
-    uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
-    if (n > max_out) n = max_out;
-    if (n) HIPCHK(hipMemcpyAsync(out, c->levels, sizeof(adsb_frame_level) * n, hipMemcpyDeviceToHost, c->aux));
-    HIPCHK(hipStreamSynchronize(c->aux));
-    *n_out = (size_t)n;
-    return ADSB_OK;
-}
-
-static bool levels_in_device_memory(const adsb_ctx *c, const void *p)
-{
-    hipPointerAttribute_t at{};
-    const bool yes = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice &&
-                     at.device == c->cfg.device;
-    (void)hipGetLastError(); // a plain host pointer is an error to the query: do not leave it to the launches after it
-    return yes;
-}
-
-template <typename T>
-static int grow_device(T **p, size_t *have, size_t want)
-{
-    if (*have >= want) return ADSB_OK;
-    (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    if (hipMalloc((void **)p, sizeof(T) * want) != hipSuccess) {
-        (void)hipGetLastError();
-        return ADSB_E_NOMEM;
-    }
-    *have = want;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_levels_of(adsb_ctx *c, const void *iq_dev, size_t n_samples, uint64_t first_sample_index,
-                              const adsb_frame *frames, size_t n, adsb_frame_level *out)
-{
-    if (!c || !iq_dev || ((!frames || !out) && n)) return ADSB_E_ARG;
-    if ((uintptr_t)iq_dev & (c->bps - 1u)) return ADSB_E_ARG;
-    if (n > 0xFFFFFFFFull) return ADSB_E_CAPACITY;
-    if (n == 0) return ADSB_OK;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    HIPCHK(hipStreamSynchronize(c->aux)); // an earlier call's kernel may still read the scratch that is about to grow
-    int rc = grow_device(&c->lvof_out, &c->lvof_out_n, n);
-    if (rc != ADSB_OK) return rc;
-    const adsb_frame *list = frames;
-    if (!levels_in_device_memory(c, frames)) {
-        if ((rc = grow_device(&c->lvof_frames, &c->lvof_frames_n, n)) != ADSB_OK) return rc;
-        HIPCHK(hipMemcpyAsync(c->lvof_frames, frames, sizeof(adsb_frame) * n, hipMemcpyHostToDevice, c->aux));
-        list = c->lvof_frames;
-    }
-    adsbk::LevelsArgs a{};
-    a.iq = iq_dev;
-    a.n_samples = n_samples;
-    a.channel_stride = n_samples;
-    a.offset_base = first_sample_index;
-    a.frames = list;
-    a.hdr = nullptr;
-    a.cap = (uint32_t)n;
-    a.n_channels = 1;
-    a.chan_prefix = nullptr;
-    a.out = c->lvof_out;
-    HIPCHK(adsbk::launch_frame_levels(c->aux, c->cfg.sample_type, a, levels_grid(c, n)));
-    HIPCHK(hipMemcpyAsync(out, c->lvof_out, sizeof(adsb_frame_level) * n, hipMemcpyDeviceToHost, c->aux));
-    HIPCHK(hipStreamSynchronize(c->aux));
-    return ADSB_OK;
-}
-
-// ---- wire output: Beast binary / AVR text (adsb_wire.hip) ---------------------------------------------------------------
-static int wire_reserve(adsb_ctx::Wire *w, size_t frames)
-{
-    if (frames * (uint64_t)adsbk::kWireMaxBytes > 0xFFFFFFFFull) return ADSB_E_CAPACITY; // ends[] are 32 bits wide
-    if (w->frames >= frames && w->hdr) return ADSB_OK;
-    (void)hipFree(w->out);
-    (void)hipFree(w->ends);
-    (void)hipFree(w->block);
-    (void)hipFree(w->hdr);
-    *w = adsb_ctx::Wire{};
-    const size_t f = std::max<size_t>(frames, 1);
-    if (hipMalloc((void **)&w->out, f * adsbk::kWireMaxBytes) != hipSuccess ||
-        hipMalloc((void **)&w->ends, f * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&w->block, (size_t)adsbk::wire_blocks(f) * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&w->hdr, 2 * sizeof(uint64_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(w->out);
-        (void)hipFree(w->ends);
-        (void)hipFree(w->block);
-        (void)hipFree(w->hdr);
-        *w = adsb_ctx::Wire{};
-        return ADSB_E_NOMEM;
-    }
-    w->frames = frames;
-    return ADSB_OK;
-}
-
-static adsbk::WireArgs wire_args(const adsb_ctx *c, const adsb_ctx::Wire &w, const adsb_wire_cfg &cfg)
-{
-    adsbk::WireArgs a{};
-    a.format = cfg.format;
-    a.sample_type = c->cfg.sample_type;
-    a.tick_bias = cfg.tick_bias;
-    a.out = w.out;
-    a.ends = w.ends;
-    a.block = w.block;
-    a.wire_hdr = w.hdr;
-    return a;
-}
-
-static bool wire_wants_levels(const adsb_wire_cfg &cfg) { return cfg.signal != 0 && cfg.format == ADSB_WIRE_BEAST; }
-
-extern "C" int adsb_wire_device_async(adsb_ctx *c, const adsb_wire_cfg *cfg)
-{
-    if (!c || !adsbk::wire_cfg_ok(cfg)) return ADSB_E_ARG;
-    if (!c->launched) return ADSB_E_STATE;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    int rc = wire_reserve(&c->wire, (size_t)c->cfg.max_out);
-    if (rc != ADSB_OK) return rc;
-    if (wire_wants_levels(*cfg) && !c->levels_current && (rc = adsb_levels_device_async(c)) != ADSB_OK) return rc;
-    adsbk::WireArgs a = wire_args(c, c->wire, *cfg);
-    a.frames = c->last_out;
-    a.levels = wire_wants_levels(*cfg) ? c->levels : nullptr;
-    a.hdr = c->rs[c->last].hdr;
-    a.cap = c->last_cap;
-    // same stream as the ordering pass (and the levels kernel), so it sees the finished list, header and levels
-    HIPCHK(adsbk::launch_wire(c->aux, a));
-    c->wire_cfg = *cfg;
-    c->wire_current = true;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_wire_device(adsb_ctx *c, const uint8_t **bytes_dev, const uint32_t **ends_dev, const void **header_dev)
-{
-    if (!c) return ADSB_E_ARG;
-    if (bytes_dev) *bytes_dev = c->wire.out;
-    if (ends_dev) *ends_dev = c->wire.ends;
-    if (header_dev) *header_dev = c->wire.hdr;
-    return c->wire.hdr ? ADSB_OK : ADSB_E_STATE;
-}
-
-// The finished stream of `w` (n frames encoded on c->aux) to the host: the whole of it if cap holds it, else the longest
-// prefix of whole frames; ends[] takes min(n, max_ends) entries.
-static int wire_copy_out(adsb_ctx *c, const adsb_ctx::Wire &w, uint8_t *out, size_t cap, size_t *n_bytes, uint32_t *ends,
-                         size_t max_ends, size_t *n_frames)
-{
-    uint64_t hdr[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(hdr, w.hdr, sizeof(hdr), hipMemcpyDeviceToHost, c->aux));
-    HIPCHK(hipStreamSynchronize(c->aux));
-    const size_t total = (size_t)hdr[0], n = (size_t)hdr[1];
-    size_t take = total;
-    std::vector<uint32_t> all;
-    const uint32_t *host_ends = nullptr;
-    const size_t n_ends = ends ? std::min(n, max_ends) : 0;
-    if (total > cap) { // whole frames only: the last end at or below cap
-        all.resize(n);
-        HIPCHK(hipMemcpyAsync(all.data(), w.ends, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->aux));
-        HIPCHK(hipStreamSynchronize(c->aux));
-        const size_t k = (size_t)(std::upper_bound(all.begin(), all.end(), (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu)) - all.begin());
-        take = k ? all[k - 1] : 0;
-        host_ends = all.data();
-    }
-    if (take) HIPCHK(hipMemcpyAsync(out, w.out, take, hipMemcpyDeviceToHost, c->aux));
-    if (n_ends) {
-        if (host_ends) std::memcpy(ends, host_ends, sizeof(uint32_t) * n_ends);
-        else HIPCHK(hipMemcpyAsync(ends, w.ends, sizeof(uint32_t) * n_ends, hipMemcpyDeviceToHost, c->aux));
-    }
-    HIPCHK(hipStreamSynchronize(c->aux));
-    *n_bytes = total;
-    if (n_frames) *n_frames = n;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_fetch_wire(adsb_ctx *c, uint8_t *out, size_t cap, size_t *n_bytes, uint32_t *ends, size_t max_ends,
-                               size_t *n_frames)
-{
-    if (!c || !n_bytes || !n_frames || (!out && cap) || (!ends && max_ends)) return ADSB_E_ARG;
-    if (!c->launched || !c->wire.hdr || !c->wire_current) return ADSB_E_STATE;
-    int rc = sync_header(c);
-    if (rc != ADSB_OK) return rc;
-    // the wait found holes in the list and rebuilt it (slot-pool overflow): the stream enqueued before is of the list
-    // with holes.  Again, for the rebuilt one (and its levels, which the same wait marked stale).
-    if (!c->wire_current) {
-        const adsb_wire_cfg cfg = c->wire_cfg;
-        if ((rc = adsb_wire_device_async(c, &cfg)) != ADSB_OK) return rc;
-    }
-    return wire_copy_out(c, c->wire, out, cap, n_bytes, ends, max_ends, n_frames);
-}
-
-extern "C" int adsb_wire_of(adsb_ctx *c, const adsb_wire_cfg *cfg, const adsb_frame *frames, const adsb_frame_level *levels,
-                            size_t n, uint8_t *out, size_t cap, size_t *n_bytes, uint32_t *ends)
-{
-    if (!c || !adsbk::wire_cfg_ok(cfg) || !n_bytes || (!frames && n) || (!out && cap)) return ADSB_E_ARG;
-    if (n * (uint64_t)adsbk::kWireMaxBytes > 0xFFFFFFFFull) return ADSB_E_CAPACITY;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    HIPCHK(hipStreamSynchronize(c->aux)); // an earlier call's kernels may still use the scratch that is about to grow
-    int rc = wire_reserve(&c->wof, n);
-    if (rc != ADSB_OK) return rc;
-    const adsb_frame *list = frames;
-    if (n && !levels_in_device_memory(c, frames)) {
-        if ((rc = grow_device(&c->wof_frames, &c->wof_frames_n, n)) != ADSB_OK) return rc;
-        HIPCHK(hipMemcpyAsync(c->wof_frames, frames, sizeof(adsb_frame) * n, hipMemcpyHostToDevice, c->aux));
-        list = c->wof_frames;
-    }
-    const adsb_frame_level *lv = wire_wants_levels(*cfg) ? levels : nullptr;
-    if (n && lv && !levels_in_device_memory(c, lv)) {
-        if ((rc = grow_device(&c->wof_levels, &c->wof_levels_n, n)) != ADSB_OK) return rc;
-        HIPCHK(hipMemcpyAsync(c->wof_levels, lv, sizeof(adsb_frame_level) * n, hipMemcpyHostToDevice, c->aux));
-        lv = c->wof_levels;
-    }
-    adsbk::WireArgs a = wire_args(c, c->wof, *cfg);
-    a.frames = list;
-    a.levels = lv;
-    a.hdr = nullptr;
-    a.cap = (uint32_t)n;
-    HIPCHK(adsbk::launch_wire(c->aux, a));
-    return wire_copy_out(c, c->wof, out, cap, n_bytes, ends, n, nullptr);
-}
-
-extern "C" int adsb_debug_wire_geometry(uint32_t *frames_per_block, uint32_t *scan_threads)
-{
-    if (frames_per_block) *frames_per_block = adsbk::kWireBlockFrames;
-    if (scan_threads) *scan_threads = adsbk::kWireScanThreads;
     return ADSB_OK;
 }
 

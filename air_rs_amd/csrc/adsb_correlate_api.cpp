@@ -7,68 +7,42 @@
 #include <vector>
 
 #include "adsb_correlate.h"
-#include "adsb_ctx.h"
-
-static bool corr_in_device_memory(const adsb_ctx *c, const void *p)
-{
-    hipPointerAttribute_t at{};
-    const bool yes = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice &&
-                     at.device == c->cfg.device;
-    (void)hipGetLastError(); // a plain host pointer is an error to the query: do not leave it to the launches after it
-    return yes;
-}
+#include "adsb_scratch.h"
 
 // One block for `frames` receptions (at least one).  Every array starts 256-byte aligned.
 static int corr_reserve(adsb_ctx *c, size_t frames)
 {
     adsb_ctx::Corr &k = c->corr;
-    if (k.block && k.frames >= frames) return ADSB_OK;
-    if (k.block) HIPCHK(hipStreamSynchronize(c->aux)); // an earlier call's kernels may still use the block
-    (void)hipFree(k.block);
-    k = adsb_ctx::Corr{};
+    if (k.mem.p && k.frames >= frames) return ADSB_OK;
     const size_t f = std::max<size_t>(frames, 1);
     const size_t temp_bytes = adsbk::corr_temp_bytes(f);
+    k.done = false;
+    k.frames = 0;
     if (temp_bytes == 0) return ADSB_E_NOMEM;
-    size_t total = 0;
-    const auto take = [&total](size_t bytes) {
-        const size_t at = total;
-        total += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    const size_t o_t = take(8 * f), o_lo = take(8 * f), o_hi = take(8 * f), o_ht = take(8 * f);
-    const size_t o_rx = take(4 * f), o_ord = take(4 * f), o_pos = take(4 * f), o_midx = take(4 * f);
-    const size_t o_scan = take(sizeof(adsbk::CorrAgg) * f), o_temp = take(temp_bytes);
-    const size_t o_msgs = take(sizeof(adsb_message) * f), o_fout = take(sizeof(adsb_frame) * f);
-    const size_t o_recs = take(sizeof(adsb_reception) * f), o_hdr = take(2 * sizeof(uint64_t));
-    const size_t o_prefix = take(8 * (adsbk::kCorrMaxReceivers + 1)), o_base = take(8 * adsbk::kCorrMaxReceivers);
-    const size_t o_inf = take(sizeof(adsb_frame) * f), o_inl = take(sizeof(adsb_frame_level) * f);
-    char *b = nullptr;
-    if (hipMalloc((void **)&b, total) != hipSuccess) {
-        (void)hipGetLastError();
-        return ADSB_E_NOMEM;
-    }
-    k.block = b;
+    const int rc = carve_block(c, k.mem, [&k, f, temp_bytes](Carve &cv) {
+        adsbk::CorrArgs &a = k.a;
+        a.t = cv.take<uint64_t>(f);
+        a.lo = cv.take<uint64_t>(f);
+        a.hi = cv.take<uint64_t>(f);
+        a.head_t = cv.take<uint64_t>(f);
+        a.rx = cv.take<uint32_t>(f);
+        a.ord = cv.take<uint32_t>(f);
+        a.pos = cv.take<uint32_t>(f);
+        a.midx = cv.take<uint32_t>(f);
+        a.scan = cv.take<adsbk::CorrAgg>(f);
+        a.temp = cv.take<char>(temp_bytes);
+        a.temp_bytes = temp_bytes;
+        a.msgs = cv.take<adsb_message>(f);
+        a.frames_out = cv.take<adsb_frame>(f);
+        a.recs = cv.take<adsb_reception>(f);
+        a.hdr = cv.take<uint64_t>(2);
+        k.prefix = cv.take<uint64_t>(adsbk::kCorrMaxReceivers + 1);
+        k.base = cv.take<uint64_t>(adsbk::kCorrMaxReceivers);
+        k.in_frames = cv.take<adsb_frame>(f);
+        k.in_levels = cv.take<adsb_frame_level>(f);
+    });
+    if (rc != ADSB_OK) return rc;
     k.frames = f;
-    adsbk::CorrArgs &a = k.a;
-    a.t = (uint64_t *)(b + o_t);
-    a.lo = (uint64_t *)(b + o_lo);
-    a.hi = (uint64_t *)(b + o_hi);
-    a.head_t = (uint64_t *)(b + o_ht);
-    a.rx = (uint32_t *)(b + o_rx);
-    a.ord = (uint32_t *)(b + o_ord);
-    a.pos = (uint32_t *)(b + o_pos);
-    a.midx = (uint32_t *)(b + o_midx);
-    a.scan = (adsbk::CorrAgg *)(b + o_scan);
-    a.temp = b + o_temp;
-    a.temp_bytes = temp_bytes;
-    a.msgs = (adsb_message *)(b + o_msgs);
-    a.frames_out = (adsb_frame *)(b + o_fout);
-    a.recs = (adsb_reception *)(b + o_recs);
-    a.hdr = (uint64_t *)(b + o_hdr);
-    k.prefix = (uint64_t *)(b + o_prefix);
-    k.base = (uint64_t *)(b + o_base);
-    k.in_frames = (adsb_frame *)(b + o_inf);
-    k.in_levels = (adsb_frame_level *)(b + o_inl);
     return ADSB_OK;
 }
 
@@ -89,11 +63,11 @@ static int corr_run(adsb_ctx *c, const adsb_correlate_cfg &cfg, const adsb_frame
     a.prefix = k.prefix;
     a.base = sample_base ? k.base : nullptr;
     if (n) {
-        if (!corr_in_device_memory(c, frames)) {
+        if (!in_device_memory(c, frames)) {
             HIPCHK(hipMemcpyAsync(k.in_frames, frames, sizeof(adsb_frame) * n, hipMemcpyHostToDevice, c->aux));
             a.frames = k.in_frames;
         }
-        if (levels && !corr_in_device_memory(c, levels)) {
+        if (levels && !in_device_memory(c, levels)) {
             HIPCHK(hipMemcpyAsync(k.in_levels, levels, sizeof(adsb_frame_level) * n, hipMemcpyHostToDevice, c->aux));
             a.levels = k.in_levels;
         }

@@ -1,12 +1,19 @@
-// adsb_ctx.h -- what the two halves of the C boundary share: the context (adsb_api.cpp owns it; adsb_track_api.cpp
-// reads the last launch and uses the tracker scratch), the error macro, and the one function the tracker needs from
-// adsb_api.cpp.  Internal.
+// adsb_ctx.h -- what the files of the C boundary share: the context (adsb_api.cpp creates and destroys it; each feature's
+// adsb_*_api.cpp reads the last launch and keeps its own scratch in it), the error macro, and the one function the others
+// need from adsb_api.cpp.  The rule the scratch is grown by is adsb_scratch.h.  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "adsb_kernels.h"
 
 constexpr int kTimingRing = 512;
+
+// A device buffer of n records, grown on demand and never shrunk (adsb_scratch.h); the carved blocks count in bytes.
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;
+};
 
 struct adsb_ctx {
     adsb_cfg cfg{};
@@ -44,28 +51,28 @@ struct adsb_ctx {
     adsb_frame_level *levels = nullptr; // [max_out], allocated on first adsb_levels_device_async
     bool levels_current = false;    // levels[] belongs to the last launch
     // adsb_levels_of's own scratch (grown on demand): the records, and the device copy of a host frame list
-    adsb_frame_level *lvof_out = nullptr;
-    adsb_frame *lvof_frames = nullptr;
-    size_t lvof_out_n = 0, lvof_frames_n = 0;
+    DevBuf<adsb_frame_level> lvof_out;
+    DevBuf<adsb_frame> lvof_frames;
     uint32_t levels_blocks = 0;     // the levels kernel's largest grid: a few waves per SIMD of this device
-    // wire output (adsb_wire.hip), allocated on first adsb_wire_device_async: the stream, the frames' ends, one word per
-    // workgroup, the stream's header; and adsb_wire_of's own scratch (grown on demand) with the device copies of host lists
+    // wire output (adsb_wire.hip), allocated on first adsb_wire_device_async: one hipMalloc carved into the stream, the
+    // frames' ends, one word per workgroup, the stream's header; and adsb_wire_of's own scratch (grown on demand) with the
+    // device copies of host lists
     struct Wire {
+        DevBuf<char> mem;           // the four below point into it
         uint8_t *out = nullptr;     // [44 x frames]
         uint32_t *ends = nullptr;   // [frames]
         uint32_t *block = nullptr;  // [wire_blocks(frames)]
         uint64_t *hdr = nullptr;    // {n_bytes, n_frames}
         size_t frames = 0;          // what the four hold
     } wire, wof;
-    adsb_frame *wof_frames = nullptr;
-    adsb_frame_level *wof_levels = nullptr;
-    size_t wof_frames_n = 0, wof_levels_n = 0;
+    DevBuf<adsb_frame> wof_frames;
+    DevBuf<adsb_frame_level> wof_levels;
     adsb_wire_cfg wire_cfg{};       // of the last adsb_wire_device_async
     bool wire_current = false;      // wire.out belongs to the last launch
     // correlate (adsb_correlate.hip), allocated on first adsb_correlate_launch / adsb_correlate_of and grown on demand:
     // one hipMalloc carved into the kernels' arrays, the receivers' prefix and bases, and device copies of host lists
     struct Corr {
-        void *block = nullptr;      // everything in `a` below points into it
+        DevBuf<char> mem;           // everything in `a` below points into it
         size_t frames = 0;          // what it holds
         adsbk::CorrArgs a{};        // scratch and result pointers (frames, levels, n, ... are set per call)
         uint64_t *prefix = nullptr, *base = nullptr; // [257], [256]
@@ -75,30 +82,30 @@ struct adsb_ctx {
         uint32_t n = 0;             // receptions of the last call's list (what adsb_multilaterate sizes its grid by)
     } corr;
     // multilaterate (adsb_mlat.hip), allocated on first adsb_multilaterate / adsb_multilaterate_of and grown on demand:
-    // the fixes, the header, the stations, the reduction's temporary storage, and device copies of host lists
+    // one hipMalloc carved into the fixes, the reduction's temporary storage, the header and the stations; and device
+    // copies of host lists
     struct Mlat {
+        DevBuf<char> mem;                    // the four below point into it
+        size_t msgs = 0;                     // what it holds
         adsb_mlat_fix *fixes = nullptr;      // [msgs]
-        size_t msgs = 0;
         void *temp = nullptr;
         size_t temp_bytes = 0;
         adsb_mlat_header *hdr = nullptr;
         adsbk::MlatStation *stations = nullptr; // [256]
-        adsb_message *in_msgs = nullptr;     // [in_msgs_n], of a host list
-        adsb_reception *in_recs = nullptr;   // [in_recs_n]
-        adsb_wire_rx *in_rx = nullptr;       // [in_rx_n]
-        size_t in_msgs_n = 0, in_recs_n = 0, in_rx_n = 0;
+        DevBuf<adsb_message> in_msgs;        // of a host list
+        DevBuf<adsb_reception> in_recs;
+        DevBuf<adsb_wire_rx> in_rx;
         bool done = false;          // a multilaterate call has been enqueued
     } mlat;
     // wire input (adsb_wire_in.hip), allocated on first adsb_wire_in_of and grown on demand: one hipMalloc carved into the
     // kernels' arrays and the results, and the device copy of a host input
     struct WireIn {
-        void *block = nullptr;      // everything in `a` below points into it
+        DevBuf<char> mem;           // everything in `a` below points into it
         size_t bytes = 0, frames = 0; // the input length and the frames it is good for
         bool levels = false;        // ... with level records
         adsbk::WireInArgs a{};      // scratch and result pointers (the input and the cfg are set per call)
         uint32_t *ends = nullptr;   // [256]
-        uint8_t *in = nullptr;      // [in_bytes], of a host input
-        size_t in_bytes = 0;
+        DevBuf<uint8_t> in;         // of a host input, in whole dwords
         uint32_t n_streams = 0;     // of the last call
         bool with_levels = false;   // the last call wrote level records
         bool done = false;          // a call has been enqueued

@@ -1,5 +1,6 @@
-// adsb_kernels.h -- launch interface between the C-ABI layer (adsb_api.cpp, adsb_track_api.cpp) and the gfx950
-// kernels (adsb_kernels.hip, adsb_track.hip).  Internal; the public boundary is include/adsb_hip.h.
+// adsb_kernels.h -- launch interface between the C-ABI layer (adsb_api.cpp and the features' adsb_*_api.cpp) and the
+// gfx950 kernels (adsb_kernels.hip, adsb_track.hip, adsb_levels.hip, ...).  Internal; the public boundary is
+// include/adsb_hip.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -1,38 +1,33 @@
 // adsb_mlat_api.cpp -- the C boundary of multilaterate (include/adsb_hip.h, "Multilaterate"): argument checks, the
-// stations' ECEF positions (computed here, on the host, by the text the CPU mirror uses), the device buffers, the copies of
-// host lists, and the fetch.  The kernel is adsb_mlat.hip.
+// stations' ECEF positions (computed here, on the host, by the text the CPU mirror uses), the one device block the
+// results are carved from, the copies of host lists, and the fetch.  The kernel is adsb_mlat.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "adsb_ctx.h"
 #include "adsb_mlat.h"
+#include "adsb_scratch.h"
 
-static bool mlat_in_device_memory(const adsb_ctx *c, const void *p)
+// One block for the fixes of `msgs` messages (at least one).  Every array starts 256-byte aligned.
+static int mlat_reserve(adsb_ctx *c, size_t msgs)
 {
-    hipPointerAttribute_t at{};
-    const bool yes = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice &&
-                     at.device == c->cfg.device;
-    (void)hipGetLastError(); // a plain host pointer is an error to the query: do not leave it to the launches after it
-    return yes;
-}
-
-// *buf holds at least `need` records of `size` bytes afterwards (at least one); *have is what it holds.
-static int mlat_grow(adsb_ctx *c, void **buf, size_t *have, size_t need, size_t size)
-{
-    need = std::max<size_t>(need, 1);
-    if (*buf && *have >= need) return ADSB_OK;
-    if (*buf) HIPCHK(hipStreamSynchronize(c->aux)); // an earlier call's kernels may still use it
-    (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    if (hipMalloc(buf, need * size) != hipSuccess) {
-        (void)hipGetLastError();
-        *buf = nullptr;
-        return ADSB_E_NOMEM;
-    }
-    *have = need;
+    adsb_ctx::Mlat &k = c->mlat;
+    if (k.mem.p && k.msgs >= msgs) return ADSB_OK;
+    const size_t f = std::max<size_t>(msgs, 1);
+    const size_t temp_bytes = adsbk::mlat_temp_bytes(f);
+    k.done = false; // (what adsb_fetch_mlat would copy from goes)
+    k.msgs = 0;
+    if (temp_bytes == 0) return ADSB_E_NOMEM;
+    const int rc = carve_block(c, k.mem, [&k, f, temp_bytes](Carve &cv) {
+        k.fixes = cv.take<adsb_mlat_fix>(f);
+        k.temp = cv.take<char>(temp_bytes);
+        k.temp_bytes = temp_bytes;
+        k.hdr = cv.take<adsb_mlat_header>(1);
+        k.stations = cv.take<adsbk::MlatStation>(adsbk::kMlatMaxReceivers);
+    });
+    if (rc != ADSB_OK) return rc;
+    k.msgs = f;
     return ADSB_OK;
 }
 
@@ -52,15 +47,8 @@ static int mlat_run(adsb_ctx *c, const adsb_mlat_cfg &cfg, const adsb_mlat_recei
                     adsbk::MlatArgs a)
 {
     adsb_ctx::Mlat &k = c->mlat;
-    int rc = mlat_grow(c, (void **)&k.fixes, &k.msgs, a.n_msgs, sizeof(adsb_mlat_fix));
+    const int rc = mlat_reserve(c, a.n_msgs);
     if (rc != ADSB_OK) return rc;
-    const size_t temp = adsbk::mlat_temp_bytes(std::max<size_t>(k.msgs, 1));
-    if (temp == 0) return ADSB_E_NOMEM;
-    if ((rc = mlat_grow(c, &k.temp, &k.temp_bytes, temp, 1)) != ADSB_OK) return rc;
-    size_t one = k.hdr ? 1 : 0, all = k.stations ? adsbk::kMlatMaxReceivers : 0;
-    if ((rc = mlat_grow(c, (void **)&k.hdr, &one, 1, sizeof(adsb_mlat_header))) != ADSB_OK) return rc;
-    if ((rc = mlat_grow(c, (void **)&k.stations, &all, adsbk::kMlatMaxReceivers, sizeof(adsbk::MlatStation))) != ADSB_OK)
-        return rc;
     std::vector<adsbk::MlatStation> st(n_receivers);
     for (uint32_t r = 0; r < n_receivers; ++r) st[r] = adsbk::mlat_station_of(receivers[r]);
     HIPCHK(hipMemcpyAsync(k.stations, st.data(), sizeof(adsbk::MlatStation) * n_receivers, hipMemcpyHostToDevice, c->aux));
@@ -77,19 +65,6 @@ static int mlat_run(adsb_ctx *c, const adsb_mlat_cfg &cfg, const adsb_mlat_recei
     return ADSB_OK;
 }
 
-// dst (grown to n records) receives the host list src; *use = where the kernel reads the list
-template <class T>
-static int mlat_stage_list(adsb_ctx *c, const T *src, size_t n, T **dst, size_t *have, const T **use)
-{
-    *use = src;
-    if (!n || mlat_in_device_memory(c, src)) return ADSB_OK;
-    const int rc = mlat_grow(c, (void **)dst, have, n, sizeof(T));
-    if (rc != ADSB_OK) return rc;
-    HIPCHK(hipMemcpyAsync(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice, c->aux));
-    *use = *dst;
-    return ADSB_OK;
-}
-
 extern "C" int adsb_multilaterate_of(adsb_ctx *c, const adsb_mlat_cfg *cfg, const adsb_mlat_receiver *receivers,
                                      uint32_t n_receivers, const adsb_message *msgs, size_t n_msgs,
                                      const adsb_reception *recs, size_t n_recs, const adsb_wire_rx *rx, size_t n_rx)
@@ -102,9 +77,9 @@ extern "C" int adsb_multilaterate_of(adsb_ctx *c, const adsb_mlat_cfg *cfg, cons
     HIPCHK(hipSetDevice(c->cfg.device));
     adsb_ctx::Mlat &k = c->mlat;
     adsbk::MlatArgs a{};
-    if ((rc = mlat_stage_list(c, msgs, n_msgs, &k.in_msgs, &k.in_msgs_n, &a.msgs)) != ADSB_OK) return rc;
-    if ((rc = mlat_stage_list(c, recs, n_recs, &k.in_recs, &k.in_recs_n, &a.recs)) != ADSB_OK) return rc;
-    if ((rc = mlat_stage_list(c, rx, n_rx, &k.in_rx, &k.in_rx_n, &a.rx)) != ADSB_OK) return rc;
+    if ((rc = stage_list(c, msgs, n_msgs, k.in_msgs, &a.msgs)) != ADSB_OK) return rc;
+    if ((rc = stage_list(c, recs, n_recs, k.in_recs, &a.recs)) != ADSB_OK) return rc;
+    if ((rc = stage_list(c, rx, n_rx, k.in_rx, &a.rx)) != ADSB_OK) return rc;
     a.n_msgs = (uint32_t)n_msgs;
     a.n_recs = (uint32_t)n_recs;
     a.n_rx = (uint32_t)n_rx;
@@ -127,7 +102,7 @@ extern "C" int adsb_multilaterate(adsb_ctx *c, const adsb_mlat_cfg *cfg, const a
     a.counts_dev = corr.a.hdr;
     a.n_msgs = a.n_recs = corr.n;
     if (rx) {
-        if ((rc = mlat_stage_list(c, rx, (size_t)corr.n, &k.in_rx, &k.in_rx_n, &a.rx)) != ADSB_OK) return rc;
+        if ((rc = stage_list(c, rx, (size_t)corr.n, k.in_rx, &a.rx)) != ADSB_OK) return rc;
         a.n_rx = corr.n;
     }
     return mlat_run(c, *cfg, receivers, n_receivers, a);

@@ -12,8 +12,8 @@
 #include <new>
 #include <vector>
 
-#include "adsb_ctx.h"
 #include "adsb_fix.h"
+#include "adsb_scratch.h"
 
 using adsbk::TrackKind;
 using adsbk::TrackRecord;
@@ -259,15 +259,6 @@ static int store_created(S *s, bool allocated, void (*destroy)(S *), S **out)
     }
     *out = s;
     return ADSB_OK;
-}
-
-static bool in_device_memory(const adsb_ctx *c, const void *p)
-{
-    hipPointerAttribute_t at{};
-    const bool yes = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice &&
-                     at.device == c->cfg.device;
-    (void)hipGetLastError(); // a plain host pointer is an error to the query: do not leave it to the launches after it
-    return yes;
 }
 
 // Host frames through the pinned staging, so the caller's array is free when the update returns.  The caller has waited

@@ -6,69 +6,41 @@
 #include <algorithm>
 #include <vector>
 
-#include "adsb_ctx.h"
+#include "adsb_scratch.h"
 #include "adsb_wire_in.h"
-
-static bool win_in_device_memory(const adsb_ctx *c, const void *p)
-{
-    hipPointerAttribute_t at{};
-    const bool yes = hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeDevice &&
-                     at.device == c->cfg.device;
-    (void)hipGetLastError(); // a plain host pointer is an error to the query: do not leave it to the launches after it
-    return yes;
-}
 
 // One block for an input of `bytes` bytes and `frames` kept frames.  Every array starts 256-byte aligned.
 static int win_reserve(adsb_ctx *c, size_t bytes, size_t frames, bool levels)
 {
     adsb_ctx::WireIn &k = c->win;
-    if (k.block && k.bytes >= bytes && k.frames >= frames && (k.levels || !levels)) return ADSB_OK;
-    if (k.block) HIPCHK(hipStreamSynchronize(c->aux)); // an earlier call's kernels may still use the block
+    if (k.mem.p && k.bytes >= bytes && k.frames >= frames && (k.levels || !levels)) return ADSB_OK;
     bytes = std::max(bytes, k.bytes);
     frames = std::max(frames, k.frames);
     levels = levels || k.levels;
-    (void)hipFree(k.block);
-    k.block = nullptr;
     k.bytes = k.frames = 0;
     k.levels = k.done = false;
     const size_t f = std::max<size_t>(frames, 1);
     const size_t spans = (size_t)adsbk::wire_in_spans((uint64_t)bytes + 3) + 1; // whatever the input's alignment
-    size_t total = 0;
-    const auto take = [&total](size_t n) {
-        const size_t at = total;
-        total += (n + 255) & ~(size_t)255;
-        return at;
-    };
-    const size_t o_last = take(4 * spans), o_carry = take(8 * spans), o_tally = take(sizeof(adsbk::WireInTally) * spans);
-    const size_t o_inc = take(4 * adsbk::kWireInMaxStreams), o_tail = take(4 * adsbk::kWireInMaxStreams);
-    const size_t o_ends = take(4 * adsbk::kWireInMaxStreams);
-    const size_t o_frames = take(sizeof(adsb_frame) * f), o_rx = take(sizeof(adsb_wire_rx) * f);
-    const size_t o_levels = take(levels ? sizeof(adsb_frame_level) * f : 0);
-    const size_t o_counts = take(8 * adsbk::kWireInMaxStreams), o_consumed = take(8 * adsbk::kWireInMaxStreams);
-    const size_t o_hdr = take(sizeof(adsb_wire_in_header));
-    char *b = nullptr;
-    if (hipMalloc((void **)&b, total) != hipSuccess) {
-        (void)hipGetLastError();
-        return ADSB_E_NOMEM;
-    }
-    k.block = b;
+    const int rc = carve_block(c, k.mem, [&k, f, spans, levels](Carve &cv) {
+        adsbk::WireInArgs &a = k.a;
+        a = adsbk::WireInArgs{};
+        a.last = cv.take<uint32_t>(spans);
+        a.carry = cv.take<uint64_t>(spans);
+        a.tally = cv.take<adsbk::WireInTally>(spans);
+        a.inc = cv.take<uint32_t>(adsbk::kWireInMaxStreams);
+        a.tail = cv.take<uint32_t>(adsbk::kWireInMaxStreams);
+        k.ends = cv.take<uint32_t>(adsbk::kWireInMaxStreams);
+        a.frames = cv.take<adsb_frame>(f);
+        a.rx = cv.take<adsb_wire_rx>(f);
+        a.levels = levels ? cv.take<adsb_frame_level>(f) : nullptr;
+        a.counts = cv.take<uint64_t>(adsbk::kWireInMaxStreams);
+        a.consumed = cv.take<uint64_t>(adsbk::kWireInMaxStreams);
+        a.hdr = cv.take<adsb_wire_in_header>(1);
+    });
+    if (rc != ADSB_OK) return rc;
     k.bytes = bytes;
     k.frames = frames;
     k.levels = levels;
-    adsbk::WireInArgs &a = k.a;
-    a = adsbk::WireInArgs{};
-    a.last = (uint32_t *)(b + o_last);
-    a.carry = (uint64_t *)(b + o_carry);
-    a.tally = (adsbk::WireInTally *)(b + o_tally);
-    a.inc = (uint32_t *)(b + o_inc);
-    a.tail = (uint32_t *)(b + o_tail);
-    k.ends = (uint32_t *)(b + o_ends);
-    a.frames = (adsb_frame *)(b + o_frames);
-    a.rx = (adsb_wire_rx *)(b + o_rx);
-    a.levels = levels ? (adsb_frame_level *)(b + o_levels) : nullptr;
-    a.counts = (uint64_t *)(b + o_counts);
-    a.consumed = (uint64_t *)(b + o_consumed);
-    a.hdr = (adsb_wire_in_header *)(b + o_hdr);
     return ADSB_OK;
 }
 
@@ -103,20 +75,10 @@ extern "C" int adsb_wire_in_of(adsb_ctx *c, const adsb_wire_in_cfg *cfg, const u
     if ((rc = win_reserve(c, n_bytes, cap, cfg->levels != 0)) != ADSB_OK) return rc;
     adsb_ctx::WireIn &k = c->win;
     const uint8_t *in = bytes;
-    if (n_bytes && !win_in_device_memory(c, bytes)) {
-        if (k.in_bytes < n_bytes) {
-            if (k.in) HIPCHK(hipStreamSynchronize(c->aux)); // an earlier call's kernels may still read it
-            (void)hipFree(k.in);
-            k.in = nullptr;
-            k.in_bytes = 0;
-            if (hipMalloc((void **)&k.in, (n_bytes + 3) & ~(size_t)3) != hipSuccess) { // whole dwords
-                (void)hipGetLastError();
-                return ADSB_E_NOMEM;
-            }
-            k.in_bytes = n_bytes;
-        }
-        HIPCHK(hipMemcpyAsync(k.in, bytes, n_bytes, hipMemcpyHostToDevice, c->aux));
-        in = k.in;
+    if (n_bytes && !in_device_memory(c, bytes)) {
+        if ((rc = grow(c, k.in, (n_bytes + 3) & ~(size_t)3)) != ADSB_OK) return rc; // whole dwords
+        HIPCHK(hipMemcpyAsync(k.in.p, bytes, n_bytes, hipMemcpyHostToDevice, c->aux));
+        in = k.in.p;
     }
     HIPCHK(hipMemcpyAsync(k.ends, ends.data(), sizeof(uint32_t) * n_streams, hipMemcpyHostToDevice, c->aux));
     HIPCHK(hipStreamSynchronize(c->aux)); // the host arrays are the caller's (and this frame's) again
