@@ -108,6 +108,27 @@ def test_slot_pool_loss_is_repaired(gpu, oracle):
         _eq(frames, want)
 
 
+def test_crc_classes_in_big_tiles(dem, oracle):
+    """every CRC syndrome class (tests/crc_cases.py) in tiles of 33..64, 65..128 and more than 128 survivors, at this kernel's
+    tile length: through finish_big_tile, then with the tiles' slots taken away (counted by count_candidate, re-run by the host)"""
+    from tests import crc_cases as C
+    from tests import survivor_cases as S
+    for path in ("pool", "dense"):
+        c = C.cases(oracle, TILE, path)
+        mag = C.magnitudes(c)
+        iq = S.to_iq(mag, np.int8)
+        C.check_bands(c, mag)
+        C.check_mix(c)
+        want = _check(dem, oracle, iq)
+        C.check_figures(c, want)  # (the list equals the oracle's: its figures for every class)
+        dem.pool_limit(True)
+        try:
+            _check(dem, oracle, iq)
+        finally:
+            dem.pool_limit(False)
+        _check(dem, oracle, iq)
+
+
 def test_multi_channel(gpu, oracle):
     cfg = A.synth_default(seed=3, slot_len=800)
     nch, n = 5, 70_000 + 8
