@@ -196,32 +196,18 @@ __device__ __forceinline__ void mags8_i8(u32x4 v, uint32_t &lo, uint32_t &hi)
 // so the estimate is floor(s) or floor(s) + 1 (either of them when the fraction of s is within 0.007 of one
 // half), and r * r > n tells which (r <= 46341: r * r < 2^32).
 // gfx950 does not interlock a transcendental result against the next VALU instruction (one wait state is
-// required) and hipcc pads nothing inside or around inline asm: the s_nop between v_sqrt_f32 and its reader
-// below is load-bearing.
+// required) and hipcc pads nothing inside or around inline asm: the s_nops in mags4_i16 below are load-bearing.
 __device__ __forceinline__ uint32_t mag_i16_fix(uint32_t r, uint32_t n)
 {
     return r - ((__umul24(r, r) > n) ? 1u : 0u); // r < 2^24: the 24-bit multiply is exact and full rate
-}
-__device__ __forceinline__ uint32_t mag_i16(uint32_t iq)
-{
-    uint32_t n, r; // n = 2^31 for (-32768, -32768): the i32 result wraps to the right bits
-    // (VOP3P form with the inline constant 0 as accumulator: for the builtin hipcc picks v_dot2c, which needs
-    // a v_mov per call to preload it; gfx950 wants 3 wait states between a DOT and a VALU reading it)
-    asm("v_dot2_i32_i16 %0, %2, %2, 0\n\t"
-        "s_nop 2\n\t"
-        "v_cvt_f32_u32 %1, %0\n\t"
-        "v_sqrt_f32 %1, %1\n\t"
-        "s_nop 0\n\t"
-        "v_cvt_rpi_i32_f32 %1, %1"
-        : "=&v"(n), "=&v"(r)
-        : "v"(iq));
-    return mag_i16_fix(r, n);
 }
 // four samples (one 16-byte load) -> two words of packed u16 magnitudes; each group of four like instructions
 // issues back to back, which also covers the wait states between a group and the next
 __device__ __forceinline__ void mags4_i16(u32x4 v, uint32_t &lo, uint32_t &hi)
 {
-    uint32_t n0, n1, n2, n3, r0, r1, r2, r3;
+    uint32_t n0, n1, n2, n3, r0, r1, r2, r3; // n = 2^31 for (-32768, -32768): the i32 result wraps to the right bits
+    // (VOP3P form with the inline constant 0 as accumulator: for the builtin hipcc picks v_dot2c, which needs
+    // a v_mov per call to preload it; gfx950 wants 3 wait states between a DOT and a VALU reading it)
     asm("v_dot2_i32_i16 %0, %8, %8, 0\n\t"
         "v_dot2_i32_i16 %1, %9, %9, 0\n\t"
         "v_dot2_i32_i16 %2, %10, %10, 0\n\t"
@@ -1697,9 +1683,18 @@ __global__ void magnitudes_kernel(const void *iq, size_t n, uint16_t *out)
                 if (g * 8 + k < n) out[g * 8 + k] = (uint16_t)(((k < 4 ? lo : hi) >> (8 * (k & 3))) & 0xFFu);
         }
     } else {
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(iq);
-        for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride)
-            out[k] = (uint16_t)mag_i16(src[k]);
+        // 4 samples per thread-step through the same code path as the tile kernel
+        const size_t groups = (n + 3) / 4;
+        for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += stride) {
+            const uint32_t *src = reinterpret_cast<const uint32_t *>(iq) + g * 4;
+            uint32_t tmp[4];
+            for (int k = 0; k < 4; ++k) tmp[k] = (g * 4 + k < n) ? src[k] : 0u;
+            u32x4 v = {tmp[0], tmp[1], tmp[2], tmp[3]};
+            uint32_t lo, hi;
+            mags4_i16(v, lo, hi);
+            for (int k = 0; k < 4; ++k)
+                if (g * 4 + k < n) out[g * 4 + k] = (uint16_t)((k < 2 ? lo : hi) >> (16 * (k & 1)));
+        }
     }
     if (MAGMODE == 1) __builtin_amdgcn_s_setreg((1 | (0 << 6) | ((2 - 1) << 11)), 0);
 }

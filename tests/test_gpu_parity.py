@@ -82,12 +82,32 @@ def test_magnitude_i16(dem16, oracle):
                            np.array([[-32768, -32768], [32767, 32767], [0, 0], [-32768, 0], [181, 181]])])
     # every perfect square and its neighbour the i16 range can carry: (k, 0) -> k^2, (k, 1) -> k^2 + 1, and the
     # k^2 - 1 cases that are sums of two squares are met by the random draw (the biased float estimate in
-    # mag_i16 is exactly wrong there without its integer correction)
+    # mags4_i16 is exactly wrong there without its integer correction)
     k = np.arange(0, 32768)
     sq = np.concatenate([np.stack([k, np.zeros_like(k)], 1), np.stack([k, np.ones_like(k)], 1),
                          np.stack([-k, k], 1), np.stack([k, -32768 * np.ones_like(k)], 1)])
     iq = np.concatenate([iq, edge.astype(np.int16), sq.astype(np.int16)])
     assert (dem16.magnitudes(iq) == oracle.get_magnitude(iq)).all()
+    # The entry runs the scan's own chain (mags4_i16: four samples per 16-byte load).  Both ends of every boundary root
+    # class (tests/cs16_cases.py: the smallest and the largest I^2 + Q^2 an i16 pair reaches in it) and the four corners of
+    # the range, each at each of the four positions of a load beside three unrelated samples ...
+    from tests import cs16_cases as C
+    vals = [C.rep(r, which, s) for r in C.R for which in ("min", "max") for s in (0, 1)] + list(C.CORNERS)
+    want = [r for r in C.R for _ in range(4)] + [46339, 46339, 46340, 46340]
+    groups = rng.integers(-32768, 32768, size=(len(vals), 4, 4, 2)).astype(np.int16)
+    for pos in range(4):
+        groups[:, pos, pos] = vals
+    full = groups.reshape(-1, 2)
+    got = dem16.magnitudes(full)
+    assert (got == oracle.get_magnitude(full)).all()
+    assert (got.reshape(len(vals), 4, 4)[:, np.arange(4), np.arange(4)] == np.array(want)[:, None]).all()
+    # ... and in a ragged last group (n = 4k + 1, 2, 3): its padding is computed and not stored
+    for cut in (1, 2, 3):
+        for g0 in (0, len(vals) // 2, len(vals) - 1):  # (the cut group holds its boundary value at position 0)
+            part = np.concatenate([full[:16 * g0], groups[g0, 0][:cut]])
+            got = dem16.magnitudes(part)
+            assert len(got) == len(part) == 16 * g0 + cut and (got == oracle.get_magnitude(part)).all(), (cut, g0)
+            assert got[16 * g0] == want[g0]
 
 
 @pytest.mark.parametrize("n", [240, 241, 255, 271, 272, 1000, 2016 + 239, 2016 + 241, 4032 + 240, 4032 + 241, 8192 + 239, 8192 + 240,
