@@ -110,7 +110,8 @@ struct adsb_ctx {
         bool with_levels = false;   // the last call wrote level records
         bool done = false;          // a call has been enqueued
     } win;
-    // tracker (allocated on first adsb_track_device)
+    // tracker (allocated on first adsb_track_device): one hipMalloc carved into the five below
+    DevBuf<char> trk_mem;
     uint32_t *trk_u32 = nullptr;    // 4 x [max_out]: keys, vals, sorted keys, sorted vals
     void *trk_temp = nullptr;
     size_t trk_temp_bytes = 0;

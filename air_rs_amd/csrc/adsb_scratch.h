@@ -15,14 +15,21 @@ static inline bool in_device_memory(const adsb_ctx *c, const void *p)
     return yes;
 }
 
+// b is empty afterwards.  The caller has waited for whatever may still use what it held.
+template <class T>
+static inline void drop(DevBuf<T> &b)
+{
+    (void)hipFree(b.p);
+    b = DevBuf<T>{};
+}
+
 // b holds exactly n records afterwards.  An earlier call's kernels may still use what it held: the host waits for c->aux
 // before freeing it, and only then.  ADSB_E_NOMEM leaves b empty.
 template <class T>
 static inline int replace(adsb_ctx *c, DevBuf<T> &b, size_t n)
 {
     if (b.p) HIPCHK(hipStreamSynchronize(c->aux));
-    (void)hipFree(b.p);
-    b = DevBuf<T>{};
+    drop(b);
     if (hipMalloc((void **)&b.p, sizeof(T) * n) != hipSuccess) {
         (void)hipGetLastError();
         b = DevBuf<T>{};

@@ -8,7 +8,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <initializer_list>
 #include <new>
 #include <vector>
 
@@ -49,14 +48,16 @@ extern "C" int adsb_track_device(adsb_ctx *c, double seconds_per_sample)
     if (!c->fields_current && (rc = adsb_decode_fields_device_async(c)) != ADSB_OK) return rc;
     HIPCHK(hipSetDevice(c->cfg.device));
     const size_t cap = (size_t)c->cfg.max_out;
-    if (!c->trk_u32) {
+    if (!c->trk_mem.p) {
         c->trk_temp_bytes = adsbk::track_sort_temp_bytes(cap);
-        if (hipMalloc((void **)&c->trk_u32, sizeof(uint32_t) * 4 * cap) != hipSuccess ||
-            hipMalloc(&c->trk_temp, c->trk_temp_bytes) != hipSuccess ||
-            hipMalloc((void **)&c->trk_points, sizeof(adsb_track_point) * cap) != hipSuccess ||
-            hipMalloc((void **)&c->trk_aircraft, sizeof(adsb_aircraft_record) * cap) != hipSuccess ||
-            hipMalloc((void **)&c->trk_n_aircraft, sizeof(uint64_t)) != hipSuccess)
-            return ADSB_E_NOMEM;
+        rc = carve_block(c, c->trk_mem, [&](Carve &k) {
+            c->trk_u32 = k.take<uint32_t>(4 * cap);
+            c->trk_temp = k.take<char>(c->trk_temp_bytes);
+            c->trk_points = k.take<adsb_track_point>(cap);
+            c->trk_aircraft = k.take<adsb_aircraft_record>(cap);
+            c->trk_n_aircraft = k.take<uint64_t>(1);
+        });
+        if (rc != ADSB_OK) return rc;
     }
     const uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
     adsbk::TrackArgs a = track_args(TrackKind::kLaunch, c->last_out, c->fields, n, seconds_per_sample, c->trk_u32, cap,
@@ -90,7 +91,7 @@ extern "C" int adsb_fetch_track(adsb_ctx *c, adsb_track_point *points, size_t ma
 }
 
 // ---- the store behind adsb_track_table_* and adsb_track_bank_* -----------------------------------------------------
-// Per-frame summaries and the changed list (adsb_track_*_summaries_reserve): everything here is allocated by the
+// Per-frame summaries and the changed list (adsb_track_*_summaries_reserve): everything here is carved by the
 // reserve; `dev.out` null = no reserve.
 struct TrackSummaries {
     adsbk::TrackSumDev dev{};
@@ -108,6 +109,9 @@ struct TrackStore {
     uint64_t max_frames = 0;
     double seconds_per_sample = 0.0;
     uint32_t n_receivers = 0, max_aircraft = 0; // max_aircraft: per receiver
+    // One block of device memory per lifetime, carved into the arrays below (adsb_scratch.h): the store's own from
+    // create to destroy, and one per reserve.  Every device pointer of the store points into one of them.
+    DevBuf<char> mem, sum_mem, lvl_mem, fix_mem;
     adsbk::TrackStoreDev dev{};     // records [R x max_aircraft], slot [max_frames]; index [2^24] or hash, prefix, scan words
     uint32_t *words = nullptr;      // [3R]: size, flags, size_next (dev.size / dev.flags / dev.size_next)
     uint32_t *u32 = nullptr;        // 4 x [max_frames]: keys, vals, sorted keys, sorted vals
@@ -121,14 +125,16 @@ struct TrackStore {
     uint32_t *exp_u32 = nullptr;    // 2 x [R x max_aircraft]: expire's keep flags and their scan
     void *exp_temp = nullptr;       // expire's scan
     size_t exp_temp_bytes = 0;
+    uint64_t *meta = nullptr;       // a bank's, device [2R + 1]: prefix of the host counts [R + 1], then sample_base [R]
+    uint64_t *meta_pinned = nullptr; // pinned staging of meta
     uint32_t n_points = 0;
     bool updated = false;
     TrackSummaries sum;
-    // per-aircraft levels (adsb_track_*_levels_reserve): all of it allocated by the reserve; dev.lvl null = no reserve
+    // per-aircraft levels (adsb_track_*_levels_reserve): all of it made by the reserve; dev.lvl null = no reserve
     adsbk::TrackLvlDev lvl{};
     adsb_frame_level *lvl_frames = nullptr; // [max_frames]: device copy of a host levels array
     adsb_frame_level *lvl_pinned = nullptr; // [max_frames]: pinned staging of that copy (s.copied covers it too)
-    // positions from single messages (adsb_track_*_fixes_reserve): all of it allocated by the reserve; dev.fix null = none
+    // positions from single messages (adsb_track_*_fixes_reserve): all of it carved by the reserve; dev.fix null = none
     adsbk::TrackFixDev fix{};
 
     size_t places() const { return (size_t)n_receivers * max_aircraft; }
@@ -137,53 +143,59 @@ struct TrackStore {
 struct adsb_track_table : TrackStore {};
 
 struct adsb_track_bank : TrackStore {
-    uint64_t *meta = nullptr;       // device [2R + 1]: prefix of the host counts [R + 1], then sample_base [R]
-    uint64_t *meta_pinned = nullptr; // pinned staging of meta
-    // the fused view (adsb_track_bank_fuse_*): all of it allocated by fuse_reserve, nothing before
-    void *fuse_keys = nullptr;      // 2 x [places] sort keys (uint32_t, uint64_t above kFuseWideReceivers): in, sorted
-    uint32_t *fuse_vals = nullptr;  // 2 x [places]: places in, sorted
-    uint32_t *fuse_start = nullptr; // [fuse_max]
-    adsb_fused_aircraft *fuse_out = nullptr; // [fuse_max]
-    adsb_fused_level *fuse_lvl_out = nullptr; // [fuse_max]: only with a levels reserve too (the second reserve makes it)
-    bool fused_levels = false;      // the last fuse also computed fuse_lvl_out
-    uint64_t *fuse_counts = nullptr; // device [3]: records written, distinct ICAOs, ADSB_TRACK_FUSED_TRUNCATED
-    void *fuse_temp = nullptr;
-    size_t fuse_temp_bytes = 0;
-    size_t fuse_max = 0;            // 0: no reserve
-    uint32_t fuse_lanes = 0;
-    bool fused = false;             // a fuse ran since the last reserve
+    // the fused view (adsb_track_bank_fuse_*): all of it made by fuse_reserve, nothing before
+    DevBuf<char> fuse_mem;          // one block, carved into the arrays of `fuse`
+    DevBuf<adsb_fused_level> fuse_lvl_out; // [fuse.max]: only with a levels reserve too (the second reserve makes it)
+    struct Fuse {
+        void *keys = nullptr;       // 2 x [places] sort keys (uint32_t, uint64_t above kFuseWideReceivers): in, sorted
+        uint32_t *vals = nullptr;   // 2 x [places]: places in, sorted
+        uint32_t *start = nullptr;  // [max]
+        adsb_fused_aircraft *out = nullptr; // [max]
+        uint64_t *counts = nullptr; // device [3]: records written, distinct ICAOs, ADSB_TRACK_FUSED_TRUNCATED
+        void *temp = nullptr;
+        size_t temp_bytes = 0;
+        size_t max = 0;             // 0: no reserve
+        uint32_t lanes = 0;
+        bool fused = false;         // a fuse ran since the last reserve
+        bool fused_levels = false;  // ... and also computed fuse_lvl_out
+    } fuse;
 };
 
-static void free_all(std::initializer_list<void *> list)
+// The three pinned staging buffers (frames, level records, a bank's meta) are host memory, not device scratch
+template <class T>
+static bool pinned_make(T *&p, size_t n)
 {
-    for (void *p : list)
-        if (p) (void)hipFree(p);
+    return hipHostMalloc((void **)&p, sizeof(T) * n, hipHostMallocDefault) == hipSuccess;
 }
 
-static void track_levels_free(TrackStore &s)
+template <class T>
+static void pinned_free(T *&p)
 {
-    free_all({s.dev.lvl, s.lvl.scan, s.lvl.temp, s.lvl_frames});
-    if (s.lvl_pinned) (void)hipHostFree(s.lvl_pinned);
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+}
+
+// The levels reserve undone.  Nothing on the device uses it any more (its clear has been waited for, or never ran).
+static void store_levels_drop(TrackStore &s)
+{
+    drop(s.lvl_mem);
+    pinned_free(s.lvl_pinned);
     s.dev.lvl = nullptr;
-    s.lvl = adsbk::TrackLvlDev{};
-    s.lvl_frames = s.lvl_pinned = nullptr;
+    s.lvl = {};
+    s.lvl_frames = nullptr;
 }
 
-static void track_fixes_free(TrackStore &s)
+// The fixes reserve undone, under the same condition.
+static void store_fixes_drop(TrackStore &s)
 {
-    free_all({s.dev.fix, (void *)s.dev.site, s.fix.out, s.fix.rem, s.fix.scan, s.fix.temp});
+    drop(s.fix_mem);
     s.dev.fix = nullptr;
     s.dev.site = nullptr;
-    s.fix = adsbk::TrackFixDev{};
+    s.fix = {};
 }
 
-static void track_summaries_free(TrackSummaries &s)
-{
-    free_all({s.dev.scan, s.dev.out, s.dev.changed, s.dev.n_changed, s.dev.temp, s.changed_rec});
-    s = TrackSummaries{};
-}
-
-// Sizes, and the buffers a table and a bank share; false: an allocation failed (the caller releases what was made)
+// Sizes, and the store's own block: what a table and a bank share, then what each kind adds (a bank has set
+// dev.hash_mask).  false: an allocation failed (the caller releases what was made)
 static bool store_alloc(TrackStore &s, adsb_ctx *c, TrackKind kind, uint32_t n_receivers, uint32_t max_aircraft, uint64_t max_frames,
                         double seconds_per_sample, size_t temp_bytes)
 {
@@ -195,38 +207,50 @@ static bool store_alloc(TrackStore &s, adsb_ctx *c, TrackKind kind, uint32_t n_r
     s.dev.max_aircraft = s.max_aircraft = max_aircraft;
     s.temp_bytes = temp_bytes;
     s.exp_temp_bytes = adsbk::track_expire_temp_bytes(s.places());
-    const size_t nf = (size_t)max_frames;
-    const bool ok = hipMalloc((void **)&s.dev.rec, sizeof(TrackRecord) * s.places()) == hipSuccess &&
-                    hipMalloc((void **)&s.words, sizeof(uint32_t) * 3 * n_receivers) == hipSuccess &&
-                    hipMalloc((void **)&s.dev.slot, sizeof(uint32_t) * nf) == hipSuccess &&
-                    hipMalloc((void **)&s.u32, sizeof(uint32_t) * 4 * nf) == hipSuccess &&
-                    hipMalloc(&s.temp, s.temp_bytes) == hipSuccess &&
-                    hipMalloc((void **)&s.frames, sizeof(adsb_frame) * nf) == hipSuccess &&
-                    hipHostMalloc((void **)&s.pinned, sizeof(adsb_frame) * nf, hipHostMallocDefault) == hipSuccess &&
-                    hipEventCreateWithFlags(&s.copied, hipEventDisableTiming) == hipSuccess &&
-                    hipMalloc((void **)&s.fields, sizeof(adsb_packet_fields) * nf) == hipSuccess &&
-                    hipMalloc((void **)&s.points, sizeof(adsb_track_point) * nf) == hipSuccess &&
-                    hipMalloc((void **)&s.exp_u32, sizeof(uint32_t) * 2 * s.places()) == hipSuccess &&
-                    hipMalloc(&s.exp_temp, s.exp_temp_bytes) == hipSuccess;
-    if (ok) {
+    const size_t nf = (size_t)max_frames, nr = n_receivers;
+    const int rc = carve_block(c, s.mem, [&](Carve &k) {
+        s.dev.rec = k.take<TrackRecord>(s.places());
+        s.words = k.take<uint32_t>(3 * nr);
         s.dev.size = s.words;
-        s.dev.flags = s.words + n_receivers;
-        s.dev.size_next = s.words + 2 * n_receivers;
-    }
-    return ok;
+        s.dev.flags = s.words + nr;
+        s.dev.size_next = s.words + 2 * nr;
+        s.dev.slot = k.take<uint32_t>(nf);
+        s.u32 = k.take<uint32_t>(4 * nf);
+        s.temp = k.take<char>(s.temp_bytes);
+        s.frames = k.take<adsb_frame>(nf);
+        s.fields = k.take<adsb_packet_fields>(nf);
+        s.points = k.take<adsb_track_point>(nf);
+        s.exp_u32 = k.take<uint32_t>(2 * s.places());
+        s.exp_temp = k.take<char>(s.exp_temp_bytes);
+        if (kind == TrackKind::kTable) {
+            s.dev.index = k.take<uint32_t>((size_t)1 << 24);
+        } else {
+            s.dev.hash = k.take<unsigned long long>(s.dev.hash_mask + 1);
+            s.dev.prefix = k.take<uint32_t>(nr + 1);
+            s.meta = k.take<uint64_t>(2 * nr + 1);
+            s.dev.sample_base = s.meta + nr + 1;
+            s.dev.mark = k.take<unsigned long long>(nf);
+            s.dev.excl = k.take<unsigned long long>(nf);
+            s.dev.seg_slot = k.take<uint32_t>(nf);
+        }
+    });
+    return rc == ADSB_OK && pinned_make(s.pinned, nf) &&
+           (kind == TrackKind::kTable || pinned_make(s.meta_pinned, 2 * nr + 1)) &&
+           hipEventCreateWithFlags(&s.copied, hipEventDisableTiming) == hipSuccess;
 }
 
-// Waits for the stream, then frees whatever of the store exists (the table's and the bank's device-view buffers too)
+// Waits for the stream, then frees whatever of the store exists
 static void store_release(TrackStore &s)
 {
     (void)hipSetDevice(s.ctx->cfg.device);
     (void)hipStreamSynchronize(s.ctx->aux);
-    track_summaries_free(s.sum);
-    track_levels_free(s);
-    track_fixes_free(s);
-    free_all({s.dev.rec, s.words, s.dev.slot, s.dev.index, s.dev.hash, s.dev.prefix, s.dev.mark, s.dev.excl,
-              s.dev.seg_slot, s.u32, s.temp, s.frames, s.fields, s.points, s.exp_u32, s.exp_temp});
-    if (s.pinned) (void)hipHostFree(s.pinned);
+    drop(s.mem);
+    drop(s.sum_mem);
+    drop(s.lvl_mem);
+    drop(s.fix_mem);
+    pinned_free(s.pinned);
+    pinned_free(s.lvl_pinned);
+    pinned_free(s.meta_pinned);
     if (s.copied) (void)hipEventDestroy(s.copied);
 }
 
@@ -307,15 +331,38 @@ static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t s
     return ADSB_OK;
 }
 
-static int store_fetch_points(TrackStore *s, adsb_track_point *points, size_t max_points, size_t *n_points)
+// The store's device arrays a caller may fetch or borrow; null: not reserved, or (the per-frame ones, which hold the
+// last update's list) no update yet.
+static const adsb_track_point *points_of(TrackStore &s) { return s.updated ? s.points : nullptr; }
+static const adsb_aircraft_record *summaries_of(TrackStore &s) { return s.sum.updated ? s.sum.dev.out : nullptr; }
+static const adsb_frame_fix *frame_fixes_of(TrackStore &s) { return s.dev.fix && s.updated ? s.fix.out : nullptr; }
+static const adsb_aircraft_level *levels_of(TrackStore &s) { return s.dev.lvl; }
+static const adsb_fix *fixes_of(TrackStore &s) { return s.dev.fix; }
+
+template <class T>
+static int store_device(TrackStore *s, const T *of(TrackStore &), const T **dev)
 {
-    if (!s || (!points && max_points)) return ADSB_E_ARG;
-    if (!s->updated) return ADSB_E_STATE;
+    if (!s) return ADSB_E_ARG;
+    const T *p = of(*s);
+    if (!p) return ADSB_E_STATE;
+    if (dev) *dev = p;
+    return ADSB_OK;
+}
+
+// Waits.  The first min(list, max) per-frame records of the last update, list order; *n = how many were copied, or the
+// list's length.
+enum class Report { kCopied, kListLength };
+template <class T>
+static int store_fetch_frames(TrackStore *s, const T *of(TrackStore &), T *out, size_t max, size_t *n, Report report)
+{
+    if (!s || (!out && max)) return ADSB_E_ARG;
+    const T *src = of(*s);
+    if (!src) return ADSB_E_STATE;
     HIPCHK(hipSetDevice(s->ctx->cfg.device));
-    const size_t np = std::min<size_t>(s->n_points, max_points);
-    if (np) HIPCHK(hipMemcpyAsync(points, s->points, sizeof(adsb_track_point) * np, hipMemcpyDeviceToHost, s->ctx->aux));
+    const size_t take = std::min<size_t>(s->n_points, max);
+    if (take) HIPCHK(hipMemcpyAsync(out, src, sizeof(T) * take, hipMemcpyDeviceToHost, s->ctx->aux));
     HIPCHK(hipStreamSynchronize(s->ctx->aux));
-    if (n_points) *n_points = np;
+    if (n) *n = report == Report::kCopied ? take : s->n_points;
     return ADSB_OK;
 }
 
@@ -385,7 +432,7 @@ static int store_expire(TrackStore *s, const double *before)
     return ADSB_OK;
 }
 
-// May wait for the device (hipMalloc); a second reserve keeps what the first one made
+// A second reserve keeps what the first one made
 static int store_summaries_reserve(TrackStore *st)
 {
     if (!st) return ADSB_E_ARG;
@@ -395,41 +442,16 @@ static int store_summaries_reserve(TrackStore *st)
     const size_t max_frames = (size_t)st->max_frames;
     s.changed_cap = std::min(max_frames, st->places());
     s.dev.temp_bytes = adsbk::track_summaries_temp_bytes(max_frames);
-    const bool ok = hipMalloc((void **)&s.dev.scan, sizeof(adsbk::TrackSumTuple) * max_frames) == hipSuccess &&
-                    hipMalloc((void **)&s.dev.changed, sizeof(uint32_t) * max_frames) == hipSuccess &&
-                    hipMalloc((void **)&s.dev.n_changed, sizeof(uint32_t)) == hipSuccess &&
-                    hipMalloc(&s.dev.temp, s.dev.temp_bytes) == hipSuccess &&
-                    hipMalloc((void **)&s.changed_rec, sizeof(TrackRecord) * s.changed_cap) == hipSuccess &&
-                    hipMalloc((void **)&s.dev.out, sizeof(adsb_aircraft_record) * max_frames) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        track_summaries_free(s);
-        return ADSB_E_NOMEM;
-    }
-    return ADSB_OK;
-}
-
-// Waits
-static int store_fetch_summaries(TrackStore *st, adsb_aircraft_record *out, size_t max, size_t *n)
-{
-    if (!st || (!out && max)) return ADSB_E_ARG;
-    if (!st->sum.dev.out || !st->sum.updated) return ADSB_E_STATE;
-    HIPCHK(hipSetDevice(st->ctx->cfg.device));
-    const size_t n_frames = st->n_points, take = std::min(n_frames, max);
-    if (take)
-        HIPCHK(hipMemcpyAsync(out, st->sum.dev.out, sizeof(adsb_aircraft_record) * take, hipMemcpyDeviceToHost,
-                              st->ctx->aux));
-    HIPCHK(hipStreamSynchronize(st->ctx->aux));
-    if (n) *n = n_frames;
-    return ADSB_OK;
-}
-
-static int store_summaries_device(TrackStore *st, const adsb_aircraft_record **dev)
-{
-    if (!st) return ADSB_E_ARG;
-    if (!st->sum.dev.out || !st->sum.updated) return ADSB_E_STATE;
-    if (dev) *dev = st->sum.dev.out;
-    return ADSB_OK;
+    const int rc = carve_block(st->ctx, st->sum_mem, [&](Carve &k) {
+        s.dev.scan = k.take<adsbk::TrackSumTuple>(max_frames);
+        s.dev.changed = k.take<uint32_t>(max_frames);
+        s.dev.n_changed = k.take<uint32_t>(1);
+        s.dev.temp = k.take<char>(s.dev.temp_bytes);
+        s.changed_rec = k.take<TrackRecord>(s.changed_cap);
+        s.dev.out = k.take<adsb_aircraft_record>(max_frames);
+    });
+    if (rc != ADSB_OK) s = {};
+    return rc;
 }
 
 // Waits; gathers the changed list's records on the device and copies only them.  counts (optional, [n_receivers]): how
@@ -468,7 +490,7 @@ static int store_fetch_changed(TrackStore *st, adsb_aircraft_record *out, double
     return ADSB_OK;
 }
 
-// May wait for the device (hipMalloc, and the wait for the clear); a second reserve keeps what the first one made
+// Waits for the device (the clear); a second reserve keeps what the first one made
 static int store_levels_reserve(TrackStore *st)
 {
     if (!st) return ADSB_E_ARG;
@@ -476,16 +498,17 @@ static int store_levels_reserve(TrackStore *st)
     if (st->dev.lvl) return ADSB_OK;
     const size_t nf = (size_t)st->max_frames;
     st->lvl.temp_bytes = adsbk::track_levels_temp_bytes(nf);
-    const bool ok = hipMalloc((void **)&st->dev.lvl, sizeof(adsb_aircraft_level) * st->places()) == hipSuccess &&
-                    hipMalloc((void **)&st->lvl.scan, sizeof(adsbk::TrackLvlTuple) * nf) == hipSuccess &&
-                    hipMalloc(&st->lvl.temp, st->lvl.temp_bytes) == hipSuccess &&
-                    hipMalloc((void **)&st->lvl_frames, sizeof(adsb_frame_level) * nf) == hipSuccess &&
-                    hipHostMalloc((void **)&st->lvl_pinned, sizeof(adsb_frame_level) * nf, hipHostMallocDefault) == hipSuccess &&
-                    adsbk::launch_track_levels_clear(st->ctx->aux, st->dev.lvl, st->places()) == hipSuccess &&
-                    hipStreamSynchronize(st->ctx->aux) == hipSuccess;
-    if (!ok) {
+    const int rc = carve_block(st->ctx, st->lvl_mem, [&](Carve &k) {
+        st->dev.lvl = k.take<adsb_aircraft_level>(st->places());
+        st->lvl.scan = k.take<adsbk::TrackLvlTuple>(nf);
+        st->lvl.temp = k.take<char>(st->lvl.temp_bytes);
+        st->lvl_frames = k.take<adsb_frame_level>(nf);
+    });
+    if (rc != ADSB_OK || !pinned_make(st->lvl_pinned, nf) ||
+        adsbk::launch_track_levels_clear(st->ctx->aux, st->dev.lvl, st->places()) != hipSuccess ||
+        hipStreamSynchronize(st->ctx->aux) != hipSuccess) {
         (void)hipGetLastError();
-        track_levels_free(*st);
+        store_levels_drop(*st);
         return ADSB_E_NOMEM;
     }
     return ADSB_OK;
@@ -494,7 +517,7 @@ static int store_levels_reserve(TrackStore *st)
 // Waits.  As store_fetch, receiver by receiver in ascending ICAO: the side record (a level record, a fix) beside each
 // record; side: the store's device array of them, one per place.
 template <class T>
-static int store_fetch_side(TrackStore *s, T *side_of(TrackStore &), T *out, size_t max, size_t *n)
+static int store_fetch_side(TrackStore *s, const T *side_of(TrackStore &), T *out, size_t max, size_t *n)
 {
     if (!s || (!out && max)) return ADSB_E_ARG;
     const T *side = side_of(*s);
@@ -533,16 +556,8 @@ static int store_fetch_side(TrackStore *s, T *side_of(TrackStore &), T *out, siz
     return ADSB_OK;
 }
 
-static adsb_aircraft_level *levels_of(TrackStore &s) { return s.dev.lvl; }
-static adsb_fix *fixes_of(TrackStore &s) { return s.dev.fix; }
-
-static int store_fetch_levels(TrackStore *s, adsb_aircraft_level *out, size_t max, size_t *n)
-{
-    return store_fetch_side(s, levels_of, out, max, n);
-}
-
 // ---- positions from single messages -----------------------------------------------------------------------------------
-// sites: [n_receivers], checked by the caller.  Waits for the device (the sizes, hipMalloc, the clear).
+// sites: [n_receivers], checked by the caller.  Waits for the device (the sizes, the clear).
 static int store_fixes_reserve(TrackStore *st, const adsb_site *sites)
 {
     adsb_ctx *c = st->ctx;
@@ -556,56 +571,23 @@ static int store_fixes_reserve(TrackStore *st, const adsb_site *sites)
     if (!st->dev.fix) {
         const size_t nf = (size_t)st->max_frames;
         st->fix.temp_bytes = adsbk::track_fixes_temp_bytes(nf);
-        const bool ok = hipMalloc((void **)&st->dev.fix, sizeof(adsb_fix) * st->places()) == hipSuccess &&
-                        hipMalloc((void **)&st->dev.site, sizeof(adsb_site) * nr) == hipSuccess &&
-                        hipMalloc((void **)&st->fix.out, sizeof(adsb_frame_fix) * nf) == hipSuccess &&
-                        hipMalloc((void **)&st->fix.rem, sizeof(adsbk::FixRem) * nf) == hipSuccess &&
-                        hipMalloc((void **)&st->fix.scan, sizeof(adsbk::TrackFixTuple) * nf) == hipSuccess &&
-                        hipMalloc(&st->fix.temp, st->fix.temp_bytes) == hipSuccess &&
-                        adsbk::launch_track_fixes_clear(c->aux, st->dev.fix, st->places()) == hipSuccess &&
-                        hipStreamSynchronize(c->aux) == hipSuccess;
-        if (!ok) {
+        const int rc = carve_block(c, st->fix_mem, [&](Carve &k) {
+            st->dev.fix = k.take<adsb_fix>(st->places());
+            st->dev.site = k.take<adsb_site>(nr);
+            st->fix.out = k.take<adsb_frame_fix>(nf);
+            st->fix.rem = k.take<adsbk::FixRem>(nf);
+            st->fix.scan = k.take<adsbk::TrackFixTuple>(nf);
+            st->fix.temp = k.take<char>(st->fix.temp_bytes);
+        });
+        if (rc != ADSB_OK || adsbk::launch_track_fixes_clear(c->aux, st->dev.fix, st->places()) != hipSuccess ||
+            hipStreamSynchronize(c->aux) != hipSuccess) {
             (void)hipGetLastError();
-            track_fixes_free(*st);
+            store_fixes_drop(*st);
             return ADSB_E_NOMEM;
         }
     }
     // the stream is idle: a plain copy from the caller's array
     HIPCHK(hipMemcpy((void *)st->dev.site, sites, sizeof(adsb_site) * nr, hipMemcpyHostToDevice));
-    return ADSB_OK;
-}
-
-static int store_fetch_fixes(TrackStore *s, adsb_fix *out, size_t max, size_t *n)
-{
-    return store_fetch_side(s, fixes_of, out, max, n);
-}
-
-static int store_fixes_device(TrackStore *s, const adsb_fix **dev)
-{
-    if (!s) return ADSB_E_ARG;
-    if (!s->dev.fix) return ADSB_E_STATE;
-    if (dev) *dev = s->dev.fix;
-    return ADSB_OK;
-}
-
-// Waits; the last update's per-frame fixes, as store_fetch_points
-static int store_fetch_frame_fixes(TrackStore *s, adsb_frame_fix *out, size_t max, size_t *n)
-{
-    if (!s || (!out && max)) return ADSB_E_ARG;
-    if (!s->dev.fix || !s->updated) return ADSB_E_STATE;
-    HIPCHK(hipSetDevice(s->ctx->cfg.device));
-    const size_t take = std::min<size_t>(s->n_points, max);
-    if (take) HIPCHK(hipMemcpyAsync(out, s->fix.out, sizeof(adsb_frame_fix) * take, hipMemcpyDeviceToHost, s->ctx->aux));
-    HIPCHK(hipStreamSynchronize(s->ctx->aux));
-    if (n) *n = take;
-    return ADSB_OK;
-}
-
-static int store_levels_device(TrackStore *s, const adsb_aircraft_level **dev)
-{
-    if (!s) return ADSB_E_ARG;
-    if (!s->dev.lvl) return ADSB_E_STATE;
-    if (dev) *dev = s->dev.lvl;
     return ADSB_OK;
 }
 
@@ -629,8 +611,7 @@ extern "C" int adsb_track_table_create(adsb_ctx *c, const adsb_track_table_cfg *
     adsb_track_table *t = new (std::nothrow) adsb_track_table;
     if (!t) return ADSB_E_NOMEM;
     const bool ok = store_alloc(*t, c, TrackKind::kTable, 1, cfg->max_aircraft ? cfg->max_aircraft : 65536u, cfg->max_frames,
-                                cfg->seconds_per_sample, adsbk::track_sort_temp_bytes((size_t)cfg->max_frames)) &&
-                    hipMalloc((void **)&t->dev.index, sizeof(uint32_t) << 24) == hipSuccess;
+                                cfg->seconds_per_sample, adsbk::track_sort_temp_bytes((size_t)cfg->max_frames));
     return store_created(t, ok, track_table_free, out);
 }
 
@@ -679,12 +660,12 @@ extern "C" int adsb_track_table_update_levels(adsb_track_table *t, const adsb_fr
 
 extern "C" int adsb_track_table_fetch_levels(adsb_track_table *t, adsb_aircraft_level *out, size_t max, size_t *n)
 {
-    return store_fetch_levels(t, out, max, n);
+    return store_fetch_side(t, levels_of, out, max, n);
 }
 
 extern "C" int adsb_track_table_levels_device(adsb_track_table *t, const adsb_aircraft_level **dev)
 {
-    return store_levels_device(t, dev);
+    return store_device(t, levels_of, dev);
 }
 
 extern "C" int adsb_track_table_fixes_reserve(adsb_track_table *t, const adsb_site *site)
@@ -695,29 +676,29 @@ extern "C" int adsb_track_table_fixes_reserve(adsb_track_table *t, const adsb_si
 
 extern "C" int adsb_track_table_fetch_fixes(adsb_track_table *t, adsb_fix *out, size_t max, size_t *n)
 {
-    return store_fetch_fixes(t, out, max, n);
+    return store_fetch_side(t, fixes_of, out, max, n);
 }
 
 extern "C" int adsb_track_table_fixes_device(adsb_track_table *t, const adsb_fix **dev)
 {
-    return store_fixes_device(t, dev);
+    return store_device(t, fixes_of, dev);
 }
 
 extern "C" int adsb_track_table_fetch_frame_fixes(adsb_track_table *t, adsb_frame_fix *out, size_t max, size_t *n)
 {
-    return store_fetch_frame_fixes(t, out, max, n);
+    return store_fetch_frames(t, frame_fixes_of, out, max, n, Report::kCopied);
 }
 
 extern "C" int adsb_track_table_summaries_reserve(adsb_track_table *t) { return store_summaries_reserve(t); }
 
 extern "C" int adsb_track_table_fetch_summaries(adsb_track_table *t, adsb_aircraft_record *out, size_t max, size_t *n)
 {
-    return store_fetch_summaries(t, out, max, n);
+    return store_fetch_frames(t, summaries_of, out, max, n, Report::kListLength);
 }
 
 extern "C" int adsb_track_table_summaries_device(adsb_track_table *t, const adsb_aircraft_record **dev)
 {
-    return store_summaries_device(t, dev);
+    return store_device(t, summaries_of, dev);
 }
 
 extern "C" int adsb_track_table_fetch_changed(adsb_track_table *t, adsb_aircraft_record *rec, double *last_heard,
@@ -729,7 +710,7 @@ extern "C" int adsb_track_table_fetch_changed(adsb_track_table *t, adsb_aircraft
 extern "C" int adsb_track_table_fetch_points(adsb_track_table *t, adsb_track_point *points, size_t max_points,
                                              size_t *n_points)
 {
-    return store_fetch_points(t, points, max_points, n_points);
+    return store_fetch_frames(t, points_of, points, max_points, n_points, Report::kCopied);
 }
 
 extern "C" int adsb_track_table_fetch(adsb_track_table *t, adsb_aircraft_record *aircraft, size_t max_aircraft,
@@ -755,25 +736,18 @@ extern "C" int adsb_track_table_fetch_velocity(adsb_track_table *t, adsb_velocit
 }
 
 // ---- a bank of persistent tables, one per receiver (adsb_track_bank_*) ----------------------------------------------
-static void track_bank_fuse_free(adsb_track_bank *b)
+// The fuse reserve gone.  The caller has waited for the fuse that may still use it.
+static void track_bank_fuse_drop(adsb_track_bank *b)
 {
-    free_all({b->fuse_keys, b->fuse_vals, b->fuse_start, b->fuse_out, b->fuse_lvl_out, b->fuse_counts, b->fuse_temp});
-    b->fuse_lvl_out = nullptr;
-    b->fused_levels = false;
-    b->fuse_keys = b->fuse_temp = nullptr;
-    b->fuse_vals = b->fuse_start = nullptr;
-    b->fuse_out = nullptr;
-    b->fuse_counts = nullptr;
-    b->fuse_max = 0;
-    b->fused = false;
+    drop(b->fuse_mem);
+    drop(b->fuse_lvl_out);
+    b->fuse = {};
 }
 
 static void track_bank_free(adsb_track_bank *b)
 {
     store_release(*b);
-    track_bank_fuse_free(b);
-    free_all({b->meta});
-    if (b->meta_pinned) (void)hipHostFree(b->meta_pinned);
+    track_bank_fuse_drop(b);
     delete b;
 }
 
@@ -792,7 +766,6 @@ extern "C" int adsb_track_bank_create(adsb_ctx *c, const adsb_track_bank_cfg *cf
     HIPCHK(hipSetDevice(c->cfg.device));
     adsb_track_bank *b = new (std::nothrow) adsb_track_bank;
     if (!b) return ADSB_E_NOMEM;
-    const size_t nf = (size_t)cfg->max_frames;
     uint64_t cap = 1;
     while (cap < 2 * n_rec) cap <<= 1;
     b->dev.hash_mask = cap - 1;
@@ -800,15 +773,7 @@ extern "C" int adsb_track_bank_create(adsb_ctx *c, const adsb_track_bank_cfg *cf
     while ((1u << bits) < nr) ++bits;
     b->dev.key_bits = 24 + bits;
     const bool ok = store_alloc(*b, c, TrackKind::kBank, nr, max_ac, cfg->max_frames, cfg->seconds_per_sample,
-                                adsbk::track_bank_temp_bytes(nf)) &&
-                    hipMalloc((void **)&b->dev.hash, sizeof(unsigned long long) * cap) == hipSuccess &&
-                    hipMalloc((void **)&b->dev.prefix, sizeof(uint32_t) * (nr + 1)) == hipSuccess &&
-                    hipMalloc((void **)&b->meta, sizeof(uint64_t) * (2 * nr + 1)) == hipSuccess &&
-                    hipHostMalloc((void **)&b->meta_pinned, sizeof(uint64_t) * (2 * nr + 1), hipHostMallocDefault) == hipSuccess &&
-                    hipMalloc((void **)&b->dev.mark, sizeof(unsigned long long) * nf) == hipSuccess &&
-                    hipMalloc((void **)&b->dev.excl, sizeof(unsigned long long) * nf) == hipSuccess &&
-                    hipMalloc((void **)&b->dev.seg_slot, sizeof(uint32_t) * nf) == hipSuccess;
-    if (ok) b->dev.sample_base = b->meta + nr + 1;
+                                adsbk::track_bank_temp_bytes((size_t)cfg->max_frames));
     return store_created(b, ok, track_bank_free, out);
 }
 
@@ -888,12 +853,10 @@ extern "C" int adsb_track_bank_update(adsb_track_bank *b, const adsb_frame *fram
 extern "C" int adsb_track_bank_levels_reserve(adsb_track_bank *b)
 {
     int rc = store_levels_reserve(b);
-    if (rc != ADSB_OK || !b->fuse_max || b->fuse_lvl_out) return rc;
+    if (rc != ADSB_OK || !b->fuse.max || b->fuse_lvl_out.p) return rc;
     // the fuse reserve came first: the fused level records are this reserve's to make
-    if (hipMalloc((void **)&b->fuse_lvl_out, sizeof(adsb_fused_level) * b->fuse_max) != hipSuccess) {
-        (void)hipGetLastError();
-        b->fuse_lvl_out = nullptr;
-        track_levels_free(*b);
+    if (replace(b->ctx, b->fuse_lvl_out, b->fuse.max) != ADSB_OK) {
+        store_levels_drop(*b);
         return ADSB_E_NOMEM;
     }
     return ADSB_OK;
@@ -910,12 +873,12 @@ extern "C" int adsb_track_bank_update_levels(adsb_track_bank *b, const adsb_fram
 
 extern "C" int adsb_track_bank_fetch_levels(adsb_track_bank *b, adsb_aircraft_level *out, size_t max, size_t *n)
 {
-    return store_fetch_levels(b, out, max, n);
+    return store_fetch_side(b, levels_of, out, max, n);
 }
 
 extern "C" int adsb_track_bank_levels_device(adsb_track_bank *b, const adsb_aircraft_level **dev)
 {
-    return store_levels_device(b, dev);
+    return store_device(b, levels_of, dev);
 }
 
 // with_levels: also the ctx's levels of the same launch (adsb_track_bank_update_launch_levels)
@@ -962,7 +925,7 @@ extern "C" int adsb_track_bank_update_launch_levels(adsb_track_bank *b, const ui
 extern "C" int adsb_track_bank_fetch_points(adsb_track_bank *b, adsb_track_point *points, size_t max_points,
                                             size_t *n_points)
 {
-    return store_fetch_points(b, points, max_points, n_points);
+    return store_fetch_frames(b, points_of, points, max_points, n_points, Report::kCopied);
 }
 
 extern "C" int adsb_track_bank_fetch(adsb_track_bank *b, adsb_aircraft_record *aircraft, size_t max_aircraft,
@@ -983,29 +946,29 @@ extern "C" int adsb_track_bank_fixes_reserve(adsb_track_bank *b, const adsb_site
 
 extern "C" int adsb_track_bank_fetch_fixes(adsb_track_bank *b, adsb_fix *out, size_t max, size_t *n)
 {
-    return store_fetch_fixes(b, out, max, n);
+    return store_fetch_side(b, fixes_of, out, max, n);
 }
 
 extern "C" int adsb_track_bank_fixes_device(adsb_track_bank *b, const adsb_fix **dev)
 {
-    return store_fixes_device(b, dev);
+    return store_device(b, fixes_of, dev);
 }
 
 extern "C" int adsb_track_bank_fetch_frame_fixes(adsb_track_bank *b, adsb_frame_fix *out, size_t max, size_t *n)
 {
-    return store_fetch_frame_fixes(b, out, max, n);
+    return store_fetch_frames(b, frame_fixes_of, out, max, n, Report::kCopied);
 }
 
 extern "C" int adsb_track_bank_summaries_reserve(adsb_track_bank *b) { return store_summaries_reserve(b); }
 
 extern "C" int adsb_track_bank_fetch_summaries(adsb_track_bank *b, adsb_aircraft_record *out, size_t max, size_t *n)
 {
-    return store_fetch_summaries(b, out, max, n);
+    return store_fetch_frames(b, summaries_of, out, max, n, Report::kListLength);
 }
 
 extern "C" int adsb_track_bank_summaries_device(adsb_track_bank *b, const adsb_aircraft_record **dev)
 {
-    return store_summaries_device(b, dev);
+    return store_device(b, summaries_of, dev);
 }
 
 extern "C" int adsb_track_bank_fetch_changed(adsb_track_bank *b, adsb_aircraft_record *rec, double *last_heard,
@@ -1032,74 +995,76 @@ extern "C" int adsb_track_bank_fuse_reserve(adsb_track_bank *b, size_t max_fused
     adsb_ctx *c = b->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
     HIPCHK(hipStreamSynchronize(c->aux)); // a fuse may still read what is freed here
-    track_bank_fuse_free(b);
+    track_bank_fuse_drop(b);
+    adsb_track_bank::Fuse &f = b->fuse;
     const uint32_t nr = b->n_receivers;
     const size_t places = b->places();
     const size_t cap = max_fused == 0 || max_fused > places ? places : max_fused; // more than `places` cannot occur
     const size_t key_bytes = nr > adsbk::kFuseWideReceivers ? sizeof(uint64_t) : sizeof(uint32_t);
-    b->fuse_temp_bytes = adsbk::track_fuse_temp_bytes(places, nr);
-    b->fuse_lanes = nr == 1 ? 1u : 4u; // measured: DESIGN 4.4f (16 and 64 lanes lost on runs of 64 and of 1 alike)
+    f.temp_bytes = adsbk::track_fuse_temp_bytes(places, nr);
+    f.lanes = nr == 1 ? 1u : 4u; // measured: DESIGN 4.4f (16 and 64 lanes lost on runs of 64 and of 1 alike)
     if (const char *fl = getenv("ADSB_FUSE_LANES")) { // measurement knob: lanes per ICAO in the reduction
         const int v = atoi(fl);
-        if (v == 1 || v == 4) b->fuse_lanes = (uint32_t)v;
+        if (v == 1 || v == 4) f.lanes = (uint32_t)v;
     }
-    const bool ok = hipMalloc(&b->fuse_keys, 2 * key_bytes * places) == hipSuccess &&
-                    hipMalloc((void **)&b->fuse_vals, 2 * sizeof(uint32_t) * places) == hipSuccess &&
-                    hipMalloc((void **)&b->fuse_start, sizeof(uint32_t) * cap) == hipSuccess &&
-                    hipMalloc((void **)&b->fuse_out, sizeof(adsb_fused_aircraft) * cap) == hipSuccess &&
-                    (!b->dev.lvl || hipMalloc((void **)&b->fuse_lvl_out, sizeof(adsb_fused_level) * cap) == hipSuccess) &&
-                    hipMalloc((void **)&b->fuse_counts, sizeof(uint64_t) * 3) == hipSuccess &&
-                    hipMalloc(&b->fuse_temp, b->fuse_temp_bytes) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        track_bank_fuse_free(b);
+    int rc = carve_block(c, b->fuse_mem, [&](Carve &k) {
+        f.keys = k.take<char>(2 * key_bytes * places);
+        f.vals = k.take<uint32_t>(2 * places);
+        f.start = k.take<uint32_t>(cap);
+        f.out = k.take<adsb_fused_aircraft>(cap);
+        f.counts = k.take<uint64_t>(3);
+        f.temp = k.take<char>(f.temp_bytes);
+    });
+    if (rc == ADSB_OK && b->dev.lvl) rc = replace(c, b->fuse_lvl_out, cap); // the levels reserve came first
+    if (rc != ADSB_OK) {
+        track_bank_fuse_drop(b);
         return ADSB_E_NOMEM;
     }
-    b->fuse_max = cap;
+    f.max = cap;
     return ADSB_OK;
 }
 
 extern "C" int adsb_track_bank_fuse(adsb_track_bank *b, double since)
 {
     if (!b || std::isnan(since)) return ADSB_E_ARG;
-    if (!b->fuse_max) return ADSB_E_STATE;
+    if (!b->fuse.max) return ADSB_E_STATE;
     HIPCHK(hipSetDevice(b->ctx->cfg.device));
     const size_t places = b->places();
     const size_t key_bytes = b->n_receivers > adsbk::kFuseWideReceivers ? sizeof(uint64_t) : sizeof(uint32_t);
     adsbk::FuseArgs a{};
     a.bank = &b->dev;
     a.since = since;                 // by value in the kernel's arguments, as expire's cuts: no staging, no wait
-    a.keys = b->fuse_keys;
-    a.skeys = (char *)b->fuse_keys + key_bytes * places;
-    a.vals = b->fuse_vals;
-    a.svals = b->fuse_vals + places;
-    a.seg_start = b->fuse_start;
-    a.out = b->fuse_out;
-    a.lvl_out = b->dev.lvl ? b->fuse_lvl_out : nullptr; // both reserves: the fused levels too
-    a.counts = b->fuse_counts;
-    a.max_fused = b->fuse_max;
-    a.temp = b->fuse_temp;
-    a.temp_bytes = b->fuse_temp_bytes;
-    a.lanes = b->fuse_lanes;
+    a.keys = b->fuse.keys;
+    a.skeys = (char *)b->fuse.keys + key_bytes * places;
+    a.vals = b->fuse.vals;
+    a.svals = b->fuse.vals + places;
+    a.seg_start = b->fuse.start;
+    a.out = b->fuse.out;
+    a.lvl_out = b->dev.lvl ? b->fuse_lvl_out.p : nullptr; // both reserves: the fused levels too
+    a.counts = b->fuse.counts;
+    a.max_fused = b->fuse.max;
+    a.temp = b->fuse.temp;
+    a.temp_bytes = b->fuse.temp_bytes;
+    a.lanes = b->fuse.lanes;
     HIPCHK(adsbk::launch_track_fuse(b->ctx->aux, a)); // after the bank's last update / expire / reset (same stream)
-    b->fused = true;
-    b->fused_levels = a.lvl_out != nullptr;
+    b->fuse.fused = true;
+    b->fuse.fused_levels = a.lvl_out != nullptr;
     return ADSB_OK;
 }
 
 extern "C" int adsb_track_bank_fetch_fused_levels(adsb_track_bank *b, adsb_fused_level *out, size_t max, size_t *n)
 {
     if (!b || (!out && max)) return ADSB_E_ARG;
-    if (!b->fused || !b->fused_levels) return ADSB_E_STATE;
+    if (!b->fuse.fused || !b->fuse.fused_levels) return ADSB_E_STATE;
     adsb_ctx *c = b->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
     uint64_t written = 0;
-    HIPCHK(hipMemcpyAsync(&written, b->fuse_counts, sizeof(written), hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipMemcpyAsync(&written, b->fuse.counts, sizeof(written), hipMemcpyDeviceToHost, c->aux));
     HIPCHK(hipStreamSynchronize(c->aux));
-    written = std::min<uint64_t>(written, b->fuse_max);
+    written = std::min<uint64_t>(written, b->fuse.max);
     const size_t take = std::min<size_t>((size_t)written, max);
     if (take) {
-        HIPCHK(hipMemcpyAsync(out, b->fuse_lvl_out, sizeof(adsb_fused_level) * take, hipMemcpyDeviceToHost, c->aux));
+        HIPCHK(hipMemcpyAsync(out, b->fuse_lvl_out.p, sizeof(adsb_fused_level) * take, hipMemcpyDeviceToHost, c->aux));
         HIPCHK(hipStreamSynchronize(c->aux));
     }
     if (n) *n = (size_t)written;
@@ -1110,15 +1075,15 @@ extern "C" int adsb_track_bank_fetch_fused(adsb_track_bank *b, adsb_fused_aircra
                                            size_t *n_total, uint32_t *flags)
 {
     if (!b || (!out && max)) return ADSB_E_ARG;
-    if (!b->fused) return ADSB_E_STATE;
+    if (!b->fuse.fused) return ADSB_E_STATE;
     adsb_ctx *c = b->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
     uint64_t w[3];
-    HIPCHK(hipMemcpyAsync(w, b->fuse_counts, sizeof(w), hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipMemcpyAsync(w, b->fuse.counts, sizeof(w), hipMemcpyDeviceToHost, c->aux));
     HIPCHK(hipStreamSynchronize(c->aux));
-    const size_t take = std::min<size_t>(std::min<uint64_t>(w[0], b->fuse_max), max);
+    const size_t take = std::min<size_t>(std::min<uint64_t>(w[0], b->fuse.max), max);
     if (take) {
-        HIPCHK(hipMemcpyAsync(out, b->fuse_out, sizeof(adsb_fused_aircraft) * take, hipMemcpyDeviceToHost, c->aux));
+        HIPCHK(hipMemcpyAsync(out, b->fuse.out, sizeof(adsb_fused_aircraft) * take, hipMemcpyDeviceToHost, c->aux));
         HIPCHK(hipStreamSynchronize(c->aux));
     }
     if (n) *n = take;
@@ -1131,8 +1096,8 @@ extern "C" int adsb_track_bank_fused_device(adsb_track_bank *b, const adsb_fused
                                             const uint64_t **counts_dev)
 {
     if (!b) return ADSB_E_ARG;
-    if (!b->fused) return ADSB_E_STATE;
-    if (fused_dev) *fused_dev = b->fuse_out;
-    if (counts_dev) *counts_dev = b->fuse_counts;
+    if (!b->fuse.fused) return ADSB_E_STATE;
+    if (fused_dev) *fused_dev = b->fuse.out;
+    if (counts_dev) *counts_dev = b->fuse.counts;
     return ADSB_OK;
 }
