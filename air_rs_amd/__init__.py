@@ -11,12 +11,15 @@ from ._lib import (ADSB_FIX_ALT, ADSB_FIX_REJECTED, ADSB_FIX_SPEED, ADSB_FIX_SUR
                    ADSB_MLAT_C, ADSB_MLAT_MAX_RECEPTIONS, ADSB_MLAT_TIME_RECEPTION, ADSB_MLAT_TIME_TICKS,
                    ADSB_MLAT_USE_ALTITUDE, ADSB_MLAT_ATTEMPTED, ADSB_MLAT_CONVERGED, ADSB_MLAT_ALTITUDE, ADSB_MLAT_TOO_FEW,
                    ADSB_MLAT_TOO_MANY, ADSB_MLAT_SINGULAR, ADSB_MLAT_REJECTED_RESIDUAL, ADSB_MLAT_REJECTED_RANGE,
-                   ADSB_MLAT_VALID, ADSB_MLAT_BAD_INDEX, ADSB_MLAT_HDR_BAD_INDEX)
+                   ADSB_MLAT_VALID, ADSB_MLAT_BAD_INDEX, ADSB_MLAT_HDR_BAD_INDEX,
+                   ADSB_CLOCK_DRIFT, ADSB_CLOCK_REFERENCE, ADSB_CLOCK_REACHED, ADSB_CLOCK_HAS_DRIFT,
+                   ADSB_CLOCK_HDR_BAD_INDEX, ADSB_CLOCK_HDR_DRIFT_DROPPED, ADSB_CLOCK_HDR_SINGULAR)
 from .demod import (AIRCRAFT_DTYPE, AIRCRAFT_LEVEL_DTYPE, FUSED_LEVEL_DTYPE, FIELDS_DTYPE, FRAME_DTYPE, FUSED_DTYPE, LEVEL_DTYPE, LEVEL_PULSE_SAMPLES, LEVEL_QUIET_SAMPLES,
                     SITE, FIX_DTYPE, FRAME_FIX_DTYPE, host_fix_of,
                     host_frame_levels, host_wire_encode, host_wire_parse, WIRE_RX_DTYPE, WIRE_IN_HEADER_DTYPE, WireIn, host_correlate, frames_of_messages, MESSAGE_DTYPE, RECEPTION_DTYPE, level_dbfs, TRACK_POINT_DTYPE, VELOCITY_DTYPE, WINDOW, AdsbDemod, AdsbGroup, Feed, Tracker,
                     TrackBank, TrackTable,
                     MLAT_FIX_DTYPE, MLAT_RECEIVER_DTYPE, MLAT_HEADER_DTYPE, host_multilaterate,
+                    CLOCK_DTYPE, CLOCK_HEADER_DTYPE, host_clock_sync, host_clock_apply,
                     group_plan,
                     cpr_position, packet_display, packet_new,
                     packet_new_from_string, synth_default, synth_fill_host, synth_slot, measure_feed, measure_pinned_copy)
@@ -40,5 +43,8 @@ __all__ = [
     "ADSB_MLAT_ATTEMPTED", "ADSB_MLAT_CONVERGED", "ADSB_MLAT_ALTITUDE", "ADSB_MLAT_TOO_FEW", "ADSB_MLAT_TOO_MANY",
     "ADSB_MLAT_SINGULAR", "ADSB_MLAT_REJECTED_RESIDUAL", "ADSB_MLAT_REJECTED_RANGE", "ADSB_MLAT_VALID",
     "ADSB_MLAT_BAD_INDEX", "ADSB_MLAT_HDR_BAD_INDEX",
+    "CLOCK_DTYPE", "CLOCK_HEADER_DTYPE", "host_clock_sync", "host_clock_apply", "ADSB_CLOCK_DRIFT", "ADSB_CLOCK_REFERENCE",
+    "ADSB_CLOCK_REACHED", "ADSB_CLOCK_HAS_DRIFT", "ADSB_CLOCK_HDR_BAD_INDEX", "ADSB_CLOCK_HDR_DRIFT_DROPPED",
+    "ADSB_CLOCK_HDR_SINGULAR",
     "synth_default", "synth_fill_host", "synth_slot", "measure_feed", "measure_pinned_copy",
 ]

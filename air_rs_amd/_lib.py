@@ -170,6 +170,30 @@ assert MLAT_RECEIVER_DTYPE.itemsize == C.sizeof(AdsbMlatReceiver) == 32
 assert MLAT_FIX_DTYPE.itemsize == C.sizeof(AdsbMlatFix) == 64 and C.sizeof(AdsbMlatCfg) == 64
 
 
+ADSB_CLOCK_DRIFT = 0x1                                       # adsb_clock_cfg.flags
+ADSB_CLOCK_REFERENCE, ADSB_CLOCK_REACHED, ADSB_CLOCK_HAS_DRIFT = 0x1, 0x2, 0x4   # adsb_clock.flags
+ADSB_CLOCK_HDR_BAD_INDEX, ADSB_CLOCK_HDR_DRIFT_DROPPED, ADSB_CLOCK_HDR_SINGULAR = 0x1, 0x2, 0x4  # adsb_clock_header.flags
+
+
+class AdsbClockCfg(C.Structure):
+    """adsb_clock_cfg: the time source and units, the reference receiver, and the second pass's limit (64 bytes)."""
+    _fields_ = [("time_source", C.c_uint32), ("flags", C.c_uint32), ("reference", C.c_uint32), ("min_rows", C.c_uint32),
+                ("seconds_per_tick", C.c_double), ("seconds_per_time", C.c_double), ("max_residual_s", C.c_double),
+                ("max_range_nm", C.c_double), ("reserved", C.c_uint64 * 2)]
+
+
+class AdsbClockHeader(C.Structure):
+    """adsb_clock_header: the totals of one clock-sync call (64 bytes)."""
+    _fields_ = [(k, C.c_uint64) for k in ("n_messages", "n_eligible", "n_rows", "n_dropped", "n_reached", "flags")] + \
+               [("reserved", C.c_uint64 * 2)]
+
+
+CLOCK_DTYPE = np.dtype([("offset_s", "<f8"), ("fine_offset_s", "<f8"), ("drift", "<f8"), ("residual_rms_s", "<f4"),
+                        ("n_rows", "<u4"), ("n_dropped", "<u4"), ("n_partners", "<u4"), ("flags", "<u4"),
+                        ("reserved", "<u4", (5,))])
+assert CLOCK_DTYPE.itemsize == 64 and C.sizeof(AdsbClockCfg) == 64 and C.sizeof(AdsbClockHeader) == 64
+
+
 class AdsbTrackPoint(C.Structure):
     _fields_ = [("latitude", C.c_double), ("longitude", C.c_double), ("icao", C.c_uint32), ("flags", C.c_uint32)]
 
@@ -339,6 +363,15 @@ PROTOTYPES = {
     "adsb_fetch_mlat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), _P(AdsbMlatHeader)]),
     "adsb_mlat_device": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p)]),
     "adsb_debug_mlat_geometry": (C.c_int, [_P(C.c_uint32), _P(C.c_uint32)]),
+    "adsb_clock_sync": (C.c_int, [C.c_void_p, _P(AdsbClockCfg), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "adsb_clock_sync_of": (C.c_int, [C.c_void_p, _P(AdsbClockCfg), C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "adsb_fetch_clocks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), _P(AdsbClockHeader)]),
+    "adsb_clocks_device": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p)]),
+    "adsb_clock_apply": (C.c_int, [C.c_void_p]),
+    "adsb_fetch_clock_receptions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), _P(C.c_size_t)]),
+    "adsb_clock_receptions_device": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t)]),
+    "adsb_debug_clock_geometry": (C.c_int, [_P(C.c_uint32), _P(C.c_uint32)]),
     "adsb_track_device": (C.c_int, [C.c_void_p, C.c_double]),
     "adsb_fetch_track": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t,
                                    _P(C.c_size_t)]),
@@ -480,6 +513,10 @@ PROTOTYPES = {
                                       C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p]),
     "adsb_host_multilaterate": (C.c_int, [_P(AdsbMlatCfg), C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                           C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, _P(AdsbMlatHeader)]),
+    "adsb_host_clock_sync": (C.c_int, [_P(AdsbClockCfg), C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, _P(AdsbClockHeader), C.c_void_p]),
+    "adsb_host_clock_apply": (C.c_int, [_P(AdsbClockCfg), C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adsb_host_fix_of": (C.c_int, [_P(AdsbSite), _P(C.c_uint8 * 14), C.c_double, _P(AdsbFix), _P(C.c_uint32)]),
 }
 

@@ -1,6 +1,7 @@
 // adsb_api.cpp -- the extern "C" boundary (include/adsb_hip.h) over the gfx950 scan kernels: the context, the launches,
 // the fetch and the decoded fields.  Every other part of the boundary has a file of its own: adsb_track_api.cpp,
-// adsb_levels_api.cpp, adsb_wire_api.cpp, adsb_wire_in_api.cpp, adsb_correlate_api.cpp, adsb_mlat_api.cpp.
+// adsb_levels_api.cpp, adsb_wire_api.cpp, adsb_wire_in_api.cpp, adsb_correlate_api.cpp, adsb_mlat_api.cpp,
+// adsb_clock_api.cpp.
 //
 // Replaces, per received buffer, the body of the reference's thread 2 loop
 // (src/adsb.rs:95-116).  There is NO CPU fallback: without a HIP device adsb_create() fails with
@@ -64,7 +65,8 @@ extern "C" void adsb_destroy(adsb_ctx *c)
     }
     void *const owned[] = {c->staging, c->out_start, c->fields, c->levels, c->lvof_out.p, c->lvof_frames.p, c->wire.mem.p,
                            c->wof.mem.p, c->wof_frames.p, c->wof_levels.p, c->corr.mem.p, c->mlat.mem.p, c->mlat.in_msgs.p,
-                           c->mlat.in_recs.p, c->mlat.in_rx.p, c->win.mem.p, c->win.in.p, c->trk_mem.p, c->scratch,
+                           c->mlat.in_recs.p, c->mlat.in_rx.p, c->clock.mem.p, c->clock.in_msgs.p, c->clock.in_recs.p,
+                           c->clock.in_rx.p, c->win.mem.p, c->win.in.p, c->trk_mem.p, c->scratch,
                            c->stamps, c->lb, c->sm.done};
     for (void *p : owned) (void)hipFree(p);
     for (char *b : c->sm.blob) if (b) (void)hipHostFree(b);

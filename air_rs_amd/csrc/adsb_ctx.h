@@ -97,6 +97,18 @@ struct adsb_ctx {
         DevBuf<adsb_wire_rx> in_rx;
         bool done = false;          // a multilaterate call has been enqueued
     } mlat;
+    // clock sync (adsb_clock.hip), allocated on first adsb_clock_sync / adsb_clock_sync_of and grown on demand: one
+    // hipMalloc carved into everything `a` below points into, and device copies of host lists
+    struct Clock {
+        DevBuf<char> mem;
+        size_t msgs = 0, recs = 0;           // what it holds
+        adsbk::ClockArgs a{};                // scratch and result pointers; the lists and the cfg of the last sync
+        DevBuf<adsb_message> in_msgs;        // of a host list
+        DevBuf<adsb_reception> in_recs;
+        DevBuf<adsb_wire_rx> in_rx;
+        bool done = false;          // a clock-sync call has been enqueued
+        bool applied = false;       // ... and adsb_clock_apply behind it
+    } clock;
     // wire input (adsb_wire_in.hip), allocated on first adsb_wire_in_of and grown on demand: one hipMalloc carved into the
     // kernels' arrays and the results, and the device copy of a host input
     struct WireIn {

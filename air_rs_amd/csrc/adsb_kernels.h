@@ -8,6 +8,7 @@
 
 #include "../../include/adsb_hip.h"
 #include "adsb_mlat.h"
+#include "adsb_clock_records.h"
 
 namespace adsbk {
 
@@ -280,6 +281,35 @@ struct MlatArgs {
 };
 size_t mlat_temp_bytes(size_t n_msgs);
 hipError_t launch_mlat(hipStream_t s, const MlatArgs &a);
+
+// receiver clocks from position messages (adsb_clock.hip; adsb_clock.h has the shared text)
+constexpr uint32_t kClockBlock = 256;                           // threads per workgroup of every clock kernel
+constexpr uint32_t kClockPerBlock = kClockBlock / kClockLanes;  // messages per workgroup of the rows and apply kernels
+struct ClockArgs {
+    const adsb_message *msgs;        // [n_msgs]
+    const adsb_reception *recs;      // [n_recs]
+    const adsb_wire_rx *rx;          // [n_rx] or null (TIME_RECEPTION)
+    const uint64_t *counts_dev;      // as MlatArgs'
+    uint32_t n_msgs, n_recs, n_rx, n_receivers;
+    const ClockStation *stations;    // [n_receivers]
+    ClockParams p;
+    void *temp;
+    size_t temp_bytes;               // >= clock_temp_bytes(n_recs)
+    // scratch
+    double *tau, *yp;                // [n_recs] each: the rows, slot for slot
+    uint32_t *key, *key_sorted, *slot_sorted; // [n_recs] each
+    uint8_t *msg_flags;              // [n_msgs]
+    ClockPair *pairs, *pairs_first;  // [256 x 256] each: the sums of the last pass, and of the first
+    double *normal;                  // [kClockMaxUnknowns x kClockMaxUnknowns]
+    ClockSol *sol;                   // [256]
+    // results
+    adsb_clock *clocks;              // [n_receivers]
+    adsb_clock_header *hdr;
+    adsb_reception *corrected;       // [n_recs]
+};
+size_t clock_temp_bytes(size_t n_recs);
+hipError_t launch_clock_sync(hipStream_t s, const ClockArgs &a);
+hipError_t launch_clock_apply(hipStream_t s, const ClockArgs &a);
 
 // tracker + CPR position decode over an ordered frame list (adsb_track.hip)
 // One aircraft of a persistent table (adsb_track_table_*): the public record plus the last even and the last odd

@@ -314,6 +314,54 @@ def host_multilaterate(receivers, messages, receptions, rx=None, **cfg):
     return fixes[:nm].copy(), np.frombuffer(bytes(hdr), dtype=MLAT_HEADER_DTYPE)[0]
 
 
+CLOCK_DTYPE = L.CLOCK_DTYPE
+CLOCK_HEADER_DTYPE = np.dtype([(k, "<u8") for k in ("n_messages", "n_eligible", "n_rows", "n_dropped", "n_reached",
+                                                    "flags")] + [("reserved", "<u8", (2,))])
+assert CLOCK_HEADER_DTYPE.itemsize == C.sizeof(L.AdsbClockHeader) == 64
+
+
+def _clock_cfg(time_source="reception", seconds_per_tick=0.0, seconds_per_time=0.0, reference=0, drift=True, min_rows=0,
+               max_residual_s=0.0, max_range_nm=0.0):
+    src = MLAT_TIME_SOURCES[time_source] if isinstance(time_source, str) else int(time_source)
+    return L.AdsbClockCfg(src, L.ADSB_CLOCK_DRIFT if drift else 0, int(reference), int(min_rows), float(seconds_per_tick),
+                          float(seconds_per_time), float(max_residual_s), float(max_range_nm))
+
+
+def host_clock_sync(receivers, messages, receptions, rx=None, row_state=False, **cfg):
+    """adsb_host_clock_sync, the CPU mirror of AdsbDemod.clock_sync_of: (CLOCK_DTYPE clocks, one per receiver; the
+    CLOCK_HEADER_DTYPE record[; one byte per reception slot: 0 empty, 1 a kept row, 2 a dropped row]) of a correlate
+    result heard by `receivers`, whose clock_offset_s is the prior.  Keywords: time_source ("reception" / "ticks"),
+    seconds_per_tick, seconds_per_time (the unit of the messages' time), reference, drift (solve one per receiver),
+    min_rows, max_residual_s (> 0: a second pass without the rows beyond it), max_range_nm.  Needs no device."""
+    rcv = _mlat_receivers(receivers)
+    c = _clock_cfg(**cfg)
+    msgs, mptr, nm = _host_list(messages, MESSAGE_DTYPE)
+    recs, rptr, nr = _host_list(receptions, RECEPTION_DTYPE)
+    rxa, xptr, nx = _mlat_list(rx, WIRE_RX_DTYPE)
+    clocks = np.zeros(max(len(rcv), 1), dtype=CLOCK_DTYPE)
+    state = np.zeros(max(nr, 1), dtype=np.uint8)
+    hdr = L.AdsbClockHeader()
+    L.check(L.load().adsb_host_clock_sync(C.byref(c), rcv.ctypes.data if len(rcv) else None, len(rcv), mptr, nm, rptr,
+                                          nr, xptr, nx, clocks.ctypes.data, C.byref(hdr), state.ctypes.data),
+            "adsb_host_clock_sync")
+    out = (clocks[:len(rcv)].copy(), np.frombuffer(bytes(hdr), dtype=CLOCK_HEADER_DTYPE)[0])
+    return out + (state[:nr].copy(),) if row_state else out
+
+
+def host_clock_apply(clocks, messages, receptions, rx=None, **cfg):
+    """adsb_host_clock_apply, the CPU mirror of AdsbDemod.clock_apply: the RECEPTION_DTYPE list with corrected times, in
+    units of seconds_per_tick / 256.  cfg: the keywords of the sync."""
+    clocks = np.ascontiguousarray(clocks, dtype=CLOCK_DTYPE)
+    c = _clock_cfg(**cfg)
+    msgs, mptr, nm = _host_list(messages, MESSAGE_DTYPE)
+    recs, rptr, nr = _host_list(receptions, RECEPTION_DTYPE)
+    rxa, xptr, nx = _mlat_list(rx, WIRE_RX_DTYPE)
+    out = np.zeros(max(nr, 1), dtype=RECEPTION_DTYPE)
+    L.check(L.load().adsb_host_clock_apply(C.byref(c), clocks.ctypes.data if len(clocks) else None, len(clocks), mptr, nm,
+                                           rptr, nr, xptr, nx, out.ctypes.data), "adsb_host_clock_apply")
+    return out[:nr].copy()
+
+
 def level_dbfs(sample_type, total, n_samples):
     """adsb_level_dbfs: 10 log10(total / n_samples / full scale) -- a LEVEL_DTYPE sum as mean power in dBFS (-inf for
     0).  level_dbfs(st, rec["signal_sum"], LEVEL_PULSE_SAMPLES), level_dbfs(st, rec["noise_sum"], LEVEL_QUIET_SAMPLES)."""
@@ -779,11 +827,99 @@ class AdsbDemod:
         L.check(self._lib.adsb_multilaterate(self._h, C.byref(c), rcv.ctypes.data if len(rcv) else None, len(rcv), xptr),
                 "adsb_multilaterate")
 
-    def multilaterate(self, receivers, rx=None, **cfg):
+    def multilaterate(self, receivers, rx=None, clocks=False, clock_cfg=None, **cfg):
         """Where each message of the last correlate call was sent from -> (MLAT_FIX_DTYPE fixes, header).  See
-        multilaterate_async."""
-        self.multilaterate_async(receivers, rx, **cfg)
+        multilaterate_async.  clocks=True: clock sync first (clock_cfg: clock_sync's keywords beyond the times, which
+        are cfg's), then the corrected receptions, then the solver on those, in stream order with ONE host wait: the
+        solver's entry point takes the lists' lengths from the host, so the two counts of the correlate header are read
+        after sync and apply have been enqueued.  The receivers' clock_offset_s are then the sync's priors."""
+        if not clocks:
+            self.multilaterate_async(receivers, rx, **cfg)
+            return self.fetch_mlat()
+        times = {k: cfg[k] for k in ("time_source", "seconds_per_tick") if k in cfg}
+        self.clock_sync_async(receivers, rx, **dict(times, **(clock_cfg or {})))
+        self.clock_apply_async()
+        spt = float(cfg.get("seconds_per_tick") or 1.0 / 12e6)
+        plain = _mlat_receivers(receivers).copy()
+        plain["clock_offset_s"] = 0.0
+        msgs_dev, _, _, hdr_dev = self.correlated_device()
+        recs_dev, n = self.clock_receptions_device()
+        # the lists where they lie; the solver's entry point takes their lengths from the host, so the two counts of the
+        # correlate header are read here, behind everything enqueued above
+        n_msgs, n_recs = C.c_size_t(), C.c_size_t()
+        L.check(self._lib.adsb_fetch_correlated(self._h, None, 0, C.byref(n_msgs), None, 0, C.byref(n_recs)),
+                "adsb_fetch_correlated")
+        rest = {k: v for k, v in cfg.items() if k not in ("time_source", "seconds_per_tick")}
+        self.multilaterate_of_async(plain, (msgs_dev, n_msgs.value), (recs_dev, min(n, n_recs.value)), None,
+                                    time_source="reception", seconds_per_tick=spt / 256.0, **rest)
         return self.fetch_mlat()
+
+    def clock_sync_async(self, receivers, rx=None, **cfg):
+        """adsb_clock_sync alone: the last correlate call's result, where it lies on the device.  rx as for
+        multilaterate_async.  See host_clock_sync for receivers and the keywords."""
+        rcv = _mlat_receivers(receivers)
+        c = _clock_cfg(**cfg)
+        keep, xptr = (None, rx) if isinstance(rx, int) else _mlat_list(rx, WIRE_RX_DTYPE)[:2]
+        L.check(self._lib.adsb_clock_sync(self._h, C.byref(c), rcv.ctypes.data if len(rcv) else None, len(rcv), xptr),
+                "adsb_clock_sync")
+
+    def clock_sync(self, receivers, rx=None, **cfg):
+        """Every receiver's clock against the reference, from the position messages of the last correlate call ->
+        (CLOCK_DTYPE clocks, the CLOCK_HEADER_DTYPE record).  clock_apply() then corrects the receptions."""
+        self.clock_sync_async(receivers, rx, **cfg)
+        return self.fetch_clocks()
+
+    def clock_sync_of_async(self, receivers, messages, receptions, rx=None, **cfg):
+        """adsb_clock_sync_of alone: any correlate result, each list a host array or a (device pointer, count) pair."""
+        rcv = _mlat_receivers(receivers)
+        c = _clock_cfg(**cfg)
+        msgs, mptr, nm = _mlat_list(messages, MESSAGE_DTYPE)
+        recs, rptr, nr = _mlat_list(receptions, RECEPTION_DTYPE)
+        rxa, xptr, nx = _mlat_list(rx, WIRE_RX_DTYPE)
+        L.check(self._lib.adsb_clock_sync_of(self._h, C.byref(c), rcv.ctypes.data if len(rcv) else None, len(rcv), mptr,
+                                             nm, rptr, nr, xptr, nx), "adsb_clock_sync_of")
+
+    def clock_sync_of(self, receivers, messages, receptions, rx=None, **cfg):
+        """adsb_clock_sync_of -> (clocks, header).  See host_clock_sync, its CPU mirror."""
+        self.clock_sync_of_async(receivers, messages, receptions, rx, **cfg)
+        return self.fetch_clocks()
+
+    def fetch_clocks(self):
+        """adsb_fetch_clocks: waits for the last clock-sync call -> (clocks, the CLOCK_HEADER_DTYPE record)."""
+        hdr, got = L.AdsbClockHeader(), C.c_size_t()
+        clocks = np.zeros(256, dtype=CLOCK_DTYPE)
+        rc = self._lib.adsb_fetch_clocks(self._h, clocks.ctypes.data, 256, C.byref(got), C.byref(hdr))
+        if rc != L.ADSB_OK and not (rc == L.ADSB_E_ARG and hdr.flags & L.ADSB_CLOCK_HDR_BAD_INDEX):
+            L.check(rc, "adsb_fetch_clocks")
+        return clocks[:got.value].copy(), np.frombuffer(bytes(hdr), dtype=CLOCK_HEADER_DTYPE)[0]
+
+    def clocks_device(self):
+        """adsb_clocks_device: device addresses (clocks, header); no synchronisation."""
+        k, h = C.c_void_p(), C.c_void_p()
+        L.check(self._lib.adsb_clocks_device(self._h, C.byref(k), C.byref(h)), "adsb_clocks_device")
+        return k.value, h.value
+
+    def clock_apply_async(self):
+        """adsb_clock_apply alone: the last clock sync's receptions with corrected times, on the device."""
+        L.check(self._lib.adsb_clock_apply(self._h), "adsb_clock_apply")
+
+    def clock_apply(self):
+        """adsb_clock_apply -> the corrected RECEPTION_DTYPE list, times in units of seconds_per_tick / 256: an argument
+        for multilaterate_of(..., time_source="reception", seconds_per_tick=spt / 256) with all clock offsets 0."""
+        self.clock_apply_async()
+        got, total = C.c_size_t(), C.c_size_t()
+        L.check(self._lib.adsb_fetch_clock_receptions(self._h, None, 0, C.byref(got), C.byref(total)),
+                "adsb_fetch_clock_receptions")
+        out = np.zeros(max(total.value, 1), dtype=RECEPTION_DTYPE)
+        L.check(self._lib.adsb_fetch_clock_receptions(self._h, out.ctypes.data, total.value, C.byref(got), C.byref(total)),
+                "adsb_fetch_clock_receptions")
+        return out[:got.value].copy()
+
+    def clock_receptions_device(self):
+        """adsb_clock_receptions_device: (device address of the corrected receptions, their count's upper bound)."""
+        p, n = C.c_void_p(), C.c_size_t()
+        L.check(self._lib.adsb_clock_receptions_device(self._h, C.byref(p), C.byref(n)), "adsb_clock_receptions_device")
+        return p.value, n.value
 
     def multilaterate_of_async(self, receivers, messages, receptions, rx=None, **cfg):
         """adsb_multilaterate_of alone: any correlate result, each list a host array or a (device pointer, count)

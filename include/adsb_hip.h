@@ -652,6 +652,146 @@ int adsb_mlat_device(adsb_ctx *ctx, const adsb_mlat_fix **fixes_dev, const void 
 int adsb_debug_mlat_geometry(uint32_t *lanes_per_message, uint32_t *messages_per_block);
 
 /*
+ * Clock sync: every receiver's clock offset and drift against one reference receiver, from the position messages of a
+ * correlated list.  An airborne position message says where it was sent from, so a message heard by two receivers
+ * measures the difference of their clocks; all such messages of a list are one linear least-squares problem.  f64;
+ * stateless; computed on the device.  adsb_clock_apply then writes the receptions with corrected times, which
+ * multilaterate takes through its TIME_RECEPTION input.
+ *   INPUT  a correlate result msgs[M] / recs[N]; adsb_mlat_receiver receivers[R], 1 <= R <= 256, positions as for
+ *     multilaterate; clock_offset_s is the caller's PRIOR, the coarse alignment it already used to make correlate group
+ *     the receptions (0 if none; |.| <= 1e6); optionally adsb_wire_rx rx[n_rx]; an adsb_clock_cfg.
+ *   TIMES  Multilaterate's, by the same functions: time_source (RECEPTION or TICKS), seconds_per_tick (spt; TICKS: 0 =
+ *     1 / 12e6), the integer difference dticks_k of used reception k against the message's first used reception (TICKS:
+ *     mod 2^48, sign-extended), and the USED rule (the earliest reception per receiver; reception 0 is always used).  A
+ *     message's own time is tau_m = (double)(int64)(msgs[m].time - msgs[0].time) x cfg.seconds_per_time, the unit of
+ *     adsb_message.time (RECEPTION: 0 = seconds_per_tick; TICKS: 0 is ADSB_E_ARG).
+ *   ELIGIBLE  The single-message position decode ("Positions from single messages") is applied to the message bytes
+ *     with the site { latitude, longitude of the first used reception's receiver, cfg.max_range_nm (0: 180) }.  The
+ *     message is eligible when the decode gives ADSB_FIX_VALID without ADSB_FIX_SURFACE, gives ADSB_FIX_ALT, the altitude
+ *     has its Q bit set and a non-zero code (multilaterate's ALTITUDE rule), it has at most ADSB_MLAT_MAX_RECEPTIONS
+ *     receptions and at least two of them are used.  Its position p is the ECEF point of (latitude, longitude,
+ *     altitude ft x 0.3048), by the conversion multilaterate uses for its stations.  Barometric altitude is taken as
+ *     height above the ellipsoid: a known approximation, tens of metres of height, which a receiver's offset absorbs
+ *     only in part.
+ *   ROWS  Each used reception k >= 1 of an eligible message gives one row (i = r_0, j = r_k, tau_m, y) with
+ *       y = (double)dticks_k x spt - (prior_j - prior_i) - (|p - s_j| - |p - s_i|) / ADSB_MLAT_C
+ *     in the slot of its reception index, msgs[m].first + k.  Every other slot is empty.  No compaction, no atomics.
+ *   MODEL  Receiver r's clock shows true time plus prior_r + a_r + b_r x tau.  A row says y = (a_j + b_j tau) -
+ *     (a_i + b_i tau).  cfg.reference (< R) has a = b = 0.
+ *   PAIRS  A row's pair is (lo, hi) = (min, max) of (i, j); its y' = y if j = hi, else -y.  Rows are ordered by (pair,
+ *     slot) with a stable radix sort whose key puts empty slots last.  A pair's sums are n and the five f64 sums of tau,
+ *     tau^2, y', tau y', y'^2: 64 partial sums folded in a butterfly.  Partial l adds the pair's rows q = l (mod 64), q
+ *     counting the pair's rows in that order, in ascending q, starting from 0; then v[l] = v[l] + v[l ^ m] for m = 32,
+ *     16, 8, 4, 2, 1.  Contraction off.
+ *   REACHED  Pairs with n >= cfg.min_rows (0: 1) are EDGES.  Receivers connected to the reference through edges are
+ *     REACHED; every other receiver gets a = b = 0.  Rows of pairs that are not edges take no part in the solve.
+ *   SOLVE  Unknowns (a_r, b_r) per reached receiver other than the reference, in ascending r, interleaved; without
+ *     ADSB_CLOCK_DRIFT in cfg.flags, a_r only.  The normal equations come from the edges' sums: the entry of (a_u, a_u)
+ *     is the sum of n over u's edges, (b_u, a_u) of the tau sums, (b_u, b_u) of the tau^2 sums, each added in ascending
+ *     partner index starting from 0; between receivers u != v joined by an edge the entries are minus that edge's sums;
+ *     the right-hand side of a_u adds +(sum of y') for each partner below u and -(sum of y') for each partner above,
+ *     of b_u likewise with the sums of tau y', in ascending partner index.  L D Lt without pivoting, left-looking: entry
+ *     (i, j) is A_ij - sum over k < j of (L_ik x D_k) x L_jk, ascending k.  Then v = the right-hand side; for k
+ *     ascending, v_i = v_i - L_ik x v_k for every i > k; v_i = v_i / D_i; for k descending, v_i = v_i - L_ki x v_k
+ *     for every i < k.  A pivot that is not greater than 1e-12 x its diagonal entry ends the solve with drift: the
+ *     whole solve is repeated for offsets only and the header gets ADSB_CLOCK_HDR_DRIFT_DROPPED.  If that fails too,
+ *     the header gets ADSB_CLOCK_HDR_SINGULAR and every a and b is 0.
+ *   SECOND PASS  With cfg.max_residual_s > 0, the residual y' - ((a_hi + b_hi tau) - (a_lo + b_lo tau)) of every row
+ *     under the first solution is computed; rows with |residual| > max_residual_s are DROPPED (their slots become
+ *     empty), and order, sums, reached set and solve are redone over the kept rows.  0: one pass.
+ *   OUTPUT  adsb_clock clocks[R]: offset_s = prior + a, fine_offset_s = a, drift = b; n_rows the kept rows the receiver
+ *     takes part in (edges or not), n_dropped the dropped ones, n_partners its edges; residual_rms_s =
+ *     sqrt(max(S, 0) / n_rows) with S the sum over its pairs, in ascending partner index, of the pair's
+ *     sum(y'^2) - 2 da sum(y') - 2 db sum(tau y') + da^2 n + 2 da db sum(tau) + db^2 sum(tau^2), da and db the pair's
+ *     hi minus lo solution (0 when n_rows = 0; a closed form, exact to about 1e-7 of the largest |y'|).  flags: REFERENCE, REACHED (the reference is), DRIFT (b was solved).
+ *     adsb_clock_header: n_messages; n_eligible; n_rows (before dropping); n_dropped; n_reached (the reference
+ *     included); flags: ADSB_CLOCK_HDR_BAD_INDEX as multilaterate defines BAD_INDEX (the message is skipped, its
+ *     stations and ticks never read), DRIFT_DROPPED, SINGULAR.
+ *   APPLY  adsb_clock_apply writes adsb_reception corrected[N]: order, frame and receiver as in recs, and for every
+ *     reception that a message owns inside recs[N] and whose own receiver (and, with TICKS, frame) the lists have
+ *       time' = (uint64)(256 x d - llrint(256 x (offset_s[r] + drift[r] x tau_m) / spt))        (mod 2^64)
+ *     d the reception's raw time as a signed integer difference against the raw time of recs[msgs[0].first] (TICKS:
+ *     mod 2^48, sign-extended; 0 is taken for that raw time if the lists do not have it), m the reception's message.  The
+ *     unit of time' is spt / 256: pass `corrected` to adsb_multilaterate_of with TIME_RECEPTION, seconds_per_tick =
+ *     spt / 256 and every clock_offset_s = 0.  An unreached receiver's receptions get offset = prior, drift = 0 (see
+ *     its clock's flags).  Messages without a position are corrected like every other: they are what this is for.
+ *     Every other reception keeps its raw time.
+ * No atomics, no library scan or reduce-by-key for the float sums, nothing depends on scheduling: two runs give the same
+ * bytes.  The CPU mirror (adsb_host_clock_sync / adsb_host_clock_apply) evaluates the same text in the same order; what
+ * may differ is the last bit of the math libraries' sin / cos / sqrt in the decode, the ECEF conversion and the ranges.
+ */
+#define ADSB_CLOCK_DRIFT 0x1u              /* adsb_clock_cfg.flags: solve a drift per receiver */
+#define ADSB_CLOCK_REFERENCE 0x1u          /* adsb_clock.flags */
+#define ADSB_CLOCK_REACHED 0x2u
+#define ADSB_CLOCK_HAS_DRIFT 0x4u          /* DRIFT: b was solved for this receiver */
+#define ADSB_CLOCK_HDR_BAD_INDEX 0x1u      /* adsb_clock_header.flags */
+#define ADSB_CLOCK_HDR_DRIFT_DROPPED 0x2u
+#define ADSB_CLOCK_HDR_SINGULAR 0x4u
+typedef struct adsb_clock_cfg {     /* 64 bytes */
+    uint32_t time_source;         /* ADSB_MLAT_TIME_*                                             */
+    uint32_t flags;               /* ADSB_CLOCK_DRIFT                                             */
+    uint32_t reference;           /* < n_receivers                                                */
+    uint32_t min_rows;            /* rows that make a pair an edge; 0: 1                          */
+    double   seconds_per_tick;    /* RECEPTION: > 0; TICKS: 0 = 1 / 12e6; at most 1               */
+    double   seconds_per_time;    /* unit of adsb_message.time; RECEPTION: 0 = seconds_per_tick   */
+    double   max_residual_s;      /* 0: one pass                                                  */
+    double   max_range_nm;        /* 0: 180; at most 180                                          */
+    uint64_t reserved[2];         /* 0 */
+} adsb_clock_cfg;
+typedef struct adsb_clock {         /* 64 bytes */
+    double   offset_s;            /* prior + a */
+    double   fine_offset_s;       /* a */
+    double   drift;               /* b, s/s */
+    float    residual_rms_s;      /* over the kept rows the receiver takes part in */
+    uint32_t n_rows;
+    uint32_t n_dropped;
+    uint32_t n_partners;          /* edges */
+    uint32_t flags;               /* ADSB_CLOCK_REFERENCE, REACHED, HAS_DRIFT */
+    uint32_t reserved[5];         /* 0 */
+} adsb_clock;
+typedef struct adsb_clock_header {  /* 64 bytes */
+    uint64_t n_messages, n_eligible, n_rows, n_dropped, n_reached, flags;
+    uint64_t reserved[2];         /* 0 */
+} adsb_clock_header;
+/* The ctx's last correlate result, where it lies: enqueued on the ctx's stream behind it, nothing read back.  receivers
+ * is host memory; rx (NULL with TIME_RECEPTION) as for adsb_multilaterate.  Buffers are allocated on first use and grown
+ * when needed (may wait for earlier work): 44 bytes per reception of capacity (rows, keys and orders, the corrected
+ * list), 1 byte per message, the sorts' temporary storage, 6 MiB of pair sums (48 bytes per pair and pass), the 2 MiB of
+ * the normal equations, and copies of host lists; a ctx that never calls it allocates nothing and launches exactly the kernels it
+ * launched before.  Replaces the result of an earlier clock-sync call.  ADSB_E_ARG for a NULL ctx, cfg or receivers,
+ * n_receivers outside 1..256, a receiver or cfg value that is negative where it may not be, not finite or out of the
+ * ranges above, an unknown time_source or flag, reference >= n_receivers, TICKS without rx or with seconds_per_time = 0;
+ * ADSB_E_STATE before any correlate call. */
+int adsb_clock_sync(adsb_ctx *ctx, const adsb_clock_cfg *cfg, const adsb_mlat_receiver *receivers, uint32_t n_receivers,
+                    const adsb_wire_rx *rx);
+/* Any lists, as for adsb_multilaterate_of, with its errors.  Device lists must stay as they are until adsb_clock_apply
+ * has run, if it is called. */
+int adsb_clock_sync_of(adsb_ctx *ctx, const adsb_clock_cfg *cfg, const adsb_mlat_receiver *receivers,
+                       uint32_t n_receivers, const adsb_message *msgs, size_t n_msgs, const adsb_reception *recs,
+                       size_t n_recs, const adsb_wire_rx *rx, size_t n_rx);
+/* Waits and copies: clocks receives min(n_receivers, max) records and *n (optional) that number; *header (optional) the
+ * totals.  ADSB_E_STATE before any clock-sync call; ADSB_E_ARG for a NULL ctx, NULL clocks with max > 0, or, after
+ * copying, when the header has ADSB_CLOCK_HDR_BAD_INDEX. */
+int adsb_fetch_clocks(adsb_ctx *ctx, adsb_clock *clocks, size_t max, size_t *n, adsb_clock_header *header);
+/* For device-side consumers; does not synchronise.  clocks[] and the header in device memory (each optional), valid until
+ * the next clock-sync call on this ctx and ordered on the ctx's stream behind it.  ADSB_E_STATE before any. */
+int adsb_clocks_device(adsb_ctx *ctx, const adsb_clock **clocks_dev, const void **header_dev);
+/* Corrects the receptions of the lists the last clock-sync call worked on, by its clocks, on the ctx's stream behind it.
+ * Replaces the result of an earlier apply.  After adsb_clock_sync those lists are the ctx's correlate result: call this
+ * before the next correlate call replaces it.  ADSB_E_STATE without a clock-sync call. */
+int adsb_clock_apply(adsb_ctx *ctx);
+/* Waits and copies min(N, max) corrected receptions; *n (optional) that number, *n_total (optional) N.  ADSB_E_STATE
+ * before any adsb_clock_apply. */
+int adsb_fetch_clock_receptions(adsb_ctx *ctx, adsb_reception *corrected, size_t max, size_t *n, size_t *n_total);
+/* For device-side consumers; does not synchronise: corrected[] in device memory, an argument for adsb_multilaterate_of,
+ * and its length's upper bound (the list's N as the host knows it).  ADSB_E_STATE before any adsb_clock_apply. */
+int adsb_clock_receptions_device(adsb_ctx *ctx, const adsb_reception **corrected_dev, size_t *n);
+/* Messages per workgroup of the rows kernel and the partial sums of a pair (a pair's partial sum holds every 64th of its
+ * rows), either may be NULL: the sizes at which the kernels take another path, for tests.  The result does not depend
+ * on the first. */
+int adsb_debug_clock_geometry(uint32_t *messages_per_block, uint32_t *pair_partials);
+
+/*
  * Tracker + global CPR position decode on the device: what the reference's display
  * threads do with every AdsbPacket, `handle_aircraft_update` (src/adsb/aircraft.rs:158-165 ->
  * Aircraft::handle_packet, aircraft.rs:48-111 -> cpr::calculate_geographic_position, cpr.rs:135-147),

@@ -161,6 +161,25 @@ int adsb_host_multilaterate(const adsb_mlat_cfg *cfg, const adsb_mlat_receiver *
                             const adsb_wire_rx *rx, size_t n_rx, adsb_mlat_fix *fixes, adsb_mlat_header *header);
 
 /*
+ * CPU mirror of adsb_clock_sync_of (adsb_hip.h, "Clock sync"): the same clocks and header from the same program text as
+ * the device's -- the rows, the pair order, the 64 partial sums folded in the same butterfly, the normal equations, the
+ * factorisation and the second pass -- on one core, no device needed.  All arrays host memory; clocks receives
+ * n_receivers records; *header is optional; row_state (optional) receives one byte per reception slot: 0 empty, 1 a kept
+ * row, 2 a dropped row.  The same argument errors as adsb_clock_sync_of, and ADSB_E_ARG for NULL clocks; ADSB_E_ARG after
+ * writing everything when the header has ADSB_CLOCK_HDR_BAD_INDEX.
+ */
+int adsb_host_clock_sync(const adsb_clock_cfg *cfg, const adsb_mlat_receiver *receivers, uint32_t n_receivers,
+                         const adsb_message *msgs, size_t n_msgs, const adsb_reception *recs, size_t n_recs,
+                         const adsb_wire_rx *rx, size_t n_rx, adsb_clock *clocks, adsb_clock_header *header,
+                         uint8_t *row_state);
+/* CPU mirror of adsb_clock_apply: corrected[n_recs] from clocks[n_receivers] (of which offset_s and drift are read) and
+ * the cfg and lists of the sync.  The argument errors of adsb_host_clock_sync (receivers are not needed), and ADSB_E_ARG
+ * for NULL clocks, or NULL corrected with n_recs > 0. */
+int adsb_host_clock_apply(const adsb_clock_cfg *cfg, const adsb_clock *clocks, uint32_t n_receivers,
+                          const adsb_message *msgs, size_t n_msgs, const adsb_reception *recs, size_t n_recs,
+                          const adsb_wire_rx *rx, size_t n_rx, adsb_reception *corrected);
+
+/*
  * CPU mirror of the per-frame fix decode of a table or bank with a fixes reserve (adsb_hip.h, "Positions from single
  * messages"): the same program text as the device's, no device needed.  *out = the adsb_fix of an aircraft whose only
  * frame since admission is this one, heard at frame time `time` by a receiver at *site: accepted: the fix with
