@@ -153,6 +153,7 @@ ADSB_HD inline void fix_decode(const adsb_site &site, const uint8_t *bytes, adsb
     f.longitude = lon;
     f.range_nm = (float)range;
     f.bearing_deg = (float)bearing;
+    if (f.bearing_deg >= 360.0f) f.bearing_deg = 0.0f; // the one rounding lifts a bearing within 1.5e-5 below 360 to 360
     f.flags = flags;
 }
 

@@ -1244,7 +1244,9 @@ int adsb_track_bank_fetch_fused_levels(adsb_track_bank *bank, adsb_fused_level *
  *     lon  = dLon (m + x), brought into [-180, 180] (cpr.rs:27-31)
  * range = haversine distance from the site in nautical miles (R = 3440.065 NM), bearing = the initial bearing
  * atan2(sin dl cos p2, cos p1 sin p2 - sin p1 cos p2 cos dl) in degrees in [0, 360); all of it f64, each rounded to
- * f32 once.  The frame is REJECTED (counted in n_rejected, the fix stays) if |lat| > 90 or the range exceeds the
+ * f32 once.  A bearing whose rounding to f32 gives 360 is returned as 0, so bearing_deg itself lies in [0, 360).  The
+ * range limit is tested on the f64 range: the f32 range_nm of an accepted frame may round up past a fractional limit
+ * by half an f32 step (7.6e-6 NM at 180 NM).  The frame is REJECTED (counted in n_rejected, the fix stays) if |lat| > 90 or the range exceeds the
  * site's limit: max_range_nm for an airborne message, min(max_range_nm, 45) for a surface one.  The decode picks the
  * position nearest the site among those half a zone apart, so it is right only for aircraft within half a zone: 180 NM
  * airborne, 45 NM surface; hence max_range_nm must lie in (0, 180].

@@ -7,6 +7,7 @@ import math
 
 import numpy as np
 
+from tests import fix_cases as FC
 from tests import fix_model as F
 from tests import mlat_cases as K
 from tests import mlat_model as M
@@ -48,15 +49,16 @@ def merge(parts, n_rcv):
 
 
 def scenario(oracle, n_rcv, n_msgs, seed, span_s=60.0, spt=SPT_12MHZ, p_heard=0.7, offset_s=1e-3, drift=50e-6,
-             heard=None, times=None, frames_of=None, tick_base=5_000_000_000, mod48=False, priors=None, extra=None):
+             heard=None, times=None, frames_of=None, tick_base=5_000_000_000, mod48=False, priors=None, extra=None,
+             centre=(K.LAT0, K.LON0)):
     """n_msgs position messages over span_s seconds, each heard by every receiver with probability p_heard (heard: the
     receivers per message instead), by clocks offset_s and drift (bounds of uniform draws, or arrays) off.
     -> dict(rcv (clock_offset_s = the priors), lst, pos, offsets, drifts, t (emission times), cfg (time keywords))"""
     rng = np.random.default_rng(seed)
     offsets = rng.uniform(-offset_s, offset_s, n_rcv) if np.isscalar(offset_s) else np.asarray(offset_s, dtype=float)
     drifts = rng.uniform(-drift, drift, n_rcv) if np.isscalar(drift) else np.asarray(drift, dtype=float)
-    rcv = K.receivers(n_rcv, seed=1000 + seed)
-    pos, _ = K.emitters(oracle, n_msgs, seed=2000 + seed)
+    rcv = K.receivers(n_rcv, seed=1000 + seed, centre=centre)
+    pos, _ = K.emitters(oracle, n_msgs, seed=2000 + seed, centre=centre)
     frames = (frames_of or position_frames)(oracle, pos)
     t = np.sort(rng.uniform(0.5, span_s, n_msgs)) if times is None else np.asarray(times, dtype=float)
     if heard is None:
@@ -107,6 +109,34 @@ def case_lists(oracle):
 def many_receivers(oracle):
     """256 receivers, all hearing two emitters half a minute apart."""
     return scenario(oracle, 256, 2, seed=68, p_heard=1.0, times=[1.0, 31.0])
+
+
+POLAR_CENTRE = (86.8, 179.8)
+
+
+def polar(oracle):
+    """6 receivers and 120 messages around (86.8, 179.8): the receivers lie on both sides of the antimeridian, the
+    emitters on both sides of it and of the 87-degree latitude at which the zone count drops from 2 to 1."""
+    return scenario(oracle, 6, 120, seed=12, centre=POLAR_CENTRE)
+
+
+def exact_counts(sc, max_range_nm=180.0):
+    """(n_eligible, n_rows) that the exact reference of tests/fix_cases.py predicts for a scenario's list: a message
+    heard by two receivers or more, with an altitude, whose position the first reception's receiver accepts (no
+    message of a scenario may be a tie); one row per further receiver."""
+    lst, eligible, rows = sc["lst"], 0, 0
+    for m in lst["msgs"]:
+        mine = lst["recs"][int(m["first"]):int(m["first"]) + int(m["n_receptions"])]
+        used = len(set(int(r) for r in mine["receiver"]))
+        if used < 2 or M.altitude_of(m["bytes"]) is None:
+            continue
+        first = sc["rcv"][int(mine["receiver"][0])]
+        d = FC.exact_decode((float(first["latitude"]), float(first["longitude"]), max_range_nm), bytes(m["bytes"]))
+        assert not d["tie"]
+        if d["verdict"] == FC.ACCEPTED and d["flags"] & (F.SURFACE | F.ALT) == F.ALT:
+            eligible += 1
+            rows += used - 1
+    return eligible, rows
 
 
 def outliers(oracle, seed=11, n_msgs=300, share=0.05):

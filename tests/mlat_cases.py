@@ -15,18 +15,24 @@ SPT_NS = 1e-9
 
 
 def _offset(lat0, lon0, east, north):
-    """Degrees of a point east / north metres from (lat0, lon0): good enough to place things."""
-    return lat0 + north / 111200.0, lon0 + east / (111200.0 * math.cos(math.radians(lat0)))
+    """Degrees of a point east / north metres from (lat0, lon0): good enough to place things.  A longitude past the
+    antimeridian comes back into [-180, 180)."""
+    lat, lon = lat0 + north / 111200.0, lon0 + east / (111200.0 * math.cos(math.radians(lat0)))
+    if lon >= 180.0:
+        lon -= 360.0
+    elif lon < -180.0:
+        lon += 360.0
+    return lat, lon
 
 
-def receivers(n, seed, clock_offsets=None):
-    """n receivers on rings of 36-60 km radius, at heights of 300-1800 m, spread in azimuth."""
+def receivers(n, seed, clock_offsets=None, centre=(LAT0, LON0)):
+    """n receivers on rings of 36-60 km radius around `centre`, at heights of 300-1800 m, spread in azimuth."""
     rng = np.random.default_rng(seed)
     out = np.zeros(n, dtype=M.RECEIVER_DTYPE)
     for k in range(n):
         az = 2 * math.pi * (k + rng.uniform(-0.25, 0.25)) / n
         rad = rng.uniform(36e3, 60e3)
-        lat, lon = _offset(LAT0, LON0, rad * math.sin(az), rad * math.cos(az))
+        lat, lon = _offset(centre[0], centre[1], rad * math.sin(az), rad * math.cos(az))
         out[k] = (lat, lon, rng.uniform(300.0, 1800.0), 0.0 if clock_offsets is None else clock_offsets[k])
     return out
 
@@ -37,15 +43,15 @@ def altitude_code(height_m):
     return (n >> 4) << 5 | 0x10 | (n & 0xF), (n * 25 - 1000) * 0.3048
 
 
-def emitters(oracle, n, seed, max_range=150e3):
-    """n emitters 0-150 km out at 3-12 km: (ECEF positions, their frames).  Each height is one its frame's altitude code
+def emitters(oracle, n, seed, max_range=150e3, centre=(LAT0, LON0)):
+    """n emitters 0-150 km out from `centre` at 3-12 km: (ECEF positions, their frames).  Each height is one its frame's altitude code
     decodes to exactly, so the altitude equation is consistent with the truth."""
     rng = np.random.default_rng(seed)
     pos, frames = [], []
     for i in range(n):
         az, rad = rng.uniform(0, 2 * math.pi), max_range * math.sqrt(rng.uniform(0, 1))
         code, h = altitude_code(rng.uniform(3000.0, 12000.0))
-        lat, lon = _offset(LAT0, LON0, rad * math.sin(az), rad * math.cos(az))
+        lat, lon = _offset(centre[0], centre[1], rad * math.sin(az), rad * math.cos(az))
         pos.append(M.ecef_of(lat, lon, h))
         frames.append(traffic.position_frame(oracle, 0x400000 + i, i & 1, int(rng.integers(0, 1 << 17)),
                                              int(rng.integers(0, 1 << 17)), alt_code=code, tc=11))

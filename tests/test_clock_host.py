@@ -60,6 +60,31 @@ def test_mirror_equals_model(lib, cases):
           f"{CM.MIRROR_VS_MODEL_MEASURED_DRIFT:.3g}, tolerance {CM.MIRROR_VS_MODEL_TOL_DRIFT:.3g})")
 
 
+def check_polar(sync, oracle, reference_sync, tol_s, tol_drift, what):
+    """clock_cases.polar: the single-message decode at sites and targets either side of the antimeridian and of the
+    87-degree transition.  The counts are the exact reference's (tests/fix_cases.py), the clocks the reference
+    implementation's under the given constants -> (largest offset gap, largest drift gap)."""
+    sc = CC.polar(oracle)
+    lons, lats = sc["rcv"]["longitude"], [np.degrees(M.geodetic_of(p)[2]) for p in sc["pos"]]
+    assert (lons > 170).any() and (lons < -170).any() and min(lats) < 87 < max(lats)
+    eligible, rows = CC.exact_counts(sc)
+    assert eligible > 100 and rows > 300
+    got, gh = sync(sc["rcv"], sc["lst"], **sc["cfg"])[:2]
+    want, wh = reference_sync(sc["rcv"], sc["lst"], **sc["cfg"])[:2]
+    assert (int(gh["n_eligible"]), int(gh["n_rows"])) == (int(wh["n_eligible"]), int(wh["n_rows"])) == (eligible, rows)
+    da, db = same_clocks(got, gh, want, wh, sc["rcv"]["clock_offset_s"], tol_s, tol_drift, what)
+    print(f"polar scenario, {what}: gap {da:.3g} s, {db:.3g} s/s; {eligible} eligible messages, {rows} rows")
+    return da, db
+
+
+def test_polar_antimeridian_scenario(lib, oracle):
+    check_polar(mirror_sync, oracle, model_sync, CM.MIRROR_VS_MODEL_TOL_S, CM.MIRROR_VS_MODEL_TOL_DRIFT, "mirror vs model")
+    sc = CC.polar(oracle)
+    ta, tb = CC.truth(sc)
+    got = mirror_sync(sc["rcv"], sc["lst"], **sc["cfg"])[0]
+    assert np.abs(got["fine_offset_s"] - ta).max() < 2e-7 and np.abs(got["drift"] - tb).max() < 2e-8   # as check_truth's
+
+
 TRUTH_ROWS = (("6 receivers, 12 MHz ticks", dict(n_rcv=6, n_msgs=300, seed=21)),
               ("8 receivers, 2 MHz samples", dict(n_rcv=8, n_msgs=300, seed=22, spt=0.5e-6)),
               ("33 receivers, heard 0.3, 20 s", dict(n_rcv=33, n_msgs=300, seed=23, p_heard=0.3, span_s=20.0)))

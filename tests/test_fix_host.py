@@ -1,7 +1,7 @@
 """adsb_host_fix_of, the CPU mirror of the tracker's single-message position decode (the text the device compiles too,
 air_rs_amd/csrc/adsb_fix.h), against tests/fix_model.py: random frames, encoded true positions, and known answers (CPU
-tier).  Tolerances: integers, flags and the f32 surface fields exact; latitude and longitude 1e-9 degree (the tracker
-tests' bound for positions); range 1e-4 NM and bearing 1e-4 degree, above f32 spacing at 256 NM and 360 degrees."""
+tier).  Tolerances: integers, flags and the f32 surface fields exact; latitude and longitude equal as doubles (no math
+library before NL, an integer); range 1e-4 NM and bearing 1e-4 degree, above f32 spacing at 256 NM and 360 degrees."""
 import ctypes as C
 import math
 

@@ -68,6 +68,13 @@ def test_case_lists_device_vs_mirror_and_model(ctx, cases):
           f"out of the corrected-time comparison: {left_out}")
 
 
+def test_polar_antimeridian_scenario(ctx, oracle):
+    H.check_polar(device_sync(ctx), oracle, H.mirror_sync, CM.DEVICE_VS_MIRROR_TOL_S, CM.DEVICE_VS_MIRROR_TOL_DRIFT,
+                  "device vs mirror")
+    H.check_polar(device_sync(ctx), oracle, H.model_sync, CM.MIRROR_VS_MODEL_TOL_S + CM.DEVICE_VS_MIRROR_TOL_S,
+                  CM.MIRROR_VS_MODEL_TOL_DRIFT + CM.DEVICE_VS_MIRROR_TOL_DRIFT, "device vs model")
+
+
 def test_shapes(ctx, oracle):
     for name, sc, kw, expect in H.shape_lists(oracle):
         H.check_shape(device_sync(ctx), name, sc, kw, expect, CM.DEVICE_VS_MIRROR_TOL_S, CM.DEVICE_VS_MIRROR_TOL_DRIFT,
