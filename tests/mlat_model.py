@@ -35,6 +35,39 @@ EP2 = (A * A - B * B) / (B * B)
 MIRROR_VS_MODEL_MEASURED_M = 6.3e-5
 MIRROR_VS_MODEL_TOL_M = 10 * MIRROR_VS_MODEL_MEASURED_M
 
+# The other fields of a fix, measured the same way over the case lists and the edge lists of tests/mlat_cases.py
+# (profiles/mlat_edges_checks.txt), over fixes with equal integers and pdop <= 20; each tolerance is 10 x the measured gap.
+#   hdop, vdop             relative
+#   time_s, height_m       absolute, seconds and metres
+#   residual_rms_m         relative above RMS_FLOOR_M: |a - b| <= RMS_FLOOR_M + rel x the reference's
+# RMS_FLOOR_M is derived, not measured.  A coordinate of the point is about 6.4e6 m, which an f64 holds to 6.4e6 x 2^-52
+# = 1.4e-9 m, so no residual of a range row (range + d - rho, the range taken from three such coordinates) is known
+# more finely than a few of these steps however the sums are ordered.  Where a fix is exactly determined (4 free
+# receivers, or 3 and the altitude) the rms is nothing but that noise, plus the s^2 / (2 range) < 1e-9 m that a last step
+# s < 0.01 m leaves undone, and two summation orders differ in it by factors.  16 steps cover the three coordinates,
+# the up to five rows of such a fix and that remainder: 16 x 6.4e6 x 2^-52 = 2.3e-8 m.
+RMS_FLOOR_M = 16 * 6.4e6 * 2.0 ** -52
+MIRROR_VS_MODEL_MEASURED = {"hdop": 0.0, "vdop": 0.0, "time_s": 2.1e-13, "height_m": 3.2e-6, "residual_rms_m": 0.0}
+# hdop, vdop and residual_rms_m are f32, and mirror and model gave the same f32 everywhere: measured 0.  Ten times
+# nothing would demand equal bits of two f64 results that may differ in their last places, which the rounding to f32
+# turns into one step of that format; so their tolerance is never below that step, 2^-23.
+F32_STEP = 2.0 ** -23
+MIRROR_VS_MODEL_TOL = {k: max(10 * v, F32_STEP) if k in ("hdop", "vdop", "residual_rms_m") else 10 * v
+                       for k, v in MIRROR_VS_MODEL_MEASURED.items()}
+
+
+def gaps_of(a, b):
+    """{field: (gap, tolerance)} of fix a against the reference fix b, in the units above."""
+    out = {}
+    for k in ("hdop", "vdop"):
+        out[k] = abs(float(a[k]) - float(b[k])) / float(b[k]) if b[k] > 0 else float(a[k] != b[k])
+    for k in ("time_s", "height_m"):
+        out[k] = abs(float(a[k]) - float(b[k]))
+    rms = float(b["residual_rms_m"])
+    over = abs(float(a["residual_rms_m"]) - rms) - RMS_FLOOR_M
+    out["residual_rms_m"] = max(over, 0.0) / rms if rms > 0 else float(over > 0)
+    return {k: (v, MIRROR_VS_MODEL_TOL[k]) for k, v in out.items()}
+
 
 def ecef_of(lat_deg, lon_deg, h):
     phi, lam = math.radians(lat_deg), math.radians(lon_deg)

@@ -8,13 +8,16 @@ from tests import mlat_cases as K
 from tests import mlat_model as M
 
 
-def same_fixes(got, want, lasts, tol_step, name, tol_m=M.MIRROR_VS_MODEL_TOL_M):
+def same_fixes(got, want, lasts, tol_step, name, tol_m=M.MIRROR_VS_MODEL_TOL_M, gaps=None):
     """The comparison rule of mirror vs model and of device vs mirror: every integer field of every fix agrees, but a
     message whose last step length lies within a factor 10 of the step tolerance may differ in CONVERGED (VALID with
-    it) and iterations, at most 1 % of the list; positions of fixes with pdop <= 20 agree within tol_m.  Returns the
-    largest position gap found."""
+    it) and iterations, at most 1 % of the list; positions of fixes with pdop <= 20 agree within tol_m, and so do their
+    hdop, vdop, time_s, height_m and residual_rms_m within the tolerances of M.gaps_of.  A SINGULAR fix has zero
+    dilutions; a fix that was not attempted is the same bytes.  Returns the largest position gap found; gaps (a dict)
+    takes the largest gap per field."""
     assert len(got) == len(want), name
     left_out, worst = 0, 0.0
+    gaps = {} if gaps is None else gaps
     for g, (a, b) in enumerate(zip(got, want)):
         ints = lambda f: (int(f["flags"]), int(f["n_used"]), int(f["iterations"]))
         if ints(a) != ints(b):
@@ -29,6 +32,11 @@ def same_fixes(got, want, lasts, tol_step, name, tol_m=M.MIRROR_VS_MODEL_TOL_M):
             worst = max(worst, gap)
             assert gap <= tol_m, (name, g, gap)
             assert abs(float(a["pdop"]) - float(b["pdop"])) <= 1e-3 * float(b["pdop"]), (name, g)
+            for field, (gap, tol) in M.gaps_of(a, b).items():
+                gaps[field] = max(gaps.get(field, 0.0), gap)
+                assert gap <= tol, (name, g, field, gap, tol, a[field], b[field])
+        if a["flags"] & M.SINGULAR:
+            assert a["pdop"] == 0 and a["hdop"] == 0 and a["vdop"] == 0, (name, g)
         if not a["flags"] & M.ATTEMPTED:
             assert a.tobytes() == b.tobytes(), (name, g)
     assert left_out <= len(want) / 100, (name, left_out)
@@ -38,23 +46,67 @@ def same_fixes(got, want, lasts, tol_step, name, tol_m=M.MIRROR_VS_MODEL_TOL_M):
 @pytest.fixture(scope="module")
 def cases(oracle):
     """(name, receivers, list, cfg, the model's fixes, the model's last step lengths) per case list, computed once."""
-    out = []
-    for name, rcv, lst, cfg in K.case_lists(oracle):
-        want, _, lasts = M.multilaterate(rcv, lst["msgs"], lst["recs"], lst["rx"], **cfg)
-        out.append((name, rcv, lst, cfg, want, lasts))
-    return out
+    return [(name, rcv, lst, cfg, want, lasts) for name, rcv, lst, cfg, expect, want, _, lasts in K.modelled(oracle)
+            if expect is None]
+
+
+def _say(what, gaps):
+    print(f"largest {what} gaps over fixes with pdop <= 20: " + ", ".join(
+        f"{k} {gaps.get(k, 0.0):.3g} (recorded {M.MIRROR_VS_MODEL_MEASURED[k]:.3g}, tolerance {tol:.3g})"
+        for k, tol in M.MIRROR_VS_MODEL_TOL.items()))
 
 
 def test_mirror_equals_model(lib, cases):
-    worst = 0.0
+    worst, gaps = 0.0, {}
     for name, rcv, lst, cfg, want, lasts in cases:
         got, hdr = lib.host_multilaterate(rcv, lst["msgs"], lst["recs"], lst["rx"], **cfg)
-        worst = max(worst, same_fixes(got, want, lasts, 0.01, name))
+        worst = max(worst, same_fixes(got, want, lasts, 0.01, name, gaps=gaps))
         assert int(hdr["n_messages"]) == len(want) and int(hdr["flags"]) == 0
         assert int(hdr["n_attempted"]) == int((got["flags"] & M.ATTEMPTED != 0).sum())
         assert int(hdr["n_valid"]) == int((got["flags"] & M.VALID != 0).sum())
     print(f"largest mirror-vs-model position gap over fixes with pdop <= 20: {worst:.3g} m "
           f"(recorded {M.MIRROR_VS_MODEL_MEASURED_M:.3g} m, tolerance {M.MIRROR_VS_MODEL_TOL_M:.3g} m)")
+    _say("mirror-vs-model", gaps)
+
+
+def test_edge_lists_mirror_equals_model(lib, oracle):
+    """The edge lists of tests/mlat_cases.py: the mirror against the model under same_fixes with NO message left out,
+    and both held to the lists' literal expectations.  The measured gaps, over the case lists too, are the recorded
+    ones (tests/mlat_model.py, profiles/mlat_edges_checks.txt)."""
+    worst, gaps, of_mirror, of_model = 0.0, {}, {}, {}
+    for name, rcv, lst, cfg, expect, want, want_hdr, lasts in K.modelled(oracle):
+        got, hdr = lib.host_multilaterate(rcv, lst["msgs"], lst["recs"], lst["rx"], **cfg)
+        tol = cfg.get("step_tol_m") or 0.01
+        worst = max(worst, same_fixes(got, want, lasts, tol, name, gaps=gaps))
+        if expect is None:
+            continue
+        assert len(want) <= 32 and [ints for ints in zip(got["flags"], got["n_used"], got["iterations"])] == \
+            [ints for ints in zip(want["flags"], want["n_used"], want["iterations"])], name
+        of_model[name], of_mirror[name] = want, got
+        error = K.check_expectations(name, want, want_hdr, expect, of_model, lasts, tol)
+        mine = K.check_expectations(name, got, hdr, expect, of_mirror, lasts, tol, model_error=error)
+        if error is not None:
+            print(f"{name}: largest error against the truth, model {error:.2f} m, mirror {mine:.2f} m")
+    print(f"largest mirror-vs-model position gap, case and edge lists: {worst:.3g} m")
+    _say("mirror-vs-model (case and edge lists)", gaps)
+    assert worst <= M.MIRROR_VS_MODEL_MEASURED_M * 1.005
+    for k, v in gaps.items():
+        assert v <= M.MIRROR_VS_MODEL_MEASURED[k], (k, v)
+
+
+def test_recorded_figures_are_the_profile_s():
+    """The constants of tests/mlat_model.py and tests/mlat_exact.py equal what profiles/mlat_edges_checks.txt records."""
+    import os
+    import re
+    from tests import mlat_exact as X
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                             "mlat_edges_checks.txt")).read()
+    said = {k: float(v) for k, v in re.findall(r"^\s+recorded (\S+) = (\S+)$", text, flags=re.M)}
+    want = {f"mirror_vs_model.{k}": v for k, v in M.MIRROR_VS_MODEL_MEASURED.items()}
+    want.update({f"exact_on_model.{k}": v for k, v in X.MODEL_MEASURED.items()})
+    want["mirror_vs_model.position_m"] = M.MIRROR_VS_MODEL_MEASURED_M
+    want["rms_floor_m"] = float(f"{M.RMS_FLOOR_M:.3g}")
+    assert said == want
 
 
 def test_case_lists_cover_the_shapes(cases):
