@@ -303,6 +303,37 @@ assert SITE.itemsize == C.sizeof(AdsbSite) == 24 and FIX_DTYPE.itemsize == C.siz
 assert FRAME_FIX_DTYPE.itemsize == C.sizeof(AdsbFrameFix) == 32
 
 
+ADSB_TRACK_MLAT_VALID = 0x1      # adsb_aircraft_mlat.flags / adsb_frame_mlat.flags: the record holds a fix
+ADSB_TRACK_MLAT_ALTITUDE = 0x2   # that fix used the message's own altitude
+ADSB_TRACK_MLAT_CHECKED = 0x4    # last_disagreement_m holds a value
+ADSB_TRACK_MLAT_DISAGREE = 0x8   # adsb_frame_mlat.flags only: beyond the limit
+ADSB_TRACK_MLAT_FAR = 0x10       # adsb_frame_mlat.flags only: the local decode was turned away
+
+
+class AdsbAircraftMlat(C.Structure):
+    """adsb_aircraft_mlat: an aircraft's newest multilaterated position and what its reported positions differ from the
+    solved ones by, beside its record (tables with an mlat reserve)."""
+    _fields_ = [("time", C.c_double), ("latitude", C.c_double), ("longitude", C.c_double), ("height_m", C.c_float),
+                ("residual_rms_m", C.c_float), ("pdop", C.c_float), ("last_disagreement_m", C.c_float),
+                ("max_disagreement_m", C.c_float), ("n_attempted", C.c_uint32), ("n_valid", C.c_uint32),
+                ("n_checked", C.c_uint32), ("n_disagree", C.c_uint32), ("n_used", C.c_uint16), ("flags", C.c_uint8),
+                ("reserved", C.c_uint8)]
+
+
+class AdsbFrameMlat(C.Structure):
+    _fields_ = [("disagreement_m", C.c_float), ("icao", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+AIRCRAFT_MLAT_DTYPE = np.dtype([("time", "<f8"), ("latitude", "<f8"), ("longitude", "<f8"), ("height_m", "<f4"),
+                                ("residual_rms_m", "<f4"), ("pdop", "<f4"), ("last_disagreement_m", "<f4"),
+                                ("max_disagreement_m", "<f4"), ("n_attempted", "<u4"), ("n_valid", "<u4"),
+                                ("n_checked", "<u4"), ("n_disagree", "<u4"), ("n_used", "<u2"), ("flags", "u1"),
+                                ("reserved", "u1")])
+FRAME_MLAT_DTYPE = np.dtype([("disagreement_m", "<f4"), ("icao", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+assert AIRCRAFT_MLAT_DTYPE.itemsize == C.sizeof(AdsbAircraftMlat) == 64
+assert FRAME_MLAT_DTYPE.itemsize == C.sizeof(AdsbFrameMlat) == 16
+
+
 class AdsbTrackBankCfg(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("n_receivers", C.c_uint32), ("max_aircraft", C.c_uint32),
                 ("reserved", C.c_uint32), ("max_frames", C.c_uint64), ("seconds_per_sample", C.c_double)]
@@ -425,6 +456,11 @@ PROTOTYPES = {
     "adsb_track_table_fetch_fixes": (C.c_int, [C.c_void_p, _P(AdsbFix), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_table_fixes_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "adsb_track_table_fetch_frame_fixes": (C.c_int, [C.c_void_p, _P(AdsbFrameFix), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_mlat_reserve": (C.c_int, [C.c_void_p, C.c_double]),
+    "adsb_track_table_update_mlat": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64]),
+    "adsb_track_table_fetch_mlat": (C.c_int, [C.c_void_p, _P(AdsbAircraftMlat), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_mlat_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "adsb_track_table_fetch_frame_mlat": (C.c_int, [C.c_void_p, _P(AdsbFrameMlat), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_bank_fixes_reserve": (C.c_int, [C.c_void_p, _P(AdsbSite)]),
     "adsb_track_bank_fetch_fixes": (C.c_int, [C.c_void_p, _P(AdsbFix), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_bank_fixes_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
@@ -518,6 +554,8 @@ PROTOTYPES = {
     "adsb_host_clock_apply": (C.c_int, [_P(AdsbClockCfg), C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adsb_host_fix_of": (C.c_int, [_P(AdsbSite), _P(C.c_uint8 * 14), C.c_double, _P(AdsbFix), _P(C.c_uint32)]),
+    "adsb_host_track_mlat_of": (C.c_int, [C.c_double, _P(C.c_uint8 * 14), _P(AdsbMlatFix), C.c_double,
+                                          _P(AdsbAircraftMlat), _P(C.c_uint32), _P(C.c_float)]),
 }
 
 _lib = None

@@ -80,8 +80,10 @@ ADSB_HD inline bool fix_movement_kt(uint32_t m, double &kt)
 
 // One frame against one site.  f.icao is always set.  Not a position message (DF 17, TC 5-8, 9-18, 20-22): everything
 // else zero.  Rejected (|lat| > 90, or farther than the site's limit): f.flags = ADSB_FIX_REJECTED (| ADSB_FIX_SURFACE)
-// and everything else zero.  Accepted: f.flags = ADSB_FIX_VALID | ..., f and r filled.
-ADSB_HD inline void fix_decode(const adsb_site &site, const uint8_t *bytes, adsb_frame_fix &f, FixRem &r)
+// and everything else zero.  Accepted: f.flags = ADSB_FIX_VALID | ..., f and r filled.  range_f64: the accepted frame's
+// range from the site in NM before its one rounding to f32 (0 otherwise), for adsb_track_mlat.h.
+ADSB_HD inline void fix_decode(const adsb_site &site, const uint8_t *bytes, adsb_frame_fix &f, FixRem &r,
+                               double &range_f64)
 {
 #pragma clang fp contract(off)
     f.latitude = 0.0;
@@ -90,6 +92,7 @@ ADSB_HD inline void fix_decode(const adsb_site &site, const uint8_t *bytes, adsb
     f.bearing_deg = 0.0f;
     f.icao = (uint32_t)bytes[1] << 16 | (uint32_t)bytes[2] << 8 | bytes[3];
     f.flags = 0;
+    range_f64 = 0.0;
     r.ground_speed_kt = 0.0f;
     r.track_deg = 0.0f;
     r.altitude = 0;
@@ -152,13 +155,20 @@ ADSB_HD inline void fix_decode(const adsb_site &site, const uint8_t *bytes, adsb
     f.latitude = lat;
     f.longitude = lon;
     f.range_nm = (float)range;
+    range_f64 = range;
     f.bearing_deg = (float)bearing;
     if (f.bearing_deg >= 360.0f) f.bearing_deg = 0.0f; // the one rounding lifts a bearing within 1.5e-5 below 360 to 360
     f.flags = flags;
 }
 
+ADSB_HD inline void fix_decode(const adsb_site &site, const uint8_t *bytes, adsb_frame_fix &f, FixRem &r)
+{
+    double range;
+    fix_decode(site, bytes, f, r, range);
+}
+
 // What a fixes reserve accepts (a NaN fails every comparison)
-inline bool fix_site_ok(const adsb_site &s)
+ADSB_HD inline bool fix_site_ok(const adsb_site &s)
 {
     return s.latitude >= -90.0 && s.latitude <= 90.0 && s.longitude >= -180.0 && s.longitude <= 180.0 &&
            s.max_range_nm > 0.0 && s.max_range_nm <= 180.0;

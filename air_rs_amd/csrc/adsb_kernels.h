@@ -346,6 +346,7 @@ struct TrackStoreDev {
                                  // and expire touch nothing more than they did)
     adsb_fix *fix;               // [n_receivers x max_aircraft] beside rec, or null: no fixes reserve (likewise)
     const adsb_site *site;       // [n_receivers] with fix: the site receiver r's frames decode against
+    adsb_aircraft_mlat *mlat;    // [n_receivers x max_aircraft] beside rec, or null: no mlat reserve (likewise; tables only)
     // table only
     uint32_t *index;             // [1 << 24]: ICAO -> record slot + 1, 0 = absent
     // bank only
@@ -410,6 +411,26 @@ struct TrackFixDev {
     void *temp;                  // the scan's scratch
     size_t temp_bytes;
 };
+// Multilaterated positions per aircraft (adsb_track_table_mlat_reserve; adsb_track_mlat.h has the per-frame text): all of
+// it allocated by the reserve.  One thread per sorted frame writes out[] at the frame's list index and the scan's operand
+// at its sorted position; one segmented inclusive scan carries, per aircraft, the sorted position + 1 of the later frame
+// with a VALID fix and of the later CHECKED frame (0 = none), the greatest disagreement and four saturating counts; one
+// thread per segment tail merges into store->mlat.  Integers and one float max: the scan's shape cannot show.
+struct TrackMlatTuple {
+    uint32_t head;               // the operand holds a segment head
+    uint32_t newest_valid, newest_checked;
+    float max_m;                 // >= 0, never NaN
+    uint32_t n_attempted, n_valid, n_checked, n_disagree;
+};
+static_assert(sizeof(TrackMlatTuple) == 32, "TrackMlatTuple: the header's memory figures assume 32 bytes");
+struct TrackMlatDev {
+    adsb_frame_mlat *out;        // [max_frames]: one per frame of the last update_mlat, list order
+    TrackMlatTuple *in;          // [max_frames]: the scan's operands, sorted order
+    TrackMlatTuple *scan;        // [max_frames]: the scan's output, sorted order
+    void *temp;                  // the scan's scratch
+    size_t temp_bytes;
+    double max_disagreement_m;   // the reserve's limit
+};
 struct TrackArgs {
     const adsb_frame *frames;
     const adsb_packet_fields *fields;
@@ -431,6 +452,8 @@ struct TrackArgs {
     const adsb_frame_level *levels; // [n] (device), list order: with lvl non-null (and store->lvl), merged into the
     const TrackLvlDev *lvl;      // per-aircraft level records; null: the level records stay as they are
     const TrackFixDev *fix;      // non-null (with store->fix and store->site): also the per-frame fixes and their merge
+    const adsb_mlat_fix *mlat_fixes; // [n] (device), list order: with mlat non-null (and store->mlat), merged into the
+    const TrackMlatDev *mlat;    // per-aircraft mlat records; null: the mlat records stay as they are
 };
 // expire (adsb_track_table_expire / adsb_track_bank_expire): a record survives unless last_heard < before[receiver]
 constexpr uint32_t kMaxReceivers = 256;
@@ -457,6 +480,9 @@ hipError_t launch_track_levels_clear(hipStream_t s, adsb_aircraft_level *lvl, si
 size_t track_fixes_temp_bytes(size_t n);
 // every fix of [0, places) empty: zeros, time NaN (the fixes reserve, and reset)
 hipError_t launch_track_fixes_clear(hipStream_t s, adsb_fix *fix, size_t places);
+size_t track_mlat_temp_bytes(size_t n);
+// every mlat record of [0, places) empty: zeros, time NaN (the mlat reserve, and reset)
+hipError_t launch_track_mlat_clear(hipStream_t s, adsb_aircraft_mlat *mlat, size_t places);
 // out[k] = rec[sum.changed[k]] for k < min(*sum.n_changed, max_n): the changed list's records, gathered on the device
 hipError_t launch_track_changed(hipStream_t s, const TrackRecord *rec, const TrackSumDev &sum, uint32_t max_n,
                                 TrackRecord *out);

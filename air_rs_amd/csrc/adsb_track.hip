@@ -88,6 +88,14 @@
 // segmented inclusive scan (16-byte tuple) finds every segment's newest accepted position message and counts, one thread
 // per segment tail merges into the side record.  Admission empties the fix of a place it admits, expire's compaction
 // moves it with the record; both only when the side array exists.
+//
+// Multilaterated positions per aircraft (adsb_track_table_mlat_reserve; the update_mlat form): a third side array, one
+// 64-byte adsb_aircraft_mlat per record place.  After 2., independent of 3.: one thread per frame takes the frame, its
+// adsb_mlat_fix and its slot through adsb_track_mlat.h (the single-message decode with the solved position as the site;
+// the text the CPU mirror compiles too) into one adsb_frame_mlat at the list index and one scan operand at the sorted
+// position, one segmented inclusive scan (32-byte tuple: integers and one float max) finds every segment's newest valid
+// fix, newest checked frame, greatest disagreement and counts, one thread per segment tail merges into the side record.
+// Admission and expire treat the array as they treat the other two.  Tables only; the templates compile for a bank too.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -96,6 +104,7 @@
 
 #include "adsb_fix.h"
 #include "adsb_kernels.h"
+#include "adsb_track_mlat.h"
 
 namespace adsbk {
 
@@ -285,6 +294,7 @@ __global__ __launch_bounds__(256) void track_admit_kernel(const uint32_t *skeys,
     t.rec[r] = empty_record(icao);
     if (t.lvl) t.lvl[r] = empty_level();
     if (t.fix) ((FixWords *)t.fix)[r] = fix_empty();
+    if (t.mlat) ((MlatWords *)t.mlat)[r] = mlat_empty();
 }
 
 // bank only: the receiver split clipped to the list (prefix[0] = 0, prefix[k] = n for k >= n_src), as adsb_fetch's
@@ -386,6 +396,7 @@ __global__ __launch_bounds__(256) void track_bank_admit_kernel(const uint32_t *s
     b.rec[a] = empty_record(key & 0xFFFFFFu);
     if (b.lvl) b.lvl[a] = empty_level();
     if (b.fix) ((FixWords *)b.fix)[a] = fix_empty();
+    if (b.mlat) ((MlatWords *)b.mlat)[a] = mlat_empty();
     b.seg_slot[g] = a + 1u;
 }
 
@@ -883,6 +894,118 @@ __global__ __launch_bounds__(256) void track_fixes_clear_kernel(FixWords *fix, u
     if (p < places) fix[p] = fix_empty();
 }
 
+// ---- multilaterated positions per aircraft (table with an mlat reserve) ----------------------------------------------
+// One thread per sorted frame s, after the pairs kernel: the frame's bytes and its fix (both at the frame's LIST index
+// i = svals[s] < n, a permutation of the list) through adsb_track_mlat.h into out[i], and the scan's operand into in[s].
+// A frame of an aircraft the table turned away gets its icao and nothing else, and counts nowhere.
+template <TrackKind K>
+__global__ __launch_bounds__(256) void track_mlat_frame_kernel(const adsb_frame *frames, const adsb_mlat_fix *fixes,
+                                                               const uint32_t *skeys, const uint32_t *svals, uint32_t n,
+                                                               TrackStoreDev d, TrackMlatDev ml)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s], i = svals[s];
+    MlatFrame m{};
+    if (d.slot[s] != kTrackUntracked) m = mlat_frame(ml.max_disagreement_m, frames[i].bytes, fixes[i]);
+    adsb_frame_mlat f;
+    f.disagreement_m = m.disagreement_m;
+    f.icao = K == TrackKind::kBank ? key & 0xFFFFFFu : key;
+    f.flags = m.flags;
+    f.reserved = 0;
+    ml.out[i] = f;
+    const bool valid = (m.flags & ADSB_TRACK_MLAT_VALID) != 0, checked = (m.flags & ADSB_TRACK_MLAT_CHECKED) != 0;
+    TrackMlatTuple v;
+    v.head = (s == 0 || skeys[s - 1] != key) ? 1u : 0u;
+    v.newest_valid = valid ? s + 1u : 0u;
+    v.newest_checked = checked ? s + 1u : 0u;
+    v.max_m = m.disagreement_m;
+    v.n_attempted = m.attempted;
+    v.n_valid = valid ? 1u : 0u;
+    v.n_checked = checked ? 1u : 0u;
+    v.n_disagree = (m.flags & ADSB_TRACK_MLAT_DISAGREE) ? 1u : 0u;
+    ml.in[s] = v;
+}
+
+// Segmented: a right operand that holds a segment head starts over; otherwise saturating sums, the float maximum (of
+// values that are >= 0 and never NaN) and the later positions (positions ascend, so the later one is the greater one).
+// Associative.
+struct MlatOp {
+    __device__ __forceinline__ TrackMlatTuple operator()(const TrackMlatTuple &l, const TrackMlatTuple &r) const
+    {
+        TrackMlatTuple o = r;
+        if (!r.head) {
+            o.head = l.head;
+            o.newest_valid = l.newest_valid > r.newest_valid ? l.newest_valid : r.newest_valid;
+            o.newest_checked = l.newest_checked > r.newest_checked ? l.newest_checked : r.newest_checked;
+            o.max_m = l.max_m > r.max_m ? l.max_m : r.max_m;
+            o.n_attempted = sat_add32(l.n_attempted, r.n_attempted);
+            o.n_valid = sat_add32(l.n_valid, r.n_valid);
+            o.n_checked = sat_add32(l.n_checked, r.n_checked);
+            o.n_disagree = sat_add32(l.n_disagree, r.n_disagree);
+        }
+        return o;
+    }
+};
+
+// One thread per segment tail whose segment adds something: this update's part merged into the aircraft's mlat record
+template <TrackKind K>
+__global__ __launch_bounds__(256) void track_mlat_merge_kernel(const adsb_frame *frames, const adsb_mlat_fix *fixes,
+                                                               const uint32_t *skeys, const uint32_t *svals, uint32_t n,
+                                                               double seconds_per_sample, uint64_t sample_base,
+                                                               TrackStoreDev d, TrackMlatDev ml)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s];
+    if (s + 1 != n && skeys[s + 1] == key) return;
+    const uint32_t slot = d.slot[s];
+    if (slot == kTrackUntracked) return;
+    const TrackMlatTuple w = ml.scan[s];
+    if (!w.n_attempted && !w.n_valid) return; // nothing counted (checked implies valid): the record stays
+    if (K == TrackKind::kBank) sample_base = d.sample_base[key >> 24];
+    MlatWords words = ((const MlatWords *)d.mlat)[slot - 1];
+    adsb_aircraft_mlat a;
+    __builtin_memcpy(&a, &words, sizeof(a));
+    if (w.newest_checked) { // <= n: a sorted position + 1 of this list
+        a.last_disagreement_m = ml.out[svals[w.newest_checked - 1]].disagreement_m;
+        a.flags |= ADSB_TRACK_MLAT_CHECKED;
+    }
+    if (w.newest_valid) {
+        const uint32_t j = svals[w.newest_valid - 1];
+        mlat_take(a, fixes[j], frame_time(frames, j, sample_base, seconds_per_sample));
+    }
+    a.max_disagreement_m = a.max_disagreement_m > w.max_m ? a.max_disagreement_m : w.max_m;
+    a.n_attempted = sat_add32(a.n_attempted, w.n_attempted);
+    a.n_valid = sat_add32(a.n_valid, w.n_valid);
+    a.n_checked = sat_add32(a.n_checked, w.n_checked);
+    a.n_disagree = sat_add32(a.n_disagree, w.n_disagree);
+    __builtin_memcpy(&words, &a, sizeof(a));
+    ((MlatWords *)d.mlat)[slot - 1] = words;
+}
+
+template <TrackKind K>
+hipError_t launch_mlat_merge(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d)
+{
+    const TrackMlatDev &ml = *a.mlat;
+    const dim3 grid((a.n + 255) / 256);
+    hipLaunchKernelGGL(track_mlat_frame_kernel<K>, grid, dim3(256), 0, st, a.frames, a.mlat_fixes,
+                       (const uint32_t *)a.skeys, (const uint32_t *)a.svals, a.n, d, ml);
+    size_t tb = ml.temp_bytes;
+    hipError_t e = rocprim::inclusive_scan(ml.temp, tb, (const TrackMlatTuple *)ml.in, ml.scan, (size_t)a.n, MlatOp(), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(track_mlat_merge_kernel<K>, grid, dim3(256), 0, st, a.frames, a.mlat_fixes,
+                       (const uint32_t *)a.skeys, (const uint32_t *)a.svals, a.n, a.seconds_per_sample, a.sample_base, d,
+                       ml);
+    return hipSuccess;
+}
+
+__global__ __launch_bounds__(256) void track_mlat_clear_kernel(MlatWords *mlat, uint64_t places)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < places) mlat[p] = mlat_empty();
+}
+
 // expire, 1: keep[g] = 1 for a record in use whose last frame is not older than the cut (last_heard < before evicts).
 // Record g is slot i of receiver r (a table: r = 0).  Slot 0 stages the old size where the compaction kernel reads it
 // (size_next[r]), since that kernel writes the new one; the pairs kernel of an update has consumed its own staging before
@@ -936,6 +1059,7 @@ __global__ __launch_bounds__(256) void track_expire_compact_kernel(TrackStoreDev
     d.rec[g] = moved;
     if (d.lvl) d.lvl[g] = d.lvl[base + lo];
     if (d.fix) ((FixWords *)d.fix)[g] = ((const FixWords *)d.fix)[base + lo];
+    if (d.mlat) ((MlatWords *)d.mlat)[g] = ((const MlatWords *)d.mlat)[base + lo];
     if (!kBank) d.index[moved.a.icao] = i + 1u;
 }
 
@@ -1311,6 +1435,22 @@ size_t track_fixes_temp_bytes(size_t n)
     return scan_bytes + 256;
 }
 
+size_t track_mlat_temp_bytes(size_t n)
+{
+    size_t scan_bytes = 0;
+    (void)rocprim::inclusive_scan(nullptr, scan_bytes, (const TrackMlatTuple *)nullptr, (TrackMlatTuple *)nullptr, n,
+                                  MlatOp(), (hipStream_t)0);
+    return scan_bytes + 256;
+}
+
+hipError_t launch_track_mlat_clear(hipStream_t st, adsb_aircraft_mlat *mlat, size_t places)
+{
+    if (places == 0) return hipSuccess;
+    hipLaunchKernelGGL(track_mlat_clear_kernel, dim3((uint32_t)((places + 255) / 256)), dim3(256), 0, st,
+                       (MlatWords *)mlat, (uint64_t)places);
+    return hipGetLastError();
+}
+
 hipError_t launch_track_fixes_clear(hipStream_t st, adsb_fix *fix, size_t places)
 {
     if (places == 0) return hipSuccess;
@@ -1353,6 +1493,8 @@ hipError_t track_tail(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d
         if (a.lvl && d.lvl) e = launch_levels_merge<K>(st, a, d); // needs d.slot only: independent of the record merge
         if (e != hipSuccess) return e;
         if (a.fix && d.fix) e = launch_fix_merge<K>(st, a, d); // needs d.slot and the frame bytes only
+        if (e != hipSuccess) return e;
+        if (a.mlat && d.mlat) e = launch_mlat_merge<K>(st, a, d); // needs d.slot, the frame bytes and the fixes only
         if (e != hipSuccess) return e;
         if (a.sum) e = launch_frame_summaries<K>(st, a, d); // before the merge
     } else {

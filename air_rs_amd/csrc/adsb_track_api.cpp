@@ -13,6 +13,7 @@
 
 #include "adsb_fix.h"
 #include "adsb_scratch.h"
+#include "adsb_track_mlat.h"
 
 using adsbk::TrackKind;
 using adsbk::TrackRecord;
@@ -111,7 +112,7 @@ struct TrackStore {
     uint32_t n_receivers = 0, max_aircraft = 0; // max_aircraft: per receiver
     // One block of device memory per lifetime, carved into the arrays below (adsb_scratch.h): the store's own from
     // create to destroy, and one per reserve.  Every device pointer of the store points into one of them.
-    DevBuf<char> mem, sum_mem, lvl_mem, fix_mem;
+    DevBuf<char> mem, sum_mem, lvl_mem, fix_mem, mlat_mem;
     adsbk::TrackStoreDev dev{};     // records [R x max_aircraft], slot [max_frames]; index [2^24] or hash, prefix, scan words
     uint32_t *words = nullptr;      // [3R]: size, flags, size_next (dev.size / dev.flags / dev.size_next)
     uint32_t *u32 = nullptr;        // 4 x [max_frames]: keys, vals, sorted keys, sorted vals
@@ -136,6 +137,13 @@ struct TrackStore {
     adsb_frame_level *lvl_pinned = nullptr; // [max_frames]: pinned staging of that copy (s.copied covers it too)
     // positions from single messages (adsb_track_*_fixes_reserve): all of it carved by the reserve; dev.fix null = none
     adsbk::TrackFixDev fix{};
+    // multilaterated positions per aircraft (adsb_track_table_mlat_reserve): all of it made by the reserve; dev.mlat null
+    // = none
+    adsbk::TrackMlatDev mlat{};
+    adsb_mlat_fix *mlat_fixes = nullptr;  // [max_frames]: device copy of a host fixes array
+    adsb_mlat_fix *mlat_pinned = nullptr; // [max_frames]: pinned staging of that copy (s.copied covers it too)
+    uint32_t mlat_n = 0;                  // frames of the last update_mlat
+    bool mlat_updated = false;            // an update_mlat ran since the reserve (and since the last reset)
 
     size_t places() const { return (size_t)n_receivers * max_aircraft; }
 };
@@ -194,6 +202,16 @@ static void store_fixes_drop(TrackStore &s)
     s.fix = {};
 }
 
+// The mlat reserve undone, under the same condition.
+static void store_mlat_drop(TrackStore &s)
+{
+    drop(s.mlat_mem);
+    pinned_free(s.mlat_pinned);
+    s.dev.mlat = nullptr;
+    s.mlat = {};
+    s.mlat_fixes = nullptr;
+}
+
 // Sizes, and the store's own block: what a table and a bank share, then what each kind adds (a bank has set
 // dev.hash_mask).  false: an allocation failed (the caller releases what was made)
 static bool store_alloc(TrackStore &s, adsb_ctx *c, TrackKind kind, uint32_t n_receivers, uint32_t max_aircraft, uint64_t max_frames,
@@ -248,8 +266,10 @@ static void store_release(TrackStore &s)
     drop(s.sum_mem);
     drop(s.lvl_mem);
     drop(s.fix_mem);
+    drop(s.mlat_mem);
     pinned_free(s.pinned);
     pinned_free(s.lvl_pinned);
+    pinned_free(s.mlat_pinned);
     pinned_free(s.meta_pinned);
     if (s.copied) (void)hipEventDestroy(s.copied);
 }
@@ -264,6 +284,8 @@ static int store_reset(TrackStore *s)
         HIPCHK(hipMemsetAsync(s->dev.hash, 0, sizeof(unsigned long long) * (s->dev.hash_mask + 1), s->ctx->aux));
     HIPCHK(hipMemsetAsync(s->words, 0, sizeof(uint32_t) * 3 * s->n_receivers, s->ctx->aux));
     if (s->dev.fix) HIPCHK(adsbk::launch_track_fixes_clear(s->ctx->aux, s->dev.fix, s->places()));
+    if (s->dev.mlat) HIPCHK(adsbk::launch_track_mlat_clear(s->ctx->aux, s->dev.mlat, s->places()));
+    s->mlat_updated = false;
     s->n_points = 0;
     s->updated = false;
     s->sum.updated = s->sum.changed_valid = false;
@@ -302,6 +324,14 @@ static int store_stage_levels(TrackStore &s, const adsb_frame_level *host, size_
     return ADSB_OK;
 }
 
+// The same for a host fixes array (update_mlat), under the same event
+static int store_stage_mlat(TrackStore &s, const adsb_mlat_fix *host, size_t n)
+{
+    std::memcpy(s.mlat_pinned, host, sizeof(adsb_mlat_fix) * n);
+    HIPCHK(hipMemcpyAsync(s.mlat_fixes, s.mlat_pinned, sizeof(adsb_mlat_fix) * n, hipMemcpyHostToDevice, s.ctx->aux));
+    return ADSB_OK;
+}
+
 // The bookkeeping every update starts with (an empty one too: no summaries, an empty changed list); false: n == 0,
 // nothing to launch
 static bool store_begin_update(TrackStore &s, size_t n)
@@ -314,9 +344,10 @@ static bool store_begin_update(TrackStore &s, size_t n)
 
 // Enqueues field decode and the tracker kernels over n frames at `list` (device), after the ctx's ordering pass and
 // field decode (same stream); dev: s.dev, or a bank's copy of it with this update's receiver split; levels (device,
-// or null): also the level merge
+// or null): also the level merge; mlat_fixes (device, or null): also the mlat merge
 static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t sample_base,
-                     const adsbk::TrackStoreDev &dev, const adsb_frame_level *levels = nullptr)
+                     const adsbk::TrackStoreDev &dev, const adsb_frame_level *levels = nullptr,
+                     const adsb_mlat_fix *mlat_fixes = nullptr)
 {
     HIPCHK(adsbk::launch_decode_fields(s.ctx->aux, list, nullptr, (uint32_t)n, s.fields));
     adsbk::TrackArgs a = track_args(s.kind, list, s.fields, n, s.seconds_per_sample, s.u32, (size_t)s.max_frames,
@@ -327,6 +358,8 @@ static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t s
     a.levels = levels;
     a.lvl = levels ? &s.lvl : nullptr;
     a.fix = dev.fix ? &s.fix : nullptr;
+    a.mlat_fixes = mlat_fixes;
+    a.mlat = mlat_fixes ? &s.mlat : nullptr;
     HIPCHK(adsbk::launch_track(s.ctx->aux, a));
     return ADSB_OK;
 }
@@ -338,6 +371,7 @@ static const adsb_aircraft_record *summaries_of(TrackStore &s) { return s.sum.up
 static const adsb_frame_fix *frame_fixes_of(TrackStore &s) { return s.dev.fix && s.updated ? s.fix.out : nullptr; }
 static const adsb_aircraft_level *levels_of(TrackStore &s) { return s.dev.lvl; }
 static const adsb_fix *fixes_of(TrackStore &s) { return s.dev.fix; }
+static const adsb_aircraft_mlat *mlat_of(TrackStore &s) { return s.dev.mlat; }
 
 template <class T>
 static int store_device(TrackStore *s, const T *of(TrackStore &), const T **dev)
@@ -591,6 +625,33 @@ static int store_fixes_reserve(TrackStore *st, const adsb_site *sites)
     return ADSB_OK;
 }
 
+// ---- multilaterated positions per aircraft ----------------------------------------------------------------------------
+// Waits for the device (the clear); a second reserve keeps what the first one made, its limit too
+static int store_mlat_reserve(TrackStore *st, double max_disagreement_m)
+{
+    HIPCHK(hipSetDevice(st->ctx->cfg.device));
+    if (st->dev.mlat) return ADSB_OK;
+    const size_t nf = (size_t)st->max_frames;
+    st->mlat.temp_bytes = adsbk::track_mlat_temp_bytes(nf);
+    st->mlat.max_disagreement_m = max_disagreement_m;
+    const int rc = carve_block(st->ctx, st->mlat_mem, [&](Carve &k) {
+        st->dev.mlat = k.take<adsb_aircraft_mlat>(st->places());
+        st->mlat.out = k.take<adsb_frame_mlat>(nf);
+        st->mlat.in = k.take<adsbk::TrackMlatTuple>(nf);
+        st->mlat.scan = k.take<adsbk::TrackMlatTuple>(nf);
+        st->mlat.temp = k.take<char>(st->mlat.temp_bytes);
+        st->mlat_fixes = k.take<adsb_mlat_fix>(nf);
+    });
+    if (rc != ADSB_OK || !pinned_make(st->mlat_pinned, nf) ||
+        adsbk::launch_track_mlat_clear(st->ctx->aux, st->dev.mlat, st->places()) != hipSuccess ||
+        hipStreamSynchronize(st->ctx->aux) != hipSuccess) {
+        (void)hipGetLastError();
+        store_mlat_drop(*st);
+        return ADSB_E_NOMEM;
+    }
+    return ADSB_OK;
+}
+
 // ---- persistent aircraft table (adsb_track_table_*) ------------------------------------------------------------------
 static void track_table_free(adsb_track_table *t)
 {
@@ -620,26 +681,33 @@ extern "C" void adsb_track_table_destroy(adsb_track_table *t)
     if (t) track_table_free(t);
 }
 
-// levels: null for the plain update
+// levels: null for the plain update; fixes: null unless update_mlat
 static int track_table_update(adsb_track_table *t, const adsb_frame *frames, const adsb_frame_level *levels, size_t n,
-                              uint64_t sample_base)
+                              uint64_t sample_base, const adsb_mlat_fix *fixes = nullptr)
 {
     if (n > t->max_frames) return ADSB_E_CAPACITY;
     adsb_ctx *c = t->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
+    if (fixes) { // the list fetch_frame_mlat speaks of
+        t->mlat_n = (uint32_t)n;
+        t->mlat_updated = true;
+    }
     if (!store_begin_update(*t, n)) return ADSB_OK;
     const adsb_frame *list = frames;
     const bool frames_host = !in_device_memory(c, frames), levels_host = levels && !in_device_memory(c, levels);
-    if (frames_host || levels_host) {
+    const bool fixes_host = fixes && !in_device_memory(c, fixes);
+    if (frames_host || levels_host || fixes_host) {
         HIPCHK(hipEventSynchronize(t->copied)); // the previous update's copies out of the staging have finished
         int rc = frames_host ? store_stage_frames(*t, frames, n) : ADSB_OK;
         if (rc == ADSB_OK && levels_host) rc = store_stage_levels(*t, levels, n);
+        if (rc == ADSB_OK && fixes_host) rc = store_stage_mlat(*t, fixes, n);
         if (rc != ADSB_OK) return rc;
         HIPCHK(hipEventRecord(t->copied, c->aux));
         if (frames_host) list = t->frames;
         if (levels_host) levels = t->lvl_frames;
+        if (fixes_host) fixes = t->mlat_fixes;
     }
-    return store_run(*t, list, n, sample_base, t->dev, levels);
+    return store_run(*t, list, n, sample_base, t->dev, levels, fixes);
 }
 
 extern "C" int adsb_track_table_update(adsb_track_table *t, const adsb_frame *frames, size_t n, uint64_t sample_base)
@@ -687,6 +755,48 @@ extern "C" int adsb_track_table_fixes_device(adsb_track_table *t, const adsb_fix
 extern "C" int adsb_track_table_fetch_frame_fixes(adsb_track_table *t, adsb_frame_fix *out, size_t max, size_t *n)
 {
     return store_fetch_frames(t, frame_fixes_of, out, max, n, Report::kCopied);
+}
+
+extern "C" int adsb_track_table_mlat_reserve(adsb_track_table *t, double max_disagreement_m)
+{
+    if (!t || !std::isfinite(max_disagreement_m) || !(max_disagreement_m > 0.0)) return ADSB_E_ARG; // before the handle is read
+    return store_mlat_reserve(t, max_disagreement_m);
+}
+
+extern "C" int adsb_track_table_update_mlat(adsb_track_table *t, const adsb_frame *frames, const adsb_mlat_fix *fixes,
+                                            const adsb_frame_level *levels, size_t n, uint64_t sample_base)
+{
+    if (!t || (!frames && n) || (!fixes && n)) return ADSB_E_ARG;
+    if (!t->dev.mlat || (levels && !t->dev.lvl)) return ADSB_E_STATE;
+    if (n > t->max_frames) return ADSB_E_CAPACITY;
+    if (n == 0) { // nothing to launch: the last update_mlat's list is empty
+        t->mlat_n = 0;
+        t->mlat_updated = true;
+    }
+    return track_table_update(t, frames, n ? levels : nullptr, n, sample_base, n ? fixes : nullptr);
+}
+
+extern "C" int adsb_track_table_fetch_mlat(adsb_track_table *t, adsb_aircraft_mlat *out, size_t max, size_t *n)
+{
+    return store_fetch_side(t, mlat_of, out, max, n);
+}
+
+extern "C" int adsb_track_table_mlat_device(adsb_track_table *t, const adsb_aircraft_mlat **dev)
+{
+    return store_device(t, mlat_of, dev);
+}
+
+// Waits.  As store_fetch_frames, over the last update_mlat's list (a plain update in between leaves it alone)
+extern "C" int adsb_track_table_fetch_frame_mlat(adsb_track_table *t, adsb_frame_mlat *out, size_t max, size_t *n)
+{
+    if (!t || (!out && max)) return ADSB_E_ARG;
+    if (!t->dev.mlat || !t->mlat_updated) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(t->ctx->cfg.device));
+    const size_t take = std::min<size_t>(t->mlat_n, max);
+    if (take) HIPCHK(hipMemcpyAsync(out, t->mlat.out, sizeof(adsb_frame_mlat) * take, hipMemcpyDeviceToHost, t->ctx->aux));
+    HIPCHK(hipStreamSynchronize(t->ctx->aux));
+    if (n) *n = take;
+    return ADSB_OK;
 }
 
 extern "C" int adsb_track_table_summaries_reserve(adsb_track_table *t) { return store_summaries_reserve(t); }

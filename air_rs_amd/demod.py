@@ -29,6 +29,7 @@ assert LEVEL_DTYPE.itemsize == C.sizeof(L.AdsbFrameLevel) == 32
 LEVEL_PULSE_SAMPLES, LEVEL_QUIET_SAMPLES = 116, 124  # of a frame's 240: what signal_sum and noise_sum add up
 
 SITE, FIX_DTYPE, FRAME_FIX_DTYPE = L.SITE, L.FIX_DTYPE, L.FRAME_FIX_DTYPE  # fixes_reserve / fixes / frame_fixes
+AIRCRAFT_MLAT_DTYPE, FRAME_MLAT_DTYPE = L.AIRCRAFT_MLAT_DTYPE, L.FRAME_MLAT_DTYPE  # TrackTable.mlat / frame_mlat
 WINDOW = 240  # 16 preamble + 112*2 samples (reference src/adsb.rs:98)
 
 
@@ -101,6 +102,22 @@ def host_fix_of(site, frame_bytes, time=0.0):
     L.check(L.load().adsb_host_fix_of(s.ctypes.data_as(C.POINTER(L.AdsbSite)), C.byref(b), float(time),
                                       out.ctypes.data_as(C.POINTER(L.AdsbFix)), C.byref(flags)), "adsb_host_fix_of")
     return out[0], flags.value
+
+
+def host_track_mlat_of(max_disagreement_m, frame_bytes, fix, time=0.0):
+    """adsb_host_track_mlat_of, the CPU mirror of an mlat reserve's per-frame step: (AIRCRAFT_MLAT_DTYPE record of an
+    aircraft whose only counted frame is this one with the MLAT_FIX_DTYPE record `fix`, heard at `time`; the frame's
+    FRAME_MLAT_DTYPE flags; its disagreement_m as np.float32).  Needs no device."""
+    b = (C.c_uint8 * 14)(*bytes(frame_bytes))
+    f = np.zeros(1, dtype=L.MLAT_FIX_DTYPE)
+    f[0] = fix
+    out = np.zeros(1, dtype=AIRCRAFT_MLAT_DTYPE)
+    flags, dis = C.c_uint32(), C.c_float()
+    L.check(L.load().adsb_host_track_mlat_of(float(max_disagreement_m), C.byref(b),
+                                             f.ctypes.data_as(C.POINTER(L.AdsbMlatFix)), float(time),
+                                             out.ctypes.data_as(C.POINTER(L.AdsbAircraftMlat)), C.byref(flags),
+                                             C.byref(dis)), "adsb_host_track_mlat_of")
+    return out[0], flags.value, np.float32(dis.value)
 
 
 WIRE_FORMATS = {"beast": L.ADSB_WIRE_BEAST, "avr": L.ADSB_WIRE_AVR, "avr_mlat": L.ADSB_WIRE_AVR_MLAT}
@@ -836,6 +853,13 @@ class AdsbDemod:
         if not clocks:
             self.multilaterate_async(receivers, rx, **cfg)
             return self.fetch_mlat()
+        self.multilaterate_clocks_async(receivers, rx, clock_cfg, **cfg)
+        return self.fetch_mlat()
+
+    def multilaterate_clocks_async(self, receivers, rx=None, clock_cfg=None, **cfg):
+        """multilaterate(clocks=True) without the fetch: everything stays on the device (mlat_device(),
+        correlated_device()); only the two list lengths are read back -> (messages, receptions) of the correlate
+        result, e.g. for TrackTable.update_device(frames_dev, messages, mlat_ptr=fixes_dev)."""
         times = {k: cfg[k] for k in ("time_source", "seconds_per_tick") if k in cfg}
         self.clock_sync_async(receivers, rx, **dict(times, **(clock_cfg or {})))
         self.clock_apply_async()
@@ -852,7 +876,7 @@ class AdsbDemod:
         rest = {k: v for k, v in cfg.items() if k not in ("time_source", "seconds_per_tick")}
         self.multilaterate_of_async(plain, (msgs_dev, n_msgs.value), (recs_dev, min(n, n_recs.value)), None,
                                     time_source="reception", seconds_per_tick=spt / 256.0, **rest)
-        return self.fetch_mlat()
+        return n_msgs.value, n_recs.value
 
     def clock_sync_async(self, receivers, rx=None, **cfg):
         """adsb_clock_sync alone: the last correlate call's result, where it lies on the device.  rx as for
@@ -1298,21 +1322,32 @@ class TrackTable(_TrackStore):
         self._open(dem, L.AdsbTrackTableCfg(L.ADSB_ABI_VERSION, int(max_aircraft), int(max_frames),
                                             float(seconds_per_sample)), max_frames)
 
-    def update(self, frames, sample_base=0, levels=None):
+    def update(self, frames, sample_base=0, levels=None, mlat=None):
         """frames: FRAME_DTYPE array in ascending offset (host); packet time = (sample_base + offset) x sps.  levels
-        (after levels_reserve): the frames' LEVEL_DTYPE records (host), merged into the aircraft's level records."""
+        (after levels_reserve): the frames' LEVEL_DTYPE records (host), merged into the aircraft's level records.  mlat
+        (after mlat_reserve): the frames' MLAT_FIX_DTYPE fixes (host), merged into the aircraft's mlat records."""
         frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
         ptr = frames.ctypes.data if len(frames) else None
-        if levels is None:
+        if mlat is not None:
+            fixes = np.ascontiguousarray(mlat, dtype=MLAT_FIX_DTYPE)
+            if len(fixes) != len(frames):
+                raise ValueError(f"mlat: {len(fixes)} fixes for {len(frames)} frames")
+            keep, lptr = (None, None) if levels is None else self._host_levels(levels, len(frames))
+            self._call("update_mlat", ptr, fixes.ctypes.data if len(fixes) else None, lptr, len(frames), int(sample_base))
+        elif levels is None:
             self._call("update", ptr, len(frames), int(sample_base))
         else:
             keep, lptr = self._host_levels(levels, len(frames))
             self._call("update_levels", ptr, lptr, len(frames), int(sample_base))
 
-    def update_device(self, dev_ptr, n, sample_base=0, levels_ptr=None):
+    def update_device(self, dev_ptr, n, sample_base=0, levels_ptr=None, mlat_ptr=None):
         """n frames at dev_ptr in the ctx device's memory (e.g. result_device() after fetch_counts()).  levels_ptr
-        (after levels_reserve): their n level records, on the device (e.g. levels_device()) or a host address."""
-        if levels_ptr is None:
+        (after levels_reserve): their n level records, on the device (e.g. levels_device()) or a host address.  mlat_ptr
+        (after mlat_reserve): their n adsb_mlat_fix records, on the device (e.g. mlat_device()[0]) or a host address;
+        every address may be a host one too, each on its own."""
+        if mlat_ptr is not None:
+            self._call("update_mlat", dev_ptr, mlat_ptr, levels_ptr, int(n), int(sample_base))
+        elif levels_ptr is None:
             self._call("update", dev_ptr, int(n), int(sample_base))
         else:
             self._call("update_levels", dev_ptr, levels_ptr, int(n), int(sample_base))
@@ -1320,6 +1355,28 @@ class TrackTable(_TrackStore):
     def levels(self):
         """AIRCRAFT_LEVEL_DTYPE records (each aircraft's signal level), aligned with aircraft()[0]."""
         return self._fetch("fetch_levels", [AIRCRAFT_LEVEL_DTYPE])[0]
+
+    def mlat_reserve(self, max_disagreement_m):
+        """adsb_track_table_mlat_reserve: one AIRCRAFT_MLAT_DTYPE record beside every aircraft record, which an update
+        given `mlat` merges the frames' fixes into; a reported airborne position farther than max_disagreement_m (metres)
+        from the solved one disagrees."""
+        self._call("mlat_reserve", float(max_disagreement_m))
+
+    def mlat(self):
+        """AIRCRAFT_MLAT_DTYPE records (each aircraft's newest multilaterated position and its check counts), aligned
+        with aircraft()[0]."""
+        return self._fetch("fetch_mlat", [AIRCRAFT_MLAT_DTYPE])[0]
+
+    def frame_mlat(self):
+        """One FRAME_MLAT_DTYPE record per frame of the last update given `mlat`, in its list order."""
+        return self._fetch("fetch_frame_mlat", [FRAME_MLAT_DTYPE], size=self.max_frames)[0]
+
+    def mlat_device(self):
+        """Device address of the mlat records, one per record place in slot order (as levels_device); no
+        synchronisation."""
+        dev = C.c_void_p()
+        self._call("mlat_device", C.byref(dev))
+        return dev.value
 
     def fixes_reserve(self, site):
         """adsb_track_table_fixes_reserve: from now on every update also decodes each position message on its own

@@ -1320,6 +1320,95 @@ int adsb_track_bank_fixes_device(adsb_track_bank *bank, const adsb_fix **dev);
 int adsb_track_bank_fetch_frame_fixes(adsb_track_bank *bank, adsb_frame_fix *out, size_t max, size_t *n);
 
 /*
+ * Multilaterated positions per aircraft.  adsb_multilaterate leaves one adsb_mlat_fix per correlated message; with an
+ * mlat reserve a TABLE keeps them per aircraft, one 64-byte adsb_aircraft_mlat per record place beside its record, and
+ * checks every position an aircraft reports against where its signal came from.  Correlate's messages as a plain
+ * adsb_frame[] (adsb_correlated_device's frames_dev) and fixes[] line up index for index, and both lie in device memory.  A
+ * correlated list is one merged stream, so this is for tables only: a bank has no such entry points and behaves as
+ * before.
+ *
+ * COUNTED  Frame j of an update_mlat is counted for its aircraft iff its point is not ADSB_TRACK_UNTRACKED.  A counted
+ *   frame whose fix has ADSB_MLAT_ATTEMPTED adds 1 to n_attempted, one whose fix has ADSB_MLAT_VALID adds 1 to n_valid
+ *   (both saturate at 2^32 - 1 and stay there).  The NEWEST counted frame with a VALID fix is kept: the last such frame
+ *   in list order (frames with equal offsets are applied in list order, as for the fix merge).  From it come latitude,
+ *   longitude, height_m (rounded to f32 once), residual_rms_m, pdop, n_used, ADSB_TRACK_MLAT_ALTITUDE (the fix has
+ *   ADSB_MLAT_ALTITUDE) and time, the store's frame time of that frame: (sample_base + offset) x seconds_per_sample,
+ *   the same single rounded product as every other time of the store.  A fix that is not valid (TOO_FEW, SINGULAR,
+ *   rejected, BAD_INDEX, ...) leaves the kept fix alone.
+ * THE CHECK  A counted frame is CHECKED iff its fix is VALID, the frame is an AIRBORNE position message (DF 17, TC 9-18
+ *   or 20-22; surface frames are not checked) and (fix.latitude, fix.longitude, 180 NM) is a site that
+ *   adsb_track_table_fixes_reserve accepts (a NaN or a position off the globe is none).  The frame is then decoded ON
+ *   ITS OWN with the solved position as the site, by "Positions from single messages" above, and disagreement_m is that
+ *   decode's f64 range x 1852, rounded to f32 once.  If the decode turns the frame away (|lat| > 90, or farther than
+ *   180 NM) the frame is CHECKED and FAR, its disagreement_m is 333360 (180 NM) and it disagrees.  A checked frame
+ *   DISAGREES iff it is FAR or the f64 distance in metres exceeds the reserve's max_disagreement_m.  A local decode
+ *   picks the position nearest its site among those a whole zone apart, so the check measures a displacement modulo
+ *   the zone size (360 NM in latitude): one of a whole number of zones is not seen.  last_disagreement_m is the newest checked frame's value, max_disagreement_m (the field) the
+ *   maximum over the checked frames, n_checked and n_disagree saturating sums.
+ * Every field combines by an associative rule (saturating add, max, newest by position), so one list (frames and
+ * fixes alike) cut into any sequence of update_mlat calls gives the same 64 bytes per aircraft, and two runs give the
+ * same bytes.  An EMPTY record is all zeros with time NaN.  An aircraft's is empty at admission, at re-admission after
+ * an expire, after a reset, and while the store held the aircraft from before the reserve, until its next counted
+ * frame that changes it.  Expire moves a survivor's mlat record with its record.
+ * On the device, after the pairs step: one thread per frame reads the frame, its fix and its slot and writes one
+ * adsb_frame_mlat in list order and a 32-byte scan operand in sorted order (the f64 CPR decode and the haversine are
+ * the only arithmetic), one segmented inclusive scan over the sorted list (rocPRIM; head mark, newest valid frame,
+ * newest checked frame, maximum disagreement, four saturating counts: integers and one float max, no float sums) and
+ * one thread per segment tail that merges into the side record: linear in the list however long one aircraft's part
+ * is, no atomics.  Device memory, all of it allocated by the reserve and none before: 64 bytes per place of
+ * max_aircraft, and per frame of max_frames 16 + 32 + 32 bytes plus 64 bytes of device staging for a host fixes array
+ * and rocPRIM's scan scratch; 64 bytes per frame of pinned host memory.  A table that never reserves allocates
+ * nothing, launches exactly the kernels it launched before and returns the same bytes; adsb_track_table_update and
+ * update_levels of a table that did reserve behave as before and leave the mlat records alone (apart from admission
+ * emptying a place).  fetch_changed, the per-frame summaries and a bank's fused view carry no mlat records.
+ */
+#define ADSB_TRACK_MLAT_VALID    0x1u  /* the record holds a fix                                     */
+#define ADSB_TRACK_MLAT_ALTITUDE 0x2u  /* that fix used the message's own altitude (ADSB_MLAT_ALTITUDE) */
+#define ADSB_TRACK_MLAT_CHECKED  0x4u  /* last_disagreement_m holds a value                          */
+#define ADSB_TRACK_MLAT_DISAGREE 0x8u  /* adsb_frame_mlat only: this frame's disagreement exceeds the limit */
+#define ADSB_TRACK_MLAT_FAR      0x10u /* adsb_frame_mlat only: the local decode was turned away (see above) */
+typedef struct adsb_aircraft_mlat {   /* 64 bytes, one per record place, beside the 128-byte record */
+    double   time;                  /* table frame time of the message the kept fix belongs to; NaN if none */
+    double   latitude, longitude;   /* degrees, the fix's */
+    float    height_m, residual_rms_m, pdop;   /* the fix's (height rounded to f32 once) */
+    float    last_disagreement_m;   /* of the newest CHECKED frame; 0 unless ADSB_TRACK_MLAT_CHECKED */
+    float    max_disagreement_m;    /* maximum over the checked frames since admission */
+    uint32_t n_attempted, n_valid;  /* counted frames whose fix has ADSB_MLAT_ATTEMPTED / ADSB_MLAT_VALID; saturating */
+    uint32_t n_checked, n_disagree; /* checked frames / those beyond the limit; saturating */
+    uint16_t n_used;                /* the kept fix's */
+    uint8_t  flags, reserved;       /* ADSB_TRACK_MLAT_*; 0 */
+} adsb_aircraft_mlat;
+typedef struct adsb_frame_mlat {      /* 16 bytes, one per frame of the last update_mlat, in its list order */
+    float    disagreement_m;        /* 0 unless CHECKED */
+    uint32_t icao;
+    uint32_t flags;                 /* VALID (this frame's fix was valid and counted), CHECKED, DISAGREE, FAR */
+    uint32_t reserved;              /* 0 */
+} adsb_frame_mlat;
+/* Allocates the above, keeps the limit and empties every mlat record.  May wait for the device.  A second reserve
+ * changes nothing (the first limit stays).  ADSB_E_ARG for a NULL table or a max_disagreement_m that is not finite and
+ * > 0 (checked before the table is touched); ADSB_E_NOMEM if the memory is not to be had. */
+int adsb_track_table_mlat_reserve(adsb_track_table *table, double max_disagreement_m);
+/* adsb_track_table_update plus the merge above: points, records, summaries, changed list, velocity and single-message
+ * fixes are byte for byte what update gives on the same frames.  fixes[n] is the frames' fixes in list order.  With
+ * levels not NULL it is also adsb_track_table_update_levels and needs the levels reserve.  frames, fixes and levels may
+ * each be host memory or memory of the ctx's device, independently; host arrays have been copied when this returns.
+ * ADSB_E_ARG for a NULL table, or NULL frames or fixes with n > 0; ADSB_E_STATE without an mlat reserve, or with levels
+ * and no levels reserve; ADSB_E_CAPACITY for n > max_frames; n = 0 is ADSB_OK. */
+int adsb_track_table_update_mlat(adsb_track_table *table, const adsb_frame *frames, const adsb_mlat_fix *fixes,
+                                 const adsb_frame_level *levels /* may be NULL */, size_t n, uint64_t sample_base);
+/* Waits; one mlat record per aircraft, in exactly the order adsb_track_table_fetch returns the records (ascending
+ * ICAO); *n = records held even if more than max.  ADSB_E_ARG for a NULL table, or NULL out with max > 0;
+ * ADSB_E_STATE without a reserve. */
+int adsb_track_table_fetch_mlat(adsb_track_table *table, adsb_aircraft_mlat *out, size_t max, size_t *n);
+/* Does not synchronise: the device address of the mlat records, one per record PLACE in slot order (as
+ * adsb_track_table_levels_device); dev may be NULL.  ADSB_E_ARG for a NULL table, ADSB_E_STATE without a reserve. */
+int adsb_track_table_mlat_device(adsb_track_table *table, const adsb_aircraft_mlat **dev);
+/* Waits; one adsb_frame_mlat per frame of the last update_mlat, in its list order: copies min(frames, max), *n =
+ * copied.  A frame of an aircraft the full table turned away has its icao and nothing else.  ADSB_E_ARG for a NULL
+ * table, or NULL out with max > 0; ADSB_E_STATE without a reserve or before the first update_mlat (since a reset). */
+int adsb_track_table_fetch_frame_mlat(adsb_track_table *table, adsb_frame_mlat *out, size_t max, size_t *n);
+
+/*
  * ---- several GPUs behind one call ---------------------------------------------------------
  * The reference's thread 2 is one function on one thread (src/adsb.rs:92, spawned at adsb.rs:147); a group is the
  * drop-in for that function when the buffer should be spread over N devices: one context per member, the offsets

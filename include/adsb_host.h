@@ -189,6 +189,16 @@ int adsb_host_clock_apply(const adsb_clock_cfg *cfg, const adsb_clock *clocks, u
  */
 int adsb_host_fix_of(const adsb_site *site, const uint8_t bytes[14], double time, adsb_fix *out, uint32_t *frame_flags);
 
+/*
+ * CPU mirror of the per-frame step of a table with an mlat reserve (adsb_hip.h, "Multilaterated positions per
+ * aircraft"): the same program text as the device's, no device needed.  *out = the adsb_aircraft_mlat of an aircraft
+ * whose only counted frame since admission is this one, with fix *fix, heard at frame time `time`, under the limit
+ * max_disagreement_m.  *frame_flags and *disagreement_m (each optional) = the frame's adsb_frame_mlat.flags and
+ * disagreement_m.  ADSB_E_ARG for NULL bytes, fix or out, or a limit that adsb_track_table_mlat_reserve would refuse.
+ */
+int adsb_host_track_mlat_of(double max_disagreement_m, const uint8_t bytes[14], const adsb_mlat_fix *fix, double time,
+                            adsb_aircraft_mlat *out, uint32_t *frame_flags, float *disagreement_m);
+
 /* ---- behind the channel: tracker + CPR ------------------------------------------- */
 
 /* cpr.rs:39-54 calc_num_zones; cpr.rs:135-147 calculate_geographic_position (returns 1 = Some, 0 = None).

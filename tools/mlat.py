@@ -11,7 +11,13 @@ metres, residual in metres, hdop, receivers used.
 
 --sync first estimates every receiver's clock offset and drift against receiver --reference from the position messages
 of the recordings themselves (clock sync; the clock_offset_s column is then the prior, good enough for correlate's
-window), prints one '# clock' line per receiver, and solves the fixes from the corrected times."""
+window), prints one '# clock' line per receiver, and solves the fixes from the corrected times.
+
+--aircraft feeds the correlated messages and their fixes into a track table (on the device where they lie; with --host
+through the CPU mirror of the per-frame step and a plain merge) and prints, instead of the fixes, one line per aircraft:
+ICAO, callsign, the position it reports, the multilaterated position, the age of that fix at the last message, pdop,
+valid/attempted fixes, checked/disagreeing position messages, and the largest disagreement in metres.
+--max-disagreement M (default 1000): how far a reported position may lie from the solved one."""
 import argparse
 import os
 import sys
@@ -32,6 +38,64 @@ def read_sites(path):
     return sites
 
 
+def host_table(A, frames, fixes, max_disagreement):
+    """What a table with an mlat reserve makes of the list, without a device: the CPU tracker for the records, the CPU
+    mirror of the per-frame step and the header's merge rules (saturating add, max, newest by position) for the mlat
+    records -> (AIRCRAFT_DTYPE records, AIRCRAFT_MLAT_DTYPE records), ascending ICAO."""
+    import numpy as np
+    tracker, state, count = A.Tracker(), {}, {}
+    sat = (1 << 32) - 1
+    for fr, fx in zip(frames, fixes):
+        b = fr["bytes"].tobytes()
+        time = float(int(fr["offset"])) * 0.5e-6
+        icao = b[1] << 16 | b[2] << 8 | b[3]
+        tracker.update(b, time)
+        count[icao] = count.get(icao, 0) + 1
+        one = A.host_track_mlat_of(max_disagreement, b, fx, time)[0]
+        a = state.get(icao)
+        if a is None:
+            a = np.zeros((), dtype=A.AIRCRAFT_MLAT_DTYPE)
+            a["time"] = np.nan
+        for name in ("n_attempted", "n_valid", "n_checked", "n_disagree"):
+            a[name] = min(int(a[name]) + int(one[name]), sat)
+        if one["flags"] & A.ADSB_TRACK_MLAT_VALID:
+            for name in ("time", "latitude", "longitude", "height_m", "residual_rms_m", "pdop", "n_used"):
+                a[name] = one[name]
+            a["flags"] = (int(a["flags"]) & A.ADSB_TRACK_MLAT_CHECKED) | \
+                (int(one["flags"]) & (A.ADSB_TRACK_MLAT_VALID | A.ADSB_TRACK_MLAT_ALTITUDE))
+        if one["flags"] & A.ADSB_TRACK_MLAT_CHECKED:
+            a["last_disagreement_m"] = one["last_disagreement_m"]
+            a["max_disagreement_m"] = max(a["max_disagreement_m"], one["max_disagreement_m"])
+            a["flags"] = int(a["flags"]) | A.ADSB_TRACK_MLAT_CHECKED
+        state[icao] = a
+    recs = np.zeros(len(state), dtype=A.AIRCRAFT_DTYPE)
+    mlat = np.zeros(len(state), dtype=A.AIRCRAFT_MLAT_DTYPE)
+    for k, icao in enumerate(sorted(state)):
+        s = tracker.get(icao)
+        recs[k] = (s.latitude, s.longitude, s.last_contact, icao, s.altitude, 1 if s.has_position else 0, count[icao],
+                   s.callsign)
+        mlat[k] = state[icao]
+    return recs, mlat
+
+
+def aircraft_lines(A, recs, mlat, now):
+    """One tab-separated line per aircraft, under a header line."""
+    out = ("ICAO\tCallsign\tLatitude\tLongitude\tMlatLat\tMlatLon\tAge\tPdop\tValid/Attempted\tChecked/Disagree"
+           "\tMaxDisagreement\n")
+    for r, m in zip(recs, mlat):
+        call = r["callsign"].decode("ascii", "replace").strip() or "n/a"
+        said = f"{float(r['latitude']):.5f}\t{float(r['longitude']):.5f}" if r["has_position"] else "n/a\tn/a"
+        if m["flags"] & A.ADSB_TRACK_MLAT_VALID:
+            solved = (f"{float(m['latitude']):.5f}\t{float(m['longitude']):.5f}\t{now - float(m['time']):.1f}"
+                      f"\t{float(m['pdop']):.1f}")
+        else:
+            solved = "n/a\tn/a\tn/a\tn/a"
+        worst = f"{float(m['max_disagreement_m']):.0f}" if m["flags"] & A.ADSB_TRACK_MLAT_CHECKED else "n/a"
+        out += (f"{int(r['icao']):06X}\t{call}\t{said}\t{solved}\t{int(m['n_valid'])}/{int(m['n_attempted'])}"
+                f"\t{int(m['n_checked'])}/{int(m['n_disagree'])}\t{worst}\n")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("sites")
@@ -44,6 +108,9 @@ def main():
     ap.add_argument("--reference", type=int, default=0, help="with --sync: the receiver whose clock is taken as true")
     ap.add_argument("--max-residual-us", type=float, default=0.0,
                     help="with --sync: a second pass without the rows whose residual is larger, microseconds")
+    ap.add_argument("--aircraft", action="store_true", help="one line per aircraft instead of one per fix")
+    ap.add_argument("--max-disagreement", type=float, default=1000.0,
+                    help="with --aircraft: metres a reported position may lie from the multilaterated one")
     args = ap.parse_args()
 
     import numpy as np
@@ -59,6 +126,15 @@ def main():
     # wire input's frame offsets are 2 MHz samples: the unit of the messages' own times
     sync = dict(reference=args.reference, max_residual_s=args.max_residual_us * 1e-6, seconds_per_time=0.5e-6)
     clocks = None
+    aircraft = None
+
+    def table_of(d, n_msgs):
+        """The correlated messages and their fixes, where they lie on the device, into a table -> (records, mlat)"""
+        with A.TrackTable(d, max_frames=max(n_msgs, 1), seconds_per_sample=0.5e-6) as table:
+            table.mlat_reserve(args.max_disagreement)
+            table.update_device(d.correlated_device()[1], n_msgs, 0, mlat_ptr=d.mlat_device()[0])
+            return table.aircraft()[0], table.mlat()
+
     if args.host:
         win = A.host_wire_parse(data, ends, filter=["crc", "df17"])
         msgs, _, recs = A.host_correlate(win.frames, win.counts, args.window)
@@ -70,6 +146,8 @@ def main():
                                                                               seconds_per_tick=1 / 12e6 / 256))
         else:
             fixes, hdr = A.host_multilaterate(sites, msgs, recs, win.rx, **cfg)
+        if args.aircraft:
+            aircraft = host_table(A, A.frames_of_messages(msgs), fixes, args.max_disagreement)
     elif args.sync:
         with A.AdsbDemod(max_samples=1 << 16, max_out=1024) as d:
             win = d.wire_in_of(data, ends, filter=["crc", "df17"])
@@ -77,19 +155,26 @@ def main():
             fixes, hdr = d.multilaterate(sites, rx=d.wire_in_device()[1], clocks=True, clock_cfg=sync, **cfg)
             clocks, _ = d.fetch_clocks()
             msgs, _, recs = d.fetch_correlated()
+            if args.aircraft:
+                aircraft = table_of(d, len(msgs))
     else:
         with A.AdsbDemod(max_samples=1 << 16, max_out=1024) as d:
             win = d.wire_in_of(data, ends, filter=["crc", "df17"])
             d.correlate_of_async((d.wire_in_device()[0], len(win.frames)), win.counts, args.window)
             fixes, hdr = d.multilaterate(sites, rx=d.wire_in_device()[1], **cfg)   # behind correlate, nothing fetched
             msgs, _, recs = d.fetch_correlated()
+            if args.aircraft:
+                aircraft = table_of(d, len(msgs))
     for r, k in enumerate(clocks if clocks is not None else ()):
         what = "reference" if k["flags"] & A.ADSB_CLOCK_REFERENCE else "reached" if k["flags"] & A.ADSB_CLOCK_REACHED \
             else "unreached"
         print(f"# clock {r:3d} {what:9s} offset {k['offset_s']:+.9f} s drift {k['drift'] * 1e6:+9.3f} ppm "
               f"rms {k['residual_rms_s'] * 1e9:8.1f} ns rows {int(k['n_rows'])} dropped {int(k['n_dropped'])}")
+    if aircraft is not None:
+        newest = float(int(msgs["time"][-1])) * 0.5e-6 if len(msgs) else 0.0
+        print(aircraft_lines(A, aircraft[0], aircraft[1], newest), end="")
     for m, f in zip(msgs, fixes):
-        if f["flags"] & A.ADSB_MLAT_VALID:
+        if aircraft is None and f["flags"] & A.ADSB_MLAT_VALID:
             t = int(win.rx["ticks"][recs["frame"][m["first"]]]) / 12e6
             icao = int(m["bytes"][1]) << 16 | int(m["bytes"][2]) << 8 | int(m["bytes"][3])
             print(f"{t:14.6f} {icao:06X} {f['latitude']:10.5f} {f['longitude']:11.5f} {f['height_m']:8.0f} "
