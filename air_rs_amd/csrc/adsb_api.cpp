@@ -530,20 +530,30 @@ static int small_wait(adsb_ctx *c, uint32_t set, uint64_t seq, bool at_least = f
     return ADSB_OK;
 }
 
+// Completes the list of result set `set` (a small launch that small_wait has seen complete) if tiles of it lost their
+// slots: the re-run scans the launch's samples (li.iq) AGAIN, so they must still be where the launch read them.  Leaves
+// the newest launch the one in view.
+static int small_complete(adsb_ctx *c, uint32_t set)
+{
+    const uint64_t *hdr = reinterpret_cast<const uint64_t *>(c->sm.blob[set]);
+    if (!(hdr[2] & ADSB_FLAG_INCOMPLETE)) return ADSB_OK;
+    // slot-pool overflow (pathological input): the standard re-run path completes the blob in place
+    const uint32_t newest = c->last;
+    view_launch(c, set);
+    int rc = sync_header(c);
+    view_launch(c, newest);
+    if (rc != ADSB_OK) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return ADSB_OK;
+}
+
 // Hands the finished list of result set `set` (a small launch that small_wait has seen complete) to the caller.
 static int small_collect(adsb_ctx *c, uint32_t set, adsb_frame *out, size_t max_out, size_t *n_out, uint64_t *total_found,
                          uint32_t *flags)
 {
     const uint64_t *hdr = reinterpret_cast<const uint64_t *>(c->sm.blob[set]);
-    if (hdr[2] & ADSB_FLAG_INCOMPLETE) {
-        // slot-pool overflow (pathological input): the standard re-run path completes the blob in place
-        const uint32_t newest = c->last;
-        view_launch(c, set);
-        int rc = sync_header(c);
-        view_launch(c, newest);
-        if (rc != ADSB_OK) return rc;
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
+    int rc = small_complete(c, set);
+    if (rc != ADSB_OK) return rc;
     uint64_t n = hdr[0];
     uint32_t fl = (uint32_t)hdr[2] & ~ADSB_FLAG_INCOMPLETE;
     if (n > max_out) { n = max_out; fl |= ADSB_FLAG_TRUNCATED; }
@@ -1096,7 +1106,8 @@ struct adsb_feed {
     std::vector<hipEvent_t> ring_done; // H2D out of that ring slot has completed
     std::vector<char> ring_busy;
     // a one-dispatch launch reads its samples straight from the ring slot: the slot may be overwritten once the launch's
-    // sequence word says so (ring_seq != 0: result set ring_set carries that number when the kernel has finished)
+    // sequence word says so (ring_seq != 0: result set ring_set carries that number when the kernel has finished) AND, if
+    // its buffer is still unpopped, its list is complete -- a re-run after a slot-pool overflow reads the slot again
     std::vector<uint64_t> ring_seq;
     std::vector<uint32_t> ring_set;
     uint32_t ring_next = 0;
@@ -1205,6 +1216,15 @@ static int feed_ring_slot(adsb_feed *f, uint32_t *slot)
     if (f->ring_seq[r]) { // ... and so must the one-dispatch kernel that reads its samples from the slot itself
         const int rc = small_wait(f->c, f->ring_set[r], f->ring_seq[r], true);
         if (rc != ADSB_OK) return rc;
+        // ... and, while that buffer has not been popped, so must its LIST: a launch whose tiles lost their slots is
+        // re-run from these samples (small_complete), which the pop would otherwise do after the producer has overwritten
+        // them.  (Unpopped means no later launch has used its result set: the sequence word is exactly this launch's.)
+        for (uint64_t k = f->popped; k < f->pushed; ++k) {
+            const adsb_feed::Entry &e = f->q[k & 1u];
+            if (!e.launched || !e.small || e.set != f->ring_set[r] || e.seq != f->ring_seq[r]) continue;
+            const int rc2 = small_complete(f->c, e.set);
+            if (rc2 != ADSB_OK) return rc2;
+        }
         f->ring_seq[r] = 0;
     }
     *slot = r;

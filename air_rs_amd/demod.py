@@ -1205,8 +1205,8 @@ class Feed:
         cap = self._dem.max_out if max_out is None else max_out
         out = np.zeros(max(cap, 1), dtype=FRAME_DTYPE)
         n_out, flags, first = C.c_size_t(), C.c_uint32(), C.c_uint64()
-        L.check(self._lib.adsb_feed_pop(self._h, out.ctypes.data_as(C.POINTER(L.AdsbFrame)), cap, C.byref(n_out),
-                                        C.byref(flags), C.byref(first)), "adsb_feed_pop")
+        ptr = out.ctypes.data_as(C.POINTER(L.AdsbFrame)) if cap else None    # (max_out = 0: no buffer at all)
+        L.check(self._lib.adsb_feed_pop(self._h, ptr, cap, C.byref(n_out), C.byref(flags), C.byref(first)), "adsb_feed_pop")
         return out[:n_out.value].copy(), flags.value, first.value
 
 

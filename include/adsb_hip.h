@@ -180,10 +180,17 @@ typedef struct adsb_feed_cfg {
     size_t   max_chunk;   /* largest buffer (samples) that will be pushed                          */
     uint32_t carry;       /* 0 = per-buffer semantics (reference), 1 = carry the 240-sample tail    */
     uint32_t ring_slots;  /* pinned host buffers of max_chunk samples (0: 3)                        */
+    /* Rule: a ring slot whose buffer went through the one-dispatch kernel is not handed out (adsb_feed_acquire) or
+     * overwritten (adsb_feed_push) until that buffer has been popped or its list is complete (ADSB_FLAG_INCOMPLETE
+     * cleared in its result blob): the kernel reads its samples from the slot itself, and a list with tiles over
+     * their slots is rebuilt from those same samples.  With 2 slots and two buffers in flight the slot handed out
+     * belongs to the oldest, unpopped buffer: acquire / push then wait for its kernel and, if need be, rebuild its
+     * list first.  With 3 or more slots the slot always belongs to a popped buffer. */
 } adsb_feed_cfg;
 int adsb_feed_open(adsb_ctx *ctx, const adsb_feed_cfg *cfg, adsb_feed **out_feed);
 /* Optional zero-copy producer path: a pinned ring slot (max_chunk samples) to fill in place; hand it over with
- * adsb_feed_push(feed, NULL, n).  Blocks only if the DMA out of that slot has not finished yet. */
+ * adsb_feed_push(feed, NULL, n).  Blocks only if the DMA out of that slot, or the unpopped one-dispatch launch that
+ * reads it (see ring_slots), has not finished yet. */
 int adsb_feed_acquire(adsb_feed *feed, void **host_slot);
 /* Enqueues one buffer (copied into the ring unless it was acquired) and returns without waiting for the GPU.
  * ADSB_E_STATE when two buffers are already in flight (pop first). */
