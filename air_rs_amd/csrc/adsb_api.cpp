@@ -1,7 +1,7 @@
 // adsb_api.cpp -- the extern "C" boundary (include/adsb_hip.h) over the gfx950 scan kernels: the context, the launches,
-// the fetch and the decoded fields.  Every other part of the boundary has a file of its own: adsb_track_api.cpp,
-// adsb_levels_api.cpp, adsb_wire_api.cpp, adsb_wire_in_api.cpp, adsb_correlate_api.cpp, adsb_mlat_api.cpp,
-// adsb_clock_api.cpp.
+// the fetch and the decoded fields.  Every other part of the boundary has a file of its own: adsb_feed_api.cpp,
+// adsb_track_api.cpp, adsb_levels_api.cpp, adsb_wire_api.cpp, adsb_wire_in_api.cpp, adsb_correlate_api.cpp,
+// adsb_mlat_api.cpp, adsb_clock_api.cpp.
 //
 // Replaces, per received buffer, the body of the reference's thread 2 loop
 // (src/adsb.rs:95-116).  There is NO CPU fallback: without a HIP device adsb_create() fails with
@@ -9,7 +9,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -22,6 +21,7 @@
 
 using adsbk::kTile;
 using adsbk::kWindow;
+using Launch = adsb_ctx::ResultSet::Launch;
 
 static uint32_t tiles_for(uint64_t n_samples, int sample_type, int scan)
 {
@@ -269,39 +269,62 @@ extern "C" int adsb_debug_tile_stamps(adsb_ctx *c, uint32_t *out, size_t max_til
     if (!adsbk::tile_stamps_built() || !c->stamps) return ADSB_E_STATE;
     HIPCHK(hipSetDevice(c->cfg.device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    const size_t n = std::min<size_t>(max_tiles, c->last_tiles);
+    const size_t n = std::min<size_t>(max_tiles, c->launch().tiles);
     if (n) HIPCHK(hipMemcpy(out, c->stamps, n * 64, hipMemcpyDeviceToHost));
     *n_tiles = n;
     return ADSB_OK;
 }
 
+// Records in result set `r` what launch `idx` works on, before any argument struct is built from it; the derived results
+// are stale from here.  The list goes behind the public header `hdr_pub` ([32 bytes | cap frames]) or, without one, to the
+// set's own `out`.  The launch becomes the one in view (and li.valid) only when every enqueue has succeeded.
+static Launch &record_launch(adsb_ctx *c, adsb_ctx::ResultSet &r, uint32_t idx, const void *iq, uint32_t channels,
+                             uint64_t samples, uint64_t stride, void *hdr_pub, uint32_t cap)
+{
+    Launch &li = r.li;
+    li.valid = false;
+    li.iq = iq;
+    li.channels = channels;
+    li.samples = samples;
+    li.stride = stride;
+    li.base = c->stream_base;
+    li.tpc = tiles_for(samples, c->cfg.sample_type, c->scan);
+    li.tiles = li.tpc * channels;
+    li.out = hdr_pub ? reinterpret_cast<adsb_frame *>(static_cast<char *>(hdr_pub) + 32) : r.out;
+    li.cap = cap;
+    li.hdr_pub = static_cast<uint64_t *>(hdr_pub);
+    li.idx = idx;
+    c->launched = true;
+    c->mark_derived_stale();
+    return li;
+}
+
+// (both read the launch from r.li: the first pass publishes the public header, a re-run of lost tiles does not)
 static adsbk::DemodArgs demod_args(adsb_ctx *c, adsb_ctx::ResultSet &r, uint32_t tile_first, uint32_t tile_count,
                                    bool first_pass)
 {
     adsbk::DemodArgs a{};
-    a.iq = c->last_iq;
-    a.n_samples = c->last_samples;
-    a.channel_stride = c->last_stride;
-    a.tiles_per_channel = c->last_tpc;
+    a.iq = r.li.iq;
+    a.n_samples = r.li.samples;
+    a.channel_stride = r.li.stride;
+    a.tiles_per_channel = r.li.tpc;
     a.tile_first = tile_first;
     a.tile_count = tile_count;
     a.count_groups = first_pass ? 1u : 0u;
-    a.offset_base = c->last_base;
+    a.offset_base = r.li.base;
     a.fused_pass_only = c->fused_pass_only ? 1u : 0u;
     a.seg = r.seg;
     a.slots = r.slots;
     a.pool_first = c->n_tiles_max * adsbk::kQuota;
     a.cap_slots = c->cap_slots;
     a.hdr = r.hdr;
-    a.hdr_pub = (first_pass && c->ext_blob) ? static_cast<uint64_t *>(c->ext_blob) : nullptr;
+    a.hdr_pub = first_pass ? r.li.hdr_pub : nullptr;
     a.pool_off = (c->pool_off && first_pass) ? 1u : 0u; // (first passes only: the re-run of lost tiles needs the pool)
     a.stamps = c->stamps;
     return a;
 }
 
-// launch_epoch: the index of the launch the pass belongs to (tags the look-back words)
-static adsbk::FinishArgs finish_args(adsb_ctx *c, adsb_ctx::ResultSet &r, uint32_t launch_epoch, uint32_t tile_first,
-                                     uint32_t tile_count, bool rerun)
+static adsbk::FinishArgs finish_args(adsb_ctx *c, adsb_ctx::ResultSet &r, uint32_t tile_first, uint32_t tile_count, bool rerun)
 {
     adsbk::FinishArgs a{};
     a.seg = r.seg;
@@ -310,14 +333,12 @@ static adsbk::FinishArgs finish_args(adsb_ctx *c, adsb_ctx::ResultSet &r, uint32
     a.lb = c->lb;
     a.lb_groups_at = c->lb_groups_at;
     a.chan_prefix = rerun ? nullptr : r.chan_prefix;
-    a.epoch = (launch_epoch + 1u) & 0x3FFFFFFFu;
-    const bool ext = c->ext_blob && !rerun;
-    a.out = ext ? reinterpret_cast<adsb_frame *>(static_cast<char *>(c->ext_blob) + 32) : r.out;
-    a.hdr_pub = ext ? static_cast<uint64_t *>(c->ext_blob) : nullptr;
-    a.tiles_per_channel = c->last_tpc;
-    a.n_channels = c->last_channels;
-    a.max_out = ext ? (uint32_t)std::min<size_t>(c->ext_frames, c->cfg.max_out) : (uint32_t)c->cfg.max_out;
-    if (rerun) { a.out = c->last_out; a.max_out = c->last_cap; }
+    a.epoch = (r.li.idx + 1u) & 0x3FFFFFFFu; // (the index of the launch the pass belongs to tags the look-back words)
+    a.out = r.li.out;
+    a.hdr_pub = rerun ? nullptr : r.li.hdr_pub;
+    a.tiles_per_channel = r.li.tpc;
+    a.n_channels = r.li.channels;
+    a.max_out = r.li.cap;
     a.tile_first = tile_first;
     a.tile_count = tile_count;
     a.hdr = r.hdr;
@@ -346,23 +367,12 @@ extern "C" int adsb_demod_device_async(adsb_ctx *c, const void *iq_dev, uint32_t
     if (n_channels == 1) channel_stride = n_samples;
     HIPCHK(hipSetDevice(c->cfg.device));
 
-    c->last_iq = iq_dev;
-    c->last_channels = n_channels;
-    c->last_samples = n_samples;
-    c->last_stride = channel_stride;
-    c->last_tpc = tiles_for(n_samples, c->cfg.sample_type, c->scan);
-    c->last_tiles = c->last_tpc * n_channels;
-    c->last_base = c->stream_base;
-    c->launched = true;
-    c->fields_current = false;
-    c->levels_current = false;
-    c->wire_current = false;
-    c->trk_done = false;
-
     // Launch i uses result set i & 1.  (ADSB_OVERLAP_ORDERING=1: the finishing kernel of launch i runs on `aux` beside
     // the scan of launch i+1, which only has to wait for the finishing kernel of launch i-2: same result set.)
     const uint32_t i = c->launch_idx;
     adsb_ctx::ResultSet &r = c->rs[i & 1u];
+    const Launch &li = record_launch(c, r, i, iq_dev, n_channels, n_samples, channel_stride, c->ext_blob,
+                                     (uint32_t)std::min<size_t>(c->ext_blob ? c->ext_frames : c->cfg.max_out, c->cfg.max_out));
     if (c->own_aux && r.g_pending) HIPCHK(hipStreamWaitEvent(c->stream, r.g_done, 0));
     HIPCHK(clear_exchange_words_at_wrap(c, i));
 
@@ -375,49 +385,30 @@ extern "C" int adsb_demod_device_async(adsb_ctx *c, const void *iq_dev, uint32_t
         }
         ev = c->ev[c->ev_count % kTimingRing];
     }
-    const adsbk::DemodArgs da = demod_args(c, r, 0, c->last_tiles, true);
+    const adsbk::DemodArgs da = demod_args(c, r, 0, li.tiles, true);
     // (ADSB_OVERLAP_ORDERING=1: the event the other stream waits for rides on the scan's own dispatch packet: no
     // barrier packet between two scans.)
     hipEvent_t scan_done = ev ? ev[1] : (c->own_aux ? r.k_done : nullptr);
     HIPCHK(adsbk::launch_demod(c->stream, c->cfg.sample_type, c->mag_mode, c->scan, da, ev ? ev[0] : nullptr, scan_done));
-    if (c->own_aux && scan_done && c->last_tiles) HIPCHK(hipStreamWaitEvent(c->aux, scan_done, 0));
+    if (c->own_aux && scan_done && li.tiles) HIPCHK(hipStreamWaitEvent(c->aux, scan_done, 0));
     // second kernel: CRC-24 / repair of the survivors the scan kernel sliced, and the ordered list.  Without tiles
     // (exactly 240 samples: adsb.rs:98 iterates 0..0) or in measurement mode (scan only) the list is empty.
-    if (c->last_tiles == 0 || c->fused_pass_only) {
-        adsbk::Header *hdr = r.hdr;
-        HIPCHK(adsbk::launch_empty_result(c->aux, hdr, c->ext_blob ? static_cast<uint64_t *>(c->ext_blob) : nullptr,
-                                          r.chan_prefix, c->last_channels, ev ? ev[2] : nullptr, ev ? ev[3] : nullptr));
+    if (li.tiles == 0 || c->fused_pass_only) {
+        HIPCHK(adsbk::launch_empty_result(c->aux, r.hdr, li.hdr_pub, r.chan_prefix, li.channels, ev ? ev[2] : nullptr,
+                                          ev ? ev[3] : nullptr));
     } else {
-        HIPCHK(adsbk::launch_finish(c->aux, finish_args(c, r, i, 0, c->last_tiles, false), ev ? ev[2] : nullptr, ev ? ev[3] : nullptr));
+        HIPCHK(adsbk::launch_finish(c->aux, finish_args(c, r, 0, li.tiles, false), ev ? ev[2] : nullptr, ev ? ev[3] : nullptr));
     }
     // (same stream: in-order already; adsb_stream_wait_results records the event when somebody asks for it)
     if (c->own_aux) {
         HIPCHK(hipEventRecord(r.g_done, c->aux));
         r.g_pending = true;
     }
-    c->last_out = c->ext_blob ? reinterpret_cast<adsb_frame *>(static_cast<char *>(c->ext_blob) + 32) : r.out;
-    c->last_cap = c->ext_blob ? (uint32_t)std::min<size_t>(c->ext_frames, c->cfg.max_out) : (uint32_t)c->cfg.max_out;
     c->last = i & 1u;
-    r.li.iq = c->last_iq; r.li.channels = c->last_channels; r.li.samples = c->last_samples; r.li.stride = c->last_stride;
-    r.li.base = c->last_base; r.li.tpc = c->last_tpc; r.li.tiles = c->last_tiles; r.li.out = c->last_out;
-    r.li.cap = c->last_cap; r.li.idx = i; r.li.valid = true;
+    r.li.valid = true;
     c->launch_idx = i + 1u;
-    if (ev && c->last_tiles) c->ev_count++;
+    if (ev && li.tiles) c->ev_count++;
     return ADSB_OK;
-}
-
-// Makes result set `set` (launch li.idx) the launch every fetch / re-plan function below refers to.  Only the
-// streaming front end looks at anything but the newest launch; it restores the newest before enqueueing again.
-static void view_launch(adsb_ctx *c, uint32_t set)
-{
-    const adsb_ctx::ResultSet::Launch &li = c->rs[set].li;
-    c->last = set;
-    c->last_iq = li.iq; c->last_channels = li.channels; c->last_samples = li.samples; c->last_stride = li.stride;
-    c->last_base = li.base; c->last_tpc = li.tpc; c->last_tiles = li.tiles; c->last_out = li.out; c->last_cap = li.cap;
-    c->fields_current = false;
-    c->levels_current = false;
-    c->wire_current = false;
-    c->trk_done = false;
 }
 
 // ---- the one-dispatch path for small buffers --------------------------------------------------------------------------
@@ -461,7 +452,7 @@ static int small_init(adsb_ctx *c)
 }
 
 // Can this buffer take the one-dispatch path?  (Not while the caller redirects results into a blob of its own.)
-static bool small_fits(adsb_ctx *c, size_t n_samples)
+bool small_fits(adsb_ctx *c, size_t n_samples)
 {
     return c->sm.enabled && !c->ext_blob && !c->fused_pass_only && !c->own_aux && n_samples > (size_t)kWindow &&
            small_init(c) == ADSB_OK && n_samples <= c->sm.max_samples;
@@ -469,58 +460,43 @@ static bool small_fits(adsb_ctx *c, size_t n_samples)
 
 // Enqueues one buffer (device-visible memory: pinned host or device, 16-byte aligned) as launch `launch_idx`; like
 // adsb_demod_device_async for one channel, in one dispatch.  *seq_out = the value the blob's sequence word will carry.
-static int small_launch(adsb_ctx *c, const void *iq, size_t n_samples, uint64_t *seq_out)
+int small_launch(adsb_ctx *c, const void *iq, size_t n_samples, uint64_t *seq_out)
 {
     HIPCHK(hipSetDevice(c->cfg.device));
-    c->last_iq = iq;
-    c->last_channels = 1;
-    c->last_samples = n_samples;
-    c->last_stride = n_samples;
-    c->last_tpc = tiles_for(n_samples, c->cfg.sample_type, c->scan);
-    c->last_tiles = c->last_tpc;
-    c->last_base = c->stream_base;
-    c->launched = true;
-    c->fields_current = false;
-    c->levels_current = false;
-    c->wire_current = false;
-    c->trk_done = false;
     const uint32_t i = c->launch_idx, set = i & 1u;
     adsb_ctx::ResultSet &r = c->rs[set];
+    const uint32_t tiles = record_launch(c, r, i, iq, 1, n_samples, n_samples, c->sm.blob[set], c->sm.cap).tiles;
     HIPCHK(clear_exchange_words_at_wrap(c, i));
-    adsbk::DemodArgs da = demod_args(c, r, 0, c->last_tiles, true);
-    da.hdr_pub = reinterpret_cast<uint64_t *>(c->sm.blob[set]);
-    adsbk::FinishArgs fa = finish_args(c, r, i, 0, c->last_tiles, false);
-    fa.out = reinterpret_cast<adsb_frame *>(c->sm.blob[set] + 32);
-    fa.hdr_pub = reinterpret_cast<uint64_t *>(c->sm.blob[set]);
-    fa.max_out = c->sm.cap;
+    const adsbk::DemodArgs da = demod_args(c, r, 0, tiles, true);
+    const adsbk::FinishArgs fa = finish_args(c, r, 0, tiles, false);
     adsbk::SmallArgs sa{};
     sa.done = c->sm.done + set;
     sa.seq_host = small_seq_word(c, set);
     sa.seq = ++c->sm.seq;
     HIPCHK(adsbk::launch_small(c->stream, c->cfg.sample_type, c->mag_mode, c->scan, da, fa, sa));
-    c->last_out = fa.out;
-    c->last_cap = fa.max_out;
-    c->last = set;
-    r.li.iq = iq; r.li.channels = 1; r.li.samples = n_samples; r.li.stride = n_samples;
-    r.li.base = c->last_base; r.li.tpc = c->last_tpc; r.li.tiles = c->last_tiles; r.li.out = c->last_out;
-    r.li.cap = c->last_cap; r.li.idx = i; r.li.valid = true;
+    c->last = i & 1u;
+    r.li.valid = true;
     c->launch_idx = i + 1u;
     *seq_out = sa.seq;
     return ADSB_OK;
 }
 
-// Waits (polling pinned memory, no HIP call on the usual path) until result set `set` carries sequence number `seq`.
-// (at_least: a LATER launch on the same result set has finished -- the stream is in order -- will do as well: used where
-// only "the device no longer reads that launch's input" matters)
-static int small_wait(adsb_ctx *c, uint32_t set, uint64_t seq, bool at_least = false)
+// Does result set `set` carry sequence number `seq`?  (at_least: a LATER launch on the same result set has finished -- the
+// stream is in order -- will do as well: used where only "the device no longer reads that launch's input" matters)
+bool small_reached(adsb_ctx *c, uint32_t set, uint64_t seq, bool at_least)
 {
-    volatile uint64_t *w = small_seq_word(c, set);
-    auto done = [&]() { const uint64_t v = __atomic_load_n(w, __ATOMIC_ACQUIRE); return at_least ? v >= seq : v == seq; };
-    for (uint32_t spins = 0; !done(); ++spins) {
+    const uint64_t v = __atomic_load_n(small_seq_word(c, set), __ATOMIC_ACQUIRE);
+    return at_least ? v >= seq : v == seq;
+}
+
+// Waits (polling pinned memory, no HIP call on the usual path) until it does.
+int small_wait(adsb_ctx *c, uint32_t set, uint64_t seq, bool at_least)
+{
+    for (uint32_t spins = 0; !small_reached(c, set, seq, at_least); ++spins) {
         if (spins > (1u << 22)) { // ~ tens of milliseconds of polling: let the runtime tell what happened
             HIPCHK(hipSetDevice(c->cfg.device));
             HIPCHK(hipStreamSynchronize(c->stream));
-            if (!done()) return ADSB_E_STATE;
+            if (!small_reached(c, set, seq, at_least)) return ADSB_E_STATE;
             break;
         }
 #if defined(__x86_64__)
@@ -533,23 +509,20 @@ static int small_wait(adsb_ctx *c, uint32_t set, uint64_t seq, bool at_least = f
 // Completes the list of result set `set` (a small launch that small_wait has seen complete) if tiles of it lost their
 // slots: the re-run scans the launch's samples (li.iq) AGAIN, so they must still be where the launch read them.  Leaves
 // the newest launch the one in view.
-static int small_complete(adsb_ctx *c, uint32_t set)
+int small_complete(adsb_ctx *c, uint32_t set)
 {
     const uint64_t *hdr = reinterpret_cast<const uint64_t *>(c->sm.blob[set]);
     if (!(hdr[2] & ADSB_FLAG_INCOMPLETE)) return ADSB_OK;
     // slot-pool overflow (pathological input): the standard re-run path completes the blob in place
-    const uint32_t newest = c->last;
-    view_launch(c, set);
-    int rc = sync_header(c);
-    view_launch(c, newest);
+    const int rc = with_launch_in_view(c, set, [&] { return sync_header(c); });
     if (rc != ADSB_OK) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     return ADSB_OK;
 }
 
 // Hands the finished list of result set `set` (a small launch that small_wait has seen complete) to the caller.
-static int small_collect(adsb_ctx *c, uint32_t set, adsb_frame *out, size_t max_out, size_t *n_out, uint64_t *total_found,
-                         uint32_t *flags)
+int small_collect(adsb_ctx *c, uint32_t set, adsb_frame *out, size_t max_out, size_t *n_out, uint64_t *total_found,
+                  uint32_t *flags)
 {
     const uint64_t *hdr = reinterpret_cast<const uint64_t *>(c->sm.blob[set]);
     int rc = small_complete(c, set);
@@ -571,7 +544,7 @@ static int rerun_in_batches(adsb_ctx *c, adsb_ctx::ResultSet &r)
 {
     HIPCHK(hipStreamSynchronize(c->aux));
     HIPCHK(hipStreamSynchronize(c->stream));
-    const uint32_t n = c->last_tiles;
+    const uint32_t n = r.li.tiles;
     std::vector<adsbk::Seg> seg(n);
     HIPCHK(hipMemcpyAsync(seg.data(), r.seg, sizeof(adsbk::Seg) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -583,7 +556,7 @@ static int rerun_in_batches(adsb_ctx *c, adsb_ctx::ResultSet &r)
     }
     HIPCHK(hipMemcpyAsync(c->out_start, start.data(), sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, c->stream));
     uint32_t limit = 0;
-    while (limit < n && start[limit] < c->last_cap) ++limit;
+    while (limit < n && start[limit] < r.li.cap) ++limit;
     uint32_t t0 = 0;
     int rc = ADSB_OK;
     while (t0 < limit && rc == ADSB_OK) {
@@ -596,7 +569,7 @@ static int rerun_in_batches(adsb_ctx *c, adsb_ctx::ResultSet &r)
         if ((e = hipMemsetAsync(&r.hdr->alloc, 0, sizeof(unsigned long long), c->stream)) != hipSuccess ||
             (e = adsbk::launch_demod(c->stream, c->cfg.sample_type, c->mag_mode, c->scan,
                                      demod_args(c, r, t0, t1 - t0, false))) != hipSuccess ||
-            (e = adsbk::launch_finish(c->stream, finish_args(c, r, r.li.idx, t0, t1 - t0, true))) != hipSuccess)
+            (e = adsbk::launch_finish(c->stream, finish_args(c, r, t0, t1 - t0, true))) != hipSuccess)
             rc = (int)e;
         t0 = t1;
     }
@@ -606,8 +579,8 @@ static int rerun_in_batches(adsb_ctx *c, adsb_ctx::ResultSet &r)
         c->hdr_host->flags &= ~ADSB_FLAG_INCOMPLETE;
         const uint64_t pub_flags = c->hdr_host->flags;
         HIPCHK(hipMemcpyAsync(&r.hdr->flags, &c->hdr_host->flags, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        if (c->last_out != r.out) // the launch wrote into a caller-owned blob: [n_out | total | flags | 0 | frames]
-            HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(c->last_out) - 16, &pub_flags, sizeof(uint64_t), hipMemcpyDefault, c->stream)); // (the blob may be pinned host memory: the small-buffer path)
+        if (r.li.hdr_pub) // the launch wrote into a blob: [n_out | total | flags | 0 | frames]
+            HIPCHK(hipMemcpyAsync(r.li.hdr_pub + 2, &pub_flags, sizeof(uint64_t), hipMemcpyDefault, c->stream)); // (the blob may be pinned host memory: the small-buffer path)
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     return rc;
@@ -625,10 +598,7 @@ int sync_header(adsb_ctx *c)
         int rc = rerun_in_batches(c, r);
         if (rc != ADSB_OK) return rc;
         c->hdr_host->retry = 0;
-        c->fields_current = false; // the list was rebuilt: decoded fields / levels / tracker output are stale
-        c->levels_current = false;
-        c->wire_current = false;
-        c->trk_done = false;
+        c->mark_derived_stale(); // the list was rebuilt
     }
     return ADSB_OK;
 }
@@ -654,15 +624,15 @@ extern "C" int adsb_fetch(adsb_ctx *c, adsb_frame *out, size_t max_out, size_t *
     uint32_t fl = c->hdr_host->flags;
     if (n > max_out) { n = max_out; fl |= ADSB_FLAG_TRUNCATED; }
     adsb_ctx::ResultSet &r = c->rs[c->last];
-    if (n) HIPCHK(hipMemcpyAsync(out, c->last_out, sizeof(adsb_frame) * n, hipMemcpyDefault, c->aux)); // (device memory, or the small-buffer path's pinned blob)
+    if (n) HIPCHK(hipMemcpyAsync(out, c->launch().out, sizeof(adsb_frame) * n, hipMemcpyDefault, c->aux)); // (device memory, or the small-buffer path's pinned blob)
     std::vector<uint64_t> pre;
     if (per_channel_counts) {
-        pre.resize((size_t)c->last_channels + 1);
+        pre.resize((size_t)c->launch().channels + 1);
         HIPCHK(hipMemcpyAsync(pre.data(), r.chan_prefix, sizeof(uint64_t) * pre.size(), hipMemcpyDeviceToHost, c->aux));
     }
     HIPCHK(hipStreamSynchronize(c->aux));
     if (per_channel_counts) { // frames of channel k in `out` = its share of the first n frames of the list
-        for (uint32_t k = 0; k < c->last_channels; ++k)
+        for (uint32_t k = 0; k < c->launch().channels; ++k)
             per_channel_counts[k] = std::min<uint64_t>(pre[k + 1], n) - std::min<uint64_t>(pre[k], n);
     }
     *n_out = (size_t)n;
@@ -674,7 +644,7 @@ extern "C" int adsb_fetch(adsb_ctx *c, adsb_frame *out, size_t max_out, size_t *
 extern "C" int adsb_result_device(adsb_ctx *c, const adsb_frame **frames_dev, const void **header_dev)
 {
     if (!c) return ADSB_E_ARG;
-    if (frames_dev) *frames_dev = c->last_out ? c->last_out : c->rs[c->last].out;
+    if (frames_dev) *frames_dev = c->launch().out ? c->launch().out : c->rs[c->last].out;
     if (header_dev) *header_dev = c->rs[c->last].hdr;
     return ADSB_OK;
 }
@@ -687,7 +657,7 @@ extern "C" int adsb_decode_fields_device_async(adsb_ctx *c)
     if (!c->fields && hipMalloc((void **)&c->fields, sizeof(adsb_packet_fields) * (size_t)c->cfg.max_out) != hipSuccess)
         return ADSB_E_NOMEM;
     // same stream as the ordering pass, so it sees the finished list and header
-    HIPCHK(adsbk::launch_decode_fields(c->aux, c->last_out, c->rs[c->last].hdr, c->last_cap, c->fields));
+    HIPCHK(adsbk::launch_decode_fields(c->aux, c->launch().out, c->rs[c->last].hdr, c->launch().cap, c->fields));
     c->fields_current = true;
     return ADSB_OK;
 }
@@ -705,7 +675,7 @@ extern "C" int adsb_fetch_fields(adsb_ctx *c, adsb_packet_fields *out, size_t ma
     if (!c->fields) return ADSB_E_STATE;
     int rc = sync_header(c);
     if (rc != ADSB_OK) return rc;
-    uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
+    uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->launch().cap);
     if (n > max_out) n = max_out;
     if (n) HIPCHK(hipMemcpyAsync(out, c->fields, sizeof(adsb_packet_fields) * n, hipMemcpyDeviceToHost, c->aux));
     HIPCHK(hipStreamSynchronize(c->aux));
@@ -843,121 +813,6 @@ extern "C" int adsb_time_read_ceiling(adsb_ctx *c, const void *buf_dev, size_t b
     return ADSB_OK;
 }
 
-// ---- measurement: the host-fed (PCIe-inclusive) rate of the streaming front end ---------------------------------------------
-// What the reference's thread 1 -> thread 2 hand-over costs per buffer through adsb_feed_* (src/adsb.rs:75-89: playback
-// sends 20 000-sample buffers; adsb.rs:59-64: MTU-sized reads), measured from C (no interpreter in the loop): a context
-// and a feed of its own on `device`, synthetic samples written into the pinned ring by an in-place producer (acquire /
-// push), two buffers in flight, every list popped; runs for about `seconds`.  bench.py reports it next to `value`
-// (which is the HBM-resident rate and never includes PCIe).
-extern "C" int adsb_measure_feed(int device, int sample_type, size_t chunk, double seconds, double *us_per_buffer,
-                                 double *frames_per_buffer, uint64_t *buffers)
-{
-    if (!us_per_buffer || chunk < (size_t)kWindow || seconds <= 0 || (sample_type != ADSB_SAMPLE_I8 && sample_type != ADSB_SAMPLE_I16))
-        return ADSB_E_ARG;
-    const size_t bps = sample_type == ADSB_SAMPLE_I8 ? 2 : 4;
-    adsb_synth_cfg sc;
-    adsb_synth_default(&sc);
-    sc.seed = 9;
-    if (sample_type == ADSB_SAMPLE_I16) sc.amp_shift = 5;
-    const int n_src = chunk <= (1u << 20) ? 8 : 2;
-    std::vector<char> data(chunk * bps * n_src);
-    int rc = adsb_synth_fill_host(&sc, sample_type, 0, 0, chunk * n_src, data.data());
-    if (rc != ADSB_OK) return rc;
-    adsb_cfg cfg{};
-    cfg.abi_version = ADSB_ABI_VERSION;
-    cfg.device = device;
-    cfg.sample_type = sample_type;
-    cfg.max_channels = 1;
-    cfg.max_samples = chunk + kWindow;
-    cfg.max_out = chunk / 200 + 4096;
-    adsb_ctx *ctx = nullptr;
-    if ((rc = adsb_create(&cfg, &ctx)) != ADSB_OK) return rc;
-    adsb_feed_cfg fc{};
-    fc.max_chunk = chunk;
-    fc.carry = 0;
-    fc.ring_slots = 3;
-    adsb_feed *feed = nullptr;
-    if ((rc = adsb_feed_open(ctx, &fc, &feed)) != ADSB_OK) { adsb_destroy(ctx); return rc; }
-    std::vector<adsb_frame> frames(cfg.max_out);
-    uint64_t total = 0, n_buf = 0;
-    auto one = [&](uint64_t k, bool fill) {
-        void *slot = nullptr;
-        int r = adsb_feed_acquire(feed, &slot);
-        // (a real producer -- SDR driver, file reader -- writes its samples straight into the slot: that is its cost, not
-        // the hand-over's; the slots are filled during the warm-up rounds)
-        if (r == ADSB_OK && fill) std::memcpy(slot, data.data() + (size_t)(k % n_src) * chunk * bps, chunk * bps);
-        if (r == ADSB_OK) r = adsb_feed_push(feed, nullptr, chunk);
-        if (r == ADSB_OK && adsb_feed_in_flight(feed) == 2) {
-            size_t n = 0;
-            r = adsb_feed_pop(feed, frames.data(), frames.size(), &n, nullptr, nullptr);
-            total += n;
-        }
-        return r;
-    };
-    auto drain = [&]() {
-        int r = ADSB_OK;
-        while (r == ADSB_OK && adsb_feed_in_flight(feed) > 0) {
-            size_t n = 0;
-            r = adsb_feed_pop(feed, frames.data(), frames.size(), &n, nullptr, nullptr);
-            total += n;
-        }
-        return r;
-    };
-    for (uint64_t k = 0; k < 6 && rc == ADSB_OK; ++k) rc = one(k, true);
-    if (rc == ADSB_OK) rc = drain();
-    total = 0;
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    double dt = 0;
-    while (rc == ADSB_OK) {
-        for (int k = 0; k < 16 && rc == ADSB_OK; ++k, ++n_buf) rc = one(n_buf + 6, false);
-        dt = std::chrono::duration<double>(clk::now() - t0).count();
-        if (dt >= seconds) break;
-    }
-    if (rc == ADSB_OK) rc = drain();
-    dt = std::chrono::duration<double>(clk::now() - t0).count();
-    adsb_feed_close(feed);
-    adsb_destroy(ctx);
-    if (rc != ADSB_OK) return rc;
-    *us_per_buffer = n_buf ? dt * 1e6 / (double)n_buf : 0.0;
-    if (frames_per_buffer) *frames_per_buffer = n_buf ? (double)total / (double)n_buf : 0.0;
-    if (buffers) *buffers = n_buf;
-    return ADSB_OK;
-}
-
-// The box's pinned host -> device copy rate (one stream, `bytes` per copy): the ceiling of any host-fed path.
-extern "C" int adsb_measure_pinned_copy(int device, size_t bytes, int iters, double *gbytes_per_s)
-{
-    if (!gbytes_per_s || bytes == 0 || iters <= 0) return ADSB_E_ARG;
-    HIPCHK(hipSetDevice(device));
-    void *h = nullptr, *d = nullptr;
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    hipError_t e = hipHostMalloc(&h, bytes, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc(&d, bytes);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    float ms = 0;
-    if (e == hipSuccess) {
-        std::memset(h, 1, bytes);
-        e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s); // warm-up
-        if (e == hipSuccess) e = hipEventRecord(e0, s);
-        for (int k = 0; k < iters && e == hipSuccess; ++k) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipEventRecord(e1, s);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (s) (void)hipStreamDestroy(s);
-    (void)hipFree(d);
-    if (h) (void)hipHostFree(h);
-    if (e != hipSuccess) return (int)e;
-    *gbytes_per_s = ms > 0 ? (double)bytes * iters / (ms * 1e-3) / 1e9 : 0.0;
-    return ADSB_OK;
-}
-
 extern "C" int adsb_debug_magnitudes(adsb_ctx *c, const void *iq_host, size_t n, uint16_t *mags_host)
 {
     if (!c || !iq_host || !mags_host) return ADSB_E_ARG;
@@ -1075,313 +930,5 @@ extern "C" int adsb_synth_fill_device(adsb_ctx *c, const adsb_synth_cfg *cfg, ui
     if (!c || !synth_ok(cfg) || (!iq_dev && n)) return ADSB_E_ARG;
     HIPCHK(hipSetDevice(c->cfg.device));
     HIPCHK(adsbk::launch_synth(c->stream, *cfg, c->cfg.sample_type, channel, first, n, iq_dev));
-    return ADSB_OK;
-}
-
-// ---- streaming front end (reference: the Vec-per-recv loop of src/adsb.rs:95-98 and its feeders,
-// adsb.rs:54-89) --------------------------------------------------------------------------------------------
-// Buffers arrive on the host one after the other.  Each is copied into a slot of a PINNED host ring (or was
-// written there by the producer: adsb_feed_acquire), goes to one of two device staging slots by asynchronous DMA
-// on a copy stream, and is demodulated on the ctx stream -- so the copy of buffer k+1 overlaps the kernels of
-// buffer k, and the host only blocks in adsb_feed_pop() for results that are not ready yet.  Two buffers may be
-// in flight (the ctx alternates between two result sets).
-//   parity mode (carry = 0, the reference's behaviour): every buffer is its own reference buffer; the last 240
-//     offsets of each are never looked at (adsb.rs:98); offsets are buffer-relative.
-//   carry mode (carry = 1): the last 240 samples of the stream so far are kept ON THE DEVICE and copied, device
-//     to device, in front of the next buffer before it is demodulated: the chunked stream decodes exactly like one
-//     long buffer (frames straddling two buffers are found); offsets are absolute stream positions.
-// Staging slot layout (samples): [ head: up to 240 carried samples | the buffer ], the buffer's copy lands behind
-// the carried samples and the demodulated region starts at a multiple of 8 samples (16-byte alignment).
-struct adsb_feed {
-    adsb_ctx *c = nullptr;
-    adsb_feed_cfg cfg{};
-    uint32_t bps = 2;
-    hipStream_t copy = nullptr;
-    char *dev[2] = {nullptr, nullptr};
-    hipEvent_t h2d_done[2] = {nullptr, nullptr}, kern_done[2] = {nullptr, nullptr};
-    // results of the launch from staging slot k are complete and visible to the copy engine (a default event: its
-    // record releases to system scope, unlike the ctx's device-scope events)
-    bool kern_pending[2] = {false, false};
-    std::vector<char *> ring;
-    std::vector<hipEvent_t> ring_done; // H2D out of that ring slot has completed
-    std::vector<char> ring_busy;
-    // a one-dispatch launch reads its samples straight from the ring slot: the slot may be overwritten once the launch's
-    // sequence word says so (ring_seq != 0: result set ring_set carries that number when the kernel has finished) AND, if
-    // its buffer is still unpopped, its list is complete -- a re-run after a slot-pool overflow reads the slot again
-    std::vector<uint64_t> ring_seq;
-    std::vector<uint32_t> ring_set;
-    uint32_t ring_next = 0;
-    int acquired = -1;
-    uint64_t pushed = 0, popped = 0; // buffers
-    uint64_t consumed = 0;           // samples pushed so far
-    size_t prev_start = 0, prev_len = 0; // demodulated region of the previous buffer's slot (samples)
-    struct Entry {
-        bool launched = false;
-        bool small = false;        // went through the one-dispatch path: results in the ctx's pinned blob `set`
-        uint64_t seq = 0;          // ... complete when its sequence word carries this
-        uint32_t set = 0;
-        uint64_t first_sample = 0; // stream position of the buffer's first own sample
-    } q[2];
-    adsbk::Header *hdr_host = nullptr;
-    size_t headroom = 0;           // samples in front of every ring slot's data (carry mode: room for the 240-sample tail)
-    const char *prev_host = nullptr; // where the previous buffer's demodulated region starts in HOST memory (nullptr: it
-                                     // only exists in a device staging slot)
-    uint32_t prev_ring = 0;          // ... and the ring slot that holds it
-};
-
-extern "C" void adsb_feed_close(adsb_feed *f)
-{
-    if (!f) return;
-    if (f->c) (void)hipSetDevice(f->c->cfg.device);
-    if (f->copy) (void)hipStreamSynchronize(f->copy);
-    if (f->c && f->c->stream) (void)hipStreamSynchronize(f->c->stream);
-    for (int k = 0; k < 2; ++k) {
-        (void)hipFree(f->dev[k]);
-        if (f->h2d_done[k]) (void)hipEventDestroy(f->h2d_done[k]);
-        if (f->kern_done[k]) (void)hipEventDestroy(f->kern_done[k]);
-    }
-    for (char *p : f->ring) (void)hipHostFree(p);
-    for (hipEvent_t e : f->ring_done) if (e) (void)hipEventDestroy(e);
-    if (f->hdr_host) (void)hipHostFree(f->hdr_host);
-    if (f->copy) (void)hipStreamDestroy(f->copy);
-    if (f->c) { (void)adsb_set_stream_base(f->c, 0); }
-    delete f;
-}
-
-extern "C" int adsb_feed_open(adsb_ctx *c, const adsb_feed_cfg *cfg, adsb_feed **out)
-{
-    if (!c || !cfg || !out || cfg->max_chunk == 0) return ADSB_E_ARG;
-    *out = nullptr;
-    // one launch covers the buffer, in carry mode with the 240 carried samples in front of it
-    if (cfg->max_chunk + (cfg->carry ? (size_t)kWindow : 0) > c->cfg.max_samples) return ADSB_E_CAPACITY;
-    if (c->cfg.max_channels < 1) return ADSB_E_ARG;
-    // two launches are in flight: they must not share one caller-owned result blob
-    if (c->ext_blob) return ADSB_E_STATE;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    adsb_feed *f = new (std::nothrow) adsb_feed();
-    if (!f) return ADSB_E_NOMEM;
-    f->c = c;
-    f->cfg = *cfg;
-    if (f->cfg.ring_slots < 2) f->cfg.ring_slots = 3;
-    f->bps = c->bps;
-    bool ok = hipStreamCreateWithFlags(&f->copy, hipStreamNonBlocking) == hipSuccess;
-    f->headroom = kWindow; // (240 samples = 480 / 960 bytes: keeps the data 16-byte aligned)
-    const size_t slot_bytes = (cfg->max_chunk + (size_t)kWindow + 8) * f->bps;
-    for (int k = 0; k < 2 && ok; ++k)
-        ok = hipMalloc((void **)&f->dev[k], slot_bytes) == hipSuccess &&
-             hipEventCreateWithFlags(&f->h2d_done[k], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&f->kern_done[k], hipEventDisableTiming) == hipSuccess;
-    for (uint32_t k = 0; k < f->cfg.ring_slots && ok; ++k) {
-        char *p = nullptr;
-        hipEvent_t e = nullptr;
-        ok = hipHostMalloc((void **)&p, (cfg->max_chunk + f->headroom) * f->bps, hipHostMallocDefault) == hipSuccess &&
-             hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-        if (p) f->ring.push_back(p);
-        if (e) f->ring_done.push_back(e);
-        f->ring_busy.push_back(0);
-        f->ring_seq.push_back(0);
-        f->ring_set.push_back(0);
-    }
-    ok = ok && hipHostMalloc((void **)&f->hdr_host, sizeof(adsbk::Header), hipHostMallocDefault) == hipSuccess;
-    if (!ok) { adsb_feed_close(f); return ADSB_E_NOMEM; }
-    *out = f;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_feed_in_flight(const adsb_feed *f) { return f ? (int)(f->pushed - f->popped) : ADSB_E_ARG; }
-
-// 1: adsb_feed_pop() would not wait for the GPU (the oldest buffer's kernels have finished, or it launched none);
-// 0: it would; ADSB_E_STATE: nothing in flight.
-extern "C" int adsb_feed_ready(adsb_feed *f)
-{
-    if (!f) return ADSB_E_ARG;
-    if (f->popped == f->pushed) return ADSB_E_STATE;
-    const uint32_t s = (uint32_t)(f->popped & 1u);
-    if (!f->q[s].launched) return 1;
-    if (f->q[s].small) return __atomic_load_n(small_seq_word(f->c, f->q[s].set), __ATOMIC_ACQUIRE) == f->q[s].seq ? 1 : 0;
-    HIPCHK(hipSetDevice(f->c->cfg.device));
-    const hipError_t e = hipEventQuery(f->kern_done[s]);
-    if (e == hipSuccess) return 1;
-    if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
-    return (int)e;
-}
-
-static int feed_ring_slot(adsb_feed *f, uint32_t *slot)
-{
-    const uint32_t r = f->ring_next;
-    if (f->ring_busy[r]) { // the DMA out of this slot must have finished before the host overwrites it
-        HIPCHK(hipEventSynchronize(f->ring_done[r]));
-        f->ring_busy[r] = 0;
-    }
-    if (f->ring_seq[r]) { // ... and so must the one-dispatch kernel that reads its samples from the slot itself
-        const int rc = small_wait(f->c, f->ring_set[r], f->ring_seq[r], true);
-        if (rc != ADSB_OK) return rc;
-        // ... and, while that buffer has not been popped, so must its LIST: a launch whose tiles lost their slots is
-        // re-run from these samples (small_complete), which the pop would otherwise do after the producer has overwritten
-        // them.  (Unpopped means no later launch has used its result set: the sequence word is exactly this launch's.)
-        for (uint64_t k = f->popped; k < f->pushed; ++k) {
-            const adsb_feed::Entry &e = f->q[k & 1u];
-            if (!e.launched || !e.small || e.set != f->ring_set[r] || e.seq != f->ring_seq[r]) continue;
-            const int rc2 = small_complete(f->c, e.set);
-            if (rc2 != ADSB_OK) return rc2;
-        }
-        f->ring_seq[r] = 0;
-    }
-    *slot = r;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_feed_acquire(adsb_feed *f, void **host_slot)
-{
-    if (!f || !host_slot) return ADSB_E_ARG;
-    if (f->acquired >= 0) return ADSB_E_STATE;
-    HIPCHK(hipSetDevice(f->c->cfg.device));
-    uint32_t r = 0;
-    int rc = feed_ring_slot(f, &r);
-    if (rc != ADSB_OK) return rc;
-    f->acquired = (int)r;
-    *host_slot = f->ring[r] + f->headroom * f->bps;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_feed_push(adsb_feed *f, const void *iq_host, size_t n)
-{
-    if (!f || n == 0 || n > f->cfg.max_chunk) return ADSB_E_ARG;
-    if (!iq_host && f->acquired < 0) return ADSB_E_ARG;
-    if (f->pushed - f->popped >= 2) return ADSB_E_STATE; // two buffers in flight: pop first
-    // parity mode: the reference panics on a buffer shorter than 240 samples (adsb.rs:98); nothing is consumed
-    if (!f->cfg.carry && n < (size_t)kWindow) return ADSB_E_SHORT;
-    adsb_ctx *c = f->c;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    uint32_t r = 0;
-    char *data = nullptr; // the buffer's samples in the pinned ring
-    if (f->acquired >= 0) {
-        r = (uint32_t)f->acquired;
-        data = f->ring[r] + f->headroom * f->bps;
-        if (iq_host && iq_host != data) std::memcpy(data, iq_host, n * f->bps);
-        f->acquired = -1;
-    } else {
-        int rc = feed_ring_slot(f, &r);
-        if (rc != ADSB_OK) return rc;
-        data = f->ring[r] + f->headroom * f->bps;
-        std::memcpy(data, iq_host, n * f->bps);
-    }
-    f->ring_next = (r + 1) % (uint32_t)f->ring.size();
-
-    const uint32_t s = (uint32_t)(f->pushed & 1u);
-    const size_t tail = (f->cfg.carry && f->pushed) ? std::min<size_t>(kWindow, f->prev_len) : 0;
-    const size_t len = tail + n;
-    adsb_feed::Entry &e = f->q[s];
-    e.first_sample = f->consumed;
-    e.launched = false;
-    e.small = false;
-    const uint64_t base = f->cfg.carry ? f->consumed - tail : 0;
-
-    // ---- small buffers: one dispatch, samples read from the ring and frames written to pinned memory by the device ----
-    // (carry mode: the tail of the previous buffer is copied in front of this one on the host -- 480 or 960 bytes --
-    // which needs that buffer in host memory and a 16-byte aligned start, i.e. the usual 240-sample tail)
-    if (len >= (size_t)kWindow && small_fits(c, len) && (tail == 0 || (f->prev_host && (tail * f->bps) % 16 == 0))) {
-        char *start = data - tail * f->bps;
-        if (tail) std::memcpy(start, f->prev_host + (f->prev_len - tail) * f->bps, tail * f->bps);
-        int rc = adsb_set_stream_base(c, base);
-        if (rc == ADSB_OK) rc = small_launch(c, start, len, &e.seq);
-        if (rc != ADSB_OK) return rc;
-        e.launched = true;
-        e.small = true;
-        e.set = c->last;
-        f->ring_busy[r] = 0;
-        f->ring_seq[r] = e.seq; // the kernel reads the slot until its sequence word is out (feed_ring_slot waits for it)
-        f->ring_set[r] = e.set;
-        f->prev_host = start;
-        f->prev_ring = r;
-        f->prev_start = 0;
-        f->prev_len = len;
-        f->consumed += n;
-        f->pushed++;
-        return ADSB_OK;
-    }
-
-    const size_t start = ((size_t)kWindow - tail) / 8 * 8; // 16-byte aligned start of the demodulated region
-    // this staging slot was last read by the launch two buffers ago
-    if (f->kern_pending[s]) HIPCHK(hipStreamWaitEvent(f->copy, f->kern_done[s], 0));
-    HIPCHK(hipMemcpyAsync(f->dev[s] + (start + tail) * f->bps, data, n * f->bps, hipMemcpyHostToDevice, f->copy));
-    HIPCHK(hipEventRecord(f->ring_done[r], f->copy));
-    f->ring_busy[r] = 1;
-    if (tail) { // the last `tail` samples of what the previous launch saw
-        if (f->prev_host) { // ... which went through the one-dispatch path: they are in the ring (host memory)
-            HIPCHK(hipMemcpyAsync(f->dev[s] + start * f->bps, f->prev_host + (f->prev_len - tail) * f->bps, tail * f->bps,
-                                  hipMemcpyHostToDevice, f->copy));
-            HIPCHK(hipEventRecord(f->ring_done[f->prev_ring], f->copy)); // that slot is read once more: not reusable before
-            f->ring_busy[f->prev_ring] = 1;
-        } else // ... device to device (its H2D is earlier on this stream)
-            HIPCHK(hipMemcpyAsync(f->dev[s] + start * f->bps, f->dev[s ^ 1u] + (f->prev_start + f->prev_len - tail) * f->bps,
-                                  tail * f->bps, hipMemcpyDeviceToDevice, f->copy));
-    }
-    HIPCHK(hipEventRecord(f->h2d_done[s], f->copy));
-
-    if (len >= (size_t)kWindow) {
-        HIPCHK(hipStreamWaitEvent(c->stream, f->h2d_done[s], 0));
-        // after a pop of an older launch the ctx may "view" that launch: the next enqueue starts from the newest state
-        int rc = adsb_set_stream_base(c, base);
-        if (rc == ADSB_OK) rc = adsb_demod_device_async(c, f->dev[s] + start * f->bps, 1, len, len);
-        if (rc != ADSB_OK) return rc;
-        e.launched = true;
-        e.set = c->last;
-        HIPCHK(hipEventRecord(f->kern_done[s], c->aux)); // THIS launch's kernels and results (not the stream's tail)
-        f->kern_pending[s] = true;
-    }
-    f->prev_host = nullptr;
-    f->prev_start = start;
-    f->prev_len = len;
-    f->consumed += n;
-    f->pushed++;
-    return ADSB_OK;
-}
-
-extern "C" int adsb_feed_pop(adsb_feed *f, adsb_frame *out, size_t max_out, size_t *n_out, uint32_t *flags,
-                             uint64_t *first_sample)
-{
-    if (!f || !n_out || (!out && max_out)) return ADSB_E_ARG;
-    *n_out = 0;
-    if (flags) *flags = 0;
-    if (f->popped == f->pushed) return ADSB_E_STATE;
-    adsb_ctx *c = f->c;
-    HIPCHK(hipSetDevice(c->cfg.device));
-    adsb_feed::Entry &e = f->q[f->popped & 1u];
-    if (first_sample) *first_sample = e.first_sample;
-    f->popped++;
-    if (!e.launched) return ADSB_OK; // (carry mode, fewer than 240 samples so far: nothing decodable yet)
-    if (e.small) { // the device wrote header and frames into pinned memory: poll its sequence word, copy, done
-        int rc = small_wait(c, e.set, e.seq);
-        if (rc != ADSB_OK) return rc;
-        return small_collect(c, e.set, out, max_out, n_out, nullptr, flags);
-    }
-    adsb_ctx::ResultSet &r = c->rs[e.set];
-    // results travel on the copy stream, behind this launch's ordering pass only -- not behind the kernels of the
-    // buffer pushed after it, which share the ctx stream
-    HIPCHK(hipStreamWaitEvent(f->copy, f->kern_done[(f->popped - 1) & 1u], 0));
-    HIPCHK(hipMemcpyAsync(f->hdr_host, r.hdr, sizeof(adsbk::Header), hipMemcpyDeviceToHost, f->copy));
-    HIPCHK(hipStreamSynchronize(f->copy));
-    if (f->hdr_host->retry) { // slot-pool overflow (pathological input): the slow, fully synchronous path
-        const uint32_t newest = c->last;
-        view_launch(c, e.set);
-        size_t got = 0;
-        uint32_t fl = 0;
-        int rc = adsb_fetch(c, out, max_out, &got, nullptr, nullptr, &fl);
-        view_launch(c, newest);
-        if (rc != ADSB_OK) return rc;
-        *n_out = got;
-        if (flags) *flags = fl;
-        return ADSB_OK;
-    }
-    uint64_t n = f->hdr_host->n_out;
-    uint32_t fl = f->hdr_host->flags;
-    if (n > max_out) { n = max_out; fl |= ADSB_FLAG_TRUNCATED; }
-    if (n) {
-        HIPCHK(hipMemcpyAsync(out, r.li.out, sizeof(adsb_frame) * n, hipMemcpyDeviceToHost, f->copy));
-        HIPCHK(hipStreamSynchronize(f->copy));
-    }
-    *n_out = (size_t)n;
-    if (flags) *flags = fl;
     return ADSB_OK;
 }

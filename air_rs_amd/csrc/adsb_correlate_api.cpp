@@ -103,10 +103,10 @@ extern "C" int adsb_correlate_launch(adsb_ctx *c, const adsb_correlate_cfg *cfg,
 {
     if (!c || !cfg) return ADSB_E_ARG;
     if (!c->launched) return ADSB_E_STATE;
-    if (c->last_channels > adsbk::kCorrMaxReceivers) return ADSB_E_ARG;
+    if (c->launch().channels > adsbk::kCorrMaxReceivers) return ADSB_E_ARG;
     int rc = sync_header(c); // the list's length, as adsb_fetch_counts (and the rebuild after a slot-pool overflow)
     if (rc != ADSB_OK) return rc;
-    const uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
+    const uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->launch().cap);
     HIPCHK(hipSetDevice(c->cfg.device));
     // not enqueued yet for this launch, or of the list with holes that sync_header has just rebuilt: (again) now, on the
     // stream the correlate kernels follow on
@@ -114,14 +114,14 @@ extern "C" int adsb_correlate_launch(adsb_ctx *c, const adsb_correlate_cfg *cfg,
     if (with_levels && n && !(c->levels && c->levels_current) && (rc = adsb_levels_device_async(c)) != ADSB_OK) return rc;
     adsb_ctx::ResultSet &r = c->rs[c->last];
     // the channel split as adsb_fetch's per_channel_counts reads it: chan_prefix clipped to the list
-    std::vector<uint64_t> prefix((size_t)c->last_channels + 1);
+    std::vector<uint64_t> prefix((size_t)c->launch().channels + 1);
     HIPCHK(hipMemcpyAsync(prefix.data(), r.chan_prefix, sizeof(uint64_t) * prefix.size(), hipMemcpyDeviceToHost, c->aux));
     HIPCHK(hipStreamSynchronize(c->aux));
     for (uint64_t &p : prefix) p = std::min<uint64_t>(p, n);
     prefix[0] = 0;
-    prefix[c->last_channels] = n;
-    if ((rc = corr_run(c, *cfg, c->last_out, with_levels && n ? c->levels : nullptr, (size_t)n, prefix.data(),
-                       c->last_channels, sample_base, (size_t)c->cfg.max_out)) != ADSB_OK)
+    prefix[c->launch().channels] = n;
+    if ((rc = corr_run(c, *cfg, c->launch().out, with_levels && n ? c->levels : nullptr, (size_t)n, prefix.data(),
+                       c->launch().channels, sample_base, (size_t)c->cfg.max_out)) != ADSB_OK)
         return rc;
     if (c->own_aux) { // the launch that reuses this result set waits for these kernels too
         HIPCHK(hipEventRecord(r.g_done, c->aux));

@@ -1,6 +1,7 @@
 // adsb_ctx.h -- what the files of the C boundary share: the context (adsb_api.cpp creates and destroys it; each feature's
-// adsb_*_api.cpp reads the last launch and keeps its own scratch in it), the error macro, and the one function the others
-// need from adsb_api.cpp.  The rule the scratch is grown by is adsb_scratch.h.  Internal.
+// adsb_*_api.cpp reads the launch in view, launch(), and keeps its own scratch in it), the error macro, and what the others
+// need from adsb_api.cpp: sync_header, and for the streaming feed (adsb_feed_api.cpp) the one-dispatch path and the view
+// of an older launch.  The rule the scratch is grown by is adsb_scratch.h.  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,13 +35,15 @@ struct adsb_ctx {
         uint64_t *chan_prefix = nullptr; // [max_channels + 1]: frames before each channel's first tile; last = total
         hipEvent_t k_done = nullptr, g_done = nullptr;
         bool g_pending = false;
-        // the launch whose results this set holds (the streaming front end fetches the older of two launches
-        // in flight: view_launch() makes it the one the fetch / re-plan code below works on)
+        // the launch whose results this set holds: the one record of it.  adsb_ctx::launch() is the one in view, which
+        // every fetch / re-run / levels / wire / correlate / tracker call works on (the streaming front end fetches the
+        // older of two launches in flight: with_launch_in_view())
         struct Launch {
             const void *iq = nullptr;
             uint32_t channels = 0, tpc = 0, tiles = 0, cap = 0, idx = 0;
-            uint64_t samples = 0, stride = 0, base = 0;
-            adsb_frame *out = nullptr;
+            uint64_t samples = 0, stride = 0, base = 0; // base: stream_base at the launch (re-runs of its tiles use the same)
+            adsb_frame *out = nullptr;    // where the ordered list goes, [cap]
+            uint64_t *hdr_pub = nullptr;  // the public 32-byte header `out` follows (ext_blob, the one-dispatch path's blob), or null
             bool valid = false;
         } li;
     } rs[2];
@@ -134,13 +137,10 @@ struct adsb_ctx {
     bool trk_done = false;
     void *ext_blob = nullptr;       // caller-owned [32-byte header | frames] target for the next launches
     size_t ext_frames = 0;          // frame capacity of ext_blob
-    adsb_frame *last_out = nullptr; // where the last launch's ordered list went
-    uint32_t last_cap = 0;
     bool fused_pass_only = false;   // adsb_debug_fused_pass_only (measurement)
     uint64_t stream_base = 0;       // adsb_set_stream_base: added to the offsets of the following launches
-    uint64_t last_base = 0;         // ... of the last launch (re-runs of its tiles use the same)
     uint32_t launch_idx = 0;        // launches so far
-    uint32_t last = 0;              // result set of the last launch
+    uint32_t last = 0;              // result set of the launch in view: the last one, but for with_launch_in_view()
     uint32_t *out_start = nullptr;  // [n_tiles_max + 1]  (slot-overflow re-run path only)
     uint64_t *lb = nullptr;         // finish_order's exchange words: one per workgroup, then one per 64 workgroups
     uint32_t lb_groups_at = 0;
@@ -167,19 +167,31 @@ struct adsb_ctx {
     // pinned host mirrors
     adsbk::Header *hdr_host = nullptr;
 
-    // last launch
-    bool launched = false;
-    const void *last_iq = nullptr;
-    uint32_t last_channels = 0;
-    uint64_t last_samples = 0, last_stride = 0;
-    uint32_t last_tpc = 0, last_tiles = 0;
+    bool launched = false;          // a launch has been recorded: launch() describes one
 
     // timing
     int timing = 0;                 // 0 off; N: events on every N-th launch
     hipEvent_t ev[kTimingRing][4] = {}; // scan kernel, finishing kernel: start/end each
     bool ev_made = false;
     uint32_t ev_count = 0;
+
+    const ResultSet::Launch &launch() const { return rs[last].li; }
+    // what was derived from the list in view (decoded fields, levels, wire stream, tracker output) no longer belongs to it
+    void mark_derived_stale() { fields_current = levels_current = wire_current = trk_done = false; }
+    // Makes result set `set` the one in view.  Only the streaming front end looks at anything but the newest launch.
+    void view_launch(uint32_t set) { last = set; mark_derived_stale(); }
 };
+
+// fn() with result set `set` in view, then the newest launch again (the next enqueue starts from the newest state)
+template <class F>
+int with_launch_in_view(adsb_ctx *c, uint32_t set, F fn)
+{
+    const uint32_t newest = c->last;
+    c->view_launch(set);
+    const int rc = fn();
+    c->view_launch(newest);
+    return rc;
+}
 
 #define HIPCHK(x)                                  \
     do {                                           \
@@ -187,5 +199,16 @@ struct adsb_ctx {
         if (e_ != hipSuccess) return (int)e_;      \
     } while (0)
 
-// Waits for the last launch's header in c->hdr_host (and rebuilds the list after a slot-pool overflow): adsb_api.cpp
-__attribute__((visibility("hidden"))) int sync_header(adsb_ctx *c);
+#pragma GCC visibility push(hidden)
+// Waits for the header of the launch in view in c->hdr_host (and rebuilds the list after a slot-pool overflow): adsb_api.cpp
+int sync_header(adsb_ctx *c);
+// The one-dispatch path for small buffers (adsb_api.cpp), as the streaming feed uses it: can a buffer take it; enqueue it;
+// has result set `set`'s sequence word reached `seq`, and wait for that; complete a list whose tiles lost their slots; hand it out
+bool small_fits(adsb_ctx *c, size_t n_samples);
+int small_launch(adsb_ctx *c, const void *iq, size_t n_samples, uint64_t *seq_out);
+bool small_reached(adsb_ctx *c, uint32_t set, uint64_t seq, bool at_least = false);
+int small_wait(adsb_ctx *c, uint32_t set, uint64_t seq, bool at_least = false);
+int small_complete(adsb_ctx *c, uint32_t set);
+int small_collect(adsb_ctx *c, uint32_t set, adsb_frame *out, size_t max_out, size_t *n_out, uint64_t *total_found,
+                  uint32_t *flags);
+#pragma GCC visibility pop

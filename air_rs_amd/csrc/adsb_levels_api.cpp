@@ -34,14 +34,15 @@ extern "C" int adsb_levels_device_async(adsb_ctx *c)
         c->levels = b.p;
     }
     adsbk::LevelsArgs a{};
-    a.iq = c->last_iq;
-    a.n_samples = c->last_samples;
-    a.channel_stride = c->last_stride;
-    a.offset_base = c->last_base;
-    a.frames = c->last_out;
+    const adsb_ctx::ResultSet::Launch &li = c->launch();
+    a.iq = li.iq;
+    a.n_samples = li.samples;
+    a.channel_stride = li.stride;
+    a.offset_base = li.base;
+    a.frames = li.out;
     a.hdr = c->rs[c->last].hdr;
-    a.cap = c->last_cap;
-    a.n_channels = c->last_channels;
+    a.cap = li.cap;
+    a.n_channels = li.channels;
     a.chan_prefix = c->rs[c->last].chan_prefix;
     a.out = c->levels;
     // same stream as the ordering pass, so it sees the finished list and header
@@ -66,7 +67,7 @@ extern "C" int adsb_fetch_levels(adsb_ctx *c, adsb_frame_level *out, size_t max_
     // the wait found holes in the list and rebuilt it (slot-pool overflow): the levels enqueued before are of the list
     // with holes.  Again, for the rebuilt one (the host has waited for the rebuild).
     if (!c->levels_current && (rc = adsb_levels_device_async(c)) != ADSB_OK) return rc;
-    uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
+    uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->launch().cap);
     if (n > max_out) n = max_out;
     if (n) HIPCHK(hipMemcpyAsync(out, c->levels, sizeof(adsb_frame_level) * n, hipMemcpyDeviceToHost, c->aux));
     HIPCHK(hipStreamSynchronize(c->aux));

@@ -43,7 +43,7 @@ extern "C" int adsb_track_device(adsb_ctx *c, double seconds_per_sample)
 {
     if (!c || !(seconds_per_sample > 0.0)) return ADSB_E_ARG;
     if (!c->launched) return ADSB_E_STATE;
-    if (c->last_channels != 1) return ADSB_E_ARG;
+    if (c->launch().channels != 1) return ADSB_E_ARG;
     int rc = sync_header(c); // the list's length (and the rebuild after a slot-pool overflow)
     if (rc != ADSB_OK) return rc;
     if (!c->fields_current && (rc = adsb_decode_fields_device_async(c)) != ADSB_OK) return rc;
@@ -60,8 +60,8 @@ extern "C" int adsb_track_device(adsb_ctx *c, double seconds_per_sample)
         });
         if (rc != ADSB_OK) return rc;
     }
-    const uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
-    adsbk::TrackArgs a = track_args(TrackKind::kLaunch, c->last_out, c->fields, n, seconds_per_sample, c->trk_u32, cap,
+    const uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->launch().cap);
+    adsbk::TrackArgs a = track_args(TrackKind::kLaunch, c->launch().out, c->fields, n, seconds_per_sample, c->trk_u32, cap,
                                     c->trk_temp, c->trk_temp_bytes, c->trk_points);
     a.aircraft = c->trk_aircraft;
     a.max_aircraft = (uint32_t)cap;
@@ -996,10 +996,10 @@ static int track_bank_update_launch(adsb_track_bank *b, const uint64_t *sample_b
 {
     adsb_ctx *c = b->ctx;
     if (!c->launched) return ADSB_E_STATE;
-    if (c->last_channels > b->n_receivers) return ADSB_E_ARG;
+    if (c->launch().channels > b->n_receivers) return ADSB_E_ARG;
     int rc = sync_header(c); // the list's length, as adsb_fetch_counts (and the rebuild after a slot-pool overflow)
     if (rc != ADSB_OK) return rc;
-    const uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->last_cap);
+    const uint64_t n = std::min<uint64_t>(c->hdr_host->n_out, c->launch().cap);
     if (n > b->max_frames) return ADSB_E_CAPACITY;
     HIPCHK(hipSetDevice(c->cfg.device));
     // not enqueued yet for this launch, or of the list with holes that sync_header has just rebuilt: (again) now, on
@@ -1009,7 +1009,7 @@ static int track_bank_update_launch(adsb_track_bank *b, const uint64_t *sample_b
     if ((rc = track_bank_stage(b, nullptr, sample_base, nullptr, 0)) != ADSB_OK) return rc;
     adsb_ctx::ResultSet &r = c->rs[c->last];
     // the channel split as adsb_fetch's per_channel_counts reads it: chan_prefix clipped to the list
-    if ((rc = track_bank_run(b, c->last_out, (size_t)n, r.chan_prefix, c->last_channels,
+    if ((rc = track_bank_run(b, c->launch().out, (size_t)n, r.chan_prefix, c->launch().channels,
                              with_levels ? c->levels : nullptr)) != ADSB_OK)
         return rc;
     if (c->own_aux) { // the launch that reuses this result set waits for these kernels too

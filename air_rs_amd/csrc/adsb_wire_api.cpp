@@ -54,10 +54,10 @@ extern "C" int adsb_wire_device_async(adsb_ctx *c, const adsb_wire_cfg *cfg)
     if (rc != ADSB_OK) return rc;
     if (wire_wants_levels(*cfg) && !c->levels_current && (rc = adsb_levels_device_async(c)) != ADSB_OK) return rc;
     adsbk::WireArgs a = wire_args(c, c->wire, *cfg);
-    a.frames = c->last_out;
+    a.frames = c->launch().out;
     a.levels = wire_wants_levels(*cfg) ? c->levels : nullptr;
     a.hdr = c->rs[c->last].hdr;
-    a.cap = c->last_cap;
+    a.cap = c->launch().cap;
     // same stream as the ordering pass (and the levels kernel), so it sees the finished list, header and levels
     HIPCHK(adsbk::launch_wire(c->aux, a));
     c->wire_cfg = *cfg;
