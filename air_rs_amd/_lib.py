@@ -511,6 +511,7 @@ PROTOTYPES = {
     "adsb_debug_set_launch_index": (C.c_int, [C.c_void_p, C.c_uint32]),
     "adsb_debug_finish_stall": (C.c_int, [C.c_void_p, C.c_uint32]),
     "adsb_debug_pool_limit": (C.c_int, [C.c_void_p, C.c_int]),
+    "adsb_debug_finish_geometry": (C.c_int, [_P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32), _P(C.c_uint32)]),
     "adsb_debug_tile_stamps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t)]),
     "adsb_synth_default": (None, [_P(AdsbSynthCfg)]),
     "adsb_synth_fill_host": (C.c_int, [_P(AdsbSynthCfg), C.c_int, C.c_uint32, C.c_uint64, C.c_size_t,

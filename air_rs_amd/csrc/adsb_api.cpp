@@ -263,6 +263,12 @@ extern "C" int adsb_debug_pool_limit(adsb_ctx *c, int on)
     return ADSB_OK;
 }
 
+extern "C" int adsb_debug_finish_geometry(uint32_t *tiles_per_workgroup, uint32_t *fan, uint32_t *flat, uint32_t *sums_per_round)
+{
+    adsbk::finish_geometry(tiles_per_workgroup, fan, flat, sums_per_round);
+    return ADSB_OK;
+}
+
 extern "C" int adsb_debug_tile_stamps(adsb_ctx *c, uint32_t *out, size_t max_tiles, size_t *n_tiles)
 {
     if (!c || !n_tiles || (!out && max_tiles)) return ADSB_E_ARG;

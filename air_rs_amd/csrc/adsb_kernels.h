@@ -153,6 +153,9 @@ hipError_t launch_demod(hipStream_t s, int sample_type, int mag_mode, int scan, 
 // second kernel of a launch (finish_order): CRC-24 + single-bit repair of the survivors the scan kernel sliced into
 // their slots, and the ordered frame list
 hipError_t launch_finish(hipStream_t s, const FinishArgs &a, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// finish_order's constants (adsb_debug_finish_geometry; each optional): tiles per workgroup, workgroups per second-level
+// sum, the largest grid that exchanges in one level, second-level sums a wave reads per round
+void finish_geometry(uint32_t *tiles_per_workgroup, uint32_t *fan, uint32_t *flat, uint32_t *sums_per_round);
 // the header of an empty list (no tiles, or a measurement launch without the finishing kernel)
 hipError_t launch_empty_result(hipStream_t s, Header *hdr, uint64_t *hdr_pub, uint64_t *chan_prefix, uint32_t n_channels,
                                hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);

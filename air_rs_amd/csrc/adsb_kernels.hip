@@ -1081,6 +1081,7 @@ constexpr int kFinTiles = 32;          // tiles per workgroup
 constexpr int kFinThreads = 256;
 constexpr int kFinFan = 64;            // workgroups per second-level sum
 constexpr int kFinFlat = 1024;         // up to this many workgroups exchange their aggregates in one level
+constexpr int kFinSumsPerRound = 64 * 8; // second-level sums a wave reads at a time: eight loads per lane
 constexpr uint32_t kLbReady = 1u;      // exchange word: value[31:0] | flag[33:32] | epoch[63:34]
 constexpr uint32_t kLbSpinLimit = 1u << 21; // polls (with s_sleep) before a lane gives up: ~0.1 s
 
@@ -1329,15 +1330,15 @@ __device__ __forceinline__ void finish_block(const FinishArgs &a, const uint32_t
                     bool e_ok = true;
                     if (!in_done && lane < r) vi = __hip_atomic_load(lb_a + (size_t)grp * kFinFan + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if (!e_done) {
-                        for (uint32_t k0 = 0; k0 < grp; k0 += 64u * 8u) { // (wave-uniform trip count; eight loads per lane at a time)
-                            unsigned long long v[8];
+                        for (uint32_t k0 = 0; k0 < grp; k0 += (uint32_t)kFinSumsPerRound) { // (wave-uniform trip count; eight loads per lane at a time)
+                            unsigned long long v[kFinSumsPerRound / 64];
 #pragma unroll
-                            for (int u = 0; u < 8; ++u) {
+                            for (int u = 0; u < kFinSumsPerRound / 64; ++u) {
                                 const uint32_t k = k0 + (uint32_t)u * 64u + lane;
                                 v[u] = k < grp ? __hip_atomic_load(lb_s + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : tag;
                             }
 #pragma unroll
-                            for (int u = 0; u < 8; ++u) {
+                            for (int u = 0; u < kFinSumsPerRound / 64; ++u) {
                                 e_ok = e_ok && (v[u] >> 32) == (tag >> 32);
                                 e_acc += v[u] & 0xFFFFFFFFull;
                             }
@@ -1436,6 +1437,14 @@ __global__ __launch_bounds__(kFinThreads) void finish_order(FinishArgs a)
 {
     __shared__ uint32_t lds[kFinLdsWords];
     finish_block<true>(a, blockIdx.x, gridDim.x, lds);
+}
+
+void finish_geometry(uint32_t *tiles_per_workgroup, uint32_t *fan, uint32_t *flat, uint32_t *sums_per_round)
+{
+    if (tiles_per_workgroup) *tiles_per_workgroup = kFinTiles;
+    if (fan) *fan = kFinFan;
+    if (flat) *flat = kFinFlat;
+    if (sums_per_round) *sums_per_round = kFinSumsPerRound;
 }
 
 hipError_t launch_finish(hipStream_t s, const FinishArgs &a, hipEvent_t e0, hipEvent_t e1)

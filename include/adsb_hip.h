@@ -1536,6 +1536,11 @@ int adsb_debug_set_launch_index(adsb_ctx *ctx, uint32_t idx);
  * ADSB_FLAG_INCOMPLETE, nothing hangs, and the context stays usable (the reference's only failure mode is a closed
  * channel, src/adsb.rs:108-111: the replacement must not add a hang). */
 int adsb_debug_finish_stall(adsb_ctx *ctx, uint32_t blk);
+/* finish_order's constants (each may be NULL), for tests: tiles per workgroup; workgroups whose totals one second-level
+ * sum holds; the largest number of workgroups that still exchange their totals in one level; second-level sums a
+ * workgroup reads per round.  These are the sizes at which the kernel takes another path.  The list does not depend on
+ * them. */
+int adsb_debug_finish_geometry(uint32_t *tiles_per_workgroup, uint32_t *fan, uint32_t *flat, uint32_t *sums_per_round);
 /* Diagnostic builds of demod_tiles (-DADSB_TILE_STAMPS=1) only: 16 uint32 per tile of the last launch (waves 0
  * and 3 of the tile's workgroup, 8 each: shader cycles in prologue, phase 1, barrier, phase 2, barrier, phase 3,
  * wait for the loads; s_memrealtime at start).  ADSB_E_STATE in a normal build. */

@@ -13,6 +13,7 @@ import air_rs_amd as A
 from air_rs_amd import _lib
 from tests import correlate_cases as K
 from tests import correlate_model as M
+from tests import finish_cases as FC
 from tests import wire_model as W
 from tests.traffic import ident_frame, position_frame
 
@@ -200,6 +201,40 @@ def test_from_a_launch(gpu, rebuild):
         assert (want[0]["best_receiver"] != 0xFFFF).sum() > 30
         # a wider window joins no more here than equal times do, and never fewer receptions
         M.same(d.correlate(100, delays), M.correlate(frames, counts, 100, delays), "window 100")
+    del dev
+
+
+# ---- 8b: a launch of as many channels as correlate takes receivers, and of one more ---------------------------------------
+def test_from_a_launch_of_256_and_257_channels(gpu, oracle):
+    """One-tile channels from the pool of tests/finish_cases.py, channel k as receiver k.  256 channels: what
+    correlate_of makes of the fetched list and counts (and the model).  257: ADSB_E_ARG, and the result of the call
+    before stays."""
+    L = _lib.load()
+    n = FC.SAMPLES
+    p = FC.pool(oracle, A.ADSB_SAMPLE_I8, n)
+    perm = np.random.default_rng(257).integers(0, len(p.counts), 257)
+    perm[255:] = np.nonzero(p.counts >= 2)[0][:2]                    # the last receiver of either launch has frames
+    c = FC.case_of(p, perm)
+    dev = _dev(np.ascontiguousarray(p.iq[c.perm]))
+    with A.AdsbDemod(max_samples=n, max_out=int(c.prefix[-1]) + 16, max_channels=257, host_staging=False) as d:
+        d.demod_device_async(dev.data_ptr(), n, n_channels=256, channel_stride=n)
+        base = [k % 3 for k in range(256)]                           # within the window: equal entries join across channels
+        got = d.correlate(2, base)
+        frames, counts, total, flags = d.fetch()
+        assert flags == 0 and total == len(frames) == c.prefix[256] and frames.tobytes() == c.frames[:total].tobytes()
+        assert list(counts) == c.counts[:256].tolist() and counts[255] > 0
+        want = M.correlate(frames, counts, 2, base)
+        M.same(got, want, "256 channels")
+        M.same(d.correlate_of(frames, counts, 2, base), want, "correlate_of")
+        assert want[0]["n_receivers"].max() > 1 and len(want[0]) < len(frames)
+        kept = d.fetch_correlated()
+        d.demod_device_async(dev.data_ptr(), n, n_channels=257, channel_stride=n)
+        cfg = _lib.AdsbCorrelateCfg(2, 0, 0)
+        assert L.adsb_correlate_launch(d.handle, C.byref(cfg), None) == A.ADSB_E_ARG
+        M.same(d.fetch_correlated(), kept, "the rejected launch leaves the result")
+        M.same(_device_result(d), want, "and the device arrays")
+        frames, counts, total, flags = d.fetch()                     # the launch itself is whole
+        assert flags == 0 and frames.tobytes() == c.frames.tobytes() and list(counts) == c.counts.tolist()
     del dev
 
 

@@ -13,6 +13,7 @@ import pytest
 
 import air_rs_amd as A
 from air_rs_amd import _lib
+from tests import finish_cases as FC
 from tests import levels_cases as K
 from tests import levels_model
 
@@ -92,6 +93,37 @@ def test_multi_channel_with_stride_and_base(gpu, base):
             assert (part["offset"] >= base).all()
             _same(lv[pos:pos + counts[c]], levels_model.levels(chans[c], part, first_sample=base))
             pos += counts[c]
+        del dev
+
+
+# ---- 3b: more channels than one round of the channel lookup's ballot holds ------------------------------------------------
+@pytest.mark.parametrize("nch", [64, 65, 66, 130])
+def test_channel_lookup_past_one_ballot_round(gpu, oracle, nch):
+    """frame_levels_kernel finds a frame's channel by counting, 64 channels per ballot, the channels that start at or
+    before it in the list: 64 channels are one round with lane 63 idle, 65 fill it, 66 and 130 need a second and a third.
+    One-tile channels of 1000 samples from the pool of tests/finish_cases.py, so every frame's window fits; channels
+    without frames at the front, at index 64 and 65 and at the end (their prefix entries equal their neighbours')."""
+    n = 1000
+    p = FC.pool(oracle, A.ADSB_SAMPLE_I8, n)
+    empty, full = np.nonzero(p.counts == 0)[0], np.nonzero(p.counts > 0)[0]
+    rng = np.random.default_rng(nch)
+    perm = full[rng.integers(0, len(full), nch)]
+    for k, c in enumerate(c for c in (0, 64, 65, nch - 1) if c < nch):
+        perm[c] = empty[k % len(empty)]
+    c = FC.case_of(p, perm)
+    assert c.counts[0] == c.counts[-1] == 0 and len(set(c.counts.tolist())) >= 4 and c.prefix[-1] > 4 * nch
+    buf = np.ascontiguousarray(p.iq[perm])
+    with A.AdsbDemod(max_samples=n, max_out=int(c.prefix[-1]) + 16, max_channels=nch, host_staging=False) as d:
+        dev = _dev(buf)
+        d.demod_device_async(dev.data_ptr(), n, n_channels=nch, channel_stride=n)
+        frames, counts, total, flags = d.fetch()
+        assert flags == 0 and total == len(frames) and frames.tobytes() == c.frames.tobytes()
+        assert list(counts) == c.counts.tolist()
+        lv = d.levels()
+        assert len(lv) == len(frames) and (lv["flags"] == A.ADSB_LEVEL_VALID).all()
+        for ch in range(nch):
+            part = slice(int(c.prefix[ch]), int(c.prefix[ch + 1]))
+            _same(lv[part], levels_model.levels(p.iq[perm[ch]], frames[part]))
         del dev
 
 
