@@ -518,6 +518,7 @@ PROTOTYPES = {
                                        C.c_void_p]),
     "adsb_synth_fill_device": (C.c_int, [C.c_void_p, _P(AdsbSynthCfg), C.c_uint32, C.c_uint64,
                                          C.c_size_t, C.c_void_p]),
+    "adsb_debug_synth_geometry": (C.c_int, [_P(C.c_uint32)]),
     "adsb_synth_slot": (C.c_int, [_P(AdsbSynthCfg), C.c_uint32, C.c_uint64, _P(C.c_uint64),
                                   _P(C.c_uint8 * 14), _P(C.c_uint8 * 14), _P(C.c_int)]),
     # include/adsb_host.h

@@ -938,3 +938,9 @@ extern "C" int adsb_synth_fill_device(adsb_ctx *c, const adsb_synth_cfg *cfg, ui
     HIPCHK(adsbk::launch_synth(c->stream, *cfg, c->cfg.sample_type, channel, first, n, iq_dev));
     return ADSB_OK;
 }
+
+extern "C" int adsb_debug_synth_geometry(uint32_t *threads)
+{
+    if (threads) *threads = adsbk::synth_geometry();
+    return ADSB_OK;
+}

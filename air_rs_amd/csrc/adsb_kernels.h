@@ -529,5 +529,7 @@ hipError_t launch_read_only(hipStream_t s, const void *buf, size_t bytes, uint32
 constexpr int kReadShapes = 3;
 hipError_t launch_synth(hipStream_t s, const adsb_synth_cfg &cfg, int sample_type,
                         uint32_t channel, uint64_t first, size_t n, void *iq);
+// threads of the grid launch_synth launches (adsb_debug_synth_geometry): past it a thread writes a second sample
+uint32_t synth_geometry();
 
 } // namespace adsbk

@@ -1764,6 +1764,10 @@ hipError_t launch_read_only(hipStream_t s, const void *buf, size_t bytes, uint32
 }
 
 // Synthetic source: one thread per sample (untimed; clarity over speed).
+constexpr uint32_t kSynthBlocks = 256 * 16, kSynthThreads = 256; // the whole grid; longer ranges go round the loop
+
+uint32_t synth_geometry() { return kSynthBlocks * kSynthThreads; }
+
 template <int ST>
 __global__ void synth_kernel(adsb_synth_cfg cfg, uint32_t channel, uint64_t first, size_t n, void *iq)
 {
@@ -1800,7 +1804,7 @@ hipError_t launch_synth(hipStream_t s, const adsb_synth_cfg &cfg, int sample_typ
                         uint64_t first, size_t n, void *iq)
 {
     if (n == 0) return hipSuccess;
-    dim3 grid(256 * 16), block(256);
+    dim3 grid(kSynthBlocks), block(kSynthThreads);
     if (sample_type == ADSB_SAMPLE_I8)
         hipLaunchKernelGGL((synth_kernel<ADSB_SAMPLE_I8>), grid, block, 0, s, cfg, channel, first, n, iq);
     else

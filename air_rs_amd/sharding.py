@@ -24,11 +24,12 @@ class Shard:
 
 
 def plan(total_samples: int, world: int):
-    """Even split of the offsets [0, total_samples - 240) over `world` ranks."""
+    """Even split of the offsets [0, total_samples - 240) over `world` ranks: the cut adsb_group_plan makes.  A rank's
+    share is rounded up to a multiple of 8 samples, so that every slice of one 16-byte aligned buffer starts aligned."""
     if total_samples < WINDOW:
         raise ValueError("stream shorter than 240 samples (the reference panics, adsb.rs:98)")
     n_off = total_samples - WINDOW
-    per = -(-n_off // world) if n_off else 0
+    per = (-(-n_off // world) + 7) & ~7 if n_off else 0
     shards = []
     for g in range(world):
         lo = min(g * per, n_off)

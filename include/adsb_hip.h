@@ -1565,6 +1565,9 @@ int adsb_synth_fill_host(const adsb_synth_cfg *cfg, int sample_type, uint32_t ch
                          uint64_t first_sample, size_t n_samples, void *iq_host);
 int adsb_synth_fill_device(adsb_ctx *ctx, const adsb_synth_cfg *cfg, uint32_t channel,
                            uint64_t first_sample, size_t n_samples, void *iq_dev);
+/* Threads of the grid adsb_synth_fill_device launches (may be NULL): a longer range sends threads round the kernel's
+ * loop for a second sample, for tests.  The stream does not depend on it. */
+int adsb_debug_synth_geometry(uint32_t *threads);
 /* The frame (and what the demodulator must make of it) planted in slot `slot`:
  * returns 1 if the slot carries a frame; start = first preamble sample (absolute),
  * clean14 = the error-free frame, kind: 0 clean, 1 data-bit flip, 2 crc-bit flip, 3 two flips. */

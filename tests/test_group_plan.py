@@ -1,6 +1,6 @@
 """adsb_group_plan (include/adsb_hip.h): the native time-shard plan of adsb_group_* -- a pure function of the C ABI, so it
 is checked on the CPU tier: every offset of the reference loop (adsb.rs:98) owned exactly once, 240-sample overlap, slices
-16-byte aligned; and the same cut as air_rs_amd.sharding.plan up to that alignment."""
+16-byte aligned; and the same cut as air_rs_amd.sharding.plan."""
 import pytest
 
 import air_rs_amd as A
@@ -27,12 +27,13 @@ def test_group_plan_covers_every_offset_once():
 
 
 def test_group_plan_agrees_with_the_python_plan_where_aligned():
-    """sharding.plan (what bench.py --gpus N uses) splits evenly; the native plan rounds the slice length up to a multiple
-    of 8 samples so that every slice of one 16-byte aligned buffer starts aligned.  Both own every offset exactly once."""
+    """sharding.plan and the native plan make the same cut: both round a member's share up to a multiple of 8 samples so
+    that every slice of one 16-byte aligned buffer starts aligned.  Both own every offset exactly once."""
     for n in (100_000 + 240, 3_000_017, 1 << 24):
         for world in (2, 3, 8):
             native = A.group_plan(n, world)
             py = sharding.plan(n, world)
             assert sum(s[2] for s in native) == n - 240 == sum(sh.n_offsets for sh in py)
+            assert native == [(sh.first_sample, sh.n_samples, sh.n_offsets) for sh in py]
             for sh in py:   # the same reading rule on both sides: a slice is its offsets plus the 240-sample window
                 assert sh.n_samples == sh.n_offsets + 240 and sh.first_sample == sh.first_offset
