@@ -86,7 +86,7 @@ class AdsbWireCfg(C.Structure):
     _fields_ = [("format", C.c_uint32), ("signal", C.c_uint32), ("tick_bias", C.c_uint64)]
 
 
-ADSB_WIRE_IN_CRC, ADSB_WIRE_IN_DF17 = 0x1, 0x2                 # adsb_wire_in_cfg.filter
+ADSB_WIRE_IN_CRC, ADSB_WIRE_IN_DF17, ADSB_WIRE_IN_SHORT = 0x1, 0x2, 0x4   # adsb_wire_in_cfg.filter
 
 
 class AdsbWireInCfg(C.Structure):
@@ -105,6 +105,25 @@ class AdsbWireInHeader(C.Structure):
     """adsb_wire_in_header: the totals of one parse (64 bytes)."""
     _fields_ = [(k, C.c_uint64) for k in ("n_frames", "total_found", "n_marks", "n_cut", "n_unknown", "n_other",
                                           "n_rejected", "flags")]
+
+
+ADSB_MODES_SELF, ADSB_MODES_KNOWN, ADSB_MODES_UNKNOWN, ADSB_MODES_PARITY, ADSB_MODES_UNSUPPORTED = 0, 1, 2, 3, 4
+(ADSB_MODES_ALT, ADSB_MODES_ALT_METRIC, ADSB_MODES_SQUAWK, ADSB_MODES_GROUND, ADSB_MODES_ALERT, ADSB_MODES_SPI,
+ ADSB_MODES_CALLSIGN) = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40    # adsb_modes_rec.flags
+
+
+class AdsbModesRec(C.Structure):
+    """adsb_modes_rec: one frame's address, kind and surveillance fields (32 bytes)."""
+    _fields_ = [("address", C.c_uint32), ("df", C.c_uint8), ("kind", C.c_uint8), ("flags", C.c_uint16),
+                ("altitude_ft", C.c_int32), ("squawk", C.c_uint16), ("fs", C.c_uint8), ("dr", C.c_uint8),
+                ("um", C.c_uint8), ("iid", C.c_uint8), ("ca", C.c_uint8), ("ri", C.c_uint8), ("callsign", C.c_char * 8),
+                ("reserved", C.c_uint8 * 4)]
+
+
+class AdsbModesHeader(C.Structure):
+    """adsb_modes_header: the totals of one adsb_modes_of (64 bytes)."""
+    _fields_ = [(k, C.c_uint64) for k in ("n", "n_self", "n_known", "n_unknown", "n_parity", "n_unsupported",
+                                          "n_known_out", "n_squitters")]
 
 
 class AdsbCorrelateCfg(C.Structure):
@@ -381,6 +400,11 @@ PROTOTYPES = {
                                      C.c_void_p, C.c_void_p, C.c_uint32, _P(AdsbWireInHeader)]),
     "adsb_wire_in_device": (C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 6),
     "adsb_debug_wire_in_geometry": (C.c_int, [_P(C.c_uint32), _P(C.c_uint32)]),
+    "adsb_modes_of": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
+    "adsb_fetch_modes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                   C.c_void_p, C.c_uint32, _P(AdsbModesHeader)]),
+    "adsb_modes_device": (C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 5),
+    "adsb_debug_modes_geometry": (C.c_int, [_P(C.c_uint32)]),
     "adsb_correlate_launch": (C.c_int, [C.c_void_p, _P(AdsbCorrelateCfg), C.c_void_p]),
     "adsb_correlate_of": (C.c_int, [C.c_void_p, _P(AdsbCorrelateCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                     C.c_uint32, C.c_void_p]),
@@ -547,6 +571,8 @@ PROTOTYPES = {
     "adsb_host_wire_parse": (C.c_int, [_P(AdsbWireInCfg), C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p,
                                        _P(AdsbWireInHeader)]),
+    "adsb_host_modes": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, _P(AdsbModesHeader)]),
     "adsb_host_correlate": (C.c_int, [_P(AdsbCorrelateCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
                                       C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p]),
     "adsb_host_multilaterate": (C.c_int, [_P(AdsbMlatCfg), C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,

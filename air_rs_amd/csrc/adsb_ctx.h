@@ -125,6 +125,18 @@ struct adsb_ctx {
         bool with_levels = false;   // the last call wrote level records
         bool done = false;          // a call has been enqueued
     } win;
+    // Mode S replies (adsb_modes.hip), allocated on first adsb_modes_of and grown on demand: one hipMalloc carved into
+    // everything `a` below points into and the receivers' prefix, and device copies of host lists
+    struct Modes {
+        DevBuf<char> mem;
+        size_t frames = 0, known = 0;        // what it holds: frames, and entries of known_in
+        adsbk::ModesArgs a{};                // scratch and result pointers (the lists and their lengths are set per call)
+        uint64_t *prefix = nullptr;          // [257]
+        DevBuf<adsb_frame> in_frames;        // of a host list
+        DevBuf<uint32_t> in_known;
+        uint32_t n_receivers = 0;            // of the last call; 0: it had no counts
+        bool done = false;                   // a call has been enqueued
+    } modes;
     // tracker (allocated on first adsb_track_device): one hipMalloc carved into the five below
     DevBuf<char> trk_mem;
     uint32_t *trk_u32 = nullptr;    // 4 x [max_out]: keys, vals, sorted keys, sorted vals

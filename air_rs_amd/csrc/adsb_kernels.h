@@ -264,6 +264,33 @@ struct CorrArgs {
 size_t corr_temp_bytes(size_t n);
 hipError_t launch_correlate(hipStream_t s, const CorrArgs &a);
 
+// every frame's address and surveillance fields (adsb_modes.hip: the dispatch sequence is described there)
+constexpr uint32_t kModesBlock = 256; // frames (= threads) per workgroup of the stage's kernels
+constexpr uint32_t modes_blocks(uint64_t n) { return (uint32_t)((n + kModesBlock - 1) / kModesBlock); }
+struct ModesArgs {
+    const adsb_frame *frames;        // [n], adsb_fetch's layout
+    const uint32_t *known_in;        // [n_known_in] ascending, unique, < 2^24
+    const uint64_t *prefix;          // [n_receivers + 1] frames in front of each receiver, last = n; null: no counts
+    uint32_t n, n_known_in, n_receivers;
+    // scratch; m = n_known_in + n entries
+    uint32_t *key, *val;             // [m] known_in's (address, 0), then per frame (address or 2^24, 1 + index)
+    uint32_t *key_s, *val_s;         // [m] the same in stable address order
+    uint32_t *hidx;                  // [m] heads of address runs up to and with each sorted entry
+    uint32_t *first;                 // [m] per known_out entry: 0 (of known_in) or 1 + the index of its first SELF frame
+    uint32_t *sidx;                  // [n] squitters up to and with each frame
+    uint32_t *tally;                 // [5 x modes_blocks(n)] the kinds of each workgroup's frames
+    void *temp;
+    size_t temp_bytes;               // >= modes_temp_bytes(capacity)
+    // results
+    adsb_modes_rec *recs;            // [n]
+    uint32_t *known_out;             // [m]
+    adsb_frame *squitters;           // [n]
+    uint64_t *sq_counts;             // [256]
+    adsb_modes_header *hdr;
+};
+size_t modes_temp_bytes(size_t m);
+hipError_t launch_modes(hipStream_t s, const ModesArgs &a);
+
 // transmitter positions from correlated receptions (adsb_mlat.hip; adsb_mlat.h has the solver's text)
 constexpr uint32_t kMlatBlock = 256;                          // threads per workgroup of mlat_solve
 constexpr uint32_t kMlatPerBlock = kMlatBlock / kMlatLanes;   // messages per workgroup: 16 lanes each

@@ -17,6 +17,7 @@ namespace adsbk {
 
 constexpr uint32_t kWireInHalo = 43;     // a mark at m reads at most b[m + 1 .. m + 43]: the type byte and 21 doubled bytes
 constexpr uint32_t kWireInMinBytes = 23; // the shortest long frame (Beast; an AVR line has 30 or more)
+constexpr uint32_t kWireInMinShortBytes = 16; // the shortest short frame, in both formats: 1A '2' + 14, '*' + 14 digits + ';'
 constexpr uint32_t kWireInMaxStreams = 256;
 
 // what a mark turned out to be
@@ -25,15 +26,29 @@ constexpr uint32_t kWinCut = 1;        // another mark (Beast) or a byte that do
 constexpr uint32_t kWinIncomplete = 2; // it needs a byte at or past the end of its stream
 constexpr uint32_t kWinOther = 3;      // complete, but no long message: counted, not emitted
 constexpr uint32_t kWinLong = 4;       // complete with 14 message bytes
+constexpr uint32_t kWinShort = 5;      // complete with 7 message bytes: emitted with ADSB_WIRE_IN_SHORT, else counted as other
 
 struct WireInMark {
     uint32_t state;  // kWin*
     uint32_t end;    // where reading stopped (complete: the exclusive end of the frame's bytes), a position like the mark's
     uint32_t kind;   // the type byte ('3', ...) or the lead byte ('*', '@')
-    uint32_t signal; // kWinLong, Beast: the signal byte; else 0
-    uint64_t ticks;  // kWinLong: the 48-bit timestamp; 0 for a plain '*' line
-    uint64_t hi, lo; // kWinLong: message bytes 0..5 (the low 48 bits of hi) and 6..13, big-endian
+    uint32_t signal; // kWinLong / kWinShort, Beast: the signal byte; else 0
+    uint64_t ticks;  // kWinLong / kWinShort: the 48-bit timestamp; 0 for a plain '*' line
+    uint64_t hi, lo; // kWinLong: message bytes 0..5 (the low 48 bits of hi) and 6..13, big-endian; kWinShort: 0..5 and
+                     // byte 6 in the top byte of lo, the rest of lo 0
 };
+
+// a frame that is emitted when it passes the filters
+ADSB_WIRE_HD inline bool wire_in_emits(uint32_t filter, const WireInMark &r)
+{
+    return r.state == kWinLong || (r.state == kWinShort && (filter & ADSB_WIRE_IN_SHORT));
+}
+
+// frames that can exist in n_bytes bytes: what max_frames = 0 means
+ADSB_WIRE_HD inline uint64_t wire_in_most(uint32_t filter, uint64_t n_bytes)
+{
+    return n_bytes / ((filter & ADSB_WIRE_IN_SHORT) ? kWireInMinShortBytes : kWireInMinBytes);
+}
 
 ADSB_WIRE_HD inline bool wire_in_cfg_ok(const adsb_wire_in_cfg *cfg)
 {
@@ -75,6 +90,14 @@ ADSB_WIRE_HD inline WireInMark wire_in_read_beast(const uint8_t *b, uint32_t m, 
     }
     r.end = p;
     r.state = kWinOther;
+    if (len == 7) { // 14 bytes: the timestamp is the low 48 bits of a1, then the signal byte and the message in a0
+        r.state = kWinShort;
+        r.ticks = a1 & kWireTickMask;
+        r.signal = (uint32_t)(a0 >> 56);
+        r.hi = (a0 >> 8) & kWireTickMask;
+        r.lo = (a0 & 0xFFull) << 56;
+        return r;
+    }
     if (len != 14) return r;
     r.state = kWinLong;
     r.ticks = ((a2 << 8) | (a1 >> 56)) & kWireTickMask; // bytes 0..5 of 21
@@ -119,7 +142,13 @@ ADSB_WIRE_HD inline WireInMark wire_in_read_avr(const uint8_t *b, uint32_t p, ui
             r.ticks = stamped ? ((a2 << 16) | (a1 >> 48)) & kWireTickMask : 0ull; // digits 0..11 of 40
             r.hi = a1 & kWireTickMask;                                             // the last 28 digits
             r.lo = a0;
-        } else if (h == (stamped ? 16u : 4u) || h == (stamped ? 26u : 14u)) {
+        } else if (h == (stamped ? 26u : 14u)) {
+            r.end = q + 1;
+            r.state = kWinShort;
+            r.ticks = stamped ? ((a1 << 8) | (a0 >> 56)) & kWireTickMask : 0ull; // digits 0..11 of 26
+            r.hi = (a0 >> 8) & kWireTickMask;                                     // the last 14 digits
+            r.lo = (a0 & 0xFFull) << 56;
+        } else if (h == (stamped ? 16u : 4u)) {
             r.end = q + 1;
             r.state = kWinOther;
         }
@@ -155,17 +184,40 @@ ADSB_WIRE_HD inline adsb_frame_level wire_in_level(uint32_t s, int sample_type)
     return lv;
 }
 
-// message byte k (0..13) of a long mark
+// message byte k (0..13) of a long or short mark (short: 0 from byte 7 on)
 ADSB_WIRE_HD inline uint8_t wire_in_byte(const WireInMark &r, uint32_t k)
 {
     return (uint8_t)(k < 6 ? r.hi >> (40u - 8u * k) : r.lo >> (56u - 8u * (k - 6u)));
 }
 
-// cfg.filter on a long mark: true = keep
+// CRC-24 of the first 4 bytes (a short frame's payload), the shift form of adsb_synth::crc24_11
+ADSB_WIRE_HD inline uint32_t wire_in_crc24_4(const uint8_t *d)
+{
+    uint32_t r = 0;
+    for (int b = 0; b < 4; ++b) {
+        r ^= (uint32_t)d[b] << 16;
+        for (int i = 0; i < 8; ++i) {
+            r <<= 1;
+            if (r & 0x1000000u) r ^= 0x1FFF409u;
+        }
+    }
+    return r & 0xFFFFFFu;
+}
+
+// cfg.filter on a long or short mark: true = keep.  The filters are literal: a short frame is never DF17, and an
+// address/parity reply (DF0/4/5/16/20/21) never has a zero syndrome -- adsb_modes_of is the check for those.
 ADSB_WIRE_HD inline bool wire_in_keep(uint32_t filter, const WireInMark &r)
 {
     uint8_t d[14];
     for (uint32_t k = 0; k < 14; ++k) d[k] = wire_in_byte(r, k);
+    if (r.state == kWinShort) {
+        if (filter & ADSB_WIRE_IN_DF17) return false;
+        if (filter & ADSB_WIRE_IN_CRC) {
+            const uint32_t sent = (uint32_t)d[4] << 16 | (uint32_t)d[5] << 8 | d[6];
+            if (wire_in_crc24_4(d) ^ sent) return false;
+        }
+        return true;
+    }
     if ((filter & ADSB_WIRE_IN_DF17) && (d[0] >> 3) != 17u) return false;
     if (filter & ADSB_WIRE_IN_CRC) {
         const uint32_t sent = (uint32_t)d[11] << 16 | (uint32_t)d[12] << 8 | d[13];
@@ -202,7 +254,7 @@ ADSB_WIRE_HD inline WireInMark wire_in_read(bool is_beast, const uint8_t *b, uin
     return is_beast ? wire_in_read_beast(b, m, limit) : wire_in_read_avr(b, m, limit);
 }
 
-// The header's counters as one mark changes them.  kept: the long frame passed the filters.
+// The header's counters as one mark changes them.  kept: the frame is emitted (wire_in_emits) and passed the filters.
 struct WireInTally {
     uint32_t marks, cut, unknown, other, rejected, kept;
 };
@@ -211,8 +263,9 @@ ADSB_WIRE_HD inline bool wire_in_count(const WireInMark &r, uint32_t filter, Wir
     t->marks += 1;
     t->cut += r.state == kWinCut;
     t->unknown += r.state == kWinUnknown;
-    t->other += r.state == kWinOther;
-    if (r.state != kWinLong) return false;
+    const bool emits = wire_in_emits(filter, r);
+    t->other += r.state == kWinOther || (r.state == kWinShort && !emits);
+    if (!emits) return false;
     const bool keep = wire_in_keep(filter, r);
     t->rejected += !keep;
     t->kept += keep;

@@ -21,11 +21,12 @@
 //   4 wire_in_totals  ONE workgroup: the exclusive prefix of the spans' kept frames, the header, consumed[].
 //   5 wire_in_marks<true>   the same walk again; a kept frame goes to its list index: the span's prefix plus an
 //                     exclusive sum over the threads in front (a thread's 16 bytes hold at most one kept frame: complete
-//                     frames do not overlap and a long one is 23 bytes or more).  Frames, rx and levels are written here.
+//                     frames do not overlap, a long one is 23 bytes or more and a short one, emitted with
+//                     ADSB_WIRE_IN_SHORT, 16 or more).  Frames, rx and levels are written here.
 //   6 wire_in_counts  ONE workgroup: counts[] by two binary searches per receiver over rx[].receiver, which ascends.
 // No atomics, no workgroup waits for another (the dispatch boundaries are the only ordering), and nothing depends on the
 // grid: the lists are the same bytes from run to run.  Hostile density (1A 33 1A 33 ...: a mark every 2 bytes, each cut
-// by the next) costs a thread 8 short reads; at most one kept frame exists per 23 bytes.
+// by the next) costs a thread 8 short reads; at most one kept frame exists per 23 bytes (16 with short frames).
 //
 // Everything a thread addresses:
 //   words[w]      w < ceil((lead + n_bytes) / 4): only dwords that hold at least one byte of the input are loaded (an

@@ -70,7 +70,7 @@ extern "C" int adsb_wire_in_of(adsb_ctx *c, const adsb_wire_in_cfg *cfg, const u
     int rc = win_check(cfg, bytes, n_bytes, stream_ends, n_streams, &ends);
     if (rc != ADSB_OK) return rc;
     HIPCHK(hipSetDevice(c->cfg.device));
-    const size_t most = n_bytes / adsbk::kWireInMinBytes; // frames that can exist
+    const size_t most = (size_t)adsbk::wire_in_most(cfg->filter, n_bytes); // frames that can exist
     const size_t cap = cfg->max_frames ? (size_t)std::min<uint64_t>(cfg->max_frames, most) : most;
     if ((rc = win_reserve(c, n_bytes, cap, cfg->levels != 0)) != ADSB_OK) return rc;
     adsb_ctx::WireIn &k = c->win;

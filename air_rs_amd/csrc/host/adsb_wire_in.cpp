@@ -19,7 +19,7 @@ extern "C" int adsb_host_wire_parse(const adsb_wire_in_cfg *cfg, const uint8_t *
         prev = stream_ends[r];
     }
     if (prev != (uint64_t)n_bytes) return ADSB_E_ARG;
-    const uint64_t most = n_bytes / adsbk::kWireInMinBytes;
+    const uint64_t most = adsbk::wire_in_most(cfg->filter, n_bytes);
     const uint64_t cap = cfg->max_frames ? (cfg->max_frames < most ? cfg->max_frames : most) : most;
     const bool beast = cfg->format == ADSB_WIRE_BEAST;
     adsbk::WireInTally tally{};

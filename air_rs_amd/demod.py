@@ -168,7 +168,8 @@ assert WIRE_RX_DTYPE.itemsize == C.sizeof(L.AdsbWireRx) == 16
 WIRE_IN_HEADER_DTYPE = np.dtype([(k, "<u8") for k in ("n_frames", "total_found", "n_marks", "n_cut", "n_unknown",
                                                        "n_other", "n_rejected", "flags")])
 assert WIRE_IN_HEADER_DTYPE.itemsize == C.sizeof(L.AdsbWireInHeader) == 64
-WIRE_IN_FILTERS = {"crc": L.ADSB_WIRE_IN_CRC, "df17": L.ADSB_WIRE_IN_DF17}
+WIRE_IN_FILTERS = {"crc": L.ADSB_WIRE_IN_CRC, "df17": L.ADSB_WIRE_IN_DF17, "short": L.ADSB_WIRE_IN_SHORT}
+WIRE_IN_SHORT = L.ADSB_WIRE_IN_SHORT     # filter bit: also emit the 56-bit frames (Mode S replies; see modes_of)
 WireIn = collections.namedtuple("WireIn", "frames rx levels counts consumed header")
 WireIn.__doc__ = """One parse of wire input: FRAME_DTYPE frames, WIRE_RX_DTYPE rx, LEVEL_DTYPE levels (None without
 levels=True), uint64 counts and consumed per stream, and the WIRE_IN_HEADER_DTYPE record."""
@@ -195,8 +196,9 @@ def _wire_in_input(data, stream_ends):
     return keep, (ptr if n else None), n, ends
 
 
-def _wire_in_room(n_bytes, max_frames, levels):
-    room = n_bytes // 23 if not max_frames else min(int(max_frames), n_bytes // 23)
+def _wire_in_room(n_bytes, max_frames, levels, filter_bits=0):
+    most = n_bytes // (16 if filter_bits & L.ADSB_WIRE_IN_SHORT else 23)      # the shortest emitted frame
+    room = most if not max_frames else min(int(max_frames), most)
     return (room, np.zeros(max(room, 1), dtype=FRAME_DTYPE), np.zeros(max(room, 1), dtype=WIRE_RX_DTYPE),
             np.zeros(max(room, 1), dtype=LEVEL_DTYPE) if levels else None)
 
@@ -215,7 +217,7 @@ def host_wire_parse(data, stream_ends=None, format="beast", filter=0, tick_bias=
     device."""
     keep, ptr, n, ends = _wire_in_input(data, stream_ends)
     cfg = _wire_in_cfg(format, filter, tick_bias, max_frames, sample_type, levels)
-    room, fr, rx, lv = _wire_in_room(n, max_frames, levels)
+    room, fr, rx, lv = _wire_in_room(n, max_frames, levels, cfg.filter)
     counts, consumed = np.zeros(len(ends), dtype=np.uint64), np.zeros(len(ends), dtype=np.uint64)
     got, hdr = C.c_size_t(), L.AdsbWireInHeader()
     L.check(L.load().adsb_host_wire_parse(C.byref(cfg), ptr, n, ends.ctypes.data if len(ends) else None, len(ends),
@@ -224,6 +226,49 @@ def host_wire_parse(data, stream_ends=None, format="beast", filter=0, tick_bias=
                                           consumed.ctypes.data if len(ends) else None, C.byref(hdr)),
             "adsb_host_wire_parse")
     return _wire_in_result(fr, rx, lv, got.value, counts, consumed, hdr)
+
+
+MODES_DTYPE = np.dtype([("address", "<u4"), ("df", "u1"), ("kind", "u1"), ("flags", "<u2"), ("altitude_ft", "<i4"),
+                        ("squawk", "<u2"), ("fs", "u1"), ("dr", "u1"), ("um", "u1"), ("iid", "u1"), ("ca", "u1"), ("ri", "u1"),
+                        ("callsign", "S8"), ("reserved", "u1", (4,))])
+assert MODES_DTYPE.itemsize == C.sizeof(L.AdsbModesRec) == 32
+MODES_HEADER_DTYPE = np.dtype([(k, "<u8") for k in ("n", "n_self", "n_known", "n_unknown", "n_parity", "n_unsupported",
+                                                     "n_known_out", "n_squitters")])
+assert MODES_HEADER_DTYPE.itemsize == C.sizeof(L.AdsbModesHeader) == 64
+MODES_KINDS = ("SELF", "KNOWN", "UNKNOWN", "PARITY", "UNSUPPORTED")
+
+
+def _known_list(known):
+    """(array kept alive or None, pointer or None, count) of a known-address argument: None, an ascending unique uint32
+    array, a (device pointer, count) pair, or a TrackTable, whose fetched ICAOs are used."""
+    if known is None:
+        return None, None, 0
+    if isinstance(known, tuple):
+        return None, (int(known[0]) if int(known[1]) else None), int(known[1])
+    if hasattr(known, "aircraft") and not hasattr(known, "dtype"):
+        known = np.unique(np.asarray(known.aircraft()[0]["icao"], dtype=np.uint32))     # (the table lists ascending ICAOs)
+    arr = np.ascontiguousarray(known, dtype=np.uint32).reshape(-1)
+    return arr, (arr.ctypes.data if len(arr) else None), len(arr)
+
+
+def host_modes(frames, counts=None, known=None):
+    """adsb_host_modes, the CPU mirror of AdsbDemod.modes_of: (MODES_DTYPE records, uint32 known_out, FRAME_DTYPE
+    squitters, uint64 squitter_counts or None, the MODES_HEADER_DTYPE record) of the FRAME_DTYPE list `frames`; counts[r]
+    frames per receiver (None: no squitter_counts); known: None or an ascending unique uint32 array of addresses.  Needs
+    no device."""
+    frames, fptr, n = _host_list(frames, FRAME_DTYPE)
+    karr, kptr, nk = _known_list(known)
+    cnt = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    recs, kout = np.zeros(max(n, 1), dtype=MODES_DTYPE), np.zeros(max(n + nk, 1), dtype=np.uint32)
+    sq = np.zeros(max(n, 1), dtype=FRAME_DTYPE)
+    sqc = None if cnt is None else np.zeros(max(len(cnt), 1), dtype=np.uint64)
+    hdr = L.AdsbModesHeader()
+    L.check(L.load().adsb_host_modes(fptr, n, None if cnt is None else cnt.ctypes.data, 0 if cnt is None else len(cnt),
+                                     kptr, nk, recs.ctypes.data, kout.ctypes.data, sq.ctypes.data,
+                                     None if sqc is None else sqc.ctypes.data, C.byref(hdr)), "adsb_host_modes")
+    header = np.frombuffer(bytes(hdr), dtype=MODES_HEADER_DTYPE)[0]
+    return (recs[:n].copy(), kout[:int(header["n_known_out"])].copy(), sq[:int(header["n_squitters"])].copy(),
+            None if sqc is None else sqc[:len(cnt)].copy(), header)
 
 
 MESSAGE_DTYPE = np.dtype([("time", "<u8"), ("bytes", "u1", (14,)), ("status", "u1"), ("fixed_bit", "u1"), ("first", "<u4"),
@@ -772,6 +817,49 @@ class AdsbDemod:
         synchronisation."""
         p = [C.c_void_p() for _ in range(6)]
         L.check(self._lib.adsb_wire_in_device(self._h, *[C.byref(x) for x in p]), "adsb_wire_in_device")
+        return tuple(x.value for x in p)
+
+    def modes_of_async(self, frames, counts=None, known=None):
+        """adsb_modes_of alone: enqueues and returns once the host arrays are copied.  frames: a FRAME_DTYPE array (host)
+        or (device pointer, count); counts: frames per receiver or None; known: None, an ascending unique uint32 array,
+        a (device pointer, count) pair (modes_device()[1] with the last header's n_known_out) or a TrackTable."""
+        if isinstance(frames, tuple):
+            fptr, n = (int(frames[0]) if int(frames[1]) else None), int(frames[1])
+        else:
+            frames, fptr, n = _host_list(frames, FRAME_DTYPE)
+        karr, kptr, nk = _known_list(known)
+        cnt = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+        L.check(self._lib.adsb_modes_of(self._h, fptr, n, None if cnt is None else cnt.ctypes.data,
+                                        0 if cnt is None else len(cnt), kptr, nk), "adsb_modes_of")
+        self._modes = 0 if cnt is None else len(cnt)
+
+    def fetch_modes(self):
+        """adsb_fetch_modes: waits for the last modes_of_async() -> (MODES_DTYPE records, uint32 known_out, FRAME_DTYPE
+        squitters, uint64 squitter_counts or None, the MODES_HEADER_DTYPE record)."""
+        R, hdr = getattr(self, "_modes", 0), L.AdsbModesHeader()
+        L.check(self._lib.adsb_fetch_modes(self._h, None, 0, None, 0, None, 0, None, 0, C.byref(hdr)),
+                "adsb_fetch_modes")                   # the sizes first; the lists stay where they are
+        n, nk, ns = int(hdr.n), int(hdr.n_known_out), int(hdr.n_squitters)
+        recs, kout = np.zeros(max(n, 1), dtype=MODES_DTYPE), np.zeros(max(nk, 1), dtype=np.uint32)
+        sq, sqc = np.zeros(max(ns, 1), dtype=FRAME_DTYPE), np.zeros(max(R, 1), dtype=np.uint64)
+        L.check(self._lib.adsb_fetch_modes(self._h, recs.ctypes.data, n, kout.ctypes.data, nk, sq.ctypes.data, ns,
+                                           sqc.ctypes.data if R else None, R, C.byref(hdr)), "adsb_fetch_modes")
+        header = np.frombuffer(bytes(hdr), dtype=MODES_HEADER_DTYPE)[0]
+        return recs[:n].copy(), kout[:nk].copy(), sq[:ns].copy(), (sqc[:R].copy() if R else None), header
+
+    def modes_of(self, frames, counts=None, known=None):
+        """adsb_modes_of + adsb_fetch_modes: every frame's address, kind (MODES_KINDS) and Mode S surveillance fields ->
+        (recs, known_out, squitters, squitter_counts, header).  known_out is the next call's `known`; squitters (the
+        SELF DF17/18 frames) and squitter_counts are arguments for TrackTable.update / TrackBank.update.  See
+        modes_of_async."""
+        self.modes_of_async(frames, counts, known)
+        return self.fetch_modes()
+
+    def modes_device(self):
+        """adsb_modes_device: device addresses (records, known_out, squitters, squitter_counts or None, header); no
+        synchronisation."""
+        p = [C.c_void_p() for _ in range(5)]
+        L.check(self._lib.adsb_modes_device(self._h, *[C.byref(x) for x in p]), "adsb_modes_device")
         return tuple(x.value for x in p)
 
     def correlate_async(self, window, sample_base=None, levels=False):

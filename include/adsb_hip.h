@@ -359,7 +359,8 @@ int adsb_debug_wire_geometry(uint32_t *frames_per_block, uint32_t *scan_threads)
  *       mark by the parity rule.  Needing a byte at or past N, including the partner of a final 0x1A, means the frame is
  *       INCOMPLETE.  Otherwise the frame is COMPLETE.
  *     Complete '3' frames that pass the filters are emitted.  Complete '1' and '2' frames are counted (n_other) and not
- *       emitted.  Complete frames never overlap.  Only the last mark of a stream can be incomplete.
+ *       emitted ('2' frames are emitted with ADSB_WIRE_IN_SHORT, see SHORT FRAMES).  Complete frames never overlap.
+ *       Only the last mark of a stream can be incomplete.
  *     CONSUMED  If the stream has an incomplete mark at m, consumed = m.  Otherwise let k be the number of trailing 0x1A
  *       bytes of the stream that no complete frame consumed, and consumed = N - (k mod 2).
  *     CHUNKS  The caller's next chunk is B[consumed..) + new bytes.  Parsing a stream in chunks of any sizes this way
@@ -372,12 +373,19 @@ int adsb_debug_wire_geometry(uint32_t *frames_per_block, uint32_t *scan_threads)
  *     anything else is cut.  If the digits reach the end of the stream with h at most 28 for '*' or at most 40 for '@',
  *     the candidate is incomplete and consumed = p.  Otherwise consumed = N.  Bytes between frames ('\n', '\r\n',
  *     anything) are skipped.
+ *   SHORT FRAMES  With ADSB_WIRE_IN_SHORT in cfg.filter the complete 56-bit frames -- Beast '2', '*' with 14 digits,
+ *     '@' with 26 digits (a 12-digit timestamp first) -- are emitted like long frames: bytes[0..7) = the message,
+ *     bytes[7..14) = 0, status = 0, fixed_bit = 0xFF, offset from the timestamp as for long frames, rx.kind '2', '*' or
+ *     '@', the level record from the signal byte as for '3'.  n_other then counts Mode A/C only ('1'; 4 / 16 digits).
+ *     These are the Mode S replies of transponders without ADS-B (DF0/4/5/11); adsb_modes_of ("Mode S replies") gives
+ *     each its address.  Framing, consumed[] and the chunk rule do not depend on what is emitted.  Without the bit
+ *     every output is what it was before the bit existed.
  *   OUTPUTS, all in stream order: receiver 0's frames by position, then receiver 1's, and so on.
  *     adsb_frame frames[n]: bytes = the 14 message bytes, status = 0, fixed_bit = 0xFF, offset = ((t - tick_bias) mod
  *       2^48) / 6 rounded down, the exact inverse of the encoder's timestamp for offsets below 2^48 / 6.  Plain '*'
  *       lines have t = 0.
  *     adsb_wire_rx rx[n]: the raw t, the position of the mark or lead byte inside its own stream, the signal byte, the
- *       kind ('3', '*' or '@') and the receiver (the stream's index).
+ *       kind ('3', '*' or '@'; '2' for a short Beast frame) and the receiver (the stream's index).
  *     adsb_frame_level levels[n] when cfg.levels != 0.  For a signal byte s > 0: flags = ADSB_LEVEL_VALID and signal_sum
  *       = the smallest sum whose signal byte is s for cfg.sample_type's full scale, ceil((2s-1)^2 x 116 x FS /
  *       (4 x 255^2)), and 1 for s = 1; every other field 0.  For s = 0 or AVR: an all-zero record.  With this,
@@ -388,19 +396,24 @@ int adsb_debug_wire_geometry(uint32_t *frames_per_block, uint32_t *scan_threads)
  *   FILTERS (cfg.filter bits).  A rejected frame is still a complete frame for framing and for consumed; it is counted
  *     in n_rejected and not emitted.  ADSB_WIRE_IN_CRC keeps a long frame only if crc24(bytes[0..11]) ^ bytes[11..14]
  *     == 0 (generator 0x1FFF409; no repair, a Beast sender has already done its own).  ADSB_WIRE_IN_DF17 keeps it only
- *     if bytes[0] >> 3 == 17.
- *   CAPACITY  cfg.max_frames = 0 means n_bytes / 23, which can never truncate.  Otherwise the first max_frames frames
+ *     if bytes[0] >> 3 == 17.  The filters are literal on short frames too: ADSB_WIRE_IN_DF17 rejects every short frame,
+ *     and ADSB_WIRE_IN_CRC keeps one only if crc24(bytes[0..4)) ^ bytes[4..7) == 0.  The address/parity formats
+ *     (DF0/4/5/16/20/21: the address is overlaid on the parity field) therefore NEVER pass the CRC filter, short or
+ *     long; adsb_modes_of is the check for them.
+ *   CAPACITY  cfg.max_frames = 0 means n_bytes / 23 (n_bytes / 16 with ADSB_WIRE_IN_SHORT: the shortest emitted frame
+ *     in both formats), which can never truncate.  Otherwise the first max_frames frames
  *     in order are kept, flags has ADSB_FLAG_TRUNCATED, counts[] are clipped to the list and total_found is the full
  *     number.
  * Nothing depends on atomics or scheduling: two runs give the same bytes.
  */
 #define ADSB_WIRE_IN_CRC 0x1u
 #define ADSB_WIRE_IN_DF17 0x2u
+#define ADSB_WIRE_IN_SHORT 0x4u
 typedef struct adsb_wire_in_cfg {
     uint32_t format;      /* ADSB_WIRE_*                                                       */
     uint32_t filter;      /* ADSB_WIRE_IN_* bits                                               */
     uint64_t tick_bias;   /* < 2^48                                                            */
-    uint64_t max_frames;  /* 0: n_bytes / 23                                                   */
+    uint64_t max_frames;  /* 0: n_bytes / 23 (/ 16 with ADSB_WIRE_IN_SHORT)                    */
     int32_t  sample_type; /* ADSB_SAMPLE_*: the full scale of the level records (with levels) */
     uint32_t levels;      /* != 0: level records beside the frames                             */
 } adsb_wire_in_cfg;
@@ -408,7 +421,7 @@ typedef struct adsb_wire_rx {      /* 16 bytes */
     uint64_t ticks;           /* the raw timestamp t; 0 for a plain '*' line                  */
     uint32_t pos;             /* position of the mark or lead byte inside its own stream      */
     uint8_t  signal;          /* Beast's signal byte; 0 for AVR                               */
-    uint8_t  kind;            /* '3', '*' or '@'                                              */
+    uint8_t  kind;            /* '3', '*' or '@'; '2' for a short Beast frame                 */
     uint16_t receiver;        /* the stream's index                                           */
 } adsb_wire_rx;
 typedef struct adsb_wire_in_header { /* 64 bytes */
@@ -416,7 +429,8 @@ typedef struct adsb_wire_in_header { /* 64 bytes */
 } adsb_wire_in_header;
 /* Parses.  `bytes` is host memory or device memory of the ctx's device; stream_ends is host memory.  Asynchronous on the
  * ctx's stream once host arrays are copied.  Buffers are allocated on first use and grown when needed (may wait for
- * earlier work): per input byte about 0.01 bytes of scan words, per frame of capacity 40 bytes (72 with levels), and a
+ * earlier work): per input byte about 0.01 bytes of scan words, per frame of capacity 40 bytes (72 with levels; the
+ * capacity max_frames = 0 stands for is n_bytes / 16 frames with ADSB_WIRE_IN_SHORT instead of n_bytes / 23), and a
  * copy of a host input; a ctx that never calls it allocates nothing and launches exactly the kernels it launched before.
  * Replaces the result of an earlier call.  n_bytes = 0 and empty streams are ADSB_OK.  ADSB_E_ARG for a NULL ctx, cfg or
  * stream_ends, NULL bytes with n_bytes > 0, an unknown format, tick_bias >= 2^48, a bad sample_type with levels,
@@ -522,6 +536,108 @@ int adsb_correlated_device(adsb_ctx *ctx, const adsb_message **msgs_dev, const a
 /* Threads (= receptions) per workgroup of the correlate kernels: the size at which they take another path, for tests.
  * The result does not depend on it. */
 int adsb_debug_correlate_geometry(uint32_t *threads_per_block);
+
+/*
+ * Mode S replies: the address of every frame of a list, and the surveillance fields of the replies a transponder
+ * without ADS-B sends (DF11 all-call, DF4/5/20/21 surveillance and Comm-B, DF0/16 air-air).  Everything else in this
+ * library reads the address as bytes[1..3]; that holds for DF11/17/18 only.  The other formats overlay the address on
+ * the parity field, so it is recovered as crc24(payload) ^ parity and can be trusted only if the aircraft is already
+ * known.  Stateless; computed on the device; the list is in adsb_fetch's layout and may be wire input's output (with
+ * ADSB_WIRE_IN_SHORT), correlate's frames_out or the demodulator's own list.  correlate -> clock sync -> multilaterate
+ * then place these frames unchanged (the solver does not look at the DF).
+ *   PER FRAME  b = frame.bytes, DF = b[0] >> 3, length 7 bytes for DF < 16 and 14 otherwise (bytes past the length are
+ *     ignored), S = crc24(b[0..len-3)) ^ b[len-3..len), generator 0x1FFF409.
+ *   KIND and ADDRESS
+ *     DF17, DF18: S == 0 -> SELF, address b[1..3]; else PARITY (address 0).
+ *     DF11: S == 0 -> SELF, address b[1..3].  S != 0 with S & 0xFFFF80 == 0 (a reply to interrogator iid = S & 0x7F):
+ *       address b[1..3], KNOWN if that address is known (below), else UNKNOWN.  Otherwise PARITY.
+ *     DF0, 4, 5, 16, 20, 21, 24..31: address S, KNOWN if known, else UNKNOWN.
+ *     Every other DF: UNSUPPORTED, address and all fields 0 (df is still the frame's).
+ *   KNOWN (causal, in list order)  Address a is known at list index j iff a is in known_in[], or some frame i < j of
+ *     this list is SELF with address a.  known_in[n_known_in] is ascending, unique and < 2^24, host or device memory
+ *     (a host array that breaks this is ADSB_E_ARG; for a device array it is an unchecked input contract, as the list
+ *     layout is for correlate).  known_out[] = the ascending unique union of known_in and the list's SELF addresses.
+ *     So modes(L1, K) followed by modes(L2, known_out1) gives exactly the records of modes(L1 + L2, K) and the same
+ *     final known_out: a feed carries known_out from call to call.  Nothing expires here; the caller prunes, for
+ *     example by rebuilding known_in from a track table's ICAOs after its expire.  A garbage frame of an address/parity
+ *     format is accepted as KNOWN with probability |known| / 2^24 (4096 known aircraft: 1 in 4096); consumers that
+ *     cannot bear that ask for two agreeing frames.
+ *   FIELDS are decoded whatever the kind, so consumers look at kind.  f = (b[2] & 0x1F) << 8 | b[3], bits 12..0 =
+ *     C1 A1 C2 A2 C4 A4 M B1 Q B2 D2 B4 D4 (M and Q in the AC field; 0 and D1 in the ID field).
+ *     DF4/5/20/21: fs = b[0] & 7, dr = b[1] >> 3, um = (b[1] & 7) << 3 | b[2] >> 5; GROUND for fs 1, 3; ALERT for fs
+ *       2, 3, 4; SPI for fs 4, 5.  DF0/16: GROUND for vs = b[0] >> 2 & 1, ri = (b[1] & 7) << 1 | b[2] >> 7.
+ *       DF11/17/18: ca = b[0] & 7; iid as above (DF11), else 0.
+ *     ALTITUDE (DF0/4/16/20, f = AC): f == 0: none.  M = 1: none, ALT_METRIC.  Q = 1: n = (f & 0x1F80) >> 2 |
+ *       (f & 0x20) >> 1 | (f & 0xF), altitude_ft = 25 n - 1000, ALT.  Q = 0, Gillham: h = binary of the Gray code D2 D4
+ *       A1 A2 A4 B1 B2 B4, c = binary of the Gray code C1 C2 C4 with 5 and 7 exchanged; c == 0 or c > 5: none; h odd:
+ *       c = 6 - c; altitude_ft = 500 h + 100 c - 1300, ALT.  1280 valid codes, -1200 .. 126700 ft.
+ *     SQUAWK (DF5/21, f = ID): digits A = A4 A2 A1, B, C, D likewise; squawk = 1000 A + 100 B + 10 C + D, so 7700 reads
+ *       7700; SQUAWK.
+ *     CALLSIGN (DF20/21 with b[4] == 0x20, BDS 2,0): callsign[8] = the eight 6-bit characters of b[5..11) in the ICAO
+ *       set as the field decode spells it ('_' for space, '#' for none); CALLSIGN only if every character is a letter,
+ *       a digit or the space.  Otherwise callsign is 0.
+ *   OUTPUTS  adsb_modes_rec recs[n], index for index with the list; uint32 known_out[n_known_out]; adsb_frame
+ *     squitters[n_squitters]: the SELF frames with DF 17 or 18 in list order, the sub-list that is safe to hand to
+ *     adsb_track_table_update / adsb_track_bank_update, which key on bytes[1..3]; uint64 squitter_counts[R] (squitters
+ *     of each receiver) when the call had counts[R]; the adsb_modes_header.
+ * Nothing depends on atomics or scheduling: two runs give the same bytes.
+ */
+#define ADSB_MODES_SELF 0u        /* the frame checks itself (S == 0): address from bytes[1..3] */
+#define ADSB_MODES_KNOWN 1u       /* the address (from the parity, or DF11's with an iid) is a known aircraft's */
+#define ADSB_MODES_UNKNOWN 2u     /* ... is not: a new aircraft, or garbage */
+#define ADSB_MODES_PARITY 3u      /* a self-checking format whose parity fails */
+#define ADSB_MODES_UNSUPPORTED 4u /* a DF this stage does not read */
+#define ADSB_MODES_ALT 0x1u
+#define ADSB_MODES_ALT_METRIC 0x2u
+#define ADSB_MODES_SQUAWK 0x4u
+#define ADSB_MODES_GROUND 0x8u
+#define ADSB_MODES_ALERT 0x10u
+#define ADSB_MODES_SPI 0x20u
+#define ADSB_MODES_CALLSIGN 0x40u
+typedef struct adsb_modes_rec {    /* 32 bytes */
+    uint32_t address;         /* 24 bits; 0 for PARITY and UNSUPPORTED                                 */
+    uint8_t  df;
+    uint8_t  kind;            /* ADSB_MODES_SELF ...                                                   */
+    uint16_t flags;           /* ADSB_MODES_ALT ...                                                    */
+    int32_t  altitude_ft;     /* with ADSB_MODES_ALT                                                   */
+    uint16_t squawk;          /* with ADSB_MODES_SQUAWK                                                */
+    uint8_t  fs, dr, um, iid, ca, ri;
+    char     callsign[8];     /* DF20/21 with BDS 2,0; trust it with ADSB_MODES_CALLSIGN               */
+    uint8_t  reserved[4];     /* 0 */
+} adsb_modes_rec;
+typedef struct adsb_modes_header { /* 64 bytes */
+    uint64_t n, n_self, n_known, n_unknown, n_parity, n_unsupported, n_known_out, n_squitters;
+} adsb_modes_header;
+#ifdef __cplusplus
+static_assert(sizeof(adsb_modes_rec) == 32 && sizeof(adsb_modes_header) == 64, "adsb_modes_rec / adsb_modes_header layout");
+#endif
+/* Resolves.  frames[n] and known_in[n_known_in] each in host memory or in device memory of the ctx's device; counts
+ * host memory, or NULL (then n_receivers is ignored and there are no squitter_counts).  n comes from the host, as for
+ * the other _of calls.  Asynchronous on the ctx's stream once the host arrays are copied.  Buffers are allocated on first
+ * use and grown when needed (may wait for earlier work): per frame 56 bytes of results, and per frame and known address
+ * 36 bytes of sort entries, scan words and known_out plus the sort's temporary storage; a ctx that never calls it
+ * allocates nothing and launches exactly the kernels it launched before.  Replaces the result of an earlier call.
+ * n = 0 is ADSB_OK: known_out = known_in.  ADSB_E_ARG for a NULL ctx, NULL frames with n > 0, NULL known_in with
+ * n_known_in > 0, n_known_in > 2^24, a host known_in that is not ascending, unique and < 2^24, or counts with
+ * n_receivers outside 1..256 or not summing to n; ADSB_E_CAPACITY for n + n_known_in >= 2^32. */
+int adsb_modes_of(adsb_ctx *ctx, const adsb_frame *frames, size_t n, const uint64_t *counts, uint32_t n_receivers,
+                  const uint32_t *known_in, size_t n_known_in);
+/* Waits and copies; each output may be NULL (with capacity 0).  recs receives min(header.n, max_recs) records, known_out
+ * min(header.n_known_out, max_known) addresses, squitters min(header.n_squitters, max_squitters) frames,
+ * squitter_counts n_receivers entries (at most the call's); *header the totals, whatever the capacities.
+ * ADSB_E_STATE before any adsb_modes_of; ADSB_E_ARG for a NULL ctx, a NULL array with a capacity, or n_receivers above
+ * the call's. */
+int adsb_fetch_modes(adsb_ctx *ctx, adsb_modes_rec *recs, size_t max_recs, uint32_t *known_out, size_t max_known,
+                     adsb_frame *squitters, size_t max_squitters, uint64_t *squitter_counts, uint32_t n_receivers,
+                     adsb_modes_header *header);
+/* For device-side consumers; does not synchronise.  The arrays of the last adsb_modes_of in device memory (each
+ * optional; *squitter_counts_dev is NULL when that call had no counts), valid until the next call and ordered on the
+ * ctx's stream behind it: known_out_dev is a valid known_in for the next call.  ADSB_E_STATE before any adsb_modes_of. */
+int adsb_modes_device(adsb_ctx *ctx, const adsb_modes_rec **recs_dev, const uint32_t **known_out_dev,
+                      const adsb_frame **squitters_dev, const uint64_t **squitter_counts_dev, const void **header_dev);
+/* Threads (= frames) per workgroup of the stage's kernels: the size at which they take another path, for tests.  The
+ * result does not depend on it. */
+int adsb_debug_modes_geometry(uint32_t *threads_per_block);
 
 /*
  * Multilaterate: where each correlated message was sent from, solved from the times its receivers heard it.  One small

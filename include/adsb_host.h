@@ -150,6 +150,17 @@ int adsb_host_correlate(const adsb_correlate_cfg *cfg, const adsb_frame *frames,
                         size_t max_msgs, size_t *n_msgs, adsb_frame *frames_out, adsb_reception *recs);
 
 /*
+ * CPU mirror of adsb_modes_of + adsb_fetch_modes (adsb_hip.h, "Mode S replies"): the same records, known_out, squitters
+ * and header from the same program text as the device's, on one core, no device needed.  All arrays host memory.
+ * recs[n] and squitters (room for n) may each be NULL; known_out (room for n + n_known_in, may be NULL) receives
+ * header.n_known_out addresses; squitter_counts[n_receivers] is written when counts is given; *header is optional.
+ * The same argument errors as adsb_modes_of.
+ */
+int adsb_host_modes(const adsb_frame *frames, size_t n, const uint64_t *counts, uint32_t n_receivers,
+                    const uint32_t *known_in, size_t n_known_in, adsb_modes_rec *recs, uint32_t *known_out,
+                    adsb_frame *squitters, uint64_t *squitter_counts, adsb_modes_header *header);
+
+/*
  * CPU mirror of adsb_multilaterate_of (adsb_hip.h, "Multilaterate"): the same fixes and header from the same program text
  * as the device's -- the solver, and the 16 partial sums of every sum over receptions folded in the same butterfly -- on
  * one core, no device needed.  All arrays host memory; rx / n_rx may be NULL / 0 with ADSB_MLAT_TIME_RECEPTION; fixes

@@ -17,7 +17,13 @@ window), prints one '# clock' line per receiver, and solves the fixes from the c
 through the CPU mirror of the per-frame step and a plain merge) and prints, instead of the fixes, one line per aircraft:
 ICAO, callsign, the position it reports, the multilaterated position, the age of that fix at the last message, pdop,
 valid/attempted fixes, checked/disagreeing position messages, and the largest disagreement in metres.
---max-disagreement M (default 1000): how far a reported position may lie from the solved one."""
+--max-disagreement M (default 1000): how far a reported position may lie from the solved one.
+
+--modes also places aircraft that send no ADS-B: the recordings are parsed with their 56-bit frames and without the CRC
+and DF17 filters (ADSB_WIRE_IN_SHORT), every correlated message gets its address from the Mode S stage (adsb_modes_of
+on correlate's frames_out: DF11 all-call replies teach an address, DF0/4/5/16/20/21 replies carry theirs on the parity),
+and only messages whose address is an aircraft's (kinds SELF and KNOWN) are solved and printed, with that address.  Not
+with --sync or --aircraft."""
 import argparse
 import os
 import sys
@@ -111,7 +117,10 @@ def main():
     ap.add_argument("--aircraft", action="store_true", help="one line per aircraft instead of one per fix")
     ap.add_argument("--max-disagreement", type=float, default=1000.0,
                     help="with --aircraft: metres a reported position may lie from the multilaterated one")
+    ap.add_argument("--modes", action="store_true", help="Mode S replies too: short frames, addresses from the Mode S stage")
     args = ap.parse_args()
+    if args.modes and (args.sync or args.aircraft):
+        ap.error("--modes goes with neither --sync nor --aircraft")
 
     import numpy as np
 
@@ -135,7 +144,28 @@ def main():
             table.update_device(d.correlated_device()[1], n_msgs, 0, mlat_ptr=d.mlat_device()[0])
             return table.aircraft()[0], table.mlat()
 
-    if args.host:
+    def resolved(msgs, recs, modes):
+        """The messages whose address is an aircraft's, with their receptions -> (messages, receptions, addresses)"""
+        keep = np.flatnonzero(modes["kind"] <= A.ADSB_MODES_KNOWN)
+        out = msgs[keep].copy()
+        parts = [recs[int(m["first"]):int(m["first"]) + int(m["n_receptions"])] for m in out]
+        out["first"] = np.cumsum([0] + [len(p) for p in parts])[:-1]
+        return out, (np.concatenate(parts) if parts else recs[:0]), modes["address"][keep]
+
+    address = None
+    if args.modes and args.host:
+        win = A.host_wire_parse(data, ends, filter="short")
+        msgs, fout, recs = A.host_correlate(win.frames, win.counts, args.window)
+        msgs, recs, address = resolved(msgs, recs, A.host_modes(fout)[0])
+        fixes, hdr = A.host_multilaterate(sites, msgs, recs, win.rx, **cfg)
+    elif args.modes:
+        with A.AdsbDemod(max_samples=1 << 16, max_out=1024) as d:
+            win = d.wire_in_of(data, ends, filter="short")
+            d.correlate_of_async((d.wire_in_device()[0], len(win.frames)), win.counts, args.window)
+            msgs, _, recs = d.fetch_correlated()
+            msgs, recs, address = resolved(msgs, recs, d.modes_of((d.correlated_device()[1], len(msgs)))[0])
+            fixes, hdr = d.multilaterate_of(sites, msgs, recs, (d.wire_in_device()[1], len(win.frames)), **cfg)
+    elif args.host:
         win = A.host_wire_parse(data, ends, filter=["crc", "df17"])
         msgs, _, recs = A.host_correlate(win.frames, win.counts, args.window)
         if args.sync:
@@ -173,10 +203,11 @@ def main():
     if aircraft is not None:
         newest = float(int(msgs["time"][-1])) * 0.5e-6 if len(msgs) else 0.0
         print(aircraft_lines(A, aircraft[0], aircraft[1], newest), end="")
-    for m, f in zip(msgs, fixes):
+    for k, (m, f) in enumerate(zip(msgs, fixes)):
         if aircraft is None and f["flags"] & A.ADSB_MLAT_VALID:
             t = int(win.rx["ticks"][recs["frame"][m["first"]]]) / 12e6
             icao = int(m["bytes"][1]) << 16 | int(m["bytes"][2]) << 8 | int(m["bytes"][3])
+            icao = icao if address is None else int(address[k])
             print(f"{t:14.6f} {icao:06X} {f['latitude']:10.5f} {f['longitude']:11.5f} {f['height_m']:8.0f} "
                   f"{f['residual_rms_m']:8.1f} {f['hdop']:6.1f} {int(f['n_used']):3d}")
     print(f"# {int(hdr['n_messages'])} messages, {int(hdr['n_attempted'])} attempted, {int(hdr['n_valid'])} valid",

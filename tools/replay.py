@@ -44,7 +44,10 @@ in the whole capture, so the timestamps run on across chunks.  With --beast-in /
 Beast binary or AVR text instead of samples: it is parsed on the device (adsb_wire_in_of) in 64 KiB chunks, the unparsed
 tail of each carried into the next by `consumed`, frame offsets = (timestamp - N) / 6 (--tick-bias N), and everything
 that prints from a frame list works on it: the stream text, --aircraft (with --levels: RSSI from the Beast signal
-bytes), --web, --beast, --avr.  --levels alone needs the samples.  The TEXT has not been compared with a Rust build's (there is no
+bytes), --web, --beast, --avr.  --levels alone needs the samples.  With --modes (and --beast-in / --avr-in) the 56-bit frames are
+parsed too (ADSB_WIRE_IN_SHORT), every frame gets its address on the device (adsb_modes_of, the known addresses carried from
+chunk to chunk), and one line per frame is printed instead: time in seconds, DF, kind (SELF, KNOWN, UNKNOWN, PARITY,
+UNSUPPORTED), address, altitude in feet, squawk and callsign, "-" for a missing value.  The TEXT has not been compared with a Rust build's (there is no
 Rust toolchain); only the values are checked, against the oracle."""
 import argparse
 import json
@@ -194,11 +197,40 @@ def level_lines(d, st, frames, iq, piece=LEVELS_PIECE):
 WIRE_IN_CHUNK = 1 << 16  # bytes of a Beast / AVR capture parsed at a time
 
 
-def read_wire(d, path, wire_format, tick_bias, chunk=WIRE_IN_CHUNK):
+def modes_lines(frames, recs):
+    """--modes: one line per frame from its MODES_DTYPE record."""
+    out = []
+    for f, r in zip(frames, recs):
+        flags = int(r["flags"])
+        alt = f"{int(r['altitude_ft'])}" if flags & A.ADSB_MODES_ALT else "-"
+        squawk = f"{int(r['squawk']):04d}" if flags & A.ADSB_MODES_SQUAWK else "-"
+        call = r["callsign"].decode("ascii", "replace").replace("_", " ").strip() if flags & A.ADSB_MODES_CALLSIGN else "-"
+        addr = f"{int(r['address']):06X}" if int(r["kind"]) <= A.ADSB_MODES_UNKNOWN else "-"
+        out.append(f"{int(f['offset']) * SECONDS_PER_SAMPLE:.6f} DF{int(r['df'])} {A.MODES_KINDS[int(r['kind'])]} {addr} "
+                   f"{alt} {squawk} {call or '-'}\n")
+    return "".join(out)
+
+
+def read_wire(d, path, wire_format, tick_bias, chunk=WIRE_IN_CHUNK, modes=False):
     """--beast-in / --avr-in: (frames, their level records) of a Beast or AVR capture, parsed on the device chunk by
-    chunk; what a chunk leaves unparsed (an incomplete last frame) goes in front of the next."""
+    chunk; what a chunk leaves unparsed (an incomplete last frame) goes in front of the next.  modes: short frames too,
+    and (frames, their MODES_DTYPE records), each chunk resolved where it lies with the known addresses of the chunks
+    before it."""
     import numpy as np
     frames, levels, tail = [np.zeros(0, dtype=A.FRAME_DTYPE)], [np.zeros(0, dtype=A.LEVEL_DTYPE)], b""
+    if modes:
+        recs, known = [np.zeros(0, dtype=A.MODES_DTYPE)], np.zeros(0, dtype=np.uint32)
+        with open(path, "rb") as fh:
+            while True:
+                new = fh.read(chunk)
+                if not new:
+                    break
+                got = d.wire_in_of(tail + new, format=wire_format, tick_bias=tick_bias, filter="short")
+                rec, known = d.modes_of((d.wire_in_device()[0], len(got.frames)), None, known)[:2]
+                frames.append(got.frames)
+                recs.append(rec)
+                tail = (tail + new)[int(got.consumed[0]):]
+        return np.concatenate(frames), np.concatenate(recs)
     with open(path, "rb") as fh:
         while True:
             new = fh.read(chunk)
@@ -246,6 +278,8 @@ def main():
     ap.add_argument("--mlat", action="store_true", help="with --avr: the '@' form, which carries the 12 MHz timestamp")
     ap.add_argument("--beast-in", action="store_true", help="FILE is a Beast binary capture instead of IQ")
     ap.add_argument("--avr-in", action="store_true", help="FILE is an AVR text capture instead of IQ")
+    ap.add_argument("--modes", action="store_true",
+                    help="with --beast-in / --avr-in: short frames too; print DF, kind, address, altitude, squawk, callsign per frame")
     ap.add_argument("--tick-bias", type=int, default=0, metavar="N", help="added to every timestamp (12 MHz ticks, < 2^48)")
     a = ap.parse_args()
     if a.mlat and not a.avr:
@@ -257,6 +291,8 @@ def main():
     if a.beast_in and a.avr_in:
         ap.error("--beast-in and --avr-in exclude each other")
     wire_in = "beast" if a.beast_in else "avr" if a.avr_in else None
+    if a.modes and not wire_in:
+        ap.error("--modes needs --beast-in or --avr-in")
     if wire_in and a.levels and not a.aircraft:
         ap.error("--levels alone needs the samples")
     fmt = a.format or ("c16" if a.file.endswith(".c16") else "u8")
@@ -264,6 +300,12 @@ def main():
     n_max = os.path.getsize(a.file) // (4 if fmt == "c16" else 2)
     with A.AdsbDemod(device=a.device, sample_type=st, max_samples=a.chunk + 240, max_out=a.chunk + 240,
                      host_staging=False) as d:
+        if wire_in and a.modes:
+            frames, recs = read_wire(d, a.file, wire_in, a.tick_bias, modes=True)
+            sys.stdout.write(modes_lines(frames, recs))
+            if a.summary:
+                print(f"{os.path.getsize(a.file)} bytes, {len(frames)} frames", file=sys.stderr)
+            return
         if wire_in:
             frames, parsed_levels = read_wire(d, a.file, wire_in, a.tick_bias)
             n_buf, n_samp = 0, (int(frames["offset"].max()) + A.WINDOW if len(frames) else 0)
