@@ -353,6 +353,32 @@ assert AIRCRAFT_MLAT_DTYPE.itemsize == C.sizeof(AdsbAircraftMlat) == 64
 assert FRAME_MLAT_DTYPE.itemsize == C.sizeof(AdsbFrameMlat) == 16
 
 
+ADSB_TRACK_UNADDRESSED = 0x4        # point flag: the frame's address is not an aircraft's (update_modes)
+ADSB_TRACK_MODES_ALT = 0x1          # adsb_aircraft_modes.flags: the ADSB_MODES_* bit values ...
+ADSB_TRACK_MODES_SQUAWK = 0x4
+ADSB_TRACK_MODES_GROUND = 0x8
+ADSB_TRACK_MODES_ALERT = 0x10
+ADSB_TRACK_MODES_SPI = 0x20
+ADSB_TRACK_MODES_CALLSIGN = 0x40
+ADSB_TRACK_MODES_STATUS = 0x100     # ... fs, ALERT and SPI hold a value
+ADSB_TRACK_MODES_SQUITTER = 0x200   # the aircraft has sent an accepted DF17/18 frame
+
+
+class AdsbAircraftModes(C.Structure):
+    """adsb_aircraft_modes: what an aircraft's Mode S replies say, beside its record (tables with a modes reserve)."""
+    _fields_ = [("altitude_time", C.c_double), ("squawk_time", C.c_double), ("callsign_time", C.c_double),
+                ("altitude_ft", C.c_int32), ("squawk", C.c_uint16), ("flags", C.c_uint16), ("callsign", C.c_char * 8),
+                ("n_replies", C.c_uint32), ("n_allcall", C.c_uint32), ("n_surveillance", C.c_uint32),
+                ("n_airair", C.c_uint32), ("fs", C.c_uint8), ("last_df", C.c_uint8), ("reserved", C.c_uint8 * 6)]
+
+
+AIRCRAFT_MODES_DTYPE = np.dtype([("altitude_time", "<f8"), ("squawk_time", "<f8"), ("callsign_time", "<f8"),
+                                 ("altitude_ft", "<i4"), ("squawk", "<u2"), ("flags", "<u2"), ("callsign", "S8"),
+                                 ("n_replies", "<u4"), ("n_allcall", "<u4"), ("n_surveillance", "<u4"),
+                                 ("n_airair", "<u4"), ("fs", "u1"), ("last_df", "u1"), ("reserved", "u1", (6,))])
+assert AIRCRAFT_MODES_DTYPE.itemsize == C.sizeof(AdsbAircraftModes) == 64
+
+
 class AdsbTrackBankCfg(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("n_receivers", C.c_uint32), ("max_aircraft", C.c_uint32),
                 ("reserved", C.c_uint32), ("max_frames", C.c_uint64), ("seconds_per_sample", C.c_double)]
@@ -485,6 +511,11 @@ PROTOTYPES = {
     "adsb_track_table_fetch_mlat": (C.c_int, [C.c_void_p, _P(AdsbAircraftMlat), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_table_mlat_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "adsb_track_table_fetch_frame_mlat": (C.c_int, [C.c_void_p, _P(AdsbFrameMlat), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_modes_reserve": (C.c_int, [C.c_void_p]),
+    "adsb_track_table_update_modes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                C.c_uint64]),
+    "adsb_track_table_fetch_modes": (C.c_int, [C.c_void_p, _P(AdsbAircraftModes), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_modes_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "adsb_track_bank_fixes_reserve": (C.c_int, [C.c_void_p, _P(AdsbSite)]),
     "adsb_track_bank_fetch_fixes": (C.c_int, [C.c_void_p, _P(AdsbFix), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_bank_fixes_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
@@ -584,6 +615,8 @@ PROTOTYPES = {
     "adsb_host_fix_of": (C.c_int, [_P(AdsbSite), _P(C.c_uint8 * 14), C.c_double, _P(AdsbFix), _P(C.c_uint32)]),
     "adsb_host_track_mlat_of": (C.c_int, [C.c_double, _P(C.c_uint8 * 14), _P(AdsbMlatFix), C.c_double,
                                           _P(AdsbAircraftMlat), _P(C.c_uint32), _P(C.c_float)]),
+    "adsb_host_track_modes_of": (C.c_int, [C.c_void_p, C.c_double, _P(AdsbAircraftModes), _P(C.c_uint32)]),
+    "adsb_host_track_modes_merge": (C.c_int, [_P(AdsbAircraftModes), _P(AdsbAircraftModes)]),
 }
 
 _lib = None

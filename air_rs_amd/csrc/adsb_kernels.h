@@ -377,6 +377,7 @@ struct TrackStoreDev {
     adsb_fix *fix;               // [n_receivers x max_aircraft] beside rec, or null: no fixes reserve (likewise)
     const adsb_site *site;       // [n_receivers] with fix: the site receiver r's frames decode against
     adsb_aircraft_mlat *mlat;    // [n_receivers x max_aircraft] beside rec, or null: no mlat reserve (likewise; tables only)
+    adsb_aircraft_modes *modes;  // [max_aircraft] beside rec, or null: no modes reserve (likewise; tables only)
     // table only
     uint32_t *index;             // [1 << 24]: ICAO -> record slot + 1, 0 = absent
     // bank only
@@ -461,6 +462,24 @@ struct TrackMlatDev {
     size_t temp_bytes;
     double max_disagreement_m;   // the reserve's limit
 };
+// Mode S replies per aircraft (adsb_track_table_modes_reserve; adsb_track_modes.h has the per-frame text and the
+// combine): all of it allocated by the reserve.  One thread per sorted frame writes the scan's operand at its sorted
+// position; one segmented inclusive scan carries, per aircraft, the sorted position + 1 of the later counted frame that
+// writes each field (0 = none), four saturating counts and the squitter bit; one thread per segment tail reads the
+// winning frames' records and merges into store->modes.  Integers only: the scan's shape cannot show.
+struct TrackModesTuple {
+    uint32_t head;               // the operand holds a segment head
+    uint32_t squitter;           // a counted DF17/18 frame
+    uint32_t alt, squawk, callsign, status, ground, any; // newest counted frame of each sort
+    uint32_t n_replies, n_allcall, n_surveillance, n_airair;
+};
+static_assert(sizeof(TrackModesTuple) == 48, "TrackModesTuple: the header's memory figures assume 48 bytes");
+struct TrackModesDev {
+    TrackModesTuple *in;         // [max_frames]: the scan's operands, sorted order
+    TrackModesTuple *scan;       // [max_frames]: the scan's output, sorted order
+    void *temp;                  // the 25-bit sort's, the admission scan's and this scan's scratch
+    size_t temp_bytes;
+};
 struct TrackArgs {
     const adsb_frame *frames;
     const adsb_packet_fields *fields;
@@ -484,6 +503,9 @@ struct TrackArgs {
     const TrackFixDev *fix;      // non-null (with store->fix and store->site): also the per-frame fixes and their merge
     const adsb_mlat_fix *mlat_fixes; // [n] (device), list order: with mlat non-null (and store->mlat), merged into the
     const TrackMlatDev *mlat;    // per-aircraft mlat records; null: the mlat records stay as they are
+    const adsb_modes_rec *modes_recs; // [n] (device), list order: with modes non-null (and store->modes; tables only)
+    const TrackModesDev *modes;  // the list is keyed by the records' addresses (update_modes); null: by bytes[1..3]
+    adsb_packet_fields *modes_fields; // = fields, writable: update_modes makes every other DF a frame of kind "other"
 };
 // expire (adsb_track_table_expire / adsb_track_bank_expire): a record survives unless last_heard < before[receiver]
 constexpr uint32_t kMaxReceivers = 256;
@@ -513,6 +535,9 @@ hipError_t launch_track_fixes_clear(hipStream_t s, adsb_fix *fix, size_t places)
 size_t track_mlat_temp_bytes(size_t n);
 // every mlat record of [0, places) empty: zeros, time NaN (the mlat reserve, and reset)
 hipError_t launch_track_mlat_clear(hipStream_t s, adsb_aircraft_mlat *mlat, size_t places);
+size_t track_modes_temp_bytes(size_t n); // the 25-bit sort, the admission scan and the modes scan
+// every modes record of [0, places) empty: zeros, the three times NaN (the modes reserve, and reset)
+hipError_t launch_track_modes_clear(hipStream_t s, adsb_aircraft_modes *modes, size_t places);
 // out[k] = rec[sum.changed[k]] for k < min(*sum.n_changed, max_n): the changed list's records, gathered on the device
 hipError_t launch_track_changed(hipStream_t s, const TrackRecord *rec, const TrackSumDev &sum, uint32_t max_n,
                                 TrackRecord *out);

@@ -96,6 +96,18 @@
 // position, one segmented inclusive scan (32-byte tuple: integers and one float max) finds every segment's newest valid
 // fix, newest checked frame, greatest disagreement and counts, one thread per segment tail merges into the side record.
 // Admission and expire treat the array as they treat the other two.  Tables only; the templates compile for a bank too.
+//
+// Mode S replies per aircraft (adsb_track_table_modes_reserve; the update_modes form): a fourth side array, one 64-byte
+// adsb_aircraft_modes per record place, and a list keyed by adsb_modes_of's addresses.  Instead of track_keys_kernel, a key
+// kernel of its own reads the frame's adsb_modes_rec: the sort key is the address of an accepted frame and 1 << 24 for
+// every other one (25 sorted bits: the rejected frames form one last segment), and every frame that is not an accepted
+// DF17/18 becomes a frame of kind "other" in the table's fields.  The lookup of such an update gives the last segment no
+// slot (kTrackUntracked, never new), so admission, pairs, summaries and the three merges above skip it as they skip an
+// aircraft the full table turned away, unchanged.  After them: one thread per frame writes its point (UNADDRESSED) and
+// icao where those kernels left the sentinel, and the scan operand of adsb_track_modes.h's contribution at its sorted
+// position; one segmented inclusive scan (48-byte tuple, integers only); one thread per segment tail builds the
+// segment's part from the winning frames' records and merges it into the side record.  Admission and expire treat the
+// array as they treat the other three.  Tables only.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -105,6 +117,7 @@
 #include "adsb_fix.h"
 #include "adsb_kernels.h"
 #include "adsb_track_mlat.h"
+#include "adsb_track_modes.h"
 
 namespace adsbk {
 
@@ -295,6 +308,7 @@ __global__ __launch_bounds__(256) void track_admit_kernel(const uint32_t *skeys,
     if (t.lvl) t.lvl[r] = empty_level();
     if (t.fix) ((FixWords *)t.fix)[r] = fix_empty();
     if (t.mlat) ((MlatWords *)t.mlat)[r] = mlat_empty();
+    if (t.modes) ((ModesWords *)t.modes)[r] = modes_empty();
 }
 
 // bank only: the receiver split clipped to the list (prefix[0] = 0, prefix[k] = n for k >= n_src), as adsb_fetch's
@@ -1006,6 +1020,180 @@ __global__ __launch_bounds__(256) void track_mlat_clear_kernel(MlatWords *mlat, 
     if (p < places) mlat[p] = mlat_empty();
 }
 
+// ---- Mode S replies per aircraft (table with a modes reserve) --------------------------------------------------------
+// update_modes' key kernel, in place of track_keys_kernel: one thread per frame i < n.  The key is the record's address
+// (< 2^24) for an accepted frame and kModesNoAddress for every other; fields[i] gets that address, and unless the frame
+// is an accepted DF17/18 it becomes a frame of kind "other" (the field decode reads bytes[4] >> 3 of any frame as a type
+// code).
+__global__ __launch_bounds__(256) void track_modes_keys_kernel(adsb_packet_fields *fields, const adsb_modes_rec *recs,
+                                                               uint32_t n, uint32_t *keys, uint32_t *vals)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const adsb_modes_rec r = recs[i];
+    const bool accepted = modes_accepted(r);
+    const uint32_t address = r.address & 0xFFFFFFu;
+    fields[i].icao = address;
+    if (!accepted || !modes_squitter(r.df)) {
+        fields[i].msg_kind = 2;
+        fields[i].msg_type = 0;
+    }
+    keys[i] = accepted ? address : kModesNoAddress;
+    vals[i] = i;
+}
+
+// update_modes' lookup, in place of track_lookup_kernel: the same, but the segment of kModesNoAddress is no aircraft
+// (index has 2^24 words and is not read there): no slot, never new
+__global__ __launch_bounds__(256) void track_modes_lookup_kernel(const uint32_t *skeys, uint32_t n, const uint32_t *index,
+                                                                 uint32_t *slot, uint32_t *is_new)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s]; // <= 2^24: track_modes_keys_kernel
+    if (key >= kModesNoAddress) {
+        slot[s] = kTrackUntracked;
+        is_new[s] = 0;
+        return;
+    }
+    const uint32_t idx = index[key];
+    slot[s] = idx;
+    is_new[s] = (idx == 0 && (s == 0 || skeys[s - 1] != key)) ? 1u : 0u;
+}
+
+// One thread per sorted frame s, after the pairs kernel and the other per-frame kernels of this update (svals[s] < n, a
+// permutation of the list).  A frame that is not accepted: the kernels before wrote what they write for an aircraft the
+// table turned away, with the sentinel as icao; here its point becomes UNADDRESSED and every per-frame icao the
+// record's address.  An accepted frame that is no squitter: its frame fix carries the address, not bytes[1..3].  Then
+// the scan's operand: adsb_track_modes.h's contribution of a counted frame, nothing but the head mark otherwise.
+__global__ __launch_bounds__(256) void track_modes_frame_kernel(const adsb_modes_rec *recs, const uint32_t *skeys,
+                                                                const uint32_t *svals, uint32_t n, TrackStoreDev d,
+                                                                adsb_track_point *points, adsb_aircraft_record *sum_out,
+                                                                adsb_frame_fix *fix_out, adsb_frame_mlat *mlat_out,
+                                                                TrackModesTuple *in)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s], i = svals[s];
+    const adsb_modes_rec r = recs[i];
+    TrackModesTuple v{};
+    v.head = (s == 0 || skeys[s - 1] != key) ? 1u : 0u;
+    if (key >= kModesNoAddress) {
+        adsb_track_point pt;
+        pt.latitude = 0.0;
+        pt.longitude = 0.0;
+        pt.icao = r.address;
+        pt.flags = ADSB_TRACK_UNADDRESSED;
+        points[i] = pt;
+        if (sum_out) sum_out[i].icao = r.address;
+        if (fix_out) fix_out[i].icao = r.address;
+        if (mlat_out) mlat_out[i].icao = r.address;
+        in[s] = v;
+        return;
+    }
+    if (fix_out && !modes_squitter(r.df)) fix_out[i].icao = key;
+    if (d.slot[s] != kTrackUntracked) {
+        const uint32_t w = modes_what(r), at = s + 1u;
+        v.squitter = (w & kModesSquitter) ? 1u : 0u;
+        v.alt = (w & kModesAlt) ? at : 0u;
+        v.squawk = (w & kModesSquawk) ? at : 0u;
+        v.callsign = (w & kModesCallsign) ? at : 0u;
+        v.status = (w & kModesStatus) ? at : 0u;
+        v.ground = (w & kModesGround) ? at : 0u;
+        v.any = at;
+        v.n_replies = (w & kModesReply) ? 1u : 0u;
+        v.n_allcall = (w & kModesAllcall) ? 1u : 0u;
+        v.n_surveillance = (w & kModesSurveillance) ? 1u : 0u;
+        v.n_airair = (w & kModesAirAir) ? 1u : 0u;
+    }
+    in[s] = v;
+}
+
+// Segmented: a right operand that holds a segment head starts over; otherwise OR, the later positions (positions ascend,
+// so the later one is the greater one) and saturating sums.  Associative.
+struct ModesOp {
+    __device__ __forceinline__ TrackModesTuple operator()(const TrackModesTuple &l, const TrackModesTuple &r) const
+    {
+        TrackModesTuple o = r;
+        if (!r.head) {
+            o.head = l.head;
+            o.squitter = l.squitter | r.squitter;
+            o.alt = l.alt > r.alt ? l.alt : r.alt;
+            o.squawk = l.squawk > r.squawk ? l.squawk : r.squawk;
+            o.callsign = l.callsign > r.callsign ? l.callsign : r.callsign;
+            o.status = l.status > r.status ? l.status : r.status;
+            o.ground = l.ground > r.ground ? l.ground : r.ground;
+            o.any = l.any > r.any ? l.any : r.any;
+            o.n_replies = sat_add32(l.n_replies, r.n_replies);
+            o.n_allcall = sat_add32(l.n_allcall, r.n_allcall);
+            o.n_surveillance = sat_add32(l.n_surveillance, r.n_surveillance);
+            o.n_airair = sat_add32(l.n_airair, r.n_airair);
+        }
+        return o;
+    }
+};
+
+// One thread per segment tail with a counted frame: the segment's part (adsb_track_modes.h) from the winning frames'
+// records and times, merged into the aircraft's modes record.  Every position is <= n: a sorted position + 1 of this list.
+__global__ __launch_bounds__(256) void track_modes_merge_kernel(const adsb_frame *frames, const adsb_modes_rec *recs,
+                                                                const uint32_t *skeys, const uint32_t *svals, uint32_t n,
+                                                                double seconds_per_sample, uint64_t sample_base,
+                                                                TrackStoreDev d, const TrackModesTuple *scan)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s];
+    if (s + 1 != n && skeys[s + 1] == key) return;
+    const uint32_t slot = d.slot[s];
+    if (slot == kTrackUntracked) return; // turned away, or the segment of the frames that are not accepted
+    const TrackModesTuple w = scan[s];
+    if (!w.any) return; // nothing counted: the record stays
+    // the winning frames' records where they lie (null: the segment has no such frame), and the three times
+    const adsb_modes_rec *r_alt = w.alt ? recs + svals[w.alt - 1] : nullptr;
+    const adsb_modes_rec *r_squawk = w.squawk ? recs + svals[w.squawk - 1] : nullptr;
+    const adsb_modes_rec *r_callsign = w.callsign ? recs + svals[w.callsign - 1] : nullptr;
+    const adsb_modes_rec *r_status = w.status ? recs + svals[w.status - 1] : nullptr;
+    const adsb_modes_rec *r_ground = w.ground ? recs + svals[w.ground - 1] : nullptr;
+    const double t_alt = w.alt ? frame_time(frames, svals[w.alt - 1], sample_base, seconds_per_sample) : 0.0;
+    const double t_squawk = w.squawk ? frame_time(frames, svals[w.squawk - 1], sample_base, seconds_per_sample) : 0.0;
+    const double t_callsign = w.callsign ? frame_time(frames, svals[w.callsign - 1], sample_base, seconds_per_sample) : 0.0;
+    ModesCounts c;
+    c.n_replies = w.n_replies;
+    c.n_allcall = w.n_allcall;
+    c.n_surveillance = w.n_surveillance;
+    c.n_airair = w.n_airair;
+    c.squitter = w.squitter;
+    const adsb_aircraft_modes part = modes_part(c, recs + svals[w.any - 1], r_alt, t_alt, r_squawk, t_squawk, r_callsign,
+                                                t_callsign, r_status, r_ground);
+    ModesWords words = ((const ModesWords *)d.modes)[slot - 1];
+    adsb_aircraft_modes a;
+    __builtin_memcpy(&a, &words, sizeof(a));
+    modes_merge(a, part);
+    __builtin_memcpy(&words, &a, sizeof(a));
+    ((ModesWords *)d.modes)[slot - 1] = words;
+}
+
+hipError_t launch_modes_merge(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d)
+{
+    const TrackModesDev &mo = *a.modes;
+    const dim3 grid((a.n + 255) / 256);
+    hipLaunchKernelGGL(track_modes_frame_kernel, grid, dim3(256), 0, st, a.modes_recs, (const uint32_t *)a.skeys,
+                       (const uint32_t *)a.svals, a.n, d, a.points, a.sum ? a.sum->out : nullptr,
+                       (a.fix && d.fix) ? a.fix->out : nullptr, (a.mlat && d.mlat) ? a.mlat->out : nullptr, mo.in);
+    size_t tb = mo.temp_bytes;
+    hipError_t e = rocprim::inclusive_scan(mo.temp, tb, (const TrackModesTuple *)mo.in, mo.scan, (size_t)a.n, ModesOp(), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(track_modes_merge_kernel, grid, dim3(256), 0, st, a.frames, a.modes_recs,
+                       (const uint32_t *)a.skeys, (const uint32_t *)a.svals, a.n, a.seconds_per_sample, a.sample_base, d,
+                       (const TrackModesTuple *)mo.scan);
+    return hipSuccess;
+}
+
+__global__ __launch_bounds__(256) void track_modes_clear_kernel(ModesWords *modes, uint64_t places)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < places) modes[p] = modes_empty();
+}
+
 // expire, 1: keep[g] = 1 for a record in use whose last frame is not older than the cut (last_heard < before evicts).
 // Record g is slot i of receiver r (a table: r = 0).  Slot 0 stages the old size where the compaction kernel reads it
 // (size_next[r]), since that kernel writes the new one; the pairs kernel of an update has consumed its own staging before
@@ -1060,6 +1248,7 @@ __global__ __launch_bounds__(256) void track_expire_compact_kernel(TrackStoreDev
     if (d.lvl) d.lvl[g] = d.lvl[base + lo];
     if (d.fix) ((FixWords *)d.fix)[g] = ((const FixWords *)d.fix)[base + lo];
     if (d.mlat) ((MlatWords *)d.mlat)[g] = ((const MlatWords *)d.mlat)[base + lo];
+    if (d.modes) ((ModesWords *)d.modes)[g] = ((const ModesWords *)d.modes)[base + lo];
     if (!kBank) d.index[moved.a.icao] = i + 1u;
 }
 
@@ -1443,6 +1632,27 @@ size_t track_mlat_temp_bytes(size_t n)
     return scan_bytes + 256;
 }
 
+size_t track_modes_temp_bytes(size_t n)
+{
+    size_t sort_bytes = 0, excl_bytes = 0, scan_bytes = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                    (const uint32_t *)nullptr, (uint32_t *)nullptr, n, 0, 25, (hipStream_t)0);
+    (void)rocprim::exclusive_scan(nullptr, excl_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr, 0u, n,
+                                  rocprim::plus<uint32_t>(), (hipStream_t)0);
+    (void)rocprim::inclusive_scan(nullptr, scan_bytes, (const TrackModesTuple *)nullptr, (TrackModesTuple *)nullptr, n,
+                                  ModesOp(), (hipStream_t)0);
+    const size_t most = sort_bytes > excl_bytes ? sort_bytes : excl_bytes;
+    return (most > scan_bytes ? most : scan_bytes) + 256;
+}
+
+hipError_t launch_track_modes_clear(hipStream_t st, adsb_aircraft_modes *modes, size_t places)
+{
+    if (places == 0) return hipSuccess;
+    hipLaunchKernelGGL(track_modes_clear_kernel, dim3((uint32_t)((places + 255) / 256)), dim3(256), 0, st,
+                       (ModesWords *)modes, (uint64_t)places);
+    return hipGetLastError();
+}
+
 hipError_t launch_track_mlat_clear(hipStream_t st, adsb_aircraft_mlat *mlat, size_t places)
 {
     if (places == 0) return hipSuccess;
@@ -1497,6 +1707,10 @@ hipError_t track_tail(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d
         if (a.mlat && d.mlat) e = launch_mlat_merge<K>(st, a, d); // needs d.slot, the frame bytes and the fixes only
         if (e != hipSuccess) return e;
         if (a.sum) e = launch_frame_summaries<K>(st, a, d); // before the merge
+        if constexpr (K == TrackKind::kTable) {
+            if (e != hipSuccess) return e;
+            if (a.modes && d.modes) e = launch_modes_merge(st, a, d); // after every kernel that writes a per-frame icao
+        }
     } else {
         size_t tb = a.temp_bytes;
         e = rocprim::exclusive_scan(a.temp, tb, (const uint32_t *)tail_flag, tail_pos, 0u, (size_t)n,
@@ -1531,13 +1745,22 @@ hipError_t launch_track(hipStream_t st, const TrackArgs &a)
         hipLaunchKernelGGL(track_bank_admit_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, d);
         return track_tail<TrackKind::kBank>(st, a, d);
     }
-    hipLaunchKernelGGL(track_keys_kernel, dim3(blocks), dim3(256), 0, st, a.fields, n, a.keys, a.vals);
+    const bool modes = a.kind == TrackKind::kTable && a.modes && d.modes; // update_modes: keyed by the records' addresses
+    if (modes)
+        hipLaunchKernelGGL(track_modes_keys_kernel, dim3(blocks), dim3(256), 0, st, a.modes_fields, a.modes_recs, n,
+                           a.keys, a.vals);
+    else
+        hipLaunchKernelGGL(track_keys_kernel, dim3(blocks), dim3(256), 0, st, a.fields, n, a.keys, a.vals);
     hipError_t e = rocprim::radix_sort_pairs(a.temp, tb, (const uint32_t *)a.keys, a.skeys, (const uint32_t *)a.vals,
-                                             a.svals, (size_t)n, 0, 24, st);
+                                             a.svals, (size_t)n, 0, modes ? 25 : 24, st);
     if (e != hipSuccess) return e;
     if (!store) return track_tail<TrackKind::kLaunch>(st, a, d);
-    hipLaunchKernelGGL(track_lookup_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, d.index, d.slot,
-                       a.keys /* reused: is_new */);
+    if (modes)
+        hipLaunchKernelGGL(track_modes_lookup_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, d.index, d.slot,
+                           a.keys /* reused: is_new */);
+    else
+        hipLaunchKernelGGL(track_lookup_kernel, dim3(blocks), dim3(256), 0, st, a.skeys, n, d.index, d.slot,
+                           a.keys /* reused: is_new */);
     tb = a.temp_bytes;
     e = rocprim::exclusive_scan(a.temp, tb, (const uint32_t *)a.keys, a.vals /* reused: rank */, 0u, (size_t)n,
                                 rocprim::plus<uint32_t>(), st);

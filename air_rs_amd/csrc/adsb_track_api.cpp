@@ -14,6 +14,7 @@
 #include "adsb_fix.h"
 #include "adsb_scratch.h"
 #include "adsb_track_mlat.h"
+#include "adsb_track_modes.h"
 
 using adsbk::TrackKind;
 using adsbk::TrackRecord;
@@ -112,7 +113,7 @@ struct TrackStore {
     uint32_t n_receivers = 0, max_aircraft = 0; // max_aircraft: per receiver
     // One block of device memory per lifetime, carved into the arrays below (adsb_scratch.h): the store's own from
     // create to destroy, and one per reserve.  Every device pointer of the store points into one of them.
-    DevBuf<char> mem, sum_mem, lvl_mem, fix_mem, mlat_mem;
+    DevBuf<char> mem, sum_mem, lvl_mem, fix_mem, mlat_mem, modes_mem;
     adsbk::TrackStoreDev dev{};     // records [R x max_aircraft], slot [max_frames]; index [2^24] or hash, prefix, scan words
     uint32_t *words = nullptr;      // [3R]: size, flags, size_next (dev.size / dev.flags / dev.size_next)
     uint32_t *u32 = nullptr;        // 4 x [max_frames]: keys, vals, sorted keys, sorted vals
@@ -144,6 +145,10 @@ struct TrackStore {
     adsb_mlat_fix *mlat_pinned = nullptr; // [max_frames]: pinned staging of that copy (s.copied covers it too)
     uint32_t mlat_n = 0;                  // frames of the last update_mlat
     bool mlat_updated = false;            // an update_mlat ran since the reserve (and since the last reset)
+    // Mode S replies per aircraft (adsb_track_table_modes_reserve): all of it made by the reserve; dev.modes null = none
+    adsbk::TrackModesDev modes{};
+    adsb_modes_rec *modes_recs = nullptr;   // [max_frames]: device copy of a host recs array
+    adsb_modes_rec *modes_pinned = nullptr; // [max_frames]: pinned staging of that copy (s.copied covers it too)
 
     size_t places() const { return (size_t)n_receivers * max_aircraft; }
 };
@@ -212,6 +217,16 @@ static void store_mlat_drop(TrackStore &s)
     s.mlat_fixes = nullptr;
 }
 
+// The modes reserve undone, under the same condition.
+static void store_modes_drop(TrackStore &s)
+{
+    drop(s.modes_mem);
+    pinned_free(s.modes_pinned);
+    s.dev.modes = nullptr;
+    s.modes = {};
+    s.modes_recs = nullptr;
+}
+
 // Sizes, and the store's own block: what a table and a bank share, then what each kind adds (a bank has set
 // dev.hash_mask).  false: an allocation failed (the caller releases what was made)
 static bool store_alloc(TrackStore &s, adsb_ctx *c, TrackKind kind, uint32_t n_receivers, uint32_t max_aircraft, uint64_t max_frames,
@@ -267,6 +282,7 @@ static void store_release(TrackStore &s)
     drop(s.lvl_mem);
     drop(s.fix_mem);
     drop(s.mlat_mem);
+    store_modes_drop(s);
     pinned_free(s.pinned);
     pinned_free(s.lvl_pinned);
     pinned_free(s.mlat_pinned);
@@ -285,6 +301,7 @@ static int store_reset(TrackStore *s)
     HIPCHK(hipMemsetAsync(s->words, 0, sizeof(uint32_t) * 3 * s->n_receivers, s->ctx->aux));
     if (s->dev.fix) HIPCHK(adsbk::launch_track_fixes_clear(s->ctx->aux, s->dev.fix, s->places()));
     if (s->dev.mlat) HIPCHK(adsbk::launch_track_mlat_clear(s->ctx->aux, s->dev.mlat, s->places()));
+    if (s->dev.modes) HIPCHK(adsbk::launch_track_modes_clear(s->ctx->aux, s->dev.modes, s->places()));
     s->mlat_updated = false;
     s->n_points = 0;
     s->updated = false;
@@ -332,6 +349,14 @@ static int store_stage_mlat(TrackStore &s, const adsb_mlat_fix *host, size_t n)
     return ADSB_OK;
 }
 
+// The same for a host recs array (update_modes), under the same event
+static int store_stage_modes(TrackStore &s, const adsb_modes_rec *host, size_t n)
+{
+    std::memcpy(s.modes_pinned, host, sizeof(adsb_modes_rec) * n);
+    HIPCHK(hipMemcpyAsync(s.modes_recs, s.modes_pinned, sizeof(adsb_modes_rec) * n, hipMemcpyHostToDevice, s.ctx->aux));
+    return ADSB_OK;
+}
+
 // The bookkeeping every update starts with (an empty one too: no summaries, an empty changed list); false: n == 0,
 // nothing to launch
 static bool store_begin_update(TrackStore &s, size_t n)
@@ -344,10 +369,12 @@ static bool store_begin_update(TrackStore &s, size_t n)
 
 // Enqueues field decode and the tracker kernels over n frames at `list` (device), after the ctx's ordering pass and
 // field decode (same stream); dev: s.dev, or a bank's copy of it with this update's receiver split; levels (device,
-// or null): also the level merge; mlat_fixes (device, or null): also the mlat merge
+// or null): also the level merge; mlat_fixes (device, or null): also the mlat merge; recs (device, or null): the list is
+// keyed by the records' addresses and the modes merge runs too (update_modes), with the modes reserve's scratch, which
+// holds the 25-bit sort
 static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t sample_base,
                      const adsbk::TrackStoreDev &dev, const adsb_frame_level *levels = nullptr,
-                     const adsb_mlat_fix *mlat_fixes = nullptr)
+                     const adsb_mlat_fix *mlat_fixes = nullptr, const adsb_modes_rec *recs = nullptr)
 {
     HIPCHK(adsbk::launch_decode_fields(s.ctx->aux, list, nullptr, (uint32_t)n, s.fields));
     adsbk::TrackArgs a = track_args(s.kind, list, s.fields, n, s.seconds_per_sample, s.u32, (size_t)s.max_frames,
@@ -360,6 +387,13 @@ static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t s
     a.fix = dev.fix ? &s.fix : nullptr;
     a.mlat_fixes = mlat_fixes;
     a.mlat = mlat_fixes ? &s.mlat : nullptr;
+    if (recs) {
+        a.modes_recs = recs;
+        a.modes = &s.modes;
+        a.modes_fields = s.fields;
+        a.temp = s.modes.temp;
+        a.temp_bytes = s.modes.temp_bytes;
+    }
     HIPCHK(adsbk::launch_track(s.ctx->aux, a));
     return ADSB_OK;
 }
@@ -372,6 +406,7 @@ static const adsb_frame_fix *frame_fixes_of(TrackStore &s) { return s.dev.fix &&
 static const adsb_aircraft_level *levels_of(TrackStore &s) { return s.dev.lvl; }
 static const adsb_fix *fixes_of(TrackStore &s) { return s.dev.fix; }
 static const adsb_aircraft_mlat *mlat_of(TrackStore &s) { return s.dev.mlat; }
+static const adsb_aircraft_modes *modes_of(TrackStore &s) { return s.dev.modes; }
 
 template <class T>
 static int store_device(TrackStore *s, const T *of(TrackStore &), const T **dev)
@@ -652,6 +687,31 @@ static int store_mlat_reserve(TrackStore *st, double max_disagreement_m)
     return ADSB_OK;
 }
 
+// ---- Mode S replies per aircraft --------------------------------------------------------------------------------------
+// Waits for the device (the clear); a second reserve keeps what the first one made
+static int store_modes_reserve(TrackStore *st)
+{
+    HIPCHK(hipSetDevice(st->ctx->cfg.device));
+    if (st->dev.modes) return ADSB_OK;
+    const size_t nf = (size_t)st->max_frames;
+    st->modes.temp_bytes = adsbk::track_modes_temp_bytes(nf);
+    const int rc = carve_block(st->ctx, st->modes_mem, [&](Carve &k) {
+        st->dev.modes = k.take<adsb_aircraft_modes>(st->places());
+        st->modes.in = k.take<adsbk::TrackModesTuple>(nf);
+        st->modes.scan = k.take<adsbk::TrackModesTuple>(nf);
+        st->modes.temp = k.take<char>(st->modes.temp_bytes);
+        st->modes_recs = k.take<adsb_modes_rec>(nf);
+    });
+    if (rc != ADSB_OK || !pinned_make(st->modes_pinned, nf) ||
+        adsbk::launch_track_modes_clear(st->ctx->aux, st->dev.modes, st->places()) != hipSuccess ||
+        hipStreamSynchronize(st->ctx->aux) != hipSuccess) {
+        (void)hipGetLastError();
+        store_modes_drop(*st);
+        return ADSB_E_NOMEM;
+    }
+    return ADSB_OK;
+}
+
 // ---- persistent aircraft table (adsb_track_table_*) ------------------------------------------------------------------
 static void track_table_free(adsb_track_table *t)
 {
@@ -681,9 +741,11 @@ extern "C" void adsb_track_table_destroy(adsb_track_table *t)
     if (t) track_table_free(t);
 }
 
-// levels: null for the plain update; fixes: null unless update_mlat
+// levels: null for the plain update; fixes: null unless update_mlat (or update_modes with fixes); recs: null unless
+// update_modes
 static int track_table_update(adsb_track_table *t, const adsb_frame *frames, const adsb_frame_level *levels, size_t n,
-                              uint64_t sample_base, const adsb_mlat_fix *fixes = nullptr)
+                              uint64_t sample_base, const adsb_mlat_fix *fixes = nullptr,
+                              const adsb_modes_rec *recs = nullptr)
 {
     if (n > t->max_frames) return ADSB_E_CAPACITY;
     adsb_ctx *c = t->ctx;
@@ -695,19 +757,21 @@ static int track_table_update(adsb_track_table *t, const adsb_frame *frames, con
     if (!store_begin_update(*t, n)) return ADSB_OK;
     const adsb_frame *list = frames;
     const bool frames_host = !in_device_memory(c, frames), levels_host = levels && !in_device_memory(c, levels);
-    const bool fixes_host = fixes && !in_device_memory(c, fixes);
-    if (frames_host || levels_host || fixes_host) {
+    const bool fixes_host = fixes && !in_device_memory(c, fixes), recs_host = recs && !in_device_memory(c, recs);
+    if (frames_host || levels_host || fixes_host || recs_host) {
         HIPCHK(hipEventSynchronize(t->copied)); // the previous update's copies out of the staging have finished
         int rc = frames_host ? store_stage_frames(*t, frames, n) : ADSB_OK;
         if (rc == ADSB_OK && levels_host) rc = store_stage_levels(*t, levels, n);
         if (rc == ADSB_OK && fixes_host) rc = store_stage_mlat(*t, fixes, n);
+        if (rc == ADSB_OK && recs_host) rc = store_stage_modes(*t, recs, n);
         if (rc != ADSB_OK) return rc;
         HIPCHK(hipEventRecord(t->copied, c->aux));
         if (frames_host) list = t->frames;
         if (levels_host) levels = t->lvl_frames;
         if (fixes_host) fixes = t->mlat_fixes;
+        if (recs_host) recs = t->modes_recs;
     }
-    return store_run(*t, list, n, sample_base, t->dev, levels, fixes);
+    return store_run(*t, list, n, sample_base, t->dev, levels, fixes, recs);
 }
 
 extern "C" int adsb_track_table_update(adsb_track_table *t, const adsb_frame *frames, size_t n, uint64_t sample_base)
@@ -784,6 +848,36 @@ extern "C" int adsb_track_table_fetch_mlat(adsb_track_table *t, adsb_aircraft_ml
 extern "C" int adsb_track_table_mlat_device(adsb_track_table *t, const adsb_aircraft_mlat **dev)
 {
     return store_device(t, mlat_of, dev);
+}
+
+extern "C" int adsb_track_table_modes_reserve(adsb_track_table *t)
+{
+    if (!t) return ADSB_E_ARG;
+    return store_modes_reserve(t);
+}
+
+extern "C" int adsb_track_table_update_modes(adsb_track_table *t, const adsb_frame *frames, const adsb_modes_rec *recs,
+                                             const adsb_mlat_fix *fixes, const adsb_frame_level *levels, size_t n,
+                                             uint64_t sample_base)
+{
+    if (!t || (!frames && n) || (!recs && n)) return ADSB_E_ARG;
+    if (!t->dev.modes || (fixes && !t->dev.mlat) || (levels && !t->dev.lvl)) return ADSB_E_STATE;
+    if (n > t->max_frames) return ADSB_E_CAPACITY;
+    if (n == 0 && fixes) { // nothing to launch: the last update with fixes has an empty list
+        t->mlat_n = 0;
+        t->mlat_updated = true;
+    }
+    return track_table_update(t, frames, n ? levels : nullptr, n, sample_base, n ? fixes : nullptr, n ? recs : nullptr);
+}
+
+extern "C" int adsb_track_table_fetch_modes(adsb_track_table *t, adsb_aircraft_modes *out, size_t max, size_t *n)
+{
+    return store_fetch_side(t, modes_of, out, max, n);
+}
+
+extern "C" int adsb_track_table_modes_device(adsb_track_table *t, const adsb_aircraft_modes **dev)
+{
+    return store_device(t, modes_of, dev);
 }
 
 // Waits.  As store_fetch_frames, over the last update_mlat's list (a plain update in between leaves it alone)

@@ -30,6 +30,7 @@ LEVEL_PULSE_SAMPLES, LEVEL_QUIET_SAMPLES = 116, 124  # of a frame's 240: what si
 
 SITE, FIX_DTYPE, FRAME_FIX_DTYPE = L.SITE, L.FIX_DTYPE, L.FRAME_FIX_DTYPE  # fixes_reserve / fixes / frame_fixes
 AIRCRAFT_MLAT_DTYPE, FRAME_MLAT_DTYPE = L.AIRCRAFT_MLAT_DTYPE, L.FRAME_MLAT_DTYPE  # TrackTable.mlat / frame_mlat
+AIRCRAFT_MODES_DTYPE = L.AIRCRAFT_MODES_DTYPE                                        # TrackTable.modes
 WINDOW = 240  # 16 preamble + 112*2 samples (reference src/adsb.rs:98)
 
 
@@ -118,6 +119,29 @@ def host_track_mlat_of(max_disagreement_m, frame_bytes, fix, time=0.0):
                                              out.ctypes.data_as(C.POINTER(L.AdsbAircraftMlat)), C.byref(flags),
                                              C.byref(dis)), "adsb_host_track_mlat_of")
     return out[0], flags.value, np.float32(dis.value)
+
+
+def host_track_modes_of(rec, time=0.0):
+    """adsb_host_track_modes_of, the CPU mirror of a modes reserve's per-frame step: (AIRCRAFT_MODES_DTYPE record of an
+    aircraft whose only counted frame is the one with the MODES_DTYPE record `rec`, heard at `time`; whether the frame
+    is accepted).  Needs no device."""
+    r = np.zeros(1, dtype=MODES_DTYPE)
+    r[0] = rec
+    out = np.zeros(1, dtype=AIRCRAFT_MODES_DTYPE)
+    ok = C.c_uint32()
+    L.check(L.load().adsb_host_track_modes_of(r.ctypes.data, float(time), out.ctypes.data_as(C.POINTER(L.AdsbAircraftModes)),
+                                              C.byref(ok)), "adsb_host_track_modes_of")
+    return out[0].copy(), bool(ok.value)
+
+
+def host_track_modes_merge(into, later):
+    """adsb_host_track_modes_merge, the combine of a modes reserve: the AIRCRAFT_MODES_DTYPE record `into` followed by
+    `later`, a record of the frames that come after into's.  Needs no device."""
+    a, b = np.zeros(1, dtype=AIRCRAFT_MODES_DTYPE), np.zeros(1, dtype=AIRCRAFT_MODES_DTYPE)
+    a[0], b[0] = into, later
+    P = C.POINTER(L.AdsbAircraftModes)
+    L.check(L.load().adsb_host_track_modes_merge(a.ctypes.data_as(P), b.ctypes.data_as(P)), "adsb_host_track_modes_merge")
+    return a[0].copy()
 
 
 WIRE_FORMATS = {"beast": L.ADSB_WIRE_BEAST, "avr": L.ADSB_WIRE_AVR, "avr_mlat": L.ADSB_WIRE_AVR_MLAT}
@@ -914,6 +938,14 @@ class AdsbDemod:
         msgs = msgs[:n_msgs.value].copy()
         return msgs, frames_of_messages(msgs), recs[:n_recs.value].copy()
 
+    def correlated_counts(self):
+        """(messages, receptions) of the last correlate call: waits for it and reads the two counts, nothing else; the
+        lists stay where they are (correlated_device())."""
+        n_msgs, n_recs = C.c_size_t(), C.c_size_t()
+        L.check(self._lib.adsb_fetch_correlated(self._h, None, 0, C.byref(n_msgs), None, 0, C.byref(n_recs)),
+                "adsb_fetch_correlated")
+        return n_msgs.value, n_recs.value
+
     def correlated_device(self):
         """adsb_correlated_device: device addresses (messages, frames, receptions, {u64 n_messages, u64 n_receptions});
         no synchronisation."""
@@ -1410,13 +1442,26 @@ class TrackTable(_TrackStore):
         self._open(dem, L.AdsbTrackTableCfg(L.ADSB_ABI_VERSION, int(max_aircraft), int(max_frames),
                                             float(seconds_per_sample)), max_frames)
 
-    def update(self, frames, sample_base=0, levels=None, mlat=None):
+    def update(self, frames, sample_base=0, levels=None, mlat=None, modes=None):
         """frames: FRAME_DTYPE array in ascending offset (host); packet time = (sample_base + offset) x sps.  levels
         (after levels_reserve): the frames' LEVEL_DTYPE records (host), merged into the aircraft's level records.  mlat
-        (after mlat_reserve): the frames' MLAT_FIX_DTYPE fixes (host), merged into the aircraft's mlat records."""
+        (after mlat_reserve): the frames' MLAT_FIX_DTYPE fixes (host), merged into the aircraft's mlat records.  modes
+        (after modes_reserve): the frames' MODES_DTYPE records (host); the list is then keyed by their addresses, a
+        frame that is not SELF or KNOWN touches nothing, and the aircraft's modes records take the replies."""
         frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
         ptr = frames.ctypes.data if len(frames) else None
-        if mlat is not None:
+        if modes is not None:
+            recs = np.ascontiguousarray(modes, dtype=MODES_DTYPE)
+            if len(recs) != len(frames):
+                raise ValueError(f"modes: {len(recs)} records for {len(frames)} frames")
+            fixes = None if mlat is None else np.ascontiguousarray(mlat, dtype=MLAT_FIX_DTYPE)
+            if fixes is not None and len(fixes) != len(frames):
+                raise ValueError(f"mlat: {len(fixes)} fixes for {len(frames)} frames")
+            keep, lptr = (None, None) if levels is None else self._host_levels(levels, len(frames))
+            self._call("update_modes", ptr, recs.ctypes.data if len(recs) else None,
+                       fixes.ctypes.data if fixes is not None and len(fixes) else None, lptr, len(frames),
+                       int(sample_base))
+        elif mlat is not None:
             fixes = np.ascontiguousarray(mlat, dtype=MLAT_FIX_DTYPE)
             if len(fixes) != len(frames):
                 raise ValueError(f"mlat: {len(fixes)} fixes for {len(frames)} frames")
@@ -1428,12 +1473,15 @@ class TrackTable(_TrackStore):
             keep, lptr = self._host_levels(levels, len(frames))
             self._call("update_levels", ptr, lptr, len(frames), int(sample_base))
 
-    def update_device(self, dev_ptr, n, sample_base=0, levels_ptr=None, mlat_ptr=None):
+    def update_device(self, dev_ptr, n, sample_base=0, levels_ptr=None, mlat_ptr=None, modes_ptr=None):
         """n frames at dev_ptr in the ctx device's memory (e.g. result_device() after fetch_counts()).  levels_ptr
         (after levels_reserve): their n level records, on the device (e.g. levels_device()) or a host address.  mlat_ptr
         (after mlat_reserve): their n adsb_mlat_fix records, on the device (e.g. mlat_device()[0]) or a host address;
-        every address may be a host one too, each on its own."""
-        if mlat_ptr is not None:
+        every address may be a host one too, each on its own.  modes_ptr (after modes_reserve): their n adsb_modes_rec
+        records (e.g. modes_device()[0]); the update is then update_modes."""
+        if modes_ptr is not None:
+            self._call("update_modes", dev_ptr, modes_ptr, mlat_ptr, levels_ptr, int(n), int(sample_base))
+        elif mlat_ptr is not None:
             self._call("update_mlat", dev_ptr, mlat_ptr, levels_ptr, int(n), int(sample_base))
         elif levels_ptr is None:
             self._call("update", dev_ptr, int(n), int(sample_base))
@@ -1464,6 +1512,22 @@ class TrackTable(_TrackStore):
         synchronisation."""
         dev = C.c_void_p()
         self._call("mlat_device", C.byref(dev))
+        return dev.value
+
+    def modes_reserve(self):
+        """adsb_track_table_modes_reserve: one AIRCRAFT_MODES_DTYPE record beside every aircraft record, which an update
+        given `modes` merges the frames' Mode S records into."""
+        self._call("modes_reserve")
+
+    def modes(self):
+        """AIRCRAFT_MODES_DTYPE records (what each aircraft's Mode S replies say), aligned with aircraft()[0]."""
+        return self._fetch("fetch_modes", [AIRCRAFT_MODES_DTYPE])[0]
+
+    def modes_device(self):
+        """Device address of the modes records, one per record place in slot order (as levels_device); no
+        synchronisation."""
+        dev = C.c_void_p()
+        self._call("modes_device", C.byref(dev))
         return dev.value
 
     def fixes_reserve(self, site):

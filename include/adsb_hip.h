@@ -1532,6 +1532,99 @@ int adsb_track_table_mlat_device(adsb_track_table *table, const adsb_aircraft_ml
 int adsb_track_table_fetch_frame_mlat(adsb_track_table *table, adsb_frame_mlat *out, size_t max, size_t *n);
 
 /*
+ * Mode S replies per aircraft.  adsb_modes_of gives every frame of a list its address and kind; with a modes reserve a
+ * TABLE takes the whole list, keyed by that address instead of bytes[1..3], so an aircraft that only answers
+ * interrogations (DF0/4/5/11/16/20/21) gets a record, a place for its multilaterated fix, and one 64-byte
+ * adsb_aircraft_modes beside its record with what its replies say.  Correlate's frames, adsb_modes_of's records and the
+ * solver's fixes line up index for index in device memory; update_modes takes the three.  Tables only: a bank has no
+ * such entry point and behaves as before (its 32-bit sort key, receiver << 24 | icao, has no spare bit for "no address"
+ * at 256 receivers).
+ *
+ * ACCEPTED  Frame j is accepted iff recs[j].kind is ADSB_MODES_SELF or ADSB_MODES_KNOWN; its aircraft is
+ *   recs[j].address & 0xFFFFFF.  The decision is by kind, never by the address value: address 0 from known_in is an
+ *   aircraft, a PARITY record (whose address is 0 too) is none.
+ * NOT ACCEPTED (UNKNOWN, PARITY, UNSUPPORTED)  The frame touches no record, no side record, no count, no last_heard and
+ *   no changed-list entry, never admits an aircraft and never sets ADSB_TRACK_TABLE_FULL.  Its point has icao =
+ *   recs[j].address and flags exactly ADSB_TRACK_UNADDRESSED; its per-frame summary, frame fix and frame mlat are what
+ *   an UNTRACKED frame's are, with that icao.  Garbage cannot create aircraft.
+ * MAIN RECORD  An accepted frame with DF 17 or 18 is exactly what adsb_track_table_update makes of it (for a SELF frame
+ *   the address is bytes[1..3]).  An accepted frame of any other DF is keyed by its address and is a frame of kind
+ *   "other": n_frames + 1 and last_heard, nothing else, whatever bytes[4..] look like: no identification, position or
+ *   velocity message to the pair walk, the summaries, the single-message fix (its adsb_frame_fix carries the address as
+ *   icao and nothing else) or the mlat check.  With fixes, its valid fix becomes the aircraft's kept mlat fix, as for
+ *   any counted frame.
+ * ADMISSION  An accepted frame of an address the table does not hold is admitted by the ascending-address rule together
+ *   with the list's other new addresses; turned away by a full table it is ADSB_TRACK_UNTRACKED (not UNADDRESSED).
+ * COUNTED  A frame is counted for the side record iff it is accepted and its point is not UNTRACKED.  Per counted
+ *   frame: DF17/18 sets SQUITTER; any other DF adds 1 to n_replies and also to n_allcall (DF11), n_surveillance
+ *   (DF4/5/20/21) or n_airair (DF0/16), all saturating at 2^32 - 1.  last_df is the newest counted frame's df.
+ *   altitude_ft, altitude_time and ALT come from the newest counted frame with ADSB_MODES_ALT; squawk, squawk_time and
+ *   SQUAWK likewise with ADSB_MODES_SQUAWK; callsign, callsign_time and CALLSIGN likewise with ADSB_MODES_CALLSIGN; fs,
+ *   ALERT, SPI and STATUS from the newest counted DF4/5/20/21 frame; GROUND from the newest counted frame among
+ *   DF0/4/5/16/20/21.  Newest = the last in list order (equal offsets apply in list order, as everywhere in the store).
+ *   Times are the store's frame time, the single rounded product (sample_base + offset) x seconds_per_sample.
+ * Every field combines associatively (saturating add, "later position wins", OR), so one list with its recs, fixes and
+ * levels cut into any sequence of update_modes calls gives the same 64 bytes per aircraft and the same main, mlat and
+ * level records, and two runs give the same bytes.  An EMPTY record is all zeros with the three times NaN: at
+ * admission, at re-admission after an expire, after a reset, and for aircraft held from before the reserve until a
+ * counted frame changes it.  Expire moves a survivor's record with it.
+ * On the device: a key kernel after the field decode (one thread per frame) makes every frame that is not an accepted
+ * DF17/18 one of kind "other" in the table's own fields and writes the sort key, the address or 1 << 24 for a frame
+ * that is not accepted, so the sort covers 25 bits and the rejected frames form one last segment that the lookup gives
+ * no slot.  After the pairs step one thread per frame writes a 48-byte scan operand at its sorted position (and the
+ * UNADDRESSED point), one segmented inclusive scan (rocPRIM; head mark, six "newest position" words, four saturating
+ * counts, the squitter bit) runs over the sorted list, and one thread per segment tail reads the winning frames'
+ * records and times and merges into the side record: no atomics, linear in the list.  Device memory, all of it
+ * allocated by the reserve and none before: 64 bytes per place of max_aircraft, and per frame of max_frames 48 + 48
+ * bytes plus 32 bytes of device staging for a host recs array, the 25-bit sort's and the scan's scratch; 32 bytes per
+ * frame of pinned host memory.  A table that never reserves allocates nothing, launches exactly the kernels it launched
+ * before and returns the same bytes; update, update_levels and update_mlat of a table that did reserve behave as before
+ * and leave the modes records alone (apart from admission emptying a place).
+ */
+#define ADSB_TRACK_UNADDRESSED 0x4u /* point flag: the frame's address is not an aircraft's; nothing was touched */
+#define ADSB_TRACK_MODES_ALT      0x1u   /* altitude_ft, altitude_time hold a value (ADSB_MODES_ALT's bit)   */
+#define ADSB_TRACK_MODES_SQUAWK   0x4u   /* squawk, squawk_time hold a value                                 */
+#define ADSB_TRACK_MODES_GROUND   0x8u   /* the newest DF0/4/5/16/20/21 frame said: on the ground            */
+#define ADSB_TRACK_MODES_ALERT    0x10u  /* with STATUS: the newest DF4/5/20/21 frame's alert                */
+#define ADSB_TRACK_MODES_SPI      0x20u  /* with STATUS: ... its special position identification             */
+#define ADSB_TRACK_MODES_CALLSIGN 0x40u  /* callsign, callsign_time hold a value (BDS 2,0)                   */
+#define ADSB_TRACK_MODES_STATUS   0x100u /* fs, ALERT and SPI hold a value                                   */
+#define ADSB_TRACK_MODES_SQUITTER 0x200u /* the aircraft has sent an accepted DF17/18 frame: it has ADS-B    */
+typedef struct adsb_aircraft_modes {   /* 64 bytes, one per record place, beside the 128-byte record */
+    double   altitude_time, squawk_time, callsign_time; /* store frame time of the frame each came from; NaN if none */
+    int32_t  altitude_ft;
+    uint16_t squawk;
+    uint16_t flags;                 /* ADSB_TRACK_MODES_* */
+    char     callsign[8];
+    uint32_t n_replies, n_allcall, n_surveillance, n_airair; /* saturating at 2^32 - 1 */
+    uint8_t  fs;                    /* of the newest DF4/5/20/21 frame */
+    uint8_t  last_df;               /* of the newest counted frame */
+    uint8_t  reserved[6];           /* 0 */
+} adsb_aircraft_modes;
+#ifdef __cplusplus
+static_assert(sizeof(adsb_aircraft_modes) == 64, "adsb_aircraft_modes layout");
+#endif
+/* Allocates the above and empties every modes record.  May wait for the device.  A second reserve changes nothing.
+ * ADSB_E_ARG for a NULL table; ADSB_E_NOMEM if the memory is not to be had. */
+int adsb_track_table_modes_reserve(adsb_track_table *table);
+/* The update described above.  recs[n] and, if given, fixes[n] and levels[n] are the frames' in list order.  frames,
+ * recs, fixes and levels may each be host memory or memory of the ctx's device, independently; host arrays have been
+ * copied when this returns.  recs may be adsb_modes_device's pointer (the ctx's scratch, ordered on the same stream).
+ * ADSB_E_ARG for a NULL table, or NULL frames or recs with n > 0; ADSB_E_STATE without a modes reserve, for fixes
+ * without an mlat reserve, or for levels without a levels reserve; ADSB_E_CAPACITY for n > max_frames; n = 0 is
+ * ADSB_OK. */
+int adsb_track_table_update_modes(adsb_track_table *table, const adsb_frame *frames, const adsb_modes_rec *recs,
+                                  const adsb_mlat_fix *fixes /* may be NULL */,
+                                  const adsb_frame_level *levels /* may be NULL */, size_t n, uint64_t sample_base);
+/* Waits; one modes record per aircraft, in exactly the order adsb_track_table_fetch returns the records (ascending
+ * ICAO); *n = records held even if more than max.  ADSB_E_ARG for a NULL table, or NULL out with max > 0;
+ * ADSB_E_STATE without a reserve. */
+int adsb_track_table_fetch_modes(adsb_track_table *table, adsb_aircraft_modes *out, size_t max, size_t *n);
+/* Does not synchronise: the device address of the modes records, one per record PLACE in slot order; dev may be NULL.
+ * ADSB_E_ARG for a NULL table, ADSB_E_STATE without a reserve. */
+int adsb_track_table_modes_device(adsb_track_table *table, const adsb_aircraft_modes **dev);
+
+/*
  * ---- several GPUs behind one call ---------------------------------------------------------
  * The reference's thread 2 is one function on one thread (src/adsb.rs:92, spawned at adsb.rs:147); a group is the
  * drop-in for that function when the buffer should be spread over N devices: one context per member, the offsets

@@ -210,6 +210,17 @@ int adsb_host_fix_of(const adsb_site *site, const uint8_t bytes[14], double time
 int adsb_host_track_mlat_of(double max_disagreement_m, const uint8_t bytes[14], const adsb_mlat_fix *fix, double time,
                             adsb_aircraft_mlat *out, uint32_t *frame_flags, float *disagreement_m);
 
+/*
+ * CPU mirror of the per-frame step and the combine of a table with a modes reserve (adsb_hip.h, "Mode S replies per
+ * aircraft"): the same program text as the device's, no device needed.  track_modes_of: *accepted (optional) = 1 iff
+ * the record's kind is SELF or KNOWN; *one = the adsb_aircraft_modes of an aircraft whose only counted frame since
+ * admission is this one, heard at frame time `time` (the EMPTY record for a frame that is not accepted).
+ * track_modes_merge: *into becomes *into followed by *later, a record of the frames that come after into's: the
+ * combine the device's segment tails apply.  ADSB_E_ARG for a NULL rec, one, into or later.
+ */
+int adsb_host_track_modes_of(const adsb_modes_rec *rec, double time, adsb_aircraft_modes *one, uint32_t *accepted);
+int adsb_host_track_modes_merge(adsb_aircraft_modes *into, const adsb_aircraft_modes *later);
+
 /* ---- behind the channel: tracker + CPR ------------------------------------------- */
 
 /* cpr.rs:39-54 calc_num_zones; cpr.rs:135-147 calculate_geographic_position (returns 1 = Some, 0 = None).

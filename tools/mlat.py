@@ -22,8 +22,14 @@ valid/attempted fixes, checked/disagreeing position messages, and the largest di
 --modes also places aircraft that send no ADS-B: the recordings are parsed with their 56-bit frames and without the CRC
 and DF17 filters (ADSB_WIRE_IN_SHORT), every correlated message gets its address from the Mode S stage (adsb_modes_of
 on correlate's frames_out: DF11 all-call replies teach an address, DF0/4/5/16/20/21 replies carry theirs on the parity),
-and only messages whose address is an aircraft's (kinds SELF and KNOWN) are solved and printed, with that address.  Not
-with --sync or --aircraft."""
+and only messages whose address is an aircraft's (kinds SELF and KNOWN) are printed, with that address.  On the device
+every step reads the one before where it lies: correlate's frames go to the Mode S stage, every message to the solver,
+and nothing is fetched before the end; --host solves the messages with an address only.  Not with --sync.
+
+--modes --aircraft: the table takes frames, Mode S records and fixes in one update (adsb_track_table_update_modes), so
+an aircraft that only answers interrogations has a row, keyed by the address the Mode S stage gave its replies, with its
+multilaterated position.  Five columns are appended: Alt(S), Squawk and Call(S) from its newest replies that carry them,
+Replies (DF0/4/5/11/16/20/21 frames counted), and S, which is "S" for an aircraft that has sent no DF17/18 frame."""
 import argparse
 import os
 import sys
@@ -44,18 +50,30 @@ def read_sites(path):
     return sites
 
 
-def host_table(A, frames, fixes, max_disagreement):
+def host_table(A, frames, fixes, max_disagreement, modes=None):
     """What a table with an mlat reserve makes of the list, without a device: the CPU tracker for the records, the CPU
     mirror of the per-frame step and the header's merge rules (saturating add, max, newest by position) for the mlat
-    records -> (AIRCRAFT_DTYPE records, AIRCRAFT_MLAT_DTYPE records), ascending ICAO."""
+    records -> (AIRCRAFT_DTYPE records, AIRCRAFT_MLAT_DTYPE records), ascending ICAO.  modes (the frames' MODES_DTYPE
+    records): what update_modes makes of it instead -- frames that are not SELF or KNOWN are skipped, the others are
+    keyed by their address, a frame that is no DF17/18 is one of kind "other" to the tracker -- and a third array, the
+    AIRCRAFT_MODES_DTYPE records by the CPU mirror of the modes step and its combine."""
     import numpy as np
-    tracker, state, count = A.Tracker(), {}, {}
+    tracker, state, count, side = A.Tracker(), {}, {}, {}
     sat = (1 << 32) - 1
-    for fr, fx in zip(frames, fixes):
+    for j, (fr, fx) in enumerate(zip(frames, fixes)):
         b = fr["bytes"].tobytes()
         time = float(int(fr["offset"])) * 0.5e-6
         icao = b[1] << 16 | b[2] << 8 | b[3]
-        tracker.update(b, time)
+        seen = b
+        if modes is not None:
+            if int(modes[j]["kind"]) > A.ADSB_MODES_KNOWN:
+                continue
+            icao = int(modes[j]["address"]) & 0xFFFFFF
+            if int(modes[j]["df"]) not in (17, 18):                      # no ADS-B message, whatever byte 4 looks like
+                seen = bytes([17 << 3, icao >> 16, icao >> 8 & 0xFF, icao & 0xFF]) + bytes(10)
+            one_side = A.host_track_modes_of(modes[j], time)[0]
+            side[icao] = A.host_track_modes_merge(side[icao], one_side) if icao in side else one_side
+        tracker.update(seen, time)
         count[icao] = count.get(icao, 0) + 1
         one = A.host_track_mlat_of(max_disagreement, b, fx, time)[0]
         a = state.get(icao)
@@ -81,14 +99,27 @@ def host_table(A, frames, fixes, max_disagreement):
         recs[k] = (s.latitude, s.longitude, s.last_contact, icao, s.altitude, 1 if s.has_position else 0, count[icao],
                    s.callsign)
         mlat[k] = state[icao]
-    return recs, mlat
+    if modes is None:
+        return recs, mlat
+    return recs, mlat, np.array([side[icao] for icao in sorted(state)], dtype=A.AIRCRAFT_MODES_DTYPE)
 
 
-def aircraft_lines(A, recs, mlat, now):
-    """One tab-separated line per aircraft, under a header line."""
+def modes_columns(A, s):
+    """Alt(S), Squawk, Call(S), Replies and S of one AIRCRAFT_MODES_DTYPE record."""
+    flags = int(s["flags"])
+    return "\t".join([f"{int(s['altitude_ft'])}" if flags & A.ADSB_TRACK_MODES_ALT else "n/a",
+                      f"{int(s['squawk']):04d}" if flags & A.ADSB_TRACK_MODES_SQUAWK else "n/a",
+                      (s["callsign"].decode("ascii", "replace").replace("_", " ").strip() or "n/a")
+                      if flags & A.ADSB_TRACK_MODES_CALLSIGN else "n/a",
+                      f"{int(s['n_replies'])}", "" if flags & A.ADSB_TRACK_MODES_SQUITTER else "S"])
+
+
+def aircraft_lines(A, recs, mlat, now, modes=None):
+    """One tab-separated line per aircraft, under a header line.  modes (AIRCRAFT_MODES_DTYPE records): five more
+    columns."""
     out = ("ICAO\tCallsign\tLatitude\tLongitude\tMlatLat\tMlatLon\tAge\tPdop\tValid/Attempted\tChecked/Disagree"
-           "\tMaxDisagreement\n")
-    for r, m in zip(recs, mlat):
+           "\tMaxDisagreement" + ("" if modes is None else "\tAlt(S)\tSquawk\tCall(S)\tReplies\tS") + "\n")
+    for k, (r, m) in enumerate(zip(recs, mlat)):
         call = r["callsign"].decode("ascii", "replace").strip() or "n/a"
         said = f"{float(r['latitude']):.5f}\t{float(r['longitude']):.5f}" if r["has_position"] else "n/a\tn/a"
         if m["flags"] & A.ADSB_TRACK_MLAT_VALID:
@@ -98,7 +129,8 @@ def aircraft_lines(A, recs, mlat, now):
             solved = "n/a\tn/a\tn/a\tn/a"
         worst = f"{float(m['max_disagreement_m']):.0f}" if m["flags"] & A.ADSB_TRACK_MLAT_CHECKED else "n/a"
         out += (f"{int(r['icao']):06X}\t{call}\t{said}\t{solved}\t{int(m['n_valid'])}/{int(m['n_attempted'])}"
-                f"\t{int(m['n_checked'])}/{int(m['n_disagree'])}\t{worst}\n")
+                f"\t{int(m['n_checked'])}/{int(m['n_disagree'])}\t{worst}"
+                + ("" if modes is None else "\t" + modes_columns(A, modes[k])) + "\n")
     return out
 
 
@@ -118,9 +150,12 @@ def main():
     ap.add_argument("--max-disagreement", type=float, default=1000.0,
                     help="with --aircraft: metres a reported position may lie from the multilaterated one")
     ap.add_argument("--modes", action="store_true", help="Mode S replies too: short frames, addresses from the Mode S stage")
+    ap.add_argument("--max-iterations", type=int, default=0,
+                    help="the solver's step limit (default: its own, 24); replies carry no altitude, and a free solve over "
+                         "ground receivers may need 200")
     args = ap.parse_args()
-    if args.modes and (args.sync or args.aircraft):
-        ap.error("--modes goes with neither --sync nor --aircraft")
+    if args.modes and args.sync:
+        ap.error("--modes does not go with --sync")
 
     import numpy as np
 
@@ -131,7 +166,8 @@ def main():
         raise SystemExit(f"{len(sites)} sites for {len(args.recordings)} recordings")
     streams = [open(p, "rb").read() for p in args.recordings]
     data, ends = b"".join(streams), np.cumsum([len(s) for s in streams])
-    cfg = dict(time_source="ticks", use_altitude=not args.no_altitude, max_residual_m=args.max_residual)
+    cfg = dict(time_source="ticks", use_altitude=not args.no_altitude, max_residual_m=args.max_residual,
+               max_iterations=args.max_iterations)
     # wire input's frame offsets are 2 MHz samples: the unit of the messages' own times
     sync = dict(reference=args.reference, max_residual_s=args.max_residual_us * 1e-6, seconds_per_time=0.5e-6)
     clocks = None
@@ -152,19 +188,36 @@ def main():
         out["first"] = np.cumsum([0] + [len(p) for p in parts])[:-1]
         return out, (np.concatenate(parts) if parts else recs[:0]), modes["address"][keep]
 
-    address = None
+    address = accepted = newest = None
     if args.modes and args.host:
         win = A.host_wire_parse(data, ends, filter="short")
-        msgs, fout, recs = A.host_correlate(win.frames, win.counts, args.window)
-        msgs, recs, address = resolved(msgs, recs, A.host_modes(fout)[0])
+        every, fout, recs = A.host_correlate(win.frames, win.counts, args.window)
+        mrec = A.host_modes(fout)[0]
+        msgs, recs, address = resolved(every, recs, mrec)
         fixes, hdr = A.host_multilaterate(sites, msgs, recs, win.rx, **cfg)
+        if args.aircraft:
+            spread = np.zeros(len(every), dtype=A.MLAT_FIX_DTYPE)       # a fix per message: none where none was solved
+            spread[np.flatnonzero(mrec["kind"] <= A.ADSB_MODES_KNOWN)] = fixes
+            aircraft = host_table(A, fout, spread, args.max_disagreement, modes=mrec)
+            newest = float(int(every["time"][-1])) * 0.5e-6 if len(every) else 0.0
     elif args.modes:
         with A.AdsbDemod(max_samples=1 << 16, max_out=1024) as d:
             win = d.wire_in_of(data, ends, filter="short")
             d.correlate_of_async((d.wire_in_device()[0], len(win.frames)), win.counts, args.window)
+            n_msgs = d.correlated_counts()[0]                            # the solver and the Mode S stage take it from the host
+            d.modes_of_async((d.correlated_device()[1], n_msgs))         # behind correlate, on its frames where they lie
+            d.multilaterate_async(sites, rx=d.wire_in_device()[1], **cfg)   # every message; the table takes the accepted ones
+            if args.aircraft:
+                with A.TrackTable(d, max_frames=max(n_msgs, 1), seconds_per_sample=0.5e-6) as table:
+                    table.mlat_reserve(args.max_disagreement)
+                    table.modes_reserve()
+                    table.update_device(d.correlated_device()[1], n_msgs, 0, mlat_ptr=d.mlat_device()[0],
+                                        modes_ptr=d.modes_device()[0])
+                    aircraft = (table.aircraft()[0], table.mlat(), table.modes())
+            fixes, hdr = d.fetch_mlat()
             msgs, _, recs = d.fetch_correlated()
-            msgs, recs, address = resolved(msgs, recs, d.modes_of((d.correlated_device()[1], len(msgs)))[0])
-            fixes, hdr = d.multilaterate_of(sites, msgs, recs, (d.wire_in_device()[1], len(win.frames)), **cfg)
+            mrec = d.fetch_modes()[0]
+            address, accepted = mrec["address"], mrec["kind"] <= A.ADSB_MODES_KNOWN
     elif args.host:
         win = A.host_wire_parse(data, ends, filter=["crc", "df17"])
         msgs, _, recs = A.host_correlate(win.frames, win.counts, args.window)
@@ -201,10 +254,11 @@ def main():
         print(f"# clock {r:3d} {what:9s} offset {k['offset_s']:+.9f} s drift {k['drift'] * 1e6:+9.3f} ppm "
               f"rms {k['residual_rms_s'] * 1e9:8.1f} ns rows {int(k['n_rows'])} dropped {int(k['n_dropped'])}")
     if aircraft is not None:
-        newest = float(int(msgs["time"][-1])) * 0.5e-6 if len(msgs) else 0.0
-        print(aircraft_lines(A, aircraft[0], aircraft[1], newest), end="")
+        if newest is None:
+            newest = float(int(msgs["time"][-1])) * 0.5e-6 if len(msgs) else 0.0
+        print(aircraft_lines(A, aircraft[0], aircraft[1], newest, aircraft[2] if len(aircraft) > 2 else None), end="")
     for k, (m, f) in enumerate(zip(msgs, fixes)):
-        if aircraft is None and f["flags"] & A.ADSB_MLAT_VALID:
+        if aircraft is None and f["flags"] & A.ADSB_MLAT_VALID and (accepted is None or accepted[k]):
             t = int(win.rx["ticks"][recs["frame"][m["first"]]]) / 12e6
             icao = int(m["bytes"][1]) << 16 | int(m["bytes"][2]) << 8 | int(m["bytes"][3])
             icao = icao if address is None else int(address[k])

@@ -47,7 +47,11 @@ that prints from a frame list works on it: the stream text, --aircraft (with --l
 bytes), --web, --beast, --avr.  --levels alone needs the samples.  With --modes (and --beast-in / --avr-in) the 56-bit frames are
 parsed too (ADSB_WIRE_IN_SHORT), every frame gets its address on the device (adsb_modes_of, the known addresses carried from
 chunk to chunk), and one line per frame is printed instead: time in seconds, DF, kind (SELF, KNOWN, UNKNOWN, PARITY,
-UNSUPPORTED), address, altitude in feet, squawk and callsign, "-" for a missing value.  The TEXT has not been compared with a Rust build's (there is no
+UNSUPPORTED), address, altitude in feet, squawk and callsign, "-" for a missing value.  With --modes --aircraft the frames
+and their Mode S records go through one device track table with a modes reserve (adsb_track_table_update_modes: keyed by
+the resolved address, so aircraft that only answer interrogations have a row; frames without an aircraft's address touch
+nothing) and the table is printed with five more columns: Alt(S), Squawk and Call(S) from the aircraft's newest replies
+that carry them, Replies, and S, which is "S" for an aircraft that has sent no DF17/18 frame.  The TEXT has not been compared with a Rust build's (there is no
 Rust toolchain); only the values are checked, against the oracle."""
 import argparse
 import json
@@ -96,26 +100,40 @@ def fix_columns(fx):
             f"{float(fx['ground_speed_kt']):.1f}" if fx["flags"] & A.ADSB_FIX_SPEED else "n/a"]
 
 
-def aircraft_table(d, frames, n_samples, st=None, frame_levels=None, site=None):
+def modes_columns(s):
+    """Alt(S), Squawk, Call(S), Replies and S of one AIRCRAFT_MODES_DTYPE record."""
+    flags = int(s["flags"])
+    return [f"{int(s['altitude_ft'])}" if flags & A.ADSB_TRACK_MODES_ALT else "n/a",
+            f"{int(s['squawk']):04d}" if flags & A.ADSB_TRACK_MODES_SQUAWK else "n/a",
+            (s["callsign"].decode("ascii", "replace").replace("_", " ").strip() or "n/a")
+            if flags & A.ADSB_TRACK_MODES_CALLSIGN else "n/a",
+            f"{int(s['n_replies'])}", "" if flags & A.ADSB_TRACK_MODES_SQUITTER else "S"]
+
+
+def aircraft_table(d, frames, n_samples, st=None, frame_levels=None, site=None, modes=None):
     """The capture's final aircraft table as tab-separated text: tui.rs:95's columns, rows by age (tui.rs:69), then
     ICAO.  Age = whole seconds from each aircraft's last frame to the end of the capture.  frame_levels (one
     LEVEL_DTYPE record per frame, with st the sample type): also the columns RSSI and SNR.  site ((latitude, longitude,
-    max_range_nm)): also FixLat, FixLon, Range, Bearing and GS."""
+    max_range_nm)): also FixLat, FixLon, Range, Bearing and GS.  modes (one MODES_DTYPE record per frame): the table is
+    keyed by the records' addresses (update_modes); also Alt(S), Squawk, Call(S), Replies and S."""
     with A.TrackTable(d, max_frames=max(len(frames), 1), seconds_per_sample=SECONDS_PER_SAMPLE) as t:
         if site is not None:
             t.fixes_reserve(site)
+        if modes is not None:
+            t.modes_reserve()
         if frame_levels is None:
-            t.update(frames)
+            t.update(frames, modes=modes)
         else:
             t.levels_reserve()
-            t.update(frames, levels=frame_levels)
+            t.update(frames, levels=frame_levels, modes=modes)
         recs, _ = t.aircraft()
         vel, heard = t.velocity(), t.last_heard()
+        sides = [None] * len(recs) if modes is None else t.modes()
         levels = [None] * len(recs) if frame_levels is None else t.levels()
         fixes = [None] * len(recs) if site is None else t.fixes()
     now = n_samples * SECONDS_PER_SAMPLE
     rows = []
-    for rec, v, lh, lv, fx in zip(recs, vel, heard, levels, fixes):
+    for rec, v, lh, lv, fx, side in zip(recs, vel, heard, levels, fixes, sides):
         pos, age = bool(rec["has_position"]), int(now - lh)
         rows.append((age, int(rec["icao"]), "\t".join([
             f"{int(rec['icao']):x}",
@@ -124,10 +142,12 @@ def aircraft_table(d, frames, n_samples, st=None, frame_levels=None, site=None):
             f"{float(rec['latitude']):.6f}" if pos else "n/a",
             f"{float(rec['longitude']):.6f}" if pos else "n/a",
             f"{float(v['speed_kt']):.0f}" if v["flags"] & A.ADSB_VELOCITY_SPEED else "n/a",
-            f"{age}"] + ([] if lv is None else level_columns(st, lv)) + ([] if fx is None else fix_columns(fx)))))
+            f"{age}"] + ([] if lv is None else level_columns(st, lv)) + ([] if fx is None else fix_columns(fx))
+            + ([] if side is None else modes_columns(side)))))
     rows.sort(key=lambda r: (r[0], r[1]))
     head = "ICAO\tCallsign\tAltitude\tLatitude\tLongitude\tVelocity\tAge" + ("" if frame_levels is None else "\tRSSI\tSNR")
     head += "" if site is None else "\tFixLat\tFixLon\tRange\tBearing\tGS"
+    head += "" if modes is None else "\tAlt(S)\tSquawk\tCall(S)\tReplies\tS"
     return head + "\n" + "".join(r[2] + "\n" for r in rows)
 
 
@@ -279,7 +299,8 @@ def main():
     ap.add_argument("--beast-in", action="store_true", help="FILE is a Beast binary capture instead of IQ")
     ap.add_argument("--avr-in", action="store_true", help="FILE is an AVR text capture instead of IQ")
     ap.add_argument("--modes", action="store_true",
-                    help="with --beast-in / --avr-in: short frames too; print DF, kind, address, altitude, squawk, callsign per frame")
+                    help="with --beast-in / --avr-in: short frames too; print DF, kind, address, altitude, squawk, callsign per "
+                         "frame, or with --aircraft the table keyed by those addresses")
     ap.add_argument("--tick-bias", type=int, default=0, metavar="N", help="added to every timestamp (12 MHz ticks, < 2^48)")
     a = ap.parse_args()
     if a.mlat and not a.avr:
@@ -302,7 +323,11 @@ def main():
                      host_staging=False) as d:
         if wire_in and a.modes:
             frames, recs = read_wire(d, a.file, wire_in, a.tick_bias, modes=True)
-            sys.stdout.write(modes_lines(frames, recs))
+            if a.aircraft:
+                n_samp = int(frames["offset"].max()) + A.WINDOW if len(frames) else 0
+                sys.stdout.write(aircraft_table(d, frames, n_samp, site=a.site, modes=recs))
+            else:
+                sys.stdout.write(modes_lines(frames, recs))
             if a.summary:
                 print(f"{os.path.getsize(a.file)} bytes, {len(frames)} frames", file=sys.stderr)
             return
