@@ -129,6 +129,29 @@ def test_crc_classes_in_big_tiles(dem, oracle):
         _check(dem, oracle, iq)
 
 
+def test_position_sweep(gpu, oracle):
+    """a real frame at every in-tile offset of this kernel's tile (tests/sweep_cases.py: the dense stride, real (I, Q) samples,
+    clean, repaired and tied frames at every level): whole through the tile kernel, and cut at multiples of 32 tiles
+    through the one-dispatch kernel, each slice against the oracle on that slice"""
+    from tests import sweep_cases as W
+    name = "i8 dense reg" if SCAN == "reg" else "i8 dense"
+    s, want, _ = W.reference(oracle, name)
+    assert s.tile == TILE and (np.sort(s.planted["offset"] % TILE) == np.arange(TILE)).all()
+    W.compare(want, s.planted, TILE, "the oracle against the plan")
+    with A.AdsbDemod(max_samples=len(s.iq), max_out=1 << 16) as d:
+        assert d.scan == SCAN
+        frames, flags = d.demod(s.iq)
+        assert flags == 0
+        W.compare(frames, want, TILE, f"{SCAN} scan, whole")
+        total = 0
+        for j, (first, iq, part) in enumerate(W.slice_reference(oracle, name)[0]):
+            frames, flags = d.demod(iq)
+            assert flags == 0, (j, flags)
+            W.compare(frames, part, TILE, f"{SCAN} scan, slice {j} (from sample {first})")
+            total += len(frames)
+        assert total == TILE
+
+
 def test_multi_channel(gpu, oracle):
     cfg = A.synth_default(seed=3, slot_len=800)
     nch, n = 5, 70_000 + 8

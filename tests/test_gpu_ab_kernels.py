@@ -3,8 +3,8 @@
 The product library (air_rs_amd/lib/libadsb_hip.so) carries ONE i8 scan kernel; the kernels round 3-4 measured against it
 are compiled into air_rs_amd/lib/variants/libadsb_hip_ab.so only (build.sh).  A process loads one library, so each kernel's
 cases (tests/ab_cases.py: sizes around the tile edges, constant / saturated / coarse input, error mixes, both launch paths,
-slot-pool loss, every CRC syndrome class in tiles of more than 32 survivors, channels; for the code scan its table and the
-levels where codes tie) run in a child pytest whose ADSB_HIP_LIB points at that build."""
+slot-pool loss, every CRC syndrome class in tiles of more than 32 survivors, a real frame at every in-tile offset of the
+kernel's own tile length (tests/sweep_cases.py), channels; for the code scan its table and the levels where codes tie) run in a child pytest whose ADSB_HIP_LIB points at that build."""
 import os
 import subprocess
 import sys
