@@ -126,6 +126,24 @@ class AdsbModesHeader(C.Structure):
                                           "n_known_out", "n_squitters")]
 
 
+(ADSB_COMMB_NOT_COMMB, ADSB_COMMB_EMPTY, ADSB_COMMB_NONE, ADSB_COMMB_ONE,
+ ADSB_COMMB_AMBIGUOUS) = 0, 1, 2, 3, 4                          # adsb_commb_rec.state
+(ADSB_COMMB_C10, ADSB_COMMB_C17, ADSB_COMMB_C20, ADSB_COMMB_C30, ADSB_COMMB_C40, ADSB_COMMB_C50,
+ ADSB_COMMB_C60) = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40         # adsb_commb_rec.candidates
+
+
+class AdsbCommbRec(C.Structure):
+    """adsb_commb_rec: the Comm-B register one DF20/21 frame carries, and its values (32 bytes)."""
+    _fields_ = [("state", C.c_uint8), ("bds", C.c_uint8), ("candidates", C.c_uint8), ("n_candidates", C.c_uint8),
+                ("status", C.c_uint16), ("reserved", C.c_uint16), ("value", C.c_int32 * 5), ("word", C.c_uint32)]
+
+
+class AdsbCommbHeader(C.Structure):
+    """adsb_commb_header: the totals of one adsb_commb_of (128 bytes)."""
+    _fields_ = ([(k, C.c_uint64) for k in ("n", "n_commb", "n_empty", "n_none", "n_one", "n_ambiguous")]
+                + [("n_bds", C.c_uint64 * 7), ("reserved", C.c_uint64 * 3)])
+
+
 class AdsbCorrelateCfg(C.Structure):
     """adsb_correlate_cfg: the window in samples, and whether adsb_correlate_launch takes the launch's levels."""
     _fields_ = [("window", C.c_uint32), ("use_levels", C.c_uint32), ("reserved", C.c_uint64)]
@@ -431,6 +449,10 @@ PROTOTYPES = {
                                    C.c_void_p, C.c_uint32, _P(AdsbModesHeader)]),
     "adsb_modes_device": (C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 5),
     "adsb_debug_modes_geometry": (C.c_int, [_P(C.c_uint32)]),
+    "adsb_commb_of": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_fetch_commb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(AdsbCommbHeader)]),
+    "adsb_commb_device": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p)]),
+    "adsb_debug_commb_geometry": (C.c_int, [_P(C.c_uint32)]),
     "adsb_correlate_launch": (C.c_int, [C.c_void_p, _P(AdsbCorrelateCfg), C.c_void_p]),
     "adsb_correlate_of": (C.c_int, [C.c_void_p, _P(AdsbCorrelateCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                     C.c_uint32, C.c_void_p]),
@@ -604,6 +626,8 @@ PROTOTYPES = {
                                        _P(AdsbWireInHeader)]),
     "adsb_host_modes": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, _P(AdsbModesHeader)]),
+    "adsb_host_commb": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, _P(AdsbCommbHeader)]),
+    "adsb_host_commb_as": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "adsb_host_correlate": (C.c_int, [_P(AdsbCorrelateCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
                                       C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p]),
     "adsb_host_multilaterate": (C.c_int, [_P(AdsbMlatCfg), C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,

@@ -137,6 +137,15 @@ struct adsb_ctx {
         uint32_t n_receivers = 0;            // of the last call; 0: it had no counts
         bool done = false;                   // a call has been enqueued
     } modes;
+    // Comm-B registers (adsb_commb.hip), allocated on first adsb_commb_of and grown on demand: one hipMalloc carved
+    // into the partial counts, the records and the header, and the device copy of a host list
+    struct Commb {
+        DevBuf<char> mem;
+        size_t frames = 0;                   // what it holds
+        adsbk::CommbArgs a{};                // scratch and result pointers (the list and its length are set per call)
+        DevBuf<adsb_frame> in_frames;        // of a host list
+        bool done = false;                   // a call has been enqueued
+    } commb;
     // tracker (allocated on first adsb_track_device): one hipMalloc carved into the five below
     DevBuf<char> trk_mem;
     uint32_t *trk_u32 = nullptr;    // 4 x [max_out]: keys, vals, sorted keys, sorted vals

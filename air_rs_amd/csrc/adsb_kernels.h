@@ -291,6 +291,20 @@ struct ModesArgs {
 size_t modes_temp_bytes(size_t m);
 hipError_t launch_modes(hipStream_t s, const ModesArgs &a);
 
+// the Comm-B register of every DF20/21 frame and its values (adsb_commb.hip; adsb_commb.h has the text of one frame)
+constexpr uint32_t kCommbBlock = 256; // frames (= threads) per workgroup of commb_frames
+constexpr uint32_t kCommbTallyWords = 12; // per workgroup: the five states, then the ONE records of the seven registers
+constexpr uint32_t commb_blocks(uint64_t n) { return (uint32_t)((n + kCommbBlock - 1) / kCommbBlock); }
+struct CommbArgs {
+    const adsb_frame *frames; // [n], adsb_fetch's layout
+    uint32_t n;
+    uint32_t *tally;          // [kCommbTallyWords x commb_blocks(n)]
+    // results
+    adsb_commb_rec *recs;     // [n], 16-byte aligned
+    adsb_commb_header *hdr;
+};
+hipError_t launch_commb(hipStream_t s, const CommbArgs &a);
+
 // transmitter positions from correlated receptions (adsb_mlat.hip; adsb_mlat.h has the solver's text)
 constexpr uint32_t kMlatBlock = 256;                          // threads per workgroup of mlat_solve
 constexpr uint32_t kMlatPerBlock = kMlatBlock / kMlatLanes;   // messages per workgroup: 16 lanes each

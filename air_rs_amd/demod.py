@@ -295,6 +295,60 @@ def host_modes(frames, counts=None, known=None):
             None if sqc is None else sqc[:len(cnt)].copy(), header)
 
 
+COMMB_DTYPE = np.dtype([("state", "u1"), ("bds", "u1"), ("candidates", "u1"), ("n_candidates", "u1"), ("status", "<u2"),
+                        ("reserved", "<u2"), ("value", "<i4", (5,)), ("word", "<u4")])
+assert COMMB_DTYPE.itemsize == C.sizeof(L.AdsbCommbRec) == 32
+COMMB_HEADER_DTYPE = np.dtype([(k, "<u8") for k in ("n", "n_commb", "n_empty", "n_none", "n_one", "n_ambiguous")]
+                              + [("n_bds", "<u8", (7,)), ("reserved", "<u8", (3,))])
+assert COMMB_HEADER_DTYPE.itemsize == C.sizeof(L.AdsbCommbHeader) == 128
+COMMB_STATES = ("NOT_COMMB", "EMPTY", "NONE", "ONE", "AMBIGUOUS")
+COMMB_REGISTERS = (0x10, 0x17, 0x20, 0x30, 0x40, 0x50, 0x60)     # in the order of the candidate bits and of n_bds
+# commb_physical: key -> (register, index into value[], what one unit of the value is in the key's unit)
+_COMMB_PHYSICAL = {
+    "mcp_altitude_ft": (0x40, 0, 1.0), "fms_altitude_ft": (0x40, 1, 1.0), "baro_setting_mb": (0x40, 2, 0.1),
+    "roll_deg": (0x50, 0, 45.0 / 256.0), "true_track_deg": (0x50, 1, 90.0 / 512.0),
+    "ground_speed_kt": (0x50, 2, 1.0), "track_rate_deg_s": (0x50, 3, 8.0 / 256.0),
+    "true_airspeed_kt": (0x50, 4, 1.0),
+    "magnetic_heading_deg": (0x60, 0, 90.0 / 512.0), "ias_kt": (0x60, 1, 1.0), "mach": (0x60, 2, 0.004),
+    "baro_rate_ft_min": (0x60, 3, 1.0), "inertial_rate_ft_min": (0x60, 4, 1.0),
+}
+
+
+def host_commb(frames):
+    """adsb_host_commb, the CPU mirror of AdsbDemod.commb_of: (COMMB_DTYPE records, the COMMB_HEADER_DTYPE record) of
+    the FRAME_DTYPE list `frames`.  Needs no device."""
+    frames, fptr, n = _host_list(frames, FRAME_DTYPE)
+    recs, hdr = np.zeros(max(n, 1), dtype=COMMB_DTYPE), L.AdsbCommbHeader()
+    L.check(L.load().adsb_host_commb(fptr, n, recs.ctypes.data, C.byref(hdr)), "adsb_host_commb")
+    return recs[:n].copy(), np.frombuffer(bytes(hdr), dtype=COMMB_HEADER_DTYPE)[0]
+
+
+def host_commb_as(frame_bytes, bds):
+    """adsb_host_commb_as: the COMMB_DTYPE record of one frame's 14 bytes with MB decoded as register `bds` (0x10 ...
+    0x60), whatever the inference says; AdsbError(ADSB_E_ARG) if `bds` is not among the frame's candidates.  What a
+    consumer that knows more settles an AMBIGUOUS record with.  Needs no device."""
+    b = np.zeros(14, dtype=np.uint8)
+    raw = np.frombuffer(bytes(frame_bytes), dtype=np.uint8)[:14]
+    b[:len(raw)] = raw
+    rec = np.zeros(1, dtype=COMMB_DTYPE)
+    L.check(L.load().adsb_host_commb_as(b.ctypes.data, int(bds), rec.ctypes.data), "adsb_host_commb_as")
+    return rec[0]
+
+
+def commb_physical(recs):
+    """The values of COMMB_DTYPE records in physical units: a dict of float64 arrays, one entry per record, NaN where
+    the status bit is off, the state is not ONE or the register is another.  BDS 4,0: mcp_altitude_ft, fms_altitude_ft,
+    baro_setting_mb.  BDS 5,0: roll_deg, true_track_deg, ground_speed_kt, track_rate_deg_s, true_airspeed_kt.  BDS
+    6,0: magnetic_heading_deg, ias_kt, mach, baro_rate_ft_min, inertial_rate_ft_min."""
+    recs = np.atleast_1d(np.asarray(recs, dtype=COMMB_DTYPE))
+    one = recs["state"] == L.ADSB_COMMB_ONE
+    out = {}
+    for key, (bds, k, factor) in _COMMB_PHYSICAL.items():
+        held = one & (recs["bds"] == bds) & ((recs["status"] >> k) & 1 == 1)
+        out[key] = np.where(held, recs["value"][:, k] * factor, np.nan)
+    return out
+
+
 MESSAGE_DTYPE = np.dtype([("time", "<u8"), ("bytes", "u1", (14,)), ("status", "u1"), ("fixed_bit", "u1"), ("first", "<u4"),
                           ("n_receptions", "<u4"), ("n_receivers", "<u2"), ("first_receiver", "<u2"),
                           ("best_receiver", "<u2"), ("reserved", "<u2"), ("n_clean", "<u4"), ("reserved2", "<u4"),
@@ -884,6 +938,39 @@ class AdsbDemod:
         synchronisation."""
         p = [C.c_void_p() for _ in range(5)]
         L.check(self._lib.adsb_modes_device(self._h, *[C.byref(x) for x in p]), "adsb_modes_device")
+        return tuple(x.value for x in p)
+
+    def commb_of_async(self, frames):
+        """adsb_commb_of alone: enqueues and returns once a host list is copied.  frames: a FRAME_DTYPE array (host) or
+        (device pointer, count), for example wire_in_device()[0] with the parse's frame count."""
+        if isinstance(frames, tuple):
+            fptr, n = (int(frames[0]) if int(frames[1]) else None), int(frames[1])
+        else:
+            frames, fptr, n = _host_list(frames, FRAME_DTYPE)
+        L.check(self._lib.adsb_commb_of(self._h, fptr, n), "adsb_commb_of")
+
+    def fetch_commb(self):
+        """adsb_fetch_commb: waits for the last commb_of_async() -> (COMMB_DTYPE records, the COMMB_HEADER_DTYPE
+        record)."""
+        hdr = L.AdsbCommbHeader()
+        L.check(self._lib.adsb_fetch_commb(self._h, None, 0, C.byref(hdr)), "adsb_fetch_commb")   # the size first
+        n = int(hdr.n)
+        recs = np.zeros(max(n, 1), dtype=COMMB_DTYPE)
+        L.check(self._lib.adsb_fetch_commb(self._h, recs.ctypes.data, n, C.byref(hdr)), "adsb_fetch_commb")
+        return recs[:n].copy(), np.frombuffer(bytes(hdr), dtype=COMMB_HEADER_DTYPE)[0]
+
+    def commb_of(self, frames):
+        """adsb_commb_of + adsb_fetch_commb: for every DF20/21 frame the Comm-B register its MB field carries, inferred
+        from the 56 bits (state: COMMB_STATES), and that register's values -> (recs, header), index for index with the
+        list and with modes_of's records.  commb_physical(recs) gives the values in physical units.  See
+        commb_of_async."""
+        self.commb_of_async(frames)
+        return self.fetch_commb()
+
+    def commb_device(self):
+        """adsb_commb_device: device addresses (records, header); no synchronisation."""
+        p = [C.c_void_p() for _ in range(2)]
+        L.check(self._lib.adsb_commb_device(self._h, *[C.byref(x) for x in p]), "adsb_commb_device")
         return tuple(x.value for x in p)
 
     def correlate_async(self, window, sample_base=None, levels=False):

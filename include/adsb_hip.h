@@ -640,6 +640,114 @@ int adsb_modes_device(adsb_ctx *ctx, const adsb_modes_rec **recs_dev, const uint
 int adsb_debug_modes_geometry(uint32_t *threads_per_block);
 
 /*
+ * Comm-B registers: which transponder register the 56-bit MB field of a DF20/21 reply carries, and its values.  A
+ * reply does not say which register it answers with; the interrogation did, and a receiver has not heard that.  So the
+ * register is inferred from the 56 bits alone: status bits that contradict their fields, reserved bits, and values
+ * outside what an aircraft can do.  Stateless, per frame, integers only; computed on the device; the list is in
+ * adsb_fetch's layout, as for adsb_modes_of.
+ *   BIT NUMBERING  For a frame with DF = bytes[0] >> 3 equal to 20 or 21, MB is bytes[4..11).  Bit 1 is the top bit of
+ *     bytes[4], bit 56 the low bit of bytes[10].  u(a, n) is the n bits from bit a, as an unsigned number.  s(a, n) is a
+ *     sign bit at a followed by n bits, two's complement: u(a+1, n) - (bit a ? 2^n : 0).  The "status rule (a; n)"
+ *     reads: if bit a is 0, then u(a, n+1) == 0.
+ *   STATE
+ *     NOT_COMMB  DF is not 20 or 21.  Every other field of the record is 0.
+ *     EMPTY      MB is all zero.
+ *     NONE       No candidate register passes.
+ *     ONE        Exactly one candidate passes.  bds is its code, and the values are decoded from it.
+ *     AMBIGUOUS  Two or more candidates pass.  bds is 0 and the values are 0.
+ *     candidates and n_candidates are filled for NONE, ONE and AMBIGUOUS alike.  The stage decides whatever the frame's
+ *     parity says and does not know the address: consumers pair the record with adsb_modes_rec.kind, index for index.
+ *   CANDIDATES  One bit each in candidates, in this order:
+ *     1,0  u(1,8) == 0x10; u(10,5) == 0; with ovc = u(15,1) and ver = u(17,7), either ovc == 1 && ver >= 5 or
+ *          ovc == 0 && ver <= 4.
+ *     1,7  u(29,28) == 0 and bit 7 is set (a transponder that answers Comm-B has BDS 2,0).
+ *     2,0  u(1,8) == 0x20 and each of the eight characters u(9 + 6k, 6) is a letter, a digit or the space (the rule
+ *          of ADSB_MODES_CALLSIGN).
+ *     3,0  u(1,8) == 0x30; u(29,2) != 3; u(16,7) < 48.
+ *     4,0  status rules (1;12), (14;12), (27;12); u(40,8) == 0; u(52,2) == 0.
+ *     5,0  status rules (1;10), (12;11), (24;10), (35;10), (46;10), and the limits: with bit 1, |s(2,9)| <= 284 (roll
+ *          is at most 50 degrees); with bit 24, u(25,10) <= 300 (ground speed is at most 600 kt); with bit 46,
+ *          u(47,10) <= 250 (true airspeed is at most 500 kt); with bits 24 and 46, |u(47,10) - u(25,10)| <= 100 (the
+ *          two speeds differ by at most 200 kt).
+ *     6,0  status rules (1;11), (13;10), (24;10), (35;10), (46;10), and the limits: with bit 13, u(14,10) <= 500;
+ *          with bit 24, u(25,10) <= 250 (Mach is at most 1.0); with bit 35, |s(36,9)| <= 187; with bit 46,
+ *          |s(47,9)| <= 187 (vertical rates are at most 6000 ft/min).
+ *     The limits are written as integers on the raw fields, so device, mirror and model cannot disagree at a boundary.
+ *   VALUES (state ONE)  value[0..5) are int32, bit k of status says that value[k] holds a value (it is 0 otherwise),
+ *     word is a uint32.  All are integers; the Python interface converts to physical units.
+ *     4,0  value[0] = 16 u(2,12): MCP/FCU selected altitude in feet, with bit 1.  value[1] = 16 u(15,12): FMS selected
+ *          altitude in feet, with bit 14.  value[2] = 8000 + u(28,12): barometric setting in 0.1 mb, with bit 27.
+ *          value[3] = u(49,3): VNAV, ALT HOLD, APPROACH, with bit 48.  value[4] = u(55,2): target altitude source,
+ *          with bit 54.
+ *     5,0  value[0] = s(2,9): roll, LSB 45/256 degrees, with bit 1.  value[1] = s(13,10) mod 2048: true track, LSB
+ *          90/512 degrees, 0..2047, with bit 12.  value[2] = 2 u(25,10): ground speed in kt, with bit 24.  value[3] =
+ *          s(36,9): track rate, LSB 8/256 degrees per second, with bit 35.  value[4] = 2 u(47,10): true airspeed in kt,
+ *          with bit 46.
+ *     6,0  value[0] = s(2,10) mod 2048: magnetic heading, LSB 90/512 degrees, with bit 1.  value[1] = u(14,10): IAS in
+ *          kt, with bit 13.  value[2] = u(25,10): Mach, LSB 0.004, with bit 24.  value[3] = 32 s(36,9): barometric
+ *          vertical rate in ft/min, with bit 35.  value[4] = 32 s(47,9): inertial vertical rate in ft/min, with bit 46.
+ *     3,0  status is 0x1F.  value[0] = u(9,14): ARA.  value[1] = u(23,4): RAC.  value[2] = u(27,2): RAT and MTE.
+ *          value[3] = u(29,2): TTI.  value[4] = u(31,26): TID.  word = u(1,32).
+ *     1,0  status is 0x3.  value[0] = u(17,7): subnetwork version.  value[1] = u(15,1): overlay capability.  word =
+ *          u(1,32).
+ *     1,7  status is 0.  word = u(1,28): bit 27 - k of word is MB bit k + 1.  MB bits 1 to 24 stand for these
+ *          registers, in this order: bits 1-6: 0,5 0,6 0,7 0,8 0,9 0,A; bits 7-8: 2,0 2,1; bits 9-15: 4,0 4,1 4,2 4,3
+ *          4,4 4,5 4,8; bits 16-23: 5,0 5,1 5,2 5,3 5,4 5,5 5,6 5,F; bit 24: 6,0.
+ *     2,0  status 0 and word 0.  The callsign is already in adsb_modes_rec.
+ *   OUTPUTS  adsb_commb_rec recs[n], index for index with the list, every byte of every record written; the
+ *     adsb_commb_header.
+ * Nothing depends on atomics or scheduling: two runs give the same bytes.
+ */
+#define ADSB_COMMB_NOT_COMMB 0u
+#define ADSB_COMMB_EMPTY 1u
+#define ADSB_COMMB_NONE 2u
+#define ADSB_COMMB_ONE 3u
+#define ADSB_COMMB_AMBIGUOUS 4u
+#define ADSB_COMMB_C10 0x1u
+#define ADSB_COMMB_C17 0x2u
+#define ADSB_COMMB_C20 0x4u
+#define ADSB_COMMB_C30 0x8u
+#define ADSB_COMMB_C40 0x10u
+#define ADSB_COMMB_C50 0x20u
+#define ADSB_COMMB_C60 0x40u
+typedef struct adsb_commb_rec {   /* 32 bytes */
+    uint8_t  state;               /* ADSB_COMMB_NOT_COMMB ...                                          */
+    uint8_t  bds;                 /* 0x10, 0x17, 0x20, 0x30, 0x40, 0x50, 0x60 with ONE; else 0         */
+    uint8_t  candidates;          /* ADSB_COMMB_C10 ...                                                */
+    uint8_t  n_candidates;
+    uint16_t status;
+    uint16_t reserved;            /* 0 */
+    int32_t  value[5];
+    uint32_t word;
+} adsb_commb_rec;
+typedef struct adsb_commb_header { /* 128 bytes */
+    uint64_t n, n_commb, n_empty, n_none, n_one, n_ambiguous;
+    uint64_t n_bds[7];            /* ONE records per register, in the order of the candidate bits */
+    uint64_t reserved[3];         /* 0 */
+} adsb_commb_header;
+#ifdef __cplusplus
+static_assert(sizeof(adsb_commb_rec) == 32 && sizeof(adsb_commb_header) == 128, "adsb_commb_rec / adsb_commb_header layout");
+#endif
+/* Infers and decodes.  frames[n] in host memory or in device memory of the ctx's device; n comes from the host, as for
+ * the other _of calls.  Asynchronous on the ctx's stream once a host list is copied.  Buffers are allocated on first
+ * use and grown when needed (may wait for earlier work): per frame 32 bytes of results, and 48 bytes per 256 frames of
+ * partial counts; a ctx that never calls it allocates nothing and launches exactly the kernels it launched before.
+ * Replaces the result of an earlier call; shares no buffer with another stage's result.  n = 0 is ADSB_OK.  ADSB_E_ARG
+ * for a NULL ctx or NULL frames with n > 0; ADSB_E_CAPACITY for n >= 2^32. */
+int adsb_commb_of(adsb_ctx *ctx, const adsb_frame *frames, size_t n);
+/* Waits and copies; recs may be NULL (with capacity 0) and receives min(header.n, max_recs) records; *header
+ * (optional) the totals, whatever the capacity.  ADSB_E_STATE before any adsb_commb_of; ADSB_E_ARG for a NULL ctx or
+ * NULL recs with a capacity. */
+int adsb_fetch_commb(adsb_ctx *ctx, adsb_commb_rec *recs, size_t max_recs, adsb_commb_header *header);
+/* For device-side consumers; does not synchronise.  The records and the header of the last adsb_commb_of in device
+ * memory (each optional), valid until the next call and ordered on the ctx's stream behind it.  ADSB_E_STATE before
+ * any adsb_commb_of. */
+int adsb_commb_device(adsb_ctx *ctx, const adsb_commb_rec **recs_dev, const void **header_dev);
+/* Threads (= frames) per workgroup of the stage's kernel: the size at which it takes another path, for tests.  The
+ * result does not depend on it. */
+int adsb_debug_commb_geometry(uint32_t *threads_per_block);
+
+/*
  * Multilaterate: where each correlated message was sent from, solved from the times its receivers heard it.  One small
  * non-linear least-squares problem per message, all messages of a list in one kernel; f64; stateless.
  *   INPUT  a correlate result msgs[M] / recs[N]; adsb_mlat_receiver receivers[R], 1 <= R <= 256, WGS84 degrees and

@@ -161,6 +161,19 @@ int adsb_host_modes(const adsb_frame *frames, size_t n, const uint64_t *counts, 
                     adsb_frame *squitters, uint64_t *squitter_counts, adsb_modes_header *header);
 
 /*
+ * CPU mirror of adsb_commb_of + adsb_fetch_commb (adsb_hip.h, "Comm-B registers"): the same records and header from
+ * the same program text as the device's, on one core, no device needed.  frames host memory; recs[n] and *header may
+ * each be NULL.  ADSB_E_ARG for NULL frames with n > 0; ADSB_E_CAPACITY for n >= 2^32.
+ * commb_as decodes the MB field of one frame as the register `bds` (0x10, 0x17, 0x20, 0x30, 0x40, 0x50, 0x60),
+ * whatever the inference says: *rec has state ONE, that bds and its values, with candidates and n_candidates as the
+ * inference fills them.  A consumer that knows more settles an AMBIGUOUS record with it; the usual one is a tracker
+ * that has the aircraft's ADS-B velocity.  ADSB_E_ARG for NULL bytes or rec, or a bds that is not among the frame's
+ * candidates (so for every frame that is not DF20/21 and every empty MB); *rec is then left as it was.
+ */
+int adsb_host_commb(const adsb_frame *frames, size_t n, adsb_commb_rec *recs, adsb_commb_header *header);
+int adsb_host_commb_as(const uint8_t bytes[14], uint32_t bds, adsb_commb_rec *rec);
+
+/*
  * CPU mirror of adsb_multilaterate_of (adsb_hip.h, "Multilaterate"): the same fixes and header from the same program text
  * as the device's -- the solver, and the 16 partial sums of every sum over receptions folded in the same butterfly -- on
  * one core, no device needed.  All arrays host memory; rx / n_rx may be NULL / 0 with ADSB_MLAT_TIME_RECEPTION; fixes

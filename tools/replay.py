@@ -14,6 +14,7 @@
   tools/replay.py capture.c16 --avr out.txt   # ... as AVR text, one "*...;" line per packet; --mlat: "@" + timestamp + ...
   tools/replay.py out.bin --beast-in          # FILE is a Beast capture (a receiver's TCP stream) instead of IQ
   tools/replay.py out.txt --avr-in            # ... an AVR text capture, "*" and "@" lines alike
+  tools/replay.py out.txt --avr-in --modes --commb   # one line per frame; DF20/21 lines with their Comm-B register
 
 Everything below the argument parsing is one call through the C ABI (adsb_replay_file, include/adsb_host.h).
 The "Processed Time" line carries no value (the reference prints the wall clock there).  With --aircraft, the frames
@@ -51,7 +52,12 @@ UNSUPPORTED), address, altitude in feet, squawk and callsign, "-" for a missing 
 and their Mode S records go through one device track table with a modes reserve (adsb_track_table_update_modes: keyed by
 the resolved address, so aircraft that only answer interrogations have a row; frames without an aircraft's address touch
 nothing) and the table is printed with five more columns: Alt(S), Squawk and Call(S) from the aircraft's newest replies
-that carry them, Replies, and S, which is "S" for an aircraft that has sent no DF17/18 frame.  The TEXT has not been compared with a Rust build's (there is no
+that carry them, Replies, and S, which is "S" for an aircraft that has sent no DF17/18 frame.  With --modes --commb
+every DF20/21 line also ends with the Comm-B register its MB field carries, inferred on the device from the 56 bits
+(adsb_commb_of, on the list where wire input left it): "BDS4,0 mcp=3008ft fms=3008ft baro=1020.0mb", the values whose
+status bit is set in feet, mb, degrees, kt, Mach, degrees per second and ft/min; for BDS 1,7 the registers the
+transponder reports; "?" and the candidates ("?5,0|6,0") where more than one register fits, "-" where none does or MB
+is empty.  The TEXT has not been compared with a Rust build's (there is no
 Rust toolchain); only the values are checked, against the oracle."""
 import argparse
 import json
@@ -217,29 +223,70 @@ def level_lines(d, st, frames, iq, piece=LEVELS_PIECE):
 WIRE_IN_CHUNK = 1 << 16  # bytes of a Beast / AVR capture parsed at a time
 
 
-def modes_lines(frames, recs):
-    """--modes: one line per frame from its MODES_DTYPE record."""
+COMMB_1_7 = ("0,5 0,6 0,7 0,8 0,9 0,A 2,0 2,1 4,0 4,1 4,2 4,3 4,4 4,5 4,8 5,0 5,1 5,2 5,3 5,4 5,5 5,6 5,F 6,0").split()
+COMMB_NAMES = {0x10: "1,0", 0x17: "1,7", 0x20: "2,0", 0x30: "3,0", 0x40: "4,0", 0x50: "5,0", 0x60: "6,0"}
+# --commb, registers with status bits: (label, key of commb_physical or None for the raw value, format) per value
+COMMB_FIELDS = {
+    0x40: (("mcp", "mcp_altitude_ft", "{:.0f}ft"), ("fms", "fms_altitude_ft", "{:.0f}ft"), ("baro", "baro_setting_mb", "{:.1f}mb"),
+           ("mode", None, "{}"), ("source", None, "{}")),
+    0x50: (("roll", "roll_deg", "{:.2f}"), ("track", "true_track_deg", "{:.2f}"), ("gs", "ground_speed_kt", "{:.0f}kt"),
+           ("rate", "track_rate_deg_s", "{:.3f}"), ("tas", "true_airspeed_kt", "{:.0f}kt")),
+    0x60: (("hdg", "magnetic_heading_deg", "{:.2f}"), ("ias", "ias_kt", "{:.0f}kt"), ("mach", "mach", "{:.3f}"),
+           ("baro", "baro_rate_ft_min", "{:.0f}ft/min"), ("inertial", "inertial_rate_ft_min", "{:.0f}ft/min")),
+}
+
+
+def commb_text(c):
+    """--commb: what one COMMB_DTYPE record adds to a DF20/21 line: "BDSr,n" and the register's values (those whose
+    status bit is set, in physical units), "?" and the candidates for AMBIGUOUS, "-" for an empty MB or no candidate."""
+    state = int(c["state"])
+    if state == A.ADSB_COMMB_AMBIGUOUS:
+        return "?" + "|".join(name for k, name in enumerate(COMMB_NAMES.values()) if int(c["candidates"]) >> k & 1)
+    if state != A.ADSB_COMMB_ONE:
+        return "-"
+    bds, value, word = int(c["bds"]), [int(v) for v in c["value"]], int(c["word"])
+    parts = ["BDS" + COMMB_NAMES[bds]]
+    if bds in COMMB_FIELDS:
+        phys = A.commb_physical(c)
+        for k, (label, key, fmt) in enumerate(COMMB_FIELDS[bds]):
+            if int(c["status"]) >> k & 1:
+                parts.append(label + "=" + fmt.format(value[k] if key is None else float(phys[key][0])))
+    elif bds == 0x17:
+        parts += [name for k, name in enumerate(COMMB_1_7) if word >> (27 - k) & 1]
+    elif bds == 0x10:
+        parts += [f"version={value[0]}", f"ovc={value[1]}"]
+    elif bds == 0x30:
+        parts += [f"ara={value[0]:04X}", f"rac={value[1]:X}", f"rat_mte={value[2]}", f"tti={value[3]}", f"tid={value[4]:07X}"]
+    return " ".join(parts)
+
+
+def modes_lines(frames, recs, commb=None):
+    """--modes: one line per frame from its MODES_DTYPE record; commb (one COMMB_DTYPE record per frame): the DF20/21
+    lines end with commb_text()."""
     out = []
-    for f, r in zip(frames, recs):
+    for j, (f, r) in enumerate(zip(frames, recs)):
         flags = int(r["flags"])
         alt = f"{int(r['altitude_ft'])}" if flags & A.ADSB_MODES_ALT else "-"
         squawk = f"{int(r['squawk']):04d}" if flags & A.ADSB_MODES_SQUAWK else "-"
         call = r["callsign"].decode("ascii", "replace").replace("_", " ").strip() if flags & A.ADSB_MODES_CALLSIGN else "-"
         addr = f"{int(r['address']):06X}" if int(r["kind"]) <= A.ADSB_MODES_UNKNOWN else "-"
+        more = "" if commb is None or int(r["df"]) not in (20, 21) else " " + commb_text(commb[j])
         out.append(f"{int(f['offset']) * SECONDS_PER_SAMPLE:.6f} DF{int(r['df'])} {A.MODES_KINDS[int(r['kind'])]} {addr} "
-                   f"{alt} {squawk} {call or '-'}\n")
+                   f"{alt} {squawk} {call or '-'}{more}\n")
     return "".join(out)
 
 
-def read_wire(d, path, wire_format, tick_bias, chunk=WIRE_IN_CHUNK, modes=False):
+def read_wire(d, path, wire_format, tick_bias, chunk=WIRE_IN_CHUNK, modes=False, commb=False):
     """--beast-in / --avr-in: (frames, their level records) of a Beast or AVR capture, parsed on the device chunk by
     chunk; what a chunk leaves unparsed (an incomplete last frame) goes in front of the next.  modes: short frames too,
     and (frames, their MODES_DTYPE records), each chunk resolved where it lies with the known addresses of the chunks
-    before it."""
+    before it.  commb (with modes): (frames, records, their COMMB_DTYPE records), from the same device list
+    (adsb_commb_of)."""
     import numpy as np
     frames, levels, tail = [np.zeros(0, dtype=A.FRAME_DTYPE)], [np.zeros(0, dtype=A.LEVEL_DTYPE)], b""
     if modes:
         recs, known = [np.zeros(0, dtype=A.MODES_DTYPE)], np.zeros(0, dtype=np.uint32)
+        regs = [np.zeros(0, dtype=A.COMMB_DTYPE)]
         with open(path, "rb") as fh:
             while True:
                 new = fh.read(chunk)
@@ -247,9 +294,13 @@ def read_wire(d, path, wire_format, tick_bias, chunk=WIRE_IN_CHUNK, modes=False)
                     break
                 got = d.wire_in_of(tail + new, format=wire_format, tick_bias=tick_bias, filter="short")
                 rec, known = d.modes_of((d.wire_in_device()[0], len(got.frames)), None, known)[:2]
+                if commb:
+                    regs.append(d.commb_of((d.wire_in_device()[0], len(got.frames)))[0])
                 frames.append(got.frames)
                 recs.append(rec)
                 tail = (tail + new)[int(got.consumed[0]):]
+        if commb:
+            return np.concatenate(frames), np.concatenate(recs), np.concatenate(regs)
         return np.concatenate(frames), np.concatenate(recs)
     with open(path, "rb") as fh:
         while True:
@@ -301,6 +352,8 @@ def main():
     ap.add_argument("--modes", action="store_true",
                     help="with --beast-in / --avr-in: short frames too; print DF, kind, address, altitude, squawk, callsign per "
                          "frame, or with --aircraft the table keyed by those addresses")
+    ap.add_argument("--commb", action="store_true",
+                    help="with --modes: every DF20/21 line also gets the Comm-B register inferred from its MB field and its values")
     ap.add_argument("--tick-bias", type=int, default=0, metavar="N", help="added to every timestamp (12 MHz ticks, < 2^48)")
     a = ap.parse_args()
     if a.mlat and not a.avr:
@@ -314,6 +367,8 @@ def main():
     wire_in = "beast" if a.beast_in else "avr" if a.avr_in else None
     if a.modes and not wire_in:
         ap.error("--modes needs --beast-in or --avr-in")
+    if a.commb and (not a.modes or a.aircraft):
+        ap.error("--commb needs --modes, without --aircraft")
     if wire_in and a.levels and not a.aircraft:
         ap.error("--levels alone needs the samples")
     fmt = a.format or ("c16" if a.file.endswith(".c16") else "u8")
@@ -322,12 +377,12 @@ def main():
     with A.AdsbDemod(device=a.device, sample_type=st, max_samples=a.chunk + 240, max_out=a.chunk + 240,
                      host_staging=False) as d:
         if wire_in and a.modes:
-            frames, recs = read_wire(d, a.file, wire_in, a.tick_bias, modes=True)
+            frames, recs, *regs = read_wire(d, a.file, wire_in, a.tick_bias, modes=True, commb=a.commb)
             if a.aircraft:
                 n_samp = int(frames["offset"].max()) + A.WINDOW if len(frames) else 0
                 sys.stdout.write(aircraft_table(d, frames, n_samp, site=a.site, modes=recs))
             else:
-                sys.stdout.write(modes_lines(frames, recs))
+                sys.stdout.write(modes_lines(frames, recs, regs[0] if a.commb else None))
             if a.summary:
                 print(f"{os.path.getsize(a.file)} bytes, {len(frames)} frames", file=sys.stderr)
             return
