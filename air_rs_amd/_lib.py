@@ -396,6 +396,33 @@ AIRCRAFT_MODES_DTYPE = np.dtype([("altitude_time", "<f8"), ("squawk_time", "<f8"
                                  ("n_airair", "<u4"), ("fs", "u1"), ("last_df", "u1"), ("reserved", "u1", (6,))])
 assert AIRCRAFT_MODES_DTYPE.itemsize == C.sizeof(AdsbAircraftModes) == 64
 
+ADSB_COMMB_SETTLED = 5              # adsb_commb_rec.state, only in a table's per-frame output (update_commb)
+
+
+class AdsbCommbSettleCfg(C.Structure):
+    """adsb_commb_settle_cfg: the limits a table settles 5,0 against 6,0 with (16 bytes)."""
+    _fields_ = [("max_age_s", C.c_double), ("max_speed_diff_kt", C.c_uint32), ("max_vrate_diff_fpm", C.c_uint32)]
+
+
+class AdsbCommbBlock(C.Structure):
+    """adsb_commb_block: the newest values of one register of an aircraft (32 bytes)."""
+    _fields_ = [("time", C.c_double), ("value", C.c_int32 * 5), ("status", C.c_uint16), ("settled", C.c_uint16)]
+
+
+class AdsbAircraftCommb(C.Structure):
+    """adsb_aircraft_commb: what an aircraft's Comm-B replies say, beside its record (tables with a commb reserve)."""
+    _fields_ = [("bds40", AdsbCommbBlock), ("bds50", AdsbCommbBlock), ("bds60", AdsbCommbBlock),
+                ("n_commb", C.c_uint32), ("n_settled", C.c_uint32), ("n_ambiguous", C.c_uint32), ("n_none", C.c_uint32),
+                ("capability", C.c_uint32), ("ra_word", C.c_uint32), ("ra_time", C.c_double)]
+
+
+COMMB_BLOCK_DTYPE = np.dtype([("time", "<f8"), ("value", "<i4", (5,)), ("status", "<u2"), ("settled", "<u2")])
+AIRCRAFT_COMMB_DTYPE = np.dtype([("bds40", COMMB_BLOCK_DTYPE), ("bds50", COMMB_BLOCK_DTYPE), ("bds60", COMMB_BLOCK_DTYPE),
+                                 ("n_commb", "<u4"), ("n_settled", "<u4"), ("n_ambiguous", "<u4"), ("n_none", "<u4"),
+                                 ("capability", "<u4"), ("ra_word", "<u4"), ("ra_time", "<f8")])
+assert C.sizeof(AdsbCommbSettleCfg) == 16 and COMMB_BLOCK_DTYPE.itemsize == C.sizeof(AdsbCommbBlock) == 32
+assert AIRCRAFT_COMMB_DTYPE.itemsize == C.sizeof(AdsbAircraftCommb) == 128
+
 
 class AdsbTrackBankCfg(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("n_receivers", C.c_uint32), ("max_aircraft", C.c_uint32),
@@ -538,6 +565,12 @@ PROTOTYPES = {
                                                 C.c_uint64]),
     "adsb_track_table_fetch_modes": (C.c_int, [C.c_void_p, _P(AdsbAircraftModes), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_table_modes_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "adsb_track_table_commb_reserve": (C.c_int, [C.c_void_p, _P(AdsbCommbSettleCfg)]),
+    "adsb_track_table_update_commb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_size_t, C.c_uint64]),
+    "adsb_track_table_fetch_commb": (C.c_int, [C.c_void_p, _P(AdsbAircraftCommb), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_fetch_frame_commb": (C.c_int, [C.c_void_p, _P(AdsbCommbRec), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_commb_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "adsb_track_bank_fixes_reserve": (C.c_int, [C.c_void_p, _P(AdsbSite)]),
     "adsb_track_bank_fetch_fixes": (C.c_int, [C.c_void_p, _P(AdsbFix), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_bank_fixes_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
@@ -641,6 +674,11 @@ PROTOTYPES = {
                                           _P(AdsbAircraftMlat), _P(C.c_uint32), _P(C.c_float)]),
     "adsb_host_track_modes_of": (C.c_int, [C.c_void_p, C.c_double, _P(AdsbAircraftModes), _P(C.c_uint32)]),
     "adsb_host_track_modes_merge": (C.c_int, [_P(AdsbAircraftModes), _P(AdsbAircraftModes)]),
+    "adsb_host_commb_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, _P(AdsbCommbSettleCfg),
+                                         C.c_void_p]),
+    "adsb_host_commb_reference": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "adsb_host_track_commb_of": (C.c_int, [C.c_void_p, C.c_double, _P(AdsbAircraftCommb)]),
+    "adsb_host_track_commb_merge": (C.c_int, [_P(AdsbAircraftCommb), _P(AdsbAircraftCommb)]),
 }
 
 _lib = None

@@ -406,6 +406,8 @@ struct TrackStoreDev {
     unsigned long long *mark;    // [n] per sorted frame: segment head << 32 | head of a key the hash does not hold
     unsigned long long *excl;    // [n] exclusive scan of mark
     uint32_t *seg_slot;          // [n] per segment (hi of the scan): record slot + 1 (kTrackUntracked)
+    // table only, last so that no other member moves
+    adsb_aircraft_commb *commb;  // [max_aircraft] beside rec, or null: no commb reserve (likewise; tables only)
 };
 // Per-frame summaries and the changed list of a table / bank update (adsb_track_*_summaries_reserve): all of it
 // allocated by the reserve.  One segmented inclusive max-scan over the sorted list gives every frame the sorted
@@ -488,6 +490,30 @@ struct TrackModesTuple {
     uint32_t n_replies, n_allcall, n_surveillance, n_airair;
 };
 static_assert(sizeof(TrackModesTuple) == 48, "TrackModesTuple: the header's memory figures assume 48 bytes");
+// Comm-B registers per aircraft (adsb_track_table_commb_reserve; adsb_track_commb.h has the rule, the per-frame text
+// and the combine): all of it allocated by the reserve.  A segmented scan of TrackCommbRefTuple gives every sorted frame
+// its aircraft's newest velocity frame up to it (the frame kernel reads its predecessor's: the exclusive scan); one
+// thread per sorted frame settles, writes the per-frame output at the list index and the second scan's operand at the
+// sorted position; one segmented inclusive scan; one thread per segment tail merges into store->commb.  Integers only.
+struct TrackCommbRefTuple {
+    uint32_t head;               // the operand holds a segment head
+    uint32_t vel;                // sorted position + 1 of the newest velocity frame, 0 = none
+};
+struct TrackCommbTuple {
+    uint32_t head;
+    uint32_t newest[5];          // sorted position + 1 of the newest counted frame of sort 4,0 / 5,0 / 6,0 / 1,7 / 3,0
+    uint32_t n_commb, n_settled, n_ambiguous, n_none;
+};
+static_assert(sizeof(TrackCommbTuple) == 40 && sizeof(TrackCommbRefTuple) == 8, "the header's memory figures");
+struct TrackCommbDev {
+    TrackCommbRefTuple *ref;     // [max_frames]: the first scan's output, sorted order
+    adsb_commb_rec *out;         // [max_frames]: the per-frame output of the last update_commb, list order
+    TrackCommbTuple *in;         // [max_frames]: the second scan's operands, sorted order
+    TrackCommbTuple *scan;       // [max_frames]: its output, sorted order
+    void *temp;                  // both scans' scratch
+    size_t temp_bytes;
+    adsb_commb_settle_cfg cfg;   // the reserve's
+};
 struct TrackModesDev {
     TrackModesTuple *in;         // [max_frames]: the scan's operands, sorted order
     TrackModesTuple *scan;       // [max_frames]: the scan's output, sorted order
@@ -517,6 +543,8 @@ struct TrackArgs {
     const TrackFixDev *fix;      // non-null (with store->fix and store->site): also the per-frame fixes and their merge
     const adsb_mlat_fix *mlat_fixes; // [n] (device), list order: with mlat non-null (and store->mlat), merged into the
     const TrackMlatDev *mlat;    // per-aircraft mlat records; null: the mlat records stay as they are
+    const adsb_commb_rec *commb_recs; // [n] (device), list order: with commb non-null (and modes, store->commb): the
+    const TrackCommbDev *commb;       // commb step after the modes merge (update_commb); null: the commb records stay
     const adsb_modes_rec *modes_recs; // [n] (device), list order: with modes non-null (and store->modes; tables only)
     const TrackModesDev *modes;  // the list is keyed by the records' addresses (update_modes); null: by bytes[1..3]
     adsb_packet_fields *modes_fields; // = fields, writable: update_modes makes every other DF a frame of kind "other"
@@ -552,6 +580,9 @@ hipError_t launch_track_mlat_clear(hipStream_t s, adsb_aircraft_mlat *mlat, size
 size_t track_modes_temp_bytes(size_t n); // the 25-bit sort, the admission scan and the modes scan
 // every modes record of [0, places) empty: zeros, the three times NaN (the modes reserve, and reset)
 hipError_t launch_track_modes_clear(hipStream_t s, adsb_aircraft_modes *modes, size_t places);
+size_t track_commb_temp_bytes(size_t n); // the two commb scans
+// every commb record of [0, places) empty: zeros, every time NaN (the commb reserve, and reset)
+hipError_t launch_track_commb_clear(hipStream_t s, adsb_aircraft_commb *commb, size_t places);
 // out[k] = rec[sum.changed[k]] for k < min(*sum.n_changed, max_n): the changed list's records, gathered on the device
 hipError_t launch_track_changed(hipStream_t s, const TrackRecord *rec, const TrackSumDev &sum, uint32_t max_n,
                                 TrackRecord *out);

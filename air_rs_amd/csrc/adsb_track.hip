@@ -108,6 +108,14 @@
 // position; one segmented inclusive scan (48-byte tuple, integers only); one thread per segment tail builds the
 // segment's part from the winning frames' records and merges it into the side record.  Admission and expire treat the
 // array as they treat the other three.  Tables only.
+//
+// Comm-B registers per aircraft (adsb_track_table_commb_reserve; the update_commb form): a fifth side array, one 128-byte
+// adsb_aircraft_commb per record place.  After everything update_modes launches and BEFORE the merge into the main
+// records (track_summary_kernel overwrites rec.vel, and the settle reads the velocity held from before this update): one
+// segmented scan gives every sorted frame its aircraft's newest velocity frame up to it, one thread per frame settles an
+// ambiguous {5,0; 6,0} record against the newest EARLIER one (its predecessor's scan word) or the held velocity
+// (adsb_track_commb.h), writes the per-frame output at the list index and a 40-byte operand at the sorted position, one
+// segmented inclusive scan, one thread per segment tail merges into the side record.  Tables only.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -117,6 +125,7 @@
 #include "adsb_fix.h"
 #include "adsb_kernels.h"
 #include "adsb_track_mlat.h"
+#include "adsb_track_commb.h"
 #include "adsb_track_modes.h"
 
 namespace adsbk {
@@ -309,6 +318,7 @@ __global__ __launch_bounds__(256) void track_admit_kernel(const uint32_t *skeys,
     if (t.fix) ((FixWords *)t.fix)[r] = fix_empty();
     if (t.mlat) ((MlatWords *)t.mlat)[r] = mlat_empty();
     if (t.modes) ((ModesWords *)t.modes)[r] = modes_empty();
+    if (t.commb) ((CommbWords *)t.commb)[r] = commb_empty();
 }
 
 // bank only: the receiver split clipped to the list (prefix[0] = 0, prefix[k] = n for k >= n_src), as adsb_fetch's
@@ -1194,6 +1204,170 @@ __global__ __launch_bounds__(256) void track_modes_clear_kernel(ModesWords *mode
     if (p < places) modes[p] = modes_empty();
 }
 
+// ---- Comm-B registers per aircraft (table with a modes and a commb reserve) ------------------------------------------
+// The first scan's input at sorted position s, computed where the scan loads it: s + 1 if the frame is an airborne-
+// velocity message by the merge's own test (track_summary_kernel: type code 19 of a frame the key kernel left a
+// squitter, ST 1-4), of an accepted frame
+struct CommbRefInput {
+    const uint32_t *skeys, *svals;
+    const adsb_packet_fields *fields;
+    const adsb_frame *frames;
+    __device__ __forceinline__ TrackCommbRefTuple operator()(uint32_t s) const
+    {
+        TrackCommbRefTuple v;
+        const uint32_t key = skeys[s], j = svals[s];
+        v.head = (s == 0 || skeys[s - 1] != key) ? 1u : 0u;
+        v.vel = 0u;
+        if (key < kModesNoAddress && fields[j].msg_type == 19) {
+            const uint32_t st = frames[j].bytes[4] & 7u;
+            if (st >= 1 && st <= 4) v.vel = s + 1u;
+        }
+        return v;
+    }
+};
+
+struct CommbRefOp {
+    __device__ __forceinline__ TrackCommbRefTuple operator()(const TrackCommbRefTuple &l, const TrackCommbRefTuple &r) const
+    {
+        TrackCommbRefTuple o = r;
+        if (!r.head) {
+            o.head = l.head;
+            o.vel = l.vel > r.vel ? l.vel : r.vel;
+        }
+        return o;
+    }
+};
+
+// One thread per sorted frame s (svals[s] < n, a permutation of the list; d.slot[s] - 1 < max_aircraft unless
+// kTrackUntracked; ref[s - 1].vel - 1 < s is a sorted position of the same segment).  Runs before track_summary_kernel:
+// d.rec[slot - 1].vel is the velocity held from before this update (admission emptied a new aircraft's).
+__global__ __launch_bounds__(256) void track_commb_frame_kernel(const adsb_frame *frames, const adsb_commb_rec *commb,
+                                                                const uint32_t *skeys, const uint32_t *svals, uint32_t n,
+                                                                double seconds_per_sample, uint64_t sample_base,
+                                                                TrackStoreDev d, const TrackCommbRefTuple *ref,
+                                                                adsb_commb_settle_cfg cfg, adsb_commb_rec *out,
+                                                                TrackCommbTuple *in)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s], i = svals[s];
+    adsb_commb_rec o = commb[i];
+    TrackCommbTuple v{};
+    v.head = (s == 0 || skeys[s - 1] != key) ? 1u : 0u;
+    const uint32_t slot = d.slot[s];
+    if (key < kModesNoAddress && slot != kTrackUntracked && o.state != ADSB_COMMB_NOT_COMMB) { // counted
+        if (commb_can_settle(o)) {
+            const uint32_t p = v.head ? 0u : ref[s - 1].vel;
+            CommbRef r;
+            if (p) {
+                const uint32_t j = svals[p - 1];
+                r = commb_ref_of_frame(modes_bytes(frames[j].bytes), frame_time(frames, j, sample_base, seconds_per_sample));
+            } else {
+                r = commb_ref_of_velocity(d.rec[slot - 1].vel);
+            }
+            o = commb_settle(modes_bytes(frames[i].bytes), o, r, frame_time(frames, i, sample_base, seconds_per_sample), cfg);
+        }
+        const uint32_t sort = commb_sort_of(o), at = s + 1u;
+        v.newest[0] = sort == kCommbSort40 ? at : 0u;
+        v.newest[1] = sort == kCommbSort50 ? at : 0u;
+        v.newest[2] = sort == kCommbSort60 ? at : 0u;
+        v.newest[3] = sort == kCommbSort17 ? at : 0u;
+        v.newest[4] = sort == kCommbSort30 ? at : 0u;
+        const CommbCounts c = commb_counts_of(o);
+        v.n_commb = c.n_commb;
+        v.n_settled = c.n_settled;
+        v.n_ambiguous = c.n_ambiguous;
+        v.n_none = c.n_none;
+    }
+    out[i] = o;
+    in[s] = v;
+}
+
+struct CommbOp {
+    __device__ __forceinline__ TrackCommbTuple operator()(const TrackCommbTuple &l, const TrackCommbTuple &r) const
+    {
+        TrackCommbTuple o = r;
+        if (!r.head) {
+            o.head = l.head;
+            o.newest[0] = l.newest[0] > r.newest[0] ? l.newest[0] : r.newest[0];
+            o.newest[1] = l.newest[1] > r.newest[1] ? l.newest[1] : r.newest[1];
+            o.newest[2] = l.newest[2] > r.newest[2] ? l.newest[2] : r.newest[2];
+            o.newest[3] = l.newest[3] > r.newest[3] ? l.newest[3] : r.newest[3];
+            o.newest[4] = l.newest[4] > r.newest[4] ? l.newest[4] : r.newest[4];
+            o.n_commb = sat_add32(l.n_commb, r.n_commb);
+            o.n_settled = sat_add32(l.n_settled, r.n_settled);
+            o.n_ambiguous = sat_add32(l.n_ambiguous, r.n_ambiguous);
+            o.n_none = sat_add32(l.n_none, r.n_none);
+        }
+        return o;
+    }
+};
+
+// One thread per segment tail with a counted frame: the segment's part (adsb_track_commb.h) from the winning frames'
+// per-frame outputs and times, merged into the aircraft's commb record.  Every position is <= n: a sorted position + 1.
+__global__ __launch_bounds__(256) void track_commb_merge_kernel(const adsb_frame *frames, const adsb_commb_rec *out,
+                                                                const uint32_t *skeys, const uint32_t *svals, uint32_t n,
+                                                                double seconds_per_sample, uint64_t sample_base,
+                                                                TrackStoreDev d, const TrackCommbTuple *scan)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s];
+    if (s + 1 != n && skeys[s + 1] == key) return;
+    const uint32_t slot = d.slot[s];
+    if (key >= kModesNoAddress || slot == kTrackUntracked) return;
+    const TrackCommbTuple w = scan[s];
+    if (!w.n_commb) return; // nothing counted: the record stays
+    const uint32_t p40 = w.newest[0], p50 = w.newest[1], p60 = w.newest[2], p17 = w.newest[3], p30 = w.newest[4];
+    const uint32_t i40 = p40 ? svals[p40 - 1] : 0u, i50 = p50 ? svals[p50 - 1] : 0u, i60 = p60 ? svals[p60 - 1] : 0u,
+                   i30 = p30 ? svals[p30 - 1] : 0u;
+    CommbCounts c;
+    c.n_commb = w.n_commb;
+    c.n_settled = w.n_settled;
+    c.n_ambiguous = w.n_ambiguous;
+    c.n_none = w.n_none;
+    const adsb_aircraft_commb part =
+        commb_part(c, p40 ? out + i40 : nullptr, p40 ? frame_time(frames, i40, sample_base, seconds_per_sample) : 0.0,
+                   p50 ? out + i50 : nullptr, p50 ? frame_time(frames, i50, sample_base, seconds_per_sample) : 0.0,
+                   p60 ? out + i60 : nullptr, p60 ? frame_time(frames, i60, sample_base, seconds_per_sample) : 0.0,
+                   p17 ? out + svals[p17 - 1] : nullptr, p30 ? out + i30 : nullptr,
+                   p30 ? frame_time(frames, i30, sample_base, seconds_per_sample) : 0.0);
+    CommbWords words = ((const CommbWords *)d.commb)[slot - 1];
+    adsb_aircraft_commb a;
+    __builtin_memcpy(&a, &words, sizeof(a));
+    commb_merge(a, part);
+    __builtin_memcpy(&words, &a, sizeof(a));
+    ((CommbWords *)d.commb)[slot - 1] = words;
+}
+
+hipError_t launch_commb_merge(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d)
+{
+    const TrackCommbDev &cb = *a.commb;
+    const dim3 grid((a.n + 255) / 256);
+    const auto in = rocprim::make_transform_iterator(
+        rocprim::counting_iterator<uint32_t>(0u),
+        CommbRefInput{(const uint32_t *)a.skeys, (const uint32_t *)a.svals, a.fields, a.frames});
+    size_t tb = cb.temp_bytes;
+    hipError_t e = rocprim::inclusive_scan(cb.temp, tb, in, cb.ref, (size_t)a.n, CommbRefOp(), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(track_commb_frame_kernel, grid, dim3(256), 0, st, a.frames, a.commb_recs, (const uint32_t *)a.skeys,
+                       (const uint32_t *)a.svals, a.n, a.seconds_per_sample, a.sample_base, d,
+                       (const TrackCommbRefTuple *)cb.ref, cb.cfg, cb.out, cb.in);
+    tb = cb.temp_bytes;
+    e = rocprim::inclusive_scan(cb.temp, tb, (const TrackCommbTuple *)cb.in, cb.scan, (size_t)a.n, CommbOp(), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(track_commb_merge_kernel, grid, dim3(256), 0, st, a.frames, (const adsb_commb_rec *)cb.out,
+                       (const uint32_t *)a.skeys, (const uint32_t *)a.svals, a.n, a.seconds_per_sample, a.sample_base, d,
+                       (const TrackCommbTuple *)cb.scan);
+    return hipSuccess;
+}
+
+__global__ __launch_bounds__(256) void track_commb_clear_kernel(CommbWords *commb, uint64_t places)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < places) commb[p] = commb_empty();
+}
+
 // expire, 1: keep[g] = 1 for a record in use whose last frame is not older than the cut (last_heard < before evicts).
 // Record g is slot i of receiver r (a table: r = 0).  Slot 0 stages the old size where the compaction kernel reads it
 // (size_next[r]), since that kernel writes the new one; the pairs kernel of an update has consumed its own staging before
@@ -1249,6 +1423,7 @@ __global__ __launch_bounds__(256) void track_expire_compact_kernel(TrackStoreDev
     if (d.fix) ((FixWords *)d.fix)[g] = ((const FixWords *)d.fix)[base + lo];
     if (d.mlat) ((MlatWords *)d.mlat)[g] = ((const MlatWords *)d.mlat)[base + lo];
     if (d.modes) ((ModesWords *)d.modes)[g] = ((const ModesWords *)d.modes)[base + lo];
+    if (d.commb) ((CommbWords *)d.commb)[g] = ((const CommbWords *)d.commb)[base + lo];
     if (!kBank) d.index[moved.a.icao] = i + 1u;
 }
 
@@ -1645,6 +1820,25 @@ size_t track_modes_temp_bytes(size_t n)
     return (most > scan_bytes ? most : scan_bytes) + 256;
 }
 
+size_t track_commb_temp_bytes(size_t n)
+{
+    size_t ref_bytes = 0, scan_bytes = 0;
+    const auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u),
+                                                     CommbRefInput{nullptr, nullptr, nullptr, nullptr});
+    (void)rocprim::inclusive_scan(nullptr, ref_bytes, in, (TrackCommbRefTuple *)nullptr, n, CommbRefOp(), (hipStream_t)0);
+    (void)rocprim::inclusive_scan(nullptr, scan_bytes, (const TrackCommbTuple *)nullptr, (TrackCommbTuple *)nullptr, n,
+                                  CommbOp(), (hipStream_t)0);
+    return (ref_bytes > scan_bytes ? ref_bytes : scan_bytes) + 256;
+}
+
+hipError_t launch_track_commb_clear(hipStream_t st, adsb_aircraft_commb *commb, size_t places)
+{
+    if (places == 0) return hipSuccess;
+    hipLaunchKernelGGL(track_commb_clear_kernel, dim3((uint32_t)((places + 255) / 256)), dim3(256), 0, st,
+                       (CommbWords *)commb, (uint64_t)places);
+    return hipGetLastError();
+}
+
 hipError_t launch_track_modes_clear(hipStream_t st, adsb_aircraft_modes *modes, size_t places)
 {
     if (places == 0) return hipSuccess;
@@ -1710,6 +1904,8 @@ hipError_t track_tail(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d
         if constexpr (K == TrackKind::kTable) {
             if (e != hipSuccess) return e;
             if (a.modes && d.modes) e = launch_modes_merge(st, a, d); // after every kernel that writes a per-frame icao
+            if (e != hipSuccess) return e;
+            if (a.commb && a.modes && d.commb && d.modes) e = launch_commb_merge(st, a, d); // before the merge: rec.vel
         }
     } else {
         size_t tb = a.temp_bytes;

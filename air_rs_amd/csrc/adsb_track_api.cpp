@@ -113,7 +113,7 @@ struct TrackStore {
     uint32_t n_receivers = 0, max_aircraft = 0; // max_aircraft: per receiver
     // One block of device memory per lifetime, carved into the arrays below (adsb_scratch.h): the store's own from
     // create to destroy, and one per reserve.  Every device pointer of the store points into one of them.
-    DevBuf<char> mem, sum_mem, lvl_mem, fix_mem, mlat_mem, modes_mem;
+    DevBuf<char> mem, sum_mem, lvl_mem, fix_mem, mlat_mem, modes_mem, commb_mem;
     adsbk::TrackStoreDev dev{};     // records [R x max_aircraft], slot [max_frames]; index [2^24] or hash, prefix, scan words
     uint32_t *words = nullptr;      // [3R]: size, flags, size_next (dev.size / dev.flags / dev.size_next)
     uint32_t *u32 = nullptr;        // 4 x [max_frames]: keys, vals, sorted keys, sorted vals
@@ -149,6 +149,12 @@ struct TrackStore {
     adsbk::TrackModesDev modes{};
     adsb_modes_rec *modes_recs = nullptr;   // [max_frames]: device copy of a host recs array
     adsb_modes_rec *modes_pinned = nullptr; // [max_frames]: pinned staging of that copy (s.copied covers it too)
+    // Comm-B registers per aircraft (adsb_track_table_commb_reserve): all of it made by the reserve; dev.commb null = none
+    adsbk::TrackCommbDev commb{};
+    adsb_commb_rec *commb_recs = nullptr;   // [max_frames]: device copy of a host commb array
+    adsb_commb_rec *commb_pinned = nullptr; // [max_frames]: pinned staging of that copy (s.copied covers it too)
+    uint32_t commb_n = 0;                   // frames of the last update_commb
+    bool commb_updated = false;             // an update_commb ran since the reserve (and since the last reset)
 
     size_t places() const { return (size_t)n_receivers * max_aircraft; }
 };
@@ -227,6 +233,16 @@ static void store_modes_drop(TrackStore &s)
     s.modes_recs = nullptr;
 }
 
+// The commb reserve undone, under the same condition.
+static void store_commb_drop(TrackStore &s)
+{
+    drop(s.commb_mem);
+    pinned_free(s.commb_pinned);
+    s.dev.commb = nullptr;
+    s.commb = {};
+    s.commb_recs = nullptr;
+}
+
 // Sizes, and the store's own block: what a table and a bank share, then what each kind adds (a bank has set
 // dev.hash_mask).  false: an allocation failed (the caller releases what was made)
 static bool store_alloc(TrackStore &s, adsb_ctx *c, TrackKind kind, uint32_t n_receivers, uint32_t max_aircraft, uint64_t max_frames,
@@ -283,6 +299,7 @@ static void store_release(TrackStore &s)
     drop(s.fix_mem);
     drop(s.mlat_mem);
     store_modes_drop(s);
+    store_commb_drop(s);
     pinned_free(s.pinned);
     pinned_free(s.lvl_pinned);
     pinned_free(s.mlat_pinned);
@@ -302,7 +319,9 @@ static int store_reset(TrackStore *s)
     if (s->dev.fix) HIPCHK(adsbk::launch_track_fixes_clear(s->ctx->aux, s->dev.fix, s->places()));
     if (s->dev.mlat) HIPCHK(adsbk::launch_track_mlat_clear(s->ctx->aux, s->dev.mlat, s->places()));
     if (s->dev.modes) HIPCHK(adsbk::launch_track_modes_clear(s->ctx->aux, s->dev.modes, s->places()));
+    if (s->dev.commb) HIPCHK(adsbk::launch_track_commb_clear(s->ctx->aux, s->dev.commb, s->places()));
     s->mlat_updated = false;
+    s->commb_updated = false;
     s->n_points = 0;
     s->updated = false;
     s->sum.updated = s->sum.changed_valid = false;
@@ -357,6 +376,14 @@ static int store_stage_modes(TrackStore &s, const adsb_modes_rec *host, size_t n
     return ADSB_OK;
 }
 
+// The same for a host commb array (update_commb), under the same event
+static int store_stage_commb(TrackStore &s, const adsb_commb_rec *host, size_t n)
+{
+    std::memcpy(s.commb_pinned, host, sizeof(adsb_commb_rec) * n);
+    HIPCHK(hipMemcpyAsync(s.commb_recs, s.commb_pinned, sizeof(adsb_commb_rec) * n, hipMemcpyHostToDevice, s.ctx->aux));
+    return ADSB_OK;
+}
+
 // The bookkeeping every update starts with (an empty one too: no summaries, an empty changed list); false: n == 0,
 // nothing to launch
 static bool store_begin_update(TrackStore &s, size_t n)
@@ -371,10 +398,11 @@ static bool store_begin_update(TrackStore &s, size_t n)
 // field decode (same stream); dev: s.dev, or a bank's copy of it with this update's receiver split; levels (device,
 // or null): also the level merge; mlat_fixes (device, or null): also the mlat merge; recs (device, or null): the list is
 // keyed by the records' addresses and the modes merge runs too (update_modes), with the modes reserve's scratch, which
-// holds the 25-bit sort
+// holds the 25-bit sort; commb (device, or null; only with recs): the commb step runs too (update_commb)
 static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t sample_base,
                      const adsbk::TrackStoreDev &dev, const adsb_frame_level *levels = nullptr,
-                     const adsb_mlat_fix *mlat_fixes = nullptr, const adsb_modes_rec *recs = nullptr)
+                     const adsb_mlat_fix *mlat_fixes = nullptr, const adsb_modes_rec *recs = nullptr,
+                     const adsb_commb_rec *commb = nullptr)
 {
     HIPCHK(adsbk::launch_decode_fields(s.ctx->aux, list, nullptr, (uint32_t)n, s.fields));
     adsbk::TrackArgs a = track_args(s.kind, list, s.fields, n, s.seconds_per_sample, s.u32, (size_t)s.max_frames,
@@ -393,6 +421,10 @@ static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t s
         a.modes_fields = s.fields;
         a.temp = s.modes.temp;
         a.temp_bytes = s.modes.temp_bytes;
+        if (commb) {
+            a.commb_recs = commb;
+            a.commb = &s.commb;
+        }
     }
     HIPCHK(adsbk::launch_track(s.ctx->aux, a));
     return ADSB_OK;
@@ -407,6 +439,7 @@ static const adsb_aircraft_level *levels_of(TrackStore &s) { return s.dev.lvl; }
 static const adsb_fix *fixes_of(TrackStore &s) { return s.dev.fix; }
 static const adsb_aircraft_mlat *mlat_of(TrackStore &s) { return s.dev.mlat; }
 static const adsb_aircraft_modes *modes_of(TrackStore &s) { return s.dev.modes; }
+static const adsb_aircraft_commb *commb_of(TrackStore &s) { return s.dev.commb; }
 
 template <class T>
 static int store_device(TrackStore *s, const T *of(TrackStore &), const T **dev)
@@ -712,6 +745,34 @@ static int store_modes_reserve(TrackStore *st)
     return ADSB_OK;
 }
 
+// ---- Comm-B registers per aircraft ------------------------------------------------------------------------------------
+// Waits for the device (the clear); a second reserve keeps what the first one made, its cfg too
+static int store_commb_reserve(TrackStore *st, const adsb_commb_settle_cfg &cfg)
+{
+    HIPCHK(hipSetDevice(st->ctx->cfg.device));
+    if (st->dev.commb) return ADSB_OK;
+    const size_t nf = (size_t)st->max_frames;
+    st->commb.temp_bytes = adsbk::track_commb_temp_bytes(nf);
+    st->commb.cfg = cfg;
+    const int rc = carve_block(st->ctx, st->commb_mem, [&](Carve &k) {
+        st->dev.commb = k.take<adsb_aircraft_commb>(st->places());
+        st->commb.ref = k.take<adsbk::TrackCommbRefTuple>(nf);
+        st->commb.out = k.take<adsb_commb_rec>(nf);
+        st->commb.in = k.take<adsbk::TrackCommbTuple>(nf);
+        st->commb.scan = k.take<adsbk::TrackCommbTuple>(nf);
+        st->commb.temp = k.take<char>(st->commb.temp_bytes);
+        st->commb_recs = k.take<adsb_commb_rec>(nf);
+    });
+    if (rc != ADSB_OK || !pinned_make(st->commb_pinned, nf) ||
+        adsbk::launch_track_commb_clear(st->ctx->aux, st->dev.commb, st->places()) != hipSuccess ||
+        hipStreamSynchronize(st->ctx->aux) != hipSuccess) {
+        (void)hipGetLastError();
+        store_commb_drop(*st);
+        return ADSB_E_NOMEM;
+    }
+    return ADSB_OK;
+}
+
 // ---- persistent aircraft table (adsb_track_table_*) ------------------------------------------------------------------
 static void track_table_free(adsb_track_table *t)
 {
@@ -742,10 +803,10 @@ extern "C" void adsb_track_table_destroy(adsb_track_table *t)
 }
 
 // levels: null for the plain update; fixes: null unless update_mlat (or update_modes with fixes); recs: null unless
-// update_modes
+// update_modes; commb: null unless update_commb
 static int track_table_update(adsb_track_table *t, const adsb_frame *frames, const adsb_frame_level *levels, size_t n,
                               uint64_t sample_base, const adsb_mlat_fix *fixes = nullptr,
-                              const adsb_modes_rec *recs = nullptr)
+                              const adsb_modes_rec *recs = nullptr, const adsb_commb_rec *commb = nullptr)
 {
     if (n > t->max_frames) return ADSB_E_CAPACITY;
     adsb_ctx *c = t->ctx;
@@ -758,20 +819,27 @@ static int track_table_update(adsb_track_table *t, const adsb_frame *frames, con
     const adsb_frame *list = frames;
     const bool frames_host = !in_device_memory(c, frames), levels_host = levels && !in_device_memory(c, levels);
     const bool fixes_host = fixes && !in_device_memory(c, fixes), recs_host = recs && !in_device_memory(c, recs);
-    if (frames_host || levels_host || fixes_host || recs_host) {
+    const bool commb_host = commb && !in_device_memory(c, commb);
+    if (commb) { // the list fetch_frame_commb speaks of
+        t->commb_n = (uint32_t)n;
+        t->commb_updated = true;
+    }
+    if (frames_host || levels_host || fixes_host || recs_host || commb_host) {
         HIPCHK(hipEventSynchronize(t->copied)); // the previous update's copies out of the staging have finished
         int rc = frames_host ? store_stage_frames(*t, frames, n) : ADSB_OK;
         if (rc == ADSB_OK && levels_host) rc = store_stage_levels(*t, levels, n);
         if (rc == ADSB_OK && fixes_host) rc = store_stage_mlat(*t, fixes, n);
         if (rc == ADSB_OK && recs_host) rc = store_stage_modes(*t, recs, n);
+        if (rc == ADSB_OK && commb_host) rc = store_stage_commb(*t, commb, n);
         if (rc != ADSB_OK) return rc;
         HIPCHK(hipEventRecord(t->copied, c->aux));
         if (frames_host) list = t->frames;
         if (levels_host) levels = t->lvl_frames;
         if (fixes_host) fixes = t->mlat_fixes;
         if (recs_host) recs = t->modes_recs;
+        if (commb_host) commb = t->commb_recs;
     }
-    return store_run(*t, list, n, sample_base, t->dev, levels, fixes, recs);
+    return store_run(*t, list, n, sample_base, t->dev, levels, fixes, recs, commb);
 }
 
 extern "C" int adsb_track_table_update(adsb_track_table *t, const adsb_frame *frames, size_t n, uint64_t sample_base)
@@ -878,6 +946,55 @@ extern "C" int adsb_track_table_fetch_modes(adsb_track_table *t, adsb_aircraft_m
 extern "C" int adsb_track_table_modes_device(adsb_track_table *t, const adsb_aircraft_modes **dev)
 {
     return store_device(t, modes_of, dev);
+}
+
+extern "C" int adsb_track_table_commb_reserve(adsb_track_table *t, const adsb_commb_settle_cfg *cfg)
+{
+    const adsb_commb_settle_cfg use = cfg ? *cfg : adsb_commb_settle_cfg{10.0, 40u, 1000u};
+    if (!t || !(use.max_age_s >= 0.0)) return ADSB_E_ARG; // before the handle is read
+    return store_commb_reserve(t, use);
+}
+
+extern "C" int adsb_track_table_update_commb(adsb_track_table *t, const adsb_frame *frames, const adsb_modes_rec *recs,
+                                             const adsb_commb_rec *commb, const adsb_mlat_fix *fixes,
+                                             const adsb_frame_level *levels, size_t n, uint64_t sample_base)
+{
+    if (!t || (!frames && n) || (!recs && n) || (!commb && n)) return ADSB_E_ARG;
+    if (!t->dev.modes || !t->dev.commb || (fixes && !t->dev.mlat) || (levels && !t->dev.lvl)) return ADSB_E_STATE;
+    if (n > t->max_frames) return ADSB_E_CAPACITY;
+    if (n == 0) { // nothing to launch: the last update_commb's list is empty
+        t->commb_n = 0;
+        t->commb_updated = true;
+        if (fixes) {
+            t->mlat_n = 0;
+            t->mlat_updated = true;
+        }
+    }
+    return track_table_update(t, frames, n ? levels : nullptr, n, sample_base, n ? fixes : nullptr, n ? recs : nullptr,
+                              n ? commb : nullptr);
+}
+
+extern "C" int adsb_track_table_fetch_commb(adsb_track_table *t, adsb_aircraft_commb *out, size_t max, size_t *n)
+{
+    return store_fetch_side(t, commb_of, out, max, n);
+}
+
+extern "C" int adsb_track_table_commb_device(adsb_track_table *t, const adsb_aircraft_commb **dev)
+{
+    return store_device(t, commb_of, dev);
+}
+
+// Waits.  As fetch_frame_mlat, over the last update_commb's list
+extern "C" int adsb_track_table_fetch_frame_commb(adsb_track_table *t, adsb_commb_rec *out, size_t max, size_t *n)
+{
+    if (!t || (!out && max)) return ADSB_E_ARG;
+    if (!t->dev.commb || !t->commb_updated) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(t->ctx->cfg.device));
+    const size_t take = std::min<size_t>(t->commb_n, max);
+    if (take) HIPCHK(hipMemcpyAsync(out, t->commb.out, sizeof(adsb_commb_rec) * take, hipMemcpyDeviceToHost, t->ctx->aux));
+    HIPCHK(hipStreamSynchronize(t->ctx->aux));
+    if (n) *n = take;
+    return ADSB_OK;
 }
 
 // Waits.  As store_fetch_frames, over the last update_mlat's list (a plain update in between leaves it alone)

@@ -8,12 +8,14 @@
 #define ADSB_TRACK_MODES_H
 
 #include "adsb_fix.h"
+#include "adsb_modes.h"
 
 namespace adsbk {
 
 static_assert(sizeof(adsb_aircraft_modes) == 64 && sizeof(adsb_modes_rec) == 32, "modes records");
 
-constexpr uint32_t kModesNoAddress = 1u << 24; // the sort key of a frame that is not accepted: after every address
+// kModesNoAddress (adsb_modes.h, 1 << 24): the sort key of a frame that is not accepted, after every address
+static_assert(kModesNoAddress == 1u << 24, "the 25-bit sort");
 
 // What a counted frame writes, by its record alone
 constexpr uint32_t kModesAlt = 0x1u, kModesSquawk = 0x2u, kModesCallsign = 0x4u, kModesStatus = 0x8u,

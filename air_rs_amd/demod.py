@@ -31,6 +31,7 @@ LEVEL_PULSE_SAMPLES, LEVEL_QUIET_SAMPLES = 116, 124  # of a frame's 240: what si
 SITE, FIX_DTYPE, FRAME_FIX_DTYPE = L.SITE, L.FIX_DTYPE, L.FRAME_FIX_DTYPE  # fixes_reserve / fixes / frame_fixes
 AIRCRAFT_MLAT_DTYPE, FRAME_MLAT_DTYPE = L.AIRCRAFT_MLAT_DTYPE, L.FRAME_MLAT_DTYPE  # TrackTable.mlat / frame_mlat
 AIRCRAFT_MODES_DTYPE = L.AIRCRAFT_MODES_DTYPE                                        # TrackTable.modes
+AIRCRAFT_COMMB_DTYPE = L.AIRCRAFT_COMMB_DTYPE                                        # TrackTable.commb
 WINDOW = 240  # 16 preamble + 112*2 samples (reference src/adsb.rs:98)
 
 
@@ -347,6 +348,125 @@ def commb_physical(recs):
         held = one & (recs["bds"] == bds) & ((recs["status"] >> k) & 1 == 1)
         out[key] = np.where(held, recs["value"][:, k] * factor, np.nan)
     return out
+
+
+COMMB_SETTLED = L.ADSB_COMMB_SETTLED     # COMMB_DTYPE state of a table's per-frame output: settled by the table
+# aircraft_commb_physical: key -> (block, index into value[], what one unit of the value is in the key's unit)
+_AIRCRAFT_COMMB_PHYSICAL = {key: ("bds%02x" % bds, k, factor) for key, (bds, k, factor) in _COMMB_PHYSICAL.items()}
+
+
+def aircraft_commb_physical(recs):
+    """The values of AIRCRAFT_COMMB_DTYPE records (TrackTable.commb) in physical units, the per-aircraft counterpart of
+    commb_physical: a dict of float64 arrays, one entry per aircraft, NaN for what a block does not hold (no such
+    register yet, or its status bit off).  The keys of commb_physical (feet, mb, degrees, kt, Mach, ft/min), and per
+    block "bds40_time", "bds50_time", "bds60_time" (NaN = none) and "bds40_settled" ... (1.0 where the block came from
+    a reply the table settled, 0.0 where adsb_commb_of found it unambiguous, NaN for none)."""
+    recs = np.atleast_1d(np.asarray(recs, dtype=AIRCRAFT_COMMB_DTYPE))
+    out = {}
+    for key, (block, k, factor) in _AIRCRAFT_COMMB_PHYSICAL.items():
+        b = recs[block]
+        held = ~np.isnan(b["time"]) & ((b["status"] >> k) & 1 == 1)
+        out[key] = np.where(held, b["value"][:, k] * factor, np.nan)
+    for block in ("bds40", "bds50", "bds60"):
+        b = recs[block]
+        out[block + "_time"] = b["time"].astype(np.float64)
+        out[block + "_settled"] = np.where(np.isnan(b["time"]), np.nan, b["settled"].astype(np.float64))
+    return out
+
+
+def host_commb_settle(frame_bytes, rec, reference=None, time=0.0, max_age_s=10.0, max_speed_diff_kt=40,
+                      max_vrate_diff_fpm=1000):
+    """adsb_host_commb_settle, the CPU mirror of a commb reserve's settle: the per-frame output (COMMB_DTYPE) of a
+    counted frame with these 14 bytes and stateless record `rec`, heard at `time`, against the VELOCITY_DTYPE record
+    `reference` (None: no reference).  Needs no device."""
+    b = np.zeros(14, dtype=np.uint8)
+    raw = np.frombuffer(bytes(frame_bytes), dtype=np.uint8)[:14]
+    b[:len(raw)] = raw
+    r = np.array([rec], dtype=COMMB_DTYPE)
+    ref = None if reference is None else np.array([reference], dtype=VELOCITY_DTYPE)
+    cfg = L.AdsbCommbSettleCfg(float(max_age_s), int(max_speed_diff_kt), int(max_vrate_diff_fpm))
+    out = np.zeros(1, dtype=COMMB_DTYPE)
+    L.check(L.load().adsb_host_commb_settle(b.ctypes.data, r.ctypes.data, None if ref is None else ref.ctypes.data,
+                                            float(time), C.byref(cfg), out.ctypes.data), "adsb_host_commb_settle")
+    return out[0]
+
+
+def host_commb_reference(frame_bytes, time=0.0):
+    """adsb_host_commb_reference: the VELOCITY_DTYPE record, exact fields only, that a table reads as the reference from
+    a DF17/18 TC 19 frame of the current list (subtype 0: ST 0 and 5-7 are none).  Needs no device."""
+    b = np.zeros(14, dtype=np.uint8)
+    raw = np.frombuffer(bytes(frame_bytes), dtype=np.uint8)[:14]
+    b[:len(raw)] = raw
+    out = np.zeros(1, dtype=VELOCITY_DTYPE)
+    L.check(L.load().adsb_host_commb_reference(b.ctypes.data, float(time), out.ctypes.data), "adsb_host_commb_reference")
+    return out[0]
+
+
+def host_track_commb_of(rec, time=0.0):
+    """adsb_host_track_commb_of: the AIRCRAFT_COMMB_DTYPE record of an aircraft whose only counted frame has the
+    per-frame output `rec` (COMMB_DTYPE), heard at `time`.  Needs no device."""
+    r = np.array([rec], dtype=COMMB_DTYPE)
+    out = np.zeros(1, dtype=AIRCRAFT_COMMB_DTYPE)
+    L.check(L.load().adsb_host_track_commb_of(r.ctypes.data, float(time),
+                                              out.ctypes.data_as(C.POINTER(L.AdsbAircraftCommb))),
+            "adsb_host_track_commb_of")
+    return out[0]
+
+
+def host_track_commb_merge(into, later):
+    """adsb_host_track_commb_merge, the combine of a commb reserve: the AIRCRAFT_COMMB_DTYPE record `into` followed by
+    `later` -> the merged record.  Needs no device."""
+    a, b = np.array([into], dtype=AIRCRAFT_COMMB_DTYPE), np.array([later], dtype=AIRCRAFT_COMMB_DTYPE)
+    P = C.POINTER(L.AdsbAircraftCommb)
+    L.check(L.load().adsb_host_track_commb_merge(a.ctypes.data_as(P), b.ctypes.data_as(P)), "adsb_host_track_commb_merge")
+    return a[0]
+
+
+def host_track_commb(frames, modes, commb, seconds_per_sample=0.5e-6, sample_base=0, **limits):
+    """What a table with a modes and a commb reserve (and room for every aircraft) makes of ONE list, without a device,
+    from the CPU mirror's per-frame functions: FRAME_DTYPE frames with their MODES_DTYPE and COMMB_DTYPE records ->
+    (addresses ascending, their AIRCRAFT_COMMB_DTYPE records, the per-frame COMMB_DTYPE output).  limits: commb_reserve's."""
+    frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+    out, state, held = np.array(commb, dtype=COMMB_DTYPE), {}, {}
+    for j in range(len(frames)):
+        if int(modes[j]["kind"]) > L.ADSB_MODES_KNOWN:
+            continue
+        icao, b = int(modes[j]["address"]) & 0xFFFFFF, frames["bytes"][j].tobytes()
+        t = float(int(sample_base) + int(frames["offset"][j])) * seconds_per_sample
+        if icao not in state:
+            state[icao] = host_track_commb_of(np.zeros(1, dtype=COMMB_DTYPE)[0])
+        if int(commb[j]["state"]) != L.ADSB_COMMB_NOT_COMMB:
+            out[j] = host_commb_settle(b, commb[j], held.get(icao), t, **limits)
+            state[icao] = host_track_commb_merge(state[icao], host_track_commb_of(out[j], t))
+        if int(modes[j]["df"]) in (17, 18) and b[4] >> 3 == 19:
+            v = host_commb_reference(b, t)
+            if int(v["subtype"]):
+                held[icao] = v
+    order = sorted(state)
+    return (np.array(order, dtype=np.uint32), np.array([state[a] for a in order], dtype=AIRCRAFT_COMMB_DTYPE).reshape(-1), out)
+
+
+AIRCRAFT_COMMB_COLUMNS = ("SelAlt", "QNH", "GS/Trk(B)", "Hdg", "IAS", "Mach")
+
+
+def aircraft_commb_columns(recs):
+    """AIRCRAFT_COMMB_DTYPE records as the text columns AIRCRAFT_COMMB_COLUMNS, one list of six strings per aircraft:
+    selected altitude in feet (MCP/FCU, else FMS), barometric setting in mb, ground speed in kt / true track in degrees
+    from BDS 5,0, magnetic heading, IAS and Mach from BDS 6,0; "n/a" for what the aircraft has not said, and a "*" behind
+    a value from a reply the table settled (it read as 5,0 and as 6,0; the aircraft's ADS-B velocity decided)."""
+    p = aircraft_commb_physical(recs)
+    rows = []
+    for k in range(len(p["mach"])):
+        f = lambda key, fmt: "n/a" if np.isnan(p[key][k]) else format(p[key][k], fmt)
+        m5 = "*" if p["bds50_settled"][k] == 1.0 else ""
+        m6 = "*" if p["bds60_settled"][k] == 1.0 else ""
+        sel = f("mcp_altitude_ft", ".0f") if not np.isnan(p["mcp_altitude_ft"][k]) else f("fms_altitude_ft", ".0f")
+        gs_trk = f("ground_speed_kt", ".0f") + "/" + f("true_track_deg", ".0f")
+        rows.append([sel, f("baro_setting_mb", ".1f"), "n/a" if gs_trk == "n/a/n/a" else gs_trk + m5,
+                     f("magnetic_heading_deg", ".0f") + (m6 if not np.isnan(p["magnetic_heading_deg"][k]) else ""),
+                     f("ias_kt", ".0f") + (m6 if not np.isnan(p["ias_kt"][k]) else ""),
+                     f("mach", ".3f") + (m6 if not np.isnan(p["mach"][k]) else "")])
+    return rows
 
 
 MESSAGE_DTYPE = np.dtype([("time", "<u8"), ("bytes", "u1", (14,)), ("status", "u1"), ("fixed_bit", "u1"), ("first", "<u4"),
@@ -1529,14 +1649,18 @@ class TrackTable(_TrackStore):
         self._open(dem, L.AdsbTrackTableCfg(L.ADSB_ABI_VERSION, int(max_aircraft), int(max_frames),
                                             float(seconds_per_sample)), max_frames)
 
-    def update(self, frames, sample_base=0, levels=None, mlat=None, modes=None):
+    def update(self, frames, sample_base=0, levels=None, mlat=None, modes=None, commb=None):
         """frames: FRAME_DTYPE array in ascending offset (host); packet time = (sample_base + offset) x sps.  levels
         (after levels_reserve): the frames' LEVEL_DTYPE records (host), merged into the aircraft's level records.  mlat
         (after mlat_reserve): the frames' MLAT_FIX_DTYPE fixes (host), merged into the aircraft's mlat records.  modes
         (after modes_reserve): the frames' MODES_DTYPE records (host); the list is then keyed by their addresses, a
-        frame that is not SELF or KNOWN touches nothing, and the aircraft's modes records take the replies."""
+        frame that is not SELF or KNOWN touches nothing, and the aircraft's modes records take the replies.  commb
+        (with modes, after commb_reserve): the frames' COMMB_DTYPE records (host); the aircraft's commb records take the
+        registers, and a reply that reads as 5,0 and as 6,0 is settled against the aircraft's ADS-B velocity."""
         frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
         ptr = frames.ctypes.data if len(frames) else None
+        if commb is not None and modes is None:
+            raise ValueError("commb needs modes")
         if modes is not None:
             recs = np.ascontiguousarray(modes, dtype=MODES_DTYPE)
             if len(recs) != len(frames):
@@ -1545,9 +1669,16 @@ class TrackTable(_TrackStore):
             if fixes is not None and len(fixes) != len(frames):
                 raise ValueError(f"mlat: {len(fixes)} fixes for {len(frames)} frames")
             keep, lptr = (None, None) if levels is None else self._host_levels(levels, len(frames))
-            self._call("update_modes", ptr, recs.ctypes.data if len(recs) else None,
-                       fixes.ctypes.data if fixes is not None and len(fixes) else None, lptr, len(frames),
-                       int(sample_base))
+            fptr = fixes.ctypes.data if fixes is not None and len(fixes) else None
+            if commb is not None:
+                cb = np.ascontiguousarray(commb, dtype=COMMB_DTYPE)
+                if len(cb) != len(frames):
+                    raise ValueError(f"commb: {len(cb)} records for {len(frames)} frames")
+                self._call("update_commb", ptr, recs.ctypes.data if len(recs) else None,
+                           cb.ctypes.data if len(cb) else None, fptr, lptr, len(frames), int(sample_base))
+            else:
+                self._call("update_modes", ptr, recs.ctypes.data if len(recs) else None, fptr, lptr, len(frames),
+                           int(sample_base))
         elif mlat is not None:
             fixes = np.ascontiguousarray(mlat, dtype=MLAT_FIX_DTYPE)
             if len(fixes) != len(frames):
@@ -1560,13 +1691,18 @@ class TrackTable(_TrackStore):
             keep, lptr = self._host_levels(levels, len(frames))
             self._call("update_levels", ptr, lptr, len(frames), int(sample_base))
 
-    def update_device(self, dev_ptr, n, sample_base=0, levels_ptr=None, mlat_ptr=None, modes_ptr=None):
+    def update_device(self, dev_ptr, n, sample_base=0, levels_ptr=None, mlat_ptr=None, modes_ptr=None, commb_ptr=None):
         """n frames at dev_ptr in the ctx device's memory (e.g. result_device() after fetch_counts()).  levels_ptr
         (after levels_reserve): their n level records, on the device (e.g. levels_device()) or a host address.  mlat_ptr
         (after mlat_reserve): their n adsb_mlat_fix records, on the device (e.g. mlat_device()[0]) or a host address;
         every address may be a host one too, each on its own.  modes_ptr (after modes_reserve): their n adsb_modes_rec
-        records (e.g. modes_device()[0]); the update is then update_modes."""
-        if modes_ptr is not None:
+        records (e.g. modes_device()[0]); the update is then update_modes.  commb_ptr (with modes_ptr, after
+        commb_reserve): their n adsb_commb_rec records (e.g. commb_device()[0]); the update is then update_commb."""
+        if commb_ptr is not None:
+            if modes_ptr is None:
+                raise ValueError("commb_ptr needs modes_ptr")
+            self._call("update_commb", dev_ptr, modes_ptr, commb_ptr, mlat_ptr, levels_ptr, int(n), int(sample_base))
+        elif modes_ptr is not None:
             self._call("update_modes", dev_ptr, modes_ptr, mlat_ptr, levels_ptr, int(n), int(sample_base))
         elif mlat_ptr is not None:
             self._call("update_mlat", dev_ptr, mlat_ptr, levels_ptr, int(n), int(sample_base))
@@ -1615,6 +1751,30 @@ class TrackTable(_TrackStore):
         synchronisation."""
         dev = C.c_void_p()
         self._call("modes_device", C.byref(dev))
+        return dev.value
+
+    def commb_reserve(self, max_age_s=10.0, max_speed_diff_kt=40, max_vrate_diff_fpm=1000):
+        """adsb_track_table_commb_reserve: one AIRCRAFT_COMMB_DTYPE record beside every aircraft record, which an update
+        given `modes` and `commb` merges the frames' Comm-B registers into.  An ambiguous {5,0; 6,0} reply is settled
+        against the aircraft's airborne velocity if that is at most max_age_s old, with these tolerances."""
+        cfg = L.AdsbCommbSettleCfg(float(max_age_s), int(max_speed_diff_kt), int(max_vrate_diff_fpm))
+        self._call("commb_reserve", C.byref(cfg))
+
+    def commb(self):
+        """AIRCRAFT_COMMB_DTYPE records (what each aircraft's Comm-B replies say), aligned with aircraft()[0];
+        aircraft_commb_physical() gives them in physical units."""
+        return self._fetch("fetch_commb", [AIRCRAFT_COMMB_DTYPE])[0]
+
+    def frame_commb(self):
+        """One COMMB_DTYPE record per frame of the last update given `commb`, in its list order: the frame's record,
+        with state COMMB_SETTLED and the settled register's values where the table settled it."""
+        return self._fetch("fetch_frame_commb", [COMMB_DTYPE], size=self.max_frames)[0]
+
+    def commb_device(self):
+        """Device address of the commb records, one per record place in slot order (as levels_device); no
+        synchronisation."""
+        dev = C.c_void_p()
+        self._call("commb_device", C.byref(dev))
         return dev.value
 
     def fixes_reserve(self, site):

@@ -1733,6 +1733,124 @@ int adsb_track_table_fetch_modes(adsb_track_table *table, adsb_aircraft_modes *o
 int adsb_track_table_modes_device(adsb_track_table *table, const adsb_aircraft_modes **dev);
 
 /*
+ * Comm-B registers per aircraft.  adsb_commb_of decodes BDS 1,0 to 6,0 of every DF20/21 reply and is stateless; with a
+ * commb reserve (beside the modes reserve) a TABLE keeps, per aircraft, the newest 4,0, 5,0 and 6,0 values, the newest
+ * 1,7 capability word and 3,0 word, and four counts, in one 128-byte adsb_aircraft_commb beside its record.  It also
+ * settles what the stateless stage cannot: a payload that passes as 5,0 and as 6,0 is read against the aircraft's own
+ * ADS-B airborne velocity, which the table holds.  update_commb is update_modes plus the frames' adsb_commb_rec[]:
+ * everything update_modes does it does, with the same results; what follows is what it adds.  Tables only.
+ *
+ * COUNTED  A frame is counted iff update_modes counts it (accepted by kind, its point not UNTRACKED) and its commb
+ *   state is not NOT_COMMB.  Per counted frame, by its PER-FRAME OUTPUT (below):
+ *     n_commb + 1.
+ *     NONE: n_none + 1.
+ *     ONE or SETTLED with bds 0x40 / 0x50 / 0x60: that block becomes { frame time, value[5], status, settled = 1 for
+ *       SETTLED and 0 for ONE }.  SETTLED also adds 1 to n_settled.
+ *     ONE with bds 0x17: capability = word (a 1,7 word is never 0, bit 7 is set; a record with word 0 writes nothing).
+ *     ONE with bds 0x30: ra_word = word, ra_time = frame time.
+ *     AMBIGUOUS (it stayed ambiguous): n_ambiguous + 1.
+ *     EMPTY, ONE with bds 0x10 or 0x20, and any other state or bds: only n_commb.
+ *   Counts saturate at 2^32 - 1.  Every combine is a saturating add or "the later list position wins", so it is
+ *   associative.  The EMPTY record has every time NaN and everything else 0 and is the identity of the merge: at
+ *   admission, at re-admission after an expire, after a reset, and for aircraft held from before the reserve.  Times
+ *   are the store's frame time, the single rounded product (sample_base + offset) x seconds_per_sample.
+ * PER-FRAME OUTPUT  frame_commb[j] is commb[j] byte for byte, except for a settled frame: state ADSB_COMMB_SETTLED and
+ *   the bds, status, value and word that the decode of the frame's MB as the settled register gives (what
+ *   adsb_host_commb_as gives); candidates, n_candidates and reserved stay.  A frame that is not counted is never settled.
+ * WHICH FRAMES  Only a counted frame whose record is AMBIGUOUS with candidates == ADSB_COMMB_C50 | ADSB_COMMB_C60.
+ *   Every other candidate set stays ambiguous.
+ * REFERENCE R  The aircraft's newest airborne-velocity message that precedes the frame in list order, over the table's
+ *   whole history since the aircraft's admission: an accepted DF17/18 frame with TC 19 and ST 1-4 (exactly what the
+ *   record's adsb_velocity takes).  In the current list it is the newest such frame of the aircraft before the frame
+ *   being settled; if the list has none before it, R is the record's adsb_velocity as it stood before this update.  R
+ *   is usable iff 0 <= t_frame - R.time <= max_age_s, computed in f64 with one subtraction (NaN: not usable).  Without
+ *   a usable R nothing is settled.
+ * EXACT FIELDS  The rule reads v_ew_kt, v_ns_kt, vertical_rate_fpm, subtype, flags and airspeed_tas; for ST 3-4 also
+ *   speed_kt (an integer value, "airspeed" below) and h10 = direction_deg x 128 / 45 (an exact integer, the 10-bit
+ *   heading).  It never reads direction_deg or speed_kt of ST 1-2.  SPEED, DIRECTION, VRATE: R's flags.
+ * DEFINITIONS  S = max_speed_diff_kt, V = max_vrate_diff_fpm, s2 = v_ew^2 + v_ns^2, vr = vertical_rate_fpm.
+ *   sector16(ew, ns), with a = |ew| and b = |ns|: k = 0 if 985 a < 408 b, else k = 1 if a < b, else k = 2 if
+ *   408 a < 985 b, else k = 3; the sector is k for ew >= 0 and ns > 0, 7 - k for ew > 0 and ns <= 0, 8 + k for ew <= 0
+ *   and ns < 0, and 15 - k otherwise.  Sector distance is circular over 16.  value[] and status are those of the
+ *   reading in question (VALUES above).
+ * CHECKS ON THE READING AS 5,0
+ *   status bit 2, R ST 1-2 with SPEED: passes iff max(g - S, 0)^2 <= s2 <= (g + S)^2 with g = value[2].
+ *   status bit 1, R ST 1-2 with SPEED and s2 > 0: passes iff the distance of value[1] >> 7 and sector16 is <= 1.
+ *   status bit 4, R ST 3-4 with SPEED and airspeed_tas = 1: passes iff |value[4] - airspeed| <= S.
+ * CHECKS ON THE READING AS 6,0
+ *   status bit 0, R ST 1-2 with SPEED and s2 > 0: passes iff the distance of value[0] >> 7 and sector16 is <= 2
+ *     (heading differs from track by drift and magnetic variation).
+ *   status bit 0, R ST 3-4 with DIRECTION: passes iff the circular |value[0] - 2 h10| over 2048 is <= 128.
+ *   status bit 1, R ST 3-4 with SPEED and airspeed_tas = 0: passes iff |value[1] - airspeed| <= S.
+ *   status bit 3, R with VRATE: passes iff |value[3] - vr| <= V.
+ *   status bit 4, R with VRATE: passes iff |value[4] - vr| <= V.
+ * DECISION  A reading is supported iff at least one check applies and none fails, contradicted iff at least one fails.
+ *   The frame is settled to X iff X is supported and the other reading is contradicted.
+ * CUT INVARIANCE  The rule depends only on the frame sequence: one list cut into any sequence of update_commb calls
+ *   gives the same 128 bytes per aircraft, and the concatenated frame_commb is the uncut call's.
+ * On the device, after everything update_modes launches and before the merge into the main records (so the held
+ * velocity is still the one from before this update): one segmented scan over the sorted list gives every frame the
+ * sorted position of its aircraft's newest earlier velocity frame; one thread per frame resolves R, settles, writes
+ * frame_commb[j] and a 40-byte scan operand at its sorted position; one segmented inclusive scan (head mark, five
+ * "newest position" words, four saturating counts); one thread per segment tail reads the winners' frame_commb and
+ * times and merges into the side record.  No atomics, integers only, linear in the list.  Device memory, all of it
+ * allocated by the reserve: 128 bytes per place of max_aircraft, and per frame of max_frames 8 + 32 + 40 + 40 bytes
+ * plus 32 bytes of device staging for a host commb array and the scans' scratch; 32 bytes per frame of pinned host
+ * memory.  A table that never reserves allocates nothing and launches exactly the kernels it launched before; update,
+ * update_levels, update_mlat and update_modes of a table that did reserve behave as before and leave the commb
+ * records alone (apart from admission emptying a place).
+ */
+#define ADSB_COMMB_SETTLED 5u     /* only in a table's per-frame output, never from adsb_commb_of */
+typedef struct adsb_commb_settle_cfg { /* 16 bytes */
+    double   max_age_s;           /* R is usable up to this age; 10.0 is the store's own CPR pairing window */
+    uint32_t max_speed_diff_kt;   /* S */
+    uint32_t max_vrate_diff_fpm;  /* V */
+} adsb_commb_settle_cfg;
+typedef struct adsb_commb_block { /* 32 bytes */
+    double   time;                /* store frame time of the frame it came from; NaN = none */
+    int32_t  value[5];            /* as in adsb_commb_rec */
+    uint16_t status;
+    uint16_t settled;             /* 1: the frame was settled by the table, 0: adsb_commb_of found it unambiguous */
+} adsb_commb_block;
+/* (tag first, typedef after: the one record of this header with members of a struct type) */
+struct adsb_aircraft_commb {          /* 128 bytes, one per record place */
+    adsb_commb_block bds40, bds50, bds60;               /* newest of each; time NaN = none */
+    uint32_t n_commb, n_settled, n_ambiguous, n_none;   /* saturating at 2^32 - 1 */
+    uint32_t capability;          /* newest 1,7 word; 0 = none */
+    uint32_t ra_word;             /* newest 3,0 word */
+    double   ra_time;             /* its frame time; NaN = none */
+};
+typedef struct adsb_aircraft_commb adsb_aircraft_commb;
+#ifdef __cplusplus
+static_assert(sizeof(adsb_commb_settle_cfg) == 16 && sizeof(adsb_commb_block) == 32 && sizeof(adsb_aircraft_commb) == 128,
+              "adsb_aircraft_commb layout");
+#endif
+/* Allocates the above and empties every commb record.  cfg NULL: 10.0 s, 40 kt, 1000 ft/min (policy, not
+ * measurements).  May wait for the device.  A second reserve changes nothing, its cfg neither.  ADSB_E_ARG for a NULL
+ * table or a max_age_s that is NaN or negative; ADSB_E_NOMEM if the memory is not to be had. */
+int adsb_track_table_commb_reserve(adsb_track_table *table, const adsb_commb_settle_cfg *cfg);
+/* The update described above.  recs[n], commb[n] and, if given, fixes[n] and levels[n] are the frames' in list order.
+ * Each may be host memory or memory of the ctx's device, independently; host arrays have been copied when this returns.
+ * recs may be adsb_modes_device's pointer and commb adsb_commb_device's (the ctx's scratch, ordered on the same
+ * stream).  ADSB_E_ARG for a NULL table, or NULL frames, recs or commb with n > 0; ADSB_E_STATE without a modes reserve
+ * or without a commb reserve, for fixes without an mlat reserve, or for levels without a levels reserve;
+ * ADSB_E_CAPACITY for n > max_frames; n = 0 is ADSB_OK. */
+int adsb_track_table_update_commb(adsb_track_table *table, const adsb_frame *frames, const adsb_modes_rec *recs,
+                                  const adsb_commb_rec *commb, const adsb_mlat_fix *fixes /* may be NULL */,
+                                  const adsb_frame_level *levels /* may be NULL */, size_t n, uint64_t sample_base);
+/* Waits; one commb record per aircraft, in exactly the order adsb_track_table_fetch returns the records (ascending
+ * ICAO); *n = records held even if more than max.  ADSB_E_ARG for a NULL table, or NULL out with max > 0;
+ * ADSB_E_STATE without a reserve. */
+int adsb_track_table_fetch_commb(adsb_track_table *table, adsb_aircraft_commb *out, size_t max, size_t *n);
+/* Waits; the per-frame output of the last update_commb, in list order (another update in between leaves it alone);
+ * *n = min(frames of that update, max).  ADSB_E_ARG for a NULL table, or NULL out with max > 0; ADSB_E_STATE without a
+ * reserve or before any update_commb since the reserve or the last reset. */
+int adsb_track_table_fetch_frame_commb(adsb_track_table *table, adsb_commb_rec *out, size_t max, size_t *n);
+/* Does not synchronise: the device address of the commb records, one per record PLACE in slot order; dev may be NULL.
+ * ADSB_E_ARG for a NULL table, ADSB_E_STATE without a reserve. */
+int adsb_track_table_commb_device(adsb_track_table *table, const adsb_aircraft_commb **dev);
+
+/*
  * ---- several GPUs behind one call ---------------------------------------------------------
  * The reference's thread 2 is one function on one thread (src/adsb.rs:92, spawned at adsb.rs:147); a group is the
  * drop-in for that function when the buffer should be spread over N devices: one context per member, the offsets

@@ -234,6 +234,27 @@ int adsb_host_track_mlat_of(double max_disagreement_m, const uint8_t bytes[14], 
 int adsb_host_track_modes_of(const adsb_modes_rec *rec, double time, adsb_aircraft_modes *one, uint32_t *accepted);
 int adsb_host_track_modes_merge(adsb_aircraft_modes *into, const adsb_aircraft_modes *later);
 
+/*
+ * CPU mirror of the Comm-B step of a table with a commb reserve (adsb_hip.h, "Comm-B registers per aircraft"): the same
+ * program text as the device's, no device needed.
+ * commb_settle: *out = the per-frame output of a COUNTED frame with these bytes and stateless record *rec, heard at
+ * frame time `time`, against the reference *reference (NULL, or subtype 0: none); cfg NULL: the reserve's defaults.
+ * *out is *rec byte for byte unless the frame is settled.  rec and out may be the same.
+ * commb_reference: the fields of an adsb_velocity that the rule reads, from the 14 bytes of a DF17/18 TC 19 frame heard
+ * at `time` (integers only: speed_kt and direction_deg are filled for ST 3-4 and left 0 for ST 1-2); subtype 0 for ST 0
+ * and 5-7.  It is what the device reads for a reference in the current list.
+ * track_commb_of: *one = the adsb_aircraft_commb of an aircraft whose only counted frame since admission has the
+ * per-frame output *rec, heard at `time` (the EMPTY record for NOT_COMMB).  track_commb_merge: *into becomes *into
+ * followed by *later, a record of the frames that come after into's: the combine the device's segment tails apply.
+ * ADSB_E_ARG for a NULL bytes, rec, out, reference (commb_reference), one, into or later, or a cfg whose max_age_s is
+ * NaN or negative.
+ */
+int adsb_host_commb_settle(const uint8_t bytes[14], const adsb_commb_rec *rec, const adsb_velocity *reference, double time,
+                           const adsb_commb_settle_cfg *cfg, adsb_commb_rec *out);
+int adsb_host_commb_reference(const uint8_t bytes[14], double time, adsb_velocity *reference);
+int adsb_host_track_commb_of(const adsb_commb_rec *rec, double time, adsb_aircraft_commb *one);
+int adsb_host_track_commb_merge(adsb_aircraft_commb *into, const adsb_aircraft_commb *later);
+
 /* ---- behind the channel: tracker + CPR ------------------------------------------- */
 
 /* cpr.rs:39-54 calc_num_zones; cpr.rs:135-147 calculate_geographic_position (returns 1 = Some, 0 = None).

@@ -29,7 +29,12 @@ and nothing is fetched before the end; --host solves the messages with an addres
 --modes --aircraft: the table takes frames, Mode S records and fixes in one update (adsb_track_table_update_modes), so
 an aircraft that only answers interrogations has a row, keyed by the address the Mode S stage gave its replies, with its
 multilaterated position.  Five columns are appended: Alt(S), Squawk and Call(S) from its newest replies that carry them,
-Replies (DF0/4/5/11/16/20/21 frames counted), and S, which is "S" for an aircraft that has sent no DF17/18 frame."""
+Replies (DF0/4/5/11/16/20/21 frames counted), and S, which is "S" for an aircraft that has sent no DF17/18 frame.
+
+--modes --commb --aircraft: the Comm-B stage (adsb_commb_of) reads the same frames where they lie and the table takes its
+records too (adsb_track_table_update_commb): per aircraft the newest BDS 4,0, 5,0 and 6,0, a reply that reads as 5,0 and
+as 6,0 settled from the aircraft's own ADS-B velocity.  Six more columns: SelAlt, QNH, GS/Trk(B), Hdg, IAS, Mach, with a
+"*" behind a value from a settled reply."""
 import argparse
 import os
 import sys
@@ -114,11 +119,13 @@ def modes_columns(A, s):
                       f"{int(s['n_replies'])}", "" if flags & A.ADSB_TRACK_MODES_SQUITTER else "S"])
 
 
-def aircraft_lines(A, recs, mlat, now, modes=None):
+def aircraft_lines(A, recs, mlat, now, modes=None, commb=None):
     """One tab-separated line per aircraft, under a header line.  modes (AIRCRAFT_MODES_DTYPE records): five more
-    columns."""
+    columns.  commb (AIRCRAFT_COMMB_DTYPE records): six more."""
     out = ("ICAO\tCallsign\tLatitude\tLongitude\tMlatLat\tMlatLon\tAge\tPdop\tValid/Attempted\tChecked/Disagree"
-           "\tMaxDisagreement" + ("" if modes is None else "\tAlt(S)\tSquawk\tCall(S)\tReplies\tS") + "\n")
+           "\tMaxDisagreement" + ("" if modes is None else "\tAlt(S)\tSquawk\tCall(S)\tReplies\tS")
+           + ("" if commb is None else "\t" + "\t".join(A.AIRCRAFT_COMMB_COLUMNS)) + "\n")
+    registers = None if commb is None else A.aircraft_commb_columns(commb)
     for k, (r, m) in enumerate(zip(recs, mlat)):
         call = r["callsign"].decode("ascii", "replace").strip() or "n/a"
         said = f"{float(r['latitude']):.5f}\t{float(r['longitude']):.5f}" if r["has_position"] else "n/a\tn/a"
@@ -130,7 +137,8 @@ def aircraft_lines(A, recs, mlat, now, modes=None):
         worst = f"{float(m['max_disagreement_m']):.0f}" if m["flags"] & A.ADSB_TRACK_MLAT_CHECKED else "n/a"
         out += (f"{int(r['icao']):06X}\t{call}\t{said}\t{solved}\t{int(m['n_valid'])}/{int(m['n_attempted'])}"
                 f"\t{int(m['n_checked'])}/{int(m['n_disagree'])}\t{worst}"
-                + ("" if modes is None else "\t" + modes_columns(A, modes[k])) + "\n")
+                + ("" if modes is None else "\t" + modes_columns(A, modes[k]))
+                + ("" if registers is None else "\t" + "\t".join(registers[k])) + "\n")
     return out
 
 
@@ -150,12 +158,16 @@ def main():
     ap.add_argument("--max-disagreement", type=float, default=1000.0,
                     help="with --aircraft: metres a reported position may lie from the multilaterated one")
     ap.add_argument("--modes", action="store_true", help="Mode S replies too: short frames, addresses from the Mode S stage")
+    ap.add_argument("--commb", action="store_true",
+                    help="with --modes --aircraft: the aircraft's Comm-B registers too, six more columns")
     ap.add_argument("--max-iterations", type=int, default=0,
                     help="the solver's step limit (default: its own, 24); replies carry no altitude, and a free solve over "
                          "ground receivers may need 200")
     args = ap.parse_args()
     if args.modes and args.sync:
         ap.error("--modes does not go with --sync")
+    if args.commb and not (args.modes and args.aircraft):
+        ap.error("--commb needs --modes and --aircraft")
 
     import numpy as np
 
@@ -199,6 +211,8 @@ def main():
             spread = np.zeros(len(every), dtype=A.MLAT_FIX_DTYPE)       # a fix per message: none where none was solved
             spread[np.flatnonzero(mrec["kind"] <= A.ADSB_MODES_KNOWN)] = fixes
             aircraft = host_table(A, fout, spread, args.max_disagreement, modes=mrec)
+            if args.commb:                                              # every accepted address has a row in both
+                aircraft += (A.host_track_commb(fout, mrec, A.host_commb(fout)[0])[1],)
             newest = float(int(every["time"][-1])) * 0.5e-6 if len(every) else 0.0
     elif args.modes:
         with A.AdsbDemod(max_samples=1 << 16, max_out=1024) as d:
@@ -211,9 +225,14 @@ def main():
                 with A.TrackTable(d, max_frames=max(n_msgs, 1), seconds_per_sample=0.5e-6) as table:
                     table.mlat_reserve(args.max_disagreement)
                     table.modes_reserve()
+                    commb_ptr = None
+                    if args.commb:
+                        table.commb_reserve()
+                        d.commb_of_async((d.correlated_device()[1], n_msgs))     # the same frames, where they lie
+                        commb_ptr = d.commb_device()[0]
                     table.update_device(d.correlated_device()[1], n_msgs, 0, mlat_ptr=d.mlat_device()[0],
-                                        modes_ptr=d.modes_device()[0])
-                    aircraft = (table.aircraft()[0], table.mlat(), table.modes())
+                                        modes_ptr=d.modes_device()[0], commb_ptr=commb_ptr)
+                    aircraft = (table.aircraft()[0], table.mlat(), table.modes()) + ((table.commb(),) if args.commb else ())
             fixes, hdr = d.fetch_mlat()
             msgs, _, recs = d.fetch_correlated()
             mrec = d.fetch_modes()[0]
@@ -256,7 +275,8 @@ def main():
     if aircraft is not None:
         if newest is None:
             newest = float(int(msgs["time"][-1])) * 0.5e-6 if len(msgs) else 0.0
-        print(aircraft_lines(A, aircraft[0], aircraft[1], newest, aircraft[2] if len(aircraft) > 2 else None), end="")
+        print(aircraft_lines(A, aircraft[0], aircraft[1], newest, aircraft[2] if len(aircraft) > 2 else None,
+                             aircraft[3] if len(aircraft) > 3 else None), end="")
     for k, (m, f) in enumerate(zip(msgs, fixes)):
         if aircraft is None and f["flags"] & A.ADSB_MLAT_VALID and (accepted is None or accepted[k]):
             t = int(win.rx["ticks"][recs["frame"][m["first"]]]) / 12e6

@@ -116,30 +116,38 @@ def modes_columns(s):
             f"{int(s['n_replies'])}", "" if flags & A.ADSB_TRACK_MODES_SQUITTER else "S"]
 
 
-def aircraft_table(d, frames, n_samples, st=None, frame_levels=None, site=None, modes=None):
+def aircraft_table(d, frames, n_samples, st=None, frame_levels=None, site=None, modes=None, commb=None):
     """The capture's final aircraft table as tab-separated text: tui.rs:95's columns, rows by age (tui.rs:69), then
     ICAO.  Age = whole seconds from each aircraft's last frame to the end of the capture.  frame_levels (one
     LEVEL_DTYPE record per frame, with st the sample type): also the columns RSSI and SNR.  site ((latitude, longitude,
     max_range_nm)): also FixLat, FixLon, Range, Bearing and GS.  modes (one MODES_DTYPE record per frame): the table is
-    keyed by the records' addresses (update_modes); also Alt(S), Squawk, Call(S), Replies and S."""
+    keyed by the records' addresses (update_modes); also Alt(S), Squawk, Call(S), Replies and S.  commb (with modes: one
+    COMMB_DTYPE record per frame): the table also keeps the aircraft's Comm-B registers (update_commb) and settles a reply
+    that reads as 5,0 and as 6,0 from the aircraft's ADS-B velocity; also SelAlt, QNH, GS/Trk(B), Hdg, IAS and Mach, with
+    a "*" behind a value from a settled reply."""
     with A.TrackTable(d, max_frames=max(len(frames), 1), seconds_per_sample=SECONDS_PER_SAMPLE) as t:
         if site is not None:
             t.fixes_reserve(site)
         if modes is not None:
             t.modes_reserve()
+        more = {}
+        if commb is not None:
+            t.commb_reserve()
+            more["commb"] = commb
         if frame_levels is None:
-            t.update(frames, modes=modes)
+            t.update(frames, modes=modes, **more)
         else:
             t.levels_reserve()
-            t.update(frames, levels=frame_levels, modes=modes)
+            t.update(frames, levels=frame_levels, modes=modes, **more)
         recs, _ = t.aircraft()
         vel, heard = t.velocity(), t.last_heard()
         sides = [None] * len(recs) if modes is None else t.modes()
         levels = [None] * len(recs) if frame_levels is None else t.levels()
         fixes = [None] * len(recs) if site is None else t.fixes()
+        registers = [None] * len(recs) if commb is None else A.aircraft_commb_columns(t.commb())
     now = n_samples * SECONDS_PER_SAMPLE
     rows = []
-    for rec, v, lh, lv, fx, side in zip(recs, vel, heard, levels, fixes, sides):
+    for rec, v, lh, lv, fx, side, reg in zip(recs, vel, heard, levels, fixes, sides, registers):
         pos, age = bool(rec["has_position"]), int(now - lh)
         rows.append((age, int(rec["icao"]), "\t".join([
             f"{int(rec['icao']):x}",
@@ -149,11 +157,12 @@ def aircraft_table(d, frames, n_samples, st=None, frame_levels=None, site=None, 
             f"{float(rec['longitude']):.6f}" if pos else "n/a",
             f"{float(v['speed_kt']):.0f}" if v["flags"] & A.ADSB_VELOCITY_SPEED else "n/a",
             f"{age}"] + ([] if lv is None else level_columns(st, lv)) + ([] if fx is None else fix_columns(fx))
-            + ([] if side is None else modes_columns(side)))))
+            + ([] if side is None else modes_columns(side)) + ([] if reg is None else reg))))
     rows.sort(key=lambda r: (r[0], r[1]))
     head = "ICAO\tCallsign\tAltitude\tLatitude\tLongitude\tVelocity\tAge" + ("" if frame_levels is None else "\tRSSI\tSNR")
     head += "" if site is None else "\tFixLat\tFixLon\tRange\tBearing\tGS"
     head += "" if modes is None else "\tAlt(S)\tSquawk\tCall(S)\tReplies\tS"
+    head += "" if commb is None else "\t" + "\t".join(A.AIRCRAFT_COMMB_COLUMNS)
     return head + "\n" + "".join(r[2] + "\n" for r in rows)
 
 
@@ -353,7 +362,8 @@ def main():
                     help="with --beast-in / --avr-in: short frames too; print DF, kind, address, altitude, squawk, callsign per "
                          "frame, or with --aircraft the table keyed by those addresses")
     ap.add_argument("--commb", action="store_true",
-                    help="with --modes: every DF20/21 line also gets the Comm-B register inferred from its MB field and its values")
+                    help="with --modes: every DF20/21 line also gets the Comm-B register inferred from its MB field and its "
+                         "values; with --modes --aircraft: six more columns from the aircraft's Comm-B registers")
     ap.add_argument("--tick-bias", type=int, default=0, metavar="N", help="added to every timestamp (12 MHz ticks, < 2^48)")
     a = ap.parse_args()
     if a.mlat and not a.avr:
@@ -367,8 +377,8 @@ def main():
     wire_in = "beast" if a.beast_in else "avr" if a.avr_in else None
     if a.modes and not wire_in:
         ap.error("--modes needs --beast-in or --avr-in")
-    if a.commb and (not a.modes or a.aircraft):
-        ap.error("--commb needs --modes, without --aircraft")
+    if a.commb and not a.modes:
+        ap.error("--commb needs --modes")
     if wire_in and a.levels and not a.aircraft:
         ap.error("--levels alone needs the samples")
     fmt = a.format or ("c16" if a.file.endswith(".c16") else "u8")
@@ -380,7 +390,7 @@ def main():
             frames, recs, *regs = read_wire(d, a.file, wire_in, a.tick_bias, modes=True, commb=a.commb)
             if a.aircraft:
                 n_samp = int(frames["offset"].max()) + A.WINDOW if len(frames) else 0
-                sys.stdout.write(aircraft_table(d, frames, n_samp, site=a.site, modes=recs))
+                sys.stdout.write(aircraft_table(d, frames, n_samp, site=a.site, modes=recs, commb=regs[0] if a.commb else None))
             else:
                 sys.stdout.write(modes_lines(frames, recs, regs[0] if a.commb else None))
             if a.summary:
