@@ -144,6 +144,32 @@ class AdsbCommbHeader(C.Structure):
                 + [("n_bds", C.c_uint64 * 7), ("reserved", C.c_uint64 * 3)])
 
 
+(ADSB_ES_NOT_ES, ADSB_ES_FOREIGN, ADSB_ES_CATEGORY, ADSB_ES_POSITION, ADSB_ES_VELOCITY, ADSB_ES_EMERGENCY, ADSB_ES_ACAS_RA,
+ ADSB_ES_TARGET_STATE, ADSB_ES_OPERATIONAL, ADSB_ES_RESERVED) = range(10)                       # adsb_es_rec.state
+ES_PRESENT = ("CATEGORY", "NIC_B", "RC", "NAC_V", "VELOCITY_FLAGS", "EMERGENCY", "SQUAWK", "RA", "SIL_SUPPLEMENT", "ALT_SOURCE",
+              "SELECTED_ALT", "BARO", "HEADING", "NAC_P", "NIC_BARO", "SIL", "MODES", "TCAS", "VERSION", "CC_OM", "NIC_A", "HRD",
+              "TRACK_HEADING", "LENGTH_WIDTH", "SDA", "GVA", "NIC_C")                            # adsb_es_rec.present, bit k
+ES_FLAGS = ("INTENT_CHANGE", "IFR", "ALT_FMS", "AUTOPILOT", "VNAV", "ALT_HOLD", "APPROACH", "LNAV", "TCAS", "HRD",
+            "TRACK_HEADING")                                                                    # adsb_es_rec.flags, bit k
+globals().update({"ADSB_ES_HAS_" + name: 1 << k for k, name in enumerate(ES_PRESENT)})
+globals().update({"ADSB_ES_" + name: 1 << k for k, name in enumerate(ES_FLAGS)})
+ADSB_ES_VERSION_UNKNOWN = 0xFF
+
+
+class AdsbEsRec(C.Structure):
+    """adsb_es_rec: what one DF17/18 frame says about the aircraft's status (32 bytes)."""
+    _fields_ = ([("state", C.c_uint8), ("type_code", C.c_uint8), ("subtype", C.c_uint8), ("version", C.c_uint8),
+                 ("present", C.c_uint32)]
+                + [(k, C.c_uint8) for k in ("nic_a", "nic_b", "nic_c", "nac_p", "nac_v", "sil", "sil_supplement", "gva", "sda",
+                                            "nic_baro", "category", "emergency", "length_width", "reserved")]
+                + [("flags", C.c_uint16), ("value", C.c_uint32), ("half", C.c_uint16 * 2)])
+
+
+class AdsbEsHeader(C.Structure):
+    """adsb_es_header: the totals of one adsb_es_of (128 bytes)."""
+    _fields_ = [("n", C.c_uint64), ("n_state", C.c_uint64 * 10), ("n_version", C.c_uint64 * 4), ("reserved", C.c_uint64)]
+
+
 class AdsbCorrelateCfg(C.Structure):
     """adsb_correlate_cfg: the window in samples, and whether adsb_correlate_launch takes the launch's levels."""
     _fields_ = [("window", C.c_uint32), ("use_levels", C.c_uint32), ("reserved", C.c_uint64)]
@@ -480,6 +506,10 @@ PROTOTYPES = {
     "adsb_fetch_commb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(AdsbCommbHeader)]),
     "adsb_commb_device": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p)]),
     "adsb_debug_commb_geometry": (C.c_int, [_P(C.c_uint32)]),
+    "adsb_es_of": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "adsb_fetch_es": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(AdsbEsHeader)]),
+    "adsb_es_device": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p)]),
+    "adsb_debug_es_geometry": (C.c_int, [_P(C.c_uint32)]),
     "adsb_correlate_launch": (C.c_int, [C.c_void_p, _P(AdsbCorrelateCfg), C.c_void_p]),
     "adsb_correlate_of": (C.c_int, [C.c_void_p, _P(AdsbCorrelateCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                     C.c_uint32, C.c_void_p]),
@@ -661,6 +691,8 @@ PROTOTYPES = {
                                   C.c_void_p, C.c_void_p, C.c_void_p, _P(AdsbModesHeader)]),
     "adsb_host_commb": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, _P(AdsbCommbHeader)]),
     "adsb_host_commb_as": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
+    "adsb_host_es": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, _P(AdsbEsHeader)]),
+    "adsb_host_es_integrity": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
     "adsb_host_correlate": (C.c_int, [_P(AdsbCorrelateCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
                                       C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p]),
     "adsb_host_multilaterate": (C.c_int, [_P(AdsbMlatCfg), C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,

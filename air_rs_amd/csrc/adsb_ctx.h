@@ -146,6 +146,15 @@ struct adsb_ctx {
         DevBuf<adsb_frame> in_frames;        // of a host list
         bool done = false;                   // a call has been enqueued
     } commb;
+    // Extended squitter status (adsb_es.hip), allocated on first adsb_es_of and grown on demand: one hipMalloc carved
+    // into the partial counts, the records and the header, and the device copy of a host list
+    struct Es {
+        DevBuf<char> mem;
+        size_t frames = 0;                   // what it holds
+        adsbk::EsArgs a{};                   // scratch and result pointers (the list and its length are set per call)
+        DevBuf<adsb_frame> in_frames;        // of a host list
+        bool done = false;                   // a call has been enqueued
+    } es;
     // tracker (allocated on first adsb_track_device): one hipMalloc carved into the five below
     DevBuf<char> trk_mem;
     uint32_t *trk_u32 = nullptr;    // 4 x [max_out]: keys, vals, sorted keys, sorted vals

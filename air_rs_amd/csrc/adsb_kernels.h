@@ -305,6 +305,20 @@ struct CommbArgs {
 };
 hipError_t launch_commb(hipStream_t s, const CommbArgs &a);
 
+// the extended squitter status of every DF17/18 frame (adsb_es.hip; adsb_es.h has the text of one frame)
+constexpr uint32_t kEsBlock = 256; // frames (= threads) per workgroup of es_frames
+constexpr uint32_t kEsTallyWords = 14; // per workgroup: the ten states, then the OPERATIONAL records of version 0, 1, 2, 3-7
+constexpr uint32_t es_blocks(uint64_t n) { return (uint32_t)((n + kEsBlock - 1) / kEsBlock); }
+struct EsArgs {
+    const adsb_frame *frames; // [n], adsb_fetch's layout
+    uint32_t n;
+    uint32_t *tally;          // [kEsTallyWords x es_blocks(n)]
+    // results
+    adsb_es_rec *recs;        // [n], 16-byte aligned
+    adsb_es_header *hdr;
+};
+hipError_t launch_es(hipStream_t s, const EsArgs &a);
+
 // transmitter positions from correlated receptions (adsb_mlat.hip; adsb_mlat.h has the solver's text)
 constexpr uint32_t kMlatBlock = 256;                          // threads per workgroup of mlat_solve
 constexpr uint32_t kMlatPerBlock = kMlatBlock / kMlatLanes;   // messages per workgroup: 16 lanes each

@@ -350,6 +350,54 @@ def commb_physical(recs):
     return out
 
 
+ES_DTYPE = np.dtype([("state", "u1"), ("type_code", "u1"), ("subtype", "u1"), ("version", "u1"), ("present", "<u4")]
+                    + [(k, "u1") for k in ("nic_a", "nic_b", "nic_c", "nac_p", "nac_v", "sil", "sil_supplement", "gva", "sda",
+                                           "nic_baro", "category", "emergency", "length_width", "reserved")]
+                    + [("flags", "<u2"), ("value", "<u4"), ("half", "<u2", (2,))])
+assert ES_DTYPE.itemsize == C.sizeof(L.AdsbEsRec) == 32
+ES_HEADER_DTYPE = np.dtype([("n", "<u8"), ("n_state", "<u8", (10,)), ("n_version", "<u8", (4,)), ("reserved", "<u8")])
+assert ES_HEADER_DTYPE.itemsize == C.sizeof(L.AdsbEsHeader) == 128
+ES_STATES = ("NOT_ES", "FOREIGN", "CATEGORY", "POSITION", "VELOCITY", "EMERGENCY", "ACAS_RA", "TARGET_STATE", "OPERATIONAL",
+             "RESERVED")
+# es_physical: key -> (present bit, field, index into it or None, what one unit of the value is in the key's unit)
+_ES_PHYSICAL = {
+    "rc_m": (L.ADSB_ES_HAS_RC, "value", None, 0.1),
+    "selected_altitude_ft": (L.ADSB_ES_HAS_SELECTED_ALT, "value", None, 1.0),
+    "baro_setting_mb": (L.ADSB_ES_HAS_BARO, "half", 0, 0.1),
+    "selected_heading_deg": (L.ADSB_ES_HAS_HEADING, "half", 1, 180.0 / 256.0),
+}
+
+
+def host_es(frames):
+    """adsb_host_es, the CPU mirror of AdsbDemod.es_of: (ES_DTYPE records, the ES_HEADER_DTYPE record) of the
+    FRAME_DTYPE list `frames`.  Needs no device."""
+    frames, fptr, n = _host_list(frames, FRAME_DTYPE)
+    recs, hdr = np.zeros(max(n, 1), dtype=ES_DTYPE), L.AdsbEsHeader()
+    L.check(L.load().adsb_host_es(fptr, n, recs.ctypes.data, C.byref(hdr)), "adsb_host_es")
+    return recs[:n].copy(), np.frombuffer(bytes(hdr), dtype=ES_HEADER_DTYPE)[0]
+
+
+def host_es_integrity(tc, version, supp=0):
+    """adsb_host_es_integrity: (NIC, Rc in decimetres, 0 for unknown) of a position message with type code `tc` from an
+    aircraft of ADS-B `version` (ADSB_ES_VERSION_UNKNOWN reads as 0) with the NIC supplements `supp` (bit 0 = A, bit 1 =
+    B, bit 2 = C).  Needs no device."""
+    nic, rc = C.c_uint32(), C.c_uint32()
+    L.check(L.load().adsb_host_es_integrity(int(tc), int(version), int(supp), C.byref(nic), C.byref(rc)), "adsb_host_es_integrity")
+    return nic.value, rc.value
+
+
+def es_physical(recs):
+    """The values of ES_DTYPE records in physical units: a dict of float64 arrays, one entry per record, NaN where the
+    record does not hold the value (its present bit is off).  POSITION: rc_m, the containment radius the type code alone
+    gives, in metres.  TARGET_STATE: selected_altitude_ft, baro_setting_mb, selected_heading_deg."""
+    recs = np.atleast_1d(np.asarray(recs, dtype=ES_DTYPE))
+    out = {}
+    for key, (bit, field, k, factor) in _ES_PHYSICAL.items():
+        raw = recs[field] if k is None else recs[field][:, k]
+        out[key] = np.where(recs["present"] & bit != 0, raw * factor, np.nan)
+    return out
+
+
 COMMB_SETTLED = L.ADSB_COMMB_SETTLED     # COMMB_DTYPE state of a table's per-frame output: settled by the table
 # aircraft_commb_physical: key -> (block, index into value[], what one unit of the value is in the key's unit)
 _AIRCRAFT_COMMB_PHYSICAL = {key: ("bds%02x" % bds, k, factor) for key, (bds, k, factor) in _COMMB_PHYSICAL.items()}
@@ -1091,6 +1139,38 @@ class AdsbDemod:
         """adsb_commb_device: device addresses (records, header); no synchronisation."""
         p = [C.c_void_p() for _ in range(2)]
         L.check(self._lib.adsb_commb_device(self._h, *[C.byref(x) for x in p]), "adsb_commb_device")
+        return tuple(x.value for x in p)
+
+    def es_of_async(self, frames):
+        """adsb_es_of alone: enqueues and returns once a host list is copied.  frames: a FRAME_DTYPE array (host) or
+        (device pointer, count), for example modes_device()[2] with the squitter count."""
+        if isinstance(frames, tuple):
+            fptr, n = (int(frames[0]) if int(frames[1]) else None), int(frames[1])
+        else:
+            frames, fptr, n = _host_list(frames, FRAME_DTYPE)
+        L.check(self._lib.adsb_es_of(self._h, fptr, n), "adsb_es_of")
+
+    def fetch_es(self):
+        """adsb_fetch_es: waits for the last es_of_async() -> (ES_DTYPE records, the ES_HEADER_DTYPE record)."""
+        hdr = L.AdsbEsHeader()
+        L.check(self._lib.adsb_fetch_es(self._h, None, 0, C.byref(hdr)), "adsb_fetch_es")   # the size first
+        n = int(hdr.n)
+        recs = np.zeros(max(n, 1), dtype=ES_DTYPE)
+        L.check(self._lib.adsb_fetch_es(self._h, recs.ctypes.data, n, C.byref(hdr)), "adsb_fetch_es")
+        return recs[:n].copy(), np.frombuffer(bytes(hdr), dtype=ES_HEADER_DTYPE)[0]
+
+    def es_of(self, frames):
+        """adsb_es_of + adsb_fetch_es: for every DF17/18 frame what it says about the aircraft's status (state:
+        ES_STATES; the emitter category, the emergency state and squawk, the ACAS RA, the target state, the operational
+        status, NACv and NIC supplement B) -> (recs, header), index for index with the list and with modes_of's
+        records.  es_physical(recs) gives the values in physical units.  See es_of_async."""
+        self.es_of_async(frames)
+        return self.fetch_es()
+
+    def es_device(self):
+        """adsb_es_device: device addresses (records, header); no synchronisation."""
+        p = [C.c_void_p() for _ in range(2)]
+        L.check(self._lib.adsb_es_device(self._h, *[C.byref(x) for x in p]), "adsb_es_device")
         return tuple(x.value for x in p)
 
     def correlate_async(self, window, sample_base=None, levels=False):

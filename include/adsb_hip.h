@@ -748,6 +748,156 @@ int adsb_commb_device(adsb_ctx *ctx, const adsb_commb_rec **recs_dev, const void
 int adsb_debug_commb_geometry(uint32_t *threads_per_block);
 
 /*
+ * Extended squitter status: what a DF17/18 frame says about the aircraft beside identity, position and velocity: the
+ * emitter category (TC 1-4), the emergency state and squawk and the ACAS RA broadcast (TC 28), the target state (TC 29),
+ * the operational status with the ADS-B version and the integrity and accuracy categories (TC 31), NACv of a velocity
+ * (TC 19), NIC supplement B and the stand-alone containment radius of a position (TC 5-18, 20-22).  Stateless, per
+ * frame, integers only, no inference (an extended squitter says what it is); computed on the device; the list is in
+ * adsb_fetch's layout, as for adsb_modes_of and adsb_commb_of.  The stage decides whatever the frame's parity says:
+ * consumers pair the record with adsb_modes_rec.kind, index for index.
+ *   BIT NUMBERING  ME is bytes[4..11).  Bit 1 is the top bit of bytes[4], bit 56 the low bit of bytes[10]; u(a, n) is
+ *     the n bits from bit a as an unsigned number (the numbering of MB in "Comm-B registers").  DF = bytes[0] >> 3,
+ *     TC = u(1,5), ST = u(6,3).
+ *   STATE  the first rule that applies:
+ *     NOT_ES        DF is not 17 or 18.  Every other byte of the record is 0.
+ *     FOREIGN       DF 18 with bytes[0] & 7 not 0 or 1 (TIS-B, ADS-R and the rest: other ME layouts).  Every other
+ *                   byte is 0.
+ *     CATEGORY      TC 1-4.
+ *     POSITION      TC 0, 5-8, 9-18, 20-22.
+ *     VELOCITY      TC 19 with ST 1-4.
+ *     EMERGENCY     TC 28 with ST 1.
+ *     ACAS_RA       TC 28 with ST 2.
+ *     TARGET_STATE  TC 29 with u(6,2) == 1 (DO-260B; the DO-260A form, u(6,2) == 0, is counted as RESERVED).
+ *     OPERATIONAL   TC 31 with ST 0 (airborne) or 1 (surface).
+ *     RESERVED      everything else: type_code and subtype and nothing more.
+ *     type_code is set in every state from CATEGORY on.  subtype is u(6,3) in VELOCITY, EMERGENCY, ACAS_RA,
+ *     OPERATIONAL and RESERVED, u(6,2) for TC 29 (TARGET_STATE, or RESERVED), and 0 in CATEGORY and POSITION, whose
+ *     bits 6-8 are no subtype.
+ *   FIELDS  Bit ADSB_ES_HAS_x of `present` says that field x holds a value; a field whose bit is off is 0.
+ *     CATEGORY      category = (0xE - TC) << 4 | u(6,3): set A to D in the high nibble, so TC 4 with CA 0 is 0xA0.
+ *     POSITION      nic_b = u(8,1) for TC 9-18.  value = the containment radius Rc in decimetres that the type code
+ *                   alone gives (the version-0 reading of adsb_host_es_integrity's table), with HAS_RC where it gives
+ *                   one.  A consumer that knows the aircraft's version and supplements replaces it.
+ *     VELOCITY      nac_v = u(11,3); flags INTENT_CHANGE = u(9,1) and IFR = u(10,1), with HAS_VELOCITY_FLAGS.
+ *     EMERGENCY     emergency = u(9,3).  half[0] = the squawk of the 13 bits u(12,13), C1 A1 C2 A2 C4 A4 X B1 D1 B2 D2
+ *                   B4 D4, as adsb_modes_rec.squawk spells it: 7700 reads 7700, X is ignored.
+ *     ACAS_RA       value = u(9,32), half[0] = u(41,16): ARA 14, RAC 4, RAT 1, MTE 1, TTI 2, TID 26 bits, what BDS 3,0
+ *                   carries at MB 9-56.
+ *     TARGET_STATE  version = 2.  sil_supplement = u(8,1).  Flag ALT_FMS = u(9,1) (0: MCP/FCU) and flag TCAS = u(53,1),
+ *                   always.  value = 32 (n - 1) feet with n = u(10,11) != 0: the selected altitude.  half[0] = 8000 +
+ *                   8 (n - 1) tenths of a millibar with n = u(21,9) != 0: the barometric setting, in the unit of BDS
+ *                   4,0's value[2].  half[1] = u(31,9) with u(30,1) set: the selected heading, LSB 180/256 degrees.
+ *                   nac_p = u(40,4), nic_baro = u(44,1), sil = u(45,2).  With u(47,1) set, HAS_MODES and the flags
+ *                   AUTOPILOT = u(48,1), VNAV = u(49,1), ALT_HOLD = u(50,1), APPROACH = u(52,1), LNAV = u(54,1).
+ *     OPERATIONAL   version = u(41,3).  Version 0, 1, 2: half[0] = cc = u(9,16) and half[1] = om = u(25,16), raw.
+ *                   Version 1 and 2: nic_a = u(44,1), nac_p = u(45,4), sil = u(51,2), flag HRD = u(54,1); ST 0:
+ *                   nic_baro = u(53,1); ST 1: flag TRACK_HEADING = u(53,1) and length_width = u(21,4).  Version 2 also:
+ *                   sil_supplement = u(55,1), sda = u(31,2); ST 0: gva = u(49,2); ST 1: nic_c = u(20,1) and the
+ *                   surface nac_v = u(17,3).  Version 3-7: the version and nothing more.
+ *   OUTPUTS  adsb_es_rec recs[n], index for index with the list, every byte of every record written; the
+ *     adsb_es_header.
+ * Nothing depends on atomics or scheduling: two runs give the same bytes.
+ */
+#define ADSB_ES_NOT_ES 0u
+#define ADSB_ES_FOREIGN 1u
+#define ADSB_ES_CATEGORY 2u
+#define ADSB_ES_POSITION 3u
+#define ADSB_ES_VELOCITY 4u
+#define ADSB_ES_EMERGENCY 5u
+#define ADSB_ES_ACAS_RA 6u
+#define ADSB_ES_TARGET_STATE 7u
+#define ADSB_ES_OPERATIONAL 8u
+#define ADSB_ES_RESERVED 9u
+#define ADSB_ES_STATES 10u
+/* adsb_es_rec.present */
+#define ADSB_ES_HAS_CATEGORY 0x1u
+#define ADSB_ES_HAS_NIC_B 0x2u
+#define ADSB_ES_HAS_RC 0x4u
+#define ADSB_ES_HAS_NAC_V 0x8u
+#define ADSB_ES_HAS_VELOCITY_FLAGS 0x10u
+#define ADSB_ES_HAS_EMERGENCY 0x20u
+#define ADSB_ES_HAS_SQUAWK 0x40u
+#define ADSB_ES_HAS_RA 0x80u
+#define ADSB_ES_HAS_SIL_SUPPLEMENT 0x100u
+#define ADSB_ES_HAS_ALT_SOURCE 0x200u
+#define ADSB_ES_HAS_SELECTED_ALT 0x400u
+#define ADSB_ES_HAS_BARO 0x800u
+#define ADSB_ES_HAS_HEADING 0x1000u
+#define ADSB_ES_HAS_NAC_P 0x2000u
+#define ADSB_ES_HAS_NIC_BARO 0x4000u
+#define ADSB_ES_HAS_SIL 0x8000u
+#define ADSB_ES_HAS_MODES 0x10000u
+#define ADSB_ES_HAS_TCAS 0x20000u
+#define ADSB_ES_HAS_VERSION 0x40000u
+#define ADSB_ES_HAS_CC_OM 0x80000u
+#define ADSB_ES_HAS_NIC_A 0x100000u
+#define ADSB_ES_HAS_HRD 0x200000u
+#define ADSB_ES_HAS_TRACK_HEADING 0x400000u
+#define ADSB_ES_HAS_LENGTH_WIDTH 0x800000u
+#define ADSB_ES_HAS_SDA 0x1000000u
+#define ADSB_ES_HAS_GVA 0x2000000u
+#define ADSB_ES_HAS_NIC_C 0x4000000u
+/* adsb_es_rec.flags */
+#define ADSB_ES_INTENT_CHANGE 0x1u
+#define ADSB_ES_IFR 0x2u
+#define ADSB_ES_ALT_FMS 0x4u
+#define ADSB_ES_AUTOPILOT 0x8u
+#define ADSB_ES_VNAV 0x10u
+#define ADSB_ES_ALT_HOLD 0x20u
+#define ADSB_ES_APPROACH 0x40u
+#define ADSB_ES_LNAV 0x80u
+#define ADSB_ES_TCAS 0x100u
+#define ADSB_ES_HRD 0x200u
+#define ADSB_ES_TRACK_HEADING 0x400u
+/* the version argument of adsb_host_es_integrity for an aircraft whose operational status has not been heard */
+#define ADSB_ES_VERSION_UNKNOWN 0xFFu
+typedef struct adsb_es_rec {      /* 32 bytes */
+    uint8_t  state;               /* ADSB_ES_NOT_ES ...                                                */
+    uint8_t  type_code;
+    uint8_t  subtype;
+    uint8_t  version;
+    uint32_t present;             /* ADSB_ES_HAS_...                                                   */
+    uint8_t  nic_a, nic_b, nic_c;
+    uint8_t  nac_p, nac_v;
+    uint8_t  sil, sil_supplement;
+    uint8_t  gva, sda, nic_baro;
+    uint8_t  category;
+    uint8_t  emergency;
+    uint8_t  length_width;
+    uint8_t  reserved;            /* 0 */
+    uint16_t flags;               /* ADSB_ES_INTENT_CHANGE ...                                         */
+    uint32_t value;               /* Rc in dm / selected altitude in ft / u(9,32) of an RA             */
+    uint16_t half[2];             /* squawk, - / baro setting, heading / cc, om / u(41,16) of an RA, -  */
+} adsb_es_rec;
+typedef struct adsb_es_header {   /* 128 bytes */
+    uint64_t n;
+    uint64_t n_state[10];         /* records per state, n_state[ADSB_ES_NOT_ES] ...                    */
+    uint64_t n_version[4];        /* OPERATIONAL records of version 0, 1, 2 and 3-7                    */
+    uint64_t reserved;            /* 0 */
+} adsb_es_header;
+#ifdef __cplusplus
+static_assert(sizeof(adsb_es_rec) == 32 && sizeof(adsb_es_header) == 128, "adsb_es_rec / adsb_es_header layout");
+#endif
+/* Reads every frame.  frames[n] in host memory or in device memory of the ctx's device; n comes from the host, as for
+ * the other _of calls.  Asynchronous on the ctx's stream once a host list is copied.  Buffers are allocated on first
+ * use and grown when needed (may wait for earlier work): per frame 32 bytes of results, and 56 bytes per 256 frames of
+ * partial counts; a ctx that never calls it allocates nothing and launches exactly the kernels it launched before.
+ * Replaces the result of an earlier call; shares no buffer with another stage's result.  n = 0 is ADSB_OK.  ADSB_E_ARG
+ * for a NULL ctx or NULL frames with n > 0; ADSB_E_CAPACITY for n >= 2^32. */
+int adsb_es_of(adsb_ctx *ctx, const adsb_frame *frames, size_t n);
+/* Waits and copies; recs may be NULL (with capacity 0) and receives min(header.n, max_recs) records; *header
+ * (optional) the totals, whatever the capacity.  ADSB_E_STATE before any adsb_es_of; ADSB_E_ARG for a NULL ctx or NULL
+ * recs with a capacity. */
+int adsb_fetch_es(adsb_ctx *ctx, adsb_es_rec *recs, size_t max_recs, adsb_es_header *header);
+/* For device-side consumers; does not synchronise.  The records and the header of the last adsb_es_of in device memory
+ * (each optional), valid until the next call and ordered on the ctx's stream behind it.  ADSB_E_STATE before any
+ * adsb_es_of. */
+int adsb_es_device(adsb_ctx *ctx, const adsb_es_rec **recs_dev, const void **header_dev);
+/* Threads (= frames) per workgroup of the stage's kernel: the size at which it takes another path, for tests.  The
+ * result does not depend on it. */
+int adsb_debug_es_geometry(uint32_t *threads_per_block);
+
+/*
  * Multilaterate: where each correlated message was sent from, solved from the times its receivers heard it.  One small
  * non-linear least-squares problem per message, all messages of a list in one kernel; f64; stateless.
  *   INPUT  a correlate result msgs[M] / recs[N]; adsb_mlat_receiver receivers[R], 1 <= R <= 256, WGS84 degrees and

@@ -174,6 +174,37 @@ int adsb_host_commb(const adsb_frame *frames, size_t n, adsb_commb_rec *recs, ad
 int adsb_host_commb_as(const uint8_t bytes[14], uint32_t bds, adsb_commb_rec *rec);
 
 /*
+ * CPU mirror of adsb_es_of + adsb_fetch_es (adsb_hip.h, "Extended squitter status"): the same records and header from
+ * the same program text as the device's, on one core, no device needed.  frames host memory; recs[n] and *header may
+ * each be NULL.  ADSB_E_ARG for NULL frames with n > 0; ADSB_E_CAPACITY for n >= 2^32.
+ * es_integrity: the navigation integrity category and the containment radius Rc in decimetres (0: unknown) of a
+ * position message with type code tc, from an aircraft of ADS-B `version` whose NIC supplements are `supp` (bit 0 = A
+ * and bit 2 = C from its operational status, bit 1 = B from the position message itself).  A version from 3 on reads
+ * as 2, ADSB_ES_VERSION_UNKNOWN as 0; version 0 has no NIC (its NUCp is another scale) and reports 0; version 1
+ * ignores B and C.  Each of *nic and *rc_dm may be NULL; always ADSB_OK.  THE TABLE, Rc in metres, "-" unknown:
+ *     TC          version 0   version 1 and 2: NIC, Rc
+ *     0, 18, 22   -           0, -
+ *     9, 20       7.5         11, 7.5
+ *     10, 21      25          10, 25
+ *     11          185.2       9, 75 with A (v1) or A and B (v2); else 8, 185.2
+ *     12          370.4       7, 370.4
+ *     13          926         6; v1: 1111.2 with A, else 926; v2: 1111.2 with A, else 555.6 with B, else 926
+ *     14          1852        5, 1852
+ *     15          3704        4, 3704
+ *     16          18520       3, 7408 with A (v1) or A and B (v2); else 2, 14816
+ *     17          37040       1, 37040
+ *     5           7.5         11, 7.5
+ *     6           25          10, 25
+ *     7           185.2       9, 75 with A (v1) or A and not C (v2); else 8, 185.2
+ *     8           -           v1: 0, -; v2: A and C: 7, 370.4; A alone: 6, 555.6; C alone: 6, 1111.2; neither: 0, -
+ *     any other   -           0, -
+ *   The table was written down from memory of RTCA DO-260B table N-4 and of readsb's compute_nic / compute_rc, without
+ *   either at hand: compare before relying on a row.
+ */
+int adsb_host_es(const adsb_frame *frames, size_t n, adsb_es_rec *recs, adsb_es_header *header);
+int adsb_host_es_integrity(uint32_t tc, uint32_t version, uint32_t supp, uint32_t *nic, uint32_t *rc_dm);
+
+/*
  * CPU mirror of adsb_multilaterate_of (adsb_hip.h, "Multilaterate"): the same fixes and header from the same program text
  * as the device's -- the solver, and the 16 partial sums of every sum over receptions folded in the same butterfly -- on
  * one core, no device needed.  All arrays host memory; rx / n_rx may be NULL / 0 with ADSB_MLAT_TIME_RECEPTION; fixes

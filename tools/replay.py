@@ -15,6 +15,7 @@
   tools/replay.py out.bin --beast-in          # FILE is a Beast capture (a receiver's TCP stream) instead of IQ
   tools/replay.py out.txt --avr-in            # ... an AVR text capture, "*" and "@" lines alike
   tools/replay.py out.txt --avr-in --modes --commb   # one line per frame; DF20/21 lines with their Comm-B register
+  tools/replay.py out.txt --avr-in --es       # one line per DF17/18 frame: what it says about the aircraft's status
 
 Everything below the argument parsing is one call through the C ABI (adsb_replay_file, include/adsb_host.h).
 The "Processed Time" line carries no value (the reference prints the wall clock there).  With --aircraft, the frames
@@ -57,7 +58,14 @@ every DF20/21 line also ends with the Comm-B register its MB field carries, infe
 (adsb_commb_of, on the list where wire input left it): "BDS4,0 mcp=3008ft fms=3008ft baro=1020.0mb", the values whose
 status bit is set in feet, mb, degrees, kt, Mach, degrees per second and ft/min; for BDS 1,7 the registers the
 transponder reports; "?" and the candidates ("?5,0|6,0") where more than one register fits, "-" where none does or MB
-is empty.  The TEXT has not been compared with a Rust build's (there is no
+is empty.  With --es (on samples, --beast-in and --avr-in alike) the frame list goes through the extended squitter
+status stage (adsb_es_of) and one line per DF17/18 frame is printed instead: time in seconds, DF, the address in the
+frame, and the state with its values: "CATEGORY A0", "POSITION tc=11 nic_b=0 rc=185.2m", "VELOCITY st=1 nac_v=0 ifr",
+"EMERGENCY state=0 squawk=6513", "ACAS_RA ara=... rac=. rat=. mte=. tti=. tid=.......", "TARGET_STATE alt=16992ft(mcp)
+baro=1012.8mb hdg=66.8 nac_p=9 nic_baro=1 sil=3 modes=autopilot,vnav,lnav tcas", "OPERATIONAL st=0 v2 cc=2300 om=0300
+nic_a=0 nac_p=9 sil=3 nic_baro=1 sil_supp=0 sda=3 gva=2", "RESERVED tc=23 st=0", "FOREIGN"; a value the frame does not hold is left
+out.  The stage does not check parity: the frames of a Beast or AVR capture are read as they stand.
+The TEXT has not been compared with a Rust build's (there is no
 Rust toolchain); only the values are checked, against the oracle."""
 import argparse
 import json
@@ -269,6 +277,73 @@ def commb_text(c):
     return " ".join(parts)
 
 
+ES_MODE_FLAGS = (("autopilot", A.ADSB_ES_AUTOPILOT), ("vnav", A.ADSB_ES_VNAV), ("alt_hold", A.ADSB_ES_ALT_HOLD),
+                 ("approach", A.ADSB_ES_APPROACH), ("lnav", A.ADSB_ES_LNAV))
+# --es, OPERATIONAL: (label, field, present bit) in the order printed
+ES_OPERATIONAL = (("nic_a", "nic_a", A.ADSB_ES_HAS_NIC_A), ("nac_p", "nac_p", A.ADSB_ES_HAS_NAC_P), ("sil", "sil", A.ADSB_ES_HAS_SIL),
+                  ("nic_baro", "nic_baro", A.ADSB_ES_HAS_NIC_BARO), ("lw", "length_width", A.ADSB_ES_HAS_LENGTH_WIDTH),
+                  ("sil_supp", "sil_supplement", A.ADSB_ES_HAS_SIL_SUPPLEMENT), ("sda", "sda", A.ADSB_ES_HAS_SDA),
+                  ("gva", "gva", A.ADSB_ES_HAS_GVA), ("nic_c", "nic_c", A.ADSB_ES_HAS_NIC_C), ("nac_v", "nac_v", A.ADSB_ES_HAS_NAC_V))
+
+
+def es_text(r):
+    """--es: the state of one ES_DTYPE record and the values it holds, in physical units where es_physical has one."""
+    state, has, flags = int(r["state"]), int(r["present"]), int(r["flags"])
+    parts, phys = [A.ES_STATES[state]], A.es_physical(r)
+    if state == A.ADSB_ES_CATEGORY:
+        parts.append(f"{int(r['category']):02X}")
+    elif state == A.ADSB_ES_POSITION:
+        parts.append(f"tc={int(r['type_code'])}")
+        if has & A.ADSB_ES_HAS_NIC_B:
+            parts.append(f"nic_b={int(r['nic_b'])}")
+        if has & A.ADSB_ES_HAS_RC:
+            parts.append(f"rc={float(phys['rc_m'][0]):.1f}m")
+    elif state == A.ADSB_ES_VELOCITY:
+        parts += [f"st={int(r['subtype'])}", f"nac_v={int(r['nac_v'])}"]
+        parts += [name for name, bit in (("intent", A.ADSB_ES_INTENT_CHANGE), ("ifr", A.ADSB_ES_IFR)) if flags & bit]
+    elif state == A.ADSB_ES_EMERGENCY:
+        parts += [f"state={int(r['emergency'])}", f"squawk={int(r['half'][0]):04d}"]
+    elif state == A.ADSB_ES_ACAS_RA:
+        bits = int(r["value"]) << 16 | int(r["half"][0])             # ARA 14, RAC 4, RAT 1, MTE 1, TTI 2, TID 26
+        parts += [f"ara={bits >> 34:04X}", f"rac={bits >> 30 & 15:X}", f"rat={bits >> 29 & 1}", f"mte={bits >> 28 & 1}",
+                  f"tti={bits >> 26 & 3}", f"tid={bits & 0x3FFFFFF:07X}"]
+    elif state == A.ADSB_ES_TARGET_STATE:
+        if has & A.ADSB_ES_HAS_SELECTED_ALT:
+            parts.append(f"alt={float(phys['selected_altitude_ft'][0]):.0f}ft({'fms' if flags & A.ADSB_ES_ALT_FMS else 'mcp'})")
+        if has & A.ADSB_ES_HAS_BARO:
+            parts.append(f"baro={float(phys['baro_setting_mb'][0]):.1f}mb")
+        if has & A.ADSB_ES_HAS_HEADING:
+            parts.append(f"hdg={float(phys['selected_heading_deg'][0]):.1f}")
+        parts += [f"nac_p={int(r['nac_p'])}", f"nic_baro={int(r['nic_baro'])}", f"sil={int(r['sil'])}"]
+        if int(r["sil_supplement"]):
+            parts.append("sil_supp=1")
+        if has & A.ADSB_ES_HAS_MODES:
+            parts.append("modes=" + (",".join(name for name, bit in ES_MODE_FLAGS if flags & bit) or "none"))
+        if flags & A.ADSB_ES_TCAS:
+            parts.append("tcas")
+    elif state == A.ADSB_ES_OPERATIONAL:
+        parts += [f"st={int(r['subtype'])}", f"v{int(r['version'])}"]
+        if has & A.ADSB_ES_HAS_CC_OM:
+            parts += [f"cc={int(r['half'][0]):04X}", f"om={int(r['half'][1]):04X}"]
+        parts += [f"{label}={int(r[field])}" for label, field, bit in ES_OPERATIONAL if has & bit]
+        parts += [name for name, bit, on in (("hrd", A.ADSB_ES_HAS_HRD, A.ADSB_ES_HRD),
+                                             ("heading", A.ADSB_ES_HAS_TRACK_HEADING, A.ADSB_ES_TRACK_HEADING)) if has & bit and flags & on]
+    elif state == A.ADSB_ES_RESERVED:
+        parts += [f"tc={int(r['type_code'])}", f"st={int(r['subtype'])}"]
+    return " ".join(parts)
+
+
+def es_lines(frames, recs):
+    """--es: one line per DF17/18 frame from its ES_DTYPE record."""
+    out = []
+    for f, r in zip(frames, recs):
+        if int(r["state"]) != A.ADSB_ES_NOT_ES:
+            b = f["bytes"]
+            out.append(f"{int(f['offset']) * SECONDS_PER_SAMPLE:.6f} DF{int(b[0]) >> 3} {int(b[1]) << 16 | int(b[2]) << 8 | int(b[3]):06X} "
+                       f"{es_text(r)}\n")
+    return "".join(out)
+
+
 def modes_lines(frames, recs, commb=None):
     """--modes: one line per frame from its MODES_DTYPE record; commb (one COMMB_DTYPE record per frame): the DF20/21
     lines end with commb_text()."""
@@ -364,6 +439,9 @@ def main():
     ap.add_argument("--commb", action="store_true",
                     help="with --modes: every DF20/21 line also gets the Comm-B register inferred from its MB field and its "
                          "values; with --modes --aircraft: six more columns from the aircraft's Comm-B registers")
+    ap.add_argument("--es", action="store_true",
+                    help="print one line per DF17/18 frame instead: its extended squitter status (category, emergency, target "
+                         "state, operational status, NACv, NIC supplement B, stand-alone Rc)")
     ap.add_argument("--tick-bias", type=int, default=0, metavar="N", help="added to every timestamp (12 MHz ticks, < 2^48)")
     a = ap.parse_args()
     if a.mlat and not a.avr:
@@ -381,6 +459,8 @@ def main():
         ap.error("--commb needs --modes")
     if wire_in and a.levels and not a.aircraft:
         ap.error("--levels alone needs the samples")
+    if a.es and (a.modes or a.aircraft or a.web or a.levels):
+        ap.error("--es prints lines of its own: not with --modes, --aircraft, --web or --levels")
     fmt = a.format or ("c16" if a.file.endswith(".c16") else "u8")
     st = A.ADSB_SAMPLE_I16 if fmt == "c16" else A.ADSB_SAMPLE_I8
     n_max = os.path.getsize(a.file) // (4 if fmt == "c16" else 2)
@@ -401,6 +481,8 @@ def main():
             n_buf, n_samp = 0, (int(frames["offset"].max()) + A.WINDOW if len(frames) else 0)
             if a.aircraft:
                 text = aircraft_table(d, frames, n_samp, st, parsed_levels if a.levels else None, site=a.site)
+            elif a.es:
+                text = es_lines(frames, d.es_of(frames)[0])
             else:
                 text = web_stream(d, frames, a.chunk) if a.web else stream_text(frames)
             write_wire(d, frames, a, fmt, parsed_levels)
@@ -420,6 +502,8 @@ def main():
             text = web_stream(d, frames, a.chunk)
         elif a.levels:
             text = level_lines(d, st, frames, read_capture(a.file, fmt))
+        elif a.es:
+            text = es_lines(frames, d.es_of(frames)[0])
         write_wire(d, frames, a, fmt)
     sys.stdout.write(text)
     if a.summary:
