@@ -449,6 +449,33 @@ AIRCRAFT_COMMB_DTYPE = np.dtype([("bds40", COMMB_BLOCK_DTYPE), ("bds50", COMMB_B
 assert C.sizeof(AdsbCommbSettleCfg) == 16 and COMMB_BLOCK_DTYPE.itemsize == C.sizeof(AdsbCommbBlock) == 32
 assert AIRCRAFT_COMMB_DTYPE.itemsize == C.sizeof(AdsbAircraftCommb) == 128
 
+(ADSB_TRACK_ES_COUNTED, ADSB_TRACK_ES_POSITION, ADSB_TRACK_ES_VERSIONED, ADSB_TRACK_ES_STALE_A,
+ ADSB_TRACK_ES_STALE_C) = 0x1, 0x2, 0x4, 0x8, 0x10                  # adsb_frame_integrity.flags
+
+
+class AdsbEsTrackCfg(C.Structure):
+    """adsb_es_track_cfg: how long a table uses a NIC supplement (16 bytes)."""
+    _fields_ = [("max_age_s", C.c_double), ("reserved", C.c_uint32 * 2)]
+
+
+class AdsbFrameIntegrity(C.Structure):
+    """adsb_frame_integrity: NIC and Rc of one frame, resolved by a table with an es reserve (8 bytes)."""
+    _fields_ = [("rc_dm", C.c_uint32), ("nic", C.c_uint8), ("version", C.c_uint8), ("supp", C.c_uint8), ("flags", C.c_uint8)]
+
+
+class AdsbAircraftEs(C.Structure):
+    """adsb_aircraft_es: what an aircraft's extended squitters say, beside its record (tables with an es reserve)."""
+    _fields_ = ([(k, AdsbEsRec) for k in ("operational_airborne", "operational_surface", "target_state", "emergency", "acas_ra")]
+                + [("time", C.c_double * 5)]
+                + [(k, C.c_double) for k in ("version_time", "nic_a_time", "nic_c_time", "position_time")]
+                + [("rc_dm", C.c_uint32)]
+                + [(k, C.c_uint8) for k in ("nic", "position_tc", "nic_b", "position_supp", "version", "nic_a", "nic_c", "category")]
+                + [("n_es", C.c_uint32), ("n_position", C.c_uint32)]
+                + [(k, C.c_uint8) for k in ("nac_v", "velocity_flags", "has", "reserved")])
+
+
+assert C.sizeof(AdsbEsTrackCfg) == 16 and C.sizeof(AdsbFrameIntegrity) == 8 and C.sizeof(AdsbAircraftEs) == 256
+
 
 class AdsbTrackBankCfg(C.Structure):
     _fields_ = [("abi_version", C.c_uint32), ("n_receivers", C.c_uint32), ("max_aircraft", C.c_uint32),
@@ -601,6 +628,12 @@ PROTOTYPES = {
     "adsb_track_table_fetch_commb": (C.c_int, [C.c_void_p, _P(AdsbAircraftCommb), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_table_fetch_frame_commb": (C.c_int, [C.c_void_p, _P(AdsbCommbRec), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_table_commb_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "adsb_track_table_es_reserve": (C.c_int, [C.c_void_p, _P(AdsbEsTrackCfg)]),
+    "adsb_track_table_update_es": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_uint64]),
+    "adsb_track_table_fetch_es": (C.c_int, [C.c_void_p, _P(AdsbAircraftEs), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_fetch_frame_es": (C.c_int, [C.c_void_p, _P(AdsbFrameIntegrity), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_es_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "adsb_track_bank_fixes_reserve": (C.c_int, [C.c_void_p, _P(AdsbSite)]),
     "adsb_track_bank_fetch_fixes": (C.c_int, [C.c_void_p, _P(AdsbFix), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_bank_fixes_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
@@ -711,6 +744,9 @@ PROTOTYPES = {
     "adsb_host_commb_reference": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
     "adsb_host_track_commb_of": (C.c_int, [C.c_void_p, C.c_double, _P(AdsbAircraftCommb)]),
     "adsb_host_track_commb_merge": (C.c_int, [_P(AdsbAircraftCommb), _P(AdsbAircraftCommb)]),
+    "adsb_host_es_resolve": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p, _P(AdsbEsTrackCfg), C.c_void_p]),
+    "adsb_host_track_es_of": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    "adsb_host_track_es_merge": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -422,6 +422,7 @@ struct TrackStoreDev {
     uint32_t *seg_slot;          // [n] per segment (hi of the scan): record slot + 1 (kTrackUntracked)
     // table only, last so that no other member moves
     adsb_aircraft_commb *commb;  // [max_aircraft] beside rec, or null: no commb reserve (likewise; tables only)
+    adsb_aircraft_es *es;        // [max_aircraft] beside rec, or null: no es reserve (likewise; tables only)
 };
 // Per-frame summaries and the changed list of a table / bank update (adsb_track_*_summaries_reserve): all of it
 // allocated by the reserve.  One segmented inclusive max-scan over the sorted list gives every frame the sorted
@@ -528,6 +529,31 @@ struct TrackCommbDev {
     size_t temp_bytes;
     adsb_commb_settle_cfg cfg;   // the reserve's
 };
+// Extended squitter status per aircraft (adsb_track_table_es_reserve; adsb_track_es.h has the rule, the per-frame text
+// and the combine): all of it allocated by the reserve.  A segmented scan of TrackEsRefTuple gives every sorted frame
+// its aircraft's newest frames with a version, a supplement A and a supplement C up to it (the frame kernel reads its
+// predecessor's: the exclusive scan); one thread per sorted frame resolves, writes the per-frame output at the list
+// index and the second scan's operand at the sorted position; one segmented inclusive scan; one thread per segment
+// tail merges into store->es.  Integers and one f64 subtraction for an age.
+struct TrackEsRefTuple {
+    uint32_t head;               // the operand holds a segment head
+    uint32_t version, a, c;      // sorted position + 1 of the newest frame with HAS_VERSION / HAS_NIC_A / HAS_NIC_C, 0 = none
+};
+struct TrackEsTuple {
+    uint32_t head;
+    uint32_t newest[11];         // sorted position + 1 of the newest counted frame that writes group g (adsb_track_es.h)
+    uint32_t n_es, n_position;
+};
+static_assert(sizeof(TrackEsTuple) == 56 && sizeof(TrackEsRefTuple) == 16, "the header's memory figures");
+struct TrackEsDev {
+    TrackEsRefTuple *ref;        // [max_frames]: the first scan's output, sorted order
+    adsb_frame_integrity *out;   // [max_frames]: the per-frame output of the last update_es, list order
+    TrackEsTuple *in;            // [max_frames]: the second scan's operands, sorted order
+    TrackEsTuple *scan;          // [max_frames]: its output, sorted order
+    void *temp;                  // both scans' scratch
+    size_t temp_bytes;
+    double max_age_s;            // the reserve's
+};
 struct TrackModesDev {
     TrackModesTuple *in;         // [max_frames]: the scan's operands, sorted order
     TrackModesTuple *scan;       // [max_frames]: the scan's output, sorted order
@@ -559,6 +585,8 @@ struct TrackArgs {
     const TrackMlatDev *mlat;    // per-aircraft mlat records; null: the mlat records stay as they are
     const adsb_commb_rec *commb_recs; // [n] (device), list order: with commb non-null (and modes, store->commb): the
     const TrackCommbDev *commb;       // commb step after the modes merge (update_commb); null: the commb records stay
+    const adsb_es_rec *es_recs;       // [n] (device), list order: with es non-null (and store->es): the es step beside
+    const TrackEsDev *es;             // the levels / fix merges (update_es); null: the es records stay as they are
     const adsb_modes_rec *modes_recs; // [n] (device), list order: with modes non-null (and store->modes; tables only)
     const TrackModesDev *modes;  // the list is keyed by the records' addresses (update_modes); null: by bytes[1..3]
     adsb_packet_fields *modes_fields; // = fields, writable: update_modes makes every other DF a frame of kind "other"
@@ -597,6 +625,9 @@ hipError_t launch_track_modes_clear(hipStream_t s, adsb_aircraft_modes *modes, s
 size_t track_commb_temp_bytes(size_t n); // the two commb scans
 // every commb record of [0, places) empty: zeros, every time NaN (the commb reserve, and reset)
 hipError_t launch_track_commb_clear(hipStream_t s, adsb_aircraft_commb *commb, size_t places);
+size_t track_es_temp_bytes(size_t n); // the two es scans
+// every es record of [0, places) empty: zeros, every time NaN (the es reserve, and reset)
+hipError_t launch_track_es_clear(hipStream_t s, adsb_aircraft_es *es, size_t places);
 // out[k] = rec[sum.changed[k]] for k < min(*sum.n_changed, max_n): the changed list's records, gathered on the device
 hipError_t launch_track_changed(hipStream_t s, const TrackRecord *rec, const TrackSumDev &sum, uint32_t max_n,
                                 TrackRecord *out);

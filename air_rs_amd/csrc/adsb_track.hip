@@ -116,6 +116,14 @@
 // ambiguous {5,0; 6,0} record against the newest EARLIER one (its predecessor's scan word) or the held velocity
 // (adsb_track_commb.h), writes the per-frame output at the list index and a 40-byte operand at the sorted position, one
 // segmented inclusive scan, one thread per segment tail merges into the side record.  Tables only.
+//
+// Extended squitter status per aircraft (adsb_track_table_es_reserve; the update_es form): a sixth side array, one
+// 256-byte adsb_aircraft_es per record place.  Beside the levels / fix / mlat merges, since it needs the sort, d.slot
+// and its own side array only, and behind either key kernel (a plain key is below kModesNoAddress): one segmented scan
+// gives every sorted frame its aircraft's newest frames with a version and with NIC supplements A and C up to it, one
+// thread per frame resolves a position message against the newest EARLIER ones (its predecessor's scan words) or the
+// held record (adsb_track_es.h), writes the per-frame output at the list index and a 56-byte operand at the sorted
+// position, one segmented inclusive scan, one thread per segment tail merges into the side record.  Tables only.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -126,6 +134,7 @@
 #include "adsb_kernels.h"
 #include "adsb_track_mlat.h"
 #include "adsb_track_commb.h"
+#include "adsb_track_es.h"
 #include "adsb_track_modes.h"
 
 namespace adsbk {
@@ -319,6 +328,7 @@ __global__ __launch_bounds__(256) void track_admit_kernel(const uint32_t *skeys,
     if (t.mlat) ((MlatWords *)t.mlat)[r] = mlat_empty();
     if (t.modes) ((ModesWords *)t.modes)[r] = modes_empty();
     if (t.commb) ((CommbWords *)t.commb)[r] = commb_empty();
+    if (t.es) ((EsWords *)t.es)[r] = es_track_empty();
 }
 
 // bank only: the receiver split clipped to the list (prefix[0] = 0, prefix[k] = n for k >= n_src), as adsb_fetch's
@@ -1368,6 +1378,191 @@ __global__ __launch_bounds__(256) void track_commb_clear_kernel(CommbWords *comm
     if (p < places) commb[p] = commb_empty();
 }
 
+// ---- Extended squitter status per aircraft (table with an es reserve) -------------------------------------------------
+// The first scan's input at sorted position s, computed where the scan loads it: s + 1 in each word whose present bit
+// the frame's es record has.  A frame that has one of them is an extended squitter (never NOT_ES or FOREIGN), and key
+// and slot are its whole segment's, so within a counted segment these are exactly the counted frames.
+struct EsRefInput {
+    const uint32_t *skeys, *svals;
+    const adsb_es_rec *es;
+    __device__ __forceinline__ TrackEsRefTuple operator()(uint32_t s) const
+    {
+        TrackEsRefTuple v;
+        const uint32_t present = es_track_counted(es[svals[s]]) ? es[svals[s]].present : 0u;
+        v.head = (s == 0 || skeys[s - 1] != skeys[s]) ? 1u : 0u;
+        v.version = (present & ADSB_ES_HAS_VERSION) ? s + 1u : 0u;
+        v.a = (present & ADSB_ES_HAS_NIC_A) ? s + 1u : 0u;
+        v.c = (present & ADSB_ES_HAS_NIC_C) ? s + 1u : 0u;
+        return v;
+    }
+};
+
+struct EsRefOp {
+    __device__ __forceinline__ TrackEsRefTuple operator()(const TrackEsRefTuple &l, const TrackEsRefTuple &r) const
+    {
+        TrackEsRefTuple o = r;
+        if (!r.head) {
+            o.head = l.head;
+            o.version = l.version > r.version ? l.version : r.version;
+            o.a = l.a > r.a ? l.a : r.a;
+            o.c = l.c > r.c ? l.c : r.c;
+        }
+        return o;
+    }
+};
+
+// One thread per sorted frame s (svals[s] < n, a permutation of the list; d.slot[s] - 1 < max_aircraft unless
+// kTrackUntracked; ref[s - 1]'s words - 1 < s are sorted positions of the same segment).  d.es[slot - 1] is the record
+// from before this update: the merge kernel below is the only writer and runs after the second scan.
+__global__ __launch_bounds__(256) void track_es_frame_kernel(const adsb_frame *frames, const adsb_es_rec *es,
+                                                             const uint32_t *skeys, const uint32_t *svals, uint32_t n,
+                                                             double seconds_per_sample, uint64_t sample_base,
+                                                             TrackStoreDev d, const TrackEsRefTuple *ref, double max_age_s,
+                                                             adsb_frame_integrity *out, TrackEsTuple *in)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s], i = svals[s];
+    const adsb_es_rec r = es[i];
+    TrackEsTuple v{};
+    adsb_frame_integrity o{};
+    v.head = (s == 0 || skeys[s - 1] != key) ? 1u : 0u;
+    const uint32_t slot = d.slot[s];
+    if (key < kModesNoAddress && slot != kTrackUntracked && es_track_counted(r)) {
+        TrackEsRefTuple p{};
+        if (!v.head) p = ref[s - 1];
+        const adsb_aircraft_es *held = d.es + (slot - 1);
+        EsKnown k;
+        if (p.version) {
+            const uint32_t j = svals[p.version - 1];
+            k.version = es[j].version;
+            k.version_time = frame_time(frames, j, sample_base, seconds_per_sample);
+        } else {
+            k.version = held->version;
+            k.version_time = held->version_time;
+        }
+        if (p.a) {
+            const uint32_t j = svals[p.a - 1];
+            k.a = es[j].nic_a;
+            k.a_time = frame_time(frames, j, sample_base, seconds_per_sample);
+        } else {
+            k.a = held->nic_a;
+            k.a_time = held->nic_a_time;
+        }
+        if (p.c) {
+            const uint32_t j = svals[p.c - 1];
+            k.c = es[j].nic_c;
+            k.c_time = frame_time(frames, j, sample_base, seconds_per_sample);
+        } else {
+            k.c = held->nic_c;
+            k.c_time = held->nic_c_time;
+        }
+        o = es_track_resolve(r, frame_time(frames, i, sample_base, seconds_per_sample), k, max_age_s);
+        const uint32_t m = es_track_writes(r), at = s + 1u;
+#pragma unroll
+        for (uint32_t g = 0; g < kEsTrackGroups; ++g) v.newest[g] = ((m >> g) & 1u) ? at : 0u;
+        v.n_es = 1u;
+        v.n_position = (m >> kEsTrackPosition) & 1u;
+    }
+    out[i] = o;
+    in[s] = v;
+}
+
+struct EsOp {
+    __device__ __forceinline__ TrackEsTuple operator()(const TrackEsTuple &l, const TrackEsTuple &r) const
+    {
+        TrackEsTuple o = r;
+        if (!r.head) {
+            o.head = l.head;
+#pragma unroll
+            for (uint32_t g = 0; g < kEsTrackGroups; ++g) o.newest[g] = l.newest[g] > r.newest[g] ? l.newest[g] : r.newest[g];
+            o.n_es = sat_add32(l.n_es, r.n_es);
+            o.n_position = sat_add32(l.n_position, r.n_position);
+        }
+        return o;
+    }
+};
+
+// group G of the part from the segment's winner at sorted position p - 1 (p = 0: the segment has none)
+template <uint32_t G>
+__device__ __forceinline__ void es_part_take(adsb_aircraft_es &part, uint32_t p, const adsb_frame *frames,
+                                             const adsb_es_rec *es, const adsb_frame_integrity *out,
+                                             const uint32_t *svals, double seconds_per_sample, uint64_t sample_base)
+{
+    if (!p) return;
+    const uint32_t j = svals[p - 1];
+    adsb_frame_integrity f{};
+    if (G == kEsTrackPosition) f = out[j];
+    es_track_set(part, G, es[j], f, frame_time(frames, j, sample_base, seconds_per_sample));
+}
+
+// One thread per segment tail with a counted frame: the segment's part (adsb_track_es.h) from the winning frames' es
+// records, per-frame outputs and times, merged into the aircraft's es record.  Every position is <= n: a sorted
+// position + 1.
+__global__ __launch_bounds__(256) void track_es_merge_kernel(const adsb_frame *frames, const adsb_es_rec *es,
+                                                             const adsb_frame_integrity *out, const uint32_t *skeys,
+                                                             const uint32_t *svals, uint32_t n, double seconds_per_sample,
+                                                             uint64_t sample_base, TrackStoreDev d, const TrackEsTuple *scan)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s];
+    if (s + 1 != n && skeys[s + 1] == key) return;
+    const uint32_t slot = d.slot[s];
+    if (key >= kModesNoAddress || slot == kTrackUntracked) return;
+    const TrackEsTuple w = scan[s];
+    if (!w.n_es) return; // nothing counted: the record stays
+    adsb_aircraft_es part = es_track_empty_record();
+    part.n_es = w.n_es;
+    part.n_position = w.n_position;
+    es_part_take<kEsTrackOpAir>(part, w.newest[0], frames, es, out, svals, seconds_per_sample, sample_base);
+    es_part_take<kEsTrackOpSurface>(part, w.newest[1], frames, es, out, svals, seconds_per_sample, sample_base);
+    es_part_take<kEsTrackTargetState>(part, w.newest[2], frames, es, out, svals, seconds_per_sample, sample_base);
+    es_part_take<kEsTrackEmergency>(part, w.newest[3], frames, es, out, svals, seconds_per_sample, sample_base);
+    es_part_take<kEsTrackAcasRa>(part, w.newest[4], frames, es, out, svals, seconds_per_sample, sample_base);
+    es_part_take<kEsTrackVersion>(part, w.newest[5], frames, es, out, svals, seconds_per_sample, sample_base);
+    es_part_take<kEsTrackNicA>(part, w.newest[6], frames, es, out, svals, seconds_per_sample, sample_base);
+    es_part_take<kEsTrackNicC>(part, w.newest[7], frames, es, out, svals, seconds_per_sample, sample_base);
+    es_part_take<kEsTrackPosition>(part, w.newest[8], frames, es, out, svals, seconds_per_sample, sample_base);
+    es_part_take<kEsTrackCategory>(part, w.newest[9], frames, es, out, svals, seconds_per_sample, sample_base);
+    es_part_take<kEsTrackNacV>(part, w.newest[10], frames, es, out, svals, seconds_per_sample, sample_base);
+    EsWords words = ((const EsWords *)d.es)[slot - 1];
+    adsb_aircraft_es a;
+    __builtin_memcpy(&a, &words, sizeof(a));
+    es_track_merge(a, part);
+    __builtin_memcpy(&words, &a, sizeof(a));
+    ((EsWords *)d.es)[slot - 1] = words;
+}
+
+hipError_t launch_es_merge(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d)
+{
+    const TrackEsDev &x = *a.es;
+    const dim3 grid((a.n + 255) / 256);
+    const auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u),
+                                                     EsRefInput{(const uint32_t *)a.skeys, (const uint32_t *)a.svals, a.es_recs});
+    size_t tb = x.temp_bytes;
+    hipError_t e = rocprim::inclusive_scan(x.temp, tb, in, x.ref, (size_t)a.n, EsRefOp(), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(track_es_frame_kernel, grid, dim3(256), 0, st, a.frames, a.es_recs, (const uint32_t *)a.skeys,
+                       (const uint32_t *)a.svals, a.n, a.seconds_per_sample, a.sample_base, d,
+                       (const TrackEsRefTuple *)x.ref, x.max_age_s, x.out, x.in);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    tb = x.temp_bytes;
+    e = rocprim::inclusive_scan(x.temp, tb, (const TrackEsTuple *)x.in, x.scan, (size_t)a.n, EsOp(), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(track_es_merge_kernel, grid, dim3(256), 0, st, a.frames, a.es_recs,
+                       (const adsb_frame_integrity *)x.out, (const uint32_t *)a.skeys, (const uint32_t *)a.svals, a.n,
+                       a.seconds_per_sample, a.sample_base, d, (const TrackEsTuple *)x.scan);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void track_es_clear_kernel(EsWords *es, uint64_t places)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < places) es[p] = es_track_empty();
+}
+
 // expire, 1: keep[g] = 1 for a record in use whose last frame is not older than the cut (last_heard < before evicts).
 // Record g is slot i of receiver r (a table: r = 0).  Slot 0 stages the old size where the compaction kernel reads it
 // (size_next[r]), since that kernel writes the new one; the pairs kernel of an update has consumed its own staging before
@@ -1424,6 +1619,7 @@ __global__ __launch_bounds__(256) void track_expire_compact_kernel(TrackStoreDev
     if (d.mlat) ((MlatWords *)d.mlat)[g] = ((const MlatWords *)d.mlat)[base + lo];
     if (d.modes) ((ModesWords *)d.modes)[g] = ((const ModesWords *)d.modes)[base + lo];
     if (d.commb) ((CommbWords *)d.commb)[g] = ((const CommbWords *)d.commb)[base + lo];
+    if (d.es) ((EsWords *)d.es)[g] = ((const EsWords *)d.es)[base + lo];
     if (!kBank) d.index[moved.a.icao] = i + 1u;
 }
 
@@ -1839,6 +2035,25 @@ hipError_t launch_track_commb_clear(hipStream_t st, adsb_aircraft_commb *commb, 
     return hipGetLastError();
 }
 
+size_t track_es_temp_bytes(size_t n)
+{
+    size_t ref_bytes = 0, scan_bytes = 0;
+    const auto in = rocprim::make_transform_iterator(rocprim::counting_iterator<uint32_t>(0u),
+                                                     EsRefInput{nullptr, nullptr, nullptr});
+    (void)rocprim::inclusive_scan(nullptr, ref_bytes, in, (TrackEsRefTuple *)nullptr, n, EsRefOp(), (hipStream_t)0);
+    (void)rocprim::inclusive_scan(nullptr, scan_bytes, (const TrackEsTuple *)nullptr, (TrackEsTuple *)nullptr, n, EsOp(),
+                                  (hipStream_t)0);
+    return (ref_bytes > scan_bytes ? ref_bytes : scan_bytes) + 256;
+}
+
+hipError_t launch_track_es_clear(hipStream_t st, adsb_aircraft_es *es, size_t places)
+{
+    if (places == 0) return hipSuccess;
+    hipLaunchKernelGGL(track_es_clear_kernel, dim3((uint32_t)((places + 255) / 256)), dim3(256), 0, st, (EsWords *)es,
+                       (uint64_t)places);
+    return hipGetLastError();
+}
+
 hipError_t launch_track_modes_clear(hipStream_t st, adsb_aircraft_modes *modes, size_t places)
 {
     if (places == 0) return hipSuccess;
@@ -1900,6 +2115,10 @@ hipError_t track_tail(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d
         if (e != hipSuccess) return e;
         if (a.mlat && d.mlat) e = launch_mlat_merge<K>(st, a, d); // needs d.slot, the frame bytes and the fixes only
         if (e != hipSuccess) return e;
+        if constexpr (K == TrackKind::kTable) {
+            if (a.es && d.es) e = launch_es_merge(st, a, d); // needs d.slot, the es records and its own side array only
+            if (e != hipSuccess) return e;
+        }
         if (a.sum) e = launch_frame_summaries<K>(st, a, d); // before the merge
         if constexpr (K == TrackKind::kTable) {
             if (e != hipSuccess) return e;

@@ -113,7 +113,7 @@ struct TrackStore {
     uint32_t n_receivers = 0, max_aircraft = 0; // max_aircraft: per receiver
     // One block of device memory per lifetime, carved into the arrays below (adsb_scratch.h): the store's own from
     // create to destroy, and one per reserve.  Every device pointer of the store points into one of them.
-    DevBuf<char> mem, sum_mem, lvl_mem, fix_mem, mlat_mem, modes_mem, commb_mem;
+    DevBuf<char> mem, sum_mem, lvl_mem, fix_mem, mlat_mem, modes_mem, commb_mem, es_mem;
     adsbk::TrackStoreDev dev{};     // records [R x max_aircraft], slot [max_frames]; index [2^24] or hash, prefix, scan words
     uint32_t *words = nullptr;      // [3R]: size, flags, size_next (dev.size / dev.flags / dev.size_next)
     uint32_t *u32 = nullptr;        // 4 x [max_frames]: keys, vals, sorted keys, sorted vals
@@ -155,6 +155,12 @@ struct TrackStore {
     adsb_commb_rec *commb_pinned = nullptr; // [max_frames]: pinned staging of that copy (s.copied covers it too)
     uint32_t commb_n = 0;                   // frames of the last update_commb
     bool commb_updated = false;             // an update_commb ran since the reserve (and since the last reset)
+    // Extended squitter status per aircraft (adsb_track_table_es_reserve): all of it made by the reserve; dev.es null = none
+    adsbk::TrackEsDev es{};
+    adsb_es_rec *es_recs = nullptr;         // [max_frames]: device copy of a host es array
+    adsb_es_rec *es_pinned = nullptr;       // [max_frames]: pinned staging of that copy (s.copied covers it too)
+    uint32_t es_n = 0;                      // frames of the last update_es
+    bool es_updated = false;                // an update_es ran since the reserve (and since the last reset)
 
     size_t places() const { return (size_t)n_receivers * max_aircraft; }
 };
@@ -243,6 +249,16 @@ static void store_commb_drop(TrackStore &s)
     s.commb_recs = nullptr;
 }
 
+// The es reserve undone, under the same condition.
+static void store_es_drop(TrackStore &s)
+{
+    drop(s.es_mem);
+    pinned_free(s.es_pinned);
+    s.dev.es = nullptr;
+    s.es = {};
+    s.es_recs = nullptr;
+}
+
 // Sizes, and the store's own block: what a table and a bank share, then what each kind adds (a bank has set
 // dev.hash_mask).  false: an allocation failed (the caller releases what was made)
 static bool store_alloc(TrackStore &s, adsb_ctx *c, TrackKind kind, uint32_t n_receivers, uint32_t max_aircraft, uint64_t max_frames,
@@ -300,6 +316,7 @@ static void store_release(TrackStore &s)
     drop(s.mlat_mem);
     store_modes_drop(s);
     store_commb_drop(s);
+    store_es_drop(s);
     pinned_free(s.pinned);
     pinned_free(s.lvl_pinned);
     pinned_free(s.mlat_pinned);
@@ -321,7 +338,9 @@ static int store_reset(TrackStore *s)
     if (s->dev.modes) HIPCHK(adsbk::launch_track_modes_clear(s->ctx->aux, s->dev.modes, s->places()));
     if (s->dev.commb) HIPCHK(adsbk::launch_track_commb_clear(s->ctx->aux, s->dev.commb, s->places()));
     s->mlat_updated = false;
+    if (s->dev.es) HIPCHK(adsbk::launch_track_es_clear(s->ctx->aux, s->dev.es, s->places()));
     s->commb_updated = false;
+    s->es_updated = false;
     s->n_points = 0;
     s->updated = false;
     s->sum.updated = s->sum.changed_valid = false;
@@ -384,6 +403,14 @@ static int store_stage_commb(TrackStore &s, const adsb_commb_rec *host, size_t n
     return ADSB_OK;
 }
 
+// The same for a host es array (update_es), under the same event
+static int store_stage_es(TrackStore &s, const adsb_es_rec *host, size_t n)
+{
+    std::memcpy(s.es_pinned, host, sizeof(adsb_es_rec) * n);
+    HIPCHK(hipMemcpyAsync(s.es_recs, s.es_pinned, sizeof(adsb_es_rec) * n, hipMemcpyHostToDevice, s.ctx->aux));
+    return ADSB_OK;
+}
+
 // The bookkeeping every update starts with (an empty one too: no summaries, an empty changed list); false: n == 0,
 // nothing to launch
 static bool store_begin_update(TrackStore &s, size_t n)
@@ -398,11 +425,12 @@ static bool store_begin_update(TrackStore &s, size_t n)
 // field decode (same stream); dev: s.dev, or a bank's copy of it with this update's receiver split; levels (device,
 // or null): also the level merge; mlat_fixes (device, or null): also the mlat merge; recs (device, or null): the list is
 // keyed by the records' addresses and the modes merge runs too (update_modes), with the modes reserve's scratch, which
-// holds the 25-bit sort; commb (device, or null; only with recs): the commb step runs too (update_commb)
+// holds the 25-bit sort; commb (device, or null; only with recs): the commb step runs too (update_commb); es (device,
+// or null): the es step runs too (update_es)
 static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t sample_base,
                      const adsbk::TrackStoreDev &dev, const adsb_frame_level *levels = nullptr,
                      const adsb_mlat_fix *mlat_fixes = nullptr, const adsb_modes_rec *recs = nullptr,
-                     const adsb_commb_rec *commb = nullptr)
+                     const adsb_commb_rec *commb = nullptr, const adsb_es_rec *es = nullptr)
 {
     HIPCHK(adsbk::launch_decode_fields(s.ctx->aux, list, nullptr, (uint32_t)n, s.fields));
     adsbk::TrackArgs a = track_args(s.kind, list, s.fields, n, s.seconds_per_sample, s.u32, (size_t)s.max_frames,
@@ -426,6 +454,10 @@ static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t s
             a.commb = &s.commb;
         }
     }
+    if (es) {
+        a.es_recs = es;
+        a.es = &s.es;
+    }
     HIPCHK(adsbk::launch_track(s.ctx->aux, a));
     return ADSB_OK;
 }
@@ -440,6 +472,7 @@ static const adsb_fix *fixes_of(TrackStore &s) { return s.dev.fix; }
 static const adsb_aircraft_mlat *mlat_of(TrackStore &s) { return s.dev.mlat; }
 static const adsb_aircraft_modes *modes_of(TrackStore &s) { return s.dev.modes; }
 static const adsb_aircraft_commb *commb_of(TrackStore &s) { return s.dev.commb; }
+static const adsb_aircraft_es *es_of(TrackStore &s) { return s.dev.es; }
 
 template <class T>
 static int store_device(TrackStore *s, const T *of(TrackStore &), const T **dev)
@@ -773,6 +806,34 @@ static int store_commb_reserve(TrackStore *st, const adsb_commb_settle_cfg &cfg)
     return ADSB_OK;
 }
 
+// ---- Extended squitter status per aircraft ---------------------------------------------------------------------------
+// Waits for the device (the clear); a second reserve keeps what the first one made, its cfg too
+static int store_es_reserve(TrackStore *st, double max_age_s)
+{
+    HIPCHK(hipSetDevice(st->ctx->cfg.device));
+    if (st->dev.es) return ADSB_OK;
+    const size_t nf = (size_t)st->max_frames;
+    st->es.temp_bytes = adsbk::track_es_temp_bytes(nf);
+    st->es.max_age_s = max_age_s;
+    const int rc = carve_block(st->ctx, st->es_mem, [&](Carve &k) {
+        st->dev.es = k.take<adsb_aircraft_es>(st->places());
+        st->es.ref = k.take<adsbk::TrackEsRefTuple>(nf);
+        st->es.out = k.take<adsb_frame_integrity>(nf);
+        st->es.in = k.take<adsbk::TrackEsTuple>(nf);
+        st->es.scan = k.take<adsbk::TrackEsTuple>(nf);
+        st->es.temp = k.take<char>(st->es.temp_bytes);
+        st->es_recs = k.take<adsb_es_rec>(nf);
+    });
+    if (rc != ADSB_OK || !pinned_make(st->es_pinned, nf) ||
+        adsbk::launch_track_es_clear(st->ctx->aux, st->dev.es, st->places()) != hipSuccess ||
+        hipStreamSynchronize(st->ctx->aux) != hipSuccess) {
+        (void)hipGetLastError();
+        store_es_drop(*st);
+        return ADSB_E_NOMEM;
+    }
+    return ADSB_OK;
+}
+
 // ---- persistent aircraft table (adsb_track_table_*) ------------------------------------------------------------------
 static void track_table_free(adsb_track_table *t)
 {
@@ -803,10 +864,11 @@ extern "C" void adsb_track_table_destroy(adsb_track_table *t)
 }
 
 // levels: null for the plain update; fixes: null unless update_mlat (or update_modes with fixes); recs: null unless
-// update_modes; commb: null unless update_commb
+// update_modes; commb: null unless update_commb; es: null unless update_es
 static int track_table_update(adsb_track_table *t, const adsb_frame *frames, const adsb_frame_level *levels, size_t n,
                               uint64_t sample_base, const adsb_mlat_fix *fixes = nullptr,
-                              const adsb_modes_rec *recs = nullptr, const adsb_commb_rec *commb = nullptr)
+                              const adsb_modes_rec *recs = nullptr, const adsb_commb_rec *commb = nullptr,
+                              const adsb_es_rec *es = nullptr)
 {
     if (n > t->max_frames) return ADSB_E_CAPACITY;
     adsb_ctx *c = t->ctx;
@@ -819,18 +881,23 @@ static int track_table_update(adsb_track_table *t, const adsb_frame *frames, con
     const adsb_frame *list = frames;
     const bool frames_host = !in_device_memory(c, frames), levels_host = levels && !in_device_memory(c, levels);
     const bool fixes_host = fixes && !in_device_memory(c, fixes), recs_host = recs && !in_device_memory(c, recs);
-    const bool commb_host = commb && !in_device_memory(c, commb);
+    const bool commb_host = commb && !in_device_memory(c, commb), es_host = es && !in_device_memory(c, es);
+    if (es) { // the list fetch_frame_es speaks of
+        t->es_n = (uint32_t)n;
+        t->es_updated = true;
+    }
     if (commb) { // the list fetch_frame_commb speaks of
         t->commb_n = (uint32_t)n;
         t->commb_updated = true;
     }
-    if (frames_host || levels_host || fixes_host || recs_host || commb_host) {
+    if (frames_host || levels_host || fixes_host || recs_host || commb_host || es_host) {
         HIPCHK(hipEventSynchronize(t->copied)); // the previous update's copies out of the staging have finished
         int rc = frames_host ? store_stage_frames(*t, frames, n) : ADSB_OK;
         if (rc == ADSB_OK && levels_host) rc = store_stage_levels(*t, levels, n);
         if (rc == ADSB_OK && fixes_host) rc = store_stage_mlat(*t, fixes, n);
         if (rc == ADSB_OK && recs_host) rc = store_stage_modes(*t, recs, n);
         if (rc == ADSB_OK && commb_host) rc = store_stage_commb(*t, commb, n);
+        if (rc == ADSB_OK && es_host) rc = store_stage_es(*t, es, n);
         if (rc != ADSB_OK) return rc;
         HIPCHK(hipEventRecord(t->copied, c->aux));
         if (frames_host) list = t->frames;
@@ -838,8 +905,9 @@ static int track_table_update(adsb_track_table *t, const adsb_frame *frames, con
         if (fixes_host) fixes = t->mlat_fixes;
         if (recs_host) recs = t->modes_recs;
         if (commb_host) commb = t->commb_recs;
+        if (es_host) es = t->es_recs;
     }
-    return store_run(*t, list, n, sample_base, t->dev, levels, fixes, recs, commb);
+    return store_run(*t, list, n, sample_base, t->dev, levels, fixes, recs, commb, es);
 }
 
 extern "C" int adsb_track_table_update(adsb_track_table *t, const adsb_frame *frames, size_t n, uint64_t sample_base)
@@ -992,6 +1060,64 @@ extern "C" int adsb_track_table_fetch_frame_commb(adsb_track_table *t, adsb_comm
     HIPCHK(hipSetDevice(t->ctx->cfg.device));
     const size_t take = std::min<size_t>(t->commb_n, max);
     if (take) HIPCHK(hipMemcpyAsync(out, t->commb.out, sizeof(adsb_commb_rec) * take, hipMemcpyDeviceToHost, t->ctx->aux));
+    HIPCHK(hipStreamSynchronize(t->ctx->aux));
+    if (n) *n = take;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_table_es_reserve(adsb_track_table *t, const adsb_es_track_cfg *cfg)
+{
+    const double max_age_s = cfg ? cfg->max_age_s : 60.0;
+    if (!t || !(max_age_s >= 0.0)) return ADSB_E_ARG; // before the handle is read
+    return store_es_reserve(t, max_age_s);
+}
+
+// recs NULL: the plain update (with levels: update_levels, with fixes: update_mlat); recs: update_modes; recs and commb:
+// update_commb; each with the es step
+extern "C" int adsb_track_table_update_es(adsb_track_table *t, const adsb_frame *frames, const adsb_es_rec *es,
+                                          const adsb_modes_rec *recs, const adsb_commb_rec *commb,
+                                          const adsb_mlat_fix *fixes, const adsb_frame_level *levels, size_t n,
+                                          uint64_t sample_base)
+{
+    if (!t || (!frames && n) || (!es && n) || (commb && !recs)) return ADSB_E_ARG;
+    if (!t->dev.es || (recs && !t->dev.modes) || (commb && !t->dev.commb) || (fixes && !t->dev.mlat) ||
+        (levels && !t->dev.lvl))
+        return ADSB_E_STATE;
+    if (n > t->max_frames) return ADSB_E_CAPACITY;
+    if (n == 0) { // nothing to launch: the last update's lists are empty
+        t->es_n = 0;
+        t->es_updated = true;
+        if (commb) {
+            t->commb_n = 0;
+            t->commb_updated = true;
+        }
+        if (fixes) {
+            t->mlat_n = 0;
+            t->mlat_updated = true;
+        }
+    }
+    return track_table_update(t, frames, n ? levels : nullptr, n, sample_base, n ? fixes : nullptr, n ? recs : nullptr,
+                              n ? commb : nullptr, n ? es : nullptr);
+}
+
+extern "C" int adsb_track_table_fetch_es(adsb_track_table *t, adsb_aircraft_es *out, size_t max, size_t *n)
+{
+    return store_fetch_side(t, es_of, out, max, n);
+}
+
+extern "C" int adsb_track_table_es_device(adsb_track_table *t, const adsb_aircraft_es **dev)
+{
+    return store_device(t, es_of, dev);
+}
+
+// Waits.  As fetch_frame_commb, over the last update_es's list
+extern "C" int adsb_track_table_fetch_frame_es(adsb_track_table *t, adsb_frame_integrity *out, size_t max, size_t *n)
+{
+    if (!t || (!out && max)) return ADSB_E_ARG;
+    if (!t->dev.es || !t->es_updated) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(t->ctx->cfg.device));
+    const size_t take = std::min<size_t>(t->es_n, max);
+    if (take) HIPCHK(hipMemcpyAsync(out, t->es.out, sizeof(adsb_frame_integrity) * take, hipMemcpyDeviceToHost, t->ctx->aux));
     HIPCHK(hipStreamSynchronize(t->ctx->aux));
     if (n) *n = take;
     return ADSB_OK;

@@ -398,6 +398,134 @@ def es_physical(recs):
     return out
 
 
+FRAME_INTEGRITY_DTYPE = np.dtype([("rc_dm", "<u4"), ("nic", "u1"), ("version", "u1"), ("supp", "u1"), ("flags", "u1")])
+AIRCRAFT_ES_DTYPE = np.dtype([(k, ES_DTYPE) for k in ("operational_airborne", "operational_surface", "target_state",
+                                                      "emergency", "acas_ra")]
+                             + [("time", "<f8", (5,))]
+                             + [(k, "<f8") for k in ("version_time", "nic_a_time", "nic_c_time", "position_time")]
+                             + [("rc_dm", "<u4")]
+                             + [(k, "u1") for k in ("nic", "position_tc", "nic_b", "position_supp", "version", "nic_a",
+                                                    "nic_c", "category")]
+                             + [("n_es", "<u4"), ("n_position", "<u4")]
+                             + [(k, "u1") for k in ("nac_v", "velocity_flags", "has", "reserved")])
+assert FRAME_INTEGRITY_DTYPE.itemsize == C.sizeof(L.AdsbFrameIntegrity) == 8
+assert AIRCRAFT_ES_DTYPE.itemsize == C.sizeof(L.AdsbAircraftEs) == 256
+AIRCRAFT_ES_BLOCKS = ("operational_airborne", "operational_surface", "target_state", "emergency", "acas_ra")
+
+
+def host_es_resolve(rec, time=0.0, held=None, max_age_s=60.0):
+    """adsb_host_es_resolve, the CPU mirror of an es reserve's resolution: the FRAME_INTEGRITY_DTYPE record of a frame
+    with the ES_DTYPE record `rec` heard at `time`, of an aircraft whose AIRCRAFT_ES_DTYPE record before the frame is
+    `held` (None: the empty record).  Needs no device."""
+    r = np.array([rec], dtype=ES_DTYPE)
+    h = None if held is None else np.array([held], dtype=AIRCRAFT_ES_DTYPE)
+    cfg = L.AdsbEsTrackCfg(float(max_age_s))
+    out = np.zeros(1, dtype=FRAME_INTEGRITY_DTYPE)
+    L.check(L.load().adsb_host_es_resolve(r.ctypes.data, float(time), None if h is None else h.ctypes.data, C.byref(cfg),
+                                          out.ctypes.data), "adsb_host_es_resolve")
+    return out[0]
+
+
+def host_track_es_of(rec, integrity, time=0.0):
+    """adsb_host_track_es_of: the AIRCRAFT_ES_DTYPE record of an aircraft whose only counted frame has the ES_DTYPE
+    record `rec` and the per-frame output `integrity` (FRAME_INTEGRITY_DTYPE), heard at `time`.  Needs no device."""
+    r, f = np.array([rec], dtype=ES_DTYPE), np.array([integrity], dtype=FRAME_INTEGRITY_DTYPE)
+    out = np.zeros(1, dtype=AIRCRAFT_ES_DTYPE)
+    L.check(L.load().adsb_host_track_es_of(r.ctypes.data, f.ctypes.data, float(time), out.ctypes.data), "adsb_host_track_es_of")
+    return out[0]
+
+
+def host_track_es_merge(into, later):
+    """adsb_host_track_es_merge, the combine of an es reserve: the AIRCRAFT_ES_DTYPE record `into` followed by `later`
+    -> the merged record.  Needs no device."""
+    a, b = np.array([into], dtype=AIRCRAFT_ES_DTYPE), np.array([later], dtype=AIRCRAFT_ES_DTYPE)
+    L.check(L.load().adsb_host_track_es_merge(a.ctypes.data, b.ctypes.data), "adsb_host_track_es_merge")
+    return a[0]
+
+
+def host_track_es(frames, es, modes=None, seconds_per_sample=0.5e-6, sample_base=0, max_age_s=60.0, state=None,
+                  max_aircraft=None):
+    """What a table with an es reserve (and room for every aircraft) makes of ONE list, without a device, from the CPU
+    mirror's per-frame functions: FRAME_DTYPE frames with their ES_DTYPE records (and, on the keyed path, their
+    MODES_DTYPE records) -> (addresses ascending, their AIRCRAFT_ES_DTYPE records, the per-frame
+    FRAME_INTEGRITY_DTYPE output).  state: the dict address -> record a previous call returned through it, carried on
+    and updated in place (several updates of one table).  max_aircraft: the table's capacity; as in the table, a call
+    admits its new addresses in ascending order while there is room, and the frames of an aircraft it turns away count
+    nothing and get an all-zero output."""
+    frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+    es = np.ascontiguousarray(es, dtype=ES_DTYPE)
+    out = np.zeros(len(frames), dtype=FRAME_INTEGRITY_DTYPE)
+    state = {} if state is None else state
+    none = np.zeros(1, dtype=ES_DTYPE)[0]
+    empty = host_track_es_of(none, np.zeros(1, dtype=FRAME_INTEGRITY_DTYPE)[0])
+    keys = [int.from_bytes(frames["bytes"][j][1:4].tobytes(), "big") if modes is None
+            else None if int(modes[j]["kind"]) > L.ADSB_MODES_KNOWN else int(modes[j]["address"]) & 0xFFFFFF
+            for j in range(len(frames))]
+    new = sorted({k for k in keys if k is not None} - set(state))
+    for icao in new if max_aircraft is None else new[:max(int(max_aircraft) - len(state), 0)]:
+        state[icao] = empty
+    for j, icao in enumerate(keys):
+        if icao not in state:
+            continue
+        t = float(int(sample_base) + int(frames["offset"][j])) * seconds_per_sample
+        held = state[icao]
+        out[j] = host_es_resolve(es[j], t, held, max_age_s)
+        state[icao] = host_track_es_merge(held, host_track_es_of(es[j], out[j], t))
+    order = sorted(state)
+    return (np.array(order, dtype=np.uint32), np.array([state[a] for a in order], dtype=AIRCRAFT_ES_DTYPE).reshape(-1), out)
+
+
+def aircraft_es_physical(recs):
+    """The values of AIRCRAFT_ES_DTYPE records (TrackTable.es) in physical units, the per-aircraft counterpart of
+    es_physical with its conversions: a dict of float64 arrays, one entry per aircraft, NaN for what the aircraft has not
+    said.  rc_m: the resolved containment radius of its newest position message in metres (NaN: no position message, or
+    a radius the table calls unknown); selected_altitude_ft, baro_setting_mb, selected_heading_deg: of its newest
+    target state message."""
+    recs = np.atleast_1d(np.asarray(recs, dtype=AIRCRAFT_ES_DTYPE))
+    out = {"rc_m": np.where(~np.isnan(recs["position_time"]) & (recs["rc_dm"] != 0),
+                            recs["rc_dm"] * _ES_PHYSICAL["rc_m"][3], np.nan)}
+    held = ~np.isnan(recs["time"][:, 2])
+    for key, value in es_physical(recs["target_state"]).items():
+        if key != "rc_m":
+            out[key] = np.where(held, value, np.nan)
+    return out
+
+
+AIRCRAFT_ES_COLUMNS = ("Ver", "NIC", "Rc", "NACp", "SIL", "Emerg", "Squawk(ES)", "SelAlt")
+
+
+def aircraft_es_columns(recs):
+    """AIRCRAFT_ES_DTYPE records as the text columns AIRCRAFT_ES_COLUMNS, one list of eight strings per aircraft: the
+    ADS-B version, NIC and Rc in metres of the newest position message as the table resolved them (a "?" behind NIC
+    and Rc where the version was not known when it was heard: Rc is then what the type code alone gives), NACp and SIL
+    of the newest operational status (airborne or surface, whichever is newer) or, without one, target state message,
+    the emergency state and squawk of the newest TC 28 message, and the selected altitude in feet; "n/a" for what the
+    aircraft has not said."""
+    recs = np.atleast_1d(np.asarray(recs, dtype=AIRCRAFT_ES_DTYPE))
+    p = aircraft_es_physical(recs)
+    rows = []
+    for k, r in enumerate(recs):
+        ver = "n/a" if np.isnan(r["version_time"]) else str(int(r["version"]))
+        nic = rc = "n/a"
+        if not np.isnan(r["position_time"]):
+            mark = "" if int(r["position_supp"]) & L.ADSB_TRACK_ES_VERSIONED << 1 else "?"
+            nic = f"{int(r['nic'])}{mark}"
+            rc = "n/a" if np.isnan(p["rc_m"][k]) else f"{p['rc_m'][k]:.1f}{mark}"
+        times = np.where(np.isnan(r["time"][:3]), -np.inf, r["time"][:3])
+        nacp = sil = "n/a"
+        for name, t in sorted(zip(AIRCRAFT_ES_BLOCKS[:3], times), key=lambda x: (-x[1], x[0] == "target_state")):
+            b = r[name]
+            if t > -np.inf and int(b["present"]) & L.ADSB_ES_HAS_NAC_P:
+                nacp, sil = str(int(b["nac_p"])), str(int(b["sil"])) if int(b["present"]) & L.ADSB_ES_HAS_SIL else "n/a"
+                break
+        emerg = squawk = "n/a"
+        if not np.isnan(r["time"][3]):
+            emerg, squawk = str(int(r["emergency"]["emergency"])), f"{int(r['emergency']['half'][0]):04d}"
+        sel = "n/a" if np.isnan(p["selected_altitude_ft"][k]) else f"{p['selected_altitude_ft'][k]:.0f}"
+        rows.append([ver, nic, rc, nacp, sil, emerg, squawk, sel])
+    return rows
+
+
 COMMB_SETTLED = L.ADSB_COMMB_SETTLED     # COMMB_DTYPE state of a table's per-frame output: settled by the table
 # aircraft_commb_physical: key -> (block, index into value[], what one unit of the value is in the key's unit)
 _AIRCRAFT_COMMB_PHYSICAL = {key: ("bds%02x" % bds, k, factor) for key, (bds, k, factor) in _COMMB_PHYSICAL.items()}
@@ -1729,18 +1857,34 @@ class TrackTable(_TrackStore):
         self._open(dem, L.AdsbTrackTableCfg(L.ADSB_ABI_VERSION, int(max_aircraft), int(max_frames),
                                             float(seconds_per_sample)), max_frames)
 
-    def update(self, frames, sample_base=0, levels=None, mlat=None, modes=None, commb=None):
+    def update(self, frames, sample_base=0, levels=None, mlat=None, modes=None, commb=None, es=None):
         """frames: FRAME_DTYPE array in ascending offset (host); packet time = (sample_base + offset) x sps.  levels
         (after levels_reserve): the frames' LEVEL_DTYPE records (host), merged into the aircraft's level records.  mlat
         (after mlat_reserve): the frames' MLAT_FIX_DTYPE fixes (host), merged into the aircraft's mlat records.  modes
         (after modes_reserve): the frames' MODES_DTYPE records (host); the list is then keyed by their addresses, a
         frame that is not SELF or KNOWN touches nothing, and the aircraft's modes records take the replies.  commb
         (with modes, after commb_reserve): the frames' COMMB_DTYPE records (host); the aircraft's commb records take the
-        registers, and a reply that reads as 5,0 and as 6,0 is settled against the aircraft's ADS-B velocity."""
+        registers, and a reply that reads as 5,0 and as 6,0 is settled against the aircraft's ADS-B velocity.  es (after
+        es_reserve): the frames' ES_DTYPE records (host); the update is the one the other arguments choose, and the
+        aircraft's es records take the extended squitter status, NIC and Rc of every position message resolved."""
         frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
         ptr = frames.ctypes.data if len(frames) else None
         if commb is not None and modes is None:
             raise ValueError("commb needs modes")
+        if es is not None:
+            n = len(frames)
+            given = {"es": (es, ES_DTYPE), "modes": (modes, MODES_DTYPE), "commb": (commb, COMMB_DTYPE),
+                     "mlat": (mlat, MLAT_FIX_DTYPE)}
+            arrays = {}
+            for name, (arr, dtype) in given.items():
+                arrays[name] = None if arr is None else np.ascontiguousarray(arr, dtype=dtype)
+                if arrays[name] is not None and len(arrays[name]) != n:
+                    raise ValueError(f"{name}: {len(arrays[name])} records for {n} frames")
+            keep, lptr = (None, None) if levels is None else self._host_levels(levels, n)
+            at = lambda a: a.ctypes.data if a is not None and len(a) else None
+            self._call("update_es", ptr, at(arrays["es"]), at(arrays["modes"]), at(arrays["commb"]), at(arrays["mlat"]),
+                       lptr, n, int(sample_base))
+            return
         if modes is not None:
             recs = np.ascontiguousarray(modes, dtype=MODES_DTYPE)
             if len(recs) != len(frames):
@@ -1771,14 +1915,21 @@ class TrackTable(_TrackStore):
             keep, lptr = self._host_levels(levels, len(frames))
             self._call("update_levels", ptr, lptr, len(frames), int(sample_base))
 
-    def update_device(self, dev_ptr, n, sample_base=0, levels_ptr=None, mlat_ptr=None, modes_ptr=None, commb_ptr=None):
+    def update_device(self, dev_ptr, n, sample_base=0, levels_ptr=None, mlat_ptr=None, modes_ptr=None, commb_ptr=None,
+                      es_ptr=None):
         """n frames at dev_ptr in the ctx device's memory (e.g. result_device() after fetch_counts()).  levels_ptr
         (after levels_reserve): their n level records, on the device (e.g. levels_device()) or a host address.  mlat_ptr
         (after mlat_reserve): their n adsb_mlat_fix records, on the device (e.g. mlat_device()[0]) or a host address;
         every address may be a host one too, each on its own.  modes_ptr (after modes_reserve): their n adsb_modes_rec
         records (e.g. modes_device()[0]); the update is then update_modes.  commb_ptr (with modes_ptr, after
-        commb_reserve): their n adsb_commb_rec records (e.g. commb_device()[0]); the update is then update_commb."""
-        if commb_ptr is not None:
+        commb_reserve): their n adsb_commb_rec records (e.g. commb_device()[0]); the update is then update_commb.  es_ptr
+        (after es_reserve): their n adsb_es_rec records (e.g. es_device()[0]); the update the other arguments choose is
+        then made through update_es."""
+        if es_ptr is not None:
+            if commb_ptr is not None and modes_ptr is None:
+                raise ValueError("commb_ptr needs modes_ptr")
+            self._call("update_es", dev_ptr, es_ptr, modes_ptr, commb_ptr, mlat_ptr, levels_ptr, int(n), int(sample_base))
+        elif commb_ptr is not None:
             if modes_ptr is None:
                 raise ValueError("commb_ptr needs modes_ptr")
             self._call("update_commb", dev_ptr, modes_ptr, commb_ptr, mlat_ptr, levels_ptr, int(n), int(sample_base))
@@ -1855,6 +2006,32 @@ class TrackTable(_TrackStore):
         synchronisation."""
         dev = C.c_void_p()
         self._call("commb_device", C.byref(dev))
+        return dev.value
+
+    def es_reserve(self, max_age_s=60.0):
+        """adsb_track_table_es_reserve: one AIRCRAFT_ES_DTYPE record beside every aircraft record, which an update given
+        `es` merges the frames' extended squitter status into.  A position message's NIC and Rc are resolved with the
+        aircraft's version and with NIC supplements A and C that are at most max_age_s old (policy, not a measurement;
+        float("inf") keeps them for ever)."""
+        cfg = L.AdsbEsTrackCfg(float(max_age_s))
+        self._call("es_reserve", C.byref(cfg))
+
+    def es(self):
+        """AIRCRAFT_ES_DTYPE records (what each aircraft's extended squitters say, NIC and Rc resolved), aligned with
+        aircraft()[0]; aircraft_es_physical() gives them in physical units."""
+        return self._fetch("fetch_es", [AIRCRAFT_ES_DTYPE])[0]
+
+    def frame_es(self):
+        """One FRAME_INTEGRITY_DTYPE record per frame of the last update given `es`, in its list order: NIC and Rc of a
+        position message as resolved, the version known before the frame, and the COUNTED / POSITION / VERSIONED /
+        STALE flags; all zero for a frame that was not counted."""
+        return self._fetch("fetch_frame_es", [FRAME_INTEGRITY_DTYPE], size=self.max_frames)[0]
+
+    def es_device(self):
+        """Device address of the es records, one per record place in slot order (as levels_device); no
+        synchronisation."""
+        dev = C.c_void_p()
+        self._call("es_device", C.byref(dev))
         return dev.value
 
     def fixes_reserve(self, site):

@@ -2001,6 +2001,128 @@ int adsb_track_table_fetch_frame_commb(adsb_track_table *table, adsb_commb_rec *
 int adsb_track_table_commb_device(adsb_track_table *table, const adsb_aircraft_commb **dev);
 
 /*
+ * Extended squitter status per aircraft.  adsb_es_of reads what every DF17/18 frame says beside identity, position and
+ * velocity and is stateless; with an es reserve a TABLE keeps, per aircraft, the newest operational status (airborne
+ * and surface), target state, emergency / squawk and ACAS RA records, the ADS-B version, NIC supplements A and C, the
+ * category, NACv, and two counts, in one 256-byte adsb_aircraft_es beside its record.  It also resolves what the
+ * stateless stage cannot: NIC and the containment radius Rc of a position message depend on the aircraft's version and
+ * on supplements that arrive in OTHER messages of the same aircraft, which the table holds.  update_es is one of the
+ * existing updates plus the frames' adsb_es_rec[]: with recs NULL it is update (update_levels / update_mlat with those
+ * arrays), keyed by bytes[1..3]; with recs it is update_modes, keyed by the resolved address; with recs and commb it is
+ * update_commb.  Everything the chosen update does it does, with the same results; what follows is what it adds.
+ * Tables only.
+ *
+ * COUNTED  A frame is counted iff its sort key is an aircraft's (any key without recs; with recs, a frame update_modes
+ *   accepts by kind), its point is not UNTRACKED, and es[j].state is neither NOT_ES nor FOREIGN.  A frame that is not
+ *   counted gets an all-zero adsb_frame_integrity and touches nothing.  Per counted frame, by es[j] and its PER-FRAME
+ *   OUTPUT (below), each line on its own:
+ *     n_es + 1.
+ *     OPERATIONAL with subtype 0 / subtype 1, TARGET_STATE, EMERGENCY, ACAS_RA: operational_airborne /
+ *       operational_surface / target_state / emergency / acas_ra = es[j], all 32 bytes, and its time[] = frame time.
+ *     present has HAS_VERSION: version = es[j].version, version_time = frame time.
+ *     present has HAS_NIC_A: nic_a and nic_a_time.  present has HAS_NIC_C: nic_c and nic_c_time.
+ *     CATEGORY: category = es[j].category (never 0: a real one is >= 0xA0).
+ *     present has HAS_NAC_V (a VELOCITY, or a version-2 surface OPERATIONAL): nac_v = es[j].nac_v, and as ONE group
+ *       with it velocity_flags = the low byte of es[j].flags for a VELOCITY and 0 otherwise, has = 3 for a VELOCITY and
+ *       1 otherwise (bit 0: nac_v holds a value; bit 1: velocity_flags came from a velocity message).
+ *     POSITION: n_position + 1; rc_dm and nic = the per-frame output's; position_supp = its supp in bits 0-2 and its
+ *       VERSIONED, STALE_A and STALE_C flags in bits 3, 4 and 5 (the flag's value << 1), so the record says how its
+ *       newest position was resolved; position_tc = the type code; nic_b = es[j].nic_b with HAS_NIC_B and 0 without;
+ *       position_time = frame time.
+ *   Counts saturate at 2^32 - 1.  Every combine is a saturating add or "the later list position wins" per block and per
+ *   version / A / C / position / category / NACv group, so it is associative.  The EMPTY record has every time NaN and
+ *   everything else 0 and is the identity of the merge: at admission, at re-admission after an expire, after a reset,
+ *   and for aircraft held from before the reserve.  Times are the store's frame time, the single rounded product
+ *   (sample_base + offset) x seconds_per_sample.
+ * RESOLUTION of a counted frame heard at t.  V, A and C are the aircraft's newest counted frames BEFORE it in list
+ *   order with HAS_VERSION, HAS_NIC_A and HAS_NIC_C respectively, over the table's history since the aircraft's
+ *   admission: the newest such frame earlier in the current list, else what the record held before this update.  A
+ *   frame never uses itself or a later frame: an operational status that follows a position in the same list does not
+ *   reach it.  The version never expires.  A and C are usable iff 0 <= t - time <= max_age_s, computed in f64 with one
+ *   subtraction (NaN: not usable; a negative age, from a smaller sample_base in a later update, is not usable).  A
+ *   supplement the aircraft has but that is not usable sets STALE_A / STALE_C and enters as 0.  B is the frame's own
+ *   nic_b if it has HAS_NIC_B, else 0.
+ * PER-FRAME OUTPUT  For a counted POSITION frame: (nic, rc_dm) = what adsb_host_es_integrity gives for (type code, V's
+ *   version or ADSB_ES_VERSION_UNKNOWN, supp) with supp = A | B << 1 | C << 2; version = V's or UNKNOWN; flags =
+ *   COUNTED | POSITION, VERSIONED iff V exists, STALE_A, STALE_C.  That table decides which supplements a version and a
+ *   type code read; a version-2 supplement A held when a version-0 status arrives is handed over and ignored there.
+ *   For a counted frame that is no position: flags = COUNTED, version = V's or UNKNOWN, all else 0.
+ * CUT INVARIANCE  The rule depends only on the frame sequence: one list cut into any sequence of update_es calls gives
+ *   the same 256 bytes per aircraft, and the concatenated frame_es is the uncut call's.
+ * max_age_s is policy, not a measurement: 60.0 by default; +inf keeps a supplement for ever.
+ * On the device, beside the levels / fix / mlat merges (the step needs the sort, the record slots and its own side array
+ * only): one segmented inclusive scan whose operand is computed where it is loaded, from es[]: a head mark and the
+ * sorted position + 1 of the newest frame with HAS_VERSION, HAS_NIC_A and HAS_NIC_C; one thread per sorted frame reads
+ * its predecessor's scan words, resolves V / A / C from those frames or from the held record, writes frame_es[j] and a
+ * 56-byte scan operand at its sorted position; one segmented inclusive scan (head mark, eleven "newest position" words,
+ * two saturating counts); one thread per segment tail reads the winners' es[], frame_es and times and merges into the
+ * side record.  No atomics, no workgroup waits for another, nothing is read back, linear in the list.  Device memory,
+ * all of it allocated by the reserve: 256 bytes per place of max_aircraft, and per frame of max_frames 16 + 8 + 56 + 56
+ * bytes plus 32 bytes of device staging for a host es array and the scans' scratch; 32 bytes per frame of pinned host
+ * memory.  A table that never reserves allocates nothing and launches exactly the kernels it launched before; update,
+ * update_levels, update_mlat, update_modes and update_commb of a table that did reserve behave as before and leave the
+ * es records alone (apart from admission emptying a place).
+ */
+#define ADSB_TRACK_ES_COUNTED   0x1u  /* adsb_frame_integrity.flags: the frame was counted                          */
+#define ADSB_TRACK_ES_POSITION  0x2u  /* it is a position message: rc_dm, nic and supp hold the resolved values     */
+#define ADSB_TRACK_ES_VERSIONED 0x4u  /* with POSITION: the aircraft's version was known                            */
+#define ADSB_TRACK_ES_STALE_A   0x8u  /* with POSITION: the aircraft has a supplement A, too old (or from later)    */
+#define ADSB_TRACK_ES_STALE_C   0x10u /* likewise supplement C                                                      */
+typedef struct adsb_es_track_cfg { /* 16 bytes */
+    double   max_age_s;           /* supplements A and C are usable up to this age; policy, not a measurement */
+    uint32_t reserved[2];         /* 0 */
+} adsb_es_track_cfg;
+typedef struct adsb_frame_integrity { /* 8 bytes, one per frame of the last update_es */
+    uint32_t rc_dm;               /* resolved Rc in decimetres, 0 unknown */
+    uint8_t  nic;
+    uint8_t  version;             /* the aircraft's version as known BEFORE this frame; ADSB_ES_VERSION_UNKNOWN if none */
+    uint8_t  supp;                /* what was handed to the integrity table: bit 0 A, bit 1 B, bit 2 C */
+    uint8_t  flags;               /* ADSB_TRACK_ES_COUNTED ... */
+} adsb_frame_integrity;
+/* (tag first, typedef after, as adsb_aircraft_commb: members of a struct type) */
+struct adsb_aircraft_es {             /* 256 bytes, one per record place */
+    adsb_es_rec operational_airborne, operational_surface, target_state, emergency, acas_ra; /* newest frame's record of each */
+    double   time[5];             /* their frame times, same order; NaN = none */
+    double   version_time, nic_a_time, nic_c_time, position_time; /* NaN = none */
+    uint32_t rc_dm;               /* of the newest position message, resolved; 0 unknown */
+    uint8_t  nic, position_tc, nic_b, position_supp; /* position_supp: A, B, C as handed over, then VERSIONED, STALE_A, STALE_C */
+    uint8_t  version, nic_a, nic_c, category;   /* category 0 = none (a real one is >= 0xA0) */
+    uint32_t n_es, n_position;    /* saturating at 2^32 - 1 */
+    uint8_t  nac_v, velocity_flags, has, reserved; /* has bit 0: nac_v holds a value, bit 1: velocity_flags does */
+};
+typedef struct adsb_aircraft_es adsb_aircraft_es;
+#ifdef __cplusplus
+static_assert(sizeof(adsb_es_track_cfg) == 16 && sizeof(adsb_frame_integrity) == 8 && sizeof(adsb_aircraft_es) == 256,
+              "adsb_aircraft_es layout");
+#endif
+/* Allocates the above and empties every es record.  cfg NULL: max_age_s = 60.0 (policy, not a measurement); +inf is
+ * allowed.  May wait for the device.  A second reserve changes nothing, its cfg neither.  ADSB_E_ARG for a NULL table or
+ * a max_age_s that is NaN or negative; ADSB_E_NOMEM if the memory is not to be had. */
+int adsb_track_table_es_reserve(adsb_track_table *table, const adsb_es_track_cfg *cfg);
+/* The update described above.  es[n] and, if given, recs[n], commb[n], fixes[n] and levels[n] are the frames' in list
+ * order.  Each may be host memory or memory of the ctx's device, independently; host arrays have been copied when this
+ * returns.  es may be adsb_es_device's pointer, recs adsb_modes_device's and commb adsb_commb_device's (the ctx's
+ * scratch, ordered on the same stream).  ADSB_E_ARG for a NULL table, NULL frames or es with n > 0, or commb without
+ * recs; ADSB_E_STATE without an es reserve, for recs without a modes reserve, for commb without a commb reserve, for
+ * fixes without an mlat reserve, or for levels without a levels reserve; ADSB_E_CAPACITY for n > max_frames; n = 0 is
+ * ADSB_OK. */
+int adsb_track_table_update_es(adsb_track_table *table, const adsb_frame *frames, const adsb_es_rec *es,
+                               const adsb_modes_rec *recs /* may be NULL */, const adsb_commb_rec *commb /* may be NULL */,
+                               const adsb_mlat_fix *fixes /* may be NULL */,
+                               const adsb_frame_level *levels /* may be NULL */, size_t n, uint64_t sample_base);
+/* Waits; one es record per aircraft, in exactly the order adsb_track_table_fetch returns the records (ascending
+ * ICAO); *n = records held even if more than max.  ADSB_E_ARG for a NULL table, or NULL out with max > 0;
+ * ADSB_E_STATE without a reserve. */
+int adsb_track_table_fetch_es(adsb_track_table *table, adsb_aircraft_es *out, size_t max, size_t *n);
+/* Waits; the per-frame output of the last update_es, in list order (another update in between leaves it alone);
+ * *n = min(frames of that update, max).  ADSB_E_ARG for a NULL table, or NULL out with max > 0; ADSB_E_STATE without a
+ * reserve or before any update_es since the reserve or the last reset. */
+int adsb_track_table_fetch_frame_es(adsb_track_table *table, adsb_frame_integrity *out, size_t max, size_t *n);
+/* Does not synchronise: the device address of the es records, one per record PLACE in slot order; dev may be NULL.
+ * ADSB_E_ARG for a NULL table, ADSB_E_STATE without a reserve. */
+int adsb_track_table_es_device(adsb_track_table *table, const adsb_aircraft_es **dev);
+
+/*
  * ---- several GPUs behind one call ---------------------------------------------------------
  * The reference's thread 2 is one function on one thread (src/adsb.rs:92, spawned at adsb.rs:147); a group is the
  * drop-in for that function when the buffer should be spread over N devices: one context per member, the offsets

@@ -286,6 +286,27 @@ int adsb_host_commb_reference(const uint8_t bytes[14], double time, adsb_velocit
 int adsb_host_track_commb_of(const adsb_commb_rec *rec, double time, adsb_aircraft_commb *one);
 int adsb_host_track_commb_merge(adsb_aircraft_commb *into, const adsb_aircraft_commb *later);
 
+/*
+ * CPU mirror of the extended squitter step of a table with an es reserve (adsb_hip.h, "Extended squitter status per
+ * aircraft"): the same program text as the device's, no device needed.
+ * es_resolve: *out = the per-frame output of a frame with stateless record *rec heard at frame time `time`, whose key
+ * and point let it count, of an aircraft whose record before the frame is *held (NULL: the empty record): read from it
+ * are version / version_time, nic_a / nic_a_time and nic_c / nic_c_time, a time of NaN meaning "none".  For a position
+ * message that is NIC and Rc resolved by adsb_host_es_integrity's table; all zero for a record whose state is NOT_ES or
+ * FOREIGN.  cfg NULL: the reserve's default, max_age_s = 60.0.
+ * track_es_of: *one = the adsb_aircraft_es of an aircraft whose only counted frame since admission has the record *rec
+ * and the per-frame output *integrity, heard at `time` (the EMPTY record if *integrity is not COUNTED).
+ * track_es_merge: *into becomes *into followed by *later, a record of the frames that come after into's: the combine
+ * the device's segment tails apply.  A table's record after a list is the fold of these three over the aircraft's
+ * frames in list order.
+ * ADSB_E_ARG for a NULL rec, out, integrity, one, into or later, or a cfg whose max_age_s is NaN or negative.
+ */
+int adsb_host_es_resolve(const adsb_es_rec *rec, double time, const adsb_aircraft_es *held /* may be NULL */,
+                         const adsb_es_track_cfg *cfg /* may be NULL */, adsb_frame_integrity *out);
+int adsb_host_track_es_of(const adsb_es_rec *rec, const adsb_frame_integrity *integrity, double time,
+                          adsb_aircraft_es *one);
+int adsb_host_track_es_merge(adsb_aircraft_es *into, const adsb_aircraft_es *later);
+
 /* ---- behind the channel: tracker + CPR ------------------------------------------- */
 
 /* cpr.rs:39-54 calc_num_zones; cpr.rs:135-147 calculate_geographic_position (returns 1 = Some, 0 = None).

@@ -34,7 +34,12 @@ Replies (DF0/4/5/11/16/20/21 frames counted), and S, which is "S" for an aircraf
 --modes --commb --aircraft: the Comm-B stage (adsb_commb_of) reads the same frames where they lie and the table takes its
 records too (adsb_track_table_update_commb): per aircraft the newest BDS 4,0, 5,0 and 6,0, a reply that reads as 5,0 and
 as 6,0 settled from the aircraft's own ADS-B velocity.  Six more columns: SelAlt, QNH, GS/Trk(B), Hdg, IAS, Mach, with a
-"*" behind a value from a settled reply."""
+"*" behind a value from a settled reply.
+
+--modes --es --aircraft: the extended squitter status stage (adsb_es_of) reads the same frames and the table takes its
+records too (adsb_track_table_update_es, on the keyed path): NIC and Rc of each aircraft's newest position message resolved
+with the version and NIC supplements of its own operational status messages.  Eight more columns: Ver, NIC, Rc, NACp, SIL,
+Emerg, Squawk(ES), SelAlt, with a "?" behind NIC and Rc where no version was known when the position was heard."""
 import argparse
 import os
 import sys
@@ -119,12 +124,13 @@ def modes_columns(A, s):
                       f"{int(s['n_replies'])}", "" if flags & A.ADSB_TRACK_MODES_SQUITTER else "S"])
 
 
-def aircraft_lines(A, recs, mlat, now, modes=None, commb=None):
+def aircraft_lines(A, recs, mlat, now, modes=None, commb=None, es=None):
     """One tab-separated line per aircraft, under a header line.  modes (AIRCRAFT_MODES_DTYPE records): five more
-    columns.  commb (AIRCRAFT_COMMB_DTYPE records): six more."""
+    columns.  commb (AIRCRAFT_COMMB_DTYPE records): six more.  es (aircraft_es_columns' rows): eight more."""
     out = ("ICAO\tCallsign\tLatitude\tLongitude\tMlatLat\tMlatLon\tAge\tPdop\tValid/Attempted\tChecked/Disagree"
            "\tMaxDisagreement" + ("" if modes is None else "\tAlt(S)\tSquawk\tCall(S)\tReplies\tS")
-           + ("" if commb is None else "\t" + "\t".join(A.AIRCRAFT_COMMB_COLUMNS)) + "\n")
+           + ("" if commb is None else "\t" + "\t".join(A.AIRCRAFT_COMMB_COLUMNS))
+           + ("" if es is None else "\t" + "\t".join(A.AIRCRAFT_ES_COLUMNS)) + "\n")
     registers = None if commb is None else A.aircraft_commb_columns(commb)
     for k, (r, m) in enumerate(zip(recs, mlat)):
         call = r["callsign"].decode("ascii", "replace").strip() or "n/a"
@@ -138,7 +144,8 @@ def aircraft_lines(A, recs, mlat, now, modes=None, commb=None):
         out += (f"{int(r['icao']):06X}\t{call}\t{said}\t{solved}\t{int(m['n_valid'])}/{int(m['n_attempted'])}"
                 f"\t{int(m['n_checked'])}/{int(m['n_disagree'])}\t{worst}"
                 + ("" if modes is None else "\t" + modes_columns(A, modes[k]))
-                + ("" if registers is None else "\t" + "\t".join(registers[k])) + "\n")
+                + ("" if registers is None else "\t" + "\t".join(registers[k]))
+                + ("" if es is None else "\t" + "\t".join(es[k])) + "\n")
     return out
 
 
@@ -160,6 +167,9 @@ def main():
     ap.add_argument("--modes", action="store_true", help="Mode S replies too: short frames, addresses from the Mode S stage")
     ap.add_argument("--commb", action="store_true",
                     help="with --modes --aircraft: the aircraft's Comm-B registers too, six more columns")
+    ap.add_argument("--es", action="store_true",
+                    help="with --modes --aircraft: the aircraft's extended squitter status too, NIC and Rc resolved per "
+                         "aircraft, eight more columns")
     ap.add_argument("--max-iterations", type=int, default=0,
                     help="the solver's step limit (default: its own, 24); replies carry no altitude, and a free solve over "
                          "ground receivers may need 200")
@@ -168,6 +178,8 @@ def main():
         ap.error("--modes does not go with --sync")
     if args.commb and not (args.modes and args.aircraft):
         ap.error("--commb needs --modes and --aircraft")
+    if args.es and not (args.modes and args.aircraft):
+        ap.error("--es needs --modes and --aircraft")
 
     import numpy as np
 
@@ -200,7 +212,7 @@ def main():
         out["first"] = np.cumsum([0] + [len(p) for p in parts])[:-1]
         return out, (np.concatenate(parts) if parts else recs[:0]), modes["address"][keep]
 
-    address = accepted = newest = None
+    address = accepted = newest = commb_side = es_side = None
     if args.modes and args.host:
         win = A.host_wire_parse(data, ends, filter="short")
         every, fout, recs = A.host_correlate(win.frames, win.counts, args.window)
@@ -212,7 +224,9 @@ def main():
             spread[np.flatnonzero(mrec["kind"] <= A.ADSB_MODES_KNOWN)] = fixes
             aircraft = host_table(A, fout, spread, args.max_disagreement, modes=mrec)
             if args.commb:                                              # every accepted address has a row in both
-                aircraft += (A.host_track_commb(fout, mrec, A.host_commb(fout)[0])[1],)
+                commb_side = A.host_track_commb(fout, mrec, A.host_commb(fout)[0])[1]
+            if args.es:
+                es_side = A.aircraft_es_columns(A.host_track_es(fout, A.host_es(fout)[0], mrec)[1])
             newest = float(int(every["time"][-1])) * 0.5e-6 if len(every) else 0.0
     elif args.modes:
         with A.AdsbDemod(max_samples=1 << 16, max_out=1024) as d:
@@ -230,9 +244,16 @@ def main():
                         table.commb_reserve()
                         d.commb_of_async((d.correlated_device()[1], n_msgs))     # the same frames, where they lie
                         commb_ptr = d.commb_device()[0]
+                    es_ptr = None
+                    if args.es:
+                        table.es_reserve()
+                        d.es_of_async((d.correlated_device()[1], n_msgs))        # likewise
+                        es_ptr = d.es_device()[0]
                     table.update_device(d.correlated_device()[1], n_msgs, 0, mlat_ptr=d.mlat_device()[0],
-                                        modes_ptr=d.modes_device()[0], commb_ptr=commb_ptr)
-                    aircraft = (table.aircraft()[0], table.mlat(), table.modes()) + ((table.commb(),) if args.commb else ())
+                                        modes_ptr=d.modes_device()[0], commb_ptr=commb_ptr, es_ptr=es_ptr)
+                    aircraft = (table.aircraft()[0], table.mlat(), table.modes())
+                    commb_side = table.commb() if args.commb else None
+                    es_side = A.aircraft_es_columns(table.es()) if args.es else None
             fixes, hdr = d.fetch_mlat()
             msgs, _, recs = d.fetch_correlated()
             mrec = d.fetch_modes()[0]
@@ -275,8 +296,8 @@ def main():
     if aircraft is not None:
         if newest is None:
             newest = float(int(msgs["time"][-1])) * 0.5e-6 if len(msgs) else 0.0
-        print(aircraft_lines(A, aircraft[0], aircraft[1], newest, aircraft[2] if len(aircraft) > 2 else None,
-                             aircraft[3] if len(aircraft) > 3 else None), end="")
+        print(aircraft_lines(A, aircraft[0], aircraft[1], newest, aircraft[2] if len(aircraft) > 2 else None, commb_side,
+                             es_side), end="")
     for k, (m, f) in enumerate(zip(msgs, fixes)):
         if aircraft is None and f["flags"] & A.ADSB_MLAT_VALID and (accepted is None or accepted[k]):
             t = int(win.rx["ticks"][recs["frame"][m["first"]]]) / 12e6

@@ -65,6 +65,12 @@ frame, and the state with its values: "CATEGORY A0", "POSITION tc=11 nic_b=0 rc=
 baro=1012.8mb hdg=66.8 nac_p=9 nic_baro=1 sil=3 modes=autopilot,vnav,lnav tcas", "OPERATIONAL st=0 v2 cc=2300 om=0300
 nic_a=0 nac_p=9 sil=3 nic_baro=1 sil_supp=0 sda=3 gva=2", "RESERVED tc=23 st=0", "FOREIGN"; a value the frame does not hold is left
 out.  The stage does not check parity: the frames of a Beast or AVR capture are read as they stand.
+With --es --aircraft (samples, --beast-in, --avr-in, with --modes or without) the table takes those records too
+(adsb_track_table_update_es) and eight columns are appended: Ver (the aircraft's ADS-B version), NIC and Rc in metres of
+its newest position message, resolved with the version and the NIC supplements the aircraft sent in its operational
+status messages (a "?" behind both where no version was known when that message was heard: Rc is then what the type
+code alone gives), NACp and SIL of the newest operational status or target state message, Emerg and Squawk(ES) of the
+newest TC 28 message, and SelAlt, the selected altitude in feet.
 The TEXT has not been compared with a Rust build's (there is no
 Rust toolchain); only the values are checked, against the oracle."""
 import argparse
@@ -124,7 +130,7 @@ def modes_columns(s):
             f"{int(s['n_replies'])}", "" if flags & A.ADSB_TRACK_MODES_SQUITTER else "S"]
 
 
-def aircraft_table(d, frames, n_samples, st=None, frame_levels=None, site=None, modes=None, commb=None):
+def aircraft_table(d, frames, n_samples, st=None, frame_levels=None, site=None, modes=None, commb=None, es=None):
     """The capture's final aircraft table as tab-separated text: tui.rs:95's columns, rows by age (tui.rs:69), then
     ICAO.  Age = whole seconds from each aircraft's last frame to the end of the capture.  frame_levels (one
     LEVEL_DTYPE record per frame, with st the sample type): also the columns RSSI and SNR.  site ((latitude, longitude,
@@ -132,7 +138,10 @@ def aircraft_table(d, frames, n_samples, st=None, frame_levels=None, site=None, 
     keyed by the records' addresses (update_modes); also Alt(S), Squawk, Call(S), Replies and S.  commb (with modes: one
     COMMB_DTYPE record per frame): the table also keeps the aircraft's Comm-B registers (update_commb) and settles a reply
     that reads as 5,0 and as 6,0 from the aircraft's ADS-B velocity; also SelAlt, QNH, GS/Trk(B), Hdg, IAS and Mach, with
-    a "*" behind a value from a settled reply."""
+    a "*" behind a value from a settled reply.  es (one ES_DTYPE record per frame): the table also keeps the aircraft's
+    extended squitter status (update_es) and resolves NIC and Rc of every position message with the aircraft's version and
+    NIC supplements; also Ver, NIC, Rc, NACp, SIL, Emerg, Squawk(ES) and SelAlt, with a "?" behind NIC and Rc of an
+    aircraft whose version was not known when its newest position was heard (Rc is then the type code's own)."""
     with A.TrackTable(d, max_frames=max(len(frames), 1), seconds_per_sample=SECONDS_PER_SAMPLE) as t:
         if site is not None:
             t.fixes_reserve(site)
@@ -142,6 +151,9 @@ def aircraft_table(d, frames, n_samples, st=None, frame_levels=None, site=None, 
         if commb is not None:
             t.commb_reserve()
             more["commb"] = commb
+        if es is not None:
+            t.es_reserve()
+            more["es"] = es
         if frame_levels is None:
             t.update(frames, modes=modes, **more)
         else:
@@ -153,9 +165,12 @@ def aircraft_table(d, frames, n_samples, st=None, frame_levels=None, site=None, 
         levels = [None] * len(recs) if frame_levels is None else t.levels()
         fixes = [None] * len(recs) if site is None else t.fixes()
         registers = [None] * len(recs) if commb is None else A.aircraft_commb_columns(t.commb())
+        status = [None] * len(recs)
+        if es is not None:
+            status = A.aircraft_es_columns(t.es())
     now = n_samples * SECONDS_PER_SAMPLE
     rows = []
-    for rec, v, lh, lv, fx, side, reg in zip(recs, vel, heard, levels, fixes, sides, registers):
+    for rec, v, lh, lv, fx, side, reg, stat in zip(recs, vel, heard, levels, fixes, sides, registers, status):
         pos, age = bool(rec["has_position"]), int(now - lh)
         rows.append((age, int(rec["icao"]), "\t".join([
             f"{int(rec['icao']):x}",
@@ -165,12 +180,13 @@ def aircraft_table(d, frames, n_samples, st=None, frame_levels=None, site=None, 
             f"{float(rec['longitude']):.6f}" if pos else "n/a",
             f"{float(v['speed_kt']):.0f}" if v["flags"] & A.ADSB_VELOCITY_SPEED else "n/a",
             f"{age}"] + ([] if lv is None else level_columns(st, lv)) + ([] if fx is None else fix_columns(fx))
-            + ([] if side is None else modes_columns(side)) + ([] if reg is None else reg))))
+            + ([] if side is None else modes_columns(side)) + ([] if reg is None else reg) + ([] if stat is None else stat))))
     rows.sort(key=lambda r: (r[0], r[1]))
     head = "ICAO\tCallsign\tAltitude\tLatitude\tLongitude\tVelocity\tAge" + ("" if frame_levels is None else "\tRSSI\tSNR")
     head += "" if site is None else "\tFixLat\tFixLon\tRange\tBearing\tGS"
     head += "" if modes is None else "\tAlt(S)\tSquawk\tCall(S)\tReplies\tS"
     head += "" if commb is None else "\t" + "\t".join(A.AIRCRAFT_COMMB_COLUMNS)
+    head += "" if es is None else "\t" + "\t".join(A.AIRCRAFT_ES_COLUMNS)
     return head + "\n" + "".join(r[2] + "\n" for r in rows)
 
 
@@ -441,7 +457,8 @@ def main():
                          "values; with --modes --aircraft: six more columns from the aircraft's Comm-B registers")
     ap.add_argument("--es", action="store_true",
                     help="print one line per DF17/18 frame instead: its extended squitter status (category, emergency, target "
-                         "state, operational status, NACv, NIC supplement B, stand-alone Rc)")
+                         "state, operational status, NACv, NIC supplement B, stand-alone Rc); with --aircraft: eight more "
+                         "columns from the aircraft's extended squitter status, NIC and Rc resolved per aircraft")
     ap.add_argument("--tick-bias", type=int, default=0, metavar="N", help="added to every timestamp (12 MHz ticks, < 2^48)")
     a = ap.parse_args()
     if a.mlat and not a.avr:
@@ -459,8 +476,8 @@ def main():
         ap.error("--commb needs --modes")
     if wire_in and a.levels and not a.aircraft:
         ap.error("--levels alone needs the samples")
-    if a.es and (a.modes or a.aircraft or a.web or a.levels):
-        ap.error("--es prints lines of its own: not with --modes, --aircraft, --web or --levels")
+    if a.es and not a.aircraft and (a.modes or a.web or a.levels):
+        ap.error("--es without --aircraft prints lines of its own: not with --modes, --web or --levels")
     fmt = a.format or ("c16" if a.file.endswith(".c16") else "u8")
     st = A.ADSB_SAMPLE_I16 if fmt == "c16" else A.ADSB_SAMPLE_I8
     n_max = os.path.getsize(a.file) // (4 if fmt == "c16" else 2)
@@ -470,7 +487,8 @@ def main():
             frames, recs, *regs = read_wire(d, a.file, wire_in, a.tick_bias, modes=True, commb=a.commb)
             if a.aircraft:
                 n_samp = int(frames["offset"].max()) + A.WINDOW if len(frames) else 0
-                sys.stdout.write(aircraft_table(d, frames, n_samp, site=a.site, modes=recs, commb=regs[0] if a.commb else None))
+                sys.stdout.write(aircraft_table(d, frames, n_samp, site=a.site, modes=recs, commb=regs[0] if a.commb else None,
+                                                es=d.es_of(frames)[0] if a.es else None))
             else:
                 sys.stdout.write(modes_lines(frames, recs, regs[0] if a.commb else None))
             if a.summary:
@@ -480,7 +498,8 @@ def main():
             frames, parsed_levels = read_wire(d, a.file, wire_in, a.tick_bias)
             n_buf, n_samp = 0, (int(frames["offset"].max()) + A.WINDOW if len(frames) else 0)
             if a.aircraft:
-                text = aircraft_table(d, frames, n_samp, st, parsed_levels if a.levels else None, site=a.site)
+                text = aircraft_table(d, frames, n_samp, st, parsed_levels if a.levels else None, site=a.site,
+                                      es=d.es_of(frames)[0] if a.es else None)
             elif a.es:
                 text = es_lines(frames, d.es_of(frames)[0])
             else:
@@ -495,9 +514,9 @@ def main():
                                                     max_frames=max(n_max // 200, 1 << 16))
         if a.aircraft and a.levels:
             text = aircraft_table(d, frames, n_samp, st, A.host_frame_levels(read_capture(a.file, fmt), frames),
-                                  site=a.site)
+                                  site=a.site, es=d.es_of(frames)[0] if a.es else None)
         elif a.aircraft:
-            text = aircraft_table(d, frames, n_samp, site=a.site)
+            text = aircraft_table(d, frames, n_samp, site=a.site, es=d.es_of(frames)[0] if a.es else None)
         elif a.web:
             text = web_stream(d, frames, a.chunk)
         elif a.levels:
