@@ -170,6 +170,25 @@ class AdsbEsHeader(C.Structure):
     _fields_ = [("n", C.c_uint64), ("n_state", C.c_uint64 * 10), ("n_version", C.c_uint64 * 4), ("reserved", C.c_uint64)]
 
 
+ADSB_REPLIES_AP_KNOWN = 0x1        # adsb_replies_cfg.flags
+ADSB_MERGE_FROM_B = 0x80000000     # src[] of a merge: the frame is list B's
+
+
+class AdsbRepliesCfg(C.Structure):
+    """adsb_replies_cfg: the filter, the capacity and the stream position of one adsb_replies_of (32 bytes)."""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("max_frames", C.c_uint64),
+                ("first_sample_index", C.c_uint64), ("reserved2", C.c_uint64)]
+
+
+class AdsbRepliesHeader(C.Structure):
+    """adsb_replies_header: the totals of one adsb_replies_of (80 bytes)."""
+    _fields_ = [(k, C.c_uint64) for k in ("n_out", "total_found", "n_preamble", "n_all_call", "n_df18", "n_address_parity",
+                                          "n_not_known", "n_parity", "flags", "reserved")]
+
+
+assert C.sizeof(AdsbRepliesCfg) == 32 and C.sizeof(AdsbRepliesHeader) == 80
+
+
 class AdsbCorrelateCfg(C.Structure):
     """adsb_correlate_cfg: the window in samples, and whether adsb_correlate_launch takes the launch's levels."""
     _fields_ = [("window", C.c_uint32), ("use_levels", C.c_uint32), ("reserved", C.c_uint64)]
@@ -537,6 +556,13 @@ PROTOTYPES = {
     "adsb_fetch_es": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(AdsbEsHeader)]),
     "adsb_es_device": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_void_p)]),
     "adsb_debug_es_geometry": (C.c_int, [_P(C.c_uint32)]),
+    "adsb_replies_of": (C.c_int, [C.c_void_p, _P(AdsbRepliesCfg), C.c_void_p, C.c_uint32, C.c_size_t, C.c_size_t, C.c_void_p,
+                                  C.c_size_t]),
+    "adsb_fetch_replies": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, _P(AdsbRepliesHeader)]),
+    "adsb_replies_device": (C.c_int, [C.c_void_p] + [_P(C.c_void_p)] * 3),
+    "adsb_debug_replies_geometry": (C.c_int, [_P(C.c_uint32), _P(C.c_uint32)]),
+    "adsb_merge_lists_of": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
     "adsb_correlate_launch": (C.c_int, [C.c_void_p, _P(AdsbCorrelateCfg), C.c_void_p]),
     "adsb_correlate_of": (C.c_int, [C.c_void_p, _P(AdsbCorrelateCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                     C.c_uint32, C.c_void_p]),
@@ -726,6 +752,10 @@ PROTOTYPES = {
     "adsb_host_commb_as": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "adsb_host_es": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, _P(AdsbEsHeader)]),
     "adsb_host_es_integrity": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
+    "adsb_host_replies": (C.c_int, [C.c_int, _P(AdsbRepliesCfg), C.c_void_p, C.c_uint32, C.c_size_t, C.c_size_t, C.c_void_p,
+                                    C.c_size_t, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, _P(AdsbRepliesHeader)]),
+    "adsb_host_merge_lists": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
     "adsb_host_correlate": (C.c_int, [_P(AdsbCorrelateCfg), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32,
                                       C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_void_p]),
     "adsb_host_multilaterate": (C.c_int, [_P(AdsbMlatCfg), C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,

@@ -67,7 +67,9 @@ extern "C" void adsb_destroy(adsb_ctx *c)
                            c->wof.mem.p, c->wof_frames.p, c->wof_levels.p, c->corr.mem.p, c->mlat.mem.p, c->mlat.in_msgs.p,
                            c->mlat.in_recs.p, c->mlat.in_rx.p, c->clock.mem.p, c->clock.in_msgs.p, c->clock.in_recs.p,
                            c->clock.in_rx.p, c->win.mem.p, c->win.in.p, c->modes.mem.p, c->modes.in_frames.p, c->modes.in_known.p,
-                           c->commb.mem.p, c->commb.in_frames.p, c->es.mem.p, c->es.in_frames.p, c->trk_mem.p, c->scratch,
+                           c->commb.mem.p, c->commb.in_frames.p, c->es.mem.p, c->es.in_frames.p, c->replies.mem.p,
+                           c->replies.in_known.p, c->merge.a.p, c->merge.b.p, c->merge.out.p, c->merge.src.p,
+                           c->merge.prefix.p, c->trk_mem.p, c->scratch,
                            c->stamps, c->lb, c->sm.done};
     for (void *p : owned) (void)hipFree(p);
     for (char *b : c->sm.blob) if (b) (void)hipHostFree(b);

@@ -155,6 +155,23 @@ struct adsb_ctx {
         DevBuf<adsb_frame> in_frames;        // of a host list
         bool done = false;                   // a call has been enqueued
     } es;
+    // Mode S replies from samples (adsb_replies.hip), allocated on first adsb_replies_of and grown on demand: one
+    // hipMalloc carved into everything `a` below points into, and the device copy of a host known[]
+    struct Replies {
+        DevBuf<char> mem;
+        size_t tiles = 0, cap = 0, channels = 0; // what it holds
+        adsbk::RepliesArgs a{};              // scratch and result pointers (the samples, the cfg and known[] are set per call)
+        DevBuf<uint32_t> in_known;           // of a host list
+        uint32_t n_channels = 0;             // of the last call
+        bool done = false;                   // a call has been enqueued
+    } replies;
+    // adsb_merge_lists_of's scratch (grown on demand): device copies of host lists, the channels' prefixes, and the
+    // results on their way to host memory
+    struct Merge {
+        DevBuf<adsb_frame> a, b, out;
+        DevBuf<uint32_t> src;
+        DevBuf<uint64_t> prefix;             // [2 x (n_channels + 1)]
+    } merge;
     // tracker (allocated on first adsb_track_device): one hipMalloc carved into the five below
     DevBuf<char> trk_mem;
     uint32_t *trk_u32 = nullptr;    // 4 x [max_out]: keys, vals, sorted keys, sorted vals

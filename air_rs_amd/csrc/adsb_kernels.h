@@ -319,6 +319,42 @@ struct EsArgs {
 };
 hipError_t launch_es(hipStream_t s, const EsArgs &a);
 
+// Mode S replies from samples (adsb_replies.hip: the dispatch sequence is described there; adsb_replies.h has the text of
+// one offset and of one frame)
+constexpr uint32_t kRepliesGroupTiles = 4096; // tiles per workgroup of the two folding kernels
+constexpr uint32_t replies_groups(uint64_t n_tiles) { return (uint32_t)((n_tiles + kRepliesGroupTiles - 1) / kRepliesGroupTiles); }
+struct RepliesArgs {
+    const void *iq;              // channel 0, sample 0; 16-byte aligned
+    uint64_t n_samples;          // per channel
+    uint64_t channel_stride;     // samples, a multiple of 8
+    uint64_t offset_base;        // added to every frame's offset
+    uint32_t n_channels, tiles_per_channel, n_tiles;
+    uint32_t flags;              // ADSB_REPLIES_*
+    const uint32_t *known;       // [n_known] ascending, distinct
+    uint32_t n_known;
+    uint32_t cap;                // frames kept
+    // scratch
+    uint32_t *tile;              // [7][n_tiles]: per tile the frames kept, then the six counts of adsb_replies.h
+    uint32_t *bitmap;            // [n_tiles][256]: a tile's kept offsets, one word per thread's run; written only by a
+                                 // tile that keeps a frame
+    uint32_t *group;             // [7][replies_groups(n_tiles)]: the same seven summed over each group of tiles
+    uint64_t *prefix;            // [n_tiles + 1]: frames kept in front of each tile; last = all
+    // results
+    adsb_frame *frames;          // [cap]
+    uint64_t *counts;            // [n_channels]
+    adsb_replies_header *hdr;
+};
+hipError_t launch_replies(hipStream_t s, int sample_type, const RepliesArgs &a);
+// two per-channel-ordered lists as one (merge_lists, adsb_replies.hip)
+struct MergeArgs {
+    const adsb_frame *a, *b;     // [na], [nb]
+    const uint64_t *prefix_a, *prefix_b; // [n_channels + 1] each
+    uint32_t n_channels, na, nb;
+    adsb_frame *out;             // [na + nb]
+    uint32_t *src;               // [na + nb] or null
+};
+hipError_t launch_merge_lists(hipStream_t s, const MergeArgs &a);
+
 // transmitter positions from correlated receptions (adsb_mlat.hip; adsb_mlat.h has the solver's text)
 constexpr uint32_t kMlatBlock = 256;                          // threads per workgroup of mlat_solve
 constexpr uint32_t kMlatPerBlock = kMlatBlock / kMlatLanes;   // messages per workgroup: 16 lanes each

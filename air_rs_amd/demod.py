@@ -398,6 +398,60 @@ def es_physical(recs):
     return out
 
 
+REPLIES_HEADER_DTYPE = np.dtype([(k, "<u8") for k in ("n_out", "total_found", "n_preamble", "n_all_call", "n_df18",
+                                                      "n_address_parity", "n_not_known", "n_parity", "flags", "reserved")])
+assert REPLIES_HEADER_DTYPE.itemsize == C.sizeof(L.AdsbRepliesHeader) == 80
+REPLIES_AP = {"all": 0, "known": L.ADSB_REPLIES_AP_KNOWN}     # replies_of's `ap`: the address/parity formats kept
+
+
+def _replies_cfg(ap, max_frames, first_sample):
+    if ap not in REPLIES_AP:
+        raise ValueError(f"ap must be one of {sorted(REPLIES_AP)}, not {ap!r}")
+    return L.AdsbRepliesCfg(REPLIES_AP[ap], 0, int(max_frames), int(first_sample), 0)
+
+
+def host_replies(iq, n_channels=1, n_samples=None, channel_stride=None, known=None, ap="all", max_frames=0, first_sample=0):
+    """adsb_host_replies, the CPU mirror of AdsbDemod.replies_of: (FRAME_DTYPE frames, uint64 counts per channel, the
+    REPLIES_HEADER_DTYPE record) of the host samples `iq` (int8 or int16, [samples, 2] or flat I,Q pairs; n_channels
+    buffers of n_samples samples, channel_stride samples apart).  known: None or an ascending unique uint32 array;
+    ap: "all" or "known".  Needs no device."""
+    iq = np.ascontiguousarray(iq)
+    if iq.dtype not in (np.int8, np.int16):
+        raise ValueError("iq must be int8 or int16")
+    st = L.ADSB_SAMPLE_I8 if iq.dtype == np.int8 else L.ADSB_SAMPLE_I16
+    total = iq.size // 2
+    n_samples = total // int(n_channels) if n_samples is None else int(n_samples)
+    stride = n_samples if channel_stride is None else int(channel_stride)
+    if (int(n_channels) - 1) * stride + n_samples > total:
+        raise ValueError("iq is shorter than the channels say")
+    karr, kptr, nk = _known_list(known)
+    cfg, hdr, fn = _replies_cfg(ap, max_frames, first_sample), L.AdsbRepliesHeader(), L.load().adsb_host_replies
+    counts = np.zeros(max(int(n_channels), 1), dtype=np.uint64)
+    args = (st, C.byref(cfg), iq.ctypes.data, int(n_channels), n_samples, stride, kptr, nk)
+    L.check(fn(*args, None, 0, None, None, C.byref(hdr)), "adsb_host_replies")          # the size first
+    n = int(hdr.n_out)
+    out = np.zeros(max(n, 1), dtype=FRAME_DTYPE)
+    L.check(fn(*args, out.ctypes.data, n, None, counts.ctypes.data, C.byref(hdr)), "adsb_host_replies")
+    return out[:n].copy(), counts[:int(n_channels)].copy(), np.frombuffer(bytes(hdr), dtype=REPLIES_HEADER_DTYPE)[0]
+
+
+def host_merge_lists(a, counts_a, b, counts_b):
+    """adsb_host_merge_lists, the CPU mirror of AdsbDemod.merge_lists: two FRAME_DTYPE lists in fetch's layout (frames
+    per channel in counts_a / counts_b, each channel in ascending offset) as one -> (frames, src, counts): on equal
+    offsets a's frame first; src[k] = the index of frames[k] in its own list, ADSB_MERGE_FROM_B set for b's.  Needs no
+    device."""
+    a, aptr, na = _host_list(a, FRAME_DTYPE)
+    b, bptr, nb = _host_list(b, FRAME_DTYPE)
+    ca, cb = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1) for x in (counts_a, counts_b))
+    if len(ca) != len(cb) or int(ca.sum()) != na or int(cb.sum()) != nb:
+        raise ValueError("counts do not describe the lists")
+    out, src = np.zeros(max(na + nb, 1), dtype=FRAME_DTYPE), np.zeros(max(na + nb, 1), dtype=np.uint32)
+    counts = np.zeros(max(len(ca), 1), dtype=np.uint64)
+    L.check(L.load().adsb_host_merge_lists(aptr, ca.ctypes.data, bptr, cb.ctypes.data, len(ca), out.ctypes.data,
+                                           src.ctypes.data, counts.ctypes.data), "adsb_host_merge_lists")
+    return out[:na + nb].copy(), src[:na + nb].copy(), counts[:len(ca)].copy()
+
+
 FRAME_INTEGRITY_DTYPE = np.dtype([("rc_dm", "<u4"), ("nic", "u1"), ("version", "u1"), ("supp", "u1"), ("flags", "u1")])
 AIRCRAFT_ES_DTYPE = np.dtype([(k, ES_DTYPE) for k in ("operational_airborne", "operational_surface", "target_state",
                                                       "emergency", "acas_ra")]
@@ -1300,6 +1354,76 @@ class AdsbDemod:
         p = [C.c_void_p() for _ in range(2)]
         L.check(self._lib.adsb_es_device(self._h, *[C.byref(x) for x in p]), "adsb_es_device")
         return tuple(x.value for x in p)
+
+    def replies_of_async(self, iq, n_channels=1, n_samples=None, channel_stride=None, known=None, ap="all", max_frames=0,
+                         first_sample=0):
+        """adsb_replies_of alone: enqueues the replies scan and returns once a host known[] is copied.  iq: a device
+        pointer (then n_samples is needed) or a device tensor of I,Q pairs (data_ptr() and numel()); known: None, an
+        ascending unique uint32 array, a (device pointer, count) pair or a TrackTable; ap: "all" or "known"."""
+        if hasattr(iq, "data_ptr"):
+            if n_samples is None:
+                n_samples = int(iq.numel()) // 2 // int(n_channels)
+            iq = iq.data_ptr()
+        if n_samples is None:
+            raise ValueError("n_samples is needed with a device pointer")
+        stride = int(n_samples) if channel_stride is None else int(channel_stride)
+        karr, kptr, nk = _known_list(known)
+        cfg = _replies_cfg(ap, max_frames, first_sample)
+        L.check(self._lib.adsb_replies_of(self._h, C.byref(cfg), int(iq), int(n_channels), int(n_samples), stride, kptr, nk),
+                "adsb_replies_of")
+        self._replies_channels = int(n_channels)
+
+    def fetch_replies(self):
+        """adsb_fetch_replies: waits for the last replies_of_async() -> (FRAME_DTYPE frames, uint64 counts per channel,
+        the REPLIES_HEADER_DTYPE record)."""
+        nch, hdr = getattr(self, "_replies_channels", 1), L.AdsbRepliesHeader()
+        L.check(self._lib.adsb_fetch_replies(self._h, None, 0, None, None, C.byref(hdr)), "adsb_fetch_replies")  # the size first
+        n = int(hdr.n_out)
+        out, counts, got = np.zeros(max(n, 1), dtype=FRAME_DTYPE), np.zeros(max(nch, 1), dtype=np.uint64), C.c_size_t()
+        L.check(self._lib.adsb_fetch_replies(self._h, out.ctypes.data, n, C.byref(got), counts.ctypes.data, C.byref(hdr)),
+                "adsb_fetch_replies")
+        return out[:got.value].copy(), counts[:nch].copy(), np.frombuffer(bytes(hdr), dtype=REPLIES_HEADER_DTYPE)[0]
+
+    def replies_of(self, iq, n_channels=1, n_samples=None, channel_stride=None, known=None, ap="all", max_frames=0,
+                   first_sample=0):
+        """adsb_replies_of + adsb_fetch_replies: the Mode S replies (DF11, DF18 and the address/parity formats DF0, 4, 5,
+        16, 20, 21) in a sample buffer on the device, by the scan of include/adsb_hip.h "Mode S replies from samples" ->
+        (frames, counts, header).  The list drops into modes_of, commb_of and correlate_of; merge_lists puts it and the
+        demodulator's list into one.  See replies_of_async."""
+        self.replies_of_async(iq, n_channels, n_samples, channel_stride, known, ap, max_frames, first_sample)
+        return self.fetch_replies()
+
+    def replies_device(self):
+        """adsb_replies_device: device addresses (frames, counts, header); no synchronisation."""
+        p = [C.c_void_p() for _ in range(3)]
+        L.check(self._lib.adsb_replies_device(self._h, *[C.byref(x) for x in p]), "adsb_replies_device")
+        return tuple(x.value for x in p)
+
+    def merge_lists(self, a, counts_a, b, counts_b):
+        """adsb_merge_lists_of: two lists in fetch's layout as one, on the device -> (frames, src, counts); see
+        host_merge_lists.  a, b: FRAME_DTYPE arrays (host) or (device pointer, count) pairs; counts_a, counts_b: frames
+        per channel (host)."""
+        ca, cb = (np.ascontiguousarray(x, dtype=np.uint64).reshape(-1) for x in (counts_a, counts_b))
+        if len(ca) != len(cb):
+            raise ValueError("counts_a and counts_b differ in length")
+        ptr = []
+        for lst, cnt in ((a, ca), (b, cb)):
+            if isinstance(lst, tuple):
+                arr, p, n = None, (int(lst[0]) if int(lst[1]) else None), int(lst[1])
+            else:
+                arr, p, n = _host_list(lst, FRAME_DTYPE)
+            if n != int(cnt.sum()):
+                raise ValueError("counts do not describe the lists")
+            ptr.append((arr, p, n))
+        n = ptr[0][2] + ptr[1][2]
+        out, src = np.zeros(max(n, 1), dtype=FRAME_DTYPE), np.zeros(max(n, 1), dtype=np.uint32)
+        counts = np.zeros(max(len(ca), 1), dtype=np.uint64)
+        L.check(self._lib.adsb_merge_lists_of(self._h, ptr[0][1], ca.ctypes.data, ptr[1][1], cb.ctypes.data, len(ca),
+                                              out.ctypes.data, src.ctypes.data, counts.ctypes.data), "adsb_merge_lists_of")
+        return out[:n].copy(), src[:n].copy(), counts[:len(ca)].copy()
+
+    host_replies = staticmethod(host_replies)
+    host_merge_lists = staticmethod(host_merge_lists)
 
     def correlate_async(self, window, sample_base=None, levels=False):
         """adsb_correlate_launch alone: the last launch's list, channel k as receiver k, correlated on the device.

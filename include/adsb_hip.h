@@ -898,6 +898,101 @@ int adsb_es_device(adsb_ctx *ctx, const adsb_es_rec **recs_dev, const void **hea
 int adsb_debug_es_geometry(uint32_t *threads_per_block);
 
 /*
+ * Mode S replies from samples: a second scan of the sample buffer, beside the demodulator's, that finds the replies of
+ * transponders without ADS-B (DF11 all-call, DF4/5/20/21 surveillance and Comm-B, DF0/16 air-air) and DF18.  The
+ * demodulator keeps the reference's gate (preamble and the DF17 ordering test) and its list does not change; this scan
+ * is opt-in, has a definition of its own (the reference has none) and never emits DF17.  Computed on the device; the
+ * list is in adsb_fetch's layout and drops into adsb_modes_of, adsb_commb_of, adsb_correlate_of and
+ * adsb_track_table_update_modes unchanged; adsb_merge_lists_of puts it and the demodulator's list into one.
+ *   DEFINITION  On sample power, not on the floored magnitude: exact in integers, and no root.
+ *     p[k]    = I[k]^2 + Q[k]^2      (ADSB_SAMPLE_I8: <= 32768; ADSB_SAMPLE_I16: <= 2^31, from (-32768, -32768); uint32)
+ *     pre(i)  = min p[i+{0,2,7,9}] > max p[i+{1,3,4,5,6,8,10,11,12,13,14,15}]
+ *               STRICT: a tie fails, so constant and all-zero input give nothing.
+ *     bit_k   = p[i+16+2k] > p[i+17+2k], MSB first; a tie gives 0.
+ *     DF      = bits 0..4;  L = 56 bits for DF < 16, 112 otherwise.
+ *     WINDOW  offset i of a channel is examined iff i + 26 <= n_samples (the DF can be read), and can be emitted iff
+ *             i + 16 + 2 L <= n_samples.  Short frames in the last 240 samples ARE found.  No window crosses a channel
+ *             edge: every channel is a buffer of its own.
+ *     S       = crc24(first L - 24 bits) ^ last 24 bits, generator 0x1FFF409.
+ *     ACCEPT  DF11 iff S < 128 (a reply to interrogator S; adsb_modes_of's own rule).
+ *             DF18 iff S == 0 (no repair here).
+ *             DF0, 4, 5, 16, 20, 21 (address/parity, address = S): always; with ADSB_REPLIES_AP_KNOWN iff S is in
+ *             known[].
+ *             Every other DF, DF17 and DF24..31 included: never.  (DF24..31, first two bits 11, is a quarter of all
+ *             noise candidates and is left out on purpose.)
+ *     EMIT    per channel in ascending offset; every offset is independent of every other (nothing is skipped behind a
+ *             frame); frame.offset = cfg.first_sample_index + i.  A frame has wire input's short-frame convention:
+ *             bytes[0..7) the message and bytes[7..14) = 0 for a 56-bit frame; status = 0 and fixed_bit = 0xFF.
+ *   KNOWN  known[n_known] is ascending, distinct and < 2^24, host or device memory: adsb_modes_of's known_out, or a
+ *     table's ICAOs (a host array that breaks this is ADSB_E_ARG; for a device array it is an unchecked input
+ *     contract).  The filter is WHOLE-CALL, NOT CAUSAL: an address first heard as DF11 in this very buffer is not yet
+ *     known to the filter.  Without the filter every address/parity candidate is emitted and adsb_modes_of decides,
+ *     causally, as it does for wire input; pure noise then yields about one frame per 10 000 offsets.
+ *   RESULT  EXACT: every accepted frame is in the list, however many a tile holds, up to the capacity; there is no
+ *     per-tile quota and no host re-run.  Capacity = cfg.max_frames, 0 meaning the ctx's cfg.max_out.  Past it the first
+ *     frames in order are kept, header.flags has ADSB_FLAG_TRUNCATED, counts[] (frames per channel) are clipped to the
+ *     list and total_found is the full number, as for wire input.
+ *   HEADER  n_out frames in the list; total_found = n_all_call + n_df18 + n_address_parity, the accepted frames of each
+ *     sort; n_preamble the examined offsets with pre(i); n_not_known the address/parity frames the filter turned away;
+ *     n_parity the DF11 / DF18 candidates whose check failed.  The last four count only candidates that can be emitted
+ *     (the window rule), n_preamble all that are examined.  flags = ADSB_FLAG_*; reserved = 0.
+ * Nothing depends on atomics or scheduling: two runs give the same bytes.
+ * MERGE  adsb_merge_lists_of merges two lists in adsb_fetch's layout with the same n_channels, each channel's frames
+ *   in ascending offset, into one such list: out has counts_a[c] + counts_b[c] = counts_out[c] frames of channel c, in
+ *   ascending offset; on equal offsets list A's frame goes first; frames of one list keep their order.  src[k] = the
+ *   index of out[k] in its own list, with the top bit (ADSB_MERGE_FROM_B) set for list B, so a caller can carry side
+ *   arrays such as level records along.
+ */
+#define ADSB_REPLIES_AP_KNOWN 0x1u
+#define ADSB_MERGE_FROM_B 0x80000000u
+typedef struct adsb_replies_cfg {      /* 32 bytes */
+    uint32_t flags;               /* ADSB_REPLIES_AP_KNOWN or 0                                        */
+    uint32_t reserved;            /* 0 */
+    uint64_t max_frames;          /* 0: cfg.max_out of the ctx                                         */
+    uint64_t first_sample_index;  /* added to every offset, every channel                              */
+    uint64_t reserved2;           /* 0 */
+} adsb_replies_cfg;
+typedef struct adsb_replies_header {   /* 80 bytes */
+    uint64_t n_out, total_found, n_preamble, n_all_call, n_df18, n_address_parity, n_not_known, n_parity, flags, reserved;
+} adsb_replies_header;
+#ifdef __cplusplus
+static_assert(sizeof(adsb_replies_cfg) == 32 && sizeof(adsb_replies_header) == 80, "adsb_replies_cfg / adsb_replies_header layout");
+#endif
+/* Scans.  iq_dev, n_channels, n_samples and channel_stride as for adsb_demod_device_async (samples of the ctx's
+ * sample_type in device memory, 16-byte aligned, channel_stride a multiple of 8 and >= n_samples when n_channels > 1);
+ * known in host or device memory.  Asynchronous on the ctx's stream once a host known[] is copied; reads the samples
+ * only, so it may follow or precede a launch on the same buffer.  Buffers are allocated on first use and grown when
+ * needed (may wait for earlier work): 24 bytes per frame of capacity, and per tile of 8192 (i8) or 4096 (CS16) offsets
+ * 1 KiB of bitmap and 36 bytes of counts; a ctx that never calls it allocates nothing and launches exactly the kernels
+ * it launched before.  Replaces the result of an earlier call.  Not for use while a feed is open: a feed's consumer has
+ * the host buffer and adsb_host_replies.  ADSB_E_ARG for a NULL ctx, cfg or iq_dev, n_channels == 0, unknown flags or
+ * non-zero reserved words, a misaligned iq_dev or stride, a stride below n_samples, NULL known with n_known > 0,
+ * n_known > 2^24, or a host known[] that is not ascending, distinct and < 2^24; ADSB_E_SHORT for n_samples < 26;
+ * ADSB_E_CAPACITY for n_channels or n_samples above the ctx's, or max_frames >= 2^32.  A rejected call writes nothing
+ * and leaves an earlier result as it was. */
+int adsb_replies_of(adsb_ctx *ctx, const adsb_replies_cfg *cfg, const void *iq_dev, uint32_t n_channels, size_t n_samples,
+                    size_t channel_stride, const uint32_t *known, size_t n_known);
+/* Waits and copies; each output may be NULL.  out receives min(header.n_out, max_out) frames and *n_out that number;
+ * counts the call's n_channels entries (clipped to the list of header.n_out frames, not to max_out); *header the totals,
+ * whatever the capacity.  ADSB_E_STATE before any adsb_replies_of; ADSB_E_ARG for a NULL ctx or NULL out with a
+ * capacity. */
+int adsb_fetch_replies(adsb_ctx *ctx, adsb_frame *out, size_t max_out, size_t *n_out, uint64_t *counts,
+                       adsb_replies_header *header);
+/* For device-side consumers; does not synchronise.  The list, the per-channel counts and the header of the last
+ * adsb_replies_of in device memory (each optional), valid until the next call and ordered on the ctx's stream behind
+ * it.  ADSB_E_STATE before any adsb_replies_of. */
+int adsb_replies_device(adsb_ctx *ctx, const adsb_frame **frames_dev, const uint64_t **counts_dev, const void **header_dev);
+/* Offsets per tile (= per workgroup) of the scan for each sample type (either may be NULL): the sizes at which the scan
+ * takes another path, for tests.  The result does not depend on them. */
+int adsb_debug_replies_geometry(uint32_t *tile_offsets_i8, uint32_t *tile_offsets_i16);
+/* MERGE above.  a, b, counts_a, counts_b, out, src and counts_out each in host memory or in device memory of the ctx's
+ * device; out and src hold the sum of all counts, counts_out n_channels entries; src and counts_out may be NULL.
+ * Blocking.  ADSB_E_ARG for a NULL ctx, NULL counts, n_channels outside 1..2^20, or a NULL list or out with frames to
+ * read or write; ADSB_E_CAPACITY for 2^31 frames or more in either list. */
+int adsb_merge_lists_of(adsb_ctx *ctx, const adsb_frame *a, const uint64_t *counts_a, const adsb_frame *b,
+                        const uint64_t *counts_b, uint32_t n_channels, adsb_frame *out, uint32_t *src, uint64_t *counts_out);
+
+/*
  * Multilaterate: where each correlated message was sent from, solved from the times its receivers heard it.  One small
  * non-linear least-squares problem per message, all messages of a list in one kernel; f64; stateless.
  *   INPUT  a correlate result msgs[M] / recs[N]; adsb_mlat_receiver receivers[R], 1 <= R <= 256, WGS84 degrees and

@@ -205,6 +205,23 @@ int adsb_host_es(const adsb_frame *frames, size_t n, adsb_es_rec *recs, adsb_es_
 int adsb_host_es_integrity(uint32_t tc, uint32_t version, uint32_t supp, uint32_t *nic, uint32_t *rc_dm);
 
 /*
+ * CPU mirror of adsb_replies_of + adsb_fetch_replies (adsb_hip.h, "Mode S replies from samples"): the same list, counts
+ * and header from the same program text as the device's, on one core, no device needed.  iq is HOST memory of
+ * n_channels buffers of n_samples interleaved samples of sample_type, channel_stride samples apart (any alignment;
+ * ignored for one channel); known host memory.  out (may be NULL with max_out 0) receives min(header.n_out, max_out)
+ * frames and *n_out (optional) that number; counts[n_channels] and *header are optional.  The capacity cfg.max_frames =
+ * 0 stands for is unbounded here (there is no ctx).  What a feed's consumer, who holds the host buffer, uses.  The same
+ * argument errors as adsb_replies_of but for alignment and the ctx's sizes; ADSB_E_ARG also for a bad sample_type or
+ * NULL out with max_out > 0.
+ * merge_lists mirrors adsb_merge_lists_of: all arrays host memory; src and counts_out may be NULL.
+ */
+int adsb_host_replies(int sample_type, const adsb_replies_cfg *cfg, const void *iq, uint32_t n_channels, size_t n_samples,
+                      size_t channel_stride, const uint32_t *known, size_t n_known, adsb_frame *out, size_t max_out,
+                      size_t *n_out, uint64_t *counts, adsb_replies_header *header);
+int adsb_host_merge_lists(const adsb_frame *a, const uint64_t *counts_a, const adsb_frame *b, const uint64_t *counts_b,
+                          uint32_t n_channels, adsb_frame *out, uint32_t *src, uint64_t *counts_out);
+
+/*
  * CPU mirror of adsb_multilaterate_of (adsb_hip.h, "Multilaterate"): the same fixes and header from the same program text
  * as the device's -- the solver, and the 16 partial sums of every sum over receptions folded in the same butterfly -- on
  * one core, no device needed.  All arrays host memory; rx / n_rx may be NULL / 0 with ADSB_MLAT_TIME_RECEPTION; fixes

@@ -16,6 +16,7 @@
   tools/replay.py out.txt --avr-in            # ... an AVR text capture, "*" and "@" lines alike
   tools/replay.py out.txt --avr-in --modes --commb   # one line per frame; DF20/21 lines with their Comm-B register
   tools/replay.py out.txt --avr-in --es       # one line per DF17/18 frame: what it says about the aircraft's status
+  tools/replay.py capture.bin --replies --modes      # the packets and the Mode S replies found in the samples, one list
 
 Everything below the argument parsing is one call through the C ABI (adsb_replay_file, include/adsb_host.h).
 The "Processed Time" line carries no value (the reference prints the wall clock there).  With --aircraft, the frames
@@ -71,6 +72,12 @@ its newest position message, resolved with the version and the NIC supplements t
 status messages (a "?" behind both where no version was known when that message was heard: Rc is then what the type
 code alone gives), NACp and SIL of the newest operational status or target state message, Emerg and Squawk(ES) of the
 newest TC 28 message, and SelAlt, the selected altitude in feet.
+With --replies (on samples) the whole capture goes to device memory once: the demodulator's launch gives the DF17 list as
+ever, the replies scan (adsb_replies_of: DF11, DF18 and the address/parity formats DF0/4/5/16/20/21, by a preamble and
+parity rule of its own on sample power) gives a second list from the same samples, and the two are merged on the device
+(adsb_merge_lists_of).  One line per frame: time in seconds, offset, "demod" or "replies", DF and the message in hex.
+With --replies --modes the merged list goes through adsb_modes_of and --modes' lines are printed; with --replies --modes
+--aircraft the table keyed by the resolved addresses.  No chunking here: offsets are positions in the capture.
 The TEXT has not been compared with a Rust build's (there is no
 Rust toolchain); only the values are checked, against the oracle."""
 import argparse
@@ -376,6 +383,38 @@ def modes_lines(frames, recs, commb=None):
     return "".join(out)
 
 
+def replies_lines(frames, src):
+    """--replies: one line per frame of the merged list: time in seconds, offset, where it comes from ("demod": the
+    demodulator's DF17 list, "replies": the replies scan), DF, and the message in hex, 14 digits for a 56-bit frame."""
+    out = []
+    for f, s in zip(frames, src):
+        df = int(f["bytes"][0]) >> 3
+        msg = f["bytes"][:7 if df < 16 else 14].tobytes().hex().upper()
+        out.append(f"{int(f['offset']) * SECONDS_PER_SAMPLE:.6f} {int(f['offset'])} "
+                   f"{'replies' if int(s) & A.ADSB_MERGE_FROM_B else 'demod'} DF{df} {msg}\n")
+    return "".join(out)
+
+
+def replies_run(device, st, iq):
+    """--replies: the demodulator's launch and the replies scan over the whole capture in device memory, merged on the
+    device -> (the context, which the caller closes; merged frames; src)"""
+    import numpy as np
+    import torch
+    n = len(iq)
+    d = A.AdsbDemod(device=device, sample_type=st, max_samples=max(n, A.WINDOW), max_out=max(n // 100, 1 << 16), host_staging=False)
+    dev = torch.from_numpy(np.ascontiguousarray(iq)).to(f"cuda:{device}")
+    found = np.zeros(0, dtype=A.FRAME_DTYPE)
+    if n >= A.WINDOW:
+        d.demod_device_async(dev.data_ptr(), n)
+        found = d.fetch()[0]
+    replies, _, hdr = d.replies_of(dev.data_ptr(), n_samples=n)
+    if int(hdr["flags"]) & A.ADSB_FLAG_TRUNCATED:
+        print(f"replies scan: {int(hdr['total_found'])} frames found, {len(replies)} kept", file=sys.stderr)
+    frames, src, _ = d.merge_lists(found, [len(found)], replies, [len(replies)])
+    del dev
+    return d, frames, src
+
+
 def read_wire(d, path, wire_format, tick_bias, chunk=WIRE_IN_CHUNK, modes=False, commb=False):
     """--beast-in / --avr-in: (frames, their level records) of a Beast or AVR capture, parsed on the device chunk by
     chunk; what a chunk leaves unparsed (an incomplete last frame) goes in front of the next.  modes: short frames too,
@@ -459,6 +498,10 @@ def main():
                     help="print one line per DF17/18 frame instead: its extended squitter status (category, emergency, target "
                          "state, operational status, NACv, NIC supplement B, stand-alone Rc); with --aircraft: eight more "
                          "columns from the aircraft's extended squitter status, NIC and Rc resolved per aircraft")
+    ap.add_argument("--replies", action="store_true",
+                    help="on samples: also run the replies scan (DF11, DF18, DF0/4/5/16/20/21 from the samples), merge its list "
+                         "with the packets and print one line per frame; with --modes: address and kind per frame; with "
+                         "--modes --aircraft: the table keyed by those addresses")
     ap.add_argument("--tick-bias", type=int, default=0, metavar="N", help="added to every timestamp (12 MHz ticks, < 2^48)")
     a = ap.parse_args()
     if a.mlat and not a.avr:
@@ -470,8 +513,10 @@ def main():
     if a.beast_in and a.avr_in:
         ap.error("--beast-in and --avr-in exclude each other")
     wire_in = "beast" if a.beast_in else "avr" if a.avr_in else None
-    if a.modes and not wire_in:
-        ap.error("--modes needs --beast-in or --avr-in")
+    if a.replies and (wire_in or a.web or a.levels or a.es or a.commb or a.site or a.beast or a.avr or (a.aircraft and not a.modes)):
+        ap.error("--replies works on samples and goes with --modes and --modes --aircraft only")
+    if a.modes and not wire_in and not a.replies:
+        ap.error("--modes needs --beast-in, --avr-in or --replies")
     if a.commb and not a.modes:
         ap.error("--commb needs --modes")
     if wire_in and a.levels and not a.aircraft:
@@ -481,6 +526,18 @@ def main():
     fmt = a.format or ("c16" if a.file.endswith(".c16") else "u8")
     st = A.ADSB_SAMPLE_I16 if fmt == "c16" else A.ADSB_SAMPLE_I8
     n_max = os.path.getsize(a.file) // (4 if fmt == "c16" else 2)
+    if a.replies:
+        d, frames, src = replies_run(a.device, st, read_capture(a.file, fmt))
+        with d:
+            if a.modes:
+                recs = d.modes_of(frames)[0]
+                sys.stdout.write(aircraft_table(d, frames, n_max, modes=recs) if a.aircraft else modes_lines(frames, recs))
+            else:
+                sys.stdout.write(replies_lines(frames, src))
+        if a.summary:
+            n_replies = int(sum(1 for s in src if int(s) & A.ADSB_MERGE_FROM_B))
+            print(f"{n_max} samples, {len(frames) - n_replies} packets, {n_replies} replies", file=sys.stderr)
+        return
     with A.AdsbDemod(device=a.device, sample_type=st, max_samples=a.chunk + 240, max_out=a.chunk + 240,
                      host_staging=False) as d:
         if wire_in and a.modes:
