@@ -242,3 +242,395 @@ def merge_cases():
             ("list b empty", fl([4, 1], 0), [1, 1], fl([], 100), [0, 0]),
             ("both empty", fl([], 0), [0], fl([], 100), [0]),
             ("many frames with ties", fl(big_a, 0), [700, 300], fl(big_b, 2000), [10, 900])]
+
+
+# ---- the text only the device compiles -------------------------------------------------------------------------------
+# Cases for what adsb_replies.hip has and the mirror has not: several candidates and several kept frames in one thread's
+# run (one bitmap word), the sample-by-sample load of a ragged end, the last examined offset, the order in which
+# workgroups take tiles, more channels than a workgroup has threads, every offset of a tile, and the capacity inside a
+# word.  They are kept out of all_cases (its parametrised ids stay) and are built on demand, by name: the names need
+# no building.  Every buffer ends in TAIL full-scale samples behind the last channel, as the gaps between channels
+# hold: a read past a channel's end changes a result and stays inside the buffer.
+TAIL = 256
+AMPS = (120, 40, 12)                      # a group's members, each wholly weaker than the one before (I component)
+_BUILT, _MODELS, _SHARED = {}, {}, {}
+
+
+def run(dtype):
+    """offsets per thread of the scan: one word of a tile's bitmap"""
+    return tile(dtype) // 256
+
+
+def stage(dtype, n, n_channels=1, stride=None, seed=None):
+    """n_channels channels of n samples, zeros or (seed) low noise, stride apart; the gaps and TAIL samples behind the
+    last channel are full-scale -> (the flat buffer, a view per channel)"""
+    stride = n if stride is None else stride
+    buf = np.full(((n_channels - 1) * stride + n + TAIL, 2), np.iinfo(dtype).min, dtype=dtype)
+    views = []
+    for c in range(n_channels):
+        views.append(buf[c * stride:c * stride + n])
+        views[c][:] = 0 if seed is None else M.noise(n, dtype, seed + c, LOW)
+    return buf, views
+
+
+def up8(n):
+    return (n + 7) & ~7
+
+
+def plant_preamble(iq, at, amp=100):
+    """the four pulses of a preamble and nothing else"""
+    for s in M.PULSES:
+        iq[at + s] = (amp, 0)
+
+
+def plant_group(iq, at, k, members):
+    """`members` bare preambles k samples apart (10 <= k), the weaker written first and the stronger over them: on a zero
+    background every one passes the strict test, reads its DF from its successor's pulses and is an address/parity
+    candidate -> the members' offsets"""
+    for m in reversed(range(members)):
+        plant_preamble(iq, at + m * k, AMPS[m])
+    return [at + m * k for m in range(members)]
+
+
+def render_all(iq, msgs, offsets, pulse=(100, 0)):
+    """M.render for many messages at once"""
+    where = np.array([s for msg, at in zip(msgs, offsets) for s in M.pulse_positions(msg, at)], dtype=np.int64)
+    iq[where[where < len(iq)]] = pulse
+    return iq
+
+
+def _shared(key, make):
+    if key not in _SHARED:
+        _SHARED[key] = make()
+    return _SHARED[key]
+
+
+# a. crowded runs
+def _crowded(dt):
+    """groups of two or three kept frames in one run: in the middle of a tile, pairs 10 and 12 apart, in the last run of
+    waves 0, 1 and 2, two in one wave, in the last run of a tile with the last member at the tile's last offset (its
+    long frames' halo is the next tile, which has groups of its own inside those frames), and at a tile's start"""
+    T, R = tile(dt), run(dt)
+    m3 = 3 if R == 32 else 2                 # members 14 apart that one run holds
+    end = R - 1 - 14 * (m3 - 1)              # a group's first place when its last member is the run's last offset
+    plan = [(0, 100, 0, 14, m3), (0, 40, 5, 10, 2), (0, 45, 3, 12, 2), (0, 63, end, 14, m3), (0, 127, end, 14, m3),
+            (0, 191, end, 14, m3), (1, 70, 0, 14, m3), (1, 75, 2, 10, 2), (1, 255, end, 14, m3), (2, 32 // R, 0, 14, m3),
+            (2, 96 // R, 0, 12, 2)]
+    n = 3 * T + 777
+    buf, views = stage(dt, n)
+    groups = [plant_group(views[0], t * T + thread * R + place, k, m) for t, thread, place, k, m in plan]
+    assert all(len({o // R for o in g}) == 1 for g in groups)
+    c = case("crowded runs", buf, 1, n, n, [(0, o) for g in groups for o in g])
+    c["groups"] = groups
+    return c
+
+
+def crowded_members(dtype):
+    """per planted group of "crowded runs": (offset, the syndrome the model reports for it, None if it is not kept)"""
+    dt = np.dtype(dtype)
+    frames = device_text_model(dt, "crowded runs")[0]
+    syn = {int(f["offset"]): MM.syndrome(bytes(f["bytes"])) for f in frames}
+    return [[(o, syn.get(o)) for o in g] for g in device_text_case(dt, "crowded runs")["groups"]]
+
+
+WHICH = {"first": 0, "middle": 1, "last": -1}
+
+
+def _which(dt):
+    return ("first", "middle", "last") if run(dt) == 32 else ("first", "last")
+
+
+def _chosen(dt, which):
+    """the syndromes of the chosen member of every group whose members differ in theirs (the pairs of two DF0 of zeros do
+    not; the middle one: of groups of three), and of all the other members"""
+    chosen, others = set(), set()
+    for g in crowded_members(dt):
+        distinct = len({s for _, s in g}) == len(g) and not (which == "middle" and len(g) < 3)
+        pick = g[WHICH[which]] if distinct else None
+        for member in g:
+            if member[1] is not None:
+                (chosen if member is pick else others).add(member[1])
+    return chosen, others
+
+
+def _crowded_known(dt, which, kept):
+    base = device_text_case(dt, "crowded runs")
+    chosen, others = _chosen(dt, which)
+    known = np.array(sorted(chosen if kept else others - chosen), dtype=np.uint32)
+    inside = set(known.tolist())
+    members = [m for g in crowded_members(dt) for m in g]
+    c = case(_known_name(which, kept), base["iq"], 1, base["n_samples"], base["n_samples"],
+             [(0, o) for o, s in members if s in inside], [(0, o) for o, s in members if s not in inside], known=known, ap="known")
+    c["groups"], c["which"], c["kept"] = base["groups"], which, kept
+    return c
+
+
+def _known_name(which, kept):
+    return f"crowded runs, {'only' if kept else 'all but'} the {which} members known"
+
+
+def crowded_cuts(dtype):
+    """name -> max_frames: the whole list, one less, after the first and the second member of the word in the middle of
+    tile 0, after the first member of the word that ends tile 1, and on the first frame of tile 1"""
+    dt = np.dtype(dtype)
+    T = tile(dt)
+    offsets = device_text_model(dt, "crowded runs")[0]["offset"].tolist()
+    groups = device_text_case(dt, "crowded runs")["groups"]
+    return {"the total": len(offsets), "the total less one": len(offsets) - 1,
+            "after a word's first member": offsets.index(groups[0][0]) + 1,
+            "after a word's second member": offsets.index(groups[0][0]) + 2,
+            "inside a tile's last word": offsets.index(groups[8][0]) + 1,
+            "on a tile's first frame": next(k for k, o in enumerate(offsets) if o >= T) + 1}
+
+
+CUTS = ("the total", "the total less one", "after a word's first member", "after a word's second member",
+        "inside a tile's last word", "on a tile's first frame")
+
+
+def _crowded_cut(dt, cut):
+    base = device_text_case(dt, "crowded runs")
+    return case(f"crowded runs, the capacity {cut}", base["iq"], 1, base["n_samples"], base["n_samples"],
+                max_frames=crowded_cuts(dt)[cut])
+
+
+# b. ragged ends
+RAGGED_KINDS = (11, 18, 4, 20)
+
+
+def ragged_lengths(dtype):
+    T = tile(dtype)
+    return [2 * T + 496 + r for r in range(1, 8)] if np.dtype(dtype) == np.int8 else [2 * T + 500 + r for r in range(1, 4)]
+
+
+def _ragged(dt, n, past):
+    """one frame per channel at the last offset it fits (past = 0) or one behind it; DF11 and DF18 are kept by their last
+    24 bits, DF4 and DF20 by theirs under the known filter: the scan decides from the powers it loaded sample by sample,
+    whatever the list is sliced from afterwards"""
+    r = n % 8
+    stride = up8(n)
+    buf, views = stage(dt, n, len(RAGGED_KINDS), stride, seed=400 + 10 * r)
+    where, known = [], []
+    for c, df in enumerate(RAGGED_KINDS):
+        at = n - span(df) + past
+        k = 5 * r + 3 * c + 1
+        if c % 2:                          # DF18 and DF20 end in 1111: a first half that reads its neighbour's power is a 0
+            k = next(j for j in range(k, k + 4096) if message(df, AA + 16 * r + c, j)[-1] & 0xF == 0xF)
+        M.render(views[c], message(df, AA + 16 * r + c, k), at)
+        where.append((c, at))
+        if df in M.ADDRESS_PARITY:
+            known.append(AA + 16 * r + c)
+    return case(_ragged_name(n, past, dt), buf, len(RAGGED_KINDS), n, stride, () if past else where, where if past else (),
+                known=np.array(sorted(known), dtype=np.uint32), ap="known")
+
+
+def _ragged_name(n, past, dt):
+    return f"a ragged end, n = 2T+{n - 2 * tile(dt)}, the frames at the last offset" + (" + 1" if past else "")
+
+
+SHORT_LENGTHS = (26, 27, span(11), span(11) + 1, span(20), span(20) + 1)
+
+
+def _short(dt, n):
+    """three touching channels of n samples with a DF11, a DF20 and a DF4 at the last offset each fits, or, if it does
+    not fit, at the last examined offset (counted, not kept)"""
+    stride = up8(n)
+    buf, views = stage(dt, n, 3, stride)
+    present, absent = [], []
+    for c, df in enumerate((11, 20, 4)):
+        fits = n >= span(df)
+        at = n - span(df) if fits else n - 26
+        M.render(views[c], message(df, AA + c, n + c), at)
+        (present if fits else absent).append((c, at))
+    return case(f"three channels of {n} samples", buf, 3, n, stride, present, absent)
+
+
+# c. the window rule
+def window_lengths(dtype):
+    T = tile(dtype)
+    return {"26": 26, "27": 27, "T+25": T + 25, "T+26": T + 26, "T+29": T + 29, "2T+28": 2 * T + 28}
+
+
+def _window(dt, label, back, n_channels):
+    """a bare preamble at n - back in every channel: n - 26 is the last examined offset (counted, no frame fits), n - 25
+    is not examined"""
+    n = window_lengths(dt)[label]
+    stride = up8(n)
+    buf, views = stage(dt, n, n_channels, stride)
+    for v in views:
+        plant_preamble(v, n - back)
+    c = case(_window_name(label, back, n_channels), buf, n_channels, n, stride, (), [(ch, n - back) for ch in range(n_channels)])
+    c["n_preamble"] = n_channels if back == 26 else 0
+    return c
+
+
+def _window_name(label, back, n_channels):
+    return f"a bare preamble at n-{back}, n = {label}, {n_channels} channel" + ("s" if n_channels > 1 else "")
+
+
+# d. every tile
+def _tiles(dt, n_channels, tiles):
+    """one short frame in every tile of every channel, at a place of its own; the last tile examines T offsets"""
+    T = tile(dt)
+    n = tiles * T + 25
+    stride = up8(n)
+    buf, views = stage(dt, n, n_channels, stride, seed=500 + tiles)
+    present = []
+    for ch in range(n_channels):
+        for i in range(tiles):
+            k = i + tiles * ch
+            at = i * T + (37 + 1201 * k) % (T - 128)
+            M.render(views[ch], message((11, 4, 5, 0)[k % 4], AA + k, k), at)
+            present.append((ch, at))
+    c = case(_tiles_name(n_channels, tiles), buf, n_channels, n, stride, present)
+    c["zeros_first"] = True                # the GPU tier runs zeros of this length first: nothing stale stands in
+    return c
+
+
+def _tiles_name(n_channels, tiles):
+    return f"a frame in every tile, {n_channels} x {tiles}"
+
+
+TILES = [(1, k) for k in range(1, 18)] + [(3, 5), (8, 3)]
+
+
+# e. many short channels
+MANY = 300
+
+
+def _many_136(dt):
+    """300 touching channels of 136 samples, a short frame in channel c at offset c % 17: up to 8 it fits, from 9 on it runs
+    into the next channel (absent, counted as a preamble).  The eight samples that channel 16, 33, ... spill are in the
+    gaps of the next channel's preamble at offset 0, which therefore is none."""
+    n = 136
+    buf, _ = stage(dt, n, MANY, n)
+    present, absent = [], []
+    for c in range(MANY):
+        M.render(buf, message((11, 4, 5, 0)[c % 4], AA + c, c), c * n + c % 17)
+        fits = c % 17 <= 8 and not (c % 17 == 0 and c > 0)
+        (present if fits else absent).append((c, c % 17))
+    c = case("300 channels of 136 samples", buf, MANY, n, n, present, absent)
+    c["n_preamble"] = MANY - len([k for k in range(1, MANY) if k % 17 == 0])
+    return c
+
+
+def _many_26(dt):
+    """300 channels of 26 samples: one examined offset per tile; a bare preamble in two channels of three"""
+    buf, views = stage(dt, 26, MANY, 32)
+    marked = [c for c in range(MANY) if c % 3]
+    for c in marked:
+        plant_preamble(views[c], 0)
+    c = case("300 channels of 26 samples", buf, MANY, 26, 32, (), [(ch, 0) for ch in marked])
+    c["n_preamble"] = len(marked)
+    return c
+
+
+# f. every in-tile offset
+OFFSETS = {"short": (129, (11, 4, 5, 0)), "long": (241, (16, 18, 20, 21))}
+
+
+def _offsets_buffer(dt, kind):
+    def make():
+        T = tile(dt)
+        step, dfs = OFFSETS[kind]
+        n = step * T
+        buf, views = stage(dt, n, seed=600)
+        offsets = [k * step for k in range(T)]
+        render_all(views[0], [message(dfs[k % 4], AA + k, k) for k in range(T)], offsets)
+        return buf, n, offsets
+    return _shared(("offsets", dt.name, kind), make)
+
+
+def _offsets(dt, kind, filtered):
+    """T frames whose starts take every residue mod T once (the step is odd); with the filter, the even-indexed addresses
+    are known: DF11 and DF18 stay, every second address/parity frame goes"""
+    buf, n, offsets = _offsets_buffer(dt, kind)
+    dfs = OFFSETS[kind][1]
+    if not filtered:
+        return case(_offsets_name(kind, filtered), buf, 1, n, n, [(0, o) for o in offsets])
+    stays = [dfs[k % 4] in (11, 18) or k % 2 == 0 for k in range(len(offsets))]
+    return case(_offsets_name(kind, filtered), buf, 1, n, n, [(0, o) for o, s in zip(offsets, stays) if s],
+                [(0, o) for o, s in zip(offsets, stays) if not s],
+                known=np.arange(AA, AA + len(offsets), 2, dtype=np.uint32), ap="known")
+
+
+def _offsets_name(kind, filtered):
+    return f"every in-tile offset, {kind} frames" + (", the even addresses known" if filtered else "")
+
+
+FAMILIES = ("crowded", "ragged", "window", "tiles", "channels", "offsets")
+
+
+def _plan(dtype):
+    """(family, name, builder) of every case, in order; nothing is built here"""
+    dt = np.dtype(dtype)
+    plan = [("crowded", "crowded runs", lambda: _crowded(dt))]
+    for which in _which(dt):
+        for kept in (True, False):
+            plan.append(("crowded", _known_name(which, kept), lambda which=which, kept=kept: _crowded_known(dt, which, kept)))
+    for cut in CUTS:
+        plan.append(("crowded", f"crowded runs, the capacity {cut}", lambda cut=cut: _crowded_cut(dt, cut)))
+    for n in ragged_lengths(dt):
+        for past in (0, 1):
+            plan.append(("ragged", _ragged_name(n, past, dt), lambda n=n, past=past: _ragged(dt, n, past)))
+    for n in SHORT_LENGTHS:
+        plan.append(("ragged", f"three channels of {n} samples", lambda n=n: _short(dt, n)))
+    for n_channels in (1, 3):
+        for label in window_lengths(dt):
+            for back in (26, 25):
+                plan.append(("window", _window_name(label, back, n_channels),
+                             lambda label=label, back=back, n_channels=n_channels: _window(dt, label, back, n_channels)))
+    for n_channels, tiles in TILES:
+        plan.append(("tiles", _tiles_name(n_channels, tiles), lambda n_channels=n_channels, tiles=tiles: _tiles(dt, n_channels, tiles)))
+    plan.append(("channels", "300 channels of 136 samples", lambda: _many_136(dt)))
+    plan.append(("channels", "300 channels of 26 samples", lambda: _many_26(dt)))
+    for kind in OFFSETS:
+        for filtered in (False, True):
+            plan.append(("offsets", _offsets_name(kind, filtered), lambda kind=kind, filtered=filtered: _offsets(dt, kind, filtered)))
+    return plan
+
+
+def device_text_names(dtype, families=FAMILIES):
+    return [name for family, name, _ in _plan(dtype) if family in families]
+
+
+def device_text_case(dtype, name):
+    """the case of that name, built once; the tests leave it unchanged"""
+    key = (np.dtype(dtype).name, name)
+    if key not in _BUILT:
+        made = next(make for _, n, make in _plan(dtype) if n == name)()
+        assert made["name"] == name
+        _BUILT[key] = made
+    return _BUILT[key]
+
+
+def device_text_cases(dtype, families=FAMILIES):
+    return [device_text_case(dtype, name) for name in device_text_names(dtype, families)]
+
+
+def device_text_model(dtype, name):
+    """the model's answer to that case, computed once"""
+    key = (np.dtype(dtype).name, name)
+    if key not in _MODELS:
+        _MODELS[key] = run_model(device_text_case(dtype, name))
+    return _MODELS[key]
+
+
+# g. the merge with many channels
+def merge_many_channels():
+    """(name, a, counts_a, b, counts_b): 5000 channels with 0 to 3 frames in either list, offsets from a small range (ties
+    inside a list and between the lists), runs of channels empty in both lists at the start, in the middle and at the
+    end, and one channel with 600 frames in list a and 450 in list b"""
+    def make():
+        rng = np.random.default_rng(31)
+        n_channels, crowd = 5000, 1234
+        counts = rng.choice(np.array([0, 0, 0, 1, 2, 3]), size=(2, n_channels))
+        for lo, hi in ((0, 40), (2000, 2300), (n_channels - 55, n_channels)):
+            counts[:, lo:hi] = 0
+        counts[0, crowd], counts[1, crowd] = 600, 450
+        lists = []
+        for which in range(2):
+            offsets = np.concatenate([np.sort(rng.integers(0, 400 if c == crowd else 6, k)) for c, k in enumerate(counts[which])])
+            msgs = [message(11, AA + 100000 * which + k, k) for k in range(len(offsets))]
+            lists.append(MM.frame_list(msgs, offsets=offsets.astype(np.uint64)))
+        return ("5000 channels", lists[0], counts[0].tolist(), lists[1], counts[1].tolist())
+    return _shared("merge", make)

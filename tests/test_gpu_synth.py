@@ -20,7 +20,9 @@ SENTINEL, GUARD = 0x5A, 64      # guard samples behind every range
 @pytest.fixture(scope="module")
 def dems(gpu):
     import torch
-    stream = torch.cuda.current_stream().cuda_stream      # the sentinel fills and the generator run in one order
+    # The framework's current stream is the default one, handle 0, and a context given 0 makes a non-blocking stream of
+    # its own: nothing orders the framework's work against it.  device_fill waits for its sentinel fill before it generates.
+    stream = torch.cuda.current_stream().cuda_stream
     with A.AdsbDemod(sample_type=A.ADSB_SAMPLE_I8, max_samples=4096, max_out=16, stream=stream, host_staging=False) as d8, \
          A.AdsbDemod(sample_type=A.ADSB_SAMPLE_I16, max_samples=4096, max_out=16, stream=stream, host_staging=False) as d16:
         yield {"i8": d8, "i16": d16}
@@ -50,6 +52,7 @@ def device_fill(dems, t, cfg, channel, first, n, at=0, cuts=()):
     import torch
     bps = _bps(t)
     buf = torch.full(((at + n + GUARD) * bps,), SENTINEL, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()       # the fill is done before the generator, on the context's stream, writes over it
     edges = [0, *cuts, n]
     for a, b in zip(edges[:-1], edges[1:]):
         dems[t].synth_fill_device(cfg, channel, first + a, b - a, buf.data_ptr() + (at + a) * bps)
