@@ -70,6 +70,7 @@ class AdsbPacketFields(C.Structure):
 
 
 ADSB_LEVEL_VALID = 0x1  # adsb_frame_level.flags: the frame's window lay inside the buffer
+ADSB_LEVEL_SHORT = 0x2  # ... and it is a 56-bit frame's record: sums over 60 and 68 samples (adsb_levels_modes_of)
 
 
 class AdsbFrameLevel(C.Structure):
@@ -78,6 +79,7 @@ class AdsbFrameLevel(C.Structure):
 
 
 ADSB_WIRE_BEAST, ADSB_WIRE_AVR, ADSB_WIRE_AVR_MLAT = 0, 1, 2  # adsb_wire_cfg.format
+ADSB_WIRE_SHORT = 0x100                                      # ... a bit of it: 56-bit frames leave as short frames
 ADSB_WIRE_MAX_BYTES = 44                                     # the longest encoded frame (Beast, every byte doubled)
 
 
@@ -531,6 +533,9 @@ PROTOTYPES = {
     "adsb_levels_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "adsb_levels_of": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t,
                                  _P(AdsbFrameLevel)]),
+    "adsb_levels_modes_of": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint64, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
+    "adsb_levels_modes_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "adsb_wire_device_async": (C.c_int, [C.c_void_p, _P(AdsbWireCfg)]),
     "adsb_fetch_wire": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _P(C.c_size_t), C.c_void_p, C.c_size_t,
                                   _P(C.c_size_t)]),
@@ -740,6 +745,8 @@ PROTOTYPES = {
     "adsb_free": (None, [C.c_void_p]),
     "adsb_host_frame_levels": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t,
                                          _P(AdsbFrameLevel)]),
+    "adsb_host_frame_levels_modes": (C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_size_t, C.c_size_t, C.c_uint64,
+                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "adsb_level_dbfs": (C.c_double, [C.c_int, C.c_uint64, C.c_uint32]),
     "adsb_host_wire_encode": (C.c_int, [_P(AdsbWireCfg), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.c_size_t, _P(C.c_size_t), C.c_void_p]),

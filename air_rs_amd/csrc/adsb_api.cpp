@@ -63,7 +63,8 @@ extern "C" void adsb_destroy(adsb_ctx *c)
         if (r.k_done) (void)hipEventDestroy(r.k_done);
         if (r.g_done) (void)hipEventDestroy(r.g_done);
     }
-    void *const owned[] = {c->staging, c->out_start, c->fields, c->levels, c->lvof_out.p, c->lvof_frames.p, c->wire.mem.p,
+    void *const owned[] = {c->staging, c->out_start, c->fields, c->levels, c->lvof_out.p, c->lvof_frames.p, c->lvm_out.p,
+                           c->lvm_frames.p, c->lvm_prefix.p, c->wire.mem.p,
                            c->wof.mem.p, c->wof_frames.p, c->wof_levels.p, c->corr.mem.p, c->mlat.mem.p, c->mlat.in_msgs.p,
                            c->mlat.in_recs.p, c->mlat.in_rx.p, c->clock.mem.p, c->clock.in_msgs.p, c->clock.in_recs.p,
                            c->clock.in_rx.p, c->win.mem.p, c->win.in.p, c->modes.mem.p, c->modes.in_frames.p, c->modes.in_known.p,

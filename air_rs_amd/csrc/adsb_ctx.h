@@ -56,6 +56,12 @@ struct adsb_ctx {
     // adsb_levels_of's own scratch (grown on demand): the records, and the device copy of a host frame list
     DevBuf<adsb_frame_level> lvof_out;
     DevBuf<adsb_frame> lvof_frames;
+    // adsb_levels_modes_of's own scratch (grown on demand): the records, the device copy of a host frame list and the
+    // channels' prefix
+    DevBuf<adsb_frame_level> lvm_out;
+    DevBuf<adsb_frame> lvm_frames;
+    DevBuf<uint64_t> lvm_prefix;    // [n_channels + 1]
+    bool lvm_done = false;          // a call has filled lvm_out
     uint32_t levels_blocks = 0;     // the levels kernel's largest grid: a few waves per SIMD of this device
     // wire output (adsb_wire.hip), allocated on first adsb_wire_device_async: one hipMalloc carved into the stream, the
     // frames' ends, one word per workgroup, the stream's header; and adsb_wire_of's own scratch (grown on demand) with the

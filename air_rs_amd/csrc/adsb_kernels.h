@@ -188,6 +188,21 @@ struct LevelsArgs {
 // blocks: the grid (4 waves per block, frames in a grid-stride loop); sized from the device by the caller
 hipError_t launch_frame_levels(hipStream_t s, int sample_type, const LevelsArgs &a, uint32_t blocks);
 
+// level records by frame length, of a caller's list over many channels (adsb_levels.hip, frame_levels_modes_kernel;
+// adsb_levels.h has the per-frame text)
+struct LevelsModesArgs {
+    const void *iq;              // channel 0, sample 0 (device-visible; aligned to one sample)
+    uint64_t n_samples;          // per channel
+    uint64_t channel_stride;     // samples between channel starts
+    uint64_t offset_base;        // frame i sits at sample frames[i].offset - offset_base of its channel
+    const adsb_frame *frames;    // [n]
+    uint32_t n;
+    uint32_t n_channels;         // 1: every frame is channel 0's and prefix is not read
+    const uint64_t *prefix;      // [n_channels + 1]: frames of the list before each channel's first; last = n
+    adsb_frame_level *out;       // [n]
+};
+hipError_t launch_frame_levels_modes(hipStream_t s, int sample_type, const LevelsModesArgs &a, uint32_t blocks);
+
 // an ordered frame list as one stream of Beast binary or AVR text (adsb_wire.hip): three dispatches, see there
 constexpr uint32_t kWireBlockFrames = 256; // frames (= threads) per workgroup of the lengths and write kernels
 constexpr uint32_t kWireScanThreads = 256; // threads of the one workgroup that scans the workgroups' totals

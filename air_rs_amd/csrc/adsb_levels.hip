@@ -11,7 +11,10 @@
 // Nothing is rounded up or down to an alignment, so nothing outside [w, w + 240) of the frame's channel is addressed.
 // The two sums, two maxima, the minimum and the weak-bit count are reduced across the wave in registers; lane 0 stores
 // the 32-byte record.  No LDS, no scratch, no atomics: a latency-bound epilogue of 480 / 960 + 56 bytes per frame.
+// frame_levels_modes_kernel below (adsb_levels_modes_of) is the same plan for a list of 56-bit and 112-bit frames.
 #include "adsb_kernels.h"
+#include "adsb_levels.h"
+#include "adsb_replies.h"
 
 namespace adsbk {
 
@@ -152,7 +155,56 @@ __global__ __launch_bounds__(256) void frame_levels_kernel(const LevelsArgs a)
     }
 }
 
+// Level records by frame length (adsb_levels_modes_of): the same shape over a caller's list of short and long frames
+// from many channels.  A short frame's window is 128 samples: lanes 0-31 own them, lanes 4-31 read bytes 0..6, and
+// lanes 32-63 address nothing and carry the identities, as lanes 60-63 do for a long frame.  The frame's channel is a
+// binary search of the list's prefix (wave-uniform: every lane runs it on the same index).  The per-lane text, the
+// window test and the record are adsb_levels.h's, which the CPU mirror compiles too.
+template <int ST>
+__global__ __launch_bounds__(256) void frame_levels_modes_kernel(const LevelsModesArgs a)
+{
+    constexpr uint32_t kBps = ST == ADSB_SAMPLE_I8 ? 2u : 4u;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    const uint32_t n_waves = gridDim.x * waves_per_block;
+    for (uint64_t i = uniform(blockIdx.x * waves_per_block + (threadIdx.x >> 6)); i < a.n; i += n_waves) {
+        const adsb_frame *f = a.frames + i;
+        const uint64_t off = uniform64(f->offset);
+        const bool is_short = levels_is_short(uniform(f->bytes[0]));
+        const bool valid = levels_inside(off, a.offset_base, a.n_samples, levels_window(is_short));
+        LevelsPart t = levels_nothing();
+        if (valid) {
+            const uint32_t chan = a.n_channels > 1 ? uniform(replies_channel_of(a.prefix, a.n_channels, i)) : 0u;
+            const uint64_t first = (uint64_t)chan * a.channel_stride + (off - a.offset_base); // sample index of w
+            const char *win = static_cast<const char *>(a.iq) + first * kBps;
+            const bool dword_aligned = (uniform((uint32_t)(uintptr_t)win) & 2u) == 0;
+            if (lane < levels_lanes(is_short)) {
+                uint32_t p[4];
+                lane_powers<ST>(win + lane * kLevelsLaneSamples * kBps, dword_aligned, p);
+                t = levels_lane_part(lane, p, lane < 4u ? 0u : (uint32_t)f->bytes[(lane - 4u) >> 2]);
+            }
+            t.signal = wave_sum(t.signal);
+            t.noise = wave_sum(t.noise);
+            t.weak = wave_sum(t.weak);
+            t.pulse_max = wave_max(t.pulse_max);
+            t.quiet_max = wave_max(t.quiet_max);
+            t.pulse_min = wave_min(t.pulse_min);
+        }
+        if (lane == 0) a.out[i] = levels_record(t, valid, is_short);
+    }
+}
+
 } // namespace
+
+hipError_t launch_frame_levels_modes(hipStream_t s, int sample_type, const LevelsModesArgs &a, uint32_t blocks)
+{
+    if (a.n == 0 || blocks == 0) return hipSuccess;
+    if (sample_type == ADSB_SAMPLE_I8)
+        hipLaunchKernelGGL(frame_levels_modes_kernel<ADSB_SAMPLE_I8>, dim3(blocks), dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL(frame_levels_modes_kernel<ADSB_SAMPLE_I16>, dim3(blocks), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_frame_levels(hipStream_t s, int sample_type, const LevelsArgs &a, uint32_t blocks)
 {

@@ -4,7 +4,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <vector>
 
+#include "adsb_levels.h"
 #include "adsb_scratch.h"
 
 // The levels kernel walks its frames in a grid-stride loop, one wave each: the grid is sized from the device (a few
@@ -102,4 +104,48 @@ extern "C" int adsb_levels_of(adsb_ctx *c, const void *iq_dev, size_t n_samples,
     HIPCHK(hipMemcpyAsync(out, c->lvof_out.p, sizeof(adsb_frame_level) * n, hipMemcpyDeviceToHost, c->aux));
     HIPCHK(hipStreamSynchronize(c->aux)); // (nothing uses the scratch any more: the next call may grow it without a wait)
     return ADSB_OK;
+}
+
+extern "C" int adsb_levels_modes_of(adsb_ctx *c, const void *iq_dev, uint32_t n_channels, size_t n_samples,
+                                    size_t channel_stride, uint64_t first_sample_index, const adsb_frame *frames,
+                                    const uint64_t *counts, size_t n, adsb_frame_level *out)
+{
+    if (!c) return ADSB_E_ARG;
+    int rc = adsbk::levels_modes_args_check(iq_dev, n_channels, n_samples, channel_stride, frames, counts, n);
+    if (rc != ADSB_OK) return rc;
+    if ((uintptr_t)iq_dev & (c->bps - 1u)) return ADSB_E_ARG;
+    if (n == 0) return ADSB_OK; // nothing allocated, nothing launched; an earlier call's records stay
+    HIPCHK(hipSetDevice(c->cfg.device));
+    c->lvm_done = false; // until the records are complete: a call that fails on the way leaves none
+    if ((rc = grow(c, c->lvm_out, n)) != ADSB_OK) return rc;
+    const adsb_frame *list = nullptr;
+    if ((rc = stage_list(c, frames, n, c->lvm_frames, &list)) != ADSB_OK) return rc;
+    std::vector<uint64_t> prefix((size_t)n_channels + 1, 0);
+    for (uint32_t ch = 0; ch < n_channels; ++ch) prefix[ch + 1] = prefix[ch] + counts[ch];
+    if (n_channels > 1) {
+        if ((rc = grow(c, c->lvm_prefix, prefix.size())) != ADSB_OK) return rc;
+        HIPCHK(hipMemcpyAsync(c->lvm_prefix.p, prefix.data(), 8 * prefix.size(), hipMemcpyHostToDevice, c->aux));
+    }
+    adsbk::LevelsModesArgs a{};
+    a.iq = iq_dev;
+    a.n_samples = n_samples;
+    a.channel_stride = n_channels == 1 ? n_samples : channel_stride;
+    a.offset_base = first_sample_index;
+    a.frames = list;
+    a.n = (uint32_t)n;
+    a.n_channels = n_channels;
+    a.prefix = n_channels > 1 ? c->lvm_prefix.p : nullptr;
+    a.out = c->lvm_out.p;
+    HIPCHK(adsbk::launch_frame_levels_modes(c->aux, c->cfg.sample_type, a, levels_grid(c, n)));
+    if (out) HIPCHK(hipMemcpyAsync(out, c->lvm_out.p, sizeof(adsb_frame_level) * n, hipMemcpyDeviceToHost, c->aux));
+    HIPCHK(hipStreamSynchronize(c->aux)); // the host list and the prefix are the caller's again; the records are complete
+    c->lvm_done = true;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_levels_modes_device(adsb_ctx *c, const adsb_frame_level **levels_dev)
+{
+    if (!c || !levels_dev) return ADSB_E_ARG;
+    *levels_dev = c->lvm_done ? c->lvm_out.p : nullptr;
+    return c->lvm_done ? ADSB_OK : ADSB_E_STATE;
 }

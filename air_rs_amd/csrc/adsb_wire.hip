@@ -59,7 +59,7 @@ __device__ __forceinline__ uint32_t block_inclusive_scan(uint32_t v, uint32_t *p
 __device__ __forceinline__ void frame_stamp(const WireArgs &a, uint32_t i, const adsb_frame &f, uint64_t *t, uint32_t *s)
 {
     *t = wire_ticks(f.offset, a.tick_bias);
-    *s = a.levels ? wire_signal_of(a.levels + i, a.sample_type) : 0u;
+    *s = a.levels ? wire_signal_of(a.levels + i, a.sample_type, a.format) : 0u;
 }
 
 __global__ __launch_bounds__(kWireBlockFrames) void wire_lengths(const WireArgs a)

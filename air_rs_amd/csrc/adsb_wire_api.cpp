@@ -43,7 +43,7 @@ static adsbk::WireArgs wire_args(const adsb_ctx *c, const adsb_ctx::Wire &w, con
     return a;
 }
 
-static bool wire_wants_levels(const adsb_wire_cfg &cfg) { return cfg.signal != 0 && cfg.format == ADSB_WIRE_BEAST; }
+static bool wire_wants_levels(const adsb_wire_cfg &cfg) { return cfg.signal != 0 && adsbk::wire_base_format(cfg.format) == ADSB_WIRE_BEAST; }
 
 extern "C" int adsb_wire_device_async(adsb_ctx *c, const adsb_wire_cfg *cfg)
 {

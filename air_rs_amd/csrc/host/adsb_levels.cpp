@@ -1,6 +1,7 @@
 // adsb_levels.cpp -- CPU mirror of the device's per-frame power statistics (adsb_levels.hip): adsb_host_frame_levels and
 // adsb_level_dbfs of include/adsb_host.h.  Plain C++, no device: the definition in adsb_hip.h restated sample by sample.
 #include "../../../include/adsb_host.h"
+#include "../adsb_levels.h"
 
 #include <cmath>
 #include <cstring>
@@ -75,6 +76,49 @@ extern "C" int adsb_host_frame_levels(int sample_type, const void *iq, size_t n_
         frame_levels(static_cast<const int16_t *>(iq), n_samples, first_sample_index, frames, n, out);
     else
         return ADSB_E_ARG;
+    return ADSB_OK;
+}
+
+namespace {
+
+// adsb_levels_modes_of's records: ../adsb_levels.h's parts, which the device folds across a wave, taken in sequence
+template <typename T>
+void frame_levels_modes(const T *iq, uint32_t n_channels, size_t n_samples, size_t stride, uint64_t first,
+                        const adsb_frame *frames, const uint64_t *counts, adsb_frame_level *out)
+{
+    using namespace adsbk;
+    size_t i = 0;
+    for (uint32_t c = 0; c < n_channels; ++c) {
+        const T *chan = iq + 2 * stride * (size_t)c;
+        for (uint64_t k = 0; k < counts[c]; ++k, ++i) {
+            const adsb_frame &f = frames[i];
+            const bool is_short = levels_is_short(f.bytes[0]);
+            const bool valid = levels_inside(f.offset, first, n_samples, levels_window(is_short));
+            LevelsPart t = levels_nothing();
+            for (uint32_t l = 0; valid && l < levels_lanes(is_short); ++l) {
+                uint32_t p[4];
+                for (uint32_t s = 0; s < 4; ++s) p[s] = power(chan, (size_t)(f.offset - first) + kLevelsLaneSamples * l + s);
+                t = levels_combine(t, levels_lane_part(l, p, l < 4u ? 0u : (uint32_t)f.bytes[(l - 4u) >> 2]));
+            }
+            out[i] = levels_record(t, valid, is_short);
+        }
+    }
+}
+
+} // namespace
+
+extern "C" int adsb_host_frame_levels_modes(int sample_type, const void *iq, uint32_t n_channels, size_t n_samples,
+                                            size_t channel_stride, uint64_t first_sample_index, const adsb_frame *frames,
+                                            const uint64_t *counts, size_t n, adsb_frame_level *out)
+{
+    if ((sample_type != ADSB_SAMPLE_I8 && sample_type != ADSB_SAMPLE_I16) || (!out && n)) return ADSB_E_ARG;
+    const int rc = adsbk::levels_modes_args_check(iq, n_channels, n_samples, channel_stride, frames, counts, n);
+    if (rc != ADSB_OK) return rc;
+    if (n_channels == 1) channel_stride = n_samples;
+    if (sample_type == ADSB_SAMPLE_I8)
+        frame_levels_modes(static_cast<const int8_t *>(iq), n_channels, n_samples, channel_stride, first_sample_index, frames, counts, out);
+    else
+        frame_levels_modes(static_cast<const int16_t *>(iq), n_channels, n_samples, channel_stride, first_sample_index, frames, counts, out);
     return ADSB_OK;
 }
 

@@ -12,12 +12,12 @@ extern "C" int adsb_host_wire_encode(const adsb_wire_cfg *cfg, int sample_type, 
     if (!adsbk::wire_cfg_ok(cfg) || !n_bytes || (!frames && n) || (!out && cap)) return ADSB_E_ARG;
     if (sample_type != ADSB_SAMPLE_I8 && sample_type != ADSB_SAMPLE_I16) return ADSB_E_ARG;
     if ((uint64_t)n * adsbk::kWireMaxBytes > 0xFFFFFFFFull) return ADSB_E_CAPACITY;
-    const bool with_signal = cfg->signal != 0 && cfg->format == ADSB_WIRE_BEAST && levels;
+    const bool with_signal = cfg->signal != 0 && adsbk::wire_base_format(cfg->format) == ADSB_WIRE_BEAST && levels;
     size_t total = 0;
     bool fits = true; // whole frames only: the first frame that does not fit ends the copy, not the count
     for (size_t i = 0; i < n; ++i) {
         const uint64_t t = adsbk::wire_ticks(frames[i].offset, cfg->tick_bias);
-        const uint32_t s = with_signal ? adsbk::wire_signal_of(&levels[i], sample_type) : 0u;
+        const uint32_t s = with_signal ? adsbk::wire_signal_of(&levels[i], sample_type, cfg->format) : 0u;
         uint8_t one[adsbk::kWireMaxBytes];
         const uint32_t len = adsbk::wire_encode(cfg->format, t, s, frames[i].bytes, one);
         fits = fits && total + len <= cap;

@@ -27,6 +27,7 @@ LEVEL_DTYPE = np.dtype([("signal_sum", "<u8"), ("noise_sum", "<u8"), ("peak", "<
                         ("quiet_max", "<u4"), ("weak_bits", "<u2"), ("flags", "<u2")])
 assert LEVEL_DTYPE.itemsize == C.sizeof(L.AdsbFrameLevel) == 32
 LEVEL_PULSE_SAMPLES, LEVEL_QUIET_SAMPLES = 116, 124  # of a frame's 240: what signal_sum and noise_sum add up
+LEVEL_SHORT_PULSE_SAMPLES, LEVEL_SHORT_QUIET_SAMPLES = 60, 68  # of a 56-bit frame's 128 (ADSB_LEVEL_SHORT records)
 
 SITE, FIX_DTYPE, FRAME_FIX_DTYPE = L.SITE, L.FIX_DTYPE, L.FRAME_FIX_DTYPE  # fixes_reserve / fixes / frame_fixes
 AIRCRAFT_MLAT_DTYPE, FRAME_MLAT_DTYPE = L.AIRCRAFT_MLAT_DTYPE, L.FRAME_MLAT_DTYPE  # TrackTable.mlat / frame_mlat
@@ -76,6 +77,38 @@ def host_frame_levels(iq, frames, first_sample=0):
     L.check(L.load().adsb_host_frame_levels(st, keep.ctypes.data, n_samples, int(first_sample),
                                             frames.ctypes.data if len(frames) else None, len(frames),
                                             out.ctypes.data_as(C.POINTER(L.AdsbFrameLevel))), "adsb_host_frame_levels")
+    return out[:len(frames)].copy()
+
+
+def _channel_counts(counts, n):
+    """counts as a flat uint64 array; None: one channel of n frames.  Nothing is checked here: the library refuses
+    counts that do not add up to the list's length."""
+    return np.array([n], dtype=np.uint64) if counts is None else np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+
+
+def host_frame_levels_modes(iq, frames, counts=None, n_samples=None, channel_stride=None, first_sample=0):
+    """adsb_host_frame_levels_modes, the CPU mirror of AdsbDemod.levels_modes_of: one LEVEL_DTYPE record per frame of
+    `frames` (FRAME_DTYPE, in channel order, counts[c] of channel c; None: one channel), a 56-bit frame's over its 128
+    samples with ADSB_LEVEL_SHORT, a 112-bit frame's as host_frame_levels.  iq: int8 or int16 host samples, channel c
+    starting channel_stride samples after channel c-1 (default: n_samples).  n_samples may be left out for one channel
+    only (all of iq); with more channels it must be given, and iq must hold the last channel whole."""
+    st = _sample_type_of(iq)
+    iq = np.ascontiguousarray(iq)
+    frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+    counts = _channel_counts(counts, len(frames))
+    if n_samples is None:
+        if len(counts) != 1:
+            raise ValueError("n_samples is needed with more than one channel")
+        n_samples = iq.size // 2
+    stride = n_samples if channel_stride is None else channel_stride
+    if len(counts) and (len(counts) - 1) * stride + n_samples > iq.size // 2:
+        raise ValueError(f"iq holds {iq.size // 2} samples, {len(counts)} channels of {n_samples} at stride {stride} need more")
+    out = np.zeros(max(len(frames), 1), dtype=LEVEL_DTYPE)
+    keep = iq if iq.size else np.zeros(2, dtype=iq.dtype)
+    L.check(L.load().adsb_host_frame_levels_modes(st, keep.ctypes.data, len(counts), int(n_samples), int(stride),
+                                                  int(first_sample), frames.ctypes.data if len(frames) else None,
+                                                  counts.ctypes.data if len(counts) else None, len(frames),
+                                                  out.ctypes.data), "adsb_host_frame_levels_modes")
     return out[:len(frames)].copy()
 
 
@@ -148,9 +181,9 @@ def host_track_modes_merge(into, later):
 WIRE_FORMATS = {"beast": L.ADSB_WIRE_BEAST, "avr": L.ADSB_WIRE_AVR, "avr_mlat": L.ADSB_WIRE_AVR_MLAT}
 
 
-def _wire_cfg(format, signal, tick_bias):
+def _wire_cfg(format, signal, tick_bias, short=False):
     fmt = WIRE_FORMATS[format] if isinstance(format, str) else int(format)
-    return L.AdsbWireCfg(fmt, 1 if signal else 0, int(tick_bias))
+    return L.AdsbWireCfg(fmt | (L.ADSB_WIRE_SHORT if short else 0), 1 if signal else 0, int(tick_bias))
 
 
 def _host_list(arr, dtype, n=None):
@@ -161,16 +194,18 @@ def _host_list(arr, dtype, n=None):
     return arr, (arr.ctypes.data if len(arr) else None), len(arr)
 
 
-def host_wire_encode(frames, levels=None, format="beast", sample_type=L.ADSB_SAMPLE_I8, tick_bias=0, cap=None):
+def host_wire_encode(frames, levels=None, format="beast", sample_type=L.ADSB_SAMPLE_I8, tick_bias=0, cap=None,
+                     short=False):
     """adsb_host_wire_encode, the CPU mirror of AdsbDemod.wire_of: (stream as bytes, ends as a uint32 array) of the
     FRAME_DTYPE list `frames` with their LEVEL_DTYPE records `levels` (None: signal byte 0; sample_type gives its full
     scale).  cap (default: enough): room in the output; with less than the stream needs, `bytes` holds the longest
-    prefix of whole frames and `ends` still has every frame's end.  Needs no device."""
+    prefix of whole frames and `ends` still has every frame's end.  short: ADSB_WIRE_SHORT, 56-bit frames leave as
+    short frames (Beast '2', 14 hex digits).  Needs no device."""
     frames, fptr, n = _host_list(frames, FRAME_DTYPE)
     lptr = None
     if levels is not None:
         levels, lptr, _ = _host_list(levels, LEVEL_DTYPE, n)
-    cfg = _wire_cfg(format, levels is not None, tick_bias)
+    cfg = _wire_cfg(format, levels is not None, tick_bias, short)
     room = L.ADSB_WIRE_MAX_BYTES * n if cap is None else int(cap)
     out = np.zeros(max(room, 1), dtype=np.uint8)
     ends = np.zeros(max(n, 1), dtype=np.uint32)
@@ -1144,17 +1179,45 @@ class AdsbDemod:
                                          out.ctypes.data_as(C.POINTER(L.AdsbFrameLevel))), "adsb_levels_of")
         return out[:n].copy()
 
-    def wire_async(self, format="beast", signal=True, tick_bias=0):
+    def levels_modes_of(self, dev_ptr, n_samples, frames, counts=None, channel_stride=None, first_sample=0, fetch=True):
+        """adsb_levels_modes_of: LEVEL_DTYPE records by frame length of what replies_of / merge_lists produce -- 56-bit
+        frames over their 128 samples (ADSB_LEVEL_VALID | ADSB_LEVEL_SHORT), 112-bit frames as levels_of -- against
+        len(counts) channels of n_samples samples at dev_ptr, channel_stride samples apart (default n_samples).
+        frames: a FRAME_DTYPE array (host), or (device pointer, count), in channel order; counts: frames per channel
+        (host; None: one channel).  fetch=False leaves the records on the device: levels_modes_device() is their
+        address, which wire_of, correlate_of and a table's update(levels=) take.  Blocking; the last launch's levels
+        and levels_of's scratch stay as they are."""
+        if isinstance(frames, tuple):
+            ptr, n = int(frames[0]), int(frames[1])
+        else:
+            frames = np.ascontiguousarray(frames, dtype=FRAME_DTYPE)
+            ptr, n = (frames.ctypes.data if len(frames) else None), len(frames)
+        counts = _channel_counts(counts, n)
+        stride = n_samples if channel_stride is None else channel_stride
+        out = np.zeros(max(n, 1), dtype=LEVEL_DTYPE) if fetch else None
+        L.check(self._lib.adsb_levels_modes_of(self._h, dev_ptr, len(counts), int(n_samples), int(stride),
+                                               int(first_sample), ptr, counts.ctypes.data if len(counts) else None, n,
+                                               out.ctypes.data if fetch else None), "adsb_levels_modes_of")
+        return out[:n].copy() if fetch else None
+
+    def levels_modes_device(self):
+        """Device address of the records of the last levels_modes_of(); valid until the next one."""
+        dev = C.c_void_p()
+        L.check(self._lib.adsb_levels_modes_device(self._h, C.byref(dev)), "adsb_levels_modes_device")
+        return dev.value
+
+    def wire_async(self, format="beast", signal=True, tick_bias=0, short=False):
         """adsb_wire_device_async alone: enqueues the last launch's list as Beast binary ("beast") or AVR text ("avr",
         "avr_mlat") behind its ordering pass and returns.  signal: Beast's signal byte from the launch's levels, which
-        are enqueued here if they have not been.  Timestamp = 6 x offset + tick_bias, mod 2^48."""
-        cfg = _wire_cfg(format, signal, tick_bias)
+        are enqueued here if they have not been.  Timestamp = 6 x offset + tick_bias, mod 2^48.  short:
+        ADSB_WIRE_SHORT (the demodulator's list is all DF17, so its bytes are the same)."""
+        cfg = _wire_cfg(format, signal, tick_bias, short)
         L.check(self._lib.adsb_wire_device_async(self._h, C.byref(cfg)), "adsb_wire_device_async")
 
-    def wire(self, format="beast", signal=True, tick_bias=0):
+    def wire(self, format="beast", signal=True, tick_bias=0, short=False):
         """The last launch's frames as one stream: (bytes, ends), ends[i] the exclusive end of frame i's bytes (uint32).
         Encoded on the device; a second call with another format replaces the first's stream."""
-        self.wire_async(format, signal, tick_bias)
+        self.wire_async(format, signal, tick_bias, short)
         return self.fetch_wire()
 
     def fetch_wire(self, cap=None, max_ends=None):
@@ -1181,11 +1244,12 @@ class AdsbDemod:
         L.check(self._lib.adsb_wire_device(self._h, C.byref(b), C.byref(e), C.byref(h)), "adsb_wire_device")
         return b.value, e.value, h.value
 
-    def wire_of(self, frames, levels=None, format="beast", tick_bias=0, cap=None):
+    def wire_of(self, frames, levels=None, format="beast", tick_bias=0, cap=None, short=False):
         """adsb_wire_of: any frame list with any level list as one stream -> (bytes, ends).  frames: a FRAME_DTYPE array
         (host) or (device pointer, count); levels: None (signal byte 0), a LEVEL_DTYPE array (host) or a device pointer.
-        cap: room for the bytes (default: enough); with less, whole frames only.  Blocking; the last launch's wire
-        output stays as it is."""
+        cap: room for the bytes (default: enough); with less, whole frames only.  short: ADSB_WIRE_SHORT, 56-bit
+        frames leave as short frames and ADSB_LEVEL_SHORT records scale by 60 pulse samples.  Blocking; the last
+        launch's wire output stays as it is."""
         if isinstance(frames, tuple):
             fptr, n = int(frames[0]), int(frames[1])
         else:
@@ -1195,7 +1259,7 @@ class AdsbDemod:
             lptr = levels
         elif levels is not None:
             levels, lptr, _ = _host_list(levels, LEVEL_DTYPE, n)
-        cfg = _wire_cfg(format, levels is not None, tick_bias)
+        cfg = _wire_cfg(format, levels is not None, tick_bias, short)
         room = L.ADSB_WIRE_MAX_BYTES * n if cap is None else int(cap)
         out = np.zeros(max(room, 1), dtype=np.uint8)
         ends = np.zeros(max(n, 1), dtype=np.uint32)

@@ -251,7 +251,7 @@ typedef struct adsb_frame_level {   /* 32 bytes */
     uint32_t pulse_min;    /* min p over the pulse samples                                */
     uint32_t quiet_max;    /* max p over the quiet samples                                */
     uint16_t weak_bits;    /* bits whose pulse-sample p < 2 x their quiet-sample p (u64)  */
-    uint16_t flags;        /* ADSB_LEVEL_VALID; 0: window not inside the buffer, rest 0   */
+    uint16_t flags;        /* ADSB_LEVEL_VALID (| ADSB_LEVEL_SHORT, adsb_levels_modes_of); 0: window not inside the buffer, rest 0 */
 } adsb_frame_level;
 /* Enqueues the levels of the last launch's list behind its ordering pass (like adsb_decode_fields_device_async; the
  * count is read on the device, the host does not wait).  Reads the launch's input again: the buffer handed to
@@ -276,6 +276,39 @@ int adsb_levels_device(adsb_ctx *ctx, const adsb_frame_level **levels_dev);
  * Uses scratch of its own: the last launch's levels stay as they are.  ADSB_E_CAPACITY for n >= 2^32. */
 int adsb_levels_of(adsb_ctx *ctx, const void *iq_dev, size_t n_samples, uint64_t first_sample_index,
                    const adsb_frame *frames, size_t n, adsb_frame_level *out);
+/*
+ * Level records by frame length: what adsb_replies_of and adsb_merge_lists_of produce -- 56-bit and 112-bit frames of
+ * many channels in one list -- against the samples they came from.  A frame's length is that of its DF, bytes[0] >> 3:
+ * below 16 it is a SHORT frame of 56 bits, anything else (DF16..31, DF24..31 included) a long one of 112.  This is the
+ * rule adsb_modes_of and the replies scan use.
+ *   A long frame's record is exactly adsb_levels_of's.
+ *   A short frame's window is the 128 samples [w, w + 128).  Its 60 PULSE samples are w+0, w+2, w+7, w+9 and, per bit
+ *   b = 0..55 of bytes[0..7), w+16+2b if the bit is 1, else w+16+2b+1; the other 68 are the QUIET samples.  The fields
+ *   are the same: the two sums, peak over all 128, pulse_min, quiet_max, and weak_bits over the 56 bits.  flags =
+ *   ADSB_LEVEL_VALID | ADSB_LEVEL_SHORT.  bytes[7..14) of a short frame are never read.
+ *   A short frame is valid iff [w, w + 128) lies inside its channel, [0, n_samples): one at n_samples - 128 is valid, one
+ *   at n_samples - 127 gets zeros and flags = 0 -- a short frame in the last 240 samples of a buffer, which the replies
+ *   scan finds on purpose, has a record.  Nothing at or past w + 128 is addressed for a short frame, and nothing at or
+ *   past its channel's end for any frame.
+ * The list is in channel order: counts[c] (HOST memory, n_channels entries that add up to n) frames of channel c, whose
+ * sample 0 is at iq_dev + c x channel_stride samples (channel_stride >= n_samples; ignored for one channel); frame i of
+ * channel c sits at sample frames[i].offset - first_sample_index of it.  `frames` is host memory or device memory of the
+ * ctx's device.  `out` is host memory of n records, or NULL to leave the records on the device only.  Blocking.  Uses
+ * scratch of its own, grown on demand: the last launch's levels and adsb_levels_of's scratch stay as they are, and a ctx
+ * that never calls it allocates nothing and launches exactly the kernels it launched before.  n = 0 is ADSB_OK, allocates
+ * and launches nothing and leaves an earlier call's records as they are.  ADSB_E_ARG for a NULL
+ * ctx, iq_dev or counts, NULL frames with n > 0, iq_dev not aligned to one sample, n_channels = 0 or above 2^20,
+ * channel_stride < n_samples with more than one channel, or counts that do not add up to n; ADSB_E_CAPACITY for
+ * n >= 2^32.
+ */
+#define ADSB_LEVEL_SHORT 0x2u /* adsb_frame_level.flags: a 56-bit frame's record, sums over 60 and 68 samples */
+int adsb_levels_modes_of(adsb_ctx *ctx, const void *iq_dev, uint32_t n_channels, size_t n_samples, size_t channel_stride,
+                         uint64_t first_sample_index, const adsb_frame *frames, const uint64_t *counts, size_t n,
+                         adsb_frame_level *out /* NULL: device only */);
+/* Device pointer to the records of the last adsb_levels_modes_of, valid until the next one: what adsb_wire_of,
+ * adsb_correlate_of and a table's update take as a device level list.  ADSB_E_STATE before the first call with n > 0
+ * that returned ADSB_OK, and after one that failed on its way (its records are not complete). */
+int adsb_levels_modes_device(adsb_ctx *ctx, const adsb_frame_level **levels_dev);
 
 /*
  * Wire output: a frame list as Beast binary or AVR text, the formats readsb / dump1090 network inputs, tar1090,
@@ -295,6 +328,21 @@ int adsb_levels_of(adsb_ctx *ctx, const void *iq_dev, size_t n_samples, uint64_t
  *   ADSB_WIRE_AVR       '*', 28 upper-case hex digits, ';', '\n'.  31 bytes.
  *   ADSB_WIRE_AVR_MLAT  '@', 12 upper-case hex digits of t, 28 hex digits, ';', '\n'.  43 bytes.  (The AVR forms carry
  *                       no signal byte: `signal` is ignored.)
+ *   ADSB_WIRE_SHORT     a bit of `format`, OR-ed onto one of the three (adsb_wire_cfg has no spare field).  With it a
+ *                       frame whose length is 7 by the rule of "Level records by frame length" (bytes[0] >> 3 below 16)
+ *                       leaves as a short frame:
+ *                         Beast     1A 32, 6 bytes of t, s, bytes[0..7); every 0x1A of those 14 bytes doubled.  16..30 bytes.
+ *                         AVR       '*', 14 upper-case hex digits, ';', '\n'.  17 bytes.
+ *                         AVR_MLAT  '@', 12 digits of t, 14 digits, ';', '\n'.  29 bytes.
+ *                       bytes[7..14) are neither written nor looked at for escapes.  Long frames are written as without
+ *                       the bit, and t is the same 6 x offset + tick_bias.  SIGNAL BYTE with the bit: a level record with
+ *                       ADSB_LEVEL_SHORT is a sum over 60 pulse samples, so s is the largest s in 0..255 with (2s-1)^2 x
+ *                       60 x FS <= 4 x 255^2 x signal_sum, raised to 1 for a sum above zero and clamped as above; a record
+ *                       without that flag uses 116 whatever the frame's length (wire input's records have no SHORT flag
+ *                       and are built with 116, so they keep encoding to the byte they came from).  Without the bit
+ *                       every byte is what it was before the bit existed: 14 frame bytes, 116.  adsb_wire_in_of with
+ *                       ADSB_WIRE_IN_SHORT reads such a stream back as the same list; its own `format` does not take
+ *                       this bit.
  * The output is ONE contiguous byte stream in list order (channel 0's frames in ascending offset, then channel 1's,
  * ...) and uint32 ends[n]: the exclusive end offset of each frame's bytes, so ends[i-1] .. ends[i] is frame i (from 0
  * for frame 0) and ends[n-1] is the stream's length.  With adsb_fetch's per_channel_counts a consumer cuts the stream
@@ -303,9 +351,10 @@ int adsb_levels_of(adsb_ctx *ctx, const void *iq_dev, size_t n_samples, uint64_t
 #define ADSB_WIRE_BEAST 0u
 #define ADSB_WIRE_AVR 1u
 #define ADSB_WIRE_AVR_MLAT 2u
+#define ADSB_WIRE_SHORT 0x100u /* a bit of adsb_wire_cfg.format: 56-bit frames leave as short frames */
 #define ADSB_WIRE_MAX_BYTES 44 /* the longest encoded frame */
 typedef struct adsb_wire_cfg {
-    uint32_t format;     /* ADSB_WIRE_*                                               */
+    uint32_t format;     /* ADSB_WIRE_BEAST, _AVR or _AVR_MLAT, | ADSB_WIRE_SHORT     */
     uint32_t signal;     /* != 0: the Beast signal byte from the frames' level records */
     uint64_t tick_bias;  /* < 2^48                                                     */
 } adsb_wire_cfg;

@@ -107,9 +107,18 @@ int adsb_replay_file(adsb_ctx *ctx, const char *path, int file_format, size_t ch
  */
 int adsb_host_frame_levels(int sample_type, const void *iq, size_t n_samples, uint64_t first_sample_index,
                            const adsb_frame *frames, size_t n, adsb_frame_level *out);
+/* CPU mirror of adsb_levels_modes_of (adsb_hip.h, "Level records by frame length"): the same records from the same
+ * per-frame program text as the device's, from a HOST buffer of n_channels channels channel_stride samples apart.
+ * frames[n] in channel order with counts[n_channels] that add up to n, all host memory; a short frame (bytes[0] >> 3
+ * below 16) gets the 128-sample record with ADSB_LEVEL_SHORT, a long one adsb_host_frame_levels' record.  The same
+ * argument errors as adsb_levels_modes_of, and ADSB_E_ARG for a bad sample_type or NULL out with n > 0. */
+int adsb_host_frame_levels_modes(int sample_type, const void *iq, uint32_t n_channels, size_t n_samples,
+                                 size_t channel_stride, uint64_t first_sample_index, const adsb_frame *frames,
+                                 const uint64_t *counts, size_t n, adsb_frame_level *out);
 /* 10 log10(sum / n_samples / FS) with FS = 32768 (ADSB_SAMPLE_I8) or 2^31 (ADSB_SAMPLE_I16): the mean power of
  * n_samples samples whose p add up to `sum`, in dB below a full-scale sample.  -INFINITY for sum == 0; NaN for a bad
- * sample_type or n_samples == 0.  adsb_level_dbfs(st, level.signal_sum, 116) and (st, level.noise_sum, 124). */
+ * sample_type or n_samples == 0.  adsb_level_dbfs(st, level.signal_sum, 116) and (st, level.noise_sum, 124); 60 and 68
+ * for a record with ADSB_LEVEL_SHORT. */
 double adsb_level_dbfs(int sample_type, uint64_t sum, uint32_t n_samples);
 
 /*
@@ -117,7 +126,8 @@ double adsb_level_dbfs(int sample_type, uint64_t sum, uint32_t n_samples);
  * device needed.  frames[n] with levels[n] (NULL: s = 0), both host memory; sample_type gives the signal byte's full
  * scale.  out / cap / *n_bytes as adsb_fetch_wire: the whole stream if cap holds it, else the longest prefix of whole
  * frames, and *n_bytes = the stream's full length either way; ends (may be NULL) receives all n entries.  What a
- * feed's consumer uses on popped frames, together with adsb_host_frame_levels.  ADSB_E_ARG for a NULL cfg or n_bytes,
+ * feed's consumer uses on popped frames, together with adsb_host_frame_levels.  cfg->format takes ADSB_WIRE_SHORT as
+ * adsb_wire_of's does.  ADSB_E_ARG for a NULL cfg or n_bytes,
  * an unknown format, tick_bias >= 2^48, a bad sample_type, NULL frames with n > 0 or NULL out with cap > 0;
  * ADSB_E_CAPACITY when 44 x n does not fit uint32.
  */

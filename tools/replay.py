@@ -17,6 +17,7 @@
   tools/replay.py out.txt --avr-in --modes --commb   # one line per frame; DF20/21 lines with their Comm-B register
   tools/replay.py out.txt --avr-in --es       # one line per DF17/18 frame: what it says about the aircraft's status
   tools/replay.py capture.bin --replies --modes      # the packets and the Mode S replies found in the samples, one list
+  tools/replay.py capture.bin --replies --beast out.bin --levels   # ... sent out again, short frames as Beast '2'
 
 Everything below the argument parsing is one call through the C ABI (adsb_replay_file, include/adsb_host.h).
 The "Processed Time" line carries no value (the reference prints the wall clock there).  With --aircraft, the frames
@@ -78,6 +79,10 @@ parity rule of its own on sample power) gives a second list from the same sample
 (adsb_merge_lists_of).  One line per frame: time in seconds, offset, "demod" or "replies", DF and the message in hex.
 With --replies --modes the merged list goes through adsb_modes_of and --modes' lines are printed; with --replies --modes
 --aircraft the table keyed by the resolved addresses.  No chunking here: offsets are positions in the capture.
+With --replies --beast FILE / --avr FILE [--mlat] the merged list is also written as one stream with ADSB_WIRE_SHORT:
+56-bit frames leave as Beast '2' frames or 14-digit lines, the Beast signal bytes from the list's level records by frame
+length (adsb_levels_modes_of on the capture in device memory).  With --replies --levels one line per frame instead:
+offset, DF, signal dBFS, noise dBFS, their difference, weak bits; a 56-bit frame's over 60 pulse and 68 quiet samples.
 The TEXT has not been compared with a Rust build's (there is no
 Rust toolchain); only the values are checked, against the oracle."""
 import argparse
@@ -395,9 +400,29 @@ def replies_lines(frames, src):
     return "".join(out)
 
 
-def replies_run(device, st, iq):
+def replies_level_lines(st, frames, levels):
+    """--replies --levels: one tab-separated line per frame of the merged list: offset, DF, signal dBFS, noise dBFS,
+    signal - noise, weak bits.  A 56-bit frame's record (ADSB_LEVEL_SHORT) is over 60 pulse and 68 quiet samples, a
+    112-bit frame's over 116 and 124; a frame whose window is not inside the capture gets "n/a"."""
+    out = []
+    for f, lv in zip(frames, levels):
+        head = f"{int(f['offset'])}\tDF{int(f['bytes'][0]) >> 3}"
+        flags = int(lv["flags"])
+        if not flags & A.ADSB_LEVEL_VALID:
+            out.append(head + "\tn/a\tn/a\tn/a\tn/a\n")
+            continue
+        short = bool(flags & A.ADSB_LEVEL_SHORT)
+        sig = A.level_dbfs(st, lv["signal_sum"], A.LEVEL_SHORT_PULSE_SAMPLES if short else A.LEVEL_PULSE_SAMPLES)
+        noise = A.level_dbfs(st, lv["noise_sum"], A.LEVEL_SHORT_QUIET_SAMPLES if short else A.LEVEL_QUIET_SAMPLES)
+        out.append(f"{head}\t{sig:.1f}\t{noise:.1f}\t{sig - noise:.1f}\t{int(lv['weak_bits'])}\n")
+    return "".join(out)
+
+
+def replies_run(device, st, iq, levels=None):
     """--replies: the demodulator's launch and the replies scan over the whole capture in device memory, merged on the
-    device -> (the context, which the caller closes; merged frames; src)"""
+    device -> (the context, which the caller closes; merged frames; src; the level records or None).  levels: "device"
+    computes the merged list's level records by frame length (adsb_levels_modes_of on the capture where it lies) and
+    leaves them on the device, d.levels_modes_device(); "host" also returns them; None: no records."""
     import numpy as np
     import torch
     n = len(iq)
@@ -411,8 +436,9 @@ def replies_run(device, st, iq):
     if int(hdr["flags"]) & A.ADSB_FLAG_TRUNCATED:
         print(f"replies scan: {int(hdr['total_found'])} frames found, {len(replies)} kept", file=sys.stderr)
     frames, src, _ = d.merge_lists(found, [len(found)], replies, [len(replies)])
+    records = d.levels_modes_of(dev.data_ptr(), n, frames, fetch=levels == "host") if levels else None
     del dev
-    return d, frames, src
+    return d, frames, src, records
 
 
 def read_wire(d, path, wire_format, tick_bias, chunk=WIRE_IN_CHUNK, modes=False, commb=False):
@@ -469,6 +495,18 @@ def write_wire(d, frames, a, fmt, levels=None):
             fh.write(d.wire_of(frames, None, format="avr_mlat" if a.mlat else "avr", tick_bias=a.tick_bias)[0])
 
 
+def write_replies_wire(d, frames, a):
+    """--replies --beast / --avr: the merged list as one stream with ADSB_WIRE_SHORT, so that 56-bit frames leave as
+    Beast '2' frames or 14-digit lines; the Beast signal bytes from the level records replies_run left on the device."""
+    if a.beast:
+        with open(a.beast, "wb") as fh:
+            fh.write(d.wire_of(frames, d.levels_modes_device() if len(frames) else None, format="beast",
+                               tick_bias=a.tick_bias, short=True)[0])
+    if a.avr:
+        with open(a.avr, "wb") as fh:
+            fh.write(d.wire_of(frames, None, format="avr_mlat" if a.mlat else "avr", tick_bias=a.tick_bias, short=True)[0])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("file")
@@ -513,8 +551,8 @@ def main():
     if a.beast_in and a.avr_in:
         ap.error("--beast-in and --avr-in exclude each other")
     wire_in = "beast" if a.beast_in else "avr" if a.avr_in else None
-    if a.replies and (wire_in or a.web or a.levels or a.es or a.commb or a.site or a.beast or a.avr or (a.aircraft and not a.modes)):
-        ap.error("--replies works on samples and goes with --modes and --modes --aircraft only")
+    if a.replies and (wire_in or a.web or a.es or a.commb or a.site or (a.aircraft and not a.modes) or (a.levels and a.modes)):
+        ap.error("--replies works on samples and goes with --modes, --modes --aircraft, --levels, --beast and --avr only")
     if a.modes and not wire_in and not a.replies:
         ap.error("--modes needs --beast-in, --avr-in or --replies")
     if a.commb and not a.modes:
@@ -527,11 +565,15 @@ def main():
     st = A.ADSB_SAMPLE_I16 if fmt == "c16" else A.ADSB_SAMPLE_I8
     n_max = os.path.getsize(a.file) // (4 if fmt == "c16" else 2)
     if a.replies:
-        d, frames, src = replies_run(a.device, st, read_capture(a.file, fmt))
+        d, frames, src, records = replies_run(a.device, st, read_capture(a.file, fmt),
+                                                 levels="host" if a.levels else "device" if a.beast else None)
         with d:
+            write_replies_wire(d, frames, a)
             if a.modes:
                 recs = d.modes_of(frames)[0]
                 sys.stdout.write(aircraft_table(d, frames, n_max, modes=recs) if a.aircraft else modes_lines(frames, recs))
+            elif a.levels:
+                sys.stdout.write(replies_level_lines(st, frames, records))
             else:
                 sys.stdout.write(replies_lines(frames, src))
         if a.summary:
