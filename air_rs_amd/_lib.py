@@ -418,6 +418,63 @@ assert AIRCRAFT_MLAT_DTYPE.itemsize == C.sizeof(AdsbAircraftMlat) == 64
 assert FRAME_MLAT_DTYPE.itemsize == C.sizeof(AdsbFrameMlat) == 16
 
 
+ADSB_TRACK_FILTER_RUNNING = 0x1     # adsb_aircraft_filter.flags: the record holds a state
+ADSB_TRACK_FILTER_VELOCITY = 0x2    # run >= min_run: the velocities are worth showing
+ADSB_TRACK_FILTER_HEIGHT = 0x4      # record: the up axis has been measured since the start; operand: it is
+ADSB_TRACK_FILTER_USABLE = 0x100    # adsb_frame_filter.flags and adsb_filter_operand.flags
+ADSB_TRACK_FILTER_APPLIED = 0x200   # adsb_frame_filter.flags only, as are the next four
+ADSB_TRACK_FILTER_INIT = 0x400
+ADSB_TRACK_FILTER_RESET = 0x800
+ADSB_TRACK_FILTER_OUTLIER = 0x1000
+ADSB_TRACK_FILTER_SKIPPED = 0x2000
+
+
+class AdsbTrackFilterCfg(C.Structure):
+    """adsb_track_filter_cfg: the policy of a filter reserve; 0 takes each default (96 bytes)."""
+    _fields_ = [("accel_h", C.c_double), ("accel_v", C.c_double), ("range_sigma_m", C.c_double),
+                ("altitude_sigma_m", C.c_double), ("gate", C.c_double), ("reset_gap_s", C.c_double),
+                ("init_speed_sigma_h", C.c_double), ("init_speed_sigma_v", C.c_double), ("max_hdop", C.c_double),
+                ("max_vdop", C.c_double), ("max_outliers", C.c_uint32), ("min_run", C.c_uint32),
+                ("reserved", C.c_uint64)]
+
+
+class AdsbAircraftFilter(C.Structure):
+    """adsb_aircraft_filter: an aircraft's filtered mlat track, beside its record (tables with a filter reserve)."""
+    _fields_ = [("time", C.c_double), ("latitude", C.c_double), ("longitude", C.c_double), ("height_m", C.c_double),
+                ("v_north", C.c_double), ("v_east", C.c_double), ("v_up", C.c_double), ("p_north", C.c_double * 3),
+                ("p_east", C.c_double * 3), ("p_up", C.c_double * 3), ("n_applied", C.c_uint32),
+                ("n_outlier", C.c_uint32), ("n_reset", C.c_uint32), ("n_skipped", C.c_uint32), ("run", C.c_uint32),
+                ("outliers_run", C.c_uint32), ("last_nis", C.c_float), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32 * 8)]
+
+
+class AdsbFrameFilter(C.Structure):
+    _fields_ = [("latitude", C.c_double), ("longitude", C.c_double), ("height_m", C.c_float), ("nis", C.c_float),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class AdsbFilterOperand(C.Structure):
+    _fields_ = [("time", C.c_double), ("latitude", C.c_double), ("longitude", C.c_double), ("rn", C.c_double),
+                ("re", C.c_double), ("var_h", C.c_double), ("var_v", C.c_double), ("height_m", C.c_float),
+                ("flags", C.c_uint32)]
+
+
+AIRCRAFT_FILTER_DTYPE = np.dtype([("time", "<f8"), ("latitude", "<f8"), ("longitude", "<f8"), ("height_m", "<f8"),
+                                  ("v_north", "<f8"), ("v_east", "<f8"), ("v_up", "<f8"), ("p_north", "<f8", (3,)),
+                                  ("p_east", "<f8", (3,)), ("p_up", "<f8", (3,)), ("n_applied", "<u4"),
+                                  ("n_outlier", "<u4"), ("n_reset", "<u4"), ("n_skipped", "<u4"), ("run", "<u4"),
+                                  ("outliers_run", "<u4"), ("last_nis", "<f4"), ("flags", "<u4"),
+                                  ("reserved", "<u4", (8,))])
+FRAME_FILTER_DTYPE = np.dtype([("latitude", "<f8"), ("longitude", "<f8"), ("height_m", "<f4"), ("nis", "<f4"),
+                               ("flags", "<u4"), ("reserved", "<u4")])
+FILTER_OPERAND_DTYPE = np.dtype([("time", "<f8"), ("latitude", "<f8"), ("longitude", "<f8"), ("rn", "<f8"),
+                                 ("re", "<f8"), ("var_h", "<f8"), ("var_v", "<f8"), ("height_m", "<f4"),
+                                 ("flags", "<u4")])
+assert AIRCRAFT_FILTER_DTYPE.itemsize == C.sizeof(AdsbAircraftFilter) == 192 and C.sizeof(AdsbTrackFilterCfg) == 96
+assert FRAME_FILTER_DTYPE.itemsize == C.sizeof(AdsbFrameFilter) == 32
+assert FILTER_OPERAND_DTYPE.itemsize == C.sizeof(AdsbFilterOperand) == 64
+
+
 ADSB_TRACK_UNADDRESSED = 0x4        # point flag: the frame's address is not an aircraft's (update_modes)
 ADSB_TRACK_MODES_ALT = 0x1          # adsb_aircraft_modes.flags: the ADSB_MODES_* bit values ...
 ADSB_TRACK_MODES_SQUAWK = 0x4
@@ -648,6 +705,11 @@ PROTOTYPES = {
     "adsb_track_table_fetch_mlat": (C.c_int, [C.c_void_p, _P(AdsbAircraftMlat), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_table_mlat_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "adsb_track_table_fetch_frame_mlat": (C.c_int, [C.c_void_p, _P(AdsbFrameMlat), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_filter_reserve": (C.c_int, [C.c_void_p, _P(AdsbTrackFilterCfg)]),
+    "adsb_track_table_fetch_filter": (C.c_int, [C.c_void_p, _P(AdsbAircraftFilter), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_track_table_filter_device": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "adsb_track_table_fetch_frame_filter": (C.c_int, [C.c_void_p, _P(AdsbFrameFilter), C.c_size_t, _P(C.c_size_t)]),
+    "adsb_debug_track_filter_operands": (C.c_int, [C.c_void_p, _P(AdsbFilterOperand), C.c_size_t, _P(C.c_size_t)]),
     "adsb_track_table_modes_reserve": (C.c_int, [C.c_void_p]),
     "adsb_track_table_update_modes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                 C.c_uint64]),
@@ -774,6 +836,10 @@ PROTOTYPES = {
     "adsb_host_fix_of": (C.c_int, [_P(AdsbSite), _P(C.c_uint8 * 14), C.c_double, _P(AdsbFix), _P(C.c_uint32)]),
     "adsb_host_track_mlat_of": (C.c_int, [C.c_double, _P(C.c_uint8 * 14), _P(AdsbMlatFix), C.c_double,
                                           _P(AdsbAircraftMlat), _P(C.c_uint32), _P(C.c_float)]),
+    "adsb_host_track_filter_operand": (C.c_int, [_P(AdsbTrackFilterCfg), _P(AdsbMlatFix), C.c_double, C.c_int,
+                                                 _P(AdsbFilterOperand)]),
+    "adsb_host_track_filter_step": (C.c_int, [_P(AdsbTrackFilterCfg), _P(AdsbAircraftFilter), _P(AdsbFilterOperand),
+                                              _P(AdsbFrameFilter)]),
     "adsb_host_track_modes_of": (C.c_int, [C.c_void_p, C.c_double, _P(AdsbAircraftModes), _P(C.c_uint32)]),
     "adsb_host_track_modes_merge": (C.c_int, [_P(AdsbAircraftModes), _P(AdsbAircraftModes)]),
     "adsb_host_commb_settle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, _P(AdsbCommbSettleCfg),

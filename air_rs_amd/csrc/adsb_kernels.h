@@ -474,6 +474,7 @@ struct TrackStoreDev {
     // table only, last so that no other member moves
     adsb_aircraft_commb *commb;  // [max_aircraft] beside rec, or null: no commb reserve (likewise; tables only)
     adsb_aircraft_es *es;        // [max_aircraft] beside rec, or null: no es reserve (likewise; tables only)
+    adsb_aircraft_filter *filter; // [max_aircraft] beside rec, or null: no filter reserve (likewise; tables only)
 };
 // Per-frame summaries and the changed list of a table / bank update (adsb_track_*_summaries_reserve): all of it
 // allocated by the reserve.  One segmented inclusive max-scan over the sorted list gives every frame the sorted
@@ -543,6 +544,15 @@ struct TrackMlatDev {
     void *temp;                  // the scan's scratch
     size_t temp_bytes;
     double max_disagreement_m;   // the reserve's limit
+};
+// Filtered mlat track per aircraft (adsb_track_table_filter_reserve; adsb_track_filter.h has the operand's and the
+// step's text): all of it allocated by the reserve.  One thread per sorted frame writes the operand at its sorted
+// position; one thread per segment head walks its segment's operands through the record at store->filter and writes
+// out[] at each usable frame's list index.  No scan, no scratch.
+struct TrackFilterDev {
+    adsb_filter_operand *op;     // [max_frames]: the last update's operands, sorted order
+    adsb_frame_filter *out;      // [max_frames]: one per frame of the last update given fixes, list order
+    adsb_track_filter_cfg cfg;   // the reserve's, every default filled in
 };
 // Mode S replies per aircraft (adsb_track_table_modes_reserve; adsb_track_modes.h has the per-frame text and the
 // combine): all of it allocated by the reserve.  One thread per sorted frame writes the scan's operand at its sorted
@@ -634,6 +644,7 @@ struct TrackArgs {
     const TrackFixDev *fix;      // non-null (with store->fix and store->site): also the per-frame fixes and their merge
     const adsb_mlat_fix *mlat_fixes; // [n] (device), list order: with mlat non-null (and store->mlat), merged into the
     const TrackMlatDev *mlat;    // per-aircraft mlat records; null: the mlat records stay as they are
+    const TrackFilterDev *filter; // non-null (with mlat and store->filter): also the filter behind the mlat merge
     const adsb_commb_rec *commb_recs; // [n] (device), list order: with commb non-null (and modes, store->commb): the
     const TrackCommbDev *commb;       // commb step after the modes merge (update_commb); null: the commb records stay
     const adsb_es_rec *es_recs;       // [n] (device), list order: with es non-null (and store->es): the es step beside
@@ -670,6 +681,8 @@ hipError_t launch_track_fixes_clear(hipStream_t s, adsb_fix *fix, size_t places)
 size_t track_mlat_temp_bytes(size_t n);
 // every mlat record of [0, places) empty: zeros, time NaN (the mlat reserve, and reset)
 hipError_t launch_track_mlat_clear(hipStream_t s, adsb_aircraft_mlat *mlat, size_t places);
+// every filter record of [0, places) empty: zeros, time NaN (the filter reserve, and reset)
+hipError_t launch_track_filter_clear(hipStream_t s, adsb_aircraft_filter *filter, size_t places);
 size_t track_modes_temp_bytes(size_t n); // the 25-bit sort, the admission scan and the modes scan
 // every modes record of [0, places) empty: zeros, the three times NaN (the modes reserve, and reset)
 hipError_t launch_track_modes_clear(hipStream_t s, adsb_aircraft_modes *modes, size_t places);

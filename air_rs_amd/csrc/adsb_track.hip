@@ -97,6 +97,15 @@
 // fix, newest checked frame, greatest disagreement and counts, one thread per segment tail merges into the side record.
 // Admission and expire treat the array as they treat the other two.  Tables only; the templates compile for a bank too.
 //
+// Filtered mlat track per aircraft (adsb_track_table_filter_reserve; every update given fixes): a side array of one
+// 192-byte adsb_aircraft_filter per record place.  Behind the mlat merge, since it needs d.slot, the sort and the fixes
+// and nothing more: one thread per sorted frame writes the frame's 64-byte operand at its sorted position (all the
+// trigonometry; adsb_track_filter.h, the text the CPU mirror compiles too), one thread per segment HEAD -- the mirror
+// image of the merge kernels' tails -- loads the record, steps through its segment's consecutive operands and stores the
+// record once.  No scan: a Kalman step does not combine associatively at a price worth paying, so the critical path is
+// the longest aircraft's part of the list, not the list.  Admission and expire treat the array as they treat the
+// others.  Tables only.
+//
 // Mode S replies per aircraft (adsb_track_table_modes_reserve; the update_modes form): a fourth side array, one 64-byte
 // adsb_aircraft_modes per record place, and a list keyed by adsb_modes_of's addresses.  Instead of track_keys_kernel, a key
 // kernel of its own reads the frame's adsb_modes_rec: the sort key is the address of an accepted frame and 1 << 24 for
@@ -133,6 +142,7 @@
 #include "adsb_fix.h"
 #include "adsb_kernels.h"
 #include "adsb_track_mlat.h"
+#include "adsb_track_filter.h"
 #include "adsb_track_commb.h"
 #include "adsb_track_es.h"
 #include "adsb_track_modes.h"
@@ -329,6 +339,7 @@ __global__ __launch_bounds__(256) void track_admit_kernel(const uint32_t *skeys,
     if (t.modes) ((ModesWords *)t.modes)[r] = modes_empty();
     if (t.commb) ((CommbWords *)t.commb)[r] = commb_empty();
     if (t.es) ((EsWords *)t.es)[r] = es_track_empty();
+    if (t.filter) ((FilterWords *)t.filter)[r] = filter_empty();
 }
 
 // bank only: the receiver split clipped to the list (prefix[0] = 0, prefix[k] = n for k >= n_src), as adsb_fetch's
@@ -1040,6 +1051,97 @@ __global__ __launch_bounds__(256) void track_mlat_clear_kernel(MlatWords *mlat, 
     if (p < places) mlat[p] = mlat_empty();
 }
 
+// ---- filtered mlat track per aircraft (table with a filter reserve) --------------------------------------------------
+// One thread per sorted frame s: the operand of frame i = svals[s] at s, so that the walk reads consecutive records, and
+// the 32 zero bytes of a frame that is not usable at out[i] (the walk writes the usable ones).  sin, cos and the root of
+// the whole feature are here.
+template <TrackKind K>
+__global__ __launch_bounds__(256) void track_filter_operand_kernel(const adsb_frame *frames, const adsb_mlat_fix *fixes,
+                                                                   const uint32_t *skeys, const uint32_t *svals,
+                                                                   uint32_t n, double seconds_per_sample,
+                                                                   uint64_t sample_base, TrackStoreDev d,
+                                                                   TrackFilterDev fl)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t i = svals[s];
+    if (K == TrackKind::kBank) sample_base = d.sample_base[skeys[s] >> 24];
+    const adsb_filter_operand o = filter_operand(fl.cfg, fixes[i], frame_time(frames, i, sample_base, seconds_per_sample),
+                                                 d.slot[s] != kTrackUntracked);
+    fl.op[s] = o;
+    if (!(o.flags & ADSB_TRACK_FILTER_USABLE)) fl.out[i] = adsb_frame_filter{};
+}
+
+// One thread per segment HEAD: the aircraft's record through filter_step, frame after frame in list order, one
+// adsb_frame_filter per usable frame at the frame's list index, the record stored once.  A wave takes as long as the
+// longest segment that begins in it, and its other lanes idle meanwhile.  Workgroups are ONE wave: waves share nothing,
+// a long segment holds up no more than the heads among its own 64 frames, and the waves spread over every CU.  Measured
+// against a build with 256-thread workgroups (profiles/track_filter_timing.txt): 15-23 us faster on
+// 32 768 frames of 2 048 aircraft, 3-8 % slower on 32 768 frames of one.  The record (48 registers) and two operands (16
+// each) stay in registers; a step is some sixty dependent f64 operations, ten of them divisions, and needs three loads
+// (the next key, the 64-byte operand, its list index) whose addresses do not depend on the step before: frame j + 1's
+// are issued BEFORE frame j's step, so their latency lies under its arithmetic (13 % off the one-aircraft list).  The
+// next operand is read whoever it belongs to; the last frame of the list reads itself again, so no index passes n - 1.
+#ifndef ADSB_FILTER_WALK_BLOCK
+#define ADSB_FILTER_WALK_BLOCK 64 // the 256-thread build of that measurement sets it
+#endif
+constexpr uint32_t kFilterWalkBlock = ADSB_FILTER_WALK_BLOCK;
+template <TrackKind K>
+__global__ __launch_bounds__(kFilterWalkBlock) void track_filter_walk_kernel(const uint32_t *skeys, const uint32_t *svals,
+                                                                             uint32_t n, TrackStoreDev d,
+                                                                             TrackFilterDev fl)
+{
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t key = skeys[s];
+    if (s != 0 && skeys[s - 1] == key) return; // not a head
+    const uint32_t slot = d.slot[s];
+    if (slot == kTrackUntracked) return; // none of its frames is usable: the operand kernel wrote their outputs
+    FilterWords words = ((const FilterWords *)d.filter)[slot - 1];
+    adsb_aircraft_filter a;
+    __builtin_memcpy(&a, &words, sizeof(a));
+    bool touched = false;
+    adsb_filter_operand o = fl.op[s];
+    uint32_t i = svals[s];
+    for (uint32_t j = s;;) {
+        const uint32_t jn = j + 1, jc = jn < n ? jn : j; // the last frame of the list reads itself again: no branch
+        const uint32_t key_n = skeys[jc], i_n = svals[jc];
+        const adsb_filter_operand o_n = fl.op[jc];
+        if (o.flags & ADSB_TRACK_FILTER_USABLE) {
+            adsb_frame_filter f;
+            filter_step(fl.cfg, a, o, f);
+            fl.out[i] = f;
+            touched = true;
+        }
+        if (jn >= n || key_n != key) break;
+        o = o_n;
+        i = i_n;
+        j = jn;
+    }
+    if (!touched) return;
+    for (int k = 0; k < 8; ++k) a.reserved[k] = 0; // what it was: written as constants, the array stays out of memory
+    __builtin_memcpy(&words, &a, sizeof(a));
+    ((FilterWords *)d.filter)[slot - 1] = words;
+}
+
+template <TrackKind K>
+hipError_t launch_filter(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d)
+{
+    const TrackFilterDev &fl = *a.filter;
+    hipLaunchKernelGGL(track_filter_operand_kernel<K>, dim3((a.n + 255) / 256), dim3(256), 0, st, a.frames, a.mlat_fixes,
+                       (const uint32_t *)a.skeys, (const uint32_t *)a.svals, a.n, a.seconds_per_sample, a.sample_base, d,
+                       fl);
+    hipLaunchKernelGGL(track_filter_walk_kernel<K>, dim3((a.n + kFilterWalkBlock - 1) / kFilterWalkBlock),
+                       dim3(kFilterWalkBlock), 0, st, (const uint32_t *)a.skeys, (const uint32_t *)a.svals, a.n, d, fl);
+    return hipSuccess;
+}
+
+__global__ __launch_bounds__(256) void track_filter_clear_kernel(FilterWords *filter, uint64_t places)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < places) filter[p] = filter_empty();
+}
+
 // ---- Mode S replies per aircraft (table with a modes reserve) --------------------------------------------------------
 // update_modes' key kernel, in place of track_keys_kernel: one thread per frame i < n.  The key is the record's address
 // (< 2^24) for an accepted frame and kModesNoAddress for every other; fields[i] gets that address, and unless the frame
@@ -1620,6 +1722,7 @@ __global__ __launch_bounds__(256) void track_expire_compact_kernel(TrackStoreDev
     if (d.modes) ((ModesWords *)d.modes)[g] = ((const ModesWords *)d.modes)[base + lo];
     if (d.commb) ((CommbWords *)d.commb)[g] = ((const CommbWords *)d.commb)[base + lo];
     if (d.es) ((EsWords *)d.es)[g] = ((const EsWords *)d.es)[base + lo];
+    if (d.filter) ((FilterWords *)d.filter)[g] = ((const FilterWords *)d.filter)[base + lo];
     if (!kBank) d.index[moved.a.icao] = i + 1u;
 }
 
@@ -2070,6 +2173,14 @@ hipError_t launch_track_mlat_clear(hipStream_t st, adsb_aircraft_mlat *mlat, siz
     return hipGetLastError();
 }
 
+hipError_t launch_track_filter_clear(hipStream_t st, adsb_aircraft_filter *filter, size_t places)
+{
+    if (places == 0) return hipSuccess;
+    hipLaunchKernelGGL(track_filter_clear_kernel, dim3((uint32_t)((places + 255) / 256)), dim3(256), 0, st,
+                       (FilterWords *)filter, (uint64_t)places);
+    return hipGetLastError();
+}
+
 hipError_t launch_track_fixes_clear(hipStream_t st, adsb_fix *fix, size_t places)
 {
     if (places == 0) return hipSuccess;
@@ -2115,6 +2226,10 @@ hipError_t track_tail(hipStream_t st, const TrackArgs &a, const TrackStoreDev &d
         if (e != hipSuccess) return e;
         if (a.mlat && d.mlat) e = launch_mlat_merge<K>(st, a, d); // needs d.slot, the frame bytes and the fixes only
         if (e != hipSuccess) return e;
+        if constexpr (K == TrackKind::kTable) {
+            if (a.mlat && d.mlat && a.filter && d.filter) e = launch_filter<K>(st, a, d); // d.slot, the sort, the fixes
+            if (e != hipSuccess) return e;
+        }
         if constexpr (K == TrackKind::kTable) {
             if (a.es && d.es) e = launch_es_merge(st, a, d); // needs d.slot, the es records and its own side array only
             if (e != hipSuccess) return e;

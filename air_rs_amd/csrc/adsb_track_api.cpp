@@ -14,6 +14,7 @@
 #include "adsb_fix.h"
 #include "adsb_scratch.h"
 #include "adsb_track_mlat.h"
+#include "adsb_track_filter.h"
 #include "adsb_track_modes.h"
 
 using adsbk::TrackKind;
@@ -113,7 +114,7 @@ struct TrackStore {
     uint32_t n_receivers = 0, max_aircraft = 0; // max_aircraft: per receiver
     // One block of device memory per lifetime, carved into the arrays below (adsb_scratch.h): the store's own from
     // create to destroy, and one per reserve.  Every device pointer of the store points into one of them.
-    DevBuf<char> mem, sum_mem, lvl_mem, fix_mem, mlat_mem, modes_mem, commb_mem, es_mem;
+    DevBuf<char> mem, sum_mem, lvl_mem, fix_mem, mlat_mem, modes_mem, commb_mem, es_mem, filter_mem;
     adsbk::TrackStoreDev dev{};     // records [R x max_aircraft], slot [max_frames]; index [2^24] or hash, prefix, scan words
     uint32_t *words = nullptr;      // [3R]: size, flags, size_next (dev.size / dev.flags / dev.size_next)
     uint32_t *u32 = nullptr;        // 4 x [max_frames]: keys, vals, sorted keys, sorted vals
@@ -145,6 +146,10 @@ struct TrackStore {
     adsb_mlat_fix *mlat_pinned = nullptr; // [max_frames]: pinned staging of that copy (s.copied covers it too)
     uint32_t mlat_n = 0;                  // frames of the last update_mlat
     bool mlat_updated = false;            // an update_mlat ran since the reserve (and since the last reset)
+    // filtered mlat track per aircraft (adsb_track_table_filter_reserve): all of it carved by the reserve; dev.filter
+    // null = none.  Its per-frame arrays speak of the list mlat_n counts.
+    adsbk::TrackFilterDev filter{};
+    bool filter_updated = false;          // an update given fixes ran since the reserve (and since the last reset)
     // Mode S replies per aircraft (adsb_track_table_modes_reserve): all of it made by the reserve; dev.modes null = none
     adsbk::TrackModesDev modes{};
     adsb_modes_rec *modes_recs = nullptr;   // [max_frames]: device copy of a host recs array
@@ -227,6 +232,22 @@ static void store_mlat_drop(TrackStore &s)
     s.dev.mlat = nullptr;
     s.mlat = {};
     s.mlat_fixes = nullptr;
+}
+
+// The filter reserve undone, under the same condition.
+static void store_filter_drop(TrackStore &s)
+{
+    drop(s.filter_mem);
+    s.dev.filter = nullptr;
+    s.filter = {};
+}
+
+// The list fetch_frame_mlat (and, with a filter reserve, fetch_frame_filter) speaks of: n frames
+static void store_mlat_list(TrackStore &s, size_t n)
+{
+    s.mlat_n = (uint32_t)n;
+    s.mlat_updated = true;
+    if (s.dev.filter) s.filter_updated = true;
 }
 
 // The modes reserve undone, under the same condition.
@@ -317,6 +338,7 @@ static void store_release(TrackStore &s)
     store_modes_drop(s);
     store_commb_drop(s);
     store_es_drop(s);
+    drop(s.filter_mem);
     pinned_free(s.pinned);
     pinned_free(s.lvl_pinned);
     pinned_free(s.mlat_pinned);
@@ -338,6 +360,8 @@ static int store_reset(TrackStore *s)
     if (s->dev.modes) HIPCHK(adsbk::launch_track_modes_clear(s->ctx->aux, s->dev.modes, s->places()));
     if (s->dev.commb) HIPCHK(adsbk::launch_track_commb_clear(s->ctx->aux, s->dev.commb, s->places()));
     s->mlat_updated = false;
+    if (s->dev.filter) HIPCHK(adsbk::launch_track_filter_clear(s->ctx->aux, s->dev.filter, s->places()));
+    s->filter_updated = false;
     if (s->dev.es) HIPCHK(adsbk::launch_track_es_clear(s->ctx->aux, s->dev.es, s->places()));
     s->commb_updated = false;
     s->es_updated = false;
@@ -443,6 +467,7 @@ static int store_run(TrackStore &s, const adsb_frame *list, size_t n, uint64_t s
     a.fix = dev.fix ? &s.fix : nullptr;
     a.mlat_fixes = mlat_fixes;
     a.mlat = mlat_fixes ? &s.mlat : nullptr;
+    a.filter = mlat_fixes && dev.filter ? &s.filter : nullptr;
     if (recs) {
         a.modes_recs = recs;
         a.modes = &s.modes;
@@ -470,6 +495,7 @@ static const adsb_frame_fix *frame_fixes_of(TrackStore &s) { return s.dev.fix &&
 static const adsb_aircraft_level *levels_of(TrackStore &s) { return s.dev.lvl; }
 static const adsb_fix *fixes_of(TrackStore &s) { return s.dev.fix; }
 static const adsb_aircraft_mlat *mlat_of(TrackStore &s) { return s.dev.mlat; }
+static const adsb_aircraft_filter *filter_of(TrackStore &s) { return s.dev.filter; }
 static const adsb_aircraft_modes *modes_of(TrackStore &s) { return s.dev.modes; }
 static const adsb_aircraft_commb *commb_of(TrackStore &s) { return s.dev.commb; }
 static const adsb_aircraft_es *es_of(TrackStore &s) { return s.dev.es; }
@@ -753,6 +779,30 @@ static int store_mlat_reserve(TrackStore *st, double max_disagreement_m)
     return ADSB_OK;
 }
 
+// ---- filtered mlat track per aircraft --------------------------------------------------------------------------------
+// Waits for the device (the clear); a second reserve keeps what the first one made, its cfg too.  cfg: resolved.
+static int store_filter_reserve(TrackStore *st, const adsb_track_filter_cfg &cfg)
+{
+    HIPCHK(hipSetDevice(st->ctx->cfg.device));
+    if (!st->dev.mlat) return ADSB_E_STATE;
+    if (st->dev.filter) return ADSB_OK;
+    const size_t nf = (size_t)st->max_frames;
+    st->filter.cfg = cfg;
+    const int rc = carve_block(st->ctx, st->filter_mem, [&](Carve &k) {
+        st->dev.filter = k.take<adsb_aircraft_filter>(st->places());
+        st->filter.op = k.take<adsb_filter_operand>(nf);
+        st->filter.out = k.take<adsb_frame_filter>(nf);
+    });
+    if (rc != ADSB_OK || adsbk::launch_track_filter_clear(st->ctx->aux, st->dev.filter, st->places()) != hipSuccess ||
+        hipStreamSynchronize(st->ctx->aux) != hipSuccess) {
+        (void)hipGetLastError();
+        store_filter_drop(*st);
+        return ADSB_E_NOMEM;
+    }
+    st->filter_updated = false;
+    return ADSB_OK;
+}
+
 // ---- Mode S replies per aircraft --------------------------------------------------------------------------------------
 // Waits for the device (the clear); a second reserve keeps what the first one made
 static int store_modes_reserve(TrackStore *st)
@@ -873,10 +923,7 @@ static int track_table_update(adsb_track_table *t, const adsb_frame *frames, con
     if (n > t->max_frames) return ADSB_E_CAPACITY;
     adsb_ctx *c = t->ctx;
     HIPCHK(hipSetDevice(c->cfg.device));
-    if (fixes) { // the list fetch_frame_mlat speaks of
-        t->mlat_n = (uint32_t)n;
-        t->mlat_updated = true;
-    }
+    if (fixes) store_mlat_list(*t, n);
     if (!store_begin_update(*t, n)) return ADSB_OK;
     const adsb_frame *list = frames;
     const bool frames_host = !in_device_memory(c, frames), levels_host = levels && !in_device_memory(c, levels);
@@ -969,10 +1016,7 @@ extern "C" int adsb_track_table_update_mlat(adsb_track_table *t, const adsb_fram
     if (!t || (!frames && n) || (!fixes && n)) return ADSB_E_ARG;
     if (!t->dev.mlat || (levels && !t->dev.lvl)) return ADSB_E_STATE;
     if (n > t->max_frames) return ADSB_E_CAPACITY;
-    if (n == 0) { // nothing to launch: the last update_mlat's list is empty
-        t->mlat_n = 0;
-        t->mlat_updated = true;
-    }
+    if (n == 0) store_mlat_list(*t, 0); // nothing to launch: the last update_mlat's list is empty
     return track_table_update(t, frames, n ? levels : nullptr, n, sample_base, n ? fixes : nullptr);
 }
 
@@ -984,6 +1028,47 @@ extern "C" int adsb_track_table_fetch_mlat(adsb_track_table *t, adsb_aircraft_ml
 extern "C" int adsb_track_table_mlat_device(adsb_track_table *t, const adsb_aircraft_mlat **dev)
 {
     return store_device(t, mlat_of, dev);
+}
+
+extern "C" int adsb_track_table_filter_reserve(adsb_track_table *t, const adsb_track_filter_cfg *cfg)
+{
+    adsb_track_filter_cfg use;
+    if (!t || !adsbk::filter_cfg_resolve(cfg, use)) return ADSB_E_ARG; // before the handle is read
+    return store_filter_reserve(t, use);
+}
+
+extern "C" int adsb_track_table_fetch_filter(adsb_track_table *t, adsb_aircraft_filter *out, size_t max, size_t *n)
+{
+    return store_fetch_side(t, filter_of, out, max, n);
+}
+
+extern "C" int adsb_track_table_filter_device(adsb_track_table *t, const adsb_aircraft_filter **dev)
+{
+    return store_device(t, filter_of, dev);
+}
+
+// Waits.  The first min(list, max) records of a per-frame array of the filter, over the last update given fixes
+template <class T>
+static int table_fetch_filter_frames(adsb_track_table *t, const T *src, T *out, size_t max, size_t *n)
+{
+    if (!t || (!out && max)) return ADSB_E_ARG;
+    if (!t->dev.filter || !t->filter_updated) return ADSB_E_STATE;
+    HIPCHK(hipSetDevice(t->ctx->cfg.device));
+    const size_t take = std::min<size_t>(t->mlat_n, max);
+    if (take) HIPCHK(hipMemcpyAsync(out, src, sizeof(T) * take, hipMemcpyDeviceToHost, t->ctx->aux));
+    HIPCHK(hipStreamSynchronize(t->ctx->aux));
+    if (n) *n = take;
+    return ADSB_OK;
+}
+
+extern "C" int adsb_track_table_fetch_frame_filter(adsb_track_table *t, adsb_frame_filter *out, size_t max, size_t *n)
+{
+    return table_fetch_filter_frames(t, t ? t->filter.out : nullptr, out, max, n);
+}
+
+extern "C" int adsb_debug_track_filter_operands(adsb_track_table *t, adsb_filter_operand *out, size_t max, size_t *n)
+{
+    return table_fetch_filter_frames(t, t ? t->filter.op : nullptr, out, max, n);
 }
 
 extern "C" int adsb_track_table_modes_reserve(adsb_track_table *t)
@@ -999,10 +1084,7 @@ extern "C" int adsb_track_table_update_modes(adsb_track_table *t, const adsb_fra
     if (!t || (!frames && n) || (!recs && n)) return ADSB_E_ARG;
     if (!t->dev.modes || (fixes && !t->dev.mlat) || (levels && !t->dev.lvl)) return ADSB_E_STATE;
     if (n > t->max_frames) return ADSB_E_CAPACITY;
-    if (n == 0 && fixes) { // nothing to launch: the last update with fixes has an empty list
-        t->mlat_n = 0;
-        t->mlat_updated = true;
-    }
+    if (n == 0 && fixes) store_mlat_list(*t, 0); // nothing to launch: the last update with fixes has an empty list
     return track_table_update(t, frames, n ? levels : nullptr, n, sample_base, n ? fixes : nullptr, n ? recs : nullptr);
 }
 
@@ -1033,10 +1115,7 @@ extern "C" int adsb_track_table_update_commb(adsb_track_table *t, const adsb_fra
     if (n == 0) { // nothing to launch: the last update_commb's list is empty
         t->commb_n = 0;
         t->commb_updated = true;
-        if (fixes) {
-            t->mlat_n = 0;
-            t->mlat_updated = true;
-        }
+        if (fixes) store_mlat_list(*t, 0);
     }
     return track_table_update(t, frames, n ? levels : nullptr, n, sample_base, n ? fixes : nullptr, n ? recs : nullptr,
                               n ? commb : nullptr);
@@ -1091,10 +1170,7 @@ extern "C" int adsb_track_table_update_es(adsb_track_table *t, const adsb_frame 
             t->commb_n = 0;
             t->commb_updated = true;
         }
-        if (fixes) {
-            t->mlat_n = 0;
-            t->mlat_updated = true;
-        }
+        if (fixes) store_mlat_list(*t, 0);
     }
     return track_table_update(t, frames, n ? levels : nullptr, n, sample_base, n ? fixes : nullptr, n ? recs : nullptr,
                               n ? commb : nullptr, n ? es : nullptr);

@@ -155,6 +155,83 @@ def host_track_mlat_of(max_disagreement_m, frame_bytes, fix, time=0.0):
     return out[0], flags.value, np.float32(dis.value)
 
 
+AIRCRAFT_FILTER_DTYPE, FRAME_FILTER_DTYPE = L.AIRCRAFT_FILTER_DTYPE, L.FRAME_FILTER_DTYPE  # TrackTable.filter / frame_filter
+FILTER_OPERAND_DTYPE = L.FILTER_OPERAND_DTYPE
+FILTER_CFG_FIELDS = tuple(name for name, _ in L.AdsbTrackFilterCfg._fields_ if name != "reserved")
+
+
+def _filter_cfg(**cfg):
+    """An adsb_track_filter_cfg of keyword arguments (FILTER_CFG_FIELDS); what is not given is 0, the default."""
+    unknown = set(cfg) - set(FILTER_CFG_FIELDS)
+    if unknown:
+        raise TypeError(f"filter cfg: unknown field(s) {sorted(unknown)}")
+    c = L.AdsbTrackFilterCfg()
+    for name, value in cfg.items():
+        setattr(c, name, int(value) if name in ("max_outliers", "min_run") else float(value))
+    return c
+
+
+def filter_empty(n=1):
+    """n EMPTY AIRCRAFT_FILTER_DTYPE records: all zeros with time NaN."""
+    out = np.zeros(n, dtype=AIRCRAFT_FILTER_DTYPE)
+    out["time"] = np.nan
+    return out
+
+
+def host_track_filter_operand(fix, time, counted=True, **cfg):
+    """adsb_host_track_filter_operand, the CPU mirror of a filter reserve's per-frame kernel: the FILTER_OPERAND_DTYPE
+    record of a frame with the MLAT_FIX_DTYPE record `fix` at frame time `time`.  Needs no device."""
+    f = np.zeros(1, dtype=L.MLAT_FIX_DTYPE)
+    f[0] = fix
+    out = np.zeros(1, dtype=FILTER_OPERAND_DTYPE)
+    c = _filter_cfg(**cfg)
+    L.check(L.load().adsb_host_track_filter_operand(C.byref(c), f.ctypes.data_as(C.POINTER(L.AdsbMlatFix)), float(time),
+                                                    1 if counted else 0,
+                                                    out.ctypes.data_as(C.POINTER(L.AdsbFilterOperand))),
+            "adsb_host_track_filter_operand")
+    return out[0]
+
+
+def host_track_filter_step(record, operand, **cfg):
+    """adsb_host_track_filter_step, the CPU mirror of one step of a filter reserve's walk: (the AIRCRAFT_FILTER_DTYPE
+    record after a frame with the FILTER_OPERAND_DTYPE record `operand`, that frame's FRAME_FILTER_DTYPE record).
+    record: the aircraft's so far (filter_empty()[0] for none).  Needs no device."""
+    r = np.zeros(1, dtype=AIRCRAFT_FILTER_DTYPE)
+    r[0] = record
+    o = np.zeros(1, dtype=FILTER_OPERAND_DTYPE)
+    o[0] = operand
+    f = np.zeros(1, dtype=FRAME_FILTER_DTYPE)
+    c = _filter_cfg(**cfg)
+    L.check(L.load().adsb_host_track_filter_step(C.byref(c), r.ctypes.data_as(C.POINTER(L.AdsbAircraftFilter)),
+                                                 o.ctypes.data_as(C.POINTER(L.AdsbFilterOperand)),
+                                                 f.ctypes.data_as(C.POINTER(L.AdsbFrameFilter))),
+            "adsb_host_track_filter_step")
+    return r[0], f[0]
+
+
+FILTER_PHYSICAL_DTYPE = np.dtype([("ground_speed_kt", "<f8"), ("track_deg", "<f8"), ("vertical_rate_fpm", "<f8"),
+                                  ("position_sigma_m", "<f8"), ("speed_sigma_kt", "<f8")])
+
+
+def filter_physical(recs):
+    """AIRCRAFT_FILTER_DTYPE records in the units a display shows -> FILTER_PHYSICAL_DTYPE: ground speed in knots, track
+    in degrees clockwise from north in [0, 360), vertical rate in ft/min, and the 1-sigma of the horizontal position
+    (metres) and of the ground speed (knots) from the covariance's diagonals.  NaN where ADSB_TRACK_FILTER_VELOCITY is
+    unset (position_sigma_m: where RUNNING is)."""
+    recs = np.atleast_1d(np.asarray(recs, dtype=AIRCRAFT_FILTER_DTYPE))
+    out = np.full(len(recs), np.nan, dtype=FILTER_PHYSICAL_DTYPE)
+    running = (recs["flags"] & L.ADSB_TRACK_FILTER_RUNNING) != 0
+    vel = (recs["flags"] & L.ADSB_TRACK_FILTER_VELOCITY) != 0
+    kt = 3600.0 / 1852.0
+    vn, ve = recs["v_north"], recs["v_east"]
+    out["ground_speed_kt"][vel] = (np.hypot(vn, ve) * kt)[vel]
+    out["track_deg"][vel] = (np.degrees(np.arctan2(ve, vn)) % 360.0)[vel]
+    out["vertical_rate_fpm"][vel] = (recs["v_up"] * (60.0 / 0.3048))[vel]
+    out["position_sigma_m"][running] = np.sqrt(recs["p_north"][:, 0] + recs["p_east"][:, 0])[running]
+    out["speed_sigma_kt"][vel] = (np.sqrt((recs["p_north"][:, 2] + recs["p_east"][:, 2]) / 2.0) * kt)[vel]
+    return out
+
+
 def host_track_modes_of(rec, time=0.0):
     """adsb_host_track_modes_of, the CPU mirror of a modes reserve's per-frame step: (AIRCRAFT_MODES_DTYPE record of an
     aircraft whose only counted frame is the one with the MODES_DTYPE record `rec`, heard at `time`; whether the frame
@@ -2155,6 +2232,39 @@ class TrackTable(_TrackStore):
         dev = C.c_void_p()
         self._call("mlat_device", C.byref(dev))
         return dev.value
+
+    def filter_reserve(self, **cfg):
+        """adsb_track_table_filter_reserve (after mlat_reserve): one AIRCRAFT_FILTER_DTYPE record beside every aircraft
+        record; every update given `mlat` then also runs each aircraft's fixes through a Kalman filter (position and
+        velocity on north, east and up).  cfg: FILTER_CFG_FIELDS, each 0 or absent for its default."""
+        c = _filter_cfg(**cfg)
+        self._call("filter_reserve", C.byref(c))
+
+    def filter(self):
+        """AIRCRAFT_FILTER_DTYPE records (each aircraft's filtered mlat track), aligned with aircraft()[0];
+        filter_physical() gives speed, track and vertical rate."""
+        return self._fetch("fetch_filter", [AIRCRAFT_FILTER_DTYPE])[0]
+
+    def frame_filter(self):
+        """One FRAME_FILTER_DTYPE record per frame of the last update given `mlat`, in its list order: the aircraft's
+        filtered position right after the frame, its nis and what the filter did with it."""
+        return self._fetch("fetch_frame_filter", [FRAME_FILTER_DTYPE], size=self.max_frames)[0]
+
+    def filter_device(self):
+        """Device address of the filter records, one per record place in slot order (as levels_device); no
+        synchronisation."""
+        dev = C.c_void_p()
+        self._call("filter_device", C.byref(dev))
+        return dev.value
+
+    def filter_operands(self):
+        """adsb_debug_track_filter_operands: the FILTER_OPERAND_DTYPE records of the last update given `mlat`, in SORTED
+        order (ascending address, list order within one).  For tests."""
+        n = C.c_size_t()
+        out = np.zeros(max(self.max_frames, 1), dtype=FILTER_OPERAND_DTYPE)
+        L.check(self._lib.adsb_debug_track_filter_operands(self._h, out.ctypes.data_as(C.POINTER(L.AdsbFilterOperand)),
+                                                           len(out), C.byref(n)), "adsb_debug_track_filter_operands")
+        return out[:n.value].copy()
 
     def modes_reserve(self):
         """adsb_track_table_modes_reserve: one AIRCRAFT_MODES_DTYPE record beside every aircraft record, which an update

@@ -1934,6 +1934,130 @@ int adsb_track_table_mlat_device(adsb_track_table *table, const adsb_aircraft_ml
 int adsb_track_table_fetch_frame_mlat(adsb_track_table *table, adsb_frame_mlat *out, size_t max, size_t *n);
 
 /*
+ * Filtered mlat track per aircraft.  A single multilaterated fix scatters by hdop x 30..100 m, one wild fix would be the
+ * aircraft's position until the next, and an aircraft without ADS-B has no velocity at all.  With a FILTER reserve
+ * (beside the mlat reserve it needs) every update that merges fixes (update_mlat, and update_modes / update_commb /
+ * update_es given fixes) also runs each aircraft's fixes, in list order, through a small Kalman filter whose state is one
+ * 192-byte adsb_aircraft_filter per record place.  Tables only.  The definition is this project's own.
+ *
+ * PER FRAME, THE OPERAND (adsb_filter_operand, 64 bytes).  A frame is USABLE iff it is counted (its point is not
+ *   ADSB_TRACK_UNTRACKED, and for update_modes its address is an aircraft's), its fix has ADSB_MLAT_VALID, latitude,
+ *   longitude and height_m are finite with |latitude| <= 89 and height_m in [-1000, 100000], hdop is finite and in
+ *   (0, max_hdop], and var_h below is finite.  Every other frame's operand is 64 zero bytes.  A usable frame's holds
+ *     time      the store's frame time (sample_base + offset) x seconds_per_sample, the one rounded product
+ *     latitude, longitude  the fix's;  height_m  the fix's, rounded to f32 once (as adsb_aircraft_mlat's)
+ *     rn, re    metres per degree of latitude / of longitude at the fix: with s = sin(lat), w2 = 1 - e2 s^2, w = sqrt(w2),
+ *               M = a (1 - e2) / (w2 w), N = a / w (WGS84 a, e2):  rn = (M + h) x pi/180,  re = (N + h) x cos(lat) x pi/180
+ *     sr        = residual_rms_m if that is greater than range_sigma_m, else range_sigma_m (a NaN residual gives the latter)
+ *     var_h     = (hdop x sr)^2
+ *     var_v     = altitude_sigma_m^2 if the fix has ADSB_MLAT_ALTITUDE, else (vdop x sr)^2
+ *     HEIGHT    the vertical axis is measured: var_v is finite and, without ADSB_MLAT_ALTITUDE, vdop is in (0, max_vdop].
+ *               Without HEIGHT the var_v field holds (max_vdop x sr)^2 instead, what a start gives the up axis.
+ *   All trigonometry and every root of the feature is here; the walk has only + - x / and compares.
+ * PER AIRCRAFT, THE WALK over its usable frames in list order.  Three independent 2-state filters (position, velocity;
+ *   symmetric covariance Ppp, Ppv, Pvv) on north, east and up metres, white-acceleration model with q = accel_h^2 for
+ *   north and east and accel_v^2 for up.  For a usable frame with operand o and the aircraft's record r:
+ *     START  latitude, longitude, height_m = o's; velocities 0; P = (var, 0, init_speed_sigma^2) per axis (var_h and
+ *       init_speed_sigma_h for north and east, o.var_v and init_speed_sigma_v for up); time = o.time; run = 1,
+ *       outliers_run = 0; RUNNING set, HEIGHT as o's.  The frame is INIT and its nis is 0.  A record that is not
+ *       RUNNING starts at its first usable frame.
+ *     dt = o.time - r.time.  !(dt >= 0) (out of order, or NaN): the frame is SKIPPED, n_skipped + 1, nothing else
+ *       changes.  dt > reset_gap_s: n_reset + 1 and START (RESET | INIT).
+ *     PREDICT per axis:  p = v dt;  P'pp = Ppp + 2 dt Ppv + dt^2 Pvv + q dt^4 / 4;  P'pv = Ppv + dt Pvv + q dt^3 / 2;
+ *       P'vv = Pvv + q dt^2.
+ *     MEASURED displacement from the estimate:  zn = (o.latitude - r.latitude) rn;  ze = wrap(o.longitude - r.longitude)
+ *       re;  zu = o.height_m - r.height_m.  wrap adds or subtracts 360 once, to land in [-180, 180].
+ *     INNOVATION  y = z - p,  S = P'pp + var;  nis = yn^2 / Sn + ye^2 / Se (horizontal only, two degrees of freedom).
+ *     nis > gate^2: the frame is an OUTLIER, n_outlier + 1, outliers_run + 1, last_nis = nis; state and time are
+ *       untouched, so the next fix predicts from the last applied state.  If outliers_run has now reached max_outliers
+ *       the aircraft really is elsewhere: n_reset + 1 and START (OUTLIER | RESET | INIT; the frame keeps its nis).
+ *     Otherwise the frame is APPLIED, per measured axis:  Kp = P'pp / S, Kv = P'pv / S;  d = p + Kp y;  v += Kv y;
+ *       P = ((1 - Kp) P'pp, (1 - Kp) P'pv, P'vv - Kv P'pv).  An up axis without HEIGHT takes d = p, P = P'; with it
+ *       the record's HEIGHT is set.  Then latitude += dn / rn, longitude = wrap(longitude + de / re), height_m += du,
+ *       time = o.time, n_applied + 1, run + 1, outliers_run = 0, last_nis = nis.
+ *     VELOCITY is set in the record exactly while run >= min_run.
+ *   f64 throughout with contraction off; the four counts and run saturate at 2^32 - 1.
+ * The state is in the record and each frame's operand is its own, so one list (frames and fixes alike) cut into any
+ * sequence of updates gives the same 192 bytes per aircraft and the same per-frame outputs, and two runs give the same
+ * bytes.  An EMPTY record is all zeros with time NaN.  A place is emptied at admission, at re-admission after an expire,
+ * and at a reset; expire moves a survivor's filter record with its record.
+ * On the device, behind the mlat merge: one thread per sorted frame writes the operand at its sorted position (and 32
+ * zero bytes of output for a frame that is not usable), then one thread per segment HEAD loads the record once, steps
+ * through its segment's operands, which lie consecutively, writes one adsb_frame_filter per usable frame at the frame's
+ * list index and the record once at the end.  No atomics, no LDS, nothing read back.  The critical path of that walk is
+ * the LONGEST aircraft's part of the list, not the list: nothing here is linear however long one aircraft's part is.  It
+ * is cheap because a step is some sixty f64 operations on registers and one 64-byte load.  Device memory, all of it
+ * allocated by the reserve and none before: 192 bytes per place of max_aircraft and 64 + 32 bytes per frame of
+ * max_frames.  A table that never reserves allocates nothing, launches exactly the kernels it launched before and
+ * returns the same bytes; with the reserve every other array of the table is byte for byte what it is without.
+ * fetch_changed, the per-frame summaries and a bank's fused view carry no filter records.
+ */
+#define ADSB_TRACK_FILTER_RUNNING  0x1u   /* adsb_aircraft_filter.flags: the record holds a state           */
+#define ADSB_TRACK_FILTER_VELOCITY 0x2u   /* run >= min_run: the velocities are worth showing               */
+#define ADSB_TRACK_FILTER_HEIGHT   0x4u   /* record: the up axis has been measured since the start; operand: it is */
+#define ADSB_TRACK_FILTER_USABLE   0x100u /* adsb_frame_filter.flags and adsb_filter_operand.flags          */
+#define ADSB_TRACK_FILTER_APPLIED  0x200u /* adsb_frame_filter.flags only, as are the next four             */
+#define ADSB_TRACK_FILTER_INIT     0x400u
+#define ADSB_TRACK_FILTER_RESET    0x800u
+#define ADSB_TRACK_FILTER_OUTLIER  0x1000u
+#define ADSB_TRACK_FILTER_SKIPPED  0x2000u
+typedef struct adsb_track_filter_cfg { /* 96 bytes; every field is policy, not a measurement; 0 takes the default */
+    double   accel_h, accel_v;          /* m/s^2, 1-sigma of the white acceleration; 3, 1.5              */
+    double   range_sigma_m;             /* floor of the range error a dilution multiplies; 30            */
+    double   altitude_sigma_m;          /* of a message's own altitude; 15                               */
+    double   gate;                      /* sigmas; 4                                                     */
+    double   reset_gap_s;               /* 30                                                            */
+    double   init_speed_sigma_h, init_speed_sigma_v; /* m/s; 300, 30                                     */
+    double   max_hdop, max_vdop;        /* 20, 50                                                        */
+    uint32_t max_outliers, min_run;     /* 3, 4                                                          */
+    uint64_t reserved;                  /* 0 */
+} adsb_track_filter_cfg;
+typedef struct adsb_aircraft_filter {  /* 192 bytes, one per record place, beside the 128-byte record */
+    double   time;                      /* frame time of the last START or APPLIED frame; NaN if none    */
+    double   latitude, longitude;       /* degrees, filtered                                             */
+    double   height_m;
+    double   v_north, v_east, v_up;     /* m/s                                                           */
+    double   p_north[3], p_east[3], p_up[3]; /* Ppp (m^2), Ppv (m^2/s), Pvv (m^2/s^2) of each axis       */
+    uint32_t n_applied, n_outlier, n_reset, n_skipped; /* saturating                                     */
+    uint32_t run;                       /* START and APPLIED frames since the last START; saturating     */
+    uint32_t outliers_run;              /* OUTLIER frames since the last START or APPLIED one            */
+    float    last_nis;                  /* of the newest APPLIED or OUTLIER frame (rounded to f32 once)  */
+    uint32_t flags;                     /* ADSB_TRACK_FILTER_RUNNING / VELOCITY / HEIGHT                 */
+    uint32_t reserved[8];               /* 0 */
+} adsb_aircraft_filter;
+typedef struct adsb_frame_filter {     /* 32 bytes, one per frame of the last update given fixes, in its list order */
+    double   latitude, longitude;       /* the aircraft's filtered position right after this frame       */
+    float    height_m, nis;             /* each rounded to f32 once                                      */
+    uint32_t flags;                     /* USABLE, and APPLIED / INIT / RESET / OUTLIER / SKIPPED; 0: not usable, all else 0 */
+    uint32_t reserved;                  /* 0 */
+} adsb_frame_filter;
+typedef struct adsb_filter_operand {   /* 64 bytes per frame, in SORTED order: what the walk reads (see above) */
+    double   time, latitude, longitude;
+    double   rn, re, var_h, var_v;
+    float    height_m;
+    uint32_t flags;                     /* USABLE, HEIGHT; 0: not usable, all else 0 */
+} adsb_filter_operand;
+/* Allocates the above, keeps the cfg (NULL: every default) and empties every filter record.  May wait for the device.
+ * A second reserve changes nothing (the first cfg stays).  ADSB_E_ARG for a NULL table, or a cfg field that is neither
+ * 0 nor finite and > 0, or a reserved that is not 0 (checked before the table is touched); ADSB_E_STATE without an mlat
+ * reserve; ADSB_E_NOMEM if the memory is not to be had. */
+int adsb_track_table_filter_reserve(adsb_track_table *table, const adsb_track_filter_cfg *cfg);
+/* Waits; one filter record per aircraft, in exactly the order adsb_track_table_fetch returns the records (ascending
+ * ICAO); *n = records held even if more than max.  ADSB_E_ARG for a NULL table, or NULL out with max > 0;
+ * ADSB_E_STATE without a reserve. */
+int adsb_track_table_fetch_filter(adsb_track_table *table, adsb_aircraft_filter *out, size_t max, size_t *n);
+/* Does not synchronise: the device address of the filter records, one per record PLACE in slot order (as
+ * adsb_track_table_mlat_device); dev may be NULL.  ADSB_E_ARG for a NULL table, ADSB_E_STATE without a reserve. */
+int adsb_track_table_filter_device(adsb_track_table *table, const adsb_aircraft_filter **dev);
+/* Waits; one adsb_frame_filter per frame of the last update given fixes, in its list order: copies min(frames, max),
+ * *n = copied.  ADSB_E_ARG for a NULL table, or NULL out with max > 0; ADSB_E_STATE without a reserve or before the
+ * first such update since the reserve (and since a reset). */
+int adsb_track_table_fetch_frame_filter(adsb_track_table *table, adsb_frame_filter *out, size_t max, size_t *n);
+/* For tests.  Waits; the operands of the last update given fixes, in SORTED order (ascending address, list order within
+ * one): copies min(frames, max), *n = copied.  Errors as fetch_frame_filter. */
+int adsb_debug_track_filter_operands(adsb_track_table *table, adsb_filter_operand *out, size_t max, size_t *n);
+
+/*
  * Mode S replies per aircraft.  adsb_modes_of gives every frame of a list its address and kind; with a modes reserve a
  * TABLE takes the whole list, keyed by that address instead of bytes[1..3], so an aircraft that only answers
  * interrogations (DF0/4/5/11/16/20/21) gets a record, a place for its multilaterated fix, and one 64-byte

@@ -282,6 +282,19 @@ int adsb_host_track_mlat_of(double max_disagreement_m, const uint8_t bytes[14], 
                             adsb_aircraft_mlat *out, uint32_t *frame_flags, float *disagreement_m);
 
 /*
+ * CPU mirror of a table's filter reserve (adsb_hip.h, "Filtered mlat track per aircraft"): the same program text as the
+ * device's, no device needed.  cfg NULL: every default; a cfg as adsb_track_table_filter_reserve takes it.
+ * filter_operand: *operand = the operand of a frame with fix *fix at frame time `time`; counted 0: a frame of an aircraft
+ * the table turned away (64 zero bytes).  filter_step: *record (EMPTY: all zeros with time NaN) becomes the record after
+ * a frame with *operand, and *frame_out (optional) that frame's adsb_frame_filter; an operand that is not usable leaves
+ * the record alone.  ADSB_E_ARG for a NULL fix, operand or record, or a cfg the reserve would refuse.
+ */
+int adsb_host_track_filter_operand(const adsb_track_filter_cfg *cfg, const adsb_mlat_fix *fix, double time, int counted,
+                                   adsb_filter_operand *operand);
+int adsb_host_track_filter_step(const adsb_track_filter_cfg *cfg, adsb_aircraft_filter *record,
+                                const adsb_filter_operand *operand, adsb_frame_filter *frame_out);
+
+/*
  * CPU mirror of the per-frame step and the combine of a table with a modes reserve (adsb_hip.h, "Mode S replies per
  * aircraft"): the same program text as the device's, no device needed.  track_modes_of: *accepted (optional) = 1 iff
  * the record's kind is SELF or KNOWN; *one = the adsb_aircraft_modes of an aircraft whose only counted frame since

@@ -39,7 +39,12 @@ as 6,0 settled from the aircraft's own ADS-B velocity.  Six more columns: SelAlt
 --modes --es --aircraft: the extended squitter status stage (adsb_es_of) reads the same frames and the table takes its
 records too (adsb_track_table_update_es, on the keyed path): NIC and Rc of each aircraft's newest position message resolved
 with the version and NIC supplements of its own operational status messages.  Eight more columns: Ver, NIC, Rc, NACp, SIL,
-Emerg, Squawk(ES), SelAlt, with a "?" behind NIC and Rc where no version was known when the position was heard."""
+Emerg, Squawk(ES), SelAlt, with a "?" behind NIC and Rc where no version was known when the position was heard.
+
+--aircraft --filter: the table also runs every aircraft's fixes through its Kalman filter (adsb_track_table_filter_reserve;
+with --host the CPU mirror of its two steps), so an aircraft that sends no ADS-B has a speed and a track too.  Six columns
+are appended last: Lat(f), Lon(f) (the filtered position), GS(f) in knots, Trk(f) in degrees, VR(f) in ft/min (n/a until
+the filter has seen min_run fixes in a row) and Outl, the fixes it turned away."""
 import argparse
 import os
 import sys
@@ -60,15 +65,16 @@ def read_sites(path):
     return sites
 
 
-def host_table(A, frames, fixes, max_disagreement, modes=None):
+def host_table(A, frames, fixes, max_disagreement, modes=None, filt=False):
     """What a table with an mlat reserve makes of the list, without a device: the CPU tracker for the records, the CPU
     mirror of the per-frame step and the header's merge rules (saturating add, max, newest by position) for the mlat
     records -> (AIRCRAFT_DTYPE records, AIRCRAFT_MLAT_DTYPE records), ascending ICAO.  modes (the frames' MODES_DTYPE
     records): what update_modes makes of it instead -- frames that are not SELF or KNOWN are skipped, the others are
     keyed by their address, a frame that is no DF17/18 is one of kind "other" to the tracker -- and a third array, the
-    AIRCRAFT_MODES_DTYPE records by the CPU mirror of the modes step and its combine."""
+    AIRCRAFT_MODES_DTYPE records by the CPU mirror of the modes step and its combine.  filt: a last array, the
+    AIRCRAFT_FILTER_DTYPE records by the CPU mirror of the filter's operand and step."""
     import numpy as np
-    tracker, state, count, side = A.Tracker(), {}, {}, {}
+    tracker, state, count, side, track = A.Tracker(), {}, {}, {}, {}
     sat = (1 << 32) - 1
     for j, (fr, fx) in enumerate(zip(frames, fixes)):
         b = fr["bytes"].tobytes()
@@ -86,6 +92,9 @@ def host_table(A, frames, fixes, max_disagreement, modes=None):
         tracker.update(seen, time)
         count[icao] = count.get(icao, 0) + 1
         one = A.host_track_mlat_of(max_disagreement, b, fx, time)[0]
+        if filt:
+            track[icao] = A.host_track_filter_step(track[icao] if icao in track else A.filter_empty()[0],
+                                                   A.host_track_filter_operand(fx, time))[0]
         a = state.get(icao)
         if a is None:
             a = np.zeros((), dtype=A.AIRCRAFT_MLAT_DTYPE)
@@ -109,9 +118,12 @@ def host_table(A, frames, fixes, max_disagreement, modes=None):
         recs[k] = (s.latitude, s.longitude, s.last_contact, icao, s.altitude, 1 if s.has_position else 0, count[icao],
                    s.callsign)
         mlat[k] = state[icao]
-    if modes is None:
-        return recs, mlat
-    return recs, mlat, np.array([side[icao] for icao in sorted(state)], dtype=A.AIRCRAFT_MODES_DTYPE)
+    out = (recs, mlat)
+    if modes is not None:
+        out += (np.array([side[icao] for icao in sorted(state)], dtype=A.AIRCRAFT_MODES_DTYPE),)
+    if filt:
+        out += (np.array([track[icao] for icao in sorted(state)], dtype=A.AIRCRAFT_FILTER_DTYPE),)
+    return out
 
 
 def modes_columns(A, s):
@@ -124,13 +136,25 @@ def modes_columns(A, s):
                       f"{int(s['n_replies'])}", "" if flags & A.ADSB_TRACK_MODES_SQUITTER else "S"])
 
 
-def aircraft_lines(A, recs, mlat, now, modes=None, commb=None, es=None):
+def filter_columns(A, f):
+    """Lat(f), Lon(f), GS(f), Trk(f), VR(f) and Outl of one AIRCRAFT_FILTER_DTYPE record."""
+    flags = int(f["flags"])
+    p = A.filter_physical(f)[0]
+    place = f"{float(f['latitude']):.5f}\t{float(f['longitude']):.5f}" if flags & A.ADSB_TRACK_FILTER_RUNNING else "n/a\tn/a"
+    moving = (f"{p['ground_speed_kt']:.0f}\t{p['track_deg']:.0f}\t{p['vertical_rate_fpm']:.0f}"
+              if flags & A.ADSB_TRACK_FILTER_VELOCITY else "n/a\tn/a\tn/a")
+    return f"{place}\t{moving}\t{int(f['n_outlier'])}"
+
+
+def aircraft_lines(A, recs, mlat, now, modes=None, commb=None, es=None, filt=None):
     """One tab-separated line per aircraft, under a header line.  modes (AIRCRAFT_MODES_DTYPE records): five more
-    columns.  commb (AIRCRAFT_COMMB_DTYPE records): six more.  es (aircraft_es_columns' rows): eight more."""
+    columns.  commb (AIRCRAFT_COMMB_DTYPE records): six more.  es (aircraft_es_columns' rows): eight more.  filt
+    (AIRCRAFT_FILTER_DTYPE records): six more, last."""
     out = ("ICAO\tCallsign\tLatitude\tLongitude\tMlatLat\tMlatLon\tAge\tPdop\tValid/Attempted\tChecked/Disagree"
            "\tMaxDisagreement" + ("" if modes is None else "\tAlt(S)\tSquawk\tCall(S)\tReplies\tS")
            + ("" if commb is None else "\t" + "\t".join(A.AIRCRAFT_COMMB_COLUMNS))
-           + ("" if es is None else "\t" + "\t".join(A.AIRCRAFT_ES_COLUMNS)) + "\n")
+           + ("" if es is None else "\t" + "\t".join(A.AIRCRAFT_ES_COLUMNS))
+           + ("" if filt is None else "\tLat(f)\tLon(f)\tGS(f)\tTrk(f)\tVR(f)\tOutl") + "\n")
     registers = None if commb is None else A.aircraft_commb_columns(commb)
     for k, (r, m) in enumerate(zip(recs, mlat)):
         call = r["callsign"].decode("ascii", "replace").strip() or "n/a"
@@ -145,7 +169,8 @@ def aircraft_lines(A, recs, mlat, now, modes=None, commb=None, es=None):
                 f"\t{int(m['n_checked'])}/{int(m['n_disagree'])}\t{worst}"
                 + ("" if modes is None else "\t" + modes_columns(A, modes[k]))
                 + ("" if registers is None else "\t" + "\t".join(registers[k]))
-                + ("" if es is None else "\t" + "\t".join(es[k])) + "\n")
+                + ("" if es is None else "\t" + "\t".join(es[k]))
+                + ("" if filt is None else "\t" + filter_columns(A, filt[k])) + "\n")
     return out
 
 
@@ -170,6 +195,8 @@ def main():
     ap.add_argument("--es", action="store_true",
                     help="with --modes --aircraft: the aircraft's extended squitter status too, NIC and Rc resolved per "
                          "aircraft, eight more columns")
+    ap.add_argument("--filter", action="store_true",
+                    help="with --aircraft: each aircraft's fixes through the table's Kalman filter, six more columns")
     ap.add_argument("--max-iterations", type=int, default=0,
                     help="the solver's step limit (default: its own, 24); replies carry no altitude, and a free solve over "
                          "ground receivers may need 200")
@@ -180,6 +207,8 @@ def main():
         ap.error("--commb needs --modes and --aircraft")
     if args.es and not (args.modes and args.aircraft):
         ap.error("--es needs --modes and --aircraft")
+    if args.filter and not args.aircraft:
+        ap.error("--filter needs --aircraft")
 
     import numpy as np
 
@@ -201,8 +230,10 @@ def main():
         """The correlated messages and their fixes, where they lie on the device, into a table -> (records, mlat)"""
         with A.TrackTable(d, max_frames=max(n_msgs, 1), seconds_per_sample=0.5e-6) as table:
             table.mlat_reserve(args.max_disagreement)
+            if args.filter:
+                table.filter_reserve()
             table.update_device(d.correlated_device()[1], n_msgs, 0, mlat_ptr=d.mlat_device()[0])
-            return table.aircraft()[0], table.mlat()
+            return (table.aircraft()[0], table.mlat()) + ((table.filter(),) if args.filter else ())
 
     def resolved(msgs, recs, modes):
         """The messages whose address is an aircraft's, with their receptions -> (messages, receptions, addresses)"""
@@ -222,7 +253,7 @@ def main():
         if args.aircraft:
             spread = np.zeros(len(every), dtype=A.MLAT_FIX_DTYPE)       # a fix per message: none where none was solved
             spread[np.flatnonzero(mrec["kind"] <= A.ADSB_MODES_KNOWN)] = fixes
-            aircraft = host_table(A, fout, spread, args.max_disagreement, modes=mrec)
+            aircraft = host_table(A, fout, spread, args.max_disagreement, modes=mrec, filt=args.filter)
             if args.commb:                                              # every accepted address has a row in both
                 commb_side = A.host_track_commb(fout, mrec, A.host_commb(fout)[0])[1]
             if args.es:
@@ -239,6 +270,8 @@ def main():
                 with A.TrackTable(d, max_frames=max(n_msgs, 1), seconds_per_sample=0.5e-6) as table:
                     table.mlat_reserve(args.max_disagreement)
                     table.modes_reserve()
+                    if args.filter:
+                        table.filter_reserve()
                     commb_ptr = None
                     if args.commb:
                         table.commb_reserve()
@@ -251,7 +284,7 @@ def main():
                         es_ptr = d.es_device()[0]
                     table.update_device(d.correlated_device()[1], n_msgs, 0, mlat_ptr=d.mlat_device()[0],
                                         modes_ptr=d.modes_device()[0], commb_ptr=commb_ptr, es_ptr=es_ptr)
-                    aircraft = (table.aircraft()[0], table.mlat(), table.modes())
+                    aircraft = (table.aircraft()[0], table.mlat(), table.modes()) + ((table.filter(),) if args.filter else ())
                     commb_side = table.commb() if args.commb else None
                     es_side = A.aircraft_es_columns(table.es()) if args.es else None
             fixes, hdr = d.fetch_mlat()
@@ -270,7 +303,7 @@ def main():
         else:
             fixes, hdr = A.host_multilaterate(sites, msgs, recs, win.rx, **cfg)
         if args.aircraft:
-            aircraft = host_table(A, A.frames_of_messages(msgs), fixes, args.max_disagreement)
+            aircraft = host_table(A, A.frames_of_messages(msgs), fixes, args.max_disagreement, filt=args.filter)
     elif args.sync:
         with A.AdsbDemod(max_samples=1 << 16, max_out=1024) as d:
             win = d.wire_in_of(data, ends, filter=["crc", "df17"])
@@ -296,8 +329,9 @@ def main():
     if aircraft is not None:
         if newest is None:
             newest = float(int(msgs["time"][-1])) * 0.5e-6 if len(msgs) else 0.0
-        print(aircraft_lines(A, aircraft[0], aircraft[1], newest, aircraft[2] if len(aircraft) > 2 else None, commb_side,
-                             es_side), end="")
+        filter_side = aircraft[-1] if args.filter else None
+        print(aircraft_lines(A, aircraft[0], aircraft[1], newest, aircraft[2] if args.modes else None, commb_side,
+                             es_side, filter_side), end="")
     for k, (m, f) in enumerate(zip(msgs, fixes)):
         if aircraft is None and f["flags"] & A.ADSB_MLAT_VALID and (accepted is None or accepted[k]):
             t = int(win.rx["ticks"][recs["frame"][m["first"]]]) / 12e6
